@@ -16,6 +16,7 @@ collapse -> unit HiFi-GAN -> waveform in HBM.  The default K = 16 steps is twice
 profiles/r06_stream_sweep.txt).  Packs: 32 in rounds 1-3, 64 in round 4, 128 since round 5 (ids do not depend on the pack --
 tests/test_pack_invariance_gpu.py); with --batch 1 a step is one utterance through the single-utterance entry points.
 stdout carries ONE line under 6 KB (compact_line); the full result goes to the sidecar bench_detail.json (SS_BENCH_DETAIL) and to stderr.
+--dump-outputs DIR writes what the last timed step returned as DIR/*.npy (dump_outputs), to compare two builds on the same inputs.
 value = total audio seconds / wall seconds over all ranks (RTFx; higher is better); the line also
 carries utterances/sec, the roofline of the dominant kernel (HIP events recorded on the launch
 stream inside the timed region) and the CPU oracle timed on this box's host cores (rank 0, N=1).
@@ -66,6 +67,50 @@ def run_utterance(model, voc, pcm, utt):
 
 
 run_batch = workload.run_batch      # the timed step; tests/test_bench_config_gpu.py checks this very function against the oracle
+
+DUMP_BYTE_CAP = 64 * 10 ** 6        # --dump-outputs: all files together (npy headers included)
+
+
+def dump_outputs(path, utts, result, batched, cap=DUMP_BYTE_CAP):
+    """--dump-outputs: what the caller of the timed step received for one step, as DIR/<name>.npy in float32 (waveform
+    samples) or float64 (ids, frame indices, lengths: exact integers).  batched: `result` = run_batch(...) over the utterances
+    `utts` -> per-utterance waveforms packed end to end (`wav`, `wav_lengths`), the (token, frame) lists of both CTC heads and
+    the MT tokens incl. </s>, each flattened with its `*_lengths`.  Otherwise `result` = run_utterance(...) on the one
+    utterance `utts` -> `wav` and the three id counts it returns.  If the waveform does not fit the cap, `wav` is a fixed,
+    seeded sample of the packed samples and `wav_sample_positions` says which.  -> the names written."""
+    if batched:
+        wavs, asr, st, toks = result
+    else:
+        utts, wavs = [utts], [result[0]]
+    arrays = {"utterance_index": np.array([u.idx for u in utts], np.float64),
+              "wav_lengths": np.array([w.numel() for w in wavs], np.float64)}
+    if batched:
+        for head, res in (("asr", asr), ("st", st)):
+            arrays[f"{head}_tokens"] = np.array([t for tk, _ in res for t in tk], np.float64)
+            arrays[f"{head}_frames"] = np.array([f for _, fr in res for f in fr], np.float64)
+            arrays[f"{head}_lengths"] = np.array([len(tk) for tk, _ in res], np.float64)
+        arrays["mt_tokens"] = np.array([t for tk in toks for t in tk], np.float64)
+        arrays["mt_lengths"] = np.array([len(tk) for tk in toks], np.float64)
+    else:
+        arrays["asr_st_mt_lengths"] = np.array(result[1:4], np.float64)
+    wav = torch.cat([w.reshape(-1) for w in wavs]).float().cpu().numpy()
+    room = cap - sum(a.nbytes for a in arrays.values()) - 256 * (len(arrays) + 2)
+    if wav.nbytes > room:                  # 4 bytes per kept sample + 8 for its position
+        pos = np.sort(np.random.default_rng(0).choice(wav.size, room // 12, replace=False))
+        arrays["wav_sample_positions"] = pos.astype(np.float64)
+        wav = wav[pos]
+    arrays["wav"] = wav
+    os.makedirs(path, exist_ok=True)
+    for name in DUMP_NAMES - set(arrays):  # an earlier dump with other arguments must not leave files behind
+        if os.path.exists(os.path.join(path, name + ".npy")):
+            os.remove(os.path.join(path, name + ".npy"))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
+
+
+DUMP_NAMES = {"utterance_index", "wav", "wav_lengths", "wav_sample_positions", "asr_st_mt_lengths", "mt_tokens", "mt_lengths",
+              *(f"{h}_{k}" for h in ("asr", "st") for k in ("tokens", "frames", "lengths"))}
 
 
 def _pick_threads(O, osd, ovsd, cfg, vcfg, probe_seconds):
@@ -641,22 +686,27 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def self_launch(n):
+def self_launch(n, gpu=True):
     """`python bench.py --gpus N` typed without a launcher (fairseq's own entry does the same: distributed_utils.call_main
     spawns one process per device, fairseq/fairseq/distributed/utils.py:344-380): run the same command line under
-    torch.distributed.run, one rank per GPU, and leave with its exit code (non-zero if any rank failed)."""
+    torch.distributed.run, one rank per GPU, and leave with its exit code (non-zero if any rank failed).  gpu=False (--dry-plan):
+    the launcher and the ranks must not open the GPU either -- torch.distributed.run asks torch.cuda.is_available(), which starts
+    the HIP runtime; counted from the environment with no device visible, the answer needs no runtime."""
     import subprocess
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")        # dmabuf IPC only on this host driver (RCCL needs it)
     env["SS_BENCH_SELF_LAUNCHED"] = "1"
+    if not gpu:
+        env.update(PYTORCH_NVML_BASED_CUDA_CHECK="1", HIP_VISIBLE_DEVICES="")
     return subprocess.call(cmd, env=env)
 
 
-def comm_probe(dist, device, reps=20):
+def comm_probe(dist, device, reps=20, barrier=None):
     """The collectives of the utterance-DP path (one barrier before the timed region, MAX / SUM all-reduce and
-    one all-gather of three doubles after it), timed on an initialised process group -- untimed for `value`."""
+    one all-gather of three doubles after it), timed on an initialised process group -- untimed for `value`.  barrier: the
+    barrier to time (default dist.barrier)."""
     def sync():
         if str(device).startswith("cuda"):
             torch.cuda.synchronize()
@@ -674,7 +724,7 @@ def comm_probe(dist, device, reps=20):
     t3 = torch.tensor([1.0 + dist.get_rank(), 2.0, 3.0], dtype=torch.float64, device=device)
     outs = [torch.zeros_like(t3) for _ in range(world)]
     res = {"backend": dist.get_backend(), "world": world,
-           "barrier_us": timed(dist.barrier),
+           "barrier_us": timed(barrier or dist.barrier),
            "all_reduce_max_3xf64_us": timed(lambda: dist.all_reduce(t3.clone(), op=dist.ReduceOp.MAX)),
            "all_reduce_sum_3xf64_us": timed(lambda: dist.all_reduce(t3.clone(), op=dist.ReduceOp.SUM)),
            "all_gather_3xf64_us": timed(lambda: dist.all_gather(outs, t3))}
@@ -737,14 +787,15 @@ def rccl_probe_subprocess(timeout_s=120):
 def dry_plan(args, rank, world):
     """`--dry-plan`: the N-rank control path with no GPU -- every rank forms its share of the plan (workload.bench_plan, the
     function the real run uses), meets the barrier, and the (wall, audio seconds, utterances) statistics go through the same
-    MAX / SUM all-reduce + all-gather over gloo (tests/test_dp_gloo.py runs `bench.py --gpus 2 --dry-plan` as typed)."""
+    MAX / SUM all-reduce + all-gather over gloo (tests/test_dp_gloo.py runs `bench.py --gpus 2 --dry-plan` as typed).  No rank opens
+    the GPU: the barriers are gloo's monitored_barrier (dist.barrier first asks torch for the accelerator, which starts the HIP runtime)."""
     dist = None
     if world > 1:
         import torch.distributed as dist
         import datetime
         with _stdout_to_stderr():
             dist.init_process_group("gloo", timeout=datetime.timedelta(seconds=180))    # a rendezvous that cannot complete fails, it does not wait 30 min
-            dist.barrier()
+            dist.monitored_barrier()
     Ksteps, Bsz = max(1, args.steps), max(1, args.batch)
     mine, groups = workload.bench_plan(Ksteps, Bsz, rank, world, bucket=not args.no_length_bucketing, warm=3, strong=args.scaling == "strong")
     timed_ids = [i for g in groups for i in g]
@@ -752,12 +803,12 @@ def dry_plan(args, rank, world):
     if os.environ.get("SS_BENCH_DRY_FAIL_RANK") == str(rank):     # tests: a dying rank must fail the whole command
         raise SystemExit(3)
     if dist is not None:
-        dist.barrier()
+        dist.monitored_barrier()
     wall = 1.0 + 0.001 * rank          # a stand-in wall time: the MAX must pick the last rank's
     placement = dp.pin_rank_to_gpu_numa(rank, world, pci_bus_id=os.environ.get("SS_BENCH_DRY_PCI", "0000:00:00.0"), apply=False)
     per_rank = dp.gather_per_rank(dist, wall, audio, float(len(timed_ids)), placement=placement)
     wall_max, audio_tot, nutt = dp.reduce_stats(dist, wall, audio, float(len(timed_ids)))
-    comm = comm_probe(dist, "cpu", reps=5) if dist is not None else None
+    comm = comm_probe(dist, "cpu", reps=5, barrier=dist.monitored_barrier) if dist is not None else None
     if rank == 0:
         full = {"metric": METRIC, "dry_plan": True, "value": None, "unit": "x real-time", "n_gpus": world, "steps": Ksteps, "warmup": max(0, args.warmup),
                 "ms_per_step": None, "utterances_per_sec": None, "higher_is_better": True, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -771,7 +822,7 @@ def dry_plan(args, rank, world):
         else:
             _emit(compact_line(full))
     if dist is not None:
-        dist.barrier()
+        dist.monitored_barrier()
         dist.destroy_process_group()
 
 
@@ -809,7 +860,12 @@ def main():
                     help="no GPU: form every rank's plan and run the barrier + statistics reductions over gloo (the N > 1 control path)")
     ap.add_argument("--rccl-probe", action="store_true", help="internal: world-of-one RCCL initialisation + the DP collectives, one JSON object")
     ap.add_argument("--no-rccl-probe", action="store_true", help="skip the RCCL probe of the N = 1 line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step returned (waveforms, CTC / MT ids) to DIR/<name>.npy "
+                         "(float32 / float64, <= 64 MB; rank 0) -- the inputs are seeded, so two builds compare output for output")
     args = ap.parse_args()
+    if args.dump_outputs and (args.mode != "offline" or args.dry_plan):
+        ap.error("--dump-outputs applies to the offline timed region (not --mode streaming / --dry-plan)")
     if args.full:
         args.bracket_ab = args.bf16x3_line = True
     args.no_bracket_ab, args.no_bf16x3_line = not args.bracket_ab, not args.bf16x3_line
@@ -823,7 +879,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        sys.exit(self_launch(args.gpus))        # typed without a launcher: one rank per GPU under torch.distributed.run
+        sys.exit(self_launch(args.gpus, gpu=not args.dry_plan))   # typed without a launcher: one rank per GPU under torch.distributed.run
     _claim_stdout()                              # from here on stdout carries the one JSON line and nothing else
     if world != args.gpus and rank == 0:
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}; running with the launcher's world size", file=sys.stderr)
@@ -953,6 +1009,8 @@ def main():
     start_evt = threading.Barrier(S + 1)   # released at t0, after the counters were reset and switched on
     samples = [0] * S
     errors = []
+    dump = bool(args.dump_outputs) and rank == 0
+    last_step = [None]                     # --dump-outputs: what run_batch / run_utterance returned for the last timed step
 
     def worker(wi):
         try:
@@ -974,12 +1032,14 @@ def main():
                         break
                     if Bsz == 1:
                         u, p = work[i]
-                        wav, _, _, _ = run_utterance(m, v, p, u)
-                        samples[wi] += wav.numel()
+                        res = run_utterance(m, v, p, u)
+                        samples[wi] += res[0].numel()
                     else:
                         us, pk = work[i]
-                        wavs, _, _, _ = run_batch(m, v, pk, us)
-                        samples[wi] += sum(w.numel() for w in wavs)
+                        res = run_batch(m, v, pk, us)
+                        samples[wi] += sum(w.numel() for w in res[0])
+                    if dump and i == len(work) - 1:
+                        last_step[0] = res
                 streams[wi].synchronize()
         except Exception as e:  # noqa: BLE001
             errors.append(e)
@@ -1027,6 +1087,11 @@ def main():
            "scratch_sets": S, "scratch_set_gb": [round(sc.bytes() / 2 ** 30, 2) for sc in scratches],
            "note": "a scratch set (ss_scratch: one per stream, model + vocoder side) keeps the activations of the largest pack it has run until "
                    "ss_scratch_trim; ss_scratch_set_cap bounds it"}
+    dumped = None
+    if dump:                                 # untimed: after the clock stopped, before any later leg reuses the contexts
+        dumped = {"dir": args.dump_outputs, "step": len(work) - 1,
+                  "files": dump_outputs(args.dump_outputs, work[-1][0], last_step[0], batched=Bsz > 1)}
+        last_step[0] = None
     audio = sum(mine[i].seconds for i in timed_ids)
     per_rank = dp.gather_per_rank(dist, wall, audio, float(K), device=dev, placement=placement)
     wall, audio, nutt = dp.reduce_stats(dist, wall, audio, float(K), device=dev)
@@ -1397,6 +1462,7 @@ def main():
             "rccl": rccl if (rccl is not None or args.no_rccl_probe) else rccl_probe_subprocess(),
             "self_launched": bool(os.environ.get("SS_BENCH_SELF_LAUNCHED")),
             "timed_region_monotonic_ns": [t0_mono_ns, t1_mono_ns],   # tools/trace_gaps.py: window of a rocprofv3 kernel trace
+            "dumped_outputs": dumped,
         }
         legs["pack_invariance_census_rccl_probe"] = round(time.perf_counter() - t_leg, 2)
         t_leg = time.perf_counter()

@@ -110,3 +110,62 @@ def test_the_streaming_mode_line_is_under_the_cap():
     line = json.loads(text)
     assert len(text) < bench.LINE_BYTE_CAP and line["value"] == full["value"] and line["incremental"]["ms_per_read_call_mean"] > 0
     assert set(line["long_prefix_speedup_total"]) == {"15", "30"} and line["cpu_baseline"]["kind"] == "port"
+
+
+def _fake_batch(n_utts=3, seconds=0.05):
+    """A run_batch result of the shapes the timed step returns (CPU tensors / host lists), for dump_outputs."""
+    import numpy as np
+    import torch
+    from streamspeech_amd import workload
+    utts = workload.make_utterances(n_utts)
+    g = np.random.default_rng(7)
+    wavs = [torch.from_numpy(g.standard_normal(int(16000 * seconds) + 13 * b).astype(np.float32)) for b in range(n_utts)]
+    ctc = lambda: [(list(range(b, b + 4)), list(range(0, 8, 2))) for b in range(n_utts)]   # noqa: E731
+    toks = [list(range(5 + b)) + [2] for b in range(n_utts)]
+    return utts, (wavs, ctc(), ctc(), toks)
+
+
+def test_dump_outputs_writes_what_the_step_returned(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's waveforms (packed, float32) and ids (float64), one .npy per name."""
+    import numpy as np
+    utts, res = _fake_batch()
+    names = bench.dump_outputs(str(tmp_path), utts, res, batched=True)
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in names}
+    assert set(names) == {p.stem for p in tmp_path.iterdir()} and "wav_sample_positions" not in names
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and got["wav"].dtype == np.float32
+    wavs, asr, st, toks = res
+    assert np.array_equal(got["wav"], np.concatenate([w.numpy() for w in wavs]))
+    assert got["wav_lengths"].tolist() == [w.numel() for w in wavs] and got["utterance_index"].tolist() == [u.idx for u in utts]
+    assert got["asr_tokens"].tolist() == [t for tk, _ in asr for t in tk] and got["st_frames"].tolist() == [f for _, fr in st for f in fr]
+    assert got["mt_tokens"].tolist() == [t for tk in toks for t in tk] and got["mt_lengths"].tolist() == [len(t) for t in toks]
+
+
+def test_dump_outputs_keeps_under_the_cap_with_a_fixed_sample(tmp_path):
+    import numpy as np
+    utts, res = _fake_batch(seconds=1.0)
+    cap = 60000
+    full = np.concatenate([w.numpy() for w in res[0]])
+    assert full.nbytes > cap
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), utts, res, batched=True, cap=cap)
+        assert sum(p.stat().st_size for p in (tmp_path / d).iterdir()) <= cap
+    a, b = (np.load(tmp_path / d / "wav_sample_positions.npy") for d in ("a", "b"))
+    assert np.array_equal(a, b) and np.all(np.diff(a) > 0)               # the same positions every run, in order
+    assert np.array_equal(np.load(tmp_path / "a" / "wav.npy"), full[a.astype(np.int64)])
+    # a later full-size dump into the same directory leaves no stale sample positions behind
+    bench.dump_outputs(str(tmp_path / "a"), utts, res, batched=True)
+    assert not (tmp_path / "a" / "wav_sample_positions.npy").exists()
+
+
+def test_dump_outputs_of_a_single_utterance_step(tmp_path):
+    import numpy as np
+    utts, res = _fake_batch(n_utts=1)
+    names = bench.dump_outputs(str(tmp_path), utts[0], (res[0][0], 4, 4, 6), batched=False)
+    assert "asr_tokens" not in names and np.load(tmp_path / "asr_st_mt_lengths.npy").tolist() == [4, 4, 6]
+    assert np.array_equal(np.load(tmp_path / "wav.npy"), res[0][0].numpy())
+
+
+def test_dump_outputs_is_refused_where_there_is_no_timed_region(tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-plan", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr and not list(tmp_path.iterdir())

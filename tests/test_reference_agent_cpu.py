@@ -3,13 +3,12 @@
     (+ fairseq/fairseq/search.py) executed by oracle/make_golden_agent.py;
   * tests/golden/agent_traces.npz <- the reference agents' policy() driven chunk by chunk.
 Here the repo's generators / agents run over the oracle-backed engine (no GPU); the GPU twins are in
-tests/test_reference_agent_gpu.py.  With /root/reference present the reference agent is also run live on
-inputs the fixtures do not contain."""
+tests/test_reference_agent_gpu.py.  The reference agent's writes on inputs the trace fixtures do not contain are
+in tests/golden/pins.npz (oracle/make_golden_pins.py)."""
 import numpy as np
 import pytest
 import torch
 
-from oracle import ref_loader
 from streamspeech_amd import synth
 from streamspeech_amd.config import ModelConfig
 from streamspeech_amd.generators import CTCDecoder, CTCSequenceGenerator, SequenceGenerator
@@ -128,20 +127,18 @@ def test_text_agent_trace_matches_reference_agent(synth_weights, cmvn, name):
     RF.check_text_trace(g, name, RF.run_case(agent, cases[name]))
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="/root/reference not present")
 @pytest.mark.parametrize("segment_ms,seed,seconds", [(320, 41, 2.2), (640, 28, 4.0)])
 def test_live_reference_agent(synth_weights, cmvn, golden_dir, segment_ms, seed, seconds):
-    """The reference agent run live (not from fixtures) on another utterance, against the repo's agent."""
-    from oracle import ref_agent
+    """The reference agent on another utterance than the trace fixtures (its writes: tests/golden/pins.npz,
+    oracle/make_golden_pins.py), against the repo's agent."""
+    from oracle.make_golden_pins import agent_key
     cfg, vcfg, sd, vsd = synth_weights
     case = dict(kind="s2st", segment_ms=segment_ms, sr=16000, seed=seed, seconds=seconds, over={})
-    with torch.no_grad():
-        ref = ref_agent.make_agent(sd, vsd, cfg, vcfg, segment_ms, 16000,
-                                   cmvn_npz=os.path.join(golden_dir, "gcmvn_fr-en.npz"))
-        want = ref_agent.stream(ref, RF.trace_pcm(seed, 16000, seconds), segment_ms, 16000)
+    g = np.load(os.path.join(golden_dir, "pins.npz"))
+    k = agent_key(segment_ms, seed, seconds)
     agent = _make_agent("s2st", case, OracleEngine(sd, cfg, *cmvn), OracleVocoder(vsd, vcfg), cfg)
     got = RF.run_case(agent, case)
-    assert [w for w, _, _ in got] == [not r.is_empty for r in want]
+    assert [w for w, _, _ in got] == g[f"{k}/writes"].tolist()
     a = np.concatenate([np.asarray(c, np.float32) for _, c, _ in got if c is not None])
-    b = np.concatenate([np.asarray(r.content, np.float32) for r in want if not r.is_empty])
+    b = g[f"{k}/wav"]
     assert a.shape == b.shape and float(np.sqrt(np.mean((a - b) ** 2))) < 1e-5

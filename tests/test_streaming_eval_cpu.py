@@ -1,8 +1,7 @@
 """streamspeech_amd/streaming_eval.py (the latency bookkeeping bench.py's streaming lines report) against SimulEval's
 own classes: SpeechOutputInstance.receive_prediction / summarize (evaluator/instance.py:349-415) and the RTF /
-StartOffset / EndOffset scorers (evaluator/scorers/latency_scorer.py:540-587), executed from /root/reference
-(oracle/ref_simuleval.py) -- and against the committed fixture of their outputs, so the test also runs where the
-reference is absent."""
+StartOffset / EndOffset scorers (evaluator/scorers/latency_scorer.py:540-587), via the committed fixture of their
+outputs (written by this module's __main__, which executes them from the reference tree: oracle/ref_simuleval.py)."""
 import json
 import os
 
@@ -69,17 +68,6 @@ def test_matches_committed_reference_outputs(case):
     ours = _ours(case)
     for k, v in gold.items():
         assert ours[k] == pytest.approx(v, rel=1e-12, abs=1e-9), (case, k)
-
-
-@pytest.mark.parametrize("case", sorted(CASES))
-def test_matches_live_reference_scorers(case):
-    from oracle import ref_simuleval as RS
-    if not RS.available():
-        pytest.skip("/root/reference not present")
-    ref, ours = _reference(case), _ours(case)
-    for k, v in ref.items():
-        assert ours[k] == pytest.approx(v, rel=1e-12, abs=1e-9), (case, k)
-    assert json.load(open(FIX))[case] == pytest.approx(ref)
 
 
 def test_computation_aware_variants_only_add_compute_time():
