@@ -96,6 +96,71 @@ int ss_fbank_cmvn(ss_model* m, void* stream, const float* d_pcm16k, int n_sample
 int ss_resample(void* stream, const float* d_in, int64_t n_in, int up, int down, const float* d_taps,
                 int half_len, float* d_out, int64_t n_out);
 
+/* MP3 ingest: MPEG-1 / MPEG-2 LSF / MPEG-2.5 Layer III sources, standing in for the soundfile.read the
+ * reference's loaders call on `.mp3` paths (SimulEval/simuleval/data/dataloader/s2t_dataloader.py:62-63,
+ * fairseq/data/audio/audio_utils.py:69-110).  Two stages: the serial bitstream part (headers, side info, bit reservoir,
+ * scalefactors, Huffman) runs on the host -- no global mutable state, no HIP runtime call, safe from many threads at once --
+ * and writes one ss_mp3_granule record plus int16 q[576] per granule-channel; the numeric part (requantisation, MS stereo,
+ * alias reduction, IMDCT, overlap-add, polyphase synthesis) runs on the device over a ragged batch of files.
+ * Container: ID3v2 (with footer), trailing ID3v1 and APEv2 tags are skipped; a header is taken only when the next frame's
+ * header agrees with it (resynchronisation over garbage); CRC words are skipped unchecked; a Xing / Info frame is not audio,
+ * and a LAME tag in it sets the gapless trim (delay + 529 samples at the start, padding - 529 at the end; no tag: no trim).
+ * Refused: intensity stereo, free-format bitrate, Layers I / II and reserved header fields (SS_ERR_UNSUPPORTED = 7); corrupt or
+ * inconsistent data, including Huffman data that overruns part2_3_length (SS_ERR_BITSTREAM = 6).  A truncated last frame is
+ * dropped.  A stream whose first audio frame points back into the bit reservoir (main_data_begin > 0: cut at the front, or
+ * captured mid-stream) is refused with SS_ERR_BITSTREAM as a whole, where some decoders output silence for the granules they
+ * cannot decode and go on.  Nothing is read outside [h_data, h_data + n_bytes). */
+typedef struct ss_mp3_info {
+  int32_t version;           /* 1 = MPEG-1, 2 = MPEG-2 LSF, 25 = MPEG-2.5 */
+  int32_t sample_rate, channels;
+  int32_t frames;            /* audio frames (a Xing / Info frame is not counted) */
+  int32_t granules;          /* granules per channel: frames x (2 for MPEG-1, 1 otherwise); 576 samples each */
+  int32_t granule_channels;  /* records ss_mp3_unpack writes: granules x channels */
+  int64_t samples;           /* per channel, after the gapless trim */
+  int32_t delay, padding;    /* from the LAME tag; -1 without one */
+  int32_t skip;              /* samples trimmed at the start */
+  int32_t sr_index;          /* 0..8: 44.1, 48, 32, 22.05, 24, 16, 11.025, 12, 8 kHz */
+} ss_mp3_info;
+
+/* One granule-channel: everything the device stage needs besides q[576].  Records are ordered (granule, channel). */
+typedef struct ss_mp3_granule {
+  int16_t global_gain;
+  int16_t nz;                /* lines [nz, 576) of q are zero */
+  uint8_t scalefac_scale, preflag, block_type, mixed;
+  uint8_t ms;                /* MS stereo in this granule */
+  uint8_t sr_index;
+  uint8_t subblock_gain[3];
+  uint8_t pad0[3];
+  uint8_t sf_l[22];          /* long-block scalefactors (band 21: 0) */
+  uint8_t sf_s[13][3];       /* short-block scalefactors [band][window] (band 12: 0) */
+  uint8_t pad1[3];
+} ss_mp3_granule;            /* 80 bytes */
+
+/* One file of a ss_mp3_synthesize batch. */
+typedef struct ss_mp3_file {
+  int64_t rec_offset;        /* index of the file's first record in d_q / d_rec */
+  int64_t out_offset;        /* first float of the file's output in d_out */
+  int32_t granules;          /* granules per channel (ss_mp3_info.granules) */
+  int32_t channels;          /* 1 or 2 */
+  int32_t skip;              /* samples dropped at the start (ss_mp3_info.skip) */
+  int32_t n_out;             /* samples written per channel (ss_mp3_info.samples) */
+} ss_mp3_file;               /* 32 bytes */
+
+/* Parse the container and every frame header (no Huffman decoding).  Host only. */
+int ss_mp3_probe(const uint8_t* h_data, size_t n_bytes, ss_mp3_info* h_info);
+/* Decode the bitstream: h_q [granule_channels][576] quantised lines, h_rec [granule_channels] records, h_bits (may be NULL)
+ * [granule_channels] bits of main data each granule-channel consumed (scalefactors + Huffman; <= its part2_3_length).
+ * cap = records the buffers hold (SS_ERR_CAPACITY if fewer than the stream has).  Host only. */
+int ss_mp3_unpack(const uint8_t* h_data, size_t n_bytes, int64_t cap, int16_t* h_q, ss_mp3_granule* h_rec, int32_t* h_bits);
+/* Device stage over a ragged batch: d_q / d_rec hold n_rec records of all files, h_files [n_files] (host, read before the call
+ * returns) says where each file's records start and where its float32 PCM goes: planar [channels][n_out] at out_offset, or with
+ * mono != 0 the channel mean [n_out].  Not clipped, not rounded.  Each file's synthesis history starts at zero, so a file
+ * decodes to the same bits alone or in any batch.  d_work: caller-allocated workspace; with d_work == NULL only *work_bytes is
+ * set (the size query).  Stream-ordered, two kernels, no host round trip. */
+int ss_mp3_synthesize(void* stream, const int16_t* d_q, const ss_mp3_granule* d_rec, int64_t n_rec,
+                      const ss_mp3_file* h_files, int n_files, int mono, float* d_out, int64_t out_floats,
+                      void* d_work, size_t* work_bytes);
+
 /* Offline driver only: d_out[r] = max over the vocabulary, ids mask0..2 skipped (< 0: none), of
  * log_softmax(d_logits[r, :]) -- the per-position score `lprobs.max(dim=2)` of the reference's offline unit search
  * (researches/ctc_unity/ctc_generator.py:55-63: pad / unk / eos set to -inf AFTER the softmax), which fairseq-generate

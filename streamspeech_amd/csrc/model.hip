@@ -50,6 +50,8 @@ extern "C" const char* ss_error_string(int code) {
     case SS_ERR_MISSING_WEIGHT: return "weight slot missing or wrong size";
     case SS_ERR_CAPACITY: return "output capacity too small";
     case SS_ERR_SCRATCH_CAP: return "scratch set would grow past its cap (ss_scratch_set_cap)";
+    case SS_ERR_BITSTREAM: return "corrupt or truncated MP3 bitstream";
+    case SS_ERR_UNSUPPORTED: return "unsupported MP3 feature (intensity stereo, free format, Layer I/II or reserved header field)";
     default: return "unknown error";
   }
 }

@@ -64,6 +64,41 @@ def read_wav(path: str):
     return x, sr
 
 
+def is_mp3(path) -> bool:
+    return str(path).lower().endswith(".mp3")
+
+
+def read_audio(path: str):
+    """WAV or MP3 -> (float32 numpy samples, sample rate), mono (channel mean) as read_wav returns them.  WAV goes through
+    read_wav; MP3 through the Layer III decoder (streamspeech_amd/mp3.py: host bitstream stage, device synthesis), whose output
+    is copied back to the host here -- load_audio_batch keeps it on the device."""
+    if not is_mp3(path):
+        return read_wav(path)
+    (x, sr), = load_audio_batch([path], "cuda")
+    return x.cpu().numpy(), sr
+
+
+def load_audio_batch(paths, device):
+    """-> [(float32 mono tensor on `device`, sample rate)] for WAV / MP3 paths.  The MP3 files of the call are decoded in
+    batches of up to 640 s of audio (one ss_mp3_synthesize launch pair each, mp3.decode_batch) and stay on the device; WAV files
+    are read by read_wav and uploaded."""
+    from . import mp3
+    out = [None] * len(paths)
+    idx = [k for k, p in enumerate(paths) if is_mp3(p)]
+    if idx:
+        blobs = []
+        for k in idx:
+            with open(paths[k], "rb") as f:
+                blobs.append(f.read())
+        for k, res in zip(idx, mp3.decode_batch(blobs, device, mono=True, names=[str(paths[k]) for k in idx])):
+            out[k] = res
+    for k, p in enumerate(paths):
+        if out[k] is None:
+            x, sr = read_wav(p)
+            out[k] = (torch.from_numpy(x).to(device), sr)
+    return out
+
+
 def write_wav(path: str, samples, sr: int = 16000):
     """float samples in [-1, 1] -> 16-bit PCM WAV (generate_waveform_from_code.py dumps soundfile PCM_16)."""
     x = np.clip(np.asarray(samples, np.float32), -1.0, 1.0)

@@ -47,6 +47,9 @@ SIGNATURES = {
     "ss_fbank_cmvn": (_i, [_vp, _vp, _vp, _i, _f, _vp, C.POINTER(_i)]),
     "ss_encoder_out_len": (_i, [_i]),
     "ss_resample": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _i64]),
+    "ss_mp3_probe": (_i, [_vp, C.c_size_t, _vp]),
+    "ss_mp3_unpack": (_i, [_vp, C.c_size_t, _i64, _vp, _vp, _vp]),
+    "ss_mp3_synthesize": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp, C.POINTER(C.c_size_t)]),
     "ss_row_max_logprob": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ss_log_softmax": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ss_encoder_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),

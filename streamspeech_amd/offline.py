@@ -229,11 +229,20 @@ def main(argv: Optional[List[str]] = None):
                 rows = [(i, ln.strip()) for i, ln in enumerate(f) if ln.strip()]
         else:
             rows = load_manifest(os.path.join(a.data, a.gen_subset + ".tsv"), targets)
+        rows = rows[a.shard_id::a.num_shards]
+        # MP3 rows: batched decodes of up to 640 s of audio each, straight to the device (streamspeech_amd/mp3.py); WAV rows as before
+        mp3_rows = [k for k, (_, path) in enumerate(rows) if frontend.is_mp3(path)]
+        decoded = dict(zip(mp3_rows, frontend.load_audio_batch([rows[k][1] for k in mp3_rows], a.device))) if mp3_rows else {}
         entries = []
-        for i, path in rows:
-            x, sr = frontend.read_wav(path)
-            entries.append((i, torch.from_numpy(x), sr))
-    entries = entries[a.shard_id::a.num_shards]
+        for k, (i, path) in enumerate(rows):
+            if k in decoded:
+                x, sr = decoded[k]
+            else:
+                x, sr = frontend.read_wav(path)
+                x = torch.from_numpy(x)
+            entries.append((i, x, sr))
+    if a.synthetic > 0:
+        entries = entries[a.shard_id::a.num_shards]
     items = []
     for e in entries:
         pcm = e[1].to(a.device)
