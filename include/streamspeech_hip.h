@@ -5,7 +5,10 @@
  * makes (reference agent/speech_to_speech.streamspeech.agent.py, cited per function).  Signatures
  * carry only plain pointers and sizes: `d_*` arguments are DEVICE (HBM) pointers, `h_*` are host
  * pointers, `stream` is a hipStream_t passed as void*.  Every call is stream-ordered unless it
- * says "synchronises".  All arithmetic is FP32.  Return value: 0 = ok, non-zero = SS_ERR_*.
+ * says "synchronises".  All arithmetic is FP32.  Return value: 0 = ok, non-zero = SS_ERR_*:
+ * 1 HIP runtime error, 2 invalid argument, 3 weight slot missing or wrong size, 4 output capacity
+ * too small, 5 SS_ERR_SCRATCH_CAP (ss_scratch_set_cap), 6 SS_ERR_BITSTREAM and 7 SS_ERR_UNSUPPORTED
+ * (ss_mp3_*), 8 SS_ERR_STREAM_REPEAT (ss_encoder_stream_forward).
  *
  * Weight ownership: the caller owns one packed FP32 weight blob in HBM (built once from a fairseq
  * state dict by streamspeech_amd/weights.py) and lends it to ss_model_create(); the library keeps
@@ -72,7 +75,13 @@ void ss_model_destroy(ss_model* m);
  * Buffers grow on demand and never shrink by themselves: ss_scratch_set_cap bounds their sum (a call that would pass it returns
  * SS_ERR_SCRATCH_CAP and leaves the set as it was; 0 = no cap), ss_scratch_trim synchronises the device and lets the largest
  * re-sizable buffers go until at most keep_bytes are held (fixed pieces -- MT cache, token chain, zero-initialised counters -- stay),
- * ss_scratch_bytes reports what is held.  (The stream-K hand-off workspace, 32 MB + flags per set, is not counted.) */
+ * ss_scratch_bytes reports what is held.  Every device buffer of the set is counted and capped, the streaming encoder's per-layer
+ * state included (a grow of it holds the old and the new buffers at once, and the cap sees both).  (The stream-K hand-off
+ * workspace, 32 MB + flags per set, is not counted.)
+ * Both ss_scratch_trim and ss_model_bind_scratch (for the set the handle LEAVES) end a streaming-encoder sequence on that set: the
+ * next ss_encoder_stream_forward starts a fresh stream.  A deferred time-out check still outstanding there (ss_encoder_stream_set_deferred)
+ * is settled first -- the device is synchronised, a real time-out is counted and the set leaves the persistent form -- and its
+ * verdict is dropped, since the stream starts over anyway: nothing of the unchecked call survives. */
 int ss_scratch_create(ss_scratch** out);
 void ss_scratch_destroy(ss_scratch* sc);
 int ss_scratch_set_cap(ss_scratch* sc, size_t max_bytes);
@@ -208,7 +217,10 @@ int ss_encoder_stream_forward(ss_model* m, void* stream, const float* d_fbank, i
  * ss_encoder_stream_status waits for the stream, sets *repeat = 1 if a launch timed out (the scratch set has then left the persistent
  * form and the failed call's rows are not final any more) and 0 otherwise.  With *repeat = 1 everything computed from d_enc_out since
  * the forward call is void: call ss_encoder_stream_forward again (it now runs one launch per op and waits) and recompute.  Until the
- * status call returns 0, d_enc_out must not be trusted.  A forward call with a check still outstanding settles it first. */
+ * status call returns 0, d_enc_out must not be trusted.  A forward call with a check still outstanding (the status call was
+ * skipped) settles it first; if that check finds a time-out, the forward returns SS_ERR_STREAM_REPEAT (8) without computing
+ * anything: the unchecked call's output was void, its rows are not final any more, and the caller repeats the forward exactly as
+ * after *repeat = 1 (and recomputes what it derived from the void output). */
 int ss_encoder_stream_set_deferred(ss_model* m, int on);
 int ss_encoder_stream_status(ss_model* m, void* stream, int32_t* repeat);
 
@@ -418,6 +430,10 @@ int ss_debug_attention_q16(int v);
 /* Test hook: the next time-out check of this handle's scratch set (ss_encoder_stream_status, or the end of a non-deferred
  * ss_encoder_stream_forward) reports a time-out although none happened -- drives the fall-back and the repeat protocol. */
 int ss_debug_enc_step_inject_timeout(ss_model* m);
+/* Test hook: the booking contract of a scratch set.  *booked = the bytes the set's account holds (what ss_scratch_bytes reports),
+ * *held = the sum of the sizes of all its device buffers; the contract is *booked == *held.  SS_ERR_ARG if any buffer of the set
+ * is booked under another account or none (both outputs are written anyway). */
+int ss_debug_scratch_audit(ss_scratch* sc, size_t* booked, size_t* held);
 /* Test hook: the next launch of the persistent MT decode step behaves as if a bounded wait had timed out (it publishes -1),
  * without touching the counter above.  tests/test_mt_persistent_gpu.py drives the fall-back with it. */
 int ss_debug_mt_inject_timeout(ss_model* m);

@@ -15,6 +15,7 @@
 #define SS_ERR_SCRATCH_CAP 5       // a scratch buffer would have to grow past the cap set with ss_scratch_set_cap
 #define SS_ERR_BITSTREAM 6         // corrupt or inconsistent MP3 data (ss_mp3_*)
 #define SS_ERR_UNSUPPORTED 7       // MP3 feature outside the decoder's scope: intensity stereo, free format, Layer I/II, reserved fields
+#define SS_ERR_STREAM_REPEAT 8     // a streaming-encoder call settled an unchecked earlier call that had timed out: nothing computed, repeat it
 
 #define SS_HIP_CHECK(expr)                                                              \
   do {                                                                                  \

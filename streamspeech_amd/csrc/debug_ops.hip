@@ -77,6 +77,20 @@ extern "C" int ss_debug_conv_c32(int enable) {      // 0 / 1: the per-conv slab 
 }
 extern "C" int ss_debug_conv_c16(int enable) { conv_c16_debug(enable); return SS_OK; }
 extern "C" int64_t ss_debug_enc_step_launches(void) { return (int64_t)enc_step_launch_count(); }
+// The booking contract of a scratch set: every buffer is booked under the set's own account, and what the account says is held is what
+// the buffers hold.  Outputs are written either way; SS_ERR_ARG when a buffer is booked elsewhere (or nowhere).
+extern "C" int ss_debug_scratch_audit(ss_scratch* sc, size_t* booked, size_t* held) {
+  if (!sc || !booked || !held) return SS_ERR_ARG;
+  size_t sum = 0;
+  bool foreign = false;
+  for (DevBuf* b : sc->all()) {
+    sum += b->bytes;
+    if (b->acct != &sc->acct) foreign = true;
+  }
+  *booked = sc->acct.used;
+  *held = sum;
+  return foreign ? SS_ERR_ARG : SS_OK;
+}
 extern "C" int ss_debug_rtlin(int grid, int enable) {
   if (grid < 0) return SS_ERR_ARG;
   rtlin_debug(grid, enable);

@@ -52,6 +52,7 @@ extern "C" const char* ss_error_string(int code) {
     case SS_ERR_SCRATCH_CAP: return "scratch set would grow past its cap (ss_scratch_set_cap)";
     case SS_ERR_BITSTREAM: return "corrupt or truncated MP3 bitstream";
     case SS_ERR_UNSUPPORTED: return "unsupported MP3 feature (intensity stereo, free format, Layer I/II or reserved header field)";
+    case SS_ERR_STREAM_REPEAT: return "the previous streaming-encoder call timed out and its status was not checked: repeat the call";
     default: return "unknown error";
   }
 }
@@ -172,9 +173,11 @@ extern "C" int ss_scratch_set_cap(ss_scratch* sc, size_t max_bytes) {
   return SS_OK;
 }
 extern "C" size_t ss_scratch_bytes(ss_scratch* sc) { return sc ? sc->acct.used : 0; }
+static int es_drop_stream(ss_scratch* sc);
 extern "C" int ss_scratch_trim(ss_scratch* sc, size_t keep_bytes) {
   if (!sc) return SS_ERR_ARG;
   SS_HIP_CHECK(hipDeviceSynchronize());              // nothing queued may still read what is let go
+  RET(es_drop_stream(sc));                           // (a deferred check still outstanding is settled before anything goes)
   std::vector<DevBuf*> bufs = sc->trimmable();
   std::sort(bufs.begin(), bufs.end(), [](const DevBuf* a, const DevBuf* b) { return a->bytes > b->bytes; });
   for (DevBuf* b : bufs) {
@@ -183,7 +186,7 @@ extern "C" int ss_scratch_trim(ss_scratch* sc, size_t keep_bytes) {
   }
   // state that lived in the released buffers: a stateful sequence (ss_mt_begin ... ss_mt_append, ss_encoder_stream_*) starts over
   sc->mt_Tp = 0; sc->mt_len = 0; sc->mt_enc = nullptr;
-  sc->es_cap = 0; sc->es_final = 0; sc->es_achunk = sc->es_cchunk = -1;
+  if (!sc->es_qkv.p || !sc->es_glu.p || !sc->es_out.p) sc->es_cap = 0;
   sc->dbg_logits = nullptr; sc->dbg_rows = sc->dbg_cols = 0;
   return SS_OK;
 }
@@ -192,6 +195,7 @@ extern "C" int ss_model_bind_scratch(ss_model* m, ss_scratch* sc) {
   int rc = scratch_fit_model(sc, m->cfg);
   if (rc != SS_OK) return rc;
   if (sc != m->sc) {
+    RET(es_drop_stream(m->sc));      // a streaming sequence on the set the handle leaves ends here (settled first if a check is outstanding)
     sc->refs.fetch_add(1);
     scratch_unref(m->sc);
     m->sc = sc;
@@ -358,8 +362,7 @@ extern "C" int ss_encoder_stream_set_tail(ss_model* m, int unsettled_fbank_frame
 
 // The time-out check of the persistent layer launches: waits for the stream, reads the pinned error word; on a time-out the scratch
 // set leaves the persistent form, the rows of the failed call stop being final, and the caller must repeat the call.
-static int es_check(ss_model* m, hipStream_t s, bool* repeat) {
-  ss_scratch* sc = m->sc;
+static int es_check(ss_scratch* sc, hipStream_t s, bool* repeat) {
   *repeat = false;
   SS_HIP_CHECK(hipStreamSynchronize(s));
   sc->es_pending = 0;
@@ -382,6 +385,49 @@ static int es_check(ss_model* m, hipStream_t s, bool* repeat) {
   return SS_OK;
 }
 
+// ss_scratch_trim / ss_model_bind_scratch: the streaming state of `sc` goes.  An outstanding deferred check is settled first -- a real
+// time-out is counted and the set leaves the persistent form -- and its verdict dropped: the stream starts over anyway, and nothing may
+// bring the failed call's rows back as final afterwards (es_final_prev would point into buffers that are about to be released).
+static int es_drop_stream(ss_scratch* sc) {
+  if (sc->es_pending) {
+    SS_HIP_CHECK(hipDeviceSynchronize());          // the forward was queued on the caller's stream, which the handle no longer knows
+    bool rep = false;
+    RET(es_check(sc, nullptr, &rep));
+    SS_HIP_CHECK(hipDeviceSynchronize());          // (after a time-out es_check clears the arrival flags on the null stream)
+  }
+  sc->es_pending = 0; sc->es_final = 0; sc->es_final_prev = 0; sc->es_achunk = sc->es_cchunk = -1;
+  return SS_OK;
+}
+
+// Grows the streaming state of `m`'s scratch set to `cap` rows, keeping the first `fin` rows of every buffer.  The new buffers are booked
+// under the set -- and checked against its cap -- while the old ones are still held, since both live until the rows are copied; a grow
+// refused on the cap (SS_ERR_SCRATCH_CAP) leaves the set and the stream state exactly as they were.
+static int es_grow(ss_model* m, hipStream_t s, int cap, int fin) {
+  ss_scratch* sc = m->sc;
+  const int d = m->cfg.enc_dim, L = m->cfg.enc_layers;
+  struct Grown {                                   // the new buffers until they are swapped in, the old ones after: released on the way out
+    DevBuf q, g, o;
+    ~Grown() { q.release(); g.release(); o.release(); }
+  } nb;
+  nb.q.acct = nb.g.acct = nb.o.acct = &sc->acct;
+  RET(nb.q.ensure((size_t)L * cap * 3 * d * sizeof(float)));
+  RET(nb.g.ensure((size_t)L * cap * d * sizeof(float)));
+  RET(nb.o.ensure((size_t)cap * d * sizeof(float)));
+  if (fin > 0) {
+    for (int l = 0; l < L; ++l) {
+      SS_HIP_CHECK(hipMemcpyAsync(nb.q.f() + (size_t)l * cap * 3 * d, sc->es_qkv.f() + (size_t)l * sc->es_cap * 3 * d,
+                                  (size_t)fin * 3 * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+      SS_HIP_CHECK(hipMemcpyAsync(nb.g.f() + (size_t)l * cap * d, sc->es_glu.f() + (size_t)l * sc->es_cap * d,
+                                  (size_t)fin * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    SS_HIP_CHECK(hipMemcpyAsync(nb.o.f(), sc->es_out.f(), (size_t)fin * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SS_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  sc->es_qkv.swap(nb.q); sc->es_glu.swap(nb.g); sc->es_out.swap(nb.o);
+  sc->es_cap = cap;
+  return SS_OK;
+}
+
 extern "C" int ss_encoder_stream_set_deferred(ss_model* m, int on) {
   if (!m) return SS_ERR_ARG;
   m->sc->es_deferred = on ? 1 : 0;
@@ -393,7 +439,7 @@ extern "C" int ss_encoder_stream_status(ss_model* m, void* stream, int32_t* repe
   *repeat = 0;
   if (!m->sc->es_pending && !m->sc->es_inject) return SS_OK;
   bool rep = false;
-  RET(es_check(m, (hipStream_t)stream, &rep));
+  RET(es_check(m->sc, (hipStream_t)stream, &rep));
   *repeat = rep ? 1 : 0;
   return SS_OK;
 }
@@ -411,7 +457,8 @@ extern "C" int ss_encoder_stream_forward(ss_model* m, void* stream, const float*
   hipStream_t s = (hipStream_t)stream;
   if (m->sc->es_pending) {        // the caller skipped ss_encoder_stream_status: settle the previous call first (its rows stop being final if it failed)
     bool rep = false;
-    RET(es_check(m, s, &rep));
+    RET(es_check(m->sc, s, &rep));
+    if (rep) return SS_ERR_STREAM_REPEAT;   // ... and its output already went out unchecked: say so -- nothing computed here, repeat this call
   }
   const ss_config& c = m->cfg;
   const int d = c.enc_dim, f = c.enc_ffn, k = c.conv_kernel, Ld = c.enc_layers * d, L = c.enc_layers;
@@ -420,29 +467,12 @@ extern "C" int ss_encoder_stream_forward(ss_model* m, void* stream, const float*
   const int cchunk = (conv_chunk > 0 && conv_chunk < 999) ? conv_chunk : 0;
   const int achunk_cfg = (attn_chunk > 0 && attn_chunk < 999999) ? attn_chunk : 0;   // as configured (not clipped by T2)
   const int achunk = (achunk_cfg > 0 && achunk_cfg < T2) ? achunk_cfg : 0;
-  if (m->sc->es_achunk != achunk_cfg || m->sc->es_cchunk != cchunk) { m->sc->es_final = 0; m->sc->es_achunk = achunk_cfg; m->sc->es_cchunk = cchunk; }
-  if (m->sc->es_final > T2) m->sc->es_final = 0;           // audio got shorter: a new utterance without reset
-  if (m->sc->es_cap < T2) {                             // grow (contents are only needed below es_final: keep them)
-    const int cap = std::min(c.max_rel_pos, std::max(2 * T2, 256));
-    DevBuf nq, ng, no;
-    RET(nq.ensure((size_t)L * cap * 3 * d * sizeof(float)));
-    RET(ng.ensure((size_t)L * cap * d * sizeof(float)));
-    RET(no.ensure((size_t)cap * d * sizeof(float)));
-    if (m->sc->es_final > 0) {
-      for (int l = 0; l < L; ++l) {
-        SS_HIP_CHECK(hipMemcpyAsync(nq.f() + (size_t)l * cap * 3 * d, m->sc->es_qkv.f() + (size_t)l * m->sc->es_cap * 3 * d,
-                                    (size_t)m->sc->es_final * 3 * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-        SS_HIP_CHECK(hipMemcpyAsync(ng.f() + (size_t)l * cap * d, m->sc->es_glu.f() + (size_t)l * m->sc->es_cap * d,
-                                    (size_t)m->sc->es_final * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-      }
-      SS_HIP_CHECK(hipMemcpyAsync(no.f(), m->sc->es_out.f(), (size_t)m->sc->es_final * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-      SS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    m->sc->es_qkv.release(); m->sc->es_glu.release(); m->sc->es_out.release();
-    m->sc->es_qkv = nq; m->sc->es_glu = ng; m->sc->es_out = no;
-    nq.p = nullptr; ng.p = nullptr; no.p = nullptr;
-    m->sc->es_cap = cap;
-  }
+  int fin = m->sc->es_final;      // rows kept from earlier calls; committed once the buffers are in place (a call refused on the cap changes nothing)
+  if (m->sc->es_achunk != achunk_cfg || m->sc->es_cchunk != cchunk) fin = 0;
+  if (fin > T2) fin = 0;                                // audio got shorter: a new utterance without reset
+  if (m->sc->es_cap < T2)                               // grow (contents are only needed below es_final: keep them)
+    RET(es_grow(m, s, std::min(c.max_rel_pos, std::max(2 * T2, 256)), fin));
+  m->sc->es_final = fin; m->sc->es_achunk = achunk_cfg; m->sc->es_cchunk = cchunk;
   const int cap = m->sc->es_cap;
   const int r0 = m->sc->es_final;                       // first row to (re)compute
   const int n = T2 - r0;
@@ -548,7 +578,7 @@ extern "C" int ss_encoder_stream_forward(ss_model* m, void* stream, const float*
       m->sc->es_pending = 1;      // ss_encoder_stream_status (or the next forward) settles it
     } else {
       bool rep = false;
-      RET(es_check(m, s, &rep));
+      RET(es_check(m->sc, s, &rep));
       if (rep)                    // a workgroup of some launch was not resident: this call again, one launch per op
         return ss_encoder_stream_forward(m, stream, d_fbank, T, attn_chunk, conv_chunk, d_enc_out, n_final, n_computed);
     }

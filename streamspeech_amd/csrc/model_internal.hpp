@@ -58,10 +58,21 @@ struct WeightTable {
 // Bytes held by the buffers of one scratch set (ss_scratch): `cap` > 0 bounds them (ss_scratch_set_cap)
 struct ScratchAcct { size_t cap = 0, used = 0; };
 
+// Not copyable: a copy would share `p` and overwrite the destination's `acct`, taking the buffer off its set's books.  Ownership
+// moves with swap(), which exchanges the memory and re-books it -- each side keeps its own `acct`.
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
   ScratchAcct* acct = nullptr;       // the scratch set this buffer is booked under (null: a weight-side buffer, not capped)
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  void swap(DevBuf& o) {
+    if (acct) acct->used = acct->used - bytes + o.bytes;
+    if (o.acct) o.acct->used = o.acct->used - o.bytes + bytes;
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+  }
   int ensure(size_t need) {
     if (need <= bytes) return SS_OK;
     size_t cap = need + std::min(need / 4, (size_t)256 << 20) + 4096;   // growth slack: a quarter, at most 256 MB (a pack's activations run to 12 GB)

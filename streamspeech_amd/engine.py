@@ -142,12 +142,20 @@ class Scratch:
         L.check(self.lib.ss_scratch_set_cap(self.h, int(max_bytes)), "ss_scratch_set_cap")
 
     def trim(self, keep_bytes: int = 0):
-        """Synchronises the device and releases the re-sizable buffers, largest first, until at most keep_bytes are held."""
+        """Synchronises the device and releases the re-sizable buffers, largest first, until at most keep_bytes are held.  A streaming
+        sequence on the set starts over (a deferred time-out check still outstanding is settled first)."""
         with torch.cuda.device(self.device):
             L.check(self.lib.ss_scratch_trim(self.h, int(keep_bytes)), "ss_scratch_trim")
 
     def bytes(self) -> int:
         return int(self.lib.ss_scratch_bytes(self.h))
+
+    def audit(self) -> Tuple[int, int]:
+        """Test hook: (bytes booked, bytes the set's buffers hold) -- equal when the set keeps its books; raises if a buffer of the
+        set is booked under another account (ss_debug_scratch_audit)."""
+        booked, held = C.c_size_t(0), C.c_size_t(0)
+        L.check(self.lib.ss_debug_scratch_audit(self.h, C.byref(booked), C.byref(held)), "ss_debug_scratch_audit")
+        return int(booked.value), int(held.value)
 
     def __del__(self):
         try:
@@ -207,7 +215,7 @@ class HipModel(BatchMixin):
 
     def bind_scratch(self, scratch: "Scratch"):
         """Run this handle on `scratch` from now on (between stateful sequences only: mt_begin ... mt_append and the streaming
-        encoder keep their state in the scratch set)."""
+        encoder keep their state in the scratch set; a streaming sequence on the set the handle leaves ends here)."""
         with torch.cuda.device(self.device):
             L.check(self.lib.ss_model_bind_scratch(self.h, scratch.h), "ss_model_bind_scratch")
         self.scratch = scratch

@@ -102,6 +102,7 @@ SIGNATURES = {
     "ss_debug_conv_c32": (_i, [_i]),
     "ss_debug_conv_c16": (_i, [_i]),
     "ss_debug_enc_step_launches": (_i64, []),
+    "ss_debug_scratch_audit": (_i, [_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ss_op_ln_linear": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i]),
     "ss_debug_last_logits": (_i, [_vp, _vp, _vp, _i64, C.POINTER(_i), C.POINTER(_i)]),
     "ss_debug_sk_errors": (_i, []),
@@ -117,8 +118,18 @@ SIGNATURES = {
 _lib = None
 
 
+# return codes of the C ABI that callers act on (the full list: include/streamspeech_hip.h)
+SS_ERR_ARG = 2
+SS_ERR_SCRATCH_CAP = 5
+SS_ERR_STREAM_REPEAT = 8
+
+
 class StreamSpeechHipError(RuntimeError):
-    pass
+    """A failed library call; ``code`` is its SS_ERR_* return code (None for errors raised on the Python side)."""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 def load():
@@ -152,4 +163,4 @@ def load():
 def check(rc: int, what: str = ""):
     if rc != 0:
         msg = load().ss_error_string(rc).decode()
-        raise StreamSpeechHipError(f"{what} failed: {msg} (code {rc})")
+        raise StreamSpeechHipError(f"{what} failed: {msg} (code {rc})", rc)

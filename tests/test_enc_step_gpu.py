@@ -143,3 +143,123 @@ def test_deferred_time_out_check_and_the_repeat_protocol(model):
     _drive(model, fb_all, 8, 8, Ts[:4])
     assert lib.ss_debug_enc_step_launches() > n1
     assert lib.ss_debug_sk_errors() == 0                                 # the injected time-out is not a time-out of the process
+
+
+def _abi_forward(m, fb, ac, cc):
+    """ss_encoder_stream_forward straight through the C ABI (the engine always follows a deferred forward with the status call; these
+    tests must be able to skip it) -> (return code, output, n_final, n_computed)."""
+    import ctypes as C
+    T = fb.shape[0]
+    out = torch.empty((m.encoder_out_len(T), m.cfg.enc_dim), dtype=torch.float32, device=m.device)
+    nf, nc = C.c_int32(-1), C.c_int32(-1)
+    rc = m.lib.ss_encoder_stream_forward(m.h, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.c_void_p(fb.data_ptr()), T, ac, cc,
+                                         C.c_void_p(out.data_ptr()), C.byref(nf), C.byref(nc))
+    return rc, out, nf.value, nc.value
+
+
+def _abi_status(m):
+    import ctypes as C
+    from streamspeech_amd import lib as L
+    rep = C.c_int32(-1)
+    L.check(m.lib.ss_encoder_stream_status(m.h, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(rep)), "ss_encoder_stream_status")
+    return rep.value
+
+
+def test_skipped_status_check_is_loud(model):
+    """Deferred checks on, a time-out injected into call 7, whose status is never asked for: the next forward settles call 7, finds the
+    time-out and returns SS_ERR_STREAM_REPEAT without computing anything (call 7's output went out unchecked).  Repeated, that call
+    recomputes call 7's rows too (they are not final any more) in the launch-per-op form, and every checked output -- rows, final-row
+    counts, CTC ids -- is the reference run's."""
+    from streamspeech_amd import synth
+    from streamspeech_amd import lib as L
+    lib = model.lib
+    fb_all = torch.from_numpy(synth.synth_fbank(54, 700)).to(model.device)
+    Ts = list(range(40, 700, 32)) + [700]
+    model.set_persistent_mt_step(64)
+    model.ctc_speculate = False
+    ref, ref_final = _drive(model, fb_all, 8, 8, Ts)
+    ref_ctc = [(model.ctc_greedy(0, o)[0], model.ctc_greedy(1, o)[0]) for o in ref]
+    err0 = lib.ss_debug_sk_errors()
+    model.encoder_stream_reset()
+    L.check(lib.ss_encoder_stream_set_deferred(model.h, 1), "ss_encoder_stream_set_deferred")
+    try:
+        n0 = lib.ss_debug_enc_step_launches()
+        for i, T in enumerate(Ts):
+            fb = fb_all[:T].contiguous()
+            if i == 7:
+                assert lib.ss_debug_enc_step_launches() > n0              # the persistent form ran (its checks were deferred)
+                L.check(lib.ss_debug_enc_step_inject_timeout(model.h), "ss_debug_enc_step_inject_timeout")
+            rc, out, nf, nc = _abi_forward(model, fb, 8, 8)
+            if i == 8:
+                assert rc == L.SS_ERR_STREAM_REPEAT, rc
+                assert (nf, nc) == (-1, -1)                                 # nothing computed, nothing reported
+                n8 = lib.ss_debug_enc_step_launches()
+                rc, out, nf, nc = _abi_forward(model, fb, 8, 8)             # the repeat
+                assert lib.ss_debug_enc_step_launches() == n8               # one launch per op now
+                assert nc == model.encoder_out_len(T) - ref_final[6]        # from where call 7 started: its rows are not final any more
+            assert rc == 0, (i, rc)
+            if i == 7:
+                continue                                                    # status skipped; its output is not to be trusted
+            assert _abi_status(model) == 0
+            assert nf == ref_final[i], (i, nf, ref_final[i])
+            assert (out - ref[i]).abs().max().item() < 2e-5, i
+            assert (model.ctc_greedy(0, out)[0], model.ctc_greedy(1, out)[0]) == ref_ctc[i], i
+    finally:
+        L.check(lib.ss_encoder_stream_set_deferred(model.h, 0), "ss_encoder_stream_set_deferred")
+        model.set_persistent_mt_step(64)                                    # re-arms the persistent layer launches
+        model.encoder_stream_reset()
+    assert lib.ss_debug_sk_errors() == err0                                 # the injected time-out is not a time-out of the process
+
+
+@pytest.mark.parametrize("how", ["trim", "rebind"])
+def test_trim_or_rebind_with_a_check_pending_starts_a_fresh_stream(model, how):
+    """A deferred check is outstanding (and will report a time-out) when the scratch set is trimmed, or when the handle is bound to
+    another set and back.  Both settle it first: the set leaves the persistent form, the injected verdict is used up, and the next
+    forward starts a fresh stream -- every row computed, output equal to the full recompute -- instead of reviving final rows of
+    buffers that are gone."""
+    from streamspeech_amd import synth
+    from streamspeech_amd import lib as L
+    from streamspeech_amd.engine import Scratch
+    lib = model.lib
+    sc, other = Scratch(), Scratch()
+    m = model.new_context(scratch=sc)
+    m.set_persistent_mt_step(64)
+    fb_all = torch.from_numpy(synth.synth_fbank(55, 600)).to(model.device)
+    Ts = list(range(40, 600, 32)) + [600]
+    err0 = lib.ss_debug_sk_errors()
+    m.encoder_stream_reset()
+    L.check(lib.ss_encoder_stream_set_deferred(m.h, 1), "ss_encoder_stream_set_deferred")
+    try:
+        n0 = lib.ss_debug_enc_step_launches()
+        for i, T in enumerate(Ts):
+            fb = fb_all[:T].contiguous()
+            if i == 6:
+                assert lib.ss_debug_enc_step_launches() > n0
+                L.check(lib.ss_debug_enc_step_inject_timeout(m.h), "ss_debug_enc_step_inject_timeout")
+            rc, out, nf, nc = _abi_forward(m, fb, 8, 8)
+            assert rc == 0, (i, rc)
+            if i == 6:                                                      # the check of this call is pending: let the set go
+                assert nf > 0
+                if how == "trim":
+                    sc.trim(0)
+                else:
+                    m.bind_scratch(other)
+                    m.bind_scratch(sc)
+                booked, held = sc.audit()
+                assert booked == held == sc.bytes()
+                assert _abi_status(m) == 0                                  # settled: nothing outstanding, the injection used up
+                n7 = lib.ss_debug_enc_step_launches()
+                continue
+            assert _abi_status(m) == 0
+            full = m.encoder_forward(fb, 8, 8)
+            assert (out - full).abs().max().item() < 5e-5, i
+            if i == 7:
+                assert nc == m.encoder_out_len(T)                           # a fresh stream
+            if i > 6:
+                assert lib.ss_debug_enc_step_launches() == n7               # the settled time-out took the set off the persistent form
+        booked, held = sc.audit()
+        assert booked == held == sc.bytes()
+    finally:
+        L.check(lib.ss_encoder_stream_set_deferred(m.h, 0), "ss_encoder_stream_set_deferred")
+        m.encoder_stream_reset()
+    assert lib.ss_debug_sk_errors() == err0
