@@ -322,6 +322,19 @@ int ss_batch_ctc_greedy(ss_model* m, void* stream, int head, int B, const float*
 int ss_batch_mt_greedy(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp,
                        const int32_t* h_max_len, int min_len, int32_t* h_out_tokens, int out_stride,
                        int32_t* h_n_out, float* d_feats, int feat_rows);
+/* Beam search of the offline first-pass text decoder: the reference's SequenceGenerator.generate_decoder with beam_size_mt = beam
+ * (fairseq unity/sequence_generator.py:158-525, BeamSearch, finalize_hypos; len_penalty 1), from [</s>] with no prefix.  B
+ * utterances x beam hypothesis rows in lockstep; 1 <= beam <= 32 (else SS_ERR_ARG), B * beam <= 256 (else SS_ERR_CAPACITY), checked
+ * before anything is launched.  unk_penalty is subtracted from the <unk> log-probability (--unkpen); normalize != 0 divides a
+ * finished hypothesis' score by its length (the reference's default; --unnormalized = 0).  Per utterance b and rank i < beam, in the
+ * reference's final order (score descending): h_out_tokens [B][beam][out_stride] the tokens incl. the final </s>, h_n_out [B][beam]
+ * their number (0 for a rank with no hypothesis), h_scores [B][beam], h_pos_scores [B][beam][out_stride] (may be NULL) the per-token
+ * scores.  d_feats [B][feat_rows][dec_dim] receives the decoder states of each utterance's BEST hypothesis: h_n_out[b][0] valid rows
+ * (</s> + its tokens without the final </s>), as ss_batch_mt_greedy; rows past them are left untouched.  Buffers are booked on the
+ * handle's scratch set (SS_ERR_SCRATCH_CAP past a cap, the set stays usable).  Synchronises every few steps and at the end. */
+int ss_batch_mt_beam(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                     const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens,
+                     int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows);
 int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float* d_feats, int feat_rows,
                        const int32_t* h_n, int t2u_causal, int mask_eos, int32_t* d_raw, int32_t* d_tokens,
                        int32_t* d_counts);

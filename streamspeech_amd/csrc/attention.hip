@@ -168,15 +168,27 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs p) {
 // streams its key row (256 contiguous bytes).  P.V: lane = output dim, probabilities broadcast with
 // v_readlane, V rows read coalesced.  Same online softmax as the tiled kernel.
 // -------------------------------------------------------------------------------------------------
+template <bool ANC>
 __global__ __launch_bounds__(256) void attention_decode_kernel(AttnArgs p) {
   // 4 waves per (query, head): wave w takes key tiles w, w+4, ...; partial (max, sum, acc) merged in LDS
+  const int* anc = nullptr;
   if (p.nseg > 0) {
     const int* sg = p.segs + 4 * blockIdx.z;
     p.Tq = sg[1]; p.Tk = sg[3];
     if ((int)blockIdx.x >= p.Tq) return;
     p.Q += (size_t)sg[0] * p.ldq; p.O += (size_t)sg[0] * p.ldo;
-    p.K += (size_t)sg[2] * p.ldk; p.V += (size_t)sg[2] * p.ldv;
+    if (ANC) {
+      anc = p.anc + (size_t)blockIdx.z * p.anc_ld;
+    } else {
+      p.K += (size_t)sg[2] * p.ldk; p.V += (size_t)sg[2] * p.ldv;
+    }
   }
+  // row of key / value j: position j of the slot that holds it (ANC), else row j of the segment
+  auto krow = [&](int j) -> size_t {
+    if (!ANC) return (size_t)j;
+    const int a = min((unsigned)anc[j], (unsigned)(p.anc_slots - 1));
+    return (size_t)a * p.anc_ld + j;
+  };
   __shared__ float part_m[4], part_l[4], part_acc[4][DH];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x, h = blockIdx.y;
@@ -196,10 +208,10 @@ __global__ __launch_bounds__(256) void attention_decode_kernel(AttnArgs p) {
     // fmaf(0, v, acc) == acc, so the sum is the one the 16-row groups of the earlier form produced.
     float vv[64];
 #pragma unroll
-    for (int u = 0; u < 64; ++u) vv[u] = p.V[(size_t)min(j0 + u, kmax - 1) * p.ldv + hoff + lane];
+    for (int u = 0; u < 64; ++u) vv[u] = p.V[krow(min(j0 + u, kmax - 1)) * p.ldv + hoff + lane];
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     if (vis) {
-      const float4* kr = reinterpret_cast<const float4*>(p.K + (size_t)j * p.ldk + hoff);
+      const float4* kr = reinterpret_cast<const float4*>(p.K + krow(j) * p.ldk + hoff);
 #pragma unroll
       for (int d4 = 0; d4 < DH / 4; ++d4) {
         const float4 kv = kr[d4];
@@ -804,8 +816,14 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
   if ((a.ldk & 3) || (a.ldv & 3)) return SS_ERR_ARG;
   const int gz = a.nseg > 0 ? a.nseg : 1;
   if (a.q0 != 0 && (a.nseg > 0 || a.causal)) return SS_ERR_ARG;
+  if (a.anc) {      // the ancestry-indexed form exists in the ragged decode kernel only
+    if (a.nseg <= 0 || a.P || tq > 8 || a.q0 != 0 || a.no_decode_kernel || a.anc_ld <= 0 || a.anc_slots <= 0) return SS_ERR_ARG;
+    hipLaunchKernelGGL(attention_decode_kernel<true>, dim3(tq, a.H, gz), dim3(256), 0, stream, a);
+    SS_LAUNCH_CHECK();
+    return SS_OK;
+  }
   if (!a.P && tq <= 8 && a.q0 == 0 && !a.no_decode_kernel) {
-    hipLaunchKernelGGL(attention_decode_kernel, dim3(tq, a.H, gz), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(attention_decode_kernel<false>, dim3(tq, a.H, gz), dim3(256), 0, stream, a);
     SS_LAUNCH_CHECK();
     return SS_OK;
   }

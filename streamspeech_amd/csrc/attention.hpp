@@ -41,6 +41,11 @@ struct AttnArgs {
   // kernel -- ragged batches whose max_q depends on the pack (T2U encoder rows) must not change kernels with it (pack-invariant bits);
   // the lock-step MT decode (max_q = 1 by construction) keeps 0.
   int no_decode_kernel = 0;
+  // Ancestry indirection of the beam search (beam.hip; ragged decode form only, nullptr = plain addressing): key / value j of segment z
+  // is row anc[z * anc_ld + j] * anc_ld + j of K / V -- slot anc[..] wrote its row of position j there and never overwrites it --
+  // and the segment's k_start is ignored.  Slot ids are clamped to [0, anc_slots).  The key-tile and summation order are those of
+  // the plain form, so an identity table gives its bits.
+  const int* anc = nullptr; int anc_ld = 0; int anc_slots = 0;
 };
 constexpr int ATTN_PART_FLOATS = 5 * 256 * 4;   // 5 b128 per thread: o[4], {m, l, -, -}
 constexpr int ATTN_PART_SLOTS = 512, ATTN_CNT_SLOTS = 512;

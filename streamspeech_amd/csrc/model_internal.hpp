@@ -200,7 +200,9 @@ struct ss_scratch {
   int mt_persistent = g_mt_persistent_default;   // workgroups of the persistent decode step (ss_mt_set_persistent); 0 = launch-per-op
   DevBuf mt_tok;                 // device token chain [max_tgt_pos] (greedy search feeds itself)
   DevBuf seg_buf;                // ragged-batch segment tables / batched token chain
-  DevBuf bmt_self;               // batched MT self-attention cache [layer][B][Lcap][3D]
+  DevBuf bmt_self;               // batched MT self-attention cache [layer][B][Lcap][3D] (beam search: [layer][B*k][Lcap][3D])
+  DevBuf bmb_feat;               // beam search: post-LN decoder states of every slot and step [B*k][Lcap][D]
+  DevBuf bmb_state;              // beam search: token / score / ancestry tables, candidates, finalised hypotheses (beam.hip)
   int32_t* mt_tok_host = nullptr;  // pinned staging of the same
   size_t mt_tok_host_n = 0;
   // incremental streaming encoder (ss_encoder_stream_*): per-layer fused q|k|v rows and GLU outputs
@@ -236,10 +238,10 @@ struct ss_scratch {
     sk_workspace_free(skws);
   }
   std::vector<DevBuf*> all() {
-    return {&ws, &mt_cross, &mt_self, &mt_ws, &attn_split, &mt_gran, &mt_tok, &seg_buf, &bmt_self, &es_qkv, &es_glu, &es_out, &es_step, &v_ws, &v_small, &v_segs};
+    return {&ws, &mt_cross, &mt_self, &mt_ws, &attn_split, &mt_gran, &mt_tok, &seg_buf, &bmt_self, &bmb_feat, &bmb_state, &es_qkv, &es_glu, &es_out, &es_step, &v_ws, &v_small, &v_segs};
   }
   // what ss_scratch_trim may let go: buffers every entry point re-sizes before use (the zero-initialised ones and the KV cache stay)
-  std::vector<DevBuf*> trimmable() { return {&ws, &mt_cross, &mt_ws, &seg_buf, &bmt_self, &es_qkv, &es_glu, &es_out, &v_ws, &v_small, &v_segs}; }
+  std::vector<DevBuf*> trimmable() { return {&ws, &mt_cross, &mt_ws, &seg_buf, &bmt_self, &bmb_feat, &bmb_state, &es_qkv, &es_glu, &es_out, &v_ws, &v_small, &v_segs}; }
 };
 [[maybe_unused]] static void scratch_unref(ss_scratch* sc) { if (sc && sc->refs.fetch_sub(1) == 1) delete sc; }
 // the fixed-size pieces a model of configuration `c` needs in the scratch set it runs on: the MT self-attention cache, the token chain

@@ -42,6 +42,18 @@ def _i32(vals):
     return (C.c_int32 * len(vals))(*[int(v) for v in vals])
 
 
+MT_BEAM_MAX_ROWS = 256     # B * beam hypothesis rows of one ss_batch_mt_beam call
+MT_BEAM_MAX = 32
+
+
+def plan_beam_groups(B: int, beam: int, max_rows: int = MT_BEAM_MAX_ROWS) -> List[Tuple[int, int]]:
+    """Consecutive [start, end) utterance ranges, in order, with (end - start) * beam <= max_rows."""
+    if not 1 <= beam <= max_rows:
+        raise ValueError(f"beam {beam} outside [1, {max_rows}]")
+    per = max_rows // beam
+    return [(b, min(b + per, B)) for b in range(0, B, per)]
+
+
 class BatchMixin:
     """Ragged-batch calls on a HipModel (B utterances packed along the row axis, no padding)."""
 
@@ -93,6 +105,43 @@ class BatchMixin:
                                             stride, n_out, _ptr(feats), rows), "ss_batch_mt_greedy")
         toks = [list(out[b * stride: b * stride + n_out[b]]) for b in range(B)]
         return toks, feats, list(n_out)
+
+    def batch_mt_beam(self, enc_packed: torch.Tensor, Tp: List[int], max_len: List[int], beam: int, min_len: int = 1,
+                      unk_penalty: float = 0.0, normalize: bool = True):
+        """Beam search of the first-pass text decoder (ss_batch_mt_beam) -> (n-best lists, feats [B, Lcap, D], n_feats list).
+        nbest[b] holds up to `beam` dicts {"tokens" (incl. final eos), "score", "positional_scores"} in the reference's final order;
+        feats / n_feats are the decoder states of hypothesis 0, as batch_mt_greedy returns them.  A pack with B * beam > 256 rows
+        runs as consecutive sub-calls (plan_beam_groups); pack-invariant arithmetic makes the split invisible."""
+        B = len(Tp)
+        if not 1 <= beam <= MT_BEAM_MAX:
+            raise ValueError(f"beam {beam} outside [1, {MT_BEAM_MAX}]")
+        Lmax = max(max_len)
+        rows, stride = Lmax + 2, Lmax + 1
+        feats = torch.empty((B, rows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
+        nbest: List[List[dict]] = []
+        off = np.concatenate([[0], np.cumsum(Tp)]).astype(np.int64)
+        for b0, b1 in plan_beam_groups(B, beam):
+            n = b1 - b0
+            enc = enc_packed[int(off[b0]):int(off[b1])]
+            out = (C.c_int32 * (n * beam * stride))()
+            n_out = (C.c_int32 * (n * beam))()
+            sc = (C.c_float * (n * beam))()
+            pos = (C.c_float * (n * beam * stride))()
+            L.check(self.lib.ss_batch_mt_beam(self.h, _stream(), n, beam, _ptr(enc), _i32(Tp[b0:b1]), _i32(max_len[b0:b1]),
+                                              min_len, float(unk_penalty), 1 if normalize else 0, out, stride, n_out, sc, pos,
+                                              _ptr(feats[b0:b1]), rows), "ss_batch_mt_beam")
+            for b in range(n):
+                hyps = []
+                for i in range(beam):
+                    o = b * beam + i
+                    k = n_out[o]
+                    if k <= 0:
+                        continue
+                    hyps.append({"tokens": list(out[o * stride: o * stride + k]), "score": float(sc[o]),
+                                 "positional_scores": list(pos[o * stride: o * stride + k])})
+                nbest.append(hyps)
+        n_feats = [len(h[0]["tokens"]) if h else 0 for h in nbest]
+        return nbest, feats, n_feats
 
     def last_logits(self) -> torch.Tensor:
         """Dense logits [rows, cols] of this context's last batch_ctc_greedy / batch_t2u_units call (test hook: arg-max margins)."""

@@ -20,6 +20,9 @@ given (then both come from ss_row_max_logprob over the unit logits of the single
 point: one more kernel, no torch arithmetic).  `T-` lines (generate.py:258-259) are written when
 the manifest carries target units (`tgt_audio` column, as the reference's S2UT manifests do).
 
+The first-pass text search is greedy by default; `--beam-mt k` runs the reference's beam search (generator_mt with beam_size_mt = k,
+`--unkpen`, `--unnormalized`) on the GPU (ss_batch_mt_beam), and `--beam` is accepted for parity (the CTC unit generator has no search).
+
 Pinned against the reference's own generator classes run on CPU (oracle/ref_offline.py ->
 tests/golden/offline_generator.json; tests/test_offline_generator_cpu.py, tests/test_offline_generator_gpu.py).
 """
@@ -63,7 +66,8 @@ def ordered_batches(lengths: Sequence[int], batch_size: int, max_tokens: int = 0
 def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: Dict[str, object], results_path: str,
              subset: str = "test", batch_size: int = 32, max_tokens: int = 0, max_len_a: float = 0.0,
              max_len_b: int = 200, max_len_a_mt: float = 0.0, max_len_b_mt: int = 200, dur_prediction: bool = True, dump_wav: bool = True, t2u_causal: bool = False,
-             scores: bool = False, log=None, targets: Optional[Dict[int, Sequence[int]]] = None) -> Dict[int, Dict]:
+             scores: bool = False, log=None, targets: Optional[Dict[int, Sequence[int]]] = None, beam_mt: int = 1,
+             unk_penalty: float = 0.0, normalize: bool = True) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses."""
     cfg = model.cfg
@@ -93,7 +97,13 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
         # :130-131); src_len is the fbank frame count.  --max-len-a/-b configure the (NAR) unit generator, which has
         # no length search here.
         mx = [min(int(max_len_a_mt * t + max_len_b_mt), cfg.max_target_positions - 1) for t in T]
-        toks, feats, n = model.batch_mt_greedy(enc, Tp, mx)
+        if beam_mt > 1:
+            # --beam-mt k: the reference's beam search (generator_mt with beam_size_mt = k, --unkpen, --unnormalized); the D- text
+            # and the T2U input are hypothesis 0 of each n-best list (sequence_generator_multi_decoder_ctc.py:265-300)
+            nbest, feats, n = model.batch_mt_beam(enc, Tp, mx, beam_mt, 1, unk_penalty, normalize)
+            toks = [h[0]["tokens"] if h else [] for h in nbest]
+        else:
+            toks, feats, n = model.batch_mt_greedy(enc, Tp, mx)
         unit_toks = model.batch_t2u_units(feats, n, t2u_causal=t2u_causal, mask_eos=True)
         codes = [units_from_tokens(t, cfg) for t in unit_toks]
         have = [b for b, c in enumerate(codes) if len(c) > 0]
@@ -176,9 +186,7 @@ def load_manifest(path: str, targets: Optional[Dict[int, List[int]]] = None) -> 
     return rows
 
 
-def main(argv: Optional[List[str]] = None):
-    from .agent import StreamSpeechS2STAgent
-    from .modules import CodeHiFiGANVocoderWithDur, StreamSpeechModel, load_model_state
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("data", nargs="?", default=None, help="data root holding <gen-subset>.tsv and the config yamls")
     ap.add_argument("--gen-subset", default="test")
@@ -202,7 +210,22 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--num-shards", type=int, default=int(os.environ.get("WORLD_SIZE", "1")))
     ap.add_argument("--shard-id", type=int, default=int(os.environ.get("RANK", "0")))
     ap.add_argument("--device", default="cuda:%s" % os.environ.get("LOCAL_RANK", "0"))
+    # search options of pred.offline-s2st.sh: --beam-mt runs the first-pass text search as a beam search; --beam configures the
+    # unit generator, a CTC decoder without a search, so (as in the reference) it changes nothing
+    ap.add_argument("--beam-mt", type=int, default=1, help="beam of the first-pass text search (1 = greedy; at most 32)")
+    ap.add_argument("--beam", type=int, default=1, help="unit generator beam (accepted for parity; the CTC unit decoder has no search)")
+    ap.add_argument("--unkpen", type=float, default=0.0, help="subtracted from the <unk> log-probability of the text search")
+    ap.add_argument("--unnormalized", action="store_true", help="text search: do not divide hypothesis scores by their length")
+    return ap
+
+
+def main(argv: Optional[List[str]] = None):
+    from .agent import StreamSpeechS2STAgent
+    from .modules import CodeHiFiGANVocoderWithDur, StreamSpeechModel, load_model_state
+    ap = build_parser()
     a = ap.parse_args(argv)
+    if not 1 <= a.beam_mt <= 32:
+        ap.error("--beam-mt must be in [1, 32]")
 
     # model / dictionaries / CMVN exactly as the agent loads them (agent :355-420)
     ns = argparse.Namespace(config_yaml=a.config_yaml, multitask_config_yaml=a.multitask_config_yaml,
@@ -252,7 +275,8 @@ def main(argv: Optional[List[str]] = None):
     sub = a.gen_subset if a.num_shards == 1 else f"{a.gen_subset}.shard{a.shard_id}"
     hyps = generate(model, voc, items, holder.dict, a.results_path, sub, a.batch_size, a.max_tokens, a.max_len_a,
                     a.max_len_b, a.max_len_a_mt, a.max_len_b_mt, a.dur_prediction, not a.no_wav,
-                    getattr(holder.model, "uni_encoder", False), a.scores, targets=targets or None)
+                    getattr(holder.model, "uni_encoder", False), a.scores, targets=targets or None, beam_mt=a.beam_mt,
+                    unk_penalty=a.unkpen, normalize=not a.unnormalized)
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
 
 
