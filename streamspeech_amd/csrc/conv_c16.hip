@@ -6,15 +6,12 @@
 //     the contraction then has no weight traffic at all: per tap 4 LDS fragments and 16 MFMAs;
 //   * persistent workgroups, three per CU (24 KB of LDS each); per block of 256 output rows the input slab (256 + (k - 1) dil rows
 //     x 16 channels, rows padded to 20 floats) is staged once, input leaky-ReLU applied on the way; wave tile 64 rows x 16 columns;
-//   * float4 bias / residual / MRF accumulate / mean / output.
+//   * float4 bias / residual / MRF accumulate / mean / output (segment walk and epilogue: slab_common.hpp).
 // Exact f32, tap-major fmaf chains: differs from resblock.hip / conv_slab.hip by summation order only.
-#include "gemm.hpp"
-
-#include <cstdlib>
+#include "slab_common.hpp"
 
 namespace ss {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 namespace {
@@ -40,27 +37,10 @@ __global__ __launch_bounds__(256, 3) void conv_c16_kernel(const GemmArgs p, cons
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int r = lane & 15, g = lane >> 4;
 
-  const int nseg = p.nseg > 0 ? p.nseg : 1;
-  if (t == 0) {
-    int acc = 0;
-    for (int s = 0; s < nseg; ++s) {
-      s_blk[s] = acc;
-      const int len = p.nseg > 0 ? p.segs[4 * s + 1] : p.M;
-      acc += (len + BM - 1) / BM;
-    }
-    s_blk[nseg] = acc;
-  }
+  SlabWalk<GemmArgs> w(p, s_blk, BM);
   __syncthreads();
-  const int nblocks = s_blk[nseg];
+  const int nblocks = w.nblocks();
   const float slope = p.in_slope;
-
-  int seg = 0, seg_lo = 0, seg_hi = 0, m0 = 0;
-  auto locate = [&](int blk) {                 // blocks ascend per workgroup
-    while (blk >= s_blk[seg + 1]) ++seg;
-    seg_lo = p.nseg > 0 ? p.segs[4 * seg] : 0;
-    seg_hi = seg_lo + (p.nseg > 0 ? p.segs[4 * seg + 1] : p.in_len);
-    m0 = seg_lo + (blk - s_blk[seg]) * BM;
-  };
 
   int blk = blockIdx.x;
   if (blk >= nblocks) return;
@@ -70,8 +50,8 @@ __global__ __launch_bounds__(256, 3) void conv_c16_kernel(const GemmArgs p, cons
   for (int tap = 0; tap < TAPS; ++tap) wf[tap] = *reinterpret_cast<const f32x4*>(p.W + (size_t)r * K + tap * C + 4 * g);
 
   for (; blk < nblocks; blk += gridDim.x) {
-    locate(blk);
-    const int cm0 = m0;
+    w.locate(blk, p.in_len);
+    const int m0 = w.m0, seg_lo = w.seg_lo, seg_hi = w.seg_hi;
     const int m_hi = p.nseg > 0 ? seg_hi : min(seg_hi, p.M);
     const bool edge = (m0 - p.pad < seg_lo) || (m0 - p.pad + slab_rows > seg_hi);   // zero padding only in an utterance's first / last blocks
     __syncthreads();                                       // previous block's slab reads are done
@@ -140,43 +120,15 @@ __global__ __launch_bounds__(256, 3) void conv_c16_kernel(const GemmArgs p, cons
     f32x4 rr[WM], rr2[WM];
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
-      const int mc = min(cm0 + wave * 16 * WM + i * 16 + r_e, m_hi - 1);
+      const int mc = min(m0 + wave * 16 * WM + i * 16 + r_e, m_hi - 1);
       if (p.R) rr[i] = *reinterpret_cast<const f32x4*>(p.R + (size_t)mc * p.ldr + n);
       if (p.R2) rr2[i] = *reinterpret_cast<const f32x4*>(p.R2 + (size_t)mc * p.ldr2 + n);
     }
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
-      const int m = cm0 + wave * 16 * WM + i * 16 + r_e;
-      f32x4 v = acc[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] += bb[e];
-      if (p.act == ACT_LRELU) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.act_slope;
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] *= p.alpha;
-      if (p.R) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += rr[i][e];
-      }
-      if (p.R2) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = rr2[i][e] + v[e];
-      }
-      if (p.div > 0.f) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] / p.div;
-      }
-      if (m < m_hi) {
-        *reinterpret_cast<f32x4*>(p.C + (size_t)m * p.ldc + n) = v;
-        if (p.C2) {
-          f32x4 w2;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) w2[e] = v[e] > 0.f ? v[e] : v[e] * p.c2_slope;
-          *reinterpret_cast<f32x4*>(p.C2 + (size_t)m * p.ldc2 + n) = w2;
-        }
-      }
+      const int m = m0 + wave * 16 * WM + i * 16 + r_e;
+      const f32x4 v = slab_epi_apply(p, acc[i], bb, rr[i], rr2[i]);
+      if (m < m_hi) slab_epi_store(p, m, n, v);
     }
   }
 #endif
@@ -188,29 +140,22 @@ void conv_c16_debug(int enable) { if (enable >= 0) dispatch_edit([enable](Dispat
 bool conv_c16_enabled() { return !disp().c16_off; }
 
 bool conv_c16_eligible(const GemmArgs& a) {
-  return !disp().c16_off && a.same_rows && a.stride == 1 && a.chunk == 0 && !a.glu && !a.ln_g && !a.x3 && a.Cin == C1_C && a.N == C1_C &&
-         a.lda == C1_C && (a.ldc & 3) == 0 && (!a.R || (a.ldr & 3) == 0) && (!a.R2 || (a.ldr2 & 3) == 0) && (!a.C2 || (a.ldc2 & 3) == 0) &&
-         (a.taps == 3 || a.taps == 7 || a.taps == 11) && a.dil >= 1 && (a.taps - 1) * a.dil <= C1_MAXHALO && a.pad >= 0 &&
-         a.pad <= (a.taps - 1) * a.dil && a.nseg <= C1_MAXSEG && a.M >= disp().c16_min_rows &&
-         slab_rows_ok(a.M) &&
-         (a.in_act == ACT_NONE || (a.in_act == ACT_LRELU && a.in_slope > 0.f && a.in_slope < 1.f)) &&
-         (a.act == ACT_NONE || a.act == ACT_LRELU);
+  return !disp().c16_off && slab_conv_ok(a, C1_C) && (a.taps == 3 || a.taps == 7 || a.taps == 11) && a.dil >= 1 &&
+         (a.taps - 1) * a.dil <= C1_MAXHALO && a.pad >= 0 && a.pad <= (a.taps - 1) * a.dil && a.nseg <= C1_MAXSEG &&
+         a.M >= disp().c16_min_rows && slab_rows_ok(a.M);
 }
 
 template <int TAPS, bool LRELU>
 static int launch_c16_t(const GemmArgs& a, hipStream_t stream) {
   const int slab_rows = C1_BM + (a.taps - 1) * a.dil;
-  const size_t lds = (size_t)((slab_rows * C1_LDA + 3) & ~3) * sizeof(float) + (C1_MAXSEG + 2) * sizeof(int);
+  const size_t lds = slab_lds_bytes(slab_rows, C1_LDA, C1_MAXSEG);
   SkWorkspace* st = nullptr;                       // (only for the device's CU count, cached per context)
   int rc = sk_workspace_acquire(stream, &st);
   if (rc != SS_OK) return rc;
-  const int nseg = a.nseg > 0 ? a.nseg : 1;
-  const long long max_blocks = (long long)cdiv(a.M, C1_BM) + nseg;      // upper bound (per-segment round-up)
-  static const int occ_env = getenv("SS_CONV_C16_WG_PER_CU") ? atoi(getenv("SS_CONV_C16_WG_PER_CU")) : 0;
-  const int occ = occ_env > 0 ? occ_env : 3;       // resident workgroups per CU (<= 168 registers, 25 KB of LDS)
-  const int grid = (int)std::min<long long>((long long)occ * st->cus, std::max<long long>(1, max_blocks));
+  // three resident workgroups per CU (<= 168 registers, 25 KB of LDS)
+  const int grid = slab_grid(3, st->cus, a.M, C1_BM, a.nseg);
   ProfRec rec{}; bool prof = false;
-  rc = prof_begin(a, stream, 26, rec, prof);
+  rc = prof_begin(a, stream, PROF_CONV_C16, rec, prof);
   if (rc != SS_OK) return rc;
   hipLaunchKernelGGL((conv_c16_kernel<TAPS, LRELU>), dim3(grid), dim3(256), lds, stream, a, slab_rows);
   SS_LAUNCH_CHECK();

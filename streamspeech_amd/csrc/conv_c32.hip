@@ -13,11 +13,11 @@
 //     fragments taken from L2 straight into registers for 32 MFMAs; the ring holds the 8 fragments of TWO taps (the tap loop is
 //     unrolled by two so that ring slots are static), each slot refilled with the tap two ahead -- after the last taps with the
 //     next block's first two;
-//   * no barrier, no LDS-DMA piece, no LDS write inside the contraction; float4 bias / residual / MRF accumulate / mean / output.
+//   * no barrier, no LDS-DMA piece, no LDS write inside the contraction; float4 bias / residual / MRF accumulate / mean / output
+//     (segment walk and epilogue: slab_common.hpp).
 // Exact f32, tap-major fmaf chains: differs from resblock.hip / conv_slab.hip by summation order only.
-#include "gemm.hpp"
+#include "slab_common.hpp"
 
-#include <cstdlib>
 #include <type_traits>
 
 #ifndef C32_FENCE
@@ -31,7 +31,6 @@
 
 namespace ss {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 namespace {
@@ -58,27 +57,10 @@ __global__ __launch_bounds__(256, 3) void conv_c32_kernel(const GemmArgs p, cons
   const int r = lane & 15, g = lane >> 4;
   const int K = p.taps * C;
 
-  const int nseg = p.nseg > 0 ? p.nseg : 1;
-  if (t == 0) {
-    int acc = 0;
-    for (int s = 0; s < nseg; ++s) {
-      s_blk[s] = acc;
-      const int len = p.nseg > 0 ? p.segs[4 * s + 1] : p.M;
-      acc += (len + BM - 1) / BM;
-    }
-    s_blk[nseg] = acc;
-  }
+  SlabWalk<GemmArgs> w(p, s_blk, BM);
   __syncthreads();
-  const int nblocks = s_blk[nseg];
+  const int nblocks = w.nblocks();
   const float slope = p.in_slope;
-
-  int seg = 0, seg_lo = 0, seg_hi = 0, m0 = 0;
-  auto locate = [&](int blk) {                 // blocks ascend per workgroup
-    while (blk >= s_blk[seg + 1]) ++seg;
-    seg_lo = p.nseg > 0 ? p.segs[4 * seg] : 0;
-    seg_hi = seg_lo + (p.nseg > 0 ? p.segs[4 * seg + 1] : p.in_len);
-    m0 = seg_lo + (blk - s_blk[seg]) * BM;
-  };
 
   // weight fragment f of tap `tap`: channel block cc = f / 2, column tile j = f % 2; lane (r, g) takes 16 B of row 16 j + r
   const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, C3_NUM_RECORDS, 0x00020000);
@@ -97,8 +79,8 @@ __global__ __launch_bounds__(256, 3) void conv_c32_kernel(const GemmArgs p, cons
   for (int f = 0; f < 4; ++f) { ring[f] = wload(0, f); ring[4 + f] = wload(taps > 1 ? 1 : 0, f); }
 
   for (; blk < nblocks; blk += gridDim.x) {
-    locate(blk);
-    const int cm0 = m0;
+    w.locate(blk, p.in_len);
+    const int m0 = w.m0, seg_lo = w.seg_lo, seg_hi = w.seg_hi;
     const int m_hi = p.nseg > 0 ? seg_hi : min(seg_hi, p.M);
     const bool edge = (m0 - p.pad < seg_lo) || (m0 - p.pad + slab_rows > seg_hi);   // zero padding only in an utterance's first / last blocks
     __syncthreads();                                       // previous block's slab reads are done
@@ -196,7 +178,7 @@ __global__ __launch_bounds__(256, 3) void conv_c32_kernel(const GemmArgs p, cons
     f32x4 rr[WM][2], rr2[WM][2];
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
-      const int mc = min(cm0 + wave * 16 * WM + i * 16 + r_e, m_hi - 1);
+      const int mc = min(m0 + wave * 16 * WM + i * 16 + r_e, m_hi - 1);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         if (p.R) rr[i][j] = *reinterpret_cast<const f32x4*>(p.R + (size_t)mc * p.ldr + j * 16 + g_e * 4);
@@ -205,40 +187,11 @@ __global__ __launch_bounds__(256, 3) void conv_c32_kernel(const GemmArgs p, cons
     }
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
-      const int m = cm0 + wave * 16 * WM + i * 16 + r_e;
+      const int m = m0 + wave * 16 * WM + i * 16 + r_e;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const int n = j * 16 + g_e * 4;
-        f32x4 v = acc[i][j];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += bb[j][e];
-        if (p.act == ACT_LRELU) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.act_slope;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] *= p.alpha;
-        if (p.R) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += rr[i][j][e];
-        }
-        if (p.R2) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = rr2[i][j][e] + v[e];
-        }
-        if (p.div > 0.f) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = v[e] / p.div;
-        }
-        if (m < m_hi) {
-          *reinterpret_cast<f32x4*>(p.C + (size_t)m * p.ldc + n) = v;
-          if (p.C2) {
-            f32x4 w2;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w2[e] = v[e] > 0.f ? v[e] : v[e] * p.c2_slope;
-            *reinterpret_cast<f32x4*>(p.C2 + (size_t)m * p.ldc2 + n) = w2;
-          }
-        }
+        const f32x4 v = slab_epi_apply(p, acc[i][j], bb[j], rr[i][j], rr2[i][j]);
+        if (m < m_hi) slab_epi_store(p, m, j * 16 + g_e * 4, v);
       }
     }
   }
@@ -251,28 +204,21 @@ void conv_c32_debug(int enable) { if (enable >= 0) dispatch_edit([enable](Dispat
 bool conv_c32_enabled() { return !disp().c32_off; }
 
 bool conv_c32_eligible(const GemmArgs& a) {
-  return !disp().c32_off && a.same_rows && a.stride == 1 && a.chunk == 0 && !a.glu && !a.ln_g && !a.x3 && a.Cin == C3_C && a.N == C3_C &&
-         a.lda == C3_C && (a.ldc & 3) == 0 && (!a.R || (a.ldr & 3) == 0) && (!a.R2 || (a.ldr2 & 3) == 0) && (!a.C2 || (a.ldc2 & 3) == 0) &&
-         a.taps >= 1 && a.dil >= 1 && (a.taps - 1) * a.dil <= C3_MAXHALO && a.pad >= 0 && a.pad <= (a.taps - 1) * a.dil &&
-         a.nseg <= C3_MAXSEG && a.M >= disp().c32_min_rows && slab_rows_ok(a.M) &&
-         (a.in_act == ACT_NONE || (a.in_act == ACT_LRELU && a.in_slope > 0.f && a.in_slope < 1.f)) &&
-         (a.act == ACT_NONE || a.act == ACT_LRELU);
+  return !disp().c32_off && slab_conv_ok(a, C3_C) && a.taps >= 1 && a.dil >= 1 && (a.taps - 1) * a.dil <= C3_MAXHALO && a.pad >= 0 &&
+         a.pad <= (a.taps - 1) * a.dil && a.nseg <= C3_MAXSEG && a.M >= disp().c32_min_rows && slab_rows_ok(a.M);
 }
 
 template <bool LRELU>
 static int launch_c32_t(const GemmArgs& a, hipStream_t stream) {
   const int slab_rows = C3_BM + (a.taps - 1) * a.dil;
-  const size_t lds = (size_t)((slab_rows * C3_LDA + 3) & ~3) * sizeof(float) + (C3_MAXSEG + 2) * sizeof(int);
+  const size_t lds = slab_lds_bytes(slab_rows, C3_LDA, C3_MAXSEG);
   SkWorkspace* st = nullptr;                       // (only for the device's CU count, cached per context)
   int rc = sk_workspace_acquire(stream, &st);
   if (rc != SS_OK) return rc;
-  const int nseg = a.nseg > 0 ? a.nseg : 1;
-  const long long max_blocks = (long long)cdiv(a.M, C3_BM) + nseg;      // upper bound (per-segment round-up)
-  static const int occ_env = getenv("SS_CONV_C32_WG_PER_CU") ? atoi(getenv("SS_CONV_C32_WG_PER_CU")) : 0;
-  const int occ = occ_env > 0 ? occ_env : (int)std::min<size_t>(3, (158 * 1024) / lds);   // resident workgroups per CU
-  const int grid = (int)std::min<long long>((long long)occ * st->cus, std::max<long long>(1, max_blocks));
+  const int occ = (int)std::min<size_t>(3, (158 * 1024) / lds);   // resident workgroups per CU
+  const int grid = slab_grid(occ, st->cus, a.M, C3_BM, a.nseg);
   ProfRec rec{}; bool prof = false;
-  rc = prof_begin(a, stream, 25, rec, prof);
+  rc = prof_begin(a, stream, PROF_CONV_C32, rec, prof);
   if (rc != SS_OK) return rc;
   hipLaunchKernelGGL((conv_c32_kernel<LRELU>), dim3(grid), dim3(256), lds, stream, a, slab_rows);
   SS_LAUNCH_CHECK();

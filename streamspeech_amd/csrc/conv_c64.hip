@@ -25,12 +25,10 @@
 //     read the same fragments, so L2 serves each once per CU;
 //   * no barrier, no LDS-DMA piece and no LDS write inside the contraction: a k-step is 4 LDS + 4 L2 fragments for 64 MFMAs;
 //   * wave tile 64 rows x 64 columns (16 accumulator tiles), swapped MFMA operands (D = W . A^T) -> float4 bias / residual / MRF
-//     accumulate / output along the channels.
+//     accumulate / output along the channels (segment walk and epilogue: slab_common.hpp).
 // Exact f32; per element the fmaf chain runs tap-major (conv_sk2: channel-block-major), i.e. results differ from the stream-K path
 // by summation order only.
-#include "gemm.hpp"
-
-#include <cstdlib>
+#include "slab_common.hpp"
 
 #ifndef C64_FENCE
 #define C64_FENCE 1      // see ffn.hip: without a fence per step hipcc sinks every weight load to just before its use
@@ -43,7 +41,6 @@
 
 namespace ss {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 namespace {
@@ -70,27 +67,10 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const GemmArgs p, cons
   const int r = lane & 15, g = lane >> 4;
   const int K = p.taps * C;
 
-  const int nseg = p.nseg > 0 ? p.nseg : 1;
-  if (t == 0) {
-    int acc = 0;
-    for (int s = 0; s < nseg; ++s) {
-      s_blk[s] = acc;
-      const int len = p.nseg > 0 ? p.segs[4 * s + 1] : p.M;
-      acc += (len + BM - 1) / BM;
-    }
-    s_blk[nseg] = acc;
-  }
+  SlabWalk<GemmArgs> w(p, s_blk, BM);
   __syncthreads();
-  const int nblocks = s_blk[nseg];
+  const int nblocks = w.nblocks();
   const float slope = p.in_slope;
-
-  int seg = 0, seg_lo = 0, seg_hi = 0, m0 = 0;
-  auto locate = [&](int blk) {                 // blocks ascend per workgroup
-    while (blk >= s_blk[seg + 1]) ++seg;
-    seg_lo = p.nseg > 0 ? p.segs[4 * seg] : 0;
-    seg_hi = seg_lo + (p.nseg > 0 ? p.segs[4 * seg + 1] : p.in_len);
-    m0 = seg_lo + (blk - s_blk[seg]) * BM;     // first output row (packed coordinates)
-  };
 
   // ---- weight fragments: L2 -> registers.  Fragment f of tap `tap`: channel block cc = f / 4, column tile j = f % 4 ----
   const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, C6_NUM_RECORDS, 0x00020000);
@@ -110,8 +90,8 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const GemmArgs p, cons
   for (int f = 0; f < C6_RING; ++f) ring[f] = wload(0, f);
 
   for (; blk < nblocks; blk += gridDim.x) {
-    locate(blk);
-    const int cm0 = m0;
+    w.locate(blk, p.in_len);
+    const int m0 = w.m0, seg_lo = w.seg_lo, seg_hi = w.seg_hi;
     const int m_hi = p.nseg > 0 ? seg_hi : min(seg_hi, p.M);
     // rows of the slab outside the utterance (= the conv's zero padding) exist only in its first and last blocks
     const bool edge = (m0 - p.pad < seg_lo) || (m0 - p.pad + slab_rows > seg_hi);
@@ -201,7 +181,7 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const GemmArgs p, cons
     }
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
-      const int m = cm0 + wave * 16 * WM + i * 16 + r_e;
+      const int m = m0 + wave * 16 * WM + i * 16 + r_e;
       const int mc = min(m, m_hi - 1);
       f32x4 rr[4], rr2[4];
       if (p.R) {
@@ -214,37 +194,8 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const GemmArgs p, cons
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int n = j * 16 + g_e * 4;
-        f32x4 v = acc[i][j];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += bb[j][e];
-        if (p.act == ACT_LRELU) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.act_slope;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] *= p.alpha;
-        if (p.R) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += rr[j][e];
-        }
-        if (p.R2) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = rr2[j][e] + v[e];
-        }
-        if (p.div > 0.f) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = v[e] / p.div;
-        }
-        if (m < m_hi) {
-          *reinterpret_cast<f32x4*>(p.C + (size_t)m * p.ldc + n) = v;
-          if (p.C2) {
-            f32x4 w2;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w2[e] = v[e] > 0.f ? v[e] : v[e] * p.c2_slope;
-            *reinterpret_cast<f32x4*>(p.C2 + (size_t)m * p.ldc2 + n) = w2;
-          }
-        }
+        const f32x4 v = slab_epi_apply(p, acc[i][j], bb[j], rr[j], rr2[j]);
+        if (m < m_hi) slab_epi_store(p, m, j * 16 + g_e * 4, v);
       }
     }
   }
@@ -257,17 +208,12 @@ void conv_c64_debug(int enable) { if (enable >= 0) dispatch_edit([enable](Dispat
 bool conv_c64_enabled() { return !disp().c64_off; }
 
 bool conv_c64_eligible(const GemmArgs& a) {
-  return !disp().c64_off && a.same_rows && a.stride == 1 && a.chunk == 0 && !a.glu && !a.ln_g && !a.x3 && a.Cin == C6_C && a.N == C6_C &&
-         a.lda == C6_C && (a.ldc & 3) == 0 && (!a.R || (a.ldr & 3) == 0) && (!a.R2 || (a.ldr2 & 3) == 0) && (!a.C2 || (a.ldc2 & 3) == 0) &&
-         a.taps >= 1 && a.dil >= 1 && (a.taps - 1) * a.dil <= C6_MAXHALO && a.pad >= 0 && a.pad <= (a.taps - 1) * a.dil &&
-         a.nseg <= C6_MAXSEG && a.M >= disp().c64_min_rows && slab_rows_ok(a.M) &&
-         (size_t)a.taps * C6_C * C6_C * 4 < 0x7ff00000ull && (a.in_act == ACT_NONE || (a.in_act == ACT_LRELU && a.in_slope > 0.f && a.in_slope < 1.f)) &&
-         (a.act == ACT_NONE || a.act == ACT_LRELU);
+  return !disp().c64_off && slab_conv_ok(a, C6_C) && a.taps >= 1 && a.dil >= 1 && (a.taps - 1) * a.dil <= C6_MAXHALO && a.pad >= 0 &&
+         a.pad <= (a.taps - 1) * a.dil && a.nseg <= C6_MAXSEG && a.M >= disp().c64_min_rows && slab_rows_ok(a.M) &&
+         (size_t)a.taps * C6_C * C6_C * 4 < 0x7ff00000ull;
 }
 
-static size_t c64_lds(int bm, const GemmArgs& a) {
-  return (size_t)(((bm + (a.taps - 1) * a.dil) * C6_LDA + 3) & ~3) * sizeof(float) + (C6_MAXSEG + 2) * sizeof(int);
-}
+static size_t c64_lds(int bm, const GemmArgs& a) { return slab_lds_bytes(bm + (a.taps - 1) * a.dil, C6_LDA, C6_MAXSEG); }
 template <bool LRELU, int WM>
 static int launch_c64_t(const GemmArgs& a, hipStream_t stream) {
   constexpr int BM = 64 * WM;
@@ -277,12 +223,10 @@ static int launch_c64_t(const GemmArgs& a, hipStream_t stream) {
   SkWorkspace* st = nullptr;                       // (only for the device's CU count, cached per context)
   int rc = sk_workspace_acquire(stream, &st);
   if (rc != SS_OK) return rc;
-  const int nseg = a.nseg > 0 ? a.nseg : 1;
-  const long long max_blocks = (long long)cdiv(a.M, BM) + nseg;      // upper bound (per-segment round-up)
   const int occ = lds * 2 <= 158 * 1024 ? 2 : 1;   // resident workgroups per CU (LDS-limited; 164 registers per wave)
-  const int grid = (int)std::min<long long>((long long)occ * st->cus, std::max<long long>(1, max_blocks));
+  const int grid = slab_grid(occ, st->cus, a.M, BM, a.nseg);
   ProfRec rec{}; bool prof = false;
-  rc = prof_begin(a, stream, 24, rec, prof);
+  rc = prof_begin(a, stream, PROF_CONV_C64, rec, prof);
   if (rc != SS_OK) return rc;
   hipLaunchKernelGGL((conv_c64_kernel<LRELU, WM>), dim3(grid), dim3(256), lds, stream, a, slab_rows);
   SS_LAUNCH_CHECK();
@@ -292,8 +236,7 @@ static int launch_c64_t(const GemmArgs& a, hipStream_t stream) {
 int launch_conv_c64(const GemmArgs& a, hipStream_t stream) {
   if (!conv_c64_eligible(a)) return SS_ERR_ARG;
   // 256-row blocks when two workgroups' slabs fit a CU's LDS, else 192-row blocks (k = 11 at dilation 5: 83 KB -> 66 KB)
-  static const int force_wm = getenv("SS_CONV_C64_WM") ? atoi(getenv("SS_CONV_C64_WM")) : 0;
-  const bool wm4 = force_wm ? force_wm == 4 : 2 * c64_lds(256, a) <= 158 * 1024;
+  const bool wm4 = 2 * c64_lds(256, a) <= 158 * 1024;
   if (a.in_act == ACT_LRELU) return wm4 ? launch_c64_t<true, 4>(a, stream) : launch_c64_t<true, 3>(a, stream);
   return wm4 ? launch_c64_t<false, 4>(a, stream) : launch_c64_t<false, 3>(a, stream);
 }

@@ -20,15 +20,13 @@
 //     conv_sk2 (its A tiles arrive by LDS-DMA);
 //   * 4 weight fragments + 4 LDS reads + 8 VALU ops per 32 MFMAs, ring of 8 fragments = two sub-steps (2048 MFMA cycles) ahead.
 // Blocks cover 256 / 252 / 240 output rows at dilation 1 / 3 / 5 (whole pairs; two slabs must fit a CU's LDS); a conv whose slab
-// does not fit two per CU (k = 11 at dilation 5) stays on conv_c64.hip.
-#include "gemm.hpp"
+// does not fit two per CU (k = 11 at dilation 5) stays on conv_c64.hip.  Segment walk and epilogue: slab_common.hpp.
+#include "slab_common.hpp"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace ss {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 // Diagnostic build only (-DCW_TIMING=1, tools/cw_timing.py): thread 0 of every workgroup accumulates s_memtime cycles per phase.
@@ -113,28 +111,11 @@ __global__ __launch_bounds__(CH >= 128 ? 512 : 256, CH >= 128 ? 1 : CH == 64 ? 2
   const int r = lane & 15, g = lane >> 4;
   const int Kw = groups * 4 * C;                                           // row length of the transformed weight matrix
 
-  const int nseg = p.nseg > 0 ? p.nseg : 1;
-  if (t == 0) {
-    int acc = 0;
-    for (int s = 0; s < nseg; ++s) {
-      s_blk[s] = acc;
-      const int len = p.nseg > 0 ? p.segs[4 * s + 1] : p.M;
-      acc += (len + BME - 1) / BME;
-    }
-    s_blk[nseg] = acc;
-  }
+  SlabWalk<GemmArgs> w(p, s_blk, BME);
   __syncthreads();
-  const int nblocks = s_blk[nseg];
+  const int nblocks = w.nblocks();
   // (no input activation: slope 1 -- max(v, v * 1) = v exactly; one kernel for both, see the TAIL note below)
   const float slope = p.in_act == ACT_LRELU ? p.in_slope : 1.0f;
-
-  int seg = 0, seg_lo = 0, seg_hi = 0, m0 = 0;
-  auto locate = [&](int blk) {                 // blocks ascend per workgroup
-    while (blk >= s_blk[seg + 1]) ++seg;
-    seg_lo = p.nseg > 0 ? p.segs[4 * seg] : 0;
-    seg_hi = seg_lo + (p.nseg > 0 ? p.segs[4 * seg + 1] : p.in_len);
-    m0 = seg_lo + (blk - s_blk[seg]) * BME;    // first output row (packed coordinates)
-  };
 
   // ---- weight fragments: L2 -> registers.  Fragment (idx = group * 4 + component, channel block cc, column tile ct) ----
   const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, CW_NUM_RECORDS, 0x00020000);
@@ -171,8 +152,8 @@ __global__ __launch_bounds__(CH >= 128 ? 512 : 256, CH >= 128 ? 1 : CH == 64 ? 2
 #if CW_TIMING
     ++cw_blocks;
 #endif
-    locate(blk);
-    const int cm0 = m0;
+    w.locate(blk, p.in_len);
+    const int m0 = w.m0, seg_lo = w.seg_lo, seg_hi = w.seg_hi;
     const int m_hi = p.nseg > 0 ? seg_hi : min(seg_hi, p.M);
     const bool edge = (m0 - p.pad < seg_lo) || (m0 - p.pad + slab_rows > seg_hi);
     f32x4 acc[4][2][CT];                                   // [component][pair tile][column tile]
@@ -313,7 +294,7 @@ __global__ __launch_bounds__(CH >= 128 ? 512 : 256, CH >= 128 ? 1 : CH == 64 ? 2
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {                        // the pair's first / second row
-        const int m = cm0 + toff[i] + h * DIL;
+        const int m = m0 + toff[i] + h * DIL;
         const int mc = min(m, m_hi - 1);
         f32x4 rr[CT], rr2[CT];
         if (p.R) {
@@ -326,37 +307,10 @@ __global__ __launch_bounds__(CH >= 128 ? 512 : 256, CH >= 128 ? 1 : CH == 64 ? 2
         }
 #pragma unroll
         for (int j = 0; j < CT; ++j) {
-          const int n = col0 + j * 16 + g_e * 4;
-          f32x4 v = h == 0 ? (acc[0][i][j] + acc[1][i][j]) + acc[2][i][j] : (acc[1][i][j] - acc[2][i][j]) - acc[3][i][j];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += bb[j][e];
-          if (p.act == ACT_LRELU) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.act_slope;
-          }
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] *= p.alpha;
-          if (p.R) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += rr[j][e];
-          }
-          if (p.R2) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = rr2[j][e] + v[e];
-          }
-          if (p.div > 0.f) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] / p.div;
-          }
-          if (pv[i] && m < m_hi) {
-            *reinterpret_cast<f32x4*>(p.C + (size_t)m * p.ldc + n) = v;
-            if (CH >= 128 && p.C2) {                         // pre-activated twin for a consumer that cannot activate while staging (conv_sk2)
-              f32x4 w2;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) w2[e] = v[e] > 0.f ? v[e] : v[e] * p.c2_slope;
-              *reinterpret_cast<f32x4*>(p.C2 + (size_t)m * p.ldc2 + n) = w2;
-            }
-          }
+          const f32x4 y = h == 0 ? (acc[0][i][j] + acc[1][i][j]) + acc[2][i][j] : (acc[1][i][j] - acc[2][i][j]) - acc[3][i][j];
+          const f32x4 v = slab_epi_apply(p, y, bb[j], rr[j], rr2[j]);
+          // the pre-activated twin only for a consumer that cannot activate while staging (conv_sk2 after the 128 / 256-channel stages)
+          if (pv[i] && m < m_hi) slab_epi_store<CH >= 128>(p, m, col0 + j * 16 + g_e * 4, v);
         }
       }
     }
@@ -393,10 +347,7 @@ void conv_c256w_debug(int enable) { if (enable >= 0) dispatch_edit([enable](Disp
 bool conv_c256w_enabled() { return disp().c256w_on != 0; }
 
 static int cw_groups(const GemmArgs& a) { return (a.taps + 2) / 3; }
-static size_t cw_lds(const GemmArgs& a, int ch) {
-  const int slab_rows = cw_bme(a.dil) + 3 * cw_groups(a) * a.dil;
-  return (size_t)((slab_rows * (ch + 4) + 3) & ~3) * sizeof(float) + (CW_MAXSEG + 2) * sizeof(int);
-}
+static size_t cw_lds(const GemmArgs& a, int ch) { return slab_lds_bytes(cw_bme(a.dil) + 3 * cw_groups(a) * a.dil, ch + 4, CW_MAXSEG); }
 
 // the launches conv_c64.hip takes (checked by the caller: conv_c64_eligible) that also have transformed weights, a "same" geometry the
 // pairing covers and a slab two of which fit a CU
@@ -404,34 +355,22 @@ bool conv_c64w_eligible(const GemmArgs& a) {
   if (!disp().c64w_on || !a.Wwino || a.taps < disp().c64w_min_k || a.taps < 3 || (a.dil != 1 && a.dil != 3 && a.dil != 5) || a.C2) return false;
   if (a.pad != a.dil * (a.taps - 1) / 2) return false;
   // k = 7 at dilation 5: 1.17x fewer MFMAs against a 45-row halo on 240-row blocks -- measured slower than the direct form (283 vs 272 us)
-  static const int allow_k7d5 = getenv("SS_CONV_C64_WINOGRAD_K7D5") ? atoi(getenv("SS_CONV_C64_WINOGRAD_K7D5")) : 0;
-  if (a.taps <= 8 && a.taps > 3 && a.dil == 5 && !allow_k7d5) return false;
+  if (a.taps <= 8 && a.taps > 3 && a.dil == 5) return false;
   const int slab_rows = cw_bme(a.dil) + 3 * cw_groups(a) * a.dil;
   return slab_rows <= CW_MAXROWS && 2 * cw_lds(a, 64) <= 158 * 1024 && (size_t)cw_groups(a) * 4 * 64 * 64 * 4 < 0x7ff00000ull;
 }
 
 // The 128-channel stage: every "same" conv with C = N = 128, k >= 3 at dilation 1 / 3 / 5 of a packed batch big enough to give each CU a
 // block (one workgroup per CU: the slab is 137-158 KB).  There is no direct slab kernel at this width (measured slower than conv_sk2<128>:
-// profiles/r04_c128_bench.txt), so the stage takes this path only if ALL its convs are eligible (model.hip asks with a probe).
-bool conv_c128w_eligible(const GemmArgs& a) {
-  if (!disp().c128w_on || !a.Wwino || !a.same_rows || a.stride != 1 || a.chunk || a.glu || a.ln_g || a.x3 || a.Cin != 128 || a.N != 128) return false;
-  if (a.lda != 128 || (a.ldc & 3) || (a.R && (a.ldr & 3)) || (a.R2 && (a.ldr2 & 3)) || (a.C2 && (a.ldc2 & 3))) return false;
+// profiles/r04_c128_bench.txt), so the stage takes this path only if ALL its convs are eligible (model.hip asks with a probe).  The
+// 256-channel stage in the same form (two slab phases of 128 input channels, two column halves) likewise.
+bool conv_wide_winograd_eligible(const GemmArgs& a, int ch) {
+  if (ch != 128 && ch != 256) return false;
+  const Dispatch& d = disp();
+  if (!(ch == 128 ? d.c128w_on : d.c256w_on) || !a.Wwino || !slab_conv_ok(a, ch)) return false;
   if (a.taps < 3 || (a.dil != 1 && a.dil != 3 && a.dil != 5) || a.pad != a.dil * (a.taps - 1) / 2) return false;
-  if (a.nseg > CW_MAXSEG || a.M < disp().c128w_min_rows || !slab_rows_ok(a.M)) return false;
-  if (!(a.in_act == ACT_NONE || (a.in_act == ACT_LRELU && a.in_slope > 0.f && a.in_slope < 1.f)) || !(a.act == ACT_NONE || a.act == ACT_LRELU)) return false;
-  const int slab_rows = cw_bme(a.dil) + 3 * cw_groups(a) * a.dil;
-  return slab_rows <= CW_MAXROWS && cw_lds(a, 128) <= 160 * 1024;
-}
-
-// The 256-channel stage in the same form (two slab phases of 128 input channels, two column halves): all-or-nothing per stage like the
-// 128-channel one (model.hip probes every conv).
-bool conv_c256w_eligible(const GemmArgs& a) {
-  if (!disp().c256w_on || !a.Wwino || !a.same_rows || a.stride != 1 || a.chunk || a.glu || a.ln_g || a.x3 || a.Cin != 256 || a.N != 256) return false;
-  if (a.lda != 256 || (a.ldc & 3) || (a.R && (a.ldr & 3)) || (a.R2 && (a.ldr2 & 3)) || (a.C2 && (a.ldc2 & 3))) return false;
-  if (a.taps < 3 || (a.dil != 1 && a.dil != 3 && a.dil != 5) || a.pad != a.dil * (a.taps - 1) / 2) return false;
-  if (a.nseg > CW_MAXSEG || a.M < disp().c256w_min_rows || !slab_rows_ok(a.M)) return false;
-  if ((size_t)256 * cw_groups(a) * 4 * 256 * 4 >= 0x7ff00000ull) return false;
-  if (!(a.in_act == ACT_NONE || (a.in_act == ACT_LRELU && a.in_slope > 0.f && a.in_slope < 1.f)) || !(a.act == ACT_NONE || a.act == ACT_LRELU)) return false;
+  if (a.nseg > CW_MAXSEG || a.M < (ch == 128 ? d.c128w_min_rows : d.c256w_min_rows) || !slab_rows_ok(a.M)) return false;
+  if (ch == 256 && (size_t)256 * cw_groups(a) * 4 * 256 * 4 >= 0x7ff00000ull) return false;
   const int slab_rows = cw_bme(a.dil) + 3 * cw_groups(a) * a.dil;
   return slab_rows <= CW_MAXROWS && cw_lds(a, 128) <= 160 * 1024;
 }
@@ -453,15 +392,13 @@ static int launch_cw_t(GemmArgs a, hipStream_t stream) {
   SkWorkspace* st = nullptr;                       // (only for the device's CU count, cached per context)
   int rc = sk_workspace_acquire(stream, &st);
   if (rc != SS_OK) return rc;
-  const int nseg = a.nseg > 0 ? a.nseg : 1;
-  const long long max_blocks = (long long)cdiv(a.M, BME) + nseg;      // upper bound (per-segment round-up)
-  int grid = (int)std::min<long long>((CH >= 128 ? 1ll : CH == 64 ? 2ll : 3ll) * st->cus, std::max<long long>(1, max_blocks));
+  int grid = slab_grid(CH >= 128 ? 1 : CH == 64 ? 2 : 3, st->cus, a.M, BME, a.nseg);
   if (CH == 256) {                                 // (block, column half) items: workgroups come in groups of 16 = 8 blocks x 2 halves
-    const long long want = std::min<long long>(st->cus, 2 * ((max_blocks + 7) / 8 * 8));
+    const long long want = std::min<long long>(st->cus, 2 * ((slab_max_blocks(a.M, BME, a.nseg) + 7) / 8 * 8));
     grid = (int)std::max<long long>(16, want / 16 * 16);
   }
   ProfRec rec{}; bool prof = false;
-  rc = prof_begin(a, stream, CH == 64 ? 27 : CH == 128 ? 28 : CH == 256 ? 30 : 29, rec, prof);   // census: the conv's algorithmic (direct-form) FLOPs; the kernel issues 4 G / (2 k) of them
+  rc = prof_begin(a, stream, CH == 64 ? PROF_CONV_C64W : CH == 128 ? PROF_CONV_C128W : CH == 256 ? PROF_CONV_C256W : PROF_CONV_C32W, rec, prof);   // census: the conv's algorithmic (direct-form) FLOPs; the kernel issues 4 G / (2 k) of them
   if (rc != SS_OK) return rc;
   a.W = a.Wwino;
   hipLaunchKernelGGL((conv_c64w_kernel<DIL, CH, TAIL>), dim3(grid), dim3(CH >= 128 ? 512 : 256), lds, stream, a, groups, slab_rows);
@@ -505,11 +442,11 @@ int launch_conv_c32w(const GemmArgs& a, hipStream_t stream) {
   return launch_cw<32>(a, stream);
 }
 int launch_conv_c128w(const GemmArgs& a, hipStream_t stream) {
-  if (!conv_c128w_eligible(a)) return SS_ERR_ARG;
+  if (!conv_wide_winograd_eligible(a, 128)) return SS_ERR_ARG;
   return launch_cw<128>(a, stream);
 }
 int launch_conv_c256w(const GemmArgs& a, hipStream_t stream) {
-  if (!conv_c256w_eligible(a)) return SS_ERR_ARG;
+  if (!conv_wide_winograd_eligible(a, 256)) return SS_ERR_ARG;
   return launch_cw<256>(a, stream);
 }
 

@@ -447,7 +447,7 @@ static int launch_sk(const GemmArgs& a, hipStream_t stream, int g_force) {
   q.epoch = epoch; q.G = (int)G; q.NG = NG;
   for (int x = 0; x < 8; ++x) q.base[x] = st->base1[x];
   ProfRec rec{}; bool prof = false;
-  rc = prof_begin(a, stream, 15, rec, prof);
+  rc = prof_begin(a, stream, PROF_CONV_SK, rec, prof);
   if (rc != SS_OK) return rc;
   hipLaunchKernelGGL((conv_sk_kernel<BN, LRELU>), dim3((unsigned)G), dim3(256), kLds, stream, a, q);
   SS_LAUNCH_CHECK();

@@ -658,7 +658,7 @@ static int launch_sk2(const GemmArgs& a, hipStream_t stream, int g_force) {
   q.base = st->base2;
   q.epoch = epoch;
   ProfRec rec{}; bool prof = false;
-  rc = prof_begin(a, stream, X3 ? 19 : 18, rec, prof);
+  rc = prof_begin(a, stream, X3 ? PROF_CONV_SK2_BF16X3 : PROF_CONV_SK2, rec, prof);
   if (rc != SS_OK) return rc;
   hipLaunchKernelGGL((conv_sk2_kernel<BN, LRELU, X3>), dim3((unsigned)G), dim3(256), kLds, stream, a, q);
   SS_LAUNCH_CHECK();

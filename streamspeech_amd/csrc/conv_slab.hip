@@ -15,12 +15,10 @@
 //   * all taps are contracted out of LDS with v_mfma_f32_16x16x4_f32 (operands swapped, D = W.A^T,
 //     so the epilogue is float4 along the channels);
 //   * HBM traffic = input once (+ halo) + output once + residual operands: the algorithmic minimum.
-// Blocks never straddle utterances (per-segment block table), so validity is uniform per block.
-#include "gemm.hpp"
+// Blocks never straddle utterances (per-segment block table, slab_common.hpp), so validity is uniform per block.
+#include "slab_common.hpp"
 
 namespace ss {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int SL_BM = 128;
 constexpr int SL_MAXSEG = 256;
@@ -47,19 +45,9 @@ __global__ __launch_bounds__(256, 2) void conv_slab_kernel(const GemmArgs p, con
     const int n = idx / (K / 4), k4 = idx - n * (K / 4);
     *reinterpret_cast<f32x4*>(sW + n * LDW + k4 * 4) = *reinterpret_cast<const f32x4*>(p.W + (size_t)n * K + k4 * 4);
   }
-  // block table: s_blk[s] = first block of segment s, s_blk[nseg] = total
-  const int nseg = p.nseg > 0 ? p.nseg : 1;
-  if (t == 0) {
-    int acc = 0;
-    for (int s = 0; s < nseg; ++s) {
-      s_blk[s] = acc;
-      const int len = p.nseg > 0 ? p.segs[4 * s + 1] : p.M;
-      acc += (len + BM - 1) / BM;
-    }
-    s_blk[nseg] = acc;
-  }
+  SlabWalk<GemmArgs> w(p, s_blk, BM);
   __syncthreads();
-  const int nblocks = s_blk[nseg];
+  const int nblocks = w.nblocks();
 
   constexpr int LDA = C + 4;                   // padded slab row (floats): 16 consecutive rows x 16 B hit 16 distinct slots
   const int slab_rows = BM + (p.taps - 1) * p.dil;
@@ -69,30 +57,23 @@ __global__ __launch_bounds__(256, 2) void conv_slab_kernel(const GemmArgs p, con
   // the global-load latency hides under the MFMAs (a second LDS slab would halve the occupancy).
   constexpr int NP = Q;                        // float4 per thread: (BM + 128 halo rows) * Q / 256
   f32x4 pre[NP];
-  int seg = 0, seg_lo = 0, seg_hi = 0, m0 = 0;
-  auto locate = [&](int blk) {                 // blocks ascend per workgroup
-    while (blk >= s_blk[seg + 1]) ++seg;
-    seg_lo = p.nseg > 0 ? p.segs[4 * seg] : 0;
-    seg_hi = seg_lo + (p.nseg > 0 ? p.segs[4 * seg + 1] : p.in_len);
-    m0 = seg_lo + (blk - s_blk[seg]) * BM;     // first output row (packed coordinates)
-  };
   auto prefetch = [&]() {
 #pragma unroll
     for (int u = 0; u < NP; ++u) {
       const int idx = t + u * 256;             // Q consecutive threads read one 4C-byte row
       const int rho = idx / Q, c4 = idx - rho * Q;
-      const int gin = m0 - p.pad + rho;
+      const int gin = w.m0 - p.pad + rho;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (rho < slab_rows && gin >= seg_lo && gin < seg_hi)
+      if (rho < slab_rows && gin >= w.seg_lo && gin < w.seg_hi)
         v = *reinterpret_cast<const f32x4*>(p.A + (size_t)gin * p.lda + c4 * 4);
       pre[u] = v;
     }
   };
   int blk = blockIdx.x;
-  if (blk < nblocks) { locate(blk); prefetch(); }
+  if (blk < nblocks) { w.locate(blk, p.in_len); prefetch(); }
   for (; blk < nblocks; blk += gridDim.x) {
-    const int cm0 = m0;
-    const int m_hi = p.nseg > 0 ? seg_hi : min(seg_hi, p.M);
+    const int cm0 = w.m0;
+    const int m_hi = p.nseg > 0 ? w.seg_hi : min(w.seg_hi, p.M);
     __syncthreads();                                       // previous block's slab reads are done
 #pragma unroll
     for (int u = 0; u < NP; ++u) {
@@ -108,7 +89,7 @@ __global__ __launch_bounds__(256, 2) void conv_slab_kernel(const GemmArgs p, con
       }
     }
     __syncthreads();
-    if (blk + (int)gridDim.x < nblocks) { locate(blk + gridDim.x); prefetch(); }
+    if (blk + (int)gridDim.x < nblocks) { w.locate(blk + gridDim.x, p.in_len); prefetch(); }
 
     f32x4 acc[TM][TN];
 #pragma unroll
@@ -169,22 +150,8 @@ __global__ __launch_bounds__(256, 2) void conv_slab_kernel(const GemmArgs p, con
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] += rr[e];
         }
-        if (p.R2) {
-          const f32x4 rr = *reinterpret_cast<const f32x4*>(p.R2 + (size_t)m * p.ldr2 + n);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = rr[e] + v[e];
-        }
-        if (p.div > 0.f) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = v[e] / p.div;
-        }
-        *reinterpret_cast<f32x4*>(p.C + (size_t)m * p.ldc + n) = v;
-        if (p.C2) {
-          f32x4 w2;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) w2[e] = v[e] > 0.f ? v[e] : v[e] * p.c2_slope;
-          *reinterpret_cast<f32x4*>(p.C2 + (size_t)m * p.ldc2 + n) = w2;
-        }
+        v = slab_epi_tail(p, v, [&] { return *reinterpret_cast<const f32x4*>(p.R2 + (size_t)m * p.ldr2 + n); });
+        slab_epi_store(p, m, n, v);
       }
     }
   }
@@ -192,47 +159,26 @@ __global__ __launch_bounds__(256, 2) void conv_slab_kernel(const GemmArgs p, con
 }
 
 bool conv_slab_eligible(const GemmArgs& a) {
-  return a.same_rows && a.stride == 1 && a.chunk == 0 && !a.glu && !a.ln_g && (a.Cin == 32 || a.Cin == 16) &&
-         (a.N == 32 || a.N == 16) && a.lda == a.Cin && (a.ldc & 3) == 0 && (!a.R || (a.ldr & 3) == 0) &&
-         (!a.R2 || (a.ldr2 & 3) == 0) && (!a.C2 || (a.ldc2 & 3) == 0) && a.taps >= 1 && a.taps * a.Cin <= 512 &&
+  return slab_layout_ok(a) && (a.Cin == 32 || a.Cin == 16) && (a.N == 32 || a.N == 16) && a.taps >= 1 && a.taps * a.Cin <= 512 &&
          (a.taps - 1) * a.dil <= 128 &&   // slab <= 256 rows (register prefetch budget)
-         a.nseg <= SL_MAXSEG && a.M > 0 &&
-         slab_rows_ok(a.M) &&
-         (a.in_act == ACT_NONE || a.in_act == ACT_LRELU);
-}
-
-static int slab_cus(int& cus) {           // CU count of the CURRENT device, read once per device (thread-safe)
-  static std::mutex mu;
-  static int n[128] = {0};
-  int dev = 0;
-  SS_HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 128) return SS_ERR_ARG;
-  std::lock_guard<std::mutex> lk(mu);
-  if (n[dev] == 0) {
-    int v = 0;
-    SS_HIP_CHECK(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    n[dev] = v > 0 ? v : 256;
-  }
-  cus = n[dev];
-  return SS_OK;
+         a.nseg <= SL_MAXSEG && a.M > 0 && slab_rows_ok(a.M) && (a.in_act == ACT_NONE || a.in_act == ACT_LRELU);
 }
 
 template <int C, int N, bool LRELU>
-static int launch_slab_t(const GemmArgs& a, hipStream_t stream, int cls) {
+static int launch_slab_t(const GemmArgs& a, hipStream_t stream, ProfCls cls) {
   const int K = a.taps * C;
   const int slab_rows = SL_BM + (a.taps - 1) * a.dil;
   const size_t lds = ((size_t)((N * (K + 4) + 255) & ~255) + (size_t)((slab_rows * (C + 4) + 255) & ~255)) * sizeof(float) +
                      (SL_MAXSEG + 2) * sizeof(int);
   if (lds > 80 * 1024) return SS_ERR_ARG;
   SS_MAX_LDS_ONCE((&conv_slab_kernel<C, N, LRELU>), 80 * 1024);
-  int g_slab_cus = 0;
-  { int rc_cus = slab_cus(g_slab_cus); if (rc_cus != SS_OK) return rc_cus; }
-  const int nseg = a.nseg > 0 ? a.nseg : 1;
-  const long long max_blocks = (long long)cdiv(a.M, SL_BM) + nseg;      // upper bound (per-segment round-up)
+  int cus = 0;
+  int rc = device_cus(cus);
+  if (rc != SS_OK) return rc;
   const int occ = (int)std::max<size_t>(2, std::min<size_t>(6, (150 * 1024) / lds));   // resident workgroups per CU (LDS-limited)
-  const int grid = (int)std::min<long long>((long long)occ * g_slab_cus, std::max<long long>(1, max_blocks));
+  const int grid = slab_grid(occ, cus, a.M, SL_BM, a.nseg);
   ProfRec rec{}; bool prof = false;
-  int rc = prof_begin(a, stream, cls, rec, prof);
+  rc = prof_begin(a, stream, cls, rec, prof);
   if (rc != SS_OK) return rc;
   hipLaunchKernelGGL((conv_slab_kernel<C, N, LRELU>), dim3(grid), dim3(256), lds, stream, a, slab_rows);
   SS_LAUNCH_CHECK();
@@ -244,7 +190,7 @@ int launch_conv_slab(const GemmArgs& a, hipStream_t stream) {
   const bool lr = a.in_act == ACT_LRELU;
 #define SS_SLAB(C_, N_, CLS_) \
   if (a.Cin == C_ && a.N == N_) return lr ? launch_slab_t<C_, N_, true>(a, stream, CLS_) : launch_slab_t<C_, N_, false>(a, stream, CLS_);
-  SS_SLAB(32, 32, 16) SS_SLAB(16, 16, 17) SS_SLAB(32, 16, 16) SS_SLAB(16, 32, 17)
+  SS_SLAB(32, 32, PROF_CONV_SLAB32) SS_SLAB(16, 16, PROF_CONV_SLAB16) SS_SLAB(32, 16, PROF_CONV_SLAB32) SS_SLAB(16, 32, PROF_CONV_SLAB16)
 #undef SS_SLAB
   return SS_ERR_ARG;
 }
@@ -329,44 +275,29 @@ __global__ __launch_bounds__(256, 2) void conv_pair_kernel(const PairArgs p, con
     *reinterpret_cast<f32x4*>(sW1 + n * LDW + k4 * 4) = *reinterpret_cast<const f32x4*>(p.W1 + (size_t)n * K + k4 * 4);
     *reinterpret_cast<f32x4*>(sW2 + n * LDW + k4 * 4) = *reinterpret_cast<const f32x4*>(p.W2 + (size_t)n * K + k4 * 4);
   }
-  const int nseg = p.nseg > 0 ? p.nseg : 1;
-  if (t == 0) {
-    int acc = 0;
-    for (int s = 0; s < nseg; ++s) {
-      s_blk[s] = acc;
-      acc += ((p.nseg > 0 ? p.segs[4 * s + 1] : p.M) + BM - 1) / BM;
-    }
-    s_blk[nseg] = acc;
-  }
+  SlabWalk<PairArgs> w(p, s_blk, BM);
   __syncthreads();
-  const int nblocks = s_blk[nseg];
+  const int nblocks = w.nblocks();
   const int h1 = p.dil * (p.taps - 1) / 2, h2 = (p.taps - 1) / 2;
   const float slope = p.slope;
 
   f32x4 pre[NP];
-  int seg = 0, seg_lo = 0, seg_hi = 0, m0 = 0;
-  auto locate = [&](int blk) {
-    while (blk >= s_blk[seg + 1]) ++seg;
-    seg_lo = p.nseg > 0 ? p.segs[4 * seg] : 0;
-    seg_hi = seg_lo + (p.nseg > 0 ? p.segs[4 * seg + 1] : p.in_len);
-    m0 = seg_lo + (blk - s_blk[seg]) * BM;
-  };
   auto prefetch = [&]() {
 #pragma unroll
     for (int u = 0; u < NP; ++u) {
       const int idx = t + u * 256;
       const int rho = idx / Q, c4 = idx - rho * Q;
-      const int gin = m0 - h2 - h1 + rho;
+      const int gin = w.m0 - h2 - h1 + rho;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (rho < slab_rows && gin >= seg_lo && gin < seg_hi)
+      if (rho < slab_rows && gin >= w.seg_lo && gin < w.seg_hi)
         v = *reinterpret_cast<const f32x4*>(p.A + (size_t)gin * p.lda + c4 * 4);
       pre[u] = v;
     }
   };
   int blk = blockIdx.x;
-  if (blk < nblocks) { locate(blk); prefetch(); }
+  if (blk < nblocks) { w.locate(blk, p.in_len); prefetch(); }
   for (; blk < nblocks; blk += gridDim.x) {
-    const int cm0 = m0, clo = seg_lo, chi = seg_hi;
+    const int cm0 = w.m0, clo = w.seg_lo, chi = w.seg_hi;
     __syncthreads();                                       // previous block's conv2 is done with both slabs
 #pragma unroll
     for (int u = 0; u < NP; ++u) {
@@ -380,7 +311,7 @@ __global__ __launch_bounds__(256, 2) void conv_pair_kernel(const PairArgs p, con
       }
     }
     __syncthreads();
-    if (blk + (int)gridDim.x < nblocks) { locate(blk + gridDim.x); prefetch(); }
+    if (blk + (int)gridDim.x < nblocks) { w.locate(blk + gridDim.x, p.in_len); prefetch(); }
 
     // ---- conv1 (dilated) -> mid slab ----
     auto conv1_out = [&](int mt, const f32x4 (&a)[TN]) {   // bias, leaky-ReLU, zero outside the utterance -> mid slab
@@ -428,22 +359,8 @@ __global__ __launch_bounds__(256, 2) void conv_pair_kernel(const PairArgs p, con
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = (acc2[u][j][e] + b[e]) + xr[e];
-        if (p.R2) {
-          const f32x4 rr = *reinterpret_cast<const f32x4*>(p.R2 + (size_t)m * p.ldr2 + n);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = rr[e] + v[e];
-        }
-        if (p.div > 0.f) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = v[e] / p.div;
-        }
-        *reinterpret_cast<f32x4*>(p.C + (size_t)m * p.ldc + n) = v;
-        if (p.C2) {
-          f32x4 w2;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) w2[e] = v[e] > 0.f ? v[e] : v[e] * p.c2_slope;
-          *reinterpret_cast<f32x4*>(p.C2 + (size_t)m * p.ldc2 + n) = w2;
-        }
+        v = slab_epi_tail(p, v, [&] { return *reinterpret_cast<const f32x4*>(p.R2 + (size_t)m * p.ldr2 + n); });
+        slab_epi_store(p, m, n, v);
       }
     }
   }
@@ -468,17 +385,16 @@ template <int C>
 static int launch_pair_t(const PairArgs& a, hipStream_t stream) {
   const size_t lds = conv_pair_lds(C, a.taps, a.dil);
   SS_MAX_LDS_ONCE((&conv_pair_kernel<C>), 72 * 1024);
-  int g_slab_cus = 0;
-  { int rc_cus = slab_cus(g_slab_cus); if (rc_cus != SS_OK) return rc_cus; }
-  const int nseg = a.nseg > 0 ? a.nseg : 1;
-  const long long max_blocks = (long long)cdiv(a.M, SL_BM) + nseg;
+  int cus = 0;
+  int rc = device_cus(cus);
+  if (rc != SS_OK) return rc;
   const int occ = (int)std::max<size_t>(2, std::min<size_t>(4, (150 * 1024) / lds));
-  const int grid = (int)std::min<long long>((long long)occ * g_slab_cus, std::max<long long>(1, max_blocks));
-  // profiler class of the slab kernels (C = 32 -> 16, C = 16 -> 17); FLOPs of both convs
+  const int grid = slab_grid(occ, cus, a.M, SL_BM, a.nseg);
+  // profiler class of the slab kernels; FLOPs of both convs
   GemmArgs ga;
   ga.M = a.M; ga.N = C; ga.Cin = C; ga.taps = a.taps; ga.in_len = a.in_len; ga.algo_flops = 4.0 * (double)a.M * C * C * a.taps;
   ProfRec rec{}; bool prof = false;
-  int rc = prof_begin(ga, stream, C == 32 ? 16 : 17, rec, prof);
+  rc = prof_begin(ga, stream, C == 32 ? PROF_CONV_SLAB32 : PROF_CONV_SLAB16, rec, prof);
   if (rc != SS_OK) return rc;
   hipLaunchKernelGGL((conv_pair_kernel<C>), dim3(grid), dim3(256), lds, stream, a, 144 + (a.taps - 1) * a.dil);
   SS_LAUNCH_CHECK();

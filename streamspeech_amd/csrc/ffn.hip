@@ -455,7 +455,7 @@ static int launch_ffn_t(FfnKArgs a, int D, const float* ln2_g, hipStream_t strea
     ga.algo_flops = 4.0 * (double)a.M * D * a.F;
     ga.algo_bytes = 4.0 * (2.0 * (double)a.M * D + 2.0 * (double)D * a.F + a.F + 3.0 * D + (ln2_g ? 2.0 * D : 0.0));
     ProfRec rec{}; bool prof = false;
-    rc = prof_begin(ga, stream, 22, rec, prof);
+    rc = prof_begin(ga, stream, PROF_FFN, rec, prof);
     if (rc != SS_OK) return rc;
     hipLaunchKernelGGL(ffn_fused_kernel<WMT>, dim3((unsigned)G), dim3(256), kLds, stream, a);
     SS_LAUNCH_CHECK();
@@ -474,7 +474,7 @@ static int launch_ffn_t(FfnKArgs a, int D, const float* ln2_g, hipStream_t strea
   ga.algo_flops = 4.0 * (double)a.M * D * a.F;
   ga.algo_bytes = 4.0 * (2.0 * (double)a.M * D + 2.0 * (double)D * a.F + a.F + 3.0 * D + (ln2_g ? 2.0 * D : 0.0));
   ProfRec rec{}; bool prof = false;
-  rc = prof_begin(ga, stream, 22, rec, prof);
+  rc = prof_begin(ga, stream, PROF_FFN, rec, prof);
   if (rc != SS_OK) return rc;
   hipLaunchKernelGGL(ffn_fused_kernel<WMT>, dim3((unsigned)G), dim3(256), kLds, stream, a);
   SS_LAUNCH_CHECK();

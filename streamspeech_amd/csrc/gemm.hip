@@ -648,7 +648,7 @@ template <int KS>
 static int launch_gemv_ks(const GemmArgs& a, hipStream_t stream) {
   dim3 grid(cdiv(a.N, 4 / KS));
   ProfRec rec{}; bool prof = false;
-  int rc = prof_begin(a, stream, 12, rec, prof);     // profiled with the small-M class (decode GEMVs)
+  int rc = prof_begin(a, stream, PROF_SMALLM_4x1, rec, prof);     // profiled with the small-M class (decode GEMVs)
   if (rc != SS_OK) return rc;
   if (a.ln_g) hipLaunchKernelGGL((gemv_kernel<4, KS, true>), grid, dim3(256), 0, stream, a);
   else hipLaunchKernelGGL((gemv_kernel<4, KS, false>), grid, dim3(256), 0, stream, a);
@@ -665,7 +665,7 @@ static int launch_gemv(const GemmArgs& a, hipStream_t stream) {
 }
 
 // ---- optional event profiler -------------------------------------------------------------------
-static const char* kTileNames[kNumTileCfg] = {
+static const char* kTileNames[] = {
     "conv_gemm<128,16,16,4,1>", "conv_gemm<128,32,32,4,1>", "conv_gemm<128,32,16,4,1>", "conv_gemm<16,128,32,1,4>",
     "conv_gemm<16,128,16,1,4>", "conv_gemm<128,128,16,2,2>", "conv_gemm<128,64,32,2,2>", "conv_gemm<64,64,32,2,2>",
     "conv_gemm<64,64,16,2,2>", "conv_gemm<32,64,32,2,2>", "conv_gemm<32,64,16,2,2>", "conv_gemm<32,32,32,2,2>",
@@ -674,6 +674,7 @@ static const char* kTileNames[kNumTileCfg] = {
     // whole-ResBlock launches of the narrow vocoder stages (resblock.hip) and the fused encoder FFN (ffn.hip): kernels of their own,
     // booked under their own names (round 3 booked resblock_fused under conv_slab<..>: VERDICT r3 "mislabelled second kernel")
     "resblock_fused<32>", "resblock_fused<16>", "ffn_fused<256,2048>", "rt_linear<48,256>", "conv_c64<256,64>", "conv_c32<256,32>", "conv_c16<256,16>", "conv_c64w<256,64>", "conv_c128w<256,128>", "conv_c32w<256,32>", "conv_c256w<256,128>", "rt_linear_kb<48,256>"};
+static_assert(sizeof(kTileNames) / sizeof(kTileNames[0]) == kNumTileCfg, "one name per ProfCls, in enum order");
 static std::atomic<int> g_prof_mask{0};     // event brackets per class: written by ss_prof_enable between regions, read by every launch
 static std::vector<ProfRec> g_prof_recs;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_prof_pool;
@@ -768,7 +769,9 @@ static void algo_work(const GemmArgs& a, double& flops, double& bytes) {
   if (a.algo_bytes > 0) bytes = a.algo_bytes;
 }
 
-int prof_begin(const GemmArgs& a, hipStream_t stream, int cls, ProfRec& rec, bool& prof) {
+static bool prof_cls_winograd(ProfCls cls) { return cls >= PROF_CONV_C64W && cls <= PROF_CONV_C256W; }
+
+int prof_begin(const GemmArgs& a, hipStream_t stream, ProfCls cls, ProfRec& rec, bool& prof) {
   {
     double fl, by;
     algo_work(a, fl, by);
@@ -792,7 +795,7 @@ int prof_begin(const GemmArgs& a, hipStream_t stream, int cls, ProfRec& rec, boo
   algo_work(a, rec.flops, rec.bytes);
   // Winograd classes (conv_c64w / conv_c128w / conv_c32w / conv_c256w): 4 MFMA k-blocks per output pair and full tap group + 2 (3) for a
   // last group of one (two) taps, instead of 2 k: 4 / 10 / 15 against 6 / 14 / 22 at k = 3 / 7 / 11
-  rec.issued = (cls >= 27 && cls <= 30 && a.taps >= 3) ? rec.flops * (4.0 * (a.taps / 3) + (a.taps % 3 ? a.taps % 3 + 1 : 0)) / (2.0 * a.taps) : rec.flops;
+  rec.issued = (prof_cls_winograd(cls) && a.taps >= 3) ? rec.flops * (4.0 * (a.taps / 3) + (a.taps % 3 ? a.taps % 3 + 1 : 0)) / (2.0 * a.taps) : rec.flops;
   SS_HIP_CHECK(hipEventRecord(rec.e0, stream));
   return SS_OK;
 }
@@ -811,7 +814,7 @@ int prof_end(hipStream_t stream, ProfRec& rec, bool prof) {
 constexpr int default_pd(int, int) { return 1; }
 
 template <int BM, int BN, int BK, int WM, int WN, int KS = 1, int PD = default_pd(BM, BN), bool BLK = false>
-static int launch_cfg(const GemmArgs& a, hipStream_t stream, int cls) {
+static int launch_cfg(const GemmArgs& a, hipStream_t stream, ProfCls cls) {
   constexpr size_t kLds = (size_t)KS * 2 * (BM + BN) * (BK + 8) * sizeof(float);
   static_assert(kLds <= 160 * 1024, "LDS budget");
   static_assert((size_t)(KS - 1) * BM * BN * sizeof(float) <= kLds, "reduction scratch fits the staging buffers");
@@ -833,7 +836,7 @@ static int launch_cfg(const GemmArgs& a, hipStream_t stream, int cls) {
 
 // pick the k-split so that tiles * 4 * KS waves cover the 1024 SIMDs (each group keeps >= 2 k-steps)
 template <int BM, int BN, int BK, int WM, int WN, int MAXKS>
-static int launch_cfg_ks(const GemmArgs& a, hipStream_t stream, int cls, long tiles) {
+static int launch_cfg_ks(const GemmArgs& a, hipStream_t stream, ProfCls cls, long tiles) {
   const int nk = a.taps * (a.Cin / BK);
   int ks = 1;
   while (ks < MAXKS && tiles * 4 * ks < 1024 && nk / (ks * 2) >= 2) ks *= 2;
@@ -843,7 +846,7 @@ static int launch_cfg_ks(const GemmArgs& a, hipStream_t stream, int cls, long ti
 }
 
 template <int SK, int WN, bool GLU = false>
-static int launch_smallm(const GemmArgs& a, hipStream_t stream, int cls) {
+static int launch_smallm(const GemmArgs& a, hipStream_t stream, ProfCls cls) {
   dim3 grid((cdiv(a.N, 16 * WN) + 7) & ~7, cdiv(a.M, 16));   // see the kernel: n-tiles fastest, a multiple of 8 of them
   ProfRec rec{}; bool prof = false;
   int rc = prof_begin(a, stream, cls, rec, prof);
@@ -963,6 +966,34 @@ int sk_workspace_acquire(hipStream_t stream, SkWorkspace** out) {
   return SS_OK;
 }
 
+// (the launchers without a stream-K workspace: conv_slab / conv_pair / resblock_fused)
+int device_cus(int& cus) {
+  static std::mutex mu;
+  static int n[128] = {0};
+  int dev = 0;
+  SS_HIP_CHECK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 128) return SS_ERR_ARG;
+  std::lock_guard<std::mutex> lk(mu);
+  if (n[dev] == 0) {
+    int v = 0;
+    SS_HIP_CHECK(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
+    n[dev] = v > 0 ? v : 256;
+  }
+  cus = n[dev];
+  return SS_OK;
+}
+
+// ---- eligibility prefixes of the slab kernels (gemm.hpp) ----
+bool slab_layout_ok(const GemmArgs& a) {
+  return a.same_rows && a.stride == 1 && a.chunk == 0 && !a.glu && !a.ln_g && a.lda == a.Cin && (a.ldc & 3) == 0 &&
+         (!a.R || (a.ldr & 3) == 0) && (!a.R2 || (a.ldr2 & 3) == 0) && (!a.C2 || (a.ldc2 & 3) == 0);
+}
+bool slab_conv_ok(const GemmArgs& a, int c) {
+  return slab_layout_ok(a) && !a.x3 && a.Cin == c && a.N == c &&
+         (a.in_act == ACT_NONE || (a.in_act == ACT_LRELU && a.in_slope > 0.f && a.in_slope < 1.f)) &&
+         (a.act == ACT_NONE || a.act == ACT_LRELU);
+}
+
 int sk_workspace_error_count() {
   std::lock_guard<std::mutex> lk(g_skw_mu);
   int total = 0;
@@ -1002,10 +1033,10 @@ static int launch_canon(const GemmArgs& a, hipStream_t stream) {
   if (a.ln_out) return SS_ERR_ARG;
   if (a.canon == CANON_SMALLM) {
     if (!smallm_shape_ok(a)) return SS_ERR_ARG;
-    if (a.glu) return launch_smallm<2, 2, true>(a, stream, 13);
+    if (a.glu) return launch_smallm<2, 2, true>(a, stream, PROF_SMALLM_2x2);
     // split-K form by (N, K) alone: 4 waves on one 16-column tile's k-quarters, or 2 x 2 when N alone fills the chip
-    if (a.Cin >= 1024 || a.N <= 4096) return launch_smallm<4, 1>(a, stream, 12);
-    return launch_smallm<2, 2>(a, stream, 13);
+    if (a.Cin >= 1024 || a.N <= 4096) return launch_smallm<4, 1>(a, stream, PROF_SMALLM_4x1);
+    return launch_smallm<2, 2>(a, stream, PROF_SMALLM_2x2);
   }
   // ---- CANON_SEQ: one accumulator chain per output element ----
   if (rtlin_shape_ok(a) && (a.ln_g || rtlin_eligible(a))) return launch_rtlin(a, stream);
@@ -1014,13 +1045,13 @@ static int launch_canon(const GemmArgs& a, hipStream_t stream) {
   // (rounds 4-5 sent big N % 128 == 0 shapes to conv_sk2 cut on whole tiles -- ONE chain over all of K; its 128 accumulator
   //  registers per wave leave no room for the second accumulator set the blocked chain needs, so CANON_SEQ no longer routes there)
   // LDS-tiled kernel, one k-group, blocked chain (BLK)
-  if (a.N <= 16) return launch_cfg<128, 16, 16, 4, 1, 1, 1, true>(a, stream, 0);
-  if (a.N <= 32 && !a.glu) return k32 ? launch_cfg<128, 32, 32, 4, 1, 1, 1, true>(a, stream, 1) : launch_cfg<128, 32, 16, 4, 1, 1, 1, true>(a, stream, 2);
-  if (M <= 16) return k32 ? launch_cfg<16, 128, 32, 1, 4, 1, 1, true>(a, stream, 3) : launch_cfg<16, 128, 16, 1, 4, 1, 1, true>(a, stream, 4);
+  if (a.N <= 16) return launch_cfg<128, 16, 16, 4, 1, 1, 1, true>(a, stream, PROF_GEMM_128x16x16);
+  if (a.N <= 32 && !a.glu) return k32 ? launch_cfg<128, 32, 32, 4, 1, 1, 1, true>(a, stream, PROF_GEMM_128x32x32) : launch_cfg<128, 32, 16, 4, 1, 1, 1, true>(a, stream, PROF_GEMM_128x32x16);
+  if (M <= 16) return k32 ? launch_cfg<16, 128, 32, 1, 4, 1, 1, true>(a, stream, PROF_GEMM_16x128x32) : launch_cfg<16, 128, 16, 1, 4, 1, 1, true>(a, stream, PROF_GEMM_16x128x16);
   const long t3264 = (long)cdiv(M, 32) * cdiv(a.N, 64) * nseg;
-  if (!k32) return launch_cfg<32, 64, 16, 2, 2, 1, 1, true>(a, stream, 10);
-  if (a.glu || t3264 >= 768) return launch_cfg<32, 64, 32, 2, 2, 1, 1, true>(a, stream, 9);
-  return launch_cfg<32, 32, 32, 2, 2, 1, 1, true>(a, stream, 11);
+  if (!k32) return launch_cfg<32, 64, 16, 2, 2, 1, 1, true>(a, stream, PROF_GEMM_32x64x16);
+  if (a.glu || t3264 >= 768) return launch_cfg<32, 64, 32, 2, 2, 1, 1, true>(a, stream, PROF_GEMM_32x64x32);
+  return launch_cfg<32, 32, 32, 2, 2, 1, 1, true>(a, stream, PROF_GEMM_32x32x32);
 }
 
 bool smallm_eligible(const GemmArgs& a) {
@@ -1055,23 +1086,23 @@ int launch_conv_gemm(const GemmArgs& a_in, hipStream_t stream) {
   if (a.m_begin > 0) {       // a row range of a strided conv (ss_encoder_stream_forward): only the LDS-tile kernel starts anywhere but row 0
     if (a.nseg > 0 || a.m_begin >= a.M || a.ln_g || a.ln_out || a.N <= 32) return SS_ERR_ARG;
     const long t = (long)cdiv(a.M - a.m_begin, 32) * cdiv(a.N, 64);
-    if (k32 && t >= 768) return launch_cfg<32, 64, 32, 2, 2, 1>(a, stream, 9);
-    return k32 ? launch_cfg_ks<32, 64, 32, 2, 2, 4>(a, stream, 9, t) : launch_cfg_ks<32, 64, 16, 2, 2, 4>(a, stream, 10, t);
+    if (k32 && t >= 768) return launch_cfg<32, 64, 32, 2, 2, 1>(a, stream, PROF_GEMM_32x64x32);
+    return k32 ? launch_cfg_ks<32, 64, 32, 2, 2, 4>(a, stream, PROF_GEMM_32x64x32, t) : launch_cfg_ks<32, 64, 16, 2, 2, 4>(a, stream, PROF_GEMM_32x64x16, t);
   }
   // a forced tile (tuning hook) keeps M <= 4 launches off the GEMV -- except when the caller asked for ln_out, which only the GEMV writes
   if ((!disp().force_bm || a.ln_out) && gemv_eligible(a)) return launch_gemv(a, stream);
   if (a.ln_out) return SS_ERR_ARG;      // only the GEMV form publishes the normalised rows
   if (smallm_eligible(a)) {
-    if (a.glu) return launch_smallm<2, 2, true>(a, stream, 13);   // value / gate tiles side by side in one workgroup
+    if (a.glu) return launch_smallm<2, 2, true>(a, stream, PROF_SMALLM_2x2);   // value / gate tiles side by side in one workgroup
     const long wgs16 = (long)cdiv(M, 16) * cdiv(a.N, 16);
-    if (a.Cin >= 1024 || wgs16 <= 1024) return launch_smallm<4, 1>(a, stream, 12);
-    if (wgs16 <= 4096) return launch_smallm<2, 2>(a, stream, 13);
-    return launch_smallm<1, 4>(a, stream, 14);
+    if (a.Cin >= 1024 || wgs16 <= 1024) return launch_smallm<4, 1>(a, stream, PROF_SMALLM_4x1);
+    if (wgs16 <= 4096) return launch_smallm<2, 2>(a, stream, PROF_SMALLM_2x2);
+    return launch_smallm<1, 4>(a, stream, PROF_SMALLM_1x4);
   }
   // 64-channel vocoder stage of a packed batch: input slab in LDS once, W fragments from L2 (conv_c64.hip)
   if (!disp().force_bm && conv_c64_eligible(a)) return conv_c64w_eligible(a) ? launch_conv_c64w(a, stream) : launch_conv_c64(a, stream);
-  if (!disp().force_bm && conv_c128w_eligible(a)) return launch_conv_c128w(a, stream);
-  if (!disp().force_bm && conv_c256w_eligible(a)) return launch_conv_c256w(a, stream);
+  if (!disp().force_bm && conv_wide_winograd_eligible(a, 128)) return launch_conv_c128w(a, stream);
+  if (!disp().force_bm && conv_wide_winograd_eligible(a, 256)) return launch_conv_c256w(a, stream);
   if (!disp().force_bm && conv_c32_eligible(a)) return conv_c32w_eligible(a) ? launch_conv_c32w(a, stream) : launch_conv_c32(a, stream);
   if (!disp().force_bm && conv_c16_eligible(a)) return launch_conv_c16(a, stream);
   // K = 256 linears of packed batches (encoder projections, CTC heads, cross K|V): row tile in LDS, W fragments from L2 (rtlin.hip)
@@ -1098,27 +1129,27 @@ int launch_conv_gemm(const GemmArgs& a_in, hipStream_t stream) {
     const int f = disp().force_bm * 10000 + (disp().force_bn % 100) * 100 + disp().force_ks;   // 128x128 -> bn code 28... see cases
     switch (f) {
 #define SS_CASE(BM_, BN_, KS_, PD_, CLS_) case BM_ * 10000 + BN_ * 100 + KS_ * 10 + PD_: return launch_cfg<BM_, BN_, 32, 2, 2, KS_, PD_>(a, stream, CLS_);
-      SS_CASE(64, 64, 1, 1, 7) SS_CASE(64, 64, 1, 2, 7) SS_CASE(64, 64, 1, 3, 7)
-      SS_CASE(64, 64, 2, 2, 7) SS_CASE(64, 64, 2, 3, 7)
-      SS_CASE(32, 64, 1, 1, 9) SS_CASE(32, 64, 1, 2, 9) SS_CASE(32, 64, 1, 3, 9) SS_CASE(32, 64, 1, 4, 9)
-      SS_CASE(32, 64, 2, 3, 9) SS_CASE(32, 64, 4, 3, 9)
-      SS_CASE(32, 32, 1, 1, 11) SS_CASE(32, 32, 1, 2, 11) SS_CASE(32, 32, 1, 3, 11) SS_CASE(32, 32, 1, 4, 11)
-      SS_CASE(32, 32, 2, 3, 11) SS_CASE(32, 32, 4, 3, 11)
+      SS_CASE(64, 64, 1, 1, PROF_GEMM_64x64x32) SS_CASE(64, 64, 1, 2, PROF_GEMM_64x64x32) SS_CASE(64, 64, 1, 3, PROF_GEMM_64x64x32)
+      SS_CASE(64, 64, 2, 2, PROF_GEMM_64x64x32) SS_CASE(64, 64, 2, 3, PROF_GEMM_64x64x32)
+      SS_CASE(32, 64, 1, 1, PROF_GEMM_32x64x32) SS_CASE(32, 64, 1, 2, PROF_GEMM_32x64x32) SS_CASE(32, 64, 1, 3, PROF_GEMM_32x64x32) SS_CASE(32, 64, 1, 4, PROF_GEMM_32x64x32)
+      SS_CASE(32, 64, 2, 3, PROF_GEMM_32x64x32) SS_CASE(32, 64, 4, 3, PROF_GEMM_32x64x32)
+      SS_CASE(32, 32, 1, 1, PROF_GEMM_32x32x32) SS_CASE(32, 32, 1, 2, PROF_GEMM_32x32x32) SS_CASE(32, 32, 1, 3, PROF_GEMM_32x32x32) SS_CASE(32, 32, 1, 4, PROF_GEMM_32x32x32)
+      SS_CASE(32, 32, 2, 3, PROF_GEMM_32x32x32) SS_CASE(32, 32, 4, 3, PROF_GEMM_32x32x32)
 #undef SS_CASE
-      case 128 * 10000 + 28 * 100 + 11: return launch_cfg<128, 128, 16, 2, 2, 1, 1>(a, stream, 5);
-      case 128 * 10000 + 64 * 100 + 11: return launch_cfg<128, 64, 32, 2, 2, 1, 1>(a, stream, 6);
+      case 128 * 10000 + 28 * 100 + 11: return launch_cfg<128, 128, 16, 2, 2, 1, 1>(a, stream, PROF_GEMM_128x128x16);
+      case 128 * 10000 + 64 * 100 + 11: return launch_cfg<128, 64, 32, 2, 2, 1, 1>(a, stream, PROF_GEMM_128x64x32);
       default: break;
     }
   }
   // narrow vocoder stages: weights + input slab in LDS, one HBM pass (conv_slab.hip)
   if (disp().force_bm != 2 && conv_slab_eligible(a) && a.M >= 2048) return launch_conv_slab(a, stream);
-  if (a.N <= 16) return launch_cfg_ks<128, 16, 16, 4, 1, 2>(a, stream, 0, (long)cdiv(M, 128) * nseg);
+  if (a.N <= 16) return launch_cfg_ks<128, 16, 16, 4, 1, 2>(a, stream, PROF_GEMM_128x16x16, (long)cdiv(M, 128) * nseg);
   if (a.N <= 32 && !a.glu) {
     const long tl = (long)cdiv(M, 128) * nseg;
-    return k32 ? launch_cfg_ks<128, 32, 32, 4, 1, 2>(a, stream, 1, tl) : launch_cfg_ks<128, 32, 16, 4, 1, 2>(a, stream, 2, tl);
+    return k32 ? launch_cfg_ks<128, 32, 32, 4, 1, 2>(a, stream, PROF_GEMM_128x32x32, tl) : launch_cfg_ks<128, 32, 16, 4, 1, 2>(a, stream, PROF_GEMM_128x32x16, tl);
   }
   if (M <= 16) {
-    return k32 ? launch_cfg<16, 128, 32, 1, 4>(a, stream, 3) : launch_cfg<16, 128, 16, 1, 4>(a, stream, 4);
+    return k32 ? launch_cfg<16, 128, 32, 1, 4>(a, stream, PROF_GEMM_16x128x32) : launch_cfg<16, 128, 16, 1, 4>(a, stream, PROF_GEMM_16x128x16);
   }
   // Tile choice (tools/conv_bench.py sweep on MI355X, profiles/r01_tile_sweep.txt): these problems are
   // a few GFLOP at most, so what matters is an even spread over 1024 SIMDs with several resident
@@ -1127,14 +1158,14 @@ int launch_conv_gemm(const GemmArgs& a_in, hipStream_t stream) {
   const long t3232 = (long)cdiv(M, 32) * cdiv(a.N, 32) * nseg;
   const long t3264 = (long)cdiv(M, 32) * cdiv(a.N, 64) * nseg;
   (void)t128;   // 128x128 tiles lose to 32x64 even at batch scale (profiles/r01_tile_sweep_batch.txt)
-  if (k32 && t3264 >= 768) return launch_cfg<32, 64, 32, 2, 2, 1>(a, stream, 9);   // big (batched) problems: ~90 TFLOP/s
+  if (k32 && t3264 >= 768) return launch_cfg<32, 64, 32, 2, 2, 1>(a, stream, PROF_GEMM_32x64x32);   // big (batched) problems: ~90 TFLOP/s
   if (!k32 || a.glu) {
-    return k32 ? launch_cfg_ks<32, 64, 32, 2, 2, 4>(a, stream, 9, t3264) : launch_cfg_ks<32, 64, 16, 2, 2, 4>(a, stream, 10, t3264);
+    return k32 ? launch_cfg_ks<32, 64, 32, 2, 2, 4>(a, stream, PROF_GEMM_32x64x32, t3264) : launch_cfg_ks<32, 64, 16, 2, 2, 4>(a, stream, PROF_GEMM_32x64x16, t3264);
   }
   const int nk = a.taps * (a.Cin / 32);
-  if (t3232 >= 700 || nk < 4) return launch_cfg<32, 32, 32, 2, 2, 1>(a, stream, 11);
-  if (t3232 >= 300 || nk < 8) return launch_cfg<32, 32, 32, 2, 2, 2>(a, stream, 11);
-  return launch_cfg<32, 32, 32, 2, 2, 4>(a, stream, 11);
+  if (t3232 >= 700 || nk < 4) return launch_cfg<32, 32, 32, 2, 2, 1>(a, stream, PROF_GEMM_32x32x32);
+  if (t3232 >= 300 || nk < 8) return launch_cfg<32, 32, 32, 2, 2, 2>(a, stream, PROF_GEMM_32x32x32);
+  return launch_cfg<32, 32, 32, 2, 2, 4>(a, stream, PROF_GEMM_32x32x32);
 }
 
 }  // namespace ss

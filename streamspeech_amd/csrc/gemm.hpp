@@ -87,8 +87,19 @@ int canon_mode();                      // the calling thread's current mode
 void canon_debug_set(int mode);        // test hook: the calling thread's mode outside any scope (ss_debug_canon)
 
 // Optional per-launch timing with HIP events recorded on the launch stream (bench.py roofline
-// leg).  Tile-config classes: see kTileNames in gemm.hip.
-constexpr int kNumTileCfg = 32;
+// leg).  Kernel classes, in the order of their names (kTileNames in gemm.hip; tests and bench.py look them up by name):
+enum ProfCls : int {
+  PROF_GEMM_128x16x16 = 0, PROF_GEMM_128x32x32 = 1, PROF_GEMM_128x32x16 = 2, PROF_GEMM_16x128x32 = 3, PROF_GEMM_16x128x16 = 4,
+  PROF_GEMM_128x128x16 = 5, PROF_GEMM_128x64x32 = 6, PROF_GEMM_64x64x32 = 7, PROF_GEMM_64x64x16 = 8, PROF_GEMM_32x64x32 = 9,
+  PROF_GEMM_32x64x16 = 10, PROF_GEMM_32x32x32 = 11,
+  PROF_SMALLM_4x1 = 12, PROF_SMALLM_2x2 = 13, PROF_SMALLM_1x4 = 14,
+  PROF_CONV_SK = 15, PROF_CONV_SLAB32 = 16, PROF_CONV_SLAB16 = 17, PROF_CONV_SK2 = 18, PROF_CONV_SK2_BF16X3 = 19,
+  PROF_RESBLOCK32 = 20, PROF_RESBLOCK16 = 21, PROF_FFN = 22, PROF_RTLIN = 23,
+  PROF_CONV_C64 = 24, PROF_CONV_C32 = 25, PROF_CONV_C16 = 26,
+  PROF_CONV_C64W = 27, PROF_CONV_C128W = 28, PROF_CONV_C32W = 29, PROF_CONV_C256W = 30,   // the Winograd forms (prof_begin: issued FLOPs)
+  PROF_RTLIN_KB = 31,
+};
+constexpr int kNumTileCfg = PROF_RTLIN_KB + 1;
 void prof_enable(int cls_mask);   // bit i set -> bracket launches of tile config i with events; 0 = off
 void prof_reset();
 int prof_read(int cls, double* ms_total, double* flops_total, long long* launches, double* bytes_total = nullptr);  // synchronises
@@ -103,7 +114,7 @@ int prof_shape_dump(char* buf, int cap);
 
 // Event-profiler scope shared by the kernel launchers (gemm.hip, conv_sk.hip).
 struct ProfRec { hipEvent_t e0, e1; double flops, bytes, issued; int cls; };
-int prof_begin(const GemmArgs& a, hipStream_t stream, int cls, ProfRec& rec, bool& prof);
+int prof_begin(const GemmArgs& a, hipStream_t stream, ProfCls cls, ProfRec& rec, bool& prof);
 int prof_end(hipStream_t stream, ProfRec& rec, bool prof);
 
 // Stream-K hand-off state (partial-tile workspace, ticket counter, per-workgroup flags) of ONE execution context: an
@@ -153,6 +164,26 @@ int conv_sk2_error_count();
 // tensors to the generic tiles on a byte bound inherited from the buffer-addressed stream-K kernels); rows and segment tables are int.
 inline bool slab_rows_ok(long long rows) { return rows > 0 && rows < (1ll << 30); }
 
+// Launcher helpers of the slab kernels.  LDS of a slab of slab_rows x lda floats (16-B aligned) followed by the block table of the
+// segment walk (slab_common.hpp) for up to maxseg segments:
+inline size_t slab_lds_bytes(int slab_rows, int lda, int maxseg) {
+  return (size_t)((slab_rows * lda + 3) & ~3) * sizeof(float) + (maxseg + 2) * sizeof(int);
+}
+// upper bound of the blocks of bm rows of a launch (per-segment round-up)
+inline long long slab_max_blocks(int M, int bm, int nseg) { return (long long)cdiv(M, bm) + (nseg > 0 ? nseg : 1); }
+// persistent grid: occ resident workgroups on each of `cus` CUs, no more workgroups than blocks
+inline int slab_grid(int occ, int cus, int M, int bm, int nseg) {
+  return (int)std::min<long long>((long long)occ * cus, std::max<long long>(1, slab_max_blocks(M, bm, nseg)));
+}
+// Eligibility prefix of the GemmArgs slab kernels: "same" rows at stride 1 without the chunk / GLU / LayerNorm forms, A rows read
+// densely (lda == Cin), 16-B aligned C / R / R2 / C2 rows.
+bool slab_layout_ok(const GemmArgs& a);
+// ... and of conv_c16 / c32 / c64 / the Winograd forms on top of it: Cin = N = c, no split-bf16, input leaky-ReLU (0 < slope < 1)
+// or none, epilogue leaky-ReLU or none.
+bool slab_conv_ok(const GemmArgs& a, int c);
+// CU count of the current device, read once per device (thread-safe)
+int device_cus(int& cus);
+
 // Slab conv for the narrow vocoder stages (conv_slab.hip): C, N in {16, 32}, weights + input slab in LDS.
 bool conv_slab_eligible(const GemmArgs& a);
 int launch_conv_slab(const GemmArgs& a, hipStream_t stream);
@@ -183,13 +214,13 @@ int launch_conv_c64w(const GemmArgs& a, hipStream_t stream);
 int launch_wino_pack(const float* W, float* WW, int C, int taps, hipStream_t stream);   // WW: C * ceil(taps/3) * 4 * C floats
 void conv_c64w_debug(int enable);                 // A/B: 0 off, 1 on, -1 keep
 bool conv_c64w_enabled();
-// the same kernel at 128 channels (one workgroup per CU): the 128-channel stage's ResBlock convs instead of conv_sk2<128> + twins
-bool conv_c128w_eligible(const GemmArgs& a);
+// the same kernel at 128 channels (one workgroup per CU): the 128-channel stage's ResBlock convs instead of conv_sk2<128> + twins,
+// and at 256 (below); ch = 128 or 256
+bool conv_wide_winograd_eligible(const GemmArgs& a, int ch);
 int launch_conv_c128w(const GemmArgs& a, hipStream_t stream);
 void conv_c128w_debug(int enable);
 bool conv_c128w_enabled();
 // ... at 256 channels (two slab phases of 128 input channels, two column halves; one workgroup per CU): the 256-channel stage's ResBlock convs
-bool conv_c256w_eligible(const GemmArgs& a);
 int launch_conv_c256w(const GemmArgs& a, hipStream_t stream);
 void conv_c256w_debug(int enable);
 bool conv_c256w_enabled();

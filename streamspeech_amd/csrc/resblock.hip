@@ -23,13 +23,11 @@
 // Arithmetic per element (tap -> 16-channel group -> k order inside v_mfma_f32_16x16x4_f32, bias, leaky-ReLU, residual,
 // MRF add, mean) is the one conv_slab_kernel / conv_pair_kernel perform: results are bit-identical to the multi-launch
 // form (tests/test_batch_gpu.py).
-#include "gemm.hpp"
+#include "slab_common.hpp"
 
 #include <type_traits>
 
 namespace ss {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int RB_NW = 8;          // waves per workgroup (2 per SIMD)
 constexpr int RB_MAXSEG = 256;
@@ -171,16 +169,7 @@ __global__ __launch_bounds__(RB_NW * 64) void resblock_fused_kernel(const Resblo
   const int H = HT * (p.dil[0] + p.dil[1] + p.dil[2] + 3);
   const int BM = RX - 2 * H;
 
-  // block table: s_blk[s] = first block of utterance s
-  const int nseg = p.nseg > 0 ? p.nseg : 1;
-  if (t == 0) {
-    int acc = 0;
-    for (int s = 0; s < nseg; ++s) {
-      s_blk[s] = acc;
-      acc += ((p.nseg > 0 ? p.segs[4 * s + 1] : p.M) + BM - 1) / BM;
-    }
-    s_blk[nseg] = acc;
-  }
+  SlabWalk<ResblockArgs> w(p, s_blk, BM);        // (block table: its barrier is the one below)
   // margins and slabs start as zeros (rows no valid output ever depends on, but keep them finite)
   for (int i = t; i < 2 * G::SLAB_FLOATS; i += NT) sWb[G::NWB * G::W_FLOATS + i] = 0.f;
   if (t < 6 * C) {
@@ -188,7 +177,7 @@ __global__ __launch_bounds__(RB_NW * 64) void resblock_fused_kernel(const Resblo
     sB[t] = ((c & 1) ? p.B2[c >> 1] : p.B1[c >> 1])[n];
   }
   __syncthreads();
-  const int nblocks = s_blk[nseg];
+  const int nblocks = w.nblocks();
 
   // weights of conv `c` (0..5: pair c/2, conv1 / conv2) global -> registers -> LDS buffer c % NWB
   f32x4 wreg[WV4];
@@ -228,34 +217,27 @@ __global__ __launch_bounds__(RB_NW * 64) void resblock_fused_kernel(const Resblo
 
   // block geometry + the raw x values of this wave's units (epilogue layout: lane (r, g) holds row tau*16 + r,
   // channels n_l .. n_l + 3)
-  int seg = 0, seg_lo = 0, seg_hi = 0, m0 = 0;
-  auto locate = [&](int blk) {                 // blocks ascend per workgroup
-    while (blk >= s_blk[seg + 1]) ++seg;
-    seg_lo = p.nseg > 0 ? p.segs[4 * seg] : 0;
-    seg_hi = seg_lo + (p.nseg > 0 ? p.segs[4 * seg + 1] : p.M);
-    m0 = seg_lo + (blk - s_blk[seg]) * BM;
-  };
   f32x4 pre[SLOTS], xr[SLOTS];
   auto x_fetch = [&]() {
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
       const int tau = s * TS + tw;
-      const int gm = m0 - H + tau * 16 + r;
+      const int gm = w.m0 - H + tau * 16 + r;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (tau < NTILE && gm >= seg_lo && gm < seg_hi) v = *reinterpret_cast<const f32x4*>(p.X + (size_t)gm * p.ldx + n_l);
+      if (tau < NTILE && gm >= w.seg_lo && gm < w.seg_hi) v = *reinterpret_cast<const f32x4*>(p.X + (size_t)gm * p.ldx + n_l);
       pre[s] = v;
     }
   };
 
   int blk = blockIdx.x;
   if (blk < nblocks) {
-    locate(blk);
+    w.locate(blk, p.M);
     x_fetch();
     w_fetch(0);
     w_commit(0);
   }
   for (; blk < nblocks; blk += gridDim.x) {
-    const int cm0 = m0, clo = seg_lo, chi = seg_hi;
+    const int cm0 = w.m0, clo = w.seg_lo, chi = w.seg_hi;
     // ---- stage: raw x -> registers, lrelu(x) -> slab (rows outside the utterance were fetched as zeros) ----
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
@@ -318,7 +300,7 @@ __global__ __launch_bounds__(RB_NW * 64) void resblock_fused_kernel(const Resblo
         if (!last) w_fetch(2 * pair + 2);                  // next pair's conv1
         else {
           w_fetch(0);                                      // next block starts with conv 0 again
-          if (more) { locate(blk + gridDim.x); x_fetch(); }
+          if (more) { w.locate(blk + gridDim.x, p.M); x_fetch(); }
         }
         const float* sW = sWb + (WDB ? 1 : 0) * G::W_FLOATS;   // conv c = 2 * pair + 1: buffer 1
         const f32x4 b = *reinterpret_cast<const f32x4*>(sB + (2 * pair + 1) * C + n_l);
@@ -339,15 +321,7 @@ __global__ __launch_bounds__(RB_NW * 64) void resblock_fused_kernel(const Resblo
             for (int e = 0; e < 4; ++e) w[e] = in_utt ? (v[e] > 0.f ? v[e] : v[e] * slope) : 0.f;
             *reinterpret_cast<f32x4*>(sX + rho * LDA + n_e) = w;
           } else if (in_utt && rho >= H && rho < RX - H) {
-            if (p.R2) {
-              const f32x4 rr = *reinterpret_cast<const f32x4*>(p.R2 + (size_t)gm * p.ldr2 + n_e);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = rr[e] + v[e];
-            }
-            if (p.div > 0.f) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = v[e] / p.div;
-            }
+            v = slab_epi_tail(p, v, [&] { return *reinterpret_cast<const f32x4*>(p.R2 + (size_t)gm * p.ldr2 + n_e); });
             *reinterpret_cast<f32x4*>(p.Y + (size_t)gm * p.ldy + n_e) = v;
           }
         };
@@ -376,42 +350,24 @@ bool resblock_fused_eligible(int C, int taps, const int* dil, int ldx, int ldy, 
          slab_rows_ok(M);
 }
 
-static int rb_cus(int& cus) {             // CU count of the CURRENT device, read once per device (thread-safe)
-  static std::mutex mu;
-  static int n[128] = {0};
-  int dev = 0;
-  SS_HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 128) return SS_ERR_ARG;
-  std::lock_guard<std::mutex> lk(mu);
-  if (n[dev] == 0) {
-    int v = 0;
-    SS_HIP_CHECK(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    n[dev] = v > 0 ? v : 256;
-  }
-  cus = n[dev];
-  return SS_OK;
-}
-
 template <int C, int TAPS>
 static int launch_rb_t(const ResblockArgs& a, hipStream_t stream) {
   using G = RbGeom<C, TAPS>;
   static_assert(G::LDS_BYTES <= 160 * 1024, "slabs + one weight matrix must fit the CU's LDS");
   SS_MAX_LDS_ONCE((&resblock_fused_kernel<C, TAPS>), G::LDS_BYTES);
   int cus = 0;
-  { int rc = rb_cus(cus); if (rc != SS_OK) return rc; }
+  int rc = device_cus(cus);
+  if (rc != SS_OK) return rc;
   const int H = G::HT * (a.dil[0] + a.dil[1] + a.dil[2] + 3);
-  const int BM = G::RX - 2 * H;
-  const int nseg = a.nseg > 0 ? a.nseg : 1;
-  const long long max_blocks = (long long)cdiv(a.M, BM) + nseg;            // upper bound (per-utterance round-up)
-  const int grid = (int)std::min<long long>(cus, std::max<long long>(1, max_blocks));   // one workgroup per CU (LDS)
-  // profiler classes resblock_fused<32> / <16> (20 / 21); algorithmic work of the six convs: 12 M C^2 k FLOP; bytes: x read
+  const int grid = slab_grid(1, cus, a.M, G::RX - 2 * H, a.nseg);   // one workgroup per CU (LDS)
+  // algorithmic work of the six convs: 12 M C^2 k FLOP; bytes: x read
   // once, y written once, the MRF accumulator read once when present, the six weight matrices + biases once
   GemmArgs ga;
   ga.M = a.M; ga.N = C; ga.Cin = C; ga.taps = TAPS; ga.in_len = a.M; ga.R2 = a.R2;
   ga.algo_flops = 12.0 * (double)a.M * C * C * TAPS;
   ga.algo_bytes = 4.0 * ((double)a.M * C * (2 + (a.R2 ? 1 : 0)) + 6.0 * C * (C * TAPS + 1));
   ProfRec rec{}; bool prof = false;
-  int rc = prof_begin(ga, stream, C == 32 ? 20 : 21, rec, prof);
+  rc = prof_begin(ga, stream, C == 32 ? PROF_RESBLOCK32 : PROF_RESBLOCK16, rec, prof);
   if (rc != SS_OK) return rc;
   hipLaunchKernelGGL((resblock_fused_kernel<C, TAPS>), dim3(grid), dim3(RB_NW * 64), G::LDS_BYTES, stream, a);
   SS_LAUNCH_CHECK();

@@ -480,7 +480,7 @@ int launch_rtlin(const GemmArgs& a, hipStream_t stream) {
   if (G < 1) G = 1;
   q.G = (int)G;
   ProfRec rec{}; bool prof = false;
-  int rc = prof_begin(a, stream, 23, rec, prof);
+  int rc = prof_begin(a, stream, PROF_RTLIN, rec, prof);
   if (rc != SS_OK) return rc;
   if (a.glu) {
     SS_MAX_LDS_ONCE((&rt_linear_kernel<true>), RT_LDS);
@@ -535,7 +535,7 @@ int launch_rtlin_kb(const GemmArgs& a, hipStream_t stream) {
   q.G = (int)G;
   q.xmap = (disp().rt_kb_xmap && disp().rt_force_g <= 0 && G == 3LL * cus && (cus & 7) == 0 && ((G >> 3) % q.NCG) == 0 && U >= 2 * G) ? 1 : 0;
   ProfRec rec{}; bool prof = false;
-  int rc = prof_begin(a, stream, 31, rec, prof);
+  int rc = prof_begin(a, stream, PROF_RTLIN_KB, rec, prof);
   if (rc != SS_OK) return rc;
   if (uw == 1) {
     SS_MAX_LDS_ONCE((&rt_linear_kb_kernel<1>), RT_LDS);

@@ -201,7 +201,7 @@ static int hifigan_stack(const ss_vocoder* v, hipStream_t s, ConvFn&& conv, Stag
           probe.taps = c.resblock_kernel_sizes[j]; probe.dil = which ? 1 : c.resblock_dilations[j][dd];
           probe.pad = probe.dil * (probe.taps - 1) / 2; probe.M = probe.in_len = gM; probe.nseg = gnseg; probe.in_act = ACT_LRELU;
           probe.Wwino = which ? v->rb_c2[idx].ww : v->rb_c1[idx].ww;
-          if (!(channels == 128 ? conv_c128w_eligible(probe) : conv_c256w_eligible(probe))) return false;
+          if (!conv_wide_winograd_eligible(probe, channels)) return false;
         }
     return true;
   };
