@@ -29,6 +29,7 @@ extern "C" {
 typedef struct ss_model ss_model;      /* StreamSpeechModel replacement (encoder + CTC + MT + T2U + unit decoder): WEIGHTS of one language */
 typedef struct ss_vocoder ss_vocoder;  /* CodeHiFiGANVocoderWithDur replacement: WEIGHTS */
 typedef struct ss_scratch ss_scratch;  /* everything a call mutates: activations, KV caches, stream-K hand-off state, streaming state */
+typedef struct ss_stream_pool ss_stream_pool;  /* incremental-encoder state of many concurrent streams (ss_stream_pool_*) */
 
 /* Architecture hyper-parameters (reference researches/ctc_unity/models/streamspeech_model.py:418-430
  * and train_scripts/train.offline-s2st.sh). */
@@ -223,6 +224,42 @@ int ss_encoder_stream_forward(ss_model* m, void* stream, const float* d_fbank, i
  * after *repeat = 1 (and recomputes what it derived from the void output). */
 int ss_encoder_stream_set_deferred(ss_model* m, int on);
 int ss_encoder_stream_status(ss_model* m, void* stream, int32_t* repeat);
+
+/* ---- concurrent streaming sessions: one batched encoder step for many streams -----------------------------------------------
+ * A pool holds the incremental-encoder state of up to max_sessions independent streams in slots: per layer the q|k|v and GLU rows,
+ * the final output rows (max_rows <= max_rel_pos rows per slot, ~50 KB per row at the default sizes), the chunk sizes, the unsettled
+ * tail, and the raw per-frame arg-max of both CTC heads for rows that are final.  It is created against m's scratch set: its buffers
+ * are booked there (ss_scratch_bytes reports them, ss_scratch_trim keeps them -- a fixed piece like the MT cache), a pool that would
+ * pass ss_scratch_set_cap fails with SS_ERR_SCRATCH_CAP and leaves the set as it was, and session state is never re-allocated by a
+ * call.  The set lives until the pool is destroyed.  A pool is driven by ONE host thread at a time, like a scratch set; any handle
+ * bound to the pool's scratch set may drive it.
+ * ss_stream_pool_reset: the slot starts a fresh utterance.  ss_stream_pool_set_tail: as ss_encoder_stream_set_tail, per slot. */
+int ss_stream_pool_create(ss_model* m, int max_sessions, int max_rows, ss_stream_pool** out);
+void ss_stream_pool_destroy(ss_stream_pool* p);
+int ss_stream_pool_reset(ss_stream_pool* p, int slot);
+int ss_stream_pool_set_tail(ss_stream_pool* p, int slot, int unsettled_fbank_frames);
+/* One encoder step of n sessions (slots h_slots[i], distinct): per slot EXACTLY the semantics of ss_encoder_stream_forward -- session
+ * i passes the fbank of all its audio so far (h_fbank[i]: device pointer, h_T[i] rows of 80), rows final at its previous call come
+ * from the slot, n_final follows the same finality rule (its tail included), a change of chunk sizes or a shorter input resets the slot
+ * implicitly.  Sessions of one call may differ in length, chunk sizes and tail.  d_enc_packed [sum T2_i, 256] gets every session's
+ * output rows in call order (session 0's T2_0 rows, then session 1's, ...) -- the packed layout of ss_batch_ctc_greedy /
+ * ss_batch_mt_greedy.  h_n_final[i] / h_n_computed[i] (host, may be NULL) as in ss_encoder_stream_forward.
+ * The tail rows of all sessions go through the layers as ONE row pack, one launch per op per layer whatever n, with pack-invariant
+ * arithmetic: a session's rows are the same bits alone, in any pack and at any position in it.  Ordinary launches only -- no
+ * persistent form, no grid-wide waits, no time-out protocol.  Bad arguments, a duplicate slot or a session with more than max_rows
+ * output rows refuse the WHOLE call with SS_ERR_ARG before anything is queued; no slot changes. */
+int ss_encoder_stream_forward_batch(ss_model* m, void* stream, ss_stream_pool* p, int n, const int32_t* h_slots,
+                                    const float* const* h_fbank, const int32_t* h_T, const int32_t* h_attn_chunk,
+                                    const int32_t* h_conv_chunk, float* d_enc_packed, int32_t* h_n_final, int32_t* h_n_computed);
+/* Both-head CTC greedy search of the last step's output (head 0 = ASR, 1 = ST), outputs as ss_batch_ctc_greedy: d_raw [sum T2_i] raw
+ * arg-max, d_tokens / d_index [sum T2_i] collapsed tokens and their frame index at each session's packed offset, d_counts [n].  Slots
+ * h_slots in the same order as the forward that wrote d_enc_packed (their T2 are the pool's).  Rows below a slot's n_final never
+ * change, so their arg-max is kept in the slot: the head GEMM and arg-max run only over rows the slot does not hold yet. */
+int ss_stream_pool_ctc(ss_model* m, void* stream, ss_stream_pool* p, int head, int n, const int32_t* h_slots,
+                       const float* d_enc_packed, int32_t* d_raw, int32_t* d_tokens, int32_t* d_index, int32_t* d_counts);
+/* Test hook: the pool's counters since its creation -- kernels its calls launched (its own kernels, plus the GEMM-family launches the
+ * library's launch census saw during the call: meaningful while no other thread launches), rows its CTC calls ran through a head. */
+int ss_stream_pool_stats(ss_stream_pool* p, int64_t* launches, int64_t* head_rows);
 
 /* ---- a8: CTCDecoder.generate (agent/ctc_decoder.py:39-111): head 0 = source_unigram (ASR),
  * 1 = ctc_target_unigram (ST).  Outputs (device int32): raw argmax per frame [Tp], collapsed

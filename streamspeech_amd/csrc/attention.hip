@@ -810,6 +810,176 @@ __global__ __launch_bounds__(256) void attention_relpos_q16_kernel(AttnArgs p) {
   }
 }
 
+// -------------------------------------------------------------------------------------------------
+// The same (16-query tile, 64-key tile, head) arithmetic as attention_relpos_q16_kernel for the tail rows of MANY streaming sessions
+// in one launch (PoolAttnArgs, stream_pool.hip).  Workgroup = (16-query tile of some session, head), found through the flattened
+// prefix table; its four waves are the four 16-key sub-tiles of a key tile, and it walks the session's key tiles itself, merging each
+// tile's normalised partial into a running (max, sum, output) -- no key split across workgroups, so no hand-off state and nothing
+// that depends on what else is in the launch: a row's bits are a function of its own session.
+// -------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void attention_pool_kernel(PoolAttnArgs p) {
+  using f32x4 = __attribute__((ext_vector_type(4))) float;
+  __shared__ __attribute__((aligned(16))) float Gs_all[4 * 16 * LDG];
+  __shared__ float ms[4][16], ls[4][16];
+  __shared__ __attribute__((aligned(16))) float osum[4][16][Q16_LDO];
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int h = blockIdx.y, hoff = h * DH;
+  const int gq = blockIdx.x;
+  int lo = 0, hi = p.nsess - 1;                        // session of this query tile: last z with qt_pre[z] <= gq
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (p.qt_pre[mid] <= gq) lo = mid; else hi = mid - 1;
+  }
+  const int* se = p.sess + 8 * lo;
+  const int q_start = se[0], Tq = se[1], q0 = se[2], Tk = se[3], slot = se[4], chunk = se[5];
+  const int i0 = (gq - p.qt_pre[lo]) * 16;
+  const float* Qs = p.Qs + (size_t)q_start * p.ld;
+  float* cache = p.cache + (size_t)slot * p.slot_rows * p.ld;
+  const float* P = p.P + (size_t)(p.p_tmax - Tk) * p.ldp;
+  // key / value row j: the slot's cache below the first query, the stacked rows from there on
+  auto krow = [&](int j) -> const float* { return j < q0 ? cache + (size_t)j * p.ld : Qs + (size_t)(j - q0) * p.ld; };
+
+  const int q = t >> 4, d4 = (t & 15) * 4;              // thread (query q, columns d4 .. d4 + 3) of the cross-wave stage
+  if (i0 + q < Tq) {                                    // this tile's rows of q|k|v (head h) into the slot cache
+    const float* src = Qs + (size_t)(i0 + q) * p.ld + hoff + d4;
+    float* dst = cache + (size_t)(q0 + i0 + q) * p.ld + hoff + d4;
+#pragma unroll
+    for (int part = 0; part < 3; ++part)
+      *reinterpret_cast<f32x4*>(dst + part * p.H * DH) = *reinterpret_cast<const f32x4*>(src + part * p.H * DH);
+  }
+  const int ilast = min(i0 + 16, Tq) - 1;
+  int kmax = Tk;
+  if (chunk > 0) kmax = min(kmax, ((ilast + q0) / chunk + 1) * chunk);
+  const int s_eff = (kmax + KT - 1) / KT;
+  const int iq = i0 + r;
+  const bool q_ok = iq < Tq;
+  int lim = Tk;
+  if (chunk > 0) lim = min(lim, ((iq + q0) / chunk + 1) * chunk);
+  if (!q_ok) lim = 0;
+  f32x4 quf[4], qvf[4];
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    const int c = hoff + 16 * kk + 4 * g;
+    f32x4 qv = {0.f, 0.f, 0.f, 0.f};
+    if (q_ok) qv = *reinterpret_cast<const f32x4*>(Qs + (size_t)iq * p.ld + c);
+    const f32x4 bu = *reinterpret_cast<const f32x4*>(p.bias_u + c);
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias_v + c);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { quf[kk][e] = qv[e] + bu[e]; qvf[kk][e] = qv[e] + bv[e]; }
+  }
+  f32x4 ACC = {0.f, 0.f, 0.f, 0.f};
+  float M = -INFINITY, Lsum = 0.f;
+  for (int sp = 0; sp < s_eff; ++sp) {
+    if (sp > 0) __syncthreads();                        // the previous tile's LDS readers are done
+    const int jb = sp * KT + 16 * wave;
+    f32x4 kf[4], pa[4], pb[4];
+    float vv[4][4];
+    const int pbase = jb - (q0 + i0 + 15) + Tk - 1;
+    const int pra = pbase + r, prb = pbase + 16 + r;
+    const bool pa_ok = pra >= 0 && pra < 2 * Tk - 1, pb_ok = r < 15 && prb >= 0 && prb < 2 * Tk - 1;
+    const bool k_ok = jb + r < Tk;
+    const float* kr = krow(k_ok ? jb + r : 0);
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const int c = hoff + 16 * kk + 4 * g;
+      kf[kk] = pa[kk] = pb[kk] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (k_ok) kf[kk] = *reinterpret_cast<const f32x4*>(kr + p.H * DH + c);
+      if (pa_ok) pa[kk] = *reinterpret_cast<const f32x4*>(P + (size_t)pra * p.ldp + c);
+      if (pb_ok) pb[kk] = *reinterpret_cast<const f32x4*>(P + (size_t)prb * p.ldp + c);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int key = jb + 4 * g + e;
+      const float* vr = krow(key < Tk ? key : 0) + 2 * p.H * DH + hoff + r;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) vv[dt][e] = key < Tk ? vr[dt * 16] : 0.f;
+    }
+    f32x4 s = {0.f, 0.f, 0.f, 0.f}, ga = s, gb = s;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        s = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kk][e], quf[kk][e], s, 0, 0, 0);
+        ga = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[kk][e], qvf[kk][e], ga, 0, 0, 0);
+        gb = __builtin_amdgcn_mfma_f32_16x16x4f32(pb[kk][e], qvf[kk][e], gb, 0, 0, 0);
+      }
+    float* Gs = Gs_all + wave * 16 * LDG;
+    *reinterpret_cast<f32x4*>(Gs + r * LDG + 4 * g) = ga;
+    *reinterpret_cast<f32x4*>(Gs + r * LDG + 16 + 4 * g) = gb;
+    const float* gr = Gs + r * LDG + 15 - r + 4 * g;
+    float mw = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int j = jb + 4 * g + e;
+      s[e] = (j < lim) ? (s[e] + gr[e]) * p.scale : -INFINITY;
+      mw = fmaxf(mw, s[e]);
+    }
+    mw = fmaxf(mw, __shfl_xor(mw, 16, 64));
+    mw = fmaxf(mw, __shfl_xor(mw, 32, 64));
+    float pe[4], lw = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { pe[e] = (s[e] > -INFINITY) ? expf(s[e] - mw) : 0.f; lw += pe[e]; }
+    lw += __shfl_xor(lw, 16, 64);
+    lw += __shfl_xor(lw, 32, 64);
+    if (g == 0) { ms[wave][r] = mw; ls[wave][r] = lw; }
+    __syncthreads();
+    {
+      const float mt = fmaxf(fmaxf(ms[0][r], ms[1][r]), fmaxf(ms[2][r], ms[3][r]));
+      const float fw = (mw > -INFINITY) ? expf(mw - mt) : 0.f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) pe[e] *= fw;
+    }
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o = __builtin_amdgcn_mfma_f32_16x16x4f32(pe[e], vv[dt][e], o, 0, 0, 0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) osum[wave][4 * g + e][dt * 16 + r] = o[e];
+    }
+    __syncthreads();
+    f32x4 acc = *reinterpret_cast<const f32x4*>(&osum[0][q][d4]);
+#pragma unroll
+    for (int w2 = 1; w2 < 4; ++w2) {
+      const f32x4 o2 = *reinterpret_cast<const f32x4*>(&osum[w2][q][d4]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] += o2[e];
+    }
+    const float m_t = fmaxf(fmaxf(ms[0][q], ms[1][q]), fmaxf(ms[2][q], ms[3][q]));
+    float l_t = 0.f;
+#pragma unroll
+    for (int w2 = 0; w2 < 4; ++w2) l_t += (ms[w2][q] > -INFINITY) ? ls[w2][q] * expf(ms[w2][q] - m_t) : 0.f;
+    if (sp == 0) {
+      ACC = acc; M = m_t; Lsum = l_t;
+    } else {                                            // merge the tile into the running (max, sum, output)
+      const float mx = fmaxf(M, m_t);
+      const float fa = (M > -INFINITY) ? expf(M - mx) : 0.f, fb = (m_t > -INFINITY) ? expf(m_t - mx) : 0.f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ACC[e] = ACC[e] * fa + acc[e] * fb;
+      Lsum = Lsum * fa + l_t * fb;
+      M = mx;
+    }
+  }
+  if (i0 + q < Tq) {
+    const float inv = 1.0f / Lsum;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ACC[e] *= inv;
+    *reinterpret_cast<f32x4*>(p.O + (size_t)(q_start + i0 + q) * p.ldo + hoff + d4) = ACC;
+  }
+}
+
+int launch_attention_pool(const PoolAttnArgs& a, hipStream_t stream) {
+  if (a.qtiles <= 0) return SS_OK;
+  if (a.nsess <= 0 || !a.sess || !a.qt_pre || !a.P || !a.bias_u || !a.bias_v || a.ld != 3 * a.H * DH || (a.ldo & 3) || (a.ldp & 3) ||
+      a.slot_rows <= 0 || a.p_tmax <= 0)
+    return SS_ERR_ARG;
+  hipLaunchKernelGGL(attention_pool_kernel, dim3(a.qtiles, a.H, 1), dim3(256), 0, stream, a);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
 int launch_attention(const AttnArgs& a, hipStream_t stream) {
   const int tq = a.nseg > 0 ? a.max_q : a.Tq;
   if (tq <= 0 || (a.nseg == 0 && a.Tk <= 0)) return SS_OK;

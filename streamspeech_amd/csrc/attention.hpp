@@ -60,6 +60,23 @@ void attention_debug_q16(int v);       // test hook: 0 = never the few-queries r
 void attention_debug_split(int v);     // test hook: -1 never split, 0 heuristic, n > 0 key tiles per split = n
 
 int launch_attention(const AttnArgs& a, hipStream_t stream);
+
+// Ragged tail-query rel-pos attention of the concurrent streaming step (stream_pool.hip): ONE launch covers the tail rows of every
+// session of the step.  Session z's record sess[8 z] = {q_start, n, r0, T2, slot, chunk, -, -}: its n query rows are rows q_start ..
+// of the stacked q|k|v rows Qs (absolute positions r0 .. T2 - 1), its keys are 0 .. T2 - 1 -- rows below r0 from the slot's cache
+// (cache + slot * slot_rows * ld), the others from Qs -- its rel-pos table is P sliced at p_tmax - T2, chunk > 0 masks key j iff
+// j >= (i / chunk + 1) * chunk.  qt_pre [nsess + 1]: prefix sums of the sessions' 16-query tiles.  Each workgroup also writes its
+// query rows' head slice of q|k|v to the slot cache (rows r0 .. of the slot: nobody in the launch reads them from there).
+struct PoolAttnArgs {
+  const float* Qs = nullptr; float* cache = nullptr; float* O = nullptr;
+  int ld = 0, ldo = 0, slot_rows = 0;      // ld: q|k|v row (3 H 64), shared by Qs and the cache
+  const float* P = nullptr; int ldp = 0, p_tmax = 0;
+  const float* bias_u = nullptr; const float* bias_v = nullptr;
+  const int* sess = nullptr; const int* qt_pre = nullptr;
+  int nsess = 0, qtiles = 0, H = 0;
+  float scale = 1.f;
+};
+int launch_attention_pool(const PoolAttnArgs& a, hipStream_t stream);
 void attention_debug_no_mfma(int v);   // test hook: 1 routes plain attention to the VALU kernel
 
 }  // namespace ss

@@ -59,12 +59,15 @@ __global__ __launch_bounds__(256 * KS) void conv_gemm_kernel(const GemmArgs p) {
   const int wm = wave / WN, wn = wave % WN;
   const int r = lane & 15, g = lane >> 4;
 
-  int out_start = 0, out_len = p.M, in_start = 0, in_len = p.in_len;
+  int out_start = 0, out_len = p.M, in_start = 0, in_len = p.in_len, m_begin = p.m_begin, chunk = p.chunk;
+  const float* A = p.A;
   if (p.nseg > 0) {
     const int* s = p.segs + 4 * blockIdx.z;
     out_start = s[0]; out_len = s[1]; in_start = s[2]; in_len = s[3];
+    if (p.seg_mb) { m_begin = p.seg_mb[2 * blockIdx.z]; chunk = p.seg_mb[2 * blockIdx.z + 1]; }
+    if (p.seg_A) A = p.seg_A[blockIdx.z];
   }
-  const int m0 = blockIdx.x * BM + p.m_begin;
+  const int m0 = blockIdx.x * BM + m_begin;
   if (m0 >= out_len) return;
   const int n0 = blockIdx.y * BN;
   const int kpt = p.Cin / BK;          // k-steps per tap
@@ -81,7 +84,7 @@ __global__ __launch_bounds__(256 * KS) void conv_gemm_kernel(const GemmArgs p) {
     const int m = m0 + row;
     a_ok[i] = (f < A_F4) && (m < out_len);
     a_rin0[i] = m * p.stride - p.pad;
-    a_lim[i] = p.chunk > 0 ? ((m * p.stride) / p.chunk + 1) * p.chunk : 0x7fffffff;
+    a_lim[i] = chunk > 0 ? ((m * p.stride) / chunk + 1) * chunk : 0x7fffffff;
     a_c4[i] = c4 * 4;
     a_lds[i] = row * LDK + c4 * 4;
   }
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(256 * KS) void conv_gemm_kernel(const GemmArgs p) {
       const int rin = a_rin0[i] + tap * p.dil;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (valid && a_ok[i] && rin >= 0 && rin < in_len && rin < a_lim[i])
-        v = *reinterpret_cast<const f32x4*>(p.A + (size_t)(in_start + rin) * p.lda + ci0 + a_c4[i]);
+        v = *reinterpret_cast<const f32x4*>(A + (size_t)(in_start + rin) * p.lda + ci0 + a_c4[i]);
       ra[sl][i] = v;
     }
 #pragma unroll
@@ -1039,6 +1042,10 @@ static int launch_canon(const GemmArgs& a, hipStream_t stream) {
     return launch_smallm<2, 2>(a, stream, PROF_SMALLM_2x2);
   }
   // ---- CANON_SEQ: one accumulator chain per output element ----
+  if (a.seg_mb || a.seg_A) {     // per-segment row starts / inputs: one tile form whatever the rows (a row's bits never depend on them)
+    if (a.nseg <= 0 || a.ln_g) return SS_ERR_ARG;
+    return k32 ? launch_cfg<32, 64, 32, 2, 2, 1, 1, true>(a, stream, PROF_GEMM_32x64x32) : launch_cfg<32, 64, 16, 2, 2, 1, 1, true>(a, stream, PROF_GEMM_32x64x16);
+  }
   if (rtlin_shape_ok(a) && (a.ln_g || rtlin_eligible(a))) return launch_rtlin(a, stream);
   if (a.ln_g) return SS_ERR_ARG;            // LayerNorm prologue: the row-tile kernel only (K = 256); callers normalise first otherwise
   if (rtlin_kb_eligible(a)) return launch_rtlin_kb(a, stream);      // K = 512 ... : row tile through LDS per 256-wide k-block (same bits as the BLK tiles below)
@@ -1083,6 +1090,7 @@ int launch_conv_gemm(const GemmArgs& a_in, hipStream_t stream) {
   const int nseg = a.nseg > 0 ? a.nseg : 1;
   if (a.canon == CANON_NONE) a.canon = t_canon;
   if (a.canon != CANON_NONE && !disp().force_bm) { a.m_begin = 0; return launch_canon(a, stream); }
+  if (a.seg_mb || a.seg_A) return SS_ERR_ARG;      // the CANON_SEQ tile form only
   if (a.m_begin > 0) {       // a row range of a strided conv (ss_encoder_stream_forward): only the LDS-tile kernel starts anywhere but row 0
     if (a.nseg > 0 || a.m_begin >= a.M || a.ln_g || a.ln_out || a.N <= 32) return SS_ERR_ARG;
     const long t = (long)cdiv(a.M - a.m_begin, 32) * cdiv(a.N, 64);

@@ -46,7 +46,12 @@ struct GemmArgs {
   // ragged batch: nseg > 0 -> segs[4*s] = {out_start, out_len, in_start, in_len}; M/in_len ignored
   const int* segs = nullptr;
   int nseg = 0;
-  int max_seg_out = 0;        // max out_len over segments (grid sizing)
+  int max_seg_out = 0;        // max out_len over segments (grid sizing; with seg_mb: max of out_len - seg_mb)
+  // ragged batch of the concurrent streaming step (stream_pool.hip), pack-invariant route only (CANON_SEQ): segment z computes its
+  // output rows [seg_mb[2 z], out_len) -- the m_begin of that segment -- with chunk seg_mb[2 z + 1] (in place of `chunk`), and reads
+  // its input rows from seg_A[z] (in_start relative to it) when seg_A is set
+  const int* seg_mb = nullptr;
+  const float* const* seg_A = nullptr;
   double algo_flops = 0.0;    // algorithmic FLOPs of this launch for the profiler (0 -> 2*M*N*taps*Cin)
   double algo_bytes = 0.0;    // algorithmic bytes of this launch for the profiler (0 -> weights + in + out + residuals once)
   // fused LayerNorm prologue on the A rows (linear layers only: taps == 1, normalised over Cin):

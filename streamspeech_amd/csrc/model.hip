@@ -319,33 +319,7 @@ extern "C" int ss_encoder_forward(ss_model* m, void* stream, const float* d_fban
 // path identical.  Output == ss_encoder_forward on the same fbank up to GEMM summation order
 // (tile / split-K choices depend on the row count).
 //
-// Finality: a frame i of the 40-ms grid reaches, in one layer, keys up to the end of its attention
-// chunk and conv taps up to min(i+15, end of its conv chunk); through the subsampler it reaches
-// conv1 rows a(i) = min(2i+2, chunk end) and fbank rows b(a(i)).  The final prefix [0, n) is the
-// largest one that is closed under "reaches" and whose subsampler inputs all exist.
-static int stream_final_rows(int T, int T1, int T2, int k, int achunk, int cchunk, int dwk, int tail) {
-  if (achunk <= 0) return 0;                       // full attention: every frame sees the future
-  auto reach = [&](int i, int half, int stride) {  // last input row a stride-`stride` conv output i can read
-    int r = i * stride + half;
-    if (cchunk > 0) r = std::min(r, ((i * stride) / cchunk + 1) * cchunk - 1);
-    return r;
-  };
-  int n = 0;
-  for (int i = 0; i < T2; ++i) {                   // subsampler level: frames whose whole cone exists
-    const int a = reach(i, k / 2, 2);
-    if (a > T1 - 1) break;
-    if (reach(a, k / 2, 2) > T - 1 - tail) break;   // the last `tail` fbank frames are not settled yet
-    n = i + 1;
-  }
-  while (n > 0) {                                  // closure under one layer's reach (monotone in i)
-    const int i = n - 1;
-    const int e_att = (i / achunk + 1) * achunk - 1;
-    const int e_conv = reach(i, dwk / 2, 1);
-    if (std::max(e_att, e_conv) <= n - 1) break;
-    --n;
-  }
-  return n;
-}
+// Finality: stream_final_rows (model_internal.hpp).
 
 extern "C" int ss_encoder_stream_reset(ss_model* m) {
   if (!m) return SS_ERR_ARG;

@@ -73,9 +73,9 @@ struct DevBuf {
     std::swap(p, o.p);
     std::swap(bytes, o.bytes);
   }
-  int ensure(size_t need) {
+  int ensure(size_t need, bool exact = false) {      // exact: no growth slack (fixed pieces whose size is known up front)
     if (need <= bytes) return SS_OK;
-    size_t cap = need + std::min(need / 4, (size_t)256 << 20) + 4096;   // growth slack: a quarter, at most 256 MB (a pack's activations run to 12 GB)
+    size_t cap = exact ? need : need + std::min(need / 4, (size_t)256 << 20) + 4096;   // growth slack: a quarter, at most 256 MB (a pack's activations run to 12 GB)
     if (acct && acct->cap) {
       const size_t others = acct->used - bytes;
       if (others + cap > acct->cap) cap = need;                          // no slack under a cap ...
@@ -237,8 +237,13 @@ struct ss_scratch {
     if (es_err_host) (void)hipHostFree(es_err_host);
     sk_workspace_free(skws);
   }
+  // fixed pieces that live outside the set but are booked in it: the slot state of streaming session pools made against this set
+  // (ss_stream_pool_create; they register here and leave with the pool).  Never trimmed.
+  std::vector<DevBuf*> extra;
   std::vector<DevBuf*> all() {
-    return {&ws, &mt_cross, &mt_self, &mt_ws, &attn_split, &mt_gran, &mt_tok, &seg_buf, &bmt_self, &bmb_feat, &bmb_state, &es_qkv, &es_glu, &es_out, &es_step, &v_ws, &v_small, &v_segs};
+    std::vector<DevBuf*> v = {&ws, &mt_cross, &mt_self, &mt_ws, &attn_split, &mt_gran, &mt_tok, &seg_buf, &bmt_self, &bmb_feat, &bmb_state, &es_qkv, &es_glu, &es_out, &es_step, &v_ws, &v_small, &v_segs};
+    v.insert(v.end(), extra.begin(), extra.end());
+    return v;
   }
   // what ss_scratch_trim may let go: buffers every entry point re-sizes before use (the zero-initialised ones and the KV cache stay)
   std::vector<DevBuf*> trimmable() { return {&ws, &mt_cross, &mt_ws, &seg_buf, &bmt_self, &bmb_feat, &bmb_state, &es_qkv, &es_glu, &es_out, &v_ws, &v_small, &v_segs}; }
@@ -294,6 +299,35 @@ struct ss_model {
 }
 
 [[maybe_unused]] static int conv_out_len(int L, int k, int stride) { return (L + 2 * (k / 2) - k) / stride + 1; }
+
+// ---- incremental streaming encoder (ss_encoder_stream_forward, the session pool of stream_pool.hip) ----------------------------
+// Finality: a frame i of the 40-ms grid reaches, in one layer, keys up to the end of its attention
+// chunk and conv taps up to min(i+15, end of its conv chunk); through the subsampler it reaches
+// conv1 rows a(i) = min(2i+2, chunk end) and fbank rows b(a(i)).  The final prefix [0, n) is the
+// largest one that is closed under "reaches" and whose subsampler inputs all exist.
+[[maybe_unused]] static int stream_final_rows(int T, int T1, int T2, int k, int achunk, int cchunk, int dwk, int tail) {
+  if (achunk <= 0) return 0;                       // full attention: every frame sees the future
+  auto reach = [&](int i, int half, int stride) {  // last input row a stride-`stride` conv output i can read
+    int r = i * stride + half;
+    if (cchunk > 0) r = std::min(r, ((i * stride) / cchunk + 1) * cchunk - 1);
+    return r;
+  };
+  int n = 0;
+  for (int i = 0; i < T2; ++i) {                   // subsampler level: frames whose whole cone exists
+    const int a = reach(i, k / 2, 2);
+    if (a > T1 - 1) break;
+    if (reach(a, k / 2, 2) > T - 1 - tail) break;   // the last `tail` fbank frames are not settled yet
+    n = i + 1;
+  }
+  while (n > 0) {                                  // closure under one layer's reach (monotone in i)
+    const int i = n - 1;
+    const int e_att = (i / achunk + 1) * achunk - 1;
+    const int e_conv = reach(i, dwk / 2, 1);
+    if (std::max(e_att, e_conv) <= n - 1) break;
+    --n;
+  }
+  return n;
+}
 
 // ---- transformer layers shared by MT decoder / T2U encoder / unit decoder ----------------------
 // x [n, D] in place.  self K/V cache rows live in `selfbuf` ([*, 3D], row = absolute position).

@@ -383,6 +383,11 @@ class HipModel(BatchMixin):
         self._last_enc = (out.data_ptr(), Tp)
         return out
 
+    def stream_pool(self, max_sessions: int, max_rows: int) -> "StreamPool":
+        """A pool of `max_sessions` streaming-encoder slots of `max_rows` output rows each, booked in this handle's scratch set: one
+        batched encoder step (and one CTC call per head) for many concurrent streams (:class:`StreamPool`)."""
+        return StreamPool(self, max_sessions, max_rows)
+
     # ---- a8 -------------------------------------------------------------------------------
     # Both CTC heads behind ONE host round trip (off unless a caller sets ``ctc_speculate``; the agents do: policy() always asks for the
     # source head and then the target head of the same encoder output -- reference agent :437-452 -- and each answer used to cost a
@@ -518,6 +523,158 @@ class HipModel(BatchMixin):
         c = self.cfg
         L.check(self.lib.ss_row_max_logprob(_stream(), _ptr(logits), U, V, c.pad, c.unk, c.eos, _ptr(out)), "ss_row_max_logprob")
         return out.cpu()
+
+
+def plan_pool_step(T: List[int], n_rows: List[int], max_rows: int) -> dict:
+    """Host-side layout of one batched streaming step (what ss_encoder_stream_forward_batch packs), for checks and tests:
+    per session the output rows T2, their packed offset (call order), the stacked offset of its tail rows among the sessions
+    with rows to compute, and the 16-query tiles.  `n_rows[i]` = rows that session recomputes (T2 minus rows already final).
+    Raises ValueError as the C ABI refuses a call (SS_ERR_ARG): a session past `max_rows` output rows or no input."""
+    T2 = []
+    for t in T:
+        t = int(t)
+        if t <= 0:
+            raise ValueError("a session without fbank frames")
+        t1 = (t + 2 * 2 - 5) // 2 + 1
+        t2 = (t1 + 2 * 2 - 5) // 2 + 1
+        if t2 <= 0 or t2 > max_rows:
+            raise ValueError(f"session of {t2} output rows exceeds the pool's max_rows {max_rows}")
+        T2.append(t2)
+    off, q_start, qtiles, active = [], [], [], []
+    o = q = 0
+    for i, (t2, n) in enumerate(zip(T2, n_rows)):
+        if not 0 <= n <= t2:
+            raise ValueError("rows to compute outside [0, T2]")
+        off.append(o)
+        q_start.append(q)
+        qtiles.append((n + 15) // 16)
+        if n > 0:
+            active.append(i)
+        o += t2
+        q += n
+    return {"T2": T2, "off": off, "total": o, "q_start": q_start, "M": q, "qtiles": qtiles, "active": active}
+
+
+class StreamPool:
+    """Incremental-encoder state of up to `max_sessions` concurrent streams (ss_stream_pool): slot i holds one utterance's
+    per-layer caches, its final output rows and the cached CTC arg-max of those rows.  :meth:`forward` runs ONE encoder step for
+    any subset of slots; per slot it behaves exactly like :meth:`HipModel.encoder_stream_forward` on a context of its own.
+    Driven by one host thread at a time (like a scratch set)."""
+
+    def __init__(self, model: "HipModel", max_sessions: int, max_rows: int):
+        self.lib, self.model, self.device = model.lib, model, _require_gpu(model.device)
+        self.max_sessions, self.max_rows = int(max_sessions), int(max_rows)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(self.lib.ss_stream_pool_create(model.h, self.max_sessions, self.max_rows, C.byref(h)), "ss_stream_pool_create")
+        self.h = h
+        self._last = None          # (slots, T2 list, packed output tensor) of the last forward: what ctc() reads
+
+    def reset(self, slot: int):
+        L.check(self.lib.ss_stream_pool_reset(self.h, int(slot)), "ss_stream_pool_reset")
+
+    def set_tail(self, slot: int, unsettled_fbank_frames: int):
+        L.check(self.lib.ss_stream_pool_set_tail(self.h, int(slot), int(unsettled_fbank_frames)), "ss_stream_pool_set_tail")
+
+    def check_step(self, slots: List[int], fbanks: List[torch.Tensor], attn_chunks: Optional[List[int]] = None,
+                   conv_chunks: Optional[List[int]] = None):
+        """The argument checks of a step, on the host (ValueError), before any device call."""
+        if not slots or len(slots) != len(fbanks):
+            raise ValueError("one fbank per slot, at least one slot")
+        for name, ch in (("attn_chunks", attn_chunks), ("conv_chunks", conv_chunks)):
+            if ch is not None and len(ch) != len(slots):
+                raise ValueError(f"{name}: one entry per slot")
+        if len(set(int(s) for s in slots)) != len(slots):
+            raise ValueError("duplicate slot in one step")
+        for s in slots:
+            if not 0 <= int(s) < self.max_sessions:
+                raise ValueError(f"slot {s} outside [0, {self.max_sessions})")
+        return plan_pool_step([f.shape[0] for f in fbanks], [0] * len(fbanks), self.max_rows)
+
+    def forward(self, slots: List[int], fbanks: List[torch.Tensor], attn_chunks: List[int], conv_chunks: List[int]):
+        """One encoder step of the sessions in `slots` (fbank of ALL their audio so far each).  -> (packed output [sum T2, 256] in
+        call order, per-session views into it, n_final list, n_computed list)."""
+        plan = self.check_step(slots, fbanks, attn_chunks, conv_chunks)
+        n = len(slots)
+        for f in fbanks:
+            if not (f.device == self.device or (f.is_cuda and f.device.index == (self.device.index or 0))):
+                raise ValueError(f"fbank on {f.device}, the pool lives on {self.device}")
+            if f.dtype != torch.float32 or not f.is_contiguous() or f.dim() != 2 or f.shape[1] != self.model.cfg.input_feat:
+                raise ValueError("fbank must be a contiguous float32 [T, 80] tensor")
+        out = torch.empty((plan["total"], self.model.cfg.enc_dim), dtype=torch.float32, device=self.device)
+        nf, nc = (C.c_int32 * n)(), (C.c_int32 * n)()
+        ptrs = (C.c_void_p * n)(*[f.data_ptr() for f in fbanks])
+        L.check(self.lib.ss_encoder_stream_forward_batch(
+            self.model.h, _stream(), self.h, n, _i32(slots), ptrs, _i32([f.shape[0] for f in fbanks]),
+            _i32([min(int(a), 1 << 30) for a in attn_chunks]), _i32([min(int(c), 1 << 30) for c in conv_chunks]),
+            _ptr(out), nf, nc), "ss_encoder_stream_forward_batch")
+        views = [out[o:o + t2] for o, t2 in zip(plan["off"], plan["T2"])]
+        self._last = (list(int(s) for s in slots), plan["T2"], out)     # the tensor itself, not its pointer
+        return out, views, list(nf), list(nc)
+
+    def ctc(self, head: int, slots: Optional[List[int]] = None, enc_packed: Optional[torch.Tensor] = None, return_raw: bool = False):
+        """Greedy CTC of head `head` over the last step's output -> per-session (tokens, frame index) as ctc_greedy gives them
+        (+ the raw per-frame arg-max with return_raw).  Only rows the slots have not seen final yet go through the head."""
+        if self._last is None:
+            raise ValueError("ctc() before any forward()")
+        lslots, T2, lout = self._last
+        if slots is not None and [int(s) for s in slots] != lslots:
+            raise ValueError("ctc() takes the slots of the last forward(), in its order")
+        enc = lout if enc_packed is None else enc_packed
+        if enc.shape[0] != sum(T2):
+            raise ValueError("packed output of another step")
+        n, tot = len(lslots), sum(T2)
+        ibuf = torch.empty((3 * tot + n,), dtype=torch.int32, device=self.device)
+        raw, toks, idx, cnt = ibuf[:tot], ibuf[tot:2 * tot], ibuf[2 * tot:3 * tot], ibuf[3 * tot:]
+        L.check(self.lib.ss_stream_pool_ctc(self.model.h, _stream(), self.h, int(head), n, _i32(lslots), _ptr(enc), _ptr(raw),
+                                            _ptr(toks), _ptr(idx), _ptr(cnt)), "ss_stream_pool_ctc")
+        host = ibuf.cpu().numpy()
+        res, off = [], 0
+        for b in range(n):
+            k = int(host[3 * tot + b])
+            rec = (host[tot + off: tot + off + k].tolist(), host[2 * tot + off: 2 * tot + off + k].tolist())
+            res.append(rec + (host[off: off + T2[b]].tolist(),) if return_raw else rec)
+            off += T2[b]
+        return res
+
+    def ctc_both(self):
+        """Both heads of the last step behind ONE device-to-host copy -> (head-0 results, head-1 results), each as :meth:`ctc`."""
+        if self._last is None:
+            raise ValueError("ctc_both() before any forward()")
+        lslots, T2, enc = self._last
+        n, tot = len(lslots), sum(T2)
+        per = 3 * tot + n
+        ibuf = torch.empty((2 * per,), dtype=torch.int32, device=self.device)
+        for hd in (0, 1):
+            b = ibuf[hd * per:(hd + 1) * per]
+            L.check(self.lib.ss_stream_pool_ctc(self.model.h, _stream(), self.h, hd, n, _i32(lslots), _ptr(enc), _ptr(b[:tot]),
+                                                _ptr(b[tot:2 * tot]), _ptr(b[2 * tot:3 * tot]), _ptr(b[3 * tot:])), "ss_stream_pool_ctc")
+        host = ibuf.cpu().numpy()
+        res = []
+        for hd in (0, 1):
+            h = host[hd * per:(hd + 1) * per]
+            out, off = [], 0
+            for b in range(n):
+                k = int(h[3 * tot + b])
+                out.append((h[tot + off: tot + off + k].tolist(), h[2 * tot + off: 2 * tot + off + k].tolist()))
+                off += T2[b]
+            res.append(out)
+        return res[0], res[1]
+
+    def stats(self) -> Tuple[int, int]:
+        """Test hook: (kernels the pool's calls launched -- its own plus the GEMM-family launches the library's census saw during them --,
+        rows its CTC calls ran through a head) since creation."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        L.check(self.lib.ss_stream_pool_stats(self.h, C.byref(a), C.byref(b)), "ss_stream_pool_stats")
+        return int(a.value), int(b.value)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.lib.ss_stream_pool_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
 
 
 class HipVocoder:

@@ -60,6 +60,15 @@ SIGNATURES = {
     "ss_debug_enc_step_inject_timeout": (_i, [_vp]),
     "ss_encoder_stream_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ss_ctc_greedy": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ss_stream_pool_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    "ss_stream_pool_destroy": (None, [_vp]),
+    "ss_stream_pool_reset": (_i, [_vp, _i]),
+    "ss_stream_pool_set_tail": (_i, [_vp, _i, _i]),
+    "ss_encoder_stream_forward_batch": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32)]),
+    "ss_stream_pool_ctc": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp]),
+    "ss_stream_pool_stats": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "ss_mt_begin": (_i, [_vp, _vp, _vp, _i]),
     "ss_mt_set_persistent": (_i, [_vp, _i]),
     "ss_model_set_pack_invariant": (_i, [_vp, _i]),
