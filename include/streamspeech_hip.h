@@ -372,6 +372,32 @@ int ss_batch_mt_greedy(ss_model* m, void* stream, int B, const float* d_enc_out,
 int ss_batch_mt_beam(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
                      const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens,
                      int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows);
+/* Ragged continuation of B independent beam-1 searches: per row b exactly the semantics of ss_mt_greedy -- feed [</s>, prefix_b...]
+ * (h_prefix: the B prefixes concatenated, h_n_prefix[b] tokens each), then generate; </s> is banned at positions below min_len and
+ * forced at position h_max_len[b].  h_out_tokens [B][out_stride] receives the tokens after the prefix incl. the final </s>, h_n_out[b]
+ * their number; d_feats [B][feat_rows][dec_dim] the decoder states of every fed position, h_n_feats[b] (may be NULL) = n_prefix_b +
+ * n_out_b of them.  Encoder rows packed as in ss_batch_mt_greedy (the session pool's packed output).  The prefixes run as ONE ragged
+ * decoder pass, the generated positions in lock-step; pack-invariant arithmetic: a row's tokens and states do not depend on the rest
+ * of the call.  Checked before anything is launched: B outside [1, 256], n_prefix_b > max_len_b, h_Tp[b] <= 0 or a prefix id outside
+ * the vocabulary -> SS_ERR_ARG; max_len_b + 1 > feat_rows, max_len_b - n_prefix_b + 1 > out_stride or a position past the decoder's
+ * table -> SS_ERR_CAPACITY.  Buffers are booked on the handle's scratch set (SS_ERR_SCRATCH_CAP past a cap, the set stays usable).
+ * Synchronises every few steps and at the end. */
+int ss_batch_mt_continue(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp, const int32_t* h_prefix,
+                         const int32_t* h_n_prefix, const int32_t* h_max_len, int min_len, int32_t* h_out_tokens, int out_stride,
+                         int32_t* h_n_out, float* d_feats, int feat_rows, int32_t* h_n_feats);
+/* Host only: the layout ss_batch_mt_continue makes of such a call, and its refusals (the same codes, same order), with max_tgt_pos /
+ * vocab / eos of the model.  h_dims[4] = {S (longest prefix), Tn (most lock-step steps), Lcap (cache rows per row), Np (prefix-pass
+ * rows)}; h_tables (may be NULL; tables_cap ints) = the int tables the call uploads: max_len' [B], min_len' [B], row position offset
+ * [B], lock-step cross segments [B][4], prefix self segments [B][4], prefix cross segments [B][4], lock-step self segments
+ * [max(Tn,1)][B][4], prefix tokens / positions / cache rows / feature rows [Np] each, last prefix row [B]; *h_n_tables their count. */
+int ss_batch_mt_continue_plan(int B, const int32_t* h_Tp, const int32_t* h_prefix, const int32_t* h_n_prefix, const int32_t* h_max_len,
+                              int min_len, int out_stride, int feat_rows, int max_tgt_pos, int vocab, int eos, int32_t* h_dims,
+                              int32_t* h_tables, int64_t tables_cap, int64_t* h_n_tables);
+/* New fbank rows of B streaming sessions in one launch: session b's frames h_first[b] .. h_first[b] + h_n[b] - 1 of its own 16-kHz
+ * sample history h_pcm[b] (device; frame i reads samples 160 i .. 160 i + 399) go to h_feat[b] (device, h_n[b] rows of 80).  The
+ * same bits as ss_fbank_cmvn's rows.  h_n[b] = 0 skips a session.  1 <= B <= 65535. */
+int ss_batch_fbank_frames(ss_model* m, void* stream, int B, const float* const* h_pcm, const int32_t* h_first, const int32_t* h_n,
+                          float pcm_scale, float* const* h_feat);
 int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float* d_feats, int feat_rows,
                        const int32_t* h_n, int t2u_causal, int mask_eos, int32_t* d_raw, int32_t* d_tokens,
                        int32_t* d_counts);

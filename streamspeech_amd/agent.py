@@ -50,6 +50,25 @@ def synthesize_tail(vocoder, unit, n_new, dur_prediction, ctx=0, rf=None):
     return wav[-int(dur[:, -n_new:].sum()) * 320:], wav
 
 
+def load_dictionaries(args, cfg):
+    """The agents' dictionaries (agent :400-420): target units + the three multitask text dictionaries named by
+    --multitask-config-yaml (placeholders of the model's sizes where none is given)."""
+    d = {"tgt": Dictionary.units(1000)}
+    mt_cfg = {}
+    if args.multitask_config_yaml is not None:
+        mpath = os.path.join(args.data_bin, args.multitask_config_yaml)
+        if os.path.exists(mpath):
+            with open(mpath) as f:
+                mt_cfg = yaml.load(f, Loader=yaml.BaseLoader) or {}
+    for name, n in (("target_unigram", cfg.tgt_vocab), ("source_unigram", cfg.src_vocab),
+                    ("ctc_target_unigram", cfg.tgt_vocab)):
+        path = (mt_cfg.get(name) or {}).get("dict")
+        if path and not os.path.exists(path):
+            path = os.path.join(args.data_bin, *Path(path).parts[-2:])
+        d[name] = Dictionary.load(path) if path and os.path.exists(path) else Dictionary.placeholder(n)
+    return d
+
+
 @entrypoint
 class StreamSpeechS2STAgent(SpeechToSpeechAgent):
     """Simultaneous speech-to-speech translation agent for StreamSpeech on the HIP backend."""
@@ -218,21 +237,7 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
                 eng.encoder_stream_set_tail(unsettled_fbank_frames(int(args.sample_rate), SAMPLE_RATE,
                                                                    int(args.shift_size * SAMPLE_RATE / 1000)))
 
-        # dictionaries: target units + the three multitask text dictionaries
-        self.dict = {"tgt": Dictionary.units(1000)}
-        mt_cfg = {}
-        if args.multitask_config_yaml is not None:
-            mpath = os.path.join(args.data_bin, args.multitask_config_yaml)
-            if os.path.exists(mpath):
-                with open(mpath) as f:
-                    mt_cfg = yaml.load(f, Loader=yaml.BaseLoader) or {}
-        cfg = eng.cfg
-        for name, n in (("target_unigram", cfg.tgt_vocab), ("source_unigram", cfg.src_vocab),
-                        ("ctc_target_unigram", cfg.tgt_vocab)):
-            path = (mt_cfg.get(name) or {}).get("dict")
-            if path and not os.path.exists(path):
-                path = os.path.join(args.data_bin, *Path(path).parts[-2:])
-            self.dict[name] = Dictionary.load(path) if path and os.path.exists(path) else Dictionary.placeholder(n)
+        self.dict = load_dictionaries(args, eng.cfg)
 
     @torch.inference_mode()
     def policy(self):

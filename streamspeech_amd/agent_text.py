@@ -10,6 +10,7 @@ from .agent import StreamSpeechS2STAgent, _detok
 from .frontend import OnlineFeatureExtractor  # noqa: F401  (re-exported for parity with the reference files)
 from .generators import CTCDecoder, SequenceGenerator
 from .simuleval_shim import ReadAction, SpeechToTextAgent, WriteAction, entrypoint
+from .text_policy import s2tt_gate
 
 
 def _add_text_args(parser):
@@ -106,19 +107,13 @@ class StreamSpeechS2TTAgent(_TextAgentBase):
             return WriteAction("", finished=True) if self.states.source_finished else ReadAction()
         src_ctc = self.asr_ctc_generator.generate(enc, aux_task_name="source_unigram")[0][0]["tokens"].int()
         tgt_ctc = self.st_ctc_generator.generate(enc, aux_task_name="ctc_target_unigram")[0][0]["tokens"].int()
-        if not self.states.source_finished:
-            ns, nt = src_ctc.size(-1), tgt_ctc.size(-1)
-            if ns < self.src_ctc_prefix_length + self.stride_n or nt < self.tgt_ctc_prefix_length + self.stride_n:
-                return ReadAction()
-            self.src_ctc_prefix_length = max(ns, self.src_ctc_prefix_length)
-            self.tgt_ctc_prefix_length = max(nt, self.tgt_ctc_prefix_length)
-            subword_tokens = ((nt - self.lagging_k1) // self.stride_n) * self.stride_n
-            new_subword_tokens = (subword_tokens - self.tgt_subwords_indices.size(-1)
-                                  if self.tgt_subwords_indices is not None else subword_tokens)
-            if new_subword_tokens < 1:
-                return ReadAction()
-        else:
-            new_subword_tokens = -1
+        gate = s2tt_gate(src_ctc.size(-1), tgt_ctc.size(-1), self.src_ctc_prefix_length, self.tgt_ctc_prefix_length,
+                         self.tgt_subwords_indices.size(-1) if self.tgt_subwords_indices is not None else 0, self.lagging_k1,
+                         self.stride_n, self.states.source_finished)
+        self.src_ctc_prefix_length, self.tgt_ctc_prefix_length = gate.src_prefix_len, gate.tgt_prefix_len
+        if not gate.write:
+            return ReadAction()
+        new_subword_tokens = gate.new_tokens
         hyp = self.generator_mt.generate_decoder([enc], src_indices, src_lengths, {"id": 1}, self.tgt_subwords_indices,
                                                  None, None, aux_task_name=self.model.mt_task_name,
                                                  max_new_tokens=int(new_subword_tokens))[0][0]

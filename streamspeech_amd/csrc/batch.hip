@@ -319,3 +319,267 @@ extern "C" int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float*
   return launch_ctc_collapse(d_raw, 0, V - 1, c.pad, d_tokens, idx_scratch, d_counts, s, dt + 12 * B, B);
 }
 
+// Ragged continuation of B independent beam-1 searches (ss_batch_mt_continue): row b feeds [</s>, prefix_b...] and generates, with
+// the semantics of ss_mt_greedy per row.  Two phases:
+//  * the prefix pass: ONE ragged decoder pass over the sum(n_prefix_b + 1) fed rows (causal self-attention per segment, cross-attention
+//    per session, CANON_SEQ), its K/V rows scattered into the lock-step cache, only each segment's last row projected onto the vocabulary;
+//  * the lock-step loop: one row per session.  Row b's cache is shifted by sh_b = S - start_b (S = the longest prefix), so every row's
+//    first generated position sits at cache index S + 1 and the QKV rows of a step keep one stride.  Positions, the self-attention key
+//    range and the min / max length tests are per row (position = cache index - sh_b).
+// Host-side layout of one ss_batch_mt_continue call, and every refusal it makes (also exported as ss_batch_mt_continue_plan, which
+// engine.plan_mt_continue reads: the tables below are what the call uploads).  `head` holds, in this order: max_len' [B] | min_len'
+// [B] | row position offset [B] | lock-step cross segs [4B] | prefix self segs [4B] | prefix cross segs [4B] | lock-step self segs
+// [Tr][4B] | prefix tokens [Np] | prefix positions [Np] | prefix row -> cache row [Np] | prefix row -> feature row [Np] | last prefix
+// row of each segment [B].
+struct McPlan {
+  int S = 0, Tn = 0, Lcap = 0, Tr = 0, Np = 0, np_max = 0;   // longest prefix, most lock-step steps, cache rows, lock-step table rows,
+  std::vector<int> head;                                     // prefix-pass rows, longest segment
+};
+static int mt_continue_plan(int B, const int32_t* h_Tp, const int32_t* h_prefix, const int32_t* h_n_prefix, const int32_t* h_max_len,
+                            int min_len, int out_stride, int feat_rows, int max_tgt_pos, int vocab, int eos, McPlan& P) {
+  if (B <= 0 || B > 256 || !h_Tp || !h_n_prefix || !h_max_len) return SS_ERR_ARG;   // (256: the segment tables of the slab kernels)
+  int S = 0, Tn = 0, Np = 0, np_max = 0;
+  for (int b = 0; b < B; ++b) {
+    const int st = h_n_prefix[b];
+    if (h_Tp[b] <= 0 || st < 0 || h_max_len[b] < st) return SS_ERR_ARG;
+    if (st > 0 && !h_prefix) return SS_ERR_ARG;
+    S = std::max(S, st);
+    Tn = std::max(Tn, h_max_len[b] - st);
+    Np += st + 1;
+    np_max = std::max(np_max, st + 1);
+  }
+  {
+    int o = 0;
+    for (int b = 0; b < B; ++b) {
+      for (int i = 0; i < h_n_prefix[b]; ++i)
+        if (h_prefix[o + i] < 0 || h_prefix[o + i] >= vocab) return SS_ERR_ARG;   // nn.Embedding's IndexError in the reference
+      o += h_n_prefix[b];
+    }
+  }
+  for (int b = 0; b < B; ++b)                            // fed positions 0 .. max_len_b; tokens after the prefix up to max_len_b - st + 1
+    if (h_max_len[b] + 1 > feat_rows || h_max_len[b] - h_n_prefix[b] + 1 > out_stride || h_max_len[b] + 3 > max_tgt_pos)
+      return SS_ERR_CAPACITY;
+  const int Lcap = S + 1 + Tn, Tr = std::max(Tn, 1);
+  const Offsets oe = prefix(h_Tp, B);
+  std::vector<int> seg_len(B);
+  for (int b = 0; b < B; ++b) seg_len[b] = h_n_prefix[b] + 1;
+  const Offsets op = prefix(seg_len.data(), B);
+  const size_t np = (size_t)Np;
+  P.S = S; P.Tn = Tn; P.Lcap = Lcap; P.Tr = Tr; P.Np = Np; P.np_max = np_max;
+  P.head.assign(15 * (size_t)B + (size_t)Tr * 4 * B + 4 * np + B, 0);
+  int* ml = P.head.data(); int* mn = ml + B; int* rp = mn + B; int* cs = rp + B; int* ps = cs + 4 * B; int* pc = ps + 4 * B;
+  int* ls = pc + 4 * B; int* pt = ls + (size_t)Tr * 4 * B; int* pp = pt + np; int* pk = pp + np; int* pf = pk + np; int* pl = pf + np;
+  int o = 0;
+  for (int b = 0; b < B; ++b) {
+    const int st = h_n_prefix[b], sh = S - st, r0 = op.off[b];
+    ml[b] = h_max_len[b] + sh; mn[b] = min_len + sh; rp[b] = -sh;
+    cs[4 * b] = b; cs[4 * b + 1] = 1; cs[4 * b + 2] = oe.off[b]; cs[4 * b + 3] = h_Tp[b];
+    ps[4 * b] = r0; ps[4 * b + 1] = st + 1; ps[4 * b + 2] = r0; ps[4 * b + 3] = st + 1;
+    pc[4 * b] = r0; pc[4 * b + 1] = st + 1; pc[4 * b + 2] = oe.off[b]; pc[4 * b + 3] = h_Tp[b];
+    for (int t = 0; t < Tr; ++t) {
+      int* e = &ls[((size_t)t * B + b) * 4];
+      e[0] = b; e[1] = 1; e[2] = b * Lcap + sh; e[3] = st + 2 + t;      // keys: positions 0 .. st + 1 + t
+    }
+    for (int p = 0; p <= st; ++p) {
+      pt[r0 + p] = p == 0 ? eos : h_prefix[o + p - 1];
+      pp[r0 + p] = p;
+      pk[r0 + p] = b * Lcap + sh + p;
+      pf[r0 + p] = b * feat_rows + p;
+    }
+    pl[b] = r0 + st;
+    o += st;
+  }
+  return SS_OK;
+}
+
+extern "C" int ss_batch_mt_continue_plan(int B, const int32_t* h_Tp, const int32_t* h_prefix, const int32_t* h_n_prefix,
+                                         const int32_t* h_max_len, int min_len, int out_stride, int feat_rows, int max_tgt_pos,
+                                         int vocab, int eos, int32_t* h_dims, int32_t* h_tables, int64_t tables_cap,
+                                         int64_t* h_n_tables) {
+  McPlan P;
+  RET(mt_continue_plan(B, h_Tp, h_prefix, h_n_prefix, h_max_len, min_len, out_stride, feat_rows, max_tgt_pos, vocab, eos, P));
+  if (h_dims) { h_dims[0] = P.S; h_dims[1] = P.Tn; h_dims[2] = P.Lcap; h_dims[3] = P.Np; }
+  if (h_n_tables) *h_n_tables = (int64_t)P.head.size();
+  if (h_tables) {
+    if (tables_cap < (int64_t)P.head.size()) return SS_ERR_CAPACITY;
+    std::copy(P.head.begin(), P.head.end(), h_tables);
+  }
+  return SS_OK;
+}
+
+extern "C" int ss_batch_mt_continue(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp,
+                                    const int32_t* h_prefix, const int32_t* h_n_prefix, const int32_t* h_max_len, int min_len,
+                                    int32_t* h_out_tokens, int out_stride, int32_t* h_n_out, float* d_feats, int feat_rows,
+                                    int32_t* h_n_feats) {
+  if (!m || !d_enc_out || !h_out_tokens || !h_n_out || !d_feats) return SS_ERR_ARG;
+  const ss_config& c = m->cfg;
+  const int D = c.dec_dim, F = c.dec_ffn, V = c.tgt_vocab, H = c.dec_heads;
+  McPlan P;
+  RET(mt_continue_plan(B, h_Tp, h_prefix, h_n_prefix, h_max_len, min_len, out_stride, feat_rows, c.max_tgt_pos, V, c.eos, P));
+  const int S = P.S, Tn = P.Tn, Np = P.Np, np_max = P.np_max, Lcap = P.Lcap, Tr = P.Tr;
+  const Offsets oe = prefix(h_Tp, B);
+
+  // ---- every buffer first: a scratch cap refuses the call before anything is queued ----
+  RET(m->sc->mt_cross.ensure((size_t)c.mt_layers * oe.total * 2 * D * sizeof(float)));
+  RET(m->sc->bmt_self.ensure((size_t)c.mt_layers * B * Lcap * 3 * D * sizeof(float)));
+  const size_t np = (size_t)Np;
+  RET(m->sc->ws.ensure((np * (4 * D + 3 * D + F)) * sizeof(float)));
+  RET(m->sc->mt_ws.ensure(((size_t)B * (4 * D + F + V) + (size_t)B * Tr * D) * sizeof(float)));
+  // int tables: tokens [Tn + 2][B] | the plan's tables (mt_continue_plan) | lock-step feature map [B * Tr]
+  const size_t n_tok = (size_t)(Tn + 2) * B;
+  const size_t n_int = n_tok + P.head.size() + (size_t)B * Tr;
+  RET(m->sc->seg_buf.ensure(n_int * sizeof(int)));
+
+  SkScope sk_scope(m->sc->skws);
+  CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
+  hipStream_t s = (hipStream_t)stream;
+  int* tok = (int*)m->sc->seg_buf.p;
+  int* d_maxlen = tok + n_tok;
+  int* d_minlen = d_maxlen + B;
+  int* d_rowpos = d_minlen + B;
+  int* d_cross = d_rowpos + B;
+  int* d_pself = d_cross + 4 * B;
+  int* d_pcross = d_pself + 4 * B;
+  int* d_lself = d_pcross + 4 * B;
+  int* d_ptok = d_lself + (size_t)Tr * 4 * B;
+  int* d_ppos = d_ptok + np;
+  int* d_pcache = d_ppos + np;
+  int* d_pfeat = d_pcache + np;
+  int* d_plast = d_pfeat + np;
+  int* d_lfeat = d_plast + B;
+  RET(upload(s, d_maxlen, P.head));                      // everything from max_len' to the last-row table, one upload
+  const float emb_scale = sqrtf((float)D);
+  // cross-attention K/V of every layer over the packed encoder rows
+  for (int l = 0; l < c.mt_layers; ++l)
+    RET(linear(s, d_enc_out, c.enc_dim, oe.total, m->mt[l].cross_kv, 2 * D, c.enc_dim,
+               m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D, 2 * D));
+  // ---- the prefix pass ----
+  {
+    float* xp = m->sc->ws.f();
+    float* hp = xp + np * D;
+    float* q2p = hp + np * D;
+    float* pfo = q2p + np * D;
+    float* qkvp = pfo + np * D;
+    float* ffp = qkvp + np * 3 * D;
+    RET(launch_embed_tokens_rows(d_ptok, m->mt_emb, m->mt_pos, c.max_tgt_pos, emb_scale, c.pad + 1, d_ppos, xp, Np, D, s, c.pad, V));
+    for (int l = 0; l < c.mt_layers; ++l) {
+      AttnArgs at;
+      at.Q = qkvp; at.ldq = 3 * D; at.K = qkvp + D; at.V = qkvp + 2 * D; at.ldk = at.ldv = 3 * D;
+      at.O = hp; at.ldo = D; at.H = H; at.scale = 1.f; at.causal = 1;
+      at.segs = d_pself; at.nseg = B; at.max_q = np_max; at.no_decode_kernel = m->pack_invariant;   // max_q depends on the pack
+      AttnArgs ac;
+      ac.Q = q2p; ac.ldq = D; ac.K = m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D; ac.V = ac.K + D; ac.ldk = ac.ldv = 2 * D;
+      ac.O = hp; ac.ldo = D; ac.H = H; ac.scale = 1.f; ac.segs = d_pcross; ac.nseg = B; ac.max_q = np_max;
+      ac.no_decode_kernel = m->pack_invariant;
+      RET(dec_layer_ex(s, c, m->mt[l], xp, Np, qkvp, 3 * D, at, &ac, hp, q2p, ffp));
+      RET(launch_scatter_rows(d_pcache, qkvp, 3 * D, m->sc->bmt_self.f() + (size_t)l * B * Lcap * 3 * D, 3 * D, 3 * D, Np,
+                              B * Lcap, s));
+    }
+    RET(launch_layernorm(xp, D, pfo, D, m->mt_ln.g, m->mt_ln.b, Np, D, 1e-5f, s));
+    RET(launch_scatter_rows(d_pfeat, pfo, D, d_feats, D, D, Np, B * feat_rows, s));
+    RET(launch_gather_rows(d_plast, pfo, D, hp, B, s, Np));
+    // the first generated token: projected as a lock-step row (one row per session, CANON_SMALLM)
+    CanonScope row_scope(m->pack_invariant ? CANON_SMALLM : CANON_NONE);
+    float* logits = m->sc->mt_ws.f() + (size_t)B * (4 * D + F);
+    Lin proj{m->mt_emb, nullptr};
+    RET(linear(s, hp, D, B, proj, V, D, logits, V));
+    RET(launch_masked_argmax(logits, V, B, V, c.pad, -1, -1, -1, tok + B, s, d_maxlen, S, c.eos, d_minlen, c.eos));
+  }
+  // ---- the lock-step loop ----
+  float* x = m->sc->mt_ws.f();
+  float* h = x + (size_t)B * D;
+  float* q2 = h + (size_t)B * D;
+  float* ff = q2 + (size_t)B * D;
+  float* logits = ff + (size_t)B * F + (size_t)B * D;
+  float* lfeat = logits + (size_t)B * V;                             // [B][Tr][D]: the decode rows' states, scattered at the end
+  std::vector<int> host_tok(n_tok, c.pad);
+  std::vector<int> eos_at(B, -1);
+  int checked = 1;                                                   // token rows [1, checked) already on the host
+  constexpr int kCheck = 4;
+  CanonScope decode_scope(m->pack_invariant ? CANON_SMALLM : CANON_NONE);
+  for (int it = 0;; ++it) {                                          // `it` steps done: token rows 1 .. it + 1 exist
+    const bool last = it >= Tn;
+    if (last || it % kCheck == 0) {
+      SS_HIP_CHECK(hipMemcpyAsync(host_tok.data() + (size_t)checked * B, tok + (size_t)checked * B,
+                                  (size_t)(it + 2 - checked) * B * sizeof(int), hipMemcpyDeviceToHost, s));
+      SS_HIP_CHECK(hipStreamSynchronize(s));
+      bool all_done = true;
+      for (int b = 0; b < B; ++b) {
+        const int lim = h_max_len[b] - h_n_prefix[b] + 1;           // token row forced to </s>
+        for (int r = checked; r <= std::min(it + 1, lim) && eos_at[b] < 0; ++r)
+          if (host_tok[(size_t)r * B + b] == c.eos) eos_at[b] = r;
+        if (eos_at[b] < 0) all_done = false;
+      }
+      checked = it + 2;
+      if (all_done || last) break;
+    }
+    const int ci = S + 1 + it;                                       // cache index fed by every row
+    RET(launch_embed_tokens_rows(tok + (size_t)(it + 1) * B, m->mt_emb, m->mt_pos, c.max_tgt_pos, emb_scale, ci + c.pad + 1, d_rowpos,
+                                 x, B, D, s, c.pad, V));
+    for (int l = 0; l < c.mt_layers; ++l) {
+      float* cache = m->sc->bmt_self.f() + (size_t)l * B * Lcap * 3 * D;
+      float* rows = cache + (size_t)ci * 3 * D;                      // row b at + b*Lcap*3D
+      AttnArgs at;
+      at.Q = rows; at.ldq = Lcap * 3 * D; at.K = cache + D; at.V = cache + 2 * D; at.ldk = at.ldv = 3 * D;
+      at.O = h; at.ldo = D; at.H = H; at.scale = 1.f; at.causal = 0;   // the key range holds exactly the visible keys
+      at.segs = d_lself + (size_t)it * 4 * B; at.nseg = B; at.max_q = 1;
+      AttnArgs ac;
+      ac.Q = q2; ac.ldq = D; ac.K = m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D; ac.V = ac.K + D; ac.ldk = ac.ldv = 2 * D;
+      ac.O = h; ac.ldo = D; ac.H = H; ac.scale = 1.f; ac.segs = d_cross; ac.nseg = B; ac.max_q = 1;
+      RET(dec_layer_ex(s, c, m->mt[l], x, B, rows, Lcap * 3 * D, at, &ac, h, q2, ff));
+    }
+    float* frow = lfeat + (size_t)it * D;
+    RET(launch_layernorm(x, D, frow, Tr * D, m->mt_ln.g, m->mt_ln.b, B, D, 1e-5f, s));
+    Lin proj{m->mt_emb, nullptr};
+    RET(linear(s, frow, Tr * D, B, proj, V, D, logits, V));
+    RET(launch_masked_argmax(logits, V, B, V, c.pad, -1, -1, -1, tok + (size_t)(it + 2) * B, s, d_maxlen, ci, c.eos, d_minlen, c.eos));
+  }
+  // outputs; the decode rows' states go to their positions start_b + 1 .. in d_feats (one launch)
+  std::vector<int> fmap((size_t)B * Tr, -1);
+  int n_lfeat = 0;
+  for (int b = 0; b < B; ++b) {
+    const int st = h_n_prefix[b], end = eos_at[b];                   // token rows 1 .. end are the output
+    h_n_out[b] = end;
+    for (int r = 1; r <= end; ++r) h_out_tokens[(size_t)b * out_stride + (r - 1)] = host_tok[(size_t)r * B + b];
+    if (h_n_feats) h_n_feats[b] = st + end;                          // fed positions 0 .. st + end - 1
+    for (int t = 0; t < end - 1; ++t) fmap[(size_t)b * Tr + t] = b * feat_rows + st + 1 + t;
+    n_lfeat += end - 1;
+  }
+  if (n_lfeat > 0) {
+    RET(upload(s, d_lfeat, fmap));
+    RET(launch_scatter_rows(d_lfeat, lfeat, D, d_feats, D, D, B * Tr, B * feat_rows, s));
+  }
+  return SS_OK;
+}
+
+// New fbank rows of many streaming sessions in ONE launch (the batched front-end of the text session pool): session b's frames
+// h_first[b] .. h_first[b] + h_n[b] - 1 of its own 16-kHz sample history h_pcm[b] go to h_feat[b] (h_n[b] rows of 80).  The kernel of
+// ss_fbank_cmvn with a segment table: a row is a function of its own 400 samples, so the rows are the same bits as there.
+extern "C" int ss_batch_fbank_frames(ss_model* m, void* stream, int B, const float* const* h_pcm, const int32_t* h_first,
+                                     const int32_t* h_n, float pcm_scale, float* const* h_feat) {
+  if (!m || B <= 0 || B > 65535 || !h_pcm || !h_first || !h_n || !h_feat) return SS_ERR_ARG;   // (B is the grid's y extent)
+  constexpr int kShift = 160;
+  int mx = 0;
+  for (int b = 0; b < B; ++b) {
+    if (h_first[b] < 0 || h_n[b] < 0 || ((int64_t)h_first[b] + (int64_t)h_n[b]) * kShift > (int64_t)0x7fffffff) return SS_ERR_ARG;
+    if (h_n[b] > 0 && (!h_pcm[b] || !h_feat[b])) return SS_ERR_ARG;
+    mx = std::max(mx, h_n[b]);
+  }
+  if (mx == 0) return SS_OK;
+  hipStream_t s = (hipStream_t)stream;
+  // table: segs {pcm_start, n, 0} [3B], padded to 8 bytes, then the pcm and feature pointers [B] each
+  const size_t n_seg = (3 * (size_t)B + 1) & ~(size_t)1;
+  std::vector<int> tab(n_seg + 4 * (size_t)B, 0);
+  int64_t* ptrs = reinterpret_cast<int64_t*>(tab.data() + n_seg);
+  for (int b = 0; b < B; ++b) {
+    tab[3 * b] = h_first[b] * kShift; tab[3 * b + 1] = h_n[b]; tab[3 * b + 2] = 0;
+    ptrs[b] = (int64_t)(uintptr_t)h_pcm[b];
+    ptrs[B + b] = (int64_t)(uintptr_t)h_feat[b];
+  }
+  RET(m->sc->seg_buf.ensure(tab.size() * sizeof(int)));
+  int* dt = (int*)m->sc->seg_buf.p;
+  RET(upload(s, dt, tab));
+  const float* const* d_pcm = reinterpret_cast<const float* const*>(dt + n_seg);
+  float* const* d_feat = reinterpret_cast<float* const*>(dt + n_seg + 2 * (size_t)B);
+  return launch_fbank_cmvn_ptrs(d_pcm, d_feat, pcm_scale, m->fe_window, m->fe_melw, m->fe_mean, m->fe_std, dt, B, mx, s);
+}

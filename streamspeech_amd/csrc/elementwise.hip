@@ -145,14 +145,16 @@ int launch_dwconv_bn_silu(const float* x, int ldx, float* y, int ldy, const floa
 // ---------------------------------------------------------------------------------------------
 __global__ void embed_tokens_kernel(const int* __restrict__ tok, const float* __restrict__ emb,
                                     const float* __restrict__ pos_table, float scale, int pos0, float* out,
-                                    int n, int D, int pos_stride, int pad_id, int vocab) {
+                                    int n, int D, int pos_stride, int pad_id, int vocab, const int* __restrict__ row_pos,
+                                    int pos_rows) {
   const int i = blockIdx.y;
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= D) return;
   int tk = tok[i];
   if ((unsigned)tk >= (unsigned)vocab) tk = 0;            // ids come from device memory (the token chain): never index out of the table
   // make_positions (fairseq/utils.py:256-266): a <pad> token takes position padding_idx (the zero row)
-  const int pos = (tk == pad_id) ? pad_id : pos0 + i * pos_stride;
+  int pos = (tk == pad_id) ? pad_id : pos0 + (row_pos ? row_pos[i] : i * pos_stride);
+  if (row_pos && (unsigned)pos >= (unsigned)pos_rows) pos = pos_rows - 1;   // per-row form: a row past its search reads the last row
   out[(size_t)i * D + c] = scale * emb[(size_t)tk * D + c] + pos_table[(size_t)pos * D + c];
 }
 
@@ -160,7 +162,17 @@ int launch_embed_tokens(const int* tok, const float* emb, const float* pos_table
                         float* out, int n, int D, hipStream_t stream, int pos_stride, int pad_id, int vocab) {
   if (n <= 0) return SS_OK;
   hipLaunchKernelGGL(embed_tokens_kernel, dim3(cdiv(D, 256), n), dim3(256), 0, stream, tok, emb, pos_table,
-                     scale, pos0, out, n, D, pos_stride, pad_id, vocab);
+                     scale, pos0, out, n, D, pos_stride, pad_id, vocab, (const int*)nullptr, 0);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+int launch_embed_tokens_rows(const int* tok, const float* emb, const float* pos_table, int pos_rows, float scale, int pos0,
+                             const int* row_pos, float* out, int n, int D, hipStream_t stream, int pad_id, int vocab) {
+  if (n <= 0) return SS_OK;
+  if (pos_rows <= 0) return SS_ERR_ARG;
+  hipLaunchKernelGGL(embed_tokens_kernel, dim3(cdiv(D, 256), n), dim3(256), 0, stream, tok, emb, pos_table,
+                     scale, pos0, out, n, D, 0, pad_id, vocab, row_pos, pos_rows);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }
@@ -201,6 +213,23 @@ int launch_gather_rows(const int* idx, const float* table, int D, float* out, in
   return SS_OK;
 }
 
+__global__ void scatter_rows_kernel(const int* __restrict__ dst_row, const float* __restrict__ src, int lds, float* dst, int ldd,
+                                    int D, int dst_rows) {
+  const int i = blockIdx.y;
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  const int r = dst_row[i];
+  if (c >= D || (unsigned)r >= (unsigned)dst_rows) return;    // rows outside the destination are dropped, never written
+  dst[(size_t)r * ldd + c] = src[(size_t)i * lds + c];
+}
+
+int launch_scatter_rows(const int* dst_row, const float* src, int lds, float* dst, int ldd, int D, int n, int dst_rows,
+                        hipStream_t stream) {
+  if (n <= 0) return SS_OK;
+  hipLaunchKernelGGL(scatter_rows_kernel, dim3(cdiv(D, 256), n), dim3(256), 0, stream, dst_row, src, lds, dst, ldd, D, dst_rows);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Masked argmax over a row (CTC heads, unit head, MT next-token).  log_softmax is monotone, so the
 // reference's log_softmax -> set -inf -> max (agent/ctc_decoder.py:52-60) equals an argmax of the
@@ -208,13 +237,15 @@ int launch_gather_rows(const int* idx, const float* table, int D, float* out, in
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void masked_argmax_kernel(const float* __restrict__ logits, int ld, int M, int N,
                                                             int mask0, int mask1, int mask2, int force, int* ids,
-                                                            const int* __restrict__ row_max_len, int step, int force_id) {
+                                                            const int* __restrict__ row_max_len, int step, int force_id,
+                                                            const int* __restrict__ row_min_len, int ban_id) {
   // one workgroup per row: 256 threads stride over the vocabulary, wave shuffle + LDS reduce
   __shared__ float sb[4];
   __shared__ int si[4];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int row = blockIdx.x;
   if (row_max_len && step >= row_max_len[row]) force = force_id;   // batched search: per-utterance max length
+  if (row_min_len && step < row_min_len[row]) mask1 = ban_id;      // ... and per-utterance min length (ban_id replaces mask1)
   if (force >= 0) { if (t == 0) ids[row] = force; return; }
   const float* r = logits + (size_t)row * ld;
   float best = -INFINITY;
@@ -244,10 +275,11 @@ __global__ __launch_bounds__(256) void masked_argmax_kernel(const float* __restr
 }
 
 int launch_masked_argmax(const float* logits, int ld, int M, int N, int mask0, int mask1, int mask2,
-                         int force, int* ids, hipStream_t stream, const int* row_max_len, int step, int force_id) {
+                         int force, int* ids, hipStream_t stream, const int* row_max_len, int step, int force_id,
+                         const int* row_min_len, int ban_id) {
   if (M <= 0) return SS_OK;
   hipLaunchKernelGGL(masked_argmax_kernel, dim3(M), dim3(256), 0, stream, logits, ld, M, N, mask0,
-                     mask1, mask2, force, ids, row_max_len, step, force_id);
+                     mask1, mask2, force, ids, row_max_len, step, force_id, row_min_len, ban_id);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }

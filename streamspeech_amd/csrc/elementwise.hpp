@@ -25,6 +25,10 @@ int launch_dwconv_bn_silu(const float* x, int ldx, float* y, int ldy, const floa
 int launch_embed_tokens(const int* tok, const float* emb, const float* pos_table, float scale, int pos0,
                         float* out, int n, int D, hipStream_t stream, int pos_stride, int pad_id, int vocab);
 // pos_stride 0: same position for all rows; pad_id: token that takes position pad_id (-1: none); ids outside [0, vocab) read row 0
+// Per-row positions: row i takes position pos0 + row_pos[i] (device array; the ragged lock-step search of ss_batch_mt_continue),
+// clamped to the pos_rows rows of the table (a row whose search is over keeps being fed and must not read past it)
+int launch_embed_tokens_rows(const int* tok, const float* emb, const float* pos_table, int pos_rows, float scale, int pos0,
+                             const int* row_pos, float* out, int n, int D, hipStream_t stream, int pad_id, int vocab);
 
 // out[u,:] = src[u/up,:] + (src[u/up,0] != pad_value ? pos_row : 0)   (CTC unit decoder input,
 // reference ctc_unity/modules/ctc_transformer_unit_decoder.py:153-181)
@@ -35,7 +39,8 @@ int launch_upsample_add_pos(const float* src, int n, int up, const float* pos_ro
 // if force >= 0 the result is `force` (beam-search max-length rule).  Optionally max value out.
 int launch_masked_argmax(const float* logits, int ld, int M, int N, int mask0, int mask1, int mask2,
                          int force, int* ids, hipStream_t stream, const int* row_max_len = nullptr, int step = 0,
-                         int force_id = -1);  // row_max_len: force `force_id` on rows with step >= row_max_len[row]
+                         int force_id = -1,   // row_max_len: force `force_id` on rows with step >= row_max_len[row]
+                         const int* row_min_len = nullptr, int ban_id = -1);   // row_min_len: mask1 = ban_id on rows with step < row_min_len[row]
 
 // out[m] = max_{n not in masks} log_softmax(logits[m,:])[n]   (researches/ctc_unity/ctc_generator.py:55-63)
 int launch_log_softmax(const float* logits, int ld, int M, int N, int mask0, int mask1, int as_probs, float* out, int ldo,
@@ -50,6 +55,9 @@ int launch_ctc_collapse(const int* raw, int T, int blank, int pad, int* tokens, 
 
 // emb_out[k,:] = table[codes[k],:]
 int launch_gather_rows(const int* idx, const float* table, int D, float* out, int n, hipStream_t stream, int rows);  // ids outside [0, rows) read row 0
+// dst[dst_row[k] * ldd + c] = src[k * lds + c] for c < D; rows outside [0, dst_rows) are skipped
+int launch_scatter_rows(const int* dst_row, const float* src, int lds, float* dst, int ldd, int D, int n, int dst_rows,
+                        hipStream_t stream);
 
 // dur[k] = clamp(round_half_even(exp(logdur[k]) - 1), min 1)   (reference agent/tts/codehifigan.py:61-64);
 // forced != null overrides the prediction.  cum[0..K] = exclusive prefix sum (cum[K] = total frames).

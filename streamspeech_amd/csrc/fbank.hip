@@ -16,7 +16,9 @@ __global__ __launch_bounds__(256) void fbank_cmvn_kernel(const float* __restrict
                                                          const float* __restrict__ melw,     // [80][257]
                                                          const float* __restrict__ cmvn_mean,
                                                          const float* __restrict__ cmvn_std, float* feat,
-                                                         const int* __restrict__ segs) {
+                                                         const int* __restrict__ segs,
+                                                         const float* const* __restrict__ pcm_ptrs,
+                                                         float* const* __restrict__ feat_ptrs) {
   __shared__ float re[NFFT], im[NFFT];
   __shared__ float tw_c[NFFT / 2], tw_s[NFFT / 2];
   __shared__ float red[4];
@@ -25,6 +27,7 @@ __global__ __launch_bounds__(256) void fbank_cmvn_kernel(const float* __restrict
   if (segs) {   // ragged batch {pcm_start, n_frames, frame_start}; whole workgroup exits together
     const int* sg = segs + 3 * blockIdx.y;
     if (frame >= sg[1]) return;
+    if (pcm_ptrs) { pcm = pcm_ptrs[blockIdx.y]; feat = feat_ptrs[blockIdx.y]; }   // per-segment buffers (launch_fbank_cmvn_ptrs)
     pcm += sg[0]; feat += (size_t)sg[2] * NMEL;
   }
   const float* src = pcm + (size_t)frame * SHIFT;
@@ -96,7 +99,7 @@ int launch_fbank_cmvn(const float* pcm, int n_samples, float pcm_scale, const fl
   if (n_frames) *n_frames = T;
   if (T == 0) return SS_OK;
   hipLaunchKernelGGL(fbank_cmvn_kernel, dim3(T), dim3(256), 0, stream, pcm, pcm_scale, window, melw,
-                     cmvn_mean, cmvn_std, feat, (const int*)nullptr);
+                     cmvn_mean, cmvn_std, feat, (const int*)nullptr, (const float* const*)nullptr, (float* const*)nullptr);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }
@@ -106,7 +109,17 @@ int launch_fbank_cmvn_batch(const float* pcm, float pcm_scale, const float* wind
                             int max_frames, hipStream_t stream) {
   if (nseg <= 0 || max_frames <= 0) return SS_OK;
   hipLaunchKernelGGL(fbank_cmvn_kernel, dim3(max_frames, nseg), dim3(256), 0, stream, pcm, pcm_scale, window, melw,
-                     cmvn_mean, cmvn_std, feat, segs);
+                     cmvn_mean, cmvn_std, feat, segs, (const float* const*)nullptr, (float* const*)nullptr);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+int launch_fbank_cmvn_ptrs(const float* const* pcm_ptrs, float* const* feat_ptrs, float pcm_scale, const float* window,
+                           const float* melw, const float* cmvn_mean, const float* cmvn_std, const int* segs, int nseg,
+                           int max_frames, hipStream_t stream) {
+  if (nseg <= 0 || max_frames <= 0) return SS_OK;
+  hipLaunchKernelGGL(fbank_cmvn_kernel, dim3(max_frames, nseg), dim3(256), 0, stream, (const float*)nullptr, pcm_scale, window, melw,
+                     cmvn_mean, cmvn_std, (float*)nullptr, segs, pcm_ptrs, feat_ptrs);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }

@@ -106,6 +106,41 @@ class BatchMixin:
         toks = [list(out[b * stride: b * stride + n_out[b]]) for b in range(B)]
         return toks, feats, list(n_out)
 
+    def batch_mt_continue(self, enc_packed: torch.Tensor, Tp: List[int], prefixes: List[List[int]], max_len: List[int],
+                          min_len: int = 1) -> List[Tuple[List[int], torch.Tensor]]:
+        """B independent greedy continuations in one call (ss_batch_mt_continue): row b feeds [</s>, prefixes[b]...] over its
+        encoder rows (packed as batch_mt_greedy takes them) and generates up to position max_len[b].  -> per row (tokens after the
+        prefix incl. the final eos, decoder states [n_prefix + n_out, D] of the fed positions), as :meth:`HipModel.mt_greedy`."""
+        B = len(Tp)
+        if not (len(prefixes) == len(max_len) == B):
+            raise ValueError("one prefix and one max_len per row")
+        plan = plan_mt_continue(Tp, [len(p) for p in prefixes], max_len, min_len, max_tgt_pos=self.max_tgt_pos,
+                                prefix_ids=[int(t) for p in prefixes for t in p], vocab=self.cfg.tgt_vocab, eos=self.cfg.eos)
+        rows, stride = plan["feat_rows"], plan["out_stride"]
+        feats = torch.empty((B, rows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
+        flat = [int(t) for p in prefixes for t in p]
+        out = (C.c_int32 * (B * stride))()
+        n_out, n_feats = (C.c_int32 * B)(), (C.c_int32 * B)()
+        L.check(self.lib.ss_batch_mt_continue(self.h, _stream(), B, _ptr(enc_packed), _i32(Tp), _i32(flat or [0]),
+                                              _i32([len(p) for p in prefixes]), _i32(max_len), int(min_len), out, stride, n_out,
+                                              _ptr(feats), rows, n_feats), "ss_batch_mt_continue")
+        return [(list(out[b * stride: b * stride + n_out[b]]), feats[b, :n_feats[b]]) for b in range(B)]
+
+    def batch_fbank_frames(self, histories: List[torch.Tensor], first: List[int], counts: List[int], outs: List[torch.Tensor],
+                           pcm_scale: float = 32768.0):
+        """New fbank rows of many 16-kHz streams in one launch (ss_batch_fbank_frames): rows first[i] .. first[i] + counts[i] - 1 of
+        the sample history histories[i] (device) into outs[i] ([counts[i], 80] contiguous, device)."""
+        B = len(histories)
+        if not (len(first) == len(counts) == len(outs) == B) or B == 0:
+            raise ValueError("one history, first frame, count and output per session")
+        for h, f, n, o in zip(histories, first, counts, outs):
+            if n and (h.numel() < (int(f) + int(n) - 1) * 160 + 400 or tuple(o.shape) != (int(n), 80) or not o.is_contiguous()):
+                raise ValueError("history shorter than the frames asked for, or a wrong output view")
+        pp = (C.c_void_p * B)(*[h.data_ptr() for h in histories])
+        fp = (C.c_void_p * B)(*[o.data_ptr() if n else 0 for o, n in zip(outs, counts)])
+        L.check(self.lib.ss_batch_fbank_frames(self.h, _stream(), B, pp, _i32(first), _i32(counts), pcm_scale, fp),
+                "ss_batch_fbank_frames")
+
     def batch_mt_beam(self, enc_packed: torch.Tensor, Tp: List[int], max_len: List[int], beam: int, min_len: int = 1,
                       unk_penalty: float = 0.0, normalize: bool = True):
         """Beam search of the first-pass text decoder (ss_batch_mt_beam) -> (n-best lists, feats [B, Lcap, D], n_feats list).
@@ -523,6 +558,60 @@ class HipModel(BatchMixin):
         c = self.cfg
         L.check(self.lib.ss_row_max_logprob(_stream(), _ptr(logits), U, V, c.pad, c.unk, c.eos, _ptr(out)), "ss_row_max_logprob")
         return out.cpu()
+
+
+class ContinueRefused(ValueError):
+    """A call ss_batch_mt_continue refuses; ``code`` is the SS_ERR_* it returns for it."""
+
+    def __init__(self, msg, code):
+        super().__init__(msg)
+        self.code = code
+
+
+def plan_mt_continue(Tp: List[int], n_prefix: List[int], max_len: List[int], min_len: int = 1, feat_rows: Optional[int] = None,
+                     out_stride: Optional[int] = None, max_tgt_pos: int = 1026, prefix_ids: Optional[List[int]] = None,
+                     vocab: int = 6000, eos: int = 2) -> dict:
+    """Layout and refusals of one ss_batch_mt_continue call, as the library makes them (ss_batch_mt_continue_plan, host only -- the
+    same planner the call runs): S = the longest prefix, Tn = the most lock-step steps a row may need, Lcap = S + 1 + Tn cache rows per
+    row (row b shifted by shift[b] = S - n_prefix[b], so every row's first generated position sits at cache index S + 1), and the
+    tables the call uploads.  feat_rows / out_stride default to the least the call needs.  Raises ContinueRefused with the code the
+    call returns."""
+    B = len(Tp)
+    if len(n_prefix) != B or len(max_len) != B:
+        raise ContinueRefused("one prefix length and max_len per row", L.SS_ERR_ARG)
+    if B and feat_rows is None:
+        feat_rows = max(m + 1 for m in max_len)
+    if B and out_stride is None:
+        out_stride = max(m - n + 1 for m, n in zip(max_len, n_prefix))
+    ids = list(prefix_ids) if prefix_ids is not None else [4] * sum(max(int(n), 0) for n in n_prefix)
+    lib = L.load()
+    dims, n_tab = (C.c_int32 * 4)(), C.c_int64(0)
+    args = (B, _i32(Tp or [0]), _i32(ids or [0]), _i32(n_prefix or [0]), _i32(max_len or [0]), int(min_len), int(out_stride or 0),
+            int(feat_rows or 0), int(max_tgt_pos), int(vocab), int(eos))
+    rc = lib.ss_batch_mt_continue_plan(*args, dims, None, 0, C.byref(n_tab))
+    if rc != 0:
+        raise ContinueRefused(f"ss_batch_mt_continue refuses the call: {lib.ss_error_string(rc).decode()}", rc)
+    tab = (C.c_int32 * n_tab.value)()
+    L.check(lib.ss_batch_mt_continue_plan(*args, dims, tab, n_tab.value, C.byref(n_tab)), "ss_batch_mt_continue_plan")
+    S, Tn, Lcap, Np = list(dims)
+    t, Tr, o = list(tab), max(Tn, 1), 0
+
+    def take(n):
+        nonlocal o
+        o += n
+        return t[o - n:o]
+    quads = lambda v: [tuple(v[4 * i:4 * i + 4]) for i in range(len(v) // 4)]    # noqa: E731
+    p = {"S": S, "Tn": Tn, "Lcap": Lcap, "Np": Np, "feat_rows": feat_rows, "out_stride": out_stride}
+    p["max_len_at"], p["min_len_at"] = take(B), take(B)
+    p["shift"] = [-x for x in take(B)]
+    p["step_cross"], p["prefix_self"], p["prefix_cross"] = quads(take(4 * B)), quads(take(4 * B)), quads(take(4 * B))
+    steps = quads(take(4 * B * Tr))
+    p["step_self"] = [steps[k * B:(k + 1) * B] for k in range(Tr)]
+    p["prefix_tokens"], p["prefix_pos"], p["cache_row"], p["feat_row"] = take(Np), take(Np), take(Np), take(Np)
+    p["last_row"] = take(B)
+    p["r0"] = [seg[0] for seg in p["prefix_self"]]
+    assert o == len(t)
+    return p
 
 
 def plan_pool_step(T: List[int], n_rows: List[int], max_rows: int) -> dict:

@@ -166,13 +166,15 @@ class OnlineFeatureExtractor:
             self._np = c
         return c[:n]
 
-    def __call__(self, new_samples, sr=None):
-        sr = sr or self.sample_rate
+    def stage(self, new_samples):
+        """The host part of a call: frames of the history so far, and its new samples copied to the device history.  -> (num_frames,
+        effective samples), or None when no frame exists yet.  (The text session pool stages many sessions and computes their new
+        fbank rows in one launch: new_rows / commit_rows.)"""
         samples = new_samples
         num_frames = math.floor(
             (len(samples) - self.len_ms_to_samples(self.window_size - self.shift_size)) / self.num_samples_per_shift)
         if num_frames <= 0:
-            return torch.empty((0, self.feature_dim), device=self.engine.device)
+            return None
         effective = int(num_frames * self.len_ms_to_samples(self.shift_size)
                         + self.len_ms_to_samples(self.window_size - self.shift_size))
         x = self._samples(samples, effective)
@@ -190,6 +192,31 @@ class OnlineFeatureExtractor:
         if effective > self._n_dev:
             self._dev[self._n_dev:effective] = torch.from_numpy(x[self._n_dev:effective]).to(dev)
             self._n_dev = effective
+        return int(num_frames), effective
+
+    def new_rows(self, nf: int) -> int:
+        """16-kHz sources on the HIP engine: the first of the `nf` fbank rows that is not cached yet (the row buffer grows to hold
+        all `nf`).  The caller computes rows first .. nf - 1 into self._fb and then calls commit_rows(nf)."""
+        k = self._n_fb if self._fb is not None else 0
+        if k > nf:
+            k = 0
+        if self._fb is None or self._fb.shape[0] < nf:
+            fb = torch.empty((max(2 * nf, 512), self.feature_dim), dtype=torch.float32, device=self.engine.device)
+            if k:
+                fb[:k] = self._fb[:k]
+            self._fb = fb
+        return k
+
+    def commit_rows(self, nf: int) -> torch.Tensor:
+        self._n_fb = nf
+        return self._fb[:nf]
+
+    def __call__(self, new_samples, sr=None):
+        sr = sr or self.sample_rate
+        st = self.stage(new_samples)
+        if st is None:
+            return torch.empty((0, self.feature_dim), device=self.engine.device)
+        num_frames, effective = st
         pcm = self._dev[:effective]
         if sr != SAMPLE_RATE:
             pcm = self.engine.resample(pcm, int(sr), SAMPLE_RATE)
@@ -199,16 +226,8 @@ class OnlineFeatureExtractor:
         # A fbank row is a function of ITS 400 samples only (one workgroup per 25-ms frame, global CMVN): rows of the cached history stay
         # as they are and only the new frames are computed, into a buffer that grows by doubling.  Same bits as the full call
         # (tests/test_stages_gpu.py); the reference recomputes all frames per policy() call (agent :66-98).
-        nf = int(num_frames)
-        k = self._n_fb if self._fb is not None else 0
-        if k > nf:
-            k = 0
-        if self._fb is None or self._fb.shape[0] < nf:
-            fb = torch.empty((max(2 * nf, 512), self.feature_dim), dtype=torch.float32, device=dev)
-            if k:
-                fb[:k] = self._fb[:k]
-            self._fb = fb
+        nf = num_frames
+        k = self.new_rows(nf)
         if nf > k:
             self.engine.fbank_cmvn(self._dev[k * self.num_samples_per_shift:effective], 32768.0, out=self._fb[k:nf])
-        self._n_fb = nf
-        return self._fb[:nf]
+        return self.commit_rows(nf)

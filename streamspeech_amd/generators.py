@@ -7,6 +7,8 @@ from typing import Dict, List, Optional
 
 import torch
 
+from .text_policy import mt_max_len
+
 
 class CTCDecoder:
     """agent/ctc_decoder.py:30-111 -- ASR / ST CTC greedy search (blank = index 0)."""
@@ -86,15 +88,7 @@ class SequenceGenerator:
         src_len = src_tokens.size(1)
         prefix = [] if prefix_tokens is None else [int(t) for t in prefix_tokens.view(-1).tolist()]
         start = len(prefix)
-        if max_new_tokens == -1:
-            max_len = min(int(self.max_len_a * src_len + self.max_len_b), self.max_len - 1)
-        else:
-            max_len = start + max_new_tokens
-        assert self.min_len <= max_len, "min_len cannot be larger than max_len, please adjust these!"
-        if start > max_len:
-            # the reference's step loop `for step in range(start, max_len + 1)` (agent/sequence_generator.py:340) is empty
-            # then, nothing is finalized and the agent's finalized_mt[0][0] raises IndexError: same error here
-            raise IndexError(f"prefix of {start} tokens is longer than max_len = {max_len}: no hypothesis can be finalized")
+        max_len = mt_max_len(start, src_len, max_new_tokens, self.max_len_a, self.max_len_b, self.max_len, self.min_len)
         eng = self.engine
         if hasattr(eng, "mt_greedy"):
             out, feats = eng.mt_greedy(enc.contiguous(), prefix, max_len, self.min_len)

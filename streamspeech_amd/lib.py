@@ -93,6 +93,14 @@ SIGNATURES = {
                                 C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _vp, _i]),
     "ss_batch_mt_beam": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _f, _i,
                               C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(_f), C.POINTER(_f), _vp, _i]),
+    "ss_batch_mt_continue": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _vp, _i,
+                                  C.POINTER(C.c_int32)]),
+    "ss_batch_mt_continue_plan": (_i, [_i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32), _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                       _i64, C.POINTER(_i64)]),
+    "ss_batch_fbank_frames": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f,
+                                   C.POINTER(_vp)]),
     "ss_batch_t2u_units": (_i, [_vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp]),
     "ss_batch_vocoder_forward": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _vp, _vp, _i64, _vp,
                                       C.POINTER(_i64), C.POINTER(_i64)]),
@@ -131,6 +139,7 @@ _lib = None
 
 # return codes of the C ABI that callers act on (the full list: include/streamspeech_hip.h)
 SS_ERR_ARG = 2
+SS_ERR_CAPACITY = 4
 SS_ERR_SCRATCH_CAP = 5
 SS_ERR_STREAM_REPEAT = 8
 

@@ -1,0 +1,287 @@
+"""Concurrent streaming ASR and simultaneous S2TT sessions over one session pool (engine.StreamPool): the text-side agents
+(agent/speech_to_text.asr.streamspeech.agent.py, agent/speech_to_text.s2tt.streamspeech.agent.py; agent_text.py here) served many
+at a time.  Per session, one :meth:`TextSessionPool.step` is exactly one ``agent.pushpop(segment)`` of the matching single-session
+agent; across sessions a step is
+  * ONE fbank launch for the new frames of every 16-kHz session (ss_batch_fbank_frames; other rates resample per session),
+  * ONE batched encoder step and both CTC heads (StreamPool.forward / ctc_both; ASR sessions read head 0),
+  * the read/write gate of each session on the host (text_policy.s2tt_gate),
+  * ONE ragged greedy continuation of the committed prefix of every writing S2TT session (HipModel.batch_mt_continue).
+Driven by one host thread, like the pool."""
+import math
+import time
+from typing import Dict, Optional
+
+import torch
+
+from .frontend import SAMPLE_RATE, OnlineFeatureExtractor, unsettled_fbank_frames
+from .simuleval_shim import AgentStates, EmptySegment, TextSegment
+from .text_policy import mt_max_len, s2tt_gate
+
+KINDS = ("s2tt", "asr")
+# the text agents' first-pass search: beam 1, max_len_a = 1, max_len_b = 200, min_len = 1 (agent_text.py)
+MAX_LEN_A, MAX_LEN_B, MIN_LEN = 1, 200, 1
+
+
+def _encoder_out_len(T: int) -> int:
+    t1 = (T + 2 * 2 - 5) // 2 + 1
+    return (t1 + 2 * 2 - 5) // 2 + 1
+
+
+def fbank_frames_after(kind_sr: int, n_samples: int, shift_ms: int = 10, window_ms: int = 25) -> int:
+    """fbank rows the agent's front-end makes of `n_samples` samples at `kind_sr` Hz (OnlineFeatureExtractor, then the resampler)."""
+    per_shift = int(shift_ms * kind_sr / 1000)
+    nf = int((n_samples - (window_ms - shift_ms) * kind_sr / 1000) // per_shift)
+    if nf <= 0:
+        return 0
+    if kind_sr == SAMPLE_RATE:
+        return nf
+    effective = int(nf * shift_ms * kind_sr / 1000 + (window_ms - shift_ms) * kind_sr / 1000)
+    g = math.gcd(int(kind_sr), SAMPLE_RATE)
+    up, down = SAMPLE_RATE // g, int(kind_sr) // g
+    n16 = -(-effective * up // down)
+    return 0 if n16 < 400 else 1 + (n16 - 400) // 160
+
+
+class _Session:
+    def __init__(self, sid, kind, args, engine, dicts):
+        self.sid, self.kind, self.args = sid, kind, args
+        self.sr = int(args.sample_rate)
+        self.attn_chunk = args.source_segment_size // 40
+        self.conv_chunk = 16 if self.attn_chunk >= 16 else 8
+        self.lagging_k1, self.stride_n = args.lagging_k1, args.stride_n
+        self.tail = unsettled_fbank_frames(self.sr, SAMPLE_RATE, int(args.shift_size * SAMPLE_RATE / 1000))
+        self.fe = OnlineFeatureExtractor(args, engine)
+        self.dict = dicts
+        self.states = AgentStates()
+        self.slot = None
+        self.pending = False
+        self.reset()
+
+    def reset(self):                          # the agent's reset()
+        self.tgt_subwords = None
+        self.src_ctc_prefix_length = 0
+        self.tgt_ctc_prefix_length = 0
+        self.asr_text = ""
+        self.tgt_text = ""
+        self.states.reset()
+        self.fe.clear_cache()
+
+
+class TextSessionPool:
+    """Up to `max_sessions` concurrent ASR / S2TT sessions, each of at most `max_rows` encoder output rows (~40 ms each)."""
+
+    def __init__(self, model, max_sessions: int, max_rows: int):
+        self.model = model.hip if hasattr(model, "hip") else model
+        self.pool = self.model.stream_pool(max_sessions, max_rows)
+        self.max_sessions, self.max_rows = int(max_sessions), int(max_rows)
+        self.sessions: Dict[int, _Session] = {}
+        self.free = list(range(self.max_sessions))
+        self._next = 0
+        self.last_step: dict = {}              # timings / counts of the last step (tools/pooled_text_bench.py)
+
+    # ---- lifecycle ------------------------------------------------------------------------------------------------------------
+    def open(self, kind: str, args, dicts: Optional[dict] = None) -> int:
+        """A new session; `args` are the agent's own parsed flags (segment size, lagging_k1, stride_n, sample rate, chunk sizes).
+        `dicts` overrides the dictionaries the agent would load from the flags (keys source_unigram / target_unigram)."""
+        if kind not in KINDS:
+            raise ValueError(f"session kind {kind!r}: one of {KINDS}")
+        if dicts is None:
+            from .agent import load_dictionaries
+            dicts = load_dictionaries(args, self.model.cfg)
+        sid = self._next
+        self._next += 1
+        self.sessions[sid] = _Session(sid, kind, args, self.model, dicts)
+        return sid
+
+    def reset(self, sid: int):
+        """The agent's reset(): the session starts a fresh utterance (its slot goes back to the pool until it next has audio)."""
+        s = self._get(sid)
+        s.reset()
+        s.pending = False
+        self._release(s)
+
+    def close(self, sid: int):
+        s = self._get(sid)
+        self._release(s)
+        del self.sessions[sid]
+
+    def _get(self, sid) -> _Session:
+        if sid not in self.sessions:
+            raise KeyError(f"no open session {sid}")
+        return self.sessions[sid]
+
+    def _release(self, s: _Session):
+        if s.slot is not None:
+            self.pool.reset(s.slot)
+            self.free.append(s.slot)
+            s.slot = None
+
+    def _acquire(self, s: _Session):
+        if s.slot is None:
+            if not self.free:
+                raise ValueError(f"session {s.sid}: all {self.max_sessions} slots of the pool are taken")
+            s.slot = self.free.pop(0)
+            self.pool.reset(s.slot)
+            self.pool.set_tail(s.slot, s.tail)
+
+    # ---- one call per session ---------------------------------------------------------------------------------------------------
+    def _frames(self, s: _Session, extra: int = 0) -> int:
+        return fbank_frames_after(s.sr, len(s.states.source) + extra, s.args.shift_size, s.args.window_size)
+
+    def _admit(self, items):
+        """The capacity check of a set of pushes [(session, segment)], against everything already pushed for this step: raises
+        ValueError naming the first session refused and changes nothing.  A session is refused when it is already pushed, when
+        its audio would pass max_rows encoder rows, or when it needs a slot (frames, none held) and the free slots are spoken for."""
+        seen = set()
+        for s, _ in items:
+            if s.pending or s.sid in seen:
+                raise ValueError(f"session {s.sid}: already pushed in this step")
+            seen.add(s.sid)
+        # slots the step already needs: pushed sessions with frames and no slot (a finished agent does not encode)
+        need = sum(1 for s in self.sessions.values()
+                   if s.pending and s.slot is None and not s.states.target_finished and self._frames(s) > 0)
+        for s, seg in items:
+            if s.states.target_finished:
+                continue
+            T = self._frames(s, len(getattr(seg, "content", None) or []))
+            if T > 0 and _encoder_out_len(T) > self.max_rows:
+                raise ValueError(f"session {s.sid}: {_encoder_out_len(T)} encoder rows would pass the pool's max_rows {self.max_rows}")
+            if T > 0 and s.slot is None:
+                need += 1
+                if need > len(self.free):
+                    raise ValueError(f"session {s.sid}: no free slot -- the {self.max_sessions} slots of the pool are held or "
+                                     f"needed by other sessions of this step")
+
+    def push(self, sid: int, segment):
+        """The agent's push(), checked against the pool's capacity first (_admit): a refused push raises ValueError naming the
+        session and changes nothing; the sessions pushed before and after it step as usual."""
+        s = self._get(sid)
+        self._admit([(s, segment)])
+        s.states.update_source(segment)
+        s.pending = True
+
+    def step(self, segments: Optional[dict] = None) -> dict:
+        """{sid: SpeechSegment} -> {sid: Segment}: per session exactly one agent.pushpop(segment), for these sessions and any pushed
+        since the last step.  The pushes of `segments` are admitted together: if one is refused, ValueError names it and the WHOLE
+        call is refused before anything moves (to step the others anyway, push() them one by one and call step())."""
+        if segments:
+            items = [(self._get(sid), seg) for sid, seg in segments.items()]
+            self._admit(items)
+            for s, seg in items:
+                s.states.update_source(seg)
+                s.pending = True
+        todo = [s for s in self.sessions.values() if s.pending]
+        out: Dict[int, object] = {}
+        actions: Dict[int, tuple] = {}
+        t0 = time.perf_counter()
+        # ---- front-end: finished agents answer at once; 16-kHz sessions' new rows in one launch ----
+        feats, batch = {}, []
+        for s in todo:
+            s.pending = False
+            if s.states.target_finished:
+                out[s.sid] = EmptySegment(finished=True)
+                continue
+            st = s.fe.stage(s.states.source)
+            if st is None:
+                actions[s.sid] = ("write", "", True) if s.states.source_finished else ("read",)
+                continue
+            nf, eff = st
+            if s.sr != SAMPLE_RATE:
+                fb = self.model.fbank_cmvn(self.model.resample(s.fe._dev[:eff], s.sr, SAMPLE_RATE), 32768.0)
+                if fb.shape[0] == 0:              # too short after resampling: the agent's early return, as above
+                    actions[s.sid] = ("write", "", True) if s.states.source_finished else ("read",)
+                    continue
+                feats[s.sid] = fb
+            else:
+                k = s.fe.new_rows(nf)
+                batch.append((s, k, nf))
+        if batch:
+            self.model.batch_fbank_frames([s.fe._dev for s, _, _ in batch], [k for _, k, _ in batch], [nf - k for _, k, nf in batch],
+                                          [s.fe._fb[k:nf] for s, k, nf in batch])
+            for s, k, nf in batch:
+                feats[s.sid] = s.fe.commit_rows(nf)
+        t1 = time.perf_counter()
+        # ---- one encoder step + both CTC heads ----
+        enc = [s for s in todo if s.sid in feats]
+        writers, n_steps = [], 0
+        if enc:
+            for s in enc:
+                self._acquire(s)
+            packed, views, _, _ = self.pool.forward([s.slot for s in enc], [feats[s.sid] for s in enc],
+                                                    [s.attn_chunk for s in enc], [s.conv_chunk for s in enc])
+            src, tgt = self.pool.ctc_both()
+            t2 = time.perf_counter()
+            for i, s in enumerate(enc):
+                if s.kind == "asr":
+                    actions[s.sid] = self._asr(s, src[i][0])
+                    continue
+                g = s2tt_gate(len(src[i][0]), len(tgt[i][0]), s.src_ctc_prefix_length, s.tgt_ctc_prefix_length,
+                              len(s.tgt_subwords) if s.tgt_subwords is not None else 0, s.lagging_k1, s.stride_n,
+                              s.states.source_finished)
+                s.src_ctc_prefix_length, s.tgt_ctc_prefix_length = g.src_prefix_len, g.tgt_prefix_len
+                if not g.write:
+                    actions[s.sid] = ("read",)
+                    continue
+                prefix = list(s.tgt_subwords) if s.tgt_subwords is not None else []
+                ml = mt_max_len(len(prefix), feats[s.sid].shape[0], g.new_tokens, MAX_LEN_A, MAX_LEN_B,
+                                self.model.cfg.max_target_positions, MIN_LEN)
+                writers.append((i, s, prefix, ml, g.new_tokens))
+            # ---- one ragged continuation of every writer's prefix ----
+            if writers:
+                if len(writers) == len(enc):
+                    enc_w, Tp = packed, [views[i].shape[0] for i in range(len(enc))]
+                else:
+                    enc_w = torch.cat([views[i] for i, _, _, _, _ in writers], 0)
+                    Tp = [views[i].shape[0] for i, _, _, _, _ in writers]
+                res = self.model.batch_mt_continue(enc_w, Tp, [p for _, _, p, _, _ in writers], [m for _, _, _, m, _ in writers],
+                                                   MIN_LEN)
+                for (i, s, prefix, ml, new), (toks, _) in zip(writers, res):
+                    n_steps = max(n_steps, len(toks) - 1)
+                    actions[s.sid] = self._s2tt_write(s, prefix + toks, new)
+        else:
+            t2 = t1
+        t3 = time.perf_counter()
+        # ---- actions -> segments, as GenericAgent.pop ----
+        for s in todo:
+            if s.sid in out:
+                continue
+            a = actions[s.sid]
+            if a[0] == "read":
+                out[s.sid] = EmptySegment()
+                continue
+            seg = TextSegment(index=0, content=a[1], finished=a[2])
+            s.states.update_target(seg)
+            out[s.sid] = seg
+            if s.states.target_finished:          # finished without the agent's reset(): it answers EmptySegment(finished=True)
+                self._release(s)                  # from now on, so its slot goes back; reset(sid) starts a fresh utterance
+        self.last_step = {"sessions": len(todo), "encoded": len(enc), "writers": len(writers), "mt_steps": n_steps,
+                          "frontend_s": t1 - t0, "encoder_ctc_s": t2 - t1, "mt_s": t3 - t2, "total_s": time.perf_counter() - t0}
+        return out
+
+    # ---- the agents' write paths ------------------------------------------------------------------------------------------------
+    def _finish(self, s: _Session):
+        s.states.target_finished = True
+        s.reset()                                 # the agent's reset(): a fresh utterance, its slot back to the pool
+        self._release(s)
+
+    def _asr(self, s: _Session, tokens):
+        words = [s.dict["source_unigram"][c] for c in tokens]
+        text = " ".join(words)
+        new_text = text[len(s.asr_text):]
+        s.asr_text = text
+        if s.states.source_finished:
+            self._finish(s)
+        return ("write", new_text, s.states.target_finished)
+
+    def _s2tt_write(self, s: _Session, toks, new_tokens):
+        sub = toks[:-1] if toks[-1] == 2 else toks
+        words = [s.dict["target_unigram"][c] for c in sub]
+        if s.tgt_subwords is not None and list(s.tgt_subwords) == list(sub):
+            return ("write", "", True) if s.states.source_finished else ("read",)
+        s.tgt_subwords = list(sub)
+        text = " ".join(words)
+        new_text = text[len(s.tgt_text):]
+        s.tgt_text = text
+        if s.states.source_finished and new_tokens == -1:
+            self._finish(s)
+        return ("write", new_text, s.states.target_finished)
