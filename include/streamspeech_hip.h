@@ -407,6 +407,25 @@ int ss_batch_vocoder_forward(ss_vocoder* v, void* stream, int B, const int32_t* 
                              int dur_prediction, const int32_t* d_forced_dur, float* d_wav,
                              int64_t wav_capacity, int32_t* d_dur, int64_t* h_wav_start,
                              int64_t* h_n_samples);
+/* ss_batch_t2u_units with trailing <pad> states: row b's last h_n_tail_pad[b] (0 <= . < h_n[b]) states are masked as keys as
+ * ss_t2u_units(..., n_tail_pad) masks them -- T2U encoder self-attention, unit decoder self-attention (ctc_upsample x pad rows) and
+ * cross-attention -- and still decoded.  Rows with 0 are bit-identical to ss_batch_t2u_units; pack-invariant like it. */
+int ss_batch_t2u_units_pad(ss_model* m, void* stream, int B, const float* d_feats, int feat_rows, const int32_t* h_n,
+                           const int32_t* h_n_tail_pad, int t2u_causal, int mask_eos, int32_t* d_raw, int32_t* d_tokens,
+                           int32_t* d_counts);
+/* MT decoder states only, B rows in one ragged pass (the prefix pass of ss_batch_mt_continue): row b feeds [</s>, tokens_b
+ * (h_n_tokens[b], packed in h_tokens), <pad> x h_n_tail_pad[b]] over its h_Tp[b] packed encoder rows; d_feats [B][feat_rows][D]
+ * gets the post-LN state of every fed position -- per row what ss_mt_truncate + ss_mt_append(..., n_tail_pad) give.  No search. */
+int ss_batch_mt_features(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp, const int32_t* h_tokens,
+                         const int32_t* h_n_tokens, const int32_t* h_n_tail_pad, float* d_feats, int feat_rows);
+/* B rows of the S2ST agent's receptive-field vocoder tail: row b has h_K[b] units (packed in d_codes), the last h_n_new[b] new.  With
+ * h_ctx[b] > 0 and h_K[b] > n_new + ctx only the last n_new + ctx units are synthesised, unless the durations of context units
+ * [2, ctx) cover fewer than h_rf[b] + 2 frames -- then all units are.  Only the new units' samples are written: d_out[h_out_start[b]
+ * ..], h_n_out[b] of them (out_capacity floats in all).  h_win_first[b] = first unit synthesised; h_dur (host, sum h_K ints, row b at
+ * the prefix sum of h_K) = the durations of the synthesised units.  Synchronises once. */
+int ss_batch_vocoder_tail(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K, const int32_t* h_n_new,
+                          const int32_t* h_ctx, const int32_t* h_rf, int dur_prediction, float* d_out, int64_t out_capacity,
+                          int32_t* h_win_first, int32_t* h_dur, int64_t* h_out_start, int64_t* h_n_out);
 
 /* ---- profiling hooks for bench.py's roofline leg: bracket every conv-GEMM launch whose tile
  * configuration is in cls_mask with HIP events recorded on the launch stream.  ss_prof_read

@@ -32,6 +32,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs p) {
   if (p.nseg > 0) {   // ragged batch: rebase this workgroup onto its utterance
     const int* sg = p.segs + 4 * blockIdx.z;
     p.Tq = sg[1]; p.Tk = sg[3];
+    if (p.seg_tail) p.k_mask_tail = p.seg_tail[blockIdx.z];
     if ((int)blockIdx.x * QB >= p.Tq) return;
     p.Q += (size_t)sg[0] * p.ldq; p.O += (size_t)sg[0] * p.ldo;
     p.K += (size_t)sg[2] * p.ldk; p.V += (size_t)sg[2] * p.ldv;
@@ -175,6 +176,7 @@ __global__ __launch_bounds__(256) void attention_decode_kernel(AttnArgs p) {
   if (p.nseg > 0) {
     const int* sg = p.segs + 4 * blockIdx.z;
     p.Tq = sg[1]; p.Tk = sg[3];
+    if (p.seg_tail) p.k_mask_tail = p.seg_tail[blockIdx.z];
     if ((int)blockIdx.x >= p.Tq) return;
     p.Q += (size_t)sg[0] * p.ldq; p.O += (size_t)sg[0] * p.ldo;
     if (ANC) {
@@ -269,6 +271,7 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(AttnArgs p) {
   if (p.nseg > 0) {
     const int* sg = p.segs + 4 * blockIdx.z;
     p.Tq = sg[1]; p.Tk = sg[3];
+    if (p.seg_tail) p.k_mask_tail = p.seg_tail[blockIdx.z];
     if ((int)blockIdx.x * MQ >= p.Tq) return;
     p.Q += (size_t)sg[0] * p.ldq; p.O += (size_t)sg[0] * p.ldo;
     p.K += (size_t)sg[2] * p.ldk; p.V += (size_t)sg[2] * p.ldv;
@@ -986,6 +989,7 @@ int launch_attention(const AttnArgs& a, hipStream_t stream) {
   if ((a.ldk & 3) || (a.ldv & 3)) return SS_ERR_ARG;
   const int gz = a.nseg > 0 ? a.nseg : 1;
   if (a.q0 != 0 && (a.nseg > 0 || a.causal)) return SS_ERR_ARG;
+  if (a.seg_tail && (a.nseg <= 0 || a.P)) return SS_ERR_ARG;   // per-segment key masks: ragged plain attention only
   if (a.anc) {      // the ancestry-indexed form exists in the ragged decode kernel only
     if (a.nseg <= 0 || a.P || tq > 8 || a.q0 != 0 || a.no_decode_kernel || a.anc_ld <= 0 || a.anc_slots <= 0) return SS_ERR_ARG;
     hipLaunchKernelGGL(attention_decode_kernel<true>, dim3(tq, a.H, gz), dim3(256), 0, stream, a);

@@ -30,6 +30,10 @@ struct AttnArgs {
   // of K/V; Tq/Tk above are ignored except max_q (grid sizing).  For the rel-pos form P must point
   // at row 0 of the FULL table (relative offset p_tmax-1) and the kernel slices it per segment.
   const int* segs = nullptr; int nseg = 0; int max_q = 0; int p_tmax = 0;
+  // Ragged plain attention only: seg_tail[s] trailing key rows of segment s are padding (k_mask_tail per segment, the same masking
+  // semantics; the scalar k_mask_tail is then ignored).  nullptr = the scalar for every segment.  A count of 0 takes exactly the
+  // arithmetic of an unmasked segment.
+  const int* seg_tail = nullptr;
   // Key-split scratch of the calling context (rel-pos form, single utterance only; nullptr = never split): few query tiles
   // over many keys -- one utterance, or the tail rows of the incremental streaming encoder -- would otherwise run as
   // (query tiles x heads) workgroups that each walk ALL key tiles one after the other.  See attention_relpos_mfma_kernel.

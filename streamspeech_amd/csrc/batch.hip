@@ -247,10 +247,13 @@ extern "C" int ss_batch_mt_greedy(ss_model* m, void* stream, int B, const float*
   return SS_OK;
 }
 
-extern "C" int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float* d_feats, int feat_rows,
-                                  const int32_t* h_n, int t2u_causal, int mask_eos, int32_t* d_raw, int32_t* d_tokens,
-                                  int32_t* d_counts) {
-  if (!m || B <= 0) return SS_ERR_ARG;
+// ss_batch_t2u_units and ss_batch_t2u_units_pad.  h_pad == nullptr: no key is masked anywhere and no mask table exists (the launches
+// of ss_batch_t2u_units as they always were).  Otherwise row b's last h_pad[b] states are trailing <pad> positions, masked as keys as
+// ss_t2u_units(..., n_tail_pad) masks them: in the T2U encoder (h_pad[b] rows), the unit decoder's self-attention (up x h_pad[b]) and
+// its cross-attention (h_pad[b]); they are still decoded.  A row with h_pad[b] = 0 takes exactly the unmasked arithmetic.
+static int batch_t2u(ss_model* m, void* stream, int B, const float* d_feats, int feat_rows, const int32_t* h_n, const int32_t* h_pad,
+                     int t2u_causal, int mask_eos, int32_t* d_raw, int32_t* d_tokens, int32_t* d_counts) {
+  if (!m || B <= 0 || !h_n) return SS_ERR_ARG;
   SkScope sk_scope(m->sc->skws);
   CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
   hipStream_t s = (hipStream_t)stream;
@@ -258,6 +261,9 @@ extern "C" int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float*
   const int D = c.dec_dim, F = c.dec_ffn, V = c.unit_vocab, H = c.dec_heads, up = c.ctc_upsample;
   for (int b = 0; b < B; ++b)
     if (h_n[b] <= 0) return SS_ERR_ARG;                    // every utterance feeds at least the leading </s> state
+  if (h_pad)
+    for (int b = 0; b < B; ++b)
+      if (h_pad[b] < 0 || h_pad[b] >= h_n[b]) return SS_ERR_ARG;   // the leading </s> state is never padding
   const Offsets on = prefix(h_n, B);
   const int Nn = on.total, U = Nn * up;
   const size_t nx = (size_t)U * D;
@@ -273,7 +279,7 @@ extern "C" int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float*
   float* logits = t2u_out + (size_t)Nn * D;
   int32_t* idx_scratch = reinterpret_cast<int32_t*>(logits + (size_t)U * V);
   // tables: t2u self {off,n,off,n}; unit self {25off,25n,25off,25n}; unit cross {25off,25n,off,n}; rows {25off,25n}
-  std::vector<int> tab(14 * B + Nn);            // + the packed row -> row of d_feats map of the gather below
+  std::vector<int> tab(14 * B + Nn + (h_pad ? 3 * B : 0));   // + the packed row -> row of d_feats map of the gather below (+ the masks)
   for (int b = 0; b < B; ++b) {
     const int o = on.off[b], n = h_n[b];
     for (int r = 0; r < n; ++r) tab[14 * B + o + r] = b * feat_rows + r;
@@ -281,10 +287,15 @@ extern "C" int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float*
     int* u = &tab[4 * B + 4 * b]; u[0] = o * up; u[1] = n * up; u[2] = o * up; u[3] = n * up;
     int* x2 = &tab[8 * B + 4 * b]; x2[0] = o * up; x2[1] = n * up; x2[2] = o; x2[3] = n;
     tab[12 * B + 2 * b] = o * up; tab[12 * B + 2 * b + 1] = n * up;
+    if (h_pad) {                                  // trailing keys masked per segment: T2U self | unit self | unit cross
+      int* k = &tab[14 * B + Nn];
+      k[b] = h_pad[b]; k[B + b] = h_pad[b] * up; k[2 * B + b] = h_pad[b];
+    }
   }
   RET(m->sc->seg_buf.ensure(tab.size() * sizeof(int)));
   int* dt = (int*)m->sc->seg_buf.p;
   RET(upload(s, dt, tab));
+  const int* tail = h_pad ? dt + 14 * B + Nn : nullptr;
   // gather the decoder states of each utterance into packed rows: ONE launch (round 4 issued B device-to-device copies per pack --
   // 2975 __amd_rocclr_copyBuffer launches, 1 % of the one-stream kernel time and 64 more dependent launches per pack)
   for (int b = 0; b < B; ++b)
@@ -296,6 +307,7 @@ extern "C" int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float*
     at.O = h; at.ldo = D; at.H = H; at.scale = 1.f; at.causal = t2u_causal ? 1 : 0;
     at.segs = dt; at.nseg = B; at.max_q = on.mx;
     at.no_decode_kernel = m->pack_invariant;       // max_q is the pack's longest utterance: it must not pick the kernel
+    at.seg_tail = tail;
     RET(dec_layer_ex(s, c, m->t2u[l], x, Nn, selfbuf, 3 * D, at, nullptr, h, q2, ff));
   }
   RET(launch_layernorm(x, D, t2u_out, D, m->t2u_ln.g, m->t2u_ln.b, Nn, D, 1e-5f, s));
@@ -310,6 +322,7 @@ extern "C" int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float*
     ac.Q = q2; ac.ldq = D; ac.K = crosskv; ac.V = crosskv + D; ac.ldk = ac.ldv = 2 * D;
     ac.O = h; ac.ldo = D; ac.H = H; ac.scale = 1.f; ac.segs = dt + 8 * B; ac.nseg = B; ac.max_q = on.mx * up;
     ac.no_decode_kernel = m->pack_invariant;
+    if (tail) { at.seg_tail = tail + B; ac.seg_tail = tail + 2 * B; }
     RET(dec_layer_ex(s, c, m->unit[l], x, U, selfbuf, 3 * D, at, &ac, h, q2, ff));
   }
   RET(launch_layernorm(x, D, h, D, m->unit_ln.g, m->unit_ln.b, U, D, 1e-5f, s));
@@ -317,6 +330,19 @@ extern "C" int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float*
   m->sc->dbg_logits = logits; m->sc->dbg_rows = U; m->sc->dbg_cols = V;
   RET(launch_masked_argmax(logits, V, U, V, c.pad, c.unk, mask_eos ? c.eos : -1, -1, d_raw, s));
   return launch_ctc_collapse(d_raw, 0, V - 1, c.pad, d_tokens, idx_scratch, d_counts, s, dt + 12 * B, B);
+}
+
+extern "C" int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float* d_feats, int feat_rows,
+                                  const int32_t* h_n, int t2u_causal, int mask_eos, int32_t* d_raw, int32_t* d_tokens,
+                                  int32_t* d_counts) {
+  return batch_t2u(m, stream, B, d_feats, feat_rows, h_n, nullptr, t2u_causal, mask_eos, d_raw, d_tokens, d_counts);
+}
+
+extern "C" int ss_batch_t2u_units_pad(ss_model* m, void* stream, int B, const float* d_feats, int feat_rows, const int32_t* h_n,
+                                      const int32_t* h_n_tail_pad, int t2u_causal, int mask_eos, int32_t* d_raw, int32_t* d_tokens,
+                                      int32_t* d_counts) {
+  if (!h_n_tail_pad) return SS_ERR_ARG;
+  return batch_t2u(m, stream, B, d_feats, feat_rows, h_n, h_n_tail_pad, t2u_causal, mask_eos, d_raw, d_tokens, d_counts);
 }
 
 // Ragged continuation of B independent beam-1 searches (ss_batch_mt_continue): row b feeds [</s>, prefix_b...] and generates, with
@@ -407,6 +433,45 @@ extern "C" int ss_batch_mt_continue_plan(int B, const int32_t* h_Tp, const int32
   return SS_OK;
 }
 
+// The ragged prefix pass of ss_batch_mt_continue and ss_batch_mt_features: the Np fed rows (tokens d_ptok at positions d_ppos) through
+// every decoder layer in ONE ragged pass -- causal self-attention per segment (d_pself), cross-attention per session over the packed
+// encoder rows whose K/V the caller put in mt_cross (d_pcross, n_enc rows), CANON_SEQ -- then the final LayerNorm.  d_ptail (may be
+// null): trailing keys masked per segment in the self-attention (<pad> positions).  d_pcache (may be null): each layer's q|k|v rows
+// are also scattered to rows d_pcache[] of the lock-step cache (Lcap rows per session).  Workspace: m->sc->ws, (7 D + F) floats a
+// row, sized by the caller: x | h | q2 | post-LN states | q|k|v | ffn.  *out = the post-LN states [Np][D] (in ws).
+static int mt_prefix_pass(ss_model* m, hipStream_t s, int B, int Np, int np_max, int n_enc, const int* d_ptok, const int* d_ppos,
+                          const int* d_pself, const int* d_pcross, const int* d_ptail, const int* d_pcache, int Lcap, const float** out) {
+  const ss_config& c = m->cfg;
+  const int D = c.dec_dim, V = c.tgt_vocab, H = c.dec_heads;
+  const size_t np = (size_t)Np;
+  float* xp = m->sc->ws.f();
+  float* hp = xp + np * D;
+  float* q2p = hp + np * D;
+  float* pfo = q2p + np * D;
+  float* qkvp = pfo + np * D;
+  float* ffp = qkvp + np * 3 * D;
+  RET(launch_embed_tokens_rows(d_ptok, m->mt_emb, m->mt_pos, c.max_tgt_pos, sqrtf((float)D), c.pad + 1, d_ppos, xp, Np, D, s, c.pad,
+                               V));
+  for (int l = 0; l < c.mt_layers; ++l) {
+    AttnArgs at;
+    at.Q = qkvp; at.ldq = 3 * D; at.K = qkvp + D; at.V = qkvp + 2 * D; at.ldk = at.ldv = 3 * D;
+    at.O = hp; at.ldo = D; at.H = H; at.scale = 1.f; at.causal = 1;
+    at.segs = d_pself; at.nseg = B; at.max_q = np_max; at.no_decode_kernel = m->pack_invariant;   // max_q depends on the pack
+    at.seg_tail = d_ptail;
+    AttnArgs ac;
+    ac.Q = q2p; ac.ldq = D; ac.K = m->sc->mt_cross.f() + (size_t)l * n_enc * 2 * D; ac.V = ac.K + D; ac.ldk = ac.ldv = 2 * D;
+    ac.O = hp; ac.ldo = D; ac.H = H; ac.scale = 1.f; ac.segs = d_pcross; ac.nseg = B; ac.max_q = np_max;
+    ac.no_decode_kernel = m->pack_invariant;
+    RET(dec_layer_ex(s, c, m->mt[l], xp, Np, qkvp, 3 * D, at, &ac, hp, q2p, ffp));
+    if (d_pcache)
+      RET(launch_scatter_rows(d_pcache, qkvp, 3 * D, m->sc->bmt_self.f() + (size_t)l * B * Lcap * 3 * D, 3 * D, 3 * D, Np,
+                              B * Lcap, s));
+  }
+  RET(launch_layernorm(xp, D, pfo, D, m->mt_ln.g, m->mt_ln.b, Np, D, 1e-5f, s));
+  *out = pfo;
+  return SS_OK;
+}
+
 extern "C" int ss_batch_mt_continue(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp,
                                     const int32_t* h_prefix, const int32_t* h_n_prefix, const int32_t* h_max_len, int min_len,
                                     int32_t* h_out_tokens, int out_stride, int32_t* h_n_out, float* d_feats, int feat_rows,
@@ -455,27 +520,9 @@ extern "C" int ss_batch_mt_continue(ss_model* m, void* stream, int B, const floa
                m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D, 2 * D));
   // ---- the prefix pass ----
   {
-    float* xp = m->sc->ws.f();
-    float* hp = xp + np * D;
-    float* q2p = hp + np * D;
-    float* pfo = q2p + np * D;
-    float* qkvp = pfo + np * D;
-    float* ffp = qkvp + np * 3 * D;
-    RET(launch_embed_tokens_rows(d_ptok, m->mt_emb, m->mt_pos, c.max_tgt_pos, emb_scale, c.pad + 1, d_ppos, xp, Np, D, s, c.pad, V));
-    for (int l = 0; l < c.mt_layers; ++l) {
-      AttnArgs at;
-      at.Q = qkvp; at.ldq = 3 * D; at.K = qkvp + D; at.V = qkvp + 2 * D; at.ldk = at.ldv = 3 * D;
-      at.O = hp; at.ldo = D; at.H = H; at.scale = 1.f; at.causal = 1;
-      at.segs = d_pself; at.nseg = B; at.max_q = np_max; at.no_decode_kernel = m->pack_invariant;   // max_q depends on the pack
-      AttnArgs ac;
-      ac.Q = q2p; ac.ldq = D; ac.K = m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D; ac.V = ac.K + D; ac.ldk = ac.ldv = 2 * D;
-      ac.O = hp; ac.ldo = D; ac.H = H; ac.scale = 1.f; ac.segs = d_pcross; ac.nseg = B; ac.max_q = np_max;
-      ac.no_decode_kernel = m->pack_invariant;
-      RET(dec_layer_ex(s, c, m->mt[l], xp, Np, qkvp, 3 * D, at, &ac, hp, q2p, ffp));
-      RET(launch_scatter_rows(d_pcache, qkvp, 3 * D, m->sc->bmt_self.f() + (size_t)l * B * Lcap * 3 * D, 3 * D, 3 * D, Np,
-                              B * Lcap, s));
-    }
-    RET(launch_layernorm(xp, D, pfo, D, m->mt_ln.g, m->mt_ln.b, Np, D, 1e-5f, s));
+    const float* pfo = nullptr;
+    RET(mt_prefix_pass(m, s, B, Np, np_max, oe.total, d_ptok, d_ppos, d_pself, d_pcross, nullptr, d_pcache, Lcap, &pfo));
+    float* hp = m->sc->ws.f() + np * D;
     RET(launch_scatter_rows(d_pfeat, pfo, D, d_feats, D, D, Np, B * feat_rows, s));
     RET(launch_gather_rows(d_plast, pfo, D, hp, B, s, Np));
     // the first generated token: projected as a lock-step row (one row per session, CANON_SMALLM)
@@ -550,6 +597,63 @@ extern "C" int ss_batch_mt_continue(ss_model* m, void* stream, int B, const floa
     RET(launch_scatter_rows(d_lfeat, lfeat, D, d_feats, D, D, B * Tr, B * feat_rows, s));
   }
   return SS_OK;
+}
+
+// Decoder states of B fed rows in ONE ragged pass (the MT features the S2ST write path hands to T2U): row b feeds [</s>, tokens_b...,
+// <pad> x n_tail_pad_b] over its encoder rows and gets the post-LN state of every position, as ss_mt_truncate + ss_mt_append(...,
+// n_tail_pad) give them for one utterance: the trailing <pad> positions take the padding position and are masked as self-attention
+// keys.  Nothing is projected onto the vocabulary.  d_feats [B][feat_rows][D]: row b's 1 + n_tokens_b + n_tail_pad_b states.
+extern "C" int ss_batch_mt_features(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp,
+                                    const int32_t* h_tokens, const int32_t* h_n_tokens, const int32_t* h_n_tail_pad, float* d_feats,
+                                    int feat_rows) {
+  if (!m || B <= 0 || B > 256 || !d_enc_out || !h_Tp || !h_n_tokens || !h_n_tail_pad || !d_feats || feat_rows <= 0) return SS_ERR_ARG;
+  const ss_config& c = m->cfg;
+  const int D = c.dec_dim, F = c.dec_ffn;
+  std::vector<int> seg_len(B);
+  int tok_total = 0;
+  for (int b = 0; b < B; ++b) {
+    if (h_Tp[b] <= 0 || h_n_tokens[b] < 0 || h_n_tail_pad[b] < 0) return SS_ERR_ARG;
+    if (h_n_tokens[b] > 0 && !h_tokens) return SS_ERR_ARG;
+    for (int i = 0; i < h_n_tokens[b]; ++i)
+      if (h_tokens[tok_total + i] < 0 || h_tokens[tok_total + i] >= c.tgt_vocab) return SS_ERR_ARG;   // nn.Embedding's IndexError
+    tok_total += h_n_tokens[b];
+    seg_len[b] = 1 + h_n_tokens[b] + h_n_tail_pad[b];
+    if (seg_len[b] > feat_rows || seg_len[b] + 2 > c.max_tgt_pos) return SS_ERR_CAPACITY;   // ss_mt_append's position bound
+  }
+  const Offsets oe = prefix(h_Tp, B), op = prefix(seg_len.data(), B);
+  const int Np = op.total;
+  const size_t np = (size_t)Np;
+  // int tables: self segs [4B] | cross segs [4B] | self tail [B] | tokens [Np] | positions [Np] | feature rows [Np]
+  std::vector<int> tab(9 * (size_t)B + 3 * np);
+  int* ps = tab.data(); int* pc = ps + 4 * B; int* pt = pc + 4 * B; int* tk = pt + B; int* pp = tk + np; int* pf = pp + np;
+  for (int b = 0, o = 0; b < B; ++b) {
+    const int r0 = op.off[b], n = seg_len[b], nt = h_n_tokens[b];
+    ps[4 * b] = r0; ps[4 * b + 1] = n; ps[4 * b + 2] = r0; ps[4 * b + 3] = n;
+    pc[4 * b] = r0; pc[4 * b + 1] = n; pc[4 * b + 2] = oe.off[b]; pc[4 * b + 3] = h_Tp[b];
+    pt[b] = h_n_tail_pad[b];
+    for (int p = 0; p < n; ++p) {
+      tk[r0 + p] = p == 0 ? c.eos : p <= nt ? h_tokens[o + p - 1] : c.pad;
+      pp[r0 + p] = p;
+      pf[r0 + p] = b * feat_rows + p;
+    }
+    o += nt;
+  }
+  // ---- every buffer first: a scratch cap refuses the call before anything is queued ----
+  RET(m->sc->mt_cross.ensure((size_t)c.mt_layers * oe.total * 2 * D * sizeof(float)));
+  RET(m->sc->ws.ensure((np * (7 * D + F)) * sizeof(float)));
+  RET(m->sc->seg_buf.ensure(tab.size() * sizeof(int)));
+  SkScope sk_scope(m->sc->skws);
+  CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
+  hipStream_t s = (hipStream_t)stream;
+  int* dt = (int*)m->sc->seg_buf.p;
+  RET(upload(s, dt, tab));
+  const int *d_self = dt, *d_cross = dt + 4 * B, *d_tail = dt + 8 * B, *d_tok = dt + 9 * B, *d_pos = d_tok + np, *d_frow = d_pos + np;
+  for (int l = 0; l < c.mt_layers; ++l)
+    RET(linear(s, d_enc_out, c.enc_dim, oe.total, m->mt[l].cross_kv, 2 * D, c.enc_dim,
+               m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D, 2 * D));
+  const float* pfo = nullptr;
+  RET(mt_prefix_pass(m, s, B, Np, op.mx, oe.total, d_tok, d_pos, d_self, d_cross, d_tail, nullptr, 0, &pfo));
+  return launch_scatter_rows(d_frow, pfo, D, d_feats, D, D, Np, B * feat_rows, s);
 }
 
 // New fbank rows of many streaming sessions in ONE launch (the batched front-end of the text session pool): session b's frames

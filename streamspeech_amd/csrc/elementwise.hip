@@ -525,4 +525,42 @@ int launch_conv_post_tanh(const float* x, int T, int C, const float* w, const fl
   return SS_OK;
 }
 
+// Tail-only form (the receptive-field vocoder tail of the S2ST write path): a workgroup covers 256 kept samples of one segment; the
+// sample's arithmetic is conv_post_tanh_kernel's (same taps, same segment edges, same order), only the output address moves.
+__global__ __launch_bounds__(256) void conv_post_tanh_crop_kernel(const float* __restrict__ x, int C, const float* __restrict__ w,
+                                                                  const float* __restrict__ bias, float slope, float* wav,
+                                                                  const int* __restrict__ segs) {
+  extern __shared__ float ws[];  // 7*C weights
+  const int* sg = segs + 4 * blockIdx.y;
+  const int st = sg[0], T = sg[1], first = sg[2], out0 = sg[3];
+  if (first + (int)blockIdx.x * 256 >= T) return;          // block-uniform: no kept sample here (before the barrier)
+  for (int i = threadIdx.x; i < 7 * C; i += 256) ws[i] = w[i];
+  __syncthreads();
+  x += (size_t)st * C;
+  const int t = first + blockIdx.x * 256 + threadIdx.x;
+  if (t >= T) return;
+  float acc = 0.f;
+  for (int j = 0; j < 7; ++j) {
+    const int pos = t + j - 3;
+    if (pos < 0 || pos >= T) continue;
+    const float* xr = x + (size_t)pos * C;
+    for (int c = 0; c < C; ++c) {
+      float v = xr[c];
+      v = v > 0.f ? v : v * slope;
+      acc = fmaf(ws[j * C + c], v, acc);
+    }
+  }
+  wav[out0 + (t - first)] = tanhf(acc + bias[0]);
+}
+
+int launch_conv_post_tanh_crop(const float* x, int C, const float* w, const float* bias, float slope, float* wav, const int* segs,
+                               int nseg, int max_keep, hipStream_t stream) {
+  if (nseg <= 0 || max_keep <= 0) return SS_OK;
+  if (!segs || nseg > 65535) return SS_ERR_ARG;
+  hipLaunchKernelGGL(conv_post_tanh_crop_kernel, dim3(cdiv(max_keep, 256), nseg), dim3(256), 7 * C * sizeof(float), stream, x, C,
+                     w, bias, slope, wav, segs);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
 }  // namespace ss

@@ -73,5 +73,10 @@ int launch_repeat_rows(const float* emb, const int* cum, int K, int D, float* ou
 // reference fairseq/models/text_to_speech/hifigan.py:166-168; slope = 0.01)
 int launch_conv_post_tanh(const float* x, int T, int C, const float* w, const float* bias, float slope,
                           float* wav, hipStream_t stream, const int* segs = nullptr, int nseg = 0);  // {start,len}; T = max
+// The same conv_post + tanh computing only a tail of each segment: segs[4 s] = {sample_start, n_samples, first, out_start}; samples
+// first .. n_samples - 1 of segment s (the same arithmetic as above, whose segment it is) go to wav[out_start ..].  max_keep = the
+// longest kept tail (grid sizing).
+int launch_conv_post_tanh_crop(const float* x, int C, const float* w, const float* bias, float slope, float* wav, const int* segs,
+                               int nseg, int max_keep, hipStream_t stream);
 
 }  // namespace ss

@@ -500,3 +500,187 @@ extern "C" int ss_batch_vocoder_forward(ss_vocoder* v, void* stream, int B, cons
   return launch_conv_post_tanh(bx, of.mx * scale, C, v->post.w, v->post.b, 0.01f, d_wav, s, dwav, B);
 }
 
+
+// B rows of the S2ST agent's receptive-field vocoder tail (agent.py synthesize_tail) in one call.  Row b holds h_K[b] units (packed in
+// d_codes), of which the last h_n_new[b] are new.  With h_ctx[b] > 0 and h_K[b] > n_new + ctx only the window of the last n_new + ctx
+// units is synthesised -- kept when the durations of its context units [2, ctx) cover h_rf[b] + 2 frames, else the row falls back to
+// all its units.  Only the samples of the new units are written: row b at d_out[h_out_start[b]], h_n_out[b] samples.
+// Candidates: every row's first choice (window, or all units) and, for windowed rows, all units as well go through ONE duration
+// predictor pass; ONE synchronisation reads their cumulative durations, the host picks per row, and the generator runs over the picked
+// segments only, its conv_post computing only the kept tail of each.  h_win_first[b] = the first unit synthesised (0: all units);
+// h_dur (host, sum K ints) = the durations of what was synthesised, row b at the prefix sum of h_K, h_K[b] - h_win_first[b] of them.
+extern "C" int ss_batch_vocoder_tail(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K,
+                                     const int32_t* h_n_new, const int32_t* h_ctx, const int32_t* h_rf, int dur_prediction,
+                                     float* d_out, int64_t out_capacity, int32_t* h_win_first, int32_t* h_dur, int64_t* h_out_start,
+                                     int64_t* h_n_out) {
+  if (!v || B <= 0 || B > 32768 || !d_codes || !h_K || !h_n_new || !h_ctx || !h_rf || !d_out || !h_win_first || !h_dur ||
+      !h_out_start || !h_n_out)
+    return SS_ERR_ARG;
+  const ss_vocoder_config& c = v->cfg;
+  const int E = c.embedding_dim, Hd = c.dur_hidden;
+  for (int b = 0; b < B; ++b)
+    if (h_K[b] <= 0 || h_n_new[b] <= 0 || h_n_new[b] > h_K[b] || h_ctx[b] < 0 || (h_ctx[b] > 0 && h_rf[b] < 0)) return SS_ERR_ARG;
+  const Offsets ok = prefix(h_K, B);
+  // candidate segments of the predictor pack: [0, B) first choices, then the full sequences of the windowed rows
+  std::vector<int> cu, cl, csrc, fall(B, -1);            // pack start, length, first unit in d_codes
+  for (int b = 0; b < B; ++b) {
+    const bool win = h_ctx[b] > 0 && h_K[b] > h_n_new[b] + h_ctx[b];
+    const int first = win ? h_K[b] - (h_n_new[b] + h_ctx[b]) : 0;
+    csrc.push_back(ok.off[b] + first); cl.push_back(h_K[b] - first);
+  }
+  for (int b = 0; b < B; ++b)
+    if (cl[b] < h_K[b]) { fall[b] = (int)cl.size(); csrc.push_back(ok.off[b]); cl.push_back(h_K[b]); }
+  const int S = (int)cl.size();
+  const Offsets oc = prefix(cl.data(), S);
+  const int Kc = oc.total;
+  cu.assign(oc.off.begin(), oc.off.end() - 1);
+  // ---- buffers first ----
+  const size_t n_small = (size_t)ok.total * E + (size_t)Kc * (E + 2 * Hd + 1) + 3 * ((size_t)Kc + S + 2);
+  RET(v->sc->v_small.ensure(n_small * sizeof(float)));
+  RET(v->sc->v_segs.ensure(((size_t)Kc + 6 * S + 12 * B) * sizeof(int)));   // + conv / repeat / conv_post segs of the generator rows
+  SkScope sk_scope(v->sc->skws);
+  hipStream_t s = (hipStream_t)stream;
+  float* emb_all = v->sc->v_small.f();
+  float* emb = emb_all + (size_t)ok.total * E;
+  float* t1 = emb + (size_t)Kc * E;
+  float* t2 = t1 + (size_t)Kc * Hd;
+  float* logdur = t2 + (size_t)Kc * Hd;
+  int* dur = reinterpret_cast<int*>(logdur + Kc);           // Kc
+  int* cum = dur + Kc;                                      // Kc + S entries (one extra per segment)
+  int* aux = cum + Kc + S + 2;                              // all-ones durations [Kc], later the generator's cum [Kc + B + 1]
+  int* dk = (int*)v->sc->v_segs.p;
+  {
+    // tables: unit row map [Kc] | conv segs {out,len,in,len} [S] | dur segs {start,len} [S]
+    std::vector<int> tk((size_t)Kc + 6 * S);
+    for (int z = 0; z < S; ++z) {
+      for (int i = 0; i < cl[z]; ++i) tk[cu[z] + i] = csrc[z] + i;
+      int* a = &tk[Kc + 4 * z]; a[0] = cu[z]; a[1] = cl[z]; a[2] = cu[z]; a[3] = cl[z];
+      tk[Kc + 4 * S + 2 * z] = cu[z]; tk[Kc + 4 * S + 2 * z + 1] = cl[z];
+    }
+    RET(upload(s, dk, tk));
+  }
+  const int* dmap = dk;
+  const int* dconv = dk + Kc;
+  const int* ddur = dconv + 4 * S;
+  RET(launch_gather_rows(d_codes, v->dict, E, emb_all, ok.total, s, v->cfg.num_embeddings));
+  RET(launch_gather_rows(dmap, emb_all, E, emb, Kc, s, ok.total));
+  const int* forced = nullptr;
+  if (dur_prediction) {
+    int mx = 0;
+    for (int z = 0; z < S; ++z) mx = std::max(mx, cl[z]);
+    auto sconv = [&](const float* A, int Cin, const ConvW& cw, int Cout, int k, float* Cc, int act) {
+      GemmArgs a;
+      a.A = A; a.lda = Cin; a.W = cw.w; a.bias = cw.b; a.C = Cc; a.ldc = Cout; a.N = Cout; a.Cin = Cin; a.taps = k;
+      a.pad = (k - 1) / 2; a.act = act; a.segs = dconv; a.nseg = S; a.max_seg_out = mx; a.M = Kc; a.in_len = Kc;
+      a.canon = CANON_SEQ;      // as ss_batch_vocoder_forward: integer durations, a summation order fixed per row
+      return launch_conv_gemm(a, s);
+    };
+    RET(sconv(emb, E, v->dur_c1, Hd, c.dur_kernel, t1, ACT_RELU));
+    RET(launch_layernorm(t1, Hd, t1, Hd, v->dur_ln1.g, v->dur_ln1.b, Kc, Hd, 1e-5f, s));
+    RET(sconv(t1, Hd, v->dur_c2, Hd, c.dur_kernel, t2, ACT_RELU));
+    RET(launch_layernorm(t2, Hd, t2, Hd, v->dur_ln2.g, v->dur_ln2.b, Kc, Hd, 1e-5f, s));
+    RET(sconv(t2, Hd, v->dur_proj, 1, 1, logdur, ACT_NONE));
+  } else {
+    std::vector<int> one(Kc, 1);
+    RET(upload(s, aux, one));
+    forced = aux;
+  }
+  RET(launch_dur_predict(logdur, forced, 0, dur, cum, s, ddur, S));
+  std::vector<int> hcum((size_t)Kc + S);
+  SS_HIP_CHECK(hipMemcpyAsync(hcum.data(), cum, hcum.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  SS_HIP_CHECK(hipStreamSynchronize(s));
+  auto C_ = [&](int z, int i) { return hcum[(size_t)cu[z] + z + i]; };   // cumulative duration of the first i units of candidate z
+  // ---- per row: the window, or all units when its context does not cover the receptive field ----
+  std::vector<int> pick(B);
+  for (int b = 0; b < B; ++b) {
+    pick[b] = b;
+    if (fall[b] >= 0 && C_(b, h_ctx[b]) - C_(b, 2) < h_rf[b] + 2) pick[b] = fall[b];
+  }
+  int hop = 1;
+  for (int i = 0; i < c.n_up; ++i) hop *= c.upsample_rates[i];
+  // generator rows in pack order (first choices, then fallbacks: ascending pack start), the output in row order
+  std::vector<int> G;
+  for (int b = 0; b < B; ++b) if (pick[b] < B) G.push_back(b);
+  for (int b = 0; b < B; ++b) if (pick[b] >= B) G.push_back(b);
+  std::vector<int> Fr(B);
+  int64_t out_tot = 0;
+  for (int b = 0, o = 0; b < B; ++b) {
+    const int z = pick[b], L = cl[z];
+    Fr[b] = C_(z, L);
+    h_win_first[b] = h_K[b] - L;
+    for (int i = 0; i < L; ++i) h_dur[o + i] = C_(z, i + 1) - C_(z, i);
+    o += h_K[b];
+    h_out_start[b] = out_tot;
+    h_n_out[b] = (int64_t)(C_(z, L) - C_(z, L - h_n_new[b])) * hop;
+    out_tot += h_n_out[b];
+  }
+  if (out_tot > out_capacity || out_tot >= (1ll << 31)) return SS_ERR_CAPACITY;
+  std::vector<int> FrG(G.size());
+  for (size_t g = 0; g < G.size(); ++g) FrG[g] = Fr[G[g]];
+  const Offsets of = prefix(FrG.data(), (int)G.size());
+  const int Ft = of.total, NG = (int)G.size();
+  if (Ft <= 0) return SS_OK;
+  if ((int64_t)Ft * hop >= (1ll << 31)) return SS_ERR_CAPACITY;
+  size_t stage_max = (size_t)Ft * c.upsample_initial_channel;
+  {
+    int T = Ft, Cc = c.upsample_initial_channel;
+    for (int i = 0; i < c.n_up; ++i) { T *= c.upsample_rates[i]; Cc /= 2; stage_max = std::max(stage_max, (size_t)T * Cc); }
+  }
+  RET(v->sc->v_ws.ensure((8 * stage_max + (size_t)Ft * E) * sizeof(float)));
+  // the picked candidates' cumulative durations where repeat_rows looks for generator row g (pack start + g; g <= its candidate
+  // index, and the pack starts ascend with g, so the ranges never overlap)
+  {
+    std::vector<int> cg((size_t)Kc + B + 1, 0);
+    for (int g = 0; g < NG; ++g) {
+      const int z = pick[G[g]];
+      for (int i = 0; i <= cl[z]; ++i) cg[(size_t)cu[z] + g + i] = C_(z, i);
+    }
+    RET(upload(s, aux, cg));
+  }
+  float* frames = v->sc->v_ws.f();
+  GenBufs gb;
+  gb.bx = frames + (size_t)Ft * E;
+  gb.bt = gb.bx + stage_max;
+  gb.br = gb.bt + stage_max;
+  gb.bs = gb.br + stage_max;
+  gb.bxa = gb.bs + stage_max;
+  gb.bra = gb.bxa + stage_max;
+  gb.bsa = gb.bra + stage_max;
+  gb.br2 = gb.bsa + stage_max;
+  int* dseg = dk + Kc + 6 * S;       // conv segs [NG][4]
+  int* drep = dseg + 4 * B;          // repeat_rows segs [NG][4]
+  auto stage_segs = [&](int scale) {
+    std::vector<int> t(4 * NG);
+    for (int g = 0; g < NG; ++g) { t[4 * g] = of.off[g] * scale; t[4 * g + 1] = FrG[g] * scale; t[4 * g + 2] = t[4 * g]; t[4 * g + 3] = t[4 * g + 1]; }
+    return upload(s, dseg, t);
+  };
+  {
+    std::vector<int> t(4 * NG);
+    for (int g = 0; g < NG; ++g) {
+      const int z = pick[G[g]];
+      t[4 * g] = cu[z]; t[4 * g + 1] = cl[z]; t[4 * g + 2] = of.off[g]; t[4 * g + 3] = FrG[g];
+    }
+    RET(upload(s, drep, t));
+  }
+  RET(launch_repeat_rows(emb, aux, 0, E, frames, of.mx, s, drep, NG));
+  int scale = 1, Cf = 0;
+  RET(hifigan_stack(v, s,
+                    [&](GemmArgs& a, int sc) {
+                      a.segs = dseg; a.nseg = NG; a.max_seg_out = of.mx * sc; a.M = Ft * sc; a.in_len = Ft * sc;
+                      return launch_conv_gemm(a, s);
+                    },
+                    stage_segs,
+                    [&](int sc, int& M, const int*& segs, int& nseg) { M = Ft * sc; segs = dseg; nseg = NG; },
+                    frames, Ft, gb, &scale, &Cf));
+  // conv_post over the kept tail of each generator row only, straight into the packed output (the crop happens here)
+  int* dpost = drep + 4 * B;         // {sample_start, n_samples, first kept, out_start} [NG]
+  std::vector<int> t(4 * NG);
+  int max_keep = 0;
+  for (int g = 0; g < NG; ++g) {
+    const int b = G[g], n = FrG[g] * scale, keep = (int)h_n_out[b];
+    t[4 * g] = of.off[g] * scale; t[4 * g + 1] = n; t[4 * g + 2] = n - keep; t[4 * g + 3] = (int)h_out_start[b];
+    max_keep = std::max(max_keep, keep);
+  }
+  RET(upload(s, dpost, t));
+  return launch_conv_post_tanh_crop(gb.bx, Cf, v->post.w, v->post.b, 0.01f, d_out, dpost, NG, max_keep, s);
+}

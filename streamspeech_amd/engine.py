@@ -206,6 +206,45 @@ class BatchMixin:
             off += n_rows[b] * up
         return (out, raws) if return_raw else out
 
+    def batch_t2u_units_pad(self, feats: torch.Tensor, n_rows: List[int], n_tail_pad: List[int], t2u_causal=False, mask_eos=False,
+                            return_raw: bool = False):
+        """:meth:`batch_t2u_units` with trailing <pad> states (ss_batch_t2u_units_pad): the last n_tail_pad[b] of row b's n_rows[b]
+        states are masked as keys, as :meth:`HipModel.t2u_units` (..., n_tail_pad) masks them; they are still decoded."""
+        B, rows = feats.shape[0], feats.shape[1]
+        if len(n_rows) != B or len(n_tail_pad) != B:
+            raise ValueError("one row count and one tail pad per row")
+        up = self.cfg.ctc_upsample
+        U = sum(n_rows) * up
+        ibuf = torch.empty((2 * U + B,), dtype=torch.int32, device=self.device)
+        raw, toks, cnt = ibuf[:U], ibuf[U:2 * U], ibuf[2 * U:]
+        L.check(self.lib.ss_batch_t2u_units_pad(self.h, _stream(), B, _ptr(feats), rows, _i32(n_rows), _i32(n_tail_pad),
+                                                int(t2u_causal), int(mask_eos), _ptr(raw), _ptr(toks), _ptr(cnt)),
+                "ss_batch_t2u_units_pad")
+        host = ibuf.cpu().numpy()
+        out, raws, off = [], [], 0
+        for b in range(B):
+            k = int(host[2 * U + b])
+            out.append(host[U + off: U + off + k].tolist())
+            raws.append(host[off: off + n_rows[b] * up].tolist())
+            off += n_rows[b] * up
+        return (out, raws) if return_raw else out
+
+    def batch_mt_features(self, enc_packed: torch.Tensor, Tp: List[int], tokens: List[List[int]], n_tail_pad: List[int]) -> List[torch.Tensor]:
+        """Decoder states of B fed rows in one ragged pass (ss_batch_mt_features): row b feeds [</s>, tokens[b]..., <pad> x
+        n_tail_pad[b]] over its encoder rows (packed as batch_mt_continue takes them).  -> per row the post-LN states [n_b, D] of every
+        fed position, as mt_truncate + mt_append(..., n_tail_pad) give them."""
+        B = len(Tp)
+        if not (len(tokens) == len(n_tail_pad) == B) or B == 0:
+            raise ValueError("one token list and one tail pad per row")
+        n = [1 + len(t) + int(p) for t, p in zip(tokens, n_tail_pad)]
+        rows = max(n)
+        feats = torch.empty((B, rows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
+        flat = [int(t) for ts in tokens for t in ts]
+        L.check(self.lib.ss_batch_mt_features(self.h, _stream(), B, _ptr(enc_packed), _i32(Tp), _i32(flat or [0]),
+                                              _i32([len(t) for t in tokens]), _i32(n_tail_pad), _ptr(feats), rows),
+                "ss_batch_mt_features")
+        return [feats[b, :n[b]] for b in range(B)]
+
 
 class Scratch:
     """One scratch set (ss_scratch: activations, KV caches, stream-K hand-off state, streaming-encoder state) -- everything a call
@@ -847,6 +886,32 @@ class HipVocoder:
                                                   _ptr(wav), cap, _ptr(dur), st, ns), "ss_batch_vocoder_forward")
         wavs = [wav[st[b]: st[b] + ns[b]] for b in range(B)]
         return wavs, dur, K
+
+    def batch_tail(self, codes: List[List[int]], n_new: List[int], ctx: List[int], rf: List[int], dur_prediction: bool = True):
+        """B rows of the agent's receptive-field tail (agent.synthesize_tail) in one call (ss_batch_vocoder_tail).  -> (per row the
+        samples of its n_new[b] new units (views into one packed buffer), per row (first unit synthesised, durations of the
+        synthesised units)).  A windowed row whose context does not cover the receptive field falls back to all its units."""
+        B = len(codes)
+        if not (len(n_new) == len(ctx) == len(rf) == B) or B == 0:
+            raise ValueError("one unit list, n_new, ctx and rf per row")
+        K = [len(c) for c in codes]
+        flat = torch.tensor([u for c in codes for u in c], dtype=torch.int32)
+        self._check_units(flat)
+        flat = flat.to(self.device)
+        cap = sum(int(n) for n in n_new) * (self.max_dur if dur_prediction else 1) * self.hop
+        out = torch.empty((max(cap, 1),), dtype=torch.float32, device=self.device)
+        first = (C.c_int32 * B)()
+        dur = (C.c_int32 * max(sum(K), 1))()
+        st, ns = (C.c_int64 * B)(), (C.c_int64 * B)()
+        L.check(self.lib.ss_batch_vocoder_tail(self.h, _stream(), B, _ptr(flat), _i32(K), _i32(n_new), _i32(ctx),
+                                               _i32([-1 if r is None else r for r in rf]), int(dur_prediction), _ptr(out), cap,
+                                               first, dur, st, ns), "ss_batch_vocoder_tail")
+        tails = [out[st[b]: st[b] + ns[b]] for b in range(B)]
+        info, off = [], 0
+        for b in range(B):
+            info.append((int(first[b]), list(dur[off: off + K[b] - first[b]])))
+            off += K[b]
+        return tails, info
 
     def __del__(self):
         try:

@@ -104,6 +104,12 @@ SIGNATURES = {
     "ss_batch_t2u_units": (_i, [_vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp]),
     "ss_batch_vocoder_forward": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _vp, _vp, _i64, _vp,
                                       C.POINTER(_i64), C.POINTER(_i64)]),
+    "ss_batch_t2u_units_pad": (_i, [_vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp]),
+    "ss_batch_mt_features": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_int32), _vp, _i]),
+    "ss_batch_vocoder_tail": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32), _i, _vp, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.POINTER(_i64), C.POINTER(_i64)]),
     "ss_prof_enable": (_i, [_i]),
     "ss_prof_reset": (_i, []),
     "ss_prof_read": (_i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(C.c_double)]),

@@ -1,0 +1,193 @@
+"""Concurrent simultaneous S2ST sessions over one session pool: the speech-output agent (StreamSpeechS2STAgent, agent.py; reference
+agent/speech_to_speech.streamspeech.agent.py) served many at a time, next to the text kinds of :class:`TextSessionPool`.  Per session,
+one :meth:`SpeechSessionPool.step` is exactly one ``StreamSpeechS2STAgent.pushpop(segment)``; across sessions a step is what a text
+pool step is (one fbank launch, one encoder step with both CTC heads, the gates on the host, ONE ragged MT continuation shared with
+the S2TT writers) and then, for the S2ST sessions that write,
+  * ONE ragged MT feature pass for the rows whose final write carries a trailing <pad> (HipModel.batch_mt_features),
+  * ONE T2U + unit decoder call with per-row tail-pad masks (HipModel.batch_t2u_units_pad),
+  * ONE receptive-field vocoder tail call (HipVocoder.batch_tail; one per duration-prediction setting in use).
+Driven by one host thread, like the pool."""
+import time
+
+import torch
+
+from .frontend import SAMPLE_RATE
+from .simuleval_shim import SpeechSegment
+from .text_pool import KINDS as TEXT_KINDS
+from .text_pool import TextSessionPool, _Session
+from .text_policy import mt_max_len, s2tt_gate
+
+KINDS = TEXT_KINDS + ("s2st",)
+# the S2ST agent's first-pass search (generator_mt): beam 1, max_len_a = 0, max_len_b = 100, min_len = 1 (agent.py)
+MAX_LEN_A, MAX_LEN_B, MIN_LEN = 0, 100, 1
+DEFAULT_EOS = 2                           # agent.py DEFAULT_EOS: the literal eos the agent tests hypotheses and units against
+
+
+def vocoder_context(vocoder_cfg, want: int):
+    """(context units, receptive field) of the agent's incremental synthesis for --vocoder-context-units `want` (agent.py)."""
+    rf = vocoder_cfg.receptive_field_frames() if vocoder_cfg is not None and hasattr(vocoder_cfg, "receptive_field_frames") else None
+    ctx = 0 if (rf is None or want == 0) else (want if want > 0 else rf + 8)
+    return ctx, rf
+
+
+def whole_word_cut(tokens, symbol):
+    """The agent's whole-word cut of a non-final hypothesis: tokens before the last word-initial ('▁') subword.  -> the cut index j
+    (as the agent's loop leaves it: 999999 for an empty list, 0 when only the first subword starts a word or none does)."""
+    j = 999999
+    for j in range(len(tokens) - 1, -1, -1):
+        if symbol(tokens[j]).startswith("▁"):
+            break
+    return j
+
+
+class _SpeechSession(_Session):
+    def __init__(self, sid, kind, args, engine, dicts, vocoder_cfg):
+        super().__init__(sid, kind, args, engine, dicts)
+        self.whole_word = args.source_segment_size >= 640
+        self.dur_prediction = bool(args.dur_prediction)
+        self.vocoder_ctx, self.vocoder_rf = vocoder_context(vocoder_cfg, getattr(args, "vocoder_context_units", -1))
+
+    def reset(self):                          # the S2ST agent's reset()
+        super().reset()
+        self.prev_output_tokens_mt = None
+        self.unit = None
+        self.unfinished_wav = None
+
+
+class SpeechSessionPool(TextSessionPool):
+    """Up to `max_sessions` concurrent S2ST, S2TT and ASR sessions over one session pool.  `vocoder`: the HipVocoder (or a
+    CodeHiFiGANVocoderWithDur, whose .hip is used) every S2ST session synthesises with; without one, S2ST sessions are refused."""
+    KINDS = KINDS
+
+    def __init__(self, model, max_sessions: int, max_rows: int, vocoder=None):
+        super().__init__(model, max_sessions, max_rows)
+        self.vocoder = getattr(vocoder, "hip", vocoder)
+        self.t2u_causal = bool(getattr(model, "uni_encoder", False))   # the agent's ctc_generator: t2u_causal = model.uni_encoder
+
+    def _check_open(self, kind, args):
+        if kind != "s2st":
+            return
+        if self.vocoder is None:
+            raise ValueError("an s2st session needs the pool's vocoder: SpeechSessionPool(..., vocoder=...)")
+        if getattr(args, "full_recompute_encoder", False):
+            raise ValueError("--full-recompute-encoder: the session pool encodes incrementally by construction")
+
+    def _new_session(self, sid, kind, args, dicts):
+        if kind != "s2st":
+            return super()._new_session(sid, kind, args, dicts)
+        return _SpeechSession(sid, kind, args, self.model, dicts, getattr(self.vocoder, "cfg", None))
+
+    # ---- the S2ST agent's policy, split at the pool's shared calls ---------------------------------------------------------------
+    def _gate(self, s, src_ids, tgt_ids, n_frames):
+        """agent.py policy(): the CTC-count gate (+1 subword in whole-word mode), then the search length of the MT call."""
+        n_committed = len(s.tgt_subwords) if s.tgt_subwords is not None else 0
+        # subword_tokens + 1 - n_committed == subword_tokens - (n_committed - 1): the S2TT gate with one subword fewer committed
+        g = s2tt_gate(len(src_ids), len(tgt_ids), s.src_ctc_prefix_length, s.tgt_ctc_prefix_length,
+                      n_committed - (1 if s.whole_word else 0), s.lagging_k1, s.stride_n, s.states.source_finished)
+        s.src_ctc_prefix_length, s.tgt_ctc_prefix_length = g.src_prefix_len, g.tgt_prefix_len
+        if not g.write:
+            return ("read",)
+        prefix = list(s.tgt_subwords) if s.tgt_subwords is not None else []
+        ml = mt_max_len(len(prefix), n_frames, g.new_tokens, MAX_LEN_A, MAX_LEN_B, self.model.cfg.max_target_positions, MIN_LEN)
+        return ("write", prefix, ml, g.new_tokens)
+
+    def _finish_empty(self, s):
+        return ("speech", list(s.unfinished_wav.tolist()) if s.unfinished_wav is not None else [], True, False)
+
+    def _mt_decide(self, s, toks):
+        """The agent's host decisions between the MT search and T2U.  -> (action or None, n_tokens to keep, n_tail_pad)."""
+        fin = s.states.source_finished
+        hyp = list(toks)
+        tsi = hyp[:-1] if hyp[-1] == DEFAULT_EOS else list(hyp)
+        if s.whole_word and not fin:
+            j = whole_word_cut(tsi, lambda t: s.dict["target_unigram"][t])
+            tsi, hyp = tsi[:j], hyp[:j]
+            if j == 0:
+                return ("read",), 0, 0
+        eos = self.model.cfg.eos
+        max_tgt_len = len(hyp) + (1 if s.whole_word else 0)
+        tmp = hyp[:-1] if len(hyp) > 0 and hyp[-1] == eos else hyp
+        n_tail_pad = max_tgt_len - (len(tmp) + 1)
+        assert n_tail_pad in (0, 1), "hypothesis without eos outside whole-word mode (the reference fails here too)"
+        prev = [eos] + tmp + [self.model.cfg.pad] * n_tail_pad
+        if s.tgt_subwords is not None and list(s.tgt_subwords) == tsi:
+            return (("read",) if not fin else self._finish_empty(s)), 0, 0
+        s.tgt_subwords = tsi
+        if not fin and s.prev_output_tokens_mt is not None:
+            if s.prev_output_tokens_mt == prev or len(prev) <= len(s.prev_output_tokens_mt):
+                return ("read",), 0, 0
+        s.prev_output_tokens_mt = prev
+        return None, len(tmp), n_tail_pad
+
+    def _write_side(self, mine, views, actions):
+        t0 = time.perf_counter()
+        D = self.model.cfg.dec_dim
+        rows = []                                         # (session, mt states [n, D], n_tail_pad)
+        pads = []                                         # (index in rows, session's encoder view index, tokens)
+        for (i, s, prefix, ml, new), toks, fts in mine:
+            a, n_tok, n_pad = self._mt_decide(s, prefix + toks)
+            if a is not None:
+                actions[s.sid] = a
+                continue
+            if n_pad:
+                pads.append((len(rows), i, list(s.prev_output_tokens_mt[1:n_tok + 1])))
+            rows.append((s, fts[:n_tok + 1], n_pad))
+        feats = [f for _, f, _ in rows]
+        if pads:
+            # the trailing <pad> state of every final whole-word write: ONE ragged feature pass
+            enc = torch.cat([views[i] for _, i, _ in pads], 0)
+            pf = self.model.batch_mt_features(enc, [views[i].shape[0] for _, i, _ in pads], [t for _, _, t in pads],
+                                              [1] * len(pads))
+            for (r, _, _), f in zip(pads, pf):
+                feats[r] = torch.cat((feats[r], f[-1:]), 0)
+        t1 = time.perf_counter()
+        voc = []
+        if rows:
+            n = [f.shape[0] for f in feats]
+            packed = torch.zeros((len(rows), max(n), D), dtype=torch.float32, device=feats[0].device)
+            for r, f in enumerate(feats):
+                packed[r, :f.shape[0]] = f
+            units = self.model.batch_t2u_units_pad(packed, n, [p for _, _, p in rows], t2u_causal=self.t2u_causal)
+            for (s, _, _), toks in zip(rows, units):
+                fin = s.states.source_finished
+                if len(toks) == 0:
+                    actions[s.sid] = ("read",) if not fin else self._finish_empty(s)
+                    continue
+                if toks[-1] == DEFAULT_EOS:
+                    toks = toks[:-1]
+                unit = []
+                for c in toks:
+                    u = s.dict["tgt"][c].replace("<s>", "").replace("</s>", "")
+                    if u != "":
+                        unit.append(int(u))
+                cur = unit if s.unit is None else unit[len(s.unit):]
+                if len(unit) < 1 or len(cur) < 1:
+                    actions[s.sid] = ("read",) if not fin else self._finish_empty(s)
+                    continue
+                voc.append((s, unit, len(cur)))
+        t2 = time.perf_counter()
+        for dp in (True, False):
+            grp = [v for v in voc if v[0].dur_prediction == dp]
+            if not grp:
+                continue
+            tails, _ = self.vocoder.batch_tail([u for _, u, _ in grp], [k for _, _, k in grp], [s.vocoder_ctx for s, _, _ in grp],
+                                               [s.vocoder_rf for s, _, _ in grp], dur_prediction=dp)
+            for (s, unit, _), wav in zip(grp, tails):
+                if s.unfinished_wav is not None and len(s.unfinished_wav) > 0:
+                    wav = torch.cat((s.unfinished_wav, wav), 0)
+                s.unit = unit
+                # a final write (new_tokens == -1) ends with the agent's reset(), which runs BEFORE the agent builds its segment and
+                # clears source_finished: no write says finished=True
+                actions[s.sid] = ("speech", wav.tolist(), False, s.states.source_finished)
+        t3 = time.perf_counter()
+        self._side_times = {"mt_features_s": t1 - t0, "units_s": t2 - t1, "vocoder_s": t3 - t2,
+                            "speech_writers": len(voc)}
+
+    def _segment(self, s, a):
+        if a[0] == "write":                               # the front-end's early return of a finished source: no speech
+            return SpeechSegment(index=0, content=[], sample_rate=SAMPLE_RATE, finished=True)
+        _, content, finished, done = a
+        if done:                                          # the agent's reset(): a fresh utterance, its slot back to the pool
+            s.reset()
+            self._release(s)
+        return SpeechSegment(index=0, content=content, sample_rate=SAMPLE_RATE, finished=finished)

@@ -69,6 +69,7 @@ class _Session:
 
 class TextSessionPool:
     """Up to `max_sessions` concurrent ASR / S2TT sessions, each of at most `max_rows` encoder output rows (~40 ms each)."""
+    KINDS = KINDS
 
     def __init__(self, model, max_sessions: int, max_rows: int):
         self.model = model.hip if hasattr(model, "hip") else model
@@ -78,20 +79,28 @@ class TextSessionPool:
         self.free = list(range(self.max_sessions))
         self._next = 0
         self.last_step: dict = {}              # timings / counts of the last step (tools/pooled_text_bench.py)
+        self._side_times: dict = {}            # timings a subclass's write side adds to last_step
 
     # ---- lifecycle ------------------------------------------------------------------------------------------------------------
     def open(self, kind: str, args, dicts: Optional[dict] = None) -> int:
         """A new session; `args` are the agent's own parsed flags (segment size, lagging_k1, stride_n, sample rate, chunk sizes).
         `dicts` overrides the dictionaries the agent would load from the flags (keys source_unigram / target_unigram)."""
-        if kind not in KINDS:
-            raise ValueError(f"session kind {kind!r}: one of {KINDS}")
+        if kind not in self.KINDS:
+            raise ValueError(f"session kind {kind!r}: one of {self.KINDS}")
+        self._check_open(kind, args)
         if dicts is None:
             from .agent import load_dictionaries
             dicts = load_dictionaries(args, self.model.cfg)
         sid = self._next
         self._next += 1
-        self.sessions[sid] = _Session(sid, kind, args, self.model, dicts)
+        self.sessions[sid] = self._new_session(sid, kind, args, dicts)
         return sid
+
+    def _check_open(self, kind: str, args):
+        """Refusals of open() beyond the kind (subclasses: ValueError)."""
+
+    def _new_session(self, sid, kind, args, dicts):
+        return _Session(sid, kind, args, self.model, dicts)
 
     def reset(self, sid: int):
         """The agent's reset(): the session starts a fresh utterance (its slot goes back to the pool until it next has audio)."""
@@ -203,7 +212,7 @@ class TextSessionPool:
         t1 = time.perf_counter()
         # ---- one encoder step + both CTC heads ----
         enc = [s for s in todo if s.sid in feats]
-        writers, n_steps = [], 0
+        writers, n_steps, mine, views = [], 0, [], None
         if enc:
             for s in enc:
                 self._acquire(s)
@@ -214,6 +223,13 @@ class TextSessionPool:
             for i, s in enumerate(enc):
                 if s.kind == "asr":
                     actions[s.sid] = self._asr(s, src[i][0])
+                    continue
+                if s.kind not in KINDS:           # a subclass's kind: its own gate -> an action, or a writer (prefix, max_len, new)
+                    w = self._gate(s, src[i][0], tgt[i][0], feats[s.sid].shape[0])
+                    if w[0] == "write":
+                        writers.append((i, s) + tuple(w[1:]))
+                    else:
+                        actions[s.sid] = w
                     continue
                 g = s2tt_gate(len(src[i][0]), len(tgt[i][0]), s.src_ctc_prefix_length, s.tgt_ctc_prefix_length,
                               len(s.tgt_subwords) if s.tgt_subwords is not None else 0, s.lagging_k1, s.stride_n,
@@ -235,12 +251,18 @@ class TextSessionPool:
                     Tp = [views[i].shape[0] for i, _, _, _, _ in writers]
                 res = self.model.batch_mt_continue(enc_w, Tp, [p for _, _, p, _, _ in writers], [m for _, _, _, m, _ in writers],
                                                    MIN_LEN)
-                for (i, s, prefix, ml, new), (toks, _) in zip(writers, res):
+                for w, (toks, fts) in zip(writers, res):
+                    i, s, prefix, ml, new = w
                     n_steps = max(n_steps, len(toks) - 1)
-                    actions[s.sid] = self._s2tt_write(s, prefix + toks, new)
+                    if s.kind in KINDS:
+                        actions[s.sid] = self._s2tt_write(s, prefix + toks, new)
+                    else:
+                        mine.append((w, toks, fts))
         else:
             t2 = t1
         t3 = time.perf_counter()
+        if mine:                                  # a subclass's write side after the shared MT call (its own timings)
+            self._write_side(mine, views, actions)
         # ---- actions -> segments, as GenericAgent.pop ----
         for s in todo:
             if s.sid in out:
@@ -249,6 +271,9 @@ class TextSessionPool:
             if a[0] == "read":
                 out[s.sid] = EmptySegment()
                 continue
+            if s.kind not in KINDS:               # a subclass's kind makes its own segment
+                out[s.sid] = self._segment(s, a)
+                continue
             seg = TextSegment(index=0, content=a[1], finished=a[2])
             s.states.update_target(seg)
             out[s.sid] = seg
@@ -256,7 +281,21 @@ class TextSessionPool:
                 self._release(s)                  # from now on, so its slot goes back; reset(sid) starts a fresh utterance
         self.last_step = {"sessions": len(todo), "encoded": len(enc), "writers": len(writers), "mt_steps": n_steps,
                           "frontend_s": t1 - t0, "encoder_ctc_s": t2 - t1, "mt_s": t3 - t2, "total_s": time.perf_counter() - t0}
+        self.last_step.update(self._side_times)
+        self._side_times = {}
         return out
+
+    # ---- hooks of a subclass's session kinds (speech_pool.py) -------------------------------------------------------------------
+    def _gate(self, s, src_ids, tgt_ids, n_frames):
+        """-> ("write", prefix, max_len, new_tokens) to join the step's MT call, or the session's action."""
+        raise NotImplementedError(s.kind)
+
+    def _write_side(self, mine, views, actions):
+        """After the MT call: [((i, s, prefix, max_len, new), tokens, decoder states)] of this kind's writers -> actions[sid]."""
+        raise NotImplementedError
+
+    def _segment(self, s, a):
+        raise NotImplementedError(s.kind)
 
     # ---- the agents' write paths ------------------------------------------------------------------------------------------------
     def _finish(self, s: _Session):
