@@ -17,9 +17,11 @@ profiles/r06_stream_sweep.txt).  Packs: 32 in rounds 1-3, 64 in round 4, 128 sin
 tests/test_pack_invariance_gpu.py); with --batch 1 a step is one utterance through the single-utterance entry points.
 stdout carries ONE line under 6 KB (compact_line); the full result goes to the sidecar bench_detail.json (SS_BENCH_DETAIL) and to stderr.
 --dump-outputs DIR writes what the last timed step returned as DIR/*.npy (dump_outputs), to compare two builds on the same inputs.
-value = total audio seconds / wall seconds over all ranks (RTFx; higher is better); the line also
-carries utterances/sec, the roofline of the dominant kernel (HIP events recorded on the launch
-stream inside the timed region) and the CPU oracle timed on this box's host cores (rank 0, N=1).
+value = total audio seconds / wall seconds over all ranks (RTFx; higher is better).
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line -- nothing else.  --full adds every
+other leg: the single-stream latency pass, the one-stream replay that gives the roofline of the dominant kernel, the soak,
+the event-bracket A/B, the split-bf16 and three-language lines, the pack-invariance and RCCL checks, the CPU oracle timed on
+the host cores (rank 0, N=1) and the 320-ms streaming leg.
 """
 import argparse
 import ctypes as C
@@ -314,7 +316,7 @@ def _agent_args(segment_ms, **over):
     return a
 
 
-def streaming_measure(model, voc, lib, cfg, segment_ms=320, n_utts=12, cpu_sd=None, cpu_utts=0, long_seconds=(), configurations=None):
+def streaming_measure(model, voc, lib, cfg, segment_ms=320, n_utts=12, cpu_sd=None, cpu_utts=0, long_seconds=()):
     """BASELINE.json configs[2]: the drop-in SimulEval agent (streamspeech_amd/agent.py) fed `segment_ms` chunks of synthetic
     CVSS-C-shaped utterances, one at a time -- with the incremental encoder + receptive-field vocoder tail (default)
     and with the reference's full recompute at every policy() call (agent :425-435, 686-689, 748-751).  With `cpu_sd`
@@ -374,8 +376,6 @@ def streaming_measure(model, voc, lib, cfg, segment_ms=320, n_utts=12, cpu_sd=No
     # default with the final search left to run to the reference's 100-token cap (what random weights do without the pin)
     for name, over in (("incremental", {}), ("full_recompute", {"full_recompute_encoder": True, "vocoder_context_units": 0}),
                        ("incremental_launch_per_op_mt", {"mt_step_workgroups": 0}), ("incremental_search_to_cap", {})):
-        if configurations is not None and name not in configurations:
-            continue
         agent = StreamSpeechS2STAgent(_agent_args(segment_ms, **over), model=StreamSpeechModel.from_engine(model), vocoder=VocSurface(voc))
         if name != "incremental_search_to_cap":
             pin_final_search(agent)
@@ -831,22 +831,24 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=16, help="timed steps per GPU (one step = one ragged batch of --batch utterances)")
     ap.add_argument("--warmup", type=int, default=3, help="untimed warm-up steps per GPU before the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle leg")
     ap.add_argument("--bf16x3-line", action="store_true", help="also run the optional split-bf16 vocoder-conv leg (same batches; never the headline)")
     ap.add_argument("--no-prof", action="store_true", help="do not bracket the dominant kernel with HIP events")
     ap.add_argument("--bracket-ab", action="store_true", help="also run the event-bracket on / off A/B of the timed region (five more region passes)")
     ap.add_argument("--full", action="store_true",
-                    help="every optional leg at its long form (bracket A/B, bf16x3, 8-stream batch-1 pass, launch-per-op latency A/B, streaming: three "
-                         "agent configurations + CPU leg + long-prefix sweep); the default keeps the command under about a minute")
-    ap.add_argument("--no-multilingual", action="store_true", help="skip the configs[4] sub-object (fr/es/de weight sets resident together)")
-    ap.add_argument("--no-streaming-line", action="store_true", help="skip the configs[2] sub-object (320-ms agent policy() loop + its CPU baseline)")
+                    help="run every leg besides the headline: latency pass (+ launch-per-op A/B, 8-stream batch-1 pass), one-stream roofline replay, "
+                         "soak, bracket A/B, bf16x3, configs[4], pack-invariance and RCCL checks, CPU baseline, streaming (three agent "
+                         "configurations + CPU leg + long-prefix sweep); the --no-* options below drop single legs of it.  Without --full "
+                         "the command sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-multilingual", action="store_true", help="--full: skip the configs[4] sub-object (fr/es/de weight sets resident together)")
+    ap.add_argument("--no-streaming-line", action="store_true", help="--full: skip the configs[2] sub-object (320-ms agent policy() loop + its CPU baseline)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (default): --steps batches PER GPU; strong: --steps batches in TOTAL (configs[3] literally: "
                          "steps x batch utterances / N per GPU)")
     ap.add_argument("--streams", type=int, default=4,
                     help="concurrent HIP streams per GPU, a scratch set each (4: within 1 %% of 8 at half the HBM -- profiles/r06_stream_sweep.txt)")
-    ap.add_argument("--no-latency-pass", action="store_true", help="skip the single-stream latency measurement")
-    ap.add_argument("--no-soak", action="store_true", help="skip the >= 100-step sustained passes after the timed region")
+    ap.add_argument("--no-latency-pass", action="store_true", help="--full: a one-utterance latency pass, without the launch-per-op A/B and the 8-stream batch-1 pass")
+    ap.add_argument("--no-soak", action="store_true", help="--full: skip the >= 100-step sustained passes after the timed region")
     ap.add_argument("--batch", type=int, default=128,
                     help="utterances packed per ragged batch (1 = the one-utterance-at-a-time entry points)")
     ap.add_argument("--mode", choices=("offline", "streaming"), default="offline",
@@ -859,7 +861,7 @@ def main():
     ap.add_argument("--dry-plan", action="store_true",
                     help="no GPU: form every rank's plan and run the barrier + statistics reductions over gloo (the N > 1 control path)")
     ap.add_argument("--rccl-probe", action="store_true", help="internal: world-of-one RCCL initialisation + the DP collectives, one JSON object")
-    ap.add_argument("--no-rccl-probe", action="store_true", help="skip the RCCL probe of the N = 1 line")
+    ap.add_argument("--no-rccl-probe", action="store_true", help="--full: skip the RCCL probe of the N = 1 line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed region, write what its last step returned (waveforms, CTC / MT ids) to DIR/<name>.npy "
                          "(float32 / float64, <= 64 MB; rank 0) -- the inputs are seeded, so two builds compare output for output")
@@ -868,6 +870,8 @@ def main():
         ap.error("--dump-outputs applies to the offline timed region (not --mode streaming / --dry-plan)")
     if args.full:
         args.bracket_ab = args.bf16x3_line = True
+    elif args.mode == "offline":               # a plain run: the headline alone (the latency pass, the replay and the checks test args.full)
+        args.no_soak = args.no_multilingual = args.no_cpu_baseline = args.no_rccl_probe = args.no_streaming_line = True
     args.no_bracket_ab, args.no_bf16x3_line = not args.bracket_ab, not args.bf16x3_line
     t_process = time.perf_counter()
     legs = {}                                  # seconds per leg of this command (sidecar)
@@ -955,30 +959,31 @@ def main():
         lib.ss_prof_enable(0)
         lib.ss_prof_reset()
 
-    # single-stream latency pass (untimed for `value`; reported as latency_ms_single_stream): one utterance at a time on the
+    # single-stream latency pass (--full; untimed for `value`; reported as latency_ms_single_stream): one utterance at a time on the
     # primary context, whose MT decode step is the persistent one-launch form by default (engine.HipModel; the batched /
     # multi-stream paths of this file never use it) -- and the same utterances with the launch-per-op step for comparison
     pmt_default = int(getattr(model, "persistent_mt", 0))
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    nlat = 1 if args.no_latency_pass else min(Kpool, 8)
-    lat_idx = list(range(Wn, Wn + Kpool))[::max(1, Kpool // nlat)][:nlat]   # evenly spread over the length-sorted pool
-    for i in lat_idx:
-        run_utterance(model, voc, pcms[i], mine[i])
-    torch.cuda.synchronize()
-    single_ms = 1e3 * (time.perf_counter() - t0) / nlat
-    single_rtfx = sum(mine[i].seconds for i in lat_idx) / (single_ms * 1e-3 * nlat)
-    pmt_after = int(getattr(model, "persistent_mt", 0))      # 0 if the persistent step timed out and the context fell back
-    single_ms_lpo = None
-    if args.full and not args.no_latency_pass and hasattr(model, "set_persistent_mt_step"):
-        model.set_persistent_mt_step(0)
-        run_utterance(model, voc, pcms[lat_idx[0]], mine[lat_idx[0]])
+    single_ms = single_rtfx = pmt_after = single_ms_lpo = None
+    if args.full:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        nlat = 1 if args.no_latency_pass else min(Kpool, 8)
+        lat_idx = list(range(Wn, Wn + Kpool))[::max(1, Kpool // nlat)][:nlat]   # evenly spread over the length-sorted pool
         for i in lat_idx:
             run_utterance(model, voc, pcms[i], mine[i])
         torch.cuda.synchronize()
-        single_ms_lpo = 1e3 * (time.perf_counter() - t0) / nlat
+        single_ms = 1e3 * (time.perf_counter() - t0) / nlat
+        single_rtfx = sum(mine[i].seconds for i in lat_idx) / (single_ms * 1e-3 * nlat)
+        pmt_after = int(getattr(model, "persistent_mt", 0))      # 0 if the persistent step timed out and the context fell back
+        if not args.no_latency_pass and hasattr(model, "set_persistent_mt_step"):
+            model.set_persistent_mt_step(0)
+            run_utterance(model, voc, pcms[lat_idx[0]], mine[lat_idx[0]])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in lat_idx:
+                run_utterance(model, voc, pcms[i], mine[i])
+            torch.cuda.synchronize()
+            single_ms_lpo = 1e3 * (time.perf_counter() - t0) / nlat
     if hasattr(model, "set_persistent_mt_step"):
         model.set_persistent_mt_step(0)       # from here on this context runs next to seven others: launch-per-op (see HipModel.new_context)
 
@@ -1096,7 +1101,7 @@ def main():
     per_rank = dp.gather_per_rank(dist, wall, audio, float(K), device=dev, placement=placement)
     wall, audio, nutt = dp.reduce_stats(dist, wall, audio, float(K), device=dev)
     rccl = None
-    if dist is not None:                     # the DP path's collectives on the live communicator (untimed for `value`)
+    if dist is not None and args.full:       # the DP path's collectives on the live communicator (untimed for `value`)
         rccl = comm_probe(dist, dev if dist.get_backend() == "nccl" else "cpu")
         rccl["how"] = ("this process group: the barriers around the timed region and the MAX / SUM / all-gather of the statistics above went "
                        "through it" + ("; SS_FORCE_DIST=1 (world of one)" if force_dist else ""))
@@ -1188,7 +1193,8 @@ def main():
     roofline, roofline_conv = in_region, in_region_conv
     roofline_family, dispatch = None, None
     WINO = [c for c in range(lib.ss_prof_num_classes()) if lib.ss_prof_class_name(c).decode().startswith(("conv_c64w", "conv_c128w", "conv_c32w", "conv_c256w"))]
-    if rank == 0 and dom is not None and S > 1 and work and not os.environ.get("SS_BENCH_NO_REPLAY"):   # (ranks > 0 run no optional leg)   # (tools/jobs/*trace*: keep the trace to the timed region)
+    roofline_in_region = None
+    if args.full and rank == 0 and dom is not None and S > 1 and work and not os.environ.get("SS_BENCH_NO_REPLAY"):   # (ranks > 0 run no optional leg; SS_BENCH_NO_REPLAY: `tools/gpu_job.sh trace` keeps its trace to the timed region)
         lib.ss_prof_reset()
         mask = (1 << dom) | ((1 << dom_conv) if dom_conv is not None else 0)
         for c in WINO:
@@ -1246,6 +1252,10 @@ def main():
                 r["measured_on"] = (f"the {len(work)} timed batches replayed on one stream right after the timed region "
                                     f"(replay wall {rep_wall * 1e3:.1f} ms); HIP events on the launch stream around every launch")
                 r["in_region"] = region_stats(reg)
+    elif S > 1 and not args.full:
+        # a plain run replays nothing, and an S-stream bracket is no kernel figure: the region's sums go to the sidecar alone
+        roofline_in_region = [{"kernel": r["kernel"], **region_stats(r)} for r in (in_region, in_region_conv) if r] or None
+        roofline = roofline_conv = None
     elif roofline:
         roofline["measured_on"] = "the timed region itself (one stream); HIP events on the launch stream around every launch"
 
@@ -1310,7 +1320,7 @@ def main():
     soak = None
     try:
         if world == 1 and Bsz > 1 and S > 1 and work and not args.no_soak:
-            reps = max(1, -(-(100 if args.full else 48) // len(work)))
+            reps = max(1, -(-100 // len(work)))
             dts = [region_pass() for _ in range(reps)]
             soak = {"steps": reps * len(work), "value": round(reps * audio / sum(dts), 2), "unit": "x real-time", "ms_per_step": round(1e3 * sum(dts) / (reps * len(work)), 3),
                     "utterances": int(reps * nutt), "gpu_seconds": round(sum(dts), 3), "per_pass_value": [round(audio / d, 1) for d in dts],
@@ -1367,7 +1377,7 @@ def main():
                 per_lang[lang] = {wi: ((m, v) if wi == 0 else (m.new_context(scratch=scratches[wi]), v.new_context(scratch=scratches[wi]))) for wi in range(S)}
             pick = lambda wi, i: per_lang[order[i % 3]][wi]   # noqa: E731   batch i is of language i % 3, on whichever stream takes it
             region_pass(pick)                                  # warm pass
-            n_best = 2 if args.full else 1
+            n_best = 2
             dt_ml = min(region_pass(pick) for _ in range(n_best))
             dt_1 = min(region_pass() for _ in range(n_best))  # the single-language set through the same queues, same moment
             multilingual = {"value": round(audio / dt_ml, 2), "unit": "x real-time (audio s / wall s)", "utterances_per_sec": round(nutt / dt_ml, 3),
@@ -1438,14 +1448,16 @@ def main():
                                          "sequence cyclically resized to K = ceil(37 d), durations forced to the (1,1,2) cycle",
                        "length_bucketed_batches": (not args.no_length_bucketing) and Bsz > 1, "utterances_per_ragged_batch": Bsz, "concurrent_streams_per_gpu": S,
                        "parallelism": f"utterance-dp{world}"},
-            "latency_ms_single_stream": round(single_ms, 3), "rtfx_single_stream": round(single_rtfx, 2),
+            "latency_ms_single_stream": None if single_ms is None else round(single_ms, 3),
+            "rtfx_single_stream": None if single_rtfx is None else round(single_rtfx, 2),
             "latency_ms_single_stream_launch_per_op_mt_step": None if single_ms_lpo is None else round(single_ms_lpo, 3),
             "single_stream_mt_step": {"persistent_workgroups_default": pmt_default, "after_the_pass": pmt_after},
             "batch1_8streams": None if b1_rtfx is None else {"rtfx": round(b1_rtfx, 1), "utterances_per_sec": round(b1_ups, 1),
                                                              "note": "one utterance per call (no ragged packs), 8 concurrent streams, 64 utterances"},
-            "pack_invariance": pack_invariance_check(model, work) if (Bsz > 1 and len(work) >= 2) else None,
+            "pack_invariance": pack_invariance_check(model, work) if (args.full and Bsz > 1 and len(work) >= 2) else None,
             "stream_k_spin_timeouts": int(lib.ss_debug_sk_errors()),   # must be 0 (bounded waits of the stream-K fix-up); also asserted for the timed region
             "roofline": roofline,
+            "roofline_in_region": roofline_in_region,
             "roofline_family": roofline_family,
             "soak": soak,
             "hbm": hbm,
@@ -1468,7 +1480,7 @@ def main():
         t_leg = time.perf_counter()
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd, vsd, cfg, vcfg, workload.make_utterances(Wn + Kpool + 1)[Wn:], hip_model=model, dev=dev,
-                                               reps=5, warm=2, budget_s=30.0 if args.full else 25.0)     # ~10 s of CPU work on the GPU box's host
+                                               reps=5, warm=2, budget_s=30.0)
             out["near_tie_rows"] = out["cpu_baseline"]["oracle_check"]["near_tie_rows"]
         else:
             out["cpu_baseline"] = None
@@ -1477,14 +1489,12 @@ def main():
         t_leg = time.perf_counter()
         out["streaming_320ms"] = None
         if world == 1 and not args.no_streaming_line:
-            # BASELINE.json configs[2] inside the driver's line: the agent's policy() loop on 320-ms segments with the incremental state
-            # (--full: also the reference's full recompute, the launch-per-op A/B, the CPU baseline on the same utterances and the
-            # long-source sweep -- `bench.py --mode streaming` prints those as its own line).  A failing optional leg never costs the line.
+            # BASELINE.json configs[2] (--full): the agent's policy() loop on 320-ms segments with the incremental state, the reference's
+            # full recompute, the launch-per-op A/B, the CPU baseline on the same utterances and the long-source sweep (`bench.py --mode
+            # streaming` prints the same as its own line).  A failing optional leg never costs the line.
             try:
-                st = streaming_measure(model, voc, lib, cfg, 320, args.utterances if args.full else min(args.utterances, 6),
-                                       cpu_sd=(sd, vsd, vcfg) if (args.full and not args.no_cpu_baseline) else None,
-                                       cpu_utts=3, long_seconds=(15, 30) if args.full else (),
-                                       configurations=None if args.full else ("incremental",))
+                st = streaming_measure(model, voc, lib, cfg, 320, args.utterances, cpu_sd=None if args.no_cpu_baseline else (sd, vsd, vcfg),
+                                       cpu_utts=3, long_seconds=(15, 30))
                 for k in ("metric", "mode", "n_gpus", "dtype", "data", "higher_is_better"):
                     st.pop(k, None)
                 out["streaming_320ms"] = st

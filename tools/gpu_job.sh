@@ -4,7 +4,7 @@
 # Everything lands under gpurun_out/$TAG/ (scratch); copy what should be judged into profiles/ with tools/collect_evidence.sh.
 # Tasks:
 #   tests            pytest -m gpu + smoke + the measured-configuration parity log
-#   bench [args]     the driver's command (python bench.py [args]) + its sidecar
+#   bench [args]     the benchmark with every leg (python bench.py --full [args]) + its sidecar
 #   profile          rocprofv3 --kernel-trace --stats of the 8-stream command and of the one-stream form, share / roofline tables
 #   pmc              three separate PMC passes (FETCH_SIZE / WRITE_SIZE / MfmaUtil; --kernel-trace only, as MI355X_MICROARCH.md
 #                    prescribes) of the one-stream form -> pmc_traffic.json (what bench.py's roofline.traffic reads once copied to profiles/)
@@ -32,7 +32,7 @@ task_tests() {
   tail -3 $O/bench_config_parity.log | cut -c1-300
 }
 task_bench() {
-  bench bench "$@"
+  bench bench --full "$@"
   python -c "import json; d=json.load(open('$O/bench.json')); print(len(open('$O/bench.json').read()), 'bytes;', {k: d.get(k) for k in ('value','ms_per_step','soak','multilingual','streaming_320ms','near_tie_rows','hbm_in_use_gb')}); print(d.get('roofline'))"
 }
 task_profile() {
