@@ -44,8 +44,8 @@ extern "C" int ss_batch_encoder_forward(ss_model* m, void* stream, int B, const 
   }
   const Offsets o0 = prefix(h_T, B), o1 = prefix(T1.data(), B), o2 = prefix(T2.data(), B);
   const int M1 = o1.total, M2 = o2.total;
-  const int cchunk = (conv_chunk > 0 && conv_chunk < 999) ? conv_chunk : 0;
-  const int achunk = attn_chunk > 0 && attn_chunk < 999999 ? attn_chunk : 0;
+  const int cchunk = conv_chunk_cfg(conv_chunk);
+  const int achunk = attn_chunk_cfg(attn_chunk);
 
   // segment tables: conv0 {out,in}, conv1 {out,in}, attention {q,k}, rows {start,len}
   std::vector<int> tab(14 * B);
@@ -71,54 +71,34 @@ extern "C" int ss_batch_encoder_forward(ss_model* m, void* stream, int B, const 
   float* g2 = g + n_x;
   float* ff = g2 + n_x;
   float* qkv = ff + n_f;
-  {
-    GemmArgs a;
-    a.A = d_fbank; a.lda = c.input_feat; a.W = m->sub0.w; a.bias = m->sub0.b; a.C = h1; a.ldc = c.conv_channels / 2;
-    a.N = c.conv_channels; a.Cin = c.input_feat; a.taps = k; a.stride = 2; a.pad = k / 2; a.chunk = cchunk; a.glu = 1;
-    a.segs = d0; a.nseg = B; a.max_seg_out = o1.mx; a.M = M1; a.in_len = o0.total;
-    RET(launch_conv_gemm(a, s));
-    GemmArgs b2;
-    b2.A = h1; b2.lda = c.conv_channels / 2; b2.W = m->sub1.w; b2.bias = m->sub1.b; b2.C = g; b2.ldc = d;
-    b2.N = 2 * d; b2.Cin = c.conv_channels / 2; b2.taps = k; b2.stride = 2; b2.pad = k / 2; b2.chunk = cchunk; b2.glu = 1;
-    b2.segs = d1; b2.nseg = B; b2.max_seg_out = o2.mx; b2.M = M2; b2.in_len = M1;
-    RET(launch_conv_gemm(b2, s));
-  }
+  GemmArgs a, b;
+  subsampler_args(m, d_fbank, h1, g, a, b);
+  a.chunk = cchunk; a.segs = d0; a.nseg = B; a.max_seg_out = o1.mx; a.M = M1; a.in_len = o0.total;
+  b.chunk = cchunk; b.segs = d1; b.nseg = B; b.max_seg_out = o2.mx; b.M = M2; b.in_len = M1;
+  RET(launch_conv_gemm(a, s));
+  RET(launch_conv_gemm(b, s));
   RET(linear(s, g, d, M2, m->enc_linear, d, d, x, d));
   for (int l = 0; l < c.enc_layers; ++l) {
     const EncLayer& e = m->enc[l];
-    // macaron FFN: x += 0.5 * W2 SiLU(W1 LN(x)); packed batches: ONE launch (ffn.hip), the [rows, 2048] hidden tile stays on chip
+    // the macaron FFNs of packed batches: ONE launch each (ffn.hip), the [rows, 2048] hidden tile stays on chip
     // (pack-invariant contexts: ALWAYS the fused launch in its whole-tile form -- the two-launch form sums the 2048 hidden terms in
     //  another order, and which of the two runs must not depend on the row count)
     const bool fuse_ffn = (canon || (disp().ffn_fusion && M2 >= disp().ffn_min_rows)) && ffn_fused_eligible(d, f, ACT_SILU, M2, d, d, canon) &&
                           e.ffn1_w1.b && e.ffn1_w2.b && e.ffn2_w1.b && e.ffn2_w2.b;
     if (canon && !fuse_ffn) return SS_ERR_ARG;      // never switch FFN forms silently in a pack-invariant context (the two-launch form sums in another order)
-    if (fuse_ffn) {
-      RET(launch_ffn_fused(x, d, x, d, e.ffn1_ln.g, e.ffn1_ln.b, e.ffn1_w1.w, e.ffn1_w1.b, e.ffn1_w2.w, e.ffn1_w2.b, 0.5f, nullptr,
-                           nullptr, M2, d, f, s, canon));
-    } else {
-      RET(ln_linear(s, x, M2, e.ffn1_ln, e.ffn1_w1, f, d, ff, f, h, ACT_SILU));
-      RET(linear(s, ff, f, M2, e.ffn1_w2, d, f, x, d, ACT_NONE, 0.5f, x, d));
-    }
-    RET(ln_linear(s, x, M2, e.attn_ln, e.qkv, 3 * d, d, qkv, 3 * d, h));
-    AttnArgs at;
-    at.Q = qkv; at.K = qkv + d; at.V = qkv + 2 * d; at.ldq = at.ldk = at.ldv = 3 * d;
-    at.O = h; at.ldo = d; at.H = c.enc_heads; at.scale = 0.125f; at.chunk = achunk;
-    at.P = m->pos_proj + (size_t)l * d; at.ldp = Ld; at.p_tmax = c.max_rel_pos; at.bias_u = e.u; at.bias_v = e.v;
-    at.segs = da; at.nseg = B; at.max_q = o2.mx;
-    RET(launch_attention(at, s));
-    RET(linear(s, h, d, M2, e.out, d, d, x, d, ACT_NONE, 1.f, x, d));
-    RET(ln_linear(s, x, M2, e.conv_ln, e.pw1, 2 * d, d, g, d, h, ACT_NONE, 1.f, 1));
-    RET(launch_dwconv_bn_silu(g, d, g2, d, e.dw_wt, c.dw_kernel, e.bn_mean, e.bn_var, e.bn_g, e.bn_b, 1e-5f,
-                              o2.mx, d, cchunk, s, dr, B));
-    RET(linear(s, g2, d, M2, e.pw2, d, d, x, d, ACT_NONE, 1.f, x, d));
-    if (fuse_ffn) {                          // second FFN + the layer's final LayerNorm in the same launch
-      RET(launch_ffn_fused(x, d, x, d, e.ffn2_ln.g, e.ffn2_ln.b, e.ffn2_w1.w, e.ffn2_w1.b, e.ffn2_w2.w, e.ffn2_w2.b, 0.5f,
-                           e.final_ln.g, e.final_ln.b, M2, d, f, s, canon));
-    } else {
-      RET(ln_linear(s, x, M2, e.ffn2_ln, e.ffn2_w1, f, d, ff, f, h, ACT_SILU));
-      RET(linear(s, ff, f, M2, e.ffn2_w2, d, f, x, d, ACT_NONE, 0.5f, x, d));
-      RET(layernorm(s, x, x, e.final_ln, M2, d));
-    }
+    auto attention = [&] {
+      AttnArgs at;
+      at.Q = qkv; at.K = qkv + d; at.V = qkv + 2 * d; at.ldq = at.ldk = at.ldv = 3 * d;
+      at.O = h; at.ldo = d; at.H = c.enc_heads; at.scale = 0.125f; at.chunk = achunk;
+      at.P = m->pos_proj + (size_t)l * d; at.ldp = Ld; at.p_tmax = c.max_rel_pos; at.bias_u = e.u; at.bias_v = e.v;
+      at.segs = da; at.nseg = B; at.max_q = o2.mx;
+      return launch_attention(at, s);
+    };
+    auto dwconv = [&] {
+      return launch_dwconv_bn_silu(g, d, g2, d, e.dw_wt, c.dw_kernel, e.bn_mean, e.bn_var, e.bn_g, e.bn_b, 1e-5f, o2.mx, d, cchunk, s,
+                                   dr, B);
+    };
+    RET(enc_layer_ex(s, c, e, x, M2, h, ff, qkv, g, g2, fuse_ffn, canon, attention, dwconv));
   }
   return SS_OK;
 }

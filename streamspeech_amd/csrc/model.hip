@@ -247,8 +247,8 @@ extern "C" int ss_encoder_forward(ss_model* m, void* stream, const float* d_fban
   const int d = c.enc_dim, f = c.enc_ffn, k = c.conv_kernel, Ld = c.enc_layers * d;
   const int T1 = conv_out_len(T, k, 2), T2 = conv_out_len(T1, k, 2);
   if (T2 <= 0 || T2 > c.max_rel_pos) return SS_ERR_CAPACITY;
-  const int cchunk = (conv_chunk > 0 && conv_chunk < 999) ? conv_chunk : 0;   // chunk_causal_conv1d.py:40
-  const int achunk = (attn_chunk > 0 && attn_chunk < T2) ? attn_chunk : 0;
+  const int cchunk = conv_chunk_cfg(conv_chunk);
+  const int achunk = attn_chunk_in(attn_chunk, T2);
 
   // scratch layout (floats)
   const size_t n_h1 = (size_t)T1 * (c.conv_channels / 2);
@@ -262,46 +262,30 @@ extern "C" int ss_encoder_forward(ss_model* m, void* stream, const float* d_fban
   float* ff = g2 + n_x;                 // FFN hidden
   float* qkv = ff + n_f;
 
-  // Conv1dSubsampler: (stride-2 k5 chunk-causal conv -> GLU) x 2   (convolution.py:81-89)
-  {
-    GemmArgs a;
-    a.A = d_fbank; a.lda = c.input_feat; a.W = m->sub0.w; a.bias = m->sub0.b; a.C = h1; a.ldc = c.conv_channels / 2;
-    a.M = T1; a.N = c.conv_channels; a.Cin = c.input_feat; a.taps = k; a.stride = 2; a.pad = k / 2;
-    a.in_len = T; a.chunk = cchunk; a.glu = 1;
-    RET(launch_conv_gemm(a, s));
-    GemmArgs b;
-    b.A = h1; b.lda = c.conv_channels / 2; b.W = m->sub1.w; b.bias = m->sub1.b; b.C = g; b.ldc = d;
-    b.M = T2; b.N = 2 * d; b.Cin = c.conv_channels / 2; b.taps = k; b.stride = 2; b.pad = k / 2;
-    b.in_len = T1; b.chunk = cchunk; b.glu = 1;
-    RET(launch_conv_gemm(b, s));
-  }
+  GemmArgs a, b;                        // Conv1dSubsampler
+  subsampler_args(m, d_fbank, h1, g, a, b);
+  a.M = T1; a.in_len = T; a.chunk = cchunk;
+  b.M = T2; b.in_len = T1; b.chunk = cchunk;
+  RET(launch_conv_gemm(a, s));
+  RET(launch_conv_gemm(b, s));
   // x = Linear(sqrt(d) * x)  -- the sqrt(d)=16 scale is folded (exactly) into enc.linear.w
   RET(linear(s, g, d, T2, m->enc_linear, d, d, x, d));
   const float* P = m->pos_proj + (size_t)(c.max_rel_pos - T2) * Ld;
 
   for (int l = 0; l < c.enc_layers; ++l) {
     const EncLayer& e = m->enc[l];
-    // x = x + 0.5 * FFN1(x)
-    RET(ln_linear(s, x, T2, e.ffn1_ln, e.ffn1_w1, f, d, ff, f, h, ACT_SILU));
-    RET(linear(s, ff, f, T2, e.ffn1_w2, d, f, x, d, ACT_NONE, 0.5f, x, d));
-    // x = x + RelPosMHA(LN(x))
-    RET(ln_linear(s, x, T2, e.attn_ln, e.qkv, 3 * d, d, qkv, 3 * d, h));
-    AttnArgs at;
-    at.Q = qkv; at.K = qkv + d; at.V = qkv + 2 * d; at.ldq = at.ldk = at.ldv = 3 * d;
-    at.O = h; at.ldo = d; at.Tq = T2; at.Tk = T2; at.H = c.enc_heads; at.scale = 0.125f;
-    at.chunk = achunk; at.P = P + (size_t)l * d; at.ldp = Ld; at.bias_u = e.u; at.bias_v = e.v;
-    RET(bind_attn_split(m, at, s));
-    RET(launch_attention(at, s));
-    RET(linear(s, h, d, T2, e.out, d, d, x, d, ACT_NONE, 1.f, x, d));
-    // x = x + ConvModule(x)
-    RET(ln_linear(s, x, T2, e.conv_ln, e.pw1, 2 * d, d, g, d, h, ACT_NONE, 1.f, 1));
-    RET(launch_dwconv_bn_silu(g, d, g2, d, e.dw_wt, c.dw_kernel, e.bn_mean, e.bn_var, e.bn_g, e.bn_b, 1e-5f,
-                              T2, d, cchunk, s));
-    RET(linear(s, g2, d, T2, e.pw2, d, d, x, d, ACT_NONE, 1.f, x, d));
-    // x = LN(x + 0.5 * FFN2(x))
-    RET(ln_linear(s, x, T2, e.ffn2_ln, e.ffn2_w1, f, d, ff, f, h, ACT_SILU));
-    RET(linear(s, ff, f, T2, e.ffn2_w2, d, f, x, d, ACT_NONE, 0.5f, x, d));
-    RET(layernorm(s, x, x, e.final_ln, T2, d));
+    auto attention = [&]() -> int {
+      AttnArgs at;
+      at.Q = qkv; at.K = qkv + d; at.V = qkv + 2 * d; at.ldq = at.ldk = at.ldv = 3 * d;
+      at.O = h; at.ldo = d; at.Tq = T2; at.Tk = T2; at.H = c.enc_heads; at.scale = 0.125f;
+      at.chunk = achunk; at.P = P + (size_t)l * d; at.ldp = Ld; at.bias_u = e.u; at.bias_v = e.v;
+      RET(bind_attn_split(m, at, s));
+      return launch_attention(at, s);
+    };
+    auto dwconv = [&] {
+      return launch_dwconv_bn_silu(g, d, g2, d, e.dw_wt, c.dw_kernel, e.bn_mean, e.bn_var, e.bn_g, e.bn_b, 1e-5f, T2, d, cchunk, s);
+    };
+    RET(enc_layer_ex(s, c, e, x, T2, h, ff, qkv, g, g2, false, false, attention, dwconv));
   }
   return SS_OK;
 }
@@ -435,21 +419,15 @@ extern "C" int ss_encoder_stream_forward(ss_model* m, void* stream, const float*
     if (rep) return SS_ERR_STREAM_REPEAT;   // ... and its output already went out unchecked: say so -- nothing computed here, repeat this call
   }
   const ss_config& c = m->cfg;
-  const int d = c.enc_dim, f = c.enc_ffn, k = c.conv_kernel, Ld = c.enc_layers * d, L = c.enc_layers;
-  const int T1 = conv_out_len(T, k, 2), T2 = conv_out_len(T1, k, 2);
-  if (T2 <= 0 || T2 > c.max_rel_pos) return SS_ERR_CAPACITY;
-  const int cchunk = (conv_chunk > 0 && conv_chunk < 999) ? conv_chunk : 0;
-  const int achunk_cfg = (attn_chunk > 0 && attn_chunk < 999999) ? attn_chunk : 0;   // as configured (not clipped by T2)
-  const int achunk = (achunk_cfg > 0 && achunk_cfg < T2) ? achunk_cfg : 0;
-  int fin = m->sc->es_final;      // rows kept from earlier calls; committed once the buffers are in place (a call refused on the cap changes nothing)
-  if (m->sc->es_achunk != achunk_cfg || m->sc->es_cchunk != cchunk) fin = 0;
-  if (fin > T2) fin = 0;                                // audio got shorter: a new utterance without reset
+  const int d = c.enc_dim, f = c.enc_ffn, Ld = c.enc_layers * d, L = c.enc_layers;
+  StreamRows r;                   // rows kept from earlier calls: committed once the buffers are in place (a call refused on the cap changes nothing)
+  if (!stream_rows(c, T, attn_chunk, conv_chunk, m->sc->es_final, m->sc->es_achunk, m->sc->es_cchunk, m->sc->es_tail, c.max_rel_pos, r))
+    return SS_ERR_CAPACITY;
+  const int T1 = r.T1, T2 = r.T2, cchunk = r.cchunk, r0 = r.r0, n = r.n;
   if (m->sc->es_cap < T2)                               // grow (contents are only needed below es_final: keep them)
-    RET(es_grow(m, s, std::min(c.max_rel_pos, std::max(2 * T2, 256)), fin));
-  m->sc->es_final = fin; m->sc->es_achunk = achunk_cfg; m->sc->es_cchunk = cchunk;
+    RET(es_grow(m, s, std::min(c.max_rel_pos, std::max(2 * T2, 256)), r0));
+  m->sc->es_final = r0; m->sc->es_achunk = r.achunk_cfg; m->sc->es_cchunk = cchunk;
   const int cap = m->sc->es_cap;
-  const int r0 = m->sc->es_final;                       // first row to (re)compute
-  const int n = T2 - r0;
   if (n_computed) *n_computed = n;
 
   const size_t n_h1 = (size_t)T1 * (c.conv_channels / 2);
@@ -466,17 +444,11 @@ extern "C" int ss_encoder_stream_forward(ss_model* m, void* stream, const float*
     // Only rows >= r0 of the subsampler output are read below: conv 2 starts at row r0, conv 1 at the first row conv 2 can reach
     // (2 r0 - pad).  Both keep absolute row indices (GemmArgs::m_begin), so halo rows and the chunk rule are those of the full call;
     // with the fbank rows cached by the front-end, nothing in front of the layers grows with the length of the utterance any more.
-    GemmArgs a;
-    a.A = d_fbank; a.lda = c.input_feat; a.W = m->sub0.w; a.bias = m->sub0.b; a.C = h1; a.ldc = c.conv_channels / 2;
-    a.M = T1; a.N = c.conv_channels; a.Cin = c.input_feat; a.taps = k; a.stride = 2; a.pad = k / 2;
-    a.in_len = T; a.chunk = cchunk; a.glu = 1;
-    a.m_begin = std::min(std::max(0, 2 * r0 - k / 2), T1 - 1);
+    GemmArgs a, b;
+    subsampler_args(m, d_fbank, h1, g0, a, b);
+    a.M = T1; a.in_len = T; a.chunk = cchunk; a.m_begin = r.mb1;
+    b.M = T2; b.in_len = T1; b.chunk = cchunk; b.m_begin = r0;
     RET(launch_conv_gemm(a, s));
-    GemmArgs b;
-    b.A = h1; b.lda = c.conv_channels / 2; b.W = m->sub1.w; b.bias = m->sub1.b; b.C = g0; b.ldc = d;
-    b.M = T2; b.N = 2 * d; b.Cin = c.conv_channels / 2; b.taps = k; b.stride = 2; b.pad = k / 2;
-    b.in_len = T1; b.chunk = cchunk; b.glu = 1;
-    b.m_begin = r0;
     RET(launch_conv_gemm(b, s));
   }
   if (r0 > 0)
@@ -505,6 +477,14 @@ extern "C" int ss_encoder_stream_forward(ss_model* m, void* stream, const float*
       const EncLayer& e = m->enc[l];
       float* qkv = m->sc->es_qkv.f() + (size_t)l * cap * 3 * d;      // absolute rows
       float* glu = m->sc->es_glu.f() + (size_t)l * cap * d;
+      AttnArgs at;
+      at.Q = qkv + (size_t)r0 * 3 * d; at.K = qkv + d; at.V = qkv + 2 * d; at.ldq = at.ldk = at.ldv = 3 * d;
+      at.O = h; at.ldo = d; at.Tq = n; at.Tk = T2; at.q0 = r0; at.H = c.enc_heads; at.scale = 0.125f;
+      at.chunk = r.achunk; at.P = P + (size_t)l * d; at.ldp = Ld; at.bias_u = e.u; at.bias_v = e.v;
+      auto attention = [&]() -> int {
+        RET(bind_attn_split(m, at, s));
+        return launch_attention(at, s);
+      };
       if (es_persistent) {
         EsArgs a;
         a.w = EsLayerW{e.ffn1_ln.g, e.ffn1_ln.b, e.ffn1_w1.w, e.ffn1_w1.b, e.ffn1_w2.w, e.ffn1_w2.b,
@@ -516,34 +496,18 @@ extern "C" int ss_encoder_stream_forward(ss_model* m, void* stream, const float*
         a.ph0 = 0; a.ph1 = 2; a.bar_base = m->sc->es_bar;
         RET(launch_enc_step(a, s));
         m->sc->es_bar += (unsigned)ES_G * 2u;
-        AttnArgs at;
-        at.Q = qkv + (size_t)r0 * 3 * d; at.K = qkv + d; at.V = qkv + 2 * d; at.ldq = at.ldk = at.ldv = 3 * d;
-        at.O = h; at.ldo = d; at.Tq = n; at.Tk = T2; at.q0 = r0; at.H = c.enc_heads; at.scale = 0.125f;
-        at.chunk = achunk; at.P = P + (size_t)l * d; at.ldp = Ld; at.bias_u = e.u; at.bias_v = e.v;
-        RET(bind_attn_split(m, at, s));
-        RET(launch_attention(at, s));
+        RET(attention());
         a.ph0 = 4; a.ph1 = 9; a.bar_base = m->sc->es_bar;
         RET(launch_enc_step(a, s));
         m->sc->es_bar += (unsigned)ES_G * 5u;
         continue;
       }
-      RET(ln_linear(s, x, n, e.ffn1_ln, e.ffn1_w1, f, d, ff, f, h, ACT_SILU));
-      RET(linear(s, ff, f, n, e.ffn1_w2, d, f, x, d, ACT_NONE, 0.5f, x, d));
-      RET(ln_linear(s, x, n, e.attn_ln, e.qkv, 3 * d, d, qkv + (size_t)r0 * 3 * d, 3 * d, h));
-      AttnArgs at;
-      at.Q = qkv + (size_t)r0 * 3 * d; at.K = qkv + d; at.V = qkv + 2 * d; at.ldq = at.ldk = at.ldv = 3 * d;
-      at.O = h; at.ldo = d; at.Tq = n; at.Tk = T2; at.q0 = r0; at.H = c.enc_heads; at.scale = 0.125f;
-      at.chunk = achunk; at.P = P + (size_t)l * d; at.ldp = Ld; at.bias_u = e.u; at.bias_v = e.v;
-      RET(bind_attn_split(m, at, s));
-      RET(launch_attention(at, s));
-      RET(linear(s, h, d, n, e.out, d, d, x, d, ACT_NONE, 1.f, x, d));
-      RET(ln_linear(s, x, n, e.conv_ln, e.pw1, 2 * d, d, glu + (size_t)r0 * d, d, h, ACT_NONE, 1.f, 1));
-      RET(launch_dwconv_bn_silu(glu, d, g2, d, e.dw_wt, c.dw_kernel, e.bn_mean, e.bn_var, e.bn_g, e.bn_b, 1e-5f,
-                                T2, d, cchunk, s, nullptr, 0, r0));
-      RET(linear(s, g2 + (size_t)r0 * d, d, n, e.pw2, d, d, x, d, ACT_NONE, 1.f, x, d));
-      RET(ln_linear(s, x, n, e.ffn2_ln, e.ffn2_w1, f, d, ff, f, h, ACT_SILU));
-      RET(linear(s, ff, f, n, e.ffn2_w2, d, f, x, d, ACT_NONE, 0.5f, x, d));
-      RET(layernorm(s, x, x, e.final_ln, n, d));
+      auto dwconv = [&] {      // the depthwise conv of rows >= r0 reads the GLU rows of the earlier frames from the cache
+        return launch_dwconv_bn_silu(glu, d, g2, d, e.dw_wt, c.dw_kernel, e.bn_mean, e.bn_var, e.bn_g, e.bn_b, 1e-5f, T2, d, cchunk, s,
+                                     nullptr, 0, r0);
+      };
+      RET(enc_layer_ex(s, c, e, x, n, h, ff, qkv + (size_t)r0 * 3 * d, glu + (size_t)r0 * d, g2 + (size_t)r0 * d, false, false,
+                       attention, dwconv));
     }
   }
   if (es_persistent) {
@@ -557,7 +521,7 @@ extern "C" int ss_encoder_stream_forward(ss_model* m, void* stream, const float*
         return ss_encoder_stream_forward(m, stream, d_fbank, T, attn_chunk, conv_chunk, d_enc_out, n_final, n_computed);
     }
   }
-  const int nf = std::max(r0, stream_final_rows(T, T1, T2, k, achunk_cfg, cchunk, c.dw_kernel, m->sc->es_tail));
+  const int nf = r.nf;
   if (nf > r0)
     SS_HIP_CHECK(hipMemcpyAsync(m->sc->es_out.f() + (size_t)r0 * d, d_enc_out + (size_t)r0 * d, (size_t)(nf - r0) * d * sizeof(float),
                                 hipMemcpyDeviceToDevice, s));

@@ -300,6 +300,12 @@ struct ss_model {
 
 [[maybe_unused]] static int conv_out_len(int L, int k, int stride) { return (L + 2 * (k / 2) - k) / stride + 1; }
 
+// The encoder's chunk arguments: a conv chunk outside (0, 999) is none (chunk_causal_conv1d.py:40), an attention chunk outside
+// (0, 999999) is full attention; attn_chunk_in: the attention chunk as it acts on T2 rows (a chunk of T2 or more rows is none)
+[[maybe_unused]] static int conv_chunk_cfg(int chunk) { return (chunk > 0 && chunk < 999) ? chunk : 0; }
+[[maybe_unused]] static int attn_chunk_cfg(int chunk) { return (chunk > 0 && chunk < 999999) ? chunk : 0; }
+[[maybe_unused]] static int attn_chunk_in(int chunk, int T2) { return (chunk > 0 && chunk < T2) ? chunk : 0; }
+
 // ---- incremental streaming encoder (ss_encoder_stream_forward, the session pool of stream_pool.hip) ----------------------------
 // Finality: a frame i of the 40-ms grid reaches, in one layer, keys up to the end of its attention
 // chunk and conv taps up to min(i+15, end of its conv chunk); through the subsampler it reaches
@@ -327,6 +333,27 @@ struct ss_model {
     --n;
   }
   return n;
+}
+
+// The rows of one streaming call (ss_encoder_stream_forward, pool_plan): rows below `fin` are final from the previous call, made with
+// the chunks prev_achunk / prev_cchunk (configured values); a chunk change or a shorter input starts the stream over.  Rows [r0, T2)
+// are computed (n of them), rows below nf are final afterwards, and conv 1 of the subsampler starts at row mb1, the first one conv 2
+// reads for its row r0.  false: T2 outside [1, max_rows] (nothing else is set).
+struct StreamRows { int T1, T2, cchunk, achunk_cfg, achunk, r0, n, nf, mb1; };
+[[maybe_unused]] static bool stream_rows(const ss_config& c, int T, int attn_chunk, int conv_chunk, int fin, int prev_achunk,
+                                         int prev_cchunk, int tail, int max_rows, StreamRows& r) {
+  const int k = c.conv_kernel;
+  r.T1 = conv_out_len(T, k, 2); r.T2 = conv_out_len(r.T1, k, 2);
+  if (r.T2 <= 0 || r.T2 > max_rows) return false;
+  r.cchunk = conv_chunk_cfg(conv_chunk);
+  r.achunk_cfg = attn_chunk_cfg(attn_chunk);
+  r.achunk = attn_chunk_in(r.achunk_cfg, r.T2);
+  if (prev_achunk != r.achunk_cfg || prev_cchunk != r.cchunk) fin = 0;   // chunk change: a new stream
+  if (fin > r.T2) fin = 0;                                               // shorter input: a new utterance without reset
+  r.r0 = fin; r.n = r.T2 - fin;
+  r.nf = std::max(r.r0, stream_final_rows(T, r.T1, r.T2, k, r.achunk_cfg, r.cchunk, c.dw_kernel, tail));
+  r.mb1 = std::min(std::max(0, 2 * r.r0 - k / 2), r.T1 - 1);
+  return true;
 }
 
 // ---- transformer layers shared by MT decoder / T2U encoder / unit decoder ----------------------
@@ -366,6 +393,52 @@ struct ss_model {
     ac.O = h; ac.ldo = D; ac.Tq = n; ac.Tk = Tk_cross; ac.H = H; ac.scale = 1.f; ac.k_mask_tail = cross_tail_pad;
   }
   return dec_layer_ex(s, c, L, x, n, rows, 3 * D, at, L.has_cross ? &ac : nullptr, h, q2, ff);
+}
+
+// ---- the Conformer layer shared by the full, batched, streaming and session-pool encoders -----------------------------------------
+// Conv1dSubsampler (convolution.py:81-89): the fields of its two stride-2 chunk-causal conv-GEMMs (-> GLU) every encoder shares;
+// conv 1 reads `fbank` into `h1`, conv 2 reads `h1` into `out`.  The caller sets the rows (M, in_len, m_begin, segment tables) and
+// the chunk.
+[[maybe_unused]] static void subsampler_args(const ss_model* m, const float* fbank, float* h1, float* out, GemmArgs& a, GemmArgs& b) {
+  const ss_config& c = m->cfg;
+  const int k = c.conv_kernel, C1 = c.conv_channels / 2;
+  a.A = fbank; a.lda = c.input_feat; a.W = m->sub0.w; a.bias = m->sub0.b; a.C = h1; a.ldc = C1;
+  a.N = c.conv_channels; a.Cin = c.input_feat; a.taps = k; a.stride = 2; a.pad = k / 2; a.glu = 1;
+  b.A = h1; b.lda = C1; b.W = m->sub1.w; b.bias = m->sub1.b; b.C = out; b.ldc = c.enc_dim;
+  b.N = 2 * c.enc_dim; b.Cin = C1; b.taps = k; b.stride = 2; b.pad = k / 2; b.glu = 1;
+}
+
+// Macaron FFN half on n rows of x [n, d] in place: x += 0.5 * W2 SiLU(W1 LN(x)), then x = LN_fin(x) when `fin` is given.  `fused`:
+// ONE launch_ffn_fused (its whole-tile form when `canon`); otherwise ln_linear + linear through the hidden rows `ff` [n, f] (+ a
+// LayerNorm launch), `h` [n, d] the LayerNorm rows ln_linear may need.
+[[maybe_unused]] static int enc_ffn_half(hipStream_t s, const ss_config& c, float* x, int n, const LN& ln, const Lin& w1, const Lin& w2,
+                                         const LN* fin, bool fused, bool canon, float* h, float* ff) {
+  const int d = c.enc_dim, f = c.enc_ffn;
+  if (fused)
+    return launch_ffn_fused(x, d, x, d, ln.g, ln.b, w1.w, w1.b, w2.w, w2.b, 0.5f, fin ? fin->g : nullptr, fin ? fin->b : nullptr,
+                            n, d, f, s, canon);
+  RET(ln_linear(s, x, n, ln, w1, f, d, ff, f, h, ACT_SILU));
+  RET(linear(s, ff, f, n, w2, d, f, x, d, ACT_NONE, 0.5f, x, d));
+  return fin ? layernorm(s, x, x, *fin, n, d) : SS_OK;
+}
+
+// One Conformer layer on n rows of the residual stream x [n, d] in place: FFN1 half -> RelPosMHA -> conv module -> FFN2 half + the
+// final LayerNorm.  The QKV projection writes its rows to `qkv_rows` (ld 3d), the GLU point-wise conv to `glu_rows` (ld d), and the
+// second point-wise conv reads the depthwise output at `dw_rows` (ld d).  The caller's attention() and dwconv() launch the two steps
+// that differ between the encoders (their input and output rows are the caller's); `h` [n, d] is the attention context and the
+// LayerNorm scratch, `ff` the FFN hidden rows (two-launch form).
+template <typename Attention, typename DwConv>
+static int enc_layer_ex(hipStream_t s, const ss_config& c, const EncLayer& e, float* x, int n, float* h, float* ff, float* qkv_rows,
+                        float* glu_rows, const float* dw_rows, bool ffn_fused, bool canon, Attention&& attention, DwConv&& dwconv) {
+  const int d = c.enc_dim;
+  RET(enc_ffn_half(s, c, x, n, e.ffn1_ln, e.ffn1_w1, e.ffn1_w2, nullptr, ffn_fused, canon, h, ff));
+  RET(ln_linear(s, x, n, e.attn_ln, e.qkv, 3 * d, d, qkv_rows, 3 * d, h));
+  RET(attention());
+  RET(linear(s, h, d, n, e.out, d, d, x, d, ACT_NONE, 1.f, x, d));
+  RET(ln_linear(s, x, n, e.conv_ln, e.pw1, 2 * d, d, glu_rows, d, h, ACT_NONE, 1.f, 1));
+  RET(dwconv());
+  RET(linear(s, dw_rows, d, n, e.pw2, d, d, x, d, ACT_NONE, 1.f, x, d));
+  return enc_ffn_half(s, c, x, n, e.ffn2_ln, e.ffn2_w1, e.ffn2_w2, &e.final_ln, ffn_fused, canon, h, ff);
 }
 
 extern std::atomic<int> g_mt_timeouts;      // bounded-wait time-outs of persistent MT decode steps, process-wide (model.hip)

@@ -174,12 +174,6 @@ static int pool_mark(ss_stream_pool* p, hipStream_t s) {
   return SS_OK;
 }
 
-// the FFN form of the step: two launches per FFN (LayerNorm-fused linear + linear; the final LayerNorm its own launch) by default --
-// every output column tile is its own workgroup.  SS_POOL_FFN_FUSED=1 (A/B knob): ffn_fused_kernel's whole-tile form, one launch per
-// FFN, but one workgroup per 16..64-row tile walks all 2048 hidden columns: for the few tiles of a step that is the step's critical
-// path.  Both forms are pack-invariant; they differ in summation order, so a pool keeps the form it was made with.
-static const int g_pool_ffn_fused = getenv("SS_POOL_FFN_FUSED") ? atoi(getenv("SS_POOL_FFN_FUSED")) : 0;
-
 static void pool_free(ss_stream_pool* p) {
   DevBuf* bufs[4] = {&p->qkv, &p->glu, &p->out, &p->raw};
   for (DevBuf* b : bufs) {
@@ -249,7 +243,7 @@ extern "C" int ss_stream_pool_stats(ss_stream_pool* p, int64_t* launches, int64_
 
 // the layout of one step, planned on the host before anything touches the device
 struct PoolPlan {
-  struct Sess { int slot, T, T1, T2, r0, n, nf, mb1, achunk_cfg, achunk, cchunk, q_start, off, h1_off; };
+  struct Sess : StreamRows { int slot, T, q_start, off, h1_off; };
   std::vector<Sess> s;
   std::vector<int> act;       // indices (into s) of the sessions with rows to compute, in call order
   int M = 0, total = 0, H1 = 0, qtiles = 0;
@@ -259,7 +253,6 @@ static int pool_plan(const ss_stream_pool* p, const ss_config& c, int n, const i
                      const int32_t* h_T, const int32_t* h_attn_chunk, const int32_t* h_conv_chunk, PoolPlan& pl) {
   if (n <= 0 || n > p->S || !h_slots || !h_fbank || !h_T || !h_attn_chunk || !h_conv_chunk) return SS_ERR_ARG;
   std::vector<char> seen(p->S, 0);
-  const int k = c.conv_kernel;
   pl.s.resize(n);
   for (int i = 0; i < n; ++i) {
     PoolPlan::Sess& e = pl.s[i];
@@ -268,17 +261,8 @@ static int pool_plan(const ss_stream_pool* p, const ss_config& c, int n, const i
     seen[e.slot] = 1;
     const PoolSlot& st = p->slot[e.slot];
     e.T = h_T[i];
-    e.T1 = conv_out_len(e.T, k, 2); e.T2 = conv_out_len(e.T1, k, 2);
-    if (e.T2 <= 0 || e.T2 > p->R) return SS_ERR_ARG;                  // past the pool's rows per slot: the whole call is refused
-    e.cchunk = (h_conv_chunk[i] > 0 && h_conv_chunk[i] < 999) ? h_conv_chunk[i] : 0;
-    e.achunk_cfg = (h_attn_chunk[i] > 0 && h_attn_chunk[i] < 999999) ? h_attn_chunk[i] : 0;
-    e.achunk = (e.achunk_cfg > 0 && e.achunk_cfg < e.T2) ? e.achunk_cfg : 0;
-    int fin = st.fin;
-    if (st.achunk != e.achunk_cfg || st.cchunk != e.cchunk) fin = 0;   // chunk change: a new stream
-    if (fin > e.T2) fin = 0;                                             // shorter input: a new utterance without reset
-    e.r0 = fin; e.n = e.T2 - fin;
-    e.nf = std::max(e.r0, stream_final_rows(e.T, e.T1, e.T2, k, e.achunk_cfg, e.cchunk, c.dw_kernel, st.tail));
-    e.mb1 = std::min(std::max(0, 2 * e.r0 - k / 2), e.T1 - 1);
+    if (!stream_rows(c, e.T, h_attn_chunk[i], h_conv_chunk[i], st.fin, st.achunk, st.cchunk, st.tail, p->R, e))
+      return SS_ERR_ARG;                                                 // past the pool's rows per slot: the whole call is refused
     e.off = pl.total; pl.total += e.T2;
     e.q_start = pl.M; e.h1_off = pl.H1;
     if (e.n > 0) {
@@ -301,7 +285,7 @@ extern "C" int ss_encoder_stream_forward_batch(ss_model* m, void* stream, ss_str
   SkScope sk_scope(m->sc->skws);
   CanonScope canon_scope(CANON_SEQ);        // every row-wise op: a row's bits are a function of that row alone
   hipStream_t s = (hipStream_t)stream;
-  const int d = c.enc_dim, f = c.enc_ffn, k = c.conv_kernel, Ld = c.enc_layers * d, L = c.enc_layers;
+  const int d = c.enc_dim, f = c.enc_ffn, Ld = c.enc_layers * d, L = c.enc_layers;
   const int Na = (int)pl.act.size(), M = pl.M;
 
   // ---- tables: one upload.  Pointers first (seg_A), then int32 tables ----
@@ -337,8 +321,7 @@ extern "C" int ss_encoder_stream_forward_batch(ss_model* m, void* stream, ss_str
   const int C1 = c.conv_channels / 2;
   const size_t n_h1 = (size_t)pl.H1 * C1, n_x = (size_t)M * d;
   RET(m->sc->seg_buf.ensure(blob.size()));
-  const bool ffn_fused = g_pool_ffn_fused != 0;
-  RET(m->sc->ws.ensure((n_h1 + 7 * n_x + (ffn_fused ? 0 : (size_t)M * f)) * sizeof(float)));
+  RET(m->sc->ws.ensure((n_h1 + 7 * n_x + (size_t)M * f) * sizeof(float)));
   unsigned char* dblob = reinterpret_cast<unsigned char*>(m->sc->seg_buf.p);
   const float* const* dA = reinterpret_cast<const float* const*>(dblob);
   const int* di = reinterpret_cast<const int*>(dblob + n_ptr * sizeof(void*));
@@ -350,26 +333,19 @@ extern "C" int ss_encoder_stream_forward_batch(ss_model* m, void* stream, ss_str
   float* qkv = h + n_x;                 // stacked q|k|v rows [M][3d]
   float* glu = qkv + 3 * n_x;           // stacked GLU rows
   float* g2 = glu + n_x;                // depthwise output
-  float* ff = g2 + n_x;                 // FFN hidden [M][f] (two-launch FFN form)
+  float* ff = g2 + n_x;                 // FFN hidden [M][f]
   SS_HIP_CHECK(hipMemcpyAsync(dblob, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
   long long nl = 0;
   const long long g0 = gemm_census();   // the GEMM-family launches of the step are counted where they are launched (below: the others)
-#define PL(x) RET(x)
 
   if (M > 0) {
-    GemmArgs a;
-    a.A = h_fbank[pl.act[0]]; a.lda = c.input_feat; a.W = m->sub0.w; a.bias = m->sub0.b; a.C = h1; a.ldc = C1;
-    a.N = c.conv_channels; a.Cin = c.input_feat; a.taps = k; a.stride = 2; a.pad = k / 2; a.glu = 1;
-    a.segs = dc1; a.nseg = Na; a.seg_mb = dmb1; a.seg_A = dA; a.max_seg_out = mx1; a.M = pl.H1; a.in_len = 1;
-    a.canon = CANON_SEQ;
-    GemmArgs b;
-    b.A = h1; b.lda = C1; b.W = m->sub1.w; b.bias = m->sub1.b; b.C = h; b.ldc = d;
-    b.N = 2 * d; b.Cin = C1; b.taps = k; b.stride = 2; b.pad = k / 2; b.glu = 1;
-    b.segs = dc2; b.nseg = Na; b.seg_mb = dmb2; b.max_seg_out = mx2; b.M = M; b.in_len = 1;
-    b.canon = CANON_SEQ;
-    PL(launch_conv_gemm(a, s));
-    PL(launch_conv_gemm(b, s));
-    PL(linear(s, h, d, M, m->enc_linear, d, d, x, d));
+    GemmArgs a, b;
+    subsampler_args(m, h_fbank[pl.act[0]], h1, h, a, b);
+    a.segs = dc1; a.nseg = Na; a.seg_mb = dmb1; a.seg_A = dA; a.max_seg_out = mx1; a.M = pl.H1; a.in_len = 1; a.canon = CANON_SEQ;
+    b.segs = dc2; b.nseg = Na; b.seg_mb = dmb2; b.max_seg_out = mx2; b.M = M; b.in_len = 1; b.canon = CANON_SEQ;
+    RET(launch_conv_gemm(a, s));
+    RET(launch_conv_gemm(b, s));
+    RET(linear(s, h, d, M, m->enc_linear, d, d, x, d));
     PoolAttnArgs at;
     at.Qs = qkv; at.O = h; at.ld = 3 * d; at.ldo = d; at.slot_rows = p->R;
     at.ldp = Ld; at.p_tmax = c.max_rel_pos; at.sess = dss; at.qt_pre = dqtp; at.nsess = Na; at.qtiles = pl.qtiles;
@@ -377,35 +353,22 @@ extern "C" int ss_encoder_stream_forward_batch(ss_model* m, void* stream, ss_str
     const size_t lay_q = (size_t)p->S * p->R * 3 * d, lay_g = (size_t)p->S * p->R * d;
     for (int l = 0; l < L; ++l) {
       const EncLayer& e = m->enc[l];
-      if (ffn_fused) {
-        if (!ffn_fused_eligible(d, f, ACT_SILU, M, d, d, true) || !e.ffn1_w1.b || !e.ffn1_w2.b || !e.ffn2_w1.b || !e.ffn2_w2.b) return SS_ERR_ARG;
-        PL(launch_ffn_fused(x, d, x, d, e.ffn1_ln.g, e.ffn1_ln.b, e.ffn1_w1.w, e.ffn1_w1.b, e.ffn1_w2.w, e.ffn1_w2.b, 0.5f, nullptr, nullptr,
-                            M, d, f, s, 1));
-      } else {
-        PL(ln_linear(s, x, M, e.ffn1_ln, e.ffn1_w1, f, d, ff, f, h, ACT_SILU));
-        PL(linear(s, ff, f, M, e.ffn1_w2, d, f, x, d, ACT_NONE, 0.5f, x, d));
-      }
-      PL(ln_linear(s, x, M, e.attn_ln, e.qkv, 3 * d, d, qkv, 3 * d, h));
-      at.cache = p->qkv.f() + (size_t)l * lay_q;
-      at.P = m->pos_proj + (size_t)l * d; at.bias_u = e.u; at.bias_v = e.v;
-      RET(launch_attention_pool(at, s));
-      ++nl;
-      PL(linear(s, h, d, M, e.out, d, d, x, d, ACT_NONE, 1.f, x, d));
-      PL(ln_linear(s, x, M, e.conv_ln, e.pw1, 2 * d, d, glu, d, h, ACT_NONE, 1.f, 1));
-      hipLaunchKernelGGL(pool_dwconv_kernel, dim3(cdiv(d, PDW_TC), cdiv(mx2, PDW_TT), Na), dim3(256), 0, s, glu,
-                         p->glu.f() + (size_t)l * lay_g, p->R, g2, e.dw_wt, c.dw_kernel, e.bn_mean, e.bn_var, e.bn_g, e.bn_b, 1e-5f, d, dss);
-      SS_LAUNCH_CHECK();
-      ++nl;
-      PL(linear(s, g2, d, M, e.pw2, d, d, x, d, ACT_NONE, 1.f, x, d));
-      if (ffn_fused) {
-        PL(launch_ffn_fused(x, d, x, d, e.ffn2_ln.g, e.ffn2_ln.b, e.ffn2_w1.w, e.ffn2_w1.b, e.ffn2_w2.w, e.ffn2_w2.b, 0.5f,
-                            e.final_ln.g, e.final_ln.b, M, d, f, s, 1));
-      } else {
-        PL(ln_linear(s, x, M, e.ffn2_ln, e.ffn2_w1, f, d, ff, f, h, ACT_SILU));
-        PL(linear(s, ff, f, M, e.ffn2_w2, d, f, x, d, ACT_NONE, 0.5f, x, d));
-        RET(layernorm(s, x, x, e.final_ln, M, d));
+      auto attention = [&]() -> int {
+        at.cache = p->qkv.f() + (size_t)l * lay_q;
+        at.P = m->pos_proj + (size_t)l * d; at.bias_u = e.u; at.bias_v = e.v;
+        RET(launch_attention_pool(at, s));
         ++nl;
-      }
+        return SS_OK;
+      };
+      auto dwconv = [&]() -> int {
+        hipLaunchKernelGGL(pool_dwconv_kernel, dim3(cdiv(d, PDW_TC), cdiv(mx2, PDW_TT), Na), dim3(256), 0, s, glu,
+                           p->glu.f() + (size_t)l * lay_g, p->R, g2, e.dw_wt, c.dw_kernel, e.bn_mean, e.bn_var, e.bn_g, e.bn_b, 1e-5f, d, dss);
+        SS_LAUNCH_CHECK();
+        ++nl;
+        return SS_OK;
+      };
+      RET(enc_layer_ex(s, c, e, x, M, h, ff, qkv, glu, g2, false, false, attention, dwconv));
+      ++nl;                                 // (the layer's final LayerNorm)
     }
   }
   if (pl.total > 0) {
@@ -414,7 +377,6 @@ extern "C" int ss_encoder_stream_forward_batch(ss_model* m, void* stream, ss_str
     SS_LAUNCH_CHECK();
     ++nl;
   }
-#undef PL
   p->launches += nl + (gemm_census() - g0);
   RET(pool_mark(p, s));
   for (int i = 0; i < n; ++i) {             // commit: the call went through

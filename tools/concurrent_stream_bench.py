@@ -80,7 +80,7 @@ def main():
     cfg = ModelConfig()
     m = HipModel(synth.make_model_state_dict(0, cfg), cfg)
     res = {"workload": __doc__.split("\n\n")[0].replace("\n", " "), "chunk_rows": CHUNK,
-           "pool_ffn_form": "fused" if os.environ.get("SS_POOL_FFN_FUSED", "0") not in ("", "0") else "two-launch", "runs": []}
+           "pool_ffn_form": "two-launch", "runs": []}
     Ns = [int(x) for x in os.environ.get("SS_BENCH_N", "1,8,32,64,128").split(",")]
     for N in Ns:
         audio_s, L, steps = schedule(N)
