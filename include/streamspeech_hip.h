@@ -333,6 +333,17 @@ void ss_vocoder_destroy(ss_vocoder* v);
  * bf16(x) + bf16(x - bf16(x)) (16 significant bits), f32 accumulation -- waveform within 1e-3 RMS of the f32 path
  * (tests/test_bf16x3_gpu.py), durations untouched (the duration predictor and every argmax stage stay f32). */
 int ss_vocoder_set_bf16x3(ss_vocoder* v, int on);
+/* Optional, OFF by default; off is bit for bit the default exact-f32 path.  on != 0: every ResBlock conv of this handle's 64-, 128-
+ * and 256-channel generator stages (54 convs per forward with the default plan) runs on the FP16 matrix cores (csrc/conv_f16.hip):
+ * activations and weights rounded to FP16 (saturated to +-65504, never inf), f32 accumulation, f32 tensors in memory, at every row
+ * count and in every entry point (single utterance, ragged batch, tail).  Stay f32: conv_pre, the up-convs, the 32- and 16-channel
+ * stages, conv_post, the duration predictor (so durations are those of the f32 path) and everything upstream of the vocoder.
+ * Bars: waveform within 1e-3 RMS of the f32 path and of the FP32 oracle (tests/test_vocoder_f16_gpu.py); an output row's bits depend
+ * only on its receptive field, not on the pack.  FP16 wins over ss_vocoder_set_bf16x3 while both are on.  The first switch-on makes
+ * the FP16 weight fragments (once per blob and device, shared like the Winograd forms): the pack runs on the null stream and the call
+ * returns with the device synchronised.  SS_ERR_ARG (the handle unchanged) when a wide-stage ResBlock conv of the handle's plan does
+ * not fit the kernel: (kernel size - 1) x dilation above 64. */
+int ss_vocoder_set_f16(ss_vocoder* v, int on);
 /* d_codes [K] int32 unit ids (0..999).  dur_prediction != 0 runs the duration predictor, else every
  * unit lasts one frame; d_forced_dur (may be NULL) overrides both.  d_wav must hold
  * wav_capacity floats; *h_n_samples = 320 * sum(dur).  d_dur [K] int32.  Synchronises once
@@ -433,6 +444,8 @@ int ss_batch_vocoder_tail(ss_vocoder* v, void* stream, int B, const int32_t* d_c
  * FLOPs (2*M*N*taps*Cin per launch), the launch count and the summed algorithmic bytes (weights,
  * inputs, outputs, residuals once each) of class `cls`. */
 int ss_prof_enable(int cls_mask);
+/* The same for classes 32 and up: bit i brackets class 32 + i (ss_prof_enable's mask reaches class 31 only). */
+int ss_prof_enable_hi(int cls_mask);
 int ss_prof_reset(void);
 int ss_prof_read(int cls, double* h_ms_total, double* h_flops_total, int64_t* h_launches,
                  double* h_bytes_total);
@@ -538,6 +551,13 @@ int ss_op_conv_gemm(void* stream, const float* dA, int lda, const float* dW, con
                     const float* dR, int ldr, const float* dR2, int ldr2, float* dC, int ldc,
                     int M, int N, int Cin, int taps, int dil, int stride, int pad, int in_len,
                     int chunk, int in_act, float in_slope, int act, float alpha, float div, int glu);
+/* The FP16 conv of the wide vocoder stages (csrc/conv_f16.hip) on C x C weights dW [C][taps*C] (tap-major; packed to FP16 per
+ * call): dC [M][C] = epi(sum act_in(dA) * dW) with "same" padding dil*(taps-1)/2, act_in = in_act (0 / 3 = leaky-ReLU in_slope),
+ * epi = + dbias, act (0 / 3 leaky-ReLU 0.1), + dR, + dR2, / div (div > 0), dC2 = leaky_relu(dC, 0.1) when set.  C = 64 / 128 / 256.
+ * d_segs (device, nseg x {out_start, out_len, in_start = out_start, in_len = out_len}) makes it a ragged launch over M packed rows. */
+int ss_op_conv_f16(void* stream, const float* dA, const float* dW, const float* dbias, const float* dR, const float* dR2,
+                   float* dC, float* dC2, int M, int C, int taps, int dil, int in_act, float in_slope, int act, float div,
+                   const int32_t* d_segs, int nseg);
 int ss_op_layernorm(void* stream, const float* dx, int ldx, float* dy, int ldy, const float* dg,
                     const float* db, int M, int D, float eps);
 int ss_op_attention(void* stream, const float* dQ, int ldq, const float* dK, int ldk, const float* dV,

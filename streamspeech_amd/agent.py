@@ -107,6 +107,8 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
                 with open(args.vocoder_cfg) as f:
                     vcfg = json.load(f)
             self.vocoder = CodeHiFiGANVocoderWithDur(args.vocoder, vcfg, device=self.device)
+            if getattr(args, "vocoder_fp16", False):
+                self.vocoder.hip.set_fp16(True)
         self.dur_prediction = args.dur_prediction
         # Incremental synthesis: the reference re-synthesises ALL units at every write
         # and keeps the tail (agent :743-753).  The generator has a finite receptive field, so the same
@@ -153,6 +155,9 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
         a("--vocoder", type=str, required=True, help="path to the CodeHiFiGAN vocoder (or synthetic:<seed>)")
         a("--vocoder-cfg", type=str, required=False, default=None, help="path to the CodeHiFiGAN vocoder config")
         a("--dur-prediction", action="store_true", help="enable duration prediction (for reduced/unique code sequences)")
+        a("--vocoder-fp16", action="store_true", default=False,
+          help="run the vocoder's 64- to 256-channel ResBlock convs on FP16 matrix cores (f32 accumulation; waveform within 1e-3 RMS, "
+               "unit ids and durations unchanged); default: exact f32")
         a("--lagging-k1", type=int, default=0, help="lagging number")
         a("--lagging-k2", type=int, default=0, help="lagging number")
         a("--segment-size", type=int, default=320, help="segment-size")

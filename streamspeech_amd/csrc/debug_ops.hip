@@ -29,6 +29,26 @@ extern "C" int ss_op_conv_gemm(void* stream, const float* dA, int lda, const flo
   return launch_conv_gemm(a, (hipStream_t)stream);
 }
 
+// FP16 form of a wide-stage ResBlock conv (conv_f16.hip; the model packs the weights once per blob, here per call into one buffer per
+// stream of the calling thread, as the Winograd form above)
+extern "C" int ss_op_conv_f16(void* stream, const float* dA, const float* dW, const float* dbias, const float* dR, const float* dR2,
+                              float* dC, float* dC2, int M, int Cch, int taps, int dil, int in_act, float in_slope, int act, float div,
+                              const int32_t* d_segs, int nseg) {
+  if (!dA || !dW || !dC || M <= 0 || taps < 1 || dil < 1 || nseg < 0 || (nseg > 0 && !d_segs)) return SS_ERR_ARG;
+  if (!(Cch == 64 || Cch == 128 || Cch == 256)) return SS_ERR_ARG;
+  static thread_local std::map<hipStream_t, DevBuf> f16_tmps;
+  DevBuf& wh = f16_tmps[(hipStream_t)stream];
+  RET(wh.ensure(f16_pack_halves(Cch, taps) * sizeof(uint16_t)));
+  RET(launch_f16_pack(dW, wh.p, Cch, taps, (hipStream_t)stream));
+  GemmArgs a;
+  a.A = dA; a.lda = Cch; a.W = dW; a.Wf16 = wh.p; a.bias = dbias; a.R = dR; a.ldr = Cch; a.R2 = dR2; a.ldr2 = Cch;
+  a.C = dC; a.ldc = Cch; a.C2 = dC2; a.ldc2 = Cch; a.c2_slope = 0.1f;
+  a.M = M; a.N = Cch; a.Cin = Cch; a.taps = taps; a.dil = dil; a.stride = 1; a.pad = dil * (taps - 1) / 2; a.in_len = M;
+  a.same_rows = 1; a.in_act = in_act; a.in_slope = in_slope; a.act = act; a.act_slope = 0.1f; a.div = div;
+  a.segs = d_segs; a.nseg = nseg;
+  return launch_conv_f16(a, (hipStream_t)stream);
+}
+
 extern "C" int ss_debug_last_logits(ss_model* m, void* stream, float* d_out, int64_t cap_floats, int* h_rows, int* h_cols) {
   if (!m || !h_rows || !h_cols) return SS_ERR_ARG;
   *h_rows = m->sc->dbg_rows; *h_cols = m->sc->dbg_cols;
@@ -137,6 +157,7 @@ extern "C" int ss_op_dwconv_bn_silu(void* stream, const float* dx, int ldx, floa
 }
 
 extern "C" int ss_prof_enable(int cls_mask) { prof_enable(cls_mask); return SS_OK; }
+extern "C" int ss_prof_enable_hi(int cls_mask) { prof_enable_hi(cls_mask); return SS_OK; }
 extern "C" int ss_prof_reset(void) { prof_reset(); return SS_OK; }
 extern "C" int ss_prof_read(int cls, double* ms, double* flops, int64_t* launches, double* bytes) {
   long long n = 0;

@@ -18,6 +18,7 @@ struct GemmArgs {
   const float* A = nullptr;   // input rows, row stride lda
   const float* W = nullptr;   // [N][taps*Cin]
   const float* Wwino = nullptr;  // optional: the same weights in Winograd F(2,3) form [N][ceil(taps/3)*4*Cin] (conv_c64w.hip; made by launch_wino_pack)
+  const void* Wf16 = nullptr;    // set: the FP16 form of the weights (conv_f16.hip; made by launch_f16_pack) -- the launch runs on conv_f16 or fails
   const float* bias = nullptr;  // [N] or null
   const float* R = nullptr;   // residual [M][ldr] or null
   const float* R2 = nullptr;  // second residual (MRF accumulate) or null
@@ -103,9 +104,11 @@ enum ProfCls : int {
   PROF_CONV_C64 = 24, PROF_CONV_C32 = 25, PROF_CONV_C16 = 26,
   PROF_CONV_C64W = 27, PROF_CONV_C128W = 28, PROF_CONV_C32W = 29, PROF_CONV_C256W = 30,   // the Winograd forms (prof_begin: issued FLOPs)
   PROF_RTLIN_KB = 31,
+  PROF_CONV_F16_64 = 32, PROF_CONV_F16_128 = 33, PROF_CONV_F16_256 = 34,   // the opt-in FP16 form of the wide stages (conv_f16.hip)
 };
-constexpr int kNumTileCfg = PROF_RTLIN_KB + 1;
-void prof_enable(int cls_mask);   // bit i set -> bracket launches of tile config i with events; 0 = off
+constexpr int kNumTileCfg = PROF_CONV_F16_256 + 1;
+void prof_enable(int cls_mask);   // bit i set -> bracket launches of tile config i (< 32) with events; 0 = off
+void prof_enable_hi(int cls_mask);   // the same for tile configs 32 + i
 void prof_reset();
 int prof_read(int cls, double* ms_total, double* flops_total, long long* launches, double* bytes_total = nullptr);  // synchronises
 const char* prof_cfg_name(int cls);
@@ -247,6 +250,15 @@ bool conv_c16_eligible(const GemmArgs& a);
 bool conv_c16_enabled();
 int launch_conv_c16(const GemmArgs& a, hipStream_t stream);
 void conv_c16_debug(int enable);
+
+// Opt-in FP16 form of the wide vocoder stages' ResBlock convs (conv_f16.hip): Cin = N = 64 / 128 / 256, "same" rows, any row count,
+// ragged packs of any size; FP16 operands (input leaky-ReLU and saturation to +-65504 applied while staging), FP32 accumulation and
+// tensors.  Needs a.Wf16 = launch_f16_pack(W) (f16_pack_halves(C, taps) halves).
+bool conv_f16_eligible(const GemmArgs& a);
+bool conv_f16_geometry_ok(int C, int taps, int dil);   // channels, taps and dilation the kernel takes ((taps - 1) dil <= 64)
+int launch_conv_f16(const GemmArgs& a, hipStream_t stream);
+size_t f16_pack_halves(int C, int taps);
+int launch_f16_pack(const float* W, void* Wf, int C, int taps, hipStream_t stream);
 
 // Row-tile linear layer for K = 256 projections of packed batches (rtlin.hip): the row tile (LayerNorm-ed when a.ln_g is set) in
 // LDS, weight fragments straight from L2 to registers, bias / activation / alpha / residual or GLU epilogue per 16-column unit.

@@ -443,7 +443,8 @@ static int enc_layer_ex(hipStream_t s, const ss_config& c, const EncLayer& e, fl
 
 extern std::atomic<int> g_mt_timeouts;      // bounded-wait time-outs of persistent MT decode steps, process-wide (model.hip)
 
-struct ConvW { const float* w = nullptr; const float* b = nullptr; const float* ww = nullptr; };   // ww: Winograd form (64-channel stage ResBlock convs)
+struct ConvW { const float* w = nullptr; const float* b = nullptr; const float* ww = nullptr;   // ww: Winograd form (64-channel stage ResBlock convs)
+               const void* wh = nullptr; };                                                         // wh: FP16 fragment form (conv_f16.hip; ss_vocoder_set_f16)
 struct ss_vocoder {
   ss_vocoder_config cfg;
   WeightTable wt;
@@ -456,6 +457,9 @@ struct ss_vocoder {
   float* wino = nullptr;             // Winograd F(2,3) forms of the 32- / 64- / 128-channel stages' ResBlock conv weights (conv_c64w.hip):
   const float* wino_key = nullptr;   // ONE buffer per weight blob, shared by every context over that blob (wino_share below)
   int x3 = 0;          // split-bf16 contraction of the C >= 64 generator convs (ss_vocoder_set_bf16x3); default off = exact f32
+  int f16 = 0;         // FP16-operand ResBlock convs of the 64- / 128- / 256-channel stages (ss_vocoder_set_f16); wins over x3; default off
+  const float* blob = nullptr;       // the weight blob this handle was made over
+  void* f16w = nullptr;              // their FP16 weight fragments: ONE buffer per weight blob, shared like `wino` (made on the first switch-on)
 };
 
 namespace {

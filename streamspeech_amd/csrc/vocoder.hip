@@ -21,6 +21,19 @@ struct WinoKey {
 std::mutex g_wino_mu;
 std::map<WinoKey, WinoShared> g_wino;
 inline uint64_t fnv(uint64_t h, uint64_t v) { for (int i = 0; i < 8; ++i) { h ^= (v >> (8 * i)) & 0xff; h *= 1099511628211ull; } return h; }
+// signature of the configuration a transformed-weight buffer is laid out for (channel plan, ResBlock kernel sizes, slot offsets)
+uint64_t blob_sig(const ss_vocoder* v, const float* d_blob) {
+  const ss_vocoder_config* cfg = &v->cfg;
+  uint64_t sig = fnv(fnv(fnv(14695981039346656037ull, (uint64_t)cfg->upsample_initial_channel), (uint64_t)cfg->n_up), (uint64_t)cfg->n_res);
+  for (int j = 0; j < cfg->n_res; ++j) sig = fnv(sig, (uint64_t)cfg->resblock_kernel_sizes[j]);
+  for (size_t i = 0; i < v->rb_c1.size(); ++i) sig = fnv(fnv(sig, (uint64_t)(v->rb_c1[i].w - d_blob)), (uint64_t)(v->rb_c2[i].w - d_blob));
+  return sig;
+}
+// The FP16 fragment forms of the wide stages' ResBlock convs (conv_f16.hip), made on a handle's first ss_vocoder_set_f16(v, 1) and
+// shared per blob exactly like g_wino: same key, ref-counted, released with the last handle that took it.
+std::mutex g_f16_mu;
+std::map<WinoKey, WinoShared> g_f16;
+bool f16_stage(int ch) { return ch == 64 || ch == 128 || ch == 256; }
 }  // namespace
 
 extern "C" int ss_vocoder_create(const ss_vocoder_config* cfg, const float* d_blob, size_t blob_floats,
@@ -29,6 +42,7 @@ extern "C" int ss_vocoder_create(const ss_vocoder_config* cfg, const float* d_bl
   if (!cfg || !d_blob || !out || cfg->n_up > 8 || cfg->n_res > 4) return SS_ERR_ARG;
   ss_vocoder* v = new ss_vocoder();
   v->cfg = *cfg;
+  v->blob = d_blob;
   v->sc = new ss_scratch();          // the handle's own scratch set; ss_vocoder_bind_scratch swaps it for a shared one
   int rc = v->wt.build(d_blob, blob_floats, names, offsets, numels, n_slots);
   if (rc != SS_OK) { scratch_unref(v->sc); delete v; return rc; }
@@ -74,10 +88,7 @@ extern "C" int ss_vocoder_create(const ss_vocoder_config* cfg, const float* d_bl
       int dev = 0;
       if (hipGetDevice(&dev) != hipSuccess) { scratch_unref(v->sc); delete v; return SS_ERR_HIP; }
       std::lock_guard<std::mutex> lk(g_wino_mu);          // (held over the pack: a second context of the same blob waits for it)
-      uint64_t sig = fnv(fnv(fnv(14695981039346656037ull, (uint64_t)C0), (uint64_t)cfg->n_up), (uint64_t)cfg->n_res);
-      for (int j = 0; j < cfg->n_res; ++j) sig = fnv(sig, (uint64_t)cfg->resblock_kernel_sizes[j]);
-      for (size_t i = 0; i < v->rb_c1.size(); ++i) sig = fnv(fnv(sig, (uint64_t)(v->rb_c1[i].w - d_blob)), (uint64_t)(v->rb_c2[i].w - d_blob));
-      const WinoKey key{dev, d_blob, sig};
+      const WinoKey key{dev, d_blob, blob_sig(v, d_blob)};
       WinoShared& sh = g_wino[key];
       const bool fresh = sh.refs == 0;
       if (!fresh && sh.floats != need) { scratch_unref(v->sc); delete v; return SS_ERR_ARG; }   // (same signature, another size: cannot happen; the live entry is left alone)
@@ -124,8 +135,84 @@ extern "C" int ss_vocoder_set_bf16x3(ss_vocoder* v, int on) {
   return SS_OK;
 }
 
+// First switch-on: take (or make) the shared FP16 fragments of this handle's blob.  The pack runs on the null stream and the device is
+// synchronised before this returns, as in ss_vocoder_create.
+static int f16_take(ss_vocoder* v) {
+  const ss_vocoder_config& c = v->cfg;
+  size_t need = 0;                                         // halves
+  for (int i = 0, Cs = c.upsample_initial_channel; i < c.n_up; ++i) {
+    Cs /= 2;
+    if (f16_stage(Cs)) for (int j = 0; j < c.n_res; ++j) need += 6 * f16_pack_halves(Cs, c.resblock_kernel_sizes[j]);
+  }
+  if (!need) return SS_OK;                                 // no wide stage: nothing runs in FP16
+  // every wide-stage ResBlock conv must fit the kernel: refused here, before anything is made, rather than by every later forward
+  for (int i = 0, Cs = c.upsample_initial_channel; i < c.n_up; ++i) {
+    Cs /= 2;
+    if (!f16_stage(Cs)) continue;
+    for (int j = 0; j < c.n_res; ++j)
+      for (int dd = 0; dd < 3; ++dd)
+        if (!conv_f16_geometry_ok(Cs, c.resblock_kernel_sizes[j], c.resblock_dilations[j][dd]) ||
+            !conv_f16_geometry_ok(Cs, c.resblock_kernel_sizes[j], 1))
+          return SS_ERR_ARG;
+  }
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return SS_ERR_HIP;
+  std::lock_guard<std::mutex> lk(g_f16_mu);
+  const WinoKey key{dev, v->blob, blob_sig(v, v->blob)};
+  WinoShared& sh = g_f16[key];
+  const bool fresh = sh.refs == 0;
+  if (!fresh && sh.floats != need) return SS_ERR_ARG;
+  int rc = SS_OK;
+  if (fresh) {
+    rc = sh.buf.ensure(need * sizeof(uint16_t));
+    if (rc != SS_OK) { g_f16.erase(key); return rc; }
+    sh.floats = need;
+  }
+  char* dst = static_cast<char*>(sh.buf.p);
+  std::vector<ConvW> rb1 = v->rb_c1, rb2 = v->rb_c2;       // committed to the handle only once the whole pack succeeded
+  for (int i = 0, Cs = c.upsample_initial_channel; i < c.n_up && rc == SS_OK; ++i) {
+    Cs /= 2;
+    if (!f16_stage(Cs)) continue;
+    for (int j = 0; j < c.n_res && rc == SS_OK; ++j) {
+      const int kr = c.resblock_kernel_sizes[j];
+      const size_t n = f16_pack_halves(Cs, kr) * sizeof(uint16_t);
+      for (int dd = 0; dd < 3 && rc == SS_OK; ++dd) {
+        const int idx = (i * c.n_res + j) * 3 + dd;
+        if (fresh) rc = launch_f16_pack(rb1[idx].w, dst, Cs, kr, nullptr);
+        rb1[idx].wh = dst; dst += n;
+        if (fresh && rc == SS_OK) rc = launch_f16_pack(rb2[idx].w, dst, Cs, kr, nullptr);
+        rb2[idx].wh = dst; dst += n;
+      }
+    }
+  }
+  if (fresh && rc == SS_OK && hipDeviceSynchronize() != hipSuccess) rc = SS_ERR_HIP;
+  if (rc != SS_OK) {
+    if (fresh) { sh.buf.release(); g_f16.erase(key); }
+    return rc;
+  }
+  ++sh.refs;
+  v->rb_c1.swap(rb1); v->rb_c2.swap(rb2);
+  v->f16w = sh.buf.p;
+  return SS_OK;
+}
+
+extern "C" int ss_vocoder_set_f16(ss_vocoder* v, int on) {
+  if (!v) return SS_ERR_ARG;
+  if (on && !v->f16w) RET(f16_take(v));
+  v->f16 = on ? 1 : 0;
+  return SS_OK;
+}
+
 extern "C" void ss_vocoder_destroy(ss_vocoder* v) {
   if (!v) return;
+  if (v->f16w) {
+    std::lock_guard<std::mutex> lk(g_f16_mu);
+    for (auto it = g_f16.begin(); it != g_f16.end(); ++it)
+      if (it->first.blob == v->blob && it->second.buf.p == v->f16w) {
+        if (--it->second.refs == 0) { it->second.buf.release(); g_f16.erase(it); }
+        break;
+      }
+  }
   if (v->wino_key) {
     std::lock_guard<std::mutex> lk(g_wino_mu);
     for (auto it = g_wino.begin(); it != g_wino.end(); ++it)
@@ -166,12 +253,20 @@ template <class ConvFn, class StageFn, class GeomFn>
 static int hifigan_stack(const ss_vocoder* v, hipStream_t s, ConvFn&& conv, StageFn&& on_stage, GeomFn&& geom,
                          const float* frames, int Ft, const GenBufs& b, int* out_scale, int* out_C) {
   const ss_vocoder_config& c = v->cfg;
+  // Opt-in FP16 (ss_vocoder_set_f16): every ResBlock conv of the 64-, 128- and 256-channel stages runs on conv_f16.hip at any row count;
+  // like the Winograd slab stages it activates while staging, so those convs neither read nor write twins -- only the stage's last conv
+  // writes one when the up-conv that leaves the stage reads it.  It wins over x3, which then leaves every conv in f32.
+  // The f32 convs that feed an FP16 stage (conv_pre, the up-convs into the 256-, 128- and 64-channel stages) take the pack-invariant
+  // arithmetic (CANON_SEQ) while it is on: a row-count-dependent summation order there moves an FP16 rounding by one ulp, which the
+  // receptive-field tail synthesis (agent.py synthesize_tail, ss_batch_vocoder_tail) would see as a 1e-4 step instead of f32 noise.
+  const bool f16 = v->f16 && v->f16w;
+  const bool x3 = v->x3 && !f16;
   // Stages with >= 64 channels get their input leaky-ReLU from the PRODUCER (a second, pre-activated output: VALU work inside a
   // stream-K MFMA loop costs matrix-core time) -- except the 64-channel stage of a packed batch, whose convs run on conv_c64.hip:
   // that kernel applies the activation once per element while it stages its input slab, so no twin tensor is written or read.
   // The 32-channel stage of a packed batch runs its convs one by one on conv_c32.hip instead of one fused launch per ResBlock.
   auto slab_stage = [&](int channels) {
-    if (v->x3 || !(channels == 64 ? conv_c64_enabled() : channels == 32 ? conv_c32_enabled() : channels == 16 ? conv_c16_enabled() : false)) return false;
+    if (x3 || !(channels == 64 ? conv_c64_enabled() : channels == 32 ? conv_c32_enabled() : channels == 16 ? conv_c16_enabled() : false)) return false;
     long long rows = Ft; int ch = c.upsample_initial_channel; bool found = false;
     for (int i = 0; i < c.n_up && !found; ++i) { rows *= c.upsample_rates[i]; ch /= 2; found = ch == channels; }
     if (!found || rows >= (1ll << 30)) return false;
@@ -185,7 +280,7 @@ static int hifigan_stack(const ss_vocoder* v, hipStream_t s, ConvFn&& conv, Stag
   // activates while staging -- so the convs of that stage neither read nor write twins; only the up-conv that LEAVES the stage (on conv_sk2)
   // still reads one, written by the stage's last conv.  Taken only if every conv of the stage is eligible (there is no direct slab form).
   auto wino_slab_stage = [&](int channels) {
-    if (v->x3 || !(channels == 128 ? conv_c128w_enabled() : conv_c256w_enabled())) return false;
+    if (f16 || x3 || !(channels == 128 ? conv_c128w_enabled() : conv_c256w_enabled())) return false;
     long long rows = Ft; int ch = c.upsample_initial_channel, stage = -1;
     for (int i = 0; i < c.n_up && stage < 0; ++i) { rows *= c.upsample_rates[i]; ch /= 2; if (ch == channels) stage = i; }
     if (stage < 0 || rows >= (1ll << 30)) return false;
@@ -208,16 +303,17 @@ static int hifigan_stack(const ss_vocoder* v, hipStream_t s, ConvFn&& conv, Stag
   // (round 5: the 256-channel stage the same way -- conv_c64w.hip at CH = 256: two slab phases of 128 input channels, two column halves)
   const bool c128 = wino_slab_stage(128), c256 = wino_slab_stage(256);
   // does a ResBlock conv of this stage read a pre-activated twin?  (does the producer have to write one?)
-  auto preact = [c64, c128, c256](int channels) {
-    return channels >= 64 && !(c64 && channels == 64) && !(c128 && channels == 128) && !(c256 && channels == 256);
+  auto preact = [c64, c128, c256, f16](int channels) {
+    return channels >= 64 && !(c64 && channels == 64) && !(c128 && channels == 128) && !(c256 && channels == 256) && !(f16 && f16_stage(channels));
   };
   // the up-conv that leaves a stage runs on conv_sk2 for >= 128 channels (N = stride x C / 2) and on conv_c64 for the 64-channel stage
   auto up_preact = [c64](int channels) { return channels >= 64 && !(c64 && channels == 64); };
-  auto mk = [v](const float* A, int Cin, const ConvW& cw, int Cout, int k, int dil, float* Cc, int ldc) {
+  auto mk = [x3, f16](const float* A, int Cin, const ConvW& cw, int Cout, int k, int dil, float* Cc, int ldc) {
     GemmArgs a;
     a.A = A; a.lda = Cin; a.W = cw.w; a.Wwino = cw.ww; a.bias = cw.b; a.C = Cc; a.ldc = ldc; a.ldr = ldc; a.ldr2 = ldc; a.ldc2 = ldc;
     a.N = Cout; a.Cin = Cin; a.taps = k; a.dil = dil; a.stride = 1; a.pad = dil * (k - 1) / 2; a.same_rows = 1;
-    a.x3 = v->x3;
+    a.x3 = x3;
+    if (f16) a.Wf16 = cw.wh;           // set for the wide stages' ResBlock convs only: launch_conv_gemm sends them to conv_f16
     return a;
   };
   int scale = 1, C = c.upsample_initial_channel;
@@ -225,6 +321,7 @@ static int hifigan_stack(const ss_vocoder* v, hipStream_t s, ConvFn&& conv, Stag
   {
     GemmArgs a = mk(frames, c.model_in_dim, v->pre, C, 7, 1, b.bx, C);
     if (up_preact(C)) a.C2 = b.bxa;
+    if (f16) a.canon = CANON_SEQ;
     RET(conv(a, scale));
   }
   for (int i = 0; i < c.n_up; ++i) {
@@ -237,6 +334,7 @@ static int hifigan_stack(const ss_vocoder* v, hipStream_t s, ConvFn&& conv, Stag
       if (!pa_in) { a.in_act = ACT_LRELU; a.in_slope = 0.1f; }
       if (pa) a.C2 = b.bsa;
       a.algo_flops = 2.0 * Ft * scale * C * Co * c.upsample_kernel_sizes[i];   // zero-padded polyphase slots are not work
+      if (f16 && Co >= 64) a.canon = CANON_SEQ;
       RET(conv(a, scale));
     }
     scale *= st; C = Co;

@@ -853,7 +853,17 @@ class HipVocoder:
         v = HipVocoder(None, self.cfg, device=str(self.device), _share=self._packed, scratch=scratch)
         if getattr(self, "bf16x3", False):
             v.set_bf16x3(True)
+        if getattr(self, "fp16", False):
+            v.set_fp16(True)
         return v
+
+    def set_fp16(self, on: bool):
+        """Opt-in FP16 matrix-core ResBlock convs of the 64-, 128- and 256-channel stages of this handle (f32 accumulation; the
+        duration predictor and every other conv stay f32, so durations are unchanged; waveform within 1e-3 RMS of the f32 path).
+        Wins over bf16x3 while both are on; off (the default) is the exact f32 path."""
+        with torch.cuda.device(self.device):
+            L.check(self.lib.ss_vocoder_set_f16(self.h, int(bool(on))), "ss_vocoder_set_f16")
+        self.fp16 = bool(on)
 
     def set_bf16x3(self, on: bool):
         """Opt-in split-bf16 (3 bf16 MFMAs per k-slice) contraction for the C >= 64 generator convs of this handle; the

@@ -85,6 +85,7 @@ SIGNATURES = {
                                C.POINTER(_i64), C.POINTER(_i64), _i, C.POINTER(_vp)]),
     "ss_vocoder_destroy": (None, [_vp]),
     "ss_vocoder_set_bf16x3": (_i, [_vp, _i]),
+    "ss_vocoder_set_f16": (_i, [_vp, _i]),
     "ss_vocoder_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp, C.POINTER(_i64)]),
     "ss_batch_fbank_cmvn": (_i, [_vp, _vp, _i, _vp, C.POINTER(_i64), C.POINTER(C.c_int32), _f, _vp, C.POINTER(C.c_int32)]),
     "ss_batch_encoder_forward": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _i, _vp, C.POINTER(C.c_int32)]),
@@ -111,6 +112,7 @@ SIGNATURES = {
                                    C.POINTER(C.c_int32), _i, _vp, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(_i64), C.POINTER(_i64)]),
     "ss_prof_enable": (_i, [_i]),
+    "ss_prof_enable_hi": (_i, [_i]),
     "ss_prof_reset": (_i, []),
     "ss_prof_read": (_i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(C.c_double)]),
     "ss_prof_totals": (_i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)]),
@@ -135,6 +137,7 @@ SIGNATURES = {
     "ss_debug_attention_q16": (_i, [_i]),
     "ss_op_conv_gemm": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
                              _i, _f, _i, _f, _f, _i]),
+    "ss_op_conv_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _f, _vp, _i]),
     "ss_op_layernorm": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _f]),
     "ss_op_attention": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _i, _vp, _vp]),
     "ss_op_dwconv_bn_silu": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _i]),

@@ -205,6 +205,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--max-len-a-mt", type=float, default=0.0, help="first-pass text search: max_len = a * src_len + b")
     ap.add_argument("--max-len-b-mt", type=int, default=200)
     ap.add_argument("--dur-prediction", action="store_true")
+    ap.add_argument("--vocoder-fp16", action="store_true",
+                    help="run the vocoder's 64- to 256-channel ResBlock convs on FP16 matrix cores (f32 accumulation; waveform within "
+                         "1e-3 RMS, unit ids and durations unchanged); default: exact f32")
     ap.add_argument("--no-wav", action="store_true")
     ap.add_argument("--scores", action="store_true")
     ap.add_argument("--num-shards", type=int, default=int(os.environ.get("WORLD_SIZE", "1")))
@@ -240,6 +243,8 @@ def main(argv: Optional[List[str]] = None):
         with open(a.vocoder_cfg) as f:
             vcfg = json.load(f)
     voc = CodeHiFiGANVocoderWithDur(a.vocoder, vcfg, device=a.device).hip
+    if a.vocoder_fp16:
+        voc.set_fp16(True)
 
     targets: Dict[int, List[int]] = {}
     if a.synthetic > 0:
