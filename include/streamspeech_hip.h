@@ -404,6 +404,37 @@ int ss_batch_mt_continue(ss_model* m, void* stream, int B, const float* d_enc_ou
 int ss_batch_mt_continue_plan(int B, const int32_t* h_Tp, const int32_t* h_prefix, const int32_t* h_n_prefix, const int32_t* h_max_len,
                               int min_len, int out_stride, int feat_rows, int max_tgt_pos, int vocab, int eos, int32_t* h_dims,
                               int32_t* h_tables, int64_t tables_cap, int64_t* h_n_tables);
+/* ss_batch_mt_beam behind a forced prefix per utterance (the streaming write path): fairseq's prefix_tokens of the same generator
+ * (_prefix_tokens, fairseq/fairseq/sequence_generator.py:596-623).  Utterance b's first h_n_prefix[b] tokens (h_prefix: the B
+ * prefixes concatenated; 0 allowed) are forced: after them exactly one hypothesis is alive, its cumulative score the in-order float32
+ * sum of the forced tokens' masked log-probabilities (pad -inf, <unk> minus unk_penalty; min_len is not applied at forced steps), and
+ * the search goes on from there as ss_batch_mt_beam does from [</s>]; lengths (max_len, min_len, the normalisation) count the prefix.
+ * The forced positions are decoded ONCE per utterance, in one ragged pass (that of ss_batch_mt_continue), and the k hypothesis rows
+ * read them through the ancestry table.  Per utterance b and rank i: h_out_tokens [B][beam][out_stride] the tokens AFTER the prefix
+ * incl. the final </s>, h_n_out [B][beam] their number; h_scores [B][beam] and h_pos_scores [B][beam][out_stride] (may be NULL;
+ * h_n_prefix[b] + h_n_out entries) cover the whole hypothesis, prefix included.  d_feats [B][feat_rows][dec_dim]: the decoder
+ * states of hypothesis 0 for its h_n_prefix[b] + h_n_out[b][0] fed positions, laid out as ss_batch_mt_continue's.  With no prefix
+ * anywhere and beam > 1 the launches are ss_batch_mt_beam's; at beam 1 tokens and states are ss_batch_mt_continue's bit for bit
+ * (there the last forced token is a row of the ragged pass, at beam > 1 it is the first lock-step row of all k slots).  Pack-invariant:
+ * an utterance's n-best list does not depend on the rest of the call.  Checked before anything is launched, in this order: B <= 0 or
+ * beam outside [1, 32] -> SS_ERR_ARG; B * beam > 256 -> SS_ERR_CAPACITY; h_Tp[b] <= 0, n_prefix_b > max_len_b, min_len > max_len_b, a
+ * prefix id outside the vocabulary, or </s> / <pad> inside a prefix -> SS_ERR_ARG; max_len_b + 1 > feat_rows, max_len_b + 1 >
+ * out_stride or a position past the decoder's table -> SS_ERR_CAPACITY.  Buffers are booked on the handle's scratch set
+ * (SS_ERR_SCRATCH_CAP past a cap, the set stays usable).  Synchronises every few steps and at the end. */
+int ss_batch_mt_beam_continue(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                              const int32_t* h_prefix, const int32_t* h_n_prefix, const int32_t* h_max_len, int min_len,
+                              float unk_penalty, int normalize, int32_t* h_out_tokens, int out_stride, int32_t* h_n_out,
+                              float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows);
+/* Host only: the layout ss_batch_mt_beam_continue makes of such a call, and its refusals (the same codes, same order), with
+ * max_tgt_pos / vocab / eos / pad of the model.  h_dims[8] = {S (longest prefix), Tn (most lock-step steps after the first), Lc
+ * (cache rows per slot = S + Tn + 2), Np (prefix-pass rows), R (= B * beam slots), c0 (cache index every slot writes at lock-step
+ * index 0), prefix-pass segments, 1 if the last forced token is a prefix-pass row (beam 1)}; h_tables (may be NULL; tables_cap ints)
+ * = the int tables the call uploads: lock-step cross segments [R][4], lock-step self segments [Tn + 1][R][4], row position offset
+ * [R], first prefix-pass row [B], prefix self / cross segments [segments][4] each, prefix tokens / positions / cache rows / feature
+ * rows / forced tokens [Np] each, last prefix-pass row [B]; *h_n_tables their count. */
+int ss_batch_mt_beam_continue_plan(int B, int beam, const int32_t* h_Tp, const int32_t* h_prefix, const int32_t* h_n_prefix,
+                                   const int32_t* h_max_len, int min_len, int out_stride, int feat_rows, int max_tgt_pos, int vocab,
+                                   int eos, int pad, int32_t* h_dims, int32_t* h_tables, int64_t tables_cap, int64_t* h_n_tables);
 /* New fbank rows of B streaming sessions in one launch: session b's frames h_first[b] .. h_first[b] + h_n[b] - 1 of its own 16-kHz
  * sample history h_pcm[b] (device; frame i reads samples 160 i .. 160 i + 399) go to h_feat[b] (device, h_n[b] rows of 80).  The
  * same bits as ss_fbank_cmvn's rows.  h_n[b] = 0 skips a session.  1 <= B <= 65535. */

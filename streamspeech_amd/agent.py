@@ -8,6 +8,7 @@ stage (fbank -> encoder -> CTC x2 -> MT greedy -> T2U + unit decoder -> vocoder)
 reference it recomputes the whole utterance-so-far on every call (incremental state
 is the next step, not parity-affecting).
 """
+import argparse
 import json
 import os
 from pathlib import Path
@@ -69,6 +70,20 @@ def load_dictionaries(args, cfg):
     return d
 
 
+def _beam_mt_arg(v):
+    k = int(v)
+    if not 1 <= k <= 32:
+        raise argparse.ArgumentTypeError("--beam-mt must be in [1, 32]")
+    return k
+
+
+def _beam_kwargs(args) -> dict:
+    """generator_mt's search options beyond the reference agent's: nothing at the default beam 1 (the agent builds what it always built)."""
+    if int(getattr(args, "beam_mt", 1)) == 1:
+        return {}
+    return {"unk_penalty": float(getattr(args, "unkpen", 0.0))}
+
+
 @entrypoint
 class StreamSpeechS2STAgent(SpeechToSpeechAgent):
     """Simultaneous speech-to-speech translation agent for StreamSpeech on the HIP backend."""
@@ -86,7 +101,8 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
 
         eng = self.model.hip if hasattr(self.model, "hip") else self.model
         self.engine = eng
-        if hasattr(eng, "set_persistent_mt_step"):       # HIP engine: the MT decode step as one persistent launch (mt_step.hip)
+        beam_mt = int(getattr(args, "beam_mt", 1))
+        if hasattr(eng, "set_persistent_mt_step") and beam_mt == 1:   # HIP engine: the greedy MT decode step as one persistent launch (mt_step.hip)
             eng.set_persistent_mt_step(int(getattr(args, "mt_step_workgroups", 64)))
         tgt_dict_mt = self.dict[self.model.mt_task_name]
         tgt_dict = self.dict["tgt"]
@@ -96,9 +112,11 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
         self.st_ctc_generator = CTCDecoder(self.dict["ctc_target_unigram"], eng, 1)
         if hasattr(eng, "set_persistent_mt_step"):
             eng.ctc_speculate = True                     # policy() asks for both CTC heads of every encoder output: one host round trip (engine.ctc_greedy)
-        # generator_mt of the reference: beam 1, max_len_a=0, max_len_b=100, min_len=1 (agent :162-180)
-        self.generator_mt = SequenceGenerator(eng, tgt_dict_mt, beam_size=1, max_len_a=0, max_len_b=100, max_len=0,
-                                              min_len=1, eos=tgt_dict_mt.eos(), use_incremental_states=False)
+        # generator_mt of the reference: beam 1, max_len_a=0, max_len_b=100, min_len=1 (agent :162-180); --beam-mt k searches with a
+        # beam behind the committed prefix instead (generators.SequenceGenerator)
+        self.generator_mt = SequenceGenerator(eng, tgt_dict_mt, beam_size=beam_mt, max_len_a=0, max_len_b=100, max_len=0,
+                                              min_len=1, eos=tgt_dict_mt.eos(), use_incremental_states=False,
+                                              **_beam_kwargs(args))
         if vocoder is not None:
             self.vocoder = vocoder
         else:
@@ -171,6 +189,12 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
         a("--mt-step-workgroups", type=int, default=64,
           help="first-pass text decoder: one persistent launch per decode step on this many workgroups (64 | 128 | 256; the agent "
                "decodes one utterance at a time, which is what that form needs); 0: one launch per op")
+        a("--beam-mt", type=_beam_mt_arg, default=1,
+          help="beam of the first-pass text search behind the committed prefix (1 = greedy, the reference agent; at most 32).  Above 1 "
+               "every write is a fresh beam search with the offline generator's prefix_tokens semantics, and the persistent MT step "
+               "(--mt-step-workgroups), which belongs to the greedy search, is not armed")
+        a("--unkpen", type=float, default=0.0, help="subtracted from the <unk> log-probability of the beam search of --beam-mt > 1; ignored at --beam-mt 1 (the greedy "
+               "search of the reference agent has no such penalty)")
         a("--extra-output-dir", type=str, default=None, help="extra output dir")
         a("--output-asr-translation", type=bool, default=False, help="extra output dir")
 
@@ -355,10 +379,15 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
             # reference runs that position through the MT decoder, T2U encoder and unit decoder with
             # key-padding masks, and its 25 unit positions are decoded like any other
             eng = self.engine
-            eng.mt_truncate(len(tmp) + 1)
-            pad_feat, _ = eng.mt_append([int(prev_output_tokens_mt[0, -1])], len(tmp) + 1, False, False,
-                                        want_next=False, n_tail_pad=1)
-            mt_feats = torch.cat((mt_feats, pad_feat), 0)
+            if self.generator_mt.beam_size > 1:      # the beam search leaves no single-utterance KV cache to append to: one ragged pass
+                enc = self.encoder_outs[0]["encoder_out"][0]
+                enc = (enc[:, 0] if enc.dim() == 3 else enc).contiguous()
+                mt_feats = eng.batch_mt_features(enc, [int(enc.shape[0])], [[int(t) for t in tmp]], [1])[0]
+            else:
+                eng.mt_truncate(len(tmp) + 1)
+                pad_feat, _ = eng.mt_append([int(prev_output_tokens_mt[0, -1])], len(tmp) + 1, False, False,
+                                            want_next=False, n_tail_pad=1)
+                mt_feats = torch.cat((mt_feats, pad_feat), 0)
         self.mt_decoder_out = mt_feats
 
         # 2+3. T2U encoder + CTC unit decoder + CTC search (agent :661-689)

@@ -6,7 +6,7 @@ agent/speech_to_text.s2tt.streamspeech.agent.py:381-545 (same flags as the S2ST 
 vocoder ones)."""
 import torch
 
-from .agent import StreamSpeechS2STAgent, _detok
+from .agent import StreamSpeechS2STAgent, _beam_kwargs, _detok
 from .frontend import OnlineFeatureExtractor  # noqa: F401  (re-exported for parity with the reference files)
 from .generators import CTCDecoder, SequenceGenerator
 from .simuleval_shim import ReadAction, SpeechToTextAgent, WriteAction, entrypoint
@@ -30,7 +30,8 @@ class _TextAgentBase(SpeechToTextAgent):
         torch.set_grad_enabled(False)
         eng = self.model.hip if hasattr(self.model, "hip") else self.model
         self.engine = eng
-        if hasattr(eng, "set_persistent_mt_step"):       # HIP engine: the MT decode step as one persistent launch (mt_step.hip)
+        beam_mt = int(getattr(args, "beam_mt", 1))
+        if hasattr(eng, "set_persistent_mt_step") and beam_mt == 1:   # HIP engine: the greedy MT decode step as one persistent launch (mt_step.hip)
             eng.set_persistent_mt_step(int(getattr(args, "mt_step_workgroups", 64)))
         self.asr_ctc_generator = CTCDecoder(self.dict["source_unigram"], eng, 0)
         self.st_ctc_generator = CTCDecoder(self.dict["ctc_target_unigram"], eng, 1)
@@ -39,8 +40,8 @@ class _TextAgentBase(SpeechToTextAgent):
         tgt_dict_mt = self.dict[self.model.mt_task_name]
         # the text agents search with max_len_a=1, max_len_b=200 (s2tt agent :161-180) -- NOT the S2ST agent's 0 / 100:
         # a final hypothesis may run to (fbank frames + 200) subwords
-        self.generator_mt = SequenceGenerator(eng, tgt_dict_mt, beam_size=1, max_len_a=1, max_len_b=200, max_len=0,
-                                              min_len=1, eos=tgt_dict_mt.eos(), use_incremental_states=False)
+        self.generator_mt = SequenceGenerator(eng, tgt_dict_mt, beam_size=beam_mt, max_len_a=1, max_len_b=200, max_len=0,
+                                              min_len=1, eos=tgt_dict_mt.eos(), use_incremental_states=False, **_beam_kwargs(args))
         self.lagging_k1, self.stride_n = args.lagging_k1, args.stride_n
         self.quiet = args.extra_output_dir is None
         if not self.quiet:

@@ -173,6 +173,7 @@ template <bool ANC>
 __global__ __launch_bounds__(256) void attention_decode_kernel(AttnArgs p) {
   // 4 waves per (query, head): wave w takes key tiles w, w+4, ...; partial (max, sum, acc) merged in LDS
   const int* anc = nullptr;
+  int k0 = 0;                        // ANC: position of the segment's first key in its slot rows (k_start)
   if (p.nseg > 0) {
     const int* sg = p.segs + 4 * blockIdx.z;
     p.Tq = sg[1]; p.Tk = sg[3];
@@ -180,7 +181,8 @@ __global__ __launch_bounds__(256) void attention_decode_kernel(AttnArgs p) {
     if ((int)blockIdx.x >= p.Tq) return;
     p.Q += (size_t)sg[0] * p.ldq; p.O += (size_t)sg[0] * p.ldo;
     if (ANC) {
-      anc = p.anc + (size_t)blockIdx.z * p.anc_ld;
+      k0 = sg[2];
+      anc = p.anc + (size_t)blockIdx.z * p.anc_ld + k0;
     } else {
       p.K += (size_t)sg[2] * p.ldk; p.V += (size_t)sg[2] * p.ldv;
     }
@@ -189,7 +191,7 @@ __global__ __launch_bounds__(256) void attention_decode_kernel(AttnArgs p) {
   auto krow = [&](int j) -> size_t {
     if (!ANC) return (size_t)j;
     const int a = min((unsigned)anc[j], (unsigned)(p.anc_slots - 1));
-    return (size_t)a * p.anc_ld + j;
+    return (size_t)a * p.anc_ld + k0 + j;
   };
   __shared__ float part_m[4], part_l[4], part_acc[4][DH];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

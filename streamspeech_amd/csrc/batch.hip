@@ -417,10 +417,11 @@ extern "C" int ss_batch_mt_continue_plan(int B, const int32_t* h_Tp, const int32
 // every decoder layer in ONE ragged pass -- causal self-attention per segment (d_pself), cross-attention per session over the packed
 // encoder rows whose K/V the caller put in mt_cross (d_pcross, n_enc rows), CANON_SEQ -- then the final LayerNorm.  d_ptail (may be
 // null): trailing keys masked per segment in the self-attention (<pad> positions).  d_pcache (may be null): each layer's q|k|v rows
-// are also scattered to rows d_pcache[] of the lock-step cache (Lcap rows per session).  Workspace: m->sc->ws, (7 D + F) floats a
-// row, sized by the caller: x | h | q2 | post-LN states | q|k|v | ffn.  *out = the post-LN states [Np][D] (in ws).
-static int mt_prefix_pass(ss_model* m, hipStream_t s, int B, int Np, int np_max, int n_enc, const int* d_ptok, const int* d_ppos,
-                          const int* d_pself, const int* d_pcross, const int* d_ptail, const int* d_pcache, int Lcap, const float** out) {
+// are also scattered to rows d_pcache[] of the lock-step cache (cache_rows rows per layer: sessions x Lcap, or the beam search's
+// slots x Lc).  B = the segments of the two tables.  Workspace: m->sc->ws, (7 D + F) floats a row, sized by the caller: x | h | q2 |
+// post-LN states | q|k|v | ffn.  *out = the post-LN states [Np][D] (in ws).  Declared in model_internal.hpp (beam.hip calls it too).
+int mt_prefix_pass(ss_model* m, hipStream_t s, int B, int Np, int np_max, int n_enc, const int* d_ptok, const int* d_ppos,
+                   const int* d_pself, const int* d_pcross, const int* d_ptail, const int* d_pcache, int cache_rows, const float** out) {
   const ss_config& c = m->cfg;
   const int D = c.dec_dim, V = c.tgt_vocab, H = c.dec_heads;
   const size_t np = (size_t)Np;
@@ -444,8 +445,8 @@ static int mt_prefix_pass(ss_model* m, hipStream_t s, int B, int Np, int np_max,
     ac.no_decode_kernel = m->pack_invariant;
     RET(dec_layer_ex(s, c, m->mt[l], xp, Np, qkvp, 3 * D, at, &ac, hp, q2p, ffp));
     if (d_pcache)
-      RET(launch_scatter_rows(d_pcache, qkvp, 3 * D, m->sc->bmt_self.f() + (size_t)l * B * Lcap * 3 * D, 3 * D, 3 * D, Np,
-                              B * Lcap, s));
+      RET(launch_scatter_rows(d_pcache, qkvp, 3 * D, m->sc->bmt_self.f() + (size_t)l * cache_rows * 3 * D, 3 * D, 3 * D, Np,
+                              cache_rows, s));
   }
   RET(launch_layernorm(xp, D, pfo, D, m->mt_ln.g, m->mt_ln.b, Np, D, 1e-5f, s));
   *out = pfo;
@@ -501,7 +502,7 @@ extern "C" int ss_batch_mt_continue(ss_model* m, void* stream, int B, const floa
   // ---- the prefix pass ----
   {
     const float* pfo = nullptr;
-    RET(mt_prefix_pass(m, s, B, Np, np_max, oe.total, d_ptok, d_ppos, d_pself, d_pcross, nullptr, d_pcache, Lcap, &pfo));
+    RET(mt_prefix_pass(m, s, B, Np, np_max, oe.total, d_ptok, d_ppos, d_pself, d_pcross, nullptr, d_pcache, B * Lcap, &pfo));
     float* hp = m->sc->ws.f() + np * D;
     RET(launch_scatter_rows(d_pfeat, pfo, D, d_feats, D, D, Np, B * feat_rows, s));
     RET(launch_gather_rows(d_plast, pfo, D, hp, B, s, Np));

@@ -12,6 +12,15 @@
 //   beam_merge_kernel  one workgroup per utterance: the global top 2k in the reference's order (score, then flattened index), the
 //                      finalisation into the utterance's table, the active hypotheses, next tokens / scores / ancestry, done flag
 // The host reads the done flags every kCheck steps, as ss_batch_mt_greedy does; nothing else synchronises per step.
+//
+// ss_batch_mt_beam_continue is the same search behind a forced prefix per utterance (the streaming write path): fairseq's
+// prefix_tokens of that generator (_prefix_tokens, fairseq/fairseq/sequence_generator.py:596-623).  The forced positions run ONCE per
+// utterance, as rows of the ragged prefix pass the greedy continuation uses (mt_prefix_pass, batch.hip); their K/V rows go to the
+// utterance's slot 0, and anc[r][p] starts as "slot 0 of my utterance" for them, so nothing is copied into the other k - 1 slots.
+//   beam_prefix_score_kernel   one workgroup per forced row: log-softmax value of the forced token, masks as above
+//   beam_prefix_chain_kernel   one thread per utterance: the cumulative scores as an in-order float32 chain, and their differences
+// Lock-step index t of utterance b is the reference's step n_prefix[b] + t; row b's cache is shifted as in ss_batch_mt_continue, so
+// every row writes cache index c0 + t at step t.  ss_batch_mt_beam is the call with no prefix anywhere (c0 = 0, no prefix pass).
 #include "model_internal.hpp"
 
 namespace {
@@ -26,8 +35,10 @@ __device__ __forceinline__ bool beats(float a, int ia, float b, int ib) {
 // Row r = b*k + j of the logits -> its 2k best (score, token), score = masked log-softmax + cumulative score of the hypothesis.
 // Log-softmax numerics of log_softmax_kernel (elementwise.hip).  Masks in the reference's order (unity/sequence_generator.py:290-327):
 // NaN -> -inf, pad -inf, unk -= unk_penalty, step >= max_len: all but </s> -inf, step < min_len: </s> -inf.
-__global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict__ logits, int V, int k, int step, int min_len,
-                                                        const int* __restrict__ max_len, const int* __restrict__ done,
+// Lock-step index t; the reference's step of utterance b is npre[b] + t.
+__global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict__ logits, int V, int k, int t_step, int min_len,
+                                                        const int* __restrict__ max_len, const int* __restrict__ npre,
+                                                        const int* __restrict__ done,
                                                         const float* __restrict__ cum, int pad, int unk, int eos, float unk_pen,
                                                         float* __restrict__ cand_s, int* __restrict__ cand_t) {
   extern __shared__ float vals[];                  // [V] candidate scores of the row; NaN = already taken
@@ -35,7 +46,8 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
   __shared__ int si[4];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int row = blockIdx.x, b = row / k, j = row - b * k;
-  if (done[b] || (step == 0 && j != 0)) return;    // step 0: only beam 0 of each utterance takes part (lprobs[:, ::beam])
+  if (done[b] || (t_step == 0 && j != 0)) return;  // first free step: only beam 0 of each utterance takes part (lprobs[:, ::beam])
+  const int step = t_step + npre[b];
   const float* r = logits + (size_t)row * V;
   float mx = -INFINITY;
   for (int n = t; n < V; n += 256) mx = fmaxf(mx, r[n]);
@@ -94,22 +106,25 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
 }
 
 struct BeamState {
-  int* tok;        // [Lc + 1][R] token fed at position p by slot r
-  float* cum;      // [Lc + 1][R] cumulative score of the hypothesis fed at position p by slot r
-  int* anc;        // [2][R][Lc]  ping-pong ancestry: anc[s & 1] is read at step s
+  int* tok;        // [Tn + 3][R] token fed at lock-step index t by slot r
+  float* cum;      // [Tn + 3][R] cumulative score of the hypothesis fed at lock-step index t by slot r
+  int* anc;        // [2][R][Lc]  ping-pong ancestry over cache indices: anc[t & 1] is read at lock-step index t
   float* cand_s;   // [R][kMaxCand]
   int* cand_t;     // [R][kMaxCand]
   int* ignore;     // [R] cands_to_ignore of the reference (per utterance, per candidate position < k)
   int* done;       // [B]
   int* max_len;    // [B]
+  int* npre;       // [B] forced prefix tokens of the utterance (0: the search starts at [</s>])
   // finalised table: count [B], score [B][k] (normalised if asked), length [B][k] (tokens incl. the final </s>),
-  // tokens / positional scores / ancestry [B][k][Lc]
+  // tokens / positional scores (both after the prefix) / ancestry (by cache index) [B][k][Lc]
   int* fin_cnt; float* fin_score; int* fin_len; int* fin_tok; float* fin_pos; int* fin_anc;
 };
 
 // One workgroup per utterance: merge the k sorted per-row lists into the global top 2k, then the step logic of
-// unity/sequence_generator.py:329-470 and finalize_hypos.
-__global__ __launch_bounds__(256) void beam_merge_kernel(BeamState st, int k, int R, int Lc, int V, int step, int eos, int normalize) {
+// unity/sequence_generator.py:329-470 and finalize_hypos.  t_step is the lock-step index (reference step npre[b] + t_step); every
+// slot wrote cache index c0 + t_step at this step, so the ancestry entries in use are the cache indices 0 .. c0 + t_step.
+__global__ __launch_bounds__(256) void beam_merge_kernel(BeamState st, int k, int R, int Lc, int V, int t_step, int c0, int eos,
+                                                         int normalize) {
   __shared__ float ms[kMaxBeam * kMaxCand];
   __shared__ int mt[kMaxBeam * kMaxCand];
   __shared__ float sel_s[kMaxCand];
@@ -118,19 +133,21 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamState st, int k, in
   __shared__ int eosm[kMaxCand], f[kMaxBeam];
   __shared__ int n_fin, is_done;
   const int t = threadIdx.x, b = blockIdx.x, r0 = b * k;
-  const int* anc_cur = st.anc + (size_t)(step & 1) * R * Lc;
-  int* anc_nxt = st.anc + (size_t)((step + 1) & 1) * R * Lc;
-  int* tok_nxt = st.tok + (size_t)(step + 1) * R;
-  float* cum_nxt = st.cum + (size_t)(step + 1) * R;
+  const int npre = st.npre[b], step = t_step + npre;   // the reference's step
+  const int ci = c0 + t_step, na = ci + 2;             // cache index written at this step; ancestry entries the next step reads
+  const int* anc_cur = st.anc + (size_t)(t_step & 1) * R * Lc;
+  int* anc_nxt = st.anc + (size_t)((t_step + 1) & 1) * R * Lc;
+  int* tok_nxt = st.tok + (size_t)(t_step + 1) * R;
+  float* cum_nxt = st.cum + (size_t)(t_step + 1) * R;
   if (st.done[b]) {                  // finished utterance: its rows keep decoding (lockstep) -- keep their tables valid, nothing else
-    for (int i = t; i < k * (step + 2); i += 256) {
-      const int j = i / (step + 2), p = i - j * (step + 2);
-      anc_nxt[(size_t)(r0 + j) * Lc + p] = p <= step ? anc_cur[(size_t)(r0 + j) * Lc + p] : r0 + j;
+    for (int i = t; i < k * na; i += 256) {
+      const int j = i / na, p = i - j * na;
+      anc_nxt[(size_t)(r0 + j) * Lc + p] = p <= ci ? anc_cur[(size_t)(r0 + j) * Lc + p] : r0 + j;
     }
     if (t < k) { tok_nxt[r0 + t] = eos; cum_nxt[r0 + t] = 0.f; }
     return;
   }
-  const int nl = step == 0 ? 1 : k, nc = 2 * k;
+  const int nl = t_step == 0 ? 1 : k, nc = 2 * k;
   for (int i = t; i < nl * nc; i += 256) {
     const int l = i / nc, q = i - l * nc;
     ms[i] = st.cand_s[(size_t)(r0 + l) * kMaxCand + q];
@@ -166,8 +183,8 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamState st, int k, in
     for (int q = 0; q < k; ++q)
       if (eosm[q] && cnt < k) {
         fin_c[nf] = q; fin_e[nf] = cnt; ++nf; ++cnt;
-        st.fin_score[b * k + cnt - 1] = normalize ? sel_s[q] / (float)(step + 1) : sel_s[q];
-        st.fin_len[b * k + cnt - 1] = step + 1;
+        st.fin_score[b * k + cnt - 1] = normalize ? sel_s[q] / (float)(step + 1) : sel_s[q];   // the full length, prefix included
+        st.fin_len[b * k + cnt - 1] = t_step + 1;                                              // tokens after the prefix
       }
     bool any = false;
     for (int q = 0; q < k; ++q) any = any || eosm[q];
@@ -177,47 +194,48 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamState st, int k, in
     is_done = dn;
     st.done[b] = dn;
     // active hypotheses: the first k candidates that are neither </s> nor ignored, then the others in order (topk of active_mask)
-    int na = 0;
-    for (int q = 0; q < nc && na < k; ++q)
-      if (!(q < k ? (st.ignore[r0 + q] || eosm[q]) : eosm[q])) act_c[na++] = q;
-    for (int q = 0; q < na; ++q) f[q] = 0;
-    for (int q = 0; q < nc && na < k; ++q)
-      if (q < k ? (st.ignore[r0 + q] || eosm[q]) : eosm[q]) { f[na] = 1; act_c[na++] = q; }
+    int nact = 0;
+    for (int q = 0; q < nc && nact < k; ++q)
+      if (!(q < k ? (st.ignore[r0 + q] || eosm[q]) : eosm[q])) act_c[nact++] = q;
+    for (int q = 0; q < nact; ++q) f[q] = 0;
+    for (int q = 0; q < nc && nact < k; ++q)
+      if (q < k ? (st.ignore[r0 + q] || eosm[q]) : eosm[q]) { f[nact] = 1; act_c[nact++] = q; }
     if (!dn)
       for (int q = 0; q < k; ++q) st.ignore[r0 + q] = f[q];
   }
   __syncthreads();
-  // finalised entries: tokens 1..step and </s>, positional scores (differences of the cumulative score), ancestry snapshot
+  // finalised entries: the tokens generated so far and </s>, positional scores (differences of the cumulative score; the first one
+  // against the prefix' cumulative score when there is a prefix), ancestry snapshot
   for (int e = 0; e < n_fin; ++e) {
     const int q = fin_c[e], slot = fin_e[e], pr = r0 + sel_beam[q];
     const int* a = anc_cur + (size_t)pr * Lc;
     const size_t o = ((size_t)b * k + slot) * Lc;
-    for (int p = t; p <= step; p += 256) {
-      st.fin_anc[o + p] = a[p];
-      st.fin_tok[o + p] = p < step ? st.tok[(size_t)(p + 1) * R + a[p + 1]] : eos;
-      const float cur = p < step ? st.cum[(size_t)(p + 1) * R + a[p + 1]] : sel_s[q];
-      const float prv = p > 0 ? st.cum[(size_t)p * R + a[p]] : 0.f;
-      st.fin_pos[o + p] = p > 0 ? cur - prv : cur;
+    for (int p = t; p <= ci; p += 256) st.fin_anc[o + p] = a[p];
+    for (int u = t; u <= t_step; u += 256) {
+      st.fin_tok[o + u] = u < t_step ? st.tok[(size_t)(u + 1) * R + a[c0 + u + 1]] : eos;
+      const float cur = u < t_step ? st.cum[(size_t)(u + 1) * R + a[c0 + u + 1]] : sel_s[q];
+      const float prv = u + npre > 0 ? st.cum[(size_t)u * R + a[c0 + u]] : 0.f;
+      st.fin_pos[o + u] = u + npre > 0 ? cur - prv : cur;
     }
   }
   if (is_done) {                     // as for a finished utterance above: valid tables for the lockstep rows
-    for (int i = t; i < k * (step + 2); i += 256) {
-      const int j = i / (step + 2), p = i - j * (step + 2);
-      anc_nxt[(size_t)(r0 + j) * Lc + p] = p <= step ? anc_cur[(size_t)(r0 + j) * Lc + p] : r0 + j;
+    for (int i = t; i < k * na; i += 256) {
+      const int j = i / na, p = i - j * na;
+      anc_nxt[(size_t)(r0 + j) * Lc + p] = p <= ci ? anc_cur[(size_t)(r0 + j) * Lc + p] : r0 + j;
     }
     if (t < k) { tok_nxt[r0 + t] = eos; cum_nxt[r0 + t] = 0.f; }
     return;
   }
-  // next hypotheses: slot j continues candidate act_c[j] -- its ancestry is its parent's plus itself at step + 1
+  // next hypotheses: slot j continues candidate act_c[j] -- its ancestry is its parent's plus itself at the next cache index
   if (t < k) {
     const int q = act_c[t];
     tok_nxt[r0 + t] = sel_t[q];
     cum_nxt[r0 + t] = sel_s[q];
   }
-  for (int i = t; i < k * (step + 2); i += 256) {
-    const int j = i / (step + 2), p = i - j * (step + 2);
+  for (int i = t; i < k * na; i += 256) {
+    const int j = i / na, p = i - j * na;
     const int pr = r0 + sel_beam[act_c[j]];
-    anc_nxt[(size_t)(r0 + j) * Lc + p] = p <= step ? anc_cur[(size_t)pr * Lc + p] : r0 + j;
+    anc_nxt[(size_t)(r0 + j) * Lc + p] = p <= ci ? anc_cur[(size_t)pr * Lc + p] : r0 + j;
   }
 }
 
@@ -229,50 +247,180 @@ __global__ __launch_bounds__(256) void beam_feat_gather_kernel(const int* __rest
   for (int c = threadIdx.x; c < D; c += 256) dst[(size_t)blockIdx.x * D + c] = src[(size_t)r * D + c];
 }
 
-}  // namespace
+// Forced prefix rows: row i of the prefix pass' logits -> lp[i] = the masked log-softmax value of the token forced there (ftok[i];
+// < 0: the row forces nothing).  Log-softmax numerics of beam_topk_kernel.  The reference masks before it forces
+// (unity/sequence_generator.py:290-327, then _prefix_tokens): NaN -> -inf, pad -inf, unk -= unk_penalty; a forced step is below
+// max_len, and min_len is not applied at it.
+__global__ __launch_bounds__(256) void beam_prefix_score_kernel(const float* __restrict__ logits, int V, const int* __restrict__ ftok,
+                                                                int pad, int unk, float unk_pen, float* __restrict__ lp) {
+  __shared__ float sa[4];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, row = blockIdx.x;
+  const int tk = ftok[row];
+  if (tk < 0 || tk >= V) return;
+  const float* r = logits + (size_t)row * V;
+  float mx = -INFINITY;
+  for (int n = t; n < V; n += 256) mx = fmaxf(mx, r[n]);
+  mx = wave_max(mx);
+  if (lane == 0) sa[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(sa[0], sa[1]), fmaxf(sa[2], sa[3]));
+  __syncthreads();
+  float sum = 0.f;
+  for (int n = t; n < V; n += 256) sum += expf(r[n] - mx);
+  sum = wave_sum(sum);
+  if (lane == 0) sa[wave] = sum;
+  __syncthreads();
+  if (t != 0) return;
+  const float lse = logf((sa[0] + sa[1]) + (sa[2] + sa[3]));
+  float v = (r[tk] - mx) - lse;
+  if (v != v) v = -INFINITY;
+  if (tk == pad) v = -INFINITY;
+  if (tk == unk) v -= unk_pen;
+  lp[row] = v;
+}
 
-// Batched beam search of the first-pass text decoder (include/streamspeech_hip.h).
-extern "C" int ss_batch_mt_beam(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
-                                const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens,
-                                int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats,
-                                int feat_rows) {
-  if (!m || B <= 0 || beam < 1 || beam > kMaxBeam || !d_feats || !h_out_tokens || !h_n_out || !h_scores) return SS_ERR_ARG;
+// Per utterance the cumulative score of its forced tokens as the reference forms it (lprobs + scores[:, step - 1], step by step in
+// float32): cum_p = lp_p + cum_{p-1}.  pos[row0 + p] = cum_p - cum_{p-1}, the positional score finalize_hypos derives; the last sum
+// becomes the cumulative score hypothesis 0 enters the first free step with (cum0[b * k]).
+__global__ __launch_bounds__(256) void beam_prefix_chain_kernel(const float* __restrict__ lp, const int* __restrict__ row0,
+                                                                const int* __restrict__ npre, int B, int k, float* __restrict__ cum0,
+                                                                float* __restrict__ pos) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const int n = npre[b], r = row0[b];
+  float c = 0.f;
+  for (int p = 0; p < n; ++p) {
+    const float nc = p > 0 ? lp[r + p] + c : lp[r + p];
+    pos[r + p] = p > 0 ? nc - c : nc;
+    c = nc;
+  }
+  if (n > 0) cum0[(size_t)b * k] = c;
+}
+
+// Host-side layout of one beam call behind forced prefixes, and every refusal it makes (exported as ss_batch_mt_beam_continue_plan).
+// Utterance b has npp_b rows in the prefix pass, fed [</s>, prefix_b...] from position 0.  With beam > 1 the last forced token is the
+// first lock-step row of all k slots (pm = 0, npp_b = n_prefix_b), exactly as </s> is with no prefix: ss_batch_mt_beam is then the
+// case n_prefix = 0 launch for launch.  ss_batch_mt_beam_continue at beam 1 takes pm = 1: the last forced token is the last row of
+// the prefix pass (npp_b = n_prefix_b + 1) and the first free step reads that row's projection, which is ss_batch_mt_continue's
+// arithmetic.  Row b's cache is shifted by sh_b = Smax - npp_b (Smax = the most prefix-pass rows), so lock-step index t writes
+// cache index c0 + t everywhere (c0 = the longest prefix).
+// `tab` holds, in this order: lock-step cross segs [4R] | lock-step self segs [Tn + 1][4R] | row position offset [R] | first
+// prefix-pass row [B] | prefix self segs [4 nseg] | prefix cross segs [4 nseg] | prefix tokens | positions | cache rows | feature rows
+// | forced tokens [Np] each | last prefix-pass row [B].
+struct BcPlan {
+  int pm = 0, S = 0, Smax = 0, c0 = 0, Tn = 0, Lc = 0, Np = 0, np_max = 0, nseg = 0, R = 0;
+  std::vector<int> tab, tok0;
+  size_t o_lself = 0, o_rowpos = 0, o_row0 = 0, o_pself = 0, o_pcross = 0, o_ptok = 0, o_plast = 0;
+};
+
+int beam_continue_plan(int B, int beam, const int32_t* h_Tp, const int32_t* h_prefix, const int32_t* h_n_prefix,
+                       const int32_t* h_max_len, int min_len, int out_stride, int feat_rows, int max_tgt_pos, int vocab, int eos,
+                       int pad, int pm, BcPlan& P) {
+  if (B <= 0 || beam < 1 || beam > kMaxBeam || !h_Tp || !h_max_len) return SS_ERR_ARG;
   if ((long)B * beam > 256) return SS_ERR_CAPACITY;              // the row limit of the greedy twin (segment tables of the slab kernels)
+  if (vocab < 2 * beam + 1 || (size_t)vocab * sizeof(float) > 65536) return SS_ERR_ARG;   // the top-2k kernel holds a row in LDS
+  const int k = beam, R = B * beam;
+  auto npre = [&](int b) { return h_n_prefix ? h_n_prefix[b] : 0; };
+  int S = 0, Tn = 0, Np = 0, np_max = 0, nseg = 0;
+  for (int b = 0; b < B; ++b) {
+    const int st = npre(b);
+    if (h_Tp[b] <= 0 || st < 0 || h_max_len[b] < st || min_len > h_max_len[b]) return SS_ERR_ARG;
+    if (st > 0 && !h_prefix) return SS_ERR_ARG;
+    S = std::max(S, st);
+    Tn = std::max(Tn, h_max_len[b] - st);
+    Np += st + pm;
+    np_max = std::max(np_max, st + pm);
+    nseg += st + pm > 0 ? 1 : 0;
+  }
+  for (int b = 0, o = 0; b < B; ++b) {
+    for (int i = 0; i < npre(b); ++i) {
+      const int id = h_prefix[o + i];
+      if (id < 0 || id >= vocab) return SS_ERR_ARG;              // nn.Embedding's IndexError in the reference
+      if (id == eos || id == pad) return SS_ERR_ARG;             // a committed prefix never holds one (no replicate_first_beam, no padding)
+    }
+    o += npre(b);
+  }
+  for (int b = 0; b < B; ++b)                            // fed positions 0 .. max_len_b; scores of up to max_len_b + 1 tokens
+    if (h_max_len[b] + 1 > feat_rows || h_max_len[b] + 1 > out_stride || h_max_len[b] + 4 > max_tgt_pos) return SS_ERR_CAPACITY;
+  const int Smax = S + pm, c0 = S, Lc = c0 + Tn + 2;
+  const Offsets oe = prefix(h_Tp, B);
+  P.pm = pm; P.S = S; P.Smax = Smax; P.c0 = c0; P.Tn = Tn; P.Lc = Lc; P.Np = Np; P.np_max = np_max; P.nseg = nseg; P.R = R;
+  const size_t np = (size_t)Np, nl = (size_t)(Tn + 1) * 4 * R;
+  P.o_lself = 4 * (size_t)R; P.o_rowpos = P.o_lself + nl; P.o_row0 = P.o_rowpos + R; P.o_pself = P.o_row0 + B;
+  P.o_pcross = P.o_pself + 4 * (size_t)nseg; P.o_ptok = P.o_pcross + 4 * (size_t)nseg; P.o_plast = P.o_ptok + 5 * np;
+  P.tab.assign(P.o_plast + B, 0);
+  P.tok0.assign(R, eos);
+  int* cs = P.tab.data(); int* ls = cs + P.o_lself; int* rp = cs + P.o_rowpos; int* r0s = cs + P.o_row0; int* ps = cs + P.o_pself;
+  int* pc = cs + P.o_pcross; int* pt = cs + P.o_ptok; int* pp = pt + np; int* pk = pp + np; int* pf = pk + np; int* ft = pf + np;
+  int* pl = cs + P.o_plast;
+  for (int b = 0, o = 0, row = 0, seg = 0; b < B; ++b) {
+    const int st = npre(b), npp = st + pm, sh = Smax - npp;
+    for (int j = 0; j < k; ++j) {
+      const int r = b * k + j;
+      cs[4 * r] = r; cs[4 * r + 1] = 1; cs[4 * r + 2] = oe.off[b]; cs[4 * r + 3] = h_Tp[b];
+      rp[r] = -sh;
+      for (int t = 0; t <= Tn; ++t) {
+        int* e = &ls[((size_t)t * R + r) * 4];
+        e[0] = r; e[1] = 1; e[2] = sh; e[3] = c0 + t + 1 - sh;       // keys: cache indices sh .. c0 + t (positions 0 .. n_prefix + t)
+      }
+      if (st > 0) P.tok0[r] = h_prefix[o + st - 1];
+    }
+    r0s[b] = row;
+    pl[b] = npp > 0 ? row + npp - 1 : 0;
+    if (npp > 0) {
+      ps[4 * seg] = row; ps[4 * seg + 1] = npp; ps[4 * seg + 2] = row; ps[4 * seg + 3] = npp;
+      pc[4 * seg] = row; pc[4 * seg + 1] = npp; pc[4 * seg + 2] = oe.off[b]; pc[4 * seg + 3] = h_Tp[b];
+      ++seg;
+    }
+    for (int p = 0; p < npp; ++p) {
+      pt[row + p] = p == 0 ? eos : h_prefix[o + p - 1];
+      pp[row + p] = p;
+      pk[row + p] = b * k * Lc + sh + p;                             // slot 0 of the utterance
+      pf[row + p] = b * feat_rows + p;
+      ft[row + p] = p < st ? h_prefix[o + p] : -1;
+    }
+    row += npp;
+    o += st;
+  }
+  return SS_OK;
+}
+
+// The search of both entry points; the checks of `P` are done.
+int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp, const int32_t* h_n_prefix,
+                const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, const BcPlan& P, int32_t* h_out_tokens,
+                int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows) {
   const ss_config& c = m->cfg;
   const int D = c.dec_dim, F = c.dec_ffn, V = c.tgt_vocab, H = c.dec_heads, k = beam, R = B * beam;
-  if (V < 2 * k + 1 || (size_t)V * sizeof(float) > 65536) return SS_ERR_ARG;   // the top-2k kernel holds a row in LDS
-  int Lmax = 0;
-  for (int b = 0; b < B; ++b) {
-    if (h_Tp[b] <= 0 || h_max_len[b] < 0 || min_len > h_max_len[b]) return SS_ERR_ARG;
-    Lmax = std::max(Lmax, h_max_len[b]);
-  }
-  const int Lc = Lmax + 2;
-  if (Lc > feat_rows || Lc + 2 > c.max_tgt_pos || out_stride < Lmax + 1) return SS_ERR_CAPACITY;
+  const int Lc = P.Lc, Tn = P.Tn, c0 = P.c0, Np = P.Np;
   SkScope sk_scope(m->sc->skws);
   CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
   hipStream_t s = (hipStream_t)stream;
   const Offsets oe = prefix(h_Tp, B);
   // ---- scratch: everything booked before the first launch ----
-  const size_t n_tok = (size_t)(Lc + 1) * R, n_anc = (size_t)2 * R * Lc, n_cand = (size_t)R * kMaxCand, n_fin = (size_t)B * k * Lc;
+  const size_t np = (size_t)Np;
+  const size_t n_tok = (size_t)(Tn + 3) * R, n_anc = (size_t)2 * R * Lc, n_cand = (size_t)R * kMaxCand, n_fin = (size_t)B * k * Lc;
   const size_t n_fin_words = B + 2 * (size_t)B * k + 3 * n_fin;
-  const size_t n_state = 2 * n_tok + n_anc + 2 * n_cand + R + 2 * (size_t)B + n_fin_words;
+  const size_t n_state = 2 * n_tok + n_anc + 2 * n_cand + R + 3 * (size_t)B + n_fin_words;
   RET(m->sc->mt_cross.ensure((size_t)c.mt_layers * oe.total * 2 * D * sizeof(float)));
   RET(m->sc->bmt_self.ensure((size_t)c.mt_layers * R * Lc * 3 * D * sizeof(float)));
   RET(m->sc->bmb_feat.ensure((size_t)R * Lc * D * sizeof(float)));
-  RET(m->sc->mt_ws.ensure(((size_t)R * (3 * D + F + V)) * sizeof(float)));
+  RET(m->sc->mt_ws.ensure(((size_t)R * (3 * D + F + V) + (P.pm ? (size_t)R * D : 0)) * sizeof(float)));
   RET(m->sc->bmb_state.ensure(n_state * sizeof(int)));
-  // int tables: cross segs [R][4], self segs per step [Lc][R][4], feature gather [B][feat_rows]
-  RET(m->sc->seg_buf.ensure((4 * (size_t)R + (size_t)Lc * 4 * R + (size_t)B * feat_rows) * sizeof(int)));
+  // prefix pass: its workspace (mt_prefix_pass) | logits [Np][V] | forced log-probabilities [Np] | their positional scores [Np]
+  if (Np > 0) RET(m->sc->ws.ensure((np * (7 * D + F) + np * V + 2 * np) * sizeof(float)));
+  // int tables: the plan's tables | feature gather [B][feat_rows]
+  RET(m->sc->seg_buf.ensure((P.tab.size() + (size_t)B * feat_rows) * sizeof(int)));
 
   for (int l = 0; l < c.mt_layers; ++l)
     RET(linear(s, d_enc_out, c.enc_dim, oe.total, m->mt[l].cross_kv, 2 * D, c.enc_dim,
                m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D, 2 * D));
-  float* feat = m->sc->bmb_feat.f();           // [R][Lc][D] post-LN decoder states of every slot and step
+  float* feat = m->sc->bmb_feat.f();           // [R][Lc][D] post-LN decoder states of every slot and cache index
   float* x = m->sc->mt_ws.f();
   float* h = x + (size_t)R * D;
   float* q2 = h + (size_t)R * D;
   float* ff = q2 + (size_t)R * D;
   float* logits = ff + (size_t)R * F;
+  float* last_rows = logits + (size_t)R * V;   // beam 1: each utterance's last prefix-pass state
   int* w = (int*)m->sc->bmb_state.p;
   BeamState st;
   st.tok = w; w += n_tok;
@@ -283,6 +431,7 @@ extern "C" int ss_batch_mt_beam(ss_model* m, void* stream, int B, int beam, cons
   st.ignore = w; w += R;
   st.done = w; w += B;
   st.max_len = w; w += B;
+  st.npre = w; w += B;
   int* fin_base = w;
   st.fin_cnt = w; w += B;
   st.fin_score = (float*)w; w += (size_t)B * k;
@@ -290,54 +439,80 @@ extern "C" int ss_batch_mt_beam(ss_model* m, void* stream, int B, int beam, cons
   st.fin_tok = w; w += n_fin;
   st.fin_pos = (float*)w; w += n_fin;
   st.fin_anc = w; w += n_fin;
-  int* d_cross = (int*)m->sc->seg_buf.p;
-  int* d_self = d_cross + 4 * R;
-  int* d_gather = d_self + (size_t)Lc * 4 * R;
+  int* d_tab = (int*)m->sc->seg_buf.p;
+  const int* d_cross = d_tab;
+  const int* d_self = d_tab + P.o_lself;
+  const int* d_rowpos = d_tab + P.o_rowpos;
+  const int* d_row0 = d_tab + P.o_row0;
+  int* d_gather = d_tab + P.tab.size();
+  const std::vector<int> np0 = h_n_prefix ? std::vector<int>(h_n_prefix, h_n_prefix + B) : std::vector<int>(B, 0);   // lives to the end of the call
   SS_HIP_CHECK(hipMemsetAsync(m->sc->bmb_state.p, 0, n_state * sizeof(int), s));   // slot 0 / score 0 / nothing finalised everywhere
   {
-    std::vector<int> t0(R, c.eos), a0((size_t)R * Lc), ml(h_max_len, h_max_len + B), cs(4 * (size_t)R), ss((size_t)Lc * 4 * R);
-    for (int r = 0; r < R; ++r) {
-      const int b = r / k;
-      std::fill(a0.begin() + (size_t)r * Lc, a0.begin() + (size_t)(r + 1) * Lc, r);
-      cs[4 * r] = r; cs[4 * r + 1] = 1; cs[4 * r + 2] = oe.off[b]; cs[4 * r + 3] = h_Tp[b];
+    std::vector<int> a0((size_t)R * Lc), ml(h_max_len, h_max_len + B);
+    for (int r = 0; r < R; ++r) {                // prefix-pass positions live in slot 0 of the utterance, the others in the slot itself
+      std::fill(a0.begin() + (size_t)r * Lc, a0.begin() + (size_t)r * Lc + P.Smax, (r / k) * k);
+      std::fill(a0.begin() + (size_t)r * Lc + P.Smax, a0.begin() + (size_t)(r + 1) * Lc, r);
     }
-    for (int p = 0; p < Lc; ++p)
-      for (int r = 0; r < R; ++r) {
-        int* e = &ss[((size_t)p * R + r) * 4];
-        e[0] = r; e[1] = 1; e[2] = 0; e[3] = p + 1;
-      }
-    RET(upload(s, st.tok, t0)); RET(upload(s, st.max_len, ml)); RET(upload(s, d_cross, cs)); RET(upload(s, d_self, ss));
-    RET(upload(s, st.anc, a0));      // anc[0][r][*] = r: position 0 of every hypothesis is its own row
+    RET(upload(s, st.tok, P.tok0)); RET(upload(s, st.max_len, ml)); RET(upload(s, d_tab, P.tab));
+    RET(upload(s, st.anc, a0));
+    if (h_n_prefix) RET(upload(s, st.npre, np0));
+  }
+  const float* d_prepos = nullptr;
+  if (Np > 0) {
+    // ---- the prefix pass: every forced position once per utterance, K/V into slot 0, then the forced tokens' scores ----
+    const int* d_ptok = d_tab + P.o_ptok;
+    const int *d_ppos = d_ptok + np, *d_pcache = d_ppos + np, *d_pfeat = d_pcache + np, *d_ftok = d_pfeat + np;
+    const float* pfo = nullptr;
+    RET(mt_prefix_pass(m, s, P.nseg, Np, P.np_max, oe.total, d_ptok, d_ppos, d_tab + P.o_pself, d_tab + P.o_pcross, nullptr, d_pcache,
+                       R * Lc, &pfo));
+    RET(launch_scatter_rows(d_pfeat, pfo, D, d_feats, D, D, Np, B * feat_rows, s));
+    float* plog = m->sc->ws.f() + np * (7 * D + F);
+    float* lp = plog + np * V;
+    float* prepos = lp + np;
+    Lin proj{m->mt_emb, nullptr};
+    RET(linear(s, pfo, D, Np, proj, V, D, plog, V));
+    hipLaunchKernelGGL(beam_prefix_score_kernel, dim3(Np), dim3(256), 0, s, plog, V, d_ftok, c.pad, c.unk, unk_penalty, lp);
+    SS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(beam_prefix_chain_kernel, dim3((B + 255) / 256), dim3(256), 0, s, lp, d_row0, st.npre, B, k, st.cum, prepos);
+    SS_LAUNCH_CHECK();
+    if (P.pm) RET(launch_gather_rows(d_tab + P.o_plast, pfo, D, last_rows, B, s, Np));
+    d_prepos = prepos;
   }
   std::vector<int> host_done(B, 0);
-  int step = 0;
+  int step = 0;                                // lock-step index
   constexpr int kCheck = 4;
   CanonScope decode_scope(m->pack_invariant ? CANON_SMALLM : CANON_NONE);   // the greedy twin's decode-row GEMM form
   while (true) {
-    RET(launch_embed_tokens(st.tok + (size_t)step * R, m->mt_emb, m->mt_pos, sqrtf((float)D), step + c.pad + 1, x, R, D, s, 0, -1, V));
-    for (int l = 0; l < c.mt_layers; ++l) {
-      float* cache = m->sc->bmt_self.f() + (size_t)l * R * Lc * 3 * D;
-      float* rows = cache + (size_t)step * 3 * D;                    // slot r at + r*Lc*3D: written once, never reordered
-      AttnArgs at;
-      at.Q = rows; at.ldq = Lc * 3 * D; at.K = cache + D; at.V = cache + 2 * D; at.ldk = at.ldv = 3 * D;
-      at.O = h; at.ldo = D; at.H = H; at.scale = 1.f; at.causal = 0;
-      at.segs = d_self + (size_t)step * 4 * R; at.nseg = R; at.max_q = 1;
-      at.anc = st.anc + (size_t)(step & 1) * R * Lc; at.anc_ld = Lc; at.anc_slots = R;
-      AttnArgs ac;
-      ac.Q = q2; ac.ldq = D; ac.K = m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D; ac.V = ac.K + D; ac.ldk = ac.ldv = 2 * D;
-      ac.O = h; ac.ldo = D; ac.H = H; ac.scale = 1.f; ac.segs = d_cross; ac.nseg = R; ac.max_q = 1;
-      RET(dec_layer_ex(s, c, m->mt[l], x, R, rows, Lc * 3 * D, at, &ac, h, q2, ff));
-    }
-    float* frow = feat + (size_t)step * D;
-    RET(launch_layernorm(x, D, frow, Lc * D, m->mt_ln.g, m->mt_ln.b, R, D, 1e-5f, s));
+    const int ci = c0 + step;                  // cache index every slot writes at this step
     Lin proj{m->mt_emb, nullptr};
-    RET(linear(s, frow, Lc * D, R, proj, V, D, logits, V));
-    hipLaunchKernelGGL(beam_topk_kernel, dim3(R), dim3(256), V * sizeof(float), s, logits, V, k, step, min_len, st.max_len,
+    if (P.pm && step == 0) {                   // beam 1: the first free step reads the last prefix-pass row, projected as a lock-step row
+      RET(linear(s, last_rows, D, R, proj, V, D, logits, V));
+    } else {
+      RET(launch_embed_tokens_rows(st.tok + (size_t)step * R, m->mt_emb, m->mt_pos, c.max_tgt_pos, sqrtf((float)D), ci + c.pad + 1,
+                                   d_rowpos, x, R, D, s, -1, V));
+      for (int l = 0; l < c.mt_layers; ++l) {
+        float* cache = m->sc->bmt_self.f() + (size_t)l * R * Lc * 3 * D;
+        float* rows = cache + (size_t)ci * 3 * D;                      // slot r at + r*Lc*3D: written once, never reordered
+        AttnArgs at;
+        at.Q = rows; at.ldq = Lc * 3 * D; at.K = cache + D; at.V = cache + 2 * D; at.ldk = at.ldv = 3 * D;
+        at.O = h; at.ldo = D; at.H = H; at.scale = 1.f; at.causal = 0;
+        at.segs = d_self + (size_t)step * 4 * R; at.nseg = R; at.max_q = 1;
+        at.anc = st.anc + (size_t)(step & 1) * R * Lc; at.anc_ld = Lc; at.anc_slots = R;
+        AttnArgs ac;
+        ac.Q = q2; ac.ldq = D; ac.K = m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D; ac.V = ac.K + D; ac.ldk = ac.ldv = 2 * D;
+        ac.O = h; ac.ldo = D; ac.H = H; ac.scale = 1.f; ac.segs = d_cross; ac.nseg = R; ac.max_q = 1;
+        RET(dec_layer_ex(s, c, m->mt[l], x, R, rows, Lc * 3 * D, at, &ac, h, q2, ff));
+      }
+      float* frow = feat + (size_t)ci * D;
+      RET(launch_layernorm(x, D, frow, Lc * D, m->mt_ln.g, m->mt_ln.b, R, D, 1e-5f, s));
+      RET(linear(s, frow, Lc * D, R, proj, V, D, logits, V));
+    }
+    hipLaunchKernelGGL(beam_topk_kernel, dim3(R), dim3(256), V * sizeof(float), s, logits, V, k, step, min_len, st.max_len, st.npre,
                        st.done, st.cum + (size_t)step * R, c.pad, c.unk, c.eos, unk_penalty, st.cand_s, st.cand_t);
     SS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, s, st, k, R, Lc, V, step, c.eos, normalize ? 1 : 0);
+    hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, s, st, k, R, Lc, V, step, c0, c.eos, normalize ? 1 : 0);
     SS_LAUNCH_CHECK();
-    const bool last = step >= Lmax;            // every utterance is done at its max_len step
+    const bool last = step >= Tn;              // every utterance is done at its max_len step
     ++step;
     if (last || step % kCheck == 0) {
       SS_HIP_CHECK(hipMemcpyAsync(host_done.data(), st.done, B * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -349,7 +524,9 @@ extern "C" int ss_batch_mt_beam(ss_model* m, void* stream, int B, int beam, cons
   }
   // ---- results: the finalised tables, sorted by score (descending; ties keep finalisation order) ----
   std::vector<int> fin(n_fin_words);
+  std::vector<float> prepos(np);
   SS_HIP_CHECK(hipMemcpyAsync(fin.data(), fin_base, n_fin_words * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (Np > 0) SS_HIP_CHECK(hipMemcpyAsync(prepos.data(), d_prepos, np * sizeof(float), hipMemcpyDeviceToHost, s));
   SS_HIP_CHECK(hipStreamSynchronize(s));
   const int* f_cnt = fin.data();
   const float* f_score = reinterpret_cast<const float*>(f_cnt + B);
@@ -357,9 +534,10 @@ extern "C" int ss_batch_mt_beam(ss_model* m, void* stream, int B, int beam, cons
   const int* f_tok = f_len + (size_t)B * k;
   const float* f_pos = reinterpret_cast<const float*>(f_tok + n_fin);
   const int* f_anc = f_tok + 2 * n_fin;
+  const int* row0 = P.tab.data() + P.o_row0;
   std::vector<int> gidx((size_t)B * feat_rows, -1);
   for (int b = 0; b < B; ++b) {
-    const int n = std::min(f_cnt[b], k);
+    const int n = std::min(f_cnt[b], k), npre = h_n_prefix ? h_n_prefix[b] : 0, npp = npre + P.pm, sh = P.Smax - npp;
     std::vector<int> ord(n);
     for (int e = 0; e < n; ++e) ord[e] = e;
     std::stable_sort(ord.begin(), ord.end(), [&](int a, int e) { return f_score[b * k + a] > f_score[b * k + e]; });
@@ -371,14 +549,74 @@ extern "C" int ss_batch_mt_beam(ss_model* m, void* stream, int B, int beam, cons
       h_n_out[o] = len;
       h_scores[o] = f_score[b * k + e];
       for (int p = 0; p < len; ++p) h_out_tokens[o * out_stride + p] = f_tok[src + p];
-      if (h_pos_scores)
-        for (int p = 0; p < len; ++p) h_pos_scores[o * out_stride + p] = f_pos[src + p];
-      if (i == 0)           // the best hypothesis' decoder states: </s> + its tokens without the final </s>
-        for (int p = 0; p < len; ++p) gidx[(size_t)b * feat_rows + p] = f_anc[src + p] * Lc + p;
+      if (h_pos_scores) {                      // the whole hypothesis: the forced tokens' scores, then the generated ones'
+        for (int p = 0; p < npre; ++p) h_pos_scores[o * out_stride + p] = prepos[row0[b] + p];
+        for (int p = 0; p < len; ++p) h_pos_scores[o * out_stride + npre + p] = f_pos[src + p];
+      }
+      if (i == 0)           // the best hypothesis' decoder states past the prefix pass: fed positions npp .. n_prefix + len - 1
+        for (int q = npp; q < npre + len; ++q) gidx[(size_t)b * feat_rows + q] = f_anc[src + sh + q] * Lc + sh + q;
     }
   }
   RET(upload(s, d_gather, gidx));
   hipLaunchKernelGGL(beam_feat_gather_kernel, dim3(B * feat_rows), dim3(256), 0, s, d_gather, feat, D, R * Lc, d_feats);
   SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+}  // namespace
+
+// Batched beam search of the first-pass text decoder (include/streamspeech_hip.h): the search with no prefix anywhere.
+extern "C" int ss_batch_mt_beam(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                                const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens,
+                                int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats,
+                                int feat_rows) {
+  if (!m || B <= 0 || beam < 1 || beam > kMaxBeam || !d_feats || !h_out_tokens || !h_n_out || !h_scores) return SS_ERR_ARG;
+  if ((long)B * beam > 256) return SS_ERR_CAPACITY;              // the row limit of the greedy twin (segment tables of the slab kernels)
+  const ss_config& c = m->cfg;
+  if (c.tgt_vocab < 2 * beam + 1 || (size_t)c.tgt_vocab * sizeof(float) > 65536) return SS_ERR_ARG;   // the top-2k kernel holds a row in LDS
+  int Lmax = 0;
+  for (int b = 0; b < B; ++b) {
+    if (h_Tp[b] <= 0 || h_max_len[b] < 0 || min_len > h_max_len[b]) return SS_ERR_ARG;
+    Lmax = std::max(Lmax, h_max_len[b]);
+  }
+  if (Lmax + 2 > feat_rows || Lmax + 4 > c.max_tgt_pos || out_stride < Lmax + 1) return SS_ERR_CAPACITY;
+  BcPlan P;
+  RET(beam_continue_plan(B, beam, h_Tp, nullptr, nullptr, h_max_len, min_len, out_stride, feat_rows, c.max_tgt_pos, c.tgt_vocab, c.eos,
+                         c.pad, 0, P));      // position 0 is a lock-step row at every beam (beam 1 is ss_batch_mt_greedy bit for bit)
+  return beam_search(m, stream, B, beam, d_enc_out, h_Tp, nullptr, h_max_len, min_len, unk_penalty, normalize, P, h_out_tokens,
+                     out_stride, h_n_out, h_scores, h_pos_scores, d_feats, feat_rows);
+}
+
+// The same search behind a forced prefix per utterance (include/streamspeech_hip.h).
+extern "C" int ss_batch_mt_beam_continue(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                                         const int32_t* h_prefix, const int32_t* h_n_prefix, const int32_t* h_max_len, int min_len,
+                                         float unk_penalty, int normalize, int32_t* h_out_tokens, int out_stride, int32_t* h_n_out,
+                                         float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows) {
+  if (!m || !d_enc_out || !h_n_prefix || !d_feats || !h_out_tokens || !h_n_out || !h_scores) return SS_ERR_ARG;
+  const ss_config& c = m->cfg;
+  BcPlan P;
+  RET(beam_continue_plan(B, beam, h_Tp, h_prefix, h_n_prefix, h_max_len, min_len, out_stride, feat_rows, c.max_tgt_pos, c.tgt_vocab,
+                         c.eos, c.pad, beam == 1 ? 1 : 0, P));
+  return beam_search(m, stream, B, beam, d_enc_out, h_Tp, h_n_prefix, h_max_len, min_len, unk_penalty, normalize, P, h_out_tokens,
+                     out_stride, h_n_out, h_scores, h_pos_scores, d_feats, feat_rows);
+}
+
+extern "C" int ss_batch_mt_beam_continue_plan(int B, int beam, const int32_t* h_Tp, const int32_t* h_prefix, const int32_t* h_n_prefix,
+                                              const int32_t* h_max_len, int min_len, int out_stride, int feat_rows, int max_tgt_pos,
+                                              int vocab, int eos, int pad, int32_t* h_dims, int32_t* h_tables, int64_t tables_cap,
+                                              int64_t* h_n_tables) {
+  if (!h_n_prefix) return SS_ERR_ARG;
+  BcPlan P;
+  RET(beam_continue_plan(B, beam, h_Tp, h_prefix, h_n_prefix, h_max_len, min_len, out_stride, feat_rows, max_tgt_pos, vocab, eos, pad,
+                         beam == 1 ? 1 : 0, P));
+  if (h_dims) {
+    h_dims[0] = P.S; h_dims[1] = P.Tn; h_dims[2] = P.Lc; h_dims[3] = P.Np; h_dims[4] = P.R; h_dims[5] = P.c0; h_dims[6] = P.nseg;
+    h_dims[7] = P.pm;
+  }
+  if (h_n_tables) *h_n_tables = (int64_t)P.tab.size();
+  if (h_tables) {
+    if (tables_cap < (int64_t)P.tab.size()) return SS_ERR_CAPACITY;
+    std::copy(P.tab.begin(), P.tab.end(), h_tables);
+  }
   return SS_OK;
 }

@@ -441,6 +441,11 @@ static int enc_layer_ex(hipStream_t s, const ss_config& c, const EncLayer& e, fl
   return enc_ffn_half(s, c, x, n, e.ffn2_ln, e.ffn2_w1, e.ffn2_w2, &e.final_ln, ffn_fused, canon, h, ff);
 }
 
+// The ragged prefix pass of the MT decoder (batch.hip): shared by ss_batch_mt_continue, ss_batch_mt_features and the beam search behind
+// a forced prefix (beam.hip).
+int mt_prefix_pass(ss_model* m, hipStream_t s, int B, int Np, int np_max, int n_enc, const int* d_ptok, const int* d_ppos,
+                   const int* d_pself, const int* d_pcross, const int* d_ptail, const int* d_pcache, int cache_rows, const float** out);
+
 extern std::atomic<int> g_mt_timeouts;      // bounded-wait time-outs of persistent MT decode steps, process-wide (model.hip)
 
 struct ConvW { const float* w = nullptr; const float* b = nullptr; const float* ww = nullptr;   // ww: Winograd form (64-channel stage ResBlock convs)

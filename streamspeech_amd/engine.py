@@ -178,6 +178,48 @@ class BatchMixin:
         n_feats = [len(h[0]["tokens"]) if h else 0 for h in nbest]
         return nbest, feats, n_feats
 
+    def batch_mt_beam_continue(self, enc_packed: torch.Tensor, Tp: List[int], prefixes: List[List[int]], max_len: List[int], beam: int,
+                               min_len: int = 1, unk_penalty: float = 0.0, normalize: bool = True):
+        """Beam search behind a forced prefix per row (ss_batch_mt_beam_continue; fairseq's ``prefix_tokens`` of the offline generator)
+        -> (nbest, feats).  nbest[b] holds up to `beam` dicts, best first: "tokens" is the FULL hypothesis (prefixes[b] + generated,
+        incl. the final eos), "score" and "positional_scores" cover it whole.  feats[b] = decoder states [n_prefix_b + n_generated_b, D]
+        of hypothesis 0's fed positions, as batch_mt_continue returns them.  A pack with B * beam > 256 rows runs as consecutive
+        sub-calls (plan_beam_groups); pack-invariant arithmetic makes the split invisible."""
+        B = len(Tp)
+        if not (len(prefixes) == len(max_len) == B):
+            raise ValueError("one prefix and one max_len per row")
+        if not 1 <= beam <= MT_BEAM_MAX:
+            raise ValueError(f"beam {beam} outside [1, {MT_BEAM_MAX}]")
+        rows = stride = max(max_len) + 1
+        feats = torch.empty((B, rows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
+        nbest: List[List[dict]] = []
+        off = np.concatenate([[0], np.cumsum(Tp)]).astype(np.int64)
+        for b0, b1 in plan_beam_groups(B, beam):
+            n = b1 - b0
+            enc = enc_packed[int(off[b0]):int(off[b1])]
+            flat = [int(t) for p in prefixes[b0:b1] for t in p]
+            out = (C.c_int32 * (n * beam * stride))()
+            n_out = (C.c_int32 * (n * beam))()
+            sc = (C.c_float * (n * beam))()
+            pos = (C.c_float * (n * beam * stride))()
+            L.check(self.lib.ss_batch_mt_beam_continue(self.h, _stream(), n, beam, _ptr(enc), _i32(Tp[b0:b1]), _i32(flat or [0]),
+                                                       _i32([len(p) for p in prefixes[b0:b1]]), _i32(max_len[b0:b1]), int(min_len),
+                                                       float(unk_penalty), 1 if normalize else 0, out, stride, n_out, sc, pos,
+                                                       _ptr(feats[b0:b1]), rows), "ss_batch_mt_beam_continue")
+            for b in range(n):
+                pre = [int(t) for t in prefixes[b0 + b]]
+                hyps = []
+                for i in range(beam):
+                    o = b * beam + i
+                    k = n_out[o]
+                    if k <= 0:
+                        continue
+                    hyps.append({"tokens": pre + list(out[o * stride: o * stride + k]), "score": float(sc[o]),
+                                 "positional_scores": list(pos[o * stride: o * stride + len(pre) + k])})
+                nbest.append(hyps)
+        n_feats = [len(h[0]["tokens"]) if h else 0 for h in nbest]
+        return nbest, [feats[b, :n_feats[b]] for b in range(B)]
+
     def last_logits(self) -> torch.Tensor:
         """Dense logits [rows, cols] of this context's last batch_ctc_greedy / batch_t2u_units call (test hook: arg-max margins)."""
         rows, cols = C.c_int(0), C.c_int(0)
@@ -649,6 +691,52 @@ def plan_mt_continue(Tp: List[int], n_prefix: List[int], max_len: List[int], min
     p["prefix_tokens"], p["prefix_pos"], p["cache_row"], p["feat_row"] = take(Np), take(Np), take(Np), take(Np)
     p["last_row"] = take(B)
     p["r0"] = [seg[0] for seg in p["prefix_self"]]
+    assert o == len(t)
+    return p
+
+
+def plan_mt_beam_continue(Tp: List[int], n_prefix: List[int], max_len: List[int], beam: int, min_len: int = 1,
+                          feat_rows: Optional[int] = None, out_stride: Optional[int] = None, max_tgt_pos: int = 1026,
+                          prefix_ids: Optional[List[int]] = None, vocab: int = 6000, eos: int = 2, pad: int = 1) -> dict:
+    """Layout and refusals of one ss_batch_mt_beam_continue call, as the library makes them (ss_batch_mt_beam_continue_plan, host only
+    -- the same planner the call runs).  R = B * beam slots; row b's cache is shifted by S - n_prefix[b] (S = the longest prefix), so
+    every slot writes cache index c0 + t at lock-step index t.  feat_rows / out_stride default to the least the call needs.  Raises
+    ContinueRefused with the code the call returns."""
+    B = len(Tp)
+    if len(n_prefix) != B or len(max_len) != B:
+        raise ContinueRefused("one prefix length and max_len per row", L.SS_ERR_ARG)
+    if B and feat_rows is None:
+        feat_rows = max(m + 1 for m in max_len)
+    if B and out_stride is None:
+        out_stride = max(m + 1 for m in max_len)
+    ids = list(prefix_ids) if prefix_ids is not None else [4] * sum(max(int(n), 0) for n in n_prefix)
+    lib = L.load()
+    dims, n_tab = (C.c_int32 * 8)(), C.c_int64(0)
+    args = (B, int(beam), _i32(Tp or [0]), _i32(ids or [0]), _i32(n_prefix or [0]), _i32(max_len or [0]), int(min_len),
+            int(out_stride or 0), int(feat_rows or 0), int(max_tgt_pos), int(vocab), int(eos), int(pad))
+    rc = lib.ss_batch_mt_beam_continue_plan(*args, dims, None, 0, C.byref(n_tab))
+    if rc != 0:
+        raise ContinueRefused(f"ss_batch_mt_beam_continue refuses the call: {lib.ss_error_string(rc).decode()}", rc)
+    tab = (C.c_int32 * n_tab.value)()
+    L.check(lib.ss_batch_mt_beam_continue_plan(*args, dims, tab, n_tab.value, C.byref(n_tab)), "ss_batch_mt_beam_continue_plan")
+    S, Tn, Lc, Np, R, c0, nseg, pm = list(dims)
+    t, o = list(tab), 0
+
+    def take(n):
+        nonlocal o
+        o += n
+        return t[o - n:o]
+    quads = lambda v: [tuple(v[4 * i:4 * i + 4]) for i in range(len(v) // 4)]    # noqa: E731
+    p = {"S": S, "Tn": Tn, "Lc": Lc, "Np": Np, "R": R, "c0": c0, "prefix_segments": nseg, "last_forced_in_prefix_pass": bool(pm),
+         "feat_rows": feat_rows, "out_stride": out_stride}
+    p["step_cross"] = quads(take(4 * R))
+    steps = quads(take(4 * R * (Tn + 1)))
+    p["step_self"] = [steps[k * R:(k + 1) * R] for k in range(Tn + 1)]
+    p["shift"] = [-x for x in take(R)]
+    p["r0"] = take(B)
+    p["prefix_self"], p["prefix_cross"] = quads(take(4 * nseg)), quads(take(4 * nseg))
+    p["prefix_tokens"], p["prefix_pos"], p["cache_row"], p["feat_row"], p["forced"] = take(Np), take(Np), take(Np), take(Np), take(Np)
+    p["last_row"] = take(B)
     assert o == len(t)
     return p
 

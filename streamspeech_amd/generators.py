@@ -63,11 +63,18 @@ class SequenceGenerator:
     """agent/sequence_generator.py:165-582 at beam_size = 1: greedy first-pass text
     decoding with prefix and ``max_new_tokens``.  Keeps the reference's token-buffer semantics
     ([eos, prefix...], forced eos at max_len, eos banned below min_len) but feeds only NEW positions
-    to the decoder thanks to the KV cache (per-position results are identical)."""
+    to the decoder thanks to the KV cache (per-position results are identical).
+
+    beam_size > 1: a beam search behind the forced prefix with the semantics of the OFFLINE generator's ``prefix_tokens``
+    (unity/sequence_generator.py with fairseq's ``_prefix_tokens``: one live hypothesis after the prefix, scores and length
+    normalisation count the prefix), on the engine's ``batch_mt_beam_continue``.  The agents' own generator pre-fills the prefix and
+    ranks k identical rows at the first free step, which is defined only at beam 1; that is the path above and it is unchanged."""
 
     def __init__(self, engine, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, max_len=0, min_len=1,
-                 eos=None, use_incremental_states=False, **kw):
-        assert beam_size == 1, "the StreamSpeech agent always searches with beam 1"
+                 eos=None, use_incremental_states=False, unk_penalty=0.0, normalize_scores=True, **kw):
+        if not 1 <= int(beam_size) <= 32:
+            raise ValueError(f"beam_size {beam_size} outside [1, 32]")
+        self.beam_size, self.unk_penalty, self.normalize_scores = int(beam_size), float(unk_penalty), bool(normalize_scores)
         self.engine, self.tgt_dict = engine, tgt_dict
         self.max_len_a, self.max_len_b, self.min_len = max_len_a, max_len_b, min_len
         self.max_len = max_len or engine.cfg.max_target_positions
@@ -90,6 +97,15 @@ class SequenceGenerator:
         start = len(prefix)
         max_len = mt_max_len(start, src_len, max_new_tokens, self.max_len_a, self.max_len_b, self.max_len, self.min_len)
         eng = self.engine
+        if self.beam_size > 1:
+            enc = enc.contiguous()
+            nbest, feats = eng.batch_mt_beam_continue(enc, [int(enc.shape[0])], [prefix], [max_len], self.beam_size, self.min_len,
+                                                      self.unk_penalty, self.normalize_scores)
+            hyps = [{"tokens": torch.tensor(h["tokens"], dtype=torch.long), "features": None, "score": h["score"], "attention": None,
+                     "alignment": None, "positional_scores": torch.tensor(h["positional_scores"], dtype=torch.float32)}
+                    for h in nbest[0]]
+            hyps[0]["features"] = feats[0]
+            return [hyps]
         if hasattr(eng, "mt_greedy"):
             out, feats = eng.mt_greedy(enc.contiguous(), prefix, max_len, self.min_len)
             return [[{"tokens": torch.tensor(prefix + out, dtype=torch.long), "features": feats, "score": None,

@@ -100,6 +100,12 @@ SIGNATURES = {
     "ss_batch_mt_continue_plan": (_i, [_i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                        C.POINTER(C.c_int32), _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                        _i64, C.POINTER(_i64)]),
+    "ss_batch_mt_beam_continue": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32), _i, _f, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32),
+                                       C.POINTER(_f), C.POINTER(_f), _vp, _i]),
+    "ss_batch_mt_beam_continue_plan": (_i, [_i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), _i64, C.POINTER(_i64)]),
     "ss_batch_fbank_frames": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f,
                                    C.POINTER(_vp)]),
     "ss_batch_t2u_units": (_i, [_vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp]),

@@ -13,6 +13,7 @@ from typing import Dict, Optional
 
 import torch
 
+from .engine import MT_BEAM_MAX, plan_beam_groups
 from .frontend import SAMPLE_RATE, OnlineFeatureExtractor, unsettled_fbank_frames
 from .simuleval_shim import AgentStates, EmptySegment, TextSegment
 from .text_policy import mt_max_len, s2tt_gate
@@ -71,7 +72,12 @@ class TextSessionPool:
     """Up to `max_sessions` concurrent ASR / S2TT sessions, each of at most `max_rows` encoder output rows (~40 ms each)."""
     KINDS = KINDS
 
-    def __init__(self, model, max_sessions: int, max_rows: int):
+    def __init__(self, model, max_sessions: int, max_rows: int, beam_mt: int = 1):
+        """beam_mt > 1: the step's one ragged continuation is a beam search behind every writer's committed prefix
+        (HipModel.batch_mt_beam_continue, the agents' --beam-mt); hypothesis 0's tokens and states go on as the greedy ones do."""
+        if not 1 <= int(beam_mt) <= MT_BEAM_MAX:
+            raise ValueError(f"beam_mt {beam_mt} outside [1, {MT_BEAM_MAX}]")
+        self.beam_mt = int(beam_mt)
         self.model = model.hip if hasattr(model, "hip") else model
         self.pool = self.model.stream_pool(max_sessions, max_rows)
         self.max_sessions, self.max_rows = int(max_sessions), int(max_rows)
@@ -212,7 +218,7 @@ class TextSessionPool:
         t1 = time.perf_counter()
         # ---- one encoder step + both CTC heads ----
         enc = [s for s in todo if s.sid in feats]
-        writers, n_steps, mine, views = [], 0, [], None
+        writers, n_steps, mine, views, mt_groups = [], 0, [], None, []
         if enc:
             for s in enc:
                 self._acquire(s)
@@ -249,8 +255,7 @@ class TextSessionPool:
                 else:
                     enc_w = torch.cat([views[i] for i, _, _, _, _ in writers], 0)
                     Tp = [views[i].shape[0] for i, _, _, _, _ in writers]
-                res = self.model.batch_mt_continue(enc_w, Tp, [p for _, _, p, _, _ in writers], [m for _, _, _, m, _ in writers],
-                                                   MIN_LEN)
+                res, mt_groups = self._mt_call(enc_w, Tp, [p for _, _, p, _, _ in writers], [m for _, _, _, m, _ in writers])
                 for w, (toks, fts) in zip(writers, res):
                     i, s, prefix, ml, new = w
                     n_steps = max(n_steps, len(toks) - 1)
@@ -279,11 +284,22 @@ class TextSessionPool:
             out[s.sid] = seg
             if s.states.target_finished:          # finished without the agent's reset(): it answers EmptySegment(finished=True)
                 self._release(s)                  # from now on, so its slot goes back; reset(sid) starts a fresh utterance
-        self.last_step = {"sessions": len(todo), "encoded": len(enc), "writers": len(writers), "mt_steps": n_steps,
+        self.last_step = {"sessions": len(todo), "encoded": len(enc), "writers": len(writers), "mt_steps": n_steps, "mt_groups": mt_groups,
                           "frontend_s": t1 - t0, "encoder_ctc_s": t2 - t1, "mt_s": t3 - t2, "total_s": time.perf_counter() - t0}
         self.last_step.update(self._side_times)
         self._side_times = {}
         return out
+
+    def _mt_call(self, enc_w, Tp, prefixes, max_len):
+        """The step's ONE ragged continuation of every writer's committed prefix -> (per writer (tokens after the prefix incl. the
+        final eos, decoder states of the fed positions), the [start, end) writer ranges of the device calls it took).  beam_mt = 1:
+        the greedy continuation, as always.  beam_mt > 1: the beam search behind the prefix, hypothesis 0 of each writer; writers x
+        beam_mt hypothesis rows are at most 256 per device call, so a step with more writers runs as the consecutive sub-calls of
+        plan_beam_groups inside the engine call (nobody is refused)."""
+        if self.beam_mt == 1:
+            return self.model.batch_mt_continue(enc_w, Tp, prefixes, max_len, MIN_LEN), [(0, len(Tp))]
+        nbest, feats = self.model.batch_mt_beam_continue(enc_w, Tp, prefixes, max_len, self.beam_mt, MIN_LEN)
+        return [(h[0]["tokens"][len(p):], f) for h, f, p in zip(nbest, feats, prefixes)], plan_beam_groups(len(Tp), self.beam_mt)
 
     # ---- hooks of a subclass's session kinds (speech_pool.py) -------------------------------------------------------------------
     def _gate(self, s, src_ids, tgt_ids, n_frames):
