@@ -102,7 +102,11 @@ int ss_fbank_cmvn(ss_model* m, void* stream, const float* d_pcm16k, int n_sample
  * arithmetic outside the fbank-input parity contract).  d_out[k] = sum_m d_in[m] *
  * d_taps[half_len + k*down - m*up] for k < n_out; n_out is normally ceil(n_in*up/down), up/down in
  * lowest terms, d_taps [2*half_len+1] is the host-designed low-pass with gain `up`
- * (streamspeech_amd/frontend.py design_filter). */
+ * (streamspeech_amd/frontend.py design_filter).
+ * A STREAMING source at another rate than 16 kHz does not go through ss_resample + ss_fbank_cmvn over its growing history: the
+ * rows that can still change are made from the source-rate history in one launch for any number of sessions, with this
+ * resampler's sum inside the fbank row's workgroup (ss_batch_fbank_frames_sr and ss_fbank_sr_rows, with the ragged-batch calls
+ * below). */
 int ss_resample(void* stream, const float* d_in, int64_t n_in, int up, int down, const float* d_taps,
                 int half_len, float* d_out, int64_t n_out);
 
@@ -440,6 +444,25 @@ int ss_batch_mt_beam_continue_plan(int B, int beam, const int32_t* h_Tp, const i
  * same bits as ss_fbank_cmvn's rows.  h_n[b] = 0 skips a session.  1 <= B <= 65535. */
 int ss_batch_fbank_frames(ss_model* m, void* stream, int B, const float* const* h_pcm, const int32_t* h_first, const int32_t* h_n,
                           float pcm_scale, float* const* h_feat);
+/* ss_batch_fbank_frames for sessions at ANY source rate, each at its own, in one launch and from the source-rate history directly (no
+ * 16-kHz history in between): session b's rows h_first[b] .. h_first[b] + h_n[b] - 1 of the fbank of h_pcm[b][0 .. h_n_in[b]) (device,
+ * at the source rate) resampled by h_up[b] / h_down[b] (lowest terms) with the low-pass h_taps[b] (device, [2 * h_half_len[b] + 1], gain
+ * up: ss_resample's arguments) go to h_feat[b] (device, h_n[b] rows of 80).  Each 16-kHz sample of a row is formed by ss_resample's own
+ * sum (the history zero-padded past h_n_in[b]) and the row by ss_fbank_cmvn's code: the same bits as ss_resample over the h_n_in[b]
+ * samples followed by ss_fbank_cmvn.  A session with up == down is already at 16 kHz (its taps may be NULL): its rows are
+ * ss_batch_fbank_frames' bits.  h_n[b] = 0 skips a session (nothing else of it is read).  1 <= B <= 65535.  SS_ERR_ARG, decided for the
+ * whole call before the launch (no row is written): B outside that range, a negative first or count, a ratio ss_fbank_sr_rows refuses
+ * (up or down below 1, a negative half_len or n_in, taps that do not fit the workgroup's LDS), a row at or past the rows h_n_in[b]
+ * samples resample to, a NULL history / output / tap table of a session with rows. */
+int ss_batch_fbank_frames_sr(ss_model* m, void* stream, int B, const float* const* h_pcm, const int32_t* h_n_in, const int32_t* h_up,
+                             const int32_t* h_down, const float* const* h_taps, const int32_t* h_half_len, const int32_t* h_first,
+                             const int32_t* h_n, float pcm_scale, float* const* h_feat);
+/* Host only: the rows ss_batch_fbank_frames_sr can make of n_in source samples, *h_n_rows = 1 + (n16 - 400) / 160 with n16 =
+ * ceil(n_in * up / down) (0 below 400), and how many of them are FINAL, *h_n_final: the largest F with
+ * ((160 (F - 1) + 399) * down + half_len) / up <= n_in - 1 (integer division) -- the FIR window of the row's last sample lies inside
+ * the history, so no later call with more audio changes the row.  Rows from F on still see the zero padding and are recomputed.
+ * Either pointer may be NULL.  SS_ERR_ARG for what the entry point refuses about a ratio, from the same code. */
+int ss_fbank_sr_rows(int64_t n_in, int up, int down, int half_len, int32_t* h_n_rows, int32_t* h_n_final);
 int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float* d_feats, int feat_rows,
                        const int32_t* h_n, int t2u_causal, int mask_eos, int32_t* d_raw, int32_t* d_tokens,
                        int32_t* d_counts);

@@ -1,6 +1,7 @@
 // Ragged-batch twins of the model stages (ss_batch_*): B independent utterances packed along the row axis, no padding anywhere,
 // pack-invariant arithmetic (ss_model_set_pack_invariant).  Reference: every stage of agent/speech_to_speech.streamspeech.agent.py
 // :425-717 run for B = 1 utterances at a time.
+#include <cstring>
 #include "model_internal.hpp"
 
 // =================================================================================================
@@ -667,4 +668,51 @@ extern "C" int ss_batch_fbank_frames(ss_model* m, void* stream, int B, const flo
   const float* const* d_pcm = reinterpret_cast<const float* const*>(dt + n_seg);
   float* const* d_feat = reinterpret_cast<float* const*>(dt + n_seg + 2 * (size_t)B);
   return launch_fbank_cmvn_ptrs(d_pcm, d_feat, pcm_scale, m->fe_window, m->fe_melw, m->fe_mean, m->fe_std, dt, B, mx, s);
+}
+
+// ss_batch_fbank_frames for sessions at ANY source rate, from the source-rate histories directly (fbank.hip, fbank_cmvn_sr_kernel):
+// session b's rows h_first[b] .. h_first[b] + h_n[b] - 1 of fbank(resample(h_pcm[b][0 .. h_n_in[b]))) go to h_feat[b], the bits of
+// ss_resample + ss_fbank_cmvn over that history.  Every refusal is made here, for the whole call, before the launch; the ratio's
+// come from fbank_sr_rows, the code ss_fbank_sr_rows exports.
+extern "C" int ss_batch_fbank_frames_sr(ss_model* m, void* stream, int B, const float* const* h_pcm, const int32_t* h_n_in,
+                                        const int32_t* h_up, const int32_t* h_down, const float* const* h_taps,
+                                        const int32_t* h_half_len, const int32_t* h_first, const int32_t* h_n, float pcm_scale,
+                                        float* const* h_feat) {
+  if (!m || B <= 0 || B > 65535 || !h_pcm || !h_n_in || !h_up || !h_down || !h_taps || !h_half_len || !h_first || !h_n || !h_feat)
+    return SS_ERR_ARG;                                                                           // (B is the grid's y extent)
+  static_assert(sizeof(FbankSrSeg) % sizeof(int) == 0, "the segment table is uploaded as ints");
+  constexpr size_t kSegInts = sizeof(FbankSrSeg) / sizeof(int);
+  std::vector<int> tab(kSegInts * (size_t)B, 0);
+  int mx = 0, max_taps = 0;
+  for (int b = 0; b < B; ++b) {
+    if (h_first[b] < 0 || h_n[b] < 0) return SS_ERR_ARG;
+    FbankSrSeg sg{};                                  // h_n[b] = 0: n_rows 0, every workgroup of the segment exits
+    if (h_n[b] > 0) {
+      int rows = 0;
+      RET(fbank_sr_rows(h_n_in[b], h_up[b], h_down[b], h_half_len[b], &rows, nullptr));
+      if ((int64_t)h_first[b] + (int64_t)h_n[b] > (int64_t)rows) return SS_ERR_ARG;              // a row past what n_in resamples to
+      const bool pass = h_up[b] == h_down[b];
+      if (!h_pcm[b] || !h_feat[b] || (!pass && !h_taps[b])) return SS_ERR_ARG;
+      sg.pcm = h_pcm[b]; sg.taps = h_taps[b]; sg.feat = h_feat[b];
+      sg.n_in = h_n_in[b]; sg.up = h_up[b]; sg.down = h_down[b]; sg.half = h_half_len[b]; sg.first = h_first[b]; sg.n_rows = h_n[b];
+      mx = std::max(mx, h_n[b]);
+      if (!pass) max_taps = std::max(max_taps, 2 * h_half_len[b] + 1);
+    }
+    std::memcpy(tab.data() + kSegInts * (size_t)b, &sg, sizeof(sg));
+  }
+  if (mx == 0) return SS_OK;
+  hipStream_t s = (hipStream_t)stream;
+  RET(m->sc->seg_buf.ensure(tab.size() * sizeof(int)));
+  int* dt = (int*)m->sc->seg_buf.p;
+  RET(upload(s, dt, tab));
+  return launch_fbank_cmvn_sr(reinterpret_cast<const FbankSrSeg*>(dt), B, mx, max_taps, pcm_scale, m->fe_window, m->fe_melw,
+                              m->fe_mean, m->fe_std, s);
+}
+
+extern "C" int ss_fbank_sr_rows(int64_t n_in, int up, int down, int half_len, int32_t* h_n_rows, int32_t* h_n_final) {
+  int rows = 0, fin = 0;
+  RET(fbank_sr_rows(n_in, up, down, half_len, &rows, &fin));
+  if (h_n_rows) *h_n_rows = rows;
+  if (h_n_final) *h_n_final = fin;
+  return SS_OK;
 }

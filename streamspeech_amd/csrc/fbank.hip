@@ -11,30 +11,22 @@ namespace ss {
 
 constexpr int WIN = 400, SHIFT = 160, NFFT = 512, NBIN = 257, NMEL = 80;
 
-__global__ __launch_bounds__(256) void fbank_cmvn_kernel(const float* __restrict__ pcm, float pcm_scale,
-                                                         const float* __restrict__ window,   // [400]
-                                                         const float* __restrict__ melw,     // [80][257]
-                                                         const float* __restrict__ cmvn_mean,
-                                                         const float* __restrict__ cmvn_std, float* feat,
-                                                         const int* __restrict__ segs,
-                                                         const float* const* __restrict__ pcm_ptrs,
-                                                         float* const* __restrict__ feat_ptrs) {
+// One fbank row from the frame's 400 samples, two per thread: v0 = sample t, v1 = sample t + 256 (ignored from t = 144 on), both
+// unscaled.  Shared by fbank_cmvn_kernel (samples loaded) and fbank_cmvn_sr_kernel (samples formed by the resampling prologue), so
+// the row is ONE piece of code: the scale multiplies where it always did (hipcc contracts x0 + x1 into an fma with it), and both
+// kernels get the same contraction of every expression below -- the row's bits depend on the two sample values only.
+__device__ __forceinline__ void fbank_row(const float v0, const float v1, const float pcm_scale,
+                                          const float* __restrict__ window,   // [400]
+                                          const float* __restrict__ melw,     // [80][257]
+                                          const float* __restrict__ cmvn_mean, const float* __restrict__ cmvn_std,
+                                          float* __restrict__ feat_row) {
   __shared__ float re[NFFT], im[NFFT];
   __shared__ float tw_c[NFFT / 2], tw_s[NFFT / 2];
   __shared__ float red[4];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int frame = blockIdx.x;
-  if (segs) {   // ragged batch {pcm_start, n_frames, frame_start}; whole workgroup exits together
-    const int* sg = segs + 3 * blockIdx.y;
-    if (frame >= sg[1]) return;
-    if (pcm_ptrs) { pcm = pcm_ptrs[blockIdx.y]; feat = feat_ptrs[blockIdx.y]; }   // per-segment buffers (launch_fbank_cmvn_ptrs)
-    pcm += sg[0]; feat += (size_t)sg[2] * NMEL;
-  }
-  const float* src = pcm + (size_t)frame * SHIFT;
-
-  // load (coalesced) and frame mean
-  const float x0 = src[t] * pcm_scale;
-  const float x1 = (t + 256 < WIN) ? src[t + 256] * pcm_scale : 0.f;
+  // frame mean
+  const float x0 = v0 * pcm_scale;
+  const float x1 = (t + 256 < WIN) ? v1 * pcm_scale : 0.f;
   float s = wave_sum(x0 + x1);
   if (lane == 0) red[wave] = s;
   // twiddles e^{-2 pi i k / 512}
@@ -88,8 +80,29 @@ __global__ __launch_bounds__(256) void fbank_cmvn_kernel(const float* __restrict
     float e = 0.f;
     for (int i = 0; i < NBIN; ++i) e = fmaf(w[i], re[i], e);
     const float lg = logf(fmaxf(e, 1.1920928955078125e-07f));
-    feat[(size_t)frame * NMEL + t] = (lg - cmvn_mean[t]) / cmvn_std[t];
+    feat_row[t] = (lg - cmvn_mean[t]) / cmvn_std[t];
   }
+}
+
+__global__ __launch_bounds__(256) void fbank_cmvn_kernel(const float* __restrict__ pcm, float pcm_scale,
+                                                         const float* __restrict__ window,   // [400]
+                                                         const float* __restrict__ melw,     // [80][257]
+                                                         const float* __restrict__ cmvn_mean,
+                                                         const float* __restrict__ cmvn_std, float* feat,
+                                                         const int* __restrict__ segs,
+                                                         const float* const* __restrict__ pcm_ptrs,
+                                                         float* const* __restrict__ feat_ptrs) {
+  const int t = threadIdx.x;
+  const int frame = blockIdx.x;
+  if (segs) {   // ragged batch {pcm_start, n_frames, frame_start}; whole workgroup exits together
+    const int* sg = segs + 3 * blockIdx.y;
+    if (frame >= sg[1]) return;
+    if (pcm_ptrs) { pcm = pcm_ptrs[blockIdx.y]; feat = feat_ptrs[blockIdx.y]; }   // per-segment buffers (launch_fbank_cmvn_ptrs)
+    pcm += sg[0]; feat += (size_t)sg[2] * NMEL;
+  }
+  const float* src = pcm + (size_t)frame * SHIFT;
+  // load (coalesced)
+  fbank_row(src[t], (t + 256 < WIN) ? src[t + 256] : 0.f, pcm_scale, window, melw, cmvn_mean, cmvn_std, feat + (size_t)frame * NMEL);
 }
 
 int launch_fbank_cmvn(const float* pcm, int n_samples, float pcm_scale, const float* window,
@@ -132,6 +145,21 @@ int launch_fbank_cmvn_ptrs(const float* const* pcm_ptrs, float* const* feat_ptrs
 // `up`) are ~60/output sample for 3:1: a thread per output sample, taps through LDS when they fit.
 // HBM-bound by construction: 4*(n_in + n_out) bytes.
 // ---------------------------------------------------------------------------------------------
+// Output sample k of the resampler from the input history x[0 .. n_in) and the taps hs (LDS): the input window clamped at both
+// ends of the history (zero padding), taps in ascending m, one fmaf each.  The ONE copy of this sum: resample_kernel and the
+// resampling prologue of fbank_cmvn_sr_kernel give the same bits for the same (x, n_in, k).
+__device__ __forceinline__ float resample_sample(const float* __restrict__ x, long long n_in, int up, int down,
+                                                 const float* hs, int half, long long k) {
+  const long long c = k * down;
+  long long m_lo = c - half;                          // ceil((c - half) / up), clamped at 0
+  m_lo = m_lo <= 0 ? 0 : (m_lo + up - 1) / up;
+  long long m_hi = (c + half) / up;
+  if (m_hi > n_in - 1) m_hi = n_in - 1;
+  float acc = 0.f;
+  for (long long m = m_lo; m <= m_hi; ++m) acc = fmaf(x[m], hs[half + (int)(c - m * up)], acc);
+  return acc;
+}
+
 __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, long long n_in, int up, int down,
                                                        const float* __restrict__ h, int half, float* __restrict__ y,
                                                        long long n_out) {
@@ -141,14 +169,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
   __syncthreads();
   const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
   if (k >= n_out) return;
-  const long long c = k * down;
-  long long m_lo = c - half;                          // ceil((c - half) / up), clamped at 0
-  m_lo = m_lo <= 0 ? 0 : (m_lo + up - 1) / up;
-  long long m_hi = (c + half) / up;
-  if (m_hi > n_in - 1) m_hi = n_in - 1;
-  float acc = 0.f;
-  for (long long m = m_lo; m <= m_hi; ++m) acc = fmaf(x[m], hs[half + (int)(c - m * up)], acc);
-  y[k] = acc;
+  y[k] = resample_sample(x, n_in, up, down, hs, half, k);
 }
 
 int launch_resample(const float* x, long long n_in, int up, int down, const float* taps, int half_len, float* y,
@@ -159,6 +180,71 @@ int launch_resample(const float* x, long long n_in, int up, int down, const floa
   if (lds > 64 * 1024) return SS_ERR_ARG;             // 16 K taps: ratios up to ~800:1 in lowest terms
   hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), lds, stream, x, n_in, up, down,
                      taps, half_len, y, n_out);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// fbank rows of streaming sessions at ANY source rate, from the source-rate history directly: workgroup = one row of one session
+// (the grid and ragged exit of launch_fbank_cmvn_ptrs).  Each thread forms its one or two 16-kHz samples 160 f + t (+ 256) of the
+// row with resample_sample -- the resampler's own sum, so they are the samples ss_resample would have written -- keeps them in
+// registers and the row goes through fbank_row: the bits of fbank_cmvn(resample(x[:n_in])) without the 16-kHz history in between.
+// The session's taps sit in LDS beside fbank_row's arrays (a table per segment: the sessions of a launch may differ in ratio).
+// A segment with up == down is already at 16 kHz: its samples are loaded, as fbank_cmvn_kernel loads them.
+// ---------------------------------------------------------------------------------------------
+constexpr size_t FBANK_ROW_LDS = (2 * NFFT + 2 * (NFFT / 2) + 4) * sizeof(float);   // fbank_row's static arrays
+constexpr size_t WG_LDS = 64 * 1024;                                                // what a workgroup gets without asking for more
+constexpr int FBANK_SR_MAX_HALF = (int)(((WG_LDS - FBANK_ROW_LDS) / sizeof(float) - 1) / 2);   // 2 half + 1 taps beside the row's arrays
+
+__global__ __launch_bounds__(256) void fbank_cmvn_sr_kernel(const FbankSrSeg* __restrict__ segs, float pcm_scale,
+                                                            const float* __restrict__ window, const float* __restrict__ melw,
+                                                            const float* __restrict__ cmvn_mean,
+                                                            const float* __restrict__ cmvn_std) {
+  extern __shared__ float hs[];
+  const FbankSrSeg sg = segs[blockIdx.y];
+  if ((int)blockIdx.x >= sg.n_rows) return;           // ragged batch: the whole workgroup exits together
+  const int t = threadIdx.x;
+  const long long k0 = (long long)(sg.first + (int)blockIdx.x) * SHIFT + t;
+  float v0, v1 = 0.f;
+  if (sg.up == sg.down) {
+    v0 = sg.pcm[k0];
+    if (t + 256 < WIN) v1 = sg.pcm[k0 + 256];
+  } else {
+    const int ntaps = 2 * sg.half + 1;
+    for (int i = t; i < ntaps; i += 256) hs[i] = sg.taps[i];
+    __syncthreads();
+    v0 = resample_sample(sg.pcm, sg.n_in, sg.up, sg.down, hs, sg.half, k0);
+    if (t + 256 < WIN) v1 = resample_sample(sg.pcm, sg.n_in, sg.up, sg.down, hs, sg.half, k0 + 256);
+  }
+  fbank_row(v0, v1, pcm_scale, window, melw, cmvn_mean, cmvn_std, sg.feat + (size_t)blockIdx.x * NMEL);
+}
+
+int fbank_sr_rows(long long n_in, int up, int down, int half_len, int* n_rows, int* n_final) {
+  if (n_in < 0 || up < 1 || down < 1 || half_len < 0) return SS_ERR_ARG;
+  if (half_len > FBANK_SR_MAX_HALF) return SS_ERR_ARG;                                             // the taps do not fit the workgroup's LDS
+  if (n_in > (long long)0x7fffffff || n_in * up > (long long)0x7fffffff * down) return SS_ERR_ARG;   // 16-kHz sample indices are ints
+  const long long n16 = (n_in * up + down - 1) / down;
+  const long long rows = n16 < WIN ? 0 : 1 + (n16 - WIN) / SHIFT;
+  // sample K is settled iff its window's last input (K down + half) / up exists: K down + half < n_in up
+  const long long top = n_in * up - 1 - half_len;
+  long long fin = 0;
+  if (top >= 0) {
+    const long long kmax = top / down;                // the last settled sample
+    if (kmax >= WIN - 1) fin = 1 + (kmax - (WIN - 1)) / SHIFT;
+  }
+  if (fin > rows) fin = rows;
+  if (n_rows) *n_rows = (int)rows;
+  if (n_final) *n_final = (int)fin;
+  return SS_OK;
+}
+
+int launch_fbank_cmvn_sr(const FbankSrSeg* segs, int nseg, int max_rows, int max_taps, float pcm_scale, const float* window,
+                         const float* melw, const float* cmvn_mean, const float* cmvn_std, hipStream_t stream) {
+  if (nseg <= 0 || max_rows <= 0) return SS_OK;
+  if (max_taps < 0 || max_taps > 2 * FBANK_SR_MAX_HALF + 1) return SS_ERR_ARG;
+  const size_t lds = (size_t)max_taps * sizeof(float);
+  hipLaunchKernelGGL(fbank_cmvn_sr_kernel, dim3(max_rows, nseg), dim3(256), lds, stream, segs, pcm_scale, window, melw, cmvn_mean,
+                     cmvn_std);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }

@@ -28,4 +28,27 @@ int launch_fbank_cmvn_ptrs(const float* const* pcm_ptrs, float* const* feat_ptrs
 int launch_resample(const float* x, long long n_in, int up, int down, const float* taps, int half_len, float* y,
                     long long n_out, hipStream_t stream);
 
+// One session of launch_fbank_cmvn_sr (a device table of these): rows first .. first + n_rows - 1 of the fbank of the source-rate
+// history pcm[0 .. n_in) resampled by up / down (lowest terms; taps [2 * half + 1] on the device, unused when up == down), to feat
+// (n_rows rows of 80).
+struct FbankSrSeg {
+  const float* pcm;
+  const float* taps;
+  float* feat;
+  int n_in, up, down, half, first, n_rows;
+};
+
+// Host only: the fbank rows n_in source samples resample to -- n16 = ceil(n_in * up / down), 1 + (n16 - 400) / 160 -- and how many
+// of them are FINAL: the largest F whose last sample 160 (F - 1) + 399 has its whole FIR window inside the history,
+// ((160 (F - 1) + 399) * down + half_len) / up <= n_in - 1 (the kernel's m_hi before its clamp).  Later rows still see the zero
+// padding and change when more audio arrives.  SS_ERR_ARG: up or down below 1, a negative half_len or n_in, taps that do not fit
+// the workgroup's LDS beside the row's arrays, a history past the int range of 16-kHz sample indices.
+int fbank_sr_rows(long long n_in, int up, int down, int half_len, int* n_rows, int* n_final);
+
+// Ragged batch of sessions at their own rates (fbank.hip, fbank_cmvn_sr_kernel): segs [nseg] on the device, max_rows the largest
+// n_rows, max_taps the largest 2 * half + 1 of the segments that resample (0: none does).  Every segment must have passed
+// fbank_sr_rows and ask for rows below its n_rows: the kernel reads pcm[0 .. n_in) and nothing else.
+int launch_fbank_cmvn_sr(const FbankSrSeg* segs, int nseg, int max_rows, int max_taps, float pcm_scale, const float* window,
+                         const float* melw, const float* cmvn_mean, const float* cmvn_std, hipStream_t stream);
+
 }  // namespace ss

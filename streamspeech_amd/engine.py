@@ -42,6 +42,28 @@ def _i32(vals):
     return (C.c_int32 * len(vals))(*[int(v) for v in vals])
 
 
+def resample_ratio(sr_in: int, sr_out: int = 16000) -> Tuple[int, int, int]:
+    """(up, down, half_len) of the resampler from sr_in to sr_out: the ratio in lowest terms and the taps on either side of the
+    centre of frontend.design_filter's low-pass (0 when nothing is resampled)."""
+    import math
+    from .frontend import filter_half_len
+    g = math.gcd(int(sr_in), int(sr_out))
+    up, down = int(sr_out) // g, int(sr_in) // g
+    return up, down, (0 if up == down else filter_half_len(up, down))
+
+
+def fbank_sr_rows(n_in: int, up: int, down: int, half_len: int, lib=None) -> Optional[Tuple[int, int]]:
+    """The library's own count (ss_fbank_sr_rows, host only): (fbank rows n_in source samples resample to, how many of them are final
+    -- no later sample changes them); None for a ratio ss_batch_fbank_frames_sr refuses."""
+    lib = lib or L.load()
+    rows, fin = C.c_int32(0), C.c_int32(0)
+    rc = lib.ss_fbank_sr_rows(int(n_in), int(up), int(down), int(half_len), C.byref(rows), C.byref(fin))
+    if rc == L.SS_ERR_ARG:
+        return None
+    L.check(rc, "ss_fbank_sr_rows")
+    return rows.value, fin.value
+
+
 MT_BEAM_MAX_ROWS = 256     # B * beam hypothesis rows of one ss_batch_mt_beam call
 MT_BEAM_MAX = 32
 
@@ -140,6 +162,31 @@ class BatchMixin:
         fp = (C.c_void_p * B)(*[o.data_ptr() if n else 0 for o, n in zip(outs, counts)])
         L.check(self.lib.ss_batch_fbank_frames(self.h, _stream(), B, pp, _i32(first), _i32(counts), pcm_scale, fp),
                 "ss_batch_fbank_frames")
+
+    def batch_fbank_frames_sr(self, histories: List[torch.Tensor], n_in: List[int], rates: List[int], first: List[int],
+                              counts: List[int], outs: List[torch.Tensor], pcm_scale: float = 32768.0):
+        """batch_fbank_frames for streams at any source rate, each at its own, in one launch (ss_batch_fbank_frames_sr): rows
+        first[i] .. first[i] + counts[i] - 1 of fbank_cmvn(resample(histories[i][:n_in[i]], rates[i])) into outs[i] ([counts[i], 80]
+        contiguous, device), computed from the source-rate history.  A 16-kHz stream passes through (batch_fbank_frames' bits)."""
+        B = len(histories)
+        if not (len(n_in) == len(rates) == len(first) == len(counts) == len(outs) == B) or B == 0:
+            raise ValueError("one history, sample count, rate, first frame, count and output per session")
+        up, down, half, taps = [], [], [], []
+        for h, n, sr, c, o in zip(histories, n_in, rates, counts, outs):
+            if c and (h.numel() < int(n) or tuple(o.shape) != (int(c), 80) or not o.is_contiguous()):
+                raise ValueError("history shorter than the samples named, or a wrong output view")
+            u, d, hl = resample_ratio(sr)
+            t = self._taps(u, d) if c and u != d else None
+            up.append(u); down.append(d); half.append(hl); taps.append(t)
+        pp = (C.c_void_p * B)(*[h.data_ptr() for h in histories])
+        tp = (C.c_void_p * B)(*[t.data_ptr() if t is not None else 0 for t in taps])
+        fp = (C.c_void_p * B)(*[o.data_ptr() if n else 0 for o, n in zip(outs, counts)])
+        L.check(self.lib.ss_batch_fbank_frames_sr(self.h, _stream(), B, pp, _i32(n_in), _i32(up), _i32(down), tp, _i32(half),
+                                                  _i32(first), _i32(counts), pcm_scale, fp), "ss_batch_fbank_frames_sr")
+
+    def fbank_sr_rows(self, n_in: int, sr_in: int) -> Optional[Tuple[int, int]]:
+        """(fbank rows, final fbank rows) of n_in samples at sr_in Hz (fbank_sr_rows); None for a rate batch_fbank_frames_sr refuses."""
+        return fbank_sr_rows(n_in, *resample_ratio(sr_in), lib=self.lib)
 
     def batch_mt_beam(self, enc_packed: torch.Tensor, Tp: List[int], max_len: List[int], beam: int, min_len: int = 1,
                       unk_penalty: float = 0.0, normalize: bool = True):
@@ -396,19 +443,20 @@ class HipModel(BatchMixin):
             pass
 
     # ---- waveform front-end (§8f-3) --------------------------------------------------------
+    def _taps(self, up: int, down: int) -> torch.Tensor:
+        """design_filter(up, down) on the device, float32, made once per ratio."""
+        from .frontend import design_filter
+        cache = self.__dict__.setdefault("_resample_taps", {})
+        if (up, down) not in cache:
+            cache[(up, down)] = torch.from_numpy(design_filter(up, down).astype(np.float32)).to(self.device)
+        return cache[(up, down)]
+
     def resample(self, pcm: torch.Tensor, sr_in: int, sr_out: int = 16000) -> torch.Tensor:
         """float32 [n] on the device at sr_in -> [ceil(n*sr_out/sr_in)] at sr_out (polyphase FIR kernel)."""
-        import math
-        from .frontend import design_filter
-        g = math.gcd(int(sr_in), int(sr_out))
-        up, down = int(sr_out) // g, int(sr_in) // g
+        up, down, _ = resample_ratio(sr_in, sr_out)
         if up == down:
             return pcm
-        key = (up, down)
-        cache = self.__dict__.setdefault("_resample_taps", {})
-        if key not in cache:
-            cache[key] = torch.from_numpy(design_filter(up, down).astype(np.float32)).to(self.device)
-        taps = cache[key]
+        taps = self._taps(up, down)
         n_in = pcm.numel()
         n_out = -(-n_in * up // down)
         out = torch.empty((n_out,), dtype=torch.float32, device=self.device)

@@ -5,14 +5,22 @@ The reference resamples the whole 48 kHz sample history to 16 kHz with sox ("rat
 torchaudio.sox_effects, fairseq/data/audio/audio_utils.py:53-62) -- third-party arithmetic outside
 the parity contract (BASELINE.json: "on the same fbank input").  Here a zero-phase
 polyphase FIR with the published design of scipy.signal.resample_poly runs on the device
-(ss_resample, csrc/fbank.hip) when the source is not already 16 kHz.
+(ss_resample, csrc/fbank.hip) when the source is not already 16 kHz.  The streaming extractor does not resample the history it
+has already seen: fbank rows whose samples can no longer change are kept, and the others are made from the source-rate history
+with the resampler's sum inside the fbank kernel (ss_batch_fbank_frames_sr; OnlineFeatureExtractor.__call__).
 """
 import array
 import math
 import wave
+from typing import Optional
 
 import numpy as np
 import torch
+
+
+def filter_half_len(up: int, down: int) -> int:
+    """Taps on either side of design_filter's centre tap."""
+    return 10 * max(up, down)
 
 
 def design_filter(up: int, down: int) -> np.ndarray:
@@ -20,7 +28,7 @@ def design_filter(up: int, down: int) -> np.ndarray:
     1/max(up,down) of Nyquist, Kaiser beta 5, unit DC gain, times `up` (the design
     scipy.signal.resample_poly documents; `up`/`down` in lowest terms)."""
     max_rate = max(up, down)
-    half_len = 10 * max_rate
+    half_len = filter_half_len(up, down)
     n = np.arange(2 * half_len + 1, dtype=np.float64) - half_len
     fc = 1.0 / max_rate
     h = fc * np.sinc(fc * n) * np.kaiser(2 * half_len + 1, 5.0)
@@ -126,8 +134,8 @@ class OnlineFeatureExtractor:
         self._buf = np.zeros(0, np.float32)      # backing store of _np (grows by doubling: appending a segment does not copy the history)
         self._dev = None
         self._n_dev = 0
-        self._fb = None                          # fbank rows of the cached history (16-kHz sources on the HIP engine; see __call__)
-        self._n_fb = 0
+        self._fb = None                          # fbank rows of the cached history (HIP engine; see __call__)
+        self._n_fb = 0                           # how many of them are final
         self._src_id = None
 
     def _samples(self, samples, n):
@@ -195,8 +203,8 @@ class OnlineFeatureExtractor:
         return int(num_frames), effective
 
     def new_rows(self, nf: int) -> int:
-        """16-kHz sources on the HIP engine: the first of the `nf` fbank rows that is not cached yet (the row buffer grows to hold
-        all `nf`).  The caller computes rows first .. nf - 1 into self._fb and then calls commit_rows(nf)."""
+        """The HIP engine: the first of the `nf` fbank rows that is not cached as final yet (the row buffer grows to hold all `nf`).
+        The caller computes rows first .. nf - 1 into self._fb and then calls commit_rows(nf)."""
         k = self._n_fb if self._fb is not None else 0
         if k > nf:
             k = 0
@@ -207,9 +215,19 @@ class OnlineFeatureExtractor:
             self._fb = fb
         return k
 
-    def commit_rows(self, nf: int) -> torch.Tensor:
-        self._n_fb = nf
+    def commit_rows(self, nf: int, final: Optional[int] = None) -> torch.Tensor:
+        """The `nf` rows of this call; `final` of them (all, for a 16-kHz source) stay as they are from now on."""
+        self._n_fb = nf if final is None else final
         return self._fb[:nf]
+
+    def sr_rows(self, effective: int, sr: int):
+        """A source at another rate than 16 kHz on the HIP engine: (fbank rows `effective` samples resample to, how many of them are
+        final), as the library counts them (ss_fbank_sr_rows) -- the rows from new_rows() on are then computed from the source-rate
+        history in one launch (HipModel.batch_fbank_frames_sr) and committed with the final count.  None: the engine has no such call
+        (the CPU oracle engine) or refuses the ratio (taps too large for a workgroup), and the whole history is resampled as before."""
+        if not hasattr(self.engine, "batch_fbank_frames_sr"):
+            return None
+        return self.engine.fbank_sr_rows(effective, int(sr))
 
     def __call__(self, new_samples, sr=None):
         sr = sr or self.sample_rate
@@ -219,8 +237,20 @@ class OnlineFeatureExtractor:
         num_frames, effective = st
         pcm = self._dev[:effective]
         if sr != SAMPLE_RATE:
-            pcm = self.engine.resample(pcm, int(sr), SAMPLE_RATE)
-            return self.engine.fbank_cmvn(pcm, 32768.0)
+            plan = self.sr_rows(effective, sr)
+            if plan is None:
+                pcm = self.engine.resample(pcm, int(sr), SAMPLE_RATE)
+                return self.engine.fbank_cmvn(pcm, 32768.0)
+            # The 16-kHz branch's scheme on the source-rate history: a row whose last sample's FIR window lies inside the audio received
+            # so far never changes again (same taps, same order, same 400 samples), so rows final at the previous call come from the
+            # cache and the rest -- the new rows and the one that still saw the zero padding -- are computed from self._dev directly.
+            rows, final = plan
+            if rows == 0:
+                return torch.empty((0, self.feature_dim), device=self.engine.device)
+            k = self.new_rows(rows)
+            if rows > k:
+                self.engine.batch_fbank_frames_sr([self._dev], [effective], [int(sr)], [k], [rows - k], [self._fb[k:rows]], 32768.0)
+            return self.commit_rows(rows, final)
         if not hasattr(self.engine, "lib"):              # the CPU oracle engine: as the reference, everything every time
             return self.engine.fbank_cmvn(pcm, 32768.0)
         # A fbank row is a function of ITS 400 samples only (one workgroup per 25-ms frame, global CMVN): rows of the cached history stay

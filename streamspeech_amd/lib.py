@@ -108,6 +108,10 @@ SIGNATURES = {
                                             C.POINTER(C.c_int32), _i64, C.POINTER(_i64)]),
     "ss_batch_fbank_frames": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f,
                                    C.POINTER(_vp)]),
+    "ss_batch_fbank_frames_sr": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                      C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f,
+                                      C.POINTER(_vp)]),
+    "ss_fbank_sr_rows": (_i, [_i64, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ss_batch_t2u_units": (_i, [_vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp]),
     "ss_batch_vocoder_forward": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _vp, _vp, _i64, _vp,
                                       C.POINTER(_i64), C.POINTER(_i64)]),

@@ -2,7 +2,8 @@
 (agent/speech_to_text.asr.streamspeech.agent.py, agent/speech_to_text.s2tt.streamspeech.agent.py; agent_text.py here) served many
 at a time.  Per session, one :meth:`TextSessionPool.step` is exactly one ``agent.pushpop(segment)`` of the matching single-session
 agent; across sessions a step is
-  * ONE fbank launch for the new frames of every 16-kHz session (ss_batch_fbank_frames; other rates resample per session),
+  * ONE fbank launch for the new frames of every session, whatever its source rate (ss_batch_fbank_frames when all are at 16 kHz,
+    else ss_batch_fbank_frames_sr, which resamples inside the row's workgroup from the source-rate history),
   * ONE batched encoder step and both CTC heads (StreamPool.forward / ctc_both; ASR sessions read head 0),
   * the read/write gate of each session on the host (text_policy.s2tt_gate),
   * ONE ragged greedy continuation of the committed prefix of every writing S2TT session (HipModel.batch_mt_continue).
@@ -189,8 +190,8 @@ class TextSessionPool:
         out: Dict[int, object] = {}
         actions: Dict[int, tuple] = {}
         t0 = time.perf_counter()
-        # ---- front-end: finished agents answer at once; 16-kHz sessions' new rows in one launch ----
-        feats, batch = {}, []
+        # ---- front-end: finished agents answer at once; the new rows of every other session in one launch ----
+        feats, batch, fe_calls, fe_rows = {}, [], 0, 0
         for s in todo:
             s.pending = False
             if s.states.target_finished:
@@ -201,20 +202,33 @@ class TextSessionPool:
                 actions[s.sid] = ("write", "", True) if s.states.source_finished else ("read",)
                 continue
             nf, eff = st
+            final = nf                            # 16 kHz: every row is final
             if s.sr != SAMPLE_RATE:
-                fb = self.model.fbank_cmvn(self.model.resample(s.fe._dev[:eff], s.sr, SAMPLE_RATE), 32768.0)
-                if fb.shape[0] == 0:              # too short after resampling: the agent's early return, as above
+                plan = s.fe.sr_rows(eff, s.sr)    # rows after resampling and how many are final, as the library counts them
+                if plan is None:                  # a ratio the batched call refuses (taps too large): this session resamples its history
+                    fb = self.model.fbank_cmvn(self.model.resample(s.fe._dev[:eff], s.sr, SAMPLE_RATE), 32768.0)
+                    fe_calls, fe_rows = fe_calls + 2, fe_rows + fb.shape[0]
+                    nf = fb.shape[0]
+                    if nf:
+                        feats[s.sid] = fb
+                else:
+                    nf, final = plan
+                if nf == 0:                       # too short after resampling: the agent's early return, as above
                     actions[s.sid] = ("write", "", True) if s.states.source_finished else ("read",)
+                if nf == 0 or plan is None:
                     continue
-                feats[s.sid] = fb
-            else:
-                k = s.fe.new_rows(nf)
-                batch.append((s, k, nf))
+            batch.append((s, s.fe.new_rows(nf), nf, final, eff))
         if batch:
-            self.model.batch_fbank_frames([s.fe._dev for s, _, _ in batch], [k for _, k, _ in batch], [nf - k for _, k, nf in batch],
-                                          [s.fe._fb[k:nf] for s, k, nf in batch])
-            for s, k, nf in batch:
-                feats[s.sid] = s.fe.commit_rows(nf)
+            hist, first = [s.fe._dev for s, _, _, _, _ in batch], [k for _, k, _, _, _ in batch]
+            cnt, outs = [nf - k for _, k, nf, _, _ in batch], [s.fe._fb[k:nf] for s, k, nf, _, _ in batch]
+            if all(s.sr == SAMPLE_RATE for s, _, _, _, _ in batch):
+                self.model.batch_fbank_frames(hist, first, cnt, outs)
+            else:                                 # 16-kHz sessions of a mixed step pass through: the same bits
+                self.model.batch_fbank_frames_sr(hist, [eff for _, _, _, _, eff in batch], [s.sr for s, _, _, _, _ in batch], first,
+                                                 cnt, outs)
+            fe_calls, fe_rows = fe_calls + 1, fe_rows + sum(cnt)
+            for s, k, nf, final, _ in batch:
+                feats[s.sid] = s.fe.commit_rows(nf, final)
         t1 = time.perf_counter()
         # ---- one encoder step + both CTC heads ----
         enc = [s for s in todo if s.sid in feats]
@@ -285,6 +299,7 @@ class TextSessionPool:
             if s.states.target_finished:          # finished without the agent's reset(): it answers EmptySegment(finished=True)
                 self._release(s)                  # from now on, so its slot goes back; reset(sid) starts a fresh utterance
         self.last_step = {"sessions": len(todo), "encoded": len(enc), "writers": len(writers), "mt_steps": n_steps, "mt_groups": mt_groups,
+                          "frontend_calls": fe_calls, "fbank_rows": fe_rows,       # front-end device calls of the step, rows they computed
                           "frontend_s": t1 - t0, "encoder_ctc_s": t2 - t1, "mt_s": t3 - t2, "total_s": time.perf_counter() - t0}
         self.last_step.update(self._side_times)
         self._side_times = {}
