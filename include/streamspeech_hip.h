@@ -617,6 +617,39 @@ int ss_op_layernorm(void* stream, const float* dx, int ldx, float* dy, int ldy, 
 int ss_op_attention(void* stream, const float* dQ, int ldq, const float* dK, int ldk, const float* dV,
                     int ldv, float* dO, int ldo, int Tq, int Tk, int H, float scale, int causal,
                     int chunk, const float* dP, int ldp, const float* du, const float* dv);
+/* Every form of the attention launcher (csrc/attention.hpp): the fields mirror AttnArgs one to one (all pointers DEVICE pointers),
+ * the call fills an AttnArgs and returns what launch_attention returns, SS_ERR_ARG included.  use_split != 0 binds the process-wide
+ * key-split scratch ss_op_attention binds when dP is set; 0 leaves it unbound (the launcher then never splits keys across
+ * workgroups).  tests/test_attention_gpu.py runs every kernel of attention.hip through it. */
+typedef struct ss_op_attn_args {
+  const float* Q; const float* K; const float* V; float* O;
+  int32_t ldq, ldk, ldv, ldo;
+  int32_t Tq, Tk, H;
+  float scale;
+  int32_t causal, chunk, q0, k_mask_tail;
+  const float* P; int32_t ldp;
+  const float* bias_u; const float* bias_v;
+  const int32_t* segs; int32_t nseg, max_q, p_tmax;
+  const int32_t* seg_tail;
+  int32_t no_decode_kernel;
+  const int32_t* anc; int32_t anc_ld, anc_slots;
+  int32_t use_split;
+} ss_op_attn_args;
+int ss_op_attention_ex(void* stream, const ss_op_attn_args* a);
+/* The tail-query attention of the concurrent streaming step (PoolAttnArgs, csrc/attention.hpp), field for field; returns what
+ * launch_attention_pool returns. */
+typedef struct ss_op_pool_attn_args {
+  const float* Qs; float* cache; float* O;
+  int32_t ld, ldo, slot_rows;
+  const float* P; int32_t ldp, p_tmax;
+  const float* bias_u; const float* bias_v;
+  const int32_t* sess; const int32_t* qt_pre;
+  int32_t nsess, qtiles, H;
+  float scale;
+} ss_op_pool_attn_args;
+int ss_op_attention_pool(void* stream, const ss_op_pool_attn_args* a);
+/* Test hook: 1 routes every attention launch the MFMA kernels would take to the VALU kernel (attention_kernel), 0 = default. */
+int ss_debug_attention_no_mfma(int v);
 int ss_op_dwconv_bn_silu(void* stream, const float* dx, int ldx, float* dy, int ldy, const float* dwt,
                          int K, const float* mean, const float* var, const float* gamma,
                          const float* beta, float eps, int T, int C, int chunk);

@@ -47,7 +47,8 @@ struct AttnArgs {
   int no_decode_kernel = 0;
   // Ancestry indirection of the beam search (beam.hip; ragged decode form only, nullptr = plain addressing): key / value j of segment z
   // is row anc[z * anc_ld + k0 + j] * anc_ld + k0 + j of K / V, k0 = the segment's k_start -- slot anc[..] wrote its row of cache
-  // index k0 + j there and never overwrites it (k0 > 0: a row whose position 0 is shifted into the cache, beam.hip).  Slot ids are clamped to [0, anc_slots).  The key-tile and summation order are those of
+  // index k0 + j there and never overwrites it (k0 > 0: a row whose position 0 is shifted into the cache, beam.hip).  Slot ids are non-negative (beam.hip writes no other); an id of anc_slots or more reads
+  // the last slot (an unsigned min, which would send a negative id there as well).  The key-tile and summation order are those of
   // the plain form, so an identity table gives its bits.
   const int* anc = nullptr; int anc_ld = 0; int anc_slots = 0;
 };

@@ -129,6 +129,17 @@ extern "C" int ss_op_layernorm(void* stream, const float* dx, int ldx, float* dy
   return launch_layernorm(dx, ldx, dy, ldy, dg, db, M, D, eps, (hipStream_t)stream);
 }
 
+// test ops: one process-wide key-split scratch (callers are serial), counters zero before the first launch
+static int op_attn_bind_split(AttnArgs& a) {
+  static void* scratch = nullptr;
+  if (!scratch) {
+    SS_HIP_CHECK(hipMalloc(&scratch, attention_split_bytes()));
+    SS_HIP_CHECK(hipMemset(scratch, 0, attention_split_bytes()));
+  }
+  attention_bind_split(a, scratch);
+  return SS_OK;
+}
+
 extern "C" int ss_op_attention(void* stream, const float* dQ, int ldq, const float* dK, int ldk, const float* dV,
                                int ldv, float* dO, int ldo, int Tq, int Tk, int H, float scale, int causal, int chunk,
                                const float* dP, int ldp, const float* du, const float* dv) {
@@ -136,19 +147,42 @@ extern "C" int ss_op_attention(void* stream, const float* dQ, int ldq, const flo
   a.Q = dQ; a.ldq = ldq; a.K = dK; a.ldk = ldk; a.V = dV; a.ldv = ldv; a.O = dO; a.ldo = ldo;
   a.Tq = Tq; a.Tk = Tk; a.H = H; a.scale = scale; a.causal = causal; a.chunk = chunk;
   a.P = dP; a.ldp = ldp; a.bias_u = du; a.bias_v = dv;
-  if (dP) {                                               // test op: one process-wide key-split scratch (callers are serial)
-    static void* scratch = nullptr;
-    if (!scratch) {
-      SS_HIP_CHECK(hipMalloc(&scratch, attention_split_bytes()));
-      SS_HIP_CHECK(hipMemset(scratch, 0, attention_split_bytes()));
-    }
-    attention_bind_split(a, scratch);
-  }
+  if (dP) RET(op_attn_bind_split(a));
   return launch_attention(a, (hipStream_t)stream);
+}
+
+// every field of AttnArgs a caller can set, as the caller set it: what launch_attention answers is what the caller sees
+extern "C" int ss_op_attention_ex(void* stream, const ss_op_attn_args* x) {
+  if (!x) return SS_ERR_ARG;
+  AttnArgs a;
+  a.Q = x->Q; a.K = x->K; a.V = x->V; a.O = x->O;
+  a.ldq = x->ldq; a.ldk = x->ldk; a.ldv = x->ldv; a.ldo = x->ldo;
+  a.Tq = x->Tq; a.Tk = x->Tk; a.H = x->H; a.scale = x->scale;
+  a.causal = x->causal; a.chunk = x->chunk; a.q0 = x->q0; a.k_mask_tail = x->k_mask_tail;
+  a.P = x->P; a.ldp = x->ldp; a.bias_u = x->bias_u; a.bias_v = x->bias_v;
+  a.segs = x->segs; a.nseg = x->nseg; a.max_q = x->max_q; a.p_tmax = x->p_tmax;
+  a.seg_tail = x->seg_tail;
+  a.no_decode_kernel = x->no_decode_kernel;
+  a.anc = x->anc; a.anc_ld = x->anc_ld; a.anc_slots = x->anc_slots;
+  if (x->use_split) RET(op_attn_bind_split(a));
+  return launch_attention(a, (hipStream_t)stream);
+}
+
+extern "C" int ss_op_attention_pool(void* stream, const ss_op_pool_attn_args* x) {
+  if (!x) return SS_ERR_ARG;
+  PoolAttnArgs a;
+  a.Qs = x->Qs; a.cache = x->cache; a.O = x->O;
+  a.ld = x->ld; a.ldo = x->ldo; a.slot_rows = x->slot_rows;
+  a.P = x->P; a.ldp = x->ldp; a.p_tmax = x->p_tmax;
+  a.bias_u = x->bias_u; a.bias_v = x->bias_v;
+  a.sess = x->sess; a.qt_pre = x->qt_pre;
+  a.nsess = x->nsess; a.qtiles = x->qtiles; a.H = x->H; a.scale = x->scale;
+  return launch_attention_pool(a, (hipStream_t)stream);
 }
 
 extern "C" int ss_debug_attention_split(int v) { attention_debug_split(v); return SS_OK; }
 extern "C" int ss_debug_attention_q16(int v) { attention_debug_q16(v); return SS_OK; }
+extern "C" int ss_debug_attention_no_mfma(int v) { attention_debug_no_mfma(v); return SS_OK; }
 
 extern "C" int ss_op_dwconv_bn_silu(void* stream, const float* dx, int ldx, float* dy, int ldy, const float* dwt,
                                     int K, const float* mean, const float* var, const float* gamma,

@@ -29,6 +29,35 @@ class SSVocoderConfig(C.Structure):
 
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
+
+class SSOpAttnArgs(C.Structure):
+    """ss_op_attn_args: AttnArgs (csrc/attention.hpp) field for field, pointers as device addresses."""
+    _fields_ = [
+        ("Q", _vp), ("K", _vp), ("V", _vp), ("O", _vp),
+        ("ldq", C.c_int32), ("ldk", C.c_int32), ("ldv", C.c_int32), ("ldo", C.c_int32),
+        ("Tq", C.c_int32), ("Tk", C.c_int32), ("H", C.c_int32),
+        ("scale", _f),
+        ("causal", C.c_int32), ("chunk", C.c_int32), ("q0", C.c_int32), ("k_mask_tail", C.c_int32),
+        ("P", _vp), ("ldp", C.c_int32),
+        ("bias_u", _vp), ("bias_v", _vp),
+        ("segs", _vp), ("nseg", C.c_int32), ("max_q", C.c_int32), ("p_tmax", C.c_int32),
+        ("seg_tail", _vp),
+        ("no_decode_kernel", C.c_int32),
+        ("anc", _vp), ("anc_ld", C.c_int32), ("anc_slots", C.c_int32),
+        ("use_split", C.c_int32)]
+
+
+class SSOpPoolAttnArgs(C.Structure):
+    """ss_op_pool_attn_args: PoolAttnArgs (csrc/attention.hpp) field for field."""
+    _fields_ = [
+        ("Qs", _vp), ("cache", _vp), ("O", _vp),
+        ("ld", C.c_int32), ("ldo", C.c_int32), ("slot_rows", C.c_int32),
+        ("P", _vp), ("ldp", C.c_int32), ("p_tmax", C.c_int32),
+        ("bias_u", _vp), ("bias_v", _vp),
+        ("sess", _vp), ("qt_pre", _vp),
+        ("nsess", C.c_int32), ("qtiles", C.c_int32), ("H", C.c_int32),
+        ("scale", _f)]
+
 # symbol -> (restype, argtypes); must list every function include/streamspeech_hip.h declares
 SIGNATURES = {
     "ss_abi_version": (_i, []),
@@ -150,6 +179,9 @@ SIGNATURES = {
     "ss_op_conv_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _f, _vp, _i]),
     "ss_op_layernorm": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _f]),
     "ss_op_attention": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _i, _vp, _vp]),
+    "ss_op_attention_ex": (_i, [_vp, C.POINTER(SSOpAttnArgs)]),
+    "ss_op_attention_pool": (_i, [_vp, C.POINTER(SSOpPoolAttnArgs)]),
+    "ss_debug_attention_no_mfma": (_i, [_i]),
     "ss_op_dwconv_bn_silu": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _i]),
 }
 
