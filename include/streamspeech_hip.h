@@ -175,6 +175,40 @@ int ss_mp3_synthesize(void* stream, const int16_t* d_q, const ss_mp3_granule* d_
                       const ss_mp3_file* h_files, int n_files, int mono, float* d_out, int64_t out_floats,
                       void* d_work, size_t* work_bytes);
 
+/* Binary PCM in and out of the session pools (streamspeech_amd/pcm.py): a service that takes audio off a socket
+ * holds 16-bit PCM, float32 or G.711 bytes, not SimulEval's lists of Python floats.  A pool step copies every chunk it was pushed into
+ * ONE pinned staging buffer, uploads that once, and ss_pcm_scatter decodes all chunks into the sessions' float32 sample histories in
+ * one launch; ss_pcm_pack_s16 turns the step's synthesised speech into 16-bit PCM in one launch, for one download.
+ * Conversions (one inline function each, csrc/pcm.hpp, shared by the kernels and the host entry points; all little-endian):
+ *   s16le   mono (float)s * 2^-15; stereo ((float)l + (float)r) * 2^-16 -- frontend.read_wav's bits, channel mean included
+ *   f32le   mono: the bits are copied (NaN payloads, -0.0, denormals); stereo (l + r) * 0.5f
+ *   ulaw / alaw   the G.711 expansion to the 16-bit linear value (mu-law 0x00 -> -32124, A-law 0x2A -> -32256), then as s16le
+ *   pack    NaN -> 0, else rintf(fminf(fmaxf(x, -1), 1) * 32767), half to even -- frontend.write_wav's bits */
+enum { SS_PCM_F32LE = 0, SS_PCM_S16LE = 1, SS_PCM_ULAW = 2, SS_PCM_ALAW = 3 };
+
+/* One chunk of a ss_pcm_scatter call. */
+typedef struct ss_pcm_seg {
+  int64_t src_offset;        /* bytes into the staging buffer, a multiple of 16 */
+  int64_t dst_offset;        /* samples into destination h_dst[dst] */
+  int32_t frames;            /* sample frames (per channel) */
+  int32_t fmt, channels, dst; /* SS_PCM_*; 1 or 2, interleaved; index into h_dst */
+} ss_pcm_seg;                /* 32 bytes */
+
+/* Decode n_segs chunks of the device staging buffer d_stage [stage_bytes] into the device float32 buffers h_dst[0 .. n_dst) (capacity
+ * h_dst_cap[i] samples each): segment i writes samples [dst_offset, dst_offset + frames) of h_dst[dst] and nothing else.  h_segs,
+ * h_dst and h_dst_cap are host memory read before the call returns.  One launch, stream-ordered, no host round trip; the device copy
+ * of the table is a buffer the library keeps per stream.  Every refusal is made before any HIP call, for the whole call: first, over
+ * all segments in order, SS_ERR_ARG for n_segs < 0, a fmt outside the enum, channels not 1 or 2, frames < 0, src_offset negative or
+ * not a multiple of 16, dst outside [0, n_dst), dst_offset < 0; then, over all segments in order, SS_ERR_CAPACITY for a source range
+ * past stage_bytes or a destination range past h_dst_cap[dst].  n_segs == 0: SS_OK, no launch. */
+int ss_pcm_scatter(void* stream, const void* d_stage, int64_t stage_bytes, const ss_pcm_seg* h_segs, int n_segs,
+                   float* const* h_dst, const int64_t* h_dst_cap, int n_dst);
+/* d_out[i] = 16-bit PCM of d_src[i], i < n (device buffers).  One launch, stream-ordered.  n < 0: SS_ERR_ARG; n == 0: SS_OK, no launch. */
+int ss_pcm_pack_s16(void* stream, const float* d_src, int64_t n, int16_t* d_out);
+/* The conversions on the host, from the same inline functions: `frames` frames at h_src -> h_dst [frames].  Host only, no HIP call. */
+int ss_pcm_decode_host(const void* h_src, int fmt, int channels, int64_t frames, float* h_dst);
+int ss_pcm_pack_s16_host(const float* h_src, int64_t n, int16_t* h_out);
+
 /* Offline driver only: d_out[r] = max over the vocabulary, ids mask0..2 skipped (< 0: none), of
  * log_softmax(d_logits[r, :]) -- the per-position score `lprobs.max(dim=2)` of the reference's offline unit search
  * (researches/ctc_unity/ctc_generator.py:55-63: pad / unk / eos set to -inf AFTER the softmax), which fairseq-generate

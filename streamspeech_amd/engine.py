@@ -184,6 +184,17 @@ class BatchMixin:
         L.check(self.lib.ss_batch_fbank_frames_sr(self.h, _stream(), B, pp, _i32(n_in), _i32(up), _i32(down), tp, _i32(half),
                                                   _i32(first), _i32(counts), pcm_scale, fp), "ss_batch_fbank_frames_sr")
 
+    def pcm_scatter(self, stage: torch.Tensor, stage_bytes: int, segs, dsts: List[torch.Tensor]):
+        """Every raw PCM chunk of a step, lying in the device staging tensor `stage`, decoded into the float32 histories `dsts` in
+        one launch (ss_pcm_scatter; pcm.scatter names the segment tuple)."""
+        from . import pcm
+        pcm.scatter(self.lib, _stream(), stage, stage_bytes, segs, dsts)
+
+    def pcm_pack_s16(self, src: torch.Tensor, out: torch.Tensor):
+        """float32 device samples -> 16-bit PCM on the device, one launch (ss_pcm_pack_s16)."""
+        from . import pcm
+        pcm.pack_s16(self.lib, _stream(), src, out)
+
     def fbank_sr_rows(self, n_in: int, sr_in: int) -> Optional[Tuple[int, int]]:
         """(fbank rows, final fbank rows) of n_in samples at sr_in Hz (fbank_sr_rows); None for a rate batch_fbank_frames_sr refuses."""
         return fbank_sr_rows(n_in, *resample_ratio(sr_in), lib=self.lib)

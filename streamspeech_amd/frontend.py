@@ -53,7 +53,7 @@ def unsettled_fbank_frames(sr_in: int, sr_out: int = 16000, shift_samples: int =
 def read_wav(path: str):
     """PCM WAV (8/16/32-bit integer) -> (float32 mono samples in [-1, 1), sample rate): the `list[float]`
     the SimulEval dataloader hands the agent (SimulEval/simuleval/data/dataloader/s2t_dataloader.py).
-    MP3 (example/wavs/*.mp3) needs a decoder this image does not have; convert to WAV first."""
+    MP3 (example/wavs/*.mp3) is not read here: read_audio / load_audio_batch decode it (streamspeech_amd/mp3.py)."""
     if str(path).lower().endswith(".mp3"):
         raise IOError("no MP3 decoder is available here; convert %s to PCM WAV" % path)
     with wave.open(str(path), "rb") as w:
@@ -114,6 +114,25 @@ def write_wav(path: str, samples, sr: int = 16000):
         w.setnchannels(1); w.setsampwidth(2); w.setframerate(int(sr))
         w.writeframes(np.round(x * 32767.0).astype("<i2").tobytes())
 
+
+
+def read_wav_raw16(path: str):
+    """A 16-bit PCM WAV as it lies in the file -> (raw interleaved little-endian frames, channels, sample rate, frames), or None for
+    any other sample width (the caller then takes read_wav).  The offline driver's --pcm16-io stages these bytes and decodes them on
+    the device (ss_pcm_scatter), to read_wav's bits."""
+    with wave.open(str(path), "rb") as w:
+        if w.getsampwidth() != 2 or w.getnchannels() not in (1, 2):
+            return None
+        n = w.getnframes()
+        return w.readframes(n), w.getnchannels(), w.getframerate(), n
+
+
+def write_wav_pcm16(path: str, pcm16, sr: int = 16000):
+    """write_wav for samples that are 16-bit PCM already (ss_pcm_pack_s16: write_wav's own rounding, done on the device)."""
+    with wave.open(str(path), "wb") as w:
+        w.setnchannels(1); w.setsampwidth(2); w.setframerate(int(sr))
+        w.writeframes(np.ascontiguousarray(pcm16, dtype="<i2").tobytes())
+
 SHIFT_SIZE, WINDOW_SIZE, ORG_SAMPLE_RATE, SAMPLE_RATE, FEATURE_DIM = 10, 25, 48000, 16000, 80
 
 
@@ -137,6 +156,7 @@ class OnlineFeatureExtractor:
         self._fb = None                          # fbank rows of the cached history (HIP engine; see __call__)
         self._n_fb = 0                           # how many of them are final
         self._src_id = None
+        self.n_pcm = 0                           # the PCM route's sample counter: samples decoded into _dev so far
 
     def _samples(self, samples, n):
         """float32 array of samples[:n].  SimulEval hands the WHOLE sample history as a Python list at every policy() call
@@ -174,17 +194,26 @@ class OnlineFeatureExtractor:
             self._np = c
         return c[:n]
 
+    def frames_of(self, n_samples: int):
+        """The frame arithmetic of a call, shared by the list route (stage) and the PCM route (stage_pcm): (num_frames, effective
+        samples) of a history of `n_samples` samples, or None when no frame exists yet."""
+        num_frames = math.floor(
+            (n_samples - self.len_ms_to_samples(self.window_size - self.shift_size)) / self.num_samples_per_shift)
+        if num_frames <= 0:
+            return None
+        effective = int(num_frames * self.len_ms_to_samples(self.shift_size)
+                        + self.len_ms_to_samples(self.window_size - self.shift_size))
+        return int(num_frames), effective
+
     def stage(self, new_samples):
         """The host part of a call: frames of the history so far, and its new samples copied to the device history.  -> (num_frames,
         effective samples), or None when no frame exists yet.  (The text session pool stages many sessions and computes their new
         fbank rows in one launch: new_rows / commit_rows.)"""
         samples = new_samples
-        num_frames = math.floor(
-            (len(samples) - self.len_ms_to_samples(self.window_size - self.shift_size)) / self.num_samples_per_shift)
-        if num_frames <= 0:
+        st = self.frames_of(len(samples))
+        if st is None:
             return None
-        effective = int(num_frames * self.len_ms_to_samples(self.shift_size)
-                        + self.len_ms_to_samples(self.window_size - self.shift_size))
+        num_frames, effective = st
         x = self._samples(samples, effective)
         # device copy of the history: only the new samples cross PCIe
         dev = self.engine.device
@@ -201,6 +230,45 @@ class OnlineFeatureExtractor:
             self._dev[self._n_dev:effective] = torch.from_numpy(x[self._n_dev:effective]).to(dev)
             self._n_dev = effective
         return int(num_frames), effective
+
+    # ---- the PCM route: raw chunks decoded on the device (streamspeech_amd/pcm.py), a sample COUNTER instead of a sample list ----
+    def pcm_reserve(self, frames: int):
+        """Room for `frames` more samples in the device history (grown by doubling with a device copy, as stage() grows it) -> (the
+        history tensor, the offset the new samples go to).  The caller has them written there (one ss_pcm_scatter for all sessions
+        of a pool step) and then calls pcm_commit(frames)."""
+        if getattr(self, "_np", None) is None:
+            self.clear_cache()
+        n = self.n_pcm + int(frames)
+        if self._dev is None or self._dev.numel() < n:
+            buf = torch.empty((max(2 * n, 1 << 16),), dtype=torch.float32, device=self.engine.device)
+            if self._dev is not None and self.n_pcm:
+                buf[: self.n_pcm] = self._dev[: self.n_pcm]
+            self._dev = buf
+        return self._dev, self.n_pcm
+
+    def pcm_commit(self, frames: int):
+        self.n_pcm += int(frames)
+
+    def stage_pcm(self):
+        """stage() of the PCM route: (num_frames, effective samples) of the samples counted so far, or None.  The history may hold
+        samples past `effective`; rows are computed from the first `effective` ones, exactly as the list route does."""
+        return self.frames_of(self.n_pcm)
+
+    def call_pcm(self, data, fmt, sr=None):
+        """__call__ for a source that arrives as raw PCM chunks: `data` (bytes-like or a matching array, pcm.as_bytes) holds the NEW
+        frames in `fmt` (a pcm.PcmFormat).  -> the fbank rows of everything received so far, bitwise those of __call__ on the list
+        of the same samples.  One upload and one ss_pcm_scatter per call; a session pool does the same for all its sessions at once."""
+        from . import pcm
+        if getattr(self, "_arena", None) is None:
+            self._arena = pcm.PcmArena(self.engine.device)
+        self._arena.clear()
+        frames = fmt.frames(pcm.as_bytes(data, fmt).nbytes)
+        off = self._arena.add(data, fmt)
+        dst, at = self.pcm_reserve(frames)
+        stage, n = self._arena.upload()
+        self.engine.pcm_scatter(stage, n, [(off, at, frames, fmt.code, fmt.channels, 0)], [dst])
+        self.pcm_commit(frames)
+        return self._rows(self.stage_pcm(), sr or self.sample_rate)
 
     def new_rows(self, nf: int) -> int:
         """The HIP engine: the first of the `nf` fbank rows that is not cached as final yet (the row buffer grows to hold all `nf`).
@@ -230,8 +298,10 @@ class OnlineFeatureExtractor:
         return self.engine.fbank_sr_rows(effective, int(sr))
 
     def __call__(self, new_samples, sr=None):
-        sr = sr or self.sample_rate
-        st = self.stage(new_samples)
+        return self._rows(self.stage(new_samples), sr or self.sample_rate)
+
+    def _rows(self, st, sr):
+        """The device part of a call: the fbank rows of the staged history (st: what stage() / stage_pcm() returned)."""
         if st is None:
             return torch.empty((0, self.feature_dim), device=self.engine.device)
         num_frames, effective = st

@@ -30,6 +30,12 @@ class SSVocoderConfig(C.Structure):
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
 
+class SSPcmSeg(C.Structure):
+    """ss_pcm_seg: one chunk of a ss_pcm_scatter call (32 bytes)."""
+    _fields_ = [("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("frames", C.c_int32), ("fmt", C.c_int32),
+                ("channels", C.c_int32), ("dst", C.c_int32)]
+
+
 class SSOpAttnArgs(C.Structure):
     """ss_op_attn_args: AttnArgs (csrc/attention.hpp) field for field, pointers as device addresses."""
     _fields_ = [
@@ -79,6 +85,10 @@ SIGNATURES = {
     "ss_mp3_probe": (_i, [_vp, C.c_size_t, _vp]),
     "ss_mp3_unpack": (_i, [_vp, C.c_size_t, _i64, _vp, _vp, _vp]),
     "ss_mp3_synthesize": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp, C.POINTER(C.c_size_t)]),
+    "ss_pcm_scatter": (_i, [_vp, _vp, _i64, _vp, _i, C.POINTER(_vp), C.POINTER(_i64), _i]),
+    "ss_pcm_pack_s16": (_i, [_vp, _vp, _i64, _vp]),
+    "ss_pcm_decode_host": (_i, [_vp, _i, _i, _i64, _vp]),
+    "ss_pcm_pack_s16_host": (_i, [_vp, _i64, _vp]),
     "ss_row_max_logprob": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ss_log_softmax": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ss_encoder_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),

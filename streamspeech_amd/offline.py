@@ -67,9 +67,11 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              subset: str = "test", batch_size: int = 32, max_tokens: int = 0, max_len_a: float = 0.0,
              max_len_b: int = 200, max_len_a_mt: float = 0.0, max_len_b_mt: int = 200, dur_prediction: bool = True, dump_wav: bool = True, t2u_causal: bool = False,
              scores: bool = False, log=None, targets: Optional[Dict[int, Sequence[int]]] = None, beam_mt: int = 1,
-             unk_penalty: float = 0.0, normalize: bool = True) -> Dict[int, Dict]:
+             unk_penalty: float = 0.0, normalize: bool = True, pcm16_out: bool = False) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
-    the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses."""
+    the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
+    pcm16_out (--pcm16-io): the waveforms of a batch become 16-bit PCM on the device (one ss_pcm_pack_s16, one download per batch)
+    and pred_wav/ is written from those bytes -- the same files, without a float download and a host rounding per utterance."""
     cfg = model.cfg
     os.makedirs(results_path, exist_ok=True)
     log_f = log or open(os.path.join(results_path, f"generate-{subset}.log"), "w", encoding="utf-8")
@@ -111,6 +113,9 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
         if dump_wav and have:
             w, _, _ = vocoder.batch_forward([codes[b] for b in have], dur_prediction=dur_prediction)
             wavs = {b: w[j] for j, b in enumerate(have)}
+            if pcm16_out:
+                pcm16 = _pack_batch(model, [wavs[b] for b in have])
+                pcm16 = {b: pcm16[j] for j, b in enumerate(have)}
         for b, sid in enumerate(ids):
             a_txt = detok([dicts["source_unigram"][c] for c in asr[b][0]])
             s_txt = detok([dicts["ctc_target_unigram"][c] for c in st[b][0]])
@@ -130,11 +135,50 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
             if pos is not None:
                 print(f"P-{sid}\t" + " ".join("{:.4f}".format(x) for x in pos), file=res_f)
             hyps[sid] = {"asr": a_txt, "st": s_txt, "mt": d_txt, "units": codes[b], "wav": wavs.get(b)}
+            if pcm16_out and dump_wav and have:
+                hyps[sid]["pcm16"] = pcm16.get(b)
     res_f.close()
     if log is None:
         log_f.close()
     _cut_files(hyps, results_path, subset, dump_wav)
     return hyps
+
+
+def _pack_batch(model, wavs: List[torch.Tensor]):
+    """The waveforms of one batch -> int16 NumPy arrays: one ss_pcm_pack_s16 launch over all of them, one download."""
+    n = [int(w.numel()) for w in wavs]
+    src = torch.cat([w.reshape(-1) for w in wavs], 0)
+    out = torch.empty((max(sum(n), 1),), dtype=torch.int16, device=src.device)
+    if sum(n):
+        model.pcm_pack_s16(src, out[:sum(n)])
+    host = out[:sum(n)].cpu().numpy()
+    res, off = [], 0
+    for k in n:
+        res.append(host[off:off + k])
+        off += k
+    return res
+
+
+def stage_wavs_pcm16(model, raws, device):
+    """--pcm16-io: [(raw 16-bit frames, channels, sample rate, frames)] -> [(float32 mono tensor on the device, sample rate)], read_wav's
+    bits.  The raw bytes of all files go into one pinned arena, are uploaded ONCE and decoded by ONE ss_pcm_scatter launch into one
+    packed float32 buffer, of which the results are views."""
+    from .pcm import SS_PCM_S16LE, PcmArena
+    arena = PcmArena(device, capacity=sum(len(r[0]) for r in raws) + 16 * len(raws) + 16)
+    segs, at = [], 0
+    for raw, nch, _, n in raws:
+        segs.append((arena.add(raw), at, n, SS_PCM_S16LE, nch, 0))
+        at += n
+    packed = torch.empty((max(at, 1),), dtype=torch.float32, device=device)
+    stage, nbytes = arena.upload()
+    if nbytes:
+        model.pcm_scatter(stage, nbytes, segs, [packed])
+    arena.clear()                                 # waits for the upload: the arena goes away with this call
+    out, at = [], 0
+    for _, _, sr, n in raws:
+        out.append((packed[at:at + n], sr))
+        at += n
+    return out
 
 
 def _unit_scores(model, feats: torch.Tensor, t2u_causal: bool):
@@ -161,7 +205,9 @@ def _cut_files(hyps: Dict[int, Dict], results_path: str, subset: str, dump_wav: 
         os.makedirs(wdir, exist_ok=True)
         for n, i in enumerate(ids):
             w = hyps[i]["wav"]
-            if w is not None:
+            if hyps[i].get("pcm16") is not None:
+                frontend.write_wav_pcm16(os.path.join(wdir, f"{n}_pred.wav"), hyps[i]["pcm16"], 16000)
+            elif w is not None:
                 frontend.write_wav(os.path.join(wdir, f"{n}_pred.wav"), w.detach().cpu().numpy(), 16000)
 
 
@@ -219,6 +265,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--beam", type=int, default=1, help="unit generator beam (accepted for parity; the CTC unit decoder has no search)")
     ap.add_argument("--unkpen", type=float, default=0.0, help="subtracted from the <unk> log-probability of the text search")
     ap.add_argument("--unnormalized", action="store_true", help="text search: do not divide hypothesis scores by their length")
+    ap.add_argument("--pcm16-io", action="store_true",
+                    help="16-bit WAV sources are staged as raw frames, uploaded once and decoded on the device, and pred_wav/ is "
+                         "written from 16-bit PCM packed on the device (one download per batch); the same files as without it")
     return ap
 
 
@@ -261,6 +310,16 @@ def main(argv: Optional[List[str]] = None):
         # MP3 rows: batched decodes of up to 640 s of audio each, straight to the device (streamspeech_amd/mp3.py); WAV rows as before
         mp3_rows = [k for k, (_, path) in enumerate(rows) if frontend.is_mp3(path)]
         decoded = dict(zip(mp3_rows, frontend.load_audio_batch([rows[k][1] for k in mp3_rows], a.device))) if mp3_rows else {}
+        if a.pcm16_io:                              # 16-bit WAV rows: raw frames, one upload, one decode launch; others as before
+            raw_rows, raws = [], []
+            for k, (_, path) in enumerate(rows):
+                if k not in decoded:
+                    r = frontend.read_wav_raw16(path)
+                    if r is not None:
+                        raw_rows.append(k)
+                        raws.append(r)
+            if raws:
+                decoded.update(zip(raw_rows, stage_wavs_pcm16(model, raws, a.device)))
         entries = []
         for k, (i, path) in enumerate(rows):
             if k in decoded:
@@ -281,7 +340,8 @@ def main(argv: Optional[List[str]] = None):
     hyps = generate(model, voc, items, holder.dict, a.results_path, sub, a.batch_size, a.max_tokens, a.max_len_a,
                     a.max_len_b, a.max_len_a_mt, a.max_len_b_mt, a.dur_prediction, not a.no_wav,
                     getattr(holder.model, "uni_encoder", False), a.scores, targets=targets or None, beam_mt=a.beam_mt,
-                    unk_penalty=a.unkpen, normalize=not a.unnormalized)
+                    unk_penalty=a.unkpen, normalize=not a.unnormalized,
+                    **({"pcm16_out": True} if a.pcm16_io else {}))
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
 
 

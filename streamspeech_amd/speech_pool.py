@@ -6,12 +6,18 @@ the S2TT writers) and then, for the S2ST sessions that write,
   * ONE ragged MT feature pass for the rows whose final write carries a trailing <pad> (HipModel.batch_mt_features),
   * ONE T2U + unit decoder call with per-row tail-pad masks (HipModel.batch_t2u_units_pad),
   * ONE receptive-field vocoder tail call (HipVocoder.batch_tail; one per duration-prediction setting in use).
-Driven by one host thread, like the pool."""
+Driven by one host thread, like the pool.
+
+An S2ST session opened with ``pcm_out="s16le"`` answers :class:`PcmSegment` (16-bit PCM bytes) instead of a SpeechSegment holding a
+Python list: the tails of all such writers of a step go through ONE ss_pcm_pack_s16 launch and ONE device-to-host copy into pinned
+memory, where a list-fed session pays one ``wav.tolist()`` copy each.  The bytes are frontend.write_wav's rounding of the samples."""
 import time
 
+import numpy as np
 import torch
 
 from .frontend import SAMPLE_RATE
+from .pcm import PcmSegment, pack_s16_host
 from .simuleval_shim import SpeechSegment
 from .text_pool import KINDS as TEXT_KINDS
 from .text_pool import TextSessionPool, _Session
@@ -92,6 +98,9 @@ class SpeechSessionPool(TextSessionPool):
         return ("write", prefix, ml, g.new_tokens)
 
     def _finish_empty(self, s):
+        if s.pcm_out:                                     # a carried unfinished_wav goes out in the session's own format
+            carried = s.unfinished_wav.cpu().numpy() if s.unfinished_wav is not None else np.zeros(0, np.float32)
+            return ("speech", pack_s16_host(carried).tobytes() if carried.size else b"", True, False)
         return ("speech", list(s.unfinished_wav.tolist()) if s.unfinished_wav is not None else [], True, False)
 
     def _mt_decide(self, s, toks):
@@ -166,28 +175,73 @@ class SpeechSessionPool(TextSessionPool):
                     continue
                 voc.append((s, unit, len(cur)))
         t2 = time.perf_counter()
+        handover, raw = 0.0, []                           # raw: (session, tail) of the pcm_out writers, packed together below
         for dp in (True, False):
             grp = [v for v in voc if v[0].dur_prediction == dp]
             if not grp:
                 continue
             tails, _ = self.vocoder.batch_tail([u for _, u, _ in grp], [k for _, _, k in grp], [s.vocoder_ctx for s, _, _ in grp],
                                                [s.vocoder_rf for s, _, _ in grp], dur_prediction=dp)
+            th = time.perf_counter()
             for (s, unit, _), wav in zip(grp, tails):
                 if s.unfinished_wav is not None and len(s.unfinished_wav) > 0:
                     wav = torch.cat((s.unfinished_wav, wav), 0)
                 s.unit = unit
+                if s.pcm_out:
+                    raw.append((s, wav))
+                    continue
                 # a final write (new_tokens == -1) ends with the agent's reset(), which runs BEFORE the agent builds its segment and
                 # clears source_finished: no write says finished=True
                 actions[s.sid] = ("speech", wav.tolist(), False, s.states.source_finished)
+            handover += time.perf_counter() - th
+        th = time.perf_counter()
+        n_out = self._pack_out(raw, actions) if raw else 0
         t3 = time.perf_counter()
-        self._side_times = {"mt_features_s": t1 - t0, "units_s": t2 - t1, "vocoder_s": t3 - t2,
-                            "speech_writers": len(voc)}
+        # handover_s: from the tails' views in hand to the contents the segments carry (lists or bytes), both routes; it lies inside
+        # vocoder_s, which keeps its meaning (the tail calls and what follows them)
+        self._side_times = {"mt_features_s": t1 - t0, "units_s": t2 - t1, "vocoder_s": t3 - t2, "handover_s": handover + (t3 - th),
+                            "speech_writers": len(voc), "pcm_pack_calls": 1 if n_out else 0, "pcm_bytes_out": 2 * n_out}
+
+    def _pack_out(self, raw, actions) -> int:
+        """The tails of a step's pcm_out writers -> 16-bit PCM bytes: ONE ss_pcm_pack_s16 launch over all of them and ONE
+        device-to-host copy into pinned memory, then a bytes object per session.  -> samples packed."""
+        tails = [w for _, w in raw]
+        n = [int(w.numel()) for w in tails]
+        total = sum(n)
+        if total:
+            # views of one packed buffer that follow each other (one batch_tail call) are packed where they lie; otherwise (two
+            # duration settings in one step, a carried wav) they are gathered first
+            adjacent = all(a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
+                           and a.data_ptr() + 4 * a.numel() == b.data_ptr() for a, b in zip(tails, tails[1:]))
+            if adjacent and tails[0].is_contiguous():
+                src = tails[0].new_empty(0).set_(tails[0].untyped_storage(), tails[0].storage_offset(), (total,))
+            else:
+                src = torch.cat(tails, 0)
+            cuda = src.device.type == "cuda"
+            if getattr(self, "_out_dev", None) is None or self._out_dev.numel() < total:
+                self._out_dev = torch.empty((2 * total,), dtype=torch.int16, device=src.device)
+                self._out_host = torch.empty((2 * total,), dtype=torch.int16, pin_memory=cuda)
+            self.model.pcm_pack_s16(src, self._out_dev[:total])
+            self._out_host[:total].copy_(self._out_dev[:total], non_blocking=True)
+            if cuda:
+                torch.cuda.current_stream().synchronize()    # the bytes below are read from the pinned buffer: the copy must have landed
+        off = 0
+        for (s, _), k in zip(raw, n):
+            content = self._out_host[off:off + k].numpy().tobytes() if k else b""
+            off += k
+            actions[s.sid] = ("speech", content, False, s.states.source_finished)
+        return total
 
     def _segment(self, s, a):
         if a[0] == "write":                               # the front-end's early return of a finished source: no speech
+            if s.pcm_out:
+                return PcmSegment(index=0, content=b"", fmt=s.pcm_out, sample_rate=SAMPLE_RATE, finished=True)
             return SpeechSegment(index=0, content=[], sample_rate=SAMPLE_RATE, finished=True)
         _, content, finished, done = a
+        pcm_out = s.pcm_out
         if done:                                          # the agent's reset(): a fresh utterance, its slot back to the pool
             s.reset()
             self._release(s)
+        if pcm_out:
+            return PcmSegment(index=0, content=content, fmt=pcm_out, sample_rate=SAMPLE_RATE, finished=finished)
         return SpeechSegment(index=0, content=content, sample_rate=SAMPLE_RATE, finished=finished)

@@ -7,7 +7,12 @@ agent; across sessions a step is
   * ONE batched encoder step and both CTC heads (StreamPool.forward / ctc_both; ASR sessions read head 0),
   * the read/write gate of each session on the host (text_policy.s2tt_gate),
   * ONE ragged greedy continuation of the committed prefix of every writing S2TT session (HipModel.batch_mt_continue).
-Driven by one host thread, like the pool."""
+Driven by one host thread, like the pool.
+
+A session opened with ``pcm_in=PcmFormat(...)`` is fed raw PCM bytes (push_pcm) instead of SimulEval's lists of floats: the step copies
+the chunks of all such sessions into one pinned arena, uploads it ONCE and decodes every chunk into its session's device history in ONE
+ss_pcm_scatter launch (streamspeech_amd/pcm.py), then runs the same single fbank launch.  The decoded samples are the bits the list
+route uploads, so everything downstream is unchanged; list-fed sessions run the code they always ran, in the same step."""
 import math
 import time
 from typing import Dict, Optional
@@ -16,6 +21,7 @@ import torch
 
 from .engine import MT_BEAM_MAX, plan_beam_groups
 from .frontend import SAMPLE_RATE, OnlineFeatureExtractor, unsettled_fbank_frames
+from .pcm import PcmArena, PcmFormat
 from .simuleval_shim import AgentStates, EmptySegment, TextSegment
 from .text_policy import mt_max_len, s2tt_gate
 
@@ -57,7 +63,16 @@ class _Session:
         self.states = AgentStates()
         self.slot = None
         self.pending = False
+        self.pcm_in = None                    # a PcmFormat: the session is fed by push_pcm, and counts samples (fe.n_pcm) instead of
+        self.pcm_out = None                   # keeping them in states.source; "s16le": it answers PcmSegment (speech_pool.py)
+        self.pcm_chunk = None                 # (byte view, frames) pushed for the next step
         self.reset()
+
+    def n_source(self) -> int:
+        """Samples received so far: every host decision that reads len(states.source) of a list-fed session reads this."""
+        if self.pcm_in is None:
+            return len(self.states.source)
+        return self.fe.n_pcm + (self.pcm_chunk[1] if self.pcm_chunk is not None else 0)
 
     def reset(self):                          # the agent's reset()
         self.tgt_subwords = None
@@ -86,21 +101,31 @@ class TextSessionPool:
         self.free = list(range(self.max_sessions))
         self._next = 0
         self.last_step: dict = {}              # timings / counts of the last step (tools/pooled_text_bench.py)
+        self._arena = None                     # the pinned staging buffer of the PCM-fed sessions' chunks, made with the first one
         self._side_times: dict = {}            # timings a subclass's write side adds to last_step
 
     # ---- lifecycle ------------------------------------------------------------------------------------------------------------
-    def open(self, kind: str, args, dicts: Optional[dict] = None) -> int:
+    def open(self, kind: str, args, dicts: Optional[dict] = None, pcm_in: Optional[PcmFormat] = None,
+             pcm_out: Optional[str] = None) -> int:
         """A new session; `args` are the agent's own parsed flags (segment size, lagging_k1, stride_n, sample rate, chunk sizes).
-        `dicts` overrides the dictionaries the agent would load from the flags (keys source_unigram / target_unigram)."""
+        `dicts` overrides the dictionaries the agent would load from the flags (keys source_unigram / target_unigram).
+        pcm_in=PcmFormat(...): the session is fed raw PCM at args.sample_rate through push_pcm() and nothing else.
+        pcm_out="s16le" (s2st sessions only): it answers PcmSegment with 16-bit PCM bytes instead of SpeechSegment with a list."""
         if kind not in self.KINDS:
             raise ValueError(f"session kind {kind!r}: one of {self.KINDS}")
+        if pcm_in is not None and not isinstance(pcm_in, PcmFormat):
+            raise ValueError(f"pcm_in is a PcmFormat, not {pcm_in!r}")
+        if pcm_out is not None and (pcm_out != "s16le" or kind != "s2st"):
+            raise ValueError(f"pcm_out={pcm_out!r} for a {kind} session: only \"s16le\", and only for s2st sessions")
         self._check_open(kind, args)
         if dicts is None:
             from .agent import load_dictionaries
             dicts = load_dictionaries(args, self.model.cfg)
         sid = self._next
         self._next += 1
-        self.sessions[sid] = self._new_session(sid, kind, args, dicts)
+        s = self._new_session(sid, kind, args, dicts)
+        s.pcm_in, s.pcm_out = pcm_in, pcm_out
+        self.sessions[sid] = s
         return sid
 
     def _check_open(self, kind: str, args):
@@ -114,6 +139,7 @@ class TextSessionPool:
         s = self._get(sid)
         s.reset()
         s.pending = False
+        s.pcm_chunk = None
         self._release(s)
 
     def close(self, sid: int):
@@ -142,12 +168,13 @@ class TextSessionPool:
 
     # ---- one call per session ---------------------------------------------------------------------------------------------------
     def _frames(self, s: _Session, extra: int = 0) -> int:
-        return fbank_frames_after(s.sr, len(s.states.source) + extra, s.args.shift_size, s.args.window_size)
+        return fbank_frames_after(s.sr, s.n_source() + extra, s.args.shift_size, s.args.window_size)
 
     def _admit(self, items):
-        """The capacity check of a set of pushes [(session, segment)], against everything already pushed for this step: raises
-        ValueError naming the first session refused and changes nothing.  A session is refused when it is already pushed, when
-        its audio would pass max_rows encoder rows, or when it needs a slot (frames, none held) and the free slots are spoken for."""
+        """The capacity check of a set of pushes [(session, segment)] -- or [(session, new frames)] for PCM chunks -- against
+        everything already pushed for this step: raises ValueError naming the first session refused and changes nothing.  A session
+        is refused when it is already pushed, when its audio would pass max_rows encoder rows, or when it needs a slot (frames, none
+        held) and the free slots are spoken for."""
         seen = set()
         for s, _ in items:
             if s.pending or s.sid in seen:
@@ -159,7 +186,7 @@ class TextSessionPool:
         for s, seg in items:
             if s.states.target_finished:
                 continue
-            T = self._frames(s, len(getattr(seg, "content", None) or []))
+            T = self._frames(s, seg if isinstance(seg, int) else len(getattr(seg, "content", None) or []))
             if T > 0 and _encoder_out_len(T) > self.max_rows:
                 raise ValueError(f"session {s.sid}: {_encoder_out_len(T)} encoder rows would pass the pool's max_rows {self.max_rows}")
             if T > 0 and s.slot is None:
@@ -172,9 +199,53 @@ class TextSessionPool:
         """The agent's push(), checked against the pool's capacity first (_admit): a refused push raises ValueError naming the
         session and changes nothing; the sessions pushed before and after it step as usual."""
         s = self._get(sid)
+        self._check_route([s], pcm=False)
         self._admit([(s, segment)])
         s.states.update_source(segment)
         s.pending = True
+
+    def _check_route(self, sessions, pcm: bool):
+        """A session is fed one way for its whole life: segments (push / step) or raw PCM (push_pcm).  ValueError, nothing changes."""
+        for s in sessions:
+            if (s.pcm_in is not None) != pcm:
+                raise ValueError(f"session {s.sid}: opened with pcm_in={s.pcm_in!r}, it is fed by "
+                                 + ("push_pcm() only" if s.pcm_in is not None else "push() / step() segments only"))
+
+    def push_pcm(self, sid: int, data, finished: bool = False):
+        """push() for a session opened with pcm_in: `data` holds the new frames in the session's format -- bytes, bytearray, memoryview,
+        or a C-contiguous NumPy / CPU torch array of the matching dtype; a partial frame is ValueError.  The same admission check as
+        push(), counted in frames.  The bytes are copied at the next step(), so a mutable buffer must stay as it is until then."""
+        from .pcm import as_bytes
+        s = self._get(sid)
+        self._check_route([s], pcm=True)
+        mv = as_bytes(data, s.pcm_in)
+        frames = s.pcm_in.frames(mv.nbytes)
+        self._admit([(s, frames)])
+        s.pcm_chunk = (mv, frames)
+        s.states.source_finished = bool(finished)
+        s.pending = True
+
+    def _pcm_stage(self, sessions):
+        """The chunks of a step's PCM-fed sessions: copied into the arena, ONE upload, ONE ss_pcm_scatter into the sessions' device
+        histories.  -> bytes moved.  The arena is single-buffered: the step's CTC read (or, in a step that encodes nothing, the
+        upload's event at the next clear()) orders the copy before the buffer is written again."""
+        if self._arena is None:
+            self._arena = PcmArena(self.model.device)
+        self._arena.clear()
+        segs, dsts = [], []
+        for s in sessions:
+            mv, frames = s.pcm_chunk
+            off = self._arena.add(mv)
+            dst, at = s.fe.pcm_reserve(frames)
+            segs.append((off, at, frames, s.pcm_in.code, s.pcm_in.channels, len(dsts)))
+            dsts.append(dst)
+        stage, n = self._arena.upload()
+        if n:                                     # nothing but empty chunks (a bare finished=True): no copy, no launch
+            self.model.pcm_scatter(stage, n, segs, dsts)
+        for s in sessions:
+            s.fe.pcm_commit(s.pcm_chunk[1])
+            s.pcm_chunk = None
+        return n
 
     def step(self, segments: Optional[dict] = None) -> dict:
         """{sid: SpeechSegment} -> {sid: Segment}: per session exactly one agent.pushpop(segment), for these sessions and any pushed
@@ -182,6 +253,7 @@ class TextSessionPool:
         call is refused before anything moves (to step the others anyway, push() them one by one and call step())."""
         if segments:
             items = [(self._get(sid), seg) for sid, seg in segments.items()]
+            self._check_route([s for s, _ in items], pcm=False)
             self._admit(items)
             for s, seg in items:
                 s.states.update_source(seg)
@@ -192,12 +264,15 @@ class TextSessionPool:
         t0 = time.perf_counter()
         # ---- front-end: finished agents answer at once; the new rows of every other session in one launch ----
         feats, batch, fe_calls, fe_rows = {}, [], 0, 0
+        fed = [s for s in todo if s.pcm_chunk is not None and not s.states.target_finished]
+        pcm_bytes = self._pcm_stage(fed) if fed else 0
         for s in todo:
             s.pending = False
             if s.states.target_finished:
+                s.pcm_chunk = None                # a finished agent's audio is not kept (the list route appends and never reads it)
                 out[s.sid] = EmptySegment(finished=True)
                 continue
-            st = s.fe.stage(s.states.source)
+            st = s.fe.stage_pcm() if s.pcm_in is not None else s.fe.stage(s.states.source)
             if st is None:
                 actions[s.sid] = ("write", "", True) if s.states.source_finished else ("read",)
                 continue
@@ -239,6 +314,8 @@ class TextSessionPool:
             packed, views, _, _ = self.pool.forward([s.slot for s in enc], [feats[s.sid] for s in enc],
                                                     [s.attn_chunk for s in enc], [s.conv_chunk for s in enc])
             src, tgt = self.pool.ctc_both()
+            if fed:
+                self._arena.synchronized()        # the CTC read waited for everything queued before it, the arena's upload included
             t2 = time.perf_counter()
             for i, s in enumerate(enc):
                 if s.kind == "asr":
@@ -300,6 +377,10 @@ class TextSessionPool:
                 self._release(s)                  # from now on, so its slot goes back; reset(sid) starts a fresh utterance
         self.last_step = {"sessions": len(todo), "encoded": len(enc), "writers": len(writers), "mt_steps": n_steps, "mt_groups": mt_groups,
                           "frontend_calls": fe_calls, "fbank_rows": fe_rows,       # front-end device calls of the step, rows they computed
+                          # the PCM route: uploads and ss_pcm_scatter launches of the step (0 or 1 each), bytes uploaded; a subclass's
+                          # write side sets the pack side (ss_pcm_pack_s16 launches, bytes downloaded)
+                          "pcm_uploads": 1 if pcm_bytes else 0, "pcm_scatter_calls": 1 if pcm_bytes else 0, "pcm_bytes_in": pcm_bytes,
+                          "pcm_pack_calls": 0, "pcm_bytes_out": 0,
                           "frontend_s": t1 - t0, "encoder_ctc_s": t2 - t1, "mt_s": t3 - t2, "total_s": time.perf_counter() - t0}
         self.last_step.update(self._side_times)
         self._side_times = {}
