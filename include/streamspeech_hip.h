@@ -121,9 +121,10 @@ int ss_resample(void* stream, const float* d_in, int64_t n_in, int up, int down,
  * and a LAME tag in it sets the gapless trim (delay + 529 samples at the start, padding - 529 at the end; no tag: no trim).
  * Refused: intensity stereo, free-format bitrate, Layers I / II and reserved header fields (SS_ERR_UNSUPPORTED = 7); corrupt or
  * inconsistent data, including Huffman data that overruns part2_3_length (SS_ERR_BITSTREAM = 6).  A truncated last frame is
- * dropped.  A stream whose first audio frame points back into the bit reservoir (main_data_begin > 0: cut at the front, or
- * captured mid-stream) is refused with SS_ERR_BITSTREAM as a whole, where some decoders output silence for the granules they
- * cannot decode and go on.  Nothing is read outside [h_data, h_data + n_bytes). */
+ * dropped.  A file whose first audio frame points back into the bit reservoir (main_data_begin > 0: cut at the front) is refused
+ * with SS_ERR_BITSTREAM by the whole-file calls, where some decoders output silence for the granules they cannot decode and go on;
+ * a stream captured mid-stream is what ss_mp3_stream with join != 0 is for (below).  Nothing is read outside
+ * [h_data, h_data + n_bytes). */
 typedef struct ss_mp3_info {
   int32_t version;           /* 1 = MPEG-1, 2 = MPEG-2 LSF, 25 = MPEG-2.5 */
   int32_t sample_rate, channels;
@@ -174,6 +175,96 @@ int ss_mp3_unpack(const uint8_t* h_data, size_t n_bytes, int64_t cap, int16_t* h
 int ss_mp3_synthesize(void* stream, const int16_t* d_q, const ss_mp3_granule* d_rec, int64_t n_rec,
                       const ss_mp3_file* h_files, int n_files, int mono, float* d_out, int64_t out_floats,
                       void* d_work, size_t* work_bytes);
+
+/* MP3 streams (streamspeech_amd/mp3.py Mp3StreamDecoder): the decoder above, resumable.  A service that takes
+ * compressed audio off a socket pushes the bytes as they arrive, in chunks of any size (0 and 1 byte included); every frame a chunk
+ * completes comes out as the records and q rows ss_mp3_unpack would have written for it, in the same order, and the device stage
+ * synthesises them against two granules of IMDCT blocks carried per stream -- so the PCM of a stream fed in any chunking is, bit for
+ * bit, the PCM of the whole-file calls on the same bytes.  ss_mp3_probe and ss_mp3_unpack run on the same core (one pass with
+ * finished = 1), so the acceptance rules cannot drift:
+ *   - ID3v2 tags (+ footer) at the start are skipped, across pushes; a header is taken only when the next frame's header agrees, so a
+ *     frame is released once 4 bytes past its end have arrived, or at `finished` (a complete last frame is accepted without
+ *     look-ahead, a truncated one is dropped); resynchronisation over garbage is byte by byte; CRC words are skipped; a Xing / Info
+ *     first frame is not audio and its LAME tag sets the gapless trim; the refusals are those of the whole-file calls.
+ *   - TRAILING tags (ID3v1, APEv2) are not recognised in a stream: finding them needs the end of the file.  Their bytes go through
+ *     resynchronisation like any garbage, and a last frame directly followed by one fails its look-ahead.  The bit identity with the
+ *     whole-file calls holds for inputs whose end the whole-file scan does not cut.
+ *   - State is bounded whatever the stream length: fewer than one maximal frame (1441 bytes) + 4 unconsumed bytes, the last 511 bytes
+ *     of main data, the previous granule's scalefactors, the first accepted header, the LAME delay / padding and the count of ID3v2
+ *     bytes still to skip.  ss_mp3_stream_info.buffered reports the unconsumed bytes.
+ *   - A push is a transaction: one that fails (SS_ERR_BITSTREAM, SS_ERR_UNSUPPORTED, or SS_ERR_CAPACITY because `cap` records are too
+ *     few) leaves the object exactly as it was, so the same bytes can be pushed again with larger buffers, or other bytes instead.
+ *     ss_mp3_stream_bound gives a `cap` that always suffices for a chunk of n_bytes.
+ *   - join != 0 at create: a frame whose main_data_begin reaches back before the first main-data byte this object received is not
+ *     decoded and yields no records (its main data still enters the reservoir; skipped_frames counts it); decoding starts at the
+ *     first frame that is wholly decodable.  With join == 0 such a stream is refused with SS_ERR_BITSTREAM, as by the whole-file calls.
+ *   - Gapless: with a LAME tag the first delay + 529 decoded samples are never released and the last max(0, padding - 529) decoded so
+ *     far are held back (at `finished` they are the encoder's padding and are dropped); without a tag nothing is trimmed or held.
+ *     `samples` counts the released ones: at `finished` it equals ss_mp3_info.samples of the same bytes.
+ * Host only, no HIP call, no global mutable state; one object is driven by one thread at a time.  After a push with finished != 0
+ * the object takes no more data until it is reset (SS_ERR_ARG). */
+typedef struct ss_mp3_stream ss_mp3_stream;
+
+typedef struct ss_mp3_stream_info {
+  int32_t version;           /* as ss_mp3_info, of the first accepted header; 0 before one was accepted */
+  int32_t sample_rate, channels, sr_index;
+  int32_t delay, padding;    /* from the LAME tag; -1 without one */
+  int32_t skip;              /* decoded samples never released at the start: delay + 529, or 0 */
+  int32_t hold;              /* decoded samples held back at the end: max(0, padding - 529), or 0 */
+  int32_t buffered;          /* unconsumed bytes the object keeps (< 1441 + 4) */
+  int32_t finished;
+  int64_t frames;            /* audio frames decoded so far */
+  int64_t granules;          /* granules per channel decoded so far; 576 samples each */
+  int64_t samples;           /* per channel, released so far: max(0, 576 granules - skip - hold) */
+  int64_t skipped_frames;    /* join: frames passed over because their main data began before the stream was joined */
+  int64_t bytes_in;          /* bytes of all successful pushes */
+} ss_mp3_stream_info;        /* 80 bytes */
+
+int ss_mp3_stream_create(int join, ss_mp3_stream** out);
+void ss_mp3_stream_destroy(ss_mp3_stream* s);
+int ss_mp3_stream_reset(ss_mp3_stream* s);                   /* a fresh stream; join stays as created */
+/* Records a push of n_bytes can write at most, given what the object holds now (2 records per 24 bytes: the shortest frame). */
+int64_t ss_mp3_stream_bound(const ss_mp3_stream* s, size_t n_bytes);
+/* Consume h_data [n_bytes] (may be NULL when n_bytes == 0) and write the records of every frame the chunk completes: h_q [cap][576],
+ * h_rec [cap], h_bits [cap] (may be NULL), *n_rec of them, ordered and laid out as by ss_mp3_unpack.  h_info (may be NULL): the state
+ * after the push, or the unchanged state when it fails. */
+int ss_mp3_stream_push(ss_mp3_stream* s, const uint8_t* h_data, size_t n_bytes, int finished, int64_t cap, int16_t* h_q,
+                       ss_mp3_granule* h_rec, int32_t* h_bits, int64_t* n_rec, ss_mp3_stream_info* h_info);
+int ss_mp3_stream_query(const ss_mp3_stream* s, ss_mp3_stream_info* h_info);
+/* dst becomes an exact copy of src's state (under 2.5 KB): a caller that may have to take a SUCCESSFUL push back -- a session pool
+ * that learns only from the push how many samples it releases, and then refuses it for capacity -- copies first and copies back. */
+int ss_mp3_stream_copy(ss_mp3_stream* dst, const ss_mp3_stream* src);
+
+/* One stream's share of a ss_mp3_stream_synthesize call: `granules` new granules (x channels records from rec_offset on). */
+typedef struct ss_mp3_stream_seg {
+  int64_t rec_offset;        /* index of the segment's first record in d_q / d_rec */
+  int64_t dst_offset;        /* samples into destination h_dst[dst] where the first written sample goes */
+  int64_t ch_stride;         /* planar output (mono == 0): channel c is written ch_stride floats after channel 0 */
+  int32_t granules;          /* new granules per channel; 0: the segment costs nothing and changes nothing */
+  int32_t channels;          /* 1 or 2 */
+  int32_t skip;              /* samples of these granules dropped at the front (what is left of the gapless skip), <= 576 granules */
+  int32_t history;           /* granules the stream decoded before these, saturated at 2: how much of d_state is read */
+  int32_t dst;               /* index into h_dst */
+  int32_t pad0;
+} ss_mp3_stream_seg;         /* 48 bytes */
+
+/* Device stage of the streams of one step, a ragged batch: requantisation ... IMDCT of the new granules (the kernel of
+ * ss_mp3_synthesize), then synthesis of each against its stream's carried blocks, then the carried blocks move on -- three launches
+ * and one table upload whatever n_segs is, stream-ordered, no host round trip.  h_state[i] is segment i's device state, [2][channels]
+ * [1152] floats: the IMDCT blocks of the stream's last two granules (older first), which the synthesis of a granule overlap-adds
+ * and whose last 15 time slots stand in front of it; only `history` of them are read, so a new stream's state need not be zeroed and
+ * a first granule is formed exactly as the whole-file kernel forms it (no 0 + -0).  After the call the state holds the blocks of the
+ * last two granules again ({old last, new} after a single new granule).  Two segments must not share a state.  Segment i writes
+ * samples [dst_offset, dst_offset + 576 granules - skip) of h_dst[dst] -- the channel mean with mono != 0, else planar with ch_stride
+ * -- and nothing else; h_dst_cap[i] is the capacity of h_dst[i] in floats.  Per sample the arithmetic is that of ss_mp3_synthesize
+ * (one device function serves both kernels), so a stream decodes to the same bits in any chunking, alone or in any batch.
+ * h_segs, h_state, h_dst and h_dst_cap are host memory read before the call returns.  d_work as for ss_mp3_synthesize.  Every refusal
+ * is made before any HIP call, for the whole call: SS_ERR_ARG for a negative count, channels not 1 or 2, history outside [0, 2], skip
+ * outside [0, 576 granules], a negative offset or stride, dst outside [0, n_dst), records past n_rec, a NULL state of a segment with
+ * granules, a NULL destination of a segment that writes; then SS_ERR_CAPACITY for a destination range past h_dst_cap[dst]. */
+int ss_mp3_stream_synthesize(void* stream, const int16_t* d_q, const ss_mp3_granule* d_rec, int64_t n_rec,
+                             const ss_mp3_stream_seg* h_segs, int n_segs, float* const* h_state, float* const* h_dst,
+                             const int64_t* h_dst_cap, int n_dst, int mono, void* d_work, size_t* work_bytes);
 
 /* Binary PCM in and out of the session pools (streamspeech_amd/pcm.py): a service that takes audio off a socket
  * holds 16-bit PCM, float32 or G.711 bytes, not SimulEval's lists of Python floats.  A pool step copies every chunk it was pushed into

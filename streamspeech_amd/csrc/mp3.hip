@@ -13,6 +13,12 @@
 //      windowed sum with D[512].  The slots before the granule are recomputed from (a)'s output instead of carried, so no
 //      granule waits for another: nothing is serial across granules, and a file decodes to the same bits alone or in a batch.
 // A file's first granule sees zero overlap and zero V history.
+//
+// Streams (ss_mp3_stream_synthesize): the same kernel (a) for the new granules of every stream of a step, then a twin of (b) whose
+// granules g-1 and g-2 may lie in the stream's carried state -- the blocks of its last two granules, which is everything a granule
+// reads besides its own block: g-1 for the overlap-add and the 15 slots in front, g-2 for the overlap-add of those slots -- and a
+// third launch that moves the carried blocks on.  Both (b) kernels are one device function over two block sources, so a sample
+// goes through the same operations in the same order and a stream decodes to the bits of the whole file in any chunking.
 #include <math.h>
 #include <string.h>
 
@@ -146,19 +152,37 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int kSlots = 33;                           // 15 slots of the previous granule + 18 of this one
 constexpr int kYld = 33;                             // LDS row stride of the subband samples (bank-conflict padding)
 
-__global__ void __launch_bounds__(kThreads) mp3_synth_kernel(const float* __restrict__ blk, const FileDev* __restrict__ files,
-                                                             const int64_t* __restrict__ gpre, int n_files, int mono,
-                                                             float* __restrict__ out) {
+// Where a granule's IMDCT blocks come from.  back = 0: the granule itself, 1 / 2: the granules before it.
+struct FileBlocks {                                  // a whole file: every granule's block is in blk; the file starts from nothing
+  const float* blk;
+  int64_t rec_offset, gi;
+  int nch;
+  __device__ bool has(int back) const { return gi - back >= 0; }
+  __device__ const float* row(int back, int c) const { return blk + (rec_offset + (gi - back) * nch + c) * 1152; }
+};
+
+struct StreamBlocks {                                // a stream: the new granules in blk, the two before them in the carried state
+  const float* blk;
+  const float* state;                                // [2][nch][1152], older first
+  int64_t rec_offset, gi;                            // gi: index among the new granules
+  int nch, history;                                  // history: granules decoded before the new ones, saturated at 2
+  __device__ bool has(int back) const { return gi - back >= -(int64_t)history; }
+  __device__ const float* row(int back, int c) const {
+    const int64_t h = gi - back;
+    return h >= 0 ? blk + (rec_offset + h * nch + c) * 1152 : state + ((2 + h) * nch + c) * 1152;
+  }
+};
+
+// One granule's synthesis, the body of both synthesis kernels: sample n of the granule goes to out[c * ch_stride + o0 + n] when
+// 0 <= o0 + n < n_out (with mono: the channel mean, to out[o0 + n]).  The arithmetic of a sample depends on the blocks alone.
+template <class Blocks>
+__device__ __forceinline__ void mp3_synth_granule(const Blocks& src, int nch, int mono, float* __restrict__ out, int64_t ch_stride,
+                                                  int64_t o0, int64_t n_out) {
   __shared__ float Y[48 * kYld];                     // subband samples [slot][subband], rows >= 33 zero
   __shared__ float B[32 * 64];                       // N^T: B[k][i] = cos((16 + i)(2k + 1) pi / 64)
   __shared__ float V[kSlots * 64];
   __shared__ float D[512];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t g = blockIdx.x;
-  const int f = find_file(gpre, n_files, g);
-  const FileDev fd = files[f];
-  const int nch = fd.channels;
-  const int64_t gi = g - gpre[f];                    // granule index within the file
 
   for (int n = tid; n < 32 * 64; n += kThreads) {
     const int k = n / 64, i = n % 64;
@@ -176,12 +200,12 @@ __global__ void __launch_bounds__(kThreads) mp3_synth_kernel(const float* __rest
     // -- overlap-add + frequency inversion of slots -15..17
     for (int n = tid; n < kSlots * 32; n += kThreads) {
       const int t = n / 32, sb = n % 32;
-      const int64_t h = t < 15 ? gi - 1 : gi;        // granule the slot belongs to
+      const int back = t < 15 ? 1 : 0;               // granule the slot belongs to: the previous one, or this
       const int s = t < 15 ? t + 3 : t - 15;         // slot within it
       float y = 0.0f;
-      if (h >= 0) {
-        y = blk[(fd.rec_offset + h * nch + c) * 1152 + sb * 36 + s];
-        if (h >= 1) y += blk[(fd.rec_offset + (h - 1) * nch + c) * 1152 + sb * 36 + 18 + s];
+      if (src.has(back)) {
+        y = src.row(back, c)[sb * 36 + s];
+        if (src.has(back + 1)) y += src.row(back + 1, c)[sb * 36 + 18 + s];
         if ((sb & 1) && (s & 1)) y = -y;
       }
       Y[t * kYld + sb] = y;
@@ -223,8 +247,8 @@ __global__ void __launch_bounds__(kThreads) mp3_synth_kernel(const float* __rest
         }
         if (mono) acc[e] += s;
         else {
-          const int64_t o = gi * 576 + n - fd.skip;
-          if (o >= 0 && o < fd.n_out) out[fd.out_offset + (int64_t)c * fd.n_out + o] = s;
+          const int64_t o = o0 + n;
+          if (o >= 0 && o < n_out) out[(int64_t)c * ch_stride + o] = s;
         }
       }
     }
@@ -234,10 +258,47 @@ __global__ void __launch_bounds__(kThreads) mp3_synth_kernel(const float* __rest
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
       const int n = tid + e * kThreads;
-      const int64_t o = gi * 576 + n - fd.skip;
-      if (n < 576 && o >= 0 && o < fd.n_out) out[fd.out_offset + o] = acc[e] * inv;
+      const int64_t o = o0 + n;
+      if (n < 576 && o >= 0 && o < n_out) out[o] = acc[e] * inv;
     }
   }
+}
+
+__global__ void __launch_bounds__(kThreads) mp3_synth_kernel(const float* __restrict__ blk, const FileDev* __restrict__ files,
+                                                             const int64_t* __restrict__ gpre, int n_files, int mono,
+                                                             float* __restrict__ out) {
+  const int64_t g = blockIdx.x;
+  const int f = find_file(gpre, n_files, g);
+  const FileDev fd = files[f];
+  const int64_t gi = g - gpre[f];                    // granule index within the file
+  const FileBlocks src{blk, fd.rec_offset, gi, fd.channels};
+  mp3_synth_granule(src, fd.channels, mono, out + fd.out_offset, (int64_t)fd.n_out, gi * 576 - fd.skip, (int64_t)fd.n_out);
+}
+
+// ---- streams: the same two stages against two granules of carried blocks per stream -----------------------------------------------
+struct SegDev { float* dst; float* state; int64_t rec_offset, ch_stride; int32_t granules, channels, skip, history; };
+static_assert(sizeof(SegDev) == 48, "segment table layout");
+
+__global__ void __launch_bounds__(kThreads) mp3_stream_synth_kernel(const float* __restrict__ blk, const SegDev* __restrict__ segs,
+                                                                    const int64_t* __restrict__ gpre, int n_segs, int mono) {
+  const int64_t g = blockIdx.x;
+  const int f = find_file(gpre, n_segs, g);
+  const SegDev sd = segs[f];
+  const int64_t gi = g - gpre[f];                    // index among the segment's new granules
+  const StreamBlocks src{blk, sd.state, sd.rec_offset, gi, sd.channels, sd.history};
+  mp3_synth_granule(src, sd.channels, mono, sd.dst, sd.ch_stride, gi * 576 - sd.skip, (int64_t)sd.granules * 576 - sd.skip);
+}
+
+// After the synthesis: each stream's state becomes the blocks of its last two granules.  One workgroup column per segment; an
+// element is read and written by one thread only, so the move {old last -> older, new -> last} of a single new granule is in place.
+__global__ void __launch_bounds__(kThreads) mp3_stream_carry_kernel(const float* __restrict__ blk, const SegDev* __restrict__ segs) {
+  const SegDev sd = segs[blockIdx.y];
+  const int n = sd.channels * 1152;                  // floats of one granule's blocks (both channels)
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (sd.granules <= 0 || i >= n) return;
+  const float* last = blk + (sd.rec_offset + (int64_t)(sd.granules - 1) * sd.channels) * 1152;
+  sd.state[i] = sd.granules >= 2 ? last[i - n] : sd.state[n + i];
+  sd.state[n + i] = last[i];
 }
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -283,6 +344,70 @@ extern "C" int ss_mp3_synthesize(void* stream, const int16_t* d_q, const ss_mp3_
   hipLaunchKernelGGL(mp3_imdct_kernel, dim3((unsigned)G), dim3(kThreads), 0, st, d_q, d_rec, files, dg, n_files, blk);
   SS_LAUNCH_CHECK();
   hipLaunchKernelGGL(mp3_synth_kernel, dim3((unsigned)G), dim3(kThreads), 0, st, blk, files, dg, n_files, mono ? 1 : 0, d_out);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+extern "C" int ss_mp3_stream_synthesize(void* stream, const int16_t* d_q, const ss_mp3_granule* d_rec, int64_t n_rec,
+                                        const ss_mp3_stream_seg* h_segs, int n_segs, float* const* h_state, float* const* h_dst,
+                                        const int64_t* h_dst_cap, int n_dst, int mono, void* d_work, size_t* work_bytes) {
+  if (!work_bytes || n_segs < 0 || n_rec < 0 || n_dst < 0 || (n_segs > 0 && (!h_segs || !h_state || !h_dst || !h_dst_cap)))
+    return SS_ERR_ARG;
+  // every refusal before any HIP call: arguments first, capacities second
+  int64_t G = 0;
+  std::vector<int64_t> gpre(n_segs + 1);
+  for (int i = 0; i < n_segs; ++i) {
+    const ss_mp3_stream_seg& S = h_segs[i];
+    if (S.channels < 1 || S.channels > 2 || S.granules < 0 || S.history < 0 || S.history > 2 || S.rec_offset < 0 || S.dst_offset < 0 ||
+        S.ch_stride < 0 || S.dst < 0 || S.dst >= n_dst || S.skip < 0 || (int64_t)S.skip > (int64_t)S.granules * 576)
+      return SS_ERR_ARG;
+    if (S.rec_offset + (int64_t)S.granules * S.channels > n_rec) return SS_ERR_ARG;
+    if (S.granules > 0 && !h_state[i]) return SS_ERR_ARG;
+    if ((int64_t)S.granules * 576 > S.skip && !h_dst[S.dst]) return SS_ERR_ARG;               // something is written
+    if (!mono && S.channels == 2 && S.ch_stride < (int64_t)S.granules * 576 - S.skip) return SS_ERR_ARG;   // the planes would overlap
+    gpre[i] = G;
+    G += S.granules;
+  }
+  gpre[n_segs] = G;
+  if (G > 0x7fffffff) return SS_ERR_ARG;
+  for (int i = 0; i < n_segs; ++i) {
+    const ss_mp3_stream_seg& S = h_segs[i];
+    const int64_t n_out = (int64_t)S.granules * 576 - S.skip;
+    const int64_t planes = mono ? 0 : S.channels - 1;
+    if (n_out > 0 && S.dst_offset + planes * S.ch_stride + n_out > h_dst_cap[S.dst]) return SS_ERR_CAPACITY;
+  }
+  const size_t nt = (size_t)(n_segs > 0 ? n_segs : 1);
+  const size_t files_bytes = align256(sizeof(FileDev) * nt), segs_bytes = align256(sizeof(SegDev) * nt);
+  const size_t gpre_bytes = align256(sizeof(int64_t) * (size_t)(n_segs + 1));
+  const size_t need = files_bytes + segs_bytes + gpre_bytes + (size_t)n_rec * 1152 * sizeof(float);
+  if (!d_work) { *work_bytes = need; return SS_OK; }
+  if (*work_bytes < need) return SS_ERR_CAPACITY;
+  if (G == 0) return SS_OK;
+  if (!d_q || !d_rec) return SS_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<uint8_t> stage(files_bytes + segs_bytes + gpre_bytes, 0);
+  FileDev* hf = (FileDev*)stage.data();
+  SegDev* hs = (SegDev*)(stage.data() + files_bytes);
+  for (int i = 0; i < n_segs; ++i) {
+    const ss_mp3_stream_seg& S = h_segs[i];
+    hf[i] = FileDev{S.rec_offset, 0, S.granules, S.channels, 0, 0};                          // what the IMDCT kernel reads of a file
+    hs[i] = SegDev{h_dst[S.dst] ? h_dst[S.dst] + S.dst_offset : nullptr, h_state[i], S.rec_offset, S.ch_stride, S.granules,
+                   S.channels, S.skip, S.history};
+  }
+  memcpy(stage.data() + files_bytes + segs_bytes, gpre.data(), sizeof(int64_t) * (size_t)(n_segs + 1));
+  uint8_t* w = (uint8_t*)d_work;
+  // pageable source: the runtime has staged it when the call returns, so `stage` may go out of scope
+  SS_HIP_CHECK(hipMemcpyAsync(w, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
+  const FileDev* files = (const FileDev*)w;
+  const SegDev* segs = (const SegDev*)(w + files_bytes);
+  const int64_t* dg = (const int64_t*)(w + files_bytes + segs_bytes);
+  float* blk = (float*)(w + files_bytes + segs_bytes + gpre_bytes);
+  hipLaunchKernelGGL(mp3_imdct_kernel, dim3((unsigned)G), dim3(kThreads), 0, st, d_q, d_rec, files, dg, n_segs, blk);
+  SS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mp3_stream_synth_kernel, dim3((unsigned)G), dim3(kThreads), 0, st, blk, segs, dg, n_segs, mono ? 1 : 0);
+  SS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mp3_stream_carry_kernel, dim3((2 * 1152 + kThreads - 1) / kThreads, (unsigned)n_segs), dim3(kThreads), 0, st, blk,
+                     segs);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }

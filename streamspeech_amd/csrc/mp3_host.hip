@@ -112,72 +112,44 @@ int parse_header(const uint8_t* b, Hdr& h) {
 
 bool agrees(const Hdr& a, const Hdr& b) { return a.ver == b.ver && a.sri == b.sri && a.nch == b.nch; }
 
-// ---- container scan -------------------------------------------------------------------------------------------------------------
+// ---- the resumable core -----------------------------------------------------------------------------------------------------
+// Everything a stream carries between pushes besides its unconsumed bytes; a plain value, so a push works on a copy and commits
+// it only when it succeeds.  The whole-file calls run the same code in one pass over the file with finished = true.
+constexpr int kMaxFrame = 1441;                      // 320 kbit/s at 32 kHz, or 160 kbit/s at 8 kHz, with padding
+constexpr int kReservoir = 511;                      // main_data_begin is 9 bits: nothing further back is ever read
+
+struct Core {
+  int64_t id3_skip = 0;           // bytes of an ID3v2 tag still to pass over
+  bool tags_done = false;         // the ID3v2 tags at the start are behind us
+  bool at_audio_start = true;     // the next header examined is the first one after the tags
+  bool have_first = false;
+  bool finished = false;
+  Hdr first{};
+  int delay = -1, padding = -1;
+  int join = 0;
+  int res_len = 0;                // bytes of main data kept, the last min(received, 511)
+  uint8_t res[kReservoir];
+  uint8_t sf_prev[2][22];
+  int64_t frames = 0, granules = 0, skipped = 0, bytes_in = 0;
+  Core() { memset(res, 0, sizeof(res)); memset(sf_prev, 0, sizeof(sf_prev)); }
+};
+
+// where the frames of a run go: a scan keeps positions and headers, a decode writes records
 struct Scan {
   std::vector<int64_t> pos;       // audio frames
   std::vector<Hdr> hdr;
   int delay = -1, padding = -1;
 };
 
-uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+struct Out {
+  Scan* scan = nullptr;           // non-NULL: collect, do not decode
+  int64_t cap = 0, n_rec = 0;
+  int16_t* q = nullptr;
+  ss_mp3_granule* rec = nullptr;
+  int32_t* bits = nullptr;
+};
 
-int scan(const uint8_t* d, size_t n_bytes, Scan& s) {
-  int64_t n = (int64_t)n_bytes, pos = 0;
-  while (pos + 10 <= n && d[pos] == 'I' && d[pos + 1] == 'D' && d[pos + 2] == '3') {        // ID3v2 (+ footer)
-    if ((d[pos + 6] | d[pos + 7] | d[pos + 8] | d[pos + 9]) & 0x80) return SS_ERR_BITSTREAM;
-    int64_t sz = ((int64_t)d[pos + 6] << 21) | ((int64_t)d[pos + 7] << 14) | ((int64_t)d[pos + 8] << 7) | d[pos + 9];
-    pos += 10 + sz + ((d[pos + 5] & 0x10) ? 10 : 0);
-  }
-  int64_t end = n;
-  if (end - pos >= 128 && memcmp(d + end - 128, "TAG", 3) == 0) end -= 128;                 // ID3v1
-  if (end - pos >= 32 && memcmp(d + end - 32, "APETAGEX", 8) == 0) {                        // APEv2 footer
-    const uint8_t* f = d + end - 32;
-    int64_t sz = (int64_t)f[12] | ((int64_t)f[13] << 8) | ((int64_t)f[14] << 16) | ((int64_t)f[15] << 24);
-    bool has_hdr = (f[23] & 0x80) != 0;
-    int64_t cut = sz + (has_hdr ? 32 : 0);
-    if (cut >= 32 && cut <= end - pos) end -= cut;
-  }
-  const int64_t audio_start = pos;
-  bool have_first = false;
-  Hdr first{};
-  while (pos + 4 <= end) {
-    Hdr h;
-    int r = parse_header(d + pos, h);
-    if (pos == audio_start && (r == H_RESERVED || r == H_UNSUPPORTED)) return SS_ERR_UNSUPPORTED;
-    if (r != H_OK || (have_first && !agrees(h, first))) { ++pos; continue; }
-    if (pos + h.len > end) break;                                                            // truncated last frame
-    bool ok = pos + h.len + 4 > end;                                                         // last frame (or < 4 bytes of tail)
-    if (!ok) {
-      Hdr nx;
-      ok = parse_header(d + pos + h.len, nx) == H_OK && agrees(h, nx);
-    }
-    if (!ok) { ++pos; continue; }
-    const int crc = h.prot ? 0 : 2;
-    if (4 + crc + h.side_len > h.len) { ++pos; continue; }
-    if (h.mode == 1 && (h.modext & 1)) return SS_ERR_UNSUPPORTED;                           // intensity stereo
-    if (!have_first) {
-      have_first = true;
-      first = h;
-      const uint8_t* x = d + pos + 4 + crc + h.side_len;                                     // Xing / Info frame?
-      int64_t room = h.len - (4 + crc + h.side_len);
-      if (room >= 8 && (memcmp(x, "Xing", 4) == 0 || memcmp(x, "Info", 4) == 0)) {
-        uint32_t flags = be32(x + 4);
-        int64_t o = 8 + ((flags & 1) ? 4 : 0) + ((flags & 2) ? 4 : 0) + ((flags & 4) ? 100 : 0) + ((flags & 8) ? 4 : 0);
-        if (o + 24 <= room && (memcmp(x + o, "LAME", 4) == 0 || memcmp(x + o, "Lavc", 4) == 0 || memcmp(x + o, "Lavf", 4) == 0)) {
-          const uint8_t* q = x + o + 21;
-          s.delay = (q[0] << 4) | (q[1] >> 4);
-          s.padding = ((q[1] & 15) << 8) | q[2];
-        }
-        pos += h.len;
-        continue;
-      }
-    }
-    s.pos.push_back(pos);
-    s.hdr.push_back(h);
-    pos += h.len;
-  }
-  return SS_OK;
-}
+uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 
 void fill_info(const Scan& s, ss_mp3_info* info) {
   memset(info, 0, sizeof(*info));
@@ -308,73 +280,296 @@ int decode_granule(Bits& br, int64_t end, const GrInfo& g, const Hdr& h, int gr,
   return SS_OK;
 }
 
-int unpack(const uint8_t* d, const Scan& s, int64_t cap, int16_t* h_q, ss_mp3_granule* h_rec, int32_t* h_bits) {
+// One accepted audio frame `fr` (h.len bytes): side info, reservoir, both granules -> records at o.n_rec.
+int decode_frame(Core& c, const Hdr& h, const uint8_t* fr, Out& o) {
+  const int crc = h.prot ? 0 : 2;
+  Bits si(fr + 4 + crc, h.side_len);
+  const bool m1 = h.ver == 3;
+  const int mdb = (int)si.get(m1 ? 9 : 8);
+  si.get(m1 ? (h.nch == 1 ? 5 : 3) : (h.nch == 1 ? 1 : 2));
+  int scfsi[2][4] = {{0}};
+  if (m1)
+    for (int ch = 0; ch < h.nch; ++ch)
+      for (int k = 0; k < 4; ++k) scfsi[ch][k] = (int)si.get(1);
+  GrInfo gi[2][2];
+  for (int gr = 0; gr < h.ngr; ++gr)
+    for (int ch = 0; ch < h.nch; ++ch) {
+      GrInfo& g = gi[gr][ch];
+      g.part2_3 = (int)si.get(12); g.big_values = (int)si.get(9); g.global_gain = (int)si.get(8);
+      g.sfc = (int)si.get(m1 ? 4 : 9); g.ws = (int)si.get(1);
+      if (g.ws) {
+        g.block_type = (int)si.get(2); g.mixed = (int)si.get(1);
+        g.table[0] = (int)si.get(5); g.table[1] = (int)si.get(5); g.table[2] = 0;
+        for (int w = 0; w < 3; ++w) g.sbg[w] = (int)si.get(3);
+        g.r0 = g.r1 = 0;
+        if (g.block_type == 0) return SS_ERR_BITSTREAM;
+        if (g.mixed && h.sr_index == 8) return SS_ERR_UNSUPPORTED;    // mixed blocks at 8 kHz: long / short split undefined
+      } else {
+        g.block_type = 0; g.mixed = 0;
+        for (int k = 0; k < 3; ++k) g.table[k] = (int)si.get(5);
+        g.r0 = (int)si.get(4); g.r1 = (int)si.get(3);
+        g.sbg[0] = g.sbg[1] = g.sbg[2] = 0;
+      }
+      g.preflag = m1 ? (int)si.get(1) : 0;
+      g.sfscale = (int)si.get(1); g.c1table = (int)si.get(1);
+      if (g.big_values > 288) return SS_ERR_BITSTREAM;
+    }
+  // main data of this frame joins the reservoir; this frame's data starts main_data_begin bytes before it.  Only the last 511
+  // bytes of the earlier main data can be pointed at, so that is all the reservoir keeps.
+  const int md_off = 4 + crc + h.side_len, md_len = h.len - md_off;
+  uint8_t md[kReservoir + kMaxFrame];
+  memcpy(md, c.res, (size_t)c.res_len);
+  memcpy(md + c.res_len, fr + md_off, (size_t)md_len);
+  const int total = c.res_len + md_len;
+  const int start = c.res_len - mdb;
+  const bool decodable = start >= 0;
+  if (!decodable && !c.join) return SS_ERR_BITSTREAM;
+  if (decodable) {
+    const int nrec = h.ngr * h.nch;
+    if (o.cap - o.n_rec < nrec) return SS_ERR_CAPACITY;
+    Bits br(md, total);
+    br.pos = (int64_t)start * 8;
+    const bool ms = h.mode == 1 && (h.modext & 2);
+    int64_t rec = o.n_rec;
+    for (int gr = 0; gr < h.ngr; ++gr)
+      for (int ch = 0; ch < h.nch; ++ch, ++rec) {
+        const int64_t gstart = br.pos, gend = gstart + gi[gr][ch].part2_3;
+        if (gend > br.nbits) return SS_ERR_BITSTREAM;
+        int rc = decode_granule(br, gend, gi[gr][ch], h, gr, ch, scfsi[ch], c.sf_prev[ch], o.q + rec * 576, o.rec + rec);
+        if (rc != SS_OK) return rc;
+        o.rec[rec].ms = ms ? 1 : 0;
+        if (o.bits) o.bits[rec] = (int32_t)(br.pos - gstart);
+        br.pos = gend;
+      }
+    o.n_rec = rec;
+    ++c.frames;
+    c.granules += h.ngr;
+  } else {
+    ++c.skipped;                                     // joined mid-stream: its main data began before we listened
+  }
+  const int keep = total < kReservoir ? total : kReservoir;
+  memmove(c.res, md + total - keep, (size_t)keep);
+  c.res_len = keep;
+  return SS_OK;
+}
+
+// Advance over d[0, n): the bytes not consumed yet followed by the new ones.  *used = bytes that need not be seen again; the rest
+// (fewer than one frame + 4) is what the caller keeps for the next run.  With `finished` nothing more will come.
+int run(Core& c, const uint8_t* d, int64_t n, bool finished, Out& o, int64_t* used) {
+  int64_t pos = 0;
+  *used = 0;
+  while (!c.tags_done) {                                                                      // ID3v2 (+ footer)
+    if (c.id3_skip > 0) {
+      const int64_t take = c.id3_skip < n - pos ? c.id3_skip : n - pos;
+      pos += take;
+      c.id3_skip -= take;
+      if (c.id3_skip > 0) { *used = pos; return SS_OK; }
+    }
+    if (n - pos < 10) {
+      if (!finished) { *used = pos; return SS_OK; }
+      c.tags_done = true;
+    } else if (d[pos] == 'I' && d[pos + 1] == 'D' && d[pos + 2] == '3') {
+      if ((d[pos + 6] | d[pos + 7] | d[pos + 8] | d[pos + 9]) & 0x80) return SS_ERR_BITSTREAM;
+      int64_t sz = ((int64_t)d[pos + 6] << 21) | ((int64_t)d[pos + 7] << 14) | ((int64_t)d[pos + 8] << 7) | d[pos + 9];
+      c.id3_skip = 10 + sz + ((d[pos + 5] & 0x10) ? 10 : 0);
+    } else {
+      c.tags_done = true;
+    }
+  }
+  while (pos + 4 <= n) {
+    Hdr h;
+    int r = parse_header(d + pos, h);
+    if (c.at_audio_start) {
+      c.at_audio_start = false;
+      if (r == H_RESERVED || r == H_UNSUPPORTED) return SS_ERR_UNSUPPORTED;
+    }
+    if (r != H_OK || (c.have_first && !agrees(h, c.first))) { ++pos; continue; }
+    if (pos + h.len > n) {                                                                   // truncated last frame, or not all here yet
+      if (finished) pos = n;
+      break;
+    }
+    bool ok = pos + h.len + 4 > n;                                                           // last frame (or < 4 bytes of tail)
+    if (ok && !finished) break;                                                              // the look-ahead has not arrived
+    if (!ok) {
+      Hdr nx;
+      ok = parse_header(d + pos + h.len, nx) == H_OK && agrees(h, nx);
+    }
+    if (!ok) { ++pos; continue; }
+    const int crc = h.prot ? 0 : 2;
+    if (4 + crc + h.side_len > h.len) { ++pos; continue; }
+    if (h.mode == 1 && (h.modext & 1)) return SS_ERR_UNSUPPORTED;                           // intensity stereo
+    if (!c.have_first) {
+      c.have_first = true;
+      c.first = h;
+      const uint8_t* x = d + pos + 4 + crc + h.side_len;                                     // Xing / Info frame?
+      int64_t room = h.len - (4 + crc + h.side_len);
+      if (room >= 8 && (memcmp(x, "Xing", 4) == 0 || memcmp(x, "Info", 4) == 0)) {
+        uint32_t flags = be32(x + 4);
+        int64_t t = 8 + ((flags & 1) ? 4 : 0) + ((flags & 2) ? 4 : 0) + ((flags & 4) ? 100 : 0) + ((flags & 8) ? 4 : 0);
+        if (t + 24 <= room && (memcmp(x + t, "LAME", 4) == 0 || memcmp(x + t, "Lavc", 4) == 0 || memcmp(x + t, "Lavf", 4) == 0)) {
+          const uint8_t* q = x + t + 21;
+          c.delay = (q[0] << 4) | (q[1] >> 4);
+          c.padding = ((q[1] & 15) << 8) | q[2];
+        }
+        pos += h.len;
+        continue;
+      }
+    }
+    if (o.scan) {
+      o.scan->pos.push_back(pos);
+      o.scan->hdr.push_back(h);
+    } else {
+      int rc = decode_frame(c, h, d + pos, o);
+      if (rc != SS_OK) return rc;
+    }
+    pos += h.len;
+  }
+  if (finished) { c.finished = true; pos = n; }
+  *used = pos;
+  return SS_OK;
+}
+
+// ---- whole files: the trailing tags are cut first (they need the end of the data), then one finished run -------------------------
+int64_t audio_end(const uint8_t* d, size_t n_bytes) {
+  int64_t n = (int64_t)n_bytes, pos = 0;
+  while (pos + 10 <= n && d[pos] == 'I' && d[pos + 1] == 'D' && d[pos + 2] == '3') {        // where run() will start the audio
+    if ((d[pos + 6] | d[pos + 7] | d[pos + 8] | d[pos + 9]) & 0x80) break;                   // run() refuses it
+    int64_t sz = ((int64_t)d[pos + 6] << 21) | ((int64_t)d[pos + 7] << 14) | ((int64_t)d[pos + 8] << 7) | d[pos + 9];
+    pos += 10 + sz + ((d[pos + 5] & 0x10) ? 10 : 0);
+  }
+  int64_t end = n;
+  if (end - pos >= 128 && memcmp(d + end - 128, "TAG", 3) == 0) end -= 128;                 // ID3v1
+  if (end - pos >= 32 && memcmp(d + end - 32, "APETAGEX", 8) == 0) {                        // APEv2 footer
+    const uint8_t* f = d + end - 32;
+    int64_t sz = (int64_t)f[12] | ((int64_t)f[13] << 8) | ((int64_t)f[14] << 16) | ((int64_t)f[15] << 24);
+    bool has_hdr = (f[23] & 0x80) != 0;
+    int64_t cut = sz + (has_hdr ? 32 : 0);
+    if (cut >= 32 && cut <= end - pos) end -= cut;
+  }
+  return end;
+}
+
+int scan(const uint8_t* d, size_t n_bytes, Scan& s) {
+  Core c;
+  Out o;
+  o.scan = &s;
+  int64_t used;
+  int rc = run(c, d, audio_end(d, n_bytes), true, o, &used);
+  s.delay = c.delay;
+  s.padding = c.padding;
+  return rc;
+}
+
+int unpack(const uint8_t* d, size_t n_bytes, const Scan& s, int64_t cap, int16_t* h_q, ss_mp3_granule* h_rec, int32_t* h_bits) {
   if (s.hdr.empty()) return SS_OK;
   const Hdr& h0 = s.hdr[0];
   const int64_t need = (int64_t)s.hdr.size() * h0.ngr * h0.nch;
   if (cap < need) return SS_ERR_CAPACITY;
-  std::vector<uint8_t> res;                          // main data of all frames so far (the bit reservoir)
-  uint8_t sf_prev[2][22];
-  memset(sf_prev, 0, sizeof(sf_prev));
-  int64_t rec = 0;
-  for (size_t f = 0; f < s.pos.size(); ++f) {
-    const Hdr& h = s.hdr[f];
-    const uint8_t* fr = d + s.pos[f];
-    const int crc = h.prot ? 0 : 2;
-    Bits si(fr + 4 + crc, h.side_len);
-    const bool m1 = h.ver == 3;
-    const int mdb = (int)si.get(m1 ? 9 : 8);
-    si.get(m1 ? (h.nch == 1 ? 5 : 3) : (h.nch == 1 ? 1 : 2));
-    int scfsi[2][4] = {{0}};
-    if (m1)
-      for (int c = 0; c < h.nch; ++c)
-        for (int k = 0; k < 4; ++k) scfsi[c][k] = (int)si.get(1);
-    GrInfo gi[2][2];
-    for (int gr = 0; gr < h.ngr; ++gr)
-      for (int c = 0; c < h.nch; ++c) {
-        GrInfo& g = gi[gr][c];
-        g.part2_3 = (int)si.get(12); g.big_values = (int)si.get(9); g.global_gain = (int)si.get(8);
-        g.sfc = (int)si.get(m1 ? 4 : 9); g.ws = (int)si.get(1);
-        if (g.ws) {
-          g.block_type = (int)si.get(2); g.mixed = (int)si.get(1);
-          g.table[0] = (int)si.get(5); g.table[1] = (int)si.get(5); g.table[2] = 0;
-          for (int w = 0; w < 3; ++w) g.sbg[w] = (int)si.get(3);
-          g.r0 = g.r1 = 0;
-          if (g.block_type == 0) return SS_ERR_BITSTREAM;
-          if (g.mixed && h.sr_index == 8) return SS_ERR_UNSUPPORTED;    // mixed blocks at 8 kHz: long / short split undefined
-        } else {
-          g.block_type = 0; g.mixed = 0;
-          for (int k = 0; k < 3; ++k) g.table[k] = (int)si.get(5);
-          g.r0 = (int)si.get(4); g.r1 = (int)si.get(3);
-          g.sbg[0] = g.sbg[1] = g.sbg[2] = 0;
-        }
-        g.preflag = m1 ? (int)si.get(1) : 0;
-        g.sfscale = (int)si.get(1); g.c1table = (int)si.get(1);
-        if (g.big_values > 288) return SS_ERR_BITSTREAM;
-      }
-    // main data of this frame joins the reservoir; this frame's data starts main_data_begin bytes before it
-    const int64_t md_off = 4 + crc + h.side_len;
-    const int64_t start = (int64_t)res.size() - mdb;
-    if (start < 0) return SS_ERR_BITSTREAM;
-    res.insert(res.end(), fr + md_off, fr + h.len);
-    Bits br(res.data(), (int64_t)res.size());
-    br.pos = start * 8;
-    const bool ms = h.mode == 1 && (h.modext & 2);
-    for (int gr = 0; gr < h.ngr; ++gr)
-      for (int c = 0; c < h.nch; ++c, ++rec) {
-        const int64_t gstart = br.pos, gend = gstart + gi[gr][c].part2_3;
-        if (gend > br.nbits) return SS_ERR_BITSTREAM;
-        int rc = decode_granule(br, gend, gi[gr][c], h, gr, c, scfsi[c], sf_prev[c], h_q + rec * 576, h_rec + rec);
-        if (rc != SS_OK) return rc;
-        h_rec[rec].ms = ms ? 1 : 0;
-        if (h_bits) h_bits[rec] = (int32_t)(br.pos - gstart);
-        br.pos = gend;
-      }
+  Core c;
+  Out o;
+  o.cap = cap; o.q = h_q; o.rec = h_rec; o.bits = h_bits;
+  int64_t used;
+  return run(c, d, audio_end(d, n_bytes), true, o, &used);
+}
+
+void stream_info(const Core& c, int64_t buffered, ss_mp3_stream_info* info) {
+  memset(info, 0, sizeof(*info));
+  info->delay = c.delay;
+  info->padding = c.padding;
+  info->buffered = (int32_t)buffered;
+  info->finished = c.finished ? 1 : 0;
+  info->frames = c.frames;
+  info->granules = c.granules;
+  info->skipped_frames = c.skipped;
+  info->bytes_in = c.bytes_in;
+  if (!c.have_first) return;
+  const Hdr& h = c.first;
+  info->version = h.ver == 3 ? 1 : h.ver == 2 ? 2 : 25;
+  info->sample_rate = mp3t::kSampleRates[h.sr_index];
+  info->sr_index = h.sr_index;
+  info->channels = h.nch;
+  if (c.delay >= 0) {
+    info->skip = c.delay + 529;
+    info->hold = c.padding - 529 > 0 ? c.padding - 529 : 0;
   }
-  return SS_OK;
+  const int64_t left = c.granules * 576 - info->skip - info->hold;
+  info->samples = left > 0 ? left : 0;
 }
 
 }  // namespace
+
+struct ss_mp3_stream {
+  Core core;
+  std::vector<uint8_t> carry;     // unconsumed bytes: fewer than one frame + 4
+};
+
+extern "C" int ss_mp3_stream_create(int join, ss_mp3_stream** out) {
+  if (!out) return SS_ERR_ARG;
+  ss_mp3_stream* s = new ss_mp3_stream();
+  s->core.join = join ? 1 : 0;
+  *out = s;
+  return SS_OK;
+}
+
+extern "C" void ss_mp3_stream_destroy(ss_mp3_stream* s) { delete s; }
+
+extern "C" int ss_mp3_stream_reset(ss_mp3_stream* s) {
+  if (!s) return SS_ERR_ARG;
+  const int join = s->core.join;
+  s->core = Core();
+  s->core.join = join;
+  s->carry.clear();
+  return SS_OK;
+}
+
+extern "C" int64_t ss_mp3_stream_bound(const ss_mp3_stream* s, size_t n_bytes) {
+  if (!s) return 0;
+  return 2 * (((int64_t)s->carry.size() + (int64_t)n_bytes) / 24 + 1);
+}
+
+extern "C" int ss_mp3_stream_query(const ss_mp3_stream* s, ss_mp3_stream_info* h_info) {
+  if (!s || !h_info) return SS_ERR_ARG;
+  stream_info(s->core, (int64_t)s->carry.size(), h_info);
+  return SS_OK;
+}
+
+extern "C" int ss_mp3_stream_copy(ss_mp3_stream* dst, const ss_mp3_stream* src) {
+  if (!dst || !src) return SS_ERR_ARG;
+  if (dst != src) *dst = *src;
+  return SS_OK;
+}
+
+extern "C" int ss_mp3_stream_push(ss_mp3_stream* s, const uint8_t* h_data, size_t n_bytes, int finished, int64_t cap, int16_t* h_q,
+                                  ss_mp3_granule* h_rec, int32_t* h_bits, int64_t* n_rec, ss_mp3_stream_info* h_info) {
+  if (!s || !n_rec || cap < 0 || (n_bytes > 0 && !h_data) || (cap > 0 && (!h_q || !h_rec))) return SS_ERR_ARG;
+  *n_rec = 0;
+  if (h_info) stream_info(s->core, (int64_t)s->carry.size(), h_info);
+  if (s->core.finished) return SS_ERR_ARG;
+  // the run sees the kept bytes followed by the chunk; state and bytes are committed only when it succeeds
+  const uint8_t* d = h_data;
+  int64_t n = (int64_t)n_bytes;
+  std::vector<uint8_t> joined;
+  if (!s->carry.empty()) {
+    joined.reserve(s->carry.size() + n_bytes);
+    joined.insert(joined.end(), s->carry.begin(), s->carry.end());
+    if (n_bytes) joined.insert(joined.end(), h_data, h_data + n_bytes);
+    d = joined.data();
+    n = (int64_t)joined.size();
+  }
+  Core c = s->core;
+  Out o;
+  o.cap = cap; o.q = h_q; o.rec = h_rec; o.bits = h_bits;
+  int64_t used = 0;
+  int rc = run(c, d, n, finished != 0, o, &used);
+  if (rc != SS_OK) return rc;
+  c.bytes_in += (int64_t)n_bytes;
+  s->core = c;
+  std::vector<uint8_t> rest(d + used, d + n);
+  s->carry.swap(rest);
+  *n_rec = o.n_rec;
+  if (h_info) stream_info(s->core, (int64_t)s->carry.size(), h_info);
+  return SS_OK;
+}
 
 extern "C" int ss_mp3_probe(const uint8_t* h_data, size_t n_bytes, ss_mp3_info* h_info) {
   if (!h_data || !h_info) return SS_ERR_ARG;
@@ -393,5 +588,5 @@ extern "C" int ss_mp3_unpack(const uint8_t* h_data, size_t n_bytes, int64_t cap,
   int rc = scan(h_data, n_bytes, s);
   if (rc != SS_OK) return rc;
   if (s.pos.empty()) return SS_ERR_BITSTREAM;
-  return unpack(h_data, s, cap, h_q, h_rec, h_bits);
+  return unpack(h_data, n_bytes, s, cap, h_q, h_rec, h_bits);
 }

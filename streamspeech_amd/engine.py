@@ -190,6 +190,12 @@ class BatchMixin:
         from . import pcm
         pcm.scatter(self.lib, _stream(), stage, stage_bytes, segs, dsts)
 
+    def mp3_stream_decode(self, arena, items):
+        """The new granules of every MP3-fed session of a step (mp3.decode_stream_batch names the item tuple): one upload of the
+        arena, one ss_mp3_stream_synthesize, mono.  -> (granule-channels decoded, bytes uploaded)."""
+        from . import mp3
+        return mp3.decode_stream_batch(arena, items, True, self.lib)
+
     def pcm_pack_s16(self, src: torch.Tensor, out: torch.Tensor):
         """float32 device samples -> 16-bit PCM on the device, one launch (ss_pcm_pack_s16)."""
         from . import pcm

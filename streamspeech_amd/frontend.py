@@ -232,17 +232,19 @@ class OnlineFeatureExtractor:
         return int(num_frames), effective
 
     # ---- the PCM route: raw chunks decoded on the device (streamspeech_amd/pcm.py), a sample COUNTER instead of a sample list ----
-    def pcm_reserve(self, frames: int):
+    def pcm_reserve(self, frames: int, keep: int = 0):
         """Room for `frames` more samples in the device history (grown by doubling with a device copy, as stage() grows it) -> (the
         history tensor, the offset the new samples go to).  The caller has them written there (one ss_pcm_scatter for all sessions
-        of a pool step) and then calls pcm_commit(frames)."""
+        of a pool step) and then calls pcm_commit(frames).  keep: samples already written past n_pcm and not committed yet (what a
+        gapless MP3 stream holds back); they survive a growth, and the caller writes behind them."""
         if getattr(self, "_np", None) is None:
             self.clear_cache()
-        n = self.n_pcm + int(frames)
+        have = self.n_pcm + int(keep)
+        n = have + int(frames)
         if self._dev is None or self._dev.numel() < n:
             buf = torch.empty((max(2 * n, 1 << 16),), dtype=torch.float32, device=self.engine.device)
-            if self._dev is not None and self.n_pcm:
-                buf[: self.n_pcm] = self._dev[: self.n_pcm]
+            if self._dev is not None and have:
+                buf[:have] = self._dev[:have]
             self._dev = buf
         return self._dev, self.n_pcm
 

@@ -85,6 +85,15 @@ SIGNATURES = {
     "ss_mp3_probe": (_i, [_vp, C.c_size_t, _vp]),
     "ss_mp3_unpack": (_i, [_vp, C.c_size_t, _i64, _vp, _vp, _vp]),
     "ss_mp3_synthesize": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp, C.POINTER(C.c_size_t)]),
+    "ss_mp3_stream_create": (_i, [_i, C.POINTER(_vp)]),
+    "ss_mp3_stream_destroy": (None, [_vp]),
+    "ss_mp3_stream_reset": (_i, [_vp]),
+    "ss_mp3_stream_bound": (_i64, [_vp, C.c_size_t]),
+    "ss_mp3_stream_push": (_i, [_vp, _vp, C.c_size_t, _i, _i64, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    "ss_mp3_stream_query": (_i, [_vp, _vp]),
+    "ss_mp3_stream_copy": (_i, [_vp, _vp]),
+    "ss_mp3_stream_synthesize": (_i, [_vp, _vp, _vp, _i64, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), _i, _i, _vp,
+                                      C.POINTER(C.c_size_t)]),
     "ss_pcm_scatter": (_i, [_vp, _vp, _i64, _vp, _i, C.POINTER(_vp), C.POINTER(_i64), _i]),
     "ss_pcm_pack_s16": (_i, [_vp, _vp, _i64, _vp]),
     "ss_pcm_decode_host": (_i, [_vp, _i, _i, _i64, _vp]),

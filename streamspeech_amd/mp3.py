@@ -148,3 +148,227 @@ def _decode_group(blobs, names, dev, mono, threads):
     # work ordered after them on this stream, which is where they were used
     return res
 
+
+
+# ---- streams: the same decoder, resumable (ss_mp3_stream_*) ------------------------------------------------------
+class Mp3StreamInfo(C.Structure):
+    _fields_ = [("version", C.c_int32), ("sample_rate", C.c_int32), ("channels", C.c_int32), ("sr_index", C.c_int32),
+                ("delay", C.c_int32), ("padding", C.c_int32), ("skip", C.c_int32), ("hold", C.c_int32), ("buffered", C.c_int32),
+                ("finished", C.c_int32), ("frames", C.c_int64), ("granules", C.c_int64), ("samples", C.c_int64),
+                ("skipped_frames", C.c_int64), ("bytes_in", C.c_int64)]
+
+
+assert C.sizeof(Mp3StreamInfo) == 80
+
+# ss_mp3_stream_seg, 48 bytes
+STREAM_SEG_DTYPE = np.dtype([("rec_offset", "<i8"), ("dst_offset", "<i8"), ("ch_stride", "<i8"), ("granules", "<i4"),
+                             ("channels", "<i4"), ("skip", "<i4"), ("history", "<i4"), ("dst", "<i4"), ("pad0", "<i4")])
+assert STREAM_SEG_DTYPE.itemsize == 48
+
+
+def _info_dict(info: Mp3StreamInfo) -> dict:
+    return {k: getattr(info, k) for k, _ in Mp3StreamInfo._fields_}
+
+
+def _chunk_bytes(data) -> bytes:
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return bytes(data)
+    if isinstance(data, np.ndarray) and data.dtype == np.uint8:
+        return data.tobytes()
+    raise ValueError(f"an MP3 chunk is bytes, bytearray, memoryview or a uint8 array, not {type(data).__name__}")
+
+
+class Mp3Chunk:
+    """What one push released: the records of the frames it completed and where their samples go.
+    q [n_rec, 576] int16, rec [n_rec] GRANULE_DTYPE, bits [n_rec] int32; granules = new granules per channel, history = granules
+    decoded before them (saturated at 2), skip = samples of the new granules the gapless trim drops at the front, written = samples
+    the device stage writes (576 granules - skip), held = samples written by earlier pushes and not released yet (they lie in front
+    of the new ones), released = samples this push hands on: the first `released` of held + written."""
+    __slots__ = ("q", "rec", "bits", "channels", "granules", "history", "skip", "written", "held", "released", "n_bytes", "info")
+
+    def __init__(self, q, rec, bits, before: dict, after: dict, n_bytes: int):
+        self.q, self.rec, self.bits, self.info, self.n_bytes = q, rec, bits, after, n_bytes
+        self.channels = max(after["channels"], 1)
+        self.granules = int(after["granules"] - before["granules"])
+        self.history = int(min(before["granules"], 2))
+        syn0 = max(0, before["granules"] * 576 - after["skip"])            # the trim is known before the first audio frame
+        syn1 = max(0, after["granules"] * 576 - after["skip"])
+        self.written = int(syn1 - syn0)
+        self.skip = self.granules * 576 - self.written
+        self.held = int(syn0 - before["samples"])
+        self.released = int(after["samples"] - before["samples"])
+
+
+class Mp3Stream:
+    """The host object of one MP3 stream (ss_mp3_stream): push() takes a chunk of any size and returns the records of the frames it
+    completes.  A push the library refuses raises Mp3Error and leaves the object as it was.  mark() / rollback() take back pushes
+    that SUCCEEDED (a pool that refuses the chunk for capacity after it has seen what it releases)."""
+
+    def __init__(self, join: bool = False, name: Optional[str] = None):
+        self.lib = L.load()
+        self.name = name
+        self._h, self._spare = C.c_void_p(), C.c_void_p()
+        for h in (self._h, self._spare):
+            rc = self.lib.ss_mp3_stream_create(int(bool(join)), C.byref(h))
+            if rc:
+                _raise(rc, "ss_mp3_stream_create", name)
+
+    @property
+    def info(self) -> dict:
+        i = Mp3StreamInfo()
+        L.check(self.lib.ss_mp3_stream_query(self._h, C.byref(i)), "ss_mp3_stream_query")
+        return _info_dict(i)
+
+    def push(self, data, finished: bool = False, cap: Optional[int] = None) -> Mp3Chunk:
+        data = _chunk_bytes(data)
+        before = self.info
+        if cap is None:
+            cap = int(self.lib.ss_mp3_stream_bound(self._h, len(data)))
+        q = np.empty((max(cap, 1), 576), np.int16)
+        rec = np.empty(max(cap, 1), GRANULE_DTYPE)
+        bits = np.empty(max(cap, 1), np.int32)
+        n, info = C.c_int64(0), Mp3StreamInfo()
+        rc = self.lib.ss_mp3_stream_push(self._h, data, len(data), int(bool(finished)), int(cap), q.ctypes.data, rec.ctypes.data,
+                                         bits.ctypes.data, C.byref(n), C.byref(info))
+        if rc:
+            _raise(rc, "ss_mp3_stream_push", self.name)
+        k = n.value
+        return Mp3Chunk(q[:k], rec[:k], bits[:k], before, _info_dict(info), len(data))
+
+    def mark(self):
+        L.check(self.lib.ss_mp3_stream_copy(self._spare, self._h), "ss_mp3_stream_copy")
+
+    def rollback(self):
+        L.check(self.lib.ss_mp3_stream_copy(self._h, self._spare), "ss_mp3_stream_copy")
+
+    def reset(self):
+        L.check(self.lib.ss_mp3_stream_reset(self._h), "ss_mp3_stream_reset")
+
+    def close(self):
+        for h in (self._h, self._spare):
+            if h:
+                self.lib.ss_mp3_stream_destroy(h)
+                h.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def stream_state(channels: int, device) -> torch.Tensor:
+    """The device state of one stream: the IMDCT blocks of its last two granules, [2, channels, 1152] float32.  Not zeroed: the
+    device stage reads only as many of them as granules were decoded."""
+    return torch.empty((2, int(channels), 1152), dtype=torch.float32, device=device)
+
+
+def stream_synthesize(lib, stream, d_q: int, d_rec: int, n_rec: int, segs, states: Sequence[torch.Tensor],
+                      dsts: Sequence[torch.Tensor], mono: bool, device):
+    """ss_mp3_stream_synthesize: segs [(rec_offset, dst_offset, ch_stride, granules, channels, skip, history, index into dsts)], one
+    per state, over n_rec records at the device addresses d_q / d_rec -> three launches whatever len(segs)."""
+    for d in dsts:
+        if d.dtype != torch.float32 or not d.is_contiguous():
+            raise ValueError("an MP3 destination is a contiguous float32 tensor")
+    tab = np.zeros(max(len(segs), 1), STREAM_SEG_DTYPE)
+    for i, sg in enumerate(segs):
+        tab[i] = tuple(int(v) for v in sg) + (0,)
+    n, nd = len(segs), len(dsts)
+    sp = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in states])
+    pp = (C.c_void_p * max(nd, 1))(*[d.data_ptr() for d in dsts])
+    caps = (C.c_int64 * max(nd, 1))(*[d.numel() for d in dsts])
+    wb = C.c_size_t(0)
+    rc = lib.ss_mp3_stream_synthesize(None, None, None, n_rec, tab.ctypes.data, n, sp, pp, caps, nd, int(mono), None, C.byref(wb))
+    if rc:
+        _raise(rc, "ss_mp3_stream_synthesize (size query)", None)
+    work = torch.empty((max(wb.value, 1),), dtype=torch.uint8, device=device)
+    rc = lib.ss_mp3_stream_synthesize(stream, C.c_void_p(d_q), C.c_void_p(d_rec), n_rec, tab.ctypes.data, n, sp, pp, caps, nd,
+                                      int(mono), C.c_void_p(work.data_ptr()), C.byref(wb))
+    if rc:
+        _raise(rc, "ss_mp3_stream_synthesize", None)
+    # `work` is freed while the kernels may still run: the caching allocator reuses it only for work ordered after them on this stream
+
+
+def decode_stream_batch(arena, items, mono: bool = True, lib=None) -> Tuple[int, int]:
+    """The many-session form: items [(Mp3Chunk, state tensor, destination tensor, offset of the chunk's first written sample in it,
+    channel stride)] of one step -> (granule-channels decoded, bytes uploaded).  The q rows and records of all items are copied into
+    `arena` (a pcm.PcmArena: ONE pinned staging buffer), uploaded ONCE, and decoded by ONE ss_mp3_stream_synthesize call straight
+    into the destinations; the states move on.  Items without new granules cost nothing.  The caller owns the arena's step
+    (clear() before, synchronized() once it has waited for the device)."""
+    lib = lib or L.load()
+    items = [it for it in items if it[0].granules > 0]
+    if not items:
+        return 0, 0
+    n_rec = sum(len(it[0].rec) for it in items)
+    q_off = None
+    for ch, _, _, _, _ in items:                       # q rows are 1152 bytes and records 80: both stay contiguous on the arena's
+        off = arena.add(memoryview(np.ascontiguousarray(ch.q)).cast("B"))     # 16-byte grid
+        q_off = off if q_off is None else q_off
+    r_off = None
+    for ch, _, _, _, _ in items:
+        off = arena.add(memoryview(np.ascontiguousarray(ch.rec).view(np.uint8)).cast("B"))
+        r_off = off if r_off is None else r_off
+    stage, n_bytes = arena.upload()
+    segs, at = [], 0
+    for i, (ch, _, _, dst_off, stride) in enumerate(items):
+        segs.append((at, dst_off, stride, ch.granules, ch.channels, ch.skip, ch.history, i))
+        at += len(ch.rec)
+    dev = stage.device
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream_synthesize(lib, st, stage.data_ptr() + q_off, stage.data_ptr() + r_off, n_rec, segs, [it[1] for it in items],
+                              [it[2] for it in items], mono, dev)
+    else:
+        raise Mp3Error("the MP3 device stage needs a GPU: there is no host synthesis", L.SS_ERR_ARG)
+    return n_rec, n_bytes
+
+
+class Mp3StreamDecoder:
+    """One MP3 stream decoded incrementally on the GPU: push(chunk) -> the newly released float32 samples on `device`, [n] with
+    mono (the channel mean) or [channels, n].  Fed in any chunking, the concatenated output is bit for bit decode_batch's of the
+    whole stream (for inputs whose end the whole-file scan does not cut: trailing ID3v1 / APEv2 tags are not recognised in a
+    stream).  A frame comes out once 4 bytes past its end have arrived, or at finished=True.  join=True: the stream was captured
+    mid-way; decoding starts at the first frame whose main data this decoder holds entirely, and the first two granules after that
+    (1152 samples per channel) are formed against an empty history.  A refused push raises Mp3Error and changes nothing.
+    Until the first frame header is accepted the channel count is unknown: with mono=False the (empty) result then has one row."""
+
+    def __init__(self, device, mono: bool = True, join: bool = False, name: Optional[str] = None):
+        from .pcm import PcmArena
+        self.device, self.mono = torch.device(device), bool(mono)
+        self.host = Mp3Stream(join, name)
+        self._arena = PcmArena(self.device)
+        self._state = None
+        self._held = None                         # samples synthesised and not released yet: [rows, held]
+
+    @property
+    def info(self) -> dict:
+        return self.host.info
+
+    def _empty(self, rows: int, n: int) -> torch.Tensor:
+        return torch.empty((rows, n), dtype=torch.float32, device=self.device)
+
+    def push(self, data, finished: bool = False) -> torch.Tensor:
+        ch = self.host.push(data, finished)
+        rows = 1 if self.mono else ch.channels
+        held = self._held if self._held is not None and self._held.shape[0] == rows else self._empty(rows, 0)
+        assert held.shape[1] == ch.held
+        out = held
+        if ch.granules:
+            if self._state is None:
+                self._state = stream_state(ch.channels, self.device)
+            out = self._empty(rows, ch.held + ch.written)
+            out[:, :ch.held] = held
+            self._arena.clear()
+            decode_stream_batch(self._arena, [(ch, self._state, out, ch.held, out.shape[1])], self.mono, self.host.lib)
+        self._held = out[:, ch.released:]
+        res = out[:, :ch.released]
+        return res[0] if self.mono else res
+
+    def reset(self):
+        self.host.reset()
+        self._state, self._held = None, None
+
+    def close(self):
+        self.host.close()
+        self._state, self._held = None, None

@@ -12,7 +12,13 @@ Driven by one host thread, like the pool.
 A session opened with ``pcm_in=PcmFormat(...)`` is fed raw PCM bytes (push_pcm) instead of SimulEval's lists of floats: the step copies
 the chunks of all such sessions into one pinned arena, uploads it ONCE and decodes every chunk into its session's device history in ONE
 ss_pcm_scatter launch (streamspeech_amd/pcm.py), then runs the same single fbank launch.  The decoded samples are the bits the list
-route uploads, so everything downstream is unchanged; list-fed sessions run the code they always ran, in the same step."""
+route uploads, so everything downstream is unchanged; list-fed sessions run the code they always ran, in the same step.
+
+A session opened with ``mp3_in=True`` (or ``{"join": True}`` for a stream captured mid-way) is fed MP3 bytes as they come off the
+wire (push_mp3), in chunks of any size.  The bitstream is parsed on the host at push time (mp3.Mp3Stream: cheap, and it is what tells
+the admission check how many samples the chunk releases); the step copies the records of all such sessions into one pinned arena,
+uploads it ONCE and ONE ss_mp3_stream_synthesize call decodes them against each session's carried IMDCT blocks straight into its
+device history -- the bits of the whole-file decoder.  The three routes may share a step."""
 import math
 import time
 from typing import Dict, Optional
@@ -66,10 +72,17 @@ class _Session:
         self.pcm_in = None                    # a PcmFormat: the session is fed by push_pcm, and counts samples (fe.n_pcm) instead of
         self.pcm_out = None                   # keeping them in states.source; "s16le": it answers PcmSegment (speech_pool.py)
         self.pcm_chunk = None                 # (byte view, frames) pushed for the next step
+        self.mp3_in = None                    # {"join": bool}: the session is fed by push_mp3 and counts samples as a PCM-fed one does
+        self.mp3 = None                       # its mp3.Mp3Stream (host bitstream state), made at open()
+        self.mp3_state = None                 # its device state: the IMDCT blocks of the last two granules (mp3.stream_state)
+        self.mp3_chunk = None                 # the mp3.Mp3Chunk parsed by push_mp3 for the next step
+        self.mp3_held = 0                     # samples decoded into fe._dev past fe.n_pcm and not released yet (gapless hold-back)
         self.reset()
 
     def n_source(self) -> int:
         """Samples received so far: every host decision that reads len(states.source) of a list-fed session reads this."""
+        if self.mp3_in is not None:
+            return self.fe.n_pcm + (self.mp3_chunk.released if self.mp3_chunk is not None else 0)
         if self.pcm_in is None:
             return len(self.states.source)
         return self.fe.n_pcm + (self.pcm_chunk[1] if self.pcm_chunk is not None else 0)
@@ -82,6 +95,9 @@ class _Session:
         self.tgt_text = ""
         self.states.reset()
         self.fe.clear_cache()
+        if self.mp3 is not None:              # a fresh utterance is a fresh stream: bitstream state and carried blocks start over
+            self.mp3.reset()
+        self.mp3_state, self.mp3_chunk, self.mp3_held = None, None, 0
 
 
 class TextSessionPool:
@@ -102,21 +118,34 @@ class TextSessionPool:
         self._next = 0
         self.last_step: dict = {}              # timings / counts of the last step (tools/pooled_text_bench.py)
         self._arena = None                     # the pinned staging buffer of the PCM-fed sessions' chunks, made with the first one
+        self._mp3_arena = None                 # the same for the records of the MP3-fed sessions
         self._side_times: dict = {}            # timings a subclass's write side adds to last_step
 
     # ---- lifecycle ------------------------------------------------------------------------------------------------------------
     def open(self, kind: str, args, dicts: Optional[dict] = None, pcm_in: Optional[PcmFormat] = None,
-             pcm_out: Optional[str] = None) -> int:
+             pcm_out: Optional[str] = None, mp3_in=None) -> int:
         """A new session; `args` are the agent's own parsed flags (segment size, lagging_k1, stride_n, sample rate, chunk sizes).
         `dicts` overrides the dictionaries the agent would load from the flags (keys source_unigram / target_unigram).
         pcm_in=PcmFormat(...): the session is fed raw PCM at args.sample_rate through push_pcm() and nothing else.
-        pcm_out="s16le" (s2st sessions only): it answers PcmSegment with 16-bit PCM bytes instead of SpeechSegment with a list."""
+        pcm_out="s16le" (s2st sessions only): it answers PcmSegment with 16-bit PCM bytes instead of SpeechSegment with a list.
+        mp3_in=True or {"join": bool}: the session is fed an MP3 stream whose sample rate is args.sample_rate through push_mp3() and
+        nothing else (join: the stream was captured mid-way, mp3.Mp3StreamDecoder).  Not together with pcm_in."""
         if kind not in self.KINDS:
             raise ValueError(f"session kind {kind!r}: one of {self.KINDS}")
         if pcm_in is not None and not isinstance(pcm_in, PcmFormat):
             raise ValueError(f"pcm_in is a PcmFormat, not {pcm_in!r}")
         if pcm_out is not None and (pcm_out != "s16le" or kind != "s2st"):
             raise ValueError(f"pcm_out={pcm_out!r} for a {kind} session: only \"s16le\", and only for s2st sessions")
+        if mp3_in is not None and mp3_in is not False:
+            if pcm_in is not None:
+                raise ValueError("mp3_in and pcm_in exclude each other: a session is fed one way for its whole life")
+            if mp3_in is True:
+                mp3_in = {"join": False}
+            if not isinstance(mp3_in, dict) or set(mp3_in) - {"join"}:
+                raise ValueError(f"mp3_in is True or {{\"join\": bool}}, not {mp3_in!r}")
+            mp3_in = {"join": bool(mp3_in.get("join", False))}
+        else:
+            mp3_in = None
         self._check_open(kind, args)
         if dicts is None:
             from .agent import load_dictionaries
@@ -125,6 +154,9 @@ class TextSessionPool:
         self._next += 1
         s = self._new_session(sid, kind, args, dicts)
         s.pcm_in, s.pcm_out = pcm_in, pcm_out
+        if mp3_in is not None:
+            from .mp3 import Mp3Stream
+            s.mp3_in, s.mp3 = mp3_in, Mp3Stream(mp3_in["join"], name=f"session {sid}")
         self.sessions[sid] = s
         return sid
 
@@ -145,6 +177,9 @@ class TextSessionPool:
     def close(self, sid: int):
         s = self._get(sid)
         self._release(s)
+        if s.mp3 is not None:
+            s.mp3.close()
+            s.mp3, s.mp3_state, s.mp3_chunk = None, None, None
         del self.sessions[sid]
 
     def _get(self, sid) -> _Session:
@@ -204,9 +239,16 @@ class TextSessionPool:
         s.states.update_source(segment)
         s.pending = True
 
-    def _check_route(self, sessions, pcm: bool):
-        """A session is fed one way for its whole life: segments (push / step) or raw PCM (push_pcm).  ValueError, nothing changes."""
+    def _check_route(self, sessions, pcm: bool, mp3: bool = False):
+        """A session is fed one way for its whole life: segments (push / step), raw PCM (push_pcm) or an MP3 stream (push_mp3).
+        ValueError, nothing changes."""
         for s in sessions:
+            if (s.mp3_in is not None) != mp3:
+                raise ValueError(f"session {s.sid}: opened with mp3_in={s.mp3_in!r}, it is fed by "
+                                 + ("push_mp3() only" if s.mp3_in is not None else
+                                    "push_pcm() only" if s.pcm_in is not None else "push() / step() segments only"))
+            if mp3:
+                continue
             if (s.pcm_in is not None) != pcm:
                 raise ValueError(f"session {s.sid}: opened with pcm_in={s.pcm_in!r}, it is fed by "
                                  + ("push_pcm() only" if s.pcm_in is not None else "push() / step() segments only"))
@@ -224,6 +266,55 @@ class TextSessionPool:
         s.pcm_chunk = (mv, frames)
         s.states.source_finished = bool(finished)
         s.pending = True
+
+    def push_mp3(self, sid: int, data, finished: bool = False):
+        """push() for a session opened with mp3_in: `data` holds the next bytes of its MP3 stream, any number of them (bytes,
+        bytearray, memoryview or a uint8 array); finished=True ends the stream (a complete last frame is then accepted without its
+        look-ahead).  The bitstream is parsed here, which tells how many samples the chunk releases; the same admission check as
+        push() runs on that count.  A refused push -- route, a stream the decoder refuses (mp3.Mp3Error), a sample rate other than
+        args.sample_rate (ValueError naming both, at the first accepted header), admission -- raises naming the session and changes
+        nothing, the decoder's state included.  The samples reach the device at the next step()."""
+        s = self._get(sid)
+        self._check_route([s], pcm=False, mp3=True)
+        if s.pending:
+            raise ValueError(f"session {s.sid}: already pushed in this step")
+        s.mp3.mark()
+        chunk = s.mp3.push(data, finished)        # Mp3Error: the object is as it was
+        try:
+            rate = chunk.info["sample_rate"]
+            if rate and rate != s.sr:
+                raise ValueError(f"session {s.sid}: the MP3 stream is at {rate} Hz, the session was opened with sample_rate {s.sr}")
+            self._admit([(s, chunk.released)])
+        except ValueError:
+            s.mp3.rollback()
+            raise
+        s.mp3_chunk = chunk
+        s.states.source_finished = bool(finished)
+        s.pending = True
+
+    def _mp3_stage(self, sessions):
+        """The records of a step's MP3-fed sessions: copied into the arena, ONE upload, ONE ss_mp3_stream_synthesize into the sessions'
+        device histories (behind the samples a gapless stream still holds back), the released ones committed.
+        -> (bytes uploaded, granule-channels decoded).  Single-buffered like _pcm_stage."""
+        if self._mp3_arena is None:
+            self._mp3_arena = PcmArena(self.model.device)
+        self._mp3_arena.clear()
+        items = []
+        for s in sessions:
+            ch = s.mp3_chunk
+            if ch.granules:
+                if s.mp3_state is None:
+                    from .mp3 import stream_state
+                    s.mp3_state = stream_state(ch.channels, self.model.device)
+                dst, at = s.fe.pcm_reserve(ch.written, keep=s.mp3_held)
+                items.append((ch, s.mp3_state, dst, at + s.mp3_held, 0))
+        n_rec, n_bytes = self.model.mp3_stream_decode(self._mp3_arena, items) if items else (0, 0)
+        for s in sessions:
+            ch = s.mp3_chunk
+            s.mp3_held += ch.written - ch.released
+            s.fe.pcm_commit(ch.released)
+            s.mp3_chunk = None
+        return n_bytes, n_rec
 
     def _pcm_stage(self, sessions):
         """The chunks of a step's PCM-fed sessions: copied into the arena, ONE upload, ONE ss_pcm_scatter into the sessions' device
@@ -266,13 +357,17 @@ class TextSessionPool:
         feats, batch, fe_calls, fe_rows = {}, [], 0, 0
         fed = [s for s in todo if s.pcm_chunk is not None and not s.states.target_finished]
         pcm_bytes = self._pcm_stage(fed) if fed else 0
+        fed3 = [s for s in todo if s.mp3_chunk is not None and not s.states.target_finished]
+        mp3_bytes_in = sum(s.mp3_chunk.n_bytes for s in fed3)
+        mp3_bytes, mp3_recs = self._mp3_stage(fed3) if fed3 else (0, 0)
         for s in todo:
             s.pending = False
             if s.states.target_finished:
                 s.pcm_chunk = None                # a finished agent's audio is not kept (the list route appends and never reads it)
+                s.mp3_chunk = None
                 out[s.sid] = EmptySegment(finished=True)
                 continue
-            st = s.fe.stage_pcm() if s.pcm_in is not None else s.fe.stage(s.states.source)
+            st = s.fe.stage_pcm() if (s.pcm_in is not None or s.mp3_in is not None) else s.fe.stage(s.states.source)
             if st is None:
                 actions[s.sid] = ("write", "", True) if s.states.source_finished else ("read",)
                 continue
@@ -316,6 +411,8 @@ class TextSessionPool:
             src, tgt = self.pool.ctc_both()
             if fed:
                 self._arena.synchronized()        # the CTC read waited for everything queued before it, the arena's upload included
+            if fed3:
+                self._mp3_arena.synchronized()
             t2 = time.perf_counter()
             for i, s in enumerate(enc):
                 if s.kind == "asr":
@@ -381,6 +478,10 @@ class TextSessionPool:
                           # write side sets the pack side (ss_pcm_pack_s16 launches, bytes downloaded)
                           "pcm_uploads": 1 if pcm_bytes else 0, "pcm_scatter_calls": 1 if pcm_bytes else 0, "pcm_bytes_in": pcm_bytes,
                           "pcm_pack_calls": 0, "pcm_bytes_out": 0,
+                          # the MP3 route: uploads and ss_mp3_stream_synthesize calls of the step (0 or 1 each), MP3 bytes the step's
+                          # pushes brought, granule-channels decoded
+                          "mp3_uploads": 1 if mp3_bytes else 0, "mp3_synth_calls": 1 if mp3_recs else 0, "mp3_bytes_in": mp3_bytes_in,
+                          "mp3_granules": mp3_recs,
                           "frontend_s": t1 - t0, "encoder_ctc_s": t2 - t1, "mt_s": t3 - t2, "total_s": time.perf_counter() - t0}
         self.last_step.update(self._side_times)
         self._side_times = {}
