@@ -300,6 +300,56 @@ int ss_pcm_pack_s16(void* stream, const float* d_src, int64_t n, int16_t* d_out)
 int ss_pcm_decode_host(const void* h_src, int fmt, int channels, int64_t frames, float* h_dst);
 int ss_pcm_pack_s16_host(const float* h_src, int64_t n, int16_t* h_out);
 
+/* Speech OUT at the caller's sample rate and format (streamspeech_amd/pcm.py PcmOut): the streaming output
+ * resampler.  A session's 16-kHz float32 output of the current utterance is y[0 .. N); z = ss_resample(y) by up / down (lowest
+ * terms, taps [2 * half + 1] = design_filter(up, down), half = 10 * max(up, down)) is its output at the caller's rate.  Output
+ * sample k is settled once its FIR window no longer reaches past y, so after N samples an unfinished utterance has emitted the
+ * first K(N) = 0 if N * up - 1 - half < 0, else (N * up - 1 - half) / down + 1 samples of z, and a finished one all
+ * ceil(N * up / down), zero-padded past N as ss_resample pads.  Every sample is resample_sample's own sum (csrc/fbank.hpp: taps in
+ * ascending m, one fmaf each), so the concatenated output of a stream cut anywhere is encode(ss_resample(y)) byte for byte.  Between
+ * calls a session keeps the last min((2 * half) / up, N) samples of y in a device carry buffer; with up == down nothing is
+ * filtered and nothing is kept.  Encodings (csrc/pcm.hpp): s16le the pack above; f32le the float's bits, unclipped; ulaw / alaw
+ * the pack, then the ITU-T G.711 compression of that 16-bit value (the codes of CPython's audioop.lin2ulaw / lin2alaw). */
+typedef struct ss_pcm_emit_seg {
+  float* carry;              /* the session's carry buffer, room for (2 * half) / up samples: read, then rewritten by the call */
+  const float* tail;         /* the n_new samples y[n_before .. n_before + n_new), where they lie */
+  const float* taps;         /* [2 * half + 1]; not read when up == down */
+  int64_t n_before;          /* N before this call */
+  int64_t k0, k1;            /* the call writes samples [k0, k1) of z */
+  int64_t out_offset;        /* bytes into the output buffer, a multiple of 16 */
+  int32_t carry_len;         /* samples in carry on entry: min((2 * half) / up, n_before); 0 when up == down */
+  int32_t n_new;
+  int32_t up, down, half;
+  int32_t fmt;               /* SS_PCM_* */
+  int32_t finished;          /* != 0: the utterance ends with this call */
+  int32_t reserved;          /* 0 */
+} ss_pcm_emit_seg;           /* 88 bytes */
+
+/* K: the samples of z settled after n samples of y (the formula above; `finished` != 0: ceil(n * up / down)).  Host only.
+ * -1 for n < 0, up or down below 1, half < 0. */
+int64_t ss_pcm_emit_count(int64_t n, int up, int down, int half, int finished);
+/* One call per pool step for every session that answers at its own rate and format: segment i writes the (k1 - k0) *
+ * sample_bytes(fmt) bytes of its samples [k0, k1) at d_out + out_offset and nothing else, and leaves in its carry buffer the last
+ * min((2 * half) / up, n_before + n_new) samples of y.  Pointers of a segment are device memory; h_segs is host memory read before
+ * the call returns.  Stream-ordered, no host round trip, no atomics; at most TWO launches whatever the number of segments and their
+ * mix of ratios and formats: one grid computes and encodes (a workgroup owns a tile of one segment's samples, sized by the ratio,
+ * and stages that segment's taps in LDS), and a second, one workgroup per segment, rewrites the carry buffers -- a launch of its
+ * own because workgroups of the first still read the old carry.  The device copy of the table is a buffer the library keeps per
+ * stream.  The segments' output ranges must not overlap (not checked).
+ * Every refusal is made before any HIP call, for the whole call.  n_segs < 0 or a NULL h_segs: SS_ERR_ARG.  Then, over all segments
+ * in order, SS_ERR_ARG for: a fmt outside the enum; up or down below 1, or (when up != down) half < 1 or taps past 64 KB; n_before
+ * or n_new negative, or n_before + n_new past 2^31 - 1; carry_len other than min((2 * half) / up, n_before); k0 below
+ * ss_pcm_emit_count(n_before, unfinished) (history the carry no longer holds), k1 < k0, k1 past ss_pcm_emit_count(n_before + n_new,
+ * finished), more than 2^30 - 1 samples; out_offset negative or not a multiple of 16; a NULL d_out with samples to write, a NULL tail with n_new > 0, NULL taps
+ * with samples to write and up != down, a NULL carry with history to read or keep.  Then, over all segments in order,
+ * SS_ERR_CAPACITY for an output range past out_bytes.  n_segs == 0: SS_OK, no launch. */
+int ss_pcm_emit(void* stream, const ss_pcm_emit_seg* h_segs, int n_segs, void* d_out, int64_t out_bytes);
+/* The same call on host buffers (every pointer host memory), from the same inline functions: the same bytes and carries.  Host
+ * only, no HIP call; the same refusals in the same order. */
+int ss_pcm_emit_host(const ss_pcm_emit_seg* h_segs, int n_segs, void* h_out, int64_t out_bytes);
+/* The encodings alone: n float samples at h_src -> n * sample_bytes(fmt) bytes at h_out.  Host only. */
+int ss_pcm_encode_host(const float* h_src, int64_t n, int fmt, void* h_out);
+
 /* Offline driver only: d_out[r] = max over the vocabulary, ids mask0..2 skipped (< 0: none), of
  * log_softmax(d_logits[r, :]) -- the per-position score `lprobs.max(dim=2)` of the reference's offline unit search
  * (researches/ctc_unity/ctc_generator.py:55-63: pad / unk / eos set to -inf AFTER the softmax), which fairseq-generate

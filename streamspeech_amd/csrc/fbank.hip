@@ -145,21 +145,8 @@ int launch_fbank_cmvn_ptrs(const float* const* pcm_ptrs, float* const* feat_ptrs
 // `up`) are ~60/output sample for 3:1: a thread per output sample, taps through LDS when they fit.
 // HBM-bound by construction: 4*(n_in + n_out) bytes.
 // ---------------------------------------------------------------------------------------------
-// Output sample k of the resampler from the input history x[0 .. n_in) and the taps hs (LDS): the input window clamped at both
-// ends of the history (zero padding), taps in ascending m, one fmaf each.  The ONE copy of this sum: resample_kernel and the
-// resampling prologue of fbank_cmvn_sr_kernel give the same bits for the same (x, n_in, k).
-__device__ __forceinline__ float resample_sample(const float* __restrict__ x, long long n_in, int up, int down,
-                                                 const float* hs, int half, long long k) {
-  const long long c = k * down;
-  long long m_lo = c - half;                          // ceil((c - half) / up), clamped at 0
-  m_lo = m_lo <= 0 ? 0 : (m_lo + up - 1) / up;
-  long long m_hi = (c + half) / up;
-  if (m_hi > n_in - 1) m_hi = n_in - 1;
-  float acc = 0.f;
-  for (long long m = m_lo; m <= m_hi; ++m) acc = fmaf(x[m], hs[half + (int)(c - m * up)], acc);
-  return acc;
-}
-
+// (resample_sample, the ONE copy of the sum, lives in fbank.hpp: this kernel, the resampling prologue of fbank_cmvn_sr_kernel and
+// the streaming output resampler of pcm.hip, device and host, compile it.)
 __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, long long n_in, int up, int down,
                                                        const float* __restrict__ h, int half, float* __restrict__ y,
                                                        long long n_out) {

@@ -1,5 +1,7 @@
 // Fused fbank + CMVN front-end kernel (see fbank.hip).
 #pragma once
+#include <math.h>
+
 #include "common.hpp"
 
 namespace ss {
@@ -27,6 +29,24 @@ int launch_fbank_cmvn_ptrs(const float* const* pcm_ptrs, float* const* feat_ptrs
 // in lowest terms, taps [2*half_len+1] on the device with gain `up`).
 int launch_resample(const float* x, long long n_in, int up, int down, const float* taps, int half_len, float* y,
                     long long n_out, hipStream_t stream);
+
+// Output sample k of the resampler from the input history x[0 .. n_in) and the taps hs (LDS on the device): the input window clamped
+// at both ends of the history (zero padding), taps in ascending m, one fmaf each.  The ONE copy of this sum: resample_kernel, the
+// resampling prologue of fbank_cmvn_sr_kernel and the streaming output resampler (pcm.hip: ss_pcm_emit and its host twin) give the
+// same bits for the same (x, n_in, k) -- fmaf is correctly rounded on both sides.  X is anything that answers x[m] with a float for
+// m in [0, n_in): a pointer, or a history that lies in two pieces (pcm.hpp).
+template <class X>
+__host__ __device__ __forceinline__ float resample_sample(X x, long long n_in, int up, int down, const float* hs, int half,
+                                                          long long k) {
+  const long long c = k * down;
+  long long m_lo = c - half;                          // ceil((c - half) / up), clamped at 0
+  m_lo = m_lo <= 0 ? 0 : (m_lo + up - 1) / up;
+  long long m_hi = (c + half) / up;
+  if (m_hi > n_in - 1) m_hi = n_in - 1;
+  float acc = 0.f;
+  for (long long m = m_lo; m <= m_hi; ++m) acc = fmaf(x[m], hs[half + (int)(c - m * up)], acc);
+  return acc;
+}
 
 // One session of launch_fbank_cmvn_sr (a device table of these): rows first .. first + n_rows - 1 of the fbank of the source-rate
 // history pcm[0 .. n_in) resampled by up / down (lowest terms; taps [2 * half + 1] on the device, unused when up == down), to feat

@@ -4,12 +4,15 @@
 // into 16-bit PCM in one launch, for one download.  Both kernels are memory-bound copies with a conversion: no LDS, no atomics, 16-byte
 // loads and stores where the addresses allow them, scalar heads and tails.  The conversions are the inline functions of pcm.hpp, the
 // same ones the host entry points (ss_pcm_decode_host, ss_pcm_pack_s16_host) call.
+// ss_pcm_emit is the way out at the caller's own rate and format: the streaming output resampler (resample_sample of fbank.hpp over a
+// history that lies in the session's carry buffer and the step's new tail) and the encoders, for all such sessions of a step at once.
 #include <algorithm>
 #include <map>
 #include <mutex>
 #include <vector>
 
 #include "../../include/streamspeech_hip.h"
+#include "fbank.hpp"
 #include "pcm.hpp"
 
 namespace {
@@ -153,17 +156,139 @@ __global__ __launch_bounds__(kThreads) void pcm_pack_s16_kernel(const float* __r
   for (int64_t i = i0; i < i1; ++i) out[i] = pack_s16(src[i]);
 }
 
+// ---- speech out at the caller's rate and format ------------------------------------------------------------------------------------
+// One segment of ss_pcm_emit as the kernels see it.  A workgroup owns `tile` consecutive outputs of one segment (a multiple of
+// kTile; a lane takes groups of 8, so a whole group stores 32 / 16 / 8 aligned bytes); tile0 is the exclusive prefix sum of the
+// segments' tile counts, searched as pcm_scatter_kernel searches its own.
+struct EmitDev {
+  float* carry;
+  const float* tail;
+  const float* taps;
+  uint8_t* out;              // first byte of the segment's range, 16-byte aligned
+  long long n_before, n_after, k0;
+  long long base;            // index in y of carry[0] on entry: n_before - carry_len
+  int32_t n_out, up, down, half, fmt;
+  int32_t tile, tile0;
+  int32_t keep;              // samples of y the carry holds after the call: min((2 half) / up, n_after)
+};
+static_assert(sizeof(EmitDev) == 96, "EmitDev is 96 bytes");
+static_assert(sizeof(ss_pcm_emit_seg) == 88, "ss_pcm_emit_seg is 88 bytes");
+
+constexpr int kMaxTaps = 64 * 1024 / (int)sizeof(float);   // ss_resample's own limit: the taps go through LDS
+constexpr int kMaxTileMul = 8;
+
+// Outputs per workgroup for a table of ntaps taps: staging the table costs ntaps loads, so a workgroup that stages more writes more
+// (441:160 -- 8821 taps, 35 KB -- gets 10240 outputs where 3:1 -- 61 taps -- gets 2048).
+inline int emit_tile(int ntaps) { return kTile * std::min(kMaxTileMul, std::max(1, (ntaps + kTile - 1) / kTile)); }
+
+__host__ __device__ inline float emit_value(const float* carry, const float* tail, long long base, long long n_before,
+                                            long long n_after, int up, int down, const float* hs, int half, long long k) {
+  if (up == down) return tail[k - n_before];           // K(N) = N: sample k of z is sample k of y, and it arrived with this call
+  return ss::resample_sample(SplitHistory{carry, tail, base, n_before}, n_after, up, down, hs, half, k);
+}
+
+__host__ __device__ inline void store_sample(uint8_t* out, long long j, uint32_t bits, int fmt) {
+  if (fmt == F32LE) reinterpret_cast<uint32_t*>(out)[j] = bits;             // out is 16-byte aligned
+  else if (fmt == S16LE) reinterpret_cast<uint16_t*>(out)[j] = (uint16_t)bits;
+  else out[j] = (uint8_t)bits;
+}
+
+__global__ __launch_bounds__(kThreads) void pcm_emit_kernel(const EmitDev* __restrict__ segs, int n_segs) {
+  extern __shared__ float hs[];
+  int lo = 0, hi = n_segs;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (segs[mid].tile0 <= (int)blockIdx.x) lo = mid; else hi = mid;
+  }
+  const EmitDev sg = segs[lo];
+  if (sg.up != sg.down) {                              // the whole workgroup takes the same side
+    const int ntaps = 2 * sg.half + 1;
+    for (int i = threadIdx.x; i < ntaps; i += kThreads) hs[i] = sg.taps[i];
+    __syncthreads();
+  }
+  const int j_begin = ((int)blockIdx.x - sg.tile0) * sg.tile;
+  const int j_end = min(sg.n_out, j_begin + sg.tile);  // n_out <= 2^30 - 1: the sums stay inside the int range
+  for (int j0 = j_begin + (int)threadIdx.x * kGroup; j0 < j_end; j0 += kTile) {
+    if (j0 + kGroup <= j_end) {
+      uint32_t b[kGroup];
+#pragma unroll
+      for (int i = 0; i < kGroup; ++i)
+        b[i] = encode_sample(emit_value(sg.carry, sg.tail, sg.base, sg.n_before, sg.n_after, sg.up, sg.down, hs, sg.half,
+                                        sg.k0 + j0 + i), sg.fmt);
+      if (sg.fmt == F32LE) {
+        uint4* d = reinterpret_cast<uint4*>(sg.out + (size_t)j0 * 4);
+        d[0] = make_uint4(b[0], b[1], b[2], b[3]);
+        d[1] = make_uint4(b[4], b[5], b[6], b[7]);
+      } else if (sg.fmt == S16LE) {
+        *reinterpret_cast<uint4*>(sg.out + (size_t)j0 * 2) =
+            make_uint4(b[0] | (b[1] << 16), b[2] | (b[3] << 16), b[4] | (b[5] << 16), b[6] | (b[7] << 16));
+      } else {
+        *reinterpret_cast<uint2*>(sg.out + (size_t)j0) = make_uint2(b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24),
+                                                                    b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24));
+      }
+    } else {                                           // the segment's tail: sample by sample
+      for (int j = j0; j < j_end; ++j)
+        store_sample(sg.out, j, encode_sample(emit_value(sg.carry, sg.tail, sg.base, sg.n_before, sg.n_after, sg.up, sg.down, hs,
+                                                         sg.half, sg.k0 + j), sg.fmt), sg.fmt);
+    }
+  }
+}
+
+// The carry buffers after the emit grid has read them: workgroup = one segment.  The new carry (the last `keep` samples of y) may
+// take samples from the old one at other positions, so it goes through LDS: all reads, a barrier, all writes.
+__global__ __launch_bounds__(kThreads) void pcm_emit_carry_kernel(const EmitDev* __restrict__ segs) {
+  extern __shared__ float cs[];
+  const EmitDev sg = segs[blockIdx.x];
+  if (sg.keep == 0 || sg.n_after == sg.n_before) return;                   // nothing kept, or nothing new: the carry stays
+  const SplitHistory y{sg.carry, sg.tail, sg.base, sg.n_before};
+  const long long first = sg.n_after - sg.keep;                            // >= base
+  for (int i = threadIdx.x; i < sg.keep; i += kThreads) cs[i] = y[first + i];
+  __syncthreads();
+  for (int i = threadIdx.x; i < sg.keep; i += kThreads) sg.carry[i] = cs[i];
+}
+
+// Every refusal of ss_pcm_emit / ss_pcm_emit_host, in the header's order.
+int emit_check(const ss_pcm_emit_seg* h_segs, int n_segs, const void* out, int64_t out_bytes) {
+  if (n_segs < 0 || (n_segs > 0 && !h_segs)) return SS_ERR_ARG;
+  for (int i = 0; i < n_segs; ++i) {
+    const ss_pcm_emit_seg& s = h_segs[i];
+    if (s.fmt < 0 || s.fmt >= N_FMT) return SS_ERR_ARG;
+    if (s.up < 1 || s.down < 1) return SS_ERR_ARG;
+    if (s.up != s.down && (s.half < 1 || 2LL * s.half + 1 > kMaxTaps)) return SS_ERR_ARG;
+    if (s.n_before < 0 || s.n_new < 0 || s.n_before + s.n_new > 0x7fffffffLL) return SS_ERR_ARG;
+    const long long hist = emit_history(s.up, s.down, s.half);
+    if (s.carry_len != std::min<long long>(hist, s.n_before)) return SS_ERR_ARG;
+    const long long n_after = s.n_before + s.n_new;
+    if (s.k0 < emit_count(s.n_before, s.up, s.down, s.half, 0) || s.k1 < s.k0) return SS_ERR_ARG;
+    if (s.k1 > emit_count(n_after, s.up, s.down, s.half, s.finished != 0) || s.k1 - s.k0 > 0x3fffffffLL) return SS_ERR_ARG;
+    if (s.out_offset < 0 || (s.out_offset & 15) != 0) return SS_ERR_ARG;
+    const bool work = s.k1 > s.k0;
+    if (work && !out) return SS_ERR_ARG;
+    if (s.n_new > 0 && !s.tail) return SS_ERR_ARG;
+    if (work && s.up != s.down && !s.taps) return SS_ERR_ARG;
+    if (!s.carry && (s.carry_len > 0 || std::min<long long>(hist, n_after) > 0)) return SS_ERR_ARG;
+  }
+  if (out_bytes < 0) return SS_ERR_ARG;
+  for (int i = 0; i < n_segs; ++i) {
+    const ss_pcm_emit_seg& s = h_segs[i];
+    const int64_t bytes = (s.k1 - s.k0) * sample_bytes(s.fmt);
+    if (s.out_offset > out_bytes || bytes > out_bytes - s.out_offset) return SS_ERR_CAPACITY;
+  }
+  return SS_OK;
+}
+
 // The device copy of a call's segment table: one grow-only buffer per (device, stream), so calls on one stream reuse it in stream
-// order and calls on different streams never share one.  Buffers live until the process ends.
+// order and calls on different streams never share one; ss_pcm_scatter's table is slot 0 of a stream, ss_pcm_emit's slot 1.  Buffers
+// live until the process ends.
 struct TableBuf { void* p = nullptr; size_t cap = 0; };
 std::mutex g_mu;
-std::map<std::pair<int, void*>, TableBuf> g_tables;
+std::map<std::pair<std::pair<int, void*>, int>, TableBuf> g_tables;
 
-int table_for(void* stream, size_t bytes, void** out) {
+int table_for(void* stream, size_t bytes, void** out, int slot = 0) {
   int dev = 0;
   SS_HIP_CHECK(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_mu);
-  TableBuf& t = g_tables[{dev, stream}];
+  TableBuf& t = g_tables[{{dev, stream}, slot}];
   if (t.cap < bytes) {
     if (t.p) {
       SS_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));             // an earlier call of this stream may still read it
@@ -260,5 +385,92 @@ extern "C" int ss_pcm_pack_s16_host(const float* h_src, int64_t n, int16_t* h_ou
   if (n == 0) return SS_OK;
   if (!h_src || !h_out) return SS_ERR_ARG;
   for (int64_t i = 0; i < n; ++i) h_out[i] = pack_s16(h_src[i]);
+  return SS_OK;
+}
+
+extern "C" int64_t ss_pcm_emit_count(int64_t n, int up, int down, int half, int finished) {
+  if (n < 0 || up < 1 || down < 1 || half < 0) return -1;
+  return emit_count(n, up, down, half, finished != 0);
+}
+
+extern "C" int ss_pcm_emit(void* stream, const ss_pcm_emit_seg* h_segs, int n_segs, void* d_out, int64_t out_bytes) {
+  const int rc = emit_check(h_segs, n_segs, d_out, out_bytes);
+  if (rc != SS_OK) return rc;
+  if (n_segs == 0) return SS_OK;
+  if ((((uintptr_t)d_out) & 15) != 0) return SS_ERR_ARG;                   // the output buffer itself: an allocation
+  std::vector<EmitDev> tab((size_t)n_segs);
+  int64_t tiles = 0;
+  int max_taps = 0, max_keep = 0;
+  for (int i = 0; i < n_segs; ++i) {
+    const ss_pcm_emit_seg& s = h_segs[i];
+    EmitDev& d = tab[i];
+    d.carry = s.carry; d.tail = s.tail; d.taps = s.taps;
+    d.out = (uint8_t*)d_out + s.out_offset;
+    d.n_before = s.n_before; d.n_after = s.n_before + s.n_new; d.k0 = s.k0;
+    d.base = s.n_before - s.carry_len;
+    d.n_out = (int32_t)(s.k1 - s.k0); d.up = s.up; d.down = s.down; d.half = s.half; d.fmt = s.fmt;
+    const int ntaps = s.up == s.down ? 0 : 2 * s.half + 1;
+    d.tile = emit_tile(ntaps);
+    d.tile0 = (int32_t)tiles;
+    d.keep = (int32_t)std::min<long long>(emit_history(s.up, s.down, s.half), d.n_after);
+    if (d.n_out > 0) {
+      tiles += ((int64_t)d.n_out + d.tile - 1) / d.tile;
+      max_taps = std::max(max_taps, ntaps);
+    }
+    if (s.n_new > 0) max_keep = std::max(max_keep, d.keep);
+    if (tiles > 0x7fffffff) return SS_ERR_ARG;
+  }
+  if (tiles == 0 && max_keep == 0) return SS_OK;
+  hipStream_t st = (hipStream_t)stream;
+  void* d_tab = nullptr;
+  const size_t bytes = sizeof(EmitDev) * (size_t)n_segs;
+  const int rt = table_for(stream, bytes, &d_tab, 1);
+  if (rt != SS_OK) return rt;
+  SS_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), bytes, hipMemcpyHostToDevice, st));   // pageable source: staged when the call returns
+  if (tiles > 0) {
+    hipLaunchKernelGGL(pcm_emit_kernel, dim3((unsigned)tiles), dim3(kThreads), (size_t)max_taps * sizeof(float), st,
+                       (const EmitDev*)d_tab, n_segs);
+    SS_LAUNCH_CHECK();
+  }
+  if (max_keep > 0) {
+    hipLaunchKernelGGL(pcm_emit_carry_kernel, dim3((unsigned)n_segs), dim3(kThreads), (size_t)max_keep * sizeof(float), st,
+                       (const EmitDev*)d_tab);
+    SS_LAUNCH_CHECK();
+  }
+  return SS_OK;
+}
+
+extern "C" int ss_pcm_emit_host(const ss_pcm_emit_seg* h_segs, int n_segs, void* h_out, int64_t out_bytes) {
+  const int rc = emit_check(h_segs, n_segs, h_out, out_bytes);
+  if (rc != SS_OK) return rc;
+  if (n_segs > 0 && (((uintptr_t)h_out) & 3) != 0) return SS_ERR_ARG;      // f32le / s16le samples are stored as words
+  std::vector<float> kept;
+  for (int i = 0; i < n_segs; ++i) {
+    const ss_pcm_emit_seg& s = h_segs[i];
+    const long long n_after = s.n_before + s.n_new, base = s.n_before - s.carry_len;
+    uint8_t* out = (uint8_t*)h_out + s.out_offset;
+    for (long long k = s.k0; k < s.k1; ++k)
+      store_sample(out, k - s.k0, encode_sample(emit_value(s.carry, s.tail, base, s.n_before, n_after, s.up, s.down, s.taps, s.half,
+                                                           k), s.fmt), s.fmt);
+    const long long keep = std::min<long long>(emit_history(s.up, s.down, s.half), n_after);
+    if (keep == 0 || s.n_new == 0) continue;
+    const SplitHistory y{s.carry, s.tail, base, s.n_before};
+    kept.resize((size_t)keep);
+    for (long long j = 0; j < keep; ++j) kept[(size_t)j] = y[n_after - keep + j];
+    memcpy(s.carry, kept.data(), sizeof(float) * (size_t)keep);
+  }
+  return SS_OK;
+}
+
+extern "C" int ss_pcm_encode_host(const float* h_src, int64_t n, int fmt, void* h_out) {
+  if (n < 0 || fmt < 0 || fmt >= N_FMT) return SS_ERR_ARG;
+  if (n == 0) return SS_OK;
+  if (!h_src || !h_out) return SS_ERR_ARG;
+  uint8_t* o = (uint8_t*)h_out;
+  const int sb = sample_bytes(fmt);
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t b = encode_sample(h_src[i], fmt);
+    memcpy(o + i * sb, &b, (size_t)sb);                                    // little-endian host, as everywhere in this file
+  }
   return SS_OK;
 }

@@ -87,5 +87,62 @@ __host__ __device__ inline int16_t pack_s16(float x) {
   return (int16_t)(int)rintf(fminf(fmaxf(x, -1.0f), 1.0f) * 32767.0f);
 }
 
+// 16-bit linear value -> G.711 mu-law code (ITU-T G.711 compression of the 14-bit value s >> 2: magnitude clipped at 8159, biased
+// by 33, segment = position of its leading one, four mantissa bits below it; all bits inverted).  Not "the nearest level": at the
+// segment edges the standard's truncation picks the level below.  ulaw_from_s16(ulaw_to_s16(c)) == c except for 0x7F (negative
+// zero), which encodes as 0xFF.
+__host__ __device__ inline uint8_t ulaw_from_s16(int s) {
+  int v = s >> 2;
+  const int mask = v < 0 ? 0x7F : 0xFF;
+  if (v < 0) v = -v;
+  if (v > 8159) v = 8159;
+  v += 33;                                            // 33 .. 8192: bit 5 at least is set
+  int seg = 0;
+  while ((v >> (seg + 6)) != 0) ++seg;                // 0 .. 8 (8 only for 8192, the clipped top)
+  if (seg >= 8) return (uint8_t)(0x7F ^ mask);
+  return (uint8_t)(((seg << 4) | ((v >> (seg + 1)) & 15)) ^ mask);
+}
+
+// 16-bit linear value -> G.711 A-law code (compression of the 13-bit value s >> 3; a negative value v is coded as -v - 1; even bits
+// inverted).  alaw_from_s16(alaw_to_s16(c)) == c for every code.
+__host__ __device__ inline uint8_t alaw_from_s16(int s) {
+  int v = s >> 3;
+  const int mask = v >= 0 ? 0xD5 : 0x55;
+  if (v < 0) v = -v - 1;                              // 0 .. 4095
+  int seg = 0;
+  while ((v >> (seg + 5)) != 0) ++seg;                // 0 .. 7
+  const int q = seg < 2 ? (v >> 1) & 15 : (v >> seg) & 15;
+  return (uint8_t)(((seg << 4) | q) ^ mask);
+}
+
+// One float sample -> its sample_bytes(fmt) little-endian bytes in the low end of the result: f32le the float's bits (no clipping,
+// NaN payloads as they are), s16le pack_s16, G.711 the compression of pack_s16's value.
+__host__ __device__ inline uint32_t encode_sample(float x, int fmt) {
+  if (fmt == F32LE) return float_to_bits(x);
+  const int s = pack_s16(x);
+  if (fmt == S16LE) return (uint32_t)(uint16_t)s;
+  return fmt == ULAW ? ulaw_from_s16(s) : alaw_from_s16(s);
+}
+
+// A 16-kHz output history that lies in two pieces: samples [base, n_before) in the session's carry buffer, [n_before, ...) in the
+// new tail.  resample_sample (fbank.hpp) reads it as x[m].
+struct SplitHistory {
+  const float* carry;
+  const float* tail;
+  long long base, n_before;
+  __host__ __device__ inline float operator[](long long m) const { return m < n_before ? carry[m - base] : tail[m - n_before]; }
+};
+
+// Output samples of the streaming resampler that are settled after n input samples (ss_pcm_emit_count): all ceil(n up / down) once
+// the utterance is finished, else those whose FIR window (k down + half) / up <= n - 1 lies inside the history.
+__host__ __device__ inline long long emit_count(long long n, int up, int down, int half, int finished) {
+  if (up == down) return n;
+  if (finished) return (n * up + down - 1) / down;
+  const long long top = n * up - 1 - half;
+  return top < 0 ? 0 : top / down + 1;
+}
+// samples of history the next call may still read: (2 half) / up (0 when nothing is resampled)
+__host__ __device__ inline long long emit_history(int up, int down, int half) { return up == down ? 0 : (2LL * half) / up; }
+
 }  // namespace pcm
 }  // namespace ss

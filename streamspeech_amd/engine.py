@@ -201,6 +201,16 @@ class BatchMixin:
         from . import pcm
         pcm.pack_s16(self.lib, _stream(), src, out)
 
+    def pcm_taps(self, up: int, down: int) -> torch.Tensor:
+        """The device tap table of the ratio up / down, made once and shared with resample()."""
+        return self._taps(up, down)
+
+    def pcm_emit(self, segs, out: torch.Tensor):
+        """The speech of every session of a step that answers at its own rate and format: resampled from each one's carried history
+        and new tail, encoded, into the uint8 device tensor `out` (ss_pcm_emit; pcm.emit_plan names the segment tuple)."""
+        from . import pcm
+        pcm.emit(self.lib, _stream(), segs, out)
+
     def fbank_sr_rows(self, n_in: int, sr_in: int) -> Optional[Tuple[int, int]]:
         """(fbank rows, final fbank rows) of n_in samples at sr_in Hz (fbank_sr_rows); None for a rate batch_fbank_frames_sr refuses."""
         return fbank_sr_rows(n_in, *resample_ratio(sr_in), lib=self.lib)

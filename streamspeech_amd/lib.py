@@ -36,6 +36,13 @@ class SSPcmSeg(C.Structure):
                 ("channels", C.c_int32), ("dst", C.c_int32)]
 
 
+class SSPcmEmitSeg(C.Structure):
+    """ss_pcm_emit_seg: one session of a ss_pcm_emit call (88 bytes)."""
+    _fields_ = [("carry", _vp), ("tail", _vp), ("taps", _vp), ("n_before", C.c_int64), ("k0", C.c_int64), ("k1", C.c_int64),
+                ("out_offset", C.c_int64), ("carry_len", C.c_int32), ("n_new", C.c_int32), ("up", C.c_int32), ("down", C.c_int32),
+                ("half", C.c_int32), ("fmt", C.c_int32), ("finished", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SSOpAttnArgs(C.Structure):
     """ss_op_attn_args: AttnArgs (csrc/attention.hpp) field for field, pointers as device addresses."""
     _fields_ = [
@@ -98,6 +105,10 @@ SIGNATURES = {
     "ss_pcm_pack_s16": (_i, [_vp, _vp, _i64, _vp]),
     "ss_pcm_decode_host": (_i, [_vp, _i, _i, _i64, _vp]),
     "ss_pcm_pack_s16_host": (_i, [_vp, _i64, _vp]),
+    "ss_pcm_emit_count": (_i64, [_i64, _i, _i, _i, _i]),
+    "ss_pcm_emit": (_i, [_vp, _vp, _i, _vp, _i64]),
+    "ss_pcm_emit_host": (_i, [_vp, _i, _vp, _i64]),
+    "ss_pcm_encode_host": (_i, [_vp, _i64, _i, _vp]),
     "ss_row_max_logprob": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ss_log_softmax": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ss_encoder_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),

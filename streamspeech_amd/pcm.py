@@ -3,10 +3,15 @@ pool step.  :class:`PcmArena` is the step's one pinned host buffer -- every push
 asynchronous upload moves it, and ONE ss_pcm_scatter launch (csrc/pcm.hip) decodes all chunks into the sessions' float32 sample
 histories.  On the way out ss_pcm_pack_s16 turns the step's synthesised speech into 16-bit PCM for one download.  The conversions are
 exact and are the bits of the list route (frontend.read_wav / write_wav); ss_pcm_decode_host / ss_pcm_pack_s16_host run the same
-inline functions on the host (tests, and tools that have no device)."""
+inline functions on the host (tests, and tools that have no device).
+
+:class:`PcmOut` is the way out at the caller's own rate and format: the speech of every such session of a step goes through ONE
+ss_pcm_emit call -- the streaming output resampler with a short carried history per session, then the encoder -- and ONE download
+(:class:`PcmEmitter`; :class:`PcmStreamEncoder` is the same machinery without a pool)."""
 import ctypes as C
+import math
 from dataclasses import dataclass
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -49,9 +54,56 @@ class PcmFormat:
         return n_bytes // self.bytes_per_frame
 
 
+OUT_RATES = (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000)      # the rates the documentation names; others: PcmOut
+MAX_TAPS_BYTES = 64 * 1024                   # ss_resample's limit on a tap table (the taps go through LDS)
+
+
+@dataclass(frozen=True)
+class PcmOut:
+    """What an S2ST session answers: mono `fmt` ("s16le", "f32le", "ulaw", "alaw") at `sample_rate` Hz.  Any rate whose ratio to
+    16000 in lowest terms up / down gives a tap table ss_resample accepts (design_filter(up, down) within 64 KB: max(up, down) <= 819);
+    8000, 11025, 16000, 22050, 24000, 32000, 44100 and 48000 all are.  Anything else is ValueError here, at construction."""
+    fmt: str
+    sample_rate: int = 16000
+
+    def __post_init__(self):
+        if self.fmt not in FORMATS:
+            raise ValueError(f"PCM format {self.fmt!r}: one of {tuple(FORMATS)}")
+        sr = self.sample_rate
+        if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or sr < 1:
+            raise ValueError(f"sample rate {sr!r}: a positive integer")
+        object.__setattr__(self, "sample_rate", int(sr))
+        up, down, half = self.ratio
+        if up != down and (2 * half + 1) * 4 > MAX_TAPS_BYTES:
+            raise ValueError(f"sample rate {sr}: {up}/{down} of 16000 Hz needs {2 * half + 1} filter taps, more than the resampler's "
+                             f"{MAX_TAPS_BYTES // 4}; rates such as {OUT_RATES} are served")
+
+    @property
+    def ratio(self) -> Tuple[int, int, int]:
+        """(up, down, half): the ratio to 16000 Hz in lowest terms and design_filter's half length (0 when nothing is resampled)."""
+        g = math.gcd(self.sample_rate, 16000)
+        up, down = self.sample_rate // g, 16000 // g
+        return up, down, (0 if up == down else 10 * max(up, down))
+
+    @property
+    def code(self) -> int:
+        return FORMATS[self.fmt]
+
+    @property
+    def sample_bytes(self) -> int:
+        return _SAMPLE_BYTES[self.code]
+
+    @property
+    def history(self) -> int:
+        """Samples of 16-kHz output a session carries between calls: (2 * half) // up."""
+        up, _, half = self.ratio
+        return (2 * half) // up
+
+
 @dataclass
 class PcmSegment:
-    """A pool's answer to a session opened with pcm_out: `content` is raw mono PCM bytes in `fmt` (beside the shim's segments)."""
+    """A pool's answer to a session opened with pcm_out: `content` is raw mono PCM bytes in `fmt` at `sample_rate` (the session's own:
+    "s16le" at 16000 for pcm_out="s16le", the PcmOut's otherwise), beside the shim's segments."""
     index: int = 0
     content: bytes = b""
     fmt: str = "s16le"
@@ -202,3 +254,140 @@ def pack_s16_host(samples, lib=None) -> np.ndarray:
     L.check(lib.ss_pcm_pack_s16_host(C.c_void_p(x.ctypes.data if x.size else 0), x.size,
                                      C.c_void_p(out.ctypes.data if x.size else 0)), "ss_pcm_pack_s16_host")
     return out
+
+
+# ---- out at the caller's rate and format --------------------------------------------------------------------------------------------
+def emit_count(n: int, up: int, down: int, half: int, finished: bool = False, lib=None) -> int:
+    """ss_pcm_emit_count: K, the output samples settled after n samples at 16 kHz (all ceil(n * up / down) once finished)."""
+    k = (lib or L.load()).ss_pcm_emit_count(int(n), int(up), int(down), int(half), 1 if finished else 0)
+    if k < 0:
+        raise ValueError(f"ss_pcm_emit_count({n}, {up}, {down}, {half})")
+    return int(k)
+
+
+class PcmOutState:
+    """One session's side of the streaming output resampler: the device carry buffer (allocated here, sized from the ratio), the
+    device taps (the engine's table of the ratio) and the host counters -- n samples of 16-kHz output received in this utterance, k
+    samples emitted, flushed once the utterance has ended."""
+
+    def __init__(self, out: PcmOut, engine):
+        self.out = out
+        self.up, self.down, self.half = out.ratio
+        self.history = out.history
+        dev = torch.device(engine.device)
+        self.carry = torch.zeros((self.history,), dtype=torch.float32, device=dev) if self.history else None
+        self.taps = engine.pcm_taps(self.up, self.down) if self.up != self.down else None
+        self.reset()
+
+    def reset(self):
+        self.n, self.k, self.flushed = 0, 0, False
+
+
+def emit_plan(items, lib=None):
+    """[(PcmOutState, tail or None, finished)] -> (segment tuples of ss_pcm_emit, [(byte offset, bytes)], total bytes): every segment's
+    output on a 16-byte boundary of one buffer.  A state that has flushed emits nothing (and takes nothing) until it is reset."""
+    segs, ranges, cursor = [], [], 0
+    for st, tail, finished in items:
+        n_new = 0 if (tail is None or st.flushed) else int(tail.numel())
+        if n_new and (tail.dtype != torch.float32 or not tail.is_contiguous()):
+            raise ValueError("a PcmOut tail is a contiguous float32 tensor")
+        k1 = st.k if st.flushed else emit_count(st.n + n_new, st.up, st.down, st.half, finished, lib)
+        off = (cursor + ALIGN - 1) & ~(ALIGN - 1)
+        nbytes = (k1 - st.k) * st.out.sample_bytes
+        cursor = off + nbytes
+        segs.append((st.carry.data_ptr() if st.carry is not None else 0, tail.data_ptr() if n_new else 0,
+                     st.taps.data_ptr() if st.taps is not None else 0, st.n, st.k, k1, off, min(st.history, st.n), n_new,
+                     st.up, st.down, st.half, st.out.code, 1 if finished else 0))
+        ranges.append((off, nbytes))
+    return segs, ranges, cursor
+
+
+def _emit_table(segs):
+    tab = (L.SSPcmEmitSeg * max(len(segs), 1))()
+    for i, sg in enumerate(segs):
+        tab[i] = L.SSPcmEmitSeg(*[int(v) for v in sg], 0)
+    return tab
+
+
+def emit(lib, stream, segs, out: torch.Tensor):
+    """ss_pcm_emit: the segment tuples of emit_plan into the uint8 device tensor `out`."""
+    if out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError("emit: a contiguous uint8 output tensor")
+    L.check(lib.ss_pcm_emit(stream, _emit_table(segs), len(segs), C.c_void_p(out.data_ptr() if out.numel() else 0), out.numel()),
+            "ss_pcm_emit")
+
+
+def emit_host(segs, out: torch.Tensor, lib=None):
+    """ss_pcm_emit_host: the same call on CPU tensors (every pointer of the segments is host memory)."""
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.device.type != "cpu":
+        raise ValueError("emit_host: a contiguous uint8 CPU tensor")
+    L.check((lib or L.load()).ss_pcm_emit_host(_emit_table(segs), len(segs), C.c_void_p(out.data_ptr() if out.numel() else 0),
+                                               out.numel()), "ss_pcm_emit_host")
+
+
+def encode_host(samples, fmt: str, lib=None) -> bytes:
+    """ss_pcm_encode_host: float32 samples -> bytes in `fmt`, on the host, by the kernel's own encoders."""
+    lib = lib or L.load()
+    x = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+    out = np.empty(x.size * _SAMPLE_BYTES[FORMATS[fmt]], np.uint8)
+    L.check(lib.ss_pcm_encode_host(C.c_void_p(x.ctypes.data if x.size else 0), x.size, FORMATS[fmt],
+                                   C.c_void_p(out.ctypes.data if x.size else 0)), "ss_pcm_encode_host")
+    return out.tobytes()
+
+
+class PcmEmitter:
+    """The out side of a pool step (or of a PcmStreamEncoder): ONE engine.pcm_emit call for every session that answers at its own
+    rate and format, ONE device-to-host copy into pinned memory, then a bytes object per session.  The device and pinned buffers are
+    reused from call to call and grow by doubling.  Driven by one host thread, like the pools."""
+
+    def __init__(self, engine):
+        self.engine = engine
+        self.device = torch.device(engine.device)
+        self._dev = self._host = None
+        self.calls = 0                        # engine.pcm_emit calls since the emitter was made
+
+    def emit(self, items) -> List[bytes]:
+        """[(PcmOutState, tail or None, finished)] -> each one's new bytes; the states advance."""
+        segs, ranges, total = emit_plan(items, getattr(self.engine, "lib", None))
+        if not any(sg[8] or sg[5] > sg[4] for sg in segs):       # nothing new and nothing to flush anywhere: no call
+            return [b""] * len(items)
+        cuda = self.device.type == "cuda"
+        if self._dev is None or self._dev.numel() < total:
+            self._dev = torch.empty((max(2 * total, 4096),), dtype=torch.uint8, device=self.device)
+            self._host = torch.empty((max(2 * total, 4096),), dtype=torch.uint8, pin_memory=cuda)
+        self.engine.pcm_emit(segs, self._dev[:total])
+        self.calls += 1
+        if total:
+            self._host[:total].copy_(self._dev[:total], non_blocking=True)
+            if cuda:
+                torch.cuda.current_stream(self.device).synchronize()   # the bytes below are read from the pinned buffer
+        host = self._host.numpy()
+        out = []
+        for (st, _, finished), sg, (off, nbytes) in zip(items, segs, ranges):
+            out.append(host[off:off + nbytes].tobytes() if nbytes else b"")
+            if not st.flushed:
+                st.n, st.k, st.flushed = st.n + sg[8], sg[5], bool(finished)
+        return out
+
+
+class PcmStreamEncoder:
+    """The streaming output resampler and encoder without a pool, as Mp3StreamDecoder is for input: push() takes the next float32
+    samples of a 16-kHz stream (a tensor on the engine's device, or anything torch.as_tensor takes) and returns the bytes they settle
+    in `out`'s format at its rate; finished=True flushes the rest, after which reset() starts a new stream.  The concatenated
+    returns are encode(resample(whole stream)) byte for byte, however the stream was cut.  `engine`: a HipModel."""
+
+    def __init__(self, engine, out: PcmOut):
+        if not isinstance(out, PcmOut):
+            raise ValueError(f"a PcmOut, not {out!r}")
+        self.out = out
+        self._state = PcmOutState(out, engine)
+        self._emitter = PcmEmitter(engine)
+
+    def push(self, samples, finished: bool = False) -> bytes:
+        if self._state.flushed:
+            raise ValueError("the stream is finished: reset() starts a new one")
+        x = torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(self._emitter.device).contiguous()
+        return self._emitter.emit([(self._state, x, finished)])[0]
+
+    def reset(self):
+        self._state.reset()

@@ -10,14 +10,20 @@ Driven by one host thread, like the pool.
 
 An S2ST session opened with ``pcm_out="s16le"`` answers :class:`PcmSegment` (16-bit PCM bytes) instead of a SpeechSegment holding a
 Python list: the tails of all such writers of a step go through ONE ss_pcm_pack_s16 launch and ONE device-to-host copy into pinned
-memory, where a list-fed session pays one ``wav.tolist()`` copy each.  The bytes are frontend.write_wav's rounding of the samples."""
+memory, where a list-fed session pays one ``wav.tolist()`` copy each.  The bytes are frontend.write_wav's rounding of the samples.
+
+An S2ST session opened with ``pcm_out=PcmOut(fmt, sample_rate)`` answers :class:`PcmSegment` in that format at that rate: the tails of
+all such writers of a step, and the flush of those that finish without new speech, go through ONE ss_pcm_emit call (the streaming
+output resampler over each session's carried history, then the encoder; pcm.PcmEmitter) and ONE device-to-host copy, beside the pack
+call of the ``"s16le"`` sessions.  Over an utterance a session's contents concatenate to the encoding of ss_resample over its whole
+16-kHz output; between writes it holds back the 10-30 output samples whose filter window is not complete yet."""
 import time
 
 import numpy as np
 import torch
 
 from .frontend import SAMPLE_RATE
-from .pcm import PcmSegment, pack_s16_host
+from .pcm import PcmEmitter, PcmSegment, pack_s16_host
 from .simuleval_shim import SpeechSegment
 from .text_pool import KINDS as TEXT_KINDS
 from .text_pool import TextSessionPool, _Session
@@ -69,6 +75,8 @@ class SpeechSessionPool(TextSessionPool):
         super().__init__(model, max_sessions, max_rows, beam_mt=beam_mt)
         self.vocoder = getattr(vocoder, "hip", vocoder)
         self.t2u_causal = bool(getattr(model, "uni_encoder", False))   # the agent's ctc_generator: t2u_causal = model.uni_encoder
+        self._emitter = None                              # pcm.PcmEmitter of the PcmOut sessions, made with the first one's write
+        self._flush = []                                  # PcmOut sessions of the step that finish without new speech (_finish_empty)
 
     def _check_open(self, kind, args):
         if kind != "s2st":
@@ -98,6 +106,9 @@ class SpeechSessionPool(TextSessionPool):
         return ("write", prefix, ml, g.new_tokens)
 
     def _finish_empty(self, s):
+        if s.pcm_state is not None:                       # what its resampler still holds goes out with the step's emit call
+            self._flush.append(s)
+            return ("speech", b"", True, False)
         if s.pcm_out:                                     # a carried unfinished_wav goes out in the session's own format
             carried = s.unfinished_wav.cpu().numpy() if s.unfinished_wav is not None else np.zeros(0, np.float32)
             return ("speech", pack_s16_host(carried).tobytes() if carried.size else b"", True, False)
@@ -130,6 +141,7 @@ class SpeechSessionPool(TextSessionPool):
 
     def _write_side(self, mine, views, actions):
         t0 = time.perf_counter()
+        self._flush = []
         D = self.model.cfg.dec_dim
         rows = []                                         # (session, mt states [n, D], n_tail_pad)
         pads = []                                         # (index in rows, session's encoder view index, tokens)
@@ -176,6 +188,7 @@ class SpeechSessionPool(TextSessionPool):
                 voc.append((s, unit, len(cur)))
         t2 = time.perf_counter()
         handover, raw = 0.0, []                           # raw: (session, tail) of the pcm_out writers, packed together below
+        own = []                                          # the same of the PcmOut writers, emitted together below
         for dp in (True, False):
             grp = [v for v in voc if v[0].dur_prediction == dp]
             if not grp:
@@ -187,6 +200,9 @@ class SpeechSessionPool(TextSessionPool):
                 if s.unfinished_wav is not None and len(s.unfinished_wav) > 0:
                     wav = torch.cat((s.unfinished_wav, wav), 0)
                 s.unit = unit
+                if s.pcm_state is not None:
+                    own.append((s, wav))
+                    continue
                 if s.pcm_out:
                     raw.append((s, wav))
                     continue
@@ -196,11 +212,32 @@ class SpeechSessionPool(TextSessionPool):
             handover += time.perf_counter() - th
         th = time.perf_counter()
         n_out = self._pack_out(raw, actions) if raw else 0
+        emit_calls, emit_bytes = self._emit_out(own, self._flush, actions) if own or self._flush else (0, 0)
+        self._flush = []
         t3 = time.perf_counter()
         # handover_s: from the tails' views in hand to the contents the segments carry (lists or bytes), both routes; it lies inside
         # vocoder_s, which keeps its meaning (the tail calls and what follows them)
         self._side_times = {"mt_features_s": t1 - t0, "units_s": t2 - t1, "vocoder_s": t3 - t2, "handover_s": handover + (t3 - th),
-                            "speech_writers": len(voc), "pcm_pack_calls": 1 if n_out else 0, "pcm_bytes_out": 2 * n_out}
+                            "speech_writers": len(voc), "pcm_pack_calls": 1 if n_out else 0, "pcm_bytes_out": 2 * n_out,
+                            "pcm_emit_calls": emit_calls, "pcm_emit_bytes_out": emit_bytes}
+
+    def _emit_out(self, own, flush, actions):
+        """The tails of a step's PcmOut writers and the flushes of its PcmOut sessions that finish without new speech -> bytes at
+        each session's rate and format: ONE pcm_emit call over all of them, the tails taken where they lie, and ONE device-to-host
+        copy (pcm.PcmEmitter).  A final write ends the utterance, so it flushes too.  -> (calls made: 0 or 1, bytes out)."""
+        if self._emitter is None:
+            self._emitter = PcmEmitter(self.model)
+        items = [(s.pcm_state, wav.contiguous(), bool(s.states.source_finished)) for s, wav in own]
+        for s in flush:
+            carried = s.unfinished_wav if s.unfinished_wav is not None and len(s.unfinished_wav) > 0 else None
+            items.append((s.pcm_state, carried, True))
+        before = self._emitter.calls
+        contents = self._emitter.emit(items)
+        for (s, _), content in zip(own, contents):
+            actions[s.sid] = ("speech", content, False, s.states.source_finished)
+        for s, content in zip(flush, contents[len(own):]):
+            actions[s.sid] = ("speech", content, True, False)
+        return self._emitter.calls - before, sum(len(c) for c in contents)
 
     def _pack_out(self, raw, actions) -> int:
         """The tails of a step's pcm_out writers -> 16-bit PCM bytes: ONE ss_pcm_pack_s16 launch over all of them and ONE
@@ -233,15 +270,16 @@ class SpeechSessionPool(TextSessionPool):
         return total
 
     def _segment(self, s, a):
+        pcm_out = s.pcm_out
+        fmt, rate = (pcm_out.fmt, pcm_out.sample_rate) if s.pcm_state is not None else (pcm_out, SAMPLE_RATE)
         if a[0] == "write":                               # the front-end's early return of a finished source: no speech
-            if s.pcm_out:
-                return PcmSegment(index=0, content=b"", fmt=s.pcm_out, sample_rate=SAMPLE_RATE, finished=True)
+            if pcm_out:
+                return PcmSegment(index=0, content=b"", fmt=fmt, sample_rate=rate, finished=True)
             return SpeechSegment(index=0, content=[], sample_rate=SAMPLE_RATE, finished=True)
         _, content, finished, done = a
-        pcm_out = s.pcm_out
         if done:                                          # the agent's reset(): a fresh utterance, its slot back to the pool
             s.reset()
             self._release(s)
         if pcm_out:
-            return PcmSegment(index=0, content=content, fmt=pcm_out, sample_rate=SAMPLE_RATE, finished=finished)
+            return PcmSegment(index=0, content=content, fmt=fmt, sample_rate=rate, finished=finished)
         return SpeechSegment(index=0, content=content, sample_rate=SAMPLE_RATE, finished=finished)

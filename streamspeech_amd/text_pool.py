@@ -27,7 +27,7 @@ import torch
 
 from .engine import MT_BEAM_MAX, plan_beam_groups
 from .frontend import SAMPLE_RATE, OnlineFeatureExtractor, unsettled_fbank_frames
-from .pcm import PcmArena, PcmFormat
+from .pcm import PcmArena, PcmFormat, PcmOut
 from .simuleval_shim import AgentStates, EmptySegment, TextSegment
 from .text_policy import mt_max_len, s2tt_gate
 
@@ -71,6 +71,7 @@ class _Session:
         self.pending = False
         self.pcm_in = None                    # a PcmFormat: the session is fed by push_pcm, and counts samples (fe.n_pcm) instead of
         self.pcm_out = None                   # keeping them in states.source; "s16le": it answers PcmSegment (speech_pool.py)
+        self.pcm_state = None                 # a pcm.PcmOutState when pcm_out is a PcmOut: carry buffer, taps, counters (speech_pool.py)
         self.pcm_chunk = None                 # (byte view, frames) pushed for the next step
         self.mp3_in = None                    # {"join": bool}: the session is fed by push_mp3 and counts samples as a PCM-fed one does
         self.mp3 = None                       # its mp3.Mp3Stream (host bitstream state), made at open()
@@ -95,6 +96,8 @@ class _Session:
         self.tgt_text = ""
         self.states.reset()
         self.fe.clear_cache()
+        if self.pcm_state is not None:        # a fresh utterance: nothing received, nothing emitted, nothing carried
+            self.pcm_state.reset()
         if self.mp3 is not None:              # a fresh utterance is a fresh stream: bitstream state and carried blocks start over
             self.mp3.reset()
         self.mp3_state, self.mp3_chunk, self.mp3_held = None, None, 0
@@ -123,19 +126,22 @@ class TextSessionPool:
 
     # ---- lifecycle ------------------------------------------------------------------------------------------------------------
     def open(self, kind: str, args, dicts: Optional[dict] = None, pcm_in: Optional[PcmFormat] = None,
-             pcm_out: Optional[str] = None, mp3_in=None) -> int:
+             pcm_out=None, mp3_in=None) -> int:
         """A new session; `args` are the agent's own parsed flags (segment size, lagging_k1, stride_n, sample rate, chunk sizes).
         `dicts` overrides the dictionaries the agent would load from the flags (keys source_unigram / target_unigram).
         pcm_in=PcmFormat(...): the session is fed raw PCM at args.sample_rate through push_pcm() and nothing else.
         pcm_out="s16le" (s2st sessions only): it answers PcmSegment with 16-bit PCM bytes instead of SpeechSegment with a list.
+        pcm_out=PcmOut(fmt, sample_rate) (s2st sessions only): it answers PcmSegment in that format at that rate, resampled and
+        encoded on the device with a short history carried per session (speech_pool.py); no other string is accepted.
         mp3_in=True or {"join": bool}: the session is fed an MP3 stream whose sample rate is args.sample_rate through push_mp3() and
         nothing else (join: the stream was captured mid-way, mp3.Mp3StreamDecoder).  Not together with pcm_in."""
         if kind not in self.KINDS:
             raise ValueError(f"session kind {kind!r}: one of {self.KINDS}")
         if pcm_in is not None and not isinstance(pcm_in, PcmFormat):
             raise ValueError(f"pcm_in is a PcmFormat, not {pcm_in!r}")
-        if pcm_out is not None and (pcm_out != "s16le" or kind != "s2st"):
-            raise ValueError(f"pcm_out={pcm_out!r} for a {kind} session: only \"s16le\", and only for s2st sessions")
+        if pcm_out is not None and ((not isinstance(pcm_out, PcmOut) and not (isinstance(pcm_out, str) and pcm_out == "s16le"))
+                                    or kind != "s2st"):
+            raise ValueError(f"pcm_out={pcm_out!r} for a {kind} session: only \"s16le\" or a PcmOut, and only for s2st sessions")
         if mp3_in is not None and mp3_in is not False:
             if pcm_in is not None:
                 raise ValueError("mp3_in and pcm_in exclude each other: a session is fed one way for its whole life")
@@ -154,6 +160,9 @@ class TextSessionPool:
         self._next += 1
         s = self._new_session(sid, kind, args, dicts)
         s.pcm_in, s.pcm_out = pcm_in, pcm_out
+        if isinstance(pcm_out, PcmOut):
+            from .pcm import PcmOutState
+            s.pcm_state = PcmOutState(pcm_out, self.model)
         if mp3_in is not None:
             from .mp3 import Mp3Stream
             s.mp3_in, s.mp3 = mp3_in, Mp3Stream(mp3_in["join"], name=f"session {sid}")
@@ -177,6 +186,7 @@ class TextSessionPool:
     def close(self, sid: int):
         s = self._get(sid)
         self._release(s)
+        s.pcm_state = None
         if s.mp3 is not None:
             s.mp3.close()
             s.mp3, s.mp3_state, s.mp3_chunk = None, None, None
@@ -478,6 +488,8 @@ class TextSessionPool:
                           # write side sets the pack side (ss_pcm_pack_s16 launches, bytes downloaded)
                           "pcm_uploads": 1 if pcm_bytes else 0, "pcm_scatter_calls": 1 if pcm_bytes else 0, "pcm_bytes_in": pcm_bytes,
                           "pcm_pack_calls": 0, "pcm_bytes_out": 0,
+                          # sessions that answer at their own rate and format (PcmOut): ss_pcm_emit calls of the step (0 or 1), bytes
+                          "pcm_emit_calls": 0, "pcm_emit_bytes_out": 0,
                           # the MP3 route: uploads and ss_mp3_stream_synthesize calls of the step (0 or 1 each), MP3 bytes the step's
                           # pushes brought, granule-channels decoded
                           "mp3_uploads": 1 if mp3_bytes else 0, "mp3_synth_calls": 1 if mp3_recs else 0, "mp3_bytes_in": mp3_bytes_in,
