@@ -829,6 +829,56 @@ int ss_op_dwconv_bn_silu(void* stream, const float* dx, int ldx, float* dy, int 
                          int K, const float* mean, const float* var, const float* gamma,
                          const float* beta, float eps, int T, int C, int chunk);
 
+/* ---- the decode glue kernels (csrc/elementwise.hip), each launcher with the caller's arguments unchanged; every pointer is a DEVICE
+ * pointer, NULL where the launcher's argument is optional (segs with nseg = 0: the single-utterance form).  Semantics: the comments
+ * of csrc/elementwise.hpp; tests/test_glue_ops_gpu.py runs them against tests/glue_ref.py. ---- */
+int ss_op_masked_argmax(void* stream, const float* logits, int ld, int M, int N, int mask0, int mask1, int mask2, int force,
+                        int32_t* ids, const int32_t* row_max_len, int step, int force_id, const int32_t* row_min_len, int ban_id);
+int ss_op_ctc_collapse(void* stream, const int32_t* raw, int T, int blank, int pad, int32_t* tokens, int32_t* index, int32_t* count,
+                       const int32_t* segs, int nseg);                /* segs {start, len}: count[s] */
+int ss_op_dur_predict(void* stream, const float* logdur, const int32_t* forced, int K, int32_t* dur, int32_t* cum,
+                      const int32_t* segs, int nseg);                 /* segs {start, len}: cum of segment s at start + s */
+int ss_op_repeat_rows(void* stream, const float* emb, const int32_t* cum, int K, int D, float* out, int F, const int32_t* segs,
+                      int nseg);                                      /* segs {unit_start, n_units, frame_start, n_frames}; F = max */
+int ss_op_embed_tokens(void* stream, const int32_t* tok, const float* emb, const float* pos_table, float scale, int pos0, float* out,
+                       int n, int D, int pos_stride, int pad_id, int vocab);
+int ss_op_embed_tokens_rows(void* stream, const int32_t* tok, const float* emb, const float* pos_table, int pos_rows, float scale,
+                            int pos0, const int32_t* row_pos, float* out, int n, int D, int pad_id, int vocab);
+int ss_op_upsample_add_pos(void* stream, const float* src, int n, int up, const float* pos_row, float pad_value, float* out, int D);
+int ss_op_gather_rows(void* stream, const int32_t* idx, const float* table, int D, float* out, int n, int rows);
+int ss_op_scatter_rows(void* stream, const int32_t* dst_row, const float* src, int lds, float* dst, int ldd, int D, int n,
+                       int dst_rows);
+int ss_op_conv_post_tanh(void* stream, const float* x, int T, int C, const float* w, const float* bias, float slope, float* wav,
+                         const int32_t* segs, int nseg);              /* segs {sample_start, n_samples}; T = max */
+int ss_op_conv_post_tanh_crop(void* stream, const float* x, int C, const float* w, const float* bias, float slope, float* wav,
+                              const int32_t* segs, int nseg, int max_keep);   /* segs {sample_start, n_samples, first, out_start} */
+
+/* ---- the kernels of the beam search (csrc/beam.hip), one launch each.  R = B * k hypothesis rows; the candidate lists have a row
+ * stride of SS_OP_BEAM_CAND entries whatever k is. ---- */
+#define SS_OP_BEAM_CAND 64
+/* beam_topk_kernel: logits [R][V], cum [R], max_len / npre / done [B] -> the 2k best (score, token) of every taking-part row in
+ * cand_s / cand_t [R][SS_OP_BEAM_CAND].  1 <= k <= 32, V >= 2k + 1, V <= 16384 (SS_ERR_ARG otherwise). */
+int ss_op_beam_topk(void* stream, const float* logits, int R, int V, int k, int t_step, int min_len, const int32_t* max_len,
+                    const int32_t* npre, const int32_t* done, const float* cum, int pad, int unk, int eos, float unk_pen,
+                    float* cand_s, int32_t* cand_t);
+/* The search state beam_merge_kernel works on (BeamState of csrc/beam.hip field for field; all DEVICE pointers):
+ * tok / cum [t_step + 2][R] step-major, anc [2][R][Lc] (anc[t & 1] read at lock-step index t), cand_s / cand_t [R][SS_OP_BEAM_CAND],
+ * ignore [R], done / max_len / npre / fin_cnt [B], fin_score / fin_len [B][k], fin_tok / fin_pos / fin_anc [B][k][Lc]. */
+typedef struct ss_op_beam_state {
+  int32_t* tok; float* cum; int32_t* anc; float* cand_s; int32_t* cand_t; int32_t* ignore; int32_t* done; int32_t* max_len;
+  int32_t* npre;
+  int32_t* fin_cnt; float* fin_score; int32_t* fin_len; int32_t* fin_tok; float* fin_pos; int32_t* fin_anc;
+} ss_op_beam_state;
+/* beam_merge_kernel for one step (lock-step index t_step, first free cache index c0; c0 + t_step + 2 <= Lc) */
+int ss_op_beam_merge(void* stream, const ss_op_beam_state* st, int B, int k, int Lc, int V, int t_step, int c0, int eos,
+                     int normalize);
+/* beam_prefix_score_kernel: lp[i] = masked log-softmax of logits row i at ftok[i] (rows with ftok < 0 are left as they are) */
+int ss_op_beam_prefix_score(void* stream, const float* logits, int rows, int V, const int32_t* ftok, int pad, int unk, float unk_pen,
+                            float* lp);
+/* beam_prefix_chain_kernel: per utterance b the float32 chain over lp[row0[b] .. + npre[b]) -> pos (same rows), cum0[b * k] */
+int ss_op_beam_prefix_chain(void* stream, const float* lp, const int32_t* row0, const int32_t* npre, int B, int k, float* cum0,
+                            float* pos);
+
 #ifdef __cplusplus
 }
 #endif

@@ -620,3 +620,46 @@ extern "C" int ss_batch_mt_beam_continue_plan(int B, int beam, const int32_t* h_
   }
   return SS_OK;
 }
+
+// ---- op-level entry points of the kernels above (include/streamspeech_hip.h; tests/test_glue_ops_gpu.py) ----
+extern "C" int ss_op_beam_topk(void* stream, const float* logits, int R, int V, int k, int t_step, int min_len, const int32_t* max_len,
+                               const int32_t* npre, const int32_t* done, const float* cum, int pad, int unk, int eos, float unk_pen,
+                               float* cand_s, int32_t* cand_t) {
+  if (R <= 0 || k < 1 || k > kMaxBeam || R % k != 0) return SS_ERR_ARG;
+  if (V < 2 * k + 1 || (size_t)V * sizeof(float) > 65536) return SS_ERR_ARG;     // the search's own limits (beam_continue_plan)
+  hipLaunchKernelGGL(beam_topk_kernel, dim3(R), dim3(256), V * sizeof(float), (hipStream_t)stream, logits, V, k, t_step, min_len,
+                     max_len, npre, done, cum, pad, unk, eos, unk_pen, cand_s, cand_t);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+extern "C" int ss_op_beam_merge(void* stream, const ss_op_beam_state* x, int B, int k, int Lc, int V, int t_step, int c0, int eos,
+                                int normalize) {
+  if (!x || B <= 0 || k < 1 || k > kMaxBeam || t_step < 0 || c0 < 0 || c0 + t_step + 2 > Lc) return SS_ERR_ARG;
+  BeamState st;
+  st.tok = x->tok; st.cum = x->cum; st.anc = x->anc; st.cand_s = x->cand_s; st.cand_t = x->cand_t; st.ignore = x->ignore;
+  st.done = x->done; st.max_len = x->max_len; st.npre = x->npre;
+  st.fin_cnt = x->fin_cnt; st.fin_score = x->fin_score; st.fin_len = x->fin_len; st.fin_tok = x->fin_tok; st.fin_pos = x->fin_pos;
+  st.fin_anc = x->fin_anc;
+  hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, st, k, B * k, Lc, V, t_step, c0, eos,
+                     normalize ? 1 : 0);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+extern "C" int ss_op_beam_prefix_score(void* stream, const float* logits, int rows, int V, const int32_t* ftok, int pad, int unk,
+                                       float unk_pen, float* lp) {
+  if (rows <= 0 || V <= 0) return SS_ERR_ARG;
+  hipLaunchKernelGGL(beam_prefix_score_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, V, ftok, pad, unk, unk_pen, lp);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+extern "C" int ss_op_beam_prefix_chain(void* stream, const float* lp, const int32_t* row0, const int32_t* npre, int B, int k,
+                                       float* cum0, float* pos) {
+  if (B <= 0 || k < 1) return SS_ERR_ARG;
+  hipLaunchKernelGGL(beam_prefix_chain_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, lp, row0, npre, B, k, cum0,
+                     pos);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}

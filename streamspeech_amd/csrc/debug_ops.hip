@@ -129,6 +129,53 @@ extern "C" int ss_op_layernorm(void* stream, const float* dx, int ldx, float* dy
   return launch_layernorm(dx, ldx, dy, ldy, dg, db, M, D, eps, (hipStream_t)stream);
 }
 
+// The decode glue kernels of elementwise.hip, each launcher with the caller's arguments unchanged (tests/test_glue_ops_gpu.py)
+extern "C" int ss_op_masked_argmax(void* stream, const float* logits, int ld, int M, int N, int mask0, int mask1, int mask2, int force,
+                                   int32_t* ids, const int32_t* row_max_len, int step, int force_id, const int32_t* row_min_len,
+                                   int ban_id) {
+  return launch_masked_argmax(logits, ld, M, N, mask0, mask1, mask2, force, ids, (hipStream_t)stream, row_max_len, step, force_id,
+                              row_min_len, ban_id);
+}
+extern "C" int ss_op_ctc_collapse(void* stream, const int32_t* raw, int T, int blank, int pad, int32_t* tokens, int32_t* index,
+                                  int32_t* count, const int32_t* segs, int nseg) {
+  return launch_ctc_collapse(raw, T, blank, pad, tokens, index, count, (hipStream_t)stream, segs, nseg);
+}
+extern "C" int ss_op_dur_predict(void* stream, const float* logdur, const int32_t* forced, int K, int32_t* dur, int32_t* cum,
+                                 const int32_t* segs, int nseg) {
+  return launch_dur_predict(logdur, forced, K, dur, cum, (hipStream_t)stream, segs, nseg);
+}
+extern "C" int ss_op_repeat_rows(void* stream, const float* emb, const int32_t* cum, int K, int D, float* out, int F,
+                                 const int32_t* segs, int nseg) {
+  return launch_repeat_rows(emb, cum, K, D, out, F, (hipStream_t)stream, segs, nseg);
+}
+extern "C" int ss_op_embed_tokens(void* stream, const int32_t* tok, const float* emb, const float* pos_table, float scale, int pos0,
+                                  float* out, int n, int D, int pos_stride, int pad_id, int vocab) {
+  return launch_embed_tokens(tok, emb, pos_table, scale, pos0, out, n, D, (hipStream_t)stream, pos_stride, pad_id, vocab);
+}
+extern "C" int ss_op_embed_tokens_rows(void* stream, const int32_t* tok, const float* emb, const float* pos_table, int pos_rows,
+                                       float scale, int pos0, const int32_t* row_pos, float* out, int n, int D, int pad_id, int vocab) {
+  return launch_embed_tokens_rows(tok, emb, pos_table, pos_rows, scale, pos0, row_pos, out, n, D, (hipStream_t)stream, pad_id, vocab);
+}
+extern "C" int ss_op_upsample_add_pos(void* stream, const float* src, int n, int up, const float* pos_row, float pad_value, float* out,
+                                      int D) {
+  return launch_upsample_add_pos(src, n, up, pos_row, pad_value, out, D, (hipStream_t)stream);
+}
+extern "C" int ss_op_gather_rows(void* stream, const int32_t* idx, const float* table, int D, float* out, int n, int rows) {
+  return launch_gather_rows(idx, table, D, out, n, (hipStream_t)stream, rows);
+}
+extern "C" int ss_op_scatter_rows(void* stream, const int32_t* dst_row, const float* src, int lds, float* dst, int ldd, int D, int n,
+                                  int dst_rows) {
+  return launch_scatter_rows(dst_row, src, lds, dst, ldd, D, n, dst_rows, (hipStream_t)stream);
+}
+extern "C" int ss_op_conv_post_tanh(void* stream, const float* x, int T, int C, const float* w, const float* bias, float slope,
+                                    float* wav, const int32_t* segs, int nseg) {
+  return launch_conv_post_tanh(x, T, C, w, bias, slope, wav, (hipStream_t)stream, segs, nseg);
+}
+extern "C" int ss_op_conv_post_tanh_crop(void* stream, const float* x, int C, const float* w, const float* bias, float slope, float* wav,
+                                         const int32_t* segs, int nseg, int max_keep) {
+  return launch_conv_post_tanh_crop(x, C, w, bias, slope, wav, segs, nseg, max_keep, (hipStream_t)stream);
+}
+
 // test ops: one process-wide key-split scratch (callers are serial), counters zero before the first launch
 static int op_attn_bind_split(AttnArgs& a) {
   static void* scratch = nullptr;

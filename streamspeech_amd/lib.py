@@ -71,6 +71,15 @@ class SSOpPoolAttnArgs(C.Structure):
         ("nsess", C.c_int32), ("qtiles", C.c_int32), ("H", C.c_int32),
         ("scale", _f)]
 
+class SSOpBeamState(C.Structure):
+    """ss_op_beam_state: BeamState (csrc/beam.hip) field for field, pointers as device addresses."""
+    _fields_ = [(n, _vp) for n in (
+        "tok", "cum", "anc", "cand_s", "cand_t", "ignore", "done", "max_len", "npre",
+        "fin_cnt", "fin_score", "fin_len", "fin_tok", "fin_pos", "fin_anc")]
+
+
+SS_OP_BEAM_CAND = 64     # row stride of the candidate lists of ss_op_beam_topk / ss_op_beam_merge
+
 # symbol -> (restype, argtypes); must list every function include/streamspeech_hip.h declares
 SIGNATURES = {
     "ss_abi_version": (_i, []),
@@ -213,6 +222,21 @@ SIGNATURES = {
     "ss_op_attention_pool": (_i, [_vp, C.POINTER(SSOpPoolAttnArgs)]),
     "ss_debug_attention_no_mfma": (_i, [_i]),
     "ss_op_dwconv_bn_silu": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _i]),
+    "ss_op_masked_argmax": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i]),
+    "ss_op_ctc_collapse": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "ss_op_dur_predict": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
+    "ss_op_repeat_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),
+    "ss_op_embed_tokens": (_i, [_vp, _vp, _vp, _vp, _f, _i, _vp, _i, _i, _i, _i, _i]),
+    "ss_op_embed_tokens_rows": (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _i, _i, _i, _i]),
+    "ss_op_upsample_add_pos": (_i, [_vp, _vp, _i, _i, _vp, _f, _vp, _i]),
+    "ss_op_gather_rows": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i]),
+    "ss_op_scatter_rows": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i]),
+    "ss_op_conv_post_tanh": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _vp, _vp, _i]),
+    "ss_op_conv_post_tanh_crop": (_i, [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _i]),
+    "ss_op_beam_topk": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "ss_op_beam_merge": (_i, [_vp, C.POINTER(SSOpBeamState), _i, _i, _i, _i, _i, _i, _i, _i]),
+    "ss_op_beam_prefix_score": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _vp]),
+    "ss_op_beam_prefix_chain": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
 }
 
 _lib = None
