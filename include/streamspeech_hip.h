@@ -350,6 +350,78 @@ int ss_pcm_emit_host(const ss_pcm_emit_seg* h_segs, int n_segs, void* h_out, int
 /* The encodings alone: n float samples at h_src -> n * sample_bytes(fmt) bytes at h_out.  Host only. */
 int ss_pcm_encode_host(const float* h_src, int64_t n, int fmt, void* h_out);
 
+/* Endpointing of live PCM streams (streamspeech_amd/endpoint.py): an energy scan over the new frames of every
+ * session of a pool step, on the device where the decoded samples already lie, that cuts a continuous stream into utterances.
+ * Framing is the session's own fbank framing at its source rate: frame j of the stream (counted from the session's open or reset,
+ * int64) covers samples [j H, j H + W) of the +-1-scaled float32 history.  The arithmetic (csrc/vad.hpp, one set of inline
+ * functions for the kernel and the host twin; float32, no libm call but fmaf, no contraction the source does not spell):
+ *   power   lane l of 64 adds x[l], x[l + 64], ... in ascending order; the 64 partial sums go through the tree
+ *           p[l] += p[l + o], o = 32, 16, .. 1; m = sum * (1 / W); the second pass accumulates fmaf(x - m, x - m, acc) the same way,
+ *           P = sum2 * (1 / W).  Two passes, so a DC offset is not speech.
+ *   frame 0 of a stream: not speech, F = max(p_min, P).
+ *   else    speech = P > max(p_abs, F * snr);  F = max(p_min, min(P, F * (speech ? 1 : rise))).
+ *   IDLE    a speech frame extends run (onset = j where the run begins), another zeroes it; run >= min_speech: START at onset,
+ *           mode = SPEECH, utt_first_frame = onset, last_speech = j, run = 0, and the scan goes on.
+ *   SPEECH  a speech frame sets last_speech = j and zeroes run, another extends run.  run >= end_silence: END, cut sample
+ *           (last_speech + 1 + post_roll) H + (W - H), mode = IDLE, run = 0, the scan stops.  Otherwise
+ *           j + 1 - utt_first_frame >= max_frames (the frame of a START included): FORCED, cut sample (j + 1) H + (W - H), the mode
+ *           stays SPEECH, utt_first_frame = j + 1, last_speech = j, run = 0 (the next utterance begins at the cut), the scan stops.
+ * All thresholds are linear power ratios; the caller converts them from dB once. */
+enum { SS_VAD_IDLE = 0, SS_VAD_SPEECH = 1 };
+enum { SS_VAD_START = 1, SS_VAD_END = 2, SS_VAD_FORCED = 4 };
+
+/* A session's scan state between calls (device memory for ss_vad_scan, host memory for ss_vad_scan_host); all zero = a fresh stream. */
+typedef struct ss_vad_state {
+  int64_t onset;             /* first frame of the current run of speech frames (IDLE) */
+  int64_t last_speech;       /* last speech frame of the utterance (SPEECH) */
+  int64_t utt_first_frame;   /* frame the utterance's length is counted from */
+  float floor;               /* F after the last scanned frame */
+  int32_t mode;              /* SS_VAD_IDLE / SS_VAD_SPEECH */
+  int32_t run;               /* speech frames in a row (IDLE), other frames in a row (SPEECH) */
+  int32_t reserved;          /* 0 */
+} ss_vad_state;              /* 40 bytes */
+
+/* One session of a ss_vad_scan call. */
+typedef struct ss_vad_seg {
+  const float* hist;         /* the sample history; hist[0] is sample hist_first of the stream */
+  ss_vad_state* state;       /* read, then rewritten by the call */
+  float* powers;             /* NULL, or n_frames floats that receive P of every frame the call scanned (tests, diagnostics) */
+  int64_t hist_first;        /* absolute index of hist[0] */
+  int64_t n_hist;            /* samples present */
+  int64_t first_frame;       /* first frame to scan */
+  int32_t n_frames;          /* frames to scan at most: the scan stops early at END / FORCED */
+  int32_t H, W;              /* shift and window in samples */
+  float p_abs, p_min, snr, rise;
+  int32_t min_speech, end_silence, post_roll, max_frames;   /* in frames */
+  int32_t reserved;          /* 0 */
+} ss_vad_seg;                /* 96 bytes */
+
+typedef struct ss_vad_result {
+  int64_t consumed;          /* the first frame the call did not scan */
+  int64_t start_frame;       /* onset of the START the call raised, else -1 */
+  int64_t cut_sample;        /* cut of the END / FORCED the call raised, else -1 */
+  int64_t last_speech;       /* the state's last_speech after the call (meaningful in SPEECH and with END) */
+  int32_t events;            /* SS_VAD_START | SS_VAD_END or SS_VAD_FORCED: at most one START and one stopping event */
+  int32_t mode;              /* the state's mode after the call */
+} ss_vad_result;             /* 40 bytes */
+
+/* One call per pool step for every endpointed session: segment i scans frames [first_frame, first_frame + n_frames) of its history,
+ * or up to its first END / FORCED, rewrites its state record and writes d_results[i] (device memory, n_segs records) and, if asked,
+ * its powers -- and nothing else.  Pointers of a segment are device memory; h_segs is host memory read before the call returns.
+ * ONE launch whatever the number of segments, stream-ordered, no atomics, no host round trip: a workgroup owns a segment, its waves
+ * compute frame powers in parallel, in batches that go through LDS, and after each batch one lane walks the state machine over it.
+ * The device copy of the table is a buffer the library keeps per stream.
+ * Every refusal is made before any HIP call, for the whole call.  n_segs < 0: SS_ERR_ARG.  n_segs == 0: SS_OK, no launch.  A NULL
+ * h_segs or d_results: SS_ERR_ARG.  Then, over all segments in order, SS_ERR_ARG for: a NULL state or reserved != 0; H < 1, W < 1,
+ * H > W or W past 2^20; min_speech < 1, end_silence < 1, post_roll < 0, post_roll > end_silence, max_frames < 1; p_abs or p_min negative or NaN,
+ * snr or rise not positive (or NaN); n_frames, n_hist, first_frame or hist_first negative, or first_frame + n_frames past 2^40;
+ * a frame range whose samples the history does not hold (first_frame H < hist_first, or (first_frame + n_frames - 1) H + W past
+ * hist_first + n_hist); a NULL hist with frames to scan. */
+int ss_vad_scan(void* stream, const ss_vad_seg* h_segs, int n_segs, ss_vad_result* d_results);
+/* The same call on host buffers (every pointer host memory), from the same inline functions: the same powers, states and results,
+ * bit for bit.  Host only, no HIP call; the same refusals in the same order. */
+int ss_vad_scan_host(const ss_vad_seg* h_segs, int n_segs, ss_vad_result* h_results);
+
 /* Offline driver only: d_out[r] = max over the vocabulary, ids mask0..2 skipped (< 0: none), of
  * log_softmax(d_logits[r, :]) -- the per-position score `lprobs.max(dim=2)` of the reference's offline unit search
  * (researches/ctc_unity/ctc_generator.py:55-63: pad / unk / eos set to -inf AFTER the softmax), which fairseq-generate

@@ -211,6 +211,13 @@ class BatchMixin:
         from . import pcm
         pcm.emit(self.lib, _stream(), segs, out)
 
+    def vad_scan(self, segs, results: torch.Tensor):
+        """The endpoint scan of every endpointed session of a step, one launch (ss_vad_scan; endpoint.seg_table names the segment
+        tuple): each session's device state record is rewritten and its result record goes to row i of the uint8 device tensor
+        `results` [n, 40]."""
+        from . import endpoint
+        endpoint.scan(self.lib, _stream(), segs, results)
+
     def fbank_sr_rows(self, n_in: int, sr_in: int) -> Optional[Tuple[int, int]]:
         """(fbank rows, final fbank rows) of n_in samples at sr_in Hz (fbank_sr_rows); None for a rate batch_fbank_frames_sr refuses."""
         return fbank_sr_rows(n_in, *resample_ratio(sr_in), lib=self.lib)

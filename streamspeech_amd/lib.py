@@ -43,6 +43,27 @@ class SSPcmEmitSeg(C.Structure):
                 ("half", C.c_int32), ("fmt", C.c_int32), ("finished", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SSVadState(C.Structure):
+    """ss_vad_state: a session's scan state between ss_vad_scan calls (40 bytes); all zero = a fresh stream."""
+    _fields_ = [("onset", C.c_int64), ("last_speech", C.c_int64), ("utt_first_frame", C.c_int64), ("floor", C.c_float),
+                ("mode", C.c_int32), ("run", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SSVadSeg(C.Structure):
+    """ss_vad_seg: one session of a ss_vad_scan call (96 bytes)."""
+    _fields_ = [("hist", _vp), ("state", _vp), ("powers", _vp), ("hist_first", C.c_int64), ("n_hist", C.c_int64),
+                ("first_frame", C.c_int64), ("n_frames", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("p_abs", C.c_float), ("p_min", C.c_float), ("snr", C.c_float), ("rise", C.c_float),
+                ("min_speech", C.c_int32), ("end_silence", C.c_int32), ("post_roll", C.c_int32), ("max_frames", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class SSVadResult(C.Structure):
+    """ss_vad_result: what a ss_vad_scan call reports per session (40 bytes)."""
+    _fields_ = [("consumed", C.c_int64), ("start_frame", C.c_int64), ("cut_sample", C.c_int64), ("last_speech", C.c_int64),
+                ("events", C.c_int32), ("mode", C.c_int32)]
+
+
 class SSOpAttnArgs(C.Structure):
     """ss_op_attn_args: AttnArgs (csrc/attention.hpp) field for field, pointers as device addresses."""
     _fields_ = [
@@ -118,6 +139,8 @@ SIGNATURES = {
     "ss_pcm_emit": (_i, [_vp, _vp, _i, _vp, _i64]),
     "ss_pcm_emit_host": (_i, [_vp, _i, _vp, _i64]),
     "ss_pcm_encode_host": (_i, [_vp, _i64, _i, _vp]),
+    "ss_vad_scan": (_i, [_vp, _vp, _i, _vp]),
+    "ss_vad_scan_host": (_i, [_vp, _i, _vp]),
     "ss_row_max_logprob": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ss_log_softmax": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ss_encoder_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
