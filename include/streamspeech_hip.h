@@ -852,6 +852,42 @@ int ss_op_conv_gemm(void* stream, const float* dA, int lda, const float* dW, con
                     const float* dR, int ldr, const float* dR2, int ldr2, float* dC, int ldc,
                     int M, int N, int Cin, int taps, int dil, int stride, int pad, int in_len,
                     int chunk, int in_act, float in_slope, int act, float alpha, float div, int glu);
+/* Every form of the conv launcher (csrc/gemm.hpp): the fields mirror the GemmArgs fields a caller can set, one to one (all pointers
+ * DEVICE pointers, NULL where optional); the call fills a GemmArgs and returns what launch_conv_gemm returns.  On top of
+ * ss_op_conv_gemm: the ragged pack (segs: nseg x {out_start, out_len, in_start, in_len}, max_seg_out = the longest out_len; M and
+ * in_len are then the packed totals), the pre-activated twin dC2 = leaky_relu(dC, c2_slope), the slope of a leaky-ReLU epilogue
+ * (act_slope), and same_rows as the caller states it (1: stride 1, output row m reads rows m - pad + j * dil of the same packed
+ * buffer, segments contiguous with out_start == in_start -- what the persistent slab kernels require).
+ * tests/test_slab_ops_gpu.py runs every slab conv kernel through it against tests/slab_ref.py. */
+typedef struct ss_op_conv_args {
+  const float* A; const float* W; const float* bias; const float* R; const float* R2; float* C; float* C2;
+  int32_t lda, ldc, ldr, ldr2, ldc2;
+  int32_t M, N, Cin, taps, dil, stride, pad, in_len, chunk;
+  int32_t in_act; float in_slope;
+  int32_t act; float act_slope, alpha, div, c2_slope;
+  int32_t glu;
+  const int32_t* segs; int32_t nseg, max_seg_out;
+  int32_t same_rows;
+} ss_op_conv_args;
+int ss_op_conv_gemm_ex(void* stream, const ss_op_conv_args* a);
+/* The fused ResBlock half of the narrow vocoder stages (csrc/conv_slab.hip, launch_conv_pair with the caller's arguments unchanged):
+ * dC = conv2(lrelu(conv1_dil(lrelu(dA)) + db1)) + db2 + dA [+ dR2] [/ div], dC2 = leaky_relu(dC, c2_slope) when set; C = 16 / 32,
+ * odd taps, M >= 2048 packed rows; d_segs as above ({start, len, ., .}).  SS_ERR_ARG for what the kernel does not take. */
+int ss_op_conv_pair(void* stream, const float* dA, int lda, const float* dW1, const float* db1, const float* dW2, const float* db2,
+                    float* dC, int ldc, const float* dR2, int ldr2, float div, float* dC2, int ldc2, float c2_slope, int C, int taps,
+                    int dil, int M, int in_len, float slope, const int32_t* d_segs, int nseg);
+/* The fused ResBlock of the narrow stages (csrc/resblock.hip, launch_resblock_fused with the caller's arguments unchanged):
+ * x = dX; for i in 0..2: x = conv2_i(lrelu(conv1_i,dil[i](lrelu(x)) + B1[i])) + B2[i] + x; dY = [dR2 +] x [/ div].  dW1 / dB1 / dW2 /
+ * dB2: HOST arrays of three device pointers ([C][taps * C] tap-major matrices, [C] biases), dil: HOST array of three dilations.
+ * C = 16 / 32, taps = 3 / 7 / 11, (taps - 1) / 2 * (dil[0] + dil[1] + dil[2] + 3) <= 64, at most 256 segments; SS_ERR_ARG otherwise. */
+int ss_op_resblock_fused(void* stream, const float* dX, int ldx, const float* const* dW1, const float* const* dB1,
+                         const float* const* dW2, const float* const* dB2, const int32_t* dil, float* dY, int ldy, const float* dR2,
+                         int ldr2, float div, int C, int taps, int M, float slope, const int32_t* d_segs, int nseg);
+/* Test hook of the persistent slab kernels (conv_slab / conv_pair / resblock_fused / conv_c16 / c32 / c64 and the Winograd forms):
+ * grid > 0 caps their workgroup count (the 256-channel Winograd form keeps its minimum of 16), 0 lifts the cap; min_rows >= 0
+ * replaces the five row thresholds of the dispatch (conv_c16 / c32 / c64, the 128- and 256-channel Winograd forms), min_rows < 0
+ * restores them.  (0, -1) is the default state; a negative grid is SS_ERR_ARG.  Tests restore it in `finally`. */
+int ss_debug_slab(int grid, long long min_rows);
 /* The FP16 conv of the wide vocoder stages (csrc/conv_f16.hip) on C x C weights dW [C][taps*C] (tap-major; packed to FP16 per
  * call): dC [M][C] = epi(sum act_in(dA) * dW) with "same" padding dil*(taps-1)/2, act_in = in_act (0 / 3 = leaky-ReLU in_slope),
  * epi = + dbias, act (0 / 3 leaky-ReLU 0.1), + dR, + dR2, / div (div > 0), dC2 = leaky_relu(dC, 0.1) when set.  C = 64 / 128 / 256.

@@ -394,7 +394,8 @@ static int launch_cw_t(GemmArgs a, hipStream_t stream) {
   if (rc != SS_OK) return rc;
   int grid = slab_grid(CH >= 128 ? 1 : CH == 64 ? 2 : 3, st->cus, a.M, BME, a.nseg);
   if (CH == 256) {                                 // (block, column half) items: workgroups come in groups of 16 = 8 blocks x 2 halves
-    const long long want = std::min<long long>(st->cus, 2 * ((slab_max_blocks(a.M, BME, a.nseg) + 7) / 8 * 8));
+    long long want = std::min<long long>(st->cus, 2 * ((slab_max_blocks(a.M, BME, a.nseg) + 7) / 8 * 8));
+    if (disp().slab_grid_cap > 0) want = std::min<long long>(want, disp().slab_grid_cap);     // (test hook: down to the one group of 16)
     grid = (int)std::max<long long>(16, want / 16 * 16);
   }
   ProfRec rec{}; bool prof = false;

@@ -4,6 +4,24 @@
 // =================================================================================================
 // op-level entry points
 // =================================================================================================
+// unit-test path of the Winograd form (the model makes the transformed weights once per context): made here per call
+// (one buffer per stream of the calling thread: a re-pack for a launch on stream B must not overwrite the weights a kernel
+//  queued on stream A is still reading -- ADVICE r4)
+static int op_bind_wino(GemmArgs& a, void* stream) {
+  static thread_local std::map<hipStream_t, DevBuf> wino_tmps;
+  DevBuf& wino_tmp = wino_tmps[(hipStream_t)stream];
+  const int N = a.N, Cin = a.Cin, taps = a.taps;
+  if ((conv_c64w_enabled() && N == 64 && Cin == 64 && taps >= 3 && conv_c64_eligible(a)) ||
+      (conv_c128w_enabled() && N == 128 && Cin == 128 && taps >= 3 && a.same_rows && !a.glu) ||
+      (conv_c256w_enabled() && N == 256 && Cin == 256 && taps >= 3 && a.same_rows && !a.glu) ||
+      (conv_c32w_enabled() && N == 32 && Cin == 32 && taps >= 3 && conv_c32_eligible(a))) {
+    RET(wino_tmp.ensure((size_t)N * ((taps + 2) / 3) * 4 * N * sizeof(float)));
+    RET(launch_wino_pack(a.W, wino_tmp.f(), N, taps, (hipStream_t)stream));
+    a.Wwino = wino_tmp.f();
+  }
+  return SS_OK;
+}
+
 extern "C" int ss_op_conv_gemm(void* stream, const float* dA, int lda, const float* dW, const float* dbias,
                                const float* dR, int ldr, const float* dR2, int ldr2, float* dC, int ldc, int M,
                                int N, int Cin, int taps, int dil, int stride, int pad, int in_len, int chunk,
@@ -13,20 +31,49 @@ extern "C" int ss_op_conv_gemm(void* stream, const float* dA, int lda, const flo
   a.M = M; a.N = N; a.Cin = Cin; a.taps = taps; a.dil = dil; a.stride = stride; a.pad = pad; a.in_len = in_len;
   a.chunk = chunk; a.in_act = in_act; a.in_slope = in_slope; a.act = act; a.alpha = alpha; a.div = div; a.glu = glu;
   a.same_rows = (stride == 1 && M == in_len) ? 1 : 0;
-  // unit-test path of the Winograd form (the model makes the transformed weights once per context): made here per call
-  // (one buffer per stream of the calling thread: a re-pack for a launch on stream B must not overwrite the weights a kernel
-  //  queued on stream A is still reading -- ADVICE r4)
-  static thread_local std::map<hipStream_t, DevBuf> wino_tmps;
-  DevBuf& wino_tmp = wino_tmps[(hipStream_t)stream];
-  if ((conv_c64w_enabled() && N == 64 && Cin == 64 && taps >= 3 && conv_c64_eligible(a)) ||
-      (conv_c128w_enabled() && N == 128 && Cin == 128 && taps >= 3 && a.same_rows && !glu) ||
-      (conv_c256w_enabled() && N == 256 && Cin == 256 && taps >= 3 && a.same_rows && !glu) ||
-      (conv_c32w_enabled() && N == 32 && Cin == 32 && taps >= 3 && conv_c32_eligible(a))) {
-    RET(wino_tmp.ensure((size_t)N * ((taps + 2) / 3) * 4 * N * sizeof(float)));
-    RET(launch_wino_pack(dW, wino_tmp.f(), N, taps, (hipStream_t)stream));
-    a.Wwino = wino_tmp.f();
-  }
+  RET(op_bind_wino(a, stream));
   return launch_conv_gemm(a, (hipStream_t)stream);
+}
+
+// every field of GemmArgs a caller of the conv launcher can set, as the caller set it (ragged packs, the pre-activated twin, the
+// epilogue slope, same_rows): what launch_conv_gemm answers is what the caller sees.  The Winograd weight pack is made per call, as above.
+extern "C" int ss_op_conv_gemm_ex(void* stream, const ss_op_conv_args* x) {
+  if (!x) return SS_ERR_ARG;
+  GemmArgs a;
+  a.A = x->A; a.W = x->W; a.bias = x->bias; a.R = x->R; a.R2 = x->R2; a.C = x->C; a.C2 = x->C2;
+  a.lda = x->lda; a.ldc = x->ldc; a.ldr = x->ldr; a.ldr2 = x->ldr2; a.ldc2 = x->ldc2;
+  a.M = x->M; a.N = x->N; a.Cin = x->Cin; a.taps = x->taps; a.dil = x->dil; a.stride = x->stride; a.pad = x->pad;
+  a.in_len = x->in_len; a.chunk = x->chunk;
+  a.in_act = x->in_act; a.in_slope = x->in_slope; a.act = x->act; a.act_slope = x->act_slope; a.alpha = x->alpha; a.div = x->div;
+  a.c2_slope = x->c2_slope; a.glu = x->glu;
+  a.segs = x->segs; a.nseg = x->nseg; a.max_seg_out = x->max_seg_out; a.same_rows = x->same_rows;
+  if (a.W && a.N > 0 && a.taps > 0) RET(op_bind_wino(a, stream));
+  return launch_conv_gemm(a, (hipStream_t)stream);
+}
+// The fused ResBlock half and the fused ResBlock of the narrow vocoder stages (conv_slab.hip, resblock.hip): the launchers with the
+// caller's arguments unchanged.  W1 / B1 / W2 / B2 / dil of the ResBlock: HOST arrays of three (device pointers / dilations).
+extern "C" int ss_op_conv_pair(void* stream, const float* dA, int lda, const float* dW1, const float* db1, const float* dW2,
+                               const float* db2, float* dC, int ldc, const float* dR2, int ldr2, float div, float* dC2, int ldc2,
+                               float c2_slope, int Cch, int taps, int dil, int M, int in_len, float slope, const int32_t* d_segs,
+                               int nseg) {
+  return launch_conv_pair(dA, lda, dW1, db1, dW2, db2, dC, ldc, dR2, ldr2, div, dC2, ldc2, c2_slope, Cch, taps, dil, M, in_len, slope,
+                          d_segs, nseg, (hipStream_t)stream);
+}
+extern "C" int ss_op_resblock_fused(void* stream, const float* dX, int ldx, const float* const* dW1, const float* const* dB1,
+                                    const float* const* dW2, const float* const* dB2, const int32_t* dil, float* dY, int ldy,
+                                    const float* dR2, int ldr2, float div, int Cch, int taps, int M, float slope,
+                                    const int32_t* d_segs, int nseg) {
+  if (!dW1 || !dB1 || !dW2 || !dB2 || !dil) return SS_ERR_ARG;      // (host arrays: the launcher reads them)
+  return launch_resblock_fused(dX, ldx, dW1, dB1, dW2, dB2, dil, dY, ldy, dR2, ldr2, div, Cch, taps, M, slope, d_segs, nseg,
+                               (hipStream_t)stream);
+}
+// Test hook of the slab kernels' shared walk (slab_common.hpp): grid > 0 caps their persistent grids (every workgroup then walks many
+// blocks, across utterance edges, whatever the row count), 0 lifts the cap; min_rows >= 0 replaces the five row thresholds below which
+// conv_c16 / c32 / c64 and the wide Winograd forms refuse a launch, min_rows < 0 puts the defaults back.
+extern "C" int ss_debug_slab(int grid, long long min_rows) {
+  if (grid < 0) return SS_ERR_ARG;
+  slab_debug(grid, min_rows);
+  return SS_OK;
 }
 
 // FP16 form of a wide-stage ResBlock conv (conv_f16.hip; the model packs the weights once per blob, here per call into one buffer per

@@ -925,6 +925,16 @@ void dispatch_edit(const std::function<void(Dispatch&)>& fn) {
   fn(process_settings());
   g_disp_gen.fetch_add(1, std::memory_order_release);
 }
+void slab_debug(int grid, long long min_rows) {
+  const Dispatch dflt = env_defaults();
+  dispatch_edit([=](Dispatch& d) {
+    d.slab_grid_cap = grid > 0 ? grid : 0;
+    const bool set = min_rows >= 0;
+    d.c16_min_rows = set ? min_rows : dflt.c16_min_rows; d.c32_min_rows = set ? min_rows : dflt.c32_min_rows;
+    d.c64_min_rows = set ? min_rows : dflt.c64_min_rows;
+    d.c128w_min_rows = set ? min_rows : dflt.c128w_min_rows; d.c256w_min_rows = set ? min_rows : dflt.c256w_min_rows;
+  });
+}
 const Dispatch* CtxDispatch::refresh() {
   const unsigned now = g_disp_gen.load(std::memory_order_acquire);
   if (gen != now) {

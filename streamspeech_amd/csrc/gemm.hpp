@@ -179,10 +179,16 @@ inline size_t slab_lds_bytes(int slab_rows, int lda, int maxseg) {
 }
 // upper bound of the blocks of bm rows of a launch (per-segment round-up)
 inline long long slab_max_blocks(int M, int bm, int nseg) { return (long long)cdiv(M, bm) + (nseg > 0 ? nseg : 1); }
-// persistent grid: occ resident workgroups on each of `cus` CUs, no more workgroups than blocks
+// persistent grid: occ resident workgroups on each of `cus` CUs, no more workgroups than blocks (and no more than the test hook's
+// cap, ss_debug_slab: a small grid makes every workgroup walk many blocks whatever the row count)
 inline int slab_grid(int occ, int cus, int M, int bm, int nseg) {
-  return (int)std::min<long long>((long long)occ * cus, std::max<long long>(1, slab_max_blocks(M, bm, nseg)));
+  const long long g = std::min<long long>((long long)occ * cus, std::max<long long>(1, slab_max_blocks(M, bm, nseg)));
+  const int cap = disp().slab_grid_cap;
+  return (int)(cap > 0 ? std::min<long long>(g, cap) : g);
 }
+// test hook behind ss_debug_slab: grid > 0 caps slab_grid(), 0 lifts the cap; min_rows >= 0 replaces the five dispatch thresholds
+// (c16 / c32 / c64 / c128w / c256w_min_rows), < 0 puts the process defaults back
+void slab_debug(int grid, long long min_rows);
 // Eligibility prefix of the GemmArgs slab kernels: "same" rows at stride 1 without the chunk / GLU / LayerNorm forms, A rows read
 // densely (lda == Cin), 16-B aligned C / R / R2 / C2 rows.
 bool slab_layout_ok(const GemmArgs& a);

@@ -81,6 +81,20 @@ class SSOpAttnArgs(C.Structure):
         ("use_split", C.c_int32)]
 
 
+class SSOpConvArgs(C.Structure):
+    """ss_op_conv_args: the GemmArgs fields (csrc/gemm.hpp) a caller of the conv launcher can set, pointers as device addresses."""
+    _fields_ = [
+        ("A", _vp), ("W", _vp), ("bias", _vp), ("R", _vp), ("R2", _vp), ("C", _vp), ("C2", _vp),
+        ("lda", C.c_int32), ("ldc", C.c_int32), ("ldr", C.c_int32), ("ldr2", C.c_int32), ("ldc2", C.c_int32),
+        ("M", C.c_int32), ("N", C.c_int32), ("Cin", C.c_int32), ("taps", C.c_int32), ("dil", C.c_int32), ("stride", C.c_int32),
+        ("pad", C.c_int32), ("in_len", C.c_int32), ("chunk", C.c_int32),
+        ("in_act", C.c_int32), ("in_slope", _f),
+        ("act", C.c_int32), ("act_slope", _f), ("alpha", _f), ("div", _f), ("c2_slope", _f),
+        ("glu", C.c_int32),
+        ("segs", _vp), ("nseg", C.c_int32), ("max_seg_out", C.c_int32),
+        ("same_rows", C.c_int32)]
+
+
 class SSOpPoolAttnArgs(C.Structure):
     """ss_op_pool_attn_args: PoolAttnArgs (csrc/attention.hpp) field for field."""
     _fields_ = [
@@ -238,6 +252,10 @@ SIGNATURES = {
     "ss_debug_attention_q16": (_i, [_i]),
     "ss_op_conv_gemm": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
                              _i, _f, _i, _f, _f, _i]),
+    "ss_op_conv_gemm_ex": (_i, [_vp, C.POINTER(SSOpConvArgs)]),
+    "ss_op_conv_pair": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _vp, _i, _f, _i, _i, _i, _i, _i, _f, _vp, _i]),
+    "ss_op_resblock_fused": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _i, _i, _f, _vp, _i]),
+    "ss_debug_slab": (_i, [_i, C.c_longlong]),
     "ss_op_conv_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _f, _vp, _i]),
     "ss_op_layernorm": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _f]),
     "ss_op_attention": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _i, _vp, _vp]),

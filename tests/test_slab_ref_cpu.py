@@ -1,0 +1,161 @@
+"""tests/slab_ref.py against torch.nn.functional.conv1d in float64 -- every utterance cut out of the pack and taken through conv1d on
+its own, the epilogue / pair / ResBlock composed step by step here -- plus the ABI check of the entry points
+tests/test_slab_ops_gpu.py calls (ss_op_conv_gemm_ex, ss_op_conv_pair, ss_op_resblock_fused, ss_debug_slab)."""
+import ctypes as C
+import os
+import re
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import slab_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+NEW = {"ss_op_conv_gemm_ex": 2, "ss_op_conv_pair": 23, "ss_op_resblock_fused": 19, "ss_debug_slab": 2}
+
+
+def test_abi_symbols_header_and_bindings():
+    from streamspeech_amd import lib as L
+    lib = L.load()
+    with open(os.path.join(ROOT, "include", "streamspeech_hip.h"), encoding="utf-8") as f:
+        header = f.read()
+    for name, nargs in NEW.items():
+        assert hasattr(lib, name), f"{name} is not exported"
+        m = re.search(r"\bint\s+%s\s*\(([^;]*?)\)\s*;" % name, header, re.S)
+        assert m, f"{name} has no prototype in the header"
+        assert len(m.group(1).split(",")) == nargs, f"{name}: the header declares another argument count"
+        assert len(L.SIGNATURES[name][1]) == nargs, f"{name}: the binding has another argument count"
+    assert lib.ss_abi_version() == 2 and "#define SS_ABI_VERSION 2" in header
+    # ss_op_conv_args, field for field: the header's struct and the ctypes mirror name the same fields in the same order
+    body = re.search(r"typedef struct ss_op_conv_args \{(.*?)\} ss_op_conv_args;", header, re.S).group(1)
+    names = [n.strip().lstrip("*") for decl in body.split(";") if decl.strip()
+             for n in re.sub(r"^\s*(const\s+)?\w+\s*\*?", "", decl.strip(), count=1).split(",")]
+    assert names == [f[0] for f in L.SSOpConvArgs._fields_]
+    assert C.sizeof(L.SSOpConvArgs) == 7 * 8 + 22 * 4 + 8 + 3 * 4 + 4      # 7 pointers, 22 scalars, segs, 3 ints, tail padding
+
+
+def test_fused_entry_points_refuse_without_touching_the_device():
+    """The eligibility checks of launch_conv_pair / launch_resblock_fused come before any device call: a CPU-only machine sees them."""
+    from streamspeech_amd import lib as L
+    lib = L.load()
+    arr, dil = (C.c_void_p * 3)(0, 0, 0), (C.c_int32 * 3)(1, 3, 5)
+    rb = lambda Cc, k, d=dil, w=arr, nseg=0: lib.ss_op_resblock_fused(None, None, Cc, w, arr, arr, arr, d, None, Cc, None, Cc, 0.0, Cc, k,
+                                                                      4096, 0.1, None, nseg)
+    assert rb(64, 3) == L.SS_ERR_ARG and rb(32, 5) == L.SS_ERR_ARG and rb(32, 3, w=None) == L.SS_ERR_ARG
+    assert rb(32, 11, d=(C.c_int32 * 3)(1, 3, 6)) == L.SS_ERR_ARG and rb(16, 3, nseg=257) == L.SS_ERR_ARG
+    pair = lambda Cc, k, d, M=4096, nseg=0: lib.ss_op_conv_pair(None, None, Cc, None, None, None, None, None, Cc, None, Cc, 0.0, None, Cc,
+                                                               0.1, Cc, k, d, M, M, 0.1, None, nseg)
+    assert pair(16, 4, 1) == L.SS_ERR_ARG and pair(16, 11, 6) == L.SS_ERR_ARG and pair(16, 3, 1, M=2047) == L.SS_ERR_ARG
+    assert pair(32, 7, 1) == L.SS_ERR_ARG and pair(16, 3, 1, nseg=257) == L.SS_ERR_ARG
+    assert lib.ss_op_conv_gemm_ex(None, None) == L.SS_ERR_ARG
+
+
+def test_debug_slab_refuses_a_negative_grid():
+    from streamspeech_amd import lib as L
+    lib = L.load()
+    try:
+        assert lib.ss_debug_slab(-1, 0) == L.SS_ERR_ARG
+        assert lib.ss_debug_slab(-7, -1) == L.SS_ERR_ARG
+        assert lib.ss_debug_slab(3, 0) == 0
+        assert lib.ss_debug_slab(0, 1 << 40) == 0
+    finally:
+        assert lib.ss_debug_slab(0, -1) == 0
+
+
+def rnd(*shape, seed=0, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(*shape, generator=g) * scale).double()
+
+
+def _conv1d_utt(x, w, b, dil, left, right):
+    """One utterance [L, Cin] through F.conv1d with explicit zero padding."""
+    return F.conv1d(F.pad(x.t()[None], (left, right)), w, b, dilation=dil)[0].t()
+
+
+LENS = [1, 2, 4, 5, 6, 37, 1, 130, 3]
+
+
+@pytest.mark.parametrize("taps,dil", [(1, 1), (2, 1), (3, 1), (3, 5), (4, 3), (7, 3), (11, 1), (11, 5)])
+@pytest.mark.parametrize("cin,n", [(16, 16), (8, 24)])
+def test_segmented_conv_is_conv1d_per_utterance(taps, dil, cin, n):
+    segs = R.seg_table(LENS, start=3)                       # rows 0..2 and the tail belong to no utterance
+    M = segs[-1][0] + segs[-1][1] + 2
+    x, w, b = rnd(M, cin, seed=1), rnd(n, cin, taps, seed=2, scale=(cin * taps) ** -0.5), rnd(n, seed=3, scale=0.1)
+    Rr, R2 = rnd(M, n, seed=4), rnd(M, n, seed=5)
+    got, got2 = R.conv(x, w, segs, dil, in_slope=0.1, bias=b, act_slope=0.2, alpha=0.5, R=Rr, R2=R2, div=3.0, c2_slope=0.3)
+    plain = R.conv(x, w, segs, dil)
+    covered = torch.zeros(M, dtype=torch.bool)
+    span = dil * (taps - 1)
+    for s, L in segs:
+        covered[s:s + L] = True
+        xs = x[s:s + L]
+        y = _conv1d_utt(F.leaky_relu(xs, 0.1), w, b, dil, span // 2, span - span // 2)     # even taps: the extra row on the right
+        y = F.leaky_relu(y, 0.2) * 0.5
+        y = (R2[s:s + L] + (y + Rr[s:s + L])) / 3.0
+        assert (got[s:s + L] - y).abs().max() < 1e-12
+        assert torch.equal(got2[s:s + L], torch.where(got[s:s + L] > 0, got[s:s + L], got[s:s + L] * 0.3))
+        assert (plain[s:s + L] - _conv1d_utt(xs, w, None, dil, span // 2, span - span // 2)).abs().max() < 1e-12
+    assert torch.isnan(got[~covered]).all() and torch.isnan(plain[~covered]).all() and torch.isfinite(got[covered]).all()
+
+
+def test_segmented_conv_reads_nothing_of_the_neighbours():
+    """Changing one utterance changes its own rows only."""
+    segs = R.seg_table([5, 1, 40, 2])
+    x, w = rnd(48, 16, seed=6), rnd(16, 16, 11, seed=7, scale=0.1)
+    a = R.seg_conv(x, w, segs, 5)
+    x2 = x.clone()
+    x2[5] += 100.0                                          # the 1-row utterance
+    b = R.seg_conv(x2, w, segs, 5)
+    assert torch.equal(a[:5], b[:5]) and torch.equal(a[6:], b[6:]) and not torch.equal(a[5], b[5])
+
+
+@pytest.mark.parametrize("taps,dil", [(3, 1), (3, 5), (7, 3), (11, 5)])
+@pytest.mark.parametrize("extras", [False, True])
+def test_pair_is_two_conv1d_and_a_residual(taps, dil, extras):
+    Cc = 16
+    segs = R.seg_table(LENS)
+    M = sum(LENS)
+    x = rnd(M, Cc, seed=11)
+    w1, w2 = (rnd(Cc, Cc, taps, seed=12 + i, scale=(Cc * taps) ** -0.5) for i in range(2))
+    b1, b2 = rnd(Cc, seed=14, scale=0.1), rnd(Cc, seed=15, scale=0.1)
+    R2 = rnd(M, Cc, seed=16) if extras else None
+    got = R.pair(x, segs, w1, b1, w2, b2, dil, 0.1, R2, 3.0 if extras else 0.0)
+    for s, L in segs:
+        xs = x[s:s + L]
+        h1, h2 = dil * (taps - 1) // 2, (taps - 1) // 2
+        t = _conv1d_utt(F.leaky_relu(xs, 0.1), w1, b1, dil, h1, h1)
+        y = _conv1d_utt(F.leaky_relu(t, 0.1), w2, b2, 1, h2, h2) + xs
+        if extras:
+            y = (R2[s:s + L] + y) / 3.0
+        assert (got[s:s + L] - y).abs().max() < 1e-12
+
+
+@pytest.mark.parametrize("taps,dils", [(3, (1, 3, 5)), (7, (5, 3, 1)), (11, (1, 1, 1)), (11, (1, 3, 5))])
+@pytest.mark.parametrize("extras", [False, True])
+def test_resblock_is_the_hifigan_recurrence(taps, dils, extras):
+    """hifigan.py ResBlock.forward, utterance by utterance: for (c1, c2): xt = c2(lrelu(c1(lrelu(x)))); x = xt + x."""
+    Cc = 16
+    segs = R.seg_table(LENS)
+    M = sum(LENS)
+    x = rnd(M, Cc, seed=21)
+    W1 = [rnd(Cc, Cc, taps, seed=22 + i, scale=(Cc * taps) ** -0.5) for i in range(3)]
+    W2 = [rnd(Cc, Cc, taps, seed=25 + i, scale=(Cc * taps) ** -0.5) for i in range(3)]
+    B1 = [rnd(Cc, seed=28 + i, scale=0.1) for i in range(3)]
+    B2 = [rnd(Cc, seed=31 + i, scale=0.1) for i in range(3)]
+    R2 = rnd(M, Cc, seed=34) if extras else None
+    got = R.resblock(x, segs, W1, B1, W2, B2, dils, 0.1, R2, 3.0 if extras else 0.0)
+    for s, L in segs:
+        u = x[s:s + L].t()[None]                            # [1, C, L] as the module sees it
+        for i in range(3):
+            xt = F.conv1d(F.leaky_relu(u, 0.1), W1[i], B1[i], dilation=dils[i], padding=dils[i] * (taps - 1) // 2)
+            xt = F.conv1d(F.leaky_relu(xt, 0.1), W2[i], B2[i], padding=(taps - 1) // 2)
+            u = xt + u
+        y = u[0].t()
+        if extras:
+            y = (R2[s:s + L] + y) / 3.0
+        assert (got[s:s + L] - y).abs().max() < 1e-11
+    f32 = R.resblock(x.float(), segs, [w.float() for w in W1], [b.float() for b in B1], [w.float() for w in W2],
+                     [b.float() for b in B2], dils, 0.1, None if R2 is None else R2.float(), 3.0 if extras else 0.0)
+    assert f32.dtype == torch.float32 and (f32.double() - got).abs().max() < 1e-4      # the float32 chain is the same function
