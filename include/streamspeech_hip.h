@@ -602,6 +602,26 @@ int ss_vocoder_set_f16(ss_vocoder* v, int on);
 int ss_vocoder_forward(ss_vocoder* v, void* stream, const int32_t* d_codes, int K, int dur_prediction,
                        const int32_t* d_forced_dur, float* d_wav, int64_t wav_capacity,
                        int32_t* d_dur, int64_t* h_n_samples);
+/* ---- multi-speaker vocoders ("multispkr": true, agent/tts/codehifigan.py:13-19, 80-86) ---------------------------------------
+ * The reference concatenates the chosen speaker's embedding, repeated over all frames, to the code embeddings in front of conv_pre
+ * (2 x embedding_dim input channels).  The speaker vector is constant over time, so here conv_pre contracts the code half only
+ * ("voc.pre.w", Cin = embedding_dim -- ss_vocoder_config.model_in_dim stays that width) and one more launch adds the speaker term
+ * before the activation: slot "voc.spkr.table", [num_speakers][16][upsample_initial_channel] floats.  With W the weight-norm-folded
+ * conv_pre weight [C0][2E][7], s the speaker's embedding and G[k][co] = sum_c W[co][E + c][k] * s[c], entry (lo, hi) of a speaker
+ * holds G[lo] + G[lo + 1] + ... + G[hi] (ascending tap order, summed in float64 at packing time and rounded to float32 once) at
+ * index 4 * lo + (hi - 3), lo in 0..3, hi in 3..6.  Row t of a segment of L frames takes lo = max(0, 3 - t), hi = min(6, L + 2 - t):
+ * the taps of the 7-tap "same" conv that fall inside the segment.  Per row the device work is ONE float32 add of a table entry to
+ * conv_pre's output (then the leaky-ReLU the first up-conv reads), so the path is as pack-invariant as the single-speaker one.
+ * A handle is multi-speaker when its blob carries that slot; num_speakers = the slot's size / (16 x upsample_initial_channel).
+ * The duration predictor does not see the speaker.
+ * Refusals, all SS_ERR_ARG before any HIP call: a _spkr call with an id outside [0, num_speakers); a _spkr call on a single-speaker
+ * handle; a no-speaker call (ss_vocoder_forward, ss_batch_vocoder_forward, ss_batch_vocoder_tail) on a multi-speaker handle (the
+ * reference asserts 'require "spkr" input'). */
+int ss_vocoder_num_speakers(const ss_vocoder* v);   /* 0: a single-speaker handle */
+/* ss_vocoder_forward in the voice of speaker `spkr`. */
+int ss_vocoder_forward_spkr(ss_vocoder* v, void* stream, const int32_t* d_codes, int K, int dur_prediction,
+                            const int32_t* d_forced_dur, float* d_wav, int64_t wav_capacity,
+                            int32_t* d_dur, int64_t* h_n_samples, int32_t spkr);
 
 /* ---- ragged-batch twins (BASELINE.json configs[3]/[4]: many utterances per GPU) --------------
  * B independent utterances packed along the row axis (no padding; each keeps the B = 1 arithmetic
@@ -719,6 +739,11 @@ int ss_batch_vocoder_forward(ss_vocoder* v, void* stream, int B, const int32_t* 
                              int dur_prediction, const int32_t* d_forced_dur, float* d_wav,
                              int64_t wav_capacity, int32_t* d_dur, int64_t* h_wav_start,
                              int64_t* h_n_samples);
+/* The same with a voice per utterance: h_spkr [B] (host) -- one pack, any mix of speakers (see ss_vocoder_forward_spkr). */
+int ss_batch_vocoder_forward_spkr(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K,
+                                  int dur_prediction, const int32_t* d_forced_dur, float* d_wav,
+                                  int64_t wav_capacity, int32_t* d_dur, int64_t* h_wav_start,
+                                  int64_t* h_n_samples, const int32_t* h_spkr /* [B] */);
 /* ss_batch_t2u_units with trailing <pad> states: row b's last h_n_tail_pad[b] (0 <= . < h_n[b]) states are masked as keys as
  * ss_t2u_units(..., n_tail_pad) masks them -- T2U encoder self-attention, unit decoder self-attention (ctc_upsample x pad rows) and
  * cross-attention -- and still decoded.  Rows with 0 are bit-identical to ss_batch_t2u_units; pack-invariant like it. */
@@ -738,6 +763,12 @@ int ss_batch_mt_features(ss_model* m, void* stream, int B, const float* d_enc_ou
 int ss_batch_vocoder_tail(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K, const int32_t* h_n_new,
                           const int32_t* h_ctx, const int32_t* h_rf, int dur_prediction, float* d_out, int64_t out_capacity,
                           int32_t* h_win_first, int32_t* h_dur, int64_t* h_out_start, int64_t* h_n_out);
+/* The same with a voice per row: h_spkr [B] (host).  A row's window and its all-units fallback are synthesised in the row's voice;
+ * rows of different voices share the one predictor pass and the one generator pack. */
+int ss_batch_vocoder_tail_spkr(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K, const int32_t* h_n_new,
+                               const int32_t* h_ctx, const int32_t* h_rf, int dur_prediction, float* d_out, int64_t out_capacity,
+                               int32_t* h_win_first, int32_t* h_dur, int64_t* h_out_start, int64_t* h_n_out,
+                               const int32_t* h_spkr /* [B] */);
 
 /* ---- profiling hooks for bench.py's roofline leg: bracket every conv-GEMM launch whose tile
  * configuration is in cls_mask with HIP events recorded on the launch stream.  ss_prof_read
@@ -960,6 +991,11 @@ int ss_op_conv_post_tanh(void* stream, const float* x, int T, int C, const float
                          const int32_t* segs, int nseg);              /* segs {sample_start, n_samples}; T = max */
 int ss_op_conv_post_tanh_crop(void* stream, const float* x, int C, const float* w, const float* bias, float slope, float* wav,
                               const int32_t* segs, int nseg, int max_keep);   /* segs {sample_start, n_samples, first, out_start} */
+/* The speaker add of a multi-speaker conv_pre (see ss_vocoder_forward_spkr): y[row] = act(x[row] + table[speaker][4 lo + hi - 3]) for
+ * every row of every segment, segs {start, len, ., .} [nseg] with speakers spkr [nseg] (device) and max_seg_out the longest segment;
+ * nseg = 0: one segment of M rows, speaker spkr0.  act != 0: leaky-ReLU(slope).  y may be x; rows outside the segments stay. */
+int ss_op_spkr_pre_add(void* stream, const float* x, float* y, int ld, int C0, const float* table, const int32_t* spkr, int spkr0,
+                       const int32_t* segs, int nseg, int max_seg_out, int M, int act, float slope);
 
 /* ---- the kernels of the beam search (csrc/beam.hip), one launch each.  R = B * k hypothesis rows; the candidate lists have a row
  * stride of SS_OP_BEAM_CAND entries whatever k is. ---- */

@@ -32,21 +32,37 @@ def _detok(symbols):
     return text[1:] if len(text) > 0 and text[0] == " " else text
 
 
-def synthesize_tail(vocoder, unit, n_new, dur_prediction, ctx=0, rf=None):
+def speaker_id_arg(args, vocoder, flag="--speaker-id"):
+    """The voice of an agent or session: args.speaker_id on a multi-speaker vocoder (required there, inside its speakers), None on
+    a single-speaker one, which ignores the flag."""
+    n = int(getattr(getattr(vocoder, "hip", vocoder), "num_speakers", 0) or 0)
+    if not n:
+        return None
+    spk = getattr(args, "speaker_id", None)
+    if spk is None:
+        raise ValueError(f"the vocoder is multi-speaker ({n} speakers): {flag} is required")
+    if not 0 <= int(spk) < n:
+        raise ValueError(f"{flag} {spk} is outside the vocoder's {n} speakers")
+    return int(spk)
+
+
+def synthesize_tail(vocoder, unit, n_new, dur_prediction, ctx=0, rf=None, spkr=None):
     """Speech of the last ``n_new`` units of ``unit`` (agent :743-753: vocoder over all units, keep
     ``wav[-dur[-n_new:].sum()*320:]``).  With ``ctx`` > 0 only the last ``n_new + ctx`` units are
     synthesised: identical tail, because the frames further left than the
-    generator's receptive field ``rf`` cannot reach it.  Returns (tail, wav of what was synthesised)."""
+    generator's receptive field ``rf`` cannot reach it.  ``spkr``: the speaker id a multi-speaker vocoder synthesises with, passed
+    as ``x["spkr"]`` on both calls.  Returns (tail, wav of what was synthesised)."""
     wav = dur = None
+    extra = {} if spkr is None else {"spkr": torch.tensor([[int(spkr)]], dtype=torch.long)}
     if ctx > 0 and len(unit) > n_new + ctx:
-        x = {"code": torch.tensor(unit[-(n_new + ctx):], dtype=torch.long).view(1, -1)}
+        x = {"code": torch.tensor(unit[-(n_new + ctx):], dtype=torch.long).view(1, -1), **extra}
         wav, dur = vocoder(x, dur_prediction)
         # frames left of the new units whose durations are exact (the 2 left-most context units see a
         # truncated duration-predictor window) must cover the generator's receptive field
         if int(dur[:, 2:ctx].sum()) < rf + 2:
             wav = None
     if wav is None:
-        x = {"code": torch.tensor(unit, dtype=torch.long).view(1, -1)}
+        x = {"code": torch.tensor(unit, dtype=torch.long).view(1, -1), **extra}
         wav, dur = vocoder(x, dur_prediction)
     return wav[-int(dur[:, -n_new:].sum()) * 320:], wav
 
@@ -127,6 +143,7 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
             self.vocoder = CodeHiFiGANVocoderWithDur(args.vocoder, vcfg, device=self.device)
             if getattr(args, "vocoder_fp16", False):
                 self.vocoder.hip.set_fp16(True)
+        self.speaker_id = speaker_id_arg(args, self.vocoder)     # None: a single-speaker vocoder
         self.dur_prediction = args.dur_prediction
         # Incremental synthesis: the reference re-synthesises ALL units at every write
         # and keeps the tail (agent :743-753).  The generator has a finite receptive field, so the same
@@ -176,6 +193,8 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
         a("--vocoder-fp16", action="store_true", default=False,
           help="run the vocoder's 64- to 256-channel ResBlock convs on FP16 matrix cores (f32 accumulation; waveform within 1e-3 RMS, "
                "unit ids and durations unchanged); default: exact f32")
+        a("--speaker-id", type=int, default=None,
+          help="the voice of a multi-speaker vocoder (\"multispkr\": true in --vocoder-cfg): required there, ignored otherwise")
         a("--lagging-k1", type=int, default=0, help="lagging number")
         a("--lagging-k2", type=int, default=0, help="lagging number")
         a("--segment-size", type=int, default=320, help="segment-size")
@@ -415,7 +434,7 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
 
         # 4. vocoder over ALL units so far; emit the tail that belongs to the new units (agent :743-753)
         new_wav, wav = synthesize_tail(self.vocoder, unit, len(cur_unit), self.dur_prediction, self.vocoder_ctx,
-                                       self.vocoder_rf)
+                                       self.vocoder_rf, **({} if self.speaker_id is None else {"spkr": self.speaker_id}))
         if self.unfinished_wav is not None and len(self.unfinished_wav) > 0:
             new_wav = torch.cat((self.unfinished_wav, new_wav), dim=0)
         self.wav = wav

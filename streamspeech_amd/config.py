@@ -65,6 +65,24 @@ class VocoderConfig:
     dur_hidden: int = 128
     dur_kernel: int = 3
     code_hop_size: int = 320
+    # multi-speaker checkpoints ("multispkr": true, codehifigan.py:13-19): an nn.Embedding(num_speakers, embedding_dim) whose row is
+    # repeated over all frames and concatenated to the code embeddings in front of conv_pre (model_in_dim = 2 * embedding_dim)
+    multispkr: bool = False
+    num_speakers: int = 200
+
+    def __post_init__(self):
+        self.validate()
+
+    def validate(self):
+        """A multi-speaker config feeds conv_pre [code embedding ; speaker embedding], a single-speaker one the code embedding alone."""
+        want = 2 * self.embedding_dim if self.multispkr else self.embedding_dim
+        if self.model_in_dim != want:
+            raise ValueError(
+                f"model_in_dim = {self.model_in_dim} does not fit embedding_dim = {self.embedding_dim} with multispkr = "
+                f"{bool(self.multispkr)}: a {'multi' if self.multispkr else 'single'}-speaker vocoder needs model_in_dim == "
+                f"{'2 * ' if self.multispkr else ''}embedding_dim (f0 and embedder_params inputs are not supported)")
+        if self.multispkr and self.num_speakers < 1:
+            raise ValueError(f"num_speakers = {self.num_speakers}: a multispkr vocoder needs at least one speaker")
 
     def channels(self, stage: int) -> int:
         return self.upsample_initial_channel // (2 ** (stage + 1))
@@ -83,7 +101,7 @@ class VocoderConfig:
 
     def as_dict(self):
         """The JSON the reference ``CodeHiFiGANVocoderWithDur`` is constructed from."""
-        return {
+        d = {
             "num_embeddings": self.num_embeddings,
             "embedding_dim": self.embedding_dim,
             "model_in_dim": self.model_in_dim,
@@ -100,3 +118,7 @@ class VocoderConfig:
             },
             "code_hop_size": self.code_hop_size,
         }
+        if self.multispkr:
+            d["multispkr"] = True
+            d["num_speakers"] = self.num_speakers
+        return d

@@ -222,6 +222,10 @@ extern "C" int ss_op_conv_post_tanh_crop(void* stream, const float* x, int C, co
                                          const int32_t* segs, int nseg, int max_keep) {
   return launch_conv_post_tanh_crop(x, C, w, bias, slope, wav, segs, nseg, max_keep, (hipStream_t)stream);
 }
+extern "C" int ss_op_spkr_pre_add(void* stream, const float* x, float* y, int ld, int C0, const float* table, const int32_t* spkr,
+                                   int spkr0, const int32_t* segs, int nseg, int max_seg_out, int M, int act, float slope) {
+  return launch_spkr_pre_add(x, y, ld, C0, table, spkr, spkr0, segs, nseg, max_seg_out, M, act, slope, (hipStream_t)stream);
+}
 
 // test ops: one process-wide key-split scratch (callers are serial), counters zero before the first launch
 static int op_attn_bind_split(AttnArgs& a) {

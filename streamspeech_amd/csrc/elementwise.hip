@@ -563,4 +563,50 @@ int launch_conv_post_tanh_crop(const float* x, int C, const float* w, const floa
   return SS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Multi-speaker conv_pre: the speaker half of the concatenated input is constant over a segment's frames, so its part of conv_pre is
+// one of 16 per-speaker vectors, chosen by which of the 7 taps fall inside the segment at row t (weights.py speaker_table):
+// lo = max(0, 3 - t), hi = min(6, L + 2 - t), entry 4 * lo + (hi - 3).  y[row] = act(x[row] + table[speaker][entry]); ONE f32 add per
+// element, independent of the pack.  A workgroup covers SPK_ROWS rows of one segment, float4 along the channels.
+// ---------------------------------------------------------------------------------------------
+constexpr int SPK_ROWS = 8;
+__global__ __launch_bounds__(256) void spkr_pre_add_kernel(const float* x, float* y, int ld, int C0, const float* __restrict__ table,
+                                                           const int* __restrict__ spkr, int spkr0, const int* __restrict__ segs,
+                                                           int M, int act, float slope) {
+  int start = 0, L = M, sp = spkr0;
+  if (segs) {   // conv segs {out_start, out_len, in_start, in_len}
+    start = segs[4 * blockIdx.y]; L = segs[4 * blockIdx.y + 1]; sp = spkr[blockIdx.y];
+  }
+  const int t0 = blockIdx.x * SPK_ROWS;
+  if (t0 >= L) return;
+  const int c4n = C0 >> 2;
+  const float* tab = table + (size_t)sp * 16 * C0;
+  for (int i = threadIdx.x; i < SPK_ROWS * c4n; i += 256) {
+    const int t = t0 + i / c4n, c = (i % c4n) << 2;
+    if (t >= L || start + t >= M) continue;
+    const int lo = t < 3 ? 3 - t : 0, hi = L + 2 - t < 6 ? L + 2 - t : 6;
+    const float4 g = *reinterpret_cast<const float4*>(tab + (size_t)(4 * lo + hi - 3) * C0 + c);
+    const size_t o = (size_t)(start + t) * ld + c;
+    float4 v = *reinterpret_cast<const float4*>(x + o);
+    v.x += g.x; v.y += g.y; v.z += g.z; v.w += g.w;
+    if (act) {
+      v.x = v.x > 0.f ? v.x : v.x * slope; v.y = v.y > 0.f ? v.y : v.y * slope;
+      v.z = v.z > 0.f ? v.z : v.z * slope; v.w = v.w > 0.f ? v.w : v.w * slope;
+    }
+    *reinterpret_cast<float4*>(y + o) = v;
+  }
+}
+
+int launch_spkr_pre_add(const float* x, float* y, int ld, int C0, const float* table, const int* spkr, int spkr0, const int* segs,
+                        int nseg, int max_seg_out, int M, int act, float slope, hipStream_t stream) {
+  if (M <= 0) return SS_OK;
+  if (!x || !y || !table || C0 <= 0 || (C0 & 3) || (ld & 3) || ld < C0 || spkr0 < 0) return SS_ERR_ARG;
+  if (nseg > 0 && (!segs || !spkr || nseg > 65535 || max_seg_out <= 0)) return SS_ERR_ARG;
+  const int rows = nseg > 0 ? max_seg_out : M;
+  hipLaunchKernelGGL(spkr_pre_add_kernel, dim3(cdiv(rows, SPK_ROWS), nseg > 0 ? nseg : 1), dim3(256), 0, stream, x, y, ld, C0, table,
+                     spkr, spkr0, nseg > 0 ? segs : nullptr, M, act, slope);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
 }  // namespace ss

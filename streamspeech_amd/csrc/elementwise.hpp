@@ -79,4 +79,12 @@ int launch_conv_post_tanh(const float* x, int T, int C, const float* w, const fl
 int launch_conv_post_tanh_crop(const float* x, int C, const float* w, const float* bias, float slope, float* wav, const int* segs,
                                int nseg, int max_keep, hipStream_t stream);
 
+// Speaker term of a multi-speaker conv_pre, added to its code-half output: for row t of a segment of L rows
+// y[row, c] = act(x[row, c] + table[speaker][4 * lo + (hi - 3)][c]), lo = max(0, 3 - t), hi = min(6, L + 2 - t) (the taps of the 7-tap
+// "same" conv that fall inside the segment); table [num_speakers][16][C0] (weights.py speaker_table).  act != 0: leaky-ReLU(slope).
+// y may be x.  segs: conv segs {out_start, out_len, ., .} [nseg], spkr [nseg] the segments' speakers (device), max_seg_out the longest
+// segment; nseg = 0: one segment of M rows with speaker spkr0.  Rows outside every segment are not touched.  C0 and ld multiples of 4.
+int launch_spkr_pre_add(const float* x, float* y, int ld, int C0, const float* table, const int* spkr, int spkr0, const int* segs,
+                        int nseg, int max_seg_out, int M, int act, float slope, hipStream_t stream);
+
 }  // namespace ss

@@ -465,6 +465,8 @@ struct ss_vocoder {
   int f16 = 0;         // FP16-operand ResBlock convs of the 64- / 128- / 256-channel stages (ss_vocoder_set_f16); wins over x3; default off
   const float* blob = nullptr;       // the weight blob this handle was made over
   void* f16w = nullptr;              // their FP16 weight fragments: ONE buffer per weight blob, shared like `wino` (made on the first switch-on)
+  const float* spk_table = nullptr;  // multi-speaker blob ("voc.spkr.table"): the speaker term of conv_pre [n_spk][16][C0] (weights.py speaker_table)
+  int n_spk = 0;                     // 0: single-speaker handle
 };
 
 namespace {

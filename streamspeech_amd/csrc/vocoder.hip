@@ -74,6 +74,16 @@ extern "C" int ss_vocoder_create(const ss_vocoder_config* cfg, const float* d_bl
     C = Co;
   }
   v->post = {w.get("voc.post.w", (int64_t)7 * C), w.get("voc.post.b", 1)};
+  {
+    // a multi-speaker blob carries the speaker term of conv_pre: [num_speakers][16][C0]; cfg->model_in_dim stays the code half's width
+    auto it = w.map.find("voc.spkr.table");
+    if (it != w.map.end()) {
+      const int64_t per = (int64_t)16 * C0;
+      if (it->second.n <= 0 || it->second.n % per || it->second.n / per > INT32_MAX || (C0 & 3)) { scratch_unref(v->sc); delete v; return SS_ERR_ARG; }
+      v->spk_table = it->second.p;
+      v->n_spk = (int)(it->second.n / per);
+    }
+  }
   if (!w.missing.empty()) { scratch_unref(v->sc); delete v; return SS_ERR_MISSING_WEIGHT; }
   {
     // Winograd forms of the 32-, 64- and 128-channel stages' ResBlock convs (conv_c64w.hip), made once per context from the packed weights
@@ -128,6 +138,8 @@ extern "C" int ss_vocoder_create(const ss_vocoder_config* cfg, const float* d_bl
   *out = v;
   return SS_OK;
 }
+
+extern "C" int ss_vocoder_num_speakers(const ss_vocoder* v) { return v ? v->n_spk : 0; }
 
 extern "C" int ss_vocoder_set_bf16x3(ss_vocoder* v, int on) {
   if (!v) return SS_ERR_ARG;
@@ -248,10 +260,12 @@ extern "C" int ss_vocoder_bind_scratch(ss_vocoder* v, ss_scratch* sc) {
 // stays on the consumer's A-fragment path there.
 // -------------------------------------------------------------------------------------------------
 struct GenBufs { float *bx, *bt, *br, *bs, *bxa, *bra, *bsa, *br2; };
+// The speakers of a multi-speaker call: `seg` (device) the speaker of every segment of the pack, or `one` for the single utterance
+struct SpkSel { const int* seg = nullptr; int one = 0; int max_frames = 0; };   // max_frames: the longest segment, in frames
 
 template <class ConvFn, class StageFn, class GeomFn>
 static int hifigan_stack(const ss_vocoder* v, hipStream_t s, ConvFn&& conv, StageFn&& on_stage, GeomFn&& geom,
-                         const float* frames, int Ft, const GenBufs& b, int* out_scale, int* out_C) {
+                         const float* frames, int Ft, const GenBufs& b, int* out_scale, int* out_C, const SpkSel* spk = nullptr) {
   const ss_vocoder_config& c = v->cfg;
   // Opt-in FP16 (ss_vocoder_set_f16): every ResBlock conv of the 64-, 128- and 256-channel stages runs on conv_f16.hip at any row count;
   // like the Winograd slab stages it activates while staging, so those convs neither read nor write twins -- only the stage's last conv
@@ -320,9 +334,19 @@ static int hifigan_stack(const ss_vocoder* v, hipStream_t s, ConvFn&& conv, Stag
   RET(on_stage(scale));
   {
     GemmArgs a = mk(frames, c.model_in_dim, v->pre, C, 7, 1, b.bx, C);
-    if (up_preact(C)) a.C2 = b.bxa;
+    if (up_preact(C) && !spk) a.C2 = b.bxa;
     if (f16) a.canon = CANON_SEQ;
     RET(conv(a, scale));
+    if (spk) {
+      // multi-speaker: conv_pre above contracted the code half only; the speaker term joins BEFORE the activation, so the twin is not
+      // conv_pre's to write.  Only the first up-conv reads this tensor -- bxa when it takes a pre-activated input, else bx (it
+      // activates while loading) -- so exactly that one is written.
+      int gM = 0, gnseg = 0; const int* gsegs = nullptr;
+      geom(scale, gM, gsegs, gnseg);
+      const bool pa0 = up_preact(C);
+      RET(launch_spkr_pre_add(b.bx, pa0 ? b.bxa : b.bx, C, C, v->spk_table, spk->seg, spk->one, gsegs, gnseg, spk->max_frames, gM, pa0 ? 1 : 0,
+                              0.1f, s));
+    }
   }
   for (int i = 0; i < c.n_up; ++i) {
     const int st = c.upsample_rates[i], Co = C / 2;
@@ -416,10 +440,21 @@ static int conv1d(hipStream_t s, const float* A, int T, int Cin, const ConvW& cw
   return launch_conv_gemm(a, s);
 }
 
-extern "C" int ss_vocoder_forward(ss_vocoder* v, void* stream, const int32_t* d_codes, int K, int dur_prediction,
-                                  const int32_t* d_forced_dur, float* d_wav, int64_t wav_capacity,
-                                  int32_t* d_dur, int64_t* h_n_samples) {
+// speaker arguments of an entry point (`have`: a _spkr form was called).  A multi-speaker handle needs speakers inside [0, n_spk), a
+// single-speaker handle takes none (header).  Checked before any HIP call.
+static bool spkr_args_ok(const ss_vocoder* v, bool have, const int32_t* h_spkr, int B) {
+  if (!have) return v->n_spk == 0;
+  if (v->n_spk == 0 || !h_spkr) return false;
+  for (int b = 0; b < B; ++b)
+    if (h_spkr[b] < 0 || h_spkr[b] >= v->n_spk) return false;
+  return true;
+}
+
+static int vocoder_forward(ss_vocoder* v, void* stream, const int32_t* d_codes, int K, int dur_prediction,
+                           const int32_t* d_forced_dur, float* d_wav, int64_t wav_capacity,
+                           int32_t* d_dur, int64_t* h_n_samples, const int32_t* h_spkr) {
   if (!v || K <= 0 || !d_codes || !d_wav || !d_dur) return SS_ERR_ARG;
+  if (!spkr_args_ok(v, h_spkr != nullptr, h_spkr, 1)) return SS_ERR_ARG;
   SkScope sk_scope(v->sc->skws);
   hipStream_t s = (hipStream_t)stream;
   const ss_vocoder_config& c = v->cfg;
@@ -475,22 +510,37 @@ extern "C" int ss_vocoder_forward(ss_vocoder* v, void* stream, const int32_t* d_
   gb.br2 = gb.bsa + stage_max;           // second resblock state (fused pairs ping-pong br / br2)
   RET(launch_repeat_rows(emb, cum, K, E, frames, Fr, s));
   int T = 1, C = 0;
+  SpkSel sel;
+  if (h_spkr) { sel.one = h_spkr[0]; sel.max_frames = Fr; }
   RET(hifigan_stack(v, s, [&](GemmArgs& a, int scale) { a.M = Fr * scale; a.in_len = Fr * scale; return launch_conv_gemm(a, s); },
                     [](int) { return SS_OK; },
                     [&](int scale, int& M, const int*& segs, int& nseg) { M = Fr * scale; segs = nullptr; nseg = 0; },
-                    frames, Fr, gb, &T, &C));
+                    frames, Fr, gb, &T, &C, h_spkr ? &sel : nullptr));
   T *= Fr;
   float* bx = gb.bx;
   // leaky_relu (default slope 0.01, hifigan.py:166) -> conv_post -> tanh
   return launch_conv_post_tanh(bx, T, C, v->post.w, v->post.b, 0.01f, d_wav, s);
 }
 
+extern "C" int ss_vocoder_forward(ss_vocoder* v, void* stream, const int32_t* d_codes, int K, int dur_prediction,
+                                  const int32_t* d_forced_dur, float* d_wav, int64_t wav_capacity,
+                                  int32_t* d_dur, int64_t* h_n_samples) {
+  return vocoder_forward(v, stream, d_codes, K, dur_prediction, d_forced_dur, d_wav, wav_capacity, d_dur, h_n_samples, nullptr);
+}
 
-extern "C" int ss_batch_vocoder_forward(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K,
-                                        int dur_prediction, const int32_t* d_forced_dur, float* d_wav,
-                                        int64_t wav_capacity, int32_t* d_dur, int64_t* h_wav_start,
-                                        int64_t* h_n_samples) {
+extern "C" int ss_vocoder_forward_spkr(ss_vocoder* v, void* stream, const int32_t* d_codes, int K, int dur_prediction,
+                                       const int32_t* d_forced_dur, float* d_wav, int64_t wav_capacity,
+                                       int32_t* d_dur, int64_t* h_n_samples, int32_t spkr) {
+  return vocoder_forward(v, stream, d_codes, K, dur_prediction, d_forced_dur, d_wav, wav_capacity, d_dur, h_n_samples, &spkr);
+}
+
+
+static int batch_vocoder_forward(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K,
+                                 int dur_prediction, const int32_t* d_forced_dur, float* d_wav,
+                                 int64_t wav_capacity, int32_t* d_dur, int64_t* h_wav_start,
+                                 int64_t* h_n_samples, bool with_spkr, const int32_t* h_spkr) {
   if (!v || B <= 0 || !d_codes || !d_wav || !d_dur) return SS_ERR_ARG;
+  if (!spkr_args_ok(v, with_spkr, h_spkr, B)) return SS_ERR_ARG;
   SkScope sk_scope(v->sc->skws);
   hipStream_t s = (hipStream_t)stream;
   const ss_vocoder_config& c = v->cfg;
@@ -512,7 +562,7 @@ extern "C" int ss_batch_vocoder_forward(ss_vocoder* v, void* stream, int B, cons
     int* a = &tk[4 * b]; a[0] = ok.off[b]; a[1] = h_K[b]; a[2] = ok.off[b]; a[3] = h_K[b];
     tk[4 * B + 2 * b] = ok.off[b]; tk[4 * B + 2 * b + 1] = h_K[b];
   }
-  RET(v->sc->v_segs.ensure((6 * B + 16 * B) * sizeof(int)));
+  RET(v->sc->v_segs.ensure((6 * B + 16 * B + (with_spkr ? B : 0)) * sizeof(int)));   // + the speaker of every segment
   int* dk = (int*)v->sc->v_segs.p;
   RET(upload(s, dk, tk));
   RET(launch_gather_rows(d_codes, v->dict, E, emb, Kt, s, v->cfg.num_embeddings));
@@ -580,6 +630,12 @@ extern "C" int ss_batch_vocoder_forward(ss_vocoder* v, void* stream, int B, cons
     RET(upload(s, drep, t));
   }
   RET(launch_repeat_rows(emb, cum, 0, E, frames, of.mx, s, drep, B));
+  SpkSel sel;
+  if (with_spkr) {
+    int* dspk = dk + 6 * B + 16 * B;   // speaker of segment b [B]
+    RET(upload(s, dspk, std::vector<int>(h_spkr, h_spkr + B)));
+    sel.seg = dspk; sel.max_frames = of.mx;
+  }
   int scale = 1, C = 0;
   RET(hifigan_stack(v, s,
                     [&](GemmArgs& a, int sc) {
@@ -588,7 +644,7 @@ extern "C" int ss_batch_vocoder_forward(ss_vocoder* v, void* stream, int B, cons
                     },
                     stage_segs,
                     [&](int sc, int& M, const int*& segs, int& nseg) { M = Ft * sc; segs = dseg; nseg = B; },
-                    frames, Ft, gb, &scale, &C));
+                    frames, Ft, gb, &scale, &C, with_spkr ? &sel : nullptr));
   float* bx = gb.bx;
   {
     std::vector<int> t(2 * B);
@@ -596,6 +652,22 @@ extern "C" int ss_batch_vocoder_forward(ss_vocoder* v, void* stream, int B, cons
     RET(upload(s, dwav, t));
   }
   return launch_conv_post_tanh(bx, of.mx * scale, C, v->post.w, v->post.b, 0.01f, d_wav, s, dwav, B);
+}
+
+extern "C" int ss_batch_vocoder_forward(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K,
+                                        int dur_prediction, const int32_t* d_forced_dur, float* d_wav,
+                                        int64_t wav_capacity, int32_t* d_dur, int64_t* h_wav_start,
+                                        int64_t* h_n_samples) {
+  return batch_vocoder_forward(v, stream, B, d_codes, h_K, dur_prediction, d_forced_dur, d_wav, wav_capacity, d_dur, h_wav_start,
+                               h_n_samples, false, nullptr);
+}
+
+extern "C" int ss_batch_vocoder_forward_spkr(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K,
+                                             int dur_prediction, const int32_t* d_forced_dur, float* d_wav,
+                                             int64_t wav_capacity, int32_t* d_dur, int64_t* h_wav_start,
+                                             int64_t* h_n_samples, const int32_t* h_spkr) {
+  return batch_vocoder_forward(v, stream, B, d_codes, h_K, dur_prediction, d_forced_dur, d_wav, wav_capacity, d_dur, h_wav_start,
+                               h_n_samples, true, h_spkr);
 }
 
 
@@ -607,13 +679,16 @@ extern "C" int ss_batch_vocoder_forward(ss_vocoder* v, void* stream, int B, cons
 // predictor pass; ONE synchronisation reads their cumulative durations, the host picks per row, and the generator runs over the picked
 // segments only, its conv_post computing only the kept tail of each.  h_win_first[b] = the first unit synthesised (0: all units);
 // h_dur (host, sum K ints) = the durations of what was synthesised, row b at the prefix sum of h_K, h_K[b] - h_win_first[b] of them.
-extern "C" int ss_batch_vocoder_tail(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K,
-                                     const int32_t* h_n_new, const int32_t* h_ctx, const int32_t* h_rf, int dur_prediction,
-                                     float* d_out, int64_t out_capacity, int32_t* h_win_first, int32_t* h_dur, int64_t* h_out_start,
-                                     int64_t* h_n_out) {
+// Multi-speaker (h_spkr [B]): a row's speaker goes with the row -- its window and its fallback candidate are the same voice (the
+// duration predictor does not see the speaker), and generator row g takes the speaker of row G[g].
+static int batch_vocoder_tail(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K,
+                              const int32_t* h_n_new, const int32_t* h_ctx, const int32_t* h_rf, int dur_prediction,
+                              float* d_out, int64_t out_capacity, int32_t* h_win_first, int32_t* h_dur, int64_t* h_out_start,
+                              int64_t* h_n_out, bool with_spkr, const int32_t* h_spkr) {
   if (!v || B <= 0 || B > 32768 || !d_codes || !h_K || !h_n_new || !h_ctx || !h_rf || !d_out || !h_win_first || !h_dur ||
       !h_out_start || !h_n_out)
     return SS_ERR_ARG;
+  if (!spkr_args_ok(v, with_spkr, h_spkr, B)) return SS_ERR_ARG;
   const ss_vocoder_config& c = v->cfg;
   const int E = c.embedding_dim, Hd = c.dur_hidden;
   for (int b = 0; b < B; ++b)
@@ -635,7 +710,7 @@ extern "C" int ss_batch_vocoder_tail(ss_vocoder* v, void* stream, int B, const i
   // ---- buffers first ----
   const size_t n_small = (size_t)ok.total * E + (size_t)Kc * (E + 2 * Hd + 1) + 3 * ((size_t)Kc + S + 2);
   RET(v->sc->v_small.ensure(n_small * sizeof(float)));
-  RET(v->sc->v_segs.ensure(((size_t)Kc + 6 * S + 12 * B) * sizeof(int)));   // + conv / repeat / conv_post segs of the generator rows
+  RET(v->sc->v_segs.ensure(((size_t)Kc + 6 * S + 12 * B + (with_spkr ? B : 0)) * sizeof(int)));   // + conv / repeat / conv_post segs of the generator rows (+ their speakers)
   SkScope sk_scope(v->sc->skws);
   hipStream_t s = (hipStream_t)stream;
   float* emb_all = v->sc->v_small.f();
@@ -761,6 +836,14 @@ extern "C" int ss_batch_vocoder_tail(ss_vocoder* v, void* stream, int B, const i
     RET(upload(s, drep, t));
   }
   RET(launch_repeat_rows(emb, aux, 0, E, frames, of.mx, s, drep, NG));
+  SpkSel sel;
+  if (with_spkr) {
+    int* dspk = dk + Kc + 6 * S + 12 * B;   // speaker of generator row g [NG]
+    std::vector<int> t(NG);
+    for (int g = 0; g < NG; ++g) t[g] = h_spkr[G[g]];
+    RET(upload(s, dspk, t));
+    sel.seg = dspk; sel.max_frames = of.mx;
+  }
   int scale = 1, Cf = 0;
   RET(hifigan_stack(v, s,
                     [&](GemmArgs& a, int sc) {
@@ -769,7 +852,7 @@ extern "C" int ss_batch_vocoder_tail(ss_vocoder* v, void* stream, int B, const i
                     },
                     stage_segs,
                     [&](int sc, int& M, const int*& segs, int& nseg) { M = Ft * sc; segs = dseg; nseg = NG; },
-                    frames, Ft, gb, &scale, &Cf));
+                    frames, Ft, gb, &scale, &Cf, with_spkr ? &sel : nullptr));
   // conv_post over the kept tail of each generator row only, straight into the packed output (the crop happens here)
   int* dpost = drep + 4 * B;         // {sample_start, n_samples, first kept, out_start} [NG]
   std::vector<int> t(4 * NG);
@@ -781,4 +864,20 @@ extern "C" int ss_batch_vocoder_tail(ss_vocoder* v, void* stream, int B, const i
   }
   RET(upload(s, dpost, t));
   return launch_conv_post_tanh_crop(gb.bx, Cf, v->post.w, v->post.b, 0.01f, d_out, dpost, NG, max_keep, s);
+}
+
+extern "C" int ss_batch_vocoder_tail(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K,
+                                     const int32_t* h_n_new, const int32_t* h_ctx, const int32_t* h_rf, int dur_prediction,
+                                     float* d_out, int64_t out_capacity, int32_t* h_win_first, int32_t* h_dur, int64_t* h_out_start,
+                                     int64_t* h_n_out) {
+  return batch_vocoder_tail(v, stream, B, d_codes, h_K, h_n_new, h_ctx, h_rf, dur_prediction, d_out, out_capacity, h_win_first, h_dur,
+                            h_out_start, h_n_out, false, nullptr);
+}
+
+extern "C" int ss_batch_vocoder_tail_spkr(ss_vocoder* v, void* stream, int B, const int32_t* d_codes, const int32_t* h_K,
+                                          const int32_t* h_n_new, const int32_t* h_ctx, const int32_t* h_rf, int dur_prediction,
+                                          float* d_out, int64_t out_capacity, int32_t* h_win_first, int32_t* h_dur,
+                                          int64_t* h_out_start, int64_t* h_n_out, const int32_t* h_spkr) {
+  return batch_vocoder_tail(v, stream, B, d_codes, h_K, h_n_new, h_ctx, h_rf, dur_prediction, d_out, out_capacity, h_win_first, h_dur,
+                            h_out_start, h_n_out, true, h_spkr);
 }

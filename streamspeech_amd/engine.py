@@ -990,7 +990,10 @@ class HipVocoder:
         self._packed = (names, offsets, numels, self.blob)
         c = self.cfg
         cc = L.SSVocoderConfig()
-        cc.num_embeddings, cc.embedding_dim, cc.model_in_dim = c.num_embeddings, c.embedding_dim, c.model_in_dim
+        c.validate()
+        # model_in_dim handed to the library is the CODE half's width: a multi-speaker conv_pre contracts the code embeddings only,
+        # its speaker half is the "voc.spkr.table" slot of the blob (header: ss_vocoder_forward_spkr)
+        cc.num_embeddings, cc.embedding_dim, cc.model_in_dim = c.num_embeddings, c.embedding_dim, c.embedding_dim
         cc.upsample_initial_channel = c.upsample_initial_channel
         cc.n_up = len(c.upsample_rates)
         for i, (u, k) in enumerate(zip(c.upsample_rates, c.upsample_kernel_sizes)):
@@ -1009,6 +1012,7 @@ class HipVocoder:
             L.check(self.lib.ss_vocoder_create(C.byref(cc), _ptr(self.blob), self.blob.numel(), cn, co, cm, n,
                                                C.byref(h)), "ss_vocoder_create")
         self.h = h
+        self.num_speakers = int(self.lib.ss_vocoder_num_speakers(self.h))       # 0: single-speaker
         self.scratch = None
         if scratch is not None:
             self.bind_scratch(scratch)
@@ -1046,9 +1050,28 @@ class HipVocoder:
         if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.cfg.num_embeddings):
             raise IndexError(f"unit id outside the vocoder's {self.cfg.num_embeddings} codes")
 
-    def batch_forward(self, codes: List[List[int]], dur_prediction=True, forced_dur: Optional[List[List[int]]] = None):
-        """-> (list of wav tensors (views into one packed buffer), list of dur lists)."""
+    def _check_speakers(self, speakers, n: int) -> Optional[List[int]]:
+        """The voices of an n-row call: None on a single-speaker handle (which takes none), n ids inside [0, num_speakers) on a
+        multi-speaker one.  nn.Embedding(num_speakers, ...) of the reference raises IndexError on an id outside."""
+        if not self.num_speakers:
+            if speakers is not None:
+                raise ValueError("this vocoder is single-speaker: it takes no speaker")
+            return None
+        if speakers is None:
+            raise ValueError('require a speaker for a multi-speaker vocoder (the reference: require "spkr" input)')
+        ids = [int(x) for x in speakers]
+        if len(ids) != n:
+            raise ValueError(f"{len(ids)} speakers for {n} rows")
+        if any(x < 0 or x >= self.num_speakers for x in ids):
+            raise IndexError(f"speaker id outside the vocoder's {self.num_speakers} speakers")
+        return ids
+
+    def batch_forward(self, codes: List[List[int]], dur_prediction=True, forced_dur: Optional[List[List[int]]] = None,
+                      speakers: Optional[List[int]] = None):
+        """-> (list of wav tensors (views into one packed buffer), list of dur lists).  speakers: one id per row on a
+        multi-speaker vocoder -- any mix of voices in the one pack."""
         B = len(codes)
+        spk = self._check_speakers(speakers, B)
         K = [len(c) for c in codes]
         flat = torch.tensor([u for c in codes for u in c], dtype=torch.int32)
         self._check_units(flat)
@@ -1062,18 +1085,26 @@ class HipVocoder:
         wav = torch.empty((cap,), dtype=torch.float32, device=self.device)
         dur = torch.empty((sum(K),), dtype=torch.int32, device=self.device)
         st, ns = (C.c_int64 * B)(), (C.c_int64 * B)()
-        L.check(self.lib.ss_batch_vocoder_forward(self.h, _stream(), B, _ptr(flat), _i32(K), int(dur_prediction), _ptr(fd),
-                                                  _ptr(wav), cap, _ptr(dur), st, ns), "ss_batch_vocoder_forward")
+        if spk is None:
+            L.check(self.lib.ss_batch_vocoder_forward(self.h, _stream(), B, _ptr(flat), _i32(K), int(dur_prediction), _ptr(fd),
+                                                      _ptr(wav), cap, _ptr(dur), st, ns), "ss_batch_vocoder_forward")
+        else:
+            L.check(self.lib.ss_batch_vocoder_forward_spkr(self.h, _stream(), B, _ptr(flat), _i32(K), int(dur_prediction), _ptr(fd),
+                                                           _ptr(wav), cap, _ptr(dur), st, ns, _i32(spk)),
+                    "ss_batch_vocoder_forward_spkr")
         wavs = [wav[st[b]: st[b] + ns[b]] for b in range(B)]
         return wavs, dur, K
 
-    def batch_tail(self, codes: List[List[int]], n_new: List[int], ctx: List[int], rf: List[int], dur_prediction: bool = True):
+    def batch_tail(self, codes: List[List[int]], n_new: List[int], ctx: List[int], rf: List[int], dur_prediction: bool = True,
+                   speakers: Optional[List[int]] = None):
         """B rows of the agent's receptive-field tail (agent.synthesize_tail) in one call (ss_batch_vocoder_tail).  -> (per row the
         samples of its n_new[b] new units (views into one packed buffer), per row (first unit synthesised, durations of the
-        synthesised units)).  A windowed row whose context does not cover the receptive field falls back to all its units."""
+        synthesised units)).  A windowed row whose context does not cover the receptive field falls back to all its units.
+        speakers: one id per row on a multi-speaker vocoder; rows of different voices share the one call."""
         B = len(codes)
         if not (len(n_new) == len(ctx) == len(rf) == B) or B == 0:
             raise ValueError("one unit list, n_new, ctx and rf per row")
+        spk = self._check_speakers(speakers, B)
         K = [len(c) for c in codes]
         flat = torch.tensor([u for c in codes for u in c], dtype=torch.int32)
         self._check_units(flat)
@@ -1083,9 +1114,14 @@ class HipVocoder:
         first = (C.c_int32 * B)()
         dur = (C.c_int32 * max(sum(K), 1))()
         st, ns = (C.c_int64 * B)(), (C.c_int64 * B)()
-        L.check(self.lib.ss_batch_vocoder_tail(self.h, _stream(), B, _ptr(flat), _i32(K), _i32(n_new), _i32(ctx),
-                                               _i32([-1 if r is None else r for r in rf]), int(dur_prediction), _ptr(out), cap,
-                                               first, dur, st, ns), "ss_batch_vocoder_tail")
+        rfs = _i32([-1 if r is None else r for r in rf])
+        if spk is None:
+            L.check(self.lib.ss_batch_vocoder_tail(self.h, _stream(), B, _ptr(flat), _i32(K), _i32(n_new), _i32(ctx), rfs,
+                                                   int(dur_prediction), _ptr(out), cap, first, dur, st, ns), "ss_batch_vocoder_tail")
+        else:
+            L.check(self.lib.ss_batch_vocoder_tail_spkr(self.h, _stream(), B, _ptr(flat), _i32(K), _i32(n_new), _i32(ctx), rfs,
+                                                        int(dur_prediction), _ptr(out), cap, first, dur, st, ns, _i32(spk)),
+                    "ss_batch_vocoder_tail_spkr")
         tails = [out[st[b]: st[b] + ns[b]] for b in range(B)]
         info, off = [], 0
         for b in range(B):
@@ -1101,8 +1137,10 @@ class HipVocoder:
         except Exception:
             pass
 
-    def forward(self, codes, dur_prediction: bool = True, forced_dur=None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """codes: list/array/tensor of unit ids -> (wav [S] float32 device, dur [K] int32 device)."""
+    def forward(self, codes, dur_prediction: bool = True, forced_dur=None, speaker: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """codes: list/array/tensor of unit ids -> (wav [S] float32 device, dur [K] int32 device).  speaker: the voice, on a
+        multi-speaker vocoder (required there)."""
+        spk = self._check_speakers(None if speaker is None else [speaker], 1)
         codes_t = torch.as_tensor(codes, dtype=torch.int32).reshape(-1)
         if not codes_t.is_cuda:
             self._check_units(codes_t)                      # device-resident ids are guarded by the gather kernel instead
@@ -1113,7 +1151,12 @@ class HipVocoder:
         wav = torch.empty((cap,), dtype=torch.float32, device=self.device)
         dur = torch.empty((K,), dtype=torch.int32, device=self.device)
         ns = C.c_int64(0)
-        rc = self.lib.ss_vocoder_forward(self.h, _stream(), _ptr(codes_t), K, int(dur_prediction), _ptr(fd),
-                                         _ptr(wav), cap, _ptr(dur), C.byref(ns))
-        L.check(rc, "ss_vocoder_forward")
+        if spk is None:
+            rc = self.lib.ss_vocoder_forward(self.h, _stream(), _ptr(codes_t), K, int(dur_prediction), _ptr(fd),
+                                             _ptr(wav), cap, _ptr(dur), C.byref(ns))
+            L.check(rc, "ss_vocoder_forward")
+        else:
+            rc = self.lib.ss_vocoder_forward_spkr(self.h, _stream(), _ptr(codes_t), K, int(dur_prediction), _ptr(fd),
+                                                  _ptr(wav), cap, _ptr(dur), C.byref(ns), spk[0])
+            L.check(rc, "ss_vocoder_forward_spkr")
         return wav[: ns.value], dur

@@ -192,6 +192,13 @@ SIGNATURES = {
     "ss_vocoder_set_bf16x3": (_i, [_vp, _i]),
     "ss_vocoder_set_f16": (_i, [_vp, _i]),
     "ss_vocoder_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp, C.POINTER(_i64)]),
+    "ss_vocoder_num_speakers": (_i, [_vp]),
+    "ss_vocoder_forward_spkr": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp, C.POINTER(_i64), C.c_int32]),
+    "ss_batch_vocoder_forward_spkr": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _vp, _vp, _i64, _vp,
+                                           C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32)]),
+    "ss_batch_vocoder_tail_spkr": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), _i, _vp, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "ss_batch_fbank_cmvn": (_i, [_vp, _vp, _i, _vp, C.POINTER(_i64), C.POINTER(C.c_int32), _f, _vp, C.POINTER(C.c_int32)]),
     "ss_batch_encoder_forward": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _i, _vp, C.POINTER(C.c_int32)]),
     "ss_batch_ctc_greedy": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp]),
@@ -274,6 +281,7 @@ SIGNATURES = {
     "ss_op_scatter_rows": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i]),
     "ss_op_conv_post_tanh": (_i, [_vp, _vp, _i, _i, _vp, _vp, _f, _vp, _vp, _i]),
     "ss_op_conv_post_tanh_crop": (_i, [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _i]),
+    "ss_op_spkr_pre_add": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _f]),
     "ss_op_beam_topk": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
     "ss_op_beam_merge": (_i, [_vp, C.POINTER(SSOpBeamState), _i, _i, _i, _i, _i, _i, _i, _i]),
     "ss_op_beam_prefix_score": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _vp]),

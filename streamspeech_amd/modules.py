@@ -274,7 +274,9 @@ def load_model_state(path: str):
 
 @register_model("CodeHiFiGANVocoderWithDur")
 class CodeHiFiGANVocoderWithDur:
-    """agent/tts/vocoder.py:30-60: ``vocoder({"code": LongTensor[1,K]}, dur_prediction) -> (wav[S], dur[1,K])``."""
+    """agent/tts/vocoder.py:30-60: ``vocoder({"code": LongTensor[1,K]}, dur_prediction) -> (wav[S], dur[1,K])``.  A multi-speaker
+    vocoder (``"multispkr": true``) also reads ``x["spkr"]``, a LongTensor [1,1] (codehifigan.py:80-86); a single-speaker one
+    ignores that key like the reference (codehifigan.py:88-90)."""
 
     def __init__(self, checkpoint_path: str, model_cfg: Dict = None, fp16: bool = False, device="cuda:0"):
         assert not fp16, "the HIP path is FP32 (parity with the reference CPU path)"
@@ -296,7 +298,11 @@ class CodeHiFiGANVocoderWithDur:
         assert "code" in x
         code = x["code"]
         code = code[code >= 0].view(-1)                      # remove invalid code (vocoder.py:52-54)
-        wav, dur = self.hip.forward(code.to(torch.int32), dur_prediction)
+        speaker = None
+        if self.hip.num_speakers:
+            assert "spkr" in x, 'require "spkr" input for multispeaker CodeHiFiGAN vocoder'
+            speaker = int(torch.as_tensor(x["spkr"]).reshape(-1)[0])
+        wav, dur = self.hip.forward(code.to(torch.int32), dur_prediction, speaker=speaker)
         return wav, dur.view(1, -1).long()
 
     forward = __call__
@@ -304,7 +310,13 @@ class CodeHiFiGANVocoderWithDur:
 
 def vocoder_config_from_json(d: Dict) -> VocoderConfig:
     dp = d.get("dur_predictor_params") or {}
+    for key, what in (("f0", d.get("f0")), ("f0_quant_num_bin", (d.get("f0_quant_num_bin") or 0) > 0),
+                      ("embedder_params", d.get("embedder_params"))):
+        if what:
+            raise ValueError(f'vocoder config sets "{key}": F0-conditioned vocoders and speaker d-vectors (embedder_params) are '
+                             "not supported (multi-speaker checkpoints with a speaker embedding table are: \"multispkr\")")
     return VocoderConfig(
+        multispkr=bool(d.get("multispkr")), num_speakers=d.get("num_speakers", 200),
         num_embeddings=d.get("num_embeddings", 1000), embedding_dim=d.get("embedding_dim", 128),
         model_in_dim=d.get("model_in_dim", 128), upsample_rates=tuple(d["upsample_rates"]),
         upsample_kernel_sizes=tuple(d["upsample_kernel_sizes"]),

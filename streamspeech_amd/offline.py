@@ -29,6 +29,7 @@ tests/golden/offline_generator.json; tests/test_offline_generator_cpu.py, tests/
 import argparse
 import math
 import os
+import random
 import sys
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -67,11 +68,16 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              subset: str = "test", batch_size: int = 32, max_tokens: int = 0, max_len_a: float = 0.0,
              max_len_b: int = 200, max_len_a_mt: float = 0.0, max_len_b_mt: int = 200, dur_prediction: bool = True, dump_wav: bool = True, t2u_causal: bool = False,
              scores: bool = False, log=None, targets: Optional[Dict[int, Sequence[int]]] = None, beam_mt: int = 1,
-             unk_penalty: float = 0.0, normalize: bool = True, pcm16_out: bool = False) -> Dict[int, Dict]:
+             unk_penalty: float = 0.0, normalize: bool = True, pcm16_out: bool = False, speaker_id: int = -1) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     pcm16_out (--pcm16-io): the waveforms of a batch become 16-bit PCM on the device (one ss_pcm_pack_s16, one download per batch)
-    and pred_wav/ is written from those bytes -- the same files, without a float download and a host rounding per utterance."""
+    and pred_wav/ is written from those bytes -- the same files, without a float download and a host rounding per utterance.
+    speaker_id (--speaker-id; multi-speaker vocoders only): the voice of every utterance; -1 draws one per utterance with
+    random.randint(0, num_speakers - 1) like generate_waveform_from_code.py:69-75 and records it in the log (`K-<id>` lines)."""
+    n_spk = int(getattr(vocoder, "num_speakers", 0) or 0)
+    if n_spk and not -1 <= speaker_id < n_spk:
+        raise ValueError(f"--speaker-id {speaker_id} is outside the vocoder's {n_spk} speakers (-1: a random one per utterance)")
     cfg = model.cfg
     os.makedirs(results_path, exist_ok=True)
     log_f = log or open(os.path.join(results_path, f"generate-{subset}.log"), "w", encoding="utf-8")
@@ -111,7 +117,12 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
         have = [b for b, c in enumerate(codes) if len(c) > 0]
         wavs: Dict[int, torch.Tensor] = {}
         if dump_wav and have:
-            w, _, _ = vocoder.batch_forward([codes[b] for b in have], dur_prediction=dur_prediction)
+            spk = {}
+            if n_spk:                           # one pack, a voice per row
+                spk["speakers"] = [speaker_id if speaker_id >= 0 else random.randint(0, n_spk - 1) for _ in have]
+                for b, k in zip(have, spk["speakers"]):
+                    print(f"K-{ids[b]}\t{k}", file=log_f)
+            w, _, _ = vocoder.batch_forward([codes[b] for b in have], dur_prediction=dur_prediction, **spk)
             wavs = {b: w[j] for j, b in enumerate(have)}
             if pcm16_out:
                 pcm16 = _pack_batch(model, [wavs[b] for b in have])
@@ -254,6 +265,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--vocoder-fp16", action="store_true",
                     help="run the vocoder's 64- to 256-channel ResBlock convs on FP16 matrix cores (f32 accumulation; waveform within "
                          "1e-3 RMS, unit ids and durations unchanged); default: exact f32")
+    ap.add_argument("--speaker-id", type=int, default=-1,
+                    help="multi-speaker vocoders: the voice of every utterance; -1 (default, as generate_waveform_from_code.py) draws "
+                         "a random speaker per utterance and logs it; ignored by a single-speaker vocoder")
     ap.add_argument("--no-wav", action="store_true")
     ap.add_argument("--scores", action="store_true")
     ap.add_argument("--num-shards", type=int, default=int(os.environ.get("WORLD_SIZE", "1")))
@@ -341,7 +355,7 @@ def main(argv: Optional[List[str]] = None):
                     a.max_len_b, a.max_len_a_mt, a.max_len_b_mt, a.dur_prediction, not a.no_wav,
                     getattr(holder.model, "uni_encoder", False), a.scores, targets=targets or None, beam_mt=a.beam_mt,
                     unk_penalty=a.unkpen, normalize=not a.unnormalized,
-                    **({"pcm16_out": True} if a.pcm16_io else {}))
+                    **({"pcm16_out": True} if a.pcm16_io else {}), **({"speaker_id": a.speaker_id} if voc.num_speakers else {}))
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
 
 

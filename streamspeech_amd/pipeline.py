@@ -58,8 +58,9 @@ def units_from_tokens(tokens: List[int], cfg) -> List[int]:
 
 def offline_s2st(model: HipModel, vocoder: HipVocoder, fbank: torch.Tensor, attn_chunk: int = 999999,
                  conv_chunk: int = 999999, forced_mt_tokens: Optional[List[int]] = None,
-                 t2u_causal: bool = False, dur_prediction: bool = True) -> Dict:
-    """fbank [T,80] on the device -> dict(asr, st, mt, units, dur, wav)  (BASELINE.json configs[1])."""
+                 t2u_causal: bool = False, dur_prediction: bool = True, speaker: Optional[int] = None) -> Dict:
+    """fbank [T,80] on the device -> dict(asr, st, mt, units, dur, wav)  (BASELINE.json configs[1]).  speaker: the voice, with a
+    multi-speaker vocoder."""
     cfg = model.cfg
     enc = model.encoder_forward(fbank, attn_chunk, conv_chunk)
     asr, asr_idx, _, _ = model.ctc_greedy(0, enc)
@@ -77,7 +78,7 @@ def offline_s2st(model: HipModel, vocoder: HipVocoder, fbank: torch.Tensor, attn
     units = units_from_tokens(unit_toks, cfg)
     out = {"enc": enc, "asr": asr, "st": st, "mt": toks, "units": units, "asr_index": asr_idx, "st_index": st_idx}
     if units:
-        wav, dur = vocoder.forward(units, dur_prediction)
+        wav, dur = vocoder.forward(units, dur_prediction, **({} if speaker is None else {"speaker": speaker}))
         out["wav"], out["dur"] = wav, dur
     return out
 

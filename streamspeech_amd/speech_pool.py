@@ -5,7 +5,8 @@ pool step is (one fbank launch, one encoder step with both CTC heads, the gates 
 the S2TT writers) and then, for the S2ST sessions that write,
   * ONE ragged MT feature pass for the rows whose final write carries a trailing <pad> (HipModel.batch_mt_features),
   * ONE T2U + unit decoder call with per-row tail-pad masks (HipModel.batch_t2u_units_pad),
-  * ONE receptive-field vocoder tail call (HipVocoder.batch_tail; one per duration-prediction setting in use).
+  * ONE receptive-field vocoder tail call (HipVocoder.batch_tail; one per duration-prediction setting in use).  On a multi-speaker
+    vocoder every session has its own voice (``args.speaker_id``); the voices ride in that one call as per-row speakers.
 Driven by one host thread, like the pool.
 
 An S2ST session opened with ``pcm_out="s16le"`` answers :class:`PcmSegment` (16-bit PCM bytes) instead of a SpeechSegment holding a
@@ -22,6 +23,7 @@ import time
 import numpy as np
 import torch
 
+from .agent import speaker_id_arg
 from .frontend import SAMPLE_RATE
 from .pcm import PcmEmitter, PcmSegment, pack_s16_host
 from .simuleval_shim import SpeechSegment
@@ -53,8 +55,9 @@ def whole_word_cut(tokens, symbol):
 
 
 class _SpeechSession(_Session):
-    def __init__(self, sid, kind, args, engine, dicts, vocoder_cfg):
+    def __init__(self, sid, kind, args, engine, dicts, vocoder_cfg, speaker_id=None):
         super().__init__(sid, kind, args, engine, dicts)
+        self.speaker_id = speaker_id              # the session's voice on a multi-speaker vocoder (None: single-speaker)
         self.whole_word = args.source_segment_size >= 640
         self.dur_prediction = bool(args.dur_prediction)
         self.vocoder_ctx, self.vocoder_rf = vocoder_context(vocoder_cfg, getattr(args, "vocoder_context_units", -1))
@@ -85,11 +88,13 @@ class SpeechSessionPool(TextSessionPool):
             raise ValueError("an s2st session needs the pool's vocoder: SpeechSessionPool(..., vocoder=...)")
         if getattr(args, "full_recompute_encoder", False):
             raise ValueError("--full-recompute-encoder: the session pool encodes incrementally by construction")
+        speaker_id_arg(args, self.vocoder, "args.speaker_id (--speaker-id)")   # multi-speaker vocoder: refused here, not at the first write
 
     def _new_session(self, sid, kind, args, dicts):
         if kind != "s2st":
             return super()._new_session(sid, kind, args, dicts)
-        return _SpeechSession(sid, kind, args, self.model, dicts, getattr(self.vocoder, "cfg", None))
+        return _SpeechSession(sid, kind, args, self.model, dicts, getattr(self.vocoder, "cfg", None),
+                              speaker_id_arg(args, self.vocoder))
 
     # ---- the S2ST agent's policy, split at the pool's shared calls ---------------------------------------------------------------
     def _gate(self, s, src_ids, tgt_ids, n_frames):
@@ -189,12 +194,16 @@ class SpeechSessionPool(TextSessionPool):
         t2 = time.perf_counter()
         handover, raw = 0.0, []                           # raw: (session, tail) of the pcm_out writers, packed together below
         own = []                                          # the same of the PcmOut writers, emitted together below
+        tail_calls = 0
         for dp in (True, False):
             grp = [v for v in voc if v[0].dur_prediction == dp]
             if not grp:
                 continue
+            tail_calls += 1
+            # a multi-speaker vocoder: the rows' voices go along in the same call (no grouping by voice)
+            spk = {"speakers": [s.speaker_id for s, _, _ in grp]} if getattr(self.vocoder, "num_speakers", 0) else {}
             tails, _ = self.vocoder.batch_tail([u for _, u, _ in grp], [k for _, _, k in grp], [s.vocoder_ctx for s, _, _ in grp],
-                                               [s.vocoder_rf for s, _, _ in grp], dur_prediction=dp)
+                                               [s.vocoder_rf for s, _, _ in grp], dur_prediction=dp, **spk)
             th = time.perf_counter()
             for (s, unit, _), wav in zip(grp, tails):
                 if s.unfinished_wav is not None and len(s.unfinished_wav) > 0:
@@ -218,7 +227,8 @@ class SpeechSessionPool(TextSessionPool):
         # handover_s: from the tails' views in hand to the contents the segments carry (lists or bytes), both routes; it lies inside
         # vocoder_s, which keeps its meaning (the tail calls and what follows them)
         self._side_times = {"mt_features_s": t1 - t0, "units_s": t2 - t1, "vocoder_s": t3 - t2, "handover_s": handover + (t3 - th),
-                            "speech_writers": len(voc), "pcm_pack_calls": 1 if n_out else 0, "pcm_bytes_out": 2 * n_out,
+                            "speech_writers": len(voc), "vocoder_tail_calls": tail_calls, "pcm_pack_calls": 1 if n_out else 0,
+                            "pcm_bytes_out": 2 * n_out,
                             "pcm_emit_calls": emit_calls, "pcm_emit_bytes_out": emit_bytes}
 
     def _emit_out(self, own, flush, actions):

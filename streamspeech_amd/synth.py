@@ -191,6 +191,8 @@ def make_vocoder_state_dict(seed: int = 0, cfg: VocoderConfig = None) -> Dict[st
     sd["dur_predictor.ln2.bias"] = normal(seed, "dur.ln2.b", (H,), 0.05)
     sd["dur_predictor.proj.weight"] = normal(seed, "dur.proj.w", (1, H), 0.6 / np.sqrt(H))
     sd["dur_predictor.proj.bias"] = np.full((1,), 0.75, np.float32)
+    if cfg.multispkr:   # nn.Embedding(num_speakers, embedding_dim) of a multi-speaker checkpoint (codehifigan.py:16-17)
+        sd["spkr.weight"] = normal(seed, "spkr.weight", (cfg.num_speakers, E), 1.0)
 
     C0 = cfg.upsample_initial_channel
     wn_conv("conv_pre", (C0, cfg.model_in_dim, 7), 1.0)

@@ -19,6 +19,8 @@ Appendix A) and produces ``(names, offsets, numels, blob)`` for ``ss_model_creat
   tap index falls outside [0,k)).
 * weight-norm pairs folded with ``torch._weight_norm`` -- the op ``remove_weight_norm`` uses
   (reference fairseq/models/text_to_speech/hifigan.py:172-179).
+* multi-speaker vocoder (``spkr.weight`` present): conv_pre ``[C0, 2E, 7]`` is folded whole, its code half packed as the usual
+  ``voc.pre.w`` and its speaker half contracted with every speaker's embedding into ``voc.spkr.table`` (``speaker_table``).
 * sinusoid tables built with the same torch ops as the reference
   (fairseq/modules/positional_encoding.py:94-111, sinusoidal_positional_embedding.py:43-64).
 """
@@ -232,8 +234,34 @@ def fold_weight_norm(sd: Dict, name: str) -> torch.Tensor:
     return torch._weight_norm(_t(sd[name + ".weight_v"]), _t(sd[name + ".weight_g"]), 0)
 
 
+def speaker_table(w_pre: torch.Tensor, spkr: torch.Tensor) -> torch.Tensor:
+    """The speaker half of a multi-speaker conv_pre as a table ``[num_speakers][16][C0]`` (float32).
+
+    ``w_pre`` is the folded conv_pre weight ``[C0, 2E, 7]``, ``spkr`` the speaker embeddings ``[S, E]``.  The speaker vector is
+    constant over the frames of a segment, so its contribution to output row t of a segment of L frames (padding 3) is the sum of
+    ``G[k][co] = sum_c w_pre[co, E + c, k] * spkr[s, c]`` over the taps k that fall inside the segment, ``lo = max(0, 3 - t)`` to
+    ``hi = min(6, L + 2 - t)``: lo is in 0..3 and hi in 3..6, 16 sums.  Entry ``(lo, hi)`` sits at index ``4 * lo + (hi - 3)``.
+    G and the sums (ascending k) are computed in float64 and rounded to float32 once."""
+    E = spkr.shape[1]
+    G = torch.einsum("ock,sc->sko", w_pre[:, E:, :].double(), spkr.double())          # [S, 7, C0]
+    rows = []
+    for lo in range(4):
+        for hi in range(3, 7):
+            acc = torch.zeros_like(G[:, 0])
+            for k in range(lo, hi + 1):
+                acc = acc + G[:, k]
+            rows.append(acc)
+    return torch.stack(rows, 1).float()                                                 # [S, 16, C0]
+
+
 def pack_vocoder(vsd: Dict, vcfg: VocoderConfig):
     """state["generator"] of the unit HiFi-GAN -> (names, offsets, numels, blob)."""
+    vcfg.validate()
+    multi = "spkr.weight" in vsd
+    if multi != bool(vcfg.multispkr):
+        raise ValueError("spkr.weight in the checkpoint and multispkr in the vocoder config must come together")
+    if "spkr.bias" in vsd:
+        raise ValueError("embedder_params (a speaker d-vector through a Linear) is not supported")
     pk = Packer()
     pk.add("voc.dict", _t(vsd["dict.weight"]))
     pk.add("voc.dur.conv1.w", conv_tap_major(_t(vsd["dur_predictor.conv1.0.weight"])))
@@ -244,8 +272,17 @@ def pack_vocoder(vsd: Dict, vcfg: VocoderConfig):
     _ln(pk, "voc.dur.ln2", vsd, "dur_predictor.ln2")
     pk.add("voc.dur.proj.w", _t(vsd["dur_predictor.proj.weight"]))
     pk.add("voc.dur.proj.b", _t(vsd["dur_predictor.proj.bias"]))
-    pk.add("voc.pre.w", conv_tap_major(fold_weight_norm(vsd, "conv_pre")))
+    w_pre = fold_weight_norm(vsd, "conv_pre")               # multi-speaker: [C0, 2E, 7], g normalises over both halves
+    E = vcfg.embedding_dim
+    if w_pre.shape[1] != vcfg.model_in_dim:
+        raise ValueError(f"conv_pre has {w_pre.shape[1]} input channels, the config's model_in_dim is {vcfg.model_in_dim}")
+    pk.add("voc.pre.w", conv_tap_major(w_pre[:, :E, :]))
     pk.add("voc.pre.b", _t(vsd["conv_pre.bias"]))
+    if multi:
+        spkr = _t(vsd["spkr.weight"])
+        if tuple(spkr.shape) != (vcfg.num_speakers, E):
+            raise ValueError(f"spkr.weight is {tuple(spkr.shape)}, the config says [num_speakers = {vcfg.num_speakers}, {E}]")
+        pk.add("voc.spkr.table", speaker_table(w_pre, spkr))
     nk = len(vcfg.resblock_kernel_sizes)
     for i, u in enumerate(vcfg.upsample_rates):
         w, b = convT_polyphase(fold_weight_norm(vsd, f"ups.{i}"), _t(vsd[f"ups.{i}.bias"]), u)
