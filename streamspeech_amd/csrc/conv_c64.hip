@@ -168,34 +168,32 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const GemmArgs p, cons
       pa = pa_next;
     }
 
-    // ---- epilogue: lane holds 4 consecutive channels (4g .. 4g+3 of column tile j) of row r of row tile i; a row tile's residual
-    // operands are all requested before the first is used ----
+    // ---- epilogue: lane holds 4 consecutive channels (4g .. 4g+3 of column tile j) of row r of row tile i; the residual operands
+    // of ALL row tiles are requested before the first is used, and everything is stored last (slab_epi_batch) ----
     int le = lane;
     asm volatile("" : "+v"(le));               // addresses derived from `le` cannot be hoisted above the contraction
     const int r_e = le & 15, g_e = le >> 4;
     f32x4 bb[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      bb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (p.bias) bb[j] = *reinterpret_cast<const f32x4*>(p.bias + j * 16 + g_e * 4);
+    for (int j = 0; j < 4; ++j) bb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (p.bias) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bb[j] = *reinterpret_cast<const f32x4*>(p.bias + j * 16 + g_e * 4);
     }
+    f32x4 y[WM * 4];                           // float4 i * 4 + j
+#pragma unroll
+    for (int i = 0; i < WM; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) y[i * 4 + j] = acc[i][j];
+    const int mw = m0 + wave * 16 * WM + r_e;  // this lane's row of row tile 0
+    slab_epi_batch(p, y, bb, [&](int q, int n) -> size_t {
+      return (size_t)min(mw + (n / 4) * 16, m_hi - 1) * (q == 0 ? p.ldr : p.ldr2) + (n % 4) * 16 + g_e * 4;
+    });
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
-      const int m = m0 + wave * 16 * WM + i * 16 + r_e;
-      const int mc = min(m, m_hi - 1);
-      f32x4 rr[4], rr2[4];
-      if (p.R) {
+      if (mw + i * 16 < m_hi) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) rr[j] = *reinterpret_cast<const f32x4*>(p.R + (size_t)mc * p.ldr + j * 16 + g_e * 4);
-      }
-      if (p.R2) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rr2[j] = *reinterpret_cast<const f32x4*>(p.R2 + (size_t)mc * p.ldr2 + j * 16 + g_e * 4);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x4 v = slab_epi_apply(p, acc[i][j], bb[j], rr[j], rr2[j]);
-        if (m < m_hi) slab_epi_store(p, m, j * 16 + g_e * 4, v);
+        for (int j = 0; j < 4; ++j) slab_epi_store(p, mw + i * 16, j * 16 + g_e * 4, y[i * 4 + j]);
       }
     }
   }

@@ -284,34 +284,42 @@ __global__ __launch_bounds__(CH >= 128 ? 512 : 256, CH >= 128 ? 1 : CH == 64 ? 2
     int le = lane;
     asm volatile("" : "+v"(le));               // addresses derived from `le` cannot be hoisted above the contraction
     const int g_e = le >> 4;
-    f32x4 bb[CT];
-#pragma unroll
-    for (int j = 0; j < CT; ++j) {
-      bb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (p.bias) bb[j] = *reinterpret_cast<const f32x4*>(p.bias + col0 + j * 16 + g_e * 4);
-    }
+    const int cole = col0 + g_e * 4;
+    // The output transform first: of the four accumulator sets two results remain (float4 (i * 2 + h) * CT + j: row h of pair tile i),
+    // and the registers of the other two take the residuals -- all of a lane's R in one batch, then R2, then the stores
+    // (slab_epi_batch).  Requesting the residuals BEFORE the transform, all four sets live, spilled:
+    // profiles/r05_cw_epilogue_prefetch_experiment.txt.
+    f32x4 y[4 * CT];
+    int mrow[4];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {                        // the pair's first / second row
-        const int m = m0 + toff[i] + h * DIL;
-        const int mc = min(m, m_hi - 1);
-        f32x4 rr[CT], rr2[CT];
-        if (p.R) {
+      for (int j = 0; j < CT; ++j) {
+        y[(i * 2) * CT + j] = (acc[0][i][j] + acc[1][i][j]) + acc[2][i][j];
+        y[(i * 2 + 1) * CT + j] = (acc[1][i][j] - acc[2][i][j]) - acc[3][i][j];
+      }
+      mrow[i * 2] = m0 + toff[i];
+      mrow[i * 2 + 1] = m0 + toff[i] + DIL;
+    }
+    // (the results exist HERE: without this hipcc sinks the transform below the residual loads, all four sets live under them)
 #pragma unroll
-          for (int j = 0; j < CT; ++j) rr[j] = *reinterpret_cast<const f32x4*>(p.R + (size_t)mc * p.ldr + col0 + j * 16 + g_e * 4);
-        }
-        if (p.R2) {
+    for (int n = 0; n < 4 * CT; ++n) asm volatile("" : "+v"(y[n]));
+    f32x4 bb[CT];                                          // requested with the first batch
 #pragma unroll
-          for (int j = 0; j < CT; ++j) rr2[j] = *reinterpret_cast<const f32x4*>(p.R2 + (size_t)mc * p.ldr2 + col0 + j * 16 + g_e * 4);
-        }
+    for (int j = 0; j < CT; ++j) bb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (p.bias) {
 #pragma unroll
-        for (int j = 0; j < CT; ++j) {
-          const f32x4 y = h == 0 ? (acc[0][i][j] + acc[1][i][j]) + acc[2][i][j] : (acc[1][i][j] - acc[2][i][j]) - acc[3][i][j];
-          const f32x4 v = slab_epi_apply(p, y, bb[j], rr[j], rr2[j]);
-          // the pre-activated twin only for a consumer that cannot activate while staging (conv_sk2 after the 128 / 256-channel stages)
-          if (pv[i] && m < m_hi) slab_epi_store<CH >= 128>(p, m, col0 + j * 16 + g_e * 4, v);
-        }
+      for (int j = 0; j < CT; ++j) bb[j] = *reinterpret_cast<const f32x4*>(p.bias + cole + j * 16);
+    }
+    slab_epi_batch(p, y, bb, [&](int q, int n) -> size_t {
+      return (size_t)min(mrow[n / CT], m_hi - 1) * (q == 0 ? p.ldr : p.ldr2) + cole + (n % CT) * 16;
+    });
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (pv[q / 2] && mrow[q] < m_hi) {
+        // the pre-activated twin only for a consumer that cannot activate while staging (conv_sk2 after the 128 / 256-channel stages)
+#pragma unroll
+        for (int j = 0; j < CT; ++j) slab_epi_store<CH >= 128>(p, mrow[q], cole + j * 16, y[q * CT + j]);
       }
     }
     CW_STAMP(2);

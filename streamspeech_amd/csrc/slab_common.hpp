@@ -78,6 +78,52 @@ __device__ __forceinline__ f32x4 slab_epi_apply(const GemmArgs& p, f32x4 v, cons
   return slab_epi_tail(p, v, [&] { return rr2; });
 }
 
+// The same epilogue over ALL the N float4 a lane holds (conv_c64 and the Winograd kernels), one operation at a time with every
+// condition outside the loops: all the residuals R of the lane are requested in one batch before any is used, R2 (one conv in six) in
+// a second batch into the same registers, and the caller stores only afterwards -- one dependent round trip to memory per operand
+// and block, and no wait that covers a store (vmcnt counts stores too).  A lane still reads R / R2 of an element before it writes the
+// element (the vocoder passes R == C and R2 == C).  Every element sees the operations of slab_epi_apply in the same order; alpha and
+// R are ONE fma, which is what hipcc contracts slab_epi_apply's `v *= alpha; v += rr` to in these kernels (written out here so that
+// the bits do not hang on the contraction surviving the restructuring).
+// v[n]: accumulators in, results out; bias of v[n]: bb[n % NBB].  addr(q, n): element offset of float4 n in operand q (0: R, 1: R2).
+template <int N, int NBB, class Addr>
+__device__ __forceinline__ void slab_epi_batch(const GemmArgs& p, f32x4 (&v)[N], const f32x4 (&bb)[NBB], Addr addr) {
+  f32x4 rr[N];
+  if (p.R) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) rr[n] = *reinterpret_cast<const f32x4*>(p.R + addr(0, n));
+  }
+#pragma unroll
+  for (int n = 0; n < N; ++n) v[n] += bb[n % NBB];
+  if (p.act == ACT_LRELU) {
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[n][e] = v[n][e] > 0.f ? v[n][e] : v[n][e] * p.act_slope;
+  }
+  if (p.R) {
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[n][e] = __builtin_fmaf(v[n][e], p.alpha, rr[n][e]);
+  } else {
+#pragma unroll
+    for (int n = 0; n < N; ++n) v[n] *= p.alpha;
+  }
+  if (p.R2) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) rr[n] = *reinterpret_cast<const f32x4*>(p.R2 + addr(1, n));
+#pragma unroll
+    for (int n = 0; n < N; ++n) v[n] = rr[n] + v[n];
+  }
+  if (p.div > 0.f) {
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[n][e] = v[n][e] / p.div;
+  }
+}
+
 // Store of row m, columns n .. n + 3: C, and with TWIN the optional pre-activated twin C2 = leaky_relu(C, c2_slope) for a consumer
 // that cannot activate while staging.
 template <bool TWIN = true, class P>
