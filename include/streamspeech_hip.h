@@ -8,7 +8,9 @@
  * says "synchronises".  All arithmetic is FP32.  Return value: 0 = ok, non-zero = SS_ERR_*:
  * 1 HIP runtime error, 2 invalid argument, 3 weight slot missing or wrong size, 4 output capacity
  * too small, 5 SS_ERR_SCRATCH_CAP (ss_scratch_set_cap), 6 SS_ERR_BITSTREAM and 7 SS_ERR_UNSUPPORTED
- * (ss_mp3_*), 8 SS_ERR_STREAM_REPEAT (ss_encoder_stream_forward).
+ * (ss_mp3_*, ss_flac_*), 8 SS_ERR_STREAM_REPEAT (ss_encoder_stream_forward).
+ * Additions since ABI 2 was cut (no existing signature changed): ss_flac_streaminfo, ss_flac_probe, ss_flac_unpack,
+ * ss_flac_restore_host, ss_flac_restore (FLAC ingest) and ss_batch_cmvn (precomputed fbank rows).
  *
  * Weight ownership: the caller owns one packed FP32 weight blob in HBM (built once from a fairseq
  * state dict by streamspeech_amd/weights.py) and lends it to ss_model_create(); the library keeps
@@ -265,6 +267,83 @@ typedef struct ss_mp3_stream_seg {
 int ss_mp3_stream_synthesize(void* stream, const int16_t* d_q, const ss_mp3_granule* d_rec, int64_t n_rec,
                              const ss_mp3_stream_seg* h_segs, int n_segs, float* const* h_state, float* const* h_dst,
                              const int64_t* h_dst_cap, int n_dst, int mono, void* d_work, size_t* work_bytes);
+
+/* FLAC ingest: the audio format of every fairseq S2T / S2S preparation script (`sf.write(..., ".flac")`,
+ * the members of src_flac.zip).  Two stages, split as the MP3 ingest is: the host stage (csrc/flac_host.hip) reads the container, the
+ * metadata chain, every frame header (CRC-8 checked) and every subframe (Rice / escape residuals; frame CRC-16 checked) and writes one
+ * ss_flac_subframe record per subframe, ordered (frame, channel), plus one int32 per sample into h_res; the device stage
+ * (csrc/flac.hip) undoes the predictor, the wasted-bits shift and the inter-channel decorrelation and writes float32 PCM,
+ * float(s) * 2^-(bps-1): for a 16-bit file frontend.read_wav's bits on the same samples.  ss_flac_restore_host is the device stage's
+ * arithmetic on the host (csrc/flac.hpp holds what both share).
+ * h_res of a subframe (block_size places from res_offset): warm-up samples in the first `order` places, residuals after them; a
+ * constant subframe's value at place 0 (the other places are zero); verbatim samples whole.
+ * Refused with SS_ERR_BITSTREAM (6): a CRC mismatch, lost sync, an order above the block size, a partition order that does not divide the
+ * block or leaves the first partition shorter than the order, a negative qlp shift, reserved codes, a frame that disagrees with
+ * STREAMINFO on rate, channels or depth, a missing or misplaced STREAMINFO.  SS_ERR_UNSUPPORTED (7): more than 24 bits per sample, Ogg
+ * encapsulation.  A truncated last frame is dropped; fewer frames than STREAMINFO declares are accepted and the counted samples win.
+ * The host stage has no global mutable state, makes no HIP call and reads nothing outside [h_data, h_data + n_bytes). */
+typedef struct ss_flac_info {
+  int32_t sample_rate, channels, bits_per_sample;
+  int32_t frames;            /* complete frames */
+  int64_t subframes;         /* records ss_flac_unpack writes: the sum of the frames' channels */
+  int64_t samples;           /* per channel, counted from the frames */
+  int64_t total_samples;     /* STREAMINFO's declared total; 0 = unknown */
+  int32_t min_block, max_block;  /* STREAMINFO */
+  uint8_t md5[16];           /* STREAMINFO: MD5 of the interleaved little-endian PCM; all zero = not set */
+} ss_flac_info;              /* 64 bytes */
+
+enum { SS_FLAC_CONSTANT = 0, SS_FLAC_VERBATIM = 1, SS_FLAC_FIXED = 2, SS_FLAC_LPC = 3 };
+enum { SS_FLAC_INDEPENDENT = 0, SS_FLAC_LEFT_SIDE = 1, SS_FLAC_RIGHT_SIDE = 2, SS_FLAC_MID_SIDE = 3 };
+
+typedef struct ss_flac_subframe {
+  int64_t res_offset;        /* int32 places into h_res / d_res */
+  int64_t sample_start;      /* the frame's first sample in its file (per channel), counted */
+  int32_t block_size;
+  uint8_t type;              /* SS_FLAC_CONSTANT .. SS_FLAC_LPC */
+  uint8_t order;             /* 0-4 fixed, 1-32 lpc, 0 otherwise */
+  uint8_t bps;               /* the subframe's bits per sample: the frame's, + 1 for a side channel (wasted bits not taken off) */
+  uint8_t wasted;
+  uint8_t shift;             /* qlp shift (0 for fixed) */
+  uint8_t assignment;        /* SS_FLAC_INDEPENDENT .. SS_FLAC_MID_SIDE, of the frame */
+  uint8_t precision;         /* bits of a coefficient (lpc: as coded; fixed: 4) */
+  uint8_t channel;
+  int32_t reserved;
+  int16_t coef[32];          /* lpc: as coded; fixed: the binomial taps of the order; zero past `order` */
+} ss_flac_subframe;          /* 96 bytes */
+
+/* One file of a ss_flac_restore batch. */
+typedef struct ss_flac_file {
+  int64_t rec_offset;        /* first record of the file in d_rec */
+  int64_t out_offset;        /* first float of the file in d_out */
+  int32_t frames;            /* frames (channels records each) */
+  int32_t channels;          /* 1-8 */
+  int32_t bps;               /* bits per sample of the file, 4-24 */
+  int32_t n_out;             /* samples written per channel (ss_flac_info.samples) */
+} ss_flac_file;              /* 32 bytes */
+
+/* STREAMINFO only (marker, ID3v2 skip, first metadata block): frames / subframes / samples are left 0.  Host only. */
+int ss_flac_streaminfo(const uint8_t* h_data, size_t n_bytes, ss_flac_info* h_info);
+/* The whole container: metadata chain and every frame, as ss_flac_unpack walks them, without output.  Host only. */
+int ss_flac_probe(const uint8_t* h_data, size_t n_bytes, ss_flac_info* h_info);
+/* h_rec [cap] and h_res [res_cap] (SS_ERR_CAPACITY if the stream has more subframes than cap or more samples x channels than
+ * res_cap).  h_info may be NULL.  Host only. */
+int ss_flac_unpack(const uint8_t* h_data, size_t n_bytes, int64_t cap, int32_t* h_res, ss_flac_subframe* h_rec, int64_t res_cap,
+                   ss_flac_info* h_info);
+/* The device stage's arithmetic on the host.  h_out (may be NULL): as d_out of ss_flac_restore.  h_pcm (may be NULL): the exact
+ * integer PCM, planar [channels][n_out] per file, the files one after another in order (what a caller hashes).  Host only. */
+int ss_flac_restore_host(const int32_t* h_res, const ss_flac_subframe* h_rec, int64_t n_rec, const ss_flac_file* h_files, int n_files,
+                         int mono, float* h_out, int32_t* h_pcm);
+/* A ragged batch of files in ONE launch, stream-ordered, no host round trip: file i writes d_out[out_offset ..): planar
+ * [channels][n_out], or with mono != 0 [n_out], the ascending-channel float32 sum times 1 / channels ((l + r) * 0.5f for stereo).
+ * Integer results are those of exact integer arithmetic: a 32-bit accumulator only where bps - wasted + precision + ceil(log2(order))
+ * <= 32 proves it equal (libFLAC's rule), 64 bits otherwise.  d_work == NULL: *work_bytes = the workspace the call needs, nothing
+ * else happens; otherwise *work_bytes is the size of d_work (SS_ERR_CAPACITY if too small).  h_files is read before the call returns.
+ * Refusals before any HIP call: SS_ERR_ARG for channels outside [1, 8], bps outside [4, 24], negative counts or offsets, records past
+ * n_rec; SS_ERR_CAPACITY for an output range past out_floats.  Records are checked on the device: a record whose block does not fit
+ * its file (sample_start + block_size > n_out), or whose order exceeds 32 or its block, writes nothing. */
+int ss_flac_restore(void* stream, const int32_t* d_res, const ss_flac_subframe* d_rec, int64_t n_rec, int64_t n_res,
+                    const ss_flac_file* h_files, int n_files, int mono, float* d_out, int64_t out_floats,
+                    void* d_work, size_t* work_bytes);
 
 /* Binary PCM in and out of the session pools (streamspeech_amd/pcm.py): a service that takes audio off a socket
  * holds 16-bit PCM, float32 or G.711 bytes, not SimulEval's lists of Python floats.  A pool step copies every chunk it was pushed into
@@ -629,6 +708,10 @@ int ss_vocoder_forward_spkr(ss_vocoder* v, void* stream, const int32_t* d_codes,
  * device buffers are the concatenation of the per-utterance arrays in batch order. */
 int ss_batch_fbank_cmvn(ss_model* m, void* stream, int B, const float* d_pcm, const int64_t* h_pcm_start,
                         const int32_t* h_n_samples, float pcm_scale, float* d_feat, int32_t* h_T);
+/* Precomputed fbank rows (the recipe's src_fbank80.zip): d_out[r][c] = (d_in[r][c] - mean[c]) / std[c] over `rows` packed rows of 80
+ * raw log-mel bins, written exactly as the last line of the fbank kernel, with the model's global-CMVN vectors (a model without
+ * stats behaves as ss_batch_fbank_cmvn does without them).  One launch, stream-ordered; d_out may be d_in.  rows == 0: SS_OK. */
+int ss_batch_cmvn(ss_model* m, void* stream, const float* d_in, int64_t rows, float* d_out);
 int ss_batch_encoder_forward(ss_model* m, void* stream, int B, const float* d_fbank, const int32_t* h_T,
                              int attn_chunk, int conv_chunk, float* d_enc_out, int32_t* h_Tp);
 int ss_batch_ctc_greedy(ss_model* m, void* stream, int head, int B, const float* d_enc_out,

@@ -253,6 +253,8 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
             if os.path.exists(ypath):
                 with open(ypath, "r") as f:
                     config = yaml.load(f, Loader=yaml.BaseLoader) or {}
+                from .frontend import check_eval_transforms
+                check_eval_transforms(config, getattr(args, "gen_subset", None) or "test")
                 if "global_cmvn" in config:
                     npz = config["global_cmvn"]["stats_npz_path"]
                     if not os.path.exists(npz):  # reference YAMLs hold absolute paths of the authors' machine

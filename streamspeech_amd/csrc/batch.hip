@@ -27,6 +27,11 @@ extern "C" int ss_batch_fbank_cmvn(ss_model* m, void* stream, int B, const float
                                  (const int*)m->sc->seg_buf.p, B, mx, s);
 }
 
+extern "C" int ss_batch_cmvn(ss_model* m, void* stream, const float* d_in, int64_t rows, float* d_out) {
+  if (!m || rows < 0 || (rows > 0 && (!d_in || !d_out))) return SS_ERR_ARG;
+  return launch_cmvn_rows(d_in, rows, m->fe_mean, m->fe_std, d_out, (hipStream_t)stream);
+}
+
 extern "C" int ss_batch_encoder_forward(ss_model* m, void* stream, int B, const float* d_fbank, const int32_t* h_T,
                                         int attn_chunk, int conv_chunk, float* d_enc_out, int32_t* h_Tp) {
   if (!m || B <= 0) return SS_ERR_ARG;

@@ -127,6 +127,26 @@ int launch_fbank_cmvn_batch(const float* pcm, float pcm_scale, const float* wind
   return SS_OK;
 }
 
+// Global CMVN alone, for fbank rows that were computed elsewhere (the recipe's precomputed features): the last line of fbank_row,
+// one thread per value over the packed rows.
+__global__ __launch_bounds__(256) void cmvn_rows_kernel(const float* in, const float* __restrict__ cmvn_mean,
+                                                        const float* __restrict__ cmvn_std, float* out, long long n) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int t = (int)(i % NMEL);
+  const float lg = in[i];
+  out[i] = (lg - cmvn_mean[t]) / cmvn_std[t];
+}
+
+int launch_cmvn_rows(const float* in, long long rows, const float* cmvn_mean, const float* cmvn_std, float* out, hipStream_t stream) {
+  if (rows <= 0) return SS_OK;
+  const long long n = rows * NMEL, blocks = (n + 255) / 256;
+  if (blocks > 0x7fffffffLL) return SS_ERR_ARG;
+  hipLaunchKernelGGL(cmvn_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, in, cmvn_mean, cmvn_std, out, n);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
 int launch_fbank_cmvn_ptrs(const float* const* pcm_ptrs, float* const* feat_ptrs, float pcm_scale, const float* window,
                            const float* melw, const float* cmvn_mean, const float* cmvn_std, const int* segs, int nseg,
                            int max_frames, hipStream_t stream) {

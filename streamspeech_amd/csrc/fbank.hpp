@@ -25,6 +25,9 @@ int launch_fbank_cmvn_ptrs(const float* const* pcm_ptrs, float* const* feat_ptrs
                            const float* melw, const float* cmvn_mean, const float* cmvn_std, const int* segs, int nseg,
                            int max_frames, hipStream_t stream);
 
+// out[r][c] = (in[r][c] - cmvn_mean[c]) / cmvn_std[c] over `rows` packed rows of 80: fbank_row's last line on rows computed elsewhere.
+int launch_cmvn_rows(const float* in, long long rows, const float* cmvn_mean, const float* cmvn_std, float* out, hipStream_t stream);
+
 // y[k] = sum_m x[m] * taps[half_len + k*down - m*up] for k < n_out (zero-phase polyphase FIR; `up`/`down`
 // in lowest terms, taps [2*half_len+1] on the device with gain `up`).
 int launch_resample(const float* x, long long n_in, int up, int down, const float* taps, int half_len, float* y,

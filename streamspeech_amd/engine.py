@@ -89,6 +89,14 @@ class BatchMixin:
                                              _i32(n_samples), pcm_scale, _ptr(feat), hT), "ss_batch_fbank_cmvn")
         return feat, list(hT)
 
+    def batch_cmvn(self, feats_packed: torch.Tensor) -> torch.Tensor:
+        """Precomputed raw fbank rows [rows, 80] -> (x - mean) / std with the model's CMVN vectors, fbank_row's last line (one launch)."""
+        if feats_packed.dtype != torch.float32 or feats_packed.dim() != 2 or feats_packed.shape[1] != 80 or not feats_packed.is_contiguous():
+            raise ValueError("batch_cmvn takes a contiguous float32 [rows, 80] tensor")
+        out = torch.empty_like(feats_packed)
+        L.check(self.lib.ss_batch_cmvn(self.h, _stream(), _ptr(feats_packed), feats_packed.shape[0], _ptr(out)), "ss_batch_cmvn")
+        return out
+
     def batch_encoder_forward(self, fbank_packed: torch.Tensor, T: List[int], attn_chunk=999999, conv_chunk=999999):
         B = len(T)
         Tp = [self.lib.ss_encoder_out_len(int(t)) for t in T]

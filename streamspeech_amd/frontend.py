@@ -10,7 +10,9 @@ has already seen: fbank rows whose samples can no longer change are kept, and th
 with the resampler's sum inside the fbank kernel (ss_batch_fbank_frames_sr; OnlineFeatureExtractor.__call__).
 """
 import array
+import io
 import math
+import os
 import wave
 from typing import Optional
 
@@ -50,13 +52,16 @@ def unsettled_fbank_frames(sr_in: int, sr_out: int = 16000, shift_samples: int =
     return max(1, math.ceil(edge / shift_samples))
 
 
-def read_wav(path: str):
+def read_wav(path):
     """PCM WAV (8/16/32-bit integer) -> (float32 mono samples in [-1, 1), sample rate): the `list[float]`
     the SimulEval dataloader hands the agent (SimulEval/simuleval/data/dataloader/s2t_dataloader.py).
+    `path` is a file name or an open binary file object (a slice of a stored zip, read_audio_cell).
     MP3 (example/wavs/*.mp3) is not read here: read_audio / load_audio_batch decode it (streamspeech_amd/mp3.py)."""
-    if str(path).lower().endswith(".mp3"):
-        raise IOError("no MP3 decoder is available here; convert %s to PCM WAV" % path)
-    with wave.open(str(path), "rb") as w:
+    if isinstance(path, (str, os.PathLike)):
+        if str(path).lower().endswith(".mp3"):
+            raise IOError("no MP3 decoder is available here; convert %s to PCM WAV" % path)
+        path = str(path)
+    with wave.open(path, "rb") as w:
         sr, nch, sw, n = w.getframerate(), w.getnchannels(), w.getsampwidth(), w.getnframes()
         raw = w.readframes(n)
     if sw == 2:
@@ -76,30 +81,132 @@ def is_mp3(path) -> bool:
     return str(path).lower().endswith(".mp3")
 
 
+def is_flac(path_or_bytes) -> bool:
+    """A `.flac` path, or bytes that start with the `fLaC` marker."""
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        return bytes(path_or_bytes[:4]) == b"fLaC"
+    return str(path_or_bytes).lower().endswith(".flac")
+
+
+def parse_audio_cell(cell: str):
+    """A manifest's `audio` / `src_audio` cell, as fairseq's parse_path reads it (fairseq/data/audio/audio_utils.py): `<path>` ->
+    (path,), `<zip path>:<byte offset>:<byte length>` -> (path, offset, length).  The member is stored uncompressed, so the slice
+    is the file: no zip structure is parsed."""
+    cell = str(cell)
+    if os.path.splitext(cell)[1].lower() in (".wav", ".flac", ".ogg", ".mp3", ".npy"):
+        return (cell,)
+    path, *slices = cell.split(":")
+    if len(slices) == 0:
+        return (cell,)
+    if len(slices) != 2 or not all(v.isdigit() for v in slices):
+        raise ValueError(f"cannot read the audio cell {cell!r}: expected <path> or <zip>:<offset>:<length>")
+    return (path, int(slices[0]), int(slices[1]))
+
+
+def read_cell_bytes(cell: str) -> bytes:
+    """The bytes a cell names: the whole file, or one seek + read of a stored zip's slice."""
+    parsed = parse_audio_cell(cell)
+    with open(parsed[0], "rb") as f:
+        if len(parsed) == 1:
+            return f.read()
+        f.seek(parsed[1])
+        data = f.read(parsed[2])
+    if len(data) != parsed[2]:
+        raise ValueError(f"the audio cell {cell!r} reaches past the end of {parsed[0]}")
+    return data
+
+
+def sniff(data: bytes, cell: str = "") -> str:
+    """What a file or a zip slice holds, by its first bytes as fairseq's loader tells them apart: "npy" (precomputed features),
+    "flac", "wav", or "mp3" (no magic of its own: whatever ss_mp3_probe accepts).  Anything else raises ValueError naming the cell."""
+    head = bytes(data[:6])
+    if head == b"\x93NUMPY":
+        return "npy"
+    if head[:4] == b"fLaC":
+        return "flac"
+    if head[:4] == b"RIFF":
+        return "wav"
+    from . import mp3
+    try:
+        mp3.probe(data)
+        return "mp3"
+    except mp3.Mp3Error:
+        pass
+    raise ValueError(f"the audio cell {cell!r} holds neither npy features nor FLAC, WAV or MP3 audio")
+
+
+def read_features(data: bytes, cell: str = "") -> np.ndarray:
+    """A `.npy` of raw fbank features -> float32 [T, 80] (fairseq get_features_from_npy_or_audio: np.load, no pickles)."""
+    x = np.load(io.BytesIO(data), allow_pickle=False)
+    if x.ndim != 2 or x.shape[1] != FEATURE_DIM:
+        raise ValueError(f"the features of {cell!r} have shape {tuple(x.shape)}, expected [T, {FEATURE_DIM}]")
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def load_cells(cells, device):
+    """Manifest cells (paths or stored-zip slices) -> [("pcm", float32 mono tensor on `device`, sample rate) | ("feat", float32
+    [T, 80] tensor on `device`, None)], sniffed by content.  The FLAC cells of the call are decoded in one batch and the MP3 cells
+    in another (flac.decode_batch / mp3.decode_batch, up to 640 s of audio per launch); WAV is read by read_wav from memory."""
+    from . import flac, mp3
+    blobs = [read_cell_bytes(c) for c in cells]
+    kinds = [sniff(b, c) for b, c in zip(blobs, cells)]
+    out = [None] * len(cells)
+    for kind, mod in (("flac", flac), ("mp3", mp3)):
+        idx = [k for k, v in enumerate(kinds) if v == kind]
+        if idx:
+            for k, (x, sr) in zip(idx, mod.decode_batch([blobs[k] for k in idx], device, mono=True, names=[str(cells[k]) for k in idx])):
+                out[k] = ("pcm", x, sr)
+    for k, kind in enumerate(kinds):
+        if kind == "wav":
+            x, sr = read_wav(io.BytesIO(blobs[k]))
+            out[k] = ("pcm", torch.from_numpy(x).to(device), sr)
+        elif kind == "npy":
+            out[k] = ("feat", torch.from_numpy(read_features(blobs[k], cells[k])).to(device), None)
+    return out
+
+
+def check_eval_transforms(config: dict, split: str = "test"):
+    """The feature transforms a data config applies at evaluation (fairseq S2TDataConfig.get_transforms: the split's list, else
+    `_eval`, else `*`).  Only global_cmvn is implemented here (the model's CMVN vectors); anything else is refused by name."""
+    for key in ("transforms", "feature_transforms"):
+        tr = config.get(key) or {}
+        if not isinstance(tr, dict):
+            continue
+        cur = tr.get(split)
+        if cur is None:
+            cur = tr.get("_eval")
+        if cur is None:
+            cur = tr.get("*")
+        for name in cur or []:
+            if name != "global_cmvn":
+                raise ValueError(f"the data config lists the evaluation transform {name!r}; only global_cmvn is implemented")
+
+
 def read_audio(path: str):
-    """WAV or MP3 -> (float32 numpy samples, sample rate), mono (channel mean) as read_wav returns them.  WAV goes through
-    read_wav; MP3 through the Layer III decoder (streamspeech_amd/mp3.py: host bitstream stage, device synthesis), whose output
-    is copied back to the host here -- load_audio_batch keeps it on the device."""
-    if not is_mp3(path):
+    """WAV, FLAC or MP3 -> (float32 numpy samples, sample rate), mono (channel mean) as read_wav returns them.  WAV goes through
+    read_wav; FLAC and MP3 through the decoders of streamspeech_amd/flac.py and mp3.py (host bitstream stage, device stage), whose
+    output is copied back to the host here -- load_audio_batch keeps it on the device."""
+    if not is_mp3(path) and not is_flac(path):
         return read_wav(path)
     (x, sr), = load_audio_batch([path], "cuda")
     return x.cpu().numpy(), sr
 
 
 def load_audio_batch(paths, device):
-    """-> [(float32 mono tensor on `device`, sample rate)] for WAV / MP3 paths.  The MP3 files of the call are decoded in
-    batches of up to 640 s of audio (one ss_mp3_synthesize launch pair each, mp3.decode_batch) and stay on the device; WAV files
-    are read by read_wav and uploaded."""
-    from . import mp3
+    """-> [(float32 mono tensor on `device`, sample rate)] for WAV / FLAC / MP3 paths.  The MP3 files of the call are decoded in
+    batches of up to 640 s of audio (one ss_mp3_synthesize launch pair each, mp3.decode_batch), the FLAC files likewise
+    (flac.decode_batch, one ss_flac_restore launch each), and stay on the device; WAV files are read by read_wav and uploaded."""
+    from . import flac, mp3
     out = [None] * len(paths)
-    idx = [k for k, p in enumerate(paths) if is_mp3(p)]
-    if idx:
-        blobs = []
-        for k in idx:
-            with open(paths[k], "rb") as f:
-                blobs.append(f.read())
-        for k, res in zip(idx, mp3.decode_batch(blobs, device, mono=True, names=[str(paths[k]) for k in idx])):
-            out[k] = res
+    for pick, mod in ((is_mp3, mp3), (lambda p: is_flac(str(p)), flac)):
+        idx = [k for k, p in enumerate(paths) if pick(p)]
+        if idx:
+            blobs = []
+            for k in idx:
+                with open(paths[k], "rb") as f:
+                    blobs.append(f.read())
+            for k, res in zip(idx, mod.decode_batch(blobs, device, mono=True, names=[str(paths[k]) for k in idx])):
+                out[k] = res
     for k, p in enumerate(paths):
         if out[k] is None:
             x, sr = read_wav(p)

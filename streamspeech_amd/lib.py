@@ -145,6 +145,11 @@ SIGNATURES = {
     "ss_mp3_stream_copy": (_i, [_vp, _vp]),
     "ss_mp3_stream_synthesize": (_i, [_vp, _vp, _vp, _i64, _vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), _i, _i, _vp,
                                       C.POINTER(C.c_size_t)]),
+    "ss_flac_streaminfo": (_i, [_vp, C.c_size_t, _vp]),
+    "ss_flac_probe": (_i, [_vp, C.c_size_t, _vp]),
+    "ss_flac_unpack": (_i, [_vp, C.c_size_t, _i64, _vp, _vp, _i64, _vp]),
+    "ss_flac_restore_host": (_i, [_vp, _vp, _i64, _vp, _i, _i, _vp, _vp]),
+    "ss_flac_restore": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _i, _i, _vp, _i64, _vp, C.POINTER(C.c_size_t)]),
     "ss_pcm_scatter": (_i, [_vp, _vp, _i64, _vp, _i, C.POINTER(_vp), C.POINTER(_i64), _i]),
     "ss_pcm_pack_s16": (_i, [_vp, _vp, _i64, _vp]),
     "ss_pcm_decode_host": (_i, [_vp, _i, _i, _i64, _vp]),
@@ -200,6 +205,7 @@ SIGNATURES = {
                                         C.POINTER(C.c_int32), _i, _vp, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "ss_batch_fbank_cmvn": (_i, [_vp, _vp, _i, _vp, C.POINTER(_i64), C.POINTER(C.c_int32), _f, _vp, C.POINTER(C.c_int32)]),
+    "ss_batch_cmvn": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "ss_batch_encoder_forward": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _i, _vp, C.POINTER(C.c_int32)]),
     "ss_batch_ctc_greedy": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp]),
     "ss_batch_mt_greedy": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,

@@ -68,9 +68,12 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              subset: str = "test", batch_size: int = 32, max_tokens: int = 0, max_len_a: float = 0.0,
              max_len_b: int = 200, max_len_a_mt: float = 0.0, max_len_b_mt: int = 200, dur_prediction: bool = True, dump_wav: bool = True, t2u_causal: bool = False,
              scores: bool = False, log=None, targets: Optional[Dict[int, Sequence[int]]] = None, beam_mt: int = 1,
-             unk_penalty: float = 0.0, normalize: bool = True, pcm16_out: bool = False, speaker_id: int = -1) -> Dict[int, Dict]:
+             unk_penalty: float = 0.0, normalize: bool = True, pcm16_out: bool = False, speaker_id: int = -1,
+             features: bool = False) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
+    features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
+    src_fbank80.zip features; the model's global CMVN is applied to the packed rows (ss_batch_cmvn) and src_len is T.
     pcm16_out (--pcm16-io): the waveforms of a batch become 16-bit PCM on the device (one ss_pcm_pack_s16, one download per batch)
     and pred_wav/ is written from those bytes -- the same files, without a float download and a host rounding per utterance.
     speaker_id (--speaker-id; multi-speaker vocoders only): the voice of every utterance; -1 draws one per utterance with
@@ -83,20 +86,29 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     log_f = log or open(os.path.join(results_path, f"generate-{subset}.log"), "w", encoding="utf-8")
     res_f = open(os.path.join(results_path, f"generate-{subset}.txt"), "w", encoding="utf-8")
     hyps: Dict[int, Dict] = {}
-    lens = [int(p.numel()) for _, p in items]
-    for sid, pcm in items:                      # shorter than one 25-ms fbank window: nothing to decode
-        if pcm.numel() < 400:
+    if features:
+        for sid, f in items:
+            if f.dim() != 2 or f.shape[1] != 80 or f.dtype != torch.float32:
+                raise ValueError(f"sample {sid}: feature items are float32 [T, 80] tensors, not {f.dtype} {tuple(f.shape)}")
+    lens = [int(p.shape[0]) if features else int(p.numel()) for _, p in items]
+    min_len = 1 if features else 400
+    for k, (sid, pcm) in enumerate(items):      # shorter than one 25-ms fbank window: nothing to decode
+        if lens[k] < min_len:
             for tag in "ASD":
                 print(f"{tag}-{sid}\t", file=log_f)
             print(f"H-{sid}\t0.0\t", file=res_f)
             print(f"D-{sid}\t0.0\t", file=res_f)
             hyps[sid] = {"asr": "", "st": "", "mt": "", "units": [], "wav": None}
-    keep = [i for i in range(len(items)) if lens[i] >= 400]
+    keep = [i for i in range(len(items)) if lens[i] >= min_len]
     for group_k in ordered_batches([lens[i] for i in keep], batch_size, max_tokens):
         group = [keep[j] for j in group_k]
         ids = [items[i][0] for i in group]
-        pcm = torch.cat([items[i][1].reshape(-1) for i in group])
-        feat, T = model.batch_fbank_cmvn(pcm, [lens[i] for i in group])
+        if features:
+            T = [lens[i] for i in group]
+            feat = model.batch_cmvn(torch.cat([items[i][1] for i in group]).contiguous())
+        else:
+            pcm = torch.cat([items[i][1].reshape(-1) for i in group])
+            feat, T = model.batch_fbank_cmvn(pcm, [lens[i] for i in group])
         enc, Tp = model.batch_encoder_forward(feat, T)
         asr = model.batch_ctc_greedy(0, enc, Tp)
         st = model.batch_ctc_greedy(1, enc, Tp)
@@ -223,7 +235,8 @@ def _cut_files(hyps: Dict[int, Dict], results_path: str, subset: str, dump_wav: 
 
 
 def load_manifest(path: str, targets: Optional[Dict[int, List[int]]] = None) -> List[Tuple[int, str]]:
-    """fairseq S2T/S2S manifest (TSV with header, columns `id` and `audio` = src_audio): one WAV per row.
+    """fairseq S2T/S2S manifest (TSV with header, columns `id` and `audio` = src_audio): one cell per row -- a WAV, FLAC, MP3 or .npy
+    path, or `<zip>:<offset>:<length>` into a stored zip of such members (frontend.parse_audio_cell).
     The sample id fairseq prints is the row index.  With `targets` given, the target units of the `tgt_audio` column
     (space-separated ids, SpeechToSpeechDataset: fairseq/data/audio/speech_to_speech_dataset.py) are collected per id."""
     rows = []
@@ -253,7 +266,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--config-yaml", default=None)
     ap.add_argument("--multitask-config-yaml", default=None)
     ap.add_argument("--results-path", required=True)
-    ap.add_argument("--wav-list", default=None, help="text file with one WAV path per line (instead of a manifest)")
+    ap.add_argument("--wav-list", default=None, help="text file with one WAV / FLAC / MP3 path per line (instead of a manifest)")
     ap.add_argument("--synthetic", type=int, default=0, help="N synthetic utterances instead of files")
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--max-tokens", type=int, default=0)
@@ -296,7 +309,8 @@ def main(argv: Optional[List[str]] = None):
     # model / dictionaries / CMVN exactly as the agent loads them (agent :355-420)
     ns = argparse.Namespace(config_yaml=a.config_yaml, multitask_config_yaml=a.multitask_config_yaml,
                             data_bin=a.data or ".", model_path=a.path, global_stats=None, source_segment_size=999999 * 40,
-                            shift_size=10, window_size=25, sample_rate=16000, feature_dim=80, full_recompute_encoder=True)
+                            shift_size=10, window_size=25, sample_rate=16000, feature_dim=80, full_recompute_encoder=True,
+                            gen_subset=a.gen_subset)
     holder = argparse.Namespace(device=a.device)
     StreamSpeechS2STAgent.load_model_vocab(holder, ns)
     model = holder.model.hip
@@ -321,10 +335,24 @@ def main(argv: Optional[List[str]] = None):
         else:
             rows = load_manifest(os.path.join(a.data, a.gen_subset + ".tsv"), targets)
         rows = rows[a.shard_id::a.num_shards]
-        # MP3 rows: batched decodes of up to 640 s of audio each, straight to the device (streamspeech_amd/mp3.py); WAV rows as before
-        mp3_rows = [k for k, (_, path) in enumerate(rows) if frontend.is_mp3(path)]
+        # MP3 and FLAC rows: batched decodes of up to 640 s of audio each, straight to the device (streamspeech_amd/mp3.py, flac.py);
+        # stored-zip cells and .npy paths are read and sniffed (frontend.load_cells); WAV rows as before
+        mp3_rows = [k for k, (_, path) in enumerate(rows) if frontend.is_mp3(path) or frontend.is_flac(path)]
         decoded = dict(zip(mp3_rows, frontend.load_audio_batch([rows[k][1] for k in mp3_rows], a.device))) if mp3_rows else {}
-        if a.pcm16_io:                              # 16-bit WAV rows: raw frames, one upload, one decode launch; others as before
+        cell_rows = [k for k, (_, path) in enumerate(rows)
+                     if k not in decoded and (len(frontend.parse_audio_cell(path)) == 3 or path.lower().endswith(".npy"))]
+        feats = {}
+        if cell_rows:
+            for k, (kind, x, sr) in zip(cell_rows, frontend.load_cells([rows[k][1] for k in cell_rows], a.device)):
+                if kind == "feat":
+                    feats[k] = x
+                else:
+                    decoded[k] = (x, sr)
+        if feats and len(feats) != len(rows):
+            k = next(k for k in range(len(rows)) if k not in feats)
+            raise ValueError(f"the manifest mixes precomputed feature rows and audio rows (row {rows[k][0]}: {rows[k][1]!r} is audio); "
+                             "a manifest holds one kind")
+        if a.pcm16_io and not feats:                # 16-bit WAV rows: raw frames, one upload, one decode launch; others as before
             raw_rows, raws = [], []
             for k, (_, path) in enumerate(rows):
                 if k not in decoded:
@@ -336,6 +364,9 @@ def main(argv: Optional[List[str]] = None):
                 decoded.update(zip(raw_rows, stage_wavs_pcm16(model, raws, a.device)))
         entries = []
         for k, (i, path) in enumerate(rows):
+            if feats:
+                entries.append((i, feats[k]))
+                continue
             if k in decoded:
                 x, sr = decoded[k]
             else:
@@ -344,8 +375,12 @@ def main(argv: Optional[List[str]] = None):
             entries.append((i, x, sr))
     if a.synthetic > 0:
         entries = entries[a.shard_id::a.num_shards]
+    is_feat = a.synthetic <= 0 and bool(feats)
     items = []
     for e in entries:
+        if is_feat:
+            items.append((e[0], e[1].to(a.device)))
+            continue
         pcm = e[1].to(a.device)
         if len(e) > 2 and e[2] != 16000:
             pcm = model.resample(pcm, e[2], 16000)
@@ -355,7 +390,8 @@ def main(argv: Optional[List[str]] = None):
                     a.max_len_b, a.max_len_a_mt, a.max_len_b_mt, a.dur_prediction, not a.no_wav,
                     getattr(holder.model, "uni_encoder", False), a.scores, targets=targets or None, beam_mt=a.beam_mt,
                     unk_penalty=a.unkpen, normalize=not a.unnormalized,
-                    **({"pcm16_out": True} if a.pcm16_io else {}), **({"speaker_id": a.speaker_id} if voc.num_speakers else {}))
+                    **({"pcm16_out": True} if a.pcm16_io else {}), **({"speaker_id": a.speaker_id} if voc.num_speakers else {}),
+                    **({"features": True} if is_feat else {}))
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
 
 
