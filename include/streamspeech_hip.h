@@ -984,6 +984,14 @@ typedef struct ss_op_conv_args {
   int32_t same_rows;
 } ss_op_conv_args;
 int ss_op_conv_gemm_ex(void* stream, const ss_op_conv_args* a);
+/* ss_op_conv_gemm_ex plus the GemmArgs fields only the streaming encoder sets.  m_begin: the launch computes output rows [m_begin, M) of
+ * a single utterance, pointers / in_len / chunk rule those of row 0 (ss_encoder_stream_forward; the LDS-tile kernel with N > 32, no
+ * segments; cleared by the pack-invariant routes, which write every row).  seg_mb (device, nseg x {first row, chunk}) / seg_A (device,
+ * nseg input pointers; in_start is relative to them): the ragged subsampler of the session pool -- segment z writes rows
+ * [out_start + seg_mb[2 z], out_start + out_len) and nothing below, max_seg_out = the longest out_len - first row; legal only with
+ * canon = 1 (CANON_SEQ) and nseg > 0.  canon: the arithmetic mode of this launch (0: the calling thread's, ss_debug_canon).  Returns
+ * what launch_conv_gemm returns, SS_ERR_ARG included.  tests/test_stream_ops_gpu.py. */
+int ss_op_conv_gemm_rows(void* stream, const ss_op_conv_args* a, int m_begin, const int32_t* seg_mb, const float* const* seg_A, int canon);
 /* The fused ResBlock half of the narrow vocoder stages (csrc/conv_slab.hip, launch_conv_pair with the caller's arguments unchanged):
  * dC = conv2(lrelu(conv1_dil(lrelu(dA)) + db1)) + db2 + dA [+ dR2] [/ div], dC2 = leaky_relu(dC, c2_slope) when set; C = 16 / 32,
  * odd taps, M >= 2048 packed rows; d_segs as above ({start, len, ., .}).  SS_ERR_ARG for what the kernel does not take. */
@@ -1050,6 +1058,30 @@ int ss_debug_attention_no_mfma(int v);
 int ss_op_dwconv_bn_silu(void* stream, const float* dx, int ldx, float* dy, int ldy, const float* dwt,
                          int K, const float* mean, const float* var, const float* gamma,
                          const float* beta, float eps, int T, int C, int chunk);
+/* ... with the launcher's other forms: the ragged pack (segs: device, nseg x {row_start, len}; T = the longest len, every utterance
+ * convolved alone) and a row range (rows [t_begin, T) are written, rows below are read as input only). */
+int ss_op_dwconv_bn_silu_ex(void* stream, const float* dx, int ldx, float* dy, int ldy, const float* dwt, int K, const float* mean,
+                            const float* var, const float* gamma, const float* beta, float eps, int T, int C, int chunk,
+                            const int32_t* segs, int nseg, int t_begin);
+/* The session pool's own kernels (csrc/stream_pool.hip), each launcher with the arguments the pool step passes; all DEVICE pointers.
+ * pool_dwconv: depthwise conv + BatchNorm + SiLU of the tail rows of nsess sessions, sess = nsess x {q_start, n, r0, T, slot, -, chunk,
+ * -}: input row t of a session is row t of its slot (cache + slot * slot_rows * C) below r0, stacked row q_start + t - r0 of gs from r0
+ * on; y rows q_start .. q_start + n are written, and stacked rows are copied to slot rows [r0, r0 + n).  max_n = the largest n.
+ * K odd, <= 31.
+ * pool_gather_rows (W = 256 floats per row) / pool_gather_ids (one int32 per row): tab = nsess x {-, len, k0, nf, slot, s_start}, pre =
+ * nsess + 1 ascending row offsets of the packed output; row j of a session comes from its slot's row j below k0 and from stacked row
+ * s_start + j - k0 otherwise; rows k0 <= j < nf are also written to the slot.
+ * pool_stack_rows: out row r of segment z (rows pre[z] .. pre[z + 1]) = enc row src[z] + r - pre[z]; W % 4 == 0, W <= 1024.
+ * SS_ERR_ARG for what a kernel cannot take (nsess <= 0 included). */
+int ss_op_pool_dwconv(void* stream, const float* gs, float* cache, int slot_rows, float* y, const float* wt, int K, const float* bn_mean,
+                      const float* bn_var, const float* bn_gamma, const float* bn_beta, float bn_eps, int C, const int32_t* sess,
+                      int nsess, int max_n);
+int ss_op_pool_gather_rows(void* stream, float* out, const float* stk, float* cache, int slot_rows, int W, const int32_t* tab,
+                           const int32_t* pre, int nsess, int total);
+int ss_op_pool_gather_ids(void* stream, int32_t* out, const int32_t* stk, int32_t* cache, int slot_rows, const int32_t* tab,
+                          const int32_t* pre, int nsess, int total);
+int ss_op_pool_stack_rows(void* stream, float* out, const float* enc, int W, const int32_t* src, const int32_t* pre, int nsess,
+                          int total);
 
 /* ---- the decode glue kernels (csrc/elementwise.hip), each launcher with the caller's arguments unchanged; every pointer is a DEVICE
  * pointer, NULL where the launcher's argument is optional (segs with nseg = 0: the single-utterance form).  Semantics: the comments

@@ -37,9 +37,7 @@ extern "C" int ss_op_conv_gemm(void* stream, const float* dA, int lda, const flo
 
 // every field of GemmArgs a caller of the conv launcher can set, as the caller set it (ragged packs, the pre-activated twin, the
 // epilogue slope, same_rows): what launch_conv_gemm answers is what the caller sees.  The Winograd weight pack is made per call, as above.
-extern "C" int ss_op_conv_gemm_ex(void* stream, const ss_op_conv_args* x) {
-  if (!x) return SS_ERR_ARG;
-  GemmArgs a;
+static void op_fill_conv(GemmArgs& a, const ss_op_conv_args* x) {
   a.A = x->A; a.W = x->W; a.bias = x->bias; a.R = x->R; a.R2 = x->R2; a.C = x->C; a.C2 = x->C2;
   a.lda = x->lda; a.ldc = x->ldc; a.ldr = x->ldr; a.ldr2 = x->ldr2; a.ldc2 = x->ldc2;
   a.M = x->M; a.N = x->N; a.Cin = x->Cin; a.taps = x->taps; a.dil = x->dil; a.stride = x->stride; a.pad = x->pad;
@@ -47,6 +45,23 @@ extern "C" int ss_op_conv_gemm_ex(void* stream, const ss_op_conv_args* x) {
   a.in_act = x->in_act; a.in_slope = x->in_slope; a.act = x->act; a.act_slope = x->act_slope; a.alpha = x->alpha; a.div = x->div;
   a.c2_slope = x->c2_slope; a.glu = x->glu;
   a.segs = x->segs; a.nseg = x->nseg; a.max_seg_out = x->max_seg_out; a.same_rows = x->same_rows;
+}
+extern "C" int ss_op_conv_gemm_ex(void* stream, const ss_op_conv_args* x) {
+  if (!x) return SS_ERR_ARG;
+  GemmArgs a;
+  op_fill_conv(a, x);
+  if (a.W && a.N > 0 && a.taps > 0) RET(op_bind_wino(a, stream));
+  return launch_conv_gemm(a, (hipStream_t)stream);
+}
+// ... plus the four fields only the streaming encoder sets: the first row of a single utterance's launch (m_begin), the per-segment
+// {first row, chunk} and input pointers of the session pool's ragged subsampler (seg_mb [2 nseg] / seg_A [nseg], device arrays), and
+// the arithmetic mode of THIS launch (canon: 0 the calling thread's, 1 CANON_SEQ, 2 CANON_SMALLM)
+extern "C" int ss_op_conv_gemm_rows(void* stream, const ss_op_conv_args* x, int m_begin, const int32_t* seg_mb,
+                                    const float* const* seg_A, int canon) {
+  if (!x || canon < 0 || canon > 2) return SS_ERR_ARG;
+  GemmArgs a;
+  op_fill_conv(a, x);
+  a.m_begin = m_begin; a.seg_mb = seg_mb; a.seg_A = seg_A; a.canon = canon;
   if (a.W && a.N > 0 && a.taps > 0) RET(op_bind_wino(a, stream));
   return launch_conv_gemm(a, (hipStream_t)stream);
 }
@@ -286,6 +301,14 @@ extern "C" int ss_op_dwconv_bn_silu(void* stream, const float* dx, int ldx, floa
                                     int K, const float* mean, const float* var, const float* gamma,
                                     const float* beta, float eps, int T, int C, int chunk) {
   return launch_dwconv_bn_silu(dx, ldx, dy, ldy, dwt, K, mean, var, gamma, beta, eps, T, C, chunk, (hipStream_t)stream);
+}
+
+// ... with the ragged pack (segs: nseg x {row_start, len}, T = the longest len) and the first row of a row range (t_begin)
+extern "C" int ss_op_dwconv_bn_silu_ex(void* stream, const float* dx, int ldx, float* dy, int ldy, const float* dwt, int K,
+                                       const float* mean, const float* var, const float* gamma, const float* beta, float eps, int T,
+                                       int C, int chunk, const int32_t* segs, int nseg, int t_begin) {
+  return launch_dwconv_bn_silu(dx, ldx, dy, ldy, dwt, K, mean, var, gamma, beta, eps, T, C, chunk, (hipStream_t)stream, segs, nseg,
+                               t_begin);
 }
 
 extern "C" int ss_prof_enable(int cls_mask) { prof_enable(cls_mask); return SS_OK; }

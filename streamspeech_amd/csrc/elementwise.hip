@@ -132,7 +132,7 @@ int launch_dwconv_bn_silu(const float* x, int ldx, float* y, int ldy, const floa
                           const float* bn_beta, float bn_eps, int T, int C, int chunk, hipStream_t stream,
                           const int* segs, int nseg, int t_begin) {
   if (T - t_begin <= 0) return SS_OK;
-  if (K > DW_KMAX || (K & 1) == 0) return SS_ERR_ARG;
+  if (K > DW_KMAX || (K & 1) == 0 || t_begin < 0) return SS_ERR_ARG;     // (a negative first row would be written below the buffer)
   dim3 grid(cdiv(C, DW_TC), cdiv(T - t_begin, DW_TT), nseg > 0 ? nseg : 1);
   hipLaunchKernelGGL(dwconv_bn_silu_kernel, grid, dim3(256), 0, stream, x, ldx, y, ldy, wt, K, bn_mean,
                      bn_var, bn_gamma, bn_beta, bn_eps, T, C, chunk, nseg > 0 ? segs : nullptr, t_begin);

@@ -145,6 +145,47 @@ __global__ __launch_bounds__(256) void pool_stack_rows_kernel(float* out, const 
 
 }  // namespace
 
+// ---- launchers (the pool step below and the ss_op_pool_* entry points at the foot share them) ----------------------------------
+// max_n: the most tail rows of any session of the call (grid sizing); sess: nsess x 8 ints as pool_dwconv_kernel reads them
+static int launch_pool_dwconv(const float* gs, float* cache, int slot_rows, float* y, const float* wt, int K, const float* bn_mean,
+                              const float* bn_var, const float* bn_gamma, const float* bn_beta, float bn_eps, int C, const int* sess,
+                              int nsess, int max_n, hipStream_t s) {
+  if (K > PDW_KMAX || (K & 1) == 0 || nsess <= 0 || C <= 0 || slot_rows <= 0) return SS_ERR_ARG;
+  if (max_n <= 0) return SS_OK;
+  hipLaunchKernelGGL(pool_dwconv_kernel, dim3(cdiv(C, PDW_TC), cdiv(max_n, PDW_TT), nsess), dim3(256), 0, s, gs, cache, slot_rows, y, wt,
+                     K, bn_mean, bn_var, bn_gamma, bn_beta, bn_eps, C, sess);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+// float rows of W = 256 (the only width the kernel is instantiated for) / one int32 per row
+static int launch_pool_gather_rows(float* out, const float* stk, float* cache, int slot_rows, int W, const int* tab, const int* pre,
+                                   int nsess, int total, hipStream_t s) {
+  if (W != 256 || nsess <= 0 || slot_rows <= 0) return SS_ERR_ARG;
+  if (total <= 0) return SS_OK;
+  hipLaunchKernelGGL((pool_gather_kernel<float, 256>), dim3(cdiv(total, 4)), dim3(256), 0, s, out, stk, cache, slot_rows, tab, pre, nsess,
+                     total);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+static int launch_pool_gather_ids(int32_t* out, const int32_t* stk, int32_t* cache, int slot_rows, const int* tab, const int* pre,
+                                  int nsess, int total, hipStream_t s) {
+  if (nsess <= 0 || slot_rows <= 0) return SS_ERR_ARG;
+  if (total <= 0) return SS_OK;
+  hipLaunchKernelGGL((pool_gather_kernel<int32_t, 1>), dim3(cdiv(total, 256)), dim3(256), 0, s, out, stk, cache, slot_rows, tab, pre,
+                     nsess, total);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+// W floats per row: whole float4s, at most one 256-thread workgroup per row
+static int launch_pool_stack_rows(float* out, const float* enc, int W, const int* src, const int* pre, int nsess, int total,
+                                  hipStream_t s) {
+  if (W <= 0 || (W & 3) != 0 || W > 1024 || nsess <= 0) return SS_ERR_ARG;
+  if (total <= 0) return SS_OK;
+  hipLaunchKernelGGL(pool_stack_rows_kernel, dim3(cdiv(total, 256 / (W / 4))), dim3(256), 0, s, out, enc, W, src, pre, nsess, total);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
 // ---- the pool ----------------------------------------------------------------------------------------------------------------
 struct PoolSlot {
   int fin = 0, achunk = -1, cchunk = -1, tail = 0;   // as ss_scratch::es_final / es_achunk / es_cchunk / es_tail
@@ -279,7 +320,9 @@ extern "C" int ss_encoder_stream_forward_batch(ss_model* m, void* stream, ss_str
                                                int32_t* h_n_computed) {
   if (!m || !p || !d_enc_packed || p->sc != m->sc) return SS_ERR_ARG;
   const ss_config& c = m->cfg;
-  if (c.enc_layers != p->L || c.enc_dim != p->d || c.enc_heads * 64 != c.enc_dim || c.dw_kernel > PDW_KMAX) return SS_ERR_ARG;
+  if (c.enc_layers != p->L || c.enc_dim != p->d || c.enc_heads * 64 != c.enc_dim || c.dw_kernel > PDW_KMAX ||
+      (c.dw_kernel & 1) == 0 || c.enc_dim != 256)      // (what launch_pool_dwconv / launch_pool_gather_rows refuse: before anything is queued)
+    return SS_ERR_ARG;
   PoolPlan pl;
   RET(pool_plan(p, c, n, h_slots, h_fbank, h_T, h_attn_chunk, h_conv_chunk, pl));
   SkScope sk_scope(m->sc->skws);
@@ -361,9 +404,8 @@ extern "C" int ss_encoder_stream_forward_batch(ss_model* m, void* stream, ss_str
         return SS_OK;
       };
       auto dwconv = [&]() -> int {
-        hipLaunchKernelGGL(pool_dwconv_kernel, dim3(cdiv(d, PDW_TC), cdiv(mx2, PDW_TT), Na), dim3(256), 0, s, glu,
-                           p->glu.f() + (size_t)l * lay_g, p->R, g2, e.dw_wt, c.dw_kernel, e.bn_mean, e.bn_var, e.bn_g, e.bn_b, 1e-5f, d, dss);
-        SS_LAUNCH_CHECK();
+        RET(launch_pool_dwconv(glu, p->glu.f() + (size_t)l * lay_g, p->R, g2, e.dw_wt, c.dw_kernel, e.bn_mean, e.bn_var, e.bn_g, e.bn_b,
+                               1e-5f, d, dss, Na, mx2, s));
         ++nl;
         return SS_OK;
       };
@@ -372,9 +414,7 @@ extern "C" int ss_encoder_stream_forward_batch(ss_model* m, void* stream, ss_str
     }
   }
   if (pl.total > 0) {
-    hipLaunchKernelGGL((pool_gather_kernel<float, 256>), dim3(cdiv(pl.total, 4)), dim3(256), 0, s, d_enc_packed, x, p->out.f(), p->R,
-                       dgt, dgp, n, pl.total);
-    SS_LAUNCH_CHECK();
+    RET(launch_pool_gather_rows(d_enc_packed, x, p->out.f(), p->R, d, dgt, dgp, n, pl.total, s));
     ++nl;
   }
   p->launches += nl + (gemm_census() - g0);
@@ -432,15 +472,13 @@ extern "C" int ss_stream_pool_ctc(ss_model* m, void* stream, ss_stream_pool* p, 
   long long nl = 0;
   const long long g0 = gemm_census();
   if (Mc > 0) {              // the rows whose arg-max the slots do not hold yet: stacked, through the head, arg-max
-    hipLaunchKernelGGL(pool_stack_rows_kernel, dim3(cdiv(Mc, 256 / (d / 4))), dim3(256), 0, s, stk, d_enc_packed, d, dsrc, dsp, n, Mc);
-    SS_LAUNCH_CHECK();
+    RET(launch_pool_stack_rows(stk, d_enc_packed, d, dsrc, dsp, n, Mc, s));
     RET(linear(s, stk, d, Mc, head == 0 ? m->ctc_asr : m->ctc_st, V, d, m->sc->mt_ws.f(), V));
     RET(launch_masked_argmax(m->sc->mt_ws.f(), V, Mc, V, c.pad, c.unk, -1, -1, raw_stk, s));
     nl += 2;                 // (the head GEMM: counted by the census)
   }
-  hipLaunchKernelGGL((pool_gather_kernel<int32_t, 1>), dim3(cdiv(total, 256)), dim3(256), 0, s, d_raw, raw_stk,
-                     reinterpret_cast<int32_t*>(p->raw.p) + (size_t)head * p->S * p->R, p->R, dgt, dgp, n, total);
-  SS_LAUNCH_CHECK();
+  RET(launch_pool_gather_ids(d_raw, raw_stk, reinterpret_cast<int32_t*>(p->raw.p) + (size_t)head * p->S * p->R, p->R, dgt, dgp, n, total,
+                             s));
   RET(launch_ctc_collapse(d_raw, 0, 0, c.pad, d_tokens, d_index, d_counts, s, dcs, n));
   nl += 2;
   p->launches += nl + (gemm_census() - g0);
@@ -448,4 +486,25 @@ extern "C" int ss_stream_pool_ctc(ss_model* m, void* stream, ss_stream_pool* p, 
   p->head_rows += Mc;
   for (int i = 0; i < n; ++i) { PoolSlot& st = p->slot[h_slots[i]]; st.cfin[head] = st.nf; }
   return SS_OK;
+}
+
+// ---- op-level entry points of the pool's own kernels (tests/test_stream_ops_gpu.py): each launcher with the kernel's arguments as the
+// pool step passes them; every pointer a DEVICE pointer ----
+extern "C" int ss_op_pool_dwconv(void* stream, const float* gs, float* cache, int slot_rows, float* y, const float* wt, int K,
+                                 const float* bn_mean, const float* bn_var, const float* bn_gamma, const float* bn_beta, float bn_eps,
+                                 int C, const int32_t* sess, int nsess, int max_n) {
+  return launch_pool_dwconv(gs, cache, slot_rows, y, wt, K, bn_mean, bn_var, bn_gamma, bn_beta, bn_eps, C, sess, nsess, max_n,
+                            (hipStream_t)stream);
+}
+extern "C" int ss_op_pool_gather_rows(void* stream, float* out, const float* stk, float* cache, int slot_rows, int W, const int32_t* tab,
+                                      const int32_t* pre, int nsess, int total) {
+  return launch_pool_gather_rows(out, stk, cache, slot_rows, W, tab, pre, nsess, total, (hipStream_t)stream);
+}
+extern "C" int ss_op_pool_gather_ids(void* stream, int32_t* out, const int32_t* stk, int32_t* cache, int slot_rows, const int32_t* tab,
+                                     const int32_t* pre, int nsess, int total) {
+  return launch_pool_gather_ids(out, stk, cache, slot_rows, tab, pre, nsess, total, (hipStream_t)stream);
+}
+extern "C" int ss_op_pool_stack_rows(void* stream, float* out, const float* enc, int W, const int32_t* src, const int32_t* pre, int nsess,
+                                     int total) {
+  return launch_pool_stack_rows(out, enc, W, src, pre, nsess, total, (hipStream_t)stream);
 }

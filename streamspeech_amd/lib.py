@@ -266,6 +266,7 @@ SIGNATURES = {
     "ss_op_conv_gemm": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
                              _i, _f, _i, _f, _f, _i]),
     "ss_op_conv_gemm_ex": (_i, [_vp, C.POINTER(SSOpConvArgs)]),
+    "ss_op_conv_gemm_rows": (_i, [_vp, C.POINTER(SSOpConvArgs), _i, _vp, _vp, _i]),
     "ss_op_conv_pair": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _vp, _i, _f, _i, _i, _i, _i, _i, _f, _vp, _i]),
     "ss_op_resblock_fused": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _i, _i, _f, _vp, _i]),
     "ss_debug_slab": (_i, [_i, C.c_longlong]),
@@ -276,6 +277,11 @@ SIGNATURES = {
     "ss_op_attention_pool": (_i, [_vp, C.POINTER(SSOpPoolAttnArgs)]),
     "ss_debug_attention_no_mfma": (_i, [_i]),
     "ss_op_dwconv_bn_silu": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _i]),
+    "ss_op_dwconv_bn_silu_ex": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _i, _i]),
+    "ss_op_pool_dwconv": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _i, _vp, _i, _i]),
+    "ss_op_pool_gather_rows": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i]),
+    "ss_op_pool_gather_ids": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i]),
+    "ss_op_pool_stack_rows": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i]),
     "ss_op_masked_argmax": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i]),
     "ss_op_ctc_collapse": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
     "ss_op_dur_predict": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
