@@ -587,6 +587,20 @@ int ss_encoder_stream_forward_batch(ss_model* m, void* stream, ss_stream_pool* p
  * change, so their arg-max is kept in the slot: the head GEMM and arg-max run only over rows the slot does not hold yet. */
 int ss_stream_pool_ctc(ss_model* m, void* stream, ss_stream_pool* p, int head, int n, const int32_t* h_slots,
                        const float* d_enc_packed, int32_t* d_raw, int32_t* d_tokens, int32_t* d_index, int32_t* d_counts);
+/* Scores of the pool's CTC calls (off at creation).  on = 1 books a float cache [2 heads][max_sessions][max_rows] beside the arg-max
+ * cache on the pool's scratch set (ss_scratch_bytes reports it, ss_scratch_trim keeps it): the log-probability of each final row's
+ * arg-max, the per-frame `lprobs.max(dim=2)` of agent/ctc_decoder.py:52-61.  Past ss_scratch_set_cap it returns SS_ERR_SCRATCH_CAP and
+ * leaves the set as it was; on = 0 gives the bytes back.  Allowed only while no slot holds rows (before the first forward, or with
+ * every used slot reset), else SS_ERR_ARG: a slot's cached arg-max and its log-probability are filled together. */
+int ss_stream_pool_set_scores(ss_stream_pool* p, int on);
+/* ss_stream_pool_ctc with the scores of agent/ctc_decoder.py:52-62,104-105 (`positional_scores`): outputs as
+ * ss_batch_ctc_greedy_scored -- d_lprob [sum T2_i] per frame, d_last / d_tok_lprob [sum T2_i] per collapsed token at each session's
+ * packed offset.  As with the arg-max, rows below a slot's n_final take their log-probability from the slot (the bits they had when
+ * they became final); only the rows the slot does not hold yet go through the head.  One launch more than ss_stream_pool_ctc,
+ * whatever n.  SS_ERR_ARG unless ss_stream_pool_set_scores(p, 1). */
+int ss_stream_pool_ctc_scored(ss_model* m, void* stream, ss_stream_pool* p, int head, int n, const int32_t* h_slots,
+                              const float* d_enc_packed, int32_t* d_raw, int32_t* d_tokens, int32_t* d_index, int32_t* d_counts,
+                              float* d_lprob, int32_t* d_last, float* d_tok_lprob);
 /* Test hook: the pool's counters since its creation -- kernels its calls launched (its own kernels, plus the GEMM-family launches the
  * library's launch census saw during the call: meaningful while no other thread launches), rows its CTC calls ran through a head. */
 int ss_stream_pool_stats(ss_stream_pool* p, int64_t* launches, int64_t* head_rows);
@@ -597,6 +611,16 @@ int ss_stream_pool_stats(ss_stream_pool* p, int64_t* launches, int64_t* head_row
 int ss_ctc_greedy(ss_model* m, void* stream, int head, const float* d_enc_out, int Tp,
                   int32_t* d_raw, int32_t* d_tokens, int32_t* d_index, int32_t* d_count,
                   float* d_logits);
+
+/* The same search with the scores the reference's CTCDecoder.generate returns in every hypothesis (agent/ctc_decoder.py:52-62:
+ * lprobs = log_softmax(logits), pad and unk set to -inf, `positional_scores = lprobs.max(dim=2)`; :104-105 `score` is their sum, taken
+ * by the caller).  d_raw / d_tokens / d_index / d_count / d_logits exactly as ss_ctc_greedy.  d_lprob [Tp] float: the log-probability
+ * of each frame's arg-max, NaN for a row that holds a NaN (as torch.log_softmax).  Per collapsed token j: d_last[j] (int32) the last
+ * frame of the run of equal raw ids that starts at d_index[j], d_tok_lprob[j] (float) the sum of d_lprob over that run in ascending
+ * frame order.  Same number of launches as ss_ctc_greedy. */
+int ss_ctc_greedy_scored(ss_model* m, void* stream, int head, const float* d_enc_out, int Tp,
+                         int32_t* d_raw, int32_t* d_tokens, int32_t* d_index, int32_t* d_count,
+                         float* d_logits, float* d_lprob, int32_t* d_last, float* d_tok_lprob);
 
 /* Decode-step form of this context (the n = 1 calls of ss_mt_append / the loop inside ss_mt_greedy; reference: one
  * EnsembleModel.forward_decoder call of agent/sequence_generator.py:592-673 per generated token).  workgroups = 0 (default, or
@@ -717,6 +741,11 @@ int ss_batch_encoder_forward(ss_model* m, void* stream, int B, const float* d_fb
 int ss_batch_ctc_greedy(ss_model* m, void* stream, int head, int B, const float* d_enc_out,
                         const int32_t* h_Tp, int32_t* d_raw, int32_t* d_tokens, int32_t* d_index,
                         int32_t* d_counts);
+/* ss_batch_ctc_greedy with the scores of ss_ctc_greedy_scored (agent/ctc_decoder.py:52-62), under the same pack-invariance setting:
+ * d_lprob [sum Tp] per frame, d_last / d_tok_lprob [sum Tp] per collapsed token, packed like d_raw and d_tokens. */
+int ss_batch_ctc_greedy_scored(ss_model* m, void* stream, int head, int B, const float* d_enc_out,
+                               const int32_t* h_Tp, int32_t* d_raw, int32_t* d_tokens, int32_t* d_index,
+                               int32_t* d_counts, float* d_lprob, int32_t* d_last, float* d_tok_lprob);
 /* Lockstep beam-1 search from [</s>] (offline: no prefix).  h_max_len[b] = forced-</s> step of
  * utterance b.  h_out_tokens [B][out_stride] receives the generated tokens (incl. the final </s>),
  * h_n_out[b] their number (= rows of valid decoder states); d_feats is [B][feat_rows][dec_dim].
@@ -1090,6 +1119,13 @@ int ss_op_masked_argmax(void* stream, const float* logits, int ld, int M, int N,
                         int32_t* ids, const int32_t* row_max_len, int step, int force_id, const int32_t* row_min_len, int ban_id);
 int ss_op_ctc_collapse(void* stream, const int32_t* raw, int T, int blank, int pad, int32_t* tokens, int32_t* index, int32_t* count,
                        const int32_t* segs, int nseg);                /* segs {start, len}: count[s] */
+/* The scored twins of the two above (csrc/ctc_scores.hip; agent/ctc_decoder.py:52-62): ids as ss_op_masked_argmax without force / row
+ * lengths, lprob[row] = max over unmasked columns of log_softmax(row); tokens / index / count as ss_op_ctc_collapse, last[j] the last
+ * frame of token j's run, tok_lprob[j] the float32 sum of lprob over it.  tests/test_ctc_scores_gpu.py against tests/ctc_ref.py. */
+int ss_op_masked_argmax_lprob(void* stream, const float* logits, int ld, int M, int N, int mask0, int mask1, int mask2, int32_t* ids,
+                              float* lprob);
+int ss_op_ctc_collapse_spans(void* stream, const int32_t* raw, const float* lprob, int T, int blank, int pad, int32_t* tokens,
+                             int32_t* index, int32_t* last, float* tok_lprob, int32_t* count, const int32_t* segs, int nseg);
 int ss_op_dur_predict(void* stream, const float* logdur, const int32_t* forced, int K, int32_t* dur, int32_t* cum,
                       const int32_t* segs, int nseg);                 /* segs {start, len}: cum of segment s at start + s */
 int ss_op_repeat_rows(void* stream, const float* emb, const int32_t* cum, int K, int D, float* out, int F, const int32_t* segs,

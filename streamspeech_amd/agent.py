@@ -32,6 +32,18 @@ def _detok(symbols):
     return text[1:] if len(text) > 0 and text[0] == " " else text
 
 
+def word_details(agent, src_hyp, tgt_hyp):
+    """--word-details: the words of both CTC heads from the scored hypotheses of this policy() call.  `stable` needs the rows that
+    are final, which only the incremental encoder counts (engine.stream_stats): None under --full-recompute-encoder."""
+    from .words import details_from_hyps
+    eng = agent.model.hip if hasattr(agent.model, "hip") else agent.model
+    n_final = None
+    if getattr(agent.model.encoder, "incremental", False) and getattr(eng, "stream_stats", None) is not None:
+        n_final = int(eng.stream_stats[0])
+    return details_from_hyps(src_hyp, tgt_hyp, agent.dict["source_unigram"], agent.dict["ctc_target_unigram"], n_final=n_final,
+                             finished=bool(agent.states.source_finished))
+
+
 def speaker_id_arg(args, vocoder, flag="--speaker-id"):
     """The voice of an agent or session: args.speaker_id on a multi-speaker vocoder (required there, inside its speakers), None on
     a single-speaker one, which ignores the flag."""
@@ -214,8 +226,13 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
                "(--mt-step-workgroups), which belongs to the greedy search, is not armed")
         a("--unkpen", type=float, default=0.0, help="subtracted from the <unk> log-probability of the beam search of --beam-mt > 1; ignored at --beam-mt 1 (the greedy "
                "search of the reference agent has no such penalty)")
+        a("--word-details", action="store_true", default=False,
+          help="after every policy() that ran the encoder, agent.details holds the words of both CTC heads with their time spans, "
+               "confidences and stability (streamspeech_amd/words.py); default: off, the heads run exactly as without the flag")
         a("--extra-output-dir", type=str, default=None, help="extra output dir")
         a("--output-asr-translation", type=bool, default=False, help="extra output dir")
+
+    details = None      # --word-details: the words.CtcDetails of the last policy() that ran the encoder
 
     def reset(self):
         self.src_seg_num = 0
@@ -304,7 +321,9 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
         self.encoder_outs = [encoder_out]
 
         # ASR / ST CTC heads (agent :437-478)
-        finalized_asr = self.asr_ctc_generator.generate(encoder_out, aux_task_name="source_unigram")
+        wd = bool(getattr(self.args, "word_details", False))
+        wkw = {"want_scores": True} if wd else {}
+        finalized_asr = self.asr_ctc_generator.generate(encoder_out, aux_task_name="source_unigram", **wkw)
         src_ctc_indices = finalized_asr[0][0]["tokens"].int()
         if (self.states.source_finished and not self.quiet) or self.output_asr_translation:
             text = _detok([self.dict["source_unigram"][c] for c in src_ctc_indices])
@@ -313,8 +332,10 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
                     print(text, file=f)
             if self.output_asr_translation:
                 print("Streaming ASR:", text)
-        finalized_st = self.st_ctc_generator.generate(encoder_out, aux_task_name="ctc_target_unigram")
+        finalized_st = self.st_ctc_generator.generate(encoder_out, aux_task_name="ctc_target_unigram", **wkw)
         tgt_ctc_indices = finalized_st[0][0]["tokens"].int()
+        if wd:
+            self.details = word_details(self, finalized_asr[0][0], finalized_st[0][0])
 
         # read/write gate on the CTC token counts (agent :480-512)
         if not self.states.source_finished:

@@ -6,7 +6,7 @@ agent/speech_to_text.s2tt.streamspeech.agent.py:381-545 (same flags as the S2ST 
 vocoder ones)."""
 import torch
 
-from .agent import StreamSpeechS2STAgent, _beam_kwargs, _detok
+from .agent import StreamSpeechS2STAgent, _beam_kwargs, _detok, word_details
 from .frontend import OnlineFeatureExtractor  # noqa: F401  (re-exported for parity with the reference files)
 from .generators import CTCDecoder, SequenceGenerator
 from .simuleval_shim import ReadAction, SpeechToTextAgent, WriteAction, entrypoint
@@ -51,6 +51,16 @@ class _TextAgentBase(SpeechToTextAgent):
         self.reset()
 
     add_args = staticmethod(_add_text_args)
+    details = None      # --word-details: the words.CtcDetails of the last policy() that ran the encoder
+
+    def _ctc_hyps(self, enc):
+        """The two CTC hypotheses of policy(); with --word-details the scored form, and agent.details from them."""
+        if not getattr(self.args, "word_details", False):
+            return None
+        src = self.asr_ctc_generator.generate(enc, aux_task_name="source_unigram", want_scores=True)[0][0]
+        tgt = self.st_ctc_generator.generate(enc, aux_task_name="ctc_target_unigram", want_scores=True)[0][0]
+        self.details = word_details(self, src, tgt)
+        return src, tgt
 
     def reset(self):
         self.tgt_subwords_indices = None
@@ -83,7 +93,8 @@ class StreamSpeechASRAgent(_TextAgentBase):
         enc, _, _ = self._encode()
         if enc is None:
             return WriteAction("", finished=True) if self.states.source_finished else ReadAction()
-        hyp = self.asr_ctc_generator.generate(enc, aux_task_name="source_unigram")[0][0]
+        scored = self._ctc_hyps(enc)
+        hyp = scored[0] if scored else self.asr_ctc_generator.generate(enc, aux_task_name="source_unigram")[0][0]
         tokens = [self.dict["source_unigram"][c] for c in hyp["tokens"].int()]
         if self.states.source_finished and not self.quiet:
             with open(self.asr_file, "a") as f:
@@ -106,8 +117,12 @@ class StreamSpeechS2TTAgent(_TextAgentBase):
         enc, src_indices, src_lengths = self._encode()
         if enc is None:
             return WriteAction("", finished=True) if self.states.source_finished else ReadAction()
-        src_ctc = self.asr_ctc_generator.generate(enc, aux_task_name="source_unigram")[0][0]["tokens"].int()
-        tgt_ctc = self.st_ctc_generator.generate(enc, aux_task_name="ctc_target_unigram")[0][0]["tokens"].int()
+        scored = self._ctc_hyps(enc)
+        if scored:
+            src_ctc, tgt_ctc = scored[0]["tokens"].int(), scored[1]["tokens"].int()
+        else:
+            src_ctc = self.asr_ctc_generator.generate(enc, aux_task_name="source_unigram")[0][0]["tokens"].int()
+            tgt_ctc = self.st_ctc_generator.generate(enc, aux_task_name="ctc_target_unigram")[0][0]["tokens"].int()
         gate = s2tt_gate(src_ctc.size(-1), tgt_ctc.size(-1), self.src_ctc_prefix_length, self.tgt_ctc_prefix_length,
                          self.tgt_subwords_indices.size(-1) if self.tgt_subwords_indices is not None else 0, self.lagging_k1,
                          self.stride_n, self.states.source_finished)

@@ -131,6 +131,30 @@ extern "C" int ss_batch_ctc_greedy(ss_model* m, void* stream, int head, int B, c
   return launch_ctc_collapse(d_raw, 0, 0, c.pad, d_tokens, d_index, d_counts, s, (const int*)m->sc->seg_buf.p, B);
 }
 
+// ss_batch_ctc_greedy with scores: the same tables, head GEMM and CanonScope, the scored twins of the two glue kernels.
+extern "C" int ss_batch_ctc_greedy_scored(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp,
+                                          int32_t* d_raw, int32_t* d_tokens, int32_t* d_index, int32_t* d_counts, float* d_lprob,
+                                          int32_t* d_last, float* d_tok_lprob) {
+  if (!m || B <= 0 || head < 0 || head > 1 || !d_lprob || !d_last || !d_tok_lprob) return SS_ERR_ARG;
+  SkScope sk_scope(m->sc->skws);
+  CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
+  hipStream_t s = (hipStream_t)stream;
+  const ss_config& c = m->cfg;
+  const Offsets o = prefix(h_Tp, B);
+  const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
+  RET(m->sc->mt_ws.ensure((size_t)o.total * V * sizeof(float)));
+  float* logits = m->sc->mt_ws.f();
+  std::vector<int> tr(2 * B);
+  for (int b = 0; b < B; ++b) { tr[2 * b] = o.off[b]; tr[2 * b + 1] = h_Tp[b]; }
+  RET(m->sc->seg_buf.ensure(tr.size() * sizeof(int)));
+  RET(upload(s, (int*)m->sc->seg_buf.p, tr));
+  RET(linear(s, d_enc_out, c.enc_dim, o.total, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, logits, V));
+  m->sc->dbg_logits = logits; m->sc->dbg_rows = o.total; m->sc->dbg_cols = V;
+  RET(launch_masked_argmax_lprob(logits, V, o.total, V, c.pad, c.unk, -1, d_raw, d_lprob, s));
+  return launch_ctc_collapse_spans(d_raw, d_lprob, 0, 0, c.pad, d_tokens, d_index, d_last, d_tok_lprob, d_counts, s,
+                                   (const int*)m->sc->seg_buf.p, B);
+}
+
 // Batched beam-1 search: all utterances start from [</s>] and advance in lockstep, one row per
 // utterance (M = B GEMMs stream every decoder weight once per step for the whole batch).
 extern "C" int ss_batch_mt_greedy(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp,

@@ -202,6 +202,14 @@ extern "C" int ss_op_ctc_collapse(void* stream, const int32_t* raw, int T, int b
                                   int32_t* count, const int32_t* segs, int nseg) {
   return launch_ctc_collapse(raw, T, blank, pad, tokens, index, count, (hipStream_t)stream, segs, nseg);
 }
+extern "C" int ss_op_masked_argmax_lprob(void* stream, const float* logits, int ld, int M, int N, int mask0, int mask1, int mask2,
+                                         int32_t* ids, float* lprob) {
+  return launch_masked_argmax_lprob(logits, ld, M, N, mask0, mask1, mask2, ids, lprob, (hipStream_t)stream);
+}
+extern "C" int ss_op_ctc_collapse_spans(void* stream, const int32_t* raw, const float* lprob, int T, int blank, int pad, int32_t* tokens,
+                                        int32_t* index, int32_t* last, float* tok_lprob, int32_t* count, const int32_t* segs, int nseg) {
+  return launch_ctc_collapse_spans(raw, lprob, T, blank, pad, tokens, index, last, tok_lprob, count, (hipStream_t)stream, segs, nseg);
+}
 extern "C" int ss_op_dur_predict(void* stream, const float* logdur, const int32_t* forced, int K, int32_t* dur, int32_t* cum,
                                  const int32_t* segs, int nseg) {
   return launch_dur_predict(logdur, forced, K, dur, cum, (hipStream_t)stream, segs, nseg);

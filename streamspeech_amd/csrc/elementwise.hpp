@@ -53,6 +53,15 @@ int launch_row_max_logprob(const float* logits, int ld, int M, int N, int mask0,
 int launch_ctc_collapse(const int* raw, int T, int blank, int pad, int* tokens, int* index, int* count,
                         hipStream_t stream, const int* segs = nullptr, int nseg = 0);  // segs {start,len}: count[s]
 
+// Scored twins of the two launchers above for the text CTC heads (ctc_scores.hip; reference agent/ctc_decoder.py:52-62,
+// `positional_scores`): ids as launch_masked_argmax without force / row lengths, lprob[m] as launch_row_max_logprob from the same
+// read of the row; tokens / index / count as launch_ctc_collapse, plus per kept token the last frame of its run of equal raw ids
+// and the float32 sum of lprob over that run, added in ascending frame order.
+int launch_masked_argmax_lprob(const float* logits, int ld, int M, int N, int mask0, int mask1, int mask2, int* ids, float* lprob,
+                               hipStream_t stream);
+int launch_ctc_collapse_spans(const int* raw, const float* lprob, int T, int blank, int pad, int* tokens, int* index, int* last,
+                              float* tok_lprob, int* count, hipStream_t stream, const int* segs = nullptr, int nseg = 0);
+
 // emb_out[k,:] = table[codes[k],:]
 int launch_gather_rows(const int* idx, const float* table, int D, float* out, int n, hipStream_t stream, int rows);  // ids outside [0, rows) read row 0
 // dst[dst_row[k] * ldd + c] = src[k * lds + c] for c < D; rows outside [0, dst_rows) are skipped

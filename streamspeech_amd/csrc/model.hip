@@ -549,6 +549,26 @@ extern "C" int ss_ctc_greedy(ss_model* m, void* stream, int head, const float* d
   return launch_ctc_collapse(d_raw, Tp, 0, c.pad, d_tokens, d_index, d_count, s);
 }
 
+// ss_ctc_greedy with the per-frame log-probability of the arg-max and the spans of the collapsed tokens (ctc_scores.hip): the same
+// head GEMM, the scored twins of the two glue kernels -- the same number of launches.
+extern "C" int ss_ctc_greedy_scored(ss_model* m, void* stream, int head, const float* d_enc_out, int Tp, int32_t* d_raw,
+                                    int32_t* d_tokens, int32_t* d_index, int32_t* d_count, float* d_logits, float* d_lprob,
+                                    int32_t* d_last, float* d_tok_lprob) {
+  if (!m || Tp <= 0 || head < 0 || head > 1 || !d_lprob || !d_last || !d_tok_lprob) return SS_ERR_ARG;
+  SkScope sk_scope(m->sc->skws);
+  hipStream_t s = (hipStream_t)stream;
+  const ss_config& c = m->cfg;
+  const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
+  float* logits = d_logits;
+  if (!logits) {
+    RET(m->sc->mt_ws.ensure((size_t)Tp * V * sizeof(float)));
+    logits = m->sc->mt_ws.f();
+  }
+  RET(linear(s, d_enc_out, c.enc_dim, Tp, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, logits, V));
+  RET(launch_masked_argmax_lprob(logits, V, Tp, V, c.pad, c.unk, -1, d_raw, d_lprob, s));
+  return launch_ctc_collapse_spans(d_raw, d_lprob, Tp, 0, c.pad, d_tokens, d_index, d_last, d_tok_lprob, d_count, s);
+}
+
 extern "C" int ss_mt_begin(ss_model* m, void* stream, const float* d_enc_out, int Tp) {
   if (!m || Tp <= 0) return SS_ERR_ARG;
   SkScope sk_scope(m->sc->skws);

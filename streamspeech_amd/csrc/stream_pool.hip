@@ -191,12 +191,15 @@ struct PoolSlot {
   int fin = 0, achunk = -1, cchunk = -1, tail = 0;   // as ss_scratch::es_final / es_achunk / es_cchunk / es_tail
   int T2 = 0, nf = 0;                                  // rows of the last forward's output and the final ones among them (CTC calls)
   int cfin[2] = {0, 0};                                // rows whose raw CTC arg-max of head h the slot holds
+  int lfin[2] = {0, 0};                                // ... and whose arg-max log-probability it holds (ss_stream_pool_set_scores)
 };
 
 struct ss_stream_pool {
   ss_scratch* sc = nullptr;
   int S = 0, R = 0, L = 0, d = 0;
   DevBuf qkv, glu, out, raw;        // [L][S][R][3d], [L][S][R][d], [S][R][d], [2][S][R] (int32)
+  DevBuf lp;                        // [2][S][R] float: the arg-max log-probability of the rows in raw (booked by ss_stream_pool_set_scores)
+  bool scores = false;
   std::vector<PoolSlot> slot;
   long long launches = 0, head_rows = 0;
   hipEvent_t done = nullptr;        // recorded behind the last call's work: what ss_stream_pool_destroy waits for
@@ -216,7 +219,7 @@ static int pool_mark(ss_stream_pool* p, hipStream_t s) {
 }
 
 static void pool_free(ss_stream_pool* p) {
-  DevBuf* bufs[4] = {&p->qkv, &p->glu, &p->out, &p->raw};
+  DevBuf* bufs[5] = {&p->qkv, &p->glu, &p->out, &p->raw, &p->lp};
   for (DevBuf* b : bufs) {
     b->release();
     auto& ex = p->sc->extra;
@@ -424,7 +427,10 @@ extern "C" int ss_encoder_stream_forward_batch(ss_model* m, void* stream, ss_str
     PoolSlot& st = p->slot[e.slot];
     st.fin = e.nf; st.achunk = e.achunk_cfg; st.cchunk = e.cchunk;
     st.T2 = e.T2; st.nf = e.nf;
-    for (int hd = 0; hd < 2; ++hd) st.cfin[hd] = std::min(st.cfin[hd], e.r0);    // cached arg-max rows stay valid while final
+    for (int hd = 0; hd < 2; ++hd) {                                             // cached arg-max rows stay valid while final
+      st.cfin[hd] = std::min(st.cfin[hd], e.r0);
+      st.lfin[hd] = std::min(st.lfin[hd], e.r0);
+    }
     if (h_n_final) h_n_final[i] = e.nf;
     if (h_n_computed) h_n_computed[i] = e.n;
   }
@@ -485,6 +491,90 @@ extern "C" int ss_stream_pool_ctc(ss_model* m, void* stream, ss_stream_pool* p, 
   RET(pool_mark(p, s));
   p->head_rows += Mc;
   for (int i = 0; i < n; ++i) { PoolSlot& st = p->slot[h_slots[i]]; st.cfin[head] = st.nf; }
+  return SS_OK;
+}
+
+// Scores on: the float cache beside p->raw, booked on the pool's scratch set (exact size; refused on the cap, the set as it was).
+// Only while no slot holds rows: a slot's cached arg-max rows and their log-probabilities are filled together or not at all.
+extern "C" int ss_stream_pool_set_scores(ss_stream_pool* p, int on) {
+  if (!p) return SS_ERR_ARG;
+  if ((on != 0) == p->scores) return SS_OK;
+  for (const PoolSlot& st : p->slot)
+    if (st.fin > 0 || st.T2 > 0) return SS_ERR_ARG;
+  if (on) {
+    p->lp.acct = &p->sc->acct;
+    RET(p->lp.ensure(2 * (size_t)p->S * p->R * sizeof(float), true));
+    p->sc->extra.push_back(&p->lp);
+  } else {
+    if (p->recorded) (void)hipEventSynchronize(p->done);
+    p->lp.release();
+    auto& ex = p->sc->extra;
+    ex.erase(std::remove(ex.begin(), ex.end(), &p->lp), ex.end());
+  }
+  p->scores = on != 0;
+  return SS_OK;
+}
+
+// ss_stream_pool_ctc with scores: rows below a slot's n_final take their arg-max AND its log-probability from the slot, the rest go
+// through the head and the scored arg-max; the float cache goes through the id gather as raw bits (one launch more than the unscored
+// call, whatever n), the collapse is the span form.
+extern "C" int ss_stream_pool_ctc_scored(ss_model* m, void* stream, ss_stream_pool* p, int head, int n, const int32_t* h_slots,
+                                         const float* d_enc_packed, int32_t* d_raw, int32_t* d_tokens, int32_t* d_index,
+                                         int32_t* d_counts, float* d_lprob, int32_t* d_last, float* d_tok_lprob) {
+  if (!m || !p || p->sc != m->sc || head < 0 || head > 1 || n <= 0 || n > p->S || !h_slots || !d_enc_packed || !d_raw || !d_tokens ||
+      !d_index || !d_counts || !d_lprob || !d_last || !d_tok_lprob || m->cfg.enc_dim != p->d || !p->scores)
+    return SS_ERR_ARG;
+  const ss_config& c = m->cfg;
+  const int d = c.enc_dim, V = head == 0 ? c.src_vocab : c.tgt_vocab;
+  std::vector<char> seen(p->S, 0);
+  // tables as ss_stream_pool_ctc: gather [6 n], prefix [n + 1], stack src [n], stack prefix [n + 1], collapse {off, T2} [2 n]
+  std::vector<int> ti(6 * n + (n + 1) + n + (n + 1) + 2 * n);
+  int *gt = ti.data(), *gp = gt + 6 * n, *src = gp + n + 1, *sp = src + n, *cs = sp + n + 1;
+  int total = 0, Mc = 0;
+  for (int i = 0; i < n; ++i) {
+    const int sl = h_slots[i];
+    if (sl < 0 || sl >= p->S || seen[sl] || p->slot[sl].T2 <= 0) return SS_ERR_ARG;
+    seen[sl] = 1;
+    const PoolSlot& st = p->slot[sl];
+    const int c0 = std::min(std::min(st.cfin[head], st.lfin[head]), st.nf);   // rows the slot holds BOTH values of
+    int* r = gt + 6 * i;
+    r[0] = total; r[1] = st.T2; r[2] = c0; r[3] = st.nf; r[4] = sl; r[5] = Mc;
+    gp[i] = total;
+    src[i] = total + c0; sp[i] = Mc;
+    cs[2 * i] = total; cs[2 * i + 1] = st.T2;
+    total += st.T2; Mc += st.T2 - c0;
+  }
+  gp[n] = total; sp[n] = Mc;
+  SkScope sk_scope(m->sc->skws);
+  CanonScope canon_scope(CANON_SEQ);
+  hipStream_t s = (hipStream_t)stream;
+  RET(m->sc->seg_buf.ensure(ti.size() * sizeof(int)));
+  RET(m->sc->mt_ws.ensure((size_t)Mc * V * sizeof(float)));
+  RET(m->sc->ws.ensure((size_t)Mc * d * sizeof(float) + (size_t)Mc * (sizeof(int32_t) + sizeof(float))));
+  int* dt = (int*)m->sc->seg_buf.p;
+  RET(upload(s, dt, ti));
+  const int *dgt = dt, *dgp = dgt + 6 * n, *dsrc = dgp + n + 1, *dsp = dsrc + n, *dcs = dsp + n + 1;
+  float* stk = m->sc->ws.f();
+  int32_t* raw_stk = reinterpret_cast<int32_t*>(stk + (size_t)Mc * d);
+  float* lp_stk = reinterpret_cast<float*>(raw_stk + Mc);
+  long long nl = 0;
+  const long long g0 = gemm_census();
+  if (Mc > 0) {
+    RET(launch_pool_stack_rows(stk, d_enc_packed, d, dsrc, dsp, n, Mc, s));
+    RET(linear(s, stk, d, Mc, head == 0 ? m->ctc_asr : m->ctc_st, V, d, m->sc->mt_ws.f(), V));
+    RET(launch_masked_argmax_lprob(m->sc->mt_ws.f(), V, Mc, V, c.pad, c.unk, -1, raw_stk, lp_stk, s));
+    nl += 2;
+  }
+  const size_t hoff = (size_t)head * p->S * p->R;
+  RET(launch_pool_gather_ids(d_raw, raw_stk, reinterpret_cast<int32_t*>(p->raw.p) + hoff, p->R, dgt, dgp, n, total, s));
+  RET(launch_pool_gather_ids(reinterpret_cast<int32_t*>(d_lprob), reinterpret_cast<const int32_t*>(lp_stk),
+                             reinterpret_cast<int32_t*>(p->lp.p) + hoff, p->R, dgt, dgp, n, total, s));   // float bits, moved as int32
+  RET(launch_ctc_collapse_spans(d_raw, d_lprob, 0, 0, c.pad, d_tokens, d_index, d_last, d_tok_lprob, d_counts, s, dcs, n));
+  nl += 3;
+  p->launches += nl + (gemm_census() - g0);
+  RET(pool_mark(p, s));
+  p->head_rows += Mc;
+  for (int i = 0; i < n; ++i) { PoolSlot& st = p->slot[h_slots[i]]; st.cfin[head] = st.nf; st.lfin[head] = st.nf; }
   return SS_OK;
 }
 

@@ -42,6 +42,21 @@ def _i32(vals):
     return (C.c_int32 * len(vals))(*[int(v) for v in vals])
 
 
+def _unpack_scored(host, T: List[int], return_raw: bool = False):
+    """One head's scored CTC answer on the host: int32 [6 tot + n] = raw | tokens | index | last | lprob bits | tok_lprob bits | counts
+    (the float bits ride in the int32 buffer: one device-to-host copy).  -> per session (tokens, index, last, tok_lprob, lprob rows)."""
+    tot, fl = sum(T), host.view(np.float32)
+    out, off = [], 0
+    for b, t in enumerate(T):
+        n = int(host[6 * tot + b])
+        rec = (host[tot + off: tot + off + n].tolist(), host[2 * tot + off: 2 * tot + off + n].tolist(),
+               host[3 * tot + off: 3 * tot + off + n].tolist(), fl[5 * tot + off: 5 * tot + off + n].copy(),
+               fl[4 * tot + off: 4 * tot + off + t].copy())
+        out.append(rec + (host[off: off + t].tolist(),) if return_raw else rec)
+        off += t
+    return out
+
+
 def resample_ratio(sr_in: int, sr_out: int = 16000) -> Tuple[int, int, int]:
     """(up, down, half_len) of the resampler from sr_in to sr_out: the ratio in lowest terms and the taps on either side of the
     centre of frontend.design_filter's low-pass (0 when nothing is resampled)."""
@@ -107,9 +122,19 @@ class BatchMixin:
                                                   _ptr(out), hTp), "ss_batch_encoder_forward")
         return out, list(hTp)
 
-    def batch_ctc_greedy(self, head: int, enc_packed: torch.Tensor, Tp: List[int], return_raw: bool = False):
-        """-> per-utterance (tokens, frame index) lists (+ the raw per-frame argmax with return_raw)."""
+    def batch_ctc_greedy(self, head: int, enc_packed: torch.Tensor, Tp: List[int], return_raw: bool = False,
+                         return_scores: bool = False):
+        """-> per-utterance (tokens, frame index) lists (+ the raw per-frame argmax with return_raw).  With return_scores each
+        record is (tokens, index, last frame per token, summed log-probability per token [float32], log-probability per frame
+        [float32 Tp]) (+ raw): the reference's `positional_scores` (agent/ctc_decoder.py:61) and the spans they are summed over."""
         B, tot = len(Tp), sum(Tp)
+        if return_scores:
+            ibuf = torch.empty((6 * tot + B,), dtype=torch.int32, device=self.device)
+            fbuf = ibuf.view(torch.float32)
+            p = [_ptr(ibuf[k * tot:(k + 1) * tot]) for k in range(4)] + [_ptr(fbuf[k * tot:(k + 1) * tot]) for k in (4, 5)]
+            L.check(self.lib.ss_batch_ctc_greedy_scored(self.h, _stream(), head, B, _ptr(enc_packed), _i32(Tp), p[0], p[1], p[2],
+                                                        _ptr(ibuf[6 * tot:]), p[4], p[3], p[5]), "ss_batch_ctc_greedy_scored")
+            return _unpack_scored(ibuf.cpu().numpy(), Tp, return_raw)
         ibuf = torch.empty((3 * tot + B,), dtype=torch.int32, device=self.device)
         raw, toks, idx, cnt = ibuf[:tot], ibuf[tot:2 * tot], ibuf[2 * tot:3 * tot], ibuf[3 * tot:]
         L.check(self.lib.ss_batch_ctc_greedy(self.h, _stream(), head, B, _ptr(enc_packed), _i32(Tp), _ptr(raw),
@@ -589,10 +614,11 @@ class HipModel(BatchMixin):
         self._last_enc = (out.data_ptr(), Tp)
         return out
 
-    def stream_pool(self, max_sessions: int, max_rows: int) -> "StreamPool":
+    def stream_pool(self, max_sessions: int, max_rows: int, scores: bool = False) -> "StreamPool":
         """A pool of `max_sessions` streaming-encoder slots of `max_rows` output rows each, booked in this handle's scratch set: one
-        batched encoder step (and one CTC call per head) for many concurrent streams (:class:`StreamPool`)."""
-        return StreamPool(self, max_sessions, max_rows)
+        batched encoder step (and one CTC call per head) for many concurrent streams (:class:`StreamPool`).  `scores`: its CTC calls
+        also answer each frame's log-probability and each token's span (ss_stream_pool_set_scores)."""
+        return StreamPool(self, max_sessions, max_rows, scores)
 
     # ---- a8 -------------------------------------------------------------------------------
     # Both CTC heads behind ONE host round trip (off unless a caller sets ``ctc_speculate``; the agents do: policy() always asks for the
@@ -607,10 +633,22 @@ class HipModel(BatchMixin):
         n = int(host[3 * Tp])
         return host[Tp:Tp + n].tolist(), host[2 * Tp:2 * Tp + n].tolist(), host[:Tp], None
 
-    def ctc_greedy(self, head: int, enc_out: torch.Tensor, want_logits: bool = False):
-        """-> (tokens list, frame index list, raw argmax tensor, logits or None)."""
+    def ctc_greedy(self, head: int, enc_out: torch.Tensor, want_logits: bool = False, want_scores: bool = False):
+        """-> (tokens list, frame index list, raw argmax tensor, logits or None); with want_scores three more: last frame per token
+        (list), summed log-probability per token and log-probability per frame (float32 arrays) -- agent/ctc_decoder.py:61."""
         Tp = enc_out.shape[0]
         key = (enc_out.data_ptr(), Tp)
+        if want_scores:                    # its own call: the parked answers of the unscored form hold no scores
+            V = self.cfg.src_vocab if head == 0 else self.cfg.tgt_vocab
+            ibuf = torch.empty((6 * Tp + 1,), dtype=torch.int32, device=self.device)
+            fbuf = ibuf.view(torch.float32)
+            logits = torch.empty((Tp, V), dtype=torch.float32, device=self.device) if want_logits else None
+            L.check(self.lib.ss_ctc_greedy_scored(self.h, _stream(), head, _ptr(enc_out), Tp, _ptr(ibuf[:Tp]), _ptr(ibuf[Tp:2 * Tp]),
+                                                  _ptr(ibuf[2 * Tp:3 * Tp]), _ptr(ibuf[6 * Tp:]), _ptr(logits), _ptr(fbuf[4 * Tp:5 * Tp]),
+                                                  _ptr(ibuf[3 * Tp:4 * Tp]), _ptr(fbuf[5 * Tp:6 * Tp])), "ss_ctc_greedy_scored")
+            host = ibuf.cpu()
+            toks, idx, last, tok_lp, lp = _unpack_scored(host.numpy(), [Tp])[0]
+            return toks, idx, host[:Tp], logits, last, tok_lp, lp
         both = getattr(self, "_ctc_both", None)
         if both is not None and not want_logits and both[0] == key and head in both[1]:
             return self._ctc_unpack(both[1].pop(head), Tp)              # computed behind the streaming encoder call (handed out once)
@@ -867,17 +905,34 @@ class StreamPool:
     any subset of slots; per slot it behaves exactly like :meth:`HipModel.encoder_stream_forward` on a context of its own.
     Driven by one host thread at a time (like a scratch set)."""
 
-    def __init__(self, model: "HipModel", max_sessions: int, max_rows: int):
+    def __init__(self, model: "HipModel", max_sessions: int, max_rows: int, scores: bool = False):
         self.lib, self.model, self.device = model.lib, model, _require_gpu(model.device)
         self.max_sessions, self.max_rows = int(max_sessions), int(max_rows)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             L.check(self.lib.ss_stream_pool_create(model.h, self.max_sessions, self.max_rows, C.byref(h)), "ss_stream_pool_create")
         self.h = h
+        self.scores = False
+        if scores:
+            self.set_scores(True)
         self._last = None          # (slots, T2 list, packed output tensor) of the last forward: what ctc() reads
 
     def reset(self, slot: int):
         L.check(self.lib.ss_stream_pool_reset(self.h, int(slot)), "ss_stream_pool_reset")
+
+    def set_scores(self, on: bool):
+        """Switch the scored form of :meth:`ctc` / :meth:`ctc_both` on or off; only while no slot holds rows."""
+        with torch.cuda.device(self.device):
+            L.check(self.lib.ss_stream_pool_set_scores(self.h, 1 if on else 0), "ss_stream_pool_set_scores")
+        self.scores = bool(on)
+
+    def _ctc_scored(self, head: int, n: int, lslots, enc, ibuf, tot: int):
+        """Queue one head's scored call into ibuf (int32 [6 tot + n], the layout of _unpack_scored)."""
+        fbuf = ibuf.view(torch.float32)
+        L.check(self.lib.ss_stream_pool_ctc_scored(self.model.h, _stream(), self.h, int(head), n, _i32(lslots), _ptr(enc), _ptr(ibuf[:tot]),
+                                                   _ptr(ibuf[tot:2 * tot]), _ptr(ibuf[2 * tot:3 * tot]), _ptr(ibuf[6 * tot:]),
+                                                   _ptr(fbuf[4 * tot:5 * tot]), _ptr(ibuf[3 * tot:4 * tot]), _ptr(fbuf[5 * tot:6 * tot])),
+                "ss_stream_pool_ctc_scored")
 
     def set_tail(self, slot: int, unsettled_fbank_frames: int):
         L.check(self.lib.ss_stream_pool_set_tail(self.h, int(slot), int(unsettled_fbank_frames)), "ss_stream_pool_set_tail")
@@ -930,6 +985,10 @@ class StreamPool:
         if enc.shape[0] != sum(T2):
             raise ValueError("packed output of another step")
         n, tot = len(lslots), sum(T2)
+        if self.scores:                # -> per session (tokens, index, last, tok_lprob, lprob rows) (+ raw)
+            ibuf = torch.empty((6 * tot + n,), dtype=torch.int32, device=self.device)
+            self._ctc_scored(head, n, lslots, enc, ibuf, tot)
+            return _unpack_scored(ibuf.cpu().numpy(), T2, return_raw)
         ibuf = torch.empty((3 * tot + n,), dtype=torch.int32, device=self.device)
         raw, toks, idx, cnt = ibuf[:tot], ibuf[tot:2 * tot], ibuf[2 * tot:3 * tot], ibuf[3 * tot:]
         L.check(self.lib.ss_stream_pool_ctc(self.model.h, _stream(), self.h, int(head), n, _i32(lslots), _ptr(enc), _ptr(raw),
@@ -949,6 +1008,13 @@ class StreamPool:
             raise ValueError("ctc_both() before any forward()")
         lslots, T2, enc = self._last
         n, tot = len(lslots), sum(T2)
+        if self.scores:                # the float bits ride in the same int32 buffer: still ONE copy
+            per = 6 * tot + n
+            ibuf = torch.empty((2 * per,), dtype=torch.int32, device=self.device)
+            for hd in (0, 1):
+                self._ctc_scored(hd, n, lslots, enc, ibuf[hd * per:(hd + 1) * per], tot)
+            host = ibuf.cpu().numpy()
+            return _unpack_scored(host[:per], T2), _unpack_scored(host[per:], T2)
         per = 3 * tot + n
         ibuf = torch.empty((2 * per,), dtype=torch.int32, device=self.device)
         for hd in (0, 1):

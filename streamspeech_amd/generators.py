@@ -18,22 +18,39 @@ class CTCDecoder:
         self.pad, self.eos, self.unk = tgt_dict.pad(), tgt_dict.eos(), tgt_dict.unk()
 
     @torch.no_grad()
-    def generate(self, encoder_out, prefix=None, aux_task_name=None, want_lprobs=False, **kw):
+    def generate(self, encoder_out, prefix=None, aux_task_name=None, want_lprobs=False, want_scores=False, **kw):
+        """want_scores: the hypothesis also carries `positional_scores` (float32 [Tp], agent/ctc_decoder.py:61-62,104) and `score`
+        (their sum, :105, taken on the host in float64), plus `last` / `token_scores`: each token's last frame and the sum of
+        positional_scores over its run of frames (what streamspeech_amd.words turns into word spans and confidences)."""
         enc = encoder_out["encoder_out"][0]
         enc = enc[:, 0] if enc.dim() == 3 else enc
-        toks, index, raw, logits = self.engine.ctc_greedy(self.head, enc.contiguous(), want_logits=want_lprobs)
+        last = tok_lp = lp = None
+        if want_scores:
+            toks, index, raw, logits, last, tok_lp, lp = self.engine.ctc_greedy(self.head, enc.contiguous(), want_logits=want_lprobs,
+                                                                                want_scores=True)
+        else:
+            toks, index, raw, logits = self.engine.ctc_greedy(self.head, enc.contiguous(), want_logits=want_lprobs)
         if prefix is not None:  # agent/ctc_decoder.py:90-92
             pre = [int(t) for t in prefix.view(-1).tolist()]
             merged = pre + raw.tolist()[len(pre):]
-            from .pipeline import ctc_collapse_host
-            toks, index = ctc_collapse_host(merged, 0, self.pad)
+            from .pipeline import ctc_collapse_host, ctc_collapse_spans_host
+            if want_scores:      # the scores stay those of the arg-max (the reference splices ids only), the spans follow the merged ids
+                toks, index, last, tok_lp = ctc_collapse_spans_host(merged, lp, 0, self.pad)
+            else:
+                toks, index = ctc_collapse_host(merged, 0, self.pad)
             raw = torch.tensor(merged, dtype=torch.int32)
         lprobs = None
         if logits is not None:
             # model.get_normalized_probs + "never select pad, unk" (agent/ctc_decoder.py:52-60), on the engine (ss_log_softmax)
             lprobs = self.engine.normalized_probs(logits, True, self.pad, self.unk).unsqueeze(0)
-        return [[{"tokens": torch.tensor(toks, dtype=torch.long), "org_tokens": raw, "lprobs": lprobs,
-                  "index": index, "attn": None, "alignment": None}]]
+        hyp = {"tokens": torch.tensor(toks, dtype=torch.long), "org_tokens": raw, "lprobs": lprobs,
+               "index": index, "attn": None, "alignment": None}
+        if want_scores:
+            import numpy as np
+            hyp.update({"positional_scores": torch.from_numpy(np.ascontiguousarray(lp, dtype=np.float32)),
+                        "score": float(np.asarray(lp, dtype=np.float64).sum()), "last": list(last),
+                        "token_scores": torch.from_numpy(np.ascontiguousarray(tok_lp, dtype=np.float32))})
+        return [[hyp]]
 
 
 class CTCSequenceGenerator:

@@ -169,6 +169,7 @@ SIGNATURES = {
     "ss_encoder_stream_status": (_i, [_vp, _vp, _vp]),
     "ss_debug_enc_step_inject_timeout": (_i, [_vp]),
     "ss_encoder_stream_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ss_ctc_greedy_scored": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ss_ctc_greedy": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ss_stream_pool_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
     "ss_stream_pool_destroy": (None, [_vp]),
@@ -177,6 +178,8 @@ SIGNATURES = {
     "ss_encoder_stream_forward_batch": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int32), C.POINTER(_vp), C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int32)]),
+    "ss_stream_pool_set_scores": (_i, [_vp, _i]),
+    "ss_stream_pool_ctc_scored": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ss_stream_pool_ctc": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp]),
     "ss_stream_pool_stats": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "ss_mt_begin": (_i, [_vp, _vp, _vp, _i]),
@@ -207,6 +210,7 @@ SIGNATURES = {
     "ss_batch_fbank_cmvn": (_i, [_vp, _vp, _i, _vp, C.POINTER(_i64), C.POINTER(C.c_int32), _f, _vp, C.POINTER(C.c_int32)]),
     "ss_batch_cmvn": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "ss_batch_encoder_forward": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _i, _vp, C.POINTER(C.c_int32)]),
+    "ss_batch_ctc_greedy_scored": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ss_batch_ctc_greedy": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp]),
     "ss_batch_mt_greedy": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
                                 C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _vp, _i]),
@@ -284,6 +288,8 @@ SIGNATURES = {
     "ss_op_pool_stack_rows": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i]),
     "ss_op_masked_argmax": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i]),
     "ss_op_ctc_collapse": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "ss_op_masked_argmax_lprob": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ss_op_ctc_collapse_spans": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "ss_op_dur_predict": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
     "ss_op_repeat_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),
     "ss_op_embed_tokens": (_i, [_vp, _vp, _vp, _vp, _f, _i, _vp, _i, _i, _i, _i, _i]),

@@ -14,10 +14,13 @@ batches; each batch runs as one ragged no-padding pack through the ss_batch_* en
 utterance keeps its B = 1 arithmetic).  Sharding mirrors `--num-shards/--shard-id`.
 
 The `score` column of H-/D- is the sum of the per-position maximum log-probabilities in the
-reference (ctc_generator.py:60-91); the HIP path takes the argmax of the logits without ever forming
+reference (ctc_generator.py:60-91); the HIP path takes the argmax of the unit logits without forming
 log-probabilities, so the column is written as 0 and `P-` lines are omitted unless --scores is
 given (then both come from ss_row_max_logprob over the unit logits of the single-utterance entry
-point: one more kernel, no torch arithmetic).  `T-` lines (generate.py:258-259) are written when
+point: one more kernel, no torch arithmetic).  The two TEXT CTC heads do form them on request: `--word-times`
+runs the scored search (ss_batch_ctc_greedy_scored, the arg-max's log-probability from the same read of the row) and writes
+generate-<subset>.asr.words / .st.words, one `id\tword\tstart_ms\tend_ms\tconfidence` line per word (streamspeech_amd/words.py);
+every other file is written as without the flag.  `T-` lines (generate.py:258-259) are written when
 the manifest carries target units (`tgt_audio` column, as the reference's S2UT manifests do).
 
 The first-pass text search is greedy by default; `--beam-mt k` runs the reference's beam search (generator_mt with beam_size_mt = k,
@@ -37,6 +40,7 @@ import torch
 
 from . import frontend
 from .pipeline import units_from_tokens
+from .words import words_from_ctc
 
 
 def detok(symbols: Sequence[str]) -> str:
@@ -69,7 +73,7 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              max_len_b: int = 200, max_len_a_mt: float = 0.0, max_len_b_mt: int = 200, dur_prediction: bool = True, dump_wav: bool = True, t2u_causal: bool = False,
              scores: bool = False, log=None, targets: Optional[Dict[int, Sequence[int]]] = None, beam_mt: int = 1,
              unk_penalty: float = 0.0, normalize: bool = True, pcm16_out: bool = False, speaker_id: int = -1,
-             features: bool = False) -> Dict[int, Dict]:
+             features: bool = False, word_times: bool = False) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
@@ -86,6 +90,7 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     log_f = log or open(os.path.join(results_path, f"generate-{subset}.log"), "w", encoding="utf-8")
     res_f = open(os.path.join(results_path, f"generate-{subset}.txt"), "w", encoding="utf-8")
     hyps: Dict[int, Dict] = {}
+    words: Dict[str, Dict[int, list]] = {"asr": {}, "st": {}}
     if features:
         for sid, f in items:
             if f.dim() != 2 or f.shape[1] != 80 or f.dtype != torch.float32:
@@ -110,8 +115,15 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
             pcm = torch.cat([items[i][1].reshape(-1) for i in group])
             feat, T = model.batch_fbank_cmvn(pcm, [lens[i] for i in group])
         enc, Tp = model.batch_encoder_forward(feat, T)
-        asr = model.batch_ctc_greedy(0, enc, Tp)
-        st = model.batch_ctc_greedy(1, enc, Tp)
+        if word_times:                          # the scored search: the same tokens first in each record, spans and scores behind
+            asr = model.batch_ctc_greedy(0, enc, Tp, return_scores=True)
+            st = model.batch_ctc_greedy(1, enc, Tp, return_scores=True)
+            for b, sid in enumerate(ids):
+                for key, rec, name in (("asr", asr[b], "source_unigram"), ("st", st[b], "ctc_target_unigram")):
+                    words[key][sid] = words_from_ctc(rec[0], rec[1], rec[2], rec[3], dicts[name], finished=True)
+        else:
+            asr = model.batch_ctc_greedy(0, enc, Tp)
+            st = model.batch_ctc_greedy(1, enc, Tp)
         # first-pass text search: max_len = min(int(max_len_a_mt * src_len + max_len_b_mt), max positions - 1) with
         # the task's defaults 0 / 200 (tasks/speech_to_speech_ctc.py:39-40 -> sequence_generator_multi_decoder_ctc.py
         # :130-131); src_len is the fbank frame count.  --max-len-a/-b configure the (NAR) unit generator, which has
@@ -164,6 +176,12 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     if log is None:
         log_f.close()
     _cut_files(hyps, results_path, subset, dump_wav)
+    if word_times:
+        for key in ("asr", "st"):
+            with open(os.path.join(results_path, f"generate-{subset}.{key}.words"), "w", encoding="utf-8") as f:
+                for sid in sorted(words[key]):
+                    for w in words[key][sid]:
+                        print(f"{sid}\t{w.text}\t{w.start_ms}\t{w.end_ms}\t{w.confidence:.6g}", file=f)
     return hyps
 
 
@@ -283,6 +301,8 @@ def build_parser() -> argparse.ArgumentParser:
                          "a random speaker per utterance and logs it; ignored by a single-speaker vocoder")
     ap.add_argument("--no-wav", action="store_true")
     ap.add_argument("--scores", action="store_true")
+    ap.add_argument("--word-times", action="store_true",
+                    help="also write generate-<subset>.asr.words and .st.words: id, word, start_ms, end_ms, confidence per word of the two CTC heads")
     ap.add_argument("--num-shards", type=int, default=int(os.environ.get("WORLD_SIZE", "1")))
     ap.add_argument("--shard-id", type=int, default=int(os.environ.get("RANK", "0")))
     ap.add_argument("--device", default="cuda:%s" % os.environ.get("LOCAL_RANK", "0"))
@@ -391,7 +411,7 @@ def main(argv: Optional[List[str]] = None):
                     getattr(holder.model, "uni_encoder", False), a.scores, targets=targets or None, beam_mt=a.beam_mt,
                     unk_penalty=a.unkpen, normalize=not a.unnormalized,
                     **({"pcm16_out": True} if a.pcm16_io else {}), **({"speaker_id": a.speaker_id} if voc.num_speakers else {}),
-                    **({"features": True} if is_feat else {}))
+                    **({"features": True} if is_feat else {}), **({"word_times": True} if a.word_times else {}))
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
 
 

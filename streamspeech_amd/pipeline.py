@@ -92,3 +92,23 @@ def ctc_collapse_host(ids: List[int], blank: int, pad: int):
             toks.append(v)
             index.append(i)
     return toks, index
+
+
+def ctc_collapse_spans_host(ids: List[int], lprob, blank: int, pad: int):
+    """Host twin of the device span collapse (ctc_collapse_spans_kernel): ctc_collapse_host plus, per kept token, the last frame of
+    its run of equal ids and the float32 sum of `lprob` over the run, added in ascending frame order as the kernel adds it."""
+    import numpy as np
+    lp = np.asarray(lprob, dtype=np.float32)
+    toks, index, last, tok_lp = [], [], [], []
+    T = len(ids)
+    for i, v in enumerate(ids):
+        if (i == 0 or v != ids[i - 1]) and v != blank and v != pad:
+            e, acc = i, lp[i]
+            while e + 1 < T and ids[e + 1] == v:
+                e += 1
+                acc = np.float32(acc + lp[e])
+            toks.append(v)
+            index.append(i)
+            last.append(e)
+            tok_lp.append(acc)
+    return toks, index, last, np.asarray(tok_lp, dtype=np.float32)

@@ -74,8 +74,8 @@ class SpeechSessionPool(TextSessionPool):
     CodeHiFiGANVocoderWithDur, whose .hip is used) every S2ST session synthesises with; without one, S2ST sessions are refused."""
     KINDS = KINDS
 
-    def __init__(self, model, max_sessions: int, max_rows: int, vocoder=None, beam_mt: int = 1):
-        super().__init__(model, max_sessions, max_rows, beam_mt=beam_mt)
+    def __init__(self, model, max_sessions: int, max_rows: int, vocoder=None, beam_mt: int = 1, details: bool = False):
+        super().__init__(model, max_sessions, max_rows, beam_mt=beam_mt, details=details)
         self.vocoder = getattr(vocoder, "hip", vocoder)
         self.t2u_causal = bool(getattr(model, "uni_encoder", False))   # the agent's ctc_generator: t2u_causal = model.uni_encoder
         self._emitter = None                              # pcm.PcmEmitter of the PcmOut sessions, made with the first one's write

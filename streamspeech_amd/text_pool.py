@@ -37,6 +37,7 @@ from . import endpoint as EP
 from .pcm import PcmArena, PcmFormat, PcmOut
 from .simuleval_shim import AgentStates, EmptySegment, TextSegment
 from .text_policy import mt_max_len, s2tt_gate
+from .words import CtcDetails, words_from_ctc
 
 KINDS = ("s2tt", "asr")
 # the text agents' first-pass search: beam 1, max_len_a = 1, max_len_b = 200, min_len = 1 (agent_text.py)
@@ -92,6 +93,7 @@ class _Session:
         self.mp3_chunk = None                 # the mp3.Mp3Chunk parsed by push_mp3 for the next step
         self.mp3_held = 0                     # samples decoded into fe._dev past fe.n_pcm and not released yet (gapless hold-back)
         self.ep = None                        # an endpoint.EndpointState: the pool cuts the session's stream into utterances
+        self.details = None                   # a words.CtcDetails of the last step that encoded the session (pools with details)
         self.reset()
 
     def n_source(self) -> int:
@@ -123,14 +125,17 @@ class TextSessionPool:
     """Up to `max_sessions` concurrent ASR / S2TT sessions, each of at most `max_rows` encoder output rows (~40 ms each)."""
     KINDS = KINDS
 
-    def __init__(self, model, max_sessions: int, max_rows: int, beam_mt: int = 1):
+    def __init__(self, model, max_sessions: int, max_rows: int, beam_mt: int = 1, details: bool = False):
         """beam_mt > 1: the step's one ragged continuation is a beam search behind every writer's committed prefix
-        (HipModel.batch_mt_beam_continue, the agents' --beam-mt); hypothesis 0's tokens and states go on as the greedy ones do."""
+        (HipModel.batch_mt_beam_continue, the agents' --beam-mt); hypothesis 0's tokens and states go on as the greedy ones do.
+        details: the step's one CTC call is the scored form, and details(sid) answers the words of both heads with their time
+        spans, confidences and stability (words.py); the segments the sessions answer are the same either way."""
         if not 1 <= int(beam_mt) <= MT_BEAM_MAX:
             raise ValueError(f"beam_mt {beam_mt} outside [1, {MT_BEAM_MAX}]")
         self.beam_mt = int(beam_mt)
         self.model = model.hip if hasattr(model, "hip") else model
-        self.pool = self.model.stream_pool(max_sessions, max_rows)
+        self.with_details = bool(details)
+        self.pool = self.model.stream_pool(max_sessions, max_rows, scores=True) if details else self.model.stream_pool(max_sessions, max_rows)
         self.max_sessions, self.max_rows = int(max_sessions), int(max_rows)
         self.sessions: Dict[int, _Session] = {}
         self.free = list(range(self.max_sessions))
@@ -210,6 +215,7 @@ class TextSessionPool:
         """The agent's reset(): the session starts a fresh utterance (its slot goes back to the pool until it next has audio)."""
         s = self._get(sid)
         s.reset()
+        s.details = None
         s.pending = False
         s.pcm_chunk = None
         self._release(s)
@@ -224,6 +230,21 @@ class TextSessionPool:
             s.mp3.close()
             s.mp3, s.mp3_state, s.mp3_chunk = None, None, None
         del self.sessions[sid]
+
+    def details(self, sid: int):
+        """The session's words.CtcDetails as of the last step that encoded it: source and target words with start_ms / end_ms on the
+        session's own clock (an endpointed session: the stream's), confidence and `stable`.  None before the first such step, after
+        reset(sid), or in a pool without details."""
+        return self._get(sid).details if self.with_details else None
+
+    def _set_details(self, s: _Session, src, tgt, n_final: int):
+        t0 = 0
+        if s.ep is not None:                  # the utterance's first stream sample (an utterance that ended this step: its own)
+            a = s.ep.utterances[-1]["start"] if s.ep.final else s.ep.utt_start
+            t0 = int(a) * 1000 // s.sr
+        fin = bool(s.states.source_finished)
+        s.details = CtcDetails(*(words_from_ctc(r[0], r[1], r[2], r[3], s.dict[name], n_final=n_final, finished=fin, t0_ms=t0)
+                                 for r, name in ((src, "source_unigram"), (tgt, "target_unigram"))))
 
     def _get(self, sid) -> _Session:
         if sid not in self.sessions:
@@ -641,9 +662,12 @@ class TextSessionPool:
         if enc:
             for s in enc:
                 self._acquire(s)
-            packed, views, _, _ = self.pool.forward([s.slot for s in enc], [feats[s.sid] for s in enc],
-                                                    [s.attn_chunk for s in enc], [s.conv_chunk for s in enc])
-            src, tgt = self.pool.ctc_both()
+            packed, views, n_fin, _ = self.pool.forward([s.slot for s in enc], [feats[s.sid] for s in enc],
+                                                        [s.attn_chunk for s in enc], [s.conv_chunk for s in enc])
+            src, tgt = self.pool.ctc_both()       # (a pool with details: the scored form, records of five)
+            if self.with_details:
+                for i, s in enumerate(enc):
+                    self._set_details(s, src[i], tgt[i], n_fin[i])
             if fed:
                 self._arena.synchronized()        # the CTC read waited for everything queued before it, the arena's upload included
             if fed3:
@@ -708,6 +732,7 @@ class TextSessionPool:
             if s.states.target_finished:          # finished without the agent's reset(): it answers EmptySegment(finished=True)
                 self._release(s)                  # from now on, so its slot goes back; reset(sid) starts a fresh utterance
         self.last_step = {"sessions": len(todo), "encoded": len(enc), "writers": len(writers), "mt_steps": n_steps, "mt_groups": mt_groups,
+                          "ctc_scored": 1 if (enc and self.with_details) else 0,       # the step's CTC call was the scored form
                           "frontend_calls": fe_calls, "fbank_rows": fe_rows,       # front-end device calls of the step, rows they computed
                           # the PCM route: uploads and ss_pcm_scatter launches of the step (0 or 1 each), bytes uploaded; a subclass's
                           # write side sets the pack side (ss_pcm_pack_s16 launches, bytes downloaded)
