@@ -10,7 +10,8 @@
  * too small, 5 SS_ERR_SCRATCH_CAP (ss_scratch_set_cap), 6 SS_ERR_BITSTREAM and 7 SS_ERR_UNSUPPORTED
  * (ss_mp3_*, ss_flac_*), 8 SS_ERR_STREAM_REPEAT (ss_encoder_stream_forward).
  * Additions since ABI 2 was cut (no existing signature changed): ss_flac_streaminfo, ss_flac_probe, ss_flac_unpack,
- * ss_flac_restore_host, ss_flac_restore (FLAC ingest) and ss_batch_cmvn (precomputed fbank rows).
+ * ss_flac_restore_host, ss_flac_restore (FLAC ingest), ss_batch_cmvn (precomputed fbank rows), ss_batch_mt_attention and
+ * ss_op_attention_probs (cross-attention of the first-pass text decoder).
  *
  * Weight ownership: the caller owns one packed FP32 weight blob in HBM (built once from a fairseq
  * state dict by streamspeech_amd/weights.py) and lends it to ss_model_create(); the library keeps
@@ -867,6 +868,20 @@ int ss_batch_t2u_units_pad(ss_model* m, void* stream, int B, const float* d_feat
  * gets the post-LN state of every fed position -- per row what ss_mt_truncate + ss_mt_append(..., n_tail_pad) give.  No search. */
 int ss_batch_mt_features(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp, const int32_t* h_tokens,
                          const int32_t* h_n_tokens, const int32_t* h_n_tail_pad, float* d_feats, int feat_rows);
+/* ss_batch_mt_features' pass with n_tail_pad = 0 (row b feeds [</s>, tokens_b...]) plus the head-averaged cross-attention of the
+ * LAST decoder layer over the fed positions h_first[b] .. h_n_tokens[b] of every row (h_first NULL: 0 for every row; 0 <= h_first[b] <=
+ * h_n_tokens[b]): what fairseq returns as a hypothesis' "attention" (agent/sequence_generator.py:383-392; position p is the decoder
+ * input that predicts token p).  Row b answers n_b = h_n_tokens[b] + 1 - h_first[b] positions; R = sum n_b.
+ *   d_attn (may be NULL): row b's [n_b][h_Tp[b]] probabilities at float offset h_attn_off[b] (an OUTPUT, host, [B], may be NULL, written only
+ *     when d_attn is given and only once no refusal can follow: the blocks are packed in row order); attn_capacity = the floats d_attn holds.
+ *   d_peak [R] int32: the arg-max source frame of every answered position (lowest index of a tie); d_stat [R][2] = {its probability,
+ *     sum_j j * P[j]}; both packed in row order.
+ *   d_feats (may be NULL): [B][feat_rows][D], exactly the bits ss_batch_mt_features writes for the same rows.
+ * Checks and error codes of ss_batch_mt_features, SS_ERR_CAPACITY also for attn_capacity; nothing is queued before every check and
+ * every buffer is made.  Rewrites the scratch set's MT cross-attention K/V (as ss_batch_mt_features does).  Pack-invariant. */
+int ss_batch_mt_attention(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp, const int32_t* h_tokens,
+                          const int32_t* h_n_tokens, const int32_t* h_first, float* d_feats, int feat_rows, float* d_attn,
+                          int64_t* h_attn_off, int64_t attn_capacity, int32_t* d_peak, float* d_stat);
 /* B rows of the S2ST agent's receptive-field vocoder tail: row b has h_K[b] units (packed in d_codes), the last h_n_new[b] new.  With
  * h_ctx[b] > 0 and h_K[b] > n_new + ctx only the last n_new + ctx units are synthesised, unless the durations of context units
  * [2, ctx) cover fewer than h_rf[b] + 2 frames -- then all units are.  Only the new units' samples are written: d_out[h_out_start[b]
@@ -1070,6 +1085,21 @@ typedef struct ss_op_attn_args {
   int32_t use_split;
 } ss_op_attn_args;
 int ss_op_attention_ex(void* stream, const ss_op_attn_args* a);
+/* The head-averaged attention probabilities kernel (csrc/attn_probs.hpp, AttnProbsArgs field for field; all DEVICE pointers):
+ * segs as above, of segment s the query rows q_first[s] .. q_len - 1 are answered; answered row i is output row o = row_off[s] + i -
+ * q_first[s]: P[p_off[s] + (i - q_first[s]) * k_len + j] = mean over the H heads of softmax_j(scale * q_i . k_j) (P may be NULL),
+ * peak[o] = its arg-max (lowest j of a tie), stat[2 o] = P[i][peak], stat[2 o + 1] = sum_j j * P[i][j].  max_rows = the most answered
+ * rows of a segment.  Returns what launch_attention_probs returns.  tests/test_mt_attention_gpu.py against tests/mt_attention_ref.py. */
+typedef struct ss_op_attn_probs_args {
+  const float* Q; const float* K;
+  int32_t ldq, ldk, H;
+  float scale;
+  const int32_t* segs; int32_t nseg;
+  const int32_t* q_first; const int32_t* row_off; const int64_t* p_off;
+  float* P; int32_t* peak; float* stat;
+  int32_t max_rows;
+} ss_op_attn_probs_args;
+int ss_op_attention_probs(void* stream, const ss_op_attn_probs_args* a);
 /* The tail-query attention of the concurrent streaming step (PoolAttnArgs, csrc/attention.hpp), field for field; returns what
  * launch_attention_pool returns. */
 typedef struct ss_op_pool_attn_args {

@@ -112,6 +112,30 @@ def _beam_kwargs(args) -> dict:
     return {"unk_penalty": float(getattr(args, "unkpen", 0.0))}
 
 
+
+def mt_alignment_update(agent, enc, tokens, t0_ms=0):
+    """--mt-alignment: `tokens` are all committed target tokens (no </s>) after a write of policy(), `enc` the encoder rows that write
+    saw.  The words of the tokens this write added are placed in source time by ONE batch_mt_attention pass that answers only their
+    positions (first = the tokens placed before), over `enc` -- what the decoder attended to when it produced them, and what the
+    reference records -- and are then frozen: a later write adds words, it never changes one.  agent.alignment = all of them.
+    The pass rewrites the scratch set's MT cross-attention K/V and workspace, so the callers issue it where the search has returned
+    and no single-utterance MT state is needed any more.  (Should a whole-word cut ever shorten the committed tokens, the words that
+    reached past the cut are dropped and placed again.)"""
+    from .words import words_from_attention
+    tokens = [int(t) for t in tokens]
+    rec = agent._mt_align
+    while rec and rec[-1][0] > len(tokens):
+        rec.pop()
+    done = rec[-1][0] if rec else 0
+    if len(tokens) > done:
+        enc = (enc[:, 0] if enc.dim() == 3 else enc).contiguous()
+        _, peak, prob, _, _ = agent.engine.batch_mt_attention(enc, [int(enc.shape[0])], [tokens[:-1]], first=[done], want_matrix=False)[0]
+        words = words_from_attention(tokens[done:], peak.tolist(), prob.tolist(), agent.generator_mt.tgt_dict, t0_ms=t0_ms,
+                                     eos=agent.generator_mt.eos)
+        rec.append((len(tokens), words))
+    agent.alignment = [w for _, ws in rec for w in ws]
+
+
 @entrypoint
 class StreamSpeechS2STAgent(SpeechToSpeechAgent):
     """Simultaneous speech-to-speech translation agent for StreamSpeech on the HIP backend."""
@@ -229,12 +253,19 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
         a("--word-details", action="store_true", default=False,
           help="after every policy() that ran the encoder, agent.details holds the words of both CTC heads with their time spans, "
                "confidences and stability (streamspeech_amd/words.py); default: off, the heads run exactly as without the flag")
+        a("--mt-alignment", action="store_true", default=False,
+          help="after every policy() that wrote, agent.alignment holds the words of all committed target tokens (the text decoder's, "
+               "which the S2TT agent prints and the S2ST path speaks) with the source time span the decoder's cross-attention "
+               "points at (streamspeech_amd/words.py AlignedWord); one extra decoder pass per write; default: off, every launch "
+               "and every output as without the flag")
         a("--extra-output-dir", type=str, default=None, help="extra output dir")
         a("--output-asr-translation", type=bool, default=False, help="extra output dir")
 
     details = None      # --word-details: the words.CtcDetails of the last policy() that ran the encoder
+    alignment = None    # --mt-alignment: the words.AlignedWord list of all committed target tokens, after the last policy() that wrote
 
     def reset(self):
+        self._mt_align = []     # --mt-alignment: (committed tokens placed so far, the words of one write), frozen
         self.src_seg_num = 0
         self.tgt_subwords_indices = None
         self.src_ctc_indices = None
@@ -431,6 +462,8 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
                                             want_next=False, n_tail_pad=1)
                 mt_feats = torch.cat((mt_feats, pad_feat), 0)
         self.mt_decoder_out = mt_feats
+        if getattr(self.args, "mt_alignment", False):      # the search and the tail-pad append are done: the MT state is not needed any more
+            mt_alignment_update(self, self.encoder_outs[0]["encoder_out"][0], tmp)
 
         # 2+3. T2U encoder + CTC unit decoder + CTC search (agent :661-689)
         finalized = self.ctc_generator.generate(mt_feats, prefix=self.tgt_units_indices, n_tail_pad=n_tail_pad)

@@ -6,7 +6,7 @@ agent/speech_to_text.s2tt.streamspeech.agent.py:381-545 (same flags as the S2ST 
 vocoder ones)."""
 import torch
 
-from .agent import StreamSpeechS2STAgent, _beam_kwargs, _detok, word_details
+from .agent import StreamSpeechS2STAgent, _beam_kwargs, _detok, mt_alignment_update, word_details
 from .frontend import OnlineFeatureExtractor  # noqa: F401  (re-exported for parity with the reference files)
 from .generators import CTCDecoder, SequenceGenerator
 from .simuleval_shim import ReadAction, SpeechToTextAgent, WriteAction, entrypoint
@@ -52,6 +52,7 @@ class _TextAgentBase(SpeechToTextAgent):
 
     add_args = staticmethod(_add_text_args)
     details = None      # --word-details: the words.CtcDetails of the last policy() that ran the encoder
+    alignment = None    # --mt-alignment: the words.AlignedWord list of all committed target tokens, after the last policy() that wrote
 
     def _ctc_hyps(self, enc):
         """The two CTC hypotheses of policy(); with --word-details the scored form, and agent.details from them."""
@@ -63,6 +64,7 @@ class _TextAgentBase(SpeechToTextAgent):
         return src, tgt
 
     def reset(self):
+        self._mt_align = []     # --mt-alignment: (committed tokens placed so far, the words of one write), frozen
         self.tgt_subwords_indices = None
         self.src_ctc_prefix_length = 0
         self.tgt_ctc_prefix_length = 0
@@ -87,6 +89,11 @@ class _TextAgentBase(SpeechToTextAgent):
 @entrypoint
 class StreamSpeechASRAgent(_TextAgentBase):
     """Streaming ASR: encoder + source_unigram CTC greedy, emits the newly confirmed subwords."""
+
+    def __init__(self, args, model=None):
+        if getattr(args, "mt_alignment", False):
+            raise ValueError("--mt-alignment needs the first-pass text search; the ASR agent has none")
+        super().__init__(args, model)
 
     @torch.inference_mode()
     def policy(self):
@@ -142,6 +149,8 @@ class StreamSpeechS2TTAgent(_TextAgentBase):
         if self.tgt_subwords_indices is not None and torch.equal(self.tgt_subwords_indices, tgt_subwords_indices):
             return WriteAction("", finished=True) if self.states.source_finished else ReadAction()
         self.tgt_subwords_indices = tgt_subwords_indices
+        if getattr(self.args, "mt_alignment", False):      # the search has returned: nothing reads the MT scratch any more
+            mt_alignment_update(self, enc["encoder_out"][0], tgt_subwords_indices[0].tolist())
         text = " ".join(tokens)
         new_text = text[len(self.tgt_text):]
         self.tgt_text = text

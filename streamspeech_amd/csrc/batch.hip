@@ -610,38 +610,50 @@ extern "C" int ss_batch_mt_continue(ss_model* m, void* stream, int B, const floa
   return SS_OK;
 }
 
-// Decoder states of B fed rows in ONE ragged pass (the MT features the S2ST write path hands to T2U): row b feeds [</s>, tokens_b...,
-// <pad> x n_tail_pad_b] over its encoder rows and gets the post-LN state of every position, as ss_mt_truncate + ss_mt_append(...,
-// n_tail_pad) give them for one utterance: the trailing <pad> positions take the padding position and are masked as self-attention
-// keys.  Nothing is projected onto the vocabulary.  d_feats [B][feat_rows][D]: row b's 1 + n_tokens_b + n_tail_pad_b states.
-extern "C" int ss_batch_mt_features(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp,
-                                    const int32_t* h_tokens, const int32_t* h_n_tokens, const int32_t* h_n_tail_pad, float* d_feats,
-                                    int feat_rows) {
-  if (!m || B <= 0 || B > 256 || !d_enc_out || !h_Tp || !h_n_tokens || !h_n_tail_pad || !d_feats || feat_rows <= 0) return SS_ERR_ARG;
+// The optional second answer of the pass below (ss_batch_mt_attention): the head-averaged cross-attention of the last layer.
+struct MtAttnOut {
+  const int32_t* h_first = nullptr;      // may be null: 0 for every row
+  float* d_attn = nullptr; int64_t* h_attn_off = nullptr; int64_t attn_capacity = 0;
+  int32_t* d_peak = nullptr; float* d_stat = nullptr;
+};
+
+// ss_batch_mt_features (ao == nullptr: its launches exactly) and ss_batch_mt_attention (n_tail_pad == nullptr: no trailing <pad>).
+static int batch_mt_features(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp, const int32_t* h_tokens,
+                             const int32_t* h_n_tokens, const int32_t* h_n_tail_pad, float* d_feats, int feat_rows,
+                             const MtAttnOut* ao) {
+  if (!m || B <= 0 || B > 256 || !d_enc_out || !h_Tp || !h_n_tokens) return SS_ERR_ARG;
+  if (ao ? (!ao->d_peak || !ao->d_stat) : (!h_n_tail_pad || !d_feats)) return SS_ERR_ARG;
+  if (d_feats && feat_rows <= 0) return SS_ERR_ARG;
   const ss_config& c = m->cfg;
   const int D = c.dec_dim, F = c.dec_ffn;
+  if (ao && (c.dec_heads > ATTN_PROBS_MAX_H || c.mt_layers <= 0 || !m->mt[c.mt_layers - 1].has_cross)) return SS_ERR_ARG;
   std::vector<int> seg_len(B);
   int tok_total = 0;
   for (int b = 0; b < B; ++b) {
-    if (h_Tp[b] <= 0 || h_n_tokens[b] < 0 || h_n_tail_pad[b] < 0) return SS_ERR_ARG;
+    const int pad_b = h_n_tail_pad ? h_n_tail_pad[b] : 0;
+    if (h_Tp[b] <= 0 || h_n_tokens[b] < 0 || pad_b < 0) return SS_ERR_ARG;
     if (h_n_tokens[b] > 0 && !h_tokens) return SS_ERR_ARG;
+    if (ao && ao->h_first && (ao->h_first[b] < 0 || ao->h_first[b] > h_n_tokens[b])) return SS_ERR_ARG;
     for (int i = 0; i < h_n_tokens[b]; ++i)
       if (h_tokens[tok_total + i] < 0 || h_tokens[tok_total + i] >= c.tgt_vocab) return SS_ERR_ARG;   // nn.Embedding's IndexError
     tok_total += h_n_tokens[b];
-    seg_len[b] = 1 + h_n_tokens[b] + h_n_tail_pad[b];
-    if (seg_len[b] > feat_rows || seg_len[b] + 2 > c.max_tgt_pos) return SS_ERR_CAPACITY;   // ss_mt_append's position bound
+    seg_len[b] = 1 + h_n_tokens[b] + pad_b;
+    if ((d_feats && seg_len[b] > feat_rows) || seg_len[b] + 2 > c.max_tgt_pos) return SS_ERR_CAPACITY;   // ss_mt_append's position bound
   }
   const Offsets oe = prefix(h_Tp, B), op = prefix(seg_len.data(), B);
   const int Np = op.total;
   const size_t np = (size_t)Np;
   // int tables: self segs [4B] | cross segs [4B] | self tail [B] | tokens [Np] | positions [Np] | feature rows [Np]
-  std::vector<int> tab(9 * (size_t)B + 3 * np);
+  //             (+ with ao: first answered row [B] | output row [B] | padding to 8 bytes | offsets into d_attn [B] int64)
+  const size_t n_base = 9 * (size_t)B + 3 * np;
+  const size_t n_off = ao ? ((n_base + 2 * (size_t)B + 1) & ~(size_t)1) : n_base;
+  std::vector<int> tab(ao ? n_off + 2 * (size_t)B : n_base);
   int* ps = tab.data(); int* pc = ps + 4 * B; int* pt = pc + 4 * B; int* tk = pt + B; int* pp = tk + np; int* pf = pp + np;
   for (int b = 0, o = 0; b < B; ++b) {
     const int r0 = op.off[b], n = seg_len[b], nt = h_n_tokens[b];
     ps[4 * b] = r0; ps[4 * b + 1] = n; ps[4 * b + 2] = r0; ps[4 * b + 3] = n;
     pc[4 * b] = r0; pc[4 * b + 1] = n; pc[4 * b + 2] = oe.off[b]; pc[4 * b + 3] = h_Tp[b];
-    pt[b] = h_n_tail_pad[b];
+    pt[b] = h_n_tail_pad ? h_n_tail_pad[b] : 0;
     for (int p = 0; p < n; ++p) {
       tk[r0 + p] = p == 0 ? c.eos : p <= nt ? h_tokens[o + p - 1] : c.pad;
       pp[r0 + p] = p;
@@ -649,10 +661,27 @@ extern "C" int ss_batch_mt_features(ss_model* m, void* stream, int B, const floa
     }
     o += nt;
   }
+  int max_rows = 0;
+  if (ao) {
+    int* qf = tab.data() + n_base; int* ro = qf + B;
+    int rows = 0;
+    int64_t off = 0;
+    for (int b = 0; b < B; ++b) {
+      qf[b] = ao->h_first ? ao->h_first[b] : 0;
+      ro[b] = rows;
+      const int n = seg_len[b] - qf[b];
+      std::memcpy(tab.data() + n_off + 2 * (size_t)b, &off, sizeof(off));
+      rows += n; max_rows = std::max(max_rows, n);
+      off += (int64_t)n * h_Tp[b];
+    }
+    if (ao->d_attn && off > ao->attn_capacity) return SS_ERR_CAPACITY;
+  }
   // ---- every buffer first: a scratch cap refuses the call before anything is queued ----
   RET(m->sc->mt_cross.ensure((size_t)c.mt_layers * oe.total * 2 * D * sizeof(float)));
   RET(m->sc->ws.ensure((np * (7 * D + F)) * sizeof(float)));
   RET(m->sc->seg_buf.ensure(tab.size() * sizeof(int)));
+  if (ao && ao->d_attn && ao->h_attn_off)          // the one host output, after the last refusal
+    for (int b = 0; b < B; ++b) std::memcpy(&ao->h_attn_off[b], tab.data() + n_off + 2 * (size_t)b, sizeof(int64_t));
   SkScope sk_scope(m->sc->skws);
   CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
   hipStream_t s = (hipStream_t)stream;
@@ -664,7 +693,43 @@ extern "C" int ss_batch_mt_features(ss_model* m, void* stream, int B, const floa
                m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D, 2 * D));
   const float* pfo = nullptr;
   RET(mt_prefix_pass(m, s, B, Np, op.mx, oe.total, d_tok, d_pos, d_self, d_cross, d_tail, nullptr, 0, &pfo));
-  return launch_scatter_rows(d_frow, pfo, D, d_feats, D, D, Np, B * feat_rows, s);
+  if (d_feats) RET(launch_scatter_rows(d_frow, pfo, D, d_feats, D, D, Np, B * feat_rows, s));
+  if (!ao) return SS_OK;
+  // the last layer's cross-attention Q is still in the pass's q2 rows (mt_prefix_pass: x | h | q2 | ...; nothing after a layer's
+  // cross-attention writes them), its K in the last slice of mt_cross
+  AttnProbsArgs ap;
+  ap.Q = m->sc->ws.f() + 2 * np * D; ap.ldq = D;
+  ap.K = m->sc->mt_cross.f() + (size_t)(c.mt_layers - 1) * oe.total * 2 * D; ap.ldk = 2 * D;
+  ap.H = c.dec_heads; ap.scale = 1.f;                                   // q is pre-scaled at pack time
+  ap.segs = d_cross; ap.nseg = B;
+  ap.q_first = dt + n_base; ap.row_off = dt + n_base + B;
+  ap.p_off = reinterpret_cast<const long long*>(dt + n_off);
+  ap.P = ao->d_attn; ap.peak = ao->d_peak; ap.stat = ao->d_stat; ap.max_rows = max_rows;
+  return launch_attention_probs(ap, s);
+}
+
+// Decoder states of B fed rows in ONE ragged pass (the MT features the S2ST write path hands to T2U): row b feeds [</s>, tokens_b...,
+// <pad> x n_tail_pad_b] over its encoder rows and gets the post-LN state of every position, as ss_mt_truncate + ss_mt_append(...,
+// n_tail_pad) give them for one utterance: the trailing <pad> positions take the padding position and are masked as self-attention
+// keys.  Nothing is projected onto the vocabulary.  d_feats [B][feat_rows][D]: row b's 1 + n_tokens_b + n_tail_pad_b states.
+extern "C" int ss_batch_mt_features(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp,
+                                    const int32_t* h_tokens, const int32_t* h_n_tokens, const int32_t* h_n_tail_pad, float* d_feats,
+                                    int feat_rows) {
+  if (!h_n_tail_pad || !d_feats) return SS_ERR_ARG;
+  return batch_mt_features(m, stream, B, d_enc_out, h_Tp, h_tokens, h_n_tokens, h_n_tail_pad, d_feats, feat_rows, nullptr);
+}
+
+// The same pass without trailing <pad>, answering the head-averaged cross-attention of the last decoder layer over the fed positions
+// h_first[b] .. n_tokens_b of every row (attn_probs.hip); d_feats optional (the bits ss_batch_mt_features writes).
+extern "C" int ss_batch_mt_attention(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp,
+                                     const int32_t* h_tokens, const int32_t* h_n_tokens, const int32_t* h_first, float* d_feats,
+                                     int feat_rows, float* d_attn, int64_t* h_attn_off, int64_t attn_capacity, int32_t* d_peak,
+                                     float* d_stat) {
+  if (!d_peak || !d_stat || attn_capacity < 0) return SS_ERR_ARG;
+  MtAttnOut ao;
+  ao.h_first = h_first; ao.d_attn = d_attn; ao.h_attn_off = h_attn_off; ao.attn_capacity = attn_capacity;
+  ao.d_peak = d_peak; ao.d_stat = d_stat;
+  return batch_mt_features(m, stream, B, d_enc_out, h_Tp, h_tokens, h_n_tokens, nullptr, d_feats, feat_rows, &ao);
 }
 
 // New fbank rows of many streaming sessions in ONE launch (the batched front-end of the text session pool): session b's frames

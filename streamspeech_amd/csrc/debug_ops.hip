@@ -289,6 +289,16 @@ extern "C" int ss_op_attention_ex(void* stream, const ss_op_attn_args* x) {
   return launch_attention(a, (hipStream_t)stream);
 }
 
+extern "C" int ss_op_attention_probs(void* stream, const ss_op_attn_probs_args* x) {
+  if (!x) return SS_ERR_ARG;
+  AttnProbsArgs a;
+  a.Q = x->Q; a.K = x->K; a.ldq = x->ldq; a.ldk = x->ldk; a.H = x->H; a.scale = x->scale;
+  a.segs = x->segs; a.nseg = x->nseg; a.q_first = x->q_first; a.row_off = x->row_off;
+  a.p_off = reinterpret_cast<const long long*>(x->p_off);
+  a.P = x->P; a.peak = x->peak; a.stat = x->stat; a.max_rows = x->max_rows;
+  return launch_attention_probs(a, (hipStream_t)stream);
+}
+
 extern "C" int ss_op_attention_pool(void* stream, const ss_op_pool_attn_args* x) {
   if (!x) return SS_ERR_ARG;
   PoolAttnArgs a;

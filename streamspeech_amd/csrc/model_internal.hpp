@@ -17,6 +17,7 @@
 
 #include "../../include/streamspeech_hip.h"
 #include "attention.hpp"
+#include "attn_probs.hpp"
 #include "common.hpp"
 #include "elementwise.hpp"
 #include "fbank.hpp"

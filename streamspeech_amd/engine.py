@@ -401,6 +401,51 @@ class BatchMixin:
                 "ss_batch_mt_features")
         return [feats[b, :n[b]] for b in range(B)]
 
+    def batch_mt_attention(self, enc_packed: torch.Tensor, Tp: List[int], tokens: List[List[int]], first: Optional[List[int]] = None,
+                           want_matrix: bool = True, want_feats: bool = False):
+        """Head-averaged cross-attention of the last MT decoder layer in one ragged teacher-forced pass (ss_batch_mt_attention): row b
+        feeds [</s>, tokens[b]...] over its encoder rows (packed as batch_mt_continue takes them) and answers the fed positions
+        first[b] .. len(tokens[b]) (position p is the decoder input that predicts token p; first None: every position).
+        -> per row ``(attn, peak, peak_prob, mean_pos, feats)``: attn float32 [rows, Tp[b]] on the host (None without want_matrix:
+        nothing of that size is written or copied), peak int32 [rows] the arg-max source frame of every position, peak_prob float32
+        [rows] its probability, mean_pos float32 [rows] = sum_j j * attn[., j]; feats (want_feats) the post-LN decoder states
+        [1 + len(tokens[b]), D] on the device, the bits batch_mt_features(..., n_tail_pad = 0) gives, else None.  One device-to-host
+        copy per call.  Rewrites the scratch set's MT cross-attention K/V and workspace, as batch_mt_features does."""
+        B = len(Tp)
+        if len(tokens) != B or B == 0 or (first is not None and len(first) != B):
+            raise ValueError("one token list (and one first position) per row")
+        first = [0] * B if first is None else [int(f) for f in first]
+        n_tok = [len(t) for t in tokens]
+        rows = [n_tok[b] + 1 - first[b] for b in range(B)]
+        if any(r <= 0 for r in rows) or any(f < 0 for f in first):
+            raise ValueError("first[b] must lie in [0, len(tokens[b])]")
+        R = sum(rows)
+        n_attn = sum(r * int(t) for r, t in zip(rows, Tp)) if want_matrix else 0
+        # one buffer, one copy: attn | stat [R][2] | peak [R] (int32 bits)
+        buf = torch.empty((n_attn + 3 * R,), dtype=torch.float32, device=self.device)
+        d_attn, d_stat, d_peak = buf[:n_attn], buf[n_attn:n_attn + 2 * R], buf[n_attn + 2 * R:]
+        feats, frows = None, 0
+        if want_feats:
+            frows = max(n_tok) + 1
+            feats = torch.empty((B, frows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
+        off = (C.c_int64 * B)()
+        flat = [int(t) for ts in tokens for t in ts]
+        L.check(self.lib.ss_batch_mt_attention(self.h, _stream(), B, _ptr(enc_packed), _i32(Tp), _i32(flat or [0]), _i32(n_tok),
+                                               _i32(first), _ptr(feats) if want_feats else None, frows,
+                                               _ptr(d_attn) if want_matrix else None, off, n_attn, _ptr(d_peak), _ptr(d_stat)),
+                "ss_batch_mt_attention")
+        host = buf.cpu()
+        stat = host[n_attn:n_attn + 2 * R].view(R, 2)
+        peak = host[n_attn + 2 * R:].view(torch.int32)
+        out, r0 = [], 0
+        for b in range(B):
+            n = rows[b]
+            attn = host[int(off[b]):int(off[b]) + n * int(Tp[b])].view(n, int(Tp[b])) if want_matrix else None
+            out.append((attn, peak[r0:r0 + n], stat[r0:r0 + n, 0], stat[r0:r0 + n, 1],
+                        feats[b, :n_tok[b] + 1] if want_feats else None))
+            r0 += n
+        return out
+
 
 class Scratch:
     """One scratch set (ss_scratch: activations, KV caches, stream-K hand-off state, streaming-encoder state) -- everything a call

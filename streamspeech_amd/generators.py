@@ -85,10 +85,20 @@ class SequenceGenerator:
     beam_size > 1: a beam search behind the forced prefix with the semantics of the OFFLINE generator's ``prefix_tokens``
     (unity/sequence_generator.py with fairseq's ``_prefix_tokens``: one live hypothesis after the prefix, scores and length
     normalisation count the prefix), on the engine's ``batch_mt_beam_continue``.  The agents' own generator pre-fills the prefix and
-    ranks k identical rows at the first free step, which is defined only at beam 1; that is the path above and it is unchanged."""
+    ranks k identical rows at the first free step, which is defined only at beam 1; that is the path above and it is unchanged.
+
+    want_attention: hypothesis 0 also carries what the reference's generator records (agent/sequence_generator.py:383-392, fairseq's
+    finalize_hypos): ``"attention"``, float32 [src_len, tgt_len], the head-averaged cross-attention of the last decoder layer --
+    column p is the decoder position that predicted token p -- and ``"alignment"``, fairseq's hard alignment, an int tensor
+    [tgt_len, 2] of (arg-max source frame, target index) pairs.  Both come from ONE teacher-forced pass over the hypothesis' own
+    tokens after the search (engine.batch_mt_attention), on every route; the search itself launches what it launches without the
+    switch.  With a forced prefix the prefix columns are those of that pass (the reference's agent generator leaves them
+    uninitialised).  Hypotheses 1.. of a beam keep ``None`` in both fields.  The pass rewrites the scratch set's MT cross-attention
+    K/V: a single-utterance MT state begun with mt_begin is not live after it."""
 
     def __init__(self, engine, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, max_len=0, min_len=1,
-                 eos=None, use_incremental_states=False, unk_penalty=0.0, normalize_scores=True, **kw):
+                 eos=None, use_incremental_states=False, unk_penalty=0.0, normalize_scores=True, want_attention=False, **kw):
+        self.want_attention = bool(want_attention)
         if not 1 <= int(beam_size) <= 32:
             raise ValueError(f"beam_size {beam_size} outside [1, 32]")
         self.beam_size, self.unk_penalty, self.normalize_scores = int(beam_size), float(unk_penalty), bool(normalize_scores)
@@ -102,6 +112,13 @@ class SequenceGenerator:
 
     def reset_incremental_states(self):
         self.incremental_states = None
+
+    def _attach_attention(self, enc, hyp):
+        """The two attention fields of a finished hypothesis: its L tokens end in </s>, the L - 1 before it are fed."""
+        toks = [int(t) for t in hyp["tokens"].tolist()]
+        attn, peak, _, _, _ = self.engine.batch_mt_attention(enc, [int(enc.shape[0])], [toks[:-1]])[0]
+        hyp["attention"] = attn.t().contiguous()
+        hyp["alignment"] = torch.stack([peak.to(torch.int64), torch.arange(len(toks), dtype=torch.int64)], 1)
 
     @torch.no_grad()
     def generate_decoder(self, encoder_outs, src_tokens, src_lengths, sample=None, prefix_tokens=None,
@@ -122,12 +139,19 @@ class SequenceGenerator:
                      "alignment": None, "positional_scores": torch.tensor(h["positional_scores"], dtype=torch.float32)}
                     for h in nbest[0]]
             hyps[0]["features"] = feats[0]
+            if self.want_attention:
+                self._attach_attention(enc, hyps[0])
             return [hyps]
         if hasattr(eng, "mt_greedy"):
-            out, feats = eng.mt_greedy(enc.contiguous(), prefix, max_len, self.min_len)
-            return [[{"tokens": torch.tensor(prefix + out, dtype=torch.long), "features": feats, "score": None,
-                      "attention": None, "alignment": None, "positional_scores": None}]]
-        eng.mt_begin(enc.contiguous())
+            enc = enc.contiguous()
+            out, feats = eng.mt_greedy(enc, prefix, max_len, self.min_len)
+            hyp = {"tokens": torch.tensor(prefix + out, dtype=torch.long), "features": feats, "score": None,
+                   "attention": None, "alignment": None, "positional_scores": None}
+            if self.want_attention:
+                self._attach_attention(enc, hyp)
+            return [[hyp]]
+        enc = enc.contiguous()
+        eng.mt_begin(enc)
         feats_all = []
         feats, nxt = eng.mt_append([self.eos] + prefix, 0, ban_eos=(start < self.min_len), force_eos=(start >= max_len))
         feats_all.append(feats)
@@ -141,5 +165,8 @@ class SequenceGenerator:
         tokens = torch.tensor(prefix + out, dtype=torch.long)
         # features for positions [eos, prefix..., generated minus the last]: what the reference
         # recomputes via mt_decoder(prev_output_tokens_mt, features_only=True) (agent :638-642)
-        return [[{"tokens": tokens, "features": torch.cat(feats_all, 0), "score": None, "attention": None,
-                  "alignment": None, "positional_scores": None}]]
+        hyp = {"tokens": tokens, "features": torch.cat(feats_all, 0), "score": None, "attention": None,
+               "alignment": None, "positional_scores": None}
+        if self.want_attention:     # after the loop: the single-utterance MT state is no longer needed
+            self._attach_attention(enc, hyp)
+        return [[hyp]]

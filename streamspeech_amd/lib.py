@@ -106,6 +106,18 @@ class SSOpPoolAttnArgs(C.Structure):
         ("nsess", C.c_int32), ("qtiles", C.c_int32), ("H", C.c_int32),
         ("scale", _f)]
 
+class SSOpAttnProbsArgs(C.Structure):
+    """ss_op_attn_probs_args: AttnProbsArgs (csrc/attn_probs.hpp) field for field, pointers as device addresses."""
+    _fields_ = [
+        ("Q", _vp), ("K", _vp),
+        ("ldq", C.c_int32), ("ldk", C.c_int32), ("H", C.c_int32),
+        ("scale", _f),
+        ("segs", _vp), ("nseg", C.c_int32),
+        ("q_first", _vp), ("row_off", _vp), ("p_off", _vp),
+        ("P", _vp), ("peak", _vp), ("stat", _vp),
+        ("max_rows", C.c_int32)]
+
+
 class SSOpBeamState(C.Structure):
     """ss_op_beam_state: BeamState (csrc/beam.hip) field for field, pointers as device addresses."""
     _fields_ = [(n, _vp) for n in (
@@ -240,6 +252,8 @@ SIGNATURES = {
     "ss_batch_t2u_units_pad": (_i, [_vp, _vp, _i, _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp]),
     "ss_batch_mt_features": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), _vp, _i]),
+    "ss_batch_mt_attention": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32), _vp, _i, _vp, C.POINTER(_i64), _i64, _vp, _vp]),
     "ss_batch_vocoder_tail": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int32), _i, _vp, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(_i64), C.POINTER(_i64)]),
@@ -278,6 +292,7 @@ SIGNATURES = {
     "ss_op_layernorm": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _f]),
     "ss_op_attention": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _i, _vp, _vp]),
     "ss_op_attention_ex": (_i, [_vp, C.POINTER(SSOpAttnArgs)]),
+    "ss_op_attention_probs": (_i, [_vp, C.POINTER(SSOpAttnProbsArgs)]),
     "ss_op_attention_pool": (_i, [_vp, C.POINTER(SSOpPoolAttnArgs)]),
     "ss_debug_attention_no_mfma": (_i, [_i]),
     "ss_op_dwconv_bn_silu": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _i]),

@@ -40,7 +40,7 @@ import torch
 
 from . import frontend
 from .pipeline import units_from_tokens
-from .words import words_from_ctc
+from .words import words_from_attention, words_from_ctc
 
 
 def detok(symbols: Sequence[str]) -> str:
@@ -73,7 +73,7 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              max_len_b: int = 200, max_len_a_mt: float = 0.0, max_len_b_mt: int = 200, dur_prediction: bool = True, dump_wav: bool = True, t2u_causal: bool = False,
              scores: bool = False, log=None, targets: Optional[Dict[int, Sequence[int]]] = None, beam_mt: int = 1,
              unk_penalty: float = 0.0, normalize: bool = True, pcm16_out: bool = False, speaker_id: int = -1,
-             features: bool = False, word_times: bool = False) -> Dict[int, Dict]:
+             features: bool = False, word_times: bool = False, mt_alignment: bool = False) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
@@ -81,7 +81,10 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     pcm16_out (--pcm16-io): the waveforms of a batch become 16-bit PCM on the device (one ss_pcm_pack_s16, one download per batch)
     and pred_wav/ is written from those bytes -- the same files, without a float download and a host rounding per utterance.
     speaker_id (--speaker-id; multi-speaker vocoders only): the voice of every utterance; -1 draws one per utterance with
-    random.randint(0, num_speakers - 1) like generate_waveform_from_code.py:69-75 and records it in the log (`K-<id>` lines)."""
+    random.randint(0, num_speakers - 1) like generate_waveform_from_code.py:69-75 and records it in the log (`K-<id>` lines).
+    mt_alignment (--mt-alignment): also writes generate-<subset>.mt.words, the words of every `D-` hypothesis placed in source time by
+    the text decoder's cross-attention (words.words_from_attention), from one batch_mt_attention per batch after its search; every
+    other file is the one written without it."""
     n_spk = int(getattr(vocoder, "num_speakers", 0) or 0)
     if n_spk and not -1 <= speaker_id < n_spk:
         raise ValueError(f"--speaker-id {speaker_id} is outside the vocoder's {n_spk} speakers (-1: a random one per utterance)")
@@ -90,7 +93,7 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     log_f = log or open(os.path.join(results_path, f"generate-{subset}.log"), "w", encoding="utf-8")
     res_f = open(os.path.join(results_path, f"generate-{subset}.txt"), "w", encoding="utf-8")
     hyps: Dict[int, Dict] = {}
-    words: Dict[str, Dict[int, list]] = {"asr": {}, "st": {}}
+    words: Dict[str, Dict[int, list]] = {"asr": {}, "st": {}, "mt": {}}
     if features:
         for sid, f in items:
             if f.dim() != 2 or f.shape[1] != 80 or f.dtype != torch.float32:
@@ -138,6 +141,18 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
             toks, feats, n = model.batch_mt_greedy(enc, Tp, mx)
         unit_toks = model.batch_t2u_units(feats, n, t2u_causal=t2u_causal, mask_eos=True)
         codes = [units_from_tokens(t, cfg) for t in unit_toks]
+        if mt_alignment:                        # after the search and the unit pass: nothing of this batch reads the MT scratch any more
+            mts = [[t for t in toks[b] if t != cfg.eos] for b in range(len(ids))]
+            rows = [b for b in range(len(ids)) if mts[b]]
+            off = [0]
+            for t in Tp:
+                off.append(off[-1] + int(t))
+            if rows:
+                enc_r = enc if len(rows) == len(ids) else torch.cat([enc[off[b]:off[b + 1]] for b in rows], 0)
+                att = model.batch_mt_attention(enc_r, [Tp[b] for b in rows], [mts[b][:-1] for b in rows], want_matrix=False)
+                for b, (_, peak, prob, _, _) in zip(rows, att):
+                    words["mt"][ids[b]] = words_from_attention(mts[b], peak.tolist(), prob.tolist(), dicts["target_unigram"],
+                                                               eos=cfg.eos)
         have = [b for b, c in enumerate(codes) if len(c) > 0]
         wavs: Dict[int, torch.Tensor] = {}
         if dump_wav and have:
@@ -182,6 +197,11 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
                 for sid in sorted(words[key]):
                     for w in words[key][sid]:
                         print(f"{sid}\t{w.text}\t{w.start_ms}\t{w.end_ms}\t{w.confidence:.6g}", file=f)
+    if mt_alignment:
+        with open(os.path.join(results_path, f"generate-{subset}.mt.words"), "w", encoding="utf-8") as f:
+            for sid in sorted(words["mt"]):
+                for w in words["mt"][sid]:
+                    print(f"{sid}\t{w.text}\t{w.start_ms}\t{w.end_ms}\t{w.focus:.6g}", file=f)
     return hyps
 
 
@@ -303,6 +323,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--scores", action="store_true")
     ap.add_argument("--word-times", action="store_true",
                     help="also write generate-<subset>.asr.words and .st.words: id, word, start_ms, end_ms, confidence per word of the two CTC heads")
+    ap.add_argument("--mt-alignment", action="store_true",
+                    help="also write generate-<subset>.mt.words: id, word, start_ms, end_ms, focus per word of the D- hypothesis, placed in "
+                         "source time by the arg-max of the text decoder's cross-attention (one extra decoder pass per batch)")
     ap.add_argument("--num-shards", type=int, default=int(os.environ.get("WORLD_SIZE", "1")))
     ap.add_argument("--shard-id", type=int, default=int(os.environ.get("RANK", "0")))
     ap.add_argument("--device", default="cuda:%s" % os.environ.get("LOCAL_RANK", "0"))
@@ -411,7 +434,8 @@ def main(argv: Optional[List[str]] = None):
                     getattr(holder.model, "uni_encoder", False), a.scores, targets=targets or None, beam_mt=a.beam_mt,
                     unk_penalty=a.unkpen, normalize=not a.unnormalized,
                     **({"pcm16_out": True} if a.pcm16_io else {}), **({"speaker_id": a.speaker_id} if voc.num_speakers else {}),
-                    **({"features": True} if is_feat else {}), **({"word_times": True} if a.word_times else {}))
+                    **({"features": True} if is_feat else {}), **({"word_times": True} if a.word_times else {}),
+                    **({"mt_alignment": True} if a.mt_alignment else {}))
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
 
 

@@ -74,8 +74,9 @@ class SpeechSessionPool(TextSessionPool):
     CodeHiFiGANVocoderWithDur, whose .hip is used) every S2ST session synthesises with; without one, S2ST sessions are refused."""
     KINDS = KINDS
 
-    def __init__(self, model, max_sessions: int, max_rows: int, vocoder=None, beam_mt: int = 1, details: bool = False):
-        super().__init__(model, max_sessions, max_rows, beam_mt=beam_mt, details=details)
+    def __init__(self, model, max_sessions: int, max_rows: int, vocoder=None, beam_mt: int = 1, details: bool = False,
+                 align: bool = False):
+        super().__init__(model, max_sessions, max_rows, beam_mt=beam_mt, details=details, align=align)
         self.vocoder = getattr(vocoder, "hip", vocoder)
         self.t2u_causal = bool(getattr(model, "uni_encoder", False))   # the agent's ctc_generator: t2u_causal = model.uni_encoder
         self._emitter = None                              # pcm.PcmEmitter of the PcmOut sessions, made with the first one's write
@@ -119,7 +120,7 @@ class SpeechSessionPool(TextSessionPool):
             return ("speech", pack_s16_host(carried).tobytes() if carried.size else b"", True, False)
         return ("speech", list(s.unfinished_wav.tolist()) if s.unfinished_wav is not None else [], True, False)
 
-    def _mt_decide(self, s, toks):
+    def _mt_decide(self, s, toks, view=None):
         """The agent's host decisions between the MT search and T2U.  -> (action or None, n_tokens to keep, n_tail_pad)."""
         fin = s.states.source_finished
         hyp = list(toks)
@@ -142,6 +143,7 @@ class SpeechSessionPool(TextSessionPool):
             if s.prev_output_tokens_mt == prev or len(prev) <= len(s.prev_output_tokens_mt):
                 return ("read",), 0, 0
         s.prev_output_tokens_mt = prev
+        self._align_note(s, tmp, view)
         return None, len(tmp), n_tail_pad
 
     def _write_side(self, mine, views, actions):
@@ -151,7 +153,7 @@ class SpeechSessionPool(TextSessionPool):
         rows = []                                         # (session, mt states [n, D], n_tail_pad)
         pads = []                                         # (index in rows, session's encoder view index, tokens)
         for (i, s, prefix, ml, new), toks, fts in mine:
-            a, n_tok, n_pad = self._mt_decide(s, prefix + toks)
+            a, n_tok, n_pad = self._mt_decide(s, prefix + toks, i)
             if a is not None:
                 actions[s.sid] = a
                 continue

@@ -94,6 +94,7 @@ class _Session:
         self.mp3_held = 0                     # samples decoded into fe._dev past fe.n_pcm and not released yet (gapless hold-back)
         self.ep = None                        # an endpoint.EndpointState: the pool cuts the session's stream into utterances
         self.details = None                   # a words.CtcDetails of the last step that encoded the session (pools with details)
+        self.alignment = None                 # the words.AlignedWord list of the utterance's committed target tokens (pools with align)
         self.reset()
 
     def n_source(self) -> int:
@@ -107,6 +108,7 @@ class _Session:
         return self.fe.n_pcm + (self.pcm_chunk[1] if self.pcm_chunk is not None else 0)
 
     def reset(self):                          # the agent's reset()
+        self.align_rec = []                   # (committed tokens placed so far, the words of one write): frozen once made
         self.tgt_subwords = None
         self.src_ctc_prefix_length = 0
         self.tgt_ctc_prefix_length = 0
@@ -125,16 +127,22 @@ class TextSessionPool:
     """Up to `max_sessions` concurrent ASR / S2TT sessions, each of at most `max_rows` encoder output rows (~40 ms each)."""
     KINDS = KINDS
 
-    def __init__(self, model, max_sessions: int, max_rows: int, beam_mt: int = 1, details: bool = False):
+    def __init__(self, model, max_sessions: int, max_rows: int, beam_mt: int = 1, details: bool = False, align: bool = False):
         """beam_mt > 1: the step's one ragged continuation is a beam search behind every writer's committed prefix
         (HipModel.batch_mt_beam_continue, the agents' --beam-mt); hypothesis 0's tokens and states go on as the greedy ones do.
         details: the step's one CTC call is the scored form, and details(sid) answers the words of both heads with their time
-        spans, confidences and stability (words.py); the segments the sessions answer are the same either way."""
+        spans, confidences and stability (words.py); the segments the sessions answer are the same either way.
+        align: after the step's writes ONE ragged teacher-forced pass (HipModel.batch_mt_attention, peaks only) places the target
+        tokens every session committed in this step in source time by the text decoder's cross-attention, over the encoder rows
+        the write saw; alignment(sid) answers the words (words.AlignedWord), frozen once made.  The pass runs after everything
+        else of the step, on outputs of its own: the segments the sessions answer are the same either way."""
         if not 1 <= int(beam_mt) <= MT_BEAM_MAX:
             raise ValueError(f"beam_mt {beam_mt} outside [1, {MT_BEAM_MAX}]")
         self.beam_mt = int(beam_mt)
         self.model = model.hip if hasattr(model, "hip") else model
         self.with_details = bool(details)
+        self.with_align = bool(align)
+        self._align_jobs: list = []            # (session, encoder view index, committed tokens, tokens placed before, record list, t0_ms)
         self.pool = self.model.stream_pool(max_sessions, max_rows, scores=True) if details else self.model.stream_pool(max_sessions, max_rows)
         self.max_sessions, self.max_rows = int(max_sessions), int(max_rows)
         self.sessions: Dict[int, _Session] = {}
@@ -216,6 +224,7 @@ class TextSessionPool:
         s = self._get(sid)
         s.reset()
         s.details = None
+        s.alignment = None
         s.pending = False
         s.pcm_chunk = None
         self._release(s)
@@ -237,11 +246,53 @@ class TextSessionPool:
         reset(sid), or in a pool without details."""
         return self._get(sid).details if self.with_details else None
 
+    def alignment(self, sid: int):
+        """The words (words.AlignedWord) of all target tokens the session's utterance has committed, each with the source time span
+        the text decoder's cross-attention pointed at when the token was written (an endpointed session: on the stream's clock) and
+        its focus.  A write adds words and never changes one.  None before the first write, after reset(sid), or in a pool without
+        align; a finished utterance's words stay until then or until the next utterance's first write."""
+        return self._get(sid).alignment if self.with_align else None
+
+    @staticmethod
+    def _t0_ms(s: _Session) -> int:
+        """The session clock's time of its utterance's first sample: 0, or for an endpointed session the utterance's first stream
+        sample (an utterance that ended this step: its own)."""
+        if s.ep is None:
+            return 0
+        a = s.ep.utterances[-1]["start"] if s.ep.final else s.ep.utt_start
+        return int(a) * 1000 // s.sr
+
+    def _align_note(self, s: _Session, tokens, view):
+        """A writer committed `tokens` (all of its utterance's, no </s>): its new ones join the step's attention pass, over the
+        step's encoder view `view` (the writer's index among the step's encoded sessions)."""
+        if not self.with_align:
+            return
+        if view is None:
+            raise ValueError("a pool with align needs the writer's encoder view index")
+        rec = s.align_rec
+        while rec and rec[-1][0] > len(tokens):       # (a whole-word cut below what was placed: placed again)
+            rec.pop()
+        done = rec[-1][0] if rec else 0
+        if len(tokens) > done:
+            self._align_jobs.append((s, int(view), [int(t) for t in tokens], done, rec, self._t0_ms(s)))
+
+    def _align_flush(self, views) -> int:
+        """The step's ONE attention pass over every noted writer -> 1 if it ran."""
+        jobs, self._align_jobs = self._align_jobs, []
+        if not jobs:
+            return 0
+        from .words import words_from_attention
+        enc = torch.cat([views[i] for _, i, _, _, _, _ in jobs], 0) if len(jobs) > 1 else views[jobs[0][1]].contiguous()
+        res = self.model.batch_mt_attention(enc, [int(views[i].shape[0]) for _, i, _, _, _, _ in jobs], [t[:-1] for _, _, t, _, _, _ in jobs],
+                                            first=[d for _, _, _, d, _, _ in jobs], want_matrix=False)
+        for (s, _, toks, done, rec, t0), (_, peak, prob, _, _) in zip(jobs, res):
+            rec.append((len(toks), words_from_attention(toks[done:], peak.tolist(), prob.tolist(), s.dict["target_unigram"], t0_ms=t0,
+                                                        eos=self.model.cfg.eos)))
+            s.alignment = [w for _, ws in rec for w in ws]
+        return 1
+
     def _set_details(self, s: _Session, src, tgt, n_final: int):
-        t0 = 0
-        if s.ep is not None:                  # the utterance's first stream sample (an utterance that ended this step: its own)
-            a = s.ep.utterances[-1]["start"] if s.ep.final else s.ep.utt_start
-            t0 = int(a) * 1000 // s.sr
+        t0 = self._t0_ms(s)
         fin = bool(s.states.source_finished)
         s.details = CtcDetails(*(words_from_ctc(r[0], r[1], r[2], r[3], s.dict[name], n_final=n_final, finished=fin, t0_ms=t0)
                                  for r, name in ((src, "source_unigram"), (tgt, "target_unigram"))))
@@ -707,7 +758,7 @@ class TextSessionPool:
                     i, s, prefix, ml, new = w
                     n_steps = max(n_steps, len(toks) - 1)
                     if s.kind in KINDS:
-                        actions[s.sid] = self._s2tt_write(s, prefix + toks, new)
+                        actions[s.sid] = self._s2tt_write(s, prefix + toks, new, i)
                     else:
                         mine.append((w, toks, fts))
         else:
@@ -715,6 +766,7 @@ class TextSessionPool:
         t3 = time.perf_counter()
         if mine:                                  # a subclass's write side after the shared MT call (its own timings)
             self._write_side(mine, views, actions)
+        n_align = self._align_flush(views) if self.with_align else 0     # after every other device call of the step
         # ---- actions -> segments, as GenericAgent.pop ----
         for s in todo:
             if s.sid in out:
@@ -733,6 +785,7 @@ class TextSessionPool:
                 self._release(s)                  # from now on, so its slot goes back; reset(sid) starts a fresh utterance
         self.last_step = {"sessions": len(todo), "encoded": len(enc), "writers": len(writers), "mt_steps": n_steps, "mt_groups": mt_groups,
                           "ctc_scored": 1 if (enc and self.with_details) else 0,       # the step's CTC call was the scored form
+                          "mt_attention": n_align,                                      # batch_mt_attention calls of the step (pools with align)
                           "frontend_calls": fe_calls, "fbank_rows": fe_rows,       # front-end device calls of the step, rows they computed
                           # the PCM route: uploads and ss_pcm_scatter launches of the step (0 or 1 each), bytes uploaded; a subclass's
                           # write side sets the pack side (ss_pcm_pack_s16 launches, bytes downloaded)
@@ -793,12 +846,13 @@ class TextSessionPool:
             self._finish(s)
         return ("write", new_text, s.states.target_finished)
 
-    def _s2tt_write(self, s: _Session, toks, new_tokens):
+    def _s2tt_write(self, s: _Session, toks, new_tokens, view=None):
         sub = toks[:-1] if toks[-1] == 2 else toks
         words = [s.dict["target_unigram"][c] for c in sub]
         if s.tgt_subwords is not None and list(s.tgt_subwords) == list(sub):
             return ("write", "", True) if s.states.source_finished else ("read",)
         s.tgt_subwords = list(sub)
+        self._align_note(s, sub, view)
         text = " ".join(words)
         new_text = text[len(s.tgt_text):]
         s.tgt_text = text
