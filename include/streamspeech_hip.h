@@ -819,6 +819,48 @@ int ss_batch_mt_beam_continue(ss_model* m, void* stream, int B, int beam, const 
 int ss_batch_mt_beam_continue_plan(int B, int beam, const int32_t* h_Tp, const int32_t* h_prefix, const int32_t* h_n_prefix,
                                    const int32_t* h_max_len, int min_len, int out_stride, int feat_rows, int max_tgt_pos, int vocab,
                                    int eos, int pad, int32_t* h_dims, int32_t* h_tables, int64_t tables_cap, int64_t* h_n_tables);
+/* The controls of the first-pass text search beyond beam, unk_penalty and normalize: the reference's --no-repeat-ngram-size, --lenpen
+ * and --temperature (len_penalty, temperature and no_repeat_ngram_size of its generator; unity/sequence_generator.py and
+ * fairseq/fairseq/ngram_repeat_block.py).  size = sizeof(ss_mt_search_opts) of the caller (a smaller one is SS_ERR_ARG; fields a
+ * later header adds behind these are read only when size covers them).
+ *   no_repeat_ngram n (0 = off, else 2 .. 32): at reference step `step` (the hypothesis holds tokens[0 .. step] = </s>, the forced
+ *     prefix, the generated tokens) and step + 2 - n >= 0, every i < step + 2 - n whose window tokens[i .. i + n - 2] equals the last
+ *     n - 1 tokens bans tokens[i + n - 1]: its log-probability becomes -inf after the other masks (NaN, pad, unk, max_len, min_len)
+ *     and before the cumulative score is added.  </s> stands only at position 0 and banned tokens come from positions >= n - 1 >= 1,
+ *     so </s> is never banned and a row at max_len always keeps it.  n = 1 is refused: the reference's Python path bans nothing
+ *     there and its compiled extension bans every seen token.
+ *   len_penalty p (1 = off; finite): with normalize, a finalised hypothesis' score is cum / (float)pow(step + 1, p); p = 1 is the
+ *     plain division by step + 1, bit for bit.  Without normalize nothing is divided.
+ *   temperature T (1 = off; finite, > 0): the logits are divided by T (a float32 division) before the log-softmax, at every step and
+ *     at the forced-prefix rows.
+ * NULL, or {size, 0, 1, 1}, is the call without options: the same launches, the same bits. */
+typedef struct ss_mt_search_opts {
+  int32_t size;
+  int32_t no_repeat_ngram;
+  float len_penalty;
+  float temperature;
+} ss_mt_search_opts;
+/* ss_batch_mt_beam with search options.  Before every other check: opts->size < sizeof(ss_mt_search_opts), no_repeat_ngram outside
+ * {0, 2 .. 32}, a non-finite len_penalty, a non-finite or non-positive temperature -> SS_ERR_ARG.  Then ss_batch_mt_beam's checks. */
+int ss_batch_mt_beam_opts(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                          const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens,
+                          int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows,
+                          const ss_mt_search_opts* opts);
+/* ss_batch_mt_beam_continue with search options.  The option checks of ss_batch_mt_beam_opts come first, then
+ * ss_batch_mt_beam_continue's in their order, then, with no_repeat_ngram = n: a prefix whose own tokens (</s> in front) hold the same
+ * n-gram twice -> SS_ERR_ARG.  Such a prefix would ban one of its forced tokens, and the reference then scores every hypothesis
+ * -inf; refusing it means the prefix pass itself needs no ban.  A prefix each of whose tokens was chosen under the same ban (the
+ * agents' and session pools' committed prefixes) never trips this check. */
+int ss_batch_mt_beam_continue_opts(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                                   const int32_t* h_prefix, const int32_t* h_n_prefix, const int32_t* h_max_len, int min_len,
+                                   float unk_penalty, int normalize, int32_t* h_out_tokens, int out_stride, int32_t* h_n_out,
+                                   float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows,
+                                   const ss_mt_search_opts* opts);
+/* Host only: ss_batch_mt_beam_continue_plan with the refusals ss_batch_mt_beam_continue_opts adds, same codes, same order. */
+int ss_batch_mt_beam_continue_plan_opts(int B, int beam, const int32_t* h_Tp, const int32_t* h_prefix, const int32_t* h_n_prefix,
+                                        const int32_t* h_max_len, int min_len, int out_stride, int feat_rows, int max_tgt_pos,
+                                        int vocab, int eos, int pad, int32_t* h_dims, int32_t* h_tables, int64_t tables_cap,
+                                        int64_t* h_n_tables, const ss_mt_search_opts* opts);
 /* New fbank rows of B streaming sessions in one launch: session b's frames h_first[b] .. h_first[b] + h_n[b] - 1 of its own 16-kHz
  * sample history h_pcm[b] (device; frame i reads samples 160 i .. 160 i + 399) go to h_feat[b] (device, h_n[b] rows of 80).  The
  * same bits as ss_fbank_cmvn's rows.  h_n[b] = 0 skips a session.  1 <= B <= 65535. */
@@ -1203,6 +1245,25 @@ int ss_op_beam_prefix_score(void* stream, const float* logits, int rows, int V, 
 /* beam_prefix_chain_kernel: per utterance b the float32 chain over lp[row0[b] .. + npre[b]) -> pos (same rows), cum0[b * k] */
 int ss_op_beam_prefix_chain(void* stream, const float* lp, const int32_t* row0, const int32_t* npre, int B, int k, float* cum0,
                             float* pos);
+/* The option variants of the three kernels above (ss_mt_search_opts), one launch each.
+ * beam_topk_kernel<options>: the logits are divided by temperature; with no_repeat_ngram = n >= 2 the row's history is staged in LDS
+ * -- tokens[p] = ptok[row0[b] + p] for p < npre[b] (the utterance's prefix-pass tokens, </s> first), tokens[npre[b] + u] =
+ * tok[u][anc[r][c0 + u]] for u <= t_step (tok [t_step + 1][R] step-major, anc [R][Lc] the table read at this step) -- and the banned
+ * entries are -inf before the top-2k selection.  ptok / row0 may be NULL when every npre is 0; c0 + t_step < Lc.  row_scores (may be
+ * NULL): [R][V], every taking-part row's candidate scores as the selection sees them (masks, ban, + cum).  With temperature 1,
+ * n = 0 and row_scores NULL this launches the kernel ss_op_beam_topk launches. */
+int ss_op_beam_topk_opts(void* stream, const float* logits, int R, int V, int k, int t_step, int min_len, const int32_t* max_len,
+                         const int32_t* npre, const int32_t* done, const float* cum, int pad, int unk, int eos, float unk_pen,
+                         float* cand_s, int32_t* cand_t, float temperature, int no_repeat_ngram, const int32_t* tok,
+                         const int32_t* anc, int Lc, int c0, const int32_t* ptok, const int32_t* row0, float* row_scores);
+/* beam_merge_kernel<len_penalty>: a finalised score is cum / (float)pow(step + 1, len_penalty) when normalize; len_penalty 1
+ * launches the kernel ss_op_beam_merge launches. */
+int ss_op_beam_merge_opts(void* stream, const ss_op_beam_state* st, int B, int k, int Lc, int V, int t_step, int c0, int eos,
+                          int normalize, float len_penalty);
+/* beam_prefix_score_kernel<temperature>: the logits are divided by temperature; 1 launches the kernel ss_op_beam_prefix_score
+ * launches. */
+int ss_op_beam_prefix_score_opts(void* stream, const float* logits, int rows, int V, const int32_t* ftok, int pad, int unk,
+                                 float unk_pen, float* lp, float temperature);
 
 #ifdef __cplusplus
 }

@@ -105,11 +105,26 @@ def _beam_mt_arg(v):
     return k
 
 
-def _beam_kwargs(args) -> dict:
-    """generator_mt's search options beyond the reference agent's: nothing at the default beam 1 (the agent builds what it always built)."""
-    if int(getattr(args, "beam_mt", 1)) == 1:
+def _search_kwargs(args) -> dict:
+    """--lenpen / --temperature / --no-repeat-ngram-size as generators.SequenceGenerator takes them; nothing at their defaults."""
+    p, t, n = float(getattr(args, "lenpen", 1.0)), float(getattr(args, "temperature", 1.0)), int(getattr(args, "no_repeat_ngram_size", 0))
+    if (p, t, n) == (1.0, 1.0, 0):
         return {}
-    return {"unk_penalty": float(getattr(args, "unkpen", 0.0))}
+    return {"len_penalty": p, "temperature": t, "no_repeat_ngram_size": n}
+
+
+def _greedy_mt(args) -> bool:
+    """The reference agent's own search: beam 1 and no search option set.  Only then the persistent MT step is armed."""
+    return int(getattr(args, "beam_mt", 1)) == 1 and not _search_kwargs(args)
+
+
+def _beam_kwargs(args) -> dict:
+    """generator_mt's search options beyond the reference agent's: nothing at the default beam 1 with no search option set (the
+    agent builds what it always built)."""
+    kw = _search_kwargs(args)
+    if int(getattr(args, "beam_mt", 1)) > 1:
+        kw["unk_penalty"] = float(getattr(args, "unkpen", 0.0))
+    return kw
 
 
 
@@ -154,7 +169,7 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
         eng = self.model.hip if hasattr(self.model, "hip") else self.model
         self.engine = eng
         beam_mt = int(getattr(args, "beam_mt", 1))
-        if hasattr(eng, "set_persistent_mt_step") and beam_mt == 1:   # HIP engine: the greedy MT decode step as one persistent launch (mt_step.hip)
+        if hasattr(eng, "set_persistent_mt_step") and _greedy_mt(args):   # HIP engine: the greedy MT decode step as one persistent launch (mt_step.hip)
             eng.set_persistent_mt_step(int(getattr(args, "mt_step_workgroups", 64)))
         tgt_dict_mt = self.dict[self.model.mt_task_name]
         tgt_dict = self.dict["tgt"]
@@ -250,6 +265,13 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
                "(--mt-step-workgroups), which belongs to the greedy search, is not armed")
         a("--unkpen", type=float, default=0.0, help="subtracted from the <unk> log-probability of the beam search of --beam-mt > 1; ignored at --beam-mt 1 (the greedy "
                "search of the reference agent has no such penalty)")
+        a("--lenpen", type=float, default=1.0,
+          help="text search: a finished hypothesis' score is divided by length ** lenpen (1 = the plain length)")
+        a("--temperature", type=float, default=1.0, help="text search: the logits are divided by it before the log-softmax")
+        a("--no-repeat-ngram-size", type=int, default=0,
+          help="text search: no n-gram of this size occurs twice in a hypothesis, committed prefix included (0 = off; 2 .. 32).  With "
+               "any of these three off its default every write is a search behind the committed prefix as with --beam-mt > 1 (at "
+               "beam 1 too), and the persistent MT step is not armed")
         a("--word-details", action="store_true", default=False,
           help="after every policy() that ran the encoder, agent.details holds the words of both CTC heads with their time spans, "
                "confidences and stability (streamspeech_amd/words.py); default: off, the heads run exactly as without the flag")
@@ -452,7 +474,7 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
             # reference runs that position through the MT decoder, T2U encoder and unit decoder with
             # key-padding masks, and its 25 unit positions are decoded like any other
             eng = self.engine
-            if self.generator_mt.beam_size > 1:      # the beam search leaves no single-utterance KV cache to append to: one ragged pass
+            if self.generator_mt.beam_size > 1 or self.generator_mt.search:      # the beam search leaves no single-utterance KV cache to append to: one ragged pass
                 enc = self.encoder_outs[0]["encoder_out"][0]
                 enc = (enc[:, 0] if enc.dim() == 3 else enc).contiguous()
                 mt_feats = eng.batch_mt_features(enc, [int(enc.shape[0])], [[int(t) for t in tmp]], [1])[0]

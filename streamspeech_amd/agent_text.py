@@ -6,7 +6,7 @@ agent/speech_to_text.s2tt.streamspeech.agent.py:381-545 (same flags as the S2ST 
 vocoder ones)."""
 import torch
 
-from .agent import StreamSpeechS2STAgent, _beam_kwargs, _detok, mt_alignment_update, word_details
+from .agent import StreamSpeechS2STAgent, _beam_kwargs, _greedy_mt, _detok, mt_alignment_update, word_details
 from .frontend import OnlineFeatureExtractor  # noqa: F401  (re-exported for parity with the reference files)
 from .generators import CTCDecoder, SequenceGenerator
 from .simuleval_shim import ReadAction, SpeechToTextAgent, WriteAction, entrypoint
@@ -31,7 +31,7 @@ class _TextAgentBase(SpeechToTextAgent):
         eng = self.model.hip if hasattr(self.model, "hip") else self.model
         self.engine = eng
         beam_mt = int(getattr(args, "beam_mt", 1))
-        if hasattr(eng, "set_persistent_mt_step") and beam_mt == 1:   # HIP engine: the greedy MT decode step as one persistent launch (mt_step.hip)
+        if hasattr(eng, "set_persistent_mt_step") and _greedy_mt(args):   # HIP engine: the greedy MT decode step as one persistent launch (mt_step.hip)
             eng.set_persistent_mt_step(int(getattr(args, "mt_step_workgroups", 64)))
         self.asr_ctc_generator = CTCDecoder(self.dict["source_unigram"], eng, 0)
         self.st_ctc_generator = CTCDecoder(self.dict["ctc_target_unigram"], eng, 1)

@@ -21,6 +21,16 @@
 //   beam_prefix_chain_kernel   one thread per utterance: the cumulative scores as an in-order float32 chain, and their differences
 // Lock-step index t of utterance b is the reference's step n_prefix[b] + t; row b's cache is shifted as in ss_batch_mt_continue, so
 // every row writes cache index c0 + t at step t.  ss_batch_mt_beam is the call with no prefix anywhere (c0 = 0, no prefix pass).
+//
+// The *_opts entry points carry the reference generator's three further controls (ss_mt_search_opts): temperature and the no-repeat
+// n-gram ban are the OPT variant of the top-2k kernel (the ban reads the row's history through the ancestry table and the prefix-pass
+// tokens, on the device, inside the step), the temperature also a variant of the prefix score kernel, the length penalty a variant of
+// the merge kernel.  The variants are chosen on the host once per search; with every option at its default the launches are the plain
+// kernels, which are the `false` instantiations of the same bodies.  A forced prefix that itself repeats an n-gram is refused by the
+// planner, so the prefix pass needs no ban; the agents' and pools' committed prefixes never trip that check, because each of their
+// tokens was chosen under the same ban.
+#include <cmath>
+
 #include "model_internal.hpp"
 
 namespace {
@@ -36,11 +46,34 @@ __device__ __forceinline__ bool beats(float a, int ia, float b, int ib) {
 // Log-softmax numerics of log_softmax_kernel (elementwise.hip).  Masks in the reference's order (unity/sequence_generator.py:290-327):
 // NaN -> -inf, pad -inf, unk -= unk_penalty, step >= max_len: all but </s> -inf, step < min_len: </s> -inf.
 // Lock-step index t; the reference's step of utterance b is npre[b] + t.
-__global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict__ logits, int V, int k, int t_step, int min_len,
-                                                        const int* __restrict__ max_len, const int* __restrict__ npre,
-                                                        const int* __restrict__ done,
-                                                        const float* __restrict__ cum, int pad, int unk, int eos, float unk_pen,
-                                                        float* __restrict__ cand_s, int* __restrict__ cand_t) {
+//
+// OPT (ss_mt_search_opts; the plain search instantiates OPT = false, which is the code it always was): the logits are divided by the
+// temperature wherever they are read, and with ngram = n >= 2 the reference's no-repeat ban (fairseq/fairseq/ngram_repeat_block.py
+// ::_no_repeat_ngram) is a phase of this kernel.  The row's step + 1 tokens are staged in LDS behind vals -- the forced ones from the
+// utterance's prefix-pass tokens, the fed ones through the ancestry table -- the step + 2 - n windows are compared one per thread,
+// and a match sets the bit of the token behind the window in a V-bit map, which the mask chain reads right after min_len.
+struct TopkOpts {
+  float temp = 1.f;        // temperature
+  int ngram = 0;           // 0, or 2 .. 32
+  const int* tok = nullptr;    // [t_step + 1][R] step-major fed tokens
+  const int* anc = nullptr;    // [R][Lc] the ancestry table read at this step
+  int R = 0, Lc = 0, c0 = 0;
+  const int* ptok = nullptr;   // prefix-pass tokens (</s> first) of utterance b from row0[b]; read for positions < npre[b] only
+  const int* row0 = nullptr;
+  float* row_scores = nullptr; // [R][V] or null: the candidate scores of the row as the selection sees them
+};
+
+// dynamic LDS of the top-2k kernel: the row, and with a ban the row's history and the bit map
+size_t topk_lds_bytes(int V, int ngram, int Lc) {
+  return (size_t)V * sizeof(float) + (ngram >= 2 ? ((size_t)Lc + (size_t)(V + 31) / 32) * sizeof(int) : 0);
+}
+
+template <bool OPT>
+__device__ __forceinline__ void beam_topk_body(const float* __restrict__ logits, int V, int k, int t_step, int min_len,
+                                               const int* __restrict__ max_len, const int* __restrict__ npre,
+                                               const int* __restrict__ done,
+                                               const float* __restrict__ cum, int pad, int unk, int eos, float unk_pen,
+                                               float* __restrict__ cand_s, int* __restrict__ cand_t, const TopkOpts& o) {
   extern __shared__ float vals[];                  // [V] candidate scores of the row; NaN = already taken
   __shared__ float sa[4];
   __shared__ int si[4];
@@ -49,15 +82,44 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
   if (done[b] || (t_step == 0 && j != 0)) return;  // first free step: only beam 0 of each utterance takes part (lprobs[:, ::beam])
   const int step = t_step + npre[b];
   const float* r = logits + (size_t)row * V;
+  auto logit = [&](int n) -> float {
+    if constexpr (OPT) return r[n] / o.temp; else return r[n];
+  };
+  [[maybe_unused]] unsigned* banned = nullptr;     // [ceil(V / 32)] bit n: token n is banned at this step
+  if constexpr (OPT) {
+    if (o.ngram >= 2) {
+      int* hist = reinterpret_cast<int*>(vals + V);  // [Lc] tokens[0 .. step] of the row
+      banned = reinterpret_cast<unsigned*>(hist + o.Lc);
+      const int np = npre[b], n1 = o.ngram - 1, nwin = step + 1 - n1;
+      for (int p = t; p <= step; p += 256) {
+        int tk = -1;
+        if (p < np) tk = o.ptok[o.row0[b] + p];
+        else {
+          const int u = p - np, slot = o.anc[(size_t)row * o.Lc + o.c0 + u];
+          if ((unsigned)slot < (unsigned)o.R) tk = o.tok[(size_t)u * o.R + slot];
+        }
+        hist[p] = tk;
+      }
+      for (int w = t; w < (V + 31) / 32; w += 256) banned[w] = 0u;
+      __syncthreads();
+      for (int i = t; i < nwin; i += 256) {          // window i against the last n - 1 tokens, tokens[nwin .. step]
+        bool same = true;
+        for (int j = 0; j < n1 && same; ++j) same = hist[i + j] == hist[nwin + j];
+        const int tk = hist[i + n1];
+        if (same && (unsigned)tk < (unsigned)V) atomicOr(&banned[tk >> 5], 1u << (tk & 31));
+      }
+      __syncthreads();
+    }
+  }
   float mx = -INFINITY;
-  for (int n = t; n < V; n += 256) mx = fmaxf(mx, r[n]);
+  for (int n = t; n < V; n += 256) mx = fmaxf(mx, logit(n));
   mx = wave_max(mx);
   if (lane == 0) sa[wave] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(sa[0], sa[1]), fmaxf(sa[2], sa[3]));
   __syncthreads();
   float sum = 0.f;
-  for (int n = t; n < V; n += 256) sum += expf(r[n] - mx);
+  for (int n = t; n < V; n += 256) sum += expf(logit(n) - mx);
   sum = wave_sum(sum);
   if (lane == 0) sa[wave] = sum;
   __syncthreads();
@@ -67,13 +129,19 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
   float best = 0.f;
   int bi = -1;
   for (int n = t; n < V; n += 256) {
-    float v = (r[n] - mx) - lse;
+    float v = (logit(n) - mx) - lse;
     if (v != v) v = -INFINITY;
     if (n == pad) v = -INFINITY;
     if (n == unk) v -= unk_pen;
     if (at_max && n != eos) v = -INFINITY;
     if (step < min_len && n == eos) v = -INFINITY;
+    if constexpr (OPT) {
+      if (banned && ((banned[n >> 5] >> (n & 31)) & 1u)) v = -INFINITY;
+    }
     if (step > 0) v = v + c;
+    if constexpr (OPT) {
+      if (o.row_scores) o.row_scores[(size_t)row * V + n] = v;
+    }
     vals[n] = v;
     if (beats(v, n, best, bi)) { best = v; bi = n; }
   }
@@ -105,6 +173,23 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
   }
 }
 
+__global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict__ logits, int V, int k, int t_step, int min_len,
+                                                        const int* __restrict__ max_len, const int* __restrict__ npre,
+                                                        const int* __restrict__ done,
+                                                        const float* __restrict__ cum, int pad, int unk, int eos, float unk_pen,
+                                                        float* __restrict__ cand_s, int* __restrict__ cand_t) {
+  beam_topk_body<false>(logits, V, k, t_step, min_len, max_len, npre, done, cum, pad, unk, eos, unk_pen, cand_s, cand_t, TopkOpts{});
+}
+
+__global__ __launch_bounds__(256) void beam_topk_opts_kernel(const float* __restrict__ logits, int V, int k, int t_step, int min_len,
+                                                             const int* __restrict__ max_len, const int* __restrict__ npre,
+                                                             const int* __restrict__ done,
+                                                             const float* __restrict__ cum, int pad, int unk, int eos,
+                                                             float unk_pen, float* __restrict__ cand_s, int* __restrict__ cand_t,
+                                                             TopkOpts o) {
+  beam_topk_body<true>(logits, V, k, t_step, min_len, max_len, npre, done, cum, pad, unk, eos, unk_pen, cand_s, cand_t, o);
+}
+
 struct BeamState {
   int* tok;        // [Tn + 3][R] token fed at lock-step index t by slot r
   float* cum;      // [Tn + 3][R] cumulative score of the hypothesis fed at lock-step index t by slot r
@@ -123,8 +208,11 @@ struct BeamState {
 // One workgroup per utterance: merge the k sorted per-row lists into the global top 2k, then the step logic of
 // unity/sequence_generator.py:329-470 and finalize_hypos.  t_step is the lock-step index (reference step npre[b] + t_step); every
 // slot wrote cache index c0 + t_step at this step, so the ancestry entries in use are the cache indices 0 .. c0 + t_step.
-__global__ __launch_bounds__(256) void beam_merge_kernel(BeamState st, int k, int R, int Lc, int V, int t_step, int c0, int eos,
-                                                         int normalize) {
+// LENPEN (ss_mt_search_opts::len_penalty != 1): a finalised score is divided by (step + 1) ** len_penalty, formed as the reference forms
+// it -- the power in double, rounded to float32, then one float32 division.  The plain search instantiates LENPEN = false.
+template <bool LENPEN>
+__device__ __forceinline__ void beam_merge_body(const BeamState& st, int k, int R, int Lc, int V, int t_step, int c0, int eos,
+                                                int normalize, float len_penalty) {
   __shared__ float ms[kMaxBeam * kMaxCand];
   __shared__ int mt[kMaxBeam * kMaxCand];
   __shared__ float sel_s[kMaxCand];
@@ -183,7 +271,10 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamState st, int k, in
     for (int q = 0; q < k; ++q)
       if (eosm[q] && cnt < k) {
         fin_c[nf] = q; fin_e[nf] = cnt; ++nf; ++cnt;
-        st.fin_score[b * k + cnt - 1] = normalize ? sel_s[q] / (float)(step + 1) : sel_s[q];   // the full length, prefix included
+        if constexpr (LENPEN)
+          st.fin_score[b * k + cnt - 1] = normalize ? sel_s[q] / (float)pow((double)(step + 1), (double)len_penalty) : sel_s[q];
+        else
+          st.fin_score[b * k + cnt - 1] = normalize ? sel_s[q] / (float)(step + 1) : sel_s[q];   // the full length, prefix included
         st.fin_len[b * k + cnt - 1] = t_step + 1;                                              // tokens after the prefix
       }
     bool any = false;
@@ -239,6 +330,16 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamState st, int k, in
   }
 }
 
+__global__ __launch_bounds__(256) void beam_merge_kernel(BeamState st, int k, int R, int Lc, int V, int t_step, int c0, int eos,
+                                                         int normalize) {
+  beam_merge_body<false>(st, k, R, Lc, V, t_step, c0, eos, normalize, 1.f);
+}
+
+__global__ __launch_bounds__(256) void beam_merge_lenpen_kernel(BeamState st, int k, int R, int Lc, int V, int t_step, int c0, int eos,
+                                                                int normalize, float len_penalty) {
+  beam_merge_body<true>(st, k, R, Lc, V, t_step, c0, eos, normalize, len_penalty);
+}
+
 // d_feats row i = slot-major state row idx[i]; rows with idx < 0 (past the best hypothesis) are left as they are
 __global__ __launch_bounds__(256) void beam_feat_gather_kernel(const int* __restrict__ idx, const float* __restrict__ src, int D,
                                                                int src_rows, float* __restrict__ dst) {
@@ -251,32 +352,48 @@ __global__ __launch_bounds__(256) void beam_feat_gather_kernel(const int* __rest
 // < 0: the row forces nothing).  Log-softmax numerics of beam_topk_kernel.  The reference masks before it forces
 // (unity/sequence_generator.py:290-327, then _prefix_tokens): NaN -> -inf, pad -inf, unk -= unk_penalty; a forced step is below
 // max_len, and min_len is not applied at it.
-__global__ __launch_bounds__(256) void beam_prefix_score_kernel(const float* __restrict__ logits, int V, const int* __restrict__ ftok,
-                                                                int pad, int unk, float unk_pen, float* __restrict__ lp) {
+// TEMP: the logits are divided by the temperature wherever they are read; the plain search instantiates TEMP = false.
+template <bool TEMP>
+__device__ __forceinline__ void beam_prefix_score_body(const float* __restrict__ logits, int V, const int* __restrict__ ftok, int pad,
+                                                       int unk, float unk_pen, float* __restrict__ lp, float temp) {
   __shared__ float sa[4];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, row = blockIdx.x;
   const int tk = ftok[row];
   if (tk < 0 || tk >= V) return;
   const float* r = logits + (size_t)row * V;
+  auto logit = [&](int n) -> float {
+    if constexpr (TEMP) return r[n] / temp; else return r[n];
+  };
   float mx = -INFINITY;
-  for (int n = t; n < V; n += 256) mx = fmaxf(mx, r[n]);
+  for (int n = t; n < V; n += 256) mx = fmaxf(mx, logit(n));
   mx = wave_max(mx);
   if (lane == 0) sa[wave] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(sa[0], sa[1]), fmaxf(sa[2], sa[3]));
   __syncthreads();
   float sum = 0.f;
-  for (int n = t; n < V; n += 256) sum += expf(r[n] - mx);
+  for (int n = t; n < V; n += 256) sum += expf(logit(n) - mx);
   sum = wave_sum(sum);
   if (lane == 0) sa[wave] = sum;
   __syncthreads();
   if (t != 0) return;
   const float lse = logf((sa[0] + sa[1]) + (sa[2] + sa[3]));
-  float v = (r[tk] - mx) - lse;
+  float v = (logit(tk) - mx) - lse;
   if (v != v) v = -INFINITY;
   if (tk == pad) v = -INFINITY;
   if (tk == unk) v -= unk_pen;
   lp[row] = v;
+}
+
+__global__ __launch_bounds__(256) void beam_prefix_score_kernel(const float* __restrict__ logits, int V, const int* __restrict__ ftok,
+                                                                int pad, int unk, float unk_pen, float* __restrict__ lp) {
+  beam_prefix_score_body<false>(logits, V, ftok, pad, unk, unk_pen, lp, 1.f);
+}
+
+__global__ __launch_bounds__(256) void beam_prefix_score_temp_kernel(const float* __restrict__ logits, int V,
+                                                                     const int* __restrict__ ftok, int pad, int unk, float unk_pen,
+                                                                     float* __restrict__ lp, float temp) {
+  beam_prefix_score_body<true>(logits, V, ftok, pad, unk, unk_pen, lp, temp);
 }
 
 // Per utterance the cumulative score of its forced tokens as the reference forms it (lprobs + scores[:, step - 1], step by step in
@@ -307,6 +424,34 @@ __global__ __launch_bounds__(256) void beam_prefix_chain_kernel(const float* __r
 // `tab` holds, in this order: lock-step cross segs [4R] | lock-step self segs [Tn + 1][4R] | row position offset [R] | first
 // prefix-pass row [B] | prefix self segs [4 nseg] | prefix cross segs [4 nseg] | prefix tokens | positions | cache rows | feature rows
 // | forced tokens [Np] each | last prefix-pass row [B].
+// ss_mt_search_opts as the search uses it; the defaults are the search without options.
+struct SearchOpts {
+  int ngram = 0;
+  float len_penalty = 1.f, temp = 1.f;
+};
+
+// The option refusals of the *_opts entry points, made before every other check.
+int read_search_opts(const ss_mt_search_opts* o, SearchOpts& so) {
+  so = SearchOpts{};
+  if (!o) return SS_OK;
+  if (o->size < (int32_t)sizeof(ss_mt_search_opts)) return SS_ERR_ARG;
+  const int n = o->no_repeat_ngram;
+  if (n != 0 && (n < 2 || n > 32)) return SS_ERR_ARG;            // n = 1: the reference's two implementations disagree
+  if (!std::isfinite(o->len_penalty)) return SS_ERR_ARG;
+  if (!std::isfinite(o->temperature) || !(o->temperature > 0.f)) return SS_ERR_ARG;
+  so.ngram = n; so.len_penalty = o->len_penalty; so.temp = o->temperature;
+  return SS_OK;
+}
+
+// tokens[0 .. n) = </s>, then the prefix: does any n-gram stand in it twice?  Then the ban would hit a forced token.
+bool prefix_repeats_ngram(const std::vector<int>& tokens, int ngram) {
+  const int L = (int)tokens.size();
+  for (int e = ngram; e < L; ++e)                                // a later n-gram tokens[e - ngram + 1 .. e] ...
+    for (int i = 0; i + ngram - 1 < e; ++i)                      // ... against an earlier one tokens[i .. i + ngram - 1]
+      if (std::equal(tokens.begin() + i, tokens.begin() + i + ngram, tokens.begin() + e - ngram + 1)) return true;
+  return false;
+}
+
 struct BcPlan {
   int pm = 0, S = 0, Smax = 0, c0 = 0, Tn = 0, Lc = 0, Np = 0, np_max = 0, nseg = 0, R = 0;
   std::vector<int> tab, tok0;
@@ -315,7 +460,7 @@ struct BcPlan {
 
 int beam_continue_plan(int B, int beam, const int32_t* h_Tp, const int32_t* h_prefix, const int32_t* h_n_prefix,
                        const int32_t* h_max_len, int min_len, int out_stride, int feat_rows, int max_tgt_pos, int vocab, int eos,
-                       int pad, int pm, BcPlan& P) {
+                       int pad, int pm, BcPlan& P, int ngram = 0) {
   if (B <= 0 || beam < 1 || beam > kMaxBeam || !h_Tp || !h_max_len) return SS_ERR_ARG;
   if ((long)B * beam > 256) return SS_ERR_CAPACITY;              // the row limit of the greedy twin (segment tables of the slab kernels)
   if (vocab < 2 * beam + 1 || (size_t)vocab * sizeof(float) > 65536) return SS_ERR_ARG;   // the top-2k kernel holds a row in LDS
@@ -342,6 +487,12 @@ int beam_continue_plan(int B, int beam, const int32_t* h_Tp, const int32_t* h_pr
   }
   for (int b = 0; b < B; ++b)                            // fed positions 0 .. max_len_b; scores of up to max_len_b + 1 tokens
     if (h_max_len[b] + 1 > feat_rows || h_max_len[b] + 1 > out_stride || h_max_len[b] + 4 > max_tgt_pos) return SS_ERR_CAPACITY;
+  if (ngram >= 2)                                        // a prefix that repeats an n-gram would ban one of its own forced tokens
+    for (int b = 0, o = 0; b < B; o += npre(b), ++b) {
+      std::vector<int> tokens(1, eos);
+      tokens.insert(tokens.end(), h_prefix + (npre(b) ? o : 0), h_prefix + (npre(b) ? o + npre(b) : 0));
+      if (prefix_repeats_ngram(tokens, ngram)) return SS_ERR_ARG;
+    }
   const int Smax = S + pm, c0 = S, Lc = c0 + Tn + 2;
   const Offsets oe = prefix(h_Tp, B);
   P.pm = pm; P.S = S; P.Smax = Smax; P.c0 = c0; P.Tn = Tn; P.Lc = Lc; P.Np = Np; P.np_max = np_max; P.nseg = nseg; P.R = R;
@@ -388,10 +539,14 @@ int beam_continue_plan(int B, int beam, const int32_t* h_Tp, const int32_t* h_pr
 // The search of both entry points; the checks of `P` are done.
 int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp, const int32_t* h_n_prefix,
                 const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, const BcPlan& P, int32_t* h_out_tokens,
-                int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows) {
+                int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows,
+                const SearchOpts& so) {
   const ss_config& c = m->cfg;
   const int D = c.dec_dim, F = c.dec_ffn, V = c.tgt_vocab, H = c.dec_heads, k = beam, R = B * beam;
   const int Lc = P.Lc, Tn = P.Tn, c0 = P.c0, Np = P.Np;
+  // the option kernels are chosen here, once: a search without options launches what it always launched
+  const bool topk_opts = so.ngram >= 2 || so.temp != 1.f, merge_lenpen = normalize && so.len_penalty != 1.f;
+  if (topk_opts && topk_lds_bytes(V, so.ngram, Lc) > 65536) return SS_ERR_ARG;
   SkScope sk_scope(m->sc->skws);
   CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
   hipStream_t s = (hipStream_t)stream;
@@ -471,7 +626,11 @@ int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_o
     float* prepos = lp + np;
     Lin proj{m->mt_emb, nullptr};
     RET(linear(s, pfo, D, Np, proj, V, D, plog, V));
-    hipLaunchKernelGGL(beam_prefix_score_kernel, dim3(Np), dim3(256), 0, s, plog, V, d_ftok, c.pad, c.unk, unk_penalty, lp);
+    if (so.temp != 1.f)
+      hipLaunchKernelGGL(beam_prefix_score_temp_kernel, dim3(Np), dim3(256), 0, s, plog, V, d_ftok, c.pad, c.unk, unk_penalty, lp,
+                         so.temp);
+    else
+      hipLaunchKernelGGL(beam_prefix_score_kernel, dim3(Np), dim3(256), 0, s, plog, V, d_ftok, c.pad, c.unk, unk_penalty, lp);
     SS_LAUNCH_CHECK();
     hipLaunchKernelGGL(beam_prefix_chain_kernel, dim3((B + 255) / 256), dim3(256), 0, s, lp, d_row0, st.npre, B, k, st.cum, prepos);
     SS_LAUNCH_CHECK();
@@ -507,10 +666,22 @@ int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_o
       RET(launch_layernorm(x, D, frow, Lc * D, m->mt_ln.g, m->mt_ln.b, R, D, 1e-5f, s));
       RET(linear(s, frow, Lc * D, R, proj, V, D, logits, V));
     }
-    hipLaunchKernelGGL(beam_topk_kernel, dim3(R), dim3(256), V * sizeof(float), s, logits, V, k, step, min_len, st.max_len, st.npre,
-                       st.done, st.cum + (size_t)step * R, c.pad, c.unk, c.eos, unk_penalty, st.cand_s, st.cand_t);
+    if (topk_opts) {
+      TopkOpts to;
+      to.temp = so.temp; to.ngram = so.ngram; to.tok = st.tok; to.anc = st.anc + (size_t)(step & 1) * R * Lc; to.R = R; to.Lc = Lc;
+      to.c0 = c0; to.ptok = d_tab + P.o_ptok; to.row0 = d_row0;
+      hipLaunchKernelGGL(beam_topk_opts_kernel, dim3(R), dim3(256), topk_lds_bytes(V, so.ngram, Lc), s, logits, V, k, step, min_len,
+                         st.max_len, st.npre, st.done, st.cum + (size_t)step * R, c.pad, c.unk, c.eos, unk_penalty, st.cand_s,
+                         st.cand_t, to);
+    } else {
+      hipLaunchKernelGGL(beam_topk_kernel, dim3(R), dim3(256), V * sizeof(float), s, logits, V, k, step, min_len, st.max_len, st.npre,
+                         st.done, st.cum + (size_t)step * R, c.pad, c.unk, c.eos, unk_penalty, st.cand_s, st.cand_t);
+    }
     SS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, s, st, k, R, Lc, V, step, c0, c.eos, normalize ? 1 : 0);
+    if (merge_lenpen)
+      hipLaunchKernelGGL(beam_merge_lenpen_kernel, dim3(B), dim3(256), 0, s, st, k, R, Lc, V, step, c0, c.eos, 1, so.len_penalty);
+    else
+      hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, s, st, k, R, Lc, V, step, c0, c.eos, normalize ? 1 : 0);
     SS_LAUNCH_CHECK();
     const bool last = step >= Tn;              // every utterance is done at its max_len step
     ++step;
@@ -566,10 +737,12 @@ int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_o
 }  // namespace
 
 // Batched beam search of the first-pass text decoder (include/streamspeech_hip.h): the search with no prefix anywhere.
-extern "C" int ss_batch_mt_beam(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
-                                const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens,
-                                int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats,
-                                int feat_rows) {
+extern "C" int ss_batch_mt_beam_opts(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                                     const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens,
+                                     int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats,
+                                     int feat_rows, const ss_mt_search_opts* opts) {
+  SearchOpts so;
+  RET(read_search_opts(opts, so));
   if (!m || B <= 0 || beam < 1 || beam > kMaxBeam || !d_feats || !h_out_tokens || !h_n_out || !h_scores) return SS_ERR_ARG;
   if ((long)B * beam > 256) return SS_ERR_CAPACITY;              // the row limit of the greedy twin (segment tables of the slab kernels)
   const ss_config& c = m->cfg;
@@ -584,31 +757,54 @@ extern "C" int ss_batch_mt_beam(ss_model* m, void* stream, int B, int beam, cons
   RET(beam_continue_plan(B, beam, h_Tp, nullptr, nullptr, h_max_len, min_len, out_stride, feat_rows, c.max_tgt_pos, c.tgt_vocab, c.eos,
                          c.pad, 0, P));      // position 0 is a lock-step row at every beam (beam 1 is ss_batch_mt_greedy bit for bit)
   return beam_search(m, stream, B, beam, d_enc_out, h_Tp, nullptr, h_max_len, min_len, unk_penalty, normalize, P, h_out_tokens,
-                     out_stride, h_n_out, h_scores, h_pos_scores, d_feats, feat_rows);
+                     out_stride, h_n_out, h_scores, h_pos_scores, d_feats, feat_rows, so);
+}
+
+extern "C" int ss_batch_mt_beam(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                                const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens,
+                                int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats,
+                                int feat_rows) {
+  return ss_batch_mt_beam_opts(m, stream, B, beam, d_enc_out, h_Tp, h_max_len, min_len, unk_penalty, normalize, h_out_tokens,
+                               out_stride, h_n_out, h_scores, h_pos_scores, d_feats, feat_rows, nullptr);
 }
 
 // The same search behind a forced prefix per utterance (include/streamspeech_hip.h).
-extern "C" int ss_batch_mt_beam_continue(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
-                                         const int32_t* h_prefix, const int32_t* h_n_prefix, const int32_t* h_max_len, int min_len,
-                                         float unk_penalty, int normalize, int32_t* h_out_tokens, int out_stride, int32_t* h_n_out,
-                                         float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows) {
+extern "C" int ss_batch_mt_beam_continue_opts(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                                              const int32_t* h_prefix, const int32_t* h_n_prefix, const int32_t* h_max_len,
+                                              int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens, int out_stride,
+                                              int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows,
+                                              const ss_mt_search_opts* opts) {
+  SearchOpts so;
+  RET(read_search_opts(opts, so));
   if (!m || !d_enc_out || !h_n_prefix || !d_feats || !h_out_tokens || !h_n_out || !h_scores) return SS_ERR_ARG;
   const ss_config& c = m->cfg;
   BcPlan P;
   RET(beam_continue_plan(B, beam, h_Tp, h_prefix, h_n_prefix, h_max_len, min_len, out_stride, feat_rows, c.max_tgt_pos, c.tgt_vocab,
-                         c.eos, c.pad, beam == 1 ? 1 : 0, P));
+                         c.eos, c.pad, beam == 1 ? 1 : 0, P, so.ngram));
   return beam_search(m, stream, B, beam, d_enc_out, h_Tp, h_n_prefix, h_max_len, min_len, unk_penalty, normalize, P, h_out_tokens,
-                     out_stride, h_n_out, h_scores, h_pos_scores, d_feats, feat_rows);
+                     out_stride, h_n_out, h_scores, h_pos_scores, d_feats, feat_rows, so);
 }
 
-extern "C" int ss_batch_mt_beam_continue_plan(int B, int beam, const int32_t* h_Tp, const int32_t* h_prefix, const int32_t* h_n_prefix,
-                                              const int32_t* h_max_len, int min_len, int out_stride, int feat_rows, int max_tgt_pos,
-                                              int vocab, int eos, int pad, int32_t* h_dims, int32_t* h_tables, int64_t tables_cap,
-                                              int64_t* h_n_tables) {
+extern "C" int ss_batch_mt_beam_continue(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                                         const int32_t* h_prefix, const int32_t* h_n_prefix, const int32_t* h_max_len, int min_len,
+                                         float unk_penalty, int normalize, int32_t* h_out_tokens, int out_stride, int32_t* h_n_out,
+                                         float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows) {
+  return ss_batch_mt_beam_continue_opts(m, stream, B, beam, d_enc_out, h_Tp, h_prefix, h_n_prefix, h_max_len, min_len, unk_penalty,
+                                        normalize, h_out_tokens, out_stride, h_n_out, h_scores, h_pos_scores, d_feats, feat_rows,
+                                        nullptr);
+}
+
+extern "C" int ss_batch_mt_beam_continue_plan_opts(int B, int beam, const int32_t* h_Tp, const int32_t* h_prefix,
+                                                   const int32_t* h_n_prefix, const int32_t* h_max_len, int min_len, int out_stride,
+                                                   int feat_rows, int max_tgt_pos, int vocab, int eos, int pad, int32_t* h_dims,
+                                                   int32_t* h_tables, int64_t tables_cap, int64_t* h_n_tables,
+                                                   const ss_mt_search_opts* opts) {
+  SearchOpts so;
+  RET(read_search_opts(opts, so));
   if (!h_n_prefix) return SS_ERR_ARG;
   BcPlan P;
   RET(beam_continue_plan(B, beam, h_Tp, h_prefix, h_n_prefix, h_max_len, min_len, out_stride, feat_rows, max_tgt_pos, vocab, eos, pad,
-                         beam == 1 ? 1 : 0, P));
+                         beam == 1 ? 1 : 0, P, so.ngram));
   if (h_dims) {
     h_dims[0] = P.S; h_dims[1] = P.Tn; h_dims[2] = P.Lc; h_dims[3] = P.Np; h_dims[4] = P.R; h_dims[5] = P.c0; h_dims[6] = P.nseg;
     h_dims[7] = P.pm;
@@ -619,6 +815,14 @@ extern "C" int ss_batch_mt_beam_continue_plan(int B, int beam, const int32_t* h_
     std::copy(P.tab.begin(), P.tab.end(), h_tables);
   }
   return SS_OK;
+}
+
+extern "C" int ss_batch_mt_beam_continue_plan(int B, int beam, const int32_t* h_Tp, const int32_t* h_prefix, const int32_t* h_n_prefix,
+                                              const int32_t* h_max_len, int min_len, int out_stride, int feat_rows, int max_tgt_pos,
+                                              int vocab, int eos, int pad, int32_t* h_dims, int32_t* h_tables, int64_t tables_cap,
+                                              int64_t* h_n_tables) {
+  return ss_batch_mt_beam_continue_plan_opts(B, beam, h_Tp, h_prefix, h_n_prefix, h_max_len, min_len, out_stride, feat_rows,
+                                             max_tgt_pos, vocab, eos, pad, h_dims, h_tables, tables_cap, h_n_tables, nullptr);
 }
 
 // ---- op-level entry points of the kernels above (include/streamspeech_hip.h; tests/test_glue_ops_gpu.py) ----
@@ -660,6 +864,57 @@ extern "C" int ss_op_beam_prefix_chain(void* stream, const float* lp, const int3
   if (B <= 0 || k < 1) return SS_ERR_ARG;
   hipLaunchKernelGGL(beam_prefix_chain_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, lp, row0, npre, B, k, cum0,
                      pos);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+// ---- the option variants (ss_mt_search_opts; tests/test_search_options_gpu.py) ----
+extern "C" int ss_op_beam_topk_opts(void* stream, const float* logits, int R, int V, int k, int t_step, int min_len,
+                                    const int32_t* max_len, const int32_t* npre, const int32_t* done, const float* cum, int pad, int unk,
+                                    int eos, float unk_pen, float* cand_s, int32_t* cand_t, float temperature, int no_repeat_ngram,
+                                    const int32_t* tok, const int32_t* anc, int Lc, int c0, const int32_t* ptok, const int32_t* row0,
+                                    float* row_scores) {
+  const ss_mt_search_opts o{(int32_t)sizeof(ss_mt_search_opts), no_repeat_ngram, 1.f, temperature};
+  SearchOpts so;
+  RET(read_search_opts(&o, so));
+  if (so.ngram == 0 && so.temp == 1.f && !row_scores)
+    return ss_op_beam_topk(stream, logits, R, V, k, t_step, min_len, max_len, npre, done, cum, pad, unk, eos, unk_pen, cand_s, cand_t);
+  if (R <= 0 || k < 1 || k > kMaxBeam || R % k != 0 || t_step < 0) return SS_ERR_ARG;
+  if (V < 2 * k + 1 || (size_t)V * sizeof(float) > 65536) return SS_ERR_ARG;
+  if (so.ngram >= 2 && (!tok || !anc || c0 < 0 || c0 + t_step >= Lc)) return SS_ERR_ARG;
+  if (topk_lds_bytes(V, so.ngram, Lc) > 65536) return SS_ERR_ARG;
+  TopkOpts to;
+  to.temp = so.temp; to.ngram = so.ngram; to.tok = tok; to.anc = anc; to.R = R; to.Lc = Lc; to.c0 = c0; to.ptok = ptok; to.row0 = row0;
+  to.row_scores = row_scores;
+  hipLaunchKernelGGL(beam_topk_opts_kernel, dim3(R), dim3(256), topk_lds_bytes(V, so.ngram, Lc), (hipStream_t)stream, logits, V, k,
+                     t_step, min_len, max_len, npre, done, cum, pad, unk, eos, unk_pen, cand_s, cand_t, to);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+extern "C" int ss_op_beam_merge_opts(void* stream, const ss_op_beam_state* x, int B, int k, int Lc, int V, int t_step, int c0, int eos,
+                                     int normalize, float len_penalty) {
+  if (!std::isfinite(len_penalty)) return SS_ERR_ARG;
+  if (len_penalty == 1.f || !normalize) return ss_op_beam_merge(stream, x, B, k, Lc, V, t_step, c0, eos, normalize);
+  if (!x || B <= 0 || k < 1 || k > kMaxBeam || t_step < 0 || c0 < 0 || c0 + t_step + 2 > Lc) return SS_ERR_ARG;
+  BeamState st;
+  st.tok = x->tok; st.cum = x->cum; st.anc = x->anc; st.cand_s = x->cand_s; st.cand_t = x->cand_t; st.ignore = x->ignore;
+  st.done = x->done; st.max_len = x->max_len; st.npre = x->npre;
+  st.fin_cnt = x->fin_cnt; st.fin_score = x->fin_score; st.fin_len = x->fin_len; st.fin_tok = x->fin_tok; st.fin_pos = x->fin_pos;
+  st.fin_anc = x->fin_anc;
+  hipLaunchKernelGGL(beam_merge_lenpen_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, st, k, B * k, Lc, V, t_step, c0, eos, 1,
+                     len_penalty);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+extern "C" int ss_op_beam_prefix_score_opts(void* stream, const float* logits, int rows, int V, const int32_t* ftok, int pad, int unk,
+                                            float unk_pen, float* lp, float temperature) {
+  if (!std::isfinite(temperature) || !(temperature > 0.f)) return SS_ERR_ARG;
+  if (temperature == 1.f) return ss_op_beam_prefix_score(stream, logits, rows, V, ftok, pad, unk, unk_pen, lp);
+  if (rows <= 0 || V <= 0) return SS_ERR_ARG;
+  hipLaunchKernelGGL(beam_prefix_score_temp_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, V, ftok, pad, unk, unk_pen,
+                     lp, temperature);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }

@@ -83,6 +83,40 @@ MT_BEAM_MAX_ROWS = 256     # B * beam hypothesis rows of one ss_batch_mt_beam ca
 MT_BEAM_MAX = 32
 
 
+def check_search_options(len_penalty: float = 1.0, temperature: float = 1.0, no_repeat_ngram_size: int = 0):
+    """The library's refusals of the three search controls, raised as ValueError before anything is booked -> the ss_mt_search_opts
+    to pass (None at the defaults).  n = 1 is refused: the reference's Python path bans nothing there and its compiled extension
+    bans every seen token."""
+    n, p, t = int(no_repeat_ngram_size), float(len_penalty), float(temperature)
+    if n != no_repeat_ngram_size or (n != 0 and not 2 <= n <= 32):
+        raise ValueError(f"no_repeat_ngram_size {no_repeat_ngram_size} outside {{0, 2..32}}")
+    if not np.isfinite(p):
+        raise ValueError(f"len_penalty {len_penalty} is not finite")
+    if not (np.isfinite(t) and t > 0):
+        raise ValueError(f"temperature {temperature} is not a finite positive number")
+    return L.search_opts(p, t, n)
+
+
+class SearchOptions:
+    """The three controls of the first-pass text search as one object (the session pools' ``search=``): the reference generator's
+    len_penalty, temperature and no_repeat_ngram_size.  Refused values raise ValueError here (check_search_options)."""
+
+    def __init__(self, len_penalty: float = 1.0, temperature: float = 1.0, no_repeat_ngram_size: int = 0):
+        check_search_options(len_penalty, temperature, no_repeat_ngram_size)
+        self.len_penalty, self.temperature = float(len_penalty), float(temperature)
+        self.no_repeat_ngram_size = int(no_repeat_ngram_size)
+
+    def kwargs(self) -> dict:
+        """The keywords batch_mt_beam / batch_mt_beam_continue take; empty when every control is at its default."""
+        if (self.len_penalty, self.temperature, self.no_repeat_ngram_size) == (1.0, 1.0, 0):
+            return {}
+        return {"len_penalty": self.len_penalty, "temperature": self.temperature, "no_repeat_ngram_size": self.no_repeat_ngram_size}
+
+    def __repr__(self):
+        return (f"SearchOptions(len_penalty={self.len_penalty}, temperature={self.temperature}, "
+                f"no_repeat_ngram_size={self.no_repeat_ngram_size})")
+
+
 def plan_beam_groups(B: int, beam: int, max_rows: int = MT_BEAM_MAX_ROWS) -> List[Tuple[int, int]]:
     """Consecutive [start, end) utterance ranges, in order, with (end - start) * beam <= max_rows."""
     if not 1 <= beam <= max_rows:
@@ -256,14 +290,18 @@ class BatchMixin:
         return fbank_sr_rows(n_in, *resample_ratio(sr_in), lib=self.lib)
 
     def batch_mt_beam(self, enc_packed: torch.Tensor, Tp: List[int], max_len: List[int], beam: int, min_len: int = 1,
-                      unk_penalty: float = 0.0, normalize: bool = True):
+                      unk_penalty: float = 0.0, normalize: bool = True, len_penalty: float = 1.0, temperature: float = 1.0,
+                      no_repeat_ngram_size: int = 0):
         """Beam search of the first-pass text decoder (ss_batch_mt_beam) -> (n-best lists, feats [B, Lcap, D], n_feats list).
         nbest[b] holds up to `beam` dicts {"tokens" (incl. final eos), "score", "positional_scores"} in the reference's final order;
         feats / n_feats are the decoder states of hypothesis 0, as batch_mt_greedy returns them.  A pack with B * beam > 256 rows
-        runs as consecutive sub-calls (plan_beam_groups); pack-invariant arithmetic makes the split invisible."""
+        runs as consecutive sub-calls (plan_beam_groups); pack-invariant arithmetic makes the split invisible.  len_penalty,
+        temperature and no_repeat_ngram_size are the reference's --lenpen, --temperature and --no-repeat-ngram-size
+        (ss_mt_search_opts); at their defaults the call is ss_batch_mt_beam itself."""
         B = len(Tp)
         if not 1 <= beam <= MT_BEAM_MAX:
             raise ValueError(f"beam {beam} outside [1, {MT_BEAM_MAX}]")
+        opts = check_search_options(len_penalty, temperature, no_repeat_ngram_size)
         Lmax = max(max_len)
         rows, stride = Lmax + 2, Lmax + 1
         feats = torch.empty((B, rows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
@@ -276,9 +314,12 @@ class BatchMixin:
             n_out = (C.c_int32 * (n * beam))()
             sc = (C.c_float * (n * beam))()
             pos = (C.c_float * (n * beam * stride))()
-            L.check(self.lib.ss_batch_mt_beam(self.h, _stream(), n, beam, _ptr(enc), _i32(Tp[b0:b1]), _i32(max_len[b0:b1]),
-                                              min_len, float(unk_penalty), 1 if normalize else 0, out, stride, n_out, sc, pos,
-                                              _ptr(feats[b0:b1]), rows), "ss_batch_mt_beam")
+            args = (self.h, _stream(), n, beam, _ptr(enc), _i32(Tp[b0:b1]), _i32(max_len[b0:b1]), min_len, float(unk_penalty),
+                    1 if normalize else 0, out, stride, n_out, sc, pos, _ptr(feats[b0:b1]), rows)
+            if opts is None:
+                L.check(self.lib.ss_batch_mt_beam(*args), "ss_batch_mt_beam")
+            else:
+                L.check(self.lib.ss_batch_mt_beam_opts(*args, C.byref(opts)), "ss_batch_mt_beam_opts")
             for b in range(n):
                 hyps = []
                 for i in range(beam):
@@ -293,17 +334,20 @@ class BatchMixin:
         return nbest, feats, n_feats
 
     def batch_mt_beam_continue(self, enc_packed: torch.Tensor, Tp: List[int], prefixes: List[List[int]], max_len: List[int], beam: int,
-                               min_len: int = 1, unk_penalty: float = 0.0, normalize: bool = True):
+                               min_len: int = 1, unk_penalty: float = 0.0, normalize: bool = True, len_penalty: float = 1.0,
+                               temperature: float = 1.0, no_repeat_ngram_size: int = 0):
         """Beam search behind a forced prefix per row (ss_batch_mt_beam_continue; fairseq's ``prefix_tokens`` of the offline generator)
         -> (nbest, feats).  nbest[b] holds up to `beam` dicts, best first: "tokens" is the FULL hypothesis (prefixes[b] + generated,
         incl. the final eos), "score" and "positional_scores" cover it whole.  feats[b] = decoder states [n_prefix_b + n_generated_b, D]
         of hypothesis 0's fed positions, as batch_mt_continue returns them.  A pack with B * beam > 256 rows runs as consecutive
-        sub-calls (plan_beam_groups); pack-invariant arithmetic makes the split invisible."""
+        sub-calls (plan_beam_groups); pack-invariant arithmetic makes the split invisible.  len_penalty, temperature and
+        no_repeat_ngram_size as in batch_mt_beam (ss_batch_mt_beam_continue_opts); a prefix that itself repeats an n-gram is refused."""
         B = len(Tp)
         if not (len(prefixes) == len(max_len) == B):
             raise ValueError("one prefix and one max_len per row")
         if not 1 <= beam <= MT_BEAM_MAX:
             raise ValueError(f"beam {beam} outside [1, {MT_BEAM_MAX}]")
+        opts = check_search_options(len_penalty, temperature, no_repeat_ngram_size)
         rows = stride = max(max_len) + 1
         feats = torch.empty((B, rows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
         nbest: List[List[dict]] = []
@@ -316,10 +360,13 @@ class BatchMixin:
             n_out = (C.c_int32 * (n * beam))()
             sc = (C.c_float * (n * beam))()
             pos = (C.c_float * (n * beam * stride))()
-            L.check(self.lib.ss_batch_mt_beam_continue(self.h, _stream(), n, beam, _ptr(enc), _i32(Tp[b0:b1]), _i32(flat or [0]),
-                                                       _i32([len(p) for p in prefixes[b0:b1]]), _i32(max_len[b0:b1]), int(min_len),
-                                                       float(unk_penalty), 1 if normalize else 0, out, stride, n_out, sc, pos,
-                                                       _ptr(feats[b0:b1]), rows), "ss_batch_mt_beam_continue")
+            args = (self.h, _stream(), n, beam, _ptr(enc), _i32(Tp[b0:b1]), _i32(flat or [0]), _i32([len(p) for p in prefixes[b0:b1]]),
+                    _i32(max_len[b0:b1]), int(min_len), float(unk_penalty), 1 if normalize else 0, out, stride, n_out, sc, pos,
+                    _ptr(feats[b0:b1]), rows)
+            if opts is None:
+                L.check(self.lib.ss_batch_mt_beam_continue(*args), "ss_batch_mt_beam_continue")
+            else:
+                L.check(self.lib.ss_batch_mt_beam_continue_opts(*args, C.byref(opts)), "ss_batch_mt_beam_continue_opts")
             for b in range(n):
                 pre = [int(t) for t in prefixes[b0 + b]]
                 hyps = []
@@ -870,14 +917,20 @@ def plan_mt_continue(Tp: List[int], n_prefix: List[int], max_len: List[int], min
 
 def plan_mt_beam_continue(Tp: List[int], n_prefix: List[int], max_len: List[int], beam: int, min_len: int = 1,
                           feat_rows: Optional[int] = None, out_stride: Optional[int] = None, max_tgt_pos: int = 1026,
-                          prefix_ids: Optional[List[int]] = None, vocab: int = 6000, eos: int = 2, pad: int = 1) -> dict:
+                          prefix_ids: Optional[List[int]] = None, vocab: int = 6000, eos: int = 2, pad: int = 1,
+                          len_penalty: float = 1.0, temperature: float = 1.0, no_repeat_ngram_size: int = 0) -> dict:
     """Layout and refusals of one ss_batch_mt_beam_continue call, as the library makes them (ss_batch_mt_beam_continue_plan, host only
     -- the same planner the call runs).  R = B * beam slots; row b's cache is shifted by S - n_prefix[b] (S = the longest prefix), so
     every slot writes cache index c0 + t at lock-step index t.  feat_rows / out_stride default to the least the call needs.  Raises
-    ContinueRefused with the code the call returns."""
+    ContinueRefused with the code the call returns.  With one of the three search controls off its default the planner is
+    ss_batch_mt_beam_continue_plan_opts: the option refusals first (they reach the library as they are, so their code and their place
+    in the order are the library's), the repeated-n-gram check of the prefixes last."""
     B = len(Tp)
     if len(n_prefix) != B or len(max_len) != B:
         raise ContinueRefused("one prefix length and max_len per row", L.SS_ERR_ARG)
+    opts = None
+    if not (len_penalty == 1.0 and temperature == 1.0 and no_repeat_ngram_size == 0):
+        opts = L.SSMtSearchOpts(C.sizeof(L.SSMtSearchOpts), int(no_repeat_ngram_size), float(len_penalty), float(temperature))
     if B and feat_rows is None:
         feat_rows = max(m + 1 for m in max_len)
     if B and out_stride is None:
@@ -887,11 +940,15 @@ def plan_mt_beam_continue(Tp: List[int], n_prefix: List[int], max_len: List[int]
     dims, n_tab = (C.c_int32 * 8)(), C.c_int64(0)
     args = (B, int(beam), _i32(Tp or [0]), _i32(ids or [0]), _i32(n_prefix or [0]), _i32(max_len or [0]), int(min_len),
             int(out_stride or 0), int(feat_rows or 0), int(max_tgt_pos), int(vocab), int(eos), int(pad))
-    rc = lib.ss_batch_mt_beam_continue_plan(*args, dims, None, 0, C.byref(n_tab))
+    if opts is None:
+        plan_fn = lib.ss_batch_mt_beam_continue_plan
+    else:
+        plan_fn = lambda *a: lib.ss_batch_mt_beam_continue_plan_opts(*a, C.byref(opts))    # noqa: E731
+    rc = plan_fn(*args, dims, None, 0, C.byref(n_tab))
     if rc != 0:
         raise ContinueRefused(f"ss_batch_mt_beam_continue refuses the call: {lib.ss_error_string(rc).decode()}", rc)
     tab = (C.c_int32 * n_tab.value)()
-    L.check(lib.ss_batch_mt_beam_continue_plan(*args, dims, tab, n_tab.value, C.byref(n_tab)), "ss_batch_mt_beam_continue_plan")
+    L.check(plan_fn(*args, dims, tab, n_tab.value, C.byref(n_tab)), "ss_batch_mt_beam_continue_plan")
     S, Tn, Lc, Np, R, c0, nseg, pm = list(dims)
     t, o = list(tab), 0
 

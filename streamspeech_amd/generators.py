@@ -87,6 +87,10 @@ class SequenceGenerator:
     normalisation count the prefix), on the engine's ``batch_mt_beam_continue``.  The agents' own generator pre-fills the prefix and
     ranks k identical rows at the first free step, which is defined only at beam 1; that is the path above and it is unchanged.
 
+    len_penalty / temperature / no_repeat_ngram_size: the reference generator's arguments of the same names (ss_mt_search_opts in
+    include/streamspeech_hip.h has their exact rules).  With any of them off its default the search is ``batch_mt_beam_continue`` at
+    beam 1 as well.  ``match_source_len=True`` raises.
+
     want_attention: hypothesis 0 also carries what the reference's generator records (agent/sequence_generator.py:383-392, fairseq's
     finalize_hypos): ``"attention"``, float32 [src_len, tgt_len], the head-averaged cross-attention of the last decoder layer --
     column p is the decoder position that predicted token p -- and ``"alignment"``, fairseq's hard alignment, an int tensor
@@ -97,8 +101,19 @@ class SequenceGenerator:
     K/V: a single-utterance MT state begun with mt_begin is not live after it."""
 
     def __init__(self, engine, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, max_len=0, min_len=1,
-                 eos=None, use_incremental_states=False, unk_penalty=0.0, normalize_scores=True, want_attention=False, **kw):
+                 eos=None, use_incremental_states=False, unk_penalty=0.0, normalize_scores=True, want_attention=False,
+                 len_penalty=1.0, temperature=1.0, no_repeat_ngram_size=0, match_source_len=False, **kw):
+        from .engine import check_search_options
         self.want_attention = bool(want_attention)
+        if match_source_len:
+            raise ValueError("match_source_len is not supported: its source length is in encoder frames, which means nothing for "
+                             "the text decoder")
+        # the reference generator's len_penalty / temperature / no_repeat_ngram_size; any of them off its default sends every search
+        # through batch_mt_beam_continue (at beam 1 too, where that call is the greedy continuation bit for bit with the options off)
+        self.search = {}
+        if check_search_options(len_penalty, temperature, no_repeat_ngram_size) is not None:
+            self.search = {"len_penalty": float(len_penalty), "temperature": float(temperature),
+                           "no_repeat_ngram_size": int(no_repeat_ngram_size)}
         if not 1 <= int(beam_size) <= 32:
             raise ValueError(f"beam_size {beam_size} outside [1, 32]")
         self.beam_size, self.unk_penalty, self.normalize_scores = int(beam_size), float(unk_penalty), bool(normalize_scores)
@@ -131,10 +146,10 @@ class SequenceGenerator:
         start = len(prefix)
         max_len = mt_max_len(start, src_len, max_new_tokens, self.max_len_a, self.max_len_b, self.max_len, self.min_len)
         eng = self.engine
-        if self.beam_size > 1:
+        if self.beam_size > 1 or self.search:
             enc = enc.contiguous()
             nbest, feats = eng.batch_mt_beam_continue(enc, [int(enc.shape[0])], [prefix], [max_len], self.beam_size, self.min_len,
-                                                      self.unk_penalty, self.normalize_scores)
+                                                      self.unk_penalty, self.normalize_scores, **self.search)
             hyps = [{"tokens": torch.tensor(h["tokens"], dtype=torch.long), "features": None, "score": h["score"], "attention": None,
                      "alignment": None, "positional_scores": torch.tensor(h["positional_scores"], dtype=torch.float32)}
                     for h in nbest[0]]

@@ -125,6 +125,18 @@ class SSOpBeamState(C.Structure):
         "fin_cnt", "fin_score", "fin_len", "fin_tok", "fin_pos", "fin_anc")]
 
 
+class SSMtSearchOpts(C.Structure):
+    """ss_mt_search_opts: the search controls beyond beam / unk_penalty / normalize."""
+    _fields_ = [("size", C.c_int32), ("no_repeat_ngram", C.c_int32), ("len_penalty", _f), ("temperature", _f)]
+
+
+def search_opts(len_penalty: float = 1.0, temperature: float = 1.0, no_repeat_ngram_size: int = 0):
+    """The ss_mt_search_opts of the three controls, or None when all are at their defaults (the call without options)."""
+    if float(len_penalty) == 1.0 and float(temperature) == 1.0 and int(no_repeat_ngram_size) == 0:
+        return None
+    return SSMtSearchOpts(C.sizeof(SSMtSearchOpts), int(no_repeat_ngram_size), float(len_penalty), float(temperature))
+
+
 SS_OP_BEAM_CAND = 64     # row stride of the candidate lists of ss_op_beam_topk / ss_op_beam_merge
 
 # symbol -> (restype, argtypes); must list every function include/streamspeech_hip.h declares
@@ -240,6 +252,15 @@ SIGNATURES = {
     "ss_batch_mt_beam_continue_plan": (_i, [_i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32), _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32), _i64, C.POINTER(_i64)]),
+    "ss_batch_mt_beam_opts": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _f, _i,
+                                   C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(_f), C.POINTER(_f), _vp, _i,
+                                   C.POINTER(SSMtSearchOpts)]),
+    "ss_batch_mt_beam_continue_opts": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), _i, _f, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32),
+                                            C.POINTER(_f), C.POINTER(_f), _vp, _i, C.POINTER(SSMtSearchOpts)]),
+    "ss_batch_mt_beam_continue_plan_opts": (_i, [_i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_int32), _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_int32), _i64, C.POINTER(_i64), C.POINTER(SSMtSearchOpts)]),
     "ss_batch_fbank_frames": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f,
                                    C.POINTER(_vp)]),
     "ss_batch_fbank_frames_sr": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -319,6 +340,10 @@ SIGNATURES = {
     "ss_op_beam_merge": (_i, [_vp, C.POINTER(SSOpBeamState), _i, _i, _i, _i, _i, _i, _i, _i]),
     "ss_op_beam_prefix_score": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _vp]),
     "ss_op_beam_prefix_chain": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "ss_op_beam_topk_opts": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _f, _i, _vp, _vp, _i, _i,
+                                  _vp, _vp, _vp]),
+    "ss_op_beam_merge_opts": (_i, [_vp, C.POINTER(SSOpBeamState), _i, _i, _i, _i, _i, _i, _i, _i, _f]),
+    "ss_op_beam_prefix_score_opts": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _vp, _f]),
 }
 
 _lib = None

@@ -25,6 +25,9 @@ the manifest carries target units (`tgt_audio` column, as the reference's S2UT m
 
 The first-pass text search is greedy by default; `--beam-mt k` runs the reference's beam search (generator_mt with beam_size_mt = k,
 `--unkpen`, `--unnormalized`) on the GPU (ss_batch_mt_beam), and `--beam` is accepted for parity (the CTC unit generator has no search).
+`--no-repeat-ngram-size` and `--lenpen` are that generator's further controls (ss_batch_mt_beam_opts); either off its default runs the
+beam search at `--beam-mt 1` too.  The generator's temperature is the `temperature` argument of generate(); this driver's command
+line goes on rejecting `--temperature`, which the recipe does not pass.
 
 Pinned against the reference's own generator classes run on CPU (oracle/ref_offline.py ->
 tests/golden/offline_generator.json; tests/test_offline_generator_cpu.py, tests/test_offline_generator_gpu.py).
@@ -73,7 +76,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              max_len_b: int = 200, max_len_a_mt: float = 0.0, max_len_b_mt: int = 200, dur_prediction: bool = True, dump_wav: bool = True, t2u_causal: bool = False,
              scores: bool = False, log=None, targets: Optional[Dict[int, Sequence[int]]] = None, beam_mt: int = 1,
              unk_penalty: float = 0.0, normalize: bool = True, pcm16_out: bool = False, speaker_id: int = -1,
-             features: bool = False, word_times: bool = False, mt_alignment: bool = False) -> Dict[int, Dict]:
+             features: bool = False, word_times: bool = False, mt_alignment: bool = False, len_penalty: float = 1.0,
+             temperature: float = 1.0, no_repeat_ngram_size: int = 0) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
@@ -84,7 +88,14 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     random.randint(0, num_speakers - 1) like generate_waveform_from_code.py:69-75 and records it in the log (`K-<id>` lines).
     mt_alignment (--mt-alignment): also writes generate-<subset>.mt.words, the words of every `D-` hypothesis placed in source time by
     the text decoder's cross-attention (words.words_from_attention), from one batch_mt_attention per batch after its search; every
-    other file is the one written without it."""
+    other file is the one written without it.
+    len_penalty / temperature / no_repeat_ngram_size (--lenpen, no flag here, --no-repeat-ngram-size): the reference generator's
+    controls of the first-pass text search (ss_mt_search_opts); any of them off its default runs the beam search at beam_mt = 1 too."""
+    from .engine import check_search_options
+    search = {}
+    if check_search_options(len_penalty, temperature, no_repeat_ngram_size) is not None:
+        search = {"len_penalty": float(len_penalty), "temperature": float(temperature),
+                  "no_repeat_ngram_size": int(no_repeat_ngram_size)}
     n_spk = int(getattr(vocoder, "num_speakers", 0) or 0)
     if n_spk and not -1 <= speaker_id < n_spk:
         raise ValueError(f"--speaker-id {speaker_id} is outside the vocoder's {n_spk} speakers (-1: a random one per utterance)")
@@ -132,10 +143,10 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
         # :130-131); src_len is the fbank frame count.  --max-len-a/-b configure the (NAR) unit generator, which has
         # no length search here.
         mx = [min(int(max_len_a_mt * t + max_len_b_mt), cfg.max_target_positions - 1) for t in T]
-        if beam_mt > 1:
+        if beam_mt > 1 or search:
             # --beam-mt k: the reference's beam search (generator_mt with beam_size_mt = k, --unkpen, --unnormalized); the D- text
             # and the T2U input are hypothesis 0 of each n-best list (sequence_generator_multi_decoder_ctc.py:265-300)
-            nbest, feats, n = model.batch_mt_beam(enc, Tp, mx, beam_mt, 1, unk_penalty, normalize)
+            nbest, feats, n = model.batch_mt_beam(enc, Tp, mx, beam_mt, 1, unk_penalty, normalize, **search)
             toks = [h[0]["tokens"] if h else [] for h in nbest]
         else:
             toks, feats, n = model.batch_mt_greedy(enc, Tp, mx)
@@ -335,6 +346,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--beam", type=int, default=1, help="unit generator beam (accepted for parity; the CTC unit decoder has no search)")
     ap.add_argument("--unkpen", type=float, default=0.0, help="subtracted from the <unk> log-probability of the text search")
     ap.add_argument("--unnormalized", action="store_true", help="text search: do not divide hypothesis scores by their length")
+    ap.add_argument("--lenpen", type=float, default=1.0,
+                    help="text search: a finished hypothesis' score is divided by length ** lenpen (1 = the plain length)")
+    ap.add_argument("--no-repeat-ngram-size", type=int, default=0,
+                    help="text search: no n-gram of this size occurs twice in a hypothesis (0 = off; 2 .. 32).  Either of these two "
+                         "off its default runs the beam search at --beam-mt 1 too")
     ap.add_argument("--pcm16-io", action="store_true",
                     help="16-bit WAV sources are staged as raw frames, uploaded once and decoded on the device, and pred_wav/ is "
                          "written from 16-bit PCM packed on the device (one download per batch); the same files as without it")
@@ -348,6 +364,11 @@ def main(argv: Optional[List[str]] = None):
     a = ap.parse_args(argv)
     if not 1 <= a.beam_mt <= 32:
         ap.error("--beam-mt must be in [1, 32]")
+    from .engine import check_search_options
+    try:
+        check_search_options(a.lenpen, 1.0, a.no_repeat_ngram_size)
+    except ValueError as e:
+        ap.error(str(e))
 
     # model / dictionaries / CMVN exactly as the agent loads them (agent :355-420)
     ns = argparse.Namespace(config_yaml=a.config_yaml, multitask_config_yaml=a.multitask_config_yaml,
@@ -435,7 +456,9 @@ def main(argv: Optional[List[str]] = None):
                     unk_penalty=a.unkpen, normalize=not a.unnormalized,
                     **({"pcm16_out": True} if a.pcm16_io else {}), **({"speaker_id": a.speaker_id} if voc.num_speakers else {}),
                     **({"features": True} if is_feat else {}), **({"word_times": True} if a.word_times else {}),
-                    **({"mt_alignment": True} if a.mt_alignment else {}))
+                    **({"mt_alignment": True} if a.mt_alignment else {}),
+                    **({"len_penalty": a.lenpen, "no_repeat_ngram_size": a.no_repeat_ngram_size}
+                       if (a.lenpen, a.no_repeat_ngram_size) != (1.0, 0) else {}))
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
 
 

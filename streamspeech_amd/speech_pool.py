@@ -75,8 +75,9 @@ class SpeechSessionPool(TextSessionPool):
     KINDS = KINDS
 
     def __init__(self, model, max_sessions: int, max_rows: int, vocoder=None, beam_mt: int = 1, details: bool = False,
-                 align: bool = False):
-        super().__init__(model, max_sessions, max_rows, beam_mt=beam_mt, details=details, align=align)
+                 align: bool = False, search=None, len_penalty: float = 1.0, temperature: float = 1.0, no_repeat_ngram_size: int = 0):
+        super().__init__(model, max_sessions, max_rows, beam_mt=beam_mt, details=details, align=align, search=search,
+                         len_penalty=len_penalty, temperature=temperature, no_repeat_ngram_size=no_repeat_ngram_size)
         self.vocoder = getattr(vocoder, "hip", vocoder)
         self.t2u_causal = bool(getattr(model, "uni_encoder", False))   # the agent's ctc_generator: t2u_causal = model.uni_encoder
         self._emitter = None                              # pcm.PcmEmitter of the PcmOut sessions, made with the first one's write

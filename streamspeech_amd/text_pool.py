@@ -31,7 +31,7 @@ from typing import Dict, Optional
 
 import torch
 
-from .engine import MT_BEAM_MAX, plan_beam_groups
+from .engine import MT_BEAM_MAX, SearchOptions, plan_beam_groups
 from .frontend import SAMPLE_RATE, OnlineFeatureExtractor, unsettled_fbank_frames
 from . import endpoint as EP
 from .pcm import PcmArena, PcmFormat, PcmOut
@@ -127,7 +127,9 @@ class TextSessionPool:
     """Up to `max_sessions` concurrent ASR / S2TT sessions, each of at most `max_rows` encoder output rows (~40 ms each)."""
     KINDS = KINDS
 
-    def __init__(self, model, max_sessions: int, max_rows: int, beam_mt: int = 1, details: bool = False, align: bool = False):
+    def __init__(self, model, max_sessions: int, max_rows: int, beam_mt: int = 1, details: bool = False, align: bool = False,
+                 search: Optional[SearchOptions] = None, len_penalty: float = 1.0, temperature: float = 1.0,
+                 no_repeat_ngram_size: int = 0):
         """beam_mt > 1: the step's one ragged continuation is a beam search behind every writer's committed prefix
         (HipModel.batch_mt_beam_continue, the agents' --beam-mt); hypothesis 0's tokens and states go on as the greedy ones do.
         details: the step's one CTC call is the scored form, and details(sid) answers the words of both heads with their time
@@ -135,10 +137,17 @@ class TextSessionPool:
         align: after the step's writes ONE ragged teacher-forced pass (HipModel.batch_mt_attention, peaks only) places the target
         tokens every session committed in this step in source time by the text decoder's cross-attention, over the encoder rows
         the write saw; alignment(sid) answers the words (words.AlignedWord), frozen once made.  The pass runs after everything
-        else of the step, on outputs of its own: the segments the sessions answer are the same either way."""
+        else of the step, on outputs of its own: the segments the sessions answer are the same either way.
+        search (an engine.SearchOptions), or the three keywords len_penalty / temperature / no_repeat_ngram_size: the agents'
+        --lenpen, --temperature and --no-repeat-ngram-size.  With one of them off its default the step's continuation is the beam
+        search behind the prefix at beam_mt = 1 too; every committed token was chosen under the same ban, so a session's prefix
+        never repeats an n-gram and the call never refuses it."""
         if not 1 <= int(beam_mt) <= MT_BEAM_MAX:
             raise ValueError(f"beam_mt {beam_mt} outside [1, {MT_BEAM_MAX}]")
         self.beam_mt = int(beam_mt)
+        if search is not None and (len_penalty, temperature, no_repeat_ngram_size) != (1.0, 1.0, 0):
+            raise ValueError("give search= or the three keywords, not both")
+        self.search = search if search is not None else SearchOptions(len_penalty, temperature, no_repeat_ngram_size)
         self.model = model.hip if hasattr(model, "hip") else model
         self.with_details = bool(details)
         self.with_align = bool(align)
@@ -813,10 +822,11 @@ class TextSessionPool:
         final eos, decoder states of the fed positions), the [start, end) writer ranges of the device calls it took).  beam_mt = 1:
         the greedy continuation, as always.  beam_mt > 1: the beam search behind the prefix, hypothesis 0 of each writer; writers x
         beam_mt hypothesis rows are at most 256 per device call, so a step with more writers runs as the consecutive sub-calls of
-        plan_beam_groups inside the engine call (nobody is refused)."""
-        if self.beam_mt == 1:
+        plan_beam_groups inside the engine call (nobody is refused).  A search option set: the same beam call at beam_mt = 1 too."""
+        search = self.search.kwargs()
+        if self.beam_mt == 1 and not search:
             return self.model.batch_mt_continue(enc_w, Tp, prefixes, max_len, MIN_LEN), [(0, len(Tp))]
-        nbest, feats = self.model.batch_mt_beam_continue(enc_w, Tp, prefixes, max_len, self.beam_mt, MIN_LEN)
+        nbest, feats = self.model.batch_mt_beam_continue(enc_w, Tp, prefixes, max_len, self.beam_mt, MIN_LEN, **search)
         return [(h[0]["tokens"][len(p):], f) for h, f, p in zip(nbest, feats, prefixes)], plan_beam_groups(len(Tp), self.beam_mt)
 
     # ---- hooks of a subclass's session kinds (speech_pool.py) -------------------------------------------------------------------
