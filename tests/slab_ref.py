@@ -1,13 +1,15 @@
 """Plain torch reference of the packed-batch slab convs (csrc/conv_slab.hip, conv_c16 / c32 / c64.hip, conv_c64w.hip) and of the
 fused ResBlock (csrc/resblock.hip), in whatever dtype the inputs come in (float64 for the reference, float32 for the chain whose
 error the ResBlock bound rests on).  No conv primitive: a conv is the sum over its taps of one matmul per tap on the zero-padded
-utterance, so tests/test_slab_ref_cpu.py can check it against torch.nn.functional.conv1d written another way.
+utterance, so tests/test_slab_ref_cpu.py can check it against torch.nn.functional.conv1d written another way.  (`upsample` is the one
+exception, on purpose: torch's conv_transpose1d per utterance, the independent side of the polyphase identity.)
 
 A pack is a [M, C] tensor of utterances laid end to end; `segs` lists (start, len) per utterance.  Every utterance is convolved
 ALONE: rows outside it read as zero whatever lies next to it in the pack.  Rows of the pack no segment covers come back as NaN --
 no launch may write them.
 """
 import torch
+import torch.nn.functional as F
 
 
 def lrelu(x, slope):
@@ -45,6 +47,19 @@ def seg_conv(x, w, segs, dil=1, pad=None, in_slope=None):
     for s, n in segs:
         if n > 0:
             y[s:s + n] = _conv_one(xin[s:s + n], w, taps, dil, pad)
+    return y
+
+
+def upsample(x, w, b, segs, stride, in_slope=None):
+    """The other way round for the polyphase upsamplers (weights.convT_polyphase): torch's own ConvTranspose1d, w [Cin, Cout, k] with
+    padding (k - stride) / 2, on every utterance of the pack x [M, Cin] alone -> [M * stride, Cout]; in_slope: leaky-ReLU on the input.
+    Row q of the polyphase conv's [M, stride * Cout] result is rows q * stride .. q * stride + stride - 1 of this."""
+    k = w.shape[2]
+    xin = x if in_slope is None else lrelu(x, in_slope)
+    y = x.new_full((x.shape[0] * stride, w.shape[1]), float("nan"))
+    for s, n in segs:
+        if n > 0:
+            y[s * stride:(s + n) * stride] = F.conv_transpose1d(xin[s:s + n].t()[None], w, b, stride=stride, padding=(k - stride) // 2)[0].t()
     return y
 
 

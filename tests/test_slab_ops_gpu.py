@@ -146,15 +146,23 @@ CONV_CASES = [(name, k, d) for name, r in ROUTES.items() for (k, d) in r.get("kd
 
 
 class ConvPack:
-    """Inputs of one conv over one pack, on the host (float32 + what the float64 reference needs) and on the device."""
+    """Inputs of one conv over one pack, on the host (float32 + what the float64 reference needs) and on the device: x [M, Cc],
+    w [N, Cc, k] (N = Cc unless given; every output-side leading dimension is N).
 
-    def __init__(self, Cc, k, d, lens, guard, seed=0):
+    `on` picks the epilogue: True -- every option; False -- the plain conv; "up" -- what the vocoder's upsamplers issue on a
+    pre-activated input (no input activation, bias, the twin at slope 0.1, nothing else).
+    `grid`: the (bm, bn) of an ss_debug_force_tile route whose third argument is the workgroup count (the stream-K kernels,
+    tests/test_sk_ops_gpu.py); run(grid=G) then sets the hook to (bm, bn, G) before the launch.  The caller restores it."""
+
+    def __init__(self, Cc, k, d, lens, guard, seed=0, N=None, grid=None):
         from streamspeech_amd.weights import conv_tap_major
         self.C, self.k, self.d, self.guard = Cc, k, d, guard
+        self.N = N = Cc if N is None else N
+        self.grid = grid
         self.segs = R.seg_table(lens)
         self.M = M = sum(lens)
-        self.x, self.w = rnd(M, Cc, seed=seed + 1), rnd(Cc, Cc, k, seed=seed + 2, scale=(Cc * k) ** -0.5)
-        self.b, self.R, self.R2 = rnd(Cc, seed=seed + 3, scale=0.1), rnd(M, Cc, seed=seed + 4), rnd(M, Cc, seed=seed + 5)
+        self.x, self.w = rnd(M, Cc, seed=seed + 1), rnd(N, Cc, k, seed=seed + 2, scale=(Cc * k) ** -0.5)
+        self.b, self.R, self.R2 = rnd(N, seed=seed + 3, scale=0.1), rnd(M, N, seed=seed + 4), rnd(M, N, seed=seed + 5)
         self.dx, self.dR, self.dR2 = Rows(self.x, guard), Rows(self.R, guard), Rows(self.R2, guard)
         self.dw, self.db = conv_tap_major(self.w).to(DEV), self.b.to(DEV)
         self.dsegs = seg_dev(self.segs)
@@ -164,15 +172,20 @@ class ConvPack:
         Cc, k, d = self.C, self.k, self.d
         a = SSOpConvArgs()
         a.A, a.W, a.C = self.dx.ptr, P(self.dw), P(out)
-        a.lda = a.ldc = a.ldr = a.ldr2 = a.ldc2 = Cc
+        a.lda = Cc
+        a.ldc = a.ldr = a.ldr2 = a.ldc2 = self.N
         a.M = a.in_len = self.M
-        a.N = a.Cin = Cc
+        a.N, a.Cin = self.N, Cc
         a.taps, a.dil, a.stride, a.pad = k, d, 1, d * (k - 1) // 2
         a.in_slope, a.act_slope, a.alpha, a.c2_slope = 0.1, 0.1, 1.0, 0.1
         a.same_rows = 1
         if segmented:
             a.segs, a.nseg, a.max_seg_out = P(self.dsegs), len(self.segs), max(n for _, n in self.segs)
-        if on:       # every option: input leaky-ReLU, bias, epilogue leaky-ReLU with its own slope, alpha, R, R2, the mean, the twin
+        if on == "up":
+            a.bias = P(self.db)
+            if twin:
+                a.C2 = P(out2)
+        elif on:     # every option: input leaky-ReLU, bias, epilogue leaky-ReLU with its own slope, alpha, R, R2, the mean, the twin
             a.bias, a.R, a.R2 = P(self.db), self.dR.ptr, self.dR2.ptr
             a.in_act, a.act, a.act_slope, a.alpha, a.div = 3, 3, 0.2, 0.5, 3.0
             if twin:
@@ -183,13 +196,18 @@ class ConvPack:
         x, w = self.x.double(), self.w.double()
         if not on:
             return R.conv(x, w, self.segs, self.d), None
-        got = R.conv(x, w, self.segs, self.d, in_slope=0.1, bias=self.b.double(), act_slope=0.2, alpha=0.5, R=self.R.double(),
-                     R2=self.R2.double(), div=3.0, c2_slope=0.3)
+        if on == "up":
+            got = R.conv(x, w, self.segs, self.d, bias=self.b.double(), c2_slope=0.1)
+        else:
+            got = R.conv(x, w, self.segs, self.d, in_slope=0.1, bias=self.b.double(), act_slope=0.2, alpha=0.5, R=self.R.double(),
+                         R2=self.R2.double(), div=3.0, c2_slope=0.3)
         return got if twin else (got[0], None)
 
-    def run(self, lib, on, twin, segmented=True):
-        out, out2 = out_buf(self.M, self.guard, self.C), out_buf(self.M, self.guard, self.C)
+    def run(self, lib, on, twin, segmented=True, grid=None):
+        out, out2 = out_buf(self.M, self.guard, self.N), out_buf(self.M, self.guard, self.N)
         a = self.args(on, twin, out, out2, segmented)
+        if self.grid is not None:
+            assert lib.ss_debug_force_tile(self.grid[0], self.grid[1], grid or 0) == 0
         rc = lib.ss_op_conv_gemm_ex(S(), C.byref(a))
         torch.cuda.synchronize()
         return rc, out.cpu(), out2.cpu()

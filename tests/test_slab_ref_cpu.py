@@ -100,6 +100,44 @@ def test_segmented_conv_is_conv1d_per_utterance(taps, dil, cin, n):
     assert torch.isnan(got[~covered]).all() and torch.isnan(plain[~covered]).all() and torch.isfinite(got[covered]).all()
 
 
+def test_rectangular_conv_with_an_empty_utterance_is_conv1d_per_utterance():
+    """N != Cin (conv_pre, the upsamplers: what tests/test_sk_ops_gpu.py launches) on a pack with an utterance of no rows."""
+    lens = [5, 1, 0, 9, 2]
+    segs = R.seg_table(lens)
+    M, cin, n = sum(lens), 32, 80
+    for taps, dil in [(7, 1), (3, 1), (11, 5)]:
+        x, w, b = rnd(M, cin, seed=41), rnd(n, cin, taps, seed=42, scale=(cin * taps) ** -0.5), rnd(n, seed=43, scale=0.1)
+        got, got2 = R.conv(x, w, segs, dil, bias=b, c2_slope=0.1)
+        assert got.shape == (M, n) and torch.isfinite(got).all()         # the empty utterance leaves no uncovered row
+        h = dil * (taps - 1) // 2
+        for s, L in segs:
+            if L:
+                assert (got[s:s + L] - _conv1d_utt(x[s:s + L], w, b, dil, h, h)).abs().max() < 1e-12
+        assert torch.equal(got2, torch.where(got > 0, got, got * 0.1))
+
+
+@pytest.mark.parametrize("cin,cout,k,stride", [(64, 32, 8, 4), (128, 64, 11, 5), (16, 8, 4, 2)])
+def test_polyphase_conv_is_conv_transpose_per_utterance(cin, cout, k, stride):
+    """weights.convT_polyphase through seg_conv (3 taps, pad 1, N = stride * Cout) against F.conv_transpose1d utterance by utterance
+    (slab_ref.upsample), utterances of 0, 1 and 2 rows included: the identity the vocoder's upsamplers rest on, at every edge."""
+    from streamspeech_amd.weights import convT_polyphase
+    lens = [5, 1, 0, 9, 2, 33]
+    segs = R.seg_table(lens)
+    M = sum(lens)
+    x, wt, b = rnd(M, cin, seed=51), rnd(cin, cout, k, seed=52, scale=(cin * k / stride) ** -0.5), rnd(cout, seed=53, scale=0.1)
+    wp, bp = convT_polyphase(wt.float(), b.float(), stride)
+    assert wp.shape == (stride * cout, 3 * cin) and bp.shape == (stride * cout,)
+    w3 = wp.double().reshape(stride * cout, 3, cin).permute(0, 2, 1)          # tap-major rows -> [N, Cin, taps]
+    got = R.conv(x, w3, segs, 1, pad=1, in_slope=0.1, bias=bp.double())
+    ref = R.upsample(x, wt.float().double(), b.float().double(), segs, stride, in_slope=0.1)
+    assert ref.shape == (M * stride, cout) and torch.isfinite(ref).all()
+    assert (got.reshape(M * stride, cout) - ref).abs().max() < 1e-12
+    x2 = x.clone()
+    x2[5] += 100.0                                          # the 1-row utterance: nothing of it reaches its neighbours
+    ref2 = R.upsample(x2, wt.float().double(), b.float().double(), segs, stride, in_slope=0.1)
+    assert torch.equal(ref2[:5 * stride], ref[:5 * stride]) and torch.equal(ref2[6 * stride:], ref[6 * stride:])
+
+
 def test_segmented_conv_reads_nothing_of_the_neighbours():
     """Changing one utterance changes its own rows only."""
     segs = R.seg_table([5, 1, 40, 2])
