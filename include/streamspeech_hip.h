@@ -1007,6 +1007,10 @@ int ss_debug_rtlin(int grid, int enable);
  * with twins / to the same Winograd kernel at 128 channels; 8 / 9 the same for the 256-channel stage (the kernel at CH = 256: two slab
  * phases of 128 input channels, two column halves). */
 int ss_debug_conv_c64(int enable);
+/* A/B hook of the 256-channel form's block shape: rows = 128 (the default: a workgroup produces all 256 output columns of a block of
+ * 128 / 126 / 120 rows) or 256 (two workgroups per block of 256 / 252 / 240 rows, one per column half); 0 puts the default back
+ * (SS_CONV_C256_ROWS sets it for the process).  Both give the same bits.  Any other value is SS_ERR_ARG. */
+int ss_debug_conv_c256_rows(int rows);
 /* The same for the 32-channel stage (csrc/conv_c32.hip): 0 = one fused launch per ResBlock (round 3), 1 = one launch per conv;
  * 4 / 5 = the Winograd form of those per-conv launches (csrc/conv_c64w.hip at 32 channels) off / on. */
 int ss_debug_conv_c32(int enable);
@@ -1092,7 +1096,7 @@ int ss_op_resblock_fused(void* stream, const float* dX, int ldx, const float* co
                          const float* const* dW2, const float* const* dB2, const int32_t* dil, float* dY, int ldy, const float* dR2,
                          int ldr2, float div, int C, int taps, int M, float slope, const int32_t* d_segs, int nseg);
 /* Test hook of the persistent slab kernels (conv_slab / conv_pair / resblock_fused / conv_c16 / c32 / c64 and the Winograd forms):
- * grid > 0 caps their workgroup count (the 256-channel Winograd form keeps its minimum of 16), 0 lifts the cap; min_rows >= 0
+ * grid > 0 caps their workgroup count (the 256-channel Winograd form in 256-row blocks keeps its minimum of 16), 0 lifts the cap; min_rows >= 0
  * replaces the five row thresholds of the dispatch (conv_c16 / c32 / c64, the 128- and 256-channel Winograd forms), min_rows < 0
  * restores them.  (0, -1) is the default state; a negative grid is SS_ERR_ARG.  Tests restore it in `finally`. */
 int ss_debug_slab(int grid, long long min_rows);

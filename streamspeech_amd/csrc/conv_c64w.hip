@@ -43,8 +43,10 @@ __device__ unsigned long long g_cw_dbg[1024 * 8];
 namespace {
 constexpr int CW_MAXSEG = 256;
 constexpr int CW_MAXROWS = 320;                // slab rows a thread's staging registers cover (20 float4 per thread at 64 channels, 40 at 128)
+constexpr int CW_MAXROWS_128 = 192;            // ... of the 128-row blocks at 256 channels (k = 11 at dilation 5: 180)
 [[maybe_unused]] constexpr int CW_NUM_RECORDS = 0x7ffffff0;
-constexpr int cw_bme(int dil) { return dil == 1 ? 256 : dil == 3 ? 252 : 240; }   // output rows per block: whole pairs, <= 128 pairs
+// output rows per block: whole pairs, <= 128 pairs (rows = 128: the half-height blocks of the 256-channel form, <= 64 pairs)
+constexpr int cw_bme(int dil, int rows = 256) { return rows == 128 ? (dil == 1 ? 128 : dil == 3 ? 126 : 120) : (dil == 1 ? 256 : dil == 3 ? 252 : 240); }
 // Tap-group kinds (see the kernel): products per channel block; accumulator set / weight slot, rows and operation of the n-th product
 [[maybe_unused]] __host__ __device__ constexpr int cw_nc(int kind) { return kind == 0 ? 4 : kind == 1 ? 2 : 3; }
 [[maybe_unused]] __host__ __device__ constexpr int cw_slot(int kind, int n) { return kind == 0 ? n : kind == 1 ? (n == 0 ? 0 : 3) : (n == 2 ? 3 : n); }
@@ -89,7 +91,13 @@ __global__ void wino_pack_kernel(const float* __restrict__ W, float* __restrict_
 // (w >> 3) & 1 -- a constant of the workgroup, so its weight rows and the ring prefetch across blocks never change -- and the two
 // workgroups that share a block (w and w ^ 8) sit on the same XCD (block w % 8 of the dispatch order), so the second reader of the
 // block's input rows hits that XCD's L2.  Per (block, column half) twice the MFMA work and twice the staging of the 128-channel form.
-template <int DIL, int CH, int TAIL>
+// CH = 256, ROWS = 128 (the default at 256 channels; ROWS = 256 is the form above, kept for A/B: Dispatch::c256w_rows): the same work cut
+// the other way -- a block of 128 / 126 / 120 rows (64 pairs), ALL 256 output columns, one workgroup.  Wave (t >> 6) & 1 takes pairs
+// 0-31 / 32-63, column set t >> 7 its 64 columns, so per wave nothing changes (32 pairs x 64 columns x 4 components over two slab phases,
+// the ring, the weight rows constant across blocks) while a block's slab is 128 + halo rows that nobody stages a second time, and an
+// utterance's last, partial block costs half as much.  Blocks walk blockIdx.x, += gridDim.x as at the other widths.  Every output
+// element sums the same products in the same order (2 d divides both block heights, so the pairs are the same rows): same bits.
+template <int DIL, int CH, int TAIL, int ROWS = 256>
 __global__ __launch_bounds__(CH >= 128 ? 512 : 256, CH >= 128 ? 1 : CH == 64 ? 2 : 3) void conv_c64w_kernel(const GemmArgs p, const int groups, const int slab_rows) {
 #if __HIP_DEVICE_COMPILE__
   // (CH = 32: the k = 11 ResBlock convs of the 32-channel stage, three workgroups per CU: 2 column tiles, 16 MFMAs per sub-step)
@@ -98,15 +106,18 @@ __global__ __launch_bounds__(CH >= 128 ? 512 : 256, CH >= 128 ? 1 : CH == 64 ? 2
   constexpr int C = CH, LDA = CS + 4, CT = CH >= 64 ? 4 : CH / 16, CB = CS / 16, RING = 2 * CT, TPR = CS / 4;   // TPR threads stage one row
   constexpr int NT = CH >= 128 ? 512 : 256, RPP = NT / TPR;                 // rows per staging pass (16; 32 at 32 channels)
   // (CH = 256: the accumulators stay live across the second phase's staging -- 10 float4 in flight per thread, two passes)
-  constexpr int NP = (CW_MAXROWS + RPP - 1) / RPP, NPC = CH == 256 ? 10 : NP < 20 ? NP : 20, BME = cw_bme(DIL), NPAIR = BME / 2;
+  static_assert(ROWS == 256 || (ROWS == 128 && CH == 256), "half-height blocks: the 256-channel form only");
+  // (128-row blocks: a slab of at most 192 rows -- one pass of 10 up to 160 rows, a second one beyond)
+  constexpr int NP = ((ROWS == 128 ? CW_MAXROWS_128 : CW_MAXROWS) + RPP - 1) / RPP, NPC = CH == 256 ? 10 : NP < 20 ? NP : 20;
+  constexpr int BME = cw_bme(DIL, ROWS), NPAIR = BME / 2;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* sA = smem;                                                        // slab [slab_rows][68]
   int* s_blk = reinterpret_cast<int*>(smem + ((slab_rows * LDA + 3) & ~3));   // block prefix per segment
 
   const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((t >> 6) & 3);
-  const int cs = CH <= 64 ? 0 : __builtin_amdgcn_readfirstlane(t >> 8);     // column set of this wave
-  const int colh = CH == 256 ? (int)((blockIdx.x >> 3) & 1) : 0;             // column half of this WORKGROUP (CH = 256)
+  const int wave = __builtin_amdgcn_readfirstlane((t >> 6) & (ROWS == 128 ? 1 : 3));
+  const int cs = CH <= 64 ? 0 : __builtin_amdgcn_readfirstlane(ROWS == 128 ? t >> 7 : t >> 8);     // column set of this wave
+  const int colh = CH == 256 && ROWS == 256 ? (int)((blockIdx.x >> 3) & 1) : 0;   // column half of this WORKGROUP (CH = 256, 256-row blocks)
   const int col0 = colh * 128 + cs * 64;                                    // first output column of this wave
   const int r = lane & 15, g = lane >> 4;
   const int Kw = groups * 4 * C;                                           // row length of the transformed weight matrix
@@ -126,9 +137,10 @@ __global__ __launch_bounds__(CH >= 128 ? 512 : 256, CH >= 128 ? 1 : CH == 64 ? 2
     return f32x4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
   };
 
-  // CH = 256: workgroups 16 a + b and 16 a + 8 + b (b < 8) share block index 8 a + b and its stride (grid % 16 == 0, host)
-  int blk = CH == 256 ? (int)((blockIdx.x & 7) + 8 * (blockIdx.x >> 4)) : (int)blockIdx.x;
-  const int blk_stride = CH == 256 ? (int)(gridDim.x >> 1) : (int)gridDim.x;
+  // CH = 256, 256-row blocks: workgroups 16 a + b and 16 a + 8 + b (b < 8) share block index 8 a + b and its stride (grid % 16 == 0, host)
+  constexpr bool HALVES = CH == 256 && ROWS == 256;
+  int blk = HALVES ? (int)((blockIdx.x & 7) + 8 * (blockIdx.x >> 4)) : (int)blockIdx.x;
+  const int blk_stride = HALVES ? (int)(gridDim.x >> 1) : (int)gridDim.x;
   if (blk >= nblocks) return;
   f32x4 ring[RING];                            // sub-steps 0 and 1 of group 0: (cc 0, f 0), (cc 0, f 1)
 #pragma unroll
@@ -156,6 +168,8 @@ __global__ __launch_bounds__(CH >= 128 ? 512 : 256, CH >= 128 ? 1 : CH == 64 ? 2
     const int m0 = w.m0, seg_lo = w.seg_lo, seg_hi = w.seg_hi;
     const int m_hi = p.nseg > 0 ? seg_hi : min(seg_hi, p.M);
     const bool edge = (m0 - p.pad < seg_lo) || (m0 - p.pad + slab_rows > seg_hi);
+    // last row the staging reads (128-row blocks: the passes cover up to 61 rows more than the slab has -- no traffic for those)
+    const int row_hi = ROWS == 128 ? min(seg_hi, m0 - p.pad + slab_rows) : seg_hi;
     f32x4 acc[4][2][CT];                                   // [component][pair tile][column tile]
 #pragma unroll
     for (int f = 0; f < 4; ++f)
@@ -173,12 +187,12 @@ __global__ __launch_bounds__(CH >= 128 ? 512 : 256, CH >= 128 ? 1 : CH == 64 ? 2
     //  at once, not by when they are issued: profiles/r05_cw_early_load_experiment.txt, bench -0.5 %.)
     // ---- slab: global -> registers -> [zero padding, leaky-ReLU] -> LDS (as conv_c64.hip), 20 float4 per thread in flight at a time ----
 #pragma unroll 1
-    for (int u0 = 0; u0 < NP; u0 += NPC) {
+    for (int u0 = 0; u0 < NP && (ROWS != 128 || u0 * RPP < slab_rows); u0 += NPC) {
       f32x4 pre[NPC];
 #pragma unroll
       for (int u = 0; u < NPC; ++u) {
         const int rho = t / TPR + RPP * (u0 + u);
-        const int gc = min(max(m0 - p.pad + rho, seg_lo), seg_hi - 1);
+        const int gc = min(max(m0 - p.pad + rho, seg_lo), row_hi - 1);
         pre[u] = *reinterpret_cast<const f32x4*>(p.A + (size_t)gc * p.lda + kh * CS + (t % TPR) * 4);
       }
       float* dst = sA + (t / TPR + RPP * u0) * LDA + (t % TPR) * 4;
@@ -345,7 +359,7 @@ extern "C" int ss_debug_cw_timing(unsigned long long* h_out, int cap_wgs) {
 #endif
 
 // ---- host side ---------------------------------------------------------------------------------
-// (A/B knobs SS_CONV_C64 / C128 / C256 / C32_WINOGRAD, ..._MIN_K, ..._MIN_ROWS and these hooks: dispatch.hpp)
+// (A/B knobs SS_CONV_C64 / C128 / C256 / C32_WINOGRAD, ..._MIN_K, ..._MIN_ROWS, SS_CONV_C256_ROWS and these hooks: dispatch.hpp)
 void conv_c64w_debug(int enable) { if (enable >= 0) dispatch_edit([enable](Dispatch& d) { d.c64w_on = enable ? 1 : 0; }); }
 bool conv_c64w_enabled() { return disp().c64w_on != 0; }
 void conv_c128w_debug(int enable) { if (enable >= 0) dispatch_edit([enable](Dispatch& d) { d.c128w_on = enable ? 1 : 0; }); }
@@ -355,7 +369,11 @@ void conv_c256w_debug(int enable) { if (enable >= 0) dispatch_edit([enable](Disp
 bool conv_c256w_enabled() { return disp().c256w_on != 0; }
 
 static int cw_groups(const GemmArgs& a) { return (a.taps + 2) / 3; }
-static size_t cw_lds(const GemmArgs& a, int ch) { return slab_lds_bytes(cw_bme(a.dil) + 3 * cw_groups(a) * a.dil, ch + 4, CW_MAXSEG); }
+static size_t cw_lds(const GemmArgs& a, int ch, int rows = 256) { return slab_lds_bytes(cw_bme(a.dil, rows) + 3 * cw_groups(a) * a.dil, ch + 4, CW_MAXSEG); }
+// 128-row blocks for this launch: the setting, and a slab the staging passes cover (any k <= 12; beyond, the 256-row form)
+static bool cw_rows128(const GemmArgs& a) {
+  return disp().c256w_rows == 128 && cw_bme(a.dil, 128) + 3 * cw_groups(a) * a.dil <= CW_MAXROWS_128;
+}
 
 // the launches conv_c64.hip takes (checked by the caller: conv_c64_eligible) that also have transformed weights, a "same" geometry the
 // pairing covers and a slab two of which fit a CU
@@ -379,6 +397,7 @@ bool conv_wide_winograd_eligible(const GemmArgs& a, int ch) {
   if (a.taps < 3 || (a.dil != 1 && a.dil != 3 && a.dil != 5) || a.pad != a.dil * (a.taps - 1) / 2) return false;
   if (a.nseg > CW_MAXSEG || a.M < (ch == 128 ? d.c128w_min_rows : d.c256w_min_rows) || !slab_rows_ok(a.M)) return false;
   if (ch == 256 && (size_t)256 * cw_groups(a) * 4 * 256 * 4 >= 0x7ff00000ull) return false;
+  if (ch == 256 && cw_rows128(a)) return cw_lds(a, 128, 128) <= 160 * 1024;
   const int slab_rows = cw_bme(a.dil) + 3 * cw_groups(a) * a.dil;
   return slab_rows <= CW_MAXROWS && cw_lds(a, 128) <= 160 * 1024;
 }
@@ -390,18 +409,21 @@ int launch_wino_pack(const float* W, float* WW, int C, int taps, hipStream_t str
   return SS_OK;
 }
 
-template <int DIL, int CH, int TAIL>
+template <int DIL, int CH, int TAIL, int ROWS = 256>
 static int launch_cw_t(GemmArgs a, hipStream_t stream) {
-  constexpr int BME = cw_bme(DIL);
+  if constexpr (CH == 256 && ROWS == 256) {
+    if (cw_rows128(a)) return launch_cw_t<DIL, CH, TAIL, 128>(a, stream);
+  }
+  constexpr int BME = cw_bme(DIL, ROWS);
   const int groups = cw_groups(a);
   const int slab_rows = BME + 3 * groups * DIL;
-  const size_t lds = cw_lds(a, CH == 256 ? 128 : CH);
-  SS_MAX_LDS_ONCE((&conv_c64w_kernel<DIL, CH, TAIL>), CH >= 128 ? 160 * 1024 : 96 * 1024);
+  const size_t lds = cw_lds(a, CH == 256 ? 128 : CH, ROWS);
+  SS_MAX_LDS_ONCE((&conv_c64w_kernel<DIL, CH, TAIL, ROWS>), CH >= 128 ? 160 * 1024 : 96 * 1024);
   SkWorkspace* st = nullptr;                       // (only for the device's CU count, cached per context)
   int rc = sk_workspace_acquire(stream, &st);
   if (rc != SS_OK) return rc;
   int grid = slab_grid(CH >= 128 ? 1 : CH == 64 ? 2 : 3, st->cus, a.M, BME, a.nseg);
-  if (CH == 256) {                                 // (block, column half) items: workgroups come in groups of 16 = 8 blocks x 2 halves
+  if (CH == 256 && ROWS == 256) {                  // (block, column half) items: workgroups come in groups of 16 = 8 blocks x 2 halves
     long long want = std::min<long long>(st->cus, 2 * ((slab_max_blocks(a.M, BME, a.nseg) + 7) / 8 * 8));
     if (disp().slab_grid_cap > 0) want = std::min<long long>(want, disp().slab_grid_cap);     // (test hook: down to the one group of 16)
     grid = (int)std::max<long long>(16, want / 16 * 16);
@@ -410,7 +432,7 @@ static int launch_cw_t(GemmArgs a, hipStream_t stream) {
   rc = prof_begin(a, stream, CH == 64 ? PROF_CONV_C64W : CH == 128 ? PROF_CONV_C128W : CH == 256 ? PROF_CONV_C256W : PROF_CONV_C32W, rec, prof);   // census: the conv's algorithmic (direct-form) FLOPs; the kernel issues 4 G / (2 k) of them
   if (rc != SS_OK) return rc;
   a.W = a.Wwino;
-  hipLaunchKernelGGL((conv_c64w_kernel<DIL, CH, TAIL>), dim3(grid), dim3(CH >= 128 ? 512 : 256), lds, stream, a, groups, slab_rows);
+  hipLaunchKernelGGL((conv_c64w_kernel<DIL, CH, TAIL, ROWS>), dim3(grid), dim3(CH >= 128 ? 512 : 256), lds, stream, a, groups, slab_rows);
   SS_LAUNCH_CHECK();
   return prof_end(stream, rec, prof);
 }

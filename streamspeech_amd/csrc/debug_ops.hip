@@ -152,6 +152,8 @@ extern "C" int ss_debug_conv_c64(int enable) {
   conv_c64_debug(enable);
   return SS_OK;
 }
+// block height of the 256-channel Winograd form (conv_c64w.hip): 128 / 256 rows, 0 puts the default back
+extern "C" int ss_debug_conv_c256_rows(int rows) { return conv_c256w_rows_debug(rows); }
 extern "C" int ss_debug_conv_c32(int enable) {      // 0 / 1: the per-conv slab kernel off / on; 4 / 5: its Winograd form off / on
   if (enable == 4 || enable == 5) { conv_c32w_debug(enable == 5); return SS_OK; }
   conv_c32_debug(enable);

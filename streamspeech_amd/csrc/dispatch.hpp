@@ -25,6 +25,7 @@ struct Dispatch {
   int c64w_on = 1, c128w_on = 1, c256w_on = 1, c32w_on = 1;                           // SS_CONV_C64 / C128 / C256 / C32_WINOGRAD
   int c64w_min_k = 3;                                                                 // SS_CONV_C64_WINOGRAD_MIN_K
   long long c128w_min_rows = 65536, c256w_min_rows = 32768;                           // SS_CONV_C128 / C256_MIN_ROWS
+  int c256w_rows = 128;            // SS_CONV_C256_ROWS / ss_debug_conv_c256_rows: block height of the 256-channel Winograd form, 128 (all 256 columns, one workgroup) or 256 (two workgroups by column half)
   int slab_grid_cap = 0;           // test hook (ss_debug_slab): > 0 caps the persistent grid of every slab kernel (slab_grid, gemm.hpp)
   // conv_sk.hip
   int sk_groups = 0;               // XCD tile grouping of the first-generation stream-K kernel (tuning hook)

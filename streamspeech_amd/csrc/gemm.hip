@@ -908,6 +908,7 @@ Dispatch env_defaults() {
   d.c64w_on = I("SS_CONV_C64_WINOGRAD", 1); d.c128w_on = I("SS_CONV_C128_WINOGRAD", 1); d.c256w_on = I("SS_CONV_C256_WINOGRAD", 1);
   d.c32w_on = I("SS_CONV_C32_WINOGRAD", 1); d.c64w_min_k = I("SS_CONV_C64_WINOGRAD_MIN_K", 3);
   d.c128w_min_rows = L("SS_CONV_C128_MIN_ROWS", d.c128w_min_rows); d.c256w_min_rows = L("SS_CONV_C256_MIN_ROWS", d.c256w_min_rows);
+  if (const int r = I("SS_CONV_C256_ROWS", d.c256w_rows); r == 128 || r == 256) d.c256w_rows = r;
   if (getenv("SS_FFN_WM")) { d.ffn_wm = I("SS_FFN_WM", 3); d.ffn_wm_forced = 1; }
   d.ffn_fusion = I("SS_NO_FFN_FUSION", 0) ? 0 : 1; d.ffn_min_rows = I("SS_FFN_MIN_ROWS", d.ffn_min_rows);
   if (getenv("SS_SK_MIN_GFLOP")) d.sk_min_flops = 1e9 * atof(getenv("SS_SK_MIN_GFLOP"));
@@ -934,6 +935,13 @@ void slab_debug(int grid, long long min_rows) {
     d.c64_min_rows = set ? min_rows : dflt.c64_min_rows;
     d.c128w_min_rows = set ? min_rows : dflt.c128w_min_rows; d.c256w_min_rows = set ? min_rows : dflt.c256w_min_rows;
   });
+}
+// block height of the 256-channel Winograd form (conv_c64w.hip): 128 or 256; 0 puts the process default back
+int conv_c256w_rows_debug(int rows) {
+  if (rows != 0 && rows != 128 && rows != 256) return SS_ERR_ARG;
+  const int dflt = env_defaults().c256w_rows;
+  dispatch_edit([=](Dispatch& d) { d.c256w_rows = rows ? rows : dflt; });
+  return SS_OK;
 }
 const Dispatch* CtxDispatch::refresh() {
   const unsigned now = g_disp_gen.load(std::memory_order_acquire);

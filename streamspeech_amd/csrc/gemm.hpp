@@ -234,9 +234,11 @@ bool conv_wide_winograd_eligible(const GemmArgs& a, int ch);
 int launch_conv_c128w(const GemmArgs& a, hipStream_t stream);
 void conv_c128w_debug(int enable);
 bool conv_c128w_enabled();
-// ... at 256 channels (two slab phases of 128 input channels, two column halves; one workgroup per CU): the 256-channel stage's ResBlock convs
+// ... at 256 channels (two slab phases of 128 input channels; one workgroup per CU): the 256-channel stage's ResBlock convs, in blocks of
+// 128 rows over all columns or of 256 rows split between two workgroups by column half (Dispatch::c256w_rows)
 int launch_conv_c256w(const GemmArgs& a, hipStream_t stream);
 void conv_c256w_debug(int enable);
+int conv_c256w_rows_debug(int rows);      // A/B: 128 / 256, 0 puts the default back; SS_ERR_ARG otherwise
 bool conv_c256w_enabled();
 // ... and at 32 channels (three workgroups per CU): the per-conv launches of the 32-channel stage (k = 11)
 bool conv_c32w_eligible(const GemmArgs& a);       // call with conv_c32_eligible(a) already true

@@ -293,6 +293,7 @@ SIGNATURES = {
     "ss_debug_ffn": (_i, [_i, _i, _i]),
     "ss_debug_rtlin": (_i, [_i, _i]),
     "ss_debug_conv_c64": (_i, [_i]),
+    "ss_debug_conv_c256_rows": (_i, [_i]),
     "ss_debug_conv_c32": (_i, [_i]),
     "ss_debug_conv_c16": (_i, [_i]),
     "ss_debug_enc_step_launches": (_i64, []),

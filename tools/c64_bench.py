@@ -1,6 +1,7 @@
 """The 64-channel vocoder-stage convs of a packed batch on the slab kernel with streamed weights (csrc/conv_c64.hip, input
 leaky-ReLU applied while staging) against the stream-K kernel they ran on through round 3 (conv_sk2<64>: pre-activated input, and
-for the second conv of a pair a pre-activated twin output): us per launch and algorithmic TFLOP/s.
+for the second conv of a pair a pre-activated twin output): us per launch and algorithmic TFLOP/s.  At 256 channels the slab column
+comes twice, once per block shape of the Winograd form (256-row blocks split by column half / 128-row blocks over all columns).
     python tools/c64_bench.py [rows]"""
 import ctypes as C
 import os
@@ -40,7 +41,10 @@ def main():
         return e0.elapsed_time(e1) * 1e3 / reps
 
     print(f"{M} rows x {CH} channels; conv1 = dilated conv of lrelu(x) + bias; conv2 = conv of lrelu(h) + bias + residual")
-    print("taps dil | conv1: stream-K (pre-activated in, LRELU epilogue) | slab | conv2: stream-K (+ twin out) | slab   [us (TF/s)]")
+    # (route, slab kernel?, block height of the 256-channel Winograd form)
+    forms = [("stream-K", False, 0), ("slab 256 rows", True, 256), ("slab 128 rows", True, 128)] if CH == 256 else [("stream-K", False, 0), ("slab", True, 0)]
+    names = " | ".join(n for n, _, _ in forms)
+    print(f"taps dil | conv1 (stream-K: pre-activated in, LRELU epilogue): {names} | conv2 (stream-K: + twin out): {names}   [us (TF/s)]")
     for taps in (3, 7, 11):
         for dil in (1, 3, 5):
             W, b = rn(CH, taps * CH, sc=(taps * CH) ** -0.5), rn(CH, sc=0.1)
@@ -48,8 +52,10 @@ def main():
             pad = dil * (taps - 1) // 2
             cols = []
             for conv2 in (False, True):
-                for slab in (False, True):
+                for _, slab, c256_rows in forms:
                     dbg(1 if slab else 0)
+                    if c256_rows:
+                        assert lib.ss_debug_conv_c256_rows(c256_rows) == 0
                     # stream-K form: input already activated by the producer (in_act 0), conv1 applies the LRELU epilogue; the slab
                     # form reads raw rows (in_act 3) and writes raw rows
                     in_act = 3 if slab else 0
@@ -65,6 +71,7 @@ def main():
                     cols.append(f"{t:7.1f} ({fl / t * 1e-6:5.1f})")
             print(f"{taps:4d} {dil:3d} | " + " | ".join(cols), flush=True)
     dbg(1)
+    lib.ss_debug_conv_c256_rows(0)
     print("(the stream-K conv2 of the pipeline additionally writes the pre-activated twin of its output: +1 tensor pass not timed here)")
 
 

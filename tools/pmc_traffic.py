@@ -74,8 +74,8 @@ def main():
         if prefix.endswith("conv_c64w_kernel"):   # one kernel template, two census classes: the channel count is its third template argument
             want = "256" if cls.startswith("conv_c256w") else "128" if cls.startswith("conv_c128w") else "32" if cls.startswith("conv_c32w") else "64"
 
-            def channels(k):     # conv_c64w_kernel<DIL, CH, TAIL> (round 5) | <LRELU, DIL, CH> (round 4)
-                m = re.search(r"conv_c64w_kernel<(\d+), (\d+), (\d+)>", k)
+            def channels(k):     # conv_c64w_kernel<DIL, CH, TAIL[, ROWS]> (round 5; ROWS: block height) | <LRELU, DIL, CH> (round 4)
+                m = re.search(r"conv_c64w_kernel<(\d+), (\d+), (\d+)(?:, \d+)?>", k)
                 if m:
                     return m.group(2)
                 m = re.search(r"conv_c64w_kernel<(?:true|false), \d+, (\d+)>", k)

@@ -12,11 +12,11 @@ CLASSES = [("conv_sk2<256,128,32>", ["void ss::conv_sk2_kernel"]),
            ("conv_sk<128,BN,32>", ["void ss::conv_sk_kernel"]),
            ("conv_c64<256,64>", ["void ss::conv_c64_kernel"]),
            # one kernel template (csrc/conv_c64w.hip), four census classes: the channel count is its SECOND template argument
-           # (conv_c64w_kernel<DIL, CH, TAIL> since round 5; <LRELU, DIL, CH> in round 4: "re:" entries are regular expressions)
-           ("conv_c64w<256,64>", [r"re:void ss::conv_c64w_kernel<(?:\d+, 64, \d+|(?:true|false), \d+, 64)>"]),
-           ("conv_c32w<256,32>", [r"re:void ss::conv_c64w_kernel<(?:\d+, 32, \d+|(?:true|false), \d+, 32)>"]),
-           ("conv_c128w<256,128>", [r"re:void ss::conv_c64w_kernel<(?:\d+, 128, \d+|(?:true|false), \d+, 128)>"]),
-           ("conv_c256w<256,128>", [r"re:void ss::conv_c64w_kernel<\d+, 256, \d+>"]),
+           # (conv_c64w_kernel<DIL, CH, TAIL[, ROWS]> since round 5; <LRELU, DIL, CH> in round 4: "re:" entries are regular expressions)
+           ("conv_c64w<256,64>", [r"re:void ss::conv_c64w_kernel<(?:\d+, 64, \d+(?:, \d+)?|(?:true|false), \d+, 64)>"]),
+           ("conv_c32w<256,32>", [r"re:void ss::conv_c64w_kernel<(?:\d+, 32, \d+(?:, \d+)?|(?:true|false), \d+, 32)>"]),
+           ("conv_c128w<256,128>", [r"re:void ss::conv_c64w_kernel<(?:\d+, 128, \d+(?:, \d+)?|(?:true|false), \d+, 128)>"]),
+           ("conv_c256w<256,128>", [r"re:void ss::conv_c64w_kernel<\d+, 256, \d+(?:, \d+)?>"]),
            ("conv_c32<256,32>", ["void ss::conv_c32_kernel"]),
            ("conv_c16<256,16>", ["void ss::conv_c16_kernel"]),
            ("resblock_fused<32>", ["void ss::resblock_fused_kernel<32"]),
