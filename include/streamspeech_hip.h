@@ -747,6 +747,40 @@ int ss_batch_ctc_greedy(ss_model* m, void* stream, int head, int B, const float*
 int ss_batch_ctc_greedy_scored(ss_model* m, void* stream, int head, int B, const float* d_enc_out,
                                const int32_t* h_Tp, int32_t* d_raw, int32_t* d_tokens, int32_t* d_index,
                                int32_t* d_counts, float* d_lprob, int32_t* d_last, float* d_tok_lprob);
+/* ---- CTC forced alignment and scoring of a GIVEN label sequence on a text head (csrc/ctc_align.hip): where do these labels lie in
+ * this audio, and how likely does the model find them -- the CTC criterion's log p(y | x) (plain log_softmax, blank = 0, no pad / unk
+ * masking, so a word mapped to <unk> can still be placed; fairseq criterions/ctc.py) and its best path.  The extended sequence is
+ * [0, y0, 0, y1, ..., y(L-1), 0]; a path stays, advances by one state, or skips the blank between two different labels. ---- */
+typedef struct ss_ctc_align_result {
+  double score;      /* log p(y | x): the forward sum over every path, float64 state over the float32 per-frame log-softmax */
+  double viterbi;    /* the log-probability of the best path, the one d_path / d_first / d_last describe */
+  int32_t status;    /* 0 aligned; 1 infeasible (T' < L + number of adjacent equal labels, or every path has probability 0); 2 a NaN in
+                      * a row of the utterance */
+  int32_t n_tokens;  /* L */
+} ss_ctc_align_result;
+#define SS_CTC_ALIGN_MAX_FRAMES 1500    /* T' per utterance (max_source_positions = 6000 fbank frames) */
+#define SS_CTC_ALIGN_MAX_LABELS 1500    /* L per utterance */
+/* B utterances packed as ss_batch_ctc_greedy_scored takes them (the same head GEMM, pack-invariance setting and workspace), labels
+ * h_targets packed in the same order, h_n_targets[b] of them for utterance b (0 is legal: the score is the all-blank path).  Device
+ * outputs: d_results [B]; d_path [sum Tp] the token id of the best path per frame, 0 = blank (may be NULL); per label j, packed like
+ * h_targets: d_first[j] / d_last[j] the first and last frame of its run on the path (relative to its utterance), d_tok_lprob[j] the
+ * float32 sum of the per-frame log-probability over that run in ascending frame order (the promise of ss_ctc_greedy_scored's
+ * d_tok_lprob).  Ties: stay beats advance beats skip; at the end the trailing blank beats the last label.  status 1: score = viterbi
+ * = -inf, path / first / last -1, tok_lprob NaN; status 2: the scores NaN, the rest as status 1.  An utterance's outputs are the same
+ * bits alone and in any pack, in any order.  SS_ERR_ARG, with nothing launched or written: a label that is blank (0), pad, negative
+ * or >= the head's vocabulary, an n_targets outside [0, SS_CTC_ALIGN_MAX_LABELS], a Tp outside [1, SS_CTC_ALIGN_MAX_FRAMES], B <= 0,
+ * head outside {0, 1}, a missing pointer (d_first / d_last / d_tok_lprob / h_targets may be NULL only when there is no label at all).
+ * The per-frame values and the back-pointers are booked on the context's scratch set: sum Tp_b * (n_b + 1) floats and
+ * sum Tp_b * ceil((2 n_b + 1) / 4) bytes. */
+int ss_batch_ctc_align(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp,
+                       const int32_t* h_targets, const int32_t* h_n_targets, ss_ctc_align_result* d_results, int32_t* d_path,
+                       int32_t* d_first, int32_t* d_last, float* d_tok_lprob);
+/* The plain-C++ twin of the two kernels on host logits [sum T][ld] (V columns read; pad < 0: no pad id): the same transition code,
+ * record layout, refusals and edge cases, every pointer a HOST pointer.  h_frame_lprob [sum T] (may be NULL): the per-frame
+ * log-probability of the path's state, NaN where there is no path. */
+int ss_ctc_align_host(const float* h_logits, int ld, int V, int pad, int B, const int32_t* h_T, const int32_t* h_targets,
+                      const int32_t* h_n_targets, ss_ctc_align_result* h_results, int32_t* h_path, int32_t* h_first, int32_t* h_last,
+                      float* h_tok_lprob, float* h_frame_lprob);
 /* Lockstep beam-1 search from [</s>] (offline: no prefix).  h_max_len[b] = forced-</s> step of
  * utterance b.  h_out_tokens [B][out_stride] receives the generated tokens (incl. the final </s>),
  * h_n_out[b] their number (= rows of valid decoder states); d_feats is [B][feat_rows][dec_dim].
@@ -1202,6 +1236,11 @@ int ss_op_masked_argmax_lprob(void* stream, const float* logits, int ld, int M, 
                               float* lprob);
 int ss_op_ctc_collapse_spans(void* stream, const int32_t* raw, const float* lprob, int T, int blank, int pad, int32_t* tokens,
                              int32_t* index, int32_t* last, float* tok_lprob, int32_t* count, const int32_t* segs, int nseg);
+/* The two kernels of ss_batch_ctc_align on the caller's logits [sum T][ld] (device; V columns read), arguments and outputs as
+ * ss_ctc_align_host with device output pointers.  tests/test_ctc_align_gpu.py against tests/ctc_align_ref.py. */
+int ss_op_ctc_align(void* stream, const float* d_logits, int ld, int V, int pad, int B, const int32_t* h_T, const int32_t* h_targets,
+                    const int32_t* h_n_targets, ss_ctc_align_result* d_results, int32_t* d_path, int32_t* d_first, int32_t* d_last,
+                    float* d_tok_lprob, float* d_frame_lprob);
 int ss_op_dur_predict(void* stream, const float* logdur, const int32_t* forced, int K, int32_t* dur, int32_t* cum,
                       const int32_t* segs, int nseg);                 /* segs {start, len}: cum of segment s at start + s */
 int ss_op_repeat_rows(void* stream, const float* emb, const int32_t* cum, int K, int D, float* out, int F, const int32_t* segs,

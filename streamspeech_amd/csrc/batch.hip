@@ -3,6 +3,7 @@
 // :425-717 run for B = 1 utterances at a time.
 #include <cstring>
 #include "model_internal.hpp"
+#include "ctc_align.hpp"
 
 // =================================================================================================
 // Ragged-batch stage twins: B independent utterances packed along the row axis.  No padding exists
@@ -153,6 +154,31 @@ extern "C" int ss_batch_ctc_greedy_scored(ss_model* m, void* stream, int head, i
   RET(launch_masked_argmax_lprob(logits, V, o.total, V, c.pad, c.unk, -1, d_raw, d_lprob, s));
   return launch_ctc_collapse_spans(d_raw, d_lprob, 0, 0, c.pad, d_tokens, d_index, d_last, d_tok_lprob, d_counts, s,
                                    (const int*)m->sc->seg_buf.p, B);
+}
+
+// Forced alignment of given labels on a text head: ss_batch_ctc_greedy_scored's head GEMM (the same linear, CanonScope and workspace),
+// then the two kernels of ctc_align.hip.  Every refusal comes before the first launch; the per-frame values and the back-pointers
+// live in the encoder scratch (idle here: d_enc_out is the caller's), the tables in the segment buffer.
+extern "C" int ss_batch_ctc_align(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp,
+                                  const int32_t* h_targets, const int32_t* h_n_targets, ss_ctc_align_result* d_results,
+                                  int32_t* d_path, int32_t* d_first, int32_t* d_last, float* d_tok_lprob) {
+  if (!m || B <= 0 || head < 0 || head > 1 || !d_enc_out || !h_Tp || !h_n_targets || !d_results) return SS_ERR_ARG;
+  const ss_config& c = m->cfg;
+  const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
+  CtcAlignPlan plan;
+  RET(ctc_align_plan(V, c.pad, B, h_Tp, h_targets, h_n_targets, plan));
+  if (plan.labels > 0 && (!d_first || !d_last || !d_tok_lprob)) return SS_ERR_ARG;
+  SkScope sk_scope(m->sc->skws);
+  CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
+  hipStream_t s = (hipStream_t)stream;
+  RET(m->sc->mt_ws.ensure((size_t)plan.rows * V * sizeof(float)));
+  RET(m->sc->ws.ensure(plan.work_bytes()));
+  RET(m->sc->seg_buf.ensure(ctc_align_table_bytes(plan)));
+  float* logits = m->sc->mt_ws.f();
+  RET(linear(s, d_enc_out, c.enc_dim, plan.rows, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, logits, V));
+  m->sc->dbg_logits = logits; m->sc->dbg_rows = plan.rows; m->sc->dbg_cols = V;
+  return launch_ctc_align(logits, V, V, plan, h_targets, m->sc->seg_buf.p, m->sc->ws.p, d_results, d_path, d_first, d_last, d_tok_lprob,
+                          nullptr, s);
 }
 
 // Batched beam-1 search: all utterances start from [</s>] and advance in lockstep, one row per

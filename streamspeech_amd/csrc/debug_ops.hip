@@ -1,5 +1,6 @@
 // Op-level unit-test entry points (ss_op_*), test / A-B hooks (ss_debug_*) and the profiler's C ABI (ss_prof_*).
 #include "model_internal.hpp"
+#include "ctc_align.hpp"
 
 // =================================================================================================
 // op-level entry points
@@ -211,6 +212,22 @@ extern "C" int ss_op_masked_argmax_lprob(void* stream, const float* logits, int 
 extern "C" int ss_op_ctc_collapse_spans(void* stream, const int32_t* raw, const float* lprob, int T, int blank, int pad, int32_t* tokens,
                                         int32_t* index, int32_t* last, float* tok_lprob, int32_t* count, const int32_t* segs, int nseg) {
   return launch_ctc_collapse_spans(raw, lprob, T, blank, pad, tokens, index, last, tok_lprob, count, (hipStream_t)stream, segs, nseg);
+}
+// the two alignment kernels on the caller's logits; their scratch made here, one pair of buffers per stream of the calling thread
+// (as op_bind_wino's: a launch queued on another stream may still be reading the other pair)
+extern "C" int ss_op_ctc_align(void* stream, const float* d_logits, int ld, int V, int pad, int B, const int32_t* h_T,
+                               const int32_t* h_targets, const int32_t* h_n_targets, ss_ctc_align_result* d_results, int32_t* d_path,
+                               int32_t* d_first, int32_t* d_last, float* d_tok_lprob, float* d_frame_lprob) {
+  if (!d_logits || ld < V || !d_results) return SS_ERR_ARG;
+  CtcAlignPlan plan;
+  RET(ctc_align_plan(V, pad, B, h_T, h_targets, h_n_targets, plan));
+  if (plan.labels > 0 && (!d_first || !d_last || !d_tok_lprob)) return SS_ERR_ARG;
+  static thread_local std::map<hipStream_t, std::pair<DevBuf, DevBuf>> tmps;
+  auto& tmp = tmps[(hipStream_t)stream];
+  RET(tmp.first.ensure(ctc_align_table_bytes(plan)));
+  RET(tmp.second.ensure(plan.work_bytes()));
+  return launch_ctc_align(d_logits, ld, V, plan, h_targets, tmp.first.p, tmp.second.p, d_results, d_path, d_first, d_last, d_tok_lprob,
+                          d_frame_lprob, (hipStream_t)stream);
 }
 extern "C" int ss_op_dur_predict(void* stream, const float* logdur, const int32_t* forced, int K, int32_t* dur, int32_t* cum,
                                  const int32_t* segs, int nseg) {

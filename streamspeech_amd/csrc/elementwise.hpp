@@ -3,6 +3,8 @@
 #pragma once
 #include "common.hpp"
 
+struct ss_ctc_align_result;          // include/streamspeech_hip.h
+
 namespace ss {
 
 // y[m,:] = LayerNorm(x[m,:]) * gamma + beta   (eps 1e-5; torch.nn.LayerNorm semantics:
@@ -61,6 +63,18 @@ int launch_masked_argmax_lprob(const float* logits, int ld, int M, int N, int ma
                                hipStream_t stream);
 int launch_ctc_collapse_spans(const int* raw, const float* lprob, int T, int blank, int pad, int* tokens, int* index, int* last,
                               float* tok_lprob, int* count, hipStream_t stream, const int* segs = nullptr, int nseg = 0);
+
+// CTC forced alignment of given labels (ctc_align.hip; the plan, its checks and its limits: ctc_align.hpp).  Two launches over a
+// checked plan: per packed frame row the plain log-softmax at the utterance's states (lp, float32, the denominator arithmetic of
+// launch_masked_argmax_lprob), then one workgroup per utterance for the forward sum, the max-plus pass with 2-bit back-pointers, the
+// back-trace and each label's first / last frame and float32 sum of lp over its run in ascending frame order.  d_table
+// (ctc_align_table_bytes) and d_work (plan.work_bytes()) are the caller's scratch; path and frame_lprob (the path's lp per frame) may
+// be null.  An utterance's outputs are the same bits alone and at any place of any pack.
+struct CtcAlignPlan;
+size_t ctc_align_table_bytes(const CtcAlignPlan& p);
+int launch_ctc_align(const float* logits, int ld, int V, const CtcAlignPlan& p, const int32_t* h_targets, void* d_table, void* d_work,
+                     ss_ctc_align_result* results, int* path, int* first, int* last, float* tok_lprob, float* frame_lprob,
+                     hipStream_t stream);
 
 // emb_out[k,:] = table[codes[k],:]
 int launch_gather_rows(const int* idx, const float* table, int D, float* out, int n, hipStream_t stream, int rows);  // ids outside [0, rows) read row 0

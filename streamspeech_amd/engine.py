@@ -4,7 +4,7 @@ S2ST path runs in libstreamspeech_hip.so.
 """
 import ctypes as C
 import os
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -55,6 +55,17 @@ def _unpack_scored(host, T: List[int], return_raw: bool = False):
         out.append(rec + (host[off: off + t].tolist(),) if return_raw else rec)
         off += t
     return out
+
+
+class CtcAlignment(NamedTuple):
+    """One utterance of batch_ctc_align (ss_ctc_align_result and the spans behind it)."""
+    score: float            # log p(labels | audio): the CTC forward sum
+    viterbi_score: float    # the log-probability of the best path, the one path / first / last describe
+    status: int             # 0 aligned, 1 infeasible, 2 a NaN in a row of the utterance
+    path: Optional[List[int]]      # token id per frame, 0 = blank (-1 where there is no path); None without want_path
+    first: List[int]        # per label, the first ...
+    last: List[int]         # ... and the last frame of its run on the path (-1 where there is no path)
+    tok_lprob: np.ndarray   # per label, the float32 sum of the per-frame log-probability over that run (NaN where there is no path)
 
 
 def resample_ratio(sr_in: int, sr_out: int = 16000) -> Tuple[int, int, int]:
@@ -180,6 +191,37 @@ class BatchMixin:
             rec = (host[tot + off: tot + off + n].tolist(), host[2 * tot + off: 2 * tot + off + n].tolist())
             out.append(rec + (host[off: off + Tp[b]].tolist(),) if return_raw else rec)
             off += Tp[b]
+        return out
+
+    def batch_ctc_align(self, head: int, enc_packed: torch.Tensor, Tp: List[int], targets: List[List[int]],
+                        want_path: bool = True) -> List[CtcAlignment]:
+        """Forced alignment and score of the given label ids on a text head (ss_batch_ctc_align): per utterance where its labels lie
+        in its frames and log p(labels | audio).  The rows are packed as batch_ctc_greedy takes them; an empty label list is legal.
+        One buffer, one device-to-host copy.  The library refuses (SS_ERR_ARG, nothing launched) a label that is blank, pad, negative
+        or outside the vocabulary and more than L.CTC_ALIGN_MAX_LABELS labels or L.CTC_ALIGN_MAX_FRAMES frames per utterance."""
+        B, tot = len(Tp), sum(int(t) for t in Tp)
+        if len(targets) != B:
+            raise ValueError("one label list per utterance")
+        n = [len(t) for t in targets]
+        flat = [int(v) for t in targets for v in t]
+        nl = len(flat)
+        # int32 words: results [6 B] (two doubles and two ints each, first: 8-byte aligned) | path [tot] | first | last | tok_lprob [nl]
+        ibuf = torch.empty((6 * B + tot + 3 * nl,), dtype=torch.int32, device=self.device)
+        o_path, o_first = 6 * B, 6 * B + tot
+        L.check(self.lib.ss_batch_ctc_align(self.h, _stream(), head, B, _ptr(enc_packed), _i32(Tp), _i32(flat or [0]), _i32(n),
+                                            _ptr(ibuf), _ptr(ibuf[o_path:]) if want_path else None, _ptr(ibuf[o_first:]),
+                                            _ptr(ibuf[o_first + nl:]), _ptr(ibuf[o_first + 2 * nl:])), "ss_batch_ctc_align")
+        host = ibuf.cpu().numpy()
+        res = host[:6 * B].view(np.dtype([("score", "<f8"), ("viterbi", "<f8"), ("status", "<i4"), ("n_tokens", "<i4")]))
+        fl = host.view(np.float32)
+        out, r0, l0 = [], 0, 0
+        for b in range(B):
+            a, z = o_first + l0, o_first + l0 + n[b]
+            out.append(CtcAlignment(float(res["score"][b]), float(res["viterbi"][b]), int(res["status"][b]),
+                                    host[o_path + r0: o_path + r0 + int(Tp[b])].tolist() if want_path else None,
+                                    host[a:z].tolist(), host[a + nl:z + nl].tolist(), fl[a + 2 * nl:z + 2 * nl].copy()))
+            r0 += int(Tp[b])
+            l0 += n[b]
         return out
 
     def batch_mt_greedy(self, enc_packed: torch.Tensor, Tp: List[int], max_len: List[int], min_len: int = 1):
@@ -724,6 +766,10 @@ class HipModel(BatchMixin):
     def _ctc_unpack(self, host, Tp):
         n = int(host[3 * Tp])
         return host[Tp:Tp + n].tolist(), host[2 * Tp:2 * Tp + n].tolist(), host[:Tp], None
+
+    def ctc_align(self, head: int, enc_out: torch.Tensor, tokens: List[int], want_path: bool = True) -> CtcAlignment:
+        """Forced alignment of one utterance: the B = 1 call of batch_ctc_align."""
+        return self.batch_ctc_align(head, enc_out.contiguous(), [int(enc_out.shape[0])], [list(tokens)], want_path)[0]
 
     def ctc_greedy(self, head: int, enc_out: torch.Tensor, want_logits: bool = False, want_scores: bool = False):
         """-> (tokens list, frame index list, raw argmax tensor, logits or None); with want_scores three more: last frame per token

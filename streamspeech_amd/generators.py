@@ -53,6 +53,23 @@ class CTCDecoder:
         return [[hyp]]
 
 
+    @torch.no_grad()
+    def align(self, encoder_out, tokens, **kw):
+        """Forced alignment of the given label ids on this head: what generate takes plus the labels -> a hypothesis with `tokens`,
+        `index` (each token's first frame), `last`, `token_scores` (float32, the sum of the per-frame log-probability over the
+        token's run), `score` (log p(tokens | audio), the CTC forward sum), `viterbi_score` (the best path's), `status` (0 aligned,
+        1 infeasible, 2 NaN) and `path` (token id per frame, 0 = blank).  words.details_from_hyps / words_from_ctc take it as they
+        take generate's; an infeasible hypothesis has no tokens placed (`index` / `last` are -1, `token_scores` NaN)."""
+        enc = encoder_out["encoder_out"][0]
+        enc = enc[:, 0] if enc.dim() == 3 else enc
+        ids = [int(t) for t in (tokens.view(-1).tolist() if torch.is_tensor(tokens) else tokens)]
+        a = self.engine.ctc_align(self.head, enc.contiguous(), ids)
+        import numpy as np
+        return [[{"tokens": torch.tensor(ids, dtype=torch.long), "index": list(a.first), "last": list(a.last),
+                  "token_scores": torch.from_numpy(np.ascontiguousarray(a.tok_lprob, dtype=np.float32)), "score": a.score,
+                  "viterbi_score": a.viterbi_score, "status": a.status, "path": a.path, "attn": None, "alignment": None}]]
+
+
 class CTCSequenceGenerator:
     """agent/ctc_generator.py:26-123 -- NAR unit search over the T2U+unit-decoder stage
     (blank = tgt_dict.blank_index = 1004)."""

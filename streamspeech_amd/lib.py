@@ -64,6 +64,15 @@ class SSVadResult(C.Structure):
                 ("events", C.c_int32), ("mode", C.c_int32)]
 
 
+class SSCtcAlignResult(C.Structure):
+    """ss_ctc_align_result: what a forced alignment reports per utterance (24 bytes)."""
+    _fields_ = [("score", C.c_double), ("viterbi", C.c_double), ("status", C.c_int32), ("n_tokens", C.c_int32)]
+
+
+CTC_ALIGN_MAX_FRAMES = 1500     # SS_CTC_ALIGN_MAX_FRAMES / SS_CTC_ALIGN_MAX_LABELS of the header
+CTC_ALIGN_MAX_LABELS = 1500
+
+
 class SSOpAttnArgs(C.Structure):
     """ss_op_attn_args: AttnArgs (csrc/attention.hpp) field for field, pointers as device addresses."""
     _fields_ = [
@@ -236,6 +245,10 @@ SIGNATURES = {
     "ss_batch_encoder_forward": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _i, _vp, C.POINTER(C.c_int32)]),
     "ss_batch_ctc_greedy_scored": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ss_batch_ctc_greedy": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp]),
+    "ss_batch_ctc_align": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp,
+                                _vp, _vp]),
+    "ss_ctc_align_host": (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp,
+                               _vp, _vp, _vp]),
     "ss_batch_mt_greedy": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
                                 C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _vp, _i]),
     "ss_batch_mt_beam": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _f, _i,
@@ -327,6 +340,8 @@ SIGNATURES = {
     "ss_op_ctc_collapse": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
     "ss_op_masked_argmax_lprob": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ss_op_ctc_collapse_spans": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "ss_op_ctc_align": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp,
+                             _vp, _vp, _vp]),
     "ss_op_dur_predict": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
     "ss_op_repeat_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),
     "ss_op_embed_tokens": (_i, [_vp, _vp, _vp, _vp, _f, _i, _vp, _i, _i, _i, _i, _i]),

@@ -220,6 +220,9 @@ class Dictionary:
         self.symbols = ["<s>", "<pad>", "</s>", "<unk>"] + list(symbols) + list(extra or [])
         self.bos_index, self.pad_index, self.eos_index, self.unk_index = 0, 1, 2, 3
         self.blank_index = self.symbols.index("<blank>") if "<blank>" in self.symbols else None
+        self._index = {}
+        for i, sym in enumerate(self.symbols):
+            self._index.setdefault(sym, i)
 
     @classmethod
     def load(cls, path, extra=None):
@@ -240,6 +243,10 @@ class Dictionary:
 
     def __getitem__(self, i):
         return self.symbols[int(i)]
+
+    def index(self, symbol: str) -> int:
+        """fairseq Dictionary.index: the id of a symbol (its first occurrence), <unk>'s for one the dictionary does not hold."""
+        return self._index.get(symbol, self.unk_index)
 
     def pad(self):
         return self.pad_index

@@ -23,6 +23,12 @@ generate-<subset>.asr.words / .st.words, one `id\tword\tstart_ms\tend_ms\tconfid
 every other file is written as without the flag.  `T-` lines (generate.py:258-259) are written when
 the manifest carries target units (`tgt_audio` column, as the reference's S2UT manifests do).
 
+`--align-reference` answers the complementary question about the text the recipe ships with every utterance (the multitask
+manifests `<data>/<task>/<subset>.tsv`, columns `id` and `tgt_text`, pre-tokenised subwords): where do these words lie in this audio,
+and how likely does the model find them.  After the encoder of each batch one forced alignment per text head (ss_batch_ctc_align)
+over the rows that have a reference writes generate-<subset>.asr.ref.words / .st.ref.words (the columns of .words) and
+generate-<subset>.ref.scores (`id\thead\tn_tokens\tlog_likelihood\tviterbi_score\tstatus`); every other file is written as without it.
+
 The first-pass text search is greedy by default; `--beam-mt k` runs the reference's beam search (generator_mt with beam_size_mt = k,
 `--unkpen`, `--unnormalized`) on the GPU (ss_batch_mt_beam), and `--beam` is accepted for parity (the CTC unit generator has no search).
 `--no-repeat-ngram-size` and `--lenpen` are that generator's further controls (ss_batch_mt_beam_opts); either off its default runs the
@@ -77,7 +83,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              scores: bool = False, log=None, targets: Optional[Dict[int, Sequence[int]]] = None, beam_mt: int = 1,
              unk_penalty: float = 0.0, normalize: bool = True, pcm16_out: bool = False, speaker_id: int = -1,
              features: bool = False, word_times: bool = False, mt_alignment: bool = False, len_penalty: float = 1.0,
-             temperature: float = 1.0, no_repeat_ngram_size: int = 0) -> Dict[int, Dict]:
+             temperature: float = 1.0, no_repeat_ngram_size: int = 0,
+             references: Optional[Dict[str, Dict[int, Sequence[int]]]] = None) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
@@ -90,7 +97,11 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     the text decoder's cross-attention (words.words_from_attention), from one batch_mt_attention per batch after its search; every
     other file is the one written without it.
     len_penalty / temperature / no_repeat_ngram_size (--lenpen, no flag here, --no-repeat-ngram-size): the reference generator's
-    controls of the first-pass text search (ss_mt_search_opts); any of them off its default runs the beam search at beam_mt = 1 too."""
+    controls of the first-pass text search (ss_mt_search_opts); any of them off its default runs the beam search at beam_mt = 1 too.
+    references (--align-reference): {"asr": {sample id: label ids}, "st": {...}}, the reference text of each head as ids of its
+    dictionary.  One batch_ctc_align per head and batch over the rows that have one; writes generate-<subset>.asr.ref.words /
+    .st.ref.words and generate-<subset>.ref.scores (a line per sample and head: status aligned / infeasible / nan, or no_reference /
+    invalid_label / too_long / no_audio where nothing was aligned) and changes no other file."""
     from .engine import check_search_options
     search = {}
     if check_search_options(len_penalty, temperature, no_repeat_ngram_size) is not None:
@@ -105,6 +116,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     res_f = open(os.path.join(results_path, f"generate-{subset}.txt"), "w", encoding="utf-8")
     hyps: Dict[int, Dict] = {}
     words: Dict[str, Dict[int, list]] = {"asr": {}, "st": {}, "mt": {}}
+    ref_words: Dict[str, Dict[int, list]] = {"asr": {}, "st": {}}
+    ref_scores: Dict[Tuple[int, str], Tuple[int, float, float, str]] = {}
     if features:
         for sid, f in items:
             if f.dim() != 2 or f.shape[1] != 80 or f.dtype != torch.float32:
@@ -138,6 +151,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
         else:
             asr = model.batch_ctc_greedy(0, enc, Tp)
             st = model.batch_ctc_greedy(1, enc, Tp)
+        if references is not None:
+            _align_references(model, enc, Tp, ids, references, dicts, ref_words, ref_scores)
         # first-pass text search: max_len = min(int(max_len_a_mt * src_len + max_len_b_mt), max positions - 1) with
         # the task's defaults 0 / 200 (tasks/speech_to_speech_ctc.py:39-40 -> sequence_generator_multi_decoder_ctc.py
         # :130-131); src_len is the fbank frame count.  --max-len-a/-b configure the (NAR) unit generator, which has
@@ -208,12 +223,122 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
                 for sid in sorted(words[key]):
                     for w in words[key][sid]:
                         print(f"{sid}\t{w.text}\t{w.start_ms}\t{w.end_ms}\t{w.confidence:.6g}", file=f)
+    if references is not None:
+        for key in ("asr", "st"):
+            with open(os.path.join(results_path, f"generate-{subset}.{key}.ref.words"), "w", encoding="utf-8") as f:
+                for sid in sorted(ref_words[key]):
+                    for w in ref_words[key][sid]:
+                        print(f"{sid}\t{w.text}\t{w.start_ms}\t{w.end_ms}\t{w.confidence:.6g}", file=f)
+        with open(os.path.join(results_path, f"generate-{subset}.ref.scores"), "w", encoding="utf-8") as f:
+            for sid, _ in items:
+                for key in ("asr", "st"):
+                    ref = references.get(key, {}).get(sid)
+                    n, score, vit, status = ref_scores.get((sid, key), (0 if ref is None else len(ref), float("nan"), float("nan"),
+                                                                       "no_reference" if ref is None else "no_audio"))
+                    print(f"{sid}\t{key}\t{n}\t{score:.6f}\t{vit:.6f}\t{status}", file=f)
     if mt_alignment:
         with open(os.path.join(results_path, f"generate-{subset}.mt.words"), "w", encoding="utf-8") as f:
             for sid in sorted(words["mt"]):
                 for w in words["mt"][sid]:
                     print(f"{sid}\t{w.text}\t{w.start_ms}\t{w.end_ms}\t{w.focus:.6g}", file=f)
     return hyps
+
+
+ALIGN_STATUS = ("aligned", "infeasible", "nan")
+
+
+def _align_references(model, enc, Tp, ids, references, dicts, ref_words, ref_scores):
+    """One batch_ctc_align per text head over the rows of this batch that have a usable reference.  A reference the library would
+    refuse the whole call for (a blank, pad or out-of-vocabulary id; more labels than its limit) is recorded and left out."""
+    from .lib import CTC_ALIGN_MAX_FRAMES, CTC_ALIGN_MAX_LABELS
+    off = [0]
+    for t in Tp:
+        off.append(off[-1] + int(t))
+    nan = float("nan")
+    for head, (key, name) in enumerate((("asr", "source_unigram"), ("st", "ctc_target_unigram"))):
+        refs = references.get(key, {})
+        V, pad = (model.cfg.src_vocab, model.cfg.tgt_vocab)[head], model.cfg.pad      # the library's own refusals
+        rows = []
+        for b, sid in enumerate(ids):
+            if sid not in refs:
+                continue
+            y = [int(v) for v in refs[sid]]
+            if any(v <= 0 or v == pad or v >= V for v in y):
+                ref_scores[(sid, key)] = (len(y), nan, nan, "invalid_label")
+            elif len(y) > CTC_ALIGN_MAX_LABELS or int(Tp[b]) > CTC_ALIGN_MAX_FRAMES:
+                ref_scores[(sid, key)] = (len(y), nan, nan, "too_long")
+            else:
+                rows.append((b, y))
+        if not rows:
+            continue
+        enc_r = enc if len(rows) == len(ids) else torch.cat([enc[off[b]:off[b + 1]] for b, _ in rows], 0).contiguous()
+        got = model.batch_ctc_align(head, enc_r, [Tp[b] for b, _ in rows], [y for _, y in rows], want_path=False)
+        for (b, y), a in zip(rows, got):
+            ref_scores[(ids[b], key)] = (len(y), a.score, a.viterbi_score, ALIGN_STATUS[a.status])
+            if a.status == 0:
+                ref_words[key][ids[b]] = words_from_ctc(y, a.first, a.last, a.tok_lprob, dicts[name], finished=True)
+
+
+def multitask_text_dir(data_root: str, multitask_yaml: Optional[str], task: str) -> Optional[str]:
+    """The directory of a multitask task's text manifests: the `data:` entry of the task in the multitask YAML, or, where that path
+    does not exist here, `<data_root>/<its last component>` (as load_dictionaries resolves `dict:`).  None: the YAML names none."""
+    import yaml
+    from pathlib import Path
+    if multitask_yaml is None:
+        return None
+    mpath = multitask_yaml if os.path.isabs(multitask_yaml) else os.path.join(data_root, multitask_yaml)
+    if not os.path.exists(mpath):
+        return None
+    with open(mpath) as f:
+        cfg = yaml.load(f, Loader=yaml.BaseLoader) or {}
+    path = (cfg.get(task) or {}).get("data")
+    if not path:
+        return None
+    if not os.path.isdir(path):
+        path = os.path.join(data_root, Path(path).parts[-1])
+    return path
+
+
+def load_multitask_text(directory: str, subset: str) -> Dict[str, List[str]]:
+    """`<directory>/<subset>.tsv` of a multitask task (fairseq TextTargetMultitaskData: columns `id` and `tgt_text`, read as the
+    recipe's manifests are -- tab-separated, no quoting) -> {id: the pre-tokenised subwords of tgt_text}."""
+    import csv
+    out = {}
+    with open(os.path.join(directory, subset + ".tsv"), encoding="utf-8", newline="") as f:
+        for row in csv.DictReader(f, delimiter="\t", quotechar=None, doublequote=False, lineterminator="\n", quoting=csv.QUOTE_NONE):
+            out[row["id"]] = (row["tgt_text"] or "").split()
+    return out
+
+
+def load_manifest_ids(path: str) -> Dict[int, str]:
+    """{row index (the sample id load_manifest gives): the row's `id` cell} of a manifest."""
+    out = {}
+    with open(path, encoding="utf-8") as f:
+        header = f.readline().rstrip("\n").split("\t")
+        col = header.index("id")
+        for i, line in enumerate(f):
+            parts = line.rstrip("\n").split("\t")
+            if len(parts) > col:
+                out[i] = parts[col]
+    return out
+
+
+def load_references(data_root: str, multitask_yaml: Optional[str], subset: str, dicts) -> Optional[Dict[str, Dict[int, List[int]]]]:
+    """--align-reference: the reference label ids of both text heads per sample id, from the multitask manifests of `source_unigram`
+    and `ctc_target_unigram` joined with the manifest's `id` column; a piece the dictionary does not hold becomes <unk>.  None when
+    the YAML names no data directory for either task."""
+    dirs = {key: multitask_text_dir(data_root, multitask_yaml, name)
+            for key, name in (("asr", "source_unigram"), ("st", "ctc_target_unigram"))}
+    if not any(dirs.values()):
+        return None
+    names = load_manifest_ids(os.path.join(data_root, subset + ".tsv"))
+    out: Dict[str, Dict[int, List[int]]] = {"asr": {}, "st": {}}
+    for key, name in (("asr", "source_unigram"), ("st", "ctc_target_unigram")):
+        if dirs[key] is None:
+            continue
+        text = load_multitask_text(dirs[key], subset)
+        out[key] = {i: [dicts[name].index(p) for p in text[n]] for i, n in names.items() if n in text}
+    return out
 
 
 def _pack_batch(model, wavs: List[torch.Tensor]):
@@ -337,6 +462,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mt-alignment", action="store_true",
                     help="also write generate-<subset>.mt.words: id, word, start_ms, end_ms, focus per word of the D- hypothesis, placed in "
                          "source time by the arg-max of the text decoder's cross-attention (one extra decoder pass per batch)")
+    ap.add_argument("--align-reference", action="store_true",
+                    help="also align the recipe's reference text (the multitask manifests <task data>/<gen-subset>.tsv of source_unigram "
+                         "and ctc_target_unigram) to the audio on both CTC heads: writes generate-<subset>.asr.ref.words / .st.ref.words "
+                         "(id, word, start_ms, end_ms, confidence) and generate-<subset>.ref.scores (id, head, n_tokens, log_likelihood, "
+                         "viterbi_score, status); needs a manifest")
     ap.add_argument("--num-shards", type=int, default=int(os.environ.get("WORLD_SIZE", "1")))
     ap.add_argument("--shard-id", type=int, default=int(os.environ.get("RANK", "0")))
     ap.add_argument("--device", default="cuda:%s" % os.environ.get("LOCAL_RANK", "0"))
@@ -369,6 +499,10 @@ def main(argv: Optional[List[str]] = None):
         check_search_options(a.lenpen, 1.0, a.no_repeat_ngram_size)
     except ValueError as e:
         ap.error(str(e))
+    if a.align_reference and (a.wav_list or a.synthetic > 0 or not a.data):
+        ap.error("--align-reference needs the manifest's ids: it cannot be combined with --wav-list or --synthetic")
+    if a.align_reference and not any(multitask_text_dir(a.data, a.multitask_config_yaml, t) for t in ("source_unigram", "ctc_target_unigram")):
+        ap.error("--align-reference: the multitask YAML names no `data:` directory for source_unigram or ctc_target_unigram")
 
     # model / dictionaries / CMVN exactly as the agent loads them (agent :355-420)
     ns = argparse.Namespace(config_yaml=a.config_yaml, multitask_config_yaml=a.multitask_config_yaml,
@@ -449,6 +583,7 @@ def main(argv: Optional[List[str]] = None):
         if len(e) > 2 and e[2] != 16000:
             pcm = model.resample(pcm, e[2], 16000)
         items.append((e[0], pcm))
+    references = load_references(a.data, a.multitask_config_yaml, a.gen_subset, holder.dict) if a.align_reference else None
     sub = a.gen_subset if a.num_shards == 1 else f"{a.gen_subset}.shard{a.shard_id}"
     hyps = generate(model, voc, items, holder.dict, a.results_path, sub, a.batch_size, a.max_tokens, a.max_len_a,
                     a.max_len_b, a.max_len_a_mt, a.max_len_b_mt, a.dur_prediction, not a.no_wav,
@@ -457,6 +592,7 @@ def main(argv: Optional[List[str]] = None):
                     **({"pcm16_out": True} if a.pcm16_io else {}), **({"speaker_id": a.speaker_id} if voc.num_speakers else {}),
                     **({"features": True} if is_feat else {}), **({"word_times": True} if a.word_times else {}),
                     **({"mt_alignment": True} if a.mt_alignment else {}),
+                    **({"references": references} if references is not None else {}),
                     **({"len_penalty": a.lenpen, "no_repeat_ngram_size": a.no_repeat_ngram_size}
                        if (a.lenpen, a.no_repeat_ngram_size) != (1.0, 0) else {}))
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
