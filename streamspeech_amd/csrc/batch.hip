@@ -181,6 +181,36 @@ extern "C" int ss_batch_ctc_align(ss_model* m, void* stream, int head, int B, co
                           nullptr, s);
 }
 
+// The lock-step decode step of the three text searches (ss_batch_mt_greedy, ss_batch_mt_continue, beam.hip's beam_search; declared
+// in model_internal.hpp).  What differs between them is in `a`; when the host looks at the tokens, what follows the logits (masked
+// arg-max, or top-k and merge) and where the states end up stay with each search.
+int mt_decode_rows(ss_model* m, hipStream_t s, const MtRowsWs& w, const MtRowsStep& a) {
+  const ss_config& c = m->cfg;
+  const int D = c.dec_dim, V = c.tgt_vocab, H = c.dec_heads, n = a.rows;
+  const float emb_scale = sqrtf((float)D);
+  if (a.row_pos)
+    RET(launch_embed_tokens_rows(a.tok, m->mt_emb, m->mt_pos, c.max_tgt_pos, emb_scale, a.ci + c.pad + 1, a.row_pos, w.x, n, D, s,
+                                 a.row_pad, V));
+  else
+    RET(launch_embed_tokens(a.tok, m->mt_emb, m->mt_pos, emb_scale, a.ci + c.pad + 1, w.x, n, D, s, 0, -1, V));
+  for (int l = 0; l < c.mt_layers; ++l) {
+    float* cache = m->sc->bmt_self.f() + (size_t)l * n * a.cache_ld * 3 * D;
+    float* rows = cache + (size_t)a.ci * 3 * D;                      // search row r at + r * cache_ld * 3D: straight into its cache
+    AttnArgs at;
+    at.Q = rows; at.ldq = a.cache_ld * 3 * D; at.K = cache + D; at.V = cache + 2 * D; at.ldk = at.ldv = 3 * D;
+    at.O = w.h; at.ldo = D; at.H = H; at.scale = 1.f; at.causal = 0;   // the key range holds exactly the visible keys
+    at.segs = a.self_segs; at.nseg = n; at.max_q = 1;
+    at.anc = a.anc; at.anc_ld = a.anc_ld; at.anc_slots = a.anc_slots;
+    AttnArgs ac;
+    ac.Q = w.q2; ac.ldq = D; ac.K = m->sc->mt_cross.f() + (size_t)l * a.n_enc * 2 * D; ac.V = ac.K + D; ac.ldk = ac.ldv = 2 * D;
+    ac.O = w.h; ac.ldo = D; ac.H = H; ac.scale = 1.f; ac.segs = a.cross_segs; ac.nseg = n; ac.max_q = 1;
+    RET(dec_layer_ex(s, c, m->mt[l], w.x, n, rows, a.cache_ld * 3 * D, at, &ac, w.h, w.q2, w.ff));
+  }
+  RET(launch_layernorm(w.x, D, a.states, a.states_ld, m->mt_ln.g, m->mt_ln.b, n, D, 1e-5f, s));
+  Lin proj{m->mt_emb, nullptr};                                      // tied output projection, no bias
+  return linear(s, a.states, a.states_ld, n, proj, V, D, w.logits, V);
+}
+
 // Batched beam-1 search: all utterances start from [</s>] and advance in lockstep, one row per
 // utterance (M = B GEMMs stream every decoder weight once per step for the whole batch).
 extern "C" int ss_batch_mt_greedy(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp,
@@ -191,7 +221,7 @@ extern "C" int ss_batch_mt_greedy(ss_model* m, void* stream, int B, const float*
   CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);     // cross K|V over the packed encoder rows
   hipStream_t s = (hipStream_t)stream;
   const ss_config& c = m->cfg;
-  const int D = c.dec_dim, F = c.dec_ffn, V = c.tgt_vocab, H = c.dec_heads;
+  const int D = c.dec_dim, F = c.dec_ffn, V = c.tgt_vocab;
   int Lmax = 0;
   for (int b = 0; b < B; ++b) {
     if (h_Tp[b] <= 0 || h_max_len[b] < 0) return SS_ERR_ARG;   // an utterance without encoder rows has nothing to attend to
@@ -202,17 +232,11 @@ extern "C" int ss_batch_mt_greedy(ss_model* m, void* stream, int B, const float*
   const Offsets oe = prefix(h_Tp, B);
   // cross-attention K/V for every layer over the packed encoder rows
   RET(m->sc->mt_cross.ensure((size_t)c.mt_layers * oe.total * 2 * D * sizeof(float)));
-  for (int l = 0; l < c.mt_layers; ++l)
-    RET(linear(s, d_enc_out, c.enc_dim, oe.total, m->mt[l].cross_kv, 2 * D, c.enc_dim,
-               m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D, 2 * D));
+  RET(mt_cross_kv(m, s, d_enc_out, oe.total));
   // caches / scratch
   RET(m->sc->bmt_self.ensure((size_t)c.mt_layers * B * Lcap * 3 * D * sizeof(float)));
-  RET(m->sc->mt_ws.ensure(((size_t)B * (3 * D + F + V)) * sizeof(float)));
-  float* x = m->sc->mt_ws.f();
-  float* h = x + (size_t)B * D;
-  float* q2 = h + (size_t)B * D;
-  float* ff = q2 + (size_t)B * D;
-  float* logits = ff + (size_t)B * F;
+  RET(m->sc->mt_ws.ensure(MtRowsWs::floats(B, D, F, V) * sizeof(float)));
+  const MtRowsWs w(m->sc->mt_ws.f(), B, D, F);
   // int tables: tokens [Lcap+1][B], max_len [B], cross segs [B][4], self segs per step [Lcap][B][4]
   const size_t n_tok = (size_t)(Lcap + 1) * B;
   RET(m->sc->seg_buf.ensure((n_tok + B + 4 * B + (size_t)Lcap * 4 * B) * sizeof(int)));
@@ -239,25 +263,13 @@ extern "C" int ss_batch_mt_greedy(ss_model* m, void* stream, int B, const float*
   // heuristic would take the GEMV, with B = 64 another wave arrangement for the vocabulary projection)
   CanonScope decode_scope(m->pack_invariant ? CANON_SMALLM : CANON_NONE);
   while (true) {
-    // feed position `step` of every utterance
-    RET(launch_embed_tokens(tok + (size_t)step * B, m->mt_emb, m->mt_pos, sqrtf((float)D), step + c.pad + 1, x, B, D, s, 0, -1, c.tgt_vocab));
-    for (int l = 0; l < c.mt_layers; ++l) {
-      float* cache = m->sc->bmt_self.f() + (size_t)l * B * Lcap * 3 * D;
-      float* rows = cache + (size_t)step * 3 * D;                    // row b at + b*Lcap*3D
-      AttnArgs at;
-      at.Q = rows; at.ldq = Lcap * 3 * D; at.K = cache + D; at.V = cache + 2 * D; at.ldk = at.ldv = 3 * D;
-      at.O = h; at.ldo = D; at.H = H; at.scale = 1.f; at.causal = 0;   // cache holds exactly the visible keys
-      at.segs = d_self + (size_t)step * 4 * B; at.nseg = B; at.max_q = 1;
-      AttnArgs ac;
-      ac.Q = q2; ac.ldq = D; ac.K = m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D; ac.V = ac.K + D; ac.ldk = ac.ldv = 2 * D;
-      ac.O = h; ac.ldo = D; ac.H = H; ac.scale = 1.f; ac.segs = d_cross; ac.nseg = B; ac.max_q = 1;
-      RET(dec_layer_ex(s, c, m->mt[l], x, B, rows, Lcap * 3 * D, at, &ac, h, q2, ff));
-    }
-    float* frow = d_feats + (size_t)step * D;                         // utterance b at + b*feat_rows*D
-    RET(launch_layernorm(x, D, frow, feat_rows * D, m->mt_ln.g, m->mt_ln.b, B, D, 1e-5f, s));
-    Lin proj{m->mt_emb, nullptr};
-    RET(linear(s, frow, feat_rows * D, B, proj, V, D, logits, V));
-    RET(launch_masked_argmax(logits, V, B, V, c.pad, step < min_len ? c.eos : -1, -1, -1, tok + (size_t)(step + 1) * B, s,
+    // feed position `step` of every utterance; its states go to d_feats in place (utterance b at + b*feat_rows*D)
+    MtRowsStep a;
+    a.rows = B; a.cache_ld = Lcap; a.ci = step; a.tok = tok + (size_t)step * B;
+    a.self_segs = d_self + (size_t)step * 4 * B; a.cross_segs = d_cross; a.n_enc = oe.total;
+    a.states = d_feats + (size_t)step * D; a.states_ld = feat_rows * D;
+    RET(mt_decode_rows(m, s, w, a));
+    RET(launch_masked_argmax(w.logits, V, B, V, c.pad, step < min_len ? c.eos : -1, -1, -1, tok + (size_t)(step + 1) * B, s,
                              d_maxlen, step, c.eos));
     ++step;                                                           // tokens of row `step` now exist
     const bool last = step > Lmax;
@@ -515,7 +527,7 @@ extern "C" int ss_batch_mt_continue(ss_model* m, void* stream, int B, const floa
                                     int32_t* h_n_feats) {
   if (!m || !d_enc_out || !h_out_tokens || !h_n_out || !d_feats) return SS_ERR_ARG;
   const ss_config& c = m->cfg;
-  const int D = c.dec_dim, F = c.dec_ffn, V = c.tgt_vocab, H = c.dec_heads;
+  const int D = c.dec_dim, F = c.dec_ffn, V = c.tgt_vocab;
   McPlan P;
   RET(mt_continue_plan(B, h_Tp, h_prefix, h_n_prefix, h_max_len, min_len, out_stride, feat_rows, c.max_tgt_pos, V, c.eos, P));
   const int S = P.S, Tn = P.Tn, Np = P.Np, np_max = P.np_max, Lcap = P.Lcap, Tr = P.Tr;
@@ -526,7 +538,8 @@ extern "C" int ss_batch_mt_continue(ss_model* m, void* stream, int B, const floa
   RET(m->sc->bmt_self.ensure((size_t)c.mt_layers * B * Lcap * 3 * D * sizeof(float)));
   const size_t np = (size_t)Np;
   RET(m->sc->ws.ensure((np * (4 * D + 3 * D + F)) * sizeof(float)));
-  RET(m->sc->mt_ws.ensure(((size_t)B * (4 * D + F + V) + (size_t)B * Tr * D) * sizeof(float)));
+  // the decode rows (with a gap of B rows before the logits) | their states [B][Tr][D], scattered to d_feats at the end
+  RET(m->sc->mt_ws.ensure((MtRowsWs::floats(B, D, F, V, (size_t)B * D) + (size_t)B * Tr * D) * sizeof(float)));
   // int tables: tokens [Tn + 2][B] | the plan's tables (mt_continue_plan) | lock-step feature map [B * Tr]
   const size_t n_tok = (size_t)(Tn + 2) * B;
   const size_t n_int = n_tok + P.head.size() + (size_t)B * Tr;
@@ -550,11 +563,9 @@ extern "C" int ss_batch_mt_continue(ss_model* m, void* stream, int B, const floa
   int* d_plast = d_pfeat + np;
   int* d_lfeat = d_plast + B;
   RET(upload(s, d_maxlen, P.head));                      // everything from max_len' to the last-row table, one upload
-  const float emb_scale = sqrtf((float)D);
-  // cross-attention K/V of every layer over the packed encoder rows
-  for (int l = 0; l < c.mt_layers; ++l)
-    RET(linear(s, d_enc_out, c.enc_dim, oe.total, m->mt[l].cross_kv, 2 * D, c.enc_dim,
-               m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D, 2 * D));
+  RET(mt_cross_kv(m, s, d_enc_out, oe.total));           // of every layer over the packed encoder rows
+  const MtRowsWs w(m->sc->mt_ws.f(), B, D, F, (size_t)B * D);
+  float* lfeat = w.logits + (size_t)B * V;               // [B][Tr][D]
   // ---- the prefix pass ----
   {
     const float* pfo = nullptr;
@@ -564,18 +575,11 @@ extern "C" int ss_batch_mt_continue(ss_model* m, void* stream, int B, const floa
     RET(launch_gather_rows(d_plast, pfo, D, hp, B, s, Np));
     // the first generated token: projected as a lock-step row (one row per session, CANON_SMALLM)
     CanonScope row_scope(m->pack_invariant ? CANON_SMALLM : CANON_NONE);
-    float* logits = m->sc->mt_ws.f() + (size_t)B * (4 * D + F);
     Lin proj{m->mt_emb, nullptr};
-    RET(linear(s, hp, D, B, proj, V, D, logits, V));
-    RET(launch_masked_argmax(logits, V, B, V, c.pad, -1, -1, -1, tok + B, s, d_maxlen, S, c.eos, d_minlen, c.eos));
+    RET(linear(s, hp, D, B, proj, V, D, w.logits, V));
+    RET(launch_masked_argmax(w.logits, V, B, V, c.pad, -1, -1, -1, tok + B, s, d_maxlen, S, c.eos, d_minlen, c.eos));
   }
   // ---- the lock-step loop ----
-  float* x = m->sc->mt_ws.f();
-  float* h = x + (size_t)B * D;
-  float* q2 = h + (size_t)B * D;
-  float* ff = q2 + (size_t)B * D;
-  float* logits = ff + (size_t)B * F + (size_t)B * D;
-  float* lfeat = logits + (size_t)B * V;                             // [B][Tr][D]: the decode rows' states, scattered at the end
   std::vector<int> host_tok(n_tok, c.pad);
   std::vector<int> eos_at(B, -1);
   int checked = 1;                                                   // token rows [1, checked) already on the host
@@ -597,26 +601,14 @@ extern "C" int ss_batch_mt_continue(ss_model* m, void* stream, int B, const floa
       checked = it + 2;
       if (all_done || last) break;
     }
-    const int ci = S + 1 + it;                                       // cache index fed by every row
-    RET(launch_embed_tokens_rows(tok + (size_t)(it + 1) * B, m->mt_emb, m->mt_pos, c.max_tgt_pos, emb_scale, ci + c.pad + 1, d_rowpos,
-                                 x, B, D, s, c.pad, V));
-    for (int l = 0; l < c.mt_layers; ++l) {
-      float* cache = m->sc->bmt_self.f() + (size_t)l * B * Lcap * 3 * D;
-      float* rows = cache + (size_t)ci * 3 * D;                      // row b at + b*Lcap*3D
-      AttnArgs at;
-      at.Q = rows; at.ldq = Lcap * 3 * D; at.K = cache + D; at.V = cache + 2 * D; at.ldk = at.ldv = 3 * D;
-      at.O = h; at.ldo = D; at.H = H; at.scale = 1.f; at.causal = 0;   // the key range holds exactly the visible keys
-      at.segs = d_lself + (size_t)it * 4 * B; at.nseg = B; at.max_q = 1;
-      AttnArgs ac;
-      ac.Q = q2; ac.ldq = D; ac.K = m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D; ac.V = ac.K + D; ac.ldk = ac.ldv = 2 * D;
-      ac.O = h; ac.ldo = D; ac.H = H; ac.scale = 1.f; ac.segs = d_cross; ac.nseg = B; ac.max_q = 1;
-      RET(dec_layer_ex(s, c, m->mt[l], x, B, rows, Lcap * 3 * D, at, &ac, h, q2, ff));
-    }
-    float* frow = lfeat + (size_t)it * D;
-    RET(launch_layernorm(x, D, frow, Tr * D, m->mt_ln.g, m->mt_ln.b, B, D, 1e-5f, s));
-    Lin proj{m->mt_emb, nullptr};
-    RET(linear(s, frow, Tr * D, B, proj, V, D, logits, V));
-    RET(launch_masked_argmax(logits, V, B, V, c.pad, -1, -1, -1, tok + (size_t)(it + 2) * B, s, d_maxlen, ci, c.eos, d_minlen, c.eos));
+    MtRowsStep a;
+    a.rows = B; a.cache_ld = Lcap; a.ci = S + 1 + it;                // the cache index every row feeds
+    a.tok = tok + (size_t)(it + 1) * B; a.row_pos = d_rowpos; a.row_pad = c.pad;
+    a.self_segs = d_lself + (size_t)it * 4 * B; a.cross_segs = d_cross; a.n_enc = oe.total;
+    a.states = lfeat + (size_t)it * D; a.states_ld = Tr * D;
+    RET(mt_decode_rows(m, s, w, a));
+    RET(launch_masked_argmax(w.logits, V, B, V, c.pad, -1, -1, -1, tok + (size_t)(it + 2) * B, s, d_maxlen, a.ci, c.eos, d_minlen,
+                             c.eos));
   }
   // outputs; the decode rows' states go to their positions start_b + 1 .. in d_feats (one launch)
   std::vector<int> fmap((size_t)B * Tr, -1);
@@ -714,9 +706,7 @@ static int batch_mt_features(ss_model* m, void* stream, int B, const float* d_en
   int* dt = (int*)m->sc->seg_buf.p;
   RET(upload(s, dt, tab));
   const int *d_self = dt, *d_cross = dt + 4 * B, *d_tail = dt + 8 * B, *d_tok = dt + 9 * B, *d_pos = d_tok + np, *d_frow = d_pos + np;
-  for (int l = 0; l < c.mt_layers; ++l)
-    RET(linear(s, d_enc_out, c.enc_dim, oe.total, m->mt[l].cross_kv, 2 * D, c.enc_dim,
-               m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D, 2 * D));
+  RET(mt_cross_kv(m, s, d_enc_out, oe.total));
   const float* pfo = nullptr;
   RET(mt_prefix_pass(m, s, B, Np, op.mx, oe.total, d_tok, d_pos, d_self, d_cross, d_tail, nullptr, 0, &pfo));
   if (d_feats) RET(launch_scatter_rows(d_frow, pfo, D, d_feats, D, D, Np, B * feat_rows, s));

@@ -542,7 +542,7 @@ int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_o
                 int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows,
                 const SearchOpts& so) {
   const ss_config& c = m->cfg;
-  const int D = c.dec_dim, F = c.dec_ffn, V = c.tgt_vocab, H = c.dec_heads, k = beam, R = B * beam;
+  const int D = c.dec_dim, F = c.dec_ffn, V = c.tgt_vocab, k = beam, R = B * beam;
   const int Lc = P.Lc, Tn = P.Tn, c0 = P.c0, Np = P.Np;
   // the option kernels are chosen here, once: a search without options launches what it always launched
   const bool topk_opts = so.ngram >= 2 || so.temp != 1.f, merge_lenpen = normalize && so.len_penalty != 1.f;
@@ -559,22 +559,17 @@ int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_o
   RET(m->sc->mt_cross.ensure((size_t)c.mt_layers * oe.total * 2 * D * sizeof(float)));
   RET(m->sc->bmt_self.ensure((size_t)c.mt_layers * R * Lc * 3 * D * sizeof(float)));
   RET(m->sc->bmb_feat.ensure((size_t)R * Lc * D * sizeof(float)));
-  RET(m->sc->mt_ws.ensure(((size_t)R * (3 * D + F + V) + (P.pm ? (size_t)R * D : 0)) * sizeof(float)));
+  RET(m->sc->mt_ws.ensure((MtRowsWs::floats(R, D, F, V) + (P.pm ? (size_t)R * D : 0)) * sizeof(float)));
   RET(m->sc->bmb_state.ensure(n_state * sizeof(int)));
   // prefix pass: its workspace (mt_prefix_pass) | logits [Np][V] | forced log-probabilities [Np] | their positional scores [Np]
   if (Np > 0) RET(m->sc->ws.ensure((np * (7 * D + F) + np * V + 2 * np) * sizeof(float)));
   // int tables: the plan's tables | feature gather [B][feat_rows]
   RET(m->sc->seg_buf.ensure((P.tab.size() + (size_t)B * feat_rows) * sizeof(int)));
 
-  for (int l = 0; l < c.mt_layers; ++l)
-    RET(linear(s, d_enc_out, c.enc_dim, oe.total, m->mt[l].cross_kv, 2 * D, c.enc_dim,
-               m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D, 2 * D));
+  RET(mt_cross_kv(m, s, d_enc_out, oe.total));
   float* feat = m->sc->bmb_feat.f();           // [R][Lc][D] post-LN decoder states of every slot and cache index
-  float* x = m->sc->mt_ws.f();
-  float* h = x + (size_t)R * D;
-  float* q2 = h + (size_t)R * D;
-  float* ff = q2 + (size_t)R * D;
-  float* logits = ff + (size_t)R * F;
+  const MtRowsWs rows_ws(m->sc->mt_ws.f(), R, D, F);
+  float* logits = rows_ws.logits;
   float* last_rows = logits + (size_t)R * V;   // beam 1: each utterance's last prefix-pass state
   int* w = (int*)m->sc->bmb_state.p;
   BeamState st;
@@ -643,28 +638,16 @@ int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_o
   CanonScope decode_scope(m->pack_invariant ? CANON_SMALLM : CANON_NONE);   // the greedy twin's decode-row GEMM form
   while (true) {
     const int ci = c0 + step;                  // cache index every slot writes at this step
-    Lin proj{m->mt_emb, nullptr};
     if (P.pm && step == 0) {                   // beam 1: the first free step reads the last prefix-pass row, projected as a lock-step row
+      Lin proj{m->mt_emb, nullptr};
       RET(linear(s, last_rows, D, R, proj, V, D, logits, V));
-    } else {
-      RET(launch_embed_tokens_rows(st.tok + (size_t)step * R, m->mt_emb, m->mt_pos, c.max_tgt_pos, sqrtf((float)D), ci + c.pad + 1,
-                                   d_rowpos, x, R, D, s, -1, V));
-      for (int l = 0; l < c.mt_layers; ++l) {
-        float* cache = m->sc->bmt_self.f() + (size_t)l * R * Lc * 3 * D;
-        float* rows = cache + (size_t)ci * 3 * D;                      // slot r at + r*Lc*3D: written once, never reordered
-        AttnArgs at;
-        at.Q = rows; at.ldq = Lc * 3 * D; at.K = cache + D; at.V = cache + 2 * D; at.ldk = at.ldv = 3 * D;
-        at.O = h; at.ldo = D; at.H = H; at.scale = 1.f; at.causal = 0;
-        at.segs = d_self + (size_t)step * 4 * R; at.nseg = R; at.max_q = 1;
-        at.anc = st.anc + (size_t)(step & 1) * R * Lc; at.anc_ld = Lc; at.anc_slots = R;
-        AttnArgs ac;
-        ac.Q = q2; ac.ldq = D; ac.K = m->sc->mt_cross.f() + (size_t)l * oe.total * 2 * D; ac.V = ac.K + D; ac.ldk = ac.ldv = 2 * D;
-        ac.O = h; ac.ldo = D; ac.H = H; ac.scale = 1.f; ac.segs = d_cross; ac.nseg = R; ac.max_q = 1;
-        RET(dec_layer_ex(s, c, m->mt[l], x, R, rows, Lc * 3 * D, at, &ac, h, q2, ff));
-      }
-      float* frow = feat + (size_t)ci * D;
-      RET(launch_layernorm(x, D, frow, Lc * D, m->mt_ln.g, m->mt_ln.b, R, D, 1e-5f, s));
-      RET(linear(s, frow, Lc * D, R, proj, V, D, logits, V));
+    } else {                                   // a slot's cache rows are written once and never reordered: the ancestor table finds them
+      MtRowsStep a;
+      a.rows = R; a.cache_ld = Lc; a.ci = ci; a.tok = st.tok + (size_t)step * R; a.row_pos = d_rowpos; a.row_pad = -1;
+      a.self_segs = d_self + (size_t)step * 4 * R; a.cross_segs = d_cross; a.n_enc = oe.total;
+      a.anc = st.anc + (size_t)(step & 1) * R * Lc; a.anc_ld = Lc; a.anc_slots = R;
+      a.states = feat + (size_t)ci * D; a.states_ld = Lc * D;
+      RET(mt_decode_rows(m, s, rows_ws, a));
     }
     if (topk_opts) {
       TopkOpts to;
@@ -826,11 +809,27 @@ extern "C" int ss_batch_mt_beam_continue_plan(int B, int beam, const int32_t* h_
 }
 
 // ---- op-level entry points of the kernels above (include/streamspeech_hip.h; tests/test_glue_ops_gpu.py) ----
+// The limits both top-k ops share: the search's own (beam_continue_plan).
+static int op_topk_limits(int R, int V, int k) {
+  if (R <= 0 || k < 1 || k > kMaxBeam || R % k != 0) return SS_ERR_ARG;
+  if (V < 2 * k + 1 || (size_t)V * sizeof(float) > 65536) return SS_ERR_ARG;
+  return SS_OK;
+}
+
+// The checks of both merge ops, and their state as the kernels take it.
+static int op_beam_state(const ss_op_beam_state* x, int B, int k, int Lc, int t_step, int c0, BeamState& st) {
+  if (!x || B <= 0 || k < 1 || k > kMaxBeam || t_step < 0 || c0 < 0 || c0 + t_step + 2 > Lc) return SS_ERR_ARG;
+  st.tok = x->tok; st.cum = x->cum; st.anc = x->anc; st.cand_s = x->cand_s; st.cand_t = x->cand_t; st.ignore = x->ignore;
+  st.done = x->done; st.max_len = x->max_len; st.npre = x->npre;
+  st.fin_cnt = x->fin_cnt; st.fin_score = x->fin_score; st.fin_len = x->fin_len; st.fin_tok = x->fin_tok; st.fin_pos = x->fin_pos;
+  st.fin_anc = x->fin_anc;
+  return SS_OK;
+}
+
 extern "C" int ss_op_beam_topk(void* stream, const float* logits, int R, int V, int k, int t_step, int min_len, const int32_t* max_len,
                                const int32_t* npre, const int32_t* done, const float* cum, int pad, int unk, int eos, float unk_pen,
                                float* cand_s, int32_t* cand_t) {
-  if (R <= 0 || k < 1 || k > kMaxBeam || R % k != 0) return SS_ERR_ARG;
-  if (V < 2 * k + 1 || (size_t)V * sizeof(float) > 65536) return SS_ERR_ARG;     // the search's own limits (beam_continue_plan)
+  RET(op_topk_limits(R, V, k));
   hipLaunchKernelGGL(beam_topk_kernel, dim3(R), dim3(256), V * sizeof(float), (hipStream_t)stream, logits, V, k, t_step, min_len,
                      max_len, npre, done, cum, pad, unk, eos, unk_pen, cand_s, cand_t);
   SS_LAUNCH_CHECK();
@@ -839,12 +838,8 @@ extern "C" int ss_op_beam_topk(void* stream, const float* logits, int R, int V, 
 
 extern "C" int ss_op_beam_merge(void* stream, const ss_op_beam_state* x, int B, int k, int Lc, int V, int t_step, int c0, int eos,
                                 int normalize) {
-  if (!x || B <= 0 || k < 1 || k > kMaxBeam || t_step < 0 || c0 < 0 || c0 + t_step + 2 > Lc) return SS_ERR_ARG;
   BeamState st;
-  st.tok = x->tok; st.cum = x->cum; st.anc = x->anc; st.cand_s = x->cand_s; st.cand_t = x->cand_t; st.ignore = x->ignore;
-  st.done = x->done; st.max_len = x->max_len; st.npre = x->npre;
-  st.fin_cnt = x->fin_cnt; st.fin_score = x->fin_score; st.fin_len = x->fin_len; st.fin_tok = x->fin_tok; st.fin_pos = x->fin_pos;
-  st.fin_anc = x->fin_anc;
+  RET(op_beam_state(x, B, k, Lc, t_step, c0, st));
   hipLaunchKernelGGL(beam_merge_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, st, k, B * k, Lc, V, t_step, c0, eos,
                      normalize ? 1 : 0);
   SS_LAUNCH_CHECK();
@@ -879,8 +874,8 @@ extern "C" int ss_op_beam_topk_opts(void* stream, const float* logits, int R, in
   RET(read_search_opts(&o, so));
   if (so.ngram == 0 && so.temp == 1.f && !row_scores)
     return ss_op_beam_topk(stream, logits, R, V, k, t_step, min_len, max_len, npre, done, cum, pad, unk, eos, unk_pen, cand_s, cand_t);
-  if (R <= 0 || k < 1 || k > kMaxBeam || R % k != 0 || t_step < 0) return SS_ERR_ARG;
-  if (V < 2 * k + 1 || (size_t)V * sizeof(float) > 65536) return SS_ERR_ARG;
+  RET(op_topk_limits(R, V, k));
+  if (t_step < 0) return SS_ERR_ARG;
   if (so.ngram >= 2 && (!tok || !anc || c0 < 0 || c0 + t_step >= Lc)) return SS_ERR_ARG;
   if (topk_lds_bytes(V, so.ngram, Lc) > 65536) return SS_ERR_ARG;
   TopkOpts to;
@@ -896,12 +891,8 @@ extern "C" int ss_op_beam_merge_opts(void* stream, const ss_op_beam_state* x, in
                                      int normalize, float len_penalty) {
   if (!std::isfinite(len_penalty)) return SS_ERR_ARG;
   if (len_penalty == 1.f || !normalize) return ss_op_beam_merge(stream, x, B, k, Lc, V, t_step, c0, eos, normalize);
-  if (!x || B <= 0 || k < 1 || k > kMaxBeam || t_step < 0 || c0 < 0 || c0 + t_step + 2 > Lc) return SS_ERR_ARG;
   BeamState st;
-  st.tok = x->tok; st.cum = x->cum; st.anc = x->anc; st.cand_s = x->cand_s; st.cand_t = x->cand_t; st.ignore = x->ignore;
-  st.done = x->done; st.max_len = x->max_len; st.npre = x->npre;
-  st.fin_cnt = x->fin_cnt; st.fin_score = x->fin_score; st.fin_len = x->fin_len; st.fin_tok = x->fin_tok; st.fin_pos = x->fin_pos;
-  st.fin_anc = x->fin_anc;
+  RET(op_beam_state(x, B, k, Lc, t_step, c0, st));
   hipLaunchKernelGGL(beam_merge_lenpen_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, st, k, B * k, Lc, V, t_step, c0, eos, 1,
                      len_penalty);
   SS_LAUNCH_CHECK();

@@ -569,16 +569,21 @@ extern "C" int ss_ctc_greedy_scored(ss_model* m, void* stream, int head, const f
   return launch_ctc_collapse_spans(d_raw, d_lprob, Tp, 0, c.pad, d_tokens, d_index, d_last, d_tok_lprob, d_count, s);
 }
 
+int mt_cross_kv(ss_model* m, hipStream_t s, const float* d_enc_out, int n_rows) {
+  const ss_config& c = m->cfg;
+  const int D = c.dec_dim;
+  for (int l = 0; l < c.mt_layers; ++l)
+    RET(linear(s, d_enc_out, c.enc_dim, n_rows, m->mt[l].cross_kv, 2 * D, c.enc_dim,
+               m->sc->mt_cross.f() + (size_t)l * n_rows * 2 * D, 2 * D));
+  return SS_OK;
+}
+
 extern "C" int ss_mt_begin(ss_model* m, void* stream, const float* d_enc_out, int Tp) {
   if (!m || Tp <= 0) return SS_ERR_ARG;
   SkScope sk_scope(m->sc->skws);
-  hipStream_t s = (hipStream_t)stream;
   const ss_config& c = m->cfg;
-  const int D = c.dec_dim;
-  RET(m->sc->mt_cross.ensure((size_t)c.mt_layers * Tp * 2 * D * sizeof(float)));
-  for (int l = 0; l < c.mt_layers; ++l)
-    RET(linear(s, d_enc_out, c.enc_dim, Tp, m->mt[l].cross_kv, 2 * D, c.enc_dim,
-               m->sc->mt_cross.f() + (size_t)l * Tp * 2 * D, 2 * D));
+  RET(m->sc->mt_cross.ensure((size_t)c.mt_layers * Tp * 2 * c.dec_dim * sizeof(float)));
+  RET(mt_cross_kv(m, (hipStream_t)stream, d_enc_out, Tp));
   m->sc->mt_Tp = Tp;
   m->sc->mt_len = 0;
   m->sc->mt_enc = d_enc_out;
@@ -735,6 +740,16 @@ extern "C" int ss_mt_append(ss_model* m, void* stream, const int32_t* d_tokens, 
   return SS_OK;
 }
 
+// A negative token in the chain: a bounded wait of the persistent decode kernel (mt_step.hip) timed out.  This context falls back to
+// one launch per op for good, and the search runs again from the start.
+static int mt_greedy_after_timeout(ss_model* m, void* stream, const float* d_enc_out, int Tp, const int32_t* h_prefix, int n_prefix,
+                                   int max_len, int min_len, int32_t* h_out_tokens, int* h_n_out, float* d_feats, int* h_n_feats) {
+  fprintf(stderr, "streamspeech_hip: persistent MT decode step timed out (its %d workgroups were not all resident); "
+                  "this context falls back to one launch per op\n", m->sc->mt_persistent);
+  RET(mt_collect_errors(m));
+  m->sc->mt_persistent = 0;
+  return ss_mt_greedy(m, stream, d_enc_out, Tp, h_prefix, n_prefix, max_len, min_len, h_out_tokens, h_n_out, d_feats, h_n_feats);
+}
 
 // Whole beam-1 search in one call: the token chain lives on the device (each step's argmax writes
 // the next step's input), the host only peeks at it every kCheck steps to notice </s>.
@@ -783,12 +798,9 @@ extern "C" int ss_mt_greedy(ss_model* m, void* stream, const float* d_enc_out, i
     SS_HIP_CHECK(hipStreamSynchronize(s));
     int eos_at = -1;
     for (int i = lo; i <= hi && eos_at < 0; ++i) {
-      if (host[i] < 0) {                                    // a bounded wait of the persistent kernel timed out
-        fprintf(stderr, "streamspeech_hip: persistent MT decode step timed out (its %d workgroups were not all resident); "
-                        "this context falls back to one launch per op\n", m->sc->mt_persistent);
-        RET(mt_collect_errors(m));
-        m->sc->mt_persistent = 0;
-        return ss_mt_greedy(m, stream, d_enc_out, Tp, h_prefix, n_prefix, max_len, min_len, h_out_tokens, h_n_out, d_feats, h_n_feats);
+      if (host[i] < 0) {
+        return mt_greedy_after_timeout(m, stream, d_enc_out, Tp, h_prefix, n_prefix, max_len, min_len, h_out_tokens, h_n_out, d_feats,
+                                         h_n_feats);
       }
       if (host[i] == c.eos) eos_at = i;
     }
@@ -811,13 +823,9 @@ extern "C" int ss_mt_greedy(ss_model* m, void* stream, const float* d_enc_out, i
                                   hipMemcpyDeviceToHost, s));
       SS_HIP_CHECK(hipStreamSynchronize(s));
       for (int i = checked; i <= step && eos_at < 0; ++i) {
-        if (host[i] < 0 && m->sc->mt_persistent > 0) {          // mt_step.hip: a bounded wait of the persistent step timed out
-          fprintf(stderr, "streamspeech_hip: persistent MT decode step timed out (its %d workgroups were not all resident); "
-                          "this context falls back to one launch per op\n", m->sc->mt_persistent);
-          RET(mt_collect_errors(m));
-          m->sc->mt_persistent = 0;
-          return ss_mt_greedy(m, stream, d_enc_out, Tp, h_prefix, n_prefix, max_len, min_len, h_out_tokens, h_n_out, d_feats,
-                              h_n_feats);
+        if (host[i] < 0 && m->sc->mt_persistent > 0) {          // (the prefix pass' ss_mt_append may have taken the persistent step)
+          return mt_greedy_after_timeout(m, stream, d_enc_out, Tp, h_prefix, n_prefix, max_len, min_len, h_out_tokens, h_n_out, d_feats,
+                                           h_n_feats);
         }
         if (host[i] == c.eos) eos_at = i;
       }

@@ -447,6 +447,36 @@ static int enc_layer_ex(hipStream_t s, const ss_config& c, const EncLayer& e, fl
 int mt_prefix_pass(ss_model* m, hipStream_t s, int B, int Np, int np_max, int n_enc, const int* d_ptok, const int* d_ppos,
                    const int* d_pself, const int* d_pcross, const int* d_ptail, const int* d_pcache, int cache_rows, const float** out);
 
+// Cross-attention K/V of every MT layer over n_rows (packed) encoder rows into mt_cross, layer l at + l * n_rows * 2D (model.hip).  The
+// caller has booked mt_cross: (mt_layers * n_rows * 2D) floats.
+int mt_cross_kv(ss_model* m, hipStream_t s, const float* d_enc_out, int n_rows);
+
+// The decode rows' workspace of the lock-step text searches, carved from mt_ws: x | h | q2 | ffn | (gap floats) | logits, one row per
+// search row.  floats() is what the five parts take; a search with rows behind the logits books them on top.
+struct MtRowsWs {
+  float *x, *h, *q2, *ff, *logits;
+  static size_t floats(int rows, int D, int F, int V, size_t gap = 0) { return (size_t)rows * (3 * D + F + V) + gap; }
+  MtRowsWs(float* base, int rows, int D, int F, size_t gap = 0)
+      : x(base), h(x + (size_t)rows * D), q2(h + (size_t)rows * D), ff(q2 + (size_t)rows * D), logits(ff + (size_t)rows * F + gap) {}
+};
+
+// One lock-step decode step of a text search (batch.hip): every row feeds one token at cache index `ci`.
+struct MtRowsStep {
+  int rows = 0;                      // search rows (utterances, or utterances x beam)
+  int cache_ld = 0, ci = 0;          // rows of one search row's self-attention cache (bmt_self: [layer][rows][cache_ld][3D]); index fed
+  const int* tok = nullptr;          // [rows] the tokens fed
+  const int* row_pos = nullptr;      // null: every row at position ci (launch_embed_tokens); else row r at ci + row_pos[r], and
+  int row_pad = -1;                  // the pad argument of launch_embed_tokens_rows
+  const int* self_segs = nullptr;    // this step's self-attention segments [rows][4]
+  const int* cross_segs = nullptr;   // cross-attention segments [rows][4] over the n_enc packed encoder rows of mt_cross
+  int n_enc = 0;
+  const int* anc = nullptr; int anc_ld = 0, anc_slots = 0;   // the beam's ancestor table (AttnArgs), or none
+  float* states = nullptr; int states_ld = 0;                // post-LN states out: row r at + r * states_ld
+};
+// Embedding -> every MT layer (QKV rows straight into the cache) -> final LayerNorm -> tied vocabulary projection into w.logits.  The
+// CanonScope of the decode rows is the caller's.
+int mt_decode_rows(ss_model* m, hipStream_t s, const MtRowsWs& w, const MtRowsStep& a);
+
 extern std::atomic<int> g_mt_timeouts;      // bounded-wait time-outs of persistent MT decode steps, process-wide (model.hip)
 
 struct ConvW { const float* w = nullptr; const float* b = nullptr; const float* ww = nullptr;   // ww: Winograd form (64-channel stage ResBlock convs)

@@ -331,6 +331,46 @@ class BatchMixin:
         """(fbank rows, final fbank rows) of n_in samples at sr_in Hz (fbank_sr_rows); None for a rate batch_fbank_frames_sr refuses."""
         return fbank_sr_rows(n_in, *resample_ratio(sr_in), lib=self.lib)
 
+    def _mt_beam(self, entry: str, enc_packed: torch.Tensor, Tp: List[int], prefixes: Optional[List[List[int]]], max_len: List[int],
+                 beam: int, spare_rows: int, min_len: int, unk_penalty: float, normalize: bool, search: tuple):
+        """The calls behind batch_mt_beam (prefixes None: `entry` takes none) and batch_mt_beam_continue -> (nbest, feats [B, rows, D]),
+        rows = the longest max_len + 1 + spare_rows.  A pack with B * beam > 256 rows runs as consecutive sub-calls (plan_beam_groups).
+        search = (len_penalty, temperature, no_repeat_ngram_size): at the defaults the call is `entry` itself, otherwise `entry`_opts.
+        A hypothesis is its row's prefix + the generated tokens, and its positional scores cover both."""
+        B = len(Tp)
+        if not 1 <= beam <= MT_BEAM_MAX:
+            raise ValueError(f"beam {beam} outside [1, {MT_BEAM_MAX}]")
+        opts = check_search_options(*search)
+        name, tail = (entry, ()) if opts is None else (entry + "_opts", (C.byref(opts),))
+        stride = max(max_len) + 1
+        rows = stride + spare_rows
+        feats = torch.empty((B, rows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
+        nbest: List[List[dict]] = []
+        off = np.concatenate([[0], np.cumsum(Tp)]).astype(np.int64)
+        for b0, b1 in plan_beam_groups(B, beam):
+            n = b1 - b0
+            enc = enc_packed[int(off[b0]):int(off[b1])]
+            pre = [[int(t) for t in p] for p in prefixes[b0:b1]] if prefixes is not None else [[]] * n
+            forced = () if prefixes is None else (_i32([t for p in pre for t in p] or [0]), _i32([len(p) for p in pre]))
+            out = (C.c_int32 * (n * beam * stride))()
+            n_out = (C.c_int32 * (n * beam))()
+            sc = (C.c_float * (n * beam))()
+            pos = (C.c_float * (n * beam * stride))()
+            L.check(getattr(self.lib, name)(self.h, _stream(), n, beam, _ptr(enc), _i32(Tp[b0:b1]), *forced, _i32(max_len[b0:b1]),
+                                            int(min_len), float(unk_penalty), 1 if normalize else 0, out, stride, n_out, sc, pos,
+                                            _ptr(feats[b0:b1]), rows, *tail), name)
+            for b in range(n):
+                hyps = []
+                for i in range(beam):
+                    o = b * beam + i
+                    k = n_out[o]
+                    if k <= 0:
+                        continue
+                    hyps.append({"tokens": pre[b] + list(out[o * stride: o * stride + k]), "score": float(sc[o]),
+                                 "positional_scores": list(pos[o * stride: o * stride + len(pre[b]) + k])})
+                nbest.append(hyps)
+        return nbest, feats
+
     def batch_mt_beam(self, enc_packed: torch.Tensor, Tp: List[int], max_len: List[int], beam: int, min_len: int = 1,
                       unk_penalty: float = 0.0, normalize: bool = True, len_penalty: float = 1.0, temperature: float = 1.0,
                       no_repeat_ngram_size: int = 0):
@@ -340,40 +380,9 @@ class BatchMixin:
         runs as consecutive sub-calls (plan_beam_groups); pack-invariant arithmetic makes the split invisible.  len_penalty,
         temperature and no_repeat_ngram_size are the reference's --lenpen, --temperature and --no-repeat-ngram-size
         (ss_mt_search_opts); at their defaults the call is ss_batch_mt_beam itself."""
-        B = len(Tp)
-        if not 1 <= beam <= MT_BEAM_MAX:
-            raise ValueError(f"beam {beam} outside [1, {MT_BEAM_MAX}]")
-        opts = check_search_options(len_penalty, temperature, no_repeat_ngram_size)
-        Lmax = max(max_len)
-        rows, stride = Lmax + 2, Lmax + 1
-        feats = torch.empty((B, rows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
-        nbest: List[List[dict]] = []
-        off = np.concatenate([[0], np.cumsum(Tp)]).astype(np.int64)
-        for b0, b1 in plan_beam_groups(B, beam):
-            n = b1 - b0
-            enc = enc_packed[int(off[b0]):int(off[b1])]
-            out = (C.c_int32 * (n * beam * stride))()
-            n_out = (C.c_int32 * (n * beam))()
-            sc = (C.c_float * (n * beam))()
-            pos = (C.c_float * (n * beam * stride))()
-            args = (self.h, _stream(), n, beam, _ptr(enc), _i32(Tp[b0:b1]), _i32(max_len[b0:b1]), min_len, float(unk_penalty),
-                    1 if normalize else 0, out, stride, n_out, sc, pos, _ptr(feats[b0:b1]), rows)
-            if opts is None:
-                L.check(self.lib.ss_batch_mt_beam(*args), "ss_batch_mt_beam")
-            else:
-                L.check(self.lib.ss_batch_mt_beam_opts(*args, C.byref(opts)), "ss_batch_mt_beam_opts")
-            for b in range(n):
-                hyps = []
-                for i in range(beam):
-                    o = b * beam + i
-                    k = n_out[o]
-                    if k <= 0:
-                        continue
-                    hyps.append({"tokens": list(out[o * stride: o * stride + k]), "score": float(sc[o]),
-                                 "positional_scores": list(pos[o * stride: o * stride + k])})
-                nbest.append(hyps)
-        n_feats = [len(h[0]["tokens"]) if h else 0 for h in nbest]
-        return nbest, feats, n_feats
+        nbest, feats = self._mt_beam("ss_batch_mt_beam", enc_packed, Tp, None, max_len, beam, 1, min_len, unk_penalty, normalize,
+                                     (len_penalty, temperature, no_repeat_ngram_size))
+        return nbest, feats, [len(h[0]["tokens"]) if h else 0 for h in nbest]
 
     def batch_mt_beam_continue(self, enc_packed: torch.Tensor, Tp: List[int], prefixes: List[List[int]], max_len: List[int], beam: int,
                                min_len: int = 1, unk_penalty: float = 0.0, normalize: bool = True, len_penalty: float = 1.0,
@@ -384,44 +393,11 @@ class BatchMixin:
         of hypothesis 0's fed positions, as batch_mt_continue returns them.  A pack with B * beam > 256 rows runs as consecutive
         sub-calls (plan_beam_groups); pack-invariant arithmetic makes the split invisible.  len_penalty, temperature and
         no_repeat_ngram_size as in batch_mt_beam (ss_batch_mt_beam_continue_opts); a prefix that itself repeats an n-gram is refused."""
-        B = len(Tp)
-        if not (len(prefixes) == len(max_len) == B):
+        if not (len(prefixes) == len(max_len) == len(Tp)):
             raise ValueError("one prefix and one max_len per row")
-        if not 1 <= beam <= MT_BEAM_MAX:
-            raise ValueError(f"beam {beam} outside [1, {MT_BEAM_MAX}]")
-        opts = check_search_options(len_penalty, temperature, no_repeat_ngram_size)
-        rows = stride = max(max_len) + 1
-        feats = torch.empty((B, rows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
-        nbest: List[List[dict]] = []
-        off = np.concatenate([[0], np.cumsum(Tp)]).astype(np.int64)
-        for b0, b1 in plan_beam_groups(B, beam):
-            n = b1 - b0
-            enc = enc_packed[int(off[b0]):int(off[b1])]
-            flat = [int(t) for p in prefixes[b0:b1] for t in p]
-            out = (C.c_int32 * (n * beam * stride))()
-            n_out = (C.c_int32 * (n * beam))()
-            sc = (C.c_float * (n * beam))()
-            pos = (C.c_float * (n * beam * stride))()
-            args = (self.h, _stream(), n, beam, _ptr(enc), _i32(Tp[b0:b1]), _i32(flat or [0]), _i32([len(p) for p in prefixes[b0:b1]]),
-                    _i32(max_len[b0:b1]), int(min_len), float(unk_penalty), 1 if normalize else 0, out, stride, n_out, sc, pos,
-                    _ptr(feats[b0:b1]), rows)
-            if opts is None:
-                L.check(self.lib.ss_batch_mt_beam_continue(*args), "ss_batch_mt_beam_continue")
-            else:
-                L.check(self.lib.ss_batch_mt_beam_continue_opts(*args, C.byref(opts)), "ss_batch_mt_beam_continue_opts")
-            for b in range(n):
-                pre = [int(t) for t in prefixes[b0 + b]]
-                hyps = []
-                for i in range(beam):
-                    o = b * beam + i
-                    k = n_out[o]
-                    if k <= 0:
-                        continue
-                    hyps.append({"tokens": pre + list(out[o * stride: o * stride + k]), "score": float(sc[o]),
-                                 "positional_scores": list(pos[o * stride: o * stride + len(pre) + k])})
-                nbest.append(hyps)
-        n_feats = [len(h[0]["tokens"]) if h else 0 for h in nbest]
-        return nbest, [feats[b, :n_feats[b]] for b in range(B)]
+        nbest, feats = self._mt_beam("ss_batch_mt_beam_continue", enc_packed, Tp, prefixes, max_len, beam, 0, min_len, unk_penalty,
+                                     normalize, (len_penalty, temperature, no_repeat_ngram_size))
+        return nbest, [feats[b, :len(h[0]["tokens"]) if h else 0] for b, h in enumerate(nbest)]
 
     def last_logits(self) -> torch.Tensor:
         """Dense logits [rows, cols] of this context's last batch_ctc_greedy / batch_t2u_units call (test hook: arg-max margins)."""
@@ -915,6 +891,52 @@ class ContinueRefused(ValueError):
         self.code = code
 
 
+class _PlanTables:
+    """The int tables a planner returns, read front to back."""
+
+    def __init__(self, words):
+        self.t, self.o = list(words), 0
+
+    def take(self, n):
+        self.o += n
+        return self.t[self.o - n:self.o]
+
+    def quads(self, n):
+        v = self.take(4 * n)
+        return [tuple(v[4 * i:4 * i + 4]) for i in range(n)]
+
+    def steps(self, n_steps, rows):
+        v = self.quads(n_steps * rows)
+        return [v[k * rows:(k + 1) * rows] for k in range(n_steps)]
+
+
+def _run_planner(plan_fn, call: str, args: tuple, n_dims: int):
+    """The two-call protocol of the host-only planners: once for the size of the tables -- a refusal raises ContinueRefused with the
+    code `call` would return -- then again for the tables -> (dims, _PlanTables)."""
+    lib = L.load()
+    dims, n_tab = (C.c_int32 * n_dims)(), C.c_int64(0)
+    rc = plan_fn(*args, dims, None, 0, C.byref(n_tab))
+    if rc != 0:
+        raise ContinueRefused(f"{call} refuses the call: {lib.ss_error_string(rc).decode()}", rc)
+    tab = (C.c_int32 * n_tab.value)()
+    L.check(plan_fn(*args, dims, tab, n_tab.value, C.byref(n_tab)), call + "_plan")
+    return list(dims), _PlanTables(tab)
+
+
+def _plan_args(Tp, n_prefix, max_len, feat_rows, out_stride, prefix_ids, least_stride):
+    """What both planners do to their arguments: one length per row, feat_rows / out_stride at the least the call needs (the least
+    out_stride of row (max_len, n_prefix) is the planner's own), placeholder ids for the prefixes."""
+    B = len(Tp)
+    if len(n_prefix) != B or len(max_len) != B:
+        raise ContinueRefused("one prefix length and max_len per row", L.SS_ERR_ARG)
+    if B and feat_rows is None:
+        feat_rows = max(m + 1 for m in max_len)
+    if B and out_stride is None:
+        out_stride = max(least_stride(m, n) for m, n in zip(max_len, n_prefix))
+    ids = list(prefix_ids) if prefix_ids is not None else [4] * sum(max(int(n), 0) for n in n_prefix)
+    return B, feat_rows, out_stride, ids
+
+
 def plan_mt_continue(Tp: List[int], n_prefix: List[int], max_len: List[int], min_len: int = 1, feat_rows: Optional[int] = None,
                      out_stride: Optional[int] = None, max_tgt_pos: int = 1026, prefix_ids: Optional[List[int]] = None,
                      vocab: int = 6000, eos: int = 2) -> dict:
@@ -923,41 +945,19 @@ def plan_mt_continue(Tp: List[int], n_prefix: List[int], max_len: List[int], min
     row (row b shifted by shift[b] = S - n_prefix[b], so every row's first generated position sits at cache index S + 1), and the
     tables the call uploads.  feat_rows / out_stride default to the least the call needs.  Raises ContinueRefused with the code the
     call returns."""
-    B = len(Tp)
-    if len(n_prefix) != B or len(max_len) != B:
-        raise ContinueRefused("one prefix length and max_len per row", L.SS_ERR_ARG)
-    if B and feat_rows is None:
-        feat_rows = max(m + 1 for m in max_len)
-    if B and out_stride is None:
-        out_stride = max(m - n + 1 for m, n in zip(max_len, n_prefix))
-    ids = list(prefix_ids) if prefix_ids is not None else [4] * sum(max(int(n), 0) for n in n_prefix)
-    lib = L.load()
-    dims, n_tab = (C.c_int32 * 4)(), C.c_int64(0)
+    B, feat_rows, out_stride, ids = _plan_args(Tp, n_prefix, max_len, feat_rows, out_stride, prefix_ids, lambda m, n: m - n + 1)
     args = (B, _i32(Tp or [0]), _i32(ids or [0]), _i32(n_prefix or [0]), _i32(max_len or [0]), int(min_len), int(out_stride or 0),
             int(feat_rows or 0), int(max_tgt_pos), int(vocab), int(eos))
-    rc = lib.ss_batch_mt_continue_plan(*args, dims, None, 0, C.byref(n_tab))
-    if rc != 0:
-        raise ContinueRefused(f"ss_batch_mt_continue refuses the call: {lib.ss_error_string(rc).decode()}", rc)
-    tab = (C.c_int32 * n_tab.value)()
-    L.check(lib.ss_batch_mt_continue_plan(*args, dims, tab, n_tab.value, C.byref(n_tab)), "ss_batch_mt_continue_plan")
-    S, Tn, Lcap, Np = list(dims)
-    t, Tr, o = list(tab), max(Tn, 1), 0
-
-    def take(n):
-        nonlocal o
-        o += n
-        return t[o - n:o]
-    quads = lambda v: [tuple(v[4 * i:4 * i + 4]) for i in range(len(v) // 4)]    # noqa: E731
+    (S, Tn, Lcap, Np), t = _run_planner(L.load().ss_batch_mt_continue_plan, "ss_batch_mt_continue", args, 4)
     p = {"S": S, "Tn": Tn, "Lcap": Lcap, "Np": Np, "feat_rows": feat_rows, "out_stride": out_stride}
-    p["max_len_at"], p["min_len_at"] = take(B), take(B)
-    p["shift"] = [-x for x in take(B)]
-    p["step_cross"], p["prefix_self"], p["prefix_cross"] = quads(take(4 * B)), quads(take(4 * B)), quads(take(4 * B))
-    steps = quads(take(4 * B * Tr))
-    p["step_self"] = [steps[k * B:(k + 1) * B] for k in range(Tr)]
-    p["prefix_tokens"], p["prefix_pos"], p["cache_row"], p["feat_row"] = take(Np), take(Np), take(Np), take(Np)
-    p["last_row"] = take(B)
+    p["max_len_at"], p["min_len_at"] = t.take(B), t.take(B)
+    p["shift"] = [-x for x in t.take(B)]
+    p["step_cross"], p["prefix_self"], p["prefix_cross"] = t.quads(B), t.quads(B), t.quads(B)
+    p["step_self"] = t.steps(max(Tn, 1), B)
+    p["prefix_tokens"], p["prefix_pos"], p["cache_row"], p["feat_row"] = t.take(Np), t.take(Np), t.take(Np), t.take(Np)
+    p["last_row"] = t.take(B)
     p["r0"] = [seg[0] for seg in p["prefix_self"]]
-    assert o == len(t)
+    assert t.o == len(t.t)
     return p
 
 
@@ -971,49 +971,26 @@ def plan_mt_beam_continue(Tp: List[int], n_prefix: List[int], max_len: List[int]
     ContinueRefused with the code the call returns.  With one of the three search controls off its default the planner is
     ss_batch_mt_beam_continue_plan_opts: the option refusals first (they reach the library as they are, so their code and their place
     in the order are the library's), the repeated-n-gram check of the prefixes last."""
-    B = len(Tp)
-    if len(n_prefix) != B or len(max_len) != B:
-        raise ContinueRefused("one prefix length and max_len per row", L.SS_ERR_ARG)
-    opts = None
+    B, feat_rows, out_stride, ids = _plan_args(Tp, n_prefix, max_len, feat_rows, out_stride, prefix_ids, lambda m, n: m + 1)
+    lib = L.load()
+    plan_fn = lib.ss_batch_mt_beam_continue_plan
     if not (len_penalty == 1.0 and temperature == 1.0 and no_repeat_ngram_size == 0):
         opts = L.SSMtSearchOpts(C.sizeof(L.SSMtSearchOpts), int(no_repeat_ngram_size), float(len_penalty), float(temperature))
-    if B and feat_rows is None:
-        feat_rows = max(m + 1 for m in max_len)
-    if B and out_stride is None:
-        out_stride = max(m + 1 for m in max_len)
-    ids = list(prefix_ids) if prefix_ids is not None else [4] * sum(max(int(n), 0) for n in n_prefix)
-    lib = L.load()
-    dims, n_tab = (C.c_int32 * 8)(), C.c_int64(0)
+        plan_fn = lambda *a: lib.ss_batch_mt_beam_continue_plan_opts(*a, C.byref(opts))    # noqa: E731
     args = (B, int(beam), _i32(Tp or [0]), _i32(ids or [0]), _i32(n_prefix or [0]), _i32(max_len or [0]), int(min_len),
             int(out_stride or 0), int(feat_rows or 0), int(max_tgt_pos), int(vocab), int(eos), int(pad))
-    if opts is None:
-        plan_fn = lib.ss_batch_mt_beam_continue_plan
-    else:
-        plan_fn = lambda *a: lib.ss_batch_mt_beam_continue_plan_opts(*a, C.byref(opts))    # noqa: E731
-    rc = plan_fn(*args, dims, None, 0, C.byref(n_tab))
-    if rc != 0:
-        raise ContinueRefused(f"ss_batch_mt_beam_continue refuses the call: {lib.ss_error_string(rc).decode()}", rc)
-    tab = (C.c_int32 * n_tab.value)()
-    L.check(plan_fn(*args, dims, tab, n_tab.value, C.byref(n_tab)), "ss_batch_mt_beam_continue_plan")
-    S, Tn, Lc, Np, R, c0, nseg, pm = list(dims)
-    t, o = list(tab), 0
-
-    def take(n):
-        nonlocal o
-        o += n
-        return t[o - n:o]
-    quads = lambda v: [tuple(v[4 * i:4 * i + 4]) for i in range(len(v) // 4)]    # noqa: E731
+    (S, Tn, Lc, Np, R, c0, nseg, pm), t = _run_planner(plan_fn, "ss_batch_mt_beam_continue", args, 8)
     p = {"S": S, "Tn": Tn, "Lc": Lc, "Np": Np, "R": R, "c0": c0, "prefix_segments": nseg, "last_forced_in_prefix_pass": bool(pm),
          "feat_rows": feat_rows, "out_stride": out_stride}
-    p["step_cross"] = quads(take(4 * R))
-    steps = quads(take(4 * R * (Tn + 1)))
-    p["step_self"] = [steps[k * R:(k + 1) * R] for k in range(Tn + 1)]
-    p["shift"] = [-x for x in take(R)]
-    p["r0"] = take(B)
-    p["prefix_self"], p["prefix_cross"] = quads(take(4 * nseg)), quads(take(4 * nseg))
-    p["prefix_tokens"], p["prefix_pos"], p["cache_row"], p["feat_row"], p["forced"] = take(Np), take(Np), take(Np), take(Np), take(Np)
-    p["last_row"] = take(B)
-    assert o == len(t)
+    p["step_cross"] = t.quads(R)
+    p["step_self"] = t.steps(Tn + 1, R)
+    p["shift"] = [-x for x in t.take(R)]
+    p["r0"] = t.take(B)
+    p["prefix_self"], p["prefix_cross"] = t.quads(nseg), t.quads(nseg)
+    p["prefix_tokens"], p["prefix_pos"], p["cache_row"], p["feat_row"], p["forced"] = (t.take(Np), t.take(Np), t.take(Np), t.take(Np),
+                                                                                       t.take(Np))
+    p["last_row"] = t.take(B)
+    assert t.o == len(t.t)
     return p
 
 

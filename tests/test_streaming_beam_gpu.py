@@ -152,6 +152,32 @@ def test_beam1_is_the_greedy_continuation(hip_model):
             assert feats[b].shape == ref[b][1].shape and torch.equal(feats[b], ref[b][1]), f"row {b}: decoder states"
 
 
+def test_ragged_continuations_share_one_decode_step(hip_model):
+    """A pack of three rows behind prefixes of 0, 3 and 7 tokens, the last with max_len == n_prefix (it takes no lock-step step): at
+    beam 1 the forced beam search is batch_mt_continue bit for bit, tokens and decoder states, and every row of batch_mt_continue
+    generates what mt_greedy generates behind the same prefix."""
+    enc, Tp = _offline_utterances(hip_model)
+    Tp = [int(t) for t in Tp[:3]]
+    enc = enc[:sum(Tp)]
+    free, _, _ = hip_model.batch_mt_greedy(enc, Tp, [12] * 3)
+    prefixes = []
+    for b, n in enumerate((0, 3, 7)):
+        body = [t for t in free[b] if t != hip_model.cfg.eos]
+        prefixes.append((body * n)[:n])                   # a short search: repeat its tokens
+    assert [len(p) for p in prefixes] == [0, 3, 7]
+    mx = [10, 10, 7]
+    ref = hip_model.batch_mt_continue(enc, Tp, prefixes, mx)
+    nbest, feats = hip_model.batch_mt_beam_continue(enc, Tp, prefixes, mx, 1)
+    assert ref[2][0] == [hip_model.cfg.eos], "the full-length prefix is followed by the forced </s> alone"
+    off = np.concatenate([[0], np.cumsum(Tp)])
+    for b in range(3):
+        assert len(nbest[b]) == 1
+        assert nbest[b][0]["tokens"] == prefixes[b] + ref[b][0], f"row {b} (prefix {len(prefixes[b])})"
+        assert feats[b].shape == ref[b][1].shape and torch.equal(feats[b], ref[b][1]), f"row {b}: decoder states"
+        alone, _ = hip_model.mt_greedy(enc[int(off[b]):int(off[b + 1])], prefixes[b], mx[b])
+        assert alone == ref[b][0], f"row {b}: batch_mt_continue against mt_greedy"
+
+
 def test_no_prefix_is_the_offline_beam(hip_model):
     enc, Tp = _offline_utterances(hip_model)
     mx = [12 + (b % 3) for b in range(len(Tp))]
