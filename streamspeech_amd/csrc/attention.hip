@@ -1,13 +1,18 @@
-// Attention, wavefront-softmax form (see attention.hpp).
-//
-// Workgroup = 4 wave64 = 16 query rows of one head; wave w owns rows 4w..4w+3.  Keys are walked
-// in tiles of 64 (lane = key).  K / V (and, for the rel-pos form, the 79 positional rows the
-// 16x64 (query,key) pairs of the tile can touch) are staged in LDS; the query rows live in
-// registers (lane d holds q[.,d]) and are broadcast with v_readlane, as are the probabilities
-// for P.V (lane = output dim).  Softmax is the online (running max / running sum) form with
-// wave-wide shuffles, so the [T,T] and [T,2T-1] score matrices the reference materialises
-// (espnet_multihead_attention.py:186-196) never exist.
-#include "attention.hpp"
+// Attention kernels (see attention.hpp for the arguments and launch_attention below for who takes a call).  All use the online
+// (running max / running sum) softmax over 64-key tiles, so the [T,T] and [T,2T-1] score matrices the reference materialises
+// (espnet_multihead_attention.py:186-196) never exist.  The seven kernels and the pieces of attn_tile.hpp each is built from:
+//   attention_kernel<RELPOS>            VALU, 16 queries per workgroup, plain and rel-pos       seg_rebase
+//   attention_decode_kernel<ANC>        <= 8 queries, one wave per key tile, no LDS tiles       (own prologue: the ancestry branch)
+//   attention_mfma_kernel               plain, 64 queries x 64-key tiles in LDS                 seg_rebase, stage_kv_tile, softmax_tile,
+//                                                                                               pv_tile, store_rows
+//   attention_relpos_mfma_kernel<SPLIT> rel-pos, the same tiles + table window and skew patch   the five above + load_qu_qv, bd_skew,
+//                                                                                               chunk_bound; SPLIT: split_arrive / _reset
+//   attention_relpos_q16_kernel         rel-pos, <= 48 queries, one workgroup per key tile      load_qu_qv, chunk_bound, q16_tile,
+//                                                                                               split_arrive / _reset
+//   attention_pool_kernel               the same tile for many sessions, key tiles in a loop    load_qu_qv, chunk_bound, q16_tile
+// What the paired kernels do NOT share stays in them: the park / merge layouts of the two key splits and the merge orders (the last
+// arrival's two passes against the pool's running merge).
+#include "attn_tile.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -18,26 +23,23 @@ void attention_debug_no_mfma(int v) { dispatch_edit([v](Dispatch& d) { d.attn_no
 void attention_debug_q16(int v) { dispatch_edit([v](Dispatch& d) { d.attn_q16 = v; }); }          // test hook: 0 = the few-queries form off
 void attention_debug_split(int v) { dispatch_edit([v](Dispatch& d) { d.attn_split = v; }); }   // test hook; SS_ATTN_NO_SPLIT=1: never split
 
-constexpr int QB = 16;     // query rows per workgroup
-constexpr int KT = 64;     // keys per tile
-constexpr int DH = 64;     // head dim
+constexpr int QB = 16;     // query rows per workgroup of the VALU kernel
 constexpr int LDKS = DH + 1;
 
 __device__ __forceinline__ float rdlane(float v, int l) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
 
+// -------------------------------------------------------------------------------------------------
+// VALU form, wavefront softmax.  Workgroup = 4 wave64 = 16 query rows of one head; wave w owns rows 4w..4w+3.  Keys are walked
+// in tiles of 64 (lane = key).  K / V (and, for the rel-pos form, the 79 positional rows the
+// 16x64 (query,key) pairs of the tile can touch) are staged in LDS; the query rows live in
+// registers (lane d holds q[.,d]) and are broadcast with v_readlane, as are the probabilities
+// for P.V (lane = output dim); max and sum are wave-wide shuffles.
+// -------------------------------------------------------------------------------------------------
 template <bool RELPOS>
 __global__ __launch_bounds__(256) void attention_kernel(AttnArgs p) {
-  if (p.nseg > 0) {   // ragged batch: rebase this workgroup onto its utterance
-    const int* sg = p.segs + 4 * blockIdx.z;
-    p.Tq = sg[1]; p.Tk = sg[3];
-    if (p.seg_tail) p.k_mask_tail = p.seg_tail[blockIdx.z];
-    if ((int)blockIdx.x * QB >= p.Tq) return;
-    p.Q += (size_t)sg[0] * p.ldq; p.O += (size_t)sg[0] * p.ldo;
-    p.K += (size_t)sg[2] * p.ldk; p.V += (size_t)sg[2] * p.ldv;
-    if (RELPOS) p.P += (size_t)(p.p_tmax - p.Tk) * p.ldp;
-  }
+  if (p.nseg > 0 && !seg_rebase(p, QB, RELPOS)) return;
   __shared__ float Ks[KT * LDKS];
   __shared__ float Vs[KT * DH];
   __shared__ float Ps[RELPOS ? (KT + QB - 1) * LDKS : 1];
@@ -252,35 +254,14 @@ __global__ __launch_bounds__(256) void attention_decode_kernel(AttnArgs p) {
 // -------------------------------------------------------------------------------------------------
 // MFMA form (plain attention, Tq > 8): QK^T and PV on v_mfma_f32_16x16x4_f32, online softmax on the
 // accumulator fragments.  Workgroup = 64 queries x 1 head (4 waves x 16 queries), 64-key tiles of K
-// and V^T in LDS shared by the 4 waves.
-//
-// Fragment algebra (C/D layout: col = lane&15, row = 4*(lane>>4) + reg; lane = (r, g)):
-//   S^T = K . Q^T : A = K rows (lane (r,g) reads K[key r][16kk+4g .. +3] with one ds_read_b128 --
-//     MFMA e then contracts d = {16kk+4g'+e}, a permutation of d shared with the Q operand),
-//     B = Q rows held in registers.  The tile comes out as lane (r = query, g) holding the scores of
-//     keys 4g..4g+3: a query's row lives in the 4 lanes {r, r+16, r+32, r+48} -> row max / sum are
-//     2 shuffles, no LDS.
-//   O^T = V^T . P^T : B = P^T is EXACTLY what the lane already holds (MFMA e takes keys {4g'+e}),
-//     A = V^T[d = r][keys 4g..4g+3] is one ds_read_b128 from the transposed V tile.  The output
-//     comes out as lane (r = query, g) holding d = 16dt+4g..+3 -> float4 stores.
+// and V^T in LDS shared by the 4 waves; the fragment algebra is written down in attn_tile.hpp.
 // Same arithmetic as the reference fairseq MHA (ctc_unity/modules/multihead_attention.py:544-760):
 // fp32 scores, -inf masks (causal / key padding), softmax, PV; only the summation order differs.
 // -------------------------------------------------------------------------------------------------
-constexpr int MQ = 64;              // queries per workgroup
-constexpr int LDT = 68;             // padded LDS row (floats): 17 sixteen-byte slots -> conflict-free b128 fragments
-
 __global__ __launch_bounds__(256) void attention_mfma_kernel(AttnArgs p) {
-  if (p.nseg > 0) {
-    const int* sg = p.segs + 4 * blockIdx.z;
-    p.Tq = sg[1]; p.Tk = sg[3];
-    if (p.seg_tail) p.k_mask_tail = p.seg_tail[blockIdx.z];
-    if ((int)blockIdx.x * MQ >= p.Tq) return;
-    p.Q += (size_t)sg[0] * p.ldq; p.O += (size_t)sg[0] * p.ldo;
-    p.K += (size_t)sg[2] * p.ldk; p.V += (size_t)sg[2] * p.ldv;
-  }
+  if (p.nseg > 0 && !seg_rebase(p, MQ, false)) return;
   __shared__ __attribute__((aligned(16))) float Ks[KT * LDT];     // [key][d]
   __shared__ __attribute__((aligned(16))) float Vt[DH * LDT];     // [d][key]
-  using f32x4 = __attribute__((ext_vector_type(4))) float;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int r = lane & 15, g = lane >> 4;
   const int h = blockIdx.y, hoff = h * DH;
@@ -311,18 +292,7 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(AttnArgs p) {
 
   for (int j0 = 0; j0 < kmax; j0 += KT) {
     __syncthreads();                                  // previous tile fully consumed
-    for (int f = t; f < KT * (DH / 4); f += 256) {
-      const int row = f >> 4, c4 = (f & 15) * 4;      // 16 threads per key row (256 contiguous bytes)
-      const int j = j0 + row;
-      f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = kv;
-      if (j < p.Tk) {
-        kv = *reinterpret_cast<const f32x4*>(p.K + (size_t)j * p.ldk + hoff + c4);
-        vv = *reinterpret_cast<const f32x4*>(p.V + (size_t)j * p.ldv + hoff + c4);
-      }
-      *reinterpret_cast<f32x4*>(Ks + row * LDT + c4) = kv;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) Vt[(c4 + c) * LDT + row] = vv[c];
-    }
+    stage_kv_tile(Ks, Vt, p.K, p.V, p.ldk, p.ldv, p.Tk, j0, hoff, t);
     __syncthreads();
 
     // S^T tiles: s[kt][e] = score(query iq, key j0 + 16kt + 4g + e)
@@ -337,67 +307,10 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(AttnArgs p) {
         for (int e = 0; e < 4; ++e) s[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[e], qf[kk][e], s[kt], 0, 0, 0);
       }
     }
-    // mask, running max / sum over the query's 4 lanes
-    float mt = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int j = j0 + kt * 16 + 4 * g + e;
-        s[kt][e] = (j < lim) ? s[kt][e] * p.scale : -INFINITY;
-        mt = fmaxf(mt, s[kt][e]);
-      }
-    mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
-    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-    const float mn = fmaxf(m_run, mt);
-    float corr = 1.f, ls = 0.f;
-    if (mn > -INFINITY) {
-      corr = (m_run > -INFINITY) ? expf(m_run - mn) : 0.f;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float pe = (s[kt][e] > -INFINITY) ? expf(s[kt][e] - mn) : 0.f;
-          s[kt][e] = pe;
-          ls += pe;
-        }
-    } else {
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    ls += __shfl_xor(ls, 16, 64);
-    ls += __shfl_xor(ls, 32, 64);
-    l_run = l_run * corr + ls;
-    m_run = mn;
-    // O^T = O^T corr + V^T . P^T -- the tile's product in a FRESH accumulator (a 64-key chain), then one add into the running sum:
-    // accumulating straight into o made one chain over all Tk keys, whose rounding grew with the utterance length (round 6:
-    // unit logits of an 11-s utterance sat 1.6x farther from float64 than the oracle's, of a 1.5-s one 0.8x)
-    f32x4 ot[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) ot[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const f32x4 vf = *reinterpret_cast<const f32x4*>(Vt + (dt * 16 + r) * LDT + kt * 16 + 4 * g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ot[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[e], s[kt][e], ot[dt], 0, 0, 0);
-      }
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[dt][e] = o[dt][e] * corr + ot[dt][e];
+    const float corr = softmax_tile(s, j0, lim, p.scale, g, m_run, l_run);
+    pv_tile(o, s, Vt, r, g, corr);
   }
-  if (q_ok) {
-    const float inv = 1.0f / l_run;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      f32x4 v = o[dt];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] *= inv;
-      *reinterpret_cast<f32x4*>(p.O + (size_t)iq * p.ldo + hoff + 16 * dt + 4 * g) = v;
-    }
-  }
+  if (q_ok) store_rows(p.O, p.ldo, iq, hoff, g, o, l_run);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -411,7 +324,6 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(AttnArgs p) {
 // (64 query x 64 key) block can touch (127) are staged in LDS next to the K and V^T tiles.
 // -------------------------------------------------------------------------------------------------
 constexpr int PWIN = 2 * KT;          // staged table rows (127 used, last one zero)
-constexpr int LDG = 36;               // per-wave G patch row stride
 constexpr size_t kRelposLds = (size_t)(KT * LDT + DH * LDT + PWIN * LDT + 4 * 16 * LDG) * sizeof(float);
 
 //
@@ -423,19 +335,11 @@ constexpr size_t kRelposLds = (size_t)(KT * LDT + DH * LDT + PWIN * LDT + 4 * 16
 // atomic; sc1 loads on the other side (MI355X_MICROARCH.md: per-XCD L2s are not coherent).  Nobody waits for anybody.
 template <bool SPLIT>
 __global__ __launch_bounds__(256) void attention_relpos_mfma_kernel(AttnArgs p) {
-  if (!SPLIT && p.nseg > 0) {
-    const int* sg = p.segs + 4 * blockIdx.z;
-    p.Tq = sg[1]; p.Tk = sg[3];
-    if ((int)blockIdx.x * MQ >= p.Tq) return;
-    p.Q += (size_t)sg[0] * p.ldq; p.O += (size_t)sg[0] * p.ldo;
-    p.K += (size_t)sg[2] * p.ldk; p.V += (size_t)sg[2] * p.ldv;
-    p.P += (size_t)(p.p_tmax - p.Tk) * p.ldp;
-  }
+  if (!SPLIT && p.nseg > 0 && !seg_rebase(p, MQ, true)) return;
   extern __shared__ __attribute__((aligned(16))) float smem_rp[];
   float* Ks = smem_rp;                  // [key][d]
   float* Vt = Ks + KT * LDT;            // [d][key]
   float* Ps = Vt + DH * LDT;            // [table row][d]
-  using f32x4 = __attribute__((ext_vector_type(4))) float;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   float* Gs = Ps + PWIN * LDT + wave * 16 * LDG;
   const int r = lane & 15, g = lane >> 4;
@@ -448,26 +352,14 @@ __global__ __launch_bounds__(256) void attention_relpos_mfma_kernel(AttnArgs p) 
   const bool q_ok = iq < p.Tq;
 
   f32x4 quf[4], qvf[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    f32x4 q = {0.f, 0.f, 0.f, 0.f};
-    if (q_ok) q = *reinterpret_cast<const f32x4*>(p.Q + (size_t)iq * p.ldq + hoff + 16 * kk + 4 * g);
-    const f32x4 bu = *reinterpret_cast<const f32x4*>(p.bias_u + hoff + 16 * kk + 4 * g);
-    const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias_v + hoff + 16 * kk + 4 * g);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { quf[kk][e] = q[e] + bu[e]; qvf[kk][e] = q[e] + bv[e]; }
-  }
+  load_qu_qv(quf, qvf, p.Q, p.ldq, iq, q_ok, p.bias_u, p.bias_v, hoff, g);
   f32x4 o[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m_run = -INFINITY, l_run = 0.f;
 
-  int kmax = p.Tk;
-  const int ilast = min(i0 + MQ, p.Tq) - 1;
-  if (p.chunk > 0) kmax = min(kmax, ((ilast + q0) / p.chunk + 1) * p.chunk);
-  int lim = p.Tk;
-  if (p.chunk > 0) lim = min(lim, ((iq + q0) / p.chunk + 1) * p.chunk);
-  if (!q_ok) lim = 0;
+  const int kmax = chunk_bound(p.Tk, p.chunk, min(i0 + MQ, p.Tq) - 1 + q0);   // block-uniform loop bound
+  const int lim = q_ok ? chunk_bound(p.Tk, p.chunk, iq + q0) : 0;               // this lane's own visibility bound
   int jbeg = 0, jend = kmax, s_eff = 1;
   if (SPLIT) {
     const int span = p.ktiles_per_split * KT;
@@ -479,18 +371,7 @@ __global__ __launch_bounds__(256) void attention_relpos_mfma_kernel(AttnArgs p) 
 
   for (int j0 = jbeg; j0 < jend; j0 += KT) {
     __syncthreads();
-    for (int f = t; f < KT * (DH / 4); f += 256) {
-      const int row = f >> 4, c4 = (f & 15) * 4;
-      const int j = j0 + row;
-      f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = kv;
-      if (j < p.Tk) {
-        kv = *reinterpret_cast<const f32x4*>(p.K + (size_t)j * p.ldk + hoff + c4);
-        vv = *reinterpret_cast<const f32x4*>(p.V + (size_t)j * p.ldv + hoff + c4);
-      }
-      *reinterpret_cast<f32x4*>(Ks + row * LDT + c4) = kv;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) Vt[(c4 + c) * LDT + row] = vv[c];
-    }
+    stage_kv_tile(Ks, Vt, p.K, p.V, p.ldk, p.ldv, p.Tk, j0, hoff, t);
     {
       // local row lr <-> table row pbase + lr, pbase = j0 - (q0 + i0 + MQ - 1) + Tk - 1
       const int pbase = j0 - (q0 + i0 + MQ - 1) + p.Tk - 1;
@@ -523,60 +404,10 @@ __global__ __launch_bounds__(256) void attention_relpos_mfma_kernel(AttnArgs p) 
           gb = __builtin_amdgcn_mfma_f32_16x16x4f32(pb[e], qvf[kk][e], gb, 0, 0, 0);
         }
       }
-      // G[query r][window offset x]: x = 4g+e in ga, 16+4g+e in gb; BD for key 4g+e is x = 15 - r + 4g + e
-      *reinterpret_cast<f32x4*>(Gs + r * LDG + 4 * g) = ga;
-      *reinterpret_cast<f32x4*>(Gs + r * LDG + 16 + 4 * g) = gb;
-      const float* gr = Gs + r * LDG + 15 - r + 4 * g;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s[kt][e] += gr[e];
+      s[kt] += bd_skew(Gs, r, g, ga, gb);
     }
-    float mt = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int j = j0 + kt * 16 + 4 * g + e;
-        s[kt][e] = (j < lim) ? s[kt][e] * p.scale : -INFINITY;
-        mt = fmaxf(mt, s[kt][e]);
-      }
-    mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
-    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-    const float mn = fmaxf(m_run, mt);
-    float corr = 1.f, ls = 0.f;
-    if (mn > -INFINITY) {
-      corr = (m_run > -INFINITY) ? expf(m_run - mn) : 0.f;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float pe = (s[kt][e] > -INFINITY) ? expf(s[kt][e] - mn) : 0.f;
-          s[kt][e] = pe;
-          ls += pe;
-        }
-    } else {
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt) s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    ls += __shfl_xor(ls, 16, 64);
-    ls += __shfl_xor(ls, 32, 64);
-    l_run = l_run * corr + ls;
-    m_run = mn;
-    // the tile's P V product in a fresh accumulator, then one add into the running sum (see attention_mfma_kernel)
-    f32x4 ot[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) ot[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const f32x4 vf = *reinterpret_cast<const f32x4*>(Vt + (dt * 16 + r) * LDT + kt * 16 + 4 * g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ot[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[e], s[kt][e], ot[dt], 0, 0, 0);
-      }
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[dt][e] = o[dt][e] * corr + ot[dt][e];
+    const float corr = softmax_tile(s, j0, lim, p.scale, g, m_run, l_run);
+    pv_tile(o, s, Vt, r, g, corr);
   }
   if (SPLIT && s_eff > 1) {
     using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
@@ -594,13 +425,9 @@ __global__ __launch_bounds__(256) void attention_relpos_mfma_kernel(AttnArgs p) 
       const u32x4 ml = {__float_as_uint(m_run), __float_as_uint(l_run), 0u, 0u};
       __builtin_amdgcn_raw_buffer_store_b128(ml, rs, (4 * 256 + t) * 16, 0, 16);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
     __shared__ int s_last;
     unsigned* cnt = p.cnt + qt * (int)gridDim.y + h;
-    if (t == 0) s_last = (__hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(s_eff - 1)) ? 1 : 0;
-    __syncthreads();
-    if (!s_last) return;
+    if (!split_arrive(cnt, s_eff, &s_last)) return;
     // ---- the last arrival merges every group, in group order ----
     float mx = -INFINITY;
     for (int g2 = 0; g2 < s_eff; ++g2) {
@@ -627,18 +454,9 @@ __global__ __launch_bounds__(256) void attention_relpos_mfma_kernel(AttnArgs p) 
         for (int e = 0; e < 4; ++e) o[dt][e] += __uint_as_float(v[dt][e]) * f;
     }
     l_run = lsum;
-    if (t == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch of this context
+    split_reset(cnt);
   }
-  if (q_ok) {
-    const float inv = 1.0f / l_run;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      f32x4 v = o[dt];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] *= inv;
-      *reinterpret_cast<f32x4*>(p.O + (size_t)iq * p.ldo + hoff + 16 * dt + 4 * g) = v;
-    }
-  }
+  if (q_ok) store_rows(p.O, p.ldo, iq, hoff, g, o, l_run);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -652,120 +470,31 @@ __global__ __launch_bounds__(256) void attention_relpos_mfma_kernel(AttnArgs p) 
 // skew patch); the softmax is normalised per key tile and merged in key-tile order by the last arriving workgroup of a (query tile,
 // head) -- the hand-off protocol of the SPLIT form above.
 // -------------------------------------------------------------------------------------------------
-constexpr int Q16_LDO = 68;           // padded row of the cross-wave output sum
-
 __global__ __launch_bounds__(256) void attention_relpos_q16_kernel(AttnArgs p) {
-  using f32x4 = __attribute__((ext_vector_type(4))) float;
   using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
   __shared__ __attribute__((aligned(16))) float Gs_all[4 * 16 * LDG];
   __shared__ float ms[4][16], ls[4][16];
   __shared__ __attribute__((aligned(16))) float osum[4][16][Q16_LDO];
   __shared__ int s_last;
   const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int r = lane & 15, g = lane >> 4;
   const int h = blockIdx.y, hoff = h * DH;
   const int nqt = gridDim.x / p.ksplit;
   const int sp = blockIdx.x / nqt, qt = blockIdx.x - sp * nqt;
   const int i0 = qt * 16, q0 = p.q0;
-  const int ilast = min(i0 + 16, p.Tq) - 1;
-  int kmax = p.Tk;
-  if (p.chunk > 0) kmax = min(kmax, ((ilast + q0) / p.chunk + 1) * p.chunk);
+  const int kmax = chunk_bound(p.Tk, p.chunk, min(i0 + 16, p.Tq) - 1 + q0);
   const int s_eff = (kmax + KT - 1) / KT;              // key tiles that hold a visible key of this query tile
   if (sp >= s_eff) return;
-  const int jb = sp * KT + 16 * wave;                   // this wave's 16 keys
   const int iq = i0 + r;
   const bool q_ok = iq < p.Tq;
-  int lim = p.Tk;
-  if (p.chunk > 0) lim = min(lim, ((iq + q0) / p.chunk + 1) * p.chunk);
-  if (!q_ok) lim = 0;
+  const int lim = q_ok ? chunk_bound(p.Tk, p.chunk, iq + q0) : 0;
 
-  // ---- every operand of the wave in one round trip ----
-  f32x4 quf[4], qvf[4], kf[4], pa[4], pb[4];
-  float vv[4][4];
-  const int pbase = jb - (q0 + i0 + 15) + p.Tk - 1;     // table row of window row 0: key jb against the tile's last query
-  const int pra = pbase + r, prb = pbase + 16 + r;
-  const bool pa_ok = pra >= 0 && pra < 2 * p.Tk - 1, pb_ok = r < 15 && prb >= 0 && prb < 2 * p.Tk - 1;
-  const bool k_ok = jb + r < p.Tk;
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    const int c = hoff + 16 * kk + 4 * g;
-    f32x4 q = {0.f, 0.f, 0.f, 0.f};
-    if (q_ok) q = *reinterpret_cast<const f32x4*>(p.Q + (size_t)iq * p.ldq + c);
-    const f32x4 bu = *reinterpret_cast<const f32x4*>(p.bias_u + c);
-    const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias_v + c);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { quf[kk][e] = q[e] + bu[e]; qvf[kk][e] = q[e] + bv[e]; }
-    kf[kk] = pa[kk] = pb[kk] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (k_ok) kf[kk] = *reinterpret_cast<const f32x4*>(p.K + (size_t)(jb + r) * p.ldk + c);
-    if (pa_ok) pa[kk] = *reinterpret_cast<const f32x4*>(p.P + (size_t)pra * p.ldp + c);
-    if (pb_ok) pb[kk] = *reinterpret_cast<const f32x4*>(p.P + (size_t)prb * p.ldp + c);
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int key = jb + 4 * g + e;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) vv[dt][e] = key < p.Tk ? p.V[(size_t)key * p.ldv + hoff + dt * 16 + r] : 0.f;
-  }
-
-  // ---- scores: AC = K (q + u)^T, BD through the skew patch (see attention_relpos_mfma_kernel) ----
-  f32x4 s = {0.f, 0.f, 0.f, 0.f}, ga = s, gb = s;
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      s = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kk][e], quf[kk][e], s, 0, 0, 0);
-      ga = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[kk][e], qvf[kk][e], ga, 0, 0, 0);
-      gb = __builtin_amdgcn_mfma_f32_16x16x4f32(pb[kk][e], qvf[kk][e], gb, 0, 0, 0);
-    }
-  float* Gs = Gs_all + wave * 16 * LDG;
-  *reinterpret_cast<f32x4*>(Gs + r * LDG + 4 * g) = ga;
-  *reinterpret_cast<f32x4*>(Gs + r * LDG + 16 + 4 * g) = gb;
-  const float* gr = Gs + r * LDG + 15 - r + 4 * g;
-  float mw = -INFINITY;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int j = jb + 4 * g + e;
-    s[e] = (j < lim) ? (s[e] + gr[e]) * p.scale : -INFINITY;
-    mw = fmaxf(mw, s[e]);
-  }
-  mw = fmaxf(mw, __shfl_xor(mw, 16, 64));
-  mw = fmaxf(mw, __shfl_xor(mw, 32, 64));
-  float pe[4], lw = 0.f;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { pe[e] = (s[e] > -INFINITY) ? expf(s[e] - mw) : 0.f; lw += pe[e]; }
-  lw += __shfl_xor(lw, 16, 64);
-  lw += __shfl_xor(lw, 32, 64);
-  if (g == 0) { ms[wave][r] = mw; ls[wave][r] = lw; }
-  __syncthreads();
-  {
-    const float mt = fmaxf(fmaxf(ms[0][r], ms[1][r]), fmaxf(ms[2][r], ms[3][r]));
-    const float fw = (mw > -INFINITY) ? expf(mw - mt) : 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) pe[e] *= fw;
-  }
-  // ---- P V: D[query][d] += P[query][key] V[key][d] -- lane (r, g) ends up with queries 4 g + e', head column 16 dt + r ----
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
-    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o = __builtin_amdgcn_mfma_f32_16x16x4f32(pe[e], vv[dt][e], o, 0, 0, 0);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) osum[wave][4 * g + e][dt * 16 + r] = o[e];
-  }
-  __syncthreads();
-  // ---- thread (query q, columns d4 .. d4 + 3): the four waves' sums in wave order, the tile's (m, l) ----
-  const int q = t >> 4, d4 = (t & 15) * 4;
-  f32x4 acc = *reinterpret_cast<const f32x4*>(&osum[0][q][d4]);
-#pragma unroll
-  for (int w2 = 1; w2 < 4; ++w2) {
-    const f32x4 o2 = *reinterpret_cast<const f32x4*>(&osum[w2][q][d4]);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] += o2[e];
-  }
-  float m_run = fmaxf(fmaxf(ms[0][q], ms[1][q]), fmaxf(ms[2][q], ms[3][q])), l_run = 0.f;
-#pragma unroll
-  for (int w2 = 0; w2 < 4; ++w2) l_run += (ms[w2][q] > -INFINITY) ? ls[w2][q] * expf(ms[w2][q] - m_run) : 0.f;
+  f32x4 quf[4], qvf[4], acc;
+  float m_run, l_run;
+  load_qu_qv(quf, qvf, p.Q, p.ldq, iq, q_ok, p.bias_u, p.bias_v, hoff, g);
+  q16_tile(quf, qvf, [&](int j) { return p.K + (size_t)j * p.ldk; }, [&](int j) { return p.V + (size_t)j * p.ldv; }, p.P, p.ldp, p.Tk,
+           sp * KT, q0 + i0 + 15, lim, p.scale, hoff, Gs_all, ms, ls, osum, acc, m_run, l_run);
+  const int q = t >> 4, d4 = (t & 15) * 4;              // this thread's (query, columns d4 .. d4 + 3) of the tile's output
 
   if (s_eff > 1) {
     const int slot0 = (qt * (int)gridDim.y + h) * p.ksplit;
@@ -779,12 +508,8 @@ __global__ __launch_bounds__(256) void attention_relpos_q16_kernel(AttnArgs p) {
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(l_run), rs, (1040 + q) * 4, 0, 16);
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
     unsigned* cnt = p.cnt + qt * (int)gridDim.y + h;
-    if (t == 0) s_last = (__hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(s_eff - 1)) ? 1 : 0;
-    __syncthreads();
-    if (!s_last) return;
+    if (!split_arrive(cnt, s_eff, &s_last)) return;
     // ---- the last arrival merges every key tile, in key-tile order ----
     float mx = -INFINITY;
     for (int g2 = 0; g2 < s_eff; ++g2) {
@@ -805,7 +530,7 @@ __global__ __launch_bounds__(256) void attention_relpos_q16_kernel(AttnArgs p) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[e] += __uint_as_float(v[e]) * f;
     }
-    if (t == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch of this context
+    split_reset(cnt);
   }
   if (i0 + q < p.Tq) {
     const float inv = 1.0f / l_run;
@@ -823,12 +548,10 @@ __global__ __launch_bounds__(256) void attention_relpos_q16_kernel(AttnArgs p) {
 // that depends on what else is in the launch: a row's bits are a function of its own session.
 // -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void attention_pool_kernel(PoolAttnArgs p) {
-  using f32x4 = __attribute__((ext_vector_type(4))) float;
   __shared__ __attribute__((aligned(16))) float Gs_all[4 * 16 * LDG];
   __shared__ float ms[4][16], ls[4][16];
   __shared__ __attribute__((aligned(16))) float osum[4][16][Q16_LDO];
   const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int r = lane & 15, g = lane >> 4;
   const int h = blockIdx.y, hoff = h * DH;
   const int gq = blockIdx.x;
@@ -843,8 +566,11 @@ __global__ __launch_bounds__(256) void attention_pool_kernel(PoolAttnArgs p) {
   const float* Qs = p.Qs + (size_t)q_start * p.ld;
   float* cache = p.cache + (size_t)slot * p.slot_rows * p.ld;
   const float* P = p.P + (size_t)(p.p_tmax - Tk) * p.ldp;
-  // key / value row j: the slot's cache below the first query, the stacked rows from there on
-  auto krow = [&](int j) -> const float* { return j < q0 ? cache + (size_t)j * p.ld : Qs + (size_t)(j - q0) * p.ld; };
+  // q|k|v row of key j: the slot's cache below the first query, the stacked rows from there on (keys past the last: row 0, not read)
+  auto krow = [&](int j) -> const float* {
+    if (j >= Tk) j = 0;
+    return j < q0 ? cache + (size_t)j * p.ld : Qs + (size_t)(j - q0) * p.ld;
+  };
 
   const int q = t >> 4, d4 = (t & 15) * 4;              // thread (query q, columns d4 .. d4 + 3) of the cross-wave stage
   if (i0 + q < Tq) {                                    // this tile's rows of q|k|v (head h) into the slot cache
@@ -854,108 +580,21 @@ __global__ __launch_bounds__(256) void attention_pool_kernel(PoolAttnArgs p) {
     for (int part = 0; part < 3; ++part)
       *reinterpret_cast<f32x4*>(dst + part * p.H * DH) = *reinterpret_cast<const f32x4*>(src + part * p.H * DH);
   }
-  const int ilast = min(i0 + 16, Tq) - 1;
-  int kmax = Tk;
-  if (chunk > 0) kmax = min(kmax, ((ilast + q0) / chunk + 1) * chunk);
+  const int kmax = chunk_bound(Tk, chunk, min(i0 + 16, Tq) - 1 + q0);
   const int s_eff = (kmax + KT - 1) / KT;
   const int iq = i0 + r;
   const bool q_ok = iq < Tq;
-  int lim = Tk;
-  if (chunk > 0) lim = min(lim, ((iq + q0) / chunk + 1) * chunk);
-  if (!q_ok) lim = 0;
+  const int lim = q_ok ? chunk_bound(Tk, chunk, iq + q0) : 0;
   f32x4 quf[4], qvf[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    const int c = hoff + 16 * kk + 4 * g;
-    f32x4 qv = {0.f, 0.f, 0.f, 0.f};
-    if (q_ok) qv = *reinterpret_cast<const f32x4*>(Qs + (size_t)iq * p.ld + c);
-    const f32x4 bu = *reinterpret_cast<const f32x4*>(p.bias_u + c);
-    const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias_v + c);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { quf[kk][e] = qv[e] + bu[e]; qvf[kk][e] = qv[e] + bv[e]; }
-  }
+  load_qu_qv(quf, qvf, Qs, p.ld, iq, q_ok, p.bias_u, p.bias_v, hoff, g);
   f32x4 ACC = {0.f, 0.f, 0.f, 0.f};
   float M = -INFINITY, Lsum = 0.f;
   for (int sp = 0; sp < s_eff; ++sp) {
     if (sp > 0) __syncthreads();                        // the previous tile's LDS readers are done
-    const int jb = sp * KT + 16 * wave;
-    f32x4 kf[4], pa[4], pb[4];
-    float vv[4][4];
-    const int pbase = jb - (q0 + i0 + 15) + Tk - 1;
-    const int pra = pbase + r, prb = pbase + 16 + r;
-    const bool pa_ok = pra >= 0 && pra < 2 * Tk - 1, pb_ok = r < 15 && prb >= 0 && prb < 2 * Tk - 1;
-    const bool k_ok = jb + r < Tk;
-    const float* kr = krow(k_ok ? jb + r : 0);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const int c = hoff + 16 * kk + 4 * g;
-      kf[kk] = pa[kk] = pb[kk] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (k_ok) kf[kk] = *reinterpret_cast<const f32x4*>(kr + p.H * DH + c);
-      if (pa_ok) pa[kk] = *reinterpret_cast<const f32x4*>(P + (size_t)pra * p.ldp + c);
-      if (pb_ok) pb[kk] = *reinterpret_cast<const f32x4*>(P + (size_t)prb * p.ldp + c);
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int key = jb + 4 * g + e;
-      const float* vr = krow(key < Tk ? key : 0) + 2 * p.H * DH + hoff + r;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) vv[dt][e] = key < Tk ? vr[dt * 16] : 0.f;
-    }
-    f32x4 s = {0.f, 0.f, 0.f, 0.f}, ga = s, gb = s;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        s = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kk][e], quf[kk][e], s, 0, 0, 0);
-        ga = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[kk][e], qvf[kk][e], ga, 0, 0, 0);
-        gb = __builtin_amdgcn_mfma_f32_16x16x4f32(pb[kk][e], qvf[kk][e], gb, 0, 0, 0);
-      }
-    float* Gs = Gs_all + wave * 16 * LDG;
-    *reinterpret_cast<f32x4*>(Gs + r * LDG + 4 * g) = ga;
-    *reinterpret_cast<f32x4*>(Gs + r * LDG + 16 + 4 * g) = gb;
-    const float* gr = Gs + r * LDG + 15 - r + 4 * g;
-    float mw = -INFINITY;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int j = jb + 4 * g + e;
-      s[e] = (j < lim) ? (s[e] + gr[e]) * p.scale : -INFINITY;
-      mw = fmaxf(mw, s[e]);
-    }
-    mw = fmaxf(mw, __shfl_xor(mw, 16, 64));
-    mw = fmaxf(mw, __shfl_xor(mw, 32, 64));
-    float pe[4], lw = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { pe[e] = (s[e] > -INFINITY) ? expf(s[e] - mw) : 0.f; lw += pe[e]; }
-    lw += __shfl_xor(lw, 16, 64);
-    lw += __shfl_xor(lw, 32, 64);
-    if (g == 0) { ms[wave][r] = mw; ls[wave][r] = lw; }
-    __syncthreads();
-    {
-      const float mt = fmaxf(fmaxf(ms[0][r], ms[1][r]), fmaxf(ms[2][r], ms[3][r]));
-      const float fw = (mw > -INFINITY) ? expf(mw - mt) : 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) pe[e] *= fw;
-    }
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      f32x4 o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o = __builtin_amdgcn_mfma_f32_16x16x4f32(pe[e], vv[dt][e], o, 0, 0, 0);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) osum[wave][4 * g + e][dt * 16 + r] = o[e];
-    }
-    __syncthreads();
-    f32x4 acc = *reinterpret_cast<const f32x4*>(&osum[0][q][d4]);
-#pragma unroll
-    for (int w2 = 1; w2 < 4; ++w2) {
-      const f32x4 o2 = *reinterpret_cast<const f32x4*>(&osum[w2][q][d4]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] += o2[e];
-    }
-    const float m_t = fmaxf(fmaxf(ms[0][q], ms[1][q]), fmaxf(ms[2][q], ms[3][q]));
-    float l_t = 0.f;
-#pragma unroll
-    for (int w2 = 0; w2 < 4; ++w2) l_t += (ms[w2][q] > -INFINITY) ? ls[w2][q] * expf(ms[w2][q] - m_t) : 0.f;
+    f32x4 acc;
+    float m_t, l_t;
+    q16_tile(quf, qvf, [&](int j) { return krow(j) + p.H * DH; }, [&](int j) { return krow(j) + 2 * p.H * DH; }, P, p.ldp, Tk,
+             sp * KT, q0 + i0 + 15, lim, p.scale, hoff, Gs_all, ms, ls, osum, acc, m_t, l_t);
     if (sp == 0) {
       ACC = acc; M = m_t; Lsum = l_t;
     } else {                                            // merge the tile into the running (max, sum, output)

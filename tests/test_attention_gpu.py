@@ -675,9 +675,9 @@ _SESSIONS = [(1, 0, 7, 0), (15, 3, 2, 8), (16, 48, 9, 16), (17, 100, 0, 24), (33
 
 
 class PoolCase:
-    def __init__(self, seed, qscale=1.0):
+    def __init__(self, seed, qscale=1.0, sessions=_SESSIONS):
         pos, self.sess = G, []
-        for n, r0, slot, chunk in _SESSIONS:
+        for n, r0, slot, chunk in sessions:
             self.sess.append((pos, n, r0, r0 + n, slot, chunk))
             pos += n + G
         self.n = pos
@@ -744,22 +744,38 @@ def test_pool_kernel(lib, peaked):
             assert _same_bits(out[qs:qs + n], out9[qs:qs + n]), f"session at row {qs}: bits depend on the rest of the launch"
 
 
+def _session_on_q16(lib, c, sess):
+    """One session of a PoolCase through ss_op_attention_ex(q0 = r0) on attention_relpos_q16_kernel over the same keys (cache rows,
+    then the stacked rows)."""
+    qs, n, r0, T2, slot, chunk = sess
+    rows = torch.cat([c.cache[slot * SLOT_ROWS: slot * SLOT_ROWS + r0], c.Qs[qs:qs + n]]).cuda()
+    out = torch.full((n, DR), NAN, device="cuda")
+    f = dict(Q=at(rows, r0, 0), K=at(rows, 0, DR), V=at(rows, 0, 2 * DR), O=at(out), ldq=3 * DR, ldk=3 * DR, ldv=3 * DR, ldo=DR,
+             Tq=n, Tk=T2, H=HR, scale=0.125, chunk=chunk, q0=r0, P=at(c.dP, 1024 - T2), ldp=DR, bias_u=at(c.du), bias_v=at(c.dv),
+             use_split=1)
+    assert route(f, HR) == "q16"
+    assert launch(lib, **f) == 0
+    return out
+
+
 def test_pool_kernel_against_the_single_session_kernel(lib):
-    """Group 8: every session of the pool launch against ss_op_attention_ex(q0 = r0) on attention_relpos_q16_kernel over the same
-    keys (cache rows, then the stacked rows), 2e-5."""
+    """Group 8: every session of the pool launch against attention_relpos_q16_kernel, 2e-5 (the two merge their key tiles in
+    different orders: the last arrival's two passes against a running merge)."""
     c = PoolCase(seed=2100)
     out9, _, sess9 = c.run(lib, list(range(9)))
-    du, dv = c.du, c.dv
-    for (qs, n, r0, T2, slot, chunk) in sess9:
-        rows = torch.cat([c.cache[slot * SLOT_ROWS: slot * SLOT_ROWS + r0], c.Qs[qs:qs + n]]).cuda()
-        out = torch.full((n, DR), NAN, device="cuda")
-        f = dict(Q=at(rows, r0, 0), K=at(rows, 0, DR), V=at(rows, 0, 2 * DR), O=at(out), ldq=3 * DR, ldk=3 * DR, ldv=3 * DR, ldo=DR,
-                 Tq=n, Tk=T2, H=HR, scale=0.125, chunk=chunk, q0=r0, P=at(c.dP, 1024 - T2), ldp=DR, bias_u=at(du), bias_v=at(dv),
-                 use_split=1)
-        assert route(f, HR) == "q16"
-        assert launch(lib, **f) == 0
-        d = float((out - out9[qs:qs + n]).abs().max())
+    for sess in sess9:
+        qs, n, r0 = sess[:3]
+        d = float((_session_on_q16(lib, c, sess) - out9[qs:qs + n]).abs().max())
         assert d <= 2e-5, f"session n={n} r0={r0}: pool against q16 {d:.3e}"
+
+
+def test_pool_kernel_one_key_tile_has_the_bits_of_the_single_session_kernel(lib):
+    """Group 8: a session whose keys fit one key tile (9 rows at r0 = 40: T2 = 49).  Neither kernel merges anything then, so the
+    tile arithmetic the two share (q16_tile, csrc/attn_tile.hpp) is all there is: the same bits."""
+    c = PoolCase(seed=2300, sessions=[(9, 40, 4, 0)])
+    out, _, (sess,) = c.run(lib, [0])
+    qs, n = sess[:2]
+    assert _same_bits(out[qs:qs + n], _session_on_q16(lib, c, sess)), "pool against q16 on one key tile"
 
 
 def test_pool_refusals(lib):
