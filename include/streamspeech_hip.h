@@ -1059,6 +1059,14 @@ int64_t ss_debug_enc_step_launches(void);
 int ss_op_ln_linear(void* stream, const float* dX, int ldx, const float* ln_g, const float* ln_b, const float* dW,
                     const float* dbias, const float* dR, int ldr, float* dC, int ldc, int M, int N, int K, int act, float alpha,
                     int glu);
+/* ss_op_ln_linear plus what it cannot say.  ln_out (device, [M][K], may be NULL): the normalised rows as a second output -- only the
+ * decode GEMV (M <= 4, K % 256 == 0, K <= 2048) writes them, any other shape with ln_out set is SS_ERR_ARG.  canon: the arithmetic
+ * mode of this launch (0: the calling thread's, ss_debug_canon; 1 CANON_SEQ; 2 CANON_SMALLM, the fixed small-M form of the lock-step
+ * decode rows, up to 1024 rows).  ln_g / ln_b may both be NULL: a plain linear (ln_out is then SS_ERR_ARG, as is one of the two
+ * alone).  Returns what launch_conv_gemm returns.  tests/test_gemm_routes_gpu.py. */
+int ss_op_ln_linear_ex(void* stream, const float* dX, int ldx, const float* ln_g, const float* ln_b, float* ln_out, const float* dW,
+                       const float* dbias, const float* dR, int ldr, float* dC, int ldc, int M, int N, int K, int act, float alpha,
+                       int glu, int canon);
 
 /* Tuning / A-B hook (tools/conv_bench.py, tests): bm = 0 heuristic; 1 route every eligible launch to the first-generation
  * stream-K kernel with a grid of ks workgroups (ks = 0 -> 2 per CU; bn = 8: XCD tile groups); 2 no slab kernel; 3 the

@@ -144,6 +144,19 @@ extern "C" int ss_op_ln_linear(void* stream, const float* dX, int ldx, const flo
   a.ln_g = ln_g; a.ln_b = ln_b;
   return launch_conv_gemm(a, (hipStream_t)stream);       // SS_ERR_ARG when no kernel with a LayerNorm prologue takes the shape
 }
+// ... plus the two fields that entry cannot say: ln_out (the normalised rows as a second output, row stride K: the last launch of an MT
+// decode step) and the arithmetic mode of THIS launch (canon, as ss_op_conv_gemm_rows).  ln_g / ln_b may both be null: a plain linear,
+// which has no normalised rows to publish
+extern "C" int ss_op_ln_linear_ex(void* stream, const float* dX, int ldx, const float* ln_g, const float* ln_b, float* ln_out,
+                                  const float* dW, const float* dbias, const float* dR, int ldr, float* dC, int ldc, int M, int N, int K,
+                                  int act, float alpha, int glu, int canon) {
+  if (canon < 0 || canon > 2 || (ln_g == nullptr) != (ln_b == nullptr) || (ln_out && !ln_g)) return SS_ERR_ARG;
+  GemmArgs a;
+  a.A = dX; a.lda = ldx; a.W = dW; a.bias = dbias; a.R = dR; a.ldr = ldr; a.C = dC; a.ldc = ldc;
+  a.M = M; a.N = N; a.Cin = K; a.in_len = M; a.act = act; a.alpha = alpha; a.glu = glu; a.same_rows = 1;
+  a.ln_g = ln_g; a.ln_b = ln_b; a.ln_out = ln_out; a.canon = canon;
+  return launch_conv_gemm(a, (hipStream_t)stream);
+}
 // enable 0 / 1: the stage on conv_sk2<64> / on the slab kernels; 4 / 5: its Winograd form (conv_c64w.hip) off / on (the slab kernels stay on);
 // 6 / 7: the 128-channel stage on conv_sk2<128> / on the Winograd slab kernel
 extern "C" int ss_debug_conv_c64(int enable) {

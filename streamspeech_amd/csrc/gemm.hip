@@ -854,11 +854,11 @@ static int launch_cfg_ks(const GemmArgs& a, hipStream_t stream, ProfCls cls, lon
 
 template <int SK, int WN, bool GLU = false>
 static int launch_smallm(const GemmArgs& a, hipStream_t stream, ProfCls cls) {
+  if (a.ln_g && a.Cin > 512) return SS_ERR_ARG;   // fused LayerNorm keeps the row in registers (D <= 512); refused BEFORE prof_begin: the census counts launches
   dim3 grid((cdiv(a.N, 16 * WN) + 7) & ~7, cdiv(a.M, 16));   // see the kernel: n-tiles fastest, a multiple of 8 of them
   ProfRec rec{}; bool prof = false;
   int rc = prof_begin(a, stream, cls, rec, prof);
   if (rc != SS_OK) return rc;
-  if (a.ln_g && a.Cin > 512) return SS_ERR_ARG;   // fused LayerNorm keeps the row in registers (D <= 512)
   if (a.ln_g) hipLaunchKernelGGL((smallm_gemm_kernel<SK, WN, true, GLU>), grid, dim3(256), 0, stream, a);
   else hipLaunchKernelGGL((smallm_gemm_kernel<SK, WN, false, GLU>), grid, dim3(256), 0, stream, a);
   SS_LAUNCH_CHECK();

@@ -312,6 +312,7 @@ SIGNATURES = {
     "ss_debug_enc_step_launches": (_i64, []),
     "ss_debug_scratch_audit": (_i, [_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ss_op_ln_linear": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i]),
+    "ss_op_ln_linear_ex": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _i]),
     "ss_debug_last_logits": (_i, [_vp, _vp, _vp, _i64, C.POINTER(_i), C.POINTER(_i)]),
     "ss_debug_sk_errors": (_i, []),
     "ss_debug_attention_split": (_i, [_i]),
