@@ -60,6 +60,17 @@ enum Act : int { ACT_NONE = 0, ACT_SILU = 1, ACT_RELU = 2, ACT_LRELU = 3, ACT_TA
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
+// epilogue activation of the GEMM / conv kernels (Act codes; slope: of ACT_LRELU)
+__device__ __forceinline__ float act_apply(int act, float v, float slope) {
+  switch (act) {
+    case ACT_SILU: return v / (1.0f + expf(-v));
+    case ACT_RELU: return fmaxf(v, 0.f);
+    case ACT_TANH: return tanhf(v);
+    case ACT_LRELU: return v > 0.f ? v : v * slope;
+    default: return v;
+  }
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

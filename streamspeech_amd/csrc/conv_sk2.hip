@@ -613,7 +613,6 @@ extern "C" int ss_debug_sk2_timing(unsigned long long* h_out, int cap_wgs) {
   return g_k2_last_G;
 }
 #endif
-static const int g_k2_spare_cus = getenv("SS_SK2_SPARE_CUS") ? atoi(getenv("SS_SK2_SPARE_CUS")) : 0;   // tuning knob (measured flat)
 
 // (Rounds 4-5 had a pack-invariant mode here -- ranges cut on whole tiles, one accumulator chain over all of K.  Round 6's blocked
 //  chain needs a second accumulator set, which 128 accumulator registers per wave leave no room for: CANON_SEQ launches no longer
@@ -638,7 +637,7 @@ static int launch_sk2(const GemmArgs& a, hipStream_t stream, int g_force) {
   int cus = st->cus > K2_MAXG ? K2_MAXG : st->cus;
   // SS_SK2_SPARE_CUS = n: leave n CUs to the other streams' small kernels (a stream-K workgroup owns its CU: 480 of
   // the 512 registers per SIMD, 147 KB of LDS -- nothing can be co-resident with it)
-  if (g_k2_spare_cus > 0 && g_k2_spare_cus < cus) cus -= g_k2_spare_cus;
+  if (const int spare = disp().sk2_spare_cus; spare > 0 && spare < cus) cus -= spare;
   const long long nk = (long long)a.taps * (a.Cin / K2_BK);
   const long long U = (long long)cdiv(a.M, K2_BM) * (a.N / BN) * nk;
   long long G = g_force > 0 ? g_force : cus;        // one workgroup per CU (147 | 123 KB of LDS each), all resident

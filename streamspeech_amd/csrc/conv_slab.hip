@@ -135,16 +135,7 @@ __global__ __launch_bounds__(256, 2) void conv_slab_kernel(const GemmArgs p, con
           for (int e = 0; e < 4; ++e) v[e] += b[e];
         }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          switch (p.act) {
-            case ACT_SILU: v[e] = v[e] / (1.0f + expf(-v[e])); break;
-            case ACT_RELU: v[e] = fmaxf(v[e], 0.f); break;
-            case ACT_TANH: v[e] = tanhf(v[e]); break;
-            case ACT_LRELU: v[e] = v[e] > 0.f ? v[e] : v[e] * p.act_slope; break;
-            default: break;
-          }
-          v[e] *= p.alpha;
-        }
+        for (int e = 0; e < 4; ++e) v[e] = act_apply(p.act, v[e], p.act_slope) * p.alpha;
         if (p.R) {
           const f32x4 rr = *reinterpret_cast<const f32x4*>(p.R + (size_t)m * p.ldr + n);
 #pragma unroll
@@ -156,6 +147,17 @@ __global__ __launch_bounds__(256, 2) void conv_slab_kernel(const GemmArgs p, con
     }
   }
 #endif
+}
+
+// ---- eligibility prefixes of the slab kernels (gemm.hpp) ----
+bool slab_layout_ok(const GemmArgs& a) {
+  return a.same_rows && a.stride == 1 && a.chunk == 0 && !a.glu && !a.ln_g && a.lda == a.Cin && (a.ldc & 3) == 0 &&
+         (!a.R || (a.ldr & 3) == 0) && (!a.R2 || (a.ldr2 & 3) == 0) && (!a.C2 || (a.ldc2 & 3) == 0);
+}
+bool slab_conv_ok(const GemmArgs& a, int c) {
+  return slab_layout_ok(a) && !a.x3 && a.Cin == c && a.N == c &&
+         (a.in_act == ACT_NONE || (a.in_act == ACT_LRELU && a.in_slope > 0.f && a.in_slope < 1.f)) &&
+         (a.act == ACT_NONE || a.act == ACT_LRELU);
 }
 
 bool conv_slab_eligible(const GemmArgs& a) {

@@ -26,22 +26,31 @@ struct Dispatch {
   int c64w_min_k = 3;                                                                 // SS_CONV_C64_WINOGRAD_MIN_K
   long long c128w_min_rows = 65536, c256w_min_rows = 32768;                           // SS_CONV_C128 / C256_MIN_ROWS
   int c256w_rows = 128;            // SS_CONV_C256_ROWS / ss_debug_conv_c256_rows: block height of the 256-channel Winograd form, 128 (all 256 columns, one workgroup) or 256 (two workgroups by column half)
+  int c32_min_k = 7, c16_min_k = 11;   // SS_CONV_C32 / C16_MIN_K: smallest kernel size whose ResBlock convs run conv by conv instead of as one fused launch (vocoder.hip)
   int slab_grid_cap = 0;           // test hook (ss_debug_slab): > 0 caps the persistent grid of every slab kernel (slab_grid, gemm.hpp)
   // conv_sk.hip
   int sk_groups = 0;               // XCD tile grouping of the first-generation stream-K kernel (tuning hook)
+  // conv_sk2.hip
+  int sk2_spare_cus = 0;           // SS_SK2_SPARE_CUS: CUs left without a workgroup (tuning knob, measured flat)
   // ffn.hip / encoder FFN routing
   int ffn_force_g = 0;             // fixed grid (tests)
   int ffn_wm = 3, ffn_wm_forced = 0;   // 16-row MFMA tiles per wave; forced by SS_FFN_WM / ss_debug_ffn
+  int ffn_wm_env = 0;              // SS_FFN_WM as read at start-up (0: unset): what ss_debug_ffn(rows = 0) puts back
   int ffn_fusion = 1;              // SS_NO_FFN_FUSION
   int ffn_min_rows = 1000;         // SS_FFN_MIN_ROWS
   // gemm.hip
   int force_bm = 0, force_bn = 0, force_ks = 0;   // ss_debug_force_tile
   double sk_min_flops = 4e9;       // SS_SK_MIN_GFLOP
+  int smallm_max_rows = 192;       // SS_SMALLM_MAX_ROWS: row limit of the no-LDS small-M kernel (smallm_eligible)
+  long long sk_min_units = 12 * 512;   // SS_SK_MIN_UNITS: (tile, k-step) units from which an N % 128 == 0 shape goes to stream-K
+  int no_sk2 = 0;                  // SS_NO_SK2: A/B knob, first-generation stream-K kernel only
+  int sk2_min_k64 = 192;           // SS_SK2_MINK64: N % 128 == 64, smallest taps * Cin for conv_sk2<64>
   // vocoder ResBlock fusion (model.hip)
   int no_resblock_fusion = 0, no_pair_fusion = 0;   // SS_NO_RESBLOCK_FUSION / SS_NO_PAIR_FUSION, ss_debug_force_tile(6 | 3)
   // rtlin.hip
   int rt_off = 0, rt_min_rows = 193, rt_force_g = 0;   // SS_NO_RTLIN, SS_RTLIN_MIN_ROWS, ss_debug_rtlin
   long long rt_min_units = 4000;                       // SS_RTLIN_MIN_UNITS
+  int rt_wg_per_cu = 0;                                // SS_RTLIN_WG_PER_CU: resident rt_linear workgroups per CU (0: by the launch's unit count)
   long long rt_kb_min_units = 256;                     // SS_RTLIN_KB_MIN_UNITS: (48-row tile, 64-column group) units from which rt_linear_kb takes a K > 256 linear
   int rt_kb_xmap = 1;                                  // SS_RTLIN_KB_XMAP: 0 = every workgroup walks a contiguous (tile, column group) range; 1 = the column groups of a row tile run side by side on one XCD
   int rt_kb_uw = 0;                                    // SS_RTLIN_KB_UW: 16-column units per wave and column group (0: by the launch's unit count; 1 / 2 / 4 force)

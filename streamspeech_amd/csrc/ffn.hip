@@ -408,10 +408,9 @@ void ffn_fused_debug_grid(int g) { dispatch_edit([g](Dispatch& d) { d.ffn_force_
 // to clobber an SS_FFN_WM override with the built-in default)
 void ffn_fused_debug_rows(int wm) {
   if (wm < 0) return;
-  static const int env_wm = getenv("SS_FFN_WM") ? atoi(getenv("SS_FFN_WM")) : 0;
   dispatch_edit([wm](Dispatch& d) {
     if (wm >= 1 && wm <= 4) { d.ffn_wm = wm; d.ffn_wm_forced = 1; }
-    else if (env_wm >= 1 && env_wm <= 4) { d.ffn_wm = env_wm; d.ffn_wm_forced = 1; }
+    else if (d.ffn_wm_env >= 1 && d.ffn_wm_env <= 4) { d.ffn_wm = d.ffn_wm_env; d.ffn_wm_forced = 1; }
     else { d.ffn_wm = 3; d.ffn_wm_forced = 0; }
   });
 }

@@ -10,17 +10,7 @@
 // C/D layout (MI355X guide §3): col = lane&15, row = (lane>>4)*4 + reg.
 #include "gemm.hpp"
 
-#include <atomic>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
-#include <mutex>
-#include <tuple>
 #include <type_traits>
-#include <utility>
-#include <vector>
 
 namespace ss {
 
@@ -256,15 +246,7 @@ __global__ __launch_bounds__(256 * KS) void conv_gemm_kernel(const GemmArgs p) {
   }
 
   // ---- epilogue ----
-  auto activate = [&](float v) -> float {
-    switch (p.act) {
-      case ACT_SILU: return v / (1.0f + expf(-v));
-      case ACT_RELU: return fmaxf(v, 0.f);
-      case ACT_TANH: return tanhf(v);
-      case ACT_LRELU: return v > 0.f ? v : v * p.act_slope;
-      default: return v;
-    }
-  };
+  auto activate = [&](float v) -> float { return act_apply(p.act, v, p.act_slope); };
   // The MFMAs are issued with the operands swapped (D = W_tile . A_tile^T): in the C/D layout
   // (col = lane&15, row = 4*(lane>>4) + reg) a lane then holds 4 CONSECUTIVE output channels
   // n = 4g..4g+3 of ONE row m = r, so bias / residual / output move as float4 whenever the leading
@@ -357,6 +339,19 @@ __global__ __launch_bounds__(256 * KS) void conv_gemm_kernel(const GemmArgs p) {
   }
 }
 
+
+// Store of the two no-LDS kernels below: C[m][n] = act(acc + b) * alpha [+ R[m][n]], act = SiLU / ReLU / none
+__device__ __forceinline__ void linear_store(const GemmArgs& p, int m, int n, float acc, float b) {
+  float v = acc + b;
+  switch (p.act) {
+    case ACT_SILU: v = v / (1.0f + expf(-v)); break;
+    case ACT_RELU: v = fmaxf(v, 0.f); break;
+    default: break;
+  }
+  v *= p.alpha;
+  if (p.R) v += p.R[(size_t)m * p.ldr + n];
+  p.C[(size_t)m * p.ldc + n] = v;
+}
 
 // =================================================================================================
 // Small-M linear layers (M <= 128: every encoder/decoder projection at batch 1, decode steps at
@@ -523,17 +518,7 @@ __global__ __launch_bounds__(256) void smallm_gemm_kernel(const GemmArgs p) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int m = m0 + g * 4 + e;
-    if (m < p.M) {
-      float v = acc[e] + b;
-      switch (p.act) {
-        case ACT_SILU: v = v / (1.0f + expf(-v)); break;
-        case ACT_RELU: v = fmaxf(v, 0.f); break;
-        default: break;
-      }
-      v *= p.alpha;
-      if (p.R) v += p.R[(size_t)m * p.ldr + n];
-      p.C[(size_t)m * p.ldc + n] = v;
-    }
+    if (m < p.M) linear_store(p, m, n, acc[e], b);
   }
 }
 
@@ -630,16 +615,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemmArgs p) {
   const float b = p.bias ? p.bias[col] : 0.f;
 #pragma unroll
   for (int m = 0; m < MR; ++m) {
-    if (m >= p.M) continue;
-    float v = acc[m] + b;
-    switch (p.act) {
-      case ACT_SILU: v = v / (1.0f + expf(-v)); break;
-      case ACT_RELU: v = fmaxf(v, 0.f); break;
-      default: break;
-    }
-    v *= p.alpha;
-    if (p.R) v += p.R[(size_t)m * p.ldr + col];
-    p.C[(size_t)m * p.ldc + col] = v;
+    if (m < p.M) linear_store(p, m, col, acc[m], b);
   }
 }
 
@@ -667,155 +643,6 @@ static int launch_gemv(const GemmArgs& a, hipStream_t stream) {
   return launch_gemv_ks<4>(a, stream);
 }
 
-// ---- optional event profiler -------------------------------------------------------------------
-static const char* kTileNames[] = {
-    "conv_gemm<128,16,16,4,1>", "conv_gemm<128,32,32,4,1>", "conv_gemm<128,32,16,4,1>", "conv_gemm<16,128,32,1,4>",
-    "conv_gemm<16,128,16,1,4>", "conv_gemm<128,128,16,2,2>", "conv_gemm<128,64,32,2,2>", "conv_gemm<64,64,32,2,2>",
-    "conv_gemm<64,64,16,2,2>", "conv_gemm<32,64,32,2,2>", "conv_gemm<32,64,16,2,2>", "conv_gemm<32,32,32,2,2>",
-    "smallm_gemm<4,1>", "smallm_gemm<2,2>", "smallm_gemm<1,4>", "conv_sk<128,BN,32>",
-    "conv_slab<32>", "conv_slab<16>", "conv_sk2<256,128,32>", "conv_sk2_bf16x3<256,128,32>",
-    // whole-ResBlock launches of the narrow vocoder stages (resblock.hip) and the fused encoder FFN (ffn.hip): kernels of their own,
-    // booked under their own names (round 3 booked resblock_fused under conv_slab<..>: VERDICT r3 "mislabelled second kernel")
-    "resblock_fused<32>", "resblock_fused<16>", "ffn_fused<256,2048>", "rt_linear<48,256>", "conv_c64<256,64>", "conv_c32<256,32>", "conv_c16<256,16>", "conv_c64w<256,64>", "conv_c128w<256,128>", "conv_c32w<256,32>", "conv_c256w<256,128>", "rt_linear_kb<48,256>",
-    "conv_f16<64>", "conv_f16<128>", "conv_f16<256>"};
-static_assert(sizeof(kTileNames) / sizeof(kTileNames[0]) == kNumTileCfg, "one name per ProfCls, in enum order");
-static std::atomic<int> g_prof_mask{0};     // event brackets per class: written by ss_prof_enable between regions, read by every launch
-static std::atomic<int> g_prof_mask_hi{0};  // ... classes 32 and up (ss_prof_enable_hi)
-static std::vector<ProfRec> g_prof_recs;
-static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_prof_pool;
-static std::mutex g_prof_mu;
-
-void prof_enable(int cls_mask) { g_prof_mask.store(cls_mask, std::memory_order_relaxed); }
-void prof_enable_hi(int cls_mask) { g_prof_mask_hi.store(cls_mask, std::memory_order_relaxed); }
-const char* prof_cfg_name(int cls) { return (cls >= 0 && cls < kNumTileCfg) ? kTileNames[cls] : "?"; }
-void prof_reset() {
-  for (auto& r : g_prof_recs) g_prof_pool.push_back({r.e0, r.e1});
-  g_prof_recs.clear();
-}
-int prof_read_issued(int cls, double* issued) {
-  double v = 0;
-  for (auto& r : g_prof_recs) if (r.cls == cls) v += r.issued;
-  if (issued) *issued = v;
-  return SS_OK;
-}
-int prof_read(int cls, double* ms_total, double* flops_total, long long* launches, double* bytes_total) {
-  double ms = 0, fl = 0, by = 0; long long n = 0;
-  for (auto& r : g_prof_recs) {
-    if (r.cls != cls) continue;
-    if (hipEventSynchronize(r.e1) != hipSuccess) return SS_ERR_HIP;
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, r.e0, r.e1) != hipSuccess) return SS_ERR_HIP;
-    ms += t; fl += r.flops; by += r.bytes; ++n;
-  }
-  if (ms_total) *ms_total = ms;
-  if (flops_total) *flops_total = fl;
-  if (launches) *launches = n;
-  if (bytes_total) *bytes_total = by;
-  return SS_OK;
-}
-
-// Always-on launch census (no events, no synchronisation): launches, algorithmic FLOPs and bytes per tile class since the
-// library was loaded.  Lets a profile of a WHOLE process (rocprofv3 kernel stats, PMC passes) be divided by the
-// algorithmic work of exactly the launches it saw.
-// (relaxed atomics: eight host threads launch concurrently in bench.py; integer FLOP / byte counts -- 2^64 is ~18 EFLOP)
-struct ProfTotals { std::atomic<unsigned long long> flops{0}, bytes{0}, launches{0}; };
-static ProfTotals g_prof_totals[kNumTileCfg];
-static std::mutex g_tot_mu;          // SS_SHAPE_LOG table only
-// SS_SHAPE_LOG=<path>: per-(class, N, taps, Cin, operands) launch table written at process exit (tuning aid: which
-// layers land on which kernel)
-struct ShapeTot { long launches = 0; double rows = 0, flops = 0, bytes = 0; };
-using ShapeKey = std::tuple<int, int, int, int, int>;
-static std::map<ShapeKey, ShapeTot>* g_shapes = nullptr;
-static std::string shape_table() {
-  std::string out = "class N taps Cin operands launches mean_rows gflop_per_launch mbyte_per_launch\n";
-  if (!g_shapes) return out;
-  char line[256];
-  for (auto& kv : *g_shapes) {
-    const ShapeTot& z = kv.second;
-    snprintf(line, sizeof line, "%d %d %d %d %d %ld %.0f %.3f %.2f\n", std::get<0>(kv.first), std::get<1>(kv.first), std::get<2>(kv.first),
-             std::get<3>(kv.first), std::get<4>(kv.first), z.launches, z.rows / z.launches, z.flops / z.launches * 1e-9, z.bytes / z.launches * 1e-6);
-    out += line;
-  }
-  return out;
-}
-static void shape_log_dump() {
-  const char* path = getenv("SS_SHAPE_LOG");
-  FILE* f = path ? fopen(path, "w") : nullptr;
-  if (!f) return;
-  std::lock_guard<std::mutex> lk(g_tot_mu);
-  fputs(shape_table().c_str(), f);
-  fclose(f);
-}
-static std::atomic<int> g_shape_log{getenv("SS_SHAPE_LOG") != nullptr ? 1 : 0};
-void prof_shape_log(int on) {
-  std::lock_guard<std::mutex> lk(g_tot_mu);
-  if (on && g_shapes && !getenv("SS_SHAPE_LOG")) g_shapes->clear();     // a fresh in-process collection
-  g_shape_log.store(on ? 1 : 0, std::memory_order_relaxed);
-}
-int prof_shape_dump(char* buf, int cap) {
-  std::lock_guard<std::mutex> lk(g_tot_mu);
-  const std::string t = shape_table();
-  if (buf && cap > 0) { const int n = (int)std::min<size_t>(t.size(), (size_t)cap - 1); memcpy(buf, t.data(), n); buf[n] = 0; }
-  return (int)t.size() + 1;
-}
-int prof_totals(int cls, double* flops, double* bytes, long long* launches) {
-  if (cls < 0 || cls >= kNumTileCfg) return SS_ERR_ARG;
-  if (flops) *flops = (double)g_prof_totals[cls].flops.load(std::memory_order_relaxed);
-  if (bytes) *bytes = (double)g_prof_totals[cls].bytes.load(std::memory_order_relaxed);
-  if (launches) *launches = (long long)g_prof_totals[cls].launches.load(std::memory_order_relaxed);
-  return SS_OK;
-}
-static void algo_work(const GemmArgs& a, double& flops, double& bytes) {
-  flops = a.algo_flops > 0 ? a.algo_flops : 2.0 * (double)a.M * a.N * a.taps * a.Cin;
-  // algorithmic bytes: weights + bias once, every input row once, every output element once,
-  // residual operands once (all f32); a second (pre-activated) output is NOT algorithmic
-  const double ncols = a.glu ? a.N / 2 : a.N;
-  bytes = 4.0 * ((double)a.N * a.taps * a.Cin + (a.bias ? a.N : 0) + (double)a.in_len * a.Cin +
-                 (double)a.M * ncols * (1 + (a.R ? 1 : 0) + (a.R2 ? 1 : 0)));
-  if (a.algo_bytes > 0) bytes = a.algo_bytes;
-}
-
-static bool prof_cls_winograd(ProfCls cls) { return cls >= PROF_CONV_C64W && cls <= PROF_CONV_C256W; }
-
-int prof_begin(const GemmArgs& a, hipStream_t stream, ProfCls cls, ProfRec& rec, bool& prof) {
-  {
-    double fl, by;
-    algo_work(a, fl, by);
-    g_prof_totals[cls].flops.fetch_add((unsigned long long)(fl + 0.5), std::memory_order_relaxed);
-    g_prof_totals[cls].bytes.fetch_add((unsigned long long)(by + 0.5), std::memory_order_relaxed);
-    g_prof_totals[cls].launches.fetch_add(1ull, std::memory_order_relaxed);
-    if (g_shape_log.load(std::memory_order_relaxed)) {
-      std::lock_guard<std::mutex> lk(g_tot_mu);
-      if (!g_shapes) { g_shapes = new std::map<ShapeKey, ShapeTot>(); if (getenv("SS_SHAPE_LOG")) atexit(shape_log_dump); }
-      const int ops = (a.R ? 1 : 0) | (a.R2 ? 2 : 0) | (a.C2 ? 4 : 0) | (a.in_act != ACT_NONE ? 8 : 0) | (a.act != ACT_NONE ? 16 : 0) | (a.glu ? 32 : 0) | (a.nseg > 0 ? 64 : 0);
-      ShapeTot& z = (*g_shapes)[ShapeKey(cls, a.N, a.taps, a.Cin, ops)];
-      z.launches += 1; z.rows += a.M; z.flops += fl; z.bytes += by;
-    }
-  }
-  prof = cls < 32 ? ((unsigned)g_prof_mask.load(std::memory_order_relaxed) >> cls) & 1u
-                  : ((unsigned)g_prof_mask_hi.load(std::memory_order_relaxed) >> (cls - 32)) & 1u;
-  if (!prof) return SS_OK;
-  std::lock_guard<std::mutex> lk(g_prof_mu);
-  if (!g_prof_pool.empty()) { rec.e0 = g_prof_pool.back().first; rec.e1 = g_prof_pool.back().second; g_prof_pool.pop_back(); }
-  else { SS_HIP_CHECK(hipEventCreate(&rec.e0)); SS_HIP_CHECK(hipEventCreate(&rec.e1)); }
-  rec.cls = cls;
-  algo_work(a, rec.flops, rec.bytes);
-  // Winograd classes (conv_c64w / conv_c128w / conv_c32w / conv_c256w): 4 MFMA k-blocks per output pair and full tap group + 2 (3) for a
-  // last group of one (two) taps, instead of 2 k: 4 / 10 / 15 against 6 / 14 / 22 at k = 3 / 7 / 11
-  rec.issued = (prof_cls_winograd(cls) && a.taps >= 3) ? rec.flops * (4.0 * (a.taps / 3) + (a.taps % 3 ? a.taps % 3 + 1 : 0)) / (2.0 * a.taps) : rec.flops;
-  SS_HIP_CHECK(hipEventRecord(rec.e0, stream));
-  return SS_OK;
-}
-int prof_end(hipStream_t stream, ProfRec& rec, bool prof) {
-  if (prof) {
-    // both event records of a bracket are made under the lock (it did not cure rocprofv3 7.2's crashes on the 8-thread bench
-    // command -- those are inside its own launch interception, profiles/README.md -- but there is no reason to race here)
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    SS_HIP_CHECK(hipEventRecord(rec.e1, stream));
-    g_prof_recs.push_back(rec);
-  }
-  return SS_OK;
-}
 
 // register prefetch depth: measured flat from 1 to 4 on MI355X (profiles/r01_tile_sweep.txt) -> 1
 constexpr int default_pd(int, int) { return 1; }
@@ -865,195 +692,63 @@ static int launch_smallm(const GemmArgs& a, hipStream_t stream, ProfCls cls) {
   return prof_end(stream, rec, prof);
 }
 
-// (Dispatch::sk_min_flops, SS_SK_MIN_GFLOP: below this the small-tile kernels win -- tools/conv_bench.py sk)
-// ---- stream-K workspaces (see gemm.hpp) -----------------------------------------------------------
-constexpr size_t SKW_SYNC_BYTES = (16 + 1024) * sizeof(unsigned) + 256;      // >= both kernels' flag tables
-static std::mutex g_skw_mu;
-static std::vector<SkWorkspace*> g_skw_live;                                 // for the error count only
-static std::map<std::pair<int, hipStream_t>, SkWorkspace*> g_skw_fallback;  // launches outside any context scope
-static thread_local SkWorkspace* t_skw = nullptr;
 
-SkWorkspace* sk_workspace_new() {
-  SkWorkspace* w = new SkWorkspace();
-  std::lock_guard<std::mutex> lk(g_skw_mu);
-  g_skw_live.push_back(w);
-  return w;
-}
-void sk_workspace_free(SkWorkspace* w) {
-  if (!w) return;
-  {
-    std::lock_guard<std::mutex> lk(g_skw_mu);
-    for (size_t i = 0; i < g_skw_live.size(); ++i)
-      if (g_skw_live[i] == w) { g_skw_live.erase(g_skw_live.begin() + i); break; }
-  }
-  if (w->ws) (void)hipFree(w->ws);
-  if (w->sync1) (void)hipFree(w->sync1);
-  if (w->sync2) (void)hipFree(w->sync2);
-  if (w->sync3) (void)hipFree(w->sync3);
-  if (w->dbg) (void)hipFree(w->dbg);
-  delete w;
-}
-// ---- dispatch settings (dispatch.hpp) ---------------------------------------------------------------
-namespace {
-std::mutex g_disp_mu;
-std::atomic<unsigned> g_disp_gen{1};
-Dispatch env_defaults() {
-  Dispatch d;
-  auto I = [](const char* k, int dflt) { const char* e = getenv(k); return e ? atoi(e) : dflt; };
-  auto L = [](const char* k, long long dflt) { const char* e = getenv(k); return e ? atoll(e) : dflt; };
-  d.attn_split = I("SS_ATTN_NO_SPLIT", 0) ? -1 : 0; d.attn_q16 = I("SS_ATTN_Q16", d.attn_q16);
-  d.c16_off = I("SS_NO_CONV_C16", 0) ? 1 : 0; d.c32_off = I("SS_NO_CONV_C32", 0) ? 1 : 0; d.c64_off = I("SS_NO_CONV_C64", 0) ? 1 : 0;
-  d.c16_min_rows = L("SS_CONV_C16_MIN_ROWS", d.c16_min_rows); d.c32_min_rows = L("SS_CONV_C32_MIN_ROWS", d.c32_min_rows);
-  d.c64_min_rows = L("SS_CONV_C64_MIN_ROWS", d.c64_min_rows);
-  d.c64w_on = I("SS_CONV_C64_WINOGRAD", 1); d.c128w_on = I("SS_CONV_C128_WINOGRAD", 1); d.c256w_on = I("SS_CONV_C256_WINOGRAD", 1);
-  d.c32w_on = I("SS_CONV_C32_WINOGRAD", 1); d.c64w_min_k = I("SS_CONV_C64_WINOGRAD_MIN_K", 3);
-  d.c128w_min_rows = L("SS_CONV_C128_MIN_ROWS", d.c128w_min_rows); d.c256w_min_rows = L("SS_CONV_C256_MIN_ROWS", d.c256w_min_rows);
-  if (const int r = I("SS_CONV_C256_ROWS", d.c256w_rows); r == 128 || r == 256) d.c256w_rows = r;
-  if (getenv("SS_FFN_WM")) { d.ffn_wm = I("SS_FFN_WM", 3); d.ffn_wm_forced = 1; }
-  d.ffn_fusion = I("SS_NO_FFN_FUSION", 0) ? 0 : 1; d.ffn_min_rows = I("SS_FFN_MIN_ROWS", d.ffn_min_rows);
-  if (getenv("SS_SK_MIN_GFLOP")) d.sk_min_flops = 1e9 * atof(getenv("SS_SK_MIN_GFLOP"));
-  d.no_resblock_fusion = I("SS_NO_RESBLOCK_FUSION", 0); d.no_pair_fusion = I("SS_NO_PAIR_FUSION", 0);
-  d.rt_off = I("SS_NO_RTLIN", 0) ? 1 : 0; d.rt_min_rows = I("SS_RTLIN_MIN_ROWS", d.rt_min_rows); d.rt_min_units = L("SS_RTLIN_MIN_UNITS", d.rt_min_units);
-  d.rt_kb_min_units = L("SS_RTLIN_KB_MIN_UNITS", d.rt_kb_min_units); d.rt_kb_uw = I("SS_RTLIN_KB_UW", d.rt_kb_uw); d.rt_kb_xmap = I("SS_RTLIN_KB_XMAP", d.rt_kb_xmap);
-  return d;
-}
-Dispatch& process_settings() { static Dispatch d = env_defaults(); return d; }      // (callers hold g_disp_mu)
-thread_local const Dispatch* t_disp = nullptr;
-thread_local CtxDispatch t_disp_own;          // launches outside any context (ss_op_* unit-test entry points)
-}  // namespace
-void dispatch_edit(const std::function<void(Dispatch&)>& fn) {
-  std::lock_guard<std::mutex> lk(g_disp_mu);
-  fn(process_settings());
-  g_disp_gen.fetch_add(1, std::memory_order_release);
-}
-void slab_debug(int grid, long long min_rows) {
-  const Dispatch dflt = env_defaults();
-  dispatch_edit([=](Dispatch& d) {
-    d.slab_grid_cap = grid > 0 ? grid : 0;
-    const bool set = min_rows >= 0;
-    d.c16_min_rows = set ? min_rows : dflt.c16_min_rows; d.c32_min_rows = set ? min_rows : dflt.c32_min_rows;
-    d.c64_min_rows = set ? min_rows : dflt.c64_min_rows;
-    d.c128w_min_rows = set ? min_rows : dflt.c128w_min_rows; d.c256w_min_rows = set ? min_rows : dflt.c256w_min_rows;
-  });
-}
-// block height of the 256-channel Winograd form (conv_c64w.hip): 128 or 256; 0 puts the process default back
-int conv_c256w_rows_debug(int rows) {
-  if (rows != 0 && rows != 128 && rows != 256) return SS_ERR_ARG;
-  const int dflt = env_defaults().c256w_rows;
-  dispatch_edit([=](Dispatch& d) { d.c256w_rows = rows ? rows : dflt; });
-  return SS_OK;
-}
-const Dispatch* CtxDispatch::refresh() {
-  const unsigned now = g_disp_gen.load(std::memory_order_acquire);
-  if (gen != now) {
-    std::lock_guard<std::mutex> lk(g_disp_mu);
-    d = process_settings();
-    gen = g_disp_gen.load(std::memory_order_relaxed);
-  }
-  return &d;
-}
-const Dispatch& disp() { return t_disp ? *t_disp : *t_disp_own.refresh(); }
-DispatchScope::DispatchScope(const Dispatch* d) : prev(t_disp) { t_disp = d; }
-DispatchScope::~DispatchScope() { t_disp = prev; }
-
-SkScope::SkScope(SkWorkspace* w) : prev(t_skw), prev_disp(t_disp) { t_skw = w; t_disp = w ? w->disp.refresh() : nullptr; }
-SkScope::~SkScope() { t_skw = prev; t_disp = prev_disp; }
-
-int sk_workspace_acquire(hipStream_t stream, SkWorkspace** out) {
-  *out = nullptr;
-  int dev = 0;
-  SS_HIP_CHECK(hipGetDevice(&dev));
-  SkWorkspace* w = t_skw;
-  if (!w) {
-    std::lock_guard<std::mutex> lk(g_skw_mu);
-    SkWorkspace*& slot = g_skw_fallback[std::make_pair(dev, stream)];
-    if (!slot) { slot = new SkWorkspace(); g_skw_live.push_back(slot); }
-    w = slot;
-  }
-  if (!w->ws) {
-    int cus = 0;
-    SS_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (cus <= 0) cus = 256;
-    if (cus > 512) cus = 512;
-    w->dev = dev; w->cus = cus;
-    SS_HIP_CHECK(hipMalloc(&w->ws, (size_t)cus * 256 * 128 * sizeof(float)));
-    SS_HIP_CHECK(hipMalloc(&w->sync1, SKW_SYNC_BYTES));
-    SS_HIP_CHECK(hipMalloc(&w->sync2, SKW_SYNC_BYTES));
-    SS_HIP_CHECK(hipMemsetAsync(w->sync1, 0, SKW_SYNC_BYTES, stream));
-    SS_HIP_CHECK(hipMemsetAsync(w->sync2, 0, SKW_SYNC_BYTES, stream));
-    SS_HIP_CHECK(hipMalloc(&w->sync3, 4096 * sizeof(unsigned)));
-    SS_HIP_CHECK(hipMemsetAsync(w->sync3, 0, 4096 * sizeof(unsigned), stream));
-    SS_HIP_CHECK(hipStreamSynchronize(stream));   // once per context: a later call may arrive on another stream and must see the zeros
-  } else if (w->dev != dev) {
-    return SS_ERR_ARG;                 // a context belongs to the device it first ran on
-  }
-  *out = w;
-  return SS_OK;
+// One rung of the tile ladder: the blocked-chain form (BLK: one k-group), or the plain form with the k-split that lets
+// tiles * 4 * KS waves cover the SIMDs, up to MAXKS (1: none)
+template <bool BLK, int BM, int BN, int BK, int WM, int WN, int MAXKS>
+static int launch_rung(const GemmArgs& a, hipStream_t stream, ProfCls cls, long tiles) {
+  if constexpr (BLK) return launch_cfg<BM, BN, BK, WM, WN, 1, 1, true>(a, stream, cls);
+  else return launch_cfg_ks<BM, BN, BK, WM, WN, MAXKS>(a, stream, cls, tiles);
 }
 
-// (the launchers without a stream-K workspace: conv_slab / conv_pair / resblock_fused)
-int device_cus(int& cus) {
-  static std::mutex mu;
-  static int n[128] = {0};
-  int dev = 0;
-  SS_HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 128) return SS_ERR_ARG;
-  std::lock_guard<std::mutex> lk(mu);
-  if (n[dev] == 0) {
-    int v = 0;
-    SS_HIP_CHECK(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-    n[dev] = v > 0 ? v : 256;
-  }
-  cus = n[dev];
-  return SS_OK;
+// The 32x64 rung over `tiles` 32x64 tiles: no k-split from 768 tiles on (big batched problems: ~90 TFLOP/s)
+template <bool BLK>
+static int launch_32x64(const GemmArgs& a, hipStream_t stream, long tiles) {
+  if (a.Cin % 32 != 0) return launch_rung<BLK, 32, 64, 16, 2, 2, 4>(a, stream, PROF_GEMM_32x64x16, tiles);
+  if (tiles >= 768) return launch_rung<BLK, 32, 64, 32, 2, 2, 1>(a, stream, PROF_GEMM_32x64x32, tiles);
+  return launch_rung<BLK, 32, 64, 32, 2, 2, 4>(a, stream, PROF_GEMM_32x64x32, tiles);
 }
 
-// ---- eligibility prefixes of the slab kernels (gemm.hpp) ----
-bool slab_layout_ok(const GemmArgs& a) {
-  return a.same_rows && a.stride == 1 && a.chunk == 0 && !a.glu && !a.ln_g && a.lda == a.Cin && (a.ldc & 3) == 0 &&
-         (!a.R || (a.ldr & 3) == 0) && (!a.R2 || (a.ldr2 & 3) == 0) && (!a.C2 || (a.ldc2 & 3) == 0);
-}
-bool slab_conv_ok(const GemmArgs& a, int c) {
-  return slab_layout_ok(a) && !a.x3 && a.Cin == c && a.N == c &&
-         (a.in_act == ACT_NONE || (a.in_act == ACT_LRELU && a.in_slope > 0.f && a.in_slope < 1.f)) &&
-         (a.act == ACT_NONE || a.act == ACT_LRELU);
+// Shape-to-tile ladder of the LDS-tiled kernel, M rows in each of nseg segments.  BLK: the pack-invariant forms -- the rungs may
+// depend on M, because every BLK tile gives a row the same bits.
+// Tile choice (tools/conv_bench.py sweep on MI355X, profiles/r01_tile_sweep.txt): these problems are a few GFLOP at most, so what
+// matters is an even spread over 1024 SIMDs with several resident workgroups per CU -- small 32x32 tiles, plus intra-workgroup
+// split-K when even those are few.  (128x128 tiles lose to 32x64 even at batch scale: profiles/r01_tile_sweep_batch.txt)
+template <bool BLK>
+static int launch_tiles(const GemmArgs& a, hipStream_t stream, int M, int nseg) {
+  const bool k32 = (a.Cin % 32) == 0;
+  const long t128 = (long)cdiv(M, 128) * nseg;
+  if (a.N <= 16) return launch_rung<BLK, 128, 16, 16, 4, 1, 2>(a, stream, PROF_GEMM_128x16x16, t128);
+  if (a.N <= 32 && !a.glu)
+    return k32 ? launch_rung<BLK, 128, 32, 32, 4, 1, 2>(a, stream, PROF_GEMM_128x32x32, t128) : launch_rung<BLK, 128, 32, 16, 4, 1, 2>(a, stream, PROF_GEMM_128x32x16, t128);
+  if (M <= 16) return k32 ? launch_rung<BLK, 16, 128, 32, 1, 4, 1>(a, stream, PROF_GEMM_16x128x32, 0) : launch_rung<BLK, 16, 128, 16, 1, 4, 1>(a, stream, PROF_GEMM_16x128x16, 0);
+  const long t3264 = (long)cdiv(M, 32) * cdiv(a.N, 64) * nseg;
+  if (!k32 || a.glu || t3264 >= 768) return launch_32x64<BLK>(a, stream, t3264);
+  if constexpr (BLK) return launch_cfg<32, 32, 32, 2, 2, 1, 1, true>(a, stream, PROF_GEMM_32x32x32);
+  const long t3232 = (long)cdiv(M, 32) * cdiv(a.N, 32) * nseg;
+  const int nk = a.taps * (a.Cin / 32);
+  if (t3232 >= 700 || nk < 4) return launch_cfg<32, 32, 32, 2, 2, 1>(a, stream, PROF_GEMM_32x32x32);
+  if (t3232 >= 300 || nk < 8) return launch_cfg<32, 32, 32, 2, 2, 2>(a, stream, PROF_GEMM_32x32x32);
+  return launch_cfg<32, 32, 32, 2, 2, 4>(a, stream, PROF_GEMM_32x32x32);
 }
 
-int sk_workspace_error_count() {
-  std::lock_guard<std::mutex> lk(g_skw_mu);
-  int total = 0;
-  for (SkWorkspace* w : g_skw_live)
-    for (unsigned* sy : {w->sync1, w->sync2}) {
-      unsigned v = 0;
-      if (sy && hipMemcpy(&v, sy + 8, sizeof(v), hipMemcpyDeviceToHost) == hipSuccess) total += (int)v;
-    }
-  return total;
+// What both routes to the no-LDS kernel need of a launch: a plain linear layer with a bias / SiLU / ReLU / alpha / residual epilogue.
+// GLU (the conformer conv module's pointwise conv 1): only in its plain form -- no activation, scale or residual on top
+static bool plain_linear(const GemmArgs& a) {
+  const bool glu_ok = !a.glu || (a.N % 32 == 0 && a.act == ACT_NONE && a.alpha == 1.f && !a.R);
+  return a.taps == 1 && a.stride == 1 && a.pad == 0 && glu_ok && a.nseg == 0 && a.chunk == 0 && a.in_act == ACT_NONE && !a.R2 &&
+         !a.C2 && a.div == 0.f && (a.act == ACT_NONE || a.act == ACT_SILU || a.act == ACT_RELU) && a.Cin % 64 == 0 && (a.lda & 3) == 0;
 }
-
-void debug_force_tile(int bm, int bn, int ks) {
-  dispatch_edit([=](Dispatch& d) { d.force_bm = bm; d.force_bn = bn; d.force_ks = ks; d.sk_groups = (bm == 1 && bn == 8); });
-}
-bool debug_tile_forced() { return disp().force_bm != 0; }
-
-static thread_local int t_canon = CANON_NONE;
-CanonScope::CanonScope(int mode) : prev(t_canon) { t_canon = mode; }
-CanonScope::~CanonScope() { t_canon = prev; }
-int canon_mode() { return t_canon; }
-void canon_debug_set(int mode) { t_canon = mode; }
 
 // CANON_SMALLM: what the no-LDS kernel computes at all (smallm_eligible minus the tuning hooks)
 static bool smallm_shape_ok(const GemmArgs& a) {
-  const bool glu_ok = !a.glu || (a.N % 32 == 0 && a.act == ACT_NONE && a.alpha == 1.f && !a.R);
-  return a.taps == 1 && a.stride == 1 && a.pad == 0 && glu_ok && a.nseg == 0 && a.chunk == 0 && a.in_act == ACT_NONE && !a.R2 &&
-         !a.C2 && a.div == 0.f && !a.ln_out && (a.act == ACT_NONE || a.act == ACT_SILU || a.act == ACT_RELU) && a.M > 0 &&
-         a.M <= 1024 && a.Cin % 64 == 0 && (a.lda & 3) == 0 && (!a.ln_g || a.Cin <= 512);     // (rows = utterances of a lock-step pack: 16-row tiles are independent, any count gives a row the same bits)
+  return plain_linear(a) && !a.ln_out && a.M > 0 && a.M <= 1024 && (!a.ln_g || a.Cin <= 512);     // (rows = utterances of a lock-step pack: 16-row tiles are independent, any count gives a row the same bits)
 }
 
 // Pack-invariant routes (GemmArgs::canon): see gemm.hpp.  Nothing here may make the BITS depend on M; the choice among kernels
 // that give the same bits may.
 static int launch_canon(const GemmArgs& a, hipStream_t stream) {
   const int M = a.nseg > 0 ? a.max_seg_out : a.M;
-  const bool k32 = (a.Cin % 32) == 0;
   const int nseg = a.nseg > 0 ? a.nseg : 1;
   if (a.ln_out) return SS_ERR_ARG;
   if (a.canon == CANON_SMALLM) {
@@ -1066,7 +761,7 @@ static int launch_canon(const GemmArgs& a, hipStream_t stream) {
   // ---- CANON_SEQ: one accumulator chain per output element ----
   if (a.seg_mb || a.seg_A) {     // per-segment row starts / inputs: one tile form whatever the rows (a row's bits never depend on them)
     if (a.nseg <= 0 || a.ln_g) return SS_ERR_ARG;
-    return k32 ? launch_cfg<32, 64, 32, 2, 2, 1, 1, true>(a, stream, PROF_GEMM_32x64x32) : launch_cfg<32, 64, 16, 2, 2, 1, 1, true>(a, stream, PROF_GEMM_32x64x16);
+    return launch_32x64<true>(a, stream, 0);
   }
   if (rtlin_shape_ok(a) && (a.ln_g || rtlin_eligible(a))) return launch_rtlin(a, stream);
   if (a.ln_g) return SS_ERR_ARG;            // LayerNorm prologue: the row-tile kernel only (K = 256); callers normalise first otherwise
@@ -1074,31 +769,19 @@ static int launch_canon(const GemmArgs& a, hipStream_t stream) {
   // (rounds 4-5 sent big N % 128 == 0 shapes to conv_sk2 cut on whole tiles -- ONE chain over all of K; its 128 accumulator
   //  registers per wave leave no room for the second accumulator set the blocked chain needs, so CANON_SEQ no longer routes there)
   // LDS-tiled kernel, one k-group, blocked chain (BLK)
-  if (a.N <= 16) return launch_cfg<128, 16, 16, 4, 1, 1, 1, true>(a, stream, PROF_GEMM_128x16x16);
-  if (a.N <= 32 && !a.glu) return k32 ? launch_cfg<128, 32, 32, 4, 1, 1, 1, true>(a, stream, PROF_GEMM_128x32x32) : launch_cfg<128, 32, 16, 4, 1, 1, 1, true>(a, stream, PROF_GEMM_128x32x16);
-  if (M <= 16) return k32 ? launch_cfg<16, 128, 32, 1, 4, 1, 1, true>(a, stream, PROF_GEMM_16x128x32) : launch_cfg<16, 128, 16, 1, 4, 1, 1, true>(a, stream, PROF_GEMM_16x128x16);
-  const long t3264 = (long)cdiv(M, 32) * cdiv(a.N, 64) * nseg;
-  if (!k32) return launch_cfg<32, 64, 16, 2, 2, 1, 1, true>(a, stream, PROF_GEMM_32x64x16);
-  if (a.glu || t3264 >= 768) return launch_cfg<32, 64, 32, 2, 2, 1, 1, true>(a, stream, PROF_GEMM_32x64x32);
-  return launch_cfg<32, 32, 32, 2, 2, 1, 1, true>(a, stream, PROF_GEMM_32x32x32);
+  return launch_tiles<true>(a, stream, M, nseg);
 }
 
 bool smallm_eligible(const GemmArgs& a) {
   if (disp().force_bm > 1) return false;
   const int M = a.nseg > 0 ? a.max_seg_out : a.M;
-  // GLU (the conformer conv module's pointwise conv 1): only in its plain form -- no activation, scale or residual on top
-  const bool glu_ok = !a.glu || (a.N % 32 == 0 && a.act == ACT_NONE && a.alpha == 1.f && !a.R);
-  const bool plain_linear = a.taps == 1 && a.stride == 1 && a.pad == 0 && glu_ok && a.nseg == 0 && a.chunk == 0 &&
-                            a.in_act == ACT_NONE && !a.R2 && !a.C2 && a.div == 0.f &&
-                            (a.act == ACT_NONE || a.act == ACT_SILU || a.act == ACT_RELU);
-  // row limit of the no-LDS kernel: every 16-row tile re-streams its W columns from L2, so it only pays while the whole
-  // problem is latency-bound (SS_SMALLM_MAX_ROWS: tuning knob, tools/latency_breakdown.py)
+  // row limit of the no-LDS kernel (Dispatch::smallm_max_rows, SS_SMALLM_MAX_ROWS: tuning knob, tools/latency_breakdown.py): every
+  // 16-row tile re-streams its W columns from L2, so it only pays while the whole problem is latency-bound
   // 192: a single utterance of 5-7.7 s (T' = 129..192 encoder rows, a third of the CVSS-C length distribution) keeps its 12 x 9
   // linears on this kernel instead of the 32x32-tile kernel, whose k-loop is one global-load round trip per k-step when a
   // launch is this small: 6.43 -> 6.26 ms per utterance at T' = 131 (tools/b1_profile.py); beyond ~200 rows the re-streaming
   // costs what the tiles' latency did (8.24 vs 8.18 ms at T' = 201 with 256), and the 500-row unit decoder loses 2x.
-  static const int max_rows = getenv("SS_SMALLM_MAX_ROWS") ? atoi(getenv("SS_SMALLM_MAX_ROWS")) : 192;
-  return plain_linear && M <= max_rows && M > 0 && a.Cin % 64 == 0 && (a.lda & 3) == 0;
+  return plain_linear(a) && M <= disp().smallm_max_rows && M > 0;
 }
 
 
@@ -1111,14 +794,12 @@ int launch_conv_gemm(const GemmArgs& a_in, hipStream_t stream) {
   if (a.glu && (a.N % 32 != 0 || a.C2)) return SS_ERR_ARG;
   const bool k32 = (a.Cin % 32) == 0;
   const int nseg = a.nseg > 0 ? a.nseg : 1;
-  if (a.canon == CANON_NONE) a.canon = t_canon;
+  if (a.canon == CANON_NONE) a.canon = canon_mode();
   if (a.canon != CANON_NONE && !disp().force_bm) { a.m_begin = 0; return launch_canon(a, stream); }
   if (a.seg_mb || a.seg_A) return SS_ERR_ARG;      // the CANON_SEQ tile form only
   if (a.m_begin > 0) {       // a row range of a strided conv (ss_encoder_stream_forward): only the LDS-tile kernel starts anywhere but row 0
     if (a.nseg > 0 || a.m_begin >= a.M || a.ln_g || a.ln_out || a.N <= 32) return SS_ERR_ARG;
-    const long t = (long)cdiv(a.M - a.m_begin, 32) * cdiv(a.N, 64);
-    if (k32 && t >= 768) return launch_cfg<32, 64, 32, 2, 2, 1>(a, stream, PROF_GEMM_32x64x32);
-    return k32 ? launch_cfg_ks<32, 64, 32, 2, 2, 4>(a, stream, PROF_GEMM_32x64x32, t) : launch_cfg_ks<32, 64, 16, 2, 2, 4>(a, stream, PROF_GEMM_32x64x16, t);
+    return launch_32x64<false>(a, stream, (long)cdiv(a.M - a.m_begin, 32) * cdiv(a.N, 64));    // (that rung whatever the shape: routing as it was)
   }
   // a forced tile (tuning hook) keeps M <= 4 launches off the GEMV -- except when the caller asked for ln_out, which only the GEMV writes
   if ((!disp().force_bm || a.ln_out) && gemv_eligible(a)) return launch_gemv(a, stream);
@@ -1150,10 +831,8 @@ int launch_conv_gemm(const GemmArgs& a_in, hipStream_t stream) {
     const long long nk = (long long)a.taps * (a.Cin / 32);
     const bool wide = a.N % 128 == 0;
     const long long units = (long long)cdiv(a.M, 128) * (a.N / (wide ? 128 : 64)) * nk;
-    static const long long min_units = getenv("SS_SK_MIN_UNITS") ? atoll(getenv("SS_SK_MIN_UNITS")) : 12 * 512;   // tuning knob
-    static const bool no_sk2 = getenv("SS_NO_SK2") && atoi(getenv("SS_NO_SK2"));   // A/B knob: first-generation kernel only
-    static const int sk2_min_k64 = getenv("SS_SK2_MINK64") ? atoi(getenv("SS_SK2_MINK64")) : 192;   // N % 128 == 64: smallest taps * Cin for conv_sk2<64>
-    if (!no_sk2 && conv_sk2_eligible(a) && (wide ? units >= min_units : a.taps * a.Cin >= sk2_min_k64)) return launch_conv_sk2(a, stream);
+    const long long min_units = disp().sk_min_units;   // (SS_SK_MIN_UNITS; SS_NO_SK2: first-generation kernel only; SS_SK2_MINK64: smallest taps * Cin for conv_sk2<64>)
+    if (!disp().no_sk2 && conv_sk2_eligible(a) && (wide ? units >= min_units : a.taps * a.Cin >= disp().sk2_min_k64)) return launch_conv_sk2(a, stream);
     if (wide ? units >= min_units : a.taps * a.Cin >= 448) return launch_conv_sk(a, stream);
   }
   if (disp().force_bm && a.N > 32 && k32) {   // tuning hook (tools/conv_bench.py): ks = KS*10 + PD
@@ -1174,29 +853,7 @@ int launch_conv_gemm(const GemmArgs& a_in, hipStream_t stream) {
   }
   // narrow vocoder stages: weights + input slab in LDS, one HBM pass (conv_slab.hip)
   if (disp().force_bm != 2 && conv_slab_eligible(a) && a.M >= 2048) return launch_conv_slab(a, stream);
-  if (a.N <= 16) return launch_cfg_ks<128, 16, 16, 4, 1, 2>(a, stream, PROF_GEMM_128x16x16, (long)cdiv(M, 128) * nseg);
-  if (a.N <= 32 && !a.glu) {
-    const long tl = (long)cdiv(M, 128) * nseg;
-    return k32 ? launch_cfg_ks<128, 32, 32, 4, 1, 2>(a, stream, PROF_GEMM_128x32x32, tl) : launch_cfg_ks<128, 32, 16, 4, 1, 2>(a, stream, PROF_GEMM_128x32x16, tl);
-  }
-  if (M <= 16) {
-    return k32 ? launch_cfg<16, 128, 32, 1, 4>(a, stream, PROF_GEMM_16x128x32) : launch_cfg<16, 128, 16, 1, 4>(a, stream, PROF_GEMM_16x128x16);
-  }
-  // Tile choice (tools/conv_bench.py sweep on MI355X, profiles/r01_tile_sweep.txt): these problems are
-  // a few GFLOP at most, so what matters is an even spread over 1024 SIMDs with several resident
-  // workgroups per CU -- small 32x32 tiles, plus intra-workgroup split-K when even those are few.
-  const long t128 = (long)cdiv(M, 128) * cdiv(a.N, 128) * nseg;
-  const long t3232 = (long)cdiv(M, 32) * cdiv(a.N, 32) * nseg;
-  const long t3264 = (long)cdiv(M, 32) * cdiv(a.N, 64) * nseg;
-  (void)t128;   // 128x128 tiles lose to 32x64 even at batch scale (profiles/r01_tile_sweep_batch.txt)
-  if (k32 && t3264 >= 768) return launch_cfg<32, 64, 32, 2, 2, 1>(a, stream, PROF_GEMM_32x64x32);   // big (batched) problems: ~90 TFLOP/s
-  if (!k32 || a.glu) {
-    return k32 ? launch_cfg_ks<32, 64, 32, 2, 2, 4>(a, stream, PROF_GEMM_32x64x32, t3264) : launch_cfg_ks<32, 64, 16, 2, 2, 4>(a, stream, PROF_GEMM_32x64x16, t3264);
-  }
-  const int nk = a.taps * (a.Cin / 32);
-  if (t3232 >= 700 || nk < 4) return launch_cfg<32, 32, 32, 2, 2, 1>(a, stream, PROF_GEMM_32x32x32);
-  if (t3232 >= 300 || nk < 8) return launch_cfg<32, 32, 32, 2, 2, 2>(a, stream, PROF_GEMM_32x32x32);
-  return launch_cfg<32, 32, 32, 2, 2, 4>(a, stream, PROF_GEMM_32x32x32);
+  return launch_tiles<false>(a, stream, M, nseg);
 }
 
 }  // namespace ss

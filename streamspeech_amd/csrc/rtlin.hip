@@ -472,8 +472,7 @@ int launch_rtlin(const GemmArgs& a, hipStream_t stream) {
   // 134 registers and 49 KB of LDS per workgroup: up to three are resident per CU (waves of different workgroups share a SIMD, one's
   // tile prologue / unit epilogues run under the other's MFMAs); units are independent, so any grid gives the same bits
   // (measured: one per CU unless a workgroup would hold >= 64 units -- the vocabulary heads -- where three per CU gain 3-9 %)
-  static const int per_cu_env = getenv("SS_RTLIN_WG_PER_CU") ? atoi(getenv("SS_RTLIN_WG_PER_CU")) : 0;
-  const int per_cu = min(a.glu ? 2 : 3, per_cu_env > 0 ? per_cu_env : (U >= 64LL * cus ? 3 : 1));
+  const int per_cu = min(a.glu ? 2 : 3, disp().rt_wg_per_cu > 0 ? disp().rt_wg_per_cu : (U >= 64LL * cus ? 3 : 1));
   long long G = disp().rt_force_g > 0 ? disp().rt_force_g : (long long)cus * per_cu;      // at least 4 units (one per wave) each
   if (disp().rt_force_g <= 0 && G > U / 4) G = U / 4;
   if (G > U) G = U;

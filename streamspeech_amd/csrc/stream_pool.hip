@@ -206,7 +206,7 @@ struct ss_stream_pool {
   bool recorded = false;
 };
 
-// GEMM-family launches of the process so far (the launchers' own census, gemm.hip prof_begin): one per kernel actually launched
+// GEMM-family launches of the process so far (the launchers' own census, prof.hip prof_begin): one per kernel actually launched
 static long long gemm_census() {
   long long t = 0;
   for (int c = 0; c < kNumTileCfg; ++c) { long long n = 0; prof_totals(c, nullptr, nullptr, &n); t += n; }

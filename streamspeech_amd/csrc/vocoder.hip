@@ -377,11 +377,11 @@ static int hifigan_stack(const ss_vocoder* v, hipStream_t s, ConvFn&& conv, Stag
       // TFLOP/s in the pipeline; at k = 3 / 7 the fused launch wins (92-98 vs 56-93: the separate convs are HBM-bound there)
       // (round 5: from k = 7 -- a 7-tap conv is 10 instead of 12 MFMA k-blocks per pair since the one-tap tail group: 6243 vs 6200 x RT,
       //  k >= 3: 6221; tools/jobs/r05_m.sh)
-      static const int c32_min_k = getenv("SS_CONV_C32_MIN_K") ? atoi(getenv("SS_CONV_C32_MIN_K")) : 7;
+      // (Dispatch::c32_min_k = 7, SS_CONV_C32_MIN_K)
       // conv_c16.hip: the same split at 16 channels (weight matrix in registers): +0.5 %; the round-1 slab kernel (weights in LDS) conv by
       // conv measures -0.3 % against the fused launch, profiles/r04_c16_bench.txt + tools/jobs/r04_o.sh / r04_p.sh
-      static const int c16_min_k = getenv("SS_CONV_C16_MIN_K") ? atoi(getenv("SS_CONV_C16_MIN_K")) : 11;
-      const bool per_conv = (c32 && C == 32 && kr >= c32_min_k) || (c16 && C == 16 && kr >= c16_min_k);
+      // (Dispatch::c16_min_k = 11, SS_CONV_C16_MIN_K)
+      const bool per_conv = (c32 && C == 32 && kr >= disp().c32_min_k) || (c16 && C == 16 && kr >= disp().c16_min_k);
       if (!pa && !per_conv && !disp().no_resblock_fusion && resblock_fused_eligible(C, kr, c.resblock_dilations[j], C, C, gnseg, gM)) {
         const float *W1[3], *B1[3], *W2[3], *B2[3];
         for (int dd = 0; dd < 3; ++dd) {

@@ -622,3 +622,35 @@ def test_canon_seq_tile(lib, case):
     ragged = {k: v for k, v in kw.items() if k not in ("M", "in_len")}
     launch(lib, cls, f"{case} ragged {lens}", w, seed=601, canon=1, segs=segs, **ragged)
     w.done()
+
+
+# =====================================================================================================
+# a row limit set in the environment reaches the dispatcher through the Dispatch store (dispatch.hip: env_defaults -> disp())
+# =====================================================================================================
+def smallm_max_rows_child():
+    """What the child process of the test below runs, SS_SMALLM_MAX_ROWS=16 in its environment (launch() asserts rc, the census, the
+    float64 bound and the untouched elements)."""
+    from streamspeech_amd import lib as L
+    lib, w = L.load(), Worst("SS_SMALLM_MAX_ROWS=16")
+    launch(lib, SMALLM[4, 1], "(16, 48, 64) at the limit", w, M=16, N=48, Cin=64, entry="lin", seed=700)
+    before = census(lib)
+    launch(lib, "conv_gemm<32,32,32,2,2>", "(17, 48, 64) one row past it", w, M=17, N=48, Cin=64, entry="lin", seed=701)
+    assert not any(c in SMALLM.values() for c in took_since(lib, before))
+    print("CHILD OK")
+
+
+def test_smallm_row_limit_from_the_environment():
+    """SS_SMALLM_MAX_ROWS is read once, into Dispatch::smallm_max_rows, and smallm_eligible reads it from there.  In a fresh process
+    with the limit at 16 (default 192), a (16, 48, 64) linear is one launch of smallm_gemm<4,1> (5 <= M: not the GEMV; 1 x 3 workgroups
+    <= 1024) and a (17, 48, 64) one goes down the tile ladder: N > 32, M > 16, K % 32 == 0, 1 x 1 32x64 tiles < 768, no GLU -> the
+    32x32x32 rung at KS = 1 (nk = 2 < 4); nothing under any small-M class.  Both within TOL of tests/gemm_ref.py."""
+    import subprocess
+    import sys
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = f"import sys; sys.path[:0] = [{os.path.dirname(here)!r}, {here!r}]; import test_gemm_routes_gpu as t; t.smallm_max_rows_child()"
+    r = subprocess.run(["timeout", "-k", "10", "120", sys.executable, "-c", code], env=dict(os.environ, SS_SMALLM_MAX_ROWS="16"),
+                       capture_output=True, text=True)
+    print(r.stdout[-2000:], r.stderr[-2000:])
+    assert r.returncode == 0 and "CHILD OK" in r.stdout, f"child exit {r.returncode}"
