@@ -731,6 +731,13 @@ int ss_vocoder_forward_spkr(ss_vocoder* v, void* stream, const int32_t* d_codes,
  * B independent utterances packed along the row axis (no padding; each keeps the B = 1 arithmetic
  * of the entry points above -- SURVEY.md H2b).  h_* arrays are host arrays of length B; packed
  * device buffers are the concatenation of the per-utterance arrays in batch order. */
+/* ss_fbank_cmvn over a pack: utterance b is the h_n_samples[b] samples at d_pcm + h_pcm_start[b]; its h_T[b] =
+ * ss_fbank_num_frames(h_n_samples[b]) rows follow those of utterance b - 1 in d_feat (an utterance of fewer than 400 samples has
+ * none), each the same bits as ss_fbank_cmvn on that utterance alone.  Any B >= 1: the segment table is launched in slices of at
+ * most 65535 utterances (the grid's y extent), so a pack past that is several launches on the stream, not a refusal.
+ * SS_ERR_ARG, decided for the whole call before anything is launched or written (h_T included): B < 1; a null d_pcm, d_feat,
+ * h_pcm_start, h_n_samples or h_T; a negative h_n_samples[b] or h_pcm_start[b]; an h_pcm_start[b] or a total row count past
+ * 2^31 - 1 (the kernel's segment fields are ints). */
 int ss_batch_fbank_cmvn(ss_model* m, void* stream, int B, const float* d_pcm, const int64_t* h_pcm_start,
                         const int32_t* h_n_samples, float pcm_scale, float* d_feat, int32_t* h_T);
 /* Precomputed fbank rows (the recipe's src_fbank80.zip): d_out[r][c] = (d_in[r][c] - mean[c]) / std[c] over `rows` packed rows of 80

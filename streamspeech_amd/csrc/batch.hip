@@ -12,20 +12,40 @@
 // =================================================================================================
 extern "C" int ss_batch_fbank_cmvn(ss_model* m, void* stream, int B, const float* d_pcm, const int64_t* h_pcm_start,
                                    const int32_t* h_n_samples, float pcm_scale, float* d_feat, int32_t* h_T) {
-  if (!m || B <= 0) return SS_ERR_ARG;
+  if (!m || B <= 0 || !d_pcm || !d_feat || !h_pcm_start || !h_n_samples || !h_T) return SS_ERR_ARG;
+  // every refusal first, for the whole call: nothing is written (h_T included) and nothing launched on one.  The kernel's segment
+  // fields {pcm_start, n_frames, frame_start} are ints: a start and the pack's row count must fit them.
+  int64_t rows = 0;
+  for (int b = 0; b < B; ++b) {
+    if (h_n_samples[b] < 0 || h_pcm_start[b] < 0 || h_pcm_start[b] > (int64_t)0x7fffffff) return SS_ERR_ARG;
+    rows += ss_fbank_num_frames(h_n_samples[b]);
+  }
+  if (rows > (int64_t)0x7fffffff) return SS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  std::vector<int> segs(3 * B);
-  int row = 0, mx = 0;
+  std::vector<int> segs(3 * (size_t)B);
+  int row = 0;
   for (int b = 0; b < B; ++b) {
     const int T = ss_fbank_num_frames(h_n_samples[b]);
     h_T[b] = T;
-    segs[3 * b] = (int)h_pcm_start[b]; segs[3 * b + 1] = T; segs[3 * b + 2] = row;
-    row += T; mx = std::max(mx, T);
+    segs[3 * (size_t)b] = (int)h_pcm_start[b]; segs[3 * (size_t)b + 1] = T; segs[3 * (size_t)b + 2] = row;
+    row += T;
   }
+  if (row == 0) return SS_OK;
   RET(m->sc->seg_buf.ensure(segs.size() * sizeof(int)));
+  const int* dt = (const int*)m->sc->seg_buf.p;
   RET(upload(s, (int*)m->sc->seg_buf.p, segs));
-  return launch_fbank_cmvn_batch(d_pcm, pcm_scale, m->fe_window, m->fe_melw, m->fe_mean, m->fe_std, d_feat,
-                                 (const int*)m->sc->seg_buf.p, B, mx, s);
+  // B is the grid's y extent (at most 65535): the table goes out in slices of that many segments, each with its own longest
+  // utterance as the x extent.  A segment's fields are offsets into the whole pack, so a slice is the same kernel on a later part
+  // of the one uploaded table.
+  constexpr int kSlice = 65535;
+  for (int b0 = 0; b0 < B; b0 += kSlice) {
+    const int nb = std::min(kSlice, B - b0);
+    int mx = 0;
+    for (int b = b0; b < b0 + nb; ++b) mx = std::max(mx, segs[3 * (size_t)b + 1]);
+    RET(launch_fbank_cmvn_batch(d_pcm, pcm_scale, m->fe_window, m->fe_melw, m->fe_mean, m->fe_std, d_feat, dt + 3 * (size_t)b0, nb,
+                                mx, s));
+  }
+  return SS_OK;
 }
 
 extern "C" int ss_batch_cmvn(ss_model* m, void* stream, const float* d_in, int64_t rows, float* d_out) {
