@@ -11,7 +11,8 @@
  * (ss_mp3_*, ss_flac_*), 8 SS_ERR_STREAM_REPEAT (ss_encoder_stream_forward).
  * Additions since ABI 2 was cut (no existing signature changed): ss_flac_streaminfo, ss_flac_probe, ss_flac_unpack,
  * ss_flac_restore_host, ss_flac_restore (FLAC ingest), ss_batch_cmvn (precomputed fbank rows), ss_batch_mt_attention and
- * ss_op_attention_probs (cross-attention of the first-pass text decoder).
+ * ss_op_attention_probs (cross-attention of the first-pass text decoder), ss_batch_unit_spans, ss_unit_spans_host and
+ * ss_op_unit_spans (where each text-decoder state is spoken in the output speech).
  *
  * Weight ownership: the caller owns one packed FP32 weight blob in HBM (built once from a fairseq
  * state dict by streamspeech_amd/weights.py) and lends it to ss_model_create(); the library keeps
@@ -980,6 +981,35 @@ int ss_batch_vocoder_tail_spkr(ss_vocoder* v, void* stream, int B, const int32_t
                                int32_t* h_win_first, int32_t* h_dur, int64_t* h_out_start, int64_t* h_n_out,
                                const int32_t* h_spkr /* [B] */);
 
+/* ---- Unit spans (csrc/unit_spans.hip): where each text-decoder state is spoken in the output speech.  The unit decoder upsamples
+ * every state into ctc_upsample positions, so each raw unit arg-max belongs to one state, the duration predictor gives every unit a
+ * whole number of 20-ms frames and the vocoder writes 320 samples per frame: the mapping is exact integers.  For one row of n states,
+ * raw[0 .. up n) its arg-max ids (f counts from the row's start):
+ *   unit(f)   raw[f] is none of {blank, pad, bos (0), eos} and f == 0 or raw[f] != raw[f - 1] -- exactly what the CTC collapse of
+ *             ss_batch_t2u_units plus the callers' dictionary walk keep; its ordinal = the units before it, K = all of them;
+ *   it belongs to state f / up (a run that crosses a state boundary: to the earlier state);
+ *   d0 <= u0 <= K: dur[j - d0] = the frames of unit ordinal j >= d0 (d0: the first unit the vocoder call synthesised), u0 = the first
+ *             NEW unit (the streaming tail emits the units from K - n_new on; offline d0 = u0 = 0).
+ * Per state s, over the new units (ordinal >= u0) only: {first_unit = u0 + the new units of states < s, n_units, start_frame = the sum of
+ * dur over the new units of states < s, n_frames = the sum over its own}: four int32.  The spans tile the emitted speech: the last
+ * start_frame + n_frames, times 320, is the number of samples the vocoder call returned for the row.
+ * ss_batch_unit_spans: B rows; d_raw as ss_batch_t2u_units[_pad] leaves it (row b at ctc_upsample x the prefix sum of h_n); the
+ * durations either on the device (d_dur, as ss_vocoder_forward / ss_batch_vocoder_forward leave them: packed [sum h_K], d0 = 0 there) or
+ * on the host (h_dur, as ss_batch_vocoder_tail returns them) -- exactly one of the two non-NULL; in both, row b lies at the prefix sum of
+ * h_K and holds h_K[b] - h_dur_first[b] values.  up / blank / pad / eos are the model's.  One upload (row table and host durations
+ * together), one launch (one workgroup per row, any number of states), one download: h_spans [sum h_n][4], h_K_out [B] = the units the
+ * kernel counted in each row.  A row whose h_K_out[b] differs from h_K[b] was given the wrong count: its spans are not to be used (no
+ * duration at or past h_K[b] is read); the other rows are unaffected.  Synchronises.  SS_ERR_ARG, decided for the whole call with nothing
+ * launched or written: B < 1; a null pointer; both or neither duration pointer; an h_n[b] < 1; a negative h_K / h_dur_first;
+ * h_dur_first[b] > h_unit0[b]; h_unit0[b] > h_K[b]; a pack of 2^31 positions or units. */
+int ss_batch_unit_spans(ss_model* m, void* stream, int B, const int32_t* d_raw, const int32_t* h_n, const int32_t* h_K,
+                        const int32_t* h_dur_first, const int32_t* h_unit0, const int32_t* d_dur, const int32_t* h_dur,
+                        int32_t* h_spans, int32_t* h_K_out);
+/* The plain-C++ twin of the kernel on host arrays, explicit ids: the same definitions and refusals (also: up < 1), no HIP. */
+int ss_unit_spans_host(int B, const int32_t* h_raw, const int32_t* h_n, const int32_t* h_K, const int32_t* h_dur_first,
+                       const int32_t* h_unit0, const int32_t* h_dur, int up, int blank, int pad, int bos, int eos, int32_t* h_spans,
+                       int32_t* h_K_out);
+
 /* ---- profiling hooks for bench.py's roofline leg: bracket every conv-GEMM launch whose tile
  * configuration is in cls_mask with HIP events recorded on the launch stream.  ss_prof_read
  * synchronises on the recorded events and returns the summed kernel time, the summed algorithmic
@@ -1256,6 +1286,12 @@ int ss_op_ctc_collapse_spans(void* stream, const int32_t* raw, const float* lpro
 int ss_op_ctc_align(void* stream, const float* d_logits, int ld, int V, int pad, int B, const int32_t* h_T, const int32_t* h_targets,
                     const int32_t* h_n_targets, ss_ctc_align_result* d_results, int32_t* d_path, int32_t* d_first, int32_t* d_last,
                     float* d_tok_lprob, float* d_frame_lprob);
+/* The kernel of ss_batch_unit_spans on the caller's device arrays with explicit ids: arguments, definitions and refusals as
+ * ss_unit_spans_host, d_raw / d_dur / d_spans (16-byte aligned) / d_K_out on the device, the row table uploaded on the stream.
+ * Stream-ordered.  tests/test_unit_spans_gpu.py against tests/spans_ref.py. */
+int ss_op_unit_spans(void* stream, int B, const int32_t* d_raw, const int32_t* h_n, const int32_t* h_K, const int32_t* h_dur_first,
+                     const int32_t* h_unit0, const int32_t* d_dur, int up, int blank, int pad, int bos, int eos, int32_t* d_spans,
+                     int32_t* d_K_out);
 int ss_op_dur_predict(void* stream, const float* logdur, const int32_t* forced, int K, int32_t* dur, int32_t* cum,
                       const int32_t* segs, int nseg);                 /* segs {start, len}: cum of segment s at start + s */
 int ss_op_repeat_rows(void* stream, const float* emb, const int32_t* cum, int K, int D, float* out, int F, const int32_t* segs,

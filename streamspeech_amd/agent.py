@@ -58,24 +58,30 @@ def speaker_id_arg(args, vocoder, flag="--speaker-id"):
     return int(spk)
 
 
-def synthesize_tail(vocoder, unit, n_new, dur_prediction, ctx=0, rf=None, spkr=None):
+def synthesize_tail(vocoder, unit, n_new, dur_prediction, ctx=0, rf=None, spkr=None, info=None):
     """Speech of the last ``n_new`` units of ``unit`` (agent :743-753: vocoder over all units, keep
     ``wav[-dur[-n_new:].sum()*320:]``).  With ``ctx`` > 0 only the last ``n_new + ctx`` units are
     synthesised: identical tail, because the frames further left than the
     generator's receptive field ``rf`` cannot reach it.  ``spkr``: the speaker id a multi-speaker vocoder synthesises with, passed
-    as ``x["spkr"]`` on both calls.  Returns (tail, wav of what was synthesised)."""
+    as ``x["spkr"]`` on both calls.  Returns (tail, wav of what was synthesised).  ``info``: a dict that receives ``first`` (the
+    first unit synthesised) and ``dur`` (the durations [1, K - first] of the synthesised units) of the call whose tail is kept."""
     wav = dur = None
+    first = 0
     extra = {} if spkr is None else {"spkr": torch.tensor([[int(spkr)]], dtype=torch.long)}
     if ctx > 0 and len(unit) > n_new + ctx:
         x = {"code": torch.tensor(unit[-(n_new + ctx):], dtype=torch.long).view(1, -1), **extra}
         wav, dur = vocoder(x, dur_prediction)
         # frames left of the new units whose durations are exact (the 2 left-most context units see a
         # truncated duration-predictor window) must cover the generator's receptive field
+        first = len(unit) - (n_new + ctx)
         if int(dur[:, 2:ctx].sum()) < rf + 2:
             wav = None
     if wav is None:
+        first = 0
         x = {"code": torch.tensor(unit, dtype=torch.long).view(1, -1), **extra}
         wav, dur = vocoder(x, dur_prediction)
+    if info is not None:
+        info["first"], info["dur"] = first, dur
     return wav[-int(dur[:, -n_new:].sum()) * 320:], wav
 
 
@@ -149,6 +155,29 @@ def mt_alignment_update(agent, enc, tokens, t0_ms=0):
                                      eos=agent.generator_mt.eos)
         rec.append((len(tokens), words))
     agent.alignment = [w for _, ws in rec for w in ws]
+
+
+def spoken_update(agent, raw, n_states, n_units, n_new, first, dur, tokens, carried, emitted):
+    """--spoken-words: one write of policy() adds its segments.  `raw` = the device arg-max ids of the write's unit pass over its
+    n_states decoder states, n_units all units so far of which the last n_new are new, `first` / `dur` the first unit the tail call
+    synthesised and the durations from there on, `tokens` all committed target tokens (no </s>), `carried` the samples of an
+    unfinished_wav prepended to this write (emitted here, no state's), `emitted` the samples the write returns.  ONE
+    batch_unit_spans call; the clock at the write's start is the samples emitted before it, divided by 16.  agent.spoken then
+    answers the words of all committed tokens in the emitted speech (words.Spoken), formed when it is asked."""
+    from .words import segments_from_spans
+    rec = agent._spoken_rec
+    if rec is None:                       # the utterance's first write: the previous utterance's words go now
+        rec = agent._spoken_rec = {"segments": [], "samples": 0, "seen": 0}
+    clock = rec["samples"] // 16
+    if carried:
+        rec["segments"].append((-1, clock, clock + int(carried) // 16, 0))
+        clock += int(carried) // 16
+    spans = agent.engine.batch_unit_spans(raw, [int(n_states)], [int(n_units)], [dur], [int(first)], [int(n_units) - int(n_new)])[0]
+    rec["segments"].extend(segments_from_spans(spans, clock, rec["seen"]))
+    rec["seen"] = max(rec["seen"], int(n_states))
+    rec["samples"] += int(emitted)
+    agent._spoken_last = ([int(t) for t in tokens], rec["segments"])
+    agent._spoken_words = None
 
 
 @entrypoint
@@ -280,14 +309,34 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
                "which the S2TT agent prints and the S2ST path speaks) with the source time span the decoder's cross-attention "
                "points at (streamspeech_amd/words.py AlignedWord); one extra decoder pass per write; default: off, every launch "
                "and every output as without the flag")
+        a("--spoken-words", action="store_true", default=False,
+          help="after every policy() that wrote, agent.spoken holds the words of all committed target tokens with the time span "
+               "each is spoken at in the OUTPUT speech, in ms on the clock of the emitted samples (streamspeech_amd/words.py "
+               "Spoken); exact, from the unit decoder's arg-max and the predicted durations; one small extra launch per write; "
+               "default: off, every launch and every output as without the flag")
         a("--extra-output-dir", type=str, default=None, help="extra output dir")
         a("--output-asr-translation", type=bool, default=False, help="extra output dir")
 
     details = None      # --word-details: the words.CtcDetails of the last policy() that ran the encoder
     alignment = None    # --mt-alignment: the words.AlignedWord list of all committed target tokens, after the last policy() that wrote
+    _spoken_last = None     # --spoken-words: (committed tokens, segments) as of the last write; the segments are kept by state index
+    _spoken_words = None
+
+    @property
+    def spoken(self):
+        """--spoken-words: the words.Spoken of all committed target tokens in the emitted speech as of the last policy() that
+        wrote (None before the first); a finished utterance's words stay until the next utterance's first write."""
+        if self._spoken_last is None:
+            return None
+        if self._spoken_words is None:
+            from .words import spoken_from_segments
+            self._spoken_words = spoken_from_segments(self._spoken_last[0], self._spoken_last[1], self.generator_mt.tgt_dict,
+                                                      eos=self.generator_mt.eos)
+        return self._spoken_words
 
     def reset(self):
         self._mt_align = []     # --mt-alignment: (committed tokens placed so far, the words of one write), frozen
+        self._spoken_rec = None  # --spoken-words: segments, samples emitted and states seen of the utterance (made by its first write)
         self.src_seg_num = 0
         self.tgt_subwords_indices = None
         self.src_ctc_indices = None
@@ -488,7 +537,9 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
             mt_alignment_update(self, self.encoder_outs[0]["encoder_out"][0], tmp)
 
         # 2+3. T2U encoder + CTC unit decoder + CTC search (agent :661-689)
-        finalized = self.ctc_generator.generate(mt_feats, prefix=self.tgt_units_indices, n_tail_pad=n_tail_pad)
+        sw = bool(getattr(self.args, "spoken_words", False))
+        finalized = self.ctc_generator.generate(mt_feats, prefix=self.tgt_units_indices, n_tail_pad=n_tail_pad,
+                                                **({"keep_raw": True} if sw else {}))
         if len(finalized[0][0]["tokens"]) == 0:
             if not self.states.source_finished:
                 return ReadAction()
@@ -511,10 +562,17 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
             return self._finish_empty()
 
         # 4. vocoder over ALL units so far; emit the tail that belongs to the new units (agent :743-753)
+        tail_info = {} if sw else None
         new_wav, wav = synthesize_tail(self.vocoder, unit, len(cur_unit), self.dur_prediction, self.vocoder_ctx,
-                                       self.vocoder_rf, **({} if self.speaker_id is None else {"spkr": self.speaker_id}))
+                                       self.vocoder_rf, **({} if self.speaker_id is None else {"spkr": self.speaker_id}),
+                                       **({"info": tail_info} if sw else {}))
+        carried = 0
         if self.unfinished_wav is not None and len(self.unfinished_wav) > 0:
+            carried = len(self.unfinished_wav)
             new_wav = torch.cat((self.unfinished_wav, new_wav), dim=0)
+        if sw:
+            spoken_update(self, finalized[0][0]["raw_device"], mt_feats.shape[0], len(unit), len(cur_unit), tail_info["first"],
+                          tail_info["dur"].view(-1).tolist(), tmp.tolist(), carried, len(new_wav))
         self.wav = wav
         self.unit = unit
 

@@ -408,9 +408,10 @@ class BatchMixin:
         return out
 
     def batch_t2u_units(self, feats: torch.Tensor, n_rows: List[int], t2u_causal=False, mask_eos=False,
-                        return_raw: bool = False):
+                        return_raw: bool = False, keep_raw: bool = False):
         """feats [B, rows, D] (rows of utterance b used: n_rows[b]) -> list of collapsed unit-vocab token lists
-        (with return_raw: (collapsed lists, raw per-position argmax lists))."""
+        (with return_raw: (collapsed lists, raw per-position argmax lists)).  keep_raw: the packed DEVICE arg-max ids (int32
+        [ctc_upsample * sum n_rows], what :meth:`batch_unit_spans` reads) follow as one more element of the answer."""
         B, rows = feats.shape[0], feats.shape[1]
         up = self.cfg.ctc_upsample
         U = sum(n_rows) * up
@@ -425,12 +426,15 @@ class BatchMixin:
             out.append(host[U + off: U + off + k].tolist())
             raws.append(host[off: off + n_rows[b] * up].tolist())
             off += n_rows[b] * up
+        if keep_raw:
+            return (out, raws, raw) if return_raw else (out, raw)
         return (out, raws) if return_raw else out
 
     def batch_t2u_units_pad(self, feats: torch.Tensor, n_rows: List[int], n_tail_pad: List[int], t2u_causal=False, mask_eos=False,
-                            return_raw: bool = False):
+                            return_raw: bool = False, keep_raw: bool = False):
         """:meth:`batch_t2u_units` with trailing <pad> states (ss_batch_t2u_units_pad): the last n_tail_pad[b] of row b's n_rows[b]
-        states are masked as keys, as :meth:`HipModel.t2u_units` (..., n_tail_pad) masks them; they are still decoded."""
+        states are masked as keys, as :meth:`HipModel.t2u_units` (..., n_tail_pad) masks them; they are still decoded.  keep_raw as
+        there."""
         B, rows = feats.shape[0], feats.shape[1]
         if len(n_rows) != B or len(n_tail_pad) != B:
             raise ValueError("one row count and one tail pad per row")
@@ -448,7 +452,54 @@ class BatchMixin:
             out.append(host[U + off: U + off + k].tolist())
             raws.append(host[off: off + n_rows[b] * up].tolist())
             off += n_rows[b] * up
+        if keep_raw:
+            return (out, raws, raw) if return_raw else (out, raw)
         return (out, raws) if return_raw else out
+
+    def batch_unit_spans(self, raw: torch.Tensor, n_states: List[int], K: List[int], dur, dur_first: Optional[List[int]] = None,
+                         unit0: Optional[List[int]] = None) -> List[np.ndarray]:
+        """Where each text-decoder state is spoken (ss_batch_unit_spans): raw = the device arg-max ids a t2u call kept (keep_raw),
+        n_states[b] / K[b] the states and the units of row b, dur the durations of the vocoder call that spoke them -- a DEVICE
+        int32 tensor packed [sum K] (HipVocoder.forward / batch_forward) or per row a host sequence of the durations of units
+        dur_first[b] .. K[b] (HipVocoder.batch_tail's info) -- and unit0[b] the first NEW unit (both default to 0).  -> per row an
+        int32 [n, 4] array {first_unit, n_units, start_frame, n_frames} over the new units; one launch, one download.  A row whose
+        units the kernel counts differently from K[b] raises with the row's number."""
+        B = len(n_states)
+        d0 = [0] * B if dur_first is None else [int(x) for x in dur_first]
+        u0 = [0] * B if unit0 is None else [int(x) for x in unit0]
+        if not (len(K) == len(d0) == len(u0) == B):
+            raise ValueError("one state count, unit count, first duration and first new unit per row")
+        if raw.dtype != torch.int32 or not raw.is_contiguous() or raw.numel() < self.cfg.ctc_upsample * sum(int(n) for n in n_states):
+            raise ValueError("raw: the contiguous int32 arg-max ids of all rows")
+        d_dur = h_dur = None
+        if torch.is_tensor(dur):
+            if dur.dtype != torch.int32 or not dur.is_contiguous() or dur.numel() < sum(int(k) for k in K):
+                raise ValueError("dur: a contiguous int32 tensor with one duration per unit")
+            d_dur = dur if dur.numel() else torch.zeros((1,), dtype=torch.int32, device=raw.device)
+        else:
+            if len(dur) != B:
+                raise ValueError("dur: one sequence of durations per row")
+            h_dur = np.zeros((max(sum(int(k) for k in K), 1),), dtype=np.int32)
+            off = 0
+            for b in range(B):
+                m = int(K[b]) - d0[b]
+                if len(dur[b]) < m:
+                    raise ValueError(f"row {b}: {len(dur[b])} durations for units {d0[b]} .. {int(K[b])}")
+                h_dur[off: off + m] = np.asarray(dur[b][:m], dtype=np.int32) if m > 0 else 0
+                off += int(K[b])
+        spans = np.empty((sum(int(n) for n in n_states), 4), dtype=np.int32)
+        counted = np.empty((B,), dtype=np.int32)
+        L.check(self.lib.ss_batch_unit_spans(self.h, _stream(), B, _ptr(raw), _i32(n_states), _i32(K), _i32(d0), _i32(u0), _ptr(d_dur),
+                                             None if h_dur is None else h_dur.ctypes.data_as(C.c_void_p),
+                                             spans.ctypes.data_as(C.c_void_p), counted.ctypes.data_as(C.c_void_p)),
+                "ss_batch_unit_spans")
+        out, off = [], 0
+        for b in range(B):
+            if int(counted[b]) != int(K[b]):
+                raise L.StreamSpeechHipError(f"ss_batch_unit_spans: row {b} holds {int(counted[b])} units, the caller counted {int(K[b])}")
+            out.append(spans[off: off + int(n_states[b])])
+            off += int(n_states[b])
+        return out
 
     def batch_mt_features(self, enc_packed: torch.Tensor, Tp: List[int], tokens: List[List[int]], n_tail_pad: List[int]) -> List[torch.Tensor]:
         """Decoder states of B fed rows in one ragged pass (ss_batch_mt_features): row b feeds [</s>, tokens[b]..., <pad> x
@@ -847,8 +898,9 @@ class HipModel(BatchMixin):
 
     # ---- a11-a13 --------------------------------------------------------------------------
     def t2u_units(self, mt_feats: torch.Tensor, t2u_causal: bool = False, mask_eos: bool = False,
-                  want_logits: bool = False, n_tail_pad: int = 0):
-        """mt_feats [n,512] -> (collapsed unit-vocab tokens list, raw argmax tensor(host), logits or None)."""
+                  want_logits: bool = False, n_tail_pad: int = 0, keep_raw: bool = False):
+        """mt_feats [n,512] -> (collapsed unit-vocab tokens list, raw argmax tensor(host), logits or None); keep_raw: plus the raw
+        arg-max ids on the DEVICE (what :meth:`batch_unit_spans` reads)."""
         n = mt_feats.shape[0]
         U = n * self.cfg.ctc_upsample
         ibuf = torch.empty((2 * U + 1,), dtype=torch.int32, device=self.device)
@@ -858,6 +910,8 @@ class HipModel(BatchMixin):
                                       int(mask_eos), _ptr(raw), _ptr(toks), _ptr(cnt), _ptr(logits), n_tail_pad), "ss_t2u_units")
         host = ibuf.cpu()
         k = int(host[2 * U])
+        if keep_raw:
+            return host[U:U + k].tolist(), host[:U], logits, raw
         return host[U:U + k].tolist(), host[:U], logits
 
 

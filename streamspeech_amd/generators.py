@@ -84,10 +84,16 @@ class CTCSequenceGenerator:
         self.incremental_states = None
 
     @torch.no_grad()
-    def generate(self, mt_features: torch.Tensor, prefix=None, n_tail_pad: int = 0, **kw):
+    def generate(self, mt_features: torch.Tensor, prefix=None, n_tail_pad: int = 0, keep_raw: bool = False, **kw):
         """mt_features [n,512] = the MT decoder states the reference feeds to synthesizer_encoder
-        (agent :652-689; T2U encoder and unit decoder run inside one C-ABI stage)."""
+        (agent :652-689; T2U encoder and unit decoder run inside one C-ABI stage).  keep_raw: the hypothesis also carries
+        ``raw_device``, the arg-max ids where the engine left them (what engine.batch_unit_spans reads)."""
         assert prefix is None, "tgt_units_indices is never set by the reference agent (SURVEY.md App. B)"
+        if keep_raw:
+            toks, raw, _, raw_dev = self.engine.t2u_units(mt_features, t2u_causal=self.t2u_causal, mask_eos=self.mask_eos,
+                                                          n_tail_pad=n_tail_pad, keep_raw=True)
+            return [[{"tokens": torch.tensor(toks, dtype=torch.long), "org_tokens": raw, "attn": None, "alignment": None,
+                      "raw_device": raw_dev}]]
         toks, raw, _ = self.engine.t2u_units(mt_features, t2u_causal=self.t2u_causal, mask_eos=self.mask_eos,
                                              n_tail_pad=n_tail_pad)
         return [[{"tokens": torch.tensor(toks, dtype=torch.long), "org_tokens": raw, "attn": None, "alignment": None}]]

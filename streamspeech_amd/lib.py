@@ -291,6 +291,12 @@ SIGNATURES = {
     "ss_batch_vocoder_tail": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int32), _i, _vp, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(_i64), C.POINTER(_i64)]),
+    "ss_batch_unit_spans": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32), _vp, _vp, _vp, _vp]),
+    "ss_unit_spans_host": (_i, [_i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp,
+                                _i, _i, _i, _i, _i, _vp, _vp]),
+    "ss_op_unit_spans": (_i, [_vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                              _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ss_prof_enable": (_i, [_i]),
     "ss_prof_enable_hi": (_i, [_i]),
     "ss_prof_reset": (_i, []),

@@ -49,7 +49,7 @@ import torch
 
 from . import frontend
 from .pipeline import units_from_tokens
-from .words import words_from_attention, words_from_ctc
+from .words import segments_from_spans, spoken_from_segments, words_from_attention, words_from_ctc
 
 
 def detok(symbols: Sequence[str]) -> str:
@@ -84,7 +84,7 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              unk_penalty: float = 0.0, normalize: bool = True, pcm16_out: bool = False, speaker_id: int = -1,
              features: bool = False, word_times: bool = False, mt_alignment: bool = False, len_penalty: float = 1.0,
              temperature: float = 1.0, no_repeat_ngram_size: int = 0,
-             references: Optional[Dict[str, Dict[int, Sequence[int]]]] = None) -> Dict[int, Dict]:
+             references: Optional[Dict[str, Dict[int, Sequence[int]]]] = None, spoken_words: bool = False) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
@@ -101,8 +101,15 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     references (--align-reference): {"asr": {sample id: label ids}, "st": {...}}, the reference text of each head as ids of its
     dictionary.  One batch_ctc_align per head and batch over the rows that have one; writes generate-<subset>.asr.ref.words /
     .st.ref.words and generate-<subset>.ref.scores (a line per sample and head: status aligned / infeasible / nan, or no_reference /
-    invalid_label / too_long / no_audio where nothing was aligned) and changes no other file."""
+    invalid_label / too_long / no_audio where nothing was aligned) and changes no other file.
+    spoken_words (--spoken-words): also writes generate-<subset>.spoken.words, the words of every `D-` hypothesis with the time span
+    each is spoken at in its pred_wav (words.spoken_from_segments; a last `</s>` line holds the speech that belongs to no word, if
+    any), from ONE batch_unit_spans call per batch over the arg-max ids of its unit pass and the durations of its vocoder call;
+    rows without units get no lines; refused without the vocoder call (dump_wav False); every other file is the one written
+    without it."""
     from .engine import check_search_options
+    if spoken_words and not dump_wav:
+        raise ValueError("spoken_words needs the vocoder's durations: it cannot be combined with dump_wav=False (--no-wav)")
     search = {}
     if check_search_options(len_penalty, temperature, no_repeat_ngram_size) is not None:
         search = {"len_penalty": float(len_penalty), "temperature": float(temperature),
@@ -116,6 +123,7 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     res_f = open(os.path.join(results_path, f"generate-{subset}.txt"), "w", encoding="utf-8")
     hyps: Dict[int, Dict] = {}
     words: Dict[str, Dict[int, list]] = {"asr": {}, "st": {}, "mt": {}}
+    spoken: Dict[int, object] = {}
     ref_words: Dict[str, Dict[int, list]] = {"asr": {}, "st": {}}
     ref_scores: Dict[Tuple[int, str], Tuple[int, float, float, str]] = {}
     if features:
@@ -165,7 +173,10 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
             toks = [h[0]["tokens"] if h else [] for h in nbest]
         else:
             toks, feats, n = model.batch_mt_greedy(enc, Tp, mx)
-        unit_toks = model.batch_t2u_units(feats, n, t2u_causal=t2u_causal, mask_eos=True)
+        if spoken_words:
+            unit_toks, raw_dev = model.batch_t2u_units(feats, n, t2u_causal=t2u_causal, mask_eos=True, keep_raw=True)
+        else:
+            unit_toks = model.batch_t2u_units(feats, n, t2u_causal=t2u_causal, mask_eos=True)
         codes = [units_from_tokens(t, cfg) for t in unit_toks]
         if mt_alignment:                        # after the search and the unit pass: nothing of this batch reads the MT scratch any more
             mts = [[t for t in toks[b] if t != cfg.eos] for b in range(len(ids))]
@@ -187,8 +198,16 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
                 spk["speakers"] = [speaker_id if speaker_id >= 0 else random.randint(0, n_spk - 1) for _ in have]
                 for b, k in zip(have, spk["speakers"]):
                     print(f"K-{ids[b]}\t{k}", file=log_f)
-            w, _, _ = vocoder.batch_forward([codes[b] for b in have], dur_prediction=dur_prediction, **spk)
+            w, dur_dev, _ = vocoder.batch_forward([codes[b] for b in have], dur_prediction=dur_prediction, **spk)
             wavs = {b: w[j] for j, b in enumerate(have)}
+            if spoken_words:                    # one spans call per batch: the unit pass's ids and the vocoder call's durations, where they lie
+                up, off = cfg.ctc_upsample, [0]
+                for x in n:
+                    off.append(off[-1] + int(x))
+                raw_h = raw_dev if len(have) == len(ids) else torch.cat([raw_dev[off[b] * up: off[b + 1] * up] for b in have], 0)
+                spans = model.batch_unit_spans(raw_h, [n[b] for b in have], [len(codes[b]) for b in have], dur_dev)
+                for b, sp in zip(have, spans):
+                    spoken[ids[b]] = spoken_from_segments(toks[b], segments_from_spans(sp, 0), dicts["target_unigram"], eos=cfg.eos)
             if pcm16_out:
                 pcm16 = _pack_batch(model, [wavs[b] for b in have])
                 pcm16 = {b: pcm16[j] for j, b in enumerate(have)}
@@ -211,6 +230,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
             if pos is not None:
                 print(f"P-{sid}\t" + " ".join("{:.4f}".format(x) for x in pos), file=res_f)
             hyps[sid] = {"asr": a_txt, "st": s_txt, "mt": d_txt, "units": codes[b], "wav": wavs.get(b)}
+            if spoken_words:
+                hyps[sid]["spoken"] = spoken.get(sid)
             if pcm16_out and dump_wav and have:
                 hyps[sid]["pcm16"] = pcm16.get(b)
     res_f.close()
@@ -236,6 +257,14 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
                     n, score, vit, status = ref_scores.get((sid, key), (0 if ref is None else len(ref), float("nan"), float("nan"),
                                                                        "no_reference" if ref is None else "no_audio"))
                     print(f"{sid}\t{key}\t{n}\t{score:.6f}\t{vit:.6f}\t{status}", file=f)
+    if spoken_words:
+        with open(os.path.join(results_path, f"generate-{subset}.spoken.words"), "w", encoding="utf-8") as f:
+            for sid in sorted(spoken):
+                for w in spoken[sid].words:
+                    print(f"{sid}\t{w.text}\t{w.start_ms}\t{w.end_ms}\t{w.n_units}", file=f)
+                if spoken[sid].tail_ms > 0:
+                    t = spoken[sid]
+                    print(f"{sid}\t</s>\t{t.total_ms - t.tail_ms}\t{t.total_ms}\t0", file=f)
     if mt_alignment:
         with open(os.path.join(results_path, f"generate-{subset}.mt.words"), "w", encoding="utf-8") as f:
             for sid in sorted(words["mt"]):
@@ -462,6 +491,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mt-alignment", action="store_true",
                     help="also write generate-<subset>.mt.words: id, word, start_ms, end_ms, focus per word of the D- hypothesis, placed in "
                          "source time by the arg-max of the text decoder's cross-attention (one extra decoder pass per batch)")
+    ap.add_argument("--spoken-words", action="store_true",
+                    help="also write generate-<subset>.spoken.words: id, word, start_ms, end_ms, n_units per word of the D- hypothesis, "
+                         "the time span it is spoken at in the utterance's pred_wav (exact: from the unit decoder's arg-max and the "
+                         "predicted durations; one small extra launch per batch), plus an `</s>` line for speech that belongs to no "
+                         "word; not with --no-wav")
     ap.add_argument("--align-reference", action="store_true",
                     help="also align the recipe's reference text (the multitask manifests <task data>/<gen-subset>.tsv of source_unigram "
                          "and ctc_target_unigram) to the audio on both CTC heads: writes generate-<subset>.asr.ref.words / .st.ref.words "
@@ -499,6 +533,8 @@ def main(argv: Optional[List[str]] = None):
         check_search_options(a.lenpen, 1.0, a.no_repeat_ngram_size)
     except ValueError as e:
         ap.error(str(e))
+    if a.spoken_words and a.no_wav:
+        ap.error("--spoken-words needs the durations the vocoder predicts: it cannot be combined with --no-wav")
     if a.align_reference and (a.wav_list or a.synthetic > 0 or not a.data):
         ap.error("--align-reference needs the manifest's ids: it cannot be combined with --wav-list or --synthetic")
     if a.align_reference and not any(multitask_text_dir(a.data, a.multitask_config_yaml, t) for t in ("source_unigram", "ctc_target_unigram")):
@@ -591,7 +627,7 @@ def main(argv: Optional[List[str]] = None):
                     unk_penalty=a.unkpen, normalize=not a.unnormalized,
                     **({"pcm16_out": True} if a.pcm16_io else {}), **({"speaker_id": a.speaker_id} if voc.num_speakers else {}),
                     **({"features": True} if is_feat else {}), **({"word_times": True} if a.word_times else {}),
-                    **({"mt_alignment": True} if a.mt_alignment else {}),
+                    **({"mt_alignment": True} if a.mt_alignment else {}), **({"spoken_words": True} if a.spoken_words else {}),
                     **({"references": references} if references is not None else {}),
                     **({"len_penalty": a.lenpen, "no_repeat_ngram_size": a.no_repeat_ngram_size}
                        if (a.lenpen, a.no_repeat_ngram_size) != (1.0, 0) else {}))

@@ -7,6 +7,8 @@ the S2TT writers) and then, for the S2ST sessions that write,
   * ONE T2U + unit decoder call with per-row tail-pad masks (HipModel.batch_t2u_units_pad),
   * ONE receptive-field vocoder tail call (HipVocoder.batch_tail; one per duration-prediction setting in use).  On a multi-speaker
     vocoder every session has its own voice (``args.speaker_id``); the voices ride in that one call as per-row speakers.
+With ``spoken=True`` at most one unit-spans call (HipModel.batch_unit_spans: one launch, one download) follows each tail call, over
+that call's rows, and :meth:`SpeechSessionPool.spoken` answers where each committed word lies in the session's emitted speech.
 Driven by one host thread, like the pool.
 
 An S2ST session opened with ``pcm_out="s16le"`` answers :class:`PcmSegment` (16-bit PCM bytes) instead of a SpeechSegment holding a
@@ -61,12 +63,15 @@ class _SpeechSession(_Session):
         self.whole_word = args.source_segment_size >= 640
         self.dur_prediction = bool(args.dur_prediction)
         self.vocoder_ctx, self.vocoder_rf = vocoder_context(vocoder_cfg, getattr(args, "vocoder_context_units", -1))
+        self.spoken_last = None                   # pools with spoken: (committed tokens, segments) as of the utterance's last write
+        self.spoken_words = None                  # the words.Spoken formed of them, once asked
 
     def reset(self):                          # the S2ST agent's reset()
         super().reset()
         self.prev_output_tokens_mt = None
         self.unit = None
         self.unfinished_wav = None
+        self.spoken_rec = None                    # pools with spoken: segments, samples emitted, states seen (made by the first write)
 
 
 class SpeechSessionPool(TextSessionPool):
@@ -75,13 +80,68 @@ class SpeechSessionPool(TextSessionPool):
     KINDS = KINDS
 
     def __init__(self, model, max_sessions: int, max_rows: int, vocoder=None, beam_mt: int = 1, details: bool = False,
-                 align: bool = False, search=None, len_penalty: float = 1.0, temperature: float = 1.0, no_repeat_ngram_size: int = 0):
+                 align: bool = False, search=None, len_penalty: float = 1.0, temperature: float = 1.0, no_repeat_ngram_size: int = 0,
+                 spoken: bool = False):
+        """spoken: after every tail call of a step ONE unit-spans call (HipModel.batch_unit_spans) over that call's rows maps the
+        writers' new units to their decoder states, and spoken(sid) answers the words of the session's committed target tokens with
+        the time span each is spoken at in the emitted speech (words.Spoken).  The segments the sessions answer are the same
+        either way."""
         super().__init__(model, max_sessions, max_rows, beam_mt=beam_mt, details=details, align=align, search=search,
                          len_penalty=len_penalty, temperature=temperature, no_repeat_ngram_size=no_repeat_ngram_size)
+        self.with_spoken = bool(spoken)
         self.vocoder = getattr(vocoder, "hip", vocoder)
         self.t2u_causal = bool(getattr(model, "uni_encoder", False))   # the agent's ctc_generator: t2u_causal = model.uni_encoder
         self._emitter = None                              # pcm.PcmEmitter of the PcmOut sessions, made with the first one's write
         self._flush = []                                  # PcmOut sessions of the step that finish without new speech (_finish_empty)
+
+    def spoken(self, sid: int):
+        """The session's words.Spoken as of its last write: the words of all target tokens its utterance has committed with start_ms
+        / end_ms on the clock of the speech emitted for the utterance (16-kHz samples / 16: times of the speech, whatever rate or
+        format a PcmOut session is answered in), the tail and the total.  None before the first write, after reset(sid), for a
+        session that is not s2st, or in a pool without spoken; a finished utterance's words stay until the next one's first write."""
+        s = self._get(sid)
+        if not self.with_spoken or getattr(s, "spoken_last", None) is None:
+            return None
+        if s.spoken_words is None:                        # segments are kept by index; the words are formed when asked
+            from .words import spoken_from_segments
+            s.spoken_words = spoken_from_segments(s.spoken_last[0], s.spoken_last[1], s.dict["target_unigram"], eos=self.model.cfg.eos)
+        return s.spoken_words
+
+    def reset(self, sid: int):
+        super().reset(sid)
+        s = self._get(sid)
+        if hasattr(s, "spoken_last"):
+            s.spoken_last = s.spoken_words = None
+
+    def _spans_after_tail(self, grp, rows_of, raw, n, info):
+        """The ONE unit-spans call after a tail call: grp = the call's (session, units, n_new) rows, rows_of[sid] = the session's row
+        in the step's unit pass, raw = that pass's device arg-max ids (row r at ctc_upsample x the prefix sum of n), info = the tail
+        call's (first unit synthesised, durations) per row.  Runs before the rows' s.unit moves on."""
+        from .words import segments_from_spans
+        up = self.model.cfg.ctc_upsample
+        off = [0]
+        for x in n:
+            off.append(off[-1] + int(x))
+        idx = [rows_of[s.sid] for s, _, _ in grp]
+        if idx == list(range(len(n))):
+            sub = raw
+        else:                                             # some rows of the unit pass did not write, or wrote in the other tail call
+            sub = torch.cat([raw[off[r] * up: off[r + 1] * up] for r in idx], 0)
+        spans = self.model.batch_unit_spans(sub, [n[r] for r in idx], [len(u) for _, u, _ in grp], [d for _, d in info],
+                                            [f for f, _ in info], [len(u) - k for _, u, k in grp])
+        for (s, unit, _), sp in zip(grp, spans):
+            rec = s.spoken_rec
+            if rec is None:
+                rec = s.spoken_rec = {"segments": [], "samples": 0, "seen": 0}
+            clock = rec["samples"] // 16
+            carried = len(s.unfinished_wav) if s.unfinished_wav is not None else 0
+            if carried:
+                rec["segments"].append((-1, clock, clock + carried // 16, 0))
+                clock += carried // 16
+            rec["segments"].extend(segments_from_spans(sp, clock, rec["seen"]))
+            rec["seen"] = max(rec["seen"], int(sp.shape[0]))
+            rec["samples"] += carried + 320 * int(sp[:, 3].sum())
+            s.spoken_last, s.spoken_words = (list(s.tgt_subwords), rec["segments"]), None
 
     def _check_open(self, kind, args):
         if kind != "s2st":
@@ -176,7 +236,12 @@ class SpeechSessionPool(TextSessionPool):
             packed = torch.zeros((len(rows), max(n), D), dtype=torch.float32, device=feats[0].device)
             for r, f in enumerate(feats):
                 packed[r, :f.shape[0]] = f
-            units = self.model.batch_t2u_units_pad(packed, n, [p for _, _, p in rows], t2u_causal=self.t2u_causal)
+            if self.with_spoken:
+                units, raw_dev = self.model.batch_t2u_units_pad(packed, n, [p for _, _, p in rows], t2u_causal=self.t2u_causal,
+                                                                keep_raw=True)
+                rows_of = {s.sid: r for r, (s, _, _) in enumerate(rows)}
+            else:
+                units = self.model.batch_t2u_units_pad(packed, n, [p for _, _, p in rows], t2u_causal=self.t2u_causal)
             for (s, _, _), toks in zip(rows, units):
                 fin = s.states.source_finished
                 if len(toks) == 0:
@@ -197,7 +262,8 @@ class SpeechSessionPool(TextSessionPool):
         t2 = time.perf_counter()
         handover, raw = 0.0, []                           # raw: (session, tail) of the pcm_out writers, packed together below
         own = []                                          # the same of the PcmOut writers, emitted together below
-        tail_calls = 0
+        tail_calls = span_calls = 0
+        spans_s = 0.0
         for dp in (True, False):
             grp = [v for v in voc if v[0].dur_prediction == dp]
             if not grp:
@@ -205,8 +271,13 @@ class SpeechSessionPool(TextSessionPool):
             tail_calls += 1
             # a multi-speaker vocoder: the rows' voices go along in the same call (no grouping by voice)
             spk = {"speakers": [s.speaker_id for s, _, _ in grp]} if getattr(self.vocoder, "num_speakers", 0) else {}
-            tails, _ = self.vocoder.batch_tail([u for _, u, _ in grp], [k for _, _, k in grp], [s.vocoder_ctx for s, _, _ in grp],
-                                               [s.vocoder_rf for s, _, _ in grp], dur_prediction=dp, **spk)
+            tails, tail_info = self.vocoder.batch_tail([u for _, u, _ in grp], [k for _, _, k in grp], [s.vocoder_ctx for s, _, _ in grp],
+                                                       [s.vocoder_rf for s, _, _ in grp], dur_prediction=dp, **spk)
+            if self.with_spoken:
+                ts = time.perf_counter()
+                self._spans_after_tail(grp, rows_of, raw_dev, n, tail_info)
+                span_calls += 1
+                spans_s += time.perf_counter() - ts
             th = time.perf_counter()
             for (s, unit, _), wav in zip(grp, tails):
                 if s.unfinished_wav is not None and len(s.unfinished_wav) > 0:
@@ -233,6 +304,8 @@ class SpeechSessionPool(TextSessionPool):
                             "speech_writers": len(voc), "vocoder_tail_calls": tail_calls, "pcm_pack_calls": 1 if n_out else 0,
                             "pcm_bytes_out": 2 * n_out,
                             "pcm_emit_calls": emit_calls, "pcm_emit_bytes_out": emit_bytes}
+        if self.with_spoken:
+            self._side_times.update({"spans_s": spans_s, "span_calls": span_calls})
 
     def _emit_out(self, own, flush, actions):
         """The tails of a step's PcmOut writers and the flushes of its PcmOut sessions that finish without new speech -> bytes at

@@ -8,9 +8,14 @@ finished) and the speech-output instance's timing model (evaluator/instance.py:3
   intervals = [start_i, duration_i] with start_i = max(previous end, delay_i)                (playback never overlaps)
   RTF       = end of the last interval / source length  (scorers/latency_scorer.py:574-587; *_CA uses elapsed_i)
   StartOffset = delay_0, EndOffset = last end - source length                               (:540-571)
-Only what the S2ST hot path needs: no dataloader, no file output."""
+Only what the S2ST hot path needs: no dataloader, no file output.
+
+Word-level latency of the speech output (SimulEval's <metric>_SpeechAlign_{BOW,COW,EOW}, scorers/latency_scorer.py:590-686): there
+the word times come from a forced aligner run on the written wavs; here they are exact, from the unit spans of every write
+(agent.spoken, streamspeech_amd/words.py) -- :func:`speech_align_latency` over the playback times :func:`run_utterance` derives with
+``spoken=True``."""
 import time
-from typing import Dict, List
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -27,8 +32,67 @@ def _intervals(marks: List[float], durations: List[float]):
     return out
 
 
-def run_utterance(agent, pcm: np.ndarray, segment_ms: int = 320, sr: int = 16000, sync=True) -> Dict:
-    """Feed `pcm` to the agent chunk by chunk; time every pushpop (policy() + host glue, device synchronised)."""
+def speech_align_latency(delays_ms: Sequence[float], source_ms: float, ref_len: Optional[int] = None) -> Dict[str, float]:
+    """AL / LAAL / AP / DAL of one utterance from one delay per target word (milliseconds of source time at which the word, or the
+    chosen boundary of it, is played), as SimulEval's scorers of these names compute them (latency_scorer.py:114-293), in float64:
+      target length |Y| = ref_len when given, else the number of delays; gamma = |Y| / source_ms;
+      AL   = mean over i <= tau of d_i - (i - 1) / gamma, tau = the first i with d_i >= source_ms (all, if none); d_1 when d_1 > source_ms;
+      LAAL = AL with gamma = max(number of delays, |Y|) / source_ms;
+      AP   = sum d_i / (source_ms * |Y|);
+      DAL  = mean of d'_i - (i - 1) / gamma over all delays with gamma = number of delays / source_ms (never ref_len), d'_1 = d_1,
+             d'_i = max(d_i, d'_(i-1) + 1 / gamma)."""
+    d = [x for x in delays_ms]
+    if not d:
+        raise ValueError("no delays")
+    if not source_ms > 0:
+        raise ValueError("source_ms must be positive")
+    n = len(d)
+    tgt = n if ref_len is None else ref_len
+    out = {}
+    for name, length in (("AL", tgt), ("LAAL", max(n, tgt))):
+        if d[0] > source_ms:
+            out[name] = d[0]
+            continue
+        gamma = length / source_ms
+        acc, tau = 0, 0
+        for i, x in enumerate(d):
+            acc += x - i / gamma
+            tau = i + 1
+            if x >= source_ms:
+                break
+        out[name] = acc / tau
+    out["AP"] = sum(d) / (source_ms * tgt)
+    gamma = n / source_ms
+    acc, last = 0, 0
+    for i, x in enumerate(d):
+        last = x if i == 0 else max([x, last + 1 / gamma])
+        acc += last - i / gamma
+    out["DAL"] = acc / n
+    return out
+
+
+def playback_ms(t_ms: float, writes: Sequence, is_start: bool) -> float:
+    """When the instant t_ms of the emitted speech is played.  writes: per write (emitted_before_ms, start_ms, duration_ms) with
+    start_ms from :func:`_intervals` -- SimulEval's target_offset + 1000 * time in the written wav, where the wav holds a silence
+    wherever a write starts after the previous one ended.  t lies in the write whose emitted range holds it; on a write boundary a
+    start belongs to the later write and an end to the earlier one."""
+    if not writes:
+        raise ValueError("no write")
+    pick = None
+    for k, (before, _, dur) in enumerate(writes):
+        if (before <= t_ms < before + dur) if is_start else (before < t_ms <= before + dur):
+            pick = k
+            break
+    if pick is None:                     # outside every half-open range: the clock's first or last instant (or a zero-length write)
+        pick = 0 if t_ms <= writes[0][0] else len(writes) - 1
+    before, start, _ = writes[pick]
+    return start + (t_ms - before)
+
+
+def run_utterance(agent, pcm: np.ndarray, segment_ms: int = 320, sr: int = 16000, sync=True, spoken: bool = False) -> Dict:
+    """Feed `pcm` to the agent chunk by chunk; time every pushpop (policy() + host glue, device synchronised).  spoken: when the
+    agent carries ``.spoken`` (--spoken-words), the result also holds "spoken_words" (each word with the times it is played at) and
+    "SpeechAlign": {"BOW" | "COW" | "EOW": :func:`speech_align_latency` over the words' begin / centre / end playback times}."""
     step = sr * segment_ms // 1000
     src_ms_total = 1000.0 * len(pcm) / sr
     pos, src_ms = 0, 0.0
@@ -63,11 +127,31 @@ def run_utterance(agent, pcm: np.ndarray, segment_ms: int = 320, sr: int = 16000
     iv, iv_ca = _intervals(delays, durations), _intervals(elapsed, durations)
     end = (iv[-1][0] + iv[-1][1]) if iv else src_ms_total
     end_ca = (iv_ca[-1][0] + iv_ca[-1][1]) if iv_ca else src_ms_total + 1e3 * busy
-    return {"source_ms": src_ms_total, "compute_ms": 1e3 * busy, "calls": len(call_ms), "call_ms": call_ms,
-            "actions": "".join(actions), "writes": len(delays), "samples_out": samples_out,
-            "RTF": end / src_ms_total, "RTF_CA": end_ca / src_ms_total,
-            "StartOffset": delays[0] if delays else src_ms_total, "StartOffset_CA": elapsed[0] if elapsed else src_ms_total + 1e3 * busy,
-            "EndOffset": end - src_ms_total, "EndOffset_CA": end_ca - src_ms_total}
+    res = {"source_ms": src_ms_total, "compute_ms": 1e3 * busy, "calls": len(call_ms), "call_ms": call_ms,
+           "actions": "".join(actions), "writes": len(delays), "samples_out": samples_out,
+           "RTF": end / src_ms_total, "RTF_CA": end_ca / src_ms_total,
+           "StartOffset": delays[0] if delays else src_ms_total, "StartOffset_CA": elapsed[0] if elapsed else src_ms_total + 1e3 * busy,
+           "EndOffset": end - src_ms_total, "EndOffset_CA": end_ca - src_ms_total}
+    sp = getattr(agent, "spoken", None) if spoken else None
+    if sp is not None:
+        writes, before = [], 0.0
+        for (start, dur) in iv:
+            writes.append((before, start, dur))
+            before += dur
+        words = []
+        for w in sp.words:
+            words.append({"text": w.text, "start_ms": w.start_ms, "end_ms": w.end_ms, "n_units": w.n_units,
+                          "play_start_ms": playback_ms(w.start_ms, writes, True) if writes else None,
+                          "play_end_ms": playback_ms(w.end_ms, writes, False) if writes else None})
+        res["spoken_words"] = words
+        align = {"BOW": None, "COW": None, "EOW": None}
+        if words and writes:
+            bow = [w["play_start_ms"] for w in words]
+            eow = [w["play_end_ms"] for w in words]
+            cow = [(a + b) / 2 for a, b in zip(bow, eow)]
+            align = {k: speech_align_latency(v, src_ms_total) for k, v in (("BOW", bow), ("COW", cow), ("EOW", eow))}
+        res["SpeechAlign"] = align
+    return res
 
 
 def summarize(runs: List[Dict]) -> Dict:

@@ -7,6 +7,10 @@ encoder frame of each token's run, and the summed log-probability of the run.
 MT: the words of the first-pass text decoder's tokens (what the S2TT agent prints and the S2ST path speaks), placed by the arg-max of
 the decoder's head-averaged cross-attention (BatchMixin.batch_mt_attention) -- :func:`words_from_attention`.
 
+Spoken: where each word of the text decoder's tokens lies in the OUTPUT speech -- :func:`spoken_from_segments` over the unit spans
+of the writes (HipModel.batch_unit_spans: the unit decoder upsamples every decoder state into ctc_upsample CTC positions, the
+duration predictor gives every unit whole 20-ms frames, so the times are exact integers).
+
 Host-side glue: no device work here.
 """
 import math
@@ -92,6 +96,83 @@ def words_from_attention(tokens: Sequence[int], peak: Sequence[int], peak_prob: 
         words.append(AlignedWord(text, int(t0_ms) + min(pk) * int(frame_ms), int(t0_ms) + (max(pk) + 1) * int(frame_ms),
                                  math.fsum(float(peak_prob[j]) for j in g) / len(g)))
     return words
+
+
+UNIT_FRAME_MS = 20         # one vocoder frame: 320 samples at 16 kHz
+
+
+class SpokenWord(NamedTuple):
+    text: str               # the word's subwords joined, boundary mark removed
+    start_ms: int           # where its first unit starts on the clock of the emitted speech
+    end_ms: int             # where its last unit ends
+    n_units: int            # the units its tokens' states were given (0: nothing of the speech belongs to it)
+
+
+class Spoken(NamedTuple):
+    words: List[SpokenWord]
+    tail_ms: int            # speech of states that are not a committed token: the </s> state, a trailing <pad> state, a pending state
+    total_ms: int           # all speech emitted for the utterance: the words' segments and the tail add up to it
+
+
+def segments_from_spans(spans, clock_ms: int, n_seen: int = 0, frame_ms: int = UNIT_FRAME_MS):
+    """The segments one write adds: spans = the write's int32 [n, 4] unit spans {first_unit, n_units, start_frame, n_frames} (state s
+    is the decoder position that predicted token s), clock_ms = the speech emitted before the write.  -> [(state, start_ms, end_ms,
+    n_units)] for every state that was given a new unit, plus the zero-length segment of every state from n_seen on (the states no
+    earlier write saw), which marks where a token without units lies."""
+    out = []
+    clock_ms, frame_ms = int(clock_ms), int(frame_ms)
+    for s, (_, k, f0, nf) in enumerate(spans.tolist() if hasattr(spans, "tolist") else spans):
+        if k > 0 or s >= n_seen:
+            t0 = clock_ms + f0 * frame_ms
+            out.append((s, t0, t0 + nf * frame_ms, k))
+    return out
+
+
+def spoken_from_segments(tokens: Sequence[int], segments, symbols, eos: Optional[int] = None) -> Spoken:
+    """Words of the committed target tokens placed in the output speech.  segments: (token_index, start_ms, end_ms, n_units) in the
+    order the writes added them, times on the clock of the emitted speech; token_index s is the decoder state that predicted
+    tokens[s].  Grouping as :func:`words_from_attention` (the boundary mark starts a word, ``</s>`` is dropped).  A word's start_ms is
+    the earliest start over its segments that hold units, its end_ms their latest end, n_units their sum; a word none of whose
+    tokens received a unit is a zero-length word at the clock value of its first token's state (the first segment recorded for it).
+    Speech of an index that is not a committed token -- the state that predicts ``</s>`` or a not-yet-committed token, a trailing
+    <pad> state -- is no word: its milliseconds add up in tail_ms.  Segments are kept by index, so once such an index is a committed
+    token its earlier segments count for that token.  total_ms = the milliseconds of all segments."""
+    n = len(tokens)
+
+    def is_eos(t):
+        return (t == int(eos)) if eos is not None else (str(symbols[t]) == "</s>")
+
+    by_tok = {}
+    tail = total = 0
+    for idx, t0, t1, k in segments:
+        idx, t0, t1, k = int(idx), int(t0), int(t1), int(k)
+        if t1 < t0 or k < 0:
+            raise ValueError("a segment ends before it starts")
+        total += t1 - t0
+        if 0 <= idx < n and not is_eos(int(tokens[idx])):
+            by_tok.setdefault(idx, []).append((t0, t1, k))
+        else:
+            tail += t1 - t0
+    groups: List[List[int]] = []
+    for j in range(n):
+        t = int(tokens[j])
+        if is_eos(t):
+            continue
+        if not groups or str(symbols[t]).startswith(WORD_START):
+            groups.append([])
+        groups[-1].append(j)
+    words, clock = [], 0
+    for g in groups:
+        text = "".join(str(symbols[int(tokens[j])]) for j in g).replace(WORD_START, "")
+        segs = [sg for j in g for sg in by_tok.get(j, ()) if sg[2] > 0]
+        if segs:
+            start, end = min(sg[0] for sg in segs), max(sg[1] for sg in segs)
+        else:
+            first = by_tok.get(g[0]) or [sg for j in g for sg in by_tok.get(j, ())]
+            start = end = first[0][0] if first else clock
+        clock = max(clock, end)
+        words.append(SpokenWord(text, start, end, sum(sg[2] for sg in segs)))
+    return Spoken(words, tail, total)
 
 
 def details_from_hyps(src_hyp: dict, tgt_hyp: dict, src_symbols, tgt_symbols, n_final: Optional[int] = None, finished: bool = False,
