@@ -12,7 +12,8 @@
  * Additions since ABI 2 was cut (no existing signature changed): ss_flac_streaminfo, ss_flac_probe, ss_flac_unpack,
  * ss_flac_restore_host, ss_flac_restore (FLAC ingest), ss_batch_cmvn (precomputed fbank rows), ss_batch_mt_attention and
  * ss_op_attention_probs (cross-attention of the first-pass text decoder), ss_batch_unit_spans, ss_unit_spans_host and
- * ss_op_unit_spans (where each text-decoder state is spoken in the output speech).
+ * ss_op_unit_spans (where each text-decoder state is spoken in the output speech), ss_batch_mt_score, ss_op_mt_token_scores and
+ * ss_debug_mt_score_form (the text decoder's score of a given translation).
  *
  * Weight ownership: the caller owns one packed FP32 weight blob in HBM (built once from a fairseq
  * state dict by streamspeech_amd/weights.py) and lends it to ss_model_create(); the library keeps
@@ -966,6 +967,24 @@ int ss_batch_mt_features(ss_model* m, void* stream, int B, const float* d_enc_ou
 int ss_batch_mt_attention(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp, const int32_t* h_tokens,
                           const int32_t* h_n_tokens, const int32_t* h_first, float* d_feats, int feat_rows, float* d_attn,
                           int64_t* h_attn_off, int64_t attn_capacity, int32_t* d_peak, float* d_stat);
+/* ss_batch_mt_features' pass with n_tail_pad = 0 plus the score of the GIVEN text of every row -- fairseq's SequenceScorer
+ * (--score-reference) on the first-pass text decoder.  U utterances (h_Tp [U], d_enc_out their packed encoder rows), B >= U rows:
+ * row b is a text for utterance h_src[b] (h_src NULL: B == U, row b -> utterance b); several rows may name one utterance -- the
+ * cross-attention K/V is computed once over the U utterances, a candidate text costs no encoder copy.  Row b feeds [</s>, tokens_b...]
+ * (h_n_tokens[b] tokens WITHOUT </s>, packed in h_tokens): position p predicts tokens_b[p], the last position predicts </s>
+ * (fairseq's prev_output_tokens / target pair).  R = sum (h_n_tokens[b] + 1); per position, packed in row order:
+ *   d_stat [R][2] float: the natural-log probability of the predicted token under the plain log_softmax of the output projection
+ *     (no pad / unk masking, no unk penalty, no temperature), and the arg-max log-probability;
+ *   d_idx [R][2] int32: the arg-max id (lowest index of a tie) and the predicted token's rank (0: the model would have chosen it).
+ *   d_feats (may be NULL): [B][feat_rows][D], exactly the bits ss_batch_mt_features(..., n_tail_pad 0) writes for the same rows.
+ * The states are projected in chunks of at most 2048 rows into one logits buffer of the workspace; [R][V] never exists.  A row's
+ * answers are the same bits alone, in any pack and wherever a chunk boundary falls (pack-invariant contexts, the default).
+ * Checks and error codes of ss_batch_mt_features, plus SS_ERR_ARG for h_src[b] outside [0, U), U <= 0, U > B, B > 256, and <pad> as
+ * a text token (SequenceScorer strips pad).  Every check runs and every buffer is booked before anything is queued: a refusal
+ * leaves every output untouched.  Rewrites the scratch set's MT cross-attention K/V and workspace (as ss_batch_mt_features does). */
+int ss_batch_mt_score(ss_model* m, void* stream, int U, const float* d_enc_out, const int32_t* h_Tp, int B, const int32_t* h_src,
+                      const int32_t* h_tokens, const int32_t* h_n_tokens, float* d_feats, int feat_rows, float* d_stat,
+                      int32_t* d_idx);
 /* B rows of the S2ST agent's receptive-field vocoder tail: row b has h_K[b] units (packed in d_codes), the last h_n_new[b] new.  With
  * h_ctx[b] > 0 and h_K[b] > n_new + ctx only the last n_new + ctx units are synthesised, unless the durations of context units
  * [2, ctx) cover fewer than h_rf[b] + 2 frames -- then all units are.  Only the new units' samples are written: d_out[h_out_start[b]
@@ -1281,6 +1300,17 @@ int ss_op_masked_argmax_lprob(void* stream, const float* logits, int ld, int M, 
                               float* lprob);
 int ss_op_ctc_collapse_spans(void* stream, const int32_t* raw, const float* lprob, int T, int blank, int pad, int32_t* tokens,
                              int32_t* index, int32_t* last, float* tok_lprob, int32_t* count, const int32_t* segs, int nseg);
+/* The token score kernel of ss_batch_mt_score (csrc/mt_score.hip) on the caller's logits [rows][ld] (device; V columns read): for
+ * row r with tk = d_target[r] in [0, V): d_stat[2 r] = log_softmax(row)[tk], d_stat[2 r + 1] = the arg-max log-probability --
+ * both the bits ss_log_softmax writes at those columns -- d_idx[2 r] = the arg-max id (lowest index of a tie), d_idx[2 r + 1] =
+ * #{n: x[n] > x[tk]} + #{n < tk: x[n] == x[tk]}.  tk outside [0, V): the row writes nothing.  A row with a NaN or +inf column, or
+ * all -inf: NaN, NaN, -1, -1.  V <= 8192 is held in registers (one read of the row); wider rows, or every row after
+ * ss_debug_mt_score_form(1), take the two-read strided form with the same bits.  SS_ERR_ARG before anything is queued for a null
+ * pointer, rows <= 0, V <= 0, ld < V, or rows > 16777215 (rows is the grid's x extent: 256 threads a row must stay below 2^32).
+ * tests/test_mt_score_gpu.py against tests/mt_score_ref.py. */
+int ss_op_mt_token_scores(void* stream, const float* d_logits, int ld, int rows, int V, const int32_t* d_target, float* d_stat,
+                          int32_t* d_idx);
+int ss_debug_mt_score_form(int force_strided);
 /* The two kernels of ss_batch_ctc_align on the caller's logits [sum T][ld] (device; V columns read), arguments and outputs as
  * ss_ctc_align_host with device output pointers.  tests/test_ctc_align_gpu.py against tests/ctc_align_ref.py. */
 int ss_op_ctc_align(void* stream, const float* d_logits, int ld, int V, int pad, int B, const int32_t* h_T, const int32_t* h_targets,

@@ -655,47 +655,71 @@ struct MtAttnOut {
   int32_t* d_peak = nullptr; float* d_stat = nullptr;
 };
 
-// ss_batch_mt_features (ao == nullptr: its launches exactly) and ss_batch_mt_attention (n_tail_pad == nullptr: no trailing <pad>).
+// The optional third answer (ss_batch_mt_score): every fed position's state projected onto the vocabulary and scored against the
+// token it predicts (mt_score.hip).  The B rows are texts for U <= B utterances: h_Tp then holds U lengths and row b reads the
+// encoder rows of utterance h_src[b] (null: B == U, row b -> utterance b), so candidate texts for one audio share its cross K/V.
+struct MtScoreOut {
+  int U = 0;
+  const int32_t* h_src = nullptr;
+  float* d_stat = nullptr; int32_t* d_idx = nullptr;      // [R][2] each, R = sum (n_tokens_b + 1), packed in row order
+};
+constexpr int kMtScoreChunk = 2048;                       // state rows projected per launch: the logits buffer is [<= 2048][V]
+
+// ss_batch_mt_features (ao == so == nullptr: its launches exactly), ss_batch_mt_attention and ss_batch_mt_score (n_tail_pad ==
+// nullptr: no trailing <pad>; at most one of ao / so).
 static int batch_mt_features(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp, const int32_t* h_tokens,
                              const int32_t* h_n_tokens, const int32_t* h_n_tail_pad, float* d_feats, int feat_rows,
-                             const MtAttnOut* ao) {
-  if (!m || B <= 0 || B > 256 || !d_enc_out || !h_Tp || !h_n_tokens) return SS_ERR_ARG;
-  if (ao ? (!ao->d_peak || !ao->d_stat) : (!h_n_tail_pad || !d_feats)) return SS_ERR_ARG;
+                             const MtAttnOut* ao, const MtScoreOut* so = nullptr) {
+  if (!m || B <= 0 || B > 256 || !d_enc_out || !h_Tp || !h_n_tokens || (ao && so)) return SS_ERR_ARG;
+  if (so ? (!so->d_stat || !so->d_idx) : ao ? (!ao->d_peak || !ao->d_stat) : (!h_n_tail_pad || !d_feats)) return SS_ERR_ARG;
   if (d_feats && feat_rows <= 0) return SS_ERR_ARG;
   const ss_config& c = m->cfg;
-  const int D = c.dec_dim, F = c.dec_ffn;
+  const int D = c.dec_dim, F = c.dec_ffn, V = c.tgt_vocab;
   if (ao && (c.dec_heads > ATTN_PROBS_MAX_H || c.mt_layers <= 0 || !m->mt[c.mt_layers - 1].has_cross)) return SS_ERR_ARG;
+  const int U = so ? so->U : B;                           // utterances = entries of h_Tp
+  if (so) {
+    if (U <= 0 || U > B || (!so->h_src && U != B)) return SS_ERR_ARG;
+    for (int u = 0; u < U; ++u)
+      if (h_Tp[u] <= 0) return SS_ERR_ARG;
+    for (int b = 0; so->h_src && b < B; ++b)
+      if (so->h_src[b] < 0 || so->h_src[b] >= U) return SS_ERR_ARG;
+  }
   std::vector<int> seg_len(B);
   int tok_total = 0;
   for (int b = 0; b < B; ++b) {
     const int pad_b = h_n_tail_pad ? h_n_tail_pad[b] : 0;
-    if (h_Tp[b] <= 0 || h_n_tokens[b] < 0 || pad_b < 0) return SS_ERR_ARG;
+    if ((!so && h_Tp[b] <= 0) || h_n_tokens[b] < 0 || pad_b < 0) return SS_ERR_ARG;
     if (h_n_tokens[b] > 0 && !h_tokens) return SS_ERR_ARG;
     if (ao && ao->h_first && (ao->h_first[b] < 0 || ao->h_first[b] > h_n_tokens[b])) return SS_ERR_ARG;
-    for (int i = 0; i < h_n_tokens[b]; ++i)
+    for (int i = 0; i < h_n_tokens[b]; ++i) {
       if (h_tokens[tok_total + i] < 0 || h_tokens[tok_total + i] >= c.tgt_vocab) return SS_ERR_ARG;   // nn.Embedding's IndexError
+      if (so && h_tokens[tok_total + i] == c.pad) return SS_ERR_ARG;   // SequenceScorer strips pad: it is never a scored token
+    }
     tok_total += h_n_tokens[b];
     seg_len[b] = 1 + h_n_tokens[b] + pad_b;
     if ((d_feats && seg_len[b] > feat_rows) || seg_len[b] + 2 > c.max_tgt_pos) return SS_ERR_CAPACITY;   // ss_mt_append's position bound
   }
-  const Offsets oe = prefix(h_Tp, B), op = prefix(seg_len.data(), B);
+  const Offsets oe = prefix(h_Tp, U), op = prefix(seg_len.data(), B);
   const int Np = op.total;
   const size_t np = (size_t)Np;
   // int tables: self segs [4B] | cross segs [4B] | self tail [B] | tokens [Np] | positions [Np] | feature rows [Np]
   //             (+ with ao: first answered row [B] | output row [B] | padding to 8 bytes | offsets into d_attn [B] int64)
+  //             (+ with so: the token every position predicts [Np])
   const size_t n_base = 9 * (size_t)B + 3 * np;
   const size_t n_off = ao ? ((n_base + 2 * (size_t)B + 1) & ~(size_t)1) : n_base;
-  std::vector<int> tab(ao ? n_off + 2 * (size_t)B : n_base);
+  std::vector<int> tab(ao ? n_off + 2 * (size_t)B : so ? n_base + np : n_base);
   int* ps = tab.data(); int* pc = ps + 4 * B; int* pt = pc + 4 * B; int* tk = pt + B; int* pp = tk + np; int* pf = pp + np;
   for (int b = 0, o = 0; b < B; ++b) {
     const int r0 = op.off[b], n = seg_len[b], nt = h_n_tokens[b];
+    const int u = so && so->h_src ? so->h_src[b] : b;
     ps[4 * b] = r0; ps[4 * b + 1] = n; ps[4 * b + 2] = r0; ps[4 * b + 3] = n;
-    pc[4 * b] = r0; pc[4 * b + 1] = n; pc[4 * b + 2] = oe.off[b]; pc[4 * b + 3] = h_Tp[b];
+    pc[4 * b] = r0; pc[4 * b + 1] = n; pc[4 * b + 2] = oe.off[u]; pc[4 * b + 3] = h_Tp[u];
     pt[b] = h_n_tail_pad ? h_n_tail_pad[b] : 0;
     for (int p = 0; p < n; ++p) {
       tk[r0 + p] = p == 0 ? c.eos : p <= nt ? h_tokens[o + p - 1] : c.pad;
       pp[r0 + p] = p;
       pf[r0 + p] = b * feat_rows + p;
+      if (so) tab[n_base + r0 + p] = p < nt ? h_tokens[o + p] : c.eos;   // position p predicts token p, the last one </s>
     }
     o += nt;
   }
@@ -716,7 +740,8 @@ static int batch_mt_features(ss_model* m, void* stream, int B, const float* d_en
   }
   // ---- every buffer first: a scratch cap refuses the call before anything is queued ----
   RET(m->sc->mt_cross.ensure((size_t)c.mt_layers * oe.total * 2 * D * sizeof(float)));
-  RET(m->sc->ws.ensure((np * (7 * D + F)) * sizeof(float)));
+  const int n_log = so ? std::min(Np, kMtScoreChunk) : 0;          // logits rows behind the pass's own workspace
+  RET(m->sc->ws.ensure((np * (7 * D + F) + (size_t)n_log * V) * sizeof(float)));
   RET(m->sc->seg_buf.ensure(tab.size() * sizeof(int)));
   if (ao && ao->d_attn && ao->h_attn_off)          // the one host output, after the last refusal
     for (int b = 0; b < B; ++b) std::memcpy(&ao->h_attn_off[b], tab.data() + n_off + 2 * (size_t)b, sizeof(int64_t));
@@ -730,6 +755,19 @@ static int batch_mt_features(ss_model* m, void* stream, int B, const float* d_en
   const float* pfo = nullptr;
   RET(mt_prefix_pass(m, s, B, Np, op.mx, oe.total, d_tok, d_pos, d_self, d_cross, d_tail, nullptr, 0, &pfo));
   if (d_feats) RET(launch_scatter_rows(d_frow, pfo, D, d_feats, D, D, Np, B * feat_rows, s));
+  if (so) {
+    // the output projection of the searches' prefix rows (beam.hip), a chunk of state rows at a time: under CANON_SEQ a logits row
+    // is a function of its state row alone, so neither the chunk boundaries nor the pack change a bit; [Np][V] never exists
+    float* logits = m->sc->ws.f() + np * (7 * D + F);
+    const int* d_tgt = dt + n_base;
+    Lin proj{m->mt_emb, nullptr};
+    for (int r0 = 0; r0 < Np; r0 += kMtScoreChunk) {
+      const int rows = std::min(kMtScoreChunk, Np - r0);
+      RET(linear(s, pfo + (size_t)r0 * D, D, rows, proj, V, D, logits, V));
+      RET(launch_mt_token_scores(logits, V, rows, V, d_tgt + r0, so->d_stat + 2 * (size_t)r0, so->d_idx + 2 * (size_t)r0, s));
+    }
+    return SS_OK;
+  }
   if (!ao) return SS_OK;
   // the last layer's cross-attention Q is still in the pass's q2 rows (mt_prefix_pass: x | h | q2 | ...; nothing after a layer's
   // cross-attention writes them), its K in the last slice of mt_cross
@@ -766,6 +804,18 @@ extern "C" int ss_batch_mt_attention(ss_model* m, void* stream, int B, const flo
   ao.h_first = h_first; ao.d_attn = d_attn; ao.h_attn_off = h_attn_off; ao.attn_capacity = attn_capacity;
   ao.d_peak = d_peak; ao.d_stat = d_stat;
   return batch_mt_features(m, stream, B, d_enc_out, h_Tp, h_tokens, h_n_tokens, nullptr, d_feats, feat_rows, &ao);
+}
+
+// The same pass answering how likely the decoder finds each GIVEN text (fairseq's SequenceScorer, --score-reference): row b feeds
+// [</s>, tokens_b...] over the encoder rows of utterance h_src[b]; every position's state is projected onto the vocabulary and
+// scored against the token it predicts (the last one: </s>).  d_feats optional (the bits ss_batch_mt_features writes).
+extern "C" int ss_batch_mt_score(ss_model* m, void* stream, int U, const float* d_enc_out, const int32_t* h_Tp, int B,
+                                 const int32_t* h_src, const int32_t* h_tokens, const int32_t* h_n_tokens, float* d_feats,
+                                 int feat_rows, float* d_stat, int32_t* d_idx) {
+  if (!d_stat || !d_idx) return SS_ERR_ARG;
+  MtScoreOut so;
+  so.U = U; so.h_src = h_src; so.d_stat = d_stat; so.d_idx = d_idx;
+  return batch_mt_features(m, stream, B, d_enc_out, h_Tp, h_tokens, h_n_tokens, nullptr, d_feats, feat_rows, nullptr, &so);
 }
 
 // New fbank rows of many streaming sessions in ONE launch (the batched front-end of the text session pool): session b's frames

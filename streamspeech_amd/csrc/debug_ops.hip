@@ -222,6 +222,13 @@ extern "C" int ss_op_masked_argmax_lprob(void* stream, const float* logits, int 
                                          int32_t* ids, float* lprob) {
   return launch_masked_argmax_lprob(logits, ld, M, N, mask0, mask1, mask2, ids, lprob, (hipStream_t)stream);
 }
+// the token score kernel of ss_batch_mt_score (mt_score.hip); ss_debug_mt_score_form(1) forces its two-read strided form
+static int g_mt_score_form = 0;
+extern "C" int ss_debug_mt_score_form(int v) { g_mt_score_form = v ? 1 : 0; return SS_OK; }
+extern "C" int ss_op_mt_token_scores(void* stream, const float* d_logits, int ld, int rows, int V, const int32_t* d_target,
+                                     float* d_stat, int32_t* d_idx) {
+  return launch_mt_token_scores(d_logits, ld, rows, V, d_target, d_stat, d_idx, (hipStream_t)stream, g_mt_score_form);
+}
 extern "C" int ss_op_ctc_collapse_spans(void* stream, const int32_t* raw, const float* lprob, int T, int blank, int pad, int32_t* tokens,
                                         int32_t* index, int32_t* last, float* tok_lprob, int32_t* count, const int32_t* segs, int nseg) {
   return launch_ctc_collapse_spans(raw, lprob, T, blank, pad, tokens, index, last, tok_lprob, count, (hipStream_t)stream, segs, nseg);

@@ -64,6 +64,17 @@ int launch_masked_argmax_lprob(const float* logits, int ld, int M, int N, int ma
 int launch_ctc_collapse_spans(const int* raw, const float* lprob, int T, int blank, int pad, int* tokens, int* index, int* last,
                               float* tok_lprob, int* count, hipStream_t stream, const int* segs = nullptr, int nseg = 0);
 
+// Score of a GIVEN token per logits row (mt_score.hip; fairseq's SequenceScorer on the first-pass text decoder): for row r with
+// target[r] = tk in [0, N): stat[2r] = log_softmax(row)[tk], stat[2r + 1] = the arg-max log-probability, idx[2r] = the arg-max id
+// (lowest index of a tie), idx[2r + 1] = tk's rank (columns above it, plus equal columns below index tk).  log_softmax_kernel's
+// arithmetic, so both values are the bits launch_log_softmax writes at those columns.  tk outside [0, N): the row writes nothing.
+// A row whose values go NaN (a NaN or +inf column, or all -inf): NaN, NaN, -1, -1.  form: 0 = by width, 1 = force the two-read
+// strided form (tests).  M <= MT_SCORE_MAX_ROWS (the grid's x extent times 256 threads stays below 2^32).
+constexpr int MT_SCORE_MAX_ROWS = 16777215;
+constexpr int MT_SCORE_MAX_REG_N = 8192;          // widest row the register form holds (PER = 32)
+int launch_mt_token_scores(const float* logits, int ld, int M, int N, const int* target, float* stat, int* idx, hipStream_t stream,
+                           int form = 0);
+
 // CTC forced alignment of given labels (ctc_align.hip; the plan, its checks and its limits: ctc_align.hpp).  Two launches over a
 // checked plan: per packed frame row the plain log-softmax at the utterance's states (lp, float32, the denominator arithmetic of
 // launch_masked_argmax_lprob), then one workgroup per utterance for the forward sum, the max-plus pass with 2-bit back-pointers, the

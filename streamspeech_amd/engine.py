@@ -562,6 +562,46 @@ class BatchMixin:
             r0 += n
         return out
 
+    def batch_mt_score(self, enc_packed: torch.Tensor, Tp: List[int], tokens: List[List[int]], src: Optional[List[int]] = None,
+                       want_feats: bool = False) -> List[dict]:
+        """How likely the first-pass text decoder finds each GIVEN text, in one ragged teacher-forced pass (ss_batch_mt_score;
+        fairseq's SequenceScorer): row b feeds [</s>, tokens[b]...] (tokens without </s>) over the encoder rows of utterance src[b]
+        of the U = len(Tp) packed utterances (src None: one text per utterance, in order; several rows may name one utterance).
+        -> per row a dict: ``positional_scores`` float32 [n + 1] -- the natural-log probability of tokens[b][p] at position p and of
+        </s> at the last one, under the plain log_softmax (no pad / unk masking) -- ``score`` = their sum / (n + 1) (</s> counted, as
+        SequenceScorer forms it), ``best`` int32 [n + 1] the decoder's own arg-max at every position, ``best_lprob`` float32 [n + 1]
+        its log-probability, ``rank`` int32 [n + 1] the given token's rank (0: the decoder would have chosen it), ``feats``
+        (want_feats) the post-LN decoder states [n + 1, D] on the device, the bits batch_mt_features(..., n_tail_pad = 0) gives, else
+        None.  One device-to-host copy per call.  Rewrites the scratch set's MT cross-attention K/V and workspace, as
+        batch_mt_features does."""
+        U, B = len(Tp), len(tokens)
+        if U == 0 or B == 0 or (src is None and B != U) or (src is not None and len(src) != B):
+            raise ValueError("one text per utterance, or one utterance index per text")
+        n_tok = [len(t) for t in tokens]
+        R = sum(n_tok) + B
+        buf = torch.empty((4 * R,), dtype=torch.float32, device=self.device)      # stat [R][2] | idx [R][2] (int32 bits): one copy
+        d_stat, d_idx = buf[:2 * R], buf[2 * R:]
+        feats, frows = None, 0
+        if want_feats:
+            frows = max(n_tok) + 1
+            feats = torch.empty((B, frows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
+        flat = [int(t) for ts in tokens for t in ts]
+        L.check(self.lib.ss_batch_mt_score(self.h, _stream(), U, _ptr(enc_packed), _i32(Tp), B,
+                                           _i32([int(s) for s in src]) if src is not None else None, _i32(flat or [0]), _i32(n_tok),
+                                           _ptr(feats) if want_feats else None, frows, _ptr(d_stat), _ptr(d_idx)),
+                "ss_batch_mt_score")
+        host = buf.cpu()
+        stat, idx = host[:2 * R].view(R, 2), host[2 * R:].view(torch.int32).view(R, 2)
+        out, r0 = [], 0
+        for b in range(B):
+            n = n_tok[b] + 1
+            pos = stat[r0:r0 + n, 0].contiguous()
+            out.append({"positional_scores": pos, "score": float(pos.double().sum()) / n, "best": idx[r0:r0 + n, 0].contiguous(),
+                        "best_lprob": stat[r0:r0 + n, 1].contiguous(), "rank": idx[r0:r0 + n, 1].contiguous(),
+                        "feats": feats[b, :n] if want_feats else None})
+            r0 += n
+        return out
+
 
 class Scratch:
     """One scratch set (ss_scratch: activations, KV caches, stream-K hand-off state, streaming-encoder state) -- everything a call

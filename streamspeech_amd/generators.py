@@ -208,3 +208,53 @@ class SequenceGenerator:
         if self.want_attention:     # after the loop: the single-utterance MT state is no longer needed
             self._attach_attention(enc, hyp)
         return [[hyp]]
+
+
+class SequenceScorer:
+    """fairseq's ``sequence_scorer.SequenceScorer`` (--score-reference) on the first-pass text decoder: how likely the model finds a
+    GIVEN target, position by position.  ``SequenceScorer(tgt_dict, engine=...)``; ``generate(models, sample)`` takes
+    ``sample["target"]``, a padded int tensor [B, L] whose rows end in </s> (pad is stripped, as fairseq strips it), and the source
+    either as ``sample["encoder_out"]`` -- a list of B encoder outputs as the model wrapper's ``encoder`` returns them -- or as
+    ``sample["net_input"]`` (``src_tokens`` [B, T, 80], ``src_lengths``), encoded through ``models[0].encoder`` one utterance at a
+    time.  -> per sample ``[{"tokens", "score", "attention": None, "alignment": None, "positional_scores"}]``: tokens the target
+    without pad, positional_scores float32 [len] in natural log under the plain log_softmax, score their mean with </s> counted.
+    The B targets are scored in ONE ragged pass (engine.batch_mt_score).  No ensembles: ``models`` holds one model."""
+
+    def __init__(self, tgt_dict, softmax_batch=None, compute_alignment=False, eos=None, symbols_to_strip_from_output=None,
+                 engine=None):
+        if engine is None:
+            raise ValueError("SequenceScorer needs engine= (anything with HipModel.batch_mt_score)")
+        if compute_alignment:
+            raise ValueError("compute_alignment is not supported: SequenceGenerator(want_attention=True) gives alignments")
+        self.tgt_dict, self.engine = tgt_dict, engine
+        self.pad = tgt_dict.pad()
+        self.eos = tgt_dict.eos() if eos is None else eos
+
+    @torch.no_grad()
+    def generate(self, models, sample, **kw):
+        if models is not None and len(models) > 1:
+            raise ValueError("ensembles are not supported")
+        target = sample["target"]
+        B = int(target.size(0))
+        rows = []
+        for b in range(B):
+            t = [int(x) for x in target[b].tolist() if int(x) != self.pad]
+            if not t or t[-1] != self.eos:
+                raise ValueError(f"target row {b} does not end in </s>")
+            rows.append(t)
+        if sample.get("encoder_out") is not None:
+            eos_ = list(sample["encoder_out"])
+        else:
+            ni = sample["net_input"]
+            src, lens = ni["src_tokens"], ni.get("src_lengths")
+            eos_ = [models[0].encoder(src[b:b + 1, :int(lens[b])] if lens is not None else src[b:b + 1]) for b in range(B)]
+        if len(eos_) != B:
+            raise ValueError("one encoder output per target row")
+        encs = []
+        for eo in eos_:
+            enc = eo["encoder_out"][0]
+            encs.append((enc[:, 0] if enc.dim() == 3 else enc).contiguous())
+        packed = encs[0] if B == 1 else torch.cat(encs, 0)
+        res = self.engine.batch_mt_score(packed, [int(e.shape[0]) for e in encs], [t[:-1] for t in rows])
+        return [[{"tokens": torch.tensor(t, dtype=torch.long), "score": r["score"], "attention": None, "alignment": None,
+                  "positional_scores": r["positional_scores"]}] for t, r in zip(rows, res)]

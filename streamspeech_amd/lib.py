@@ -288,6 +288,8 @@ SIGNATURES = {
                                   C.POINTER(C.c_int32), _vp, _i]),
     "ss_batch_mt_attention": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int32), _vp, _i, _vp, C.POINTER(_i64), _i64, _vp, _vp]),
+    "ss_batch_mt_score": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                               C.POINTER(C.c_int32), _vp, _i, _vp, _vp]),
     "ss_batch_vocoder_tail": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int32), _i, _vp, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(_i64), C.POINTER(_i64)]),
@@ -346,6 +348,8 @@ SIGNATURES = {
     "ss_op_masked_argmax": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i]),
     "ss_op_ctc_collapse": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
     "ss_op_masked_argmax_lprob": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ss_op_mt_token_scores": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "ss_debug_mt_score_form": (_i, [_i]),
     "ss_op_ctc_collapse_spans": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "ss_op_ctc_align": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp,
                              _vp, _vp, _vp]),

@@ -29,6 +29,16 @@ and how likely does the model find them.  After the encoder of each batch one fo
 over the rows that have a reference writes generate-<subset>.asr.ref.words / .st.ref.words (the columns of .words) and
 generate-<subset>.ref.scores (`id\thead\tn_tokens\tlog_likelihood\tviterbi_score\tstatus`); every other file is written as without it.
 
+`--score-reference` asks the same of the autoregressive first-pass text decoder -- fairseq's `--score-reference` (SequenceScorer):
+the reference translation of the `target_unigram` multitask manifest is fed teacher-forced (one batch_mt_score per batch, after
+its search and unit pass) and scored position by position under the plain log_softmax.  It writes generate-<subset>.mt.ref.scores
+(`id\tn_tokens\tscore\tsum\taccuracy\tstatus`: n_tokens counts </s>; score = sum / n_tokens as SequenceScorer forms it; accuracy =
+the share of positions the decoder would have chosen itself) and generate-<subset>.mt.ref.words
+(`id\tword\tpieces\tlprob\tconfidence\tmin_lprob\tnot_top`).  Both files are in NATURAL logs (the `H-` / `P-` unit scores of
+--scores are base 2, as fairseq-generate prints them).  `--speak-reference` implies it and also speaks the reference: the scored rows' decoder states go through
+the unit pass and the vocoder (--speaker-id and --dur-prediction honoured) into generate-<subset>.ref.unit and ref_wav/<n>_pred.wav --
+the oracle-text upper bound of the second pass.  Every other file is written as without the flags.
+
 The first-pass text search is greedy by default; `--beam-mt k` runs the reference's beam search (generator_mt with beam_size_mt = k,
 `--unkpen`, `--unnormalized`) on the GPU (ss_batch_mt_beam), and `--beam` is accepted for parity (the CTC unit generator has no search).
 `--no-repeat-ngram-size` and `--lenpen` are that generator's further controls (ss_batch_mt_beam_opts); either off its default runs the
@@ -49,7 +59,7 @@ import torch
 
 from . import frontend
 from .pipeline import units_from_tokens
-from .words import segments_from_spans, spoken_from_segments, words_from_attention, words_from_ctc
+from .words import segments_from_spans, spoken_from_segments, words_from_attention, words_from_ctc, words_from_scores
 
 
 def detok(symbols: Sequence[str]) -> str:
@@ -84,7 +94,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              unk_penalty: float = 0.0, normalize: bool = True, pcm16_out: bool = False, speaker_id: int = -1,
              features: bool = False, word_times: bool = False, mt_alignment: bool = False, len_penalty: float = 1.0,
              temperature: float = 1.0, no_repeat_ngram_size: int = 0,
-             references: Optional[Dict[str, Dict[int, Sequence[int]]]] = None, spoken_words: bool = False) -> Dict[int, Dict]:
+             references: Optional[Dict[str, Dict[int, Sequence[int]]]] = None, spoken_words: bool = False,
+             mt_references: Optional[Dict[int, Sequence[int]]] = None, speak_reference: bool = False) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
@@ -106,10 +117,21 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     each is spoken at in its pred_wav (words.spoken_from_segments; a last `</s>` line holds the speech that belongs to no word, if
     any), from ONE batch_unit_spans call per batch over the arg-max ids of its unit pass and the durations of its vocoder call;
     rows without units get no lines; refused without the vocoder call (dump_wav False); every other file is the one written
-    without it."""
+    without it.
+    mt_references (--score-reference): {sample id: the reference translation as ids of target_unigram, without </s>}.  One
+    batch_mt_score per batch over the rows with a usable reference, after the batch's search and unit pass (it rewrites the MT
+    scratch); writes generate-<subset>.mt.ref.scores (a line per sample: n tokens with </s>, score = sum / n, sum, teacher-forced
+    accuracy, status scored / no_reference / invalid_label / too_long / no_audio) and generate-<subset>.mt.ref.words
+    (words.words_from_scores), both in natural logs, and changes no other file.
+    speak_reference (--speak-reference; needs mt_references): the scored rows' decoder states also go through batch_t2u_units and
+    vocoder.batch_forward (speaker_id and dur_prediction as for the hypotheses) into generate-<subset>.ref.unit and
+    ref_wav/<n>_pred.wav, laid out as .unit and pred_wav/ are (a line / a number per sample id; a sample without spoken reference has
+    an empty line and no file)."""
     from .engine import check_search_options
     if spoken_words and not dump_wav:
         raise ValueError("spoken_words needs the vocoder's durations: it cannot be combined with dump_wav=False (--no-wav)")
+    if speak_reference and mt_references is None:
+        raise ValueError("speak_reference needs the reference translations (mt_references)")
     search = {}
     if check_search_options(len_penalty, temperature, no_repeat_ngram_size) is not None:
         search = {"len_penalty": float(len_penalty), "temperature": float(temperature),
@@ -126,6 +148,7 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     spoken: Dict[int, object] = {}
     ref_words: Dict[str, Dict[int, list]] = {"asr": {}, "st": {}}
     ref_scores: Dict[Tuple[int, str], Tuple[int, float, float, str]] = {}
+    mt_ref: Dict[int, Dict] = {}
     if features:
         for sid, f in items:
             if f.dim() != 2 or f.shape[1] != 80 or f.dtype != torch.float32:
@@ -190,6 +213,9 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
                 for b, (_, peak, prob, _, _) in zip(rows, att):
                     words["mt"][ids[b]] = words_from_attention(mts[b], peak.tolist(), prob.tolist(), dicts["target_unigram"],
                                                                eos=cfg.eos)
+        if mt_references is not None:           # here for the same reason: the pass rewrites the MT scratch of this batch
+            _score_references(model, vocoder, enc, Tp, ids, mt_references, dicts, mt_ref, speak_reference, t2u_causal, dur_prediction,
+                              n_spk, speaker_id)
         have = [b for b, c in enumerate(codes) if len(c) > 0]
         wavs: Dict[int, torch.Tensor] = {}
         if dump_wav and have:
@@ -270,6 +296,29 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
             for sid in sorted(words["mt"]):
                 for w in words["mt"][sid]:
                     print(f"{sid}\t{w.text}\t{w.start_ms}\t{w.end_ms}\t{w.focus:.6g}", file=f)
+    if mt_references is not None:
+        nan = float("nan")
+        with open(os.path.join(results_path, f"generate-{subset}.mt.ref.scores"), "w", encoding="utf-8") as f:
+            for sid, _ in items:
+                ref = mt_references.get(sid)
+                r = mt_ref.get(sid) or {"n": 0 if ref is None else len(ref) + 1, "score": nan, "sum": nan, "accuracy": nan,
+                                        "status": "no_reference" if ref is None else "no_audio"}
+                print(f"{sid}\t{r['n']}\t{r['score']:.6f}\t{r['sum']:.6f}\t{r['accuracy']:.6f}\t{r['status']}", file=f)
+        with open(os.path.join(results_path, f"generate-{subset}.mt.ref.words"), "w", encoding="utf-8") as f:
+            for sid in sorted(mt_ref):
+                for w in mt_ref[sid].get("words", ()):
+                    print(f"{sid}\t{w.text}\t{w.pieces}\t{w.lprob:.6f}\t{w.confidence:.6g}\t{w.min_lprob:.6f}\t{w.not_top}", file=f)
+        if speak_reference:
+            ids_all = sorted(hyps)              # the lines of .unit and the numbers of pred_wav/ (_cut_files)
+            with open(os.path.join(results_path, f"generate-{subset}.ref.unit"), "w", encoding="utf-8") as f:
+                for i in ids_all:
+                    print(" ".join(str(u) for u in mt_ref.get(i, {}).get("units", ())), file=f)
+            wdir = os.path.join(results_path, "ref_wav")
+            os.makedirs(wdir, exist_ok=True)
+            for k, i in enumerate(ids_all):
+                w = mt_ref.get(i, {}).get("wav")
+                if w is not None:
+                    frontend.write_wav(os.path.join(wdir, f"{k}_pred.wav"), w.detach().cpu().numpy(), 16000)
     return hyps
 
 
@@ -306,6 +355,58 @@ def _align_references(model, enc, Tp, ids, references, dicts, ref_words, ref_sco
             ref_scores[(ids[b], key)] = (len(y), a.score, a.viterbi_score, ALIGN_STATUS[a.status])
             if a.status == 0:
                 ref_words[key][ids[b]] = words_from_ctc(y, a.first, a.last, a.tok_lprob, dicts[name], finished=True)
+
+
+def _score_references(model, vocoder, enc, Tp, ids, mt_references, dicts, mt_ref, speak, t2u_causal, dur_prediction, n_spk,
+                      speaker_id):
+    """One batch_mt_score over the rows of this batch that have a usable reference translation; with `speak` their decoder states go
+    on through the unit pass and the vocoder.  A reference the library would refuse the whole call for (an id outside the
+    dictionary, <pad>; more positions than the decoder has) is recorded and left out."""
+    cfg = model.cfg
+    nan = float("nan")
+    max_pos = int(getattr(model, "max_tgt_pos", cfg.max_target_positions + 2))
+    off = [0]
+    for t in Tp:
+        off.append(off[-1] + int(t))
+    rows = []
+    for b, sid in enumerate(ids):
+        if sid not in mt_references:
+            continue
+        y = [int(v) for v in mt_references[sid]]
+        bad = {"n": len(y) + 1, "score": nan, "sum": nan, "accuracy": nan}
+        if any(v < 0 or v >= cfg.tgt_vocab or v == cfg.pad for v in y):
+            mt_ref[sid] = dict(bad, status="invalid_label")
+        elif len(y) + 3 > max_pos:              # the library's position bound: 1 + n fed positions + 2
+            mt_ref[sid] = dict(bad, status="too_long")
+        else:
+            rows.append((b, y))
+    if not rows:
+        return
+    enc_r = enc if len(rows) == len(ids) else torch.cat([enc[off[b]:off[b + 1]] for b, _ in rows], 0).contiguous()
+    got = model.batch_mt_score(enc_r, [Tp[b] for b, _ in rows], [y for _, y in rows], want_feats=speak)
+    for (b, y), r in zip(rows, got):
+        pos, rank = r["positional_scores"].tolist(), r["rank"].tolist()
+        total = math.fsum(pos)
+        mt_ref[ids[b]] = {"n": len(pos), "score": total / len(pos), "sum": total,
+                          "accuracy": sum(1 for k in rank if k == 0) / len(rank), "status": "scored",
+                          "words": words_from_scores(y + [cfg.eos], pos, rank, dicts["target_unigram"], eos=cfg.eos)}
+    if not speak:
+        return
+    n = [len(y) + 1 for _, y in rows]
+    feats = torch.nn.utils.rnn.pad_sequence([r["feats"] for r in got], batch_first=True).contiguous()
+    codes = [units_from_tokens(t, cfg) for t in model.batch_t2u_units(feats, n, t2u_causal=t2u_causal, mask_eos=True)]
+    for (b, _), c in zip(rows, codes):
+        mt_ref[ids[b]]["units"] = c
+    have = [j for j, c in enumerate(codes) if len(c) > 0]
+    if not have:
+        return
+    spk = {}
+    if n_spk:                                   # -1: a voice per sample from a generator of its own, seeded by the sample id -- the
+        spk["speakers"] = [speaker_id if speaker_id >= 0 else random.Random(ids[rows[j][0]]).randint(0, n_spk - 1)
+                           for j in have]       # hypotheses' draws (and so pred_wav/ and the log) stay what they are without the flag
+    w, _, _ = vocoder.batch_forward([codes[j] for j in have], dur_prediction=dur_prediction, **spk)
+    for k, j in enumerate(have):
+        mt_ref[ids[rows[j][0]]]["wav"] = w[k]
 
 
 def multitask_text_dir(data_root: str, multitask_yaml: Optional[str], task: str) -> Optional[str]:
@@ -368,6 +469,18 @@ def load_references(data_root: str, multitask_yaml: Optional[str], subset: str, 
         text = load_multitask_text(dirs[key], subset)
         out[key] = {i: [dicts[name].index(p) for p in text[n]] for i, n in names.items() if n in text}
     return out
+
+
+def load_mt_references(data_root: str, multitask_yaml: Optional[str], subset: str, dicts) -> Optional[Dict[int, List[int]]]:
+    """--score-reference: the reference translation per sample id as ids of `target_unigram` (without </s>), from that task's
+    multitask manifest joined with the manifest's `id` column; a piece the dictionary does not hold becomes <unk>.  None when the
+    YAML names no data directory for the task."""
+    directory = multitask_text_dir(data_root, multitask_yaml, "target_unigram")
+    if directory is None:
+        return None
+    names = load_manifest_ids(os.path.join(data_root, subset + ".tsv"))
+    text = load_multitask_text(directory, subset)
+    return {i: [dicts["target_unigram"].index(p) for p in text[n]] for i, n in names.items() if n in text}
 
 
 def _pack_batch(model, wavs: List[torch.Tensor]):
@@ -501,6 +614,14 @@ def build_parser() -> argparse.ArgumentParser:
                          "and ctc_target_unigram) to the audio on both CTC heads: writes generate-<subset>.asr.ref.words / .st.ref.words "
                          "(id, word, start_ms, end_ms, confidence) and generate-<subset>.ref.scores (id, head, n_tokens, log_likelihood, "
                          "viterbi_score, status); needs a manifest")
+    ap.add_argument("--score-reference", action="store_true",
+                    help="also score the recipe's reference translation (the multitask manifest <task data>/<gen-subset>.tsv of "
+                         "target_unigram) with the first-pass text decoder, teacher-forced, as fairseq's --score-reference does: writes "
+                         "generate-<subset>.mt.ref.scores (id, n_tokens, score, sum, accuracy, status) and generate-<subset>.mt.ref.words "
+                         "(id, word, pieces, lprob, confidence, min_lprob, not_top), natural logs; needs a manifest")
+    ap.add_argument("--speak-reference", action="store_true",
+                    help="implies --score-reference; also speaks the reference translation through the unit pass and the vocoder: "
+                         "writes generate-<subset>.ref.unit and ref_wav/<n>_pred.wav (the second pass on oracle text)")
     ap.add_argument("--num-shards", type=int, default=int(os.environ.get("WORLD_SIZE", "1")))
     ap.add_argument("--shard-id", type=int, default=int(os.environ.get("RANK", "0")))
     ap.add_argument("--device", default="cuda:%s" % os.environ.get("LOCAL_RANK", "0"))
@@ -539,6 +660,15 @@ def main(argv: Optional[List[str]] = None):
         ap.error("--align-reference needs the manifest's ids: it cannot be combined with --wav-list or --synthetic")
     if a.align_reference and not any(multitask_text_dir(a.data, a.multitask_config_yaml, t) for t in ("source_unigram", "ctc_target_unigram")):
         ap.error("--align-reference: the multitask YAML names no `data:` directory for source_unigram or ctc_target_unigram")
+
+    if a.speak_reference:
+        a.score_reference = True
+    if a.score_reference and (a.wav_list or a.synthetic > 0 or not a.data):
+        ap.error("--score-reference needs the manifest's ids: it cannot be combined with --wav-list or --synthetic")
+    if a.score_reference and not multitask_text_dir(a.data, a.multitask_config_yaml, "target_unigram"):
+        ap.error("--score-reference: the multitask YAML names no `data:` directory for target_unigram")
+    if a.speak_reference and a.no_wav:
+        ap.error("--speak-reference runs the vocoder: it cannot be combined with --no-wav")
 
     # model / dictionaries / CMVN exactly as the agent loads them (agent :355-420)
     ns = argparse.Namespace(config_yaml=a.config_yaml, multitask_config_yaml=a.multitask_config_yaml,
@@ -620,6 +750,7 @@ def main(argv: Optional[List[str]] = None):
             pcm = model.resample(pcm, e[2], 16000)
         items.append((e[0], pcm))
     references = load_references(a.data, a.multitask_config_yaml, a.gen_subset, holder.dict) if a.align_reference else None
+    mt_references = load_mt_references(a.data, a.multitask_config_yaml, a.gen_subset, holder.dict) if a.score_reference else None
     sub = a.gen_subset if a.num_shards == 1 else f"{a.gen_subset}.shard{a.shard_id}"
     hyps = generate(model, voc, items, holder.dict, a.results_path, sub, a.batch_size, a.max_tokens, a.max_len_a,
                     a.max_len_b, a.max_len_a_mt, a.max_len_b_mt, a.dur_prediction, not a.no_wav,
@@ -629,6 +760,8 @@ def main(argv: Optional[List[str]] = None):
                     **({"features": True} if is_feat else {}), **({"word_times": True} if a.word_times else {}),
                     **({"mt_alignment": True} if a.mt_alignment else {}), **({"spoken_words": True} if a.spoken_words else {}),
                     **({"references": references} if references is not None else {}),
+                    **({"mt_references": mt_references} if mt_references is not None else {}),
+                    **({"speak_reference": True} if a.speak_reference else {}),
                     **({"len_penalty": a.lenpen, "no_repeat_ngram_size": a.no_repeat_ngram_size}
                        if (a.lenpen, a.no_repeat_ngram_size) != (1.0, 0) else {}))
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)

@@ -11,6 +11,9 @@ Spoken: where each word of the text decoder's tokens lies in the OUTPUT speech -
 of the writes (HipModel.batch_unit_spans: the unit decoder upsamples every decoder state into ctc_upsample CTC positions, the
 duration predictor gives every unit whole 20-ms frames, so the times are exact integers).
 
+Scored: the words of a GIVEN text with the log-probabilities the text decoder gives its pieces (HipModel.batch_mt_score) --
+:func:`words_from_scores`.
+
 Host-side glue: no device work here.
 """
 import math
@@ -98,7 +101,41 @@ def words_from_attention(tokens: Sequence[int], peak: Sequence[int], peak_prob: 
     return words
 
 
-UNIT_FRAME_MS = 20         # one vocoder frame: 320 samples at 16 kHz
+class ScoredWord(NamedTuple):
+    text: str               # the word's subwords joined, boundary mark removed
+    pieces: int             # its subwords
+    lprob: float            # the sum of their log-probabilities (natural log)
+    confidence: float       # exp(lprob / pieces): the geometric mean of their probabilities
+    min_lprob: float        # the least likely subword's log-probability
+    not_top: int            # subwords the decoder would not have chosen itself (rank > 0)
+
+
+def words_from_scores(tokens: Sequence[int], positional: Sequence[float], rank: Sequence[int], symbols,
+                      eos: Optional[int] = None) -> List[ScoredWord]:
+    """Group the tokens of a SCORED text (HipModel.batch_mt_score: positional[p] the natural-log probability of tokens[p], rank[p]
+    its rank among the vocabulary) into words.  Grouping and the ``</s>`` rule as :func:`words_from_attention`."""
+    n = len(tokens)
+    if not (len(positional) == len(rank) == n):
+        raise ValueError("tokens, positional and rank must have one entry per token")
+    groups: List[List[int]] = []
+    for j in range(n):
+        t = int(tokens[j])
+        if (t == int(eos)) if eos is not None else (str(symbols[t]) == "</s>"):
+            continue
+        if not groups or str(symbols[t]).startswith(WORD_START):
+            groups.append([])
+        groups[-1].append(j)
+    words = []
+    for g in groups:
+        text = "".join(str(symbols[int(tokens[j])]) for j in g).replace(WORD_START, "")
+        lps = [float(positional[j]) for j in g]
+        lp = math.fsum(lps)
+        conf = math.exp(lp / len(g)) if lp == lp else float("nan")
+        words.append(ScoredWord(text, len(g), lp, conf, min(lps), sum(1 for j in g if int(rank[j]) > 0)))
+    return words
+
+
+UNIT_FRAME_MS = 20        # one vocoder frame: 320 samples at 16 kHz
 
 
 class SpokenWord(NamedTuple):
