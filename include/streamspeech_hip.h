@@ -1091,6 +1091,15 @@ int ss_debug_ffn(int grid, int row_tiles_per_wave, int enable);
  * ss_op_conv_gemm / the model entry points): grid > 0 fixes its workgroup count (0: heuristic); enable 0 / 1 routes those linears
  * back to the LDS-tiled kernel / to it (-1: keep). */
 int ss_debug_rtlin(int grid, int enable);
+/* Test hook of the k-blocked row-tile kernel's forms (rt_linear_kb in csrc/rtlin.hip: K = 512 ... 8192 linears of the pack-invariant
+ * mode).  uw: 16-column units per wave, 0 = by the launch's unit count, 1 / 2 / 4 force.  order: -1 keep, 0 every workgroup walks a
+ * contiguous range of (row tile, column group) units, 1 the launcher's own choice, 2 the XCD-aware order -- also under a forced grid
+ * (ss_debug_rtlin(grid, 1)); a launch whose grid G and column groups per tile NCG do not meet that order's conditions (G % 8 == 0,
+ * (G / 8) % NCG == 0) then returns SS_ERR_ARG and launches nothing.  Under order 0 or 2 a forced grid is used as given, not clamped
+ * to the unit count: the workgroups past the last unit do nothing.  Every form gives the same bits.  Other values: SS_ERR_ARG. */
+int ss_debug_rtlin_kb(int uw, int order);
+/* {UW, NCG, G, xmap} of the calling process's last rt_linear_kb launch (xmap: 1 = the XCD-aware order ran); zeros before the first. */
+int ss_debug_rtlin_kb_last(int32_t out[4]);
 /* A/B hook of the 64-channel vocoder-stage kernel (csrc/conv_c64.hip): 0 routes that stage's convs back to the stream-K kernel
  * with pre-activated twin tensors (round 3), 1 to it, -1 keeps the setting; 4 / 5 switch the Winograd F(2,3) form of those convs
  * (csrc/conv_c64w.hip) off / on without touching the first setting; 6 / 7 route the 128-channel stage's ResBlock convs to conv_sk2<128>

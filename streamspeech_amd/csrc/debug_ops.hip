@@ -194,6 +194,18 @@ extern "C" int ss_debug_rtlin(int grid, int enable) {
   rtlin_debug(grid, enable);
   return SS_OK;
 }
+extern "C" int ss_debug_rtlin_kb(int uw, int order) {
+  if (!(uw == 0 || uw == 1 || uw == 2 || uw == 4) || order < -1 || order > 2) return SS_ERR_ARG;
+  rtlin_kb_debug(uw, order);
+  return SS_OK;
+}
+extern "C" int ss_debug_rtlin_kb_last(int32_t out[4]) {
+  if (!out) return SS_ERR_ARG;
+  int v[4];
+  rtlin_kb_last(v);
+  for (int i = 0; i < 4; ++i) out[i] = v[i];
+  return SS_OK;
+}
 extern "C" int ss_debug_ffn(int grid, int row_tiles_per_wave, int enable) {
   if (grid < 0 || row_tiles_per_wave < -1 || row_tiles_per_wave > 4) return SS_ERR_ARG;     // row tiles: 1..4 force, 0 process default, -1 keep
   ffn_fused_debug_grid(grid);

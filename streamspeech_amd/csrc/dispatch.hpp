@@ -53,7 +53,8 @@ struct Dispatch {
   int rt_wg_per_cu = 0;                                // SS_RTLIN_WG_PER_CU: resident rt_linear workgroups per CU (0: by the launch's unit count)
   long long rt_kb_min_units = 256;                     // SS_RTLIN_KB_MIN_UNITS: (48-row tile, 64-column group) units from which rt_linear_kb takes a K > 256 linear
   int rt_kb_xmap = 1;                                  // SS_RTLIN_KB_XMAP: 0 = every workgroup walks a contiguous (tile, column group) range; 1 = the column groups of a row tile run side by side on one XCD
-  int rt_kb_uw = 0;                                    // SS_RTLIN_KB_UW: 16-column units per wave and column group (0: by the launch's unit count; 1 / 2 / 4 force)
+  int rt_kb_uw = 0;                                    // SS_RTLIN_KB_UW / ss_debug_rtlin_kb: 16-column units per wave and column group (0: by the launch's unit count; 1 / 2 / 4 force)
+  int rt_kb_order = 1;                                 // test hook (ss_debug_rtlin_kb): 0 contiguous unit ranges, 1 by the launch (rt_kb_xmap and its conditions), 2 the XCD-aware order or SS_ERR_ARG
 };
 
 // The calling thread's settings: the scoped context's private copy, else this thread's own copy of the process settings.

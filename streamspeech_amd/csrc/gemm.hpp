@@ -247,6 +247,10 @@ void rtlin_debug(int grid, int enable);   // tests / A-B: fixed workgroup count 
 bool rtlin_kb_shape_ok(const GemmArgs& a);
 bool rtlin_kb_eligible(const GemmArgs& a);
 int launch_rtlin_kb(const GemmArgs& a, hipStream_t stream);
+// tests: uw 0 (heuristic) / 1 / 2 / 4 units per wave; order -1 keep, 0 contiguous, 1 heuristic, 2 the XCD-aware order (a launch whose
+// grid cannot take it is SS_ERR_ARG); under a forced order a forced grid is used as given, not clamped to the unit count
+void rtlin_kb_debug(int uw, int order);
+void rtlin_kb_last(int out[4]);           // {UW, NCG, G, xmap} of this process's last rt_linear_kb launch (zeros before the first)
 
 // Fused Conformer feed-forward module (ffn.hip): Y = X + alpha * (W2 . SiLU(W1 . LayerNorm(X) + b1) + b2), optionally followed by
 // LayerNorm(ln2) over the result rows; one persistent launch, hidden activations stay in registers.  D = 256, F % 64 == 0.

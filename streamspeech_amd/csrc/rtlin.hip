@@ -21,6 +21,7 @@
 #include "gemm.hpp"
 
 #include <cstdlib>
+#include <mutex>
 
 #ifndef RT_FENCE
 #define RT_FENCE 1      // see ffn.hip: without a fence per step hipcc sinks every weight load to just before its use
@@ -494,6 +495,15 @@ int launch_rtlin(const GemmArgs& a, hipStream_t stream) {
 
 
 // ---- K > 256 (rt_linear_kb_kernel) ----
+// Test hook of the kernel's forms (tests/test_rtlin_kb_gpu.py) and the form the process's last launch took
+static std::mutex g_kb_last_mu;
+static int g_kb_last[4] = {0, 0, 0, 0};          // {UW, NCG, G, xmap}
+void rtlin_kb_debug(int uw, int order) { dispatch_edit([uw, order](Dispatch& d) { d.rt_kb_uw = uw; if (order >= 0) d.rt_kb_order = order; }); }
+void rtlin_kb_last(int out[4]) {
+  std::lock_guard<std::mutex> lk(g_kb_last_mu);
+  for (int i = 0; i < 4; ++i) out[i] = g_kb_last[i];
+}
+
 bool rtlin_kb_shape_ok(const GemmArgs& a) {
   return a.taps == 1 && a.stride == 1 && a.pad == 0 && a.Cin > RT_K && a.Cin % RT_K == 0 && a.Cin <= 8192 && a.chunk == 0 &&
          a.in_act == ACT_NONE && !a.R2 && !a.C2 && a.div == 0.f && !a.ln_out && !a.ln_g && !a.x3 && !a.glu && a.N % 256 == 0 && a.M >= 1 &&
@@ -529,13 +539,26 @@ int launch_rtlin_kb(const GemmArgs& a, hipStream_t stream) {
   q.NCG = a.N / (64 * uw);
   const long long U = (long long)cdiv(a.M, RT_BM) * q.NCG;
   long long G = disp().rt_force_g > 0 ? disp().rt_force_g : 3LL * cus;
-  if (G > U) G = U;
-  if (G < 1) G = 1;
+  const int order = disp().rt_kb_order;
+  if (order == 2) {
+    // test hook: the XCD-aware order at any shape, the grid as it stands (workgroups whose first tile lies past the last one have
+    // nit = 0); the kernel's own conditions, or no launch at all
+    if ((G & 7) != 0 || ((G >> 3) % q.NCG) != 0) return SS_ERR_ARG;
+    q.xmap = 1;
+  } else {
+    if (G > U && !(order == 0 && disp().rt_force_g > 0)) G = U;      // (a forced grid under the forced contiguous order: as given -- the workgroups past the last unit get an empty range)
+    if (G < 1) G = 1;
+    q.xmap = (order == 1 && disp().rt_kb_xmap && disp().rt_force_g <= 0 && G == 3LL * cus && (cus & 7) == 0 && ((G >> 3) % q.NCG) == 0 &&
+              U >= 2 * G) ? 1 : 0;
+  }
   q.G = (int)G;
-  q.xmap = (disp().rt_kb_xmap && disp().rt_force_g <= 0 && G == 3LL * cus && (cus & 7) == 0 && ((G >> 3) % q.NCG) == 0 && U >= 2 * G) ? 1 : 0;
   ProfRec rec{}; bool prof = false;
   int rc = prof_begin(a, stream, PROF_RTLIN_KB, rec, prof);
   if (rc != SS_OK) return rc;
+  {
+    std::lock_guard<std::mutex> lk(g_kb_last_mu);
+    g_kb_last[0] = uw; g_kb_last[1] = q.NCG; g_kb_last[2] = q.G; g_kb_last[3] = q.xmap;
+  }
   if (uw == 1) {
     SS_MAX_LDS_ONCE((&rt_linear_kb_kernel<1>), RT_LDS);
     hipLaunchKernelGGL(rt_linear_kb_kernel<1>, dim3((unsigned)G), dim3(256), RT_LDS, stream, q);

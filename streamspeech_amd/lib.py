@@ -313,6 +313,8 @@ SIGNATURES = {
     "ss_op_ffn_fused": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i]),
     "ss_debug_ffn": (_i, [_i, _i, _i]),
     "ss_debug_rtlin": (_i, [_i, _i]),
+    "ss_debug_rtlin_kb": (_i, [_i, _i]),
+    "ss_debug_rtlin_kb_last": (_i, [C.POINTER(C.c_int32)]),
     "ss_debug_conv_c64": (_i, [_i]),
     "ss_debug_conv_c256_rows": (_i, [_i]),
     "ss_debug_conv_c32": (_i, [_i]),

@@ -1,7 +1,8 @@
 """Op-level tests of the three kernels of csrc/gemm.hip -- gemv_kernel, smallm_gemm_kernel and the LDS-tiled conv_gemm_kernel in its
 default and CANON_SEQ (BLK) forms -- route by route against tests/gemm_ref.py (float64), through ss_op_ln_linear_ex, ss_op_conv_gemm_ex
-and ss_op_conv_gemm_rows.  The routes with a test file of their own (rt_linear*, ffn_fused, stream-K, the slab / Winograd / FP16 convs,
-m_begin / seg_mb) and the hook-only tuning tiles are not launched here.
+and ss_op_conv_gemm_rows.  The routes with a test file of their own (rt_linear: tests/test_rtlin_gpu.py, rt_linear_kb:
+tests/test_rtlin_kb_gpu.py -- both on this file's launch(); ffn_fused, stream-K, the slab / Winograd / FP16 convs, m_begin / seg_mb) and
+the hook-only tuning tiles are not launched here.
 
 The harness is that of tests/test_slab_ops_gpu.py.  Every launch of this file:
   * inputs sit between guard rows of 1e4 and padded input columns hold 1e4, so a row or column read from outside is no small error;
@@ -84,11 +85,14 @@ def untouched(buf, mask=None):
 def launch(lib, cls, what, worst, *, M=None, N, Cin, taps=1, dil=1, stride=1, pad=0, in_len=None, chunk=0, in_act=NONE, ln=False,
            ln_out=False, bias=True, act=NONE, act_slope=0.1, alpha=1.0, R=False, R2=False, div=0.0, C2=False, c2_slope=0.1, glu=0,
            lda=None, ldc=None, ldr=None, ldr2=None, ldc2=None, segs=None, canon=0, entry="conv", inplace=False, seed=0, mean=0.0,
-           tol=TOL, W=None, b=None, expect_rc=0):
+           tol=TOL, W=None, b=None, expect_rc=0, rows=None, refs=None):
     """One launch with everything the module docstring promises checked; returns the host copies (C, C2, ln_out) and the error.
     entry "lin": ss_op_ln_linear_ex (a linear, same_rows = 1 as ln_linear() of the model sets it); "conv": ss_op_conv_gemm_ex, or
     ss_op_conv_gemm_rows when canon is set (same_rows = 0: no slab / stream-K kernel is eligible).  segs: [(out_start, out_len,
-    in_start, in_len)], M / in_len then the packed totals.  expect_rc = SS_ERR_ARG: the refusal -- census unchanged, nothing written."""
+    in_start, in_len)], M / in_len then the packed totals.  expect_rc = SS_ERR_ARG: the refusal -- census unchanged, nothing written.
+    rows (a plain linear only): the row indices the float64 oracle is computed on, for launches whose whole reference would take the
+    host many seconds; every other check still covers every element.  refs: a dict that keeps the float64 reference (and x, w) of the
+    first launch it is passed to for the later ones -- the same arguments on another kernel."""
     from streamspeech_amd.lib import SSOpConvArgs
     nout = N // 2 if glu else N
     if segs is not None:
@@ -155,13 +159,28 @@ def launch(lib, cls, what, worst, *, M=None, N, Cin, taps=1, dil=1, stride=1, pa
     kw = dict(taps=taps, dil=dil, stride=stride, pad=pad, chunk=chunk, in_slope=0.1 if in_act == LRELU else None, act=act,
               act_slope=act_slope, alpha=alpha, div=div, glu=bool(glu), c2_slope=c2_slope)
 
+    if rows is not None:
+        assert taps == 1 and stride == 1 and pad == 0 and chunk == 0 and segs is None and in_len == M and not C2 and not ln_out
+        assert rows.dtype == torch.long and rows.numel() > 0 and int(rows.min()) >= 0 and int(rows.max()) < M
+
     def reference(dt):
         f = lambda t: None if t is None else t.to(dt)
+        if rows is not None:
+            pick = lambda t: None if t is None else f(t[rows])
+            return G.gemm(pick(x), f(w), ln=(f(g), f(bt)) if ln else None, bias=f(bv), R=pick(r1), R2=pick(r2), **kw)
         return G.gemm(f(x), f(w), M=None if segs is not None else M, in_len=None if segs is not None else in_len,
                       ln=(f(g), f(bt)) if ln else None, bias=f(bv), R=f(r1), R2=f(r2), segs=segs, out_rows=M, **kw)
-    ref, ref2 = reference(torch.float64)
+    if refs is not None and "ref" in refs:
+        ref, ref2 = refs["ref"]
+    else:
+        ref, ref2 = reference(torch.float64)
+        if refs is not None:
+            refs.update(ref=(ref, ref2), x=x, w=w)
     assert torch.isfinite(out[written]).all(), f"{what}: not finite where the op writes"
-    err = (out[:M, :nout].double() - ref)[written[:M, :nout]].abs().max().item() if written.any() else 0.0
+    if rows is not None:
+        err = (out[rows][:, :nout].double() - ref).abs().max().item()
+    else:
+        err = (out[:M, :nout].double() - ref)[written[:M, :nout]].abs().max().item() if written.any() else 0.0
     line = f"{worst.route} | {what}: max abs err {err:.3e}"
     if tol == "f32 chain":      # a measured bound: 4 x the error of the plain float32 chain (two-pass LayerNorm + matmul on the host)
         chain = (reference(torch.float32)[0].double() - ref).abs().max().item()
