@@ -904,6 +904,53 @@ int ss_batch_mt_beam_continue_plan_opts(int B, int beam, const int32_t* h_Tp, co
                                         const int32_t* h_max_len, int min_len, int out_stride, int feat_rows, int max_tgt_pos,
                                         int vocab, int eos, int pad, int32_t* h_dims, int32_t* h_tables, int64_t tables_cap,
                                         int64_t* h_n_tables, const ss_mt_search_opts* opts);
+/* Sampling from the first-pass text decoder: the reference generator's --sampling, --sampling-topk, --sampling-topp and --seed
+ * (fairseq/fairseq/search.py::Sampling).  size = sizeof(ss_mt_sample_opts) of the caller, versioned as ss_mt_search_opts is.
+ *
+ * THE RULE.  A call has B utterances with k chains each (1 <= k <= 32, B * k <= 256), a 64-bit seed, one caller-given 64-bit key[b]
+ * per utterance, the masks and options of the beam search, topk (0 = off) or topp (0 = off, else in (0, 1]), and optionally a forced
+ * prefix per utterance.  Chain j of utterance b is an independent ancestral sample.  At reference step `step` (the prefix counts,
+ * as in the beam search) the row's candidate values v[n] are those of the beam search's top-2k kernel, in this order: the float32
+ * division of the logits by the temperature; the log-softmax numerics of the log-softmax kernel; the masks in the reference's
+ * order (NaN, pad, unk penalty, max_len, min_len, the no-repeat ban).  The cumulative score is NOT added to v[n].  At the first
+ * free step all k chains draw from the row of slot 0 (lprobs[:, ::beam_size] of Sampling.step).
+ *   Kept set.  topk = K keeps the K largest v[n], ties to the lower id (exact, no arithmetic).  topp = P follows _sample_topp:
+ *     order the tokens by v descending, ties to the lower id; with p[n] = exp(v[n]) a token is kept while the running mass BEFORE it
+ *     is < P, so the token that crosses P is included.  With neither, every token with v > -inf is kept.  A -inf token is never
+ *     kept; a row at max_len keeps </s> alone.
+ *   Draw.  u = (x >> 8) * 2^-24 with x = word 0 of Philox4x32-10 at counter (step, j, key_lo, key_hi) and key (seed_lo, seed_hi)
+ *     (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85).  The token is the first kept id, in ascending id
+ *     order, whose cumulative kept mass exceeds u * Z, Z the kept mass.  The sums are one fixed-order scan per row: no float
+ *     atomics, so two runs and two packs give the same bits.
+ *   Scores.  The positional score is v[token], the un-renormalised log-probability (scores_buf of Sampling.step); the cumulative
+ *     score is the in-order float32 sum of the positional scores (on top of the prefix' sum).  A chain that draws </s> is finalised
+ *     and ignored afterwards (cands_to_ignore); its score is cum / (step + 1) ** len_penalty under normalize, formed as the beam
+ *     search forms it.  The utterance is done when all k chains are finalised.  Output entries are ordered by final score
+ *     descending, ties by chain index; d_feats receives the states of entry 0.
+ * The random stream is this library's own; the kept sets, the scores and the distribution are the reference's. */
+typedef struct ss_mt_sample_opts {
+  int32_t size;
+  int32_t topk;        /* 0 = off, else 1 .. tgt_vocab */
+  float topp;          /* 0 = off, else in (0, 1] */
+  int32_t reserved;
+  uint64_t seed;
+} ss_mt_sample_opts;
+/* ss_batch_mt_beam_opts' argument list with `beam` read as the number of chains k, plus h_keys [B] and the sampling options; opts
+ * (search options) may be NULL.  Refusals, before anything is launched and in this order, all SS_ERR_ARG: sample NULL or
+ * sample->size < sizeof(ss_mt_sample_opts); topk < 0; topp not finite or outside {0} u (0, 1]; topk and topp both set (the
+ * reference silently prefers top-p); h_keys NULL; m NULL; topk > tgt_vocab.  Then the checks of ss_batch_mt_beam_opts in their
+ * order.  Every utterance returns exactly k entries. */
+int ss_batch_mt_sample(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                       const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens, int out_stride,
+                       int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows,
+                       const ss_mt_search_opts* opts, const int64_t* h_keys, const ss_mt_sample_opts* sample);
+/* The same behind a forced prefix per utterance: ss_batch_mt_beam_continue_opts' argument list, h_keys and the sampling options.
+ * The refusals of ss_batch_mt_sample first, then those of ss_batch_mt_beam_continue_opts in their order. */
+int ss_batch_mt_sample_continue(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                                const int32_t* h_prefix, const int32_t* h_n_prefix, const int32_t* h_max_len, int min_len,
+                                float unk_penalty, int normalize, int32_t* h_out_tokens, int out_stride, int32_t* h_n_out,
+                                float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows, const ss_mt_search_opts* opts,
+                                const int64_t* h_keys, const ss_mt_sample_opts* sample);
 /* New fbank rows of B streaming sessions in one launch: session b's frames h_first[b] .. h_first[b] + h_n[b] - 1 of its own 16-kHz
  * sample history h_pcm[b] (device; frame i reads samples 160 i .. 160 i + 399) go to h_feat[b] (device, h_n[b] rows of 80).  The
  * same bits as ss_fbank_cmvn's rows.  h_n[b] = 0 skips a session.  1 <= B <= 65535. */
@@ -1397,6 +1444,20 @@ int ss_op_beam_merge_opts(void* stream, const ss_op_beam_state* st, int B, int k
  * launches. */
 int ss_op_beam_prefix_score_opts(void* stream, const float* logits, int rows, int V, const int32_t* ftok, int pad, int unk,
                                  float unk_pen, float* lp, float temperature);
+/* sample_step_kernel for one step (the rule: ss_mt_sample_opts).  Every row is an utterance of its own with one chain: logits
+ * [R][V], max_len / npre [R], the chain index row_j [R] and the key keys [R] of each row (all DEVICE pointers), the mask and ban
+ * arguments of ss_op_beam_topk_opts (tok [t_step + 1][R], anc [R][Lc]).  -> per row the drawn token, its positional score v[token],
+ * the uniform u and the size of the kept set.  1 <= V <= 16384; the refusals of ss_batch_mt_sample's options, then the
+ * temperature's and the ban's as in ss_op_beam_topk_opts. */
+int ss_op_sample_step(void* stream, const float* logits, int R, int V, int t_step, int min_len, const int32_t* max_len,
+                      const int32_t* npre, int pad, int unk, int eos, float unk_pen, float temperature, int no_repeat_ngram,
+                      const int32_t* tok, const int32_t* anc, int Lc, int c0, const int32_t* ptok, const int32_t* row0,
+                      const int32_t* row_j, const int64_t* keys, const ss_mt_sample_opts* sample, int32_t* out_tok, float* out_score,
+                      float* out_u, int32_t* out_kept);
+/* The uniforms of the rule, n at once (all DEVICE pointers): seed / key [n] 64-bit, step / j [n] -> u [n] and the four Philox words
+ * [n][4] of counter (step, j, key_lo, key_hi) under key (seed_lo, seed_hi). */
+int ss_op_sample_uniform(void* stream, int n, const uint64_t* seed, const int64_t* key, const int32_t* step, const int32_t* j,
+                         float* u, uint32_t* words);
 
 #ifdef __cplusplus
 }

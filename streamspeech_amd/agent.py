@@ -119,9 +119,28 @@ def _search_kwargs(args) -> dict:
     return {"len_penalty": p, "temperature": t, "no_repeat_ngram_size": n}
 
 
+def _sampling_kwargs(args) -> dict:
+    """--sampling / --sampling-topk / --sampling-topp / --seed as generators.SequenceGenerator takes them; nothing without --sampling."""
+    if not getattr(args, "sampling", False):
+        return {}
+    return {"sampling": True, "sampling_topk": int(getattr(args, "sampling_topk", -1)),
+            "sampling_topp": float(getattr(args, "sampling_topp", -1.0)), "seed": int(getattr(args, "seed", 1))}
+
+
 def _greedy_mt(args) -> bool:
-    """The reference agent's own search: beam 1 and no search option set.  Only then the persistent MT step is armed."""
-    return int(getattr(args, "beam_mt", 1)) == 1 and not _search_kwargs(args)
+    """The reference agent's own search: beam 1, no search option set, no sampling.  Only then the persistent MT step is armed."""
+    return int(getattr(args, "beam_mt", 1)) == 1 and not _search_kwargs(args) and not _sampling_kwargs(args)
+
+
+def sampling_key_kwargs(agent) -> dict:
+    """With --sampling: the stream key of this write of the agent's generator_mt -- its --sampling-session and the count of its
+    writes since reset() -- as generate_decoder's keyword; nothing otherwise."""
+    if getattr(agent.generator_mt, "sampling", None) is None:
+        return {}
+    from .engine import sampling_stream_key
+    n = getattr(agent, "_mt_writes", 0)
+    agent._mt_writes = n + 1
+    return {"sampling_key": sampling_stream_key(int(getattr(agent.args, "sampling_session", 0)), n)}
 
 
 def _beam_kwargs(args) -> dict:
@@ -130,6 +149,7 @@ def _beam_kwargs(args) -> dict:
     kw = _search_kwargs(args)
     if int(getattr(args, "beam_mt", 1)) > 1:
         kw["unk_penalty"] = float(getattr(args, "unkpen", 0.0))
+    kw.update(_sampling_kwargs(args))
     return kw
 
 
@@ -301,6 +321,15 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
           help="text search: no n-gram of this size occurs twice in a hypothesis, committed prefix included (0 = off; 2 .. 32).  With "
                "any of these three off its default every write is a search behind the committed prefix as with --beam-mt > 1 (at "
                "beam 1 too), and the persistent MT step is not armed")
+        a("--sampling", action="store_true", default=False,
+          help="text search: every write samples --beam-mt chains behind the committed prefix and commits the best-scoring one "
+               "(the persistent MT step is not armed); the stream key of a write is --sampling-session and the count of writes so "
+               "far, so a replayed session samples the same")
+        a("--sampling-topk", type=int, default=-1, help="with --sampling: sample from the k most likely tokens (-1 = off)")
+        a("--sampling-topp", type=float, default=-1.0,
+          help="with --sampling: sample from the smallest set of tokens whose mass reaches p (-1 = off; not with top-k)")
+        a("--seed", type=int, default=1, help="seed of --sampling")
+        a("--sampling-session", type=int, default=0, help="with --sampling: this session's id in the stream key")
         a("--word-details", action="store_true", default=False,
           help="after every policy() that ran the encoder, agent.details holds the words of both CTC heads with their time spans, "
                "confidences and stability (streamspeech_amd/words.py); default: off, the heads run exactly as without the flag")
@@ -335,6 +364,7 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
         return self._spoken_words
 
     def reset(self):
+        self._mt_writes = 0     # --sampling: writes so far, the second half of the stream key
         self._mt_align = []     # --mt-alignment: (committed tokens placed so far, the words of one write), frozen
         self._spoken_rec = None  # --spoken-words: segments, samples emitted and states seen of the utterance (made by its first write)
         self.src_seg_num = 0
@@ -464,7 +494,7 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
         # 1. MT decoder: greedy continuation of the committed prefix (agent :520-538)
         finalized_mt = self.generator_mt.generate_decoder(
             self.encoder_outs, src_indices, src_lengths, {"id": 1}, self.tgt_subwords_indices, None, None,
-            aux_task_name=model.mt_task_name, max_new_tokens=new_subword_tokens)
+            aux_task_name=model.mt_task_name, max_new_tokens=new_subword_tokens, **sampling_key_kwargs(self))
         hyp = finalized_mt[0][0]
         if hyp["tokens"][-1] == 2:
             tgt_subwords_indices = hyp["tokens"][:-1].unsqueeze(0)
@@ -523,7 +553,7 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
             # reference runs that position through the MT decoder, T2U encoder and unit decoder with
             # key-padding masks, and its 25 unit positions are decoded like any other
             eng = self.engine
-            if self.generator_mt.beam_size > 1 or self.generator_mt.search:      # the beam search leaves no single-utterance KV cache to append to: one ragged pass
+            if self.generator_mt.beam_size > 1 or self.generator_mt.search or self.generator_mt.sampling is not None:   # the beam search leaves no single-utterance KV cache to append to: one ragged pass
                 enc = self.encoder_outs[0]["encoder_out"][0]
                 enc = (enc[:, 0] if enc.dim() == 3 else enc).contiguous()
                 mt_feats = eng.batch_mt_features(enc, [int(enc.shape[0])], [[int(t) for t in tmp]], [1])[0]

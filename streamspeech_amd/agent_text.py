@@ -6,7 +6,7 @@ agent/speech_to_text.s2tt.streamspeech.agent.py:381-545 (same flags as the S2ST 
 vocoder ones)."""
 import torch
 
-from .agent import StreamSpeechS2STAgent, _beam_kwargs, _greedy_mt, _detok, mt_alignment_update, word_details
+from .agent import StreamSpeechS2STAgent, _beam_kwargs, _greedy_mt, _detok, mt_alignment_update, sampling_key_kwargs, word_details
 from .frontend import OnlineFeatureExtractor  # noqa: F401  (re-exported for parity with the reference files)
 from .generators import CTCDecoder, SequenceGenerator
 from .simuleval_shim import ReadAction, SpeechToTextAgent, WriteAction, entrypoint
@@ -64,6 +64,7 @@ class _TextAgentBase(SpeechToTextAgent):
         return src, tgt
 
     def reset(self):
+        self._mt_writes = 0     # --sampling: writes so far, the second half of the stream key
         self._mt_align = []     # --mt-alignment: (committed tokens placed so far, the words of one write), frozen
         self.tgt_subwords_indices = None
         self.src_ctc_prefix_length = 0
@@ -139,7 +140,7 @@ class StreamSpeechS2TTAgent(_TextAgentBase):
         new_subword_tokens = gate.new_tokens
         hyp = self.generator_mt.generate_decoder([enc], src_indices, src_lengths, {"id": 1}, self.tgt_subwords_indices,
                                                  None, None, aux_task_name=self.model.mt_task_name,
-                                                 max_new_tokens=int(new_subword_tokens))[0][0]
+                                                 max_new_tokens=int(new_subword_tokens), **sampling_key_kwargs(self))[0][0]
         toks = hyp["tokens"]
         tgt_subwords_indices = (toks[:-1] if toks[-1] == 2 else toks).unsqueeze(0)
         tokens = [self.generator_mt.tgt_dict[c] for c in tgt_subwords_indices[0]]

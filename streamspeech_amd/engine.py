@@ -90,6 +90,12 @@ def fbank_sr_rows(n_in: int, up: int, down: int, half_len: int, lib=None) -> Opt
     return rows.value, fin.value
 
 
+def _as_i64(x: int) -> int:
+    """A 64-bit key as the signed value ctypes takes (keys are bit patterns: 2**64 - 1 and -1 are the same key)."""
+    x = int(x) & 0xFFFFFFFFFFFFFFFF
+    return x - (1 << 64) if x >= 1 << 63 else x
+
+
 MT_BEAM_MAX_ROWS = 256     # B * beam hypothesis rows of one ss_batch_mt_beam call
 MT_BEAM_MAX = 32
 
@@ -106,6 +112,56 @@ def check_search_options(len_penalty: float = 1.0, temperature: float = 1.0, no_
     if not (np.isfinite(t) and t > 0):
         raise ValueError(f"temperature {temperature} is not a finite positive number")
     return L.search_opts(p, t, n)
+
+
+def check_sampling_options(topk: int = 0, topp: float = 0.0, seed: int = 1, vocab: Optional[int] = None):
+    """The library's refusals of the sampling controls (ss_mt_sample_opts), raised as ValueError before anything is booked -> the
+    ss_mt_sample_opts to pass.  topk 0 / topp 0 switch the control off; both set is refused (the reference silently prefers
+    top-p)."""
+    k, p = int(topk), float(topp)
+    if k != topk or k < 0 or (vocab is not None and k > vocab):
+        raise ValueError(f"sampling top-k {topk} outside [0, vocabulary]")
+    if not np.isfinite(p) or p < 0.0 or p > 1.0:
+        raise ValueError(f"sampling top-p {topp} outside {{0}} u (0, 1]")
+    if k > 0 and p > 0.0:
+        raise ValueError("sampling top-k and top-p are both set")
+    if int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed {seed} is not a 64-bit unsigned integer")
+    return L.sample_opts(k, p, int(seed))
+
+
+def sampling_stream_key(session_id: int, n_writes: int) -> int:
+    """The stream key of a streaming session's write: the session id and the count of writes so far.  A replayed session samples
+    the same, and two sessions never share a stream."""
+    return ((int(session_id) & 0xFFFFFFFFFF) << 24) | (int(n_writes) & 0xFFFFFF)
+
+
+class SamplingOptions:
+    """Sampling of the first-pass text search as one object (the session pools' ``search=`` takes it in place of a SearchOptions,
+    which it may carry as ``search``): the reference generator's sampling_topk / sampling_topp (fairseq's -1 = off is 0 here) and
+    seed."""
+
+    def __init__(self, topk: int = 0, topp: float = 0.0, seed: int = 1, search=None):
+        check_sampling_options(topk, topp, seed)
+        self.topk, self.topp, self.seed = int(topk), float(topp), int(seed)
+        self.search = search
+
+    def kwargs(self) -> dict:
+        return {"topk": self.topk, "topp": self.topp, "seed": self.seed}
+
+    def __repr__(self):
+        return f"SamplingOptions(topk={self.topk}, topp={self.topp}, seed={self.seed})"
+
+
+def sampling_from_fairseq(sampling: bool, sampling_topk: int = -1, sampling_topp: float = -1.0, seed: int = 1):
+    """fairseq's generator arguments (build_generator: -1 = off) -> SamplingOptions, or None without sampling.  As there, top-k or
+    top-p without --sampling is an error."""
+    k, p = int(sampling_topk), float(sampling_topp)
+    if not sampling:
+        if k > 0 or p > 0:
+            raise ValueError("--sampling-topk / --sampling-topp require --sampling")
+        return None
+    return SamplingOptions(k if k > 0 else 0, p if p > 0 else 0.0, seed)
 
 
 class SearchOptions:
@@ -332,16 +388,21 @@ class BatchMixin:
         return fbank_sr_rows(n_in, *resample_ratio(sr_in), lib=self.lib)
 
     def _mt_beam(self, entry: str, enc_packed: torch.Tensor, Tp: List[int], prefixes: Optional[List[List[int]]], max_len: List[int],
-                 beam: int, spare_rows: int, min_len: int, unk_penalty: float, normalize: bool, search: tuple):
+                 beam: int, spare_rows: int, min_len: int, unk_penalty: float, normalize: bool, search: tuple, sample=None):
         """The calls behind batch_mt_beam (prefixes None: `entry` takes none) and batch_mt_beam_continue -> (nbest, feats [B, rows, D]),
         rows = the longest max_len + 1 + spare_rows.  A pack with B * beam > 256 rows runs as consecutive sub-calls (plan_beam_groups).
         search = (len_penalty, temperature, no_repeat_ngram_size): at the defaults the call is `entry` itself, otherwise `entry`_opts.
-        A hypothesis is its row's prefix + the generated tokens, and its positional scores cover both."""
+        A hypothesis is its row's prefix + the generated tokens, and its positional scores cover both.
+        sample = (keys, ss_mt_sample_opts): the sampling twin of `entry` (ss_batch_mt_sample / _continue), `beam` chains per row."""
         B = len(Tp)
         if not 1 <= beam <= MT_BEAM_MAX:
             raise ValueError(f"beam {beam} outside [1, {MT_BEAM_MAX}]")
         opts = check_search_options(*search)
         name, tail = (entry, ()) if opts is None else (entry + "_opts", (C.byref(opts),))
+        if sample is not None:
+            name = entry.replace("_beam", "_sample")
+            if len(sample[0]) != B:
+                raise ValueError("one key per row")
         stride = max(max_len) + 1
         rows = stride + spare_rows
         feats = torch.empty((B, rows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
@@ -356,6 +417,9 @@ class BatchMixin:
             n_out = (C.c_int32 * (n * beam))()
             sc = (C.c_float * (n * beam))()
             pos = (C.c_float * (n * beam * stride))()
+            if sample is not None:
+                keys = (C.c_int64 * n)(*[_as_i64(x) for x in sample[0][b0:b1]])
+                tail = (C.byref(opts) if opts is not None else None, keys, C.byref(sample[1]))
             L.check(getattr(self.lib, name)(self.h, _stream(), n, beam, _ptr(enc), _i32(Tp[b0:b1]), *forced, _i32(max_len[b0:b1]),
                                             int(min_len), float(unk_penalty), 1 if normalize else 0, out, stride, n_out, sc, pos,
                                             _ptr(feats[b0:b1]), rows, *tail), name)
@@ -397,6 +461,30 @@ class BatchMixin:
             raise ValueError("one prefix and one max_len per row")
         nbest, feats = self._mt_beam("ss_batch_mt_beam_continue", enc_packed, Tp, prefixes, max_len, beam, 0, min_len, unk_penalty,
                                      normalize, (len_penalty, temperature, no_repeat_ngram_size))
+        return nbest, [feats[b, :len(h[0]["tokens"]) if h else 0] for b, h in enumerate(nbest)]
+
+    def batch_mt_sample(self, enc_packed: torch.Tensor, Tp: List[int], max_len: List[int], n_samples: int, keys: List[int],
+                        topk: int = 0, topp: float = 0.0, seed: int = 1, min_len: int = 1, unk_penalty: float = 0.0,
+                        normalize: bool = True, len_penalty: float = 1.0, temperature: float = 1.0, no_repeat_ngram_size: int = 0):
+        """n_samples independent ancestral samples per row from the first-pass text decoder (ss_batch_mt_sample; the rule stands in
+        the header at ss_mt_sample_opts) -> what batch_mt_beam returns, every list holding exactly n_samples entries ordered by
+        score.  keys[b] is the row's 64-bit stream key: with `seed` it fixes the row's samples whatever else is in the pack."""
+        so = check_sampling_options(topk, topp, seed, self.cfg.tgt_vocab)
+        nbest, feats = self._mt_beam("ss_batch_mt_beam", enc_packed, Tp, None, max_len, n_samples, 1, min_len, unk_penalty, normalize,
+                                     (len_penalty, temperature, no_repeat_ngram_size), sample=(list(keys), so))
+        return nbest, feats, [len(h[0]["tokens"]) if h else 0 for h in nbest]
+
+    def batch_mt_sample_continue(self, enc_packed: torch.Tensor, Tp: List[int], prefixes: List[List[int]], max_len: List[int],
+                                 n_samples: int, keys: List[int], topk: int = 0, topp: float = 0.0, seed: int = 1, min_len: int = 1,
+                                 unk_penalty: float = 0.0, normalize: bool = True, len_penalty: float = 1.0, temperature: float = 1.0,
+                                 no_repeat_ngram_size: int = 0):
+        """batch_mt_sample behind a forced prefix per row (ss_batch_mt_sample_continue) -> what batch_mt_beam_continue returns."""
+        if not (len(prefixes) == len(max_len) == len(Tp)):
+            raise ValueError("one prefix and one max_len per row")
+        so = check_sampling_options(topk, topp, seed, self.cfg.tgt_vocab)
+        nbest, feats = self._mt_beam("ss_batch_mt_beam_continue", enc_packed, Tp, prefixes, max_len, n_samples, 0, min_len,
+                                     unk_penalty, normalize, (len_penalty, temperature, no_repeat_ngram_size),
+                                     sample=(list(keys), so))
         return nbest, [feats[b, :len(h[0]["tokens"]) if h else 0] for b, h in enumerate(nbest)]
 
     def last_logits(self) -> torch.Tensor:

@@ -114,6 +114,11 @@ class SequenceGenerator:
     include/streamspeech_hip.h has their exact rules).  With any of them off its default the search is ``batch_mt_beam_continue`` at
     beam 1 as well.  ``match_source_len=True`` raises.
 
+    sampling / sampling_topk / sampling_topp / seed: the names fairseq's ``build_generator`` reads (-1 = the control is off).  With
+    ``sampling`` the search is ``batch_mt_sample_continue``: beam_size independent ancestral samples behind the prefix, ordered by
+    score (the rule: ss_mt_sample_opts in the header).  The stream key of a call is ``sampling_key=`` of generate_decoder, else the
+    sample's ``"id"``, else 0: the same key and seed give the same samples.
+
     want_attention: hypothesis 0 also carries what the reference's generator records (agent/sequence_generator.py:383-392, fairseq's
     finalize_hypos): ``"attention"``, float32 [src_len, tgt_len], the head-averaged cross-attention of the last decoder layer --
     column p is the decoder position that predicted token p -- and ``"alignment"``, fairseq's hard alignment, an int tensor
@@ -125,8 +130,10 @@ class SequenceGenerator:
 
     def __init__(self, engine, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, max_len=0, min_len=1,
                  eos=None, use_incremental_states=False, unk_penalty=0.0, normalize_scores=True, want_attention=False,
-                 len_penalty=1.0, temperature=1.0, no_repeat_ngram_size=0, match_source_len=False, **kw):
-        from .engine import check_search_options
+                 len_penalty=1.0, temperature=1.0, no_repeat_ngram_size=0, match_source_len=False, sampling=False,
+                 sampling_topk=-1, sampling_topp=-1.0, seed=1, **kw):
+        from .engine import check_search_options, sampling_from_fairseq
+        self.sampling = sampling_from_fairseq(sampling, sampling_topk, sampling_topp, seed)
         self.want_attention = bool(want_attention)
         if match_source_len:
             raise ValueError("match_source_len is not supported: its source length is in encoder frames, which means nothing for "
@@ -169,10 +176,21 @@ class SequenceGenerator:
         start = len(prefix)
         max_len = mt_max_len(start, src_len, max_new_tokens, self.max_len_a, self.max_len_b, self.max_len, self.min_len)
         eng = self.engine
-        if self.beam_size > 1 or self.search:
+        if self.beam_size > 1 or self.search or self.sampling is not None:
             enc = enc.contiguous()
-            nbest, feats = eng.batch_mt_beam_continue(enc, [int(enc.shape[0])], [prefix], [max_len], self.beam_size, self.min_len,
-                                                      self.unk_penalty, self.normalize_scores, **self.search)
+            if self.sampling is not None:
+                key = kw.get("sampling_key")
+                if key is None:
+                    ids = sample.get("id") if isinstance(sample, dict) else None
+                    if torch.is_tensor(ids):
+                        ids = int(ids.view(-1)[0]) if ids.numel() else None
+                    key = int(ids) if ids is not None else 0
+                nbest, feats = eng.batch_mt_sample_continue(enc, [int(enc.shape[0])], [prefix], [max_len], self.beam_size, [int(key)],
+                                                            min_len=self.min_len, unk_penalty=self.unk_penalty,
+                                                            normalize=self.normalize_scores, **self.sampling.kwargs(), **self.search)
+            else:
+                nbest, feats = eng.batch_mt_beam_continue(enc, [int(enc.shape[0])], [prefix], [max_len], self.beam_size, self.min_len,
+                                                          self.unk_penalty, self.normalize_scores, **self.search)
             hyps = [{"tokens": torch.tensor(h["tokens"], dtype=torch.long), "features": None, "score": h["score"], "attention": None,
                      "alignment": None, "positional_scores": torch.tensor(h["positional_scores"], dtype=torch.float32)}
                     for h in nbest[0]]

@@ -146,6 +146,16 @@ def search_opts(len_penalty: float = 1.0, temperature: float = 1.0, no_repeat_ng
     return SSMtSearchOpts(C.sizeof(SSMtSearchOpts), int(no_repeat_ngram_size), float(len_penalty), float(temperature))
 
 
+class SSMtSampleOpts(C.Structure):
+    """ss_mt_sample_opts: top-k / top-p and the seed of the sampling search."""
+    _fields_ = [("size", C.c_int32), ("topk", C.c_int32), ("topp", _f), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+def sample_opts(topk: int = 0, topp: float = 0.0, seed: int = 1):
+    """The ss_mt_sample_opts of a sampling call (0 = the control is off)."""
+    return SSMtSampleOpts(C.sizeof(SSMtSampleOpts), int(topk), float(topp), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
 SS_OP_BEAM_CAND = 64     # row stride of the candidate lists of ss_op_beam_topk / ss_op_beam_merge
 
 # symbol -> (restype, argtypes); must list every function include/streamspeech_hip.h declares
@@ -274,6 +284,13 @@ SIGNATURES = {
     "ss_batch_mt_beam_continue_plan_opts": (_i, [_i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                  C.POINTER(C.c_int32), _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32),
                                                  C.POINTER(C.c_int32), _i64, C.POINTER(_i64), C.POINTER(SSMtSearchOpts)]),
+    "ss_batch_mt_sample": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _f, _i,
+                                C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(_f), C.POINTER(_f), _vp, _i,
+                                C.POINTER(SSMtSearchOpts), C.POINTER(_i64), C.POINTER(SSMtSampleOpts)]),
+    "ss_batch_mt_sample_continue": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), _i, _f, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32),
+                                         C.POINTER(_f), C.POINTER(_f), _vp, _i, C.POINTER(SSMtSearchOpts), C.POINTER(_i64),
+                                         C.POINTER(SSMtSampleOpts)]),
     "ss_batch_fbank_frames": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f,
                                    C.POINTER(_vp)]),
     "ss_batch_fbank_frames_sr": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -373,6 +390,9 @@ SIGNATURES = {
                                   _vp, _vp, _vp]),
     "ss_op_beam_merge_opts": (_i, [_vp, C.POINTER(SSOpBeamState), _i, _i, _i, _i, _i, _i, _i, _i, _f]),
     "ss_op_beam_prefix_score_opts": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _vp, _f]),
+    "ss_op_sample_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                               C.POINTER(SSMtSampleOpts), _vp, _vp, _vp, _vp]),
+    "ss_op_sample_uniform": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -44,6 +44,9 @@ The first-pass text search is greedy by default; `--beam-mt k` runs the referenc
 `--no-repeat-ngram-size` and `--lenpen` are that generator's further controls (ss_batch_mt_beam_opts); either off its default runs the
 beam search at `--beam-mt 1` too.  The generator's temperature is the `temperature` argument of generate(); this driver's command
 line goes on rejecting `--temperature`, which the recipe does not pass.
+`--sampling` (with `--sampling-topk K` or `--sampling-topp P`, and `--seed`) samples instead of searching: `--beam-mt N` is then the
+number of independent samples per utterance (ss_batch_mt_sample; the stream key of an utterance is its sample id).  The best-scoring
+sample is the D- text and is spoken, as hypothesis 0 of a beam is; generate-<subset>.mt.samples holds all N (id, rank, score, text).
 
 Pinned against the reference's own generator classes run on CPU (oracle/ref_offline.py ->
 tests/golden/offline_generator.json; tests/test_offline_generator_cpu.py, tests/test_offline_generator_gpu.py).
@@ -95,7 +98,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              features: bool = False, word_times: bool = False, mt_alignment: bool = False, len_penalty: float = 1.0,
              temperature: float = 1.0, no_repeat_ngram_size: int = 0,
              references: Optional[Dict[str, Dict[int, Sequence[int]]]] = None, spoken_words: bool = False,
-             mt_references: Optional[Dict[int, Sequence[int]]] = None, speak_reference: bool = False) -> Dict[int, Dict]:
+             mt_references: Optional[Dict[int, Sequence[int]]] = None, speak_reference: bool = False, sampling: bool = False,
+             sampling_topk: int = -1, sampling_topp: float = -1.0, seed: int = 1) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
@@ -109,6 +113,9 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     other file is the one written without it.
     len_penalty / temperature / no_repeat_ngram_size (--lenpen, no flag here, --no-repeat-ngram-size): the reference generator's
     controls of the first-pass text search (ss_mt_search_opts); any of them off its default runs the beam search at beam_mt = 1 too.
+    sampling / sampling_topk / sampling_topp / seed (--sampling, --sampling-topk, --sampling-topp, --seed; fairseq's names, -1 = off):
+    beam_mt independent samples per utterance instead of a search (batch_mt_sample, key = the sample id); the best-scoring one takes
+    hypothesis 0's place everywhere, and generate-<subset>.mt.samples lists them all (id, rank, score, text), beam_mt lines per id.
     references (--align-reference): {"asr": {sample id: label ids}, "st": {...}}, the reference text of each head as ids of its
     dictionary.  One batch_ctc_align per head and batch over the rows that have one; writes generate-<subset>.asr.ref.words /
     .st.ref.words and generate-<subset>.ref.scores (a line per sample and head: status aligned / infeasible / nan, or no_reference /
@@ -127,7 +134,9 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     vocoder.batch_forward (speaker_id and dur_prediction as for the hypotheses) into generate-<subset>.ref.unit and
     ref_wav/<n>_pred.wav, laid out as .unit and pred_wav/ are (a line / a number per sample id; a sample without spoken reference has
     an empty line and no file)."""
-    from .engine import check_search_options
+    from .engine import check_search_options, sampling_from_fairseq
+    sampler = sampling_from_fairseq(sampling, sampling_topk, sampling_topp, seed)
+    samples: Dict[int, list] = {}
     if spoken_words and not dump_wav:
         raise ValueError("spoken_words needs the vocoder's durations: it cannot be combined with dump_wav=False (--no-wav)")
     if speak_reference and mt_references is None:
@@ -189,7 +198,13 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
         # :130-131); src_len is the fbank frame count.  --max-len-a/-b configure the (NAR) unit generator, which has
         # no length search here.
         mx = [min(int(max_len_a_mt * t + max_len_b_mt), cfg.max_target_positions - 1) for t in T]
-        if beam_mt > 1 or search:
+        if sampler is not None:
+            nbest, feats, n = model.batch_mt_sample(enc, Tp, mx, beam_mt, [int(i) for i in ids], min_len=1, unk_penalty=unk_penalty,
+                                                    normalize=normalize, **sampler.kwargs(), **search)
+            toks = [h[0]["tokens"] if h else [] for h in nbest]
+            for b, sid in enumerate(ids):
+                samples[sid] = [(h["score"], detok([dicts["target_unigram"][c] for c in h["tokens"] if c != cfg.eos])) for h in nbest[b]]
+        elif beam_mt > 1 or search:
             # --beam-mt k: the reference's beam search (generator_mt with beam_size_mt = k, --unkpen, --unnormalized); the D- text
             # and the T2U input are hypothesis 0 of each n-best list (sequence_generator_multi_decoder_ctc.py:265-300)
             nbest, feats, n = model.batch_mt_beam(enc, Tp, mx, beam_mt, 1, unk_penalty, normalize, **search)
@@ -291,6 +306,11 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
                 if spoken[sid].tail_ms > 0:
                     t = spoken[sid]
                     print(f"{sid}\t</s>\t{t.total_ms - t.tail_ms}\t{t.total_ms}\t0", file=f)
+    if sampler is not None:
+        with open(os.path.join(results_path, f"generate-{subset}.mt.samples"), "w", encoding="utf-8") as f:
+            for sid in sorted(samples):
+                for rank, (score, text) in enumerate(samples[sid]):
+                    print(f"{sid}\t{rank}\t{score:.6f}\t{text}", file=f)
     if mt_alignment:
         with open(os.path.join(results_path, f"generate-{subset}.mt.words"), "w", encoding="utf-8") as f:
             for sid in sorted(words["mt"]):
@@ -636,6 +656,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--no-repeat-ngram-size", type=int, default=0,
                     help="text search: no n-gram of this size occurs twice in a hypothesis (0 = off; 2 .. 32).  Either of these two "
                          "off its default runs the beam search at --beam-mt 1 too")
+    ap.add_argument("--sampling", action="store_true",
+                    help="text search: draw --beam-mt independent samples per utterance instead of searching; the best-scoring one "
+                         "is spoken, all are written to generate-<subset>.mt.samples (id, rank, score, text)")
+    ap.add_argument("--sampling-topk", type=int, default=-1, help="with --sampling: sample from the k most likely tokens (-1 = off)")
+    ap.add_argument("--sampling-topp", type=float, default=-1.0,
+                    help="with --sampling: sample from the smallest set of tokens whose mass reaches p (-1 = off; not with top-k)")
+    ap.add_argument("--seed", type=int, default=1, help="seed of --sampling; an utterance's stream key is its sample id")
     ap.add_argument("--pcm16-io", action="store_true",
                     help="16-bit WAV sources are staged as raw frames, uploaded once and decoded on the device, and pred_wav/ is "
                          "written from 16-bit PCM packed on the device (one download per batch); the same files as without it")
@@ -652,6 +679,8 @@ def main(argv: Optional[List[str]] = None):
     from .engine import check_search_options
     try:
         check_search_options(a.lenpen, 1.0, a.no_repeat_ngram_size)
+        from .engine import sampling_from_fairseq
+        sampling_from_fairseq(a.sampling, a.sampling_topk, a.sampling_topp, a.seed)
     except ValueError as e:
         ap.error(str(e))
     if a.spoken_words and a.no_wav:
@@ -763,7 +792,9 @@ def main(argv: Optional[List[str]] = None):
                     **({"mt_references": mt_references} if mt_references is not None else {}),
                     **({"speak_reference": True} if a.speak_reference else {}),
                     **({"len_penalty": a.lenpen, "no_repeat_ngram_size": a.no_repeat_ngram_size}
-                       if (a.lenpen, a.no_repeat_ngram_size) != (1.0, 0) else {}))
+                       if (a.lenpen, a.no_repeat_ngram_size) != (1.0, 0) else {}),
+                    **({"sampling": True, "sampling_topk": a.sampling_topk, "sampling_topp": a.sampling_topp, "seed": a.seed}
+                       if a.sampling else {}))
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
 
 

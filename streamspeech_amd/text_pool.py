@@ -31,7 +31,7 @@ from typing import Dict, Optional
 
 import torch
 
-from .engine import MT_BEAM_MAX, SearchOptions, plan_beam_groups
+from .engine import MT_BEAM_MAX, SamplingOptions, SearchOptions, plan_beam_groups, sampling_stream_key
 from .frontend import SAMPLE_RATE, OnlineFeatureExtractor, unsettled_fbank_frames
 from . import endpoint as EP
 from .pcm import PcmArena, PcmFormat, PcmOut
@@ -108,6 +108,7 @@ class _Session:
         return self.fe.n_pcm + (self.pcm_chunk[1] if self.pcm_chunk is not None else 0)
 
     def reset(self):                          # the agent's reset()
+        self.mt_writes = 0                    # sampling: writes of this utterance so far, the second half of the stream key
         self.align_rec = []                   # (committed tokens placed so far, the words of one write): frozen once made
         self.tgt_subwords = None
         self.src_ctc_prefix_length = 0
@@ -141,12 +142,19 @@ class TextSessionPool:
         search (an engine.SearchOptions), or the three keywords len_penalty / temperature / no_repeat_ngram_size: the agents'
         --lenpen, --temperature and --no-repeat-ngram-size.  With one of them off its default the step's continuation is the beam
         search behind the prefix at beam_mt = 1 too; every committed token was chosen under the same ban, so a session's prefix
-        never repeats an n-gram and the call never refuses it."""
+        never repeats an n-gram and the call never refuses it.
+        search=engine.SamplingOptions(topk, topp, seed, search=SearchOptions or None): the agents' --sampling.  Every write draws
+        beam_mt chains behind the writer's committed prefix (HipModel.batch_mt_sample_continue) and commits the best-scoring one;
+        a write's stream key is engine.sampling_stream_key(session id, the session's writes so far), so a replayed session samples
+        the same and two sessions never share a stream."""
         if not 1 <= int(beam_mt) <= MT_BEAM_MAX:
             raise ValueError(f"beam_mt {beam_mt} outside [1, {MT_BEAM_MAX}]")
         self.beam_mt = int(beam_mt)
         if search is not None and (len_penalty, temperature, no_repeat_ngram_size) != (1.0, 1.0, 0):
             raise ValueError("give search= or the three keywords, not both")
+        self.sampling = None                   # search=SamplingOptions(...): every write samples beam_mt chains behind the prefix
+        if isinstance(search, SamplingOptions):
+            self.sampling, search = search, search.search
         self.search = search if search is not None else SearchOptions(len_penalty, temperature, no_repeat_ngram_size)
         self.model = model.hip if hasattr(model, "hip") else model
         self.with_details = bool(details)
@@ -762,7 +770,12 @@ class TextSessionPool:
                 else:
                     enc_w = torch.cat([views[i] for i, _, _, _, _ in writers], 0)
                     Tp = [views[i].shape[0] for i, _, _, _, _ in writers]
-                res, mt_groups = self._mt_call(enc_w, Tp, [p for _, _, p, _, _ in writers], [m for _, _, _, m, _ in writers])
+                keys = None
+                if self.sampling is not None:
+                    keys = [sampling_stream_key(s.sid, s.mt_writes) for _, s, _, _, _ in writers]
+                    for _, s, _, _, _ in writers:
+                        s.mt_writes += 1
+                res, mt_groups = self._mt_call(enc_w, Tp, [p for _, _, p, _, _ in writers], [m for _, _, _, m, _ in writers], keys)
                 for w, (toks, fts) in zip(writers, res):
                     i, s, prefix, ml, new = w
                     n_steps = max(n_steps, len(toks) - 1)
@@ -817,13 +830,17 @@ class TextSessionPool:
             self._endpoint_finish(eps)
         return out
 
-    def _mt_call(self, enc_w, Tp, prefixes, max_len):
+    def _mt_call(self, enc_w, Tp, prefixes, max_len, keys=None):
         """The step's ONE ragged continuation of every writer's committed prefix -> (per writer (tokens after the prefix incl. the
         final eos, decoder states of the fed positions), the [start, end) writer ranges of the device calls it took).  beam_mt = 1:
         the greedy continuation, as always.  beam_mt > 1: the beam search behind the prefix, hypothesis 0 of each writer; writers x
         beam_mt hypothesis rows are at most 256 per device call, so a step with more writers runs as the consecutive sub-calls of
         plan_beam_groups inside the engine call (nobody is refused).  A search option set: the same beam call at beam_mt = 1 too."""
         search = self.search.kwargs()
+        if self.sampling is not None:          # keys: one stream key per writer
+            nbest, feats = self.model.batch_mt_sample_continue(enc_w, Tp, prefixes, max_len, self.beam_mt, keys, min_len=MIN_LEN,
+                                                               **self.sampling.kwargs(), **search)
+            return [(h[0]["tokens"][len(p):], f) for h, f, p in zip(nbest, feats, prefixes)], plan_beam_groups(len(Tp), self.beam_mt)
         if self.beam_mt == 1 and not search:
             return self.model.batch_mt_continue(enc_w, Tp, prefixes, max_len, MIN_LEN), [(0, len(Tp))]
         nbest, feats = self.model.batch_mt_beam_continue(enc_w, Tp, prefixes, max_len, self.beam_mt, MIN_LEN, **search)
