@@ -975,6 +975,11 @@ int ss_batch_fbank_frames_sr(ss_model* m, void* stream, int B, const float* cons
  * the history, so no later call with more audio changes the row.  Rows from F on still see the zero padding and are recomputed.
  * Either pointer may be NULL.  SS_ERR_ARG for what the entry point refuses about a ratio, from the same code. */
 int ss_fbank_sr_rows(int64_t n_in, int up, int down, int half_len, int32_t* h_n_rows, int32_t* h_n_final);
+/* Host only, no GPU needed: the non-zero range of every row of a mel matrix h_melw [rows][cols] -- h_lo_hi[2 r] the first non-zero
+ * index of row r, h_lo_hi[2 r + 1] one past the last; an all-zero row gives 0, 0 (an empty range).  What a new model computes once
+ * from its fe.melw slot ([80][257]) so that the fbank kernel walks bins [lo, hi) of a mel row only: the bins it leaves out are exact
+ * zeros, so the row's sum keeps its bits.  SS_ERR_ARG for a NULL pointer or a negative count. */
+int ss_fbank_mel_ranges(const float* h_melw, int rows, int cols, int32_t* h_lo_hi);
 int ss_batch_t2u_units(ss_model* m, void* stream, int B, const float* d_feats, int feat_rows,
                        const int32_t* h_n, int t2u_causal, int mask_eos, int32_t* d_raw, int32_t* d_tokens,
                        int32_t* d_counts);
@@ -1147,6 +1152,17 @@ int ss_debug_rtlin(int grid, int enable);
 int ss_debug_rtlin_kb(int uw, int order);
 /* {UW, NCG, G, xmap} of the calling process's last rt_linear_kb launch (xmap: 1 = the XCD-aware order ran); zeros before the first. */
 int ss_debug_rtlin_kb_last(int32_t out[4]);
+/* A/B + test hook of the unit decoder's first layer in ss_batch_t2u_units / ss_batch_t2u_units_pad: its input is 25 copies of each
+ * text-decoder state's row, so under pack-invariant arithmetic the LayerNorm and the QKV linear of that layer run on the distinct rows
+ * and one copy kernel writes every result row 25 times (on = 1, the default; SS_UNIT_L0_DISTINCT sets it for the process).  on = 0:
+ * both run on all upsampled rows, as a context with pack-invariant arithmetic off always does.  The same bits either way.  -1 puts
+ * the process default back; other values: SS_ERR_ARG. */
+int ss_debug_unit_l0_distinct(int on);
+/* A/B + test hook of the fbank kernels (csrc/fbank.hip): dense = 1 walks all 257 bins of every mel row and computes the FFT twiddles
+ * with sincospif in the kernel; dense = 0 (the default; SS_FBANK_DENSE sets it for the process) reads the model's tables -- the
+ * non-zero bin range of each mel row (ss_fbank_mel_ranges) and the 256 twiddles, filled once per model by the same sincospif
+ * expression.  The same bits either way.  -1 puts the process default back; other values: SS_ERR_ARG. */
+int ss_debug_fbank_dense(int dense);
 /* A/B hook of the 64-channel vocoder-stage kernel (csrc/conv_c64.hip): 0 routes that stage's convs back to the stream-K kernel
  * with pre-activated twin tensors (round 3), 1 to it, -1 keeps the setting; 4 / 5 switch the Winograd F(2,3) form of those convs
  * (csrc/conv_c64w.hip) off / on without touching the first setting; 6 / 7 route the 128-channel stage's ResBlock convs to conv_sk2<128>

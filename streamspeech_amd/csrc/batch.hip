@@ -42,7 +42,7 @@ extern "C" int ss_batch_fbank_cmvn(ss_model* m, void* stream, int B, const float
     const int nb = std::min(kSlice, B - b0);
     int mx = 0;
     for (int b = b0; b < b0 + nb; ++b) mx = std::max(mx, segs[3 * (size_t)b + 1]);
-    RET(launch_fbank_cmvn_batch(d_pcm, pcm_scale, m->fe_window, m->fe_melw, m->fe_mean, m->fe_std, d_feat, dt + 3 * (size_t)b0, nb,
+    RET(launch_fbank_cmvn_batch(d_pcm, pcm_scale, m->fe_window, m->fe_melw, fe_tables(m), m->fe_mean, m->fe_std, d_feat, dt + 3 * (size_t)b0, nb,
                                 mx, s));
   }
   return SS_OK;
@@ -335,8 +335,13 @@ static int batch_t2u(ss_model* m, void* stream, int B, const float* d_feats, int
   const Offsets on = prefix(h_n, B);
   const int Nn = on.total, U = Nn * up;
   const size_t nx = (size_t)U * D;
+  // The unit decoder's input is up = 25 copies of each of the Nn rows t2u_out + pos_row, so its first layer's LayerNorm + QKV linear
+  // need the Nn distinct rows only: under pack-invariant arithmetic a linear's output row is a function of its input row alone
+  // (one summation order whatever the row count or kernel: launch_canon, gemm.hip) and so is the LayerNorm kernel's, hence the
+  // copies of the Nn result rows are the bits the U-row launches gave.  Without it the route depends on the row count: all rows.
+  const bool l0_distinct = m->pack_invariant && !debug_tile_forced() && disp().unit_l0_distinct && c.unit_layers > 0 && up > 1;
   RET(m->sc->ws.ensure((3 * nx + (size_t)U * 3 * D + (size_t)U * F + (size_t)Nn * 2 * D + (size_t)Nn * D +
-                    (size_t)U * V + (size_t)U) * sizeof(float)));
+                    (l0_distinct ? (size_t)Nn * 4 * D : 0) + (size_t)U * V + (size_t)U) * sizeof(float)));
   float* x = m->sc->ws.f();
   float* h = x + nx;
   float* q2 = h + nx;
@@ -344,7 +349,9 @@ static int batch_t2u(ss_model* m, void* stream, int B, const float* d_feats, int
   float* ff = selfbuf + (size_t)U * 3 * D;
   float* crosskv = ff + (size_t)U * F;
   float* t2u_out = crosskv + (size_t)Nn * 2 * D;
-  float* logits = t2u_out + (size_t)Nn * D;
+  float* x0 = t2u_out + (size_t)Nn * D;          // l0_distinct: the distinct unit-decoder input rows [Nn, D] ...
+  float* qkv0 = x0 + (size_t)Nn * D;              // ... and their first-layer QKV rows [Nn, 3D]
+  float* logits = l0_distinct ? qkv0 + (size_t)Nn * 3 * D : x0;
   int32_t* idx_scratch = reinterpret_cast<int32_t*>(logits + (size_t)U * V);
   // tables: t2u self {off,n,off,n}; unit self {25off,25n,25off,25n}; unit cross {25off,25n,off,n}; rows {25off,25n}
   std::vector<int> tab(14 * B + Nn + (h_pad ? 3 * B : 0));   // + the packed row -> row of d_feats map of the gather below (+ the masks)
@@ -391,6 +398,13 @@ static int batch_t2u(ss_model* m, void* stream, int B, const float* d_feats, int
     ac.O = h; ac.ldo = D; ac.H = H; ac.scale = 1.f; ac.segs = dt + 8 * B; ac.nseg = B; ac.max_q = on.mx * up;
     ac.no_decode_kernel = m->pack_invariant;
     if (tail) { at.seg_tail = tail + B; ac.seg_tail = tail + 2 * B; }
+    if (l == 0 && l0_distinct) {
+      RET(launch_upsample_add_pos(t2u_out, Nn, 1, m->unit_pos_row, (float)c.pad, x0, D, s));   // the same formula: row r of x0 = rows 25 r .. 25 r + 24 of x
+      RET(dec_layer_qkv(s, c, m->unit[0], x0, Nn, qkv0, 3 * D, h));
+      RET(launch_upsample_rows(qkv0, Nn, up, selfbuf, 3 * D, s));
+      RET(dec_layer_rest(s, c, m->unit[0], x, U, at, &ac, h, q2, ff));
+      continue;
+    }
     RET(dec_layer_ex(s, c, m->unit[l], x, U, selfbuf, 3 * D, at, &ac, h, q2, ff));
   }
   RET(launch_layernorm(x, D, h, D, m->unit_ln.g, m->unit_ln.b, U, D, 1e-5f, s));
@@ -847,7 +861,7 @@ extern "C" int ss_batch_fbank_frames(ss_model* m, void* stream, int B, const flo
   RET(upload(s, dt, tab));
   const float* const* d_pcm = reinterpret_cast<const float* const*>(dt + n_seg);
   float* const* d_feat = reinterpret_cast<float* const*>(dt + n_seg + 2 * (size_t)B);
-  return launch_fbank_cmvn_ptrs(d_pcm, d_feat, pcm_scale, m->fe_window, m->fe_melw, m->fe_mean, m->fe_std, dt, B, mx, s);
+  return launch_fbank_cmvn_ptrs(d_pcm, d_feat, pcm_scale, m->fe_window, m->fe_melw, fe_tables(m), m->fe_mean, m->fe_std, dt, B, mx, s);
 }
 
 // ss_batch_fbank_frames for sessions at ANY source rate, from the source-rate histories directly (fbank.hip, fbank_cmvn_sr_kernel):
@@ -885,7 +899,7 @@ extern "C" int ss_batch_fbank_frames_sr(ss_model* m, void* stream, int B, const 
   RET(m->sc->seg_buf.ensure(tab.size() * sizeof(int)));
   int* dt = (int*)m->sc->seg_buf.p;
   RET(upload(s, dt, tab));
-  return launch_fbank_cmvn_sr(reinterpret_cast<const FbankSrSeg*>(dt), B, mx, max_taps, pcm_scale, m->fe_window, m->fe_melw,
+  return launch_fbank_cmvn_sr(reinterpret_cast<const FbankSrSeg*>(dt), B, mx, max_taps, pcm_scale, m->fe_window, m->fe_melw, fe_tables(m),
                               m->fe_mean, m->fe_std, s);
 }
 

@@ -206,6 +206,19 @@ extern "C" int ss_debug_rtlin_kb_last(int32_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = v[i];
   return SS_OK;
 }
+// A/B + test hooks of the two "work nobody reads" paths: on = 1 / 0 the unit decoder's first-layer QKV over the distinct rows / over
+// all upsampled rows (batch.hip); dense = 1 / 0 the fbank mel walk over all 257 bins with in-kernel twiddles / over the model's
+// tables (fbank.hip).  -1 puts the process default (SS_UNIT_L0_DISTINCT, SS_FBANK_DENSE) back.
+extern "C" int ss_debug_unit_l0_distinct(int on) {
+  if (on < -1 || on > 1) return SS_ERR_ARG;
+  dispatch_edit([on](Dispatch& d) { d.unit_l0_distinct = on < 0 ? (getenv("SS_UNIT_L0_DISTINCT") ? atoi(getenv("SS_UNIT_L0_DISTINCT")) != 0 : 1) : on; });
+  return SS_OK;
+}
+extern "C" int ss_debug_fbank_dense(int dense) {
+  if (dense < -1 || dense > 1) return SS_ERR_ARG;
+  dispatch_edit([dense](Dispatch& d) { d.fbank_dense = dense < 0 ? (getenv("SS_FBANK_DENSE") ? atoi(getenv("SS_FBANK_DENSE")) != 0 : 0) : dense; });
+  return SS_OK;
+}
 extern "C" int ss_debug_ffn(int grid, int row_tiles_per_wave, int enable) {
   if (grid < 0 || row_tiles_per_wave < -1 || row_tiles_per_wave > 4) return SS_ERR_ARG;     // row tiles: 1..4 force, 0 process default, -1 keep
   ffn_fused_debug_grid(grid);

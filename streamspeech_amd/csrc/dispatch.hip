@@ -37,6 +37,7 @@ Dispatch env_defaults() {
   d.smallm_max_rows = I("SS_SMALLM_MAX_ROWS", d.smallm_max_rows); d.sk_min_units = L("SS_SK_MIN_UNITS", d.sk_min_units);
   d.no_sk2 = I("SS_NO_SK2", 0) ? 1 : 0; d.sk2_min_k64 = I("SS_SK2_MINK64", d.sk2_min_k64); d.sk2_spare_cus = I("SS_SK2_SPARE_CUS", 0);
   d.rt_wg_per_cu = I("SS_RTLIN_WG_PER_CU", 0); d.c32_min_k = I("SS_CONV_C32_MIN_K", d.c32_min_k); d.c16_min_k = I("SS_CONV_C16_MIN_K", d.c16_min_k);
+  d.unit_l0_distinct = I("SS_UNIT_L0_DISTINCT", 1) ? 1 : 0; d.fbank_dense = I("SS_FBANK_DENSE", 0) ? 1 : 0;
   return d;
 }
 Dispatch& process_settings() { static Dispatch d = env_defaults(); return d; }      // (callers hold g_disp_mu)

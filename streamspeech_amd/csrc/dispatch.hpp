@@ -55,6 +55,9 @@ struct Dispatch {
   int rt_kb_xmap = 1;                                  // SS_RTLIN_KB_XMAP: 0 = every workgroup walks a contiguous (tile, column group) range; 1 = the column groups of a row tile run side by side on one XCD
   int rt_kb_uw = 0;                                    // SS_RTLIN_KB_UW / ss_debug_rtlin_kb: 16-column units per wave and column group (0: by the launch's unit count; 1 / 2 / 4 force)
   int rt_kb_order = 1;                                 // test hook (ss_debug_rtlin_kb): 0 contiguous unit ranges, 1 by the launch (rt_kb_xmap and its conditions), 2 the XCD-aware order or SS_ERR_ARG
+  // work the outputs never see (batch.hip, fbank.hip): both switches give the same bits
+  int unit_l0_distinct = 1;        // SS_UNIT_L0_DISTINCT=0 / ss_debug_unit_l0_distinct: LayerNorm + QKV of the unit decoder's first layer over all 25 n upsampled rows instead of the n distinct ones (pack-invariant packs only; otherwise always all rows)
+  int fbank_dense = 0;             // SS_FBANK_DENSE=1 / ss_debug_fbank_dense: every mel row walks all 257 bins and the FFT twiddles come from sincospif in the kernel, instead of the model's FbankTables
 };
 
 // The calling thread's settings: the scoped context's private copy, else this thread's own copy of the process settings.

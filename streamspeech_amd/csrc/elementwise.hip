@@ -196,6 +196,25 @@ int launch_upsample_add_pos(const float* src, int n, int up, const float* pos_ro
   return SS_OK;
 }
 
+// out[u, :] = src[u / up, :]: a copy, four floats per thread (D % 4 == 0, rows 16-byte aligned -- the launcher checks)
+__global__ __launch_bounds__(256) void upsample_rows_kernel(const float4* __restrict__ src, int up, float4* __restrict__ out, int D4) {
+  const int u = blockIdx.x;
+  const float4* s = src + (size_t)(u / up) * D4;
+  float4* o = out + (size_t)u * D4;
+  for (int c = threadIdx.x; c < D4; c += 256) o[c] = s[c];
+}
+
+int launch_upsample_rows(const float* src, int n, int up, float* out, int D, hipStream_t stream) {
+  if (n <= 0) return SS_OK;
+  if (up <= 0 || D <= 0 || (D & 3) || (long long)n * up > 0x7fffffffLL || !src || !out ||
+      ((uintptr_t)src & 15) || ((uintptr_t)out & 15))
+    return SS_ERR_ARG;
+  hipLaunchKernelGGL(upsample_rows_kernel, dim3((unsigned)(n * up)), dim3(256), 0, stream, reinterpret_cast<const float4*>(src), up,
+                     reinterpret_cast<float4*>(out), D / 4);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
 __global__ void gather_rows_kernel(const int* __restrict__ idx, const float* __restrict__ table, int D,
                                    float* out, int rows) {
   const int i = blockIdx.y;

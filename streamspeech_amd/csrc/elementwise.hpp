@@ -37,6 +37,10 @@ int launch_embed_tokens_rows(const int* tok, const float* emb, const float* pos_
 int launch_upsample_add_pos(const float* src, int n, int up, const float* pos_row, float pad_value,
                             float* out, int D, hipStream_t stream);
 
+// out[u,:] = src[u/up,:] for u < n * up: every row of src [n, D] written `up` times in a row (the unit decoder's first-layer QKV rows,
+// computed once per distinct input row: batch.hip).  D % 4 == 0, both buffers 16-byte aligned, n * up < 2^31; else SS_ERR_ARG.
+int launch_upsample_rows(const float* src, int n, int up, float* out, int D, hipStream_t stream);
+
 // ids[m] = argmax_n logits[m,n] over n not in {mask0,mask1,mask2} (first max wins);
 // if force >= 0 the result is `force` (beam-search max-length rule).  Optionally max value out.
 int launch_masked_argmax(const float* logits, int ld, int M, int N, int mask0, int mask1, int mask2,

@@ -15,9 +15,14 @@ constexpr int WIN = 400, SHIFT = 160, NFFT = 512, NBIN = 257, NMEL = 80;
 // unscaled.  Shared by fbank_cmvn_kernel (samples loaded) and fbank_cmvn_sr_kernel (samples formed by the resampling prologue), so
 // the row is ONE piece of code: the scale multiplies where it always did (hipcc contracts x0 + x1 into an fma with it), and both
 // kernels get the same contraction of every expression below -- the row's bits depend on the two sample values only.
+// `tabs` (fbank.hpp) holds what is the same for every frame: with tabs.twiddle the twiddles are read from the table
+// fbank_twiddle_kernel filled with the expression below (the same bits), with tabs.mel_range mel row t walks its bins [lo, hi) only --
+// the bins outside are exact zeros of melw, fmaf(0, x, e) == e for the finite power spectrum and e starts at +0, so the ascending
+// walk over the range is the dense walk's chain with its no-ops left out (the same bits).  A null pointer keeps the in-kernel form.
 __device__ __forceinline__ void fbank_row(const float v0, const float v1, const float pcm_scale,
                                           const float* __restrict__ window,   // [400]
                                           const float* __restrict__ melw,     // [80][257]
+                                          const FbankTables tabs,
                                           const float* __restrict__ cmvn_mean, const float* __restrict__ cmvn_std,
                                           float* __restrict__ feat_row) {
   __shared__ float re[NFFT], im[NFFT];
@@ -30,7 +35,9 @@ __device__ __forceinline__ void fbank_row(const float v0, const float v1, const 
   float s = wave_sum(x0 + x1);
   if (lane == 0) red[wave] = s;
   // twiddles e^{-2 pi i k / 512}
-  {
+  if (tabs.twiddle) {
+    tw_c[t] = tabs.twiddle[t]; tw_s[t] = tabs.twiddle[NFFT / 2 + t];
+  } else {
     float sn, cs;
     sincospif(-2.0f * (float)t / (float)NFFT, &sn, &cs);
     tw_c[t] = cs; tw_s[t] = sn;
@@ -77,8 +84,12 @@ __device__ __forceinline__ void fbank_row(const float v0, const float v1, const 
   __syncthreads();
   if (t < NMEL) {
     const float* w = melw + t * NBIN;
+    int lo = 0, hi = NBIN;
+    if (tabs.mel_range) {                       // clamped: the table is device memory, the walk never leaves the row
+      lo = max(tabs.mel_range[2 * t], 0); hi = min(tabs.mel_range[2 * t + 1], NBIN);
+    }
     float e = 0.f;
-    for (int i = 0; i < NBIN; ++i) e = fmaf(w[i], re[i], e);
+    for (int i = lo; i < hi; ++i) e = fmaf(w[i], re[i], e);
     const float lg = logf(fmaxf(e, 1.1920928955078125e-07f));
     feat_row[t] = (lg - cmvn_mean[t]) / cmvn_std[t];
   }
@@ -87,6 +98,7 @@ __device__ __forceinline__ void fbank_row(const float v0, const float v1, const 
 __global__ __launch_bounds__(256) void fbank_cmvn_kernel(const float* __restrict__ pcm, float pcm_scale,
                                                          const float* __restrict__ window,   // [400]
                                                          const float* __restrict__ melw,     // [80][257]
+                                                         const FbankTables tabs,
                                                          const float* __restrict__ cmvn_mean,
                                                          const float* __restrict__ cmvn_std, float* feat,
                                                          const int* __restrict__ segs,
@@ -102,27 +114,54 @@ __global__ __launch_bounds__(256) void fbank_cmvn_kernel(const float* __restrict
   }
   const float* src = pcm + (size_t)frame * SHIFT;
   // load (coalesced)
-  fbank_row(src[t], (t + 256 < WIN) ? src[t + 256] : 0.f, pcm_scale, window, melw, cmvn_mean, cmvn_std, feat + (size_t)frame * NMEL);
+  fbank_row(src[t], (t + 256 < WIN) ? src[t + 256] : 0.f, pcm_scale, window, melw, tabs, cmvn_mean, cmvn_std, feat + (size_t)frame * NMEL);
+}
+
+// The twiddle table of FbankTables: fbank_row's own expression, once (cos [256] then sin [256]).
+__global__ __launch_bounds__(256) void fbank_twiddle_kernel(float* __restrict__ tw) {
+  const int t = threadIdx.x;
+  float sn, cs;
+  sincospif(-2.0f * (float)t / (float)NFFT, &sn, &cs);
+  tw[t] = cs; tw[NFFT / 2 + t] = sn;
+}
+
+int launch_fbank_twiddles(float* tw, hipStream_t stream) {
+  if (!tw) return SS_ERR_ARG;
+  hipLaunchKernelGGL(fbank_twiddle_kernel, dim3(1), dim3(NFFT / 2), 0, stream, tw);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+int fbank_mel_ranges(const float* melw, int rows, int cols, int* lo_hi) {
+  if (!melw || !lo_hi || rows < 0 || cols < 0) return SS_ERR_ARG;
+  for (int r = 0; r < rows; ++r) {
+    const float* w = melw + (size_t)r * cols;
+    int lo = 0, hi = 0;                               // an all-zero row: the empty range [0, 0)
+    for (int i = 0; i < cols; ++i)
+      if (w[i] != 0.f) { if (hi == 0) lo = i; hi = i + 1; }   // (a NaN weight counts as non-zero: it stays in the walk)
+    lo_hi[2 * r] = lo; lo_hi[2 * r + 1] = hi;
+  }
+  return SS_OK;
 }
 
 int launch_fbank_cmvn(const float* pcm, int n_samples, float pcm_scale, const float* window,
-                      const float* melw, const float* cmvn_mean, const float* cmvn_std, float* feat,
+                      const float* melw, const FbankTables& tabs, const float* cmvn_mean, const float* cmvn_std, float* feat,
                       int* n_frames, hipStream_t stream) {
   const int T = n_samples < WIN ? 0 : 1 + (n_samples - WIN) / SHIFT;
   if (n_frames) *n_frames = T;
   if (T == 0) return SS_OK;
   hipLaunchKernelGGL(fbank_cmvn_kernel, dim3(T), dim3(256), 0, stream, pcm, pcm_scale, window, melw,
-                     cmvn_mean, cmvn_std, feat, (const int*)nullptr, (const float* const*)nullptr, (float* const*)nullptr);
+                     tabs, cmvn_mean, cmvn_std, feat, (const int*)nullptr, (const float* const*)nullptr, (float* const*)nullptr);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }
 
 int launch_fbank_cmvn_batch(const float* pcm, float pcm_scale, const float* window, const float* melw,
-                            const float* cmvn_mean, const float* cmvn_std, float* feat, const int* segs, int nseg,
+                            const FbankTables& tabs, const float* cmvn_mean, const float* cmvn_std, float* feat, const int* segs, int nseg,
                             int max_frames, hipStream_t stream) {
   if (nseg <= 0 || max_frames <= 0) return SS_OK;
   hipLaunchKernelGGL(fbank_cmvn_kernel, dim3(max_frames, nseg), dim3(256), 0, stream, pcm, pcm_scale, window, melw,
-                     cmvn_mean, cmvn_std, feat, segs, (const float* const*)nullptr, (float* const*)nullptr);
+                     tabs, cmvn_mean, cmvn_std, feat, segs, (const float* const*)nullptr, (float* const*)nullptr);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }
@@ -148,11 +187,11 @@ int launch_cmvn_rows(const float* in, long long rows, const float* cmvn_mean, co
 }
 
 int launch_fbank_cmvn_ptrs(const float* const* pcm_ptrs, float* const* feat_ptrs, float pcm_scale, const float* window,
-                           const float* melw, const float* cmvn_mean, const float* cmvn_std, const int* segs, int nseg,
-                           int max_frames, hipStream_t stream) {
+                           const float* melw, const FbankTables& tabs, const float* cmvn_mean, const float* cmvn_std,
+                           const int* segs, int nseg, int max_frames, hipStream_t stream) {
   if (nseg <= 0 || max_frames <= 0) return SS_OK;
   hipLaunchKernelGGL(fbank_cmvn_kernel, dim3(max_frames, nseg), dim3(256), 0, stream, (const float*)nullptr, pcm_scale, window, melw,
-                     cmvn_mean, cmvn_std, (float*)nullptr, segs, pcm_ptrs, feat_ptrs);
+                     tabs, cmvn_mean, cmvn_std, (float*)nullptr, segs, pcm_ptrs, feat_ptrs);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }
@@ -205,7 +244,7 @@ constexpr int FBANK_SR_MAX_HALF = (int)(((WG_LDS - FBANK_ROW_LDS) / sizeof(float
 
 __global__ __launch_bounds__(256) void fbank_cmvn_sr_kernel(const FbankSrSeg* __restrict__ segs, float pcm_scale,
                                                             const float* __restrict__ window, const float* __restrict__ melw,
-                                                            const float* __restrict__ cmvn_mean,
+                                                            const FbankTables tabs, const float* __restrict__ cmvn_mean,
                                                             const float* __restrict__ cmvn_std) {
   extern __shared__ float hs[];
   const FbankSrSeg sg = segs[blockIdx.y];
@@ -223,7 +262,7 @@ __global__ __launch_bounds__(256) void fbank_cmvn_sr_kernel(const FbankSrSeg* __
     v0 = resample_sample(sg.pcm, sg.n_in, sg.up, sg.down, hs, sg.half, k0);
     if (t + 256 < WIN) v1 = resample_sample(sg.pcm, sg.n_in, sg.up, sg.down, hs, sg.half, k0 + 256);
   }
-  fbank_row(v0, v1, pcm_scale, window, melw, cmvn_mean, cmvn_std, sg.feat + (size_t)blockIdx.x * NMEL);
+  fbank_row(v0, v1, pcm_scale, window, melw, tabs, cmvn_mean, cmvn_std, sg.feat + (size_t)blockIdx.x * NMEL);
 }
 
 int fbank_sr_rows(long long n_in, int up, int down, int half_len, int* n_rows, int* n_final) {
@@ -246,12 +285,13 @@ int fbank_sr_rows(long long n_in, int up, int down, int half_len, int* n_rows, i
 }
 
 int launch_fbank_cmvn_sr(const FbankSrSeg* segs, int nseg, int max_rows, int max_taps, float pcm_scale, const float* window,
-                         const float* melw, const float* cmvn_mean, const float* cmvn_std, hipStream_t stream) {
+                         const float* melw, const FbankTables& tabs, const float* cmvn_mean, const float* cmvn_std,
+                         hipStream_t stream) {
   if (nseg <= 0 || max_rows <= 0) return SS_OK;
   if (max_taps < 0 || max_taps > 2 * FBANK_SR_MAX_HALF + 1) return SS_ERR_ARG;
   const size_t lds = (size_t)max_taps * sizeof(float);
-  hipLaunchKernelGGL(fbank_cmvn_sr_kernel, dim3(max_rows, nseg), dim3(256), lds, stream, segs, pcm_scale, window, melw, cmvn_mean,
-                     cmvn_std);
+  hipLaunchKernelGGL(fbank_cmvn_sr_kernel, dim3(max_rows, nseg), dim3(256), lds, stream, segs, pcm_scale, window, melw, tabs,
+                     cmvn_mean, cmvn_std);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }

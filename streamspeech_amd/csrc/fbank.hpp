@@ -6,24 +6,38 @@
 
 namespace ss {
 
+// What fbank_row reads that is the same for every frame, made once per model (ss_model_create) and kept on the device next to melw:
+// the first and one-past-the-last non-zero bin of every mel row, and the FFT's 256 twiddles.  Either pointer may be null: that part
+// of the row then runs as it did before the tables existed (the dense 257-bin walk, sincospif in the kernel) -- the same bits.
+struct FbankTables {
+  const int* mel_range = nullptr;     // [80][2] {lo, hi}: mel row t is zero outside bins [lo, hi)
+  const float* twiddle = nullptr;     // cos [256] then sin [256] of -2 pi k / 512, from fbank_row's own sincospif expression
+};
+
+// Host only, no GPU needed: lo_hi[2 r] / lo_hi[2 r + 1] = the first non-zero index of row r of melw [rows][cols] and one past the
+// last (an all-zero row: 0, 0 -- an empty range).
+int fbank_mel_ranges(const float* melw, int rows, int cols, int* lo_hi);
+// tw [512] on the device <- the twiddle table of FbankTables (one small launch).
+int launch_fbank_twiddles(float* tw, hipStream_t stream);
+
 // pcm: mono 16 kHz float samples on the device; each sample is multiplied by pcm_scale (2^15 for
 // [-1,1] input, reference fairseq/examples/speech_to_text/data_utils.py:85).  window [400] and
 // melw [80][257] are host-built constants living in the weight blob.  Writes feat [T,80] and
 // returns T = 1 + (n-400)/160 (snip_edges) through n_frames (host int).
 int launch_fbank_cmvn(const float* pcm, int n_samples, float pcm_scale, const float* window,
-                      const float* melw, const float* cmvn_mean, const float* cmvn_std, float* feat,
+                      const float* melw, const FbankTables& tabs, const float* cmvn_mean, const float* cmvn_std, float* feat,
                       int* n_frames, hipStream_t stream);
 
 // Ragged batch: segs[3*s] = {pcm_start, n_frames, frame_start} into the packed PCM / feature arrays.
 int launch_fbank_cmvn_batch(const float* pcm, float pcm_scale, const float* window, const float* melw,
-                            const float* cmvn_mean, const float* cmvn_std, float* feat, const int* segs, int nseg,
+                            const FbankTables& tabs, const float* cmvn_mean, const float* cmvn_std, float* feat, const int* segs, int nseg,
                             int max_frames, hipStream_t stream);
 
 // Ragged batch over separate buffers: segment s reads pcm_ptrs[s] and writes feat_ptrs[s] (device arrays of device pointers);
 // segs[3*s] = {pcm_start, n_frames, frame_start} are offsets into those buffers.  Same kernel, same bits per frame.
 int launch_fbank_cmvn_ptrs(const float* const* pcm_ptrs, float* const* feat_ptrs, float pcm_scale, const float* window,
-                           const float* melw, const float* cmvn_mean, const float* cmvn_std, const int* segs, int nseg,
-                           int max_frames, hipStream_t stream);
+                           const float* melw, const FbankTables& tabs, const float* cmvn_mean, const float* cmvn_std,
+                           const int* segs, int nseg, int max_frames, hipStream_t stream);
 
 // out[r][c] = (in[r][c] - cmvn_mean[c]) / cmvn_std[c] over `rows` packed rows of 80: fbank_row's last line on rows computed elsewhere.
 int launch_cmvn_rows(const float* in, long long rows, const float* cmvn_mean, const float* cmvn_std, float* out, hipStream_t stream);
@@ -72,6 +86,7 @@ int fbank_sr_rows(long long n_in, int up, int down, int half_len, int* n_rows, i
 // n_rows, max_taps the largest 2 * half + 1 of the segments that resample (0: none does).  Every segment must have passed
 // fbank_sr_rows and ask for rows below its n_rows: the kernel reads pcm[0 .. n_in) and nothing else.
 int launch_fbank_cmvn_sr(const FbankSrSeg* segs, int nseg, int max_rows, int max_taps, float pcm_scale, const float* window,
-                         const float* melw, const float* cmvn_mean, const float* cmvn_std, hipStream_t stream);
+                         const float* melw, const FbankTables& tabs, const float* cmvn_mean, const float* cmvn_std,
+                         hipStream_t stream);
 
 }  // namespace ss

@@ -57,6 +57,29 @@ extern "C" const char* ss_error_string(int code) {
   }
 }
 
+// FbankTables of a new model (fbank.hpp): the mel rows' non-zero ranges from a one-time host copy of fe.melw, the twiddles from a
+// one-time launch of the kernel's own expression.  Both are functions of the blob alone and never change afterwards.
+static int make_fbank_tables(ss_model* m) {
+  constexpr int R = 80, Cn = 257, NTW = 512;
+  std::vector<float> melw((size_t)R * Cn);
+  SS_HIP_CHECK(hipMemcpy(melw.data(), m->fe_melw, melw.size() * sizeof(float), hipMemcpyDeviceToHost));
+  std::vector<int> rng(2 * R);
+  RET(fbank_mel_ranges(melw.data(), R, Cn, rng.data()));
+  RET(m->fe_tab.ensure(rng.size() * sizeof(int) + NTW * sizeof(float), true));
+  int* d_rng = reinterpret_cast<int*>(m->fe_tab.p);
+  float* d_tw = reinterpret_cast<float*>(d_rng + rng.size());
+  SS_HIP_CHECK(hipMemcpy(d_rng, rng.data(), rng.size() * sizeof(int), hipMemcpyHostToDevice));
+  RET(launch_fbank_twiddles(d_tw, nullptr));
+  SS_HIP_CHECK(hipDeviceSynchronize());              // once per model: later calls arrive on any stream and must see the tables
+  m->fe_tables.mel_range = d_rng;
+  m->fe_tables.twiddle = d_tw;
+  return SS_OK;
+}
+
+extern "C" int ss_fbank_mel_ranges(const float* h_melw, int rows, int cols, int32_t* h_lo_hi) {
+  return fbank_mel_ranges(h_melw, rows, cols, h_lo_hi);
+}
+
 extern "C" int ss_model_create(const ss_config* cfg, const float* d_blob, size_t blob_floats,
                                const char* const* names, const int64_t* offsets, const int64_t* numels,
                                int n_slots, ss_model** out) {
@@ -118,6 +141,8 @@ extern "C" int ss_model_create(const ss_config* cfg, const float* d_blob, size_t
   m->unit_out = {w.get("unit.out.w", (int64_t)cfg->unit_vocab * D), nullptr};
   m->unit_pos_row = w.get("unit.pos_row", D);
   if (!w.missing.empty()) { ss_model_destroy(m); return SS_ERR_MISSING_WEIGHT; }
+  rc = make_fbank_tables(m);
+  if (rc != SS_OK) { ss_model_destroy(m); return rc; }
 
   // projected rel-pos table for every layer at once: [2Tm-1, d] x [L*d, d]^T (linear_pos has no
   // bias, espnet_multihead_attention.py:125).  Depends only on the relative offset, so it is
@@ -156,6 +181,7 @@ extern "C" void ss_model_destroy(ss_model* m) {
         break;
       }
   }
+  m->fe_tab.release();
   scratch_unref(m->sc);
   delete m;
 }
@@ -227,7 +253,7 @@ extern "C" int ss_fbank_num_frames(int n) { return n < 400 ? 0 : 1 + (n - 400) /
 extern "C" int ss_fbank_cmvn(ss_model* m, void* stream, const float* d_pcm, int n_samples, float pcm_scale,
                              float* d_feat, int* h_n_frames) {
   if (!m) return SS_ERR_ARG;
-  return launch_fbank_cmvn(d_pcm, n_samples, pcm_scale, m->fe_window, m->fe_melw, m->fe_mean, m->fe_std,
+  return launch_fbank_cmvn(d_pcm, n_samples, pcm_scale, m->fe_window, m->fe_melw, fe_tables(m), m->fe_mean, m->fe_std,
                            d_feat, h_n_frames, (hipStream_t)stream);
 }
 

@@ -276,6 +276,8 @@ struct ss_model {
   int pos_key_dev = 0;
   // front-end
   const float *fe_window = nullptr, *fe_melw = nullptr, *fe_mean = nullptr, *fe_std = nullptr;
+  DevBuf fe_tab;                     // FbankTables of this model, made once at creation: mel ranges int [80][2], then twiddles float [512]
+  FbankTables fe_tables;             // pointers into fe_tab
   // decoders
   const float* mt_emb = nullptr; const float* mt_pos = nullptr; LN mt_ln;
   std::vector<DecLayer> mt, t2u, unit;
@@ -286,6 +288,10 @@ struct ss_model {
   // is a function of that utterance alone (same bits alone, in any pack, at any position); 0 = fastest kernel per shape (round-4 routes)
   int pack_invariant = g_pack_invariant_default;
 };
+
+// The tables every fbank launch of this model passes on: the model's own, or none (the dense mel walk and the in-kernel twiddles:
+// SS_FBANK_DENSE / ss_debug_fbank_dense -- the same bits, kept for A/B and for the test that says so).
+[[maybe_unused]] static FbankTables fe_tables(const ss_model* m) { return disp().fbank_dense ? FbankTables{} : m->fe_tables; }
 
 // Key-split scratch of this context for the single-utterance rel-pos attention: allocated and zeroed on first use (the
 // counters must read zero; the stream is synchronised once so that a later call on another stream sees them).
@@ -362,10 +368,16 @@ struct StreamRows { int T1, T2, cchunk, achunk_cfg, achunk, r0, n, nf, mb1; };
 // One pre-LN transformer layer on the residual stream x [n, D].  The fused QKV rows are written to
 // `qkv_rows` with row stride ld_qkv (straight into a KV cache when decoding); the caller prepares
 // the attention descriptors (single utterance or ragged batch) -- their O is `h`, cross Q is `q2`.
-[[maybe_unused]] static int dec_layer_ex(hipStream_t s, const ss_config& c, const DecLayer& L, float* x, int n, float* qkv_rows,
-                        int ld_qkv, const AttnArgs& self_at, const AttnArgs* cross_at, float* h, float* q2, float* ff) {
+// The layer in two steps, for a caller that has a cheaper way to the same fused QKV rows (batch_t2u: the unit decoder's first layer):
+// dec_layer_qkv writes them for the n rows of x, dec_layer_rest is everything after them.  dec_layer_ex is the two in a row.
+[[maybe_unused]] static int dec_layer_qkv(hipStream_t s, const ss_config& c, const DecLayer& L, const float* x, int n, float* qkv_rows,
+                         int ld_qkv, float* h) {
+  const int D = c.dec_dim;
+  return ln_linear(s, x, n, L.self_ln, L.self_qkv, 3 * D, D, qkv_rows, ld_qkv, h);   // q (pre-scaled at pack time), k, v
+}
+[[maybe_unused]] static int dec_layer_rest(hipStream_t s, const ss_config& c, const DecLayer& L, float* x, int n, const AttnArgs& self_at,
+                          const AttnArgs* cross_at, float* h, float* q2, float* ff) {
   const int D = c.dec_dim, F = c.dec_ffn;
-  RET(ln_linear(s, x, n, L.self_ln, L.self_qkv, 3 * D, D, qkv_rows, ld_qkv, h));   // q (pre-scaled at pack time), k, v
   RET(launch_attention(self_at, s));
   RET(linear(s, h, D, n, L.self_out, D, D, x, D, ACT_NONE, 1.f, x, D));
   if (L.has_cross && cross_at) {
@@ -376,6 +388,11 @@ struct StreamRows { int T1, T2, cchunk, achunk_cfg, achunk, r0, n, nf, mb1; };
   RET(ln_linear(s, x, n, L.ffn_ln, L.fc1, F, D, ff, F, h, ACT_RELU));
   RET(linear(s, ff, F, n, L.fc2, D, F, x, D, ACT_NONE, 1.f, x, D));
   return SS_OK;
+}
+[[maybe_unused]] static int dec_layer_ex(hipStream_t s, const ss_config& c, const DecLayer& L, float* x, int n, float* qkv_rows,
+                        int ld_qkv, const AttnArgs& self_at, const AttnArgs* cross_at, float* h, float* q2, float* ff) {
+  RET(dec_layer_qkv(s, c, L, x, n, qkv_rows, ld_qkv, h));
+  return dec_layer_rest(s, c, L, x, n, self_at, cross_at, h, q2, ff);
 }
 
 // single utterance: self K/V cache rows live in `selfbuf` ([*, 3D], row = absolute position)

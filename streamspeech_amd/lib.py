@@ -332,6 +332,9 @@ SIGNATURES = {
     "ss_debug_rtlin": (_i, [_i, _i]),
     "ss_debug_rtlin_kb": (_i, [_i, _i]),
     "ss_debug_rtlin_kb_last": (_i, [C.POINTER(C.c_int32)]),
+    "ss_debug_unit_l0_distinct": (_i, [_i]),
+    "ss_debug_fbank_dense": (_i, [_i]),
+    "ss_fbank_mel_ranges": (_i, [_vp, _i, _i, C.POINTER(C.c_int32)]),
     "ss_debug_conv_c64": (_i, [_i]),
     "ss_debug_conv_c256_rows": (_i, [_i]),
     "ss_debug_conv_c32": (_i, [_i]),
