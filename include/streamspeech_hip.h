@@ -790,6 +790,40 @@ int ss_batch_ctc_align(ss_model* m, void* stream, int head, int B, const float* 
 int ss_ctc_align_host(const float* h_logits, int ld, int V, int pad, int B, const int32_t* h_T, const int32_t* h_targets,
                       const int32_t* h_n_targets, ss_ctc_align_result* h_results, int32_t* h_path, int32_t* h_first, int32_t* h_last,
                       float* h_tok_lprob, float* h_frame_lprob);
+/* ---- CTC prefix beam search on a text head (csrc/ctc_beam.hip; the search and its order: csrc/ctc_beam.hpp): the most likely TEXT --
+ * the labelling whose probability, summed over all its alignments, is highest -- and its runners-up, where ss_batch_ctc_greedy gives
+ * the most likely frame path.  Blank = 0; per frame lp = log_softmax(row) with the greedy search's denominator, pad and unk then
+ * -inf (agent/ctc_decoder.py:52-60), so a hypothesis never holds blank, pad or unk (it may hold </s>).  Per frame a prefix is
+ * extended by the `cand` unmasked non-blank columns with the largest float32 logits (the lower id on a tie; a -inf logit never),
+ * and keeps its own last label at that label's true lp.  State: float64 log-probabilities (ending in blank, ending in the last
+ * label); a prefix IS its label string, whichever route led to it and whether or not it stayed in the beam in between.  After each
+ * frame the `beam` prefixes with the largest total stay (a -inf total never).  Ties: the entries of a frame are ordered by (rank
+ * of the source prefix in the entering beam; the prefix itself, then its extensions in candidate order), and the earlier of two
+ * equal totals comes first.  score is on the scale of ss_ctc_align_result.score, log p(y | x): exact when nothing was pruned,
+ * otherwise a lower bound of the aligner's score for the same labels. ---- */
+typedef struct ss_ctc_beam_hyp {
+  double score;      /* log of the summed probability of the alignments the search kept for these labels */
+  int32_t n_tokens;
+  int32_t status;    /* 0 a hypothesis; 1 an empty slot (fewer prefixes alive than nbest, or no labelling has probability > 0);
+                      * 2 a NaN in a row of the utterance.  For 1 and 2: n_tokens = 0, score = -inf / NaN */
+} ss_ctc_beam_hyp;
+#define SS_CTC_BEAM_MAX_BEAM 32
+#define SS_CTC_BEAM_MAX_CAND 32
+#define SS_CTC_BEAM_MAX_FRAMES 1500     /* T' per utterance, as the aligner */
+/* B utterances packed as ss_batch_ctc_greedy_scored takes them (the same head GEMM, pack-invariance setting and workspace), stream-
+ * ordered.  Device outputs: d_hyps [B][nbest] best first, d_tokens [B][nbest][out_stride] (entries past n_tokens are left as they
+ * were).  An utterance's outputs are the same bits alone and in any pack, in any order.  SS_ERR_ARG, with nothing launched or
+ * written: beam outside [1, SS_CTC_BEAM_MAX_BEAM], cand outside [1, SS_CTC_BEAM_MAX_CAND], nbest outside [1, beam], a Tp outside
+ * [1, SS_CTC_BEAM_MAX_FRAMES], out_stride < max Tp, B <= 0, head outside {0, 1}, a missing pointer.  Working memory, booked on the
+ * context's scratch set (SS_ERR_SCRATCH_CAP past its cap): per utterance 8 (1 + beam Tp) bytes of trie, 12 bytes for each of the
+ * child table's slots (the power of two >= 2 beam Tp) and Tp (8 + 4 cand) bytes of per-frame values -- under 56 beam Tp + 136 Tp. */
+int ss_batch_ctc_beam(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int beam, int cand,
+                      int nbest, ss_ctc_beam_hyp* d_hyps, int32_t* d_tokens, int out_stride);
+/* The plain-C++ twin of the two kernels on host logits [sum T][ld] (V columns read; pad / unk < 0: no such id): the same step code,
+ * record layout, refusals (and ld < V) and edge cases, every pointer a HOST pointer.  h_den [sum T][2] (the row's max and log-sum;
+ * NaN for a row that holds a NaN) and h_cand_id [sum T][cand] (-1 where a row has fewer) may be NULL. */
+int ss_ctc_beam_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
+                     int nbest, ss_ctc_beam_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den, int32_t* h_cand_id);
 /* Lockstep beam-1 search from [</s>] (offline: no prefix).  h_max_len[b] = forced-</s> step of
  * utterance b.  h_out_tokens [B][out_stride] receives the generated tokens (incl. the final </s>),
  * h_n_out[b] their number (= rows of valid decoder states); d_feats is [B][feat_rows][dec_dim].
@@ -1394,6 +1428,14 @@ int ss_op_ctc_align(void* stream, const float* d_logits, int ld, int V, int pad,
 int ss_op_unit_spans(void* stream, int B, const int32_t* d_raw, const int32_t* h_n, const int32_t* h_K, const int32_t* h_dur_first,
                      const int32_t* h_unit0, const int32_t* d_dur, int up, int blank, int pad, int bos, int eos, int32_t* d_spans,
                      int32_t* d_K_out);
+/* The two kernels of ss_batch_ctc_beam on the caller's logits [sum T][ld] (device; V columns read), arguments and outputs as
+ * ss_ctc_beam_host with device output pointers.  tests/test_ctc_beam_gpu.py against tests/ctc_beam_ref.py. */
+int ss_op_ctc_beam(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam,
+                   int cand, int nbest, ss_ctc_beam_hyp* d_hyps, int32_t* d_tokens, int out_stride, float* d_den,
+                   int32_t* d_cand_id);
+/* The beam cap of ss_ctc_beam_host alone (the kernels keep SS_CTC_BEAM_MAX_BEAM): tests/test_ctc_beam_cpu.py raises it so that every
+ * labelling of a tiny case fits the beam.  -> the cap before the call; max_beam < 1 only reads it. */
+int ss_debug_ctc_beam_host_max(int max_beam);
 int ss_op_dur_predict(void* stream, const float* logdur, const int32_t* forced, int K, int32_t* dur, int32_t* cum,
                       const int32_t* segs, int nseg);                 /* segs {start, len}: cum of segment s at start + s */
 int ss_op_repeat_rows(void* stream, const float* emb, const int32_t* cum, int K, int D, float* out, int F, const int32_t* segs,

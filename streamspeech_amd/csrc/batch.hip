@@ -4,6 +4,7 @@
 #include <cstring>
 #include "model_internal.hpp"
 #include "ctc_align.hpp"
+#include "ctc_beam.hpp"
 
 // =================================================================================================
 // Ragged-batch stage twins: B independent utterances packed along the row axis.  No padding exists
@@ -229,6 +230,28 @@ int mt_decode_rows(ss_model* m, hipStream_t s, const MtRowsWs& w, const MtRowsSt
   RET(launch_layernorm(w.x, D, a.states, a.states_ld, m->mt_ln.g, m->mt_ln.b, n, D, 1e-5f, s));
   Lin proj{m->mt_emb, nullptr};                                      // tied output projection, no bias
   return linear(s, a.states, a.states_ld, n, proj, V, D, w.logits, V);
+}
+
+// Prefix beam search on a text head: ss_batch_ctc_greedy_scored's head GEMM (the same linear, CanonScope and workspace), then the
+// two kernels of ctc_beam.hip.  Every refusal comes before the first launch; the tries, child tables and per-frame values live in
+// the encoder scratch (idle here: d_enc_out is the caller's), the table of the pack in the segment buffer.
+extern "C" int ss_batch_ctc_beam(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int beam,
+                                 int cand, int nbest, ss_ctc_beam_hyp* d_hyps, int32_t* d_tokens, int out_stride) {
+  if (!m || B <= 0 || head < 0 || head > 1 || !d_enc_out || !h_Tp || !d_hyps || !d_tokens) return SS_ERR_ARG;
+  const ss_config& c = m->cfg;
+  const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
+  CtcBeamPlan plan;
+  RET(ctc_beam_plan(V, B, h_Tp, beam, cand, nbest, out_stride, plan));
+  SkScope sk_scope(m->sc->skws);
+  CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
+  hipStream_t s = (hipStream_t)stream;
+  RET(m->sc->mt_ws.ensure((size_t)plan.rows * V * sizeof(float)));
+  RET(m->sc->ws.ensure(plan.work_bytes()));
+  RET(m->sc->seg_buf.ensure(ctc_beam_table_bytes(plan)));
+  float* logits = m->sc->mt_ws.f();
+  RET(linear(s, d_enc_out, c.enc_dim, plan.rows, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, logits, V));
+  m->sc->dbg_logits = logits; m->sc->dbg_rows = plan.rows; m->sc->dbg_cols = V;
+  return launch_ctc_beam(logits, V, V, c.pad, c.unk, plan, m->sc->seg_buf.p, m->sc->ws.p, d_hyps, d_tokens, out_stride, nullptr, nullptr, s);
 }
 
 // Batched beam-1 search: all utterances start from [</s>] and advance in lockstep, one row per

@@ -1,0 +1,458 @@
+// CTC prefix beam search on the two text CTC heads (blank = 0): the most likely TEXT -- the labelling whose probability, summed over
+// all its alignments, is highest -- and its runners-up, where the greedy search (ctc_scores.hip) gives the most likely frame path
+// and the aligner (ctc_align.hip) scores a given text.  The scores are on the aligner's scale, log p(y | x).  Two kernels:
+//   ctc_beam_cand_kernel    per packed frame row the log-softmax denominator (max, log-sum) and the ids of the `cand` largest
+//                           logits among the unmasked non-blank columns
+//   ctc_beam_search_kernel  one workgroup per utterance, a loop over its frames: beam, candidates and merge state in LDS, the trie
+//                           of label strings and its child table in global scratch, the back-trace of the n-best at the end
+// plus the plain-C++ twin of both (ss_ctc_beam_host) over the same step code (ctc_beam.hpp, where the search and its order are
+// defined).
+#include "ctc_beam.hpp"
+
+#include <cstring>
+
+#include "../../include/streamspeech_hip.h"
+#include "elementwise.hpp"
+
+namespace ss {
+
+namespace {
+constexpr int NONE = 0x7fffffff;
+}
+
+// One logits row per workgroup.  den[row] = (max, log-sum) with masked_argmax_lprob_kernel's arithmetic, operation for operation:
+// an f32 max, each thread's f32 sum of expf(x - max) in ascending stride, the xor-shuffle tree, the four wave partials in index
+// order, one logf -- (NaN, NaN) for a row that holds a NaN.  cand_id[row][k]: the k-th column in the order (logit descending, id
+// ascending) among the columns that are not blank, pad or unk and whose logit is above -inf; -1 where there are fewer.  One round
+// of the block per candidate: every thread offers its best column that comes after the last winner in that order.
+// PER > 0: N <= 256 * PER, the row is read once and kept in registers; PER == 0: any N, every pass reads the row again.
+template <int PER>
+__global__ __launch_bounds__(256) void ctc_beam_cand_kernel(const float* __restrict__ logits, int ld, int N, int pad, int unk, int C,
+                                                            float* __restrict__ den, int* __restrict__ cand_id) {
+  __shared__ float sm[4], ssum[4], swv[8];
+  __shared__ int sn[4], swi[8];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int row = blockIdx.x;
+  const float* r = logits + (size_t)row * ld;
+  float v[PER > 0 ? PER : 1];
+  float mx = -INFINITY;
+  int nan = 0;
+  if constexpr (PER > 0) {
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int n = t + 256 * i;
+      v[i] = n < N ? r[n] : -INFINITY;                         // past the row: no maximum, exp(-inf - max) = 0, never a candidate
+      nan |= (v[i] != v[i]);
+      mx = fmaxf(mx, v[i]);
+    }
+  } else {
+    for (int n = t; n < N; n += 256) { const float x = r[n]; nan |= (x != x); mx = fmaxf(mx, x); }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o, 64)); nan |= __shfl_xor(nan, o, 64); }
+  if (lane == 0) { sm[wave] = mx; sn[wave] = nan; }
+  __syncthreads();
+  mx = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+  float sum = 0.f;
+  if constexpr (PER > 0) {
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const float e = expf(v[i] - mx);
+      if (t + 256 * i < N) sum += e;
+    }
+  } else {
+    for (int n = t; n < N; n += 256) sum += expf(r[n] - mx);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  if (lane == 0) ssum[wave] = sum;
+  __syncthreads();
+  if (t == 0) {
+    const bool bad = sn[0] | sn[1] | sn[2] | sn[3];
+    den[2 * (size_t)row] = bad ? __builtin_nanf("") : mx;
+    den[2 * (size_t)row + 1] = bad ? __builtin_nanf("") : logf(((ssum[0] + ssum[1]) + ssum[2]) + ssum[3]);
+  }
+  // ---- the candidates: round k finds the k-th column of the order; (lv, li) is the winner of the round before ----
+  float lv = INFINITY;
+  int li = -1;
+  for (int k = 0; k < C; ++k) {
+    float bv = -INFINITY;
+    int bi = NONE;
+    auto offer = [&](int n, float x) {                         // n ascends per thread: the first maximum wins
+      if (n == 0 || n == pad || n == unk || !(x > -INFINITY)) return;
+      if (!(x < lv || (x == lv && n > li))) return;
+      if (bi == NONE || x > bv) { bv = x; bi = n; }
+    };
+    if constexpr (PER > 0) {
+#pragma unroll
+      for (int i = 0; i < PER; ++i) offer(t + 256 * i, v[i]);
+    } else {
+      for (int n = t; n < N; n += 256) offer(n, r[n]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (oi != NONE && (bi == NONE || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+    }
+    const int buf = (k & 1) * 4;                               // two sets of wave partials: one barrier per round
+    if (lane == 0) { swv[buf + wave] = bv; swi[buf + wave] = bi; }
+    __syncthreads();
+    bv = swv[buf]; bi = swi[buf];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+      const float ov = swv[buf + w];
+      const int oi = swi[buf + w];
+      if (oi != NONE && (bi == NONE || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+    }
+    if (t == 0) cand_id[(size_t)row * C + k] = bi == NONE ? -1 : bi;
+    lv = bi == NONE ? -INFINITY : bv;                          // nothing left: nothing comes after it either
+    li = bi;
+  }
+}
+
+// One utterance per workgroup, a loop over its frames with four barriers each (the trip count and every barrier are uniform: T,
+// the beam's size and the NaN exit are the same for all threads).
+//   A  the frame's values: lp of the blank, of the candidates and of every beam prefix's last label, as (x - max) - logsum from the
+//      row itself and the candidate kernel's den
+//   B  the entries e = r * (C + 1) + k (ctc_beam.hpp): a prefix's own stay terms; an extension's term and its node from the child
+//      table -- an extension whose node is in the beam hands its term to that prefix and dies
+//   C  each prefix's own entry: pnb' = logadd(stay, handed term), total = logadd(pb', pnb')
+//   D  every live entry counts the entries that come before it (ctc_beam_before); with fewer than `beam` of them it is the next
+//      beam's prefix of that rank, and makes its node if the string is new
+// The two beams are addressed by an integer offset (0 | CTC_BEAM_MAX_BEAM), never through a pointer picked at run time (see
+// ctc_align_trellis_kernel).  Every operation of an utterance happens inside its own workgroup in an order that depends on its own
+// data alone (node ids are ctc_beam_new_node's, not a counter's; the child table's contents depend on the insertion order only in
+// which of two colliding keys sits first, never in what a lookup returns), so its outputs are the same bits alone and in any pack.
+__global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __restrict__ logits, int ld, const CtcBeamSeg* __restrict__ segs,
+                                                              int beam, int C, int nbest, const float* den, const int* cand_id,
+                                                              unsigned long long* keys_all, int* vals_all, int2* nodes_all,
+                                                              ss_ctc_beam_hyp* hyps, int* tokens, int out_stride) {
+  constexpr int MB = CTC_BEAM_MAX_BEAM;
+  __shared__ double b_pb[2 * MB], b_pnb[2 * MB], b_tot[2 * MB];
+  __shared__ int b_node[2 * MB], b_last[2 * MB];
+  __shared__ double s_pb[MB], s_pnb[MB], s_give[MB];
+  __shared__ double e_tot[CTC_BEAM_MAX_ENT];
+  __shared__ int e_node[CTC_BEAM_MAX_ENT];
+  __shared__ int s_c[CTC_BEAM_MAX_CAND];
+  __shared__ float s_lpc[CTC_BEAM_MAX_CAND], s_lpl[MB], s_lp0;
+  __shared__ int s_nb[2];
+  const int tid = threadIdx.x;
+  const CtcBeamSeg sg = segs[blockIdx.x];
+  unsigned long long* keys = keys_all + sg.tab_off;
+  int* vals = vals_all + sg.tab_off;
+  int2* nodes = nodes_all + sg.node_off;
+  const int mask = sg.tab_mask, W = C + 1;
+  if (tid == 0) {
+    b_pb[0] = 0.0; b_pnb[0] = -INFINITY; b_tot[0] = 0.0; b_node[0] = 0; b_last[0] = -1;
+    s_nb[0] = 1;
+    nodes[0] = make_int2(-1, -1);
+  }
+  __syncthreads();
+  int cur = 0;
+  bool bad = false;
+  for (int t = 0; t < sg.T; ++t) {
+    const int row = sg.row0 + t, co = cur * MB, no = (cur ^ 1) * MB;
+    const int nb = s_nb[cur];
+    const float mx = den[2 * (size_t)row], ls = den[2 * (size_t)row + 1];
+    if (ls != ls) { bad = true; break; }                       // a NaN in the row (uniform: every thread reads the same pair)
+    const float* r = logits + (size_t)row * ld;
+    // ---- A ----
+    if (tid < C) {
+      const int c = cand_id[(size_t)row * C + tid];
+      s_c[tid] = c;
+      s_lpc[tid] = c >= 0 ? ctc_beam_lp(r[c], mx, ls) : -INFINITY;
+    } else if (tid >= 64 && tid < 64 + nb) {
+      const int i = tid - 64, last = b_last[co + i];
+      s_lpl[i] = last >= 0 ? ctc_beam_lp(r[last], mx, ls) : -INFINITY;
+      s_give[i] = -INFINITY;
+    } else if (tid == 128) {
+      s_lp0 = ctc_beam_lp(r[0], mx, ls);
+      s_nb[cur ^ 1] = 0;
+    }
+    __syncthreads();
+    // ---- B ----
+    const int n_ent = nb * W;
+    for (int e = tid; e < n_ent; e += 256) {
+      const int i = e / W, k = e - i * W - 1;
+      const int node = b_node[co + i], last = b_last[co + i];
+      if (k < 0) {
+        double pb2, pnb2;
+        ctc_beam_stay(b_pnb[co + i], b_tot[co + i], last, s_lp0, s_lpl[i], &pb2, &pnb2);
+        s_pb[i] = pb2; s_pnb[i] = pnb2;
+        e_node[e] = node;                                      // (its total: pass C)
+        continue;
+      }
+      const int c = s_c[k];
+      double term = -INFINITY;
+      int child = -1;
+      if (c >= 0) {
+        term = ctc_beam_ext(b_pb[co + i], b_tot[co + i], last, c, s_lpc[k]);
+        child = ctc_beam_find(keys, vals, mask, node, c);
+        if (child >= 0) {
+          for (int j = 0; j < nb; ++j) {
+            if (b_node[co + j] == child) { s_give[j] = term; term = -INFINITY; break; }   // one parent per string: one writer per j
+          }
+        }
+      }
+      e_tot[e] = term;
+      e_node[e] = child;
+    }
+    __syncthreads();
+    // ---- C ----
+    if (tid < nb) {
+      const double pnb2 = ctc_beam_logadd(s_pnb[tid], s_give[tid]);
+      s_pnb[tid] = pnb2;
+      e_tot[tid * W] = ctc_beam_logadd(s_pb[tid], pnb2);
+    }
+    __syncthreads();
+    // ---- D ---- (a thread's up to PER entries count in ONE walk over the frame's totals: each total is read once per thread,
+    //               and no exit depends on a count, so the loads of the unrolled walk overlap)
+    constexpr int PER = (CTC_BEAM_MAX_ENT + 255) / 256;
+    double my_tot[PER];
+    int my_rank[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const int e = tid + 256 * j;
+      my_tot[j] = e < n_ent ? e_tot[e] : -INFINITY;
+      my_rank[j] = 0;
+    }
+    if (n_ent > 256 || my_tot[0] > -INFINITY) {
+#pragma unroll 4
+      for (int f = 0; f < n_ent; ++f) {
+        const double tf = e_tot[f];
+#pragma unroll
+        for (int j = 0; j < PER; ++j) my_rank[j] += ctc_beam_before(tf, f, my_tot[j], tid + 256 * j);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const int e = tid + 256 * j, rank = my_rank[j];
+      const double tot = my_tot[j];
+      if (!(tot > -INFINITY) || rank >= beam) continue;       // (an entry past n_ent is -inf)
+      const int i = e / W, k = e - i * W - 1;
+      int node = e_node[e];
+      if (k < 0) {
+        b_pb[no + rank] = s_pb[i]; b_pnb[no + rank] = s_pnb[i]; b_last[no + rank] = b_last[co + i];
+      } else {
+        const int c = s_c[k];
+        if (node < 0) {                                        // a new string: its node, then its place in the child table
+          node = ctc_beam_new_node(t, beam, rank);
+          nodes[node] = make_int2(b_node[co + i], c);
+          const unsigned long long key = ctc_beam_key(b_node[co + i], c);
+          for (int s = ctc_beam_slot(key, mask), n = 0; n <= mask; ++n, s = (s + 1) & mask) {
+            if (atomicCAS(&keys[s], CTC_BEAM_EMPTY, key) == CTC_BEAM_EMPTY) { vals[s] = node; break; }
+          }
+        }
+        b_pb[no + rank] = -INFINITY; b_pnb[no + rank] = tot; b_last[no + rank] = c;
+      }
+      b_tot[no + rank] = tot; b_node[no + rank] = node;
+      atomicMax(&s_nb[cur ^ 1], rank + 1);                     // ranks are 0 .. alive - 1 without a gap
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  // ---- the n-best: the last beam in rank order; thread r walks prefix r back through the trie ----
+  if (tid < nbest) {
+    const int nb = bad ? 0 : s_nb[cur];
+    ss_ctc_beam_hyp h;
+    h.score = bad ? (double)__builtin_nanf("") : -INFINITY;
+    h.n_tokens = 0;
+    h.status = bad ? 2 : 1;
+    if (tid < nb) {
+      const int node = b_node[cur * MB + tid];
+      int len = 0;
+      for (int n = node; n > 0; n = nodes[n].x) ++len;
+      int* out = tokens + ((size_t)blockIdx.x * nbest + tid) * out_stride;
+      int j = len;
+      for (int n = node; n > 0 && j > 0; n = nodes[n].x) out[--j] = nodes[n].y;
+      h.score = b_tot[cur * MB + tid]; h.n_tokens = len; h.status = 0;
+    }
+    hyps[(size_t)blockIdx.x * nbest + tid] = h;
+  }
+}
+
+size_t ctc_beam_table_bytes(const CtcBeamPlan& p) { return p.segs.size() * sizeof(CtcBeamSeg); }
+
+int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
+                    ss_ctc_beam_hyp* hyps, int* tokens, int out_stride, float* den_out, int* cand_out, hipStream_t stream) {
+  const int B = (int)p.segs.size();
+  if (!logits || ld < V || B <= 0 || !d_table || !d_work || !hyps || !tokens) return SS_ERR_ARG;
+  unsigned char* w = static_cast<unsigned char*>(d_work);
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(w);
+  int2* nodes = reinterpret_cast<int2*>(w + p.key_bytes());
+  int* vals = reinterpret_cast<int*>(w + p.key_bytes() + (size_t)p.nodes * 8);
+  float* den = reinterpret_cast<float*>(w + (size_t)p.slots * 12 + (size_t)p.nodes * 8);
+  int* cand = reinterpret_cast<int*>(den + 2 * (size_t)p.rows);
+  if (den_out) den = den_out;
+  if (cand_out) cand = cand_out;
+  SS_HIP_CHECK(hipMemcpyAsync(d_table, p.segs.data(), ctc_beam_table_bytes(p), hipMemcpyHostToDevice, stream));
+  SS_HIP_CHECK(hipMemsetAsync(keys, 0xff, p.key_bytes(), stream));
+#define SS_CBC(PER)                                                                                                              \
+  hipLaunchKernelGGL(ctc_beam_cand_kernel<PER>, dim3(p.rows), dim3(256), 0, stream, logits, ld, V, pad, unk, p.cand, den, cand)
+  if (V <= 2048) SS_CBC(8);
+  else if (V <= 4096) SS_CBC(16);
+  else if (V <= 6144) SS_CBC(24);
+  else if (V <= 8192) SS_CBC(32);
+  else SS_CBC(0);
+#undef SS_CBC
+  SS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(B), dim3(256), 0, stream, logits, ld, static_cast<const CtcBeamSeg*>(d_table), p.beam,
+                     p.cand, p.nbest, den, cand, keys, vals, nodes, hyps, tokens, out_stride);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+namespace {
+
+int g_host_max_beam = CTC_BEAM_MAX_BEAM;      // ss_debug_ctc_beam_host_max: the host twin's cap alone (the exhaustive test)
+
+// ctc_beam_cand_kernel's denominator on the host, in the device's order (ctc_align.hip: row_stats_host).
+void row_den_host(const float* r, int N, float* den) {
+  float mx = -INFINITY;
+  bool nan = false;
+  for (int n = 0; n < N; ++n) { nan |= r[n] != r[n]; mx = fmaxf(mx, r[n]); }
+  float part[256], tmp[256];
+  for (int t = 0; t < 256; ++t) {
+    float s = 0.f;
+    for (int n = t; n < N; n += 256) s += expf(r[n] - mx);
+    part[t] = s;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    for (int t = 0; t < 256; ++t) tmp[t] = part[t] + part[t ^ o];
+    memcpy(part, tmp, sizeof(part));
+  }
+  den[0] = nan ? __builtin_nanf("") : mx;
+  den[1] = nan ? __builtin_nanf("") : logf(((part[0] + part[64]) + part[128]) + part[192]);
+}
+
+void row_cand_host(const float* r, int N, int pad, int unk, int C, int* out) {
+  float lv = INFINITY;
+  int li = -1;
+  for (int k = 0; k < C; ++k) {
+    float bv = -INFINITY;
+    int bi = NONE;
+    for (int n = 1; n < N; ++n) {
+      const float x = r[n];
+      if (n == pad || n == unk || !(x > -INFINITY) || !(x < lv || (x == lv && n > li))) continue;
+      if (bi == NONE || x > bv) { bv = x; bi = n; }
+    }
+    out[k] = bi == NONE ? -1 : bi;
+    lv = bi == NONE ? -INFINITY : bv;
+    li = bi;
+  }
+}
+
+}  // namespace
+
+}  // namespace ss
+
+using namespace ss;
+
+extern "C" int ss_debug_ctc_beam_host_max(int max_beam) {
+  const int was = g_host_max_beam;
+  if (max_beam >= 1) g_host_max_beam = max_beam;
+  return was;
+}
+
+extern "C" int ss_ctc_beam_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
+                                int nbest, ss_ctc_beam_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den,
+                                int32_t* h_cand_id) {
+  if (!h_logits || ld < V || !h_hyps || !h_tokens) return SS_ERR_ARG;
+  CtcBeamPlan p;
+  const int rc = ctc_beam_plan(V, B, h_T, beam, cand, nbest, out_stride, p, g_host_max_beam);
+  if (rc != SS_OK) return rc;
+  const int C = cand, W = C + 1;
+  struct Pre { double pb, pnb, tot; int node, last; };
+  for (int b = 0; b < B; ++b) {
+    const CtcBeamSeg& sg = p.segs[b];
+    const int mask = sg.tab_mask;
+    std::vector<unsigned long long> keys((size_t)mask + 1, CTC_BEAM_EMPTY);
+    std::vector<int> vals((size_t)mask + 1, -1), par(1 + (size_t)beam * sg.T, -1), tok(1 + (size_t)beam * sg.T, -1);
+    std::vector<Pre> bm(1, Pre{0.0, -INFINITY, 0.0, 0, -1}), nx;
+    std::vector<double> e_tot, s_pb, s_pnb, s_give;
+    std::vector<int> e_node, cid_all((size_t)sg.T * C);
+    std::vector<float> den_all(2 * (size_t)sg.T);
+    for (int t = 0; t < sg.T; ++t) {                           // the candidate kernel: every row, whatever the search makes of it
+      const float* r = h_logits + (size_t)(sg.row0 + t) * ld;
+      row_den_host(r, V, &den_all[2 * (size_t)t]);
+      row_cand_host(r, V, pad, unk, C, &cid_all[(size_t)t * C]);
+    }
+    if (h_den) memcpy(h_den + 2 * (size_t)sg.row0, den_all.data(), den_all.size() * sizeof(float));
+    if (h_cand_id) memcpy(h_cand_id + (size_t)sg.row0 * C, cid_all.data(), cid_all.size() * sizeof(int));
+    bool bad = false;
+    for (int t = 0; t < sg.T; ++t) {
+      const float* r = h_logits + (size_t)(sg.row0 + t) * ld;
+      const float* den = &den_all[2 * (size_t)t];
+      const int* cid = &cid_all[(size_t)t * C];
+      if (den[1] != den[1]) { bad = true; break; }
+      const int nb = (int)bm.size(), n_ent = nb * W;
+      const float lp0 = ctc_beam_lp(r[0], den[0], den[1]);
+      e_tot.assign(n_ent, -INFINITY); e_node.assign(n_ent, -1);
+      s_pb.assign(nb, -INFINITY); s_pnb.assign(nb, -INFINITY); s_give.assign(nb, -INFINITY);
+      for (int e = 0; e < n_ent; ++e) {                        // B
+        const int i = e / W, k = e - i * W - 1;
+        const Pre& q = bm[i];
+        if (k < 0) {
+          ctc_beam_stay(q.pnb, q.tot, q.last, lp0, q.last >= 0 ? ctc_beam_lp(r[q.last], den[0], den[1]) : -INFINITY, &s_pb[i], &s_pnb[i]);
+          e_node[e] = q.node;
+          continue;
+        }
+        const int c = cid[k];
+        if (c < 0) continue;
+        double term = ctc_beam_ext(q.pb, q.tot, q.last, c, ctc_beam_lp(r[c], den[0], den[1]));
+        const int child = ctc_beam_find(keys.data(), vals.data(), mask, q.node, c);
+        if (child >= 0) {
+          for (int j = 0; j < nb; ++j) {
+            if (bm[j].node == child) { s_give[j] = term; term = -INFINITY; break; }
+          }
+        }
+        e_tot[e] = term; e_node[e] = child;
+      }
+      for (int i = 0; i < nb; ++i) {                           // C
+        s_pnb[i] = ctc_beam_logadd(s_pnb[i], s_give[i]);
+        e_tot[i * W] = ctc_beam_logadd(s_pb[i], s_pnb[i]);
+      }
+      nx.assign(beam, Pre{0, 0, 0, -1, -1});                   // D
+      int alive = 0;
+      for (int e = 0; e < n_ent; ++e) {
+        const double tot = e_tot[e];
+        if (!(tot > -INFINITY)) continue;
+        int rank = 0;
+        for (int f = 0; f < n_ent && rank < beam; ++f) rank += ctc_beam_before(e_tot[f], f, tot, e);
+        if (rank >= beam) continue;
+        const int i = e / W, k = e - i * W - 1;
+        int node = e_node[e];
+        if (k < 0) {
+          nx[rank] = Pre{s_pb[i], s_pnb[i], tot, node, bm[i].last};
+        } else {
+          const int c = cid[k];
+          if (node < 0) {
+            node = ctc_beam_new_node(t, beam, rank);
+            par[node] = bm[i].node; tok[node] = c;
+            const unsigned long long key = ctc_beam_key(bm[i].node, c);
+            for (int s = ctc_beam_slot(key, mask), n = 0; n <= mask; ++n, s = (s + 1) & mask) {
+              if (keys[s] == CTC_BEAM_EMPTY) { keys[s] = key; vals[s] = node; break; }
+            }
+          }
+          nx[rank] = Pre{-INFINITY, tot, tot, node, c};
+        }
+        if (rank + 1 > alive) alive = rank + 1;
+      }
+      nx.resize(alive);
+      bm.swap(nx);
+    }
+    for (int k = 0; k < nbest; ++k) {
+      ss_ctc_beam_hyp& h = h_hyps[(size_t)b * nbest + k];
+      h.score = bad ? (double)__builtin_nanf("") : -INFINITY; h.n_tokens = 0; h.status = bad ? 2 : 1;
+      if (bad || k >= (int)bm.size()) continue;
+      int len = 0;
+      for (int n = bm[k].node; n > 0; n = par[n]) ++len;
+      int32_t* out = h_tokens + ((size_t)b * nbest + k) * out_stride;
+      int j = len;
+      for (int n = bm[k].node; n > 0; n = par[n]) out[--j] = tok[n];
+      h.score = bm[k].tot; h.n_tokens = len; h.status = 0;
+    }
+  }
+  return SS_OK;
+}

@@ -1,6 +1,7 @@
 // Op-level unit-test entry points (ss_op_*), test / A-B hooks (ss_debug_*) and the profiler's C ABI (ss_prof_*).
 #include "model_internal.hpp"
 #include "ctc_align.hpp"
+#include "ctc_beam.hpp"
 
 // =================================================================================================
 // op-level entry points
@@ -273,6 +274,20 @@ extern "C" int ss_op_ctc_align(void* stream, const float* d_logits, int ld, int 
   RET(tmp.second.ensure(plan.work_bytes()));
   return launch_ctc_align(d_logits, ld, V, plan, h_targets, tmp.first.p, tmp.second.p, d_results, d_path, d_first, d_last, d_tok_lprob,
                           d_frame_lprob, (hipStream_t)stream);
+}
+// the two prefix-search kernels on the caller's logits; scratch as ss_op_ctc_align's
+extern "C" int ss_op_ctc_beam(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam,
+                              int cand, int nbest, ss_ctc_beam_hyp* d_hyps, int32_t* d_tokens, int out_stride, float* d_den,
+                              int32_t* d_cand_id) {
+  if (!d_logits || ld < V || !d_hyps || !d_tokens) return SS_ERR_ARG;
+  CtcBeamPlan plan;
+  RET(ctc_beam_plan(V, B, h_T, beam, cand, nbest, out_stride, plan));
+  static thread_local std::map<hipStream_t, std::pair<DevBuf, DevBuf>> tmps;
+  auto& tmp = tmps[(hipStream_t)stream];
+  RET(tmp.first.ensure(ctc_beam_table_bytes(plan)));
+  RET(tmp.second.ensure(plan.work_bytes()));
+  return launch_ctc_beam(d_logits, ld, V, pad, unk, plan, tmp.first.p, tmp.second.p, d_hyps, d_tokens, out_stride, d_den, d_cand_id,
+                         (hipStream_t)stream);
 }
 extern "C" int ss_op_dur_predict(void* stream, const float* logdur, const int32_t* forced, int K, int32_t* dur, int32_t* cum,
                                  const int32_t* segs, int nseg) {

@@ -4,6 +4,7 @@
 #include "common.hpp"
 
 struct ss_ctc_align_result;          // include/streamspeech_hip.h
+struct ss_ctc_beam_hyp;
 
 namespace ss {
 
@@ -90,6 +91,17 @@ size_t ctc_align_table_bytes(const CtcAlignPlan& p);
 int launch_ctc_align(const float* logits, int ld, int V, const CtcAlignPlan& p, const int32_t* h_targets, void* d_table, void* d_work,
                      ss_ctc_align_result* results, int* path, int* first, int* last, float* tok_lprob, float* frame_lprob,
                      hipStream_t stream);
+
+// CTC prefix beam search (ctc_beam.hip; the plan, its checks, its limits and the search's definition: ctc_beam.hpp).  A fill of the
+// child tables and two launches over a checked plan: per packed frame row the log-softmax denominator (den [rows][2]: max, log-sum,
+// the arithmetic of launch_masked_argmax_lprob) and the ids of the plan's `cand` largest unmasked non-blank logits (cand_id
+// [rows][cand], -1 where there are fewer), then one workgroup per utterance for the search and the back-trace of its n-best.
+// d_table (ctc_beam_table_bytes) and d_work (plan.work_bytes()) are the caller's scratch; den_out / cand_out, when given, receive
+// the first kernel's outputs instead of d_work.  An utterance's outputs are the same bits alone and at any place of any pack.
+struct CtcBeamPlan;
+size_t ctc_beam_table_bytes(const CtcBeamPlan& p);
+int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
+                    ss_ctc_beam_hyp* hyps, int* tokens, int out_stride, float* den_out, int* cand_out, hipStream_t stream);
 
 // emb_out[k,:] = table[codes[k],:]
 int launch_gather_rows(const int* idx, const float* table, int D, float* out, int n, hipStream_t stream, int rows);  // ids outside [0, rows) read row 0

@@ -68,6 +68,19 @@ class CtcAlignment(NamedTuple):
     tok_lprob: np.ndarray   # per label, the float32 sum of the per-frame log-probability over that run (NaN where there is no path)
 
 
+class CtcHypothesis(NamedTuple):
+    """One hypothesis of batch_ctc_beam."""
+    tokens: List[int]       # the labels (never blank, pad or unk)
+    score: float            # log of the summed probability of its alignments: the scale of CtcAlignment.score
+
+
+def ctc_beam_default_cand(beam: int) -> int:
+    """Candidates per frame when the caller names none: beam + 1, up to the library's cap.  A new string enters the beam only past
+    the extensions of its own parent by better tokens, and at most one of those is the parent's last label (the one token whose
+    extension weighs less), so no token below place beam + 1 of a frame can bring a new string into a beam of `beam`."""
+    return min(L.CTC_BEAM_MAX_CAND, int(beam) + 1)
+
+
 def resample_ratio(sr_in: int, sr_out: int = 16000) -> Tuple[int, int, int]:
     """(up, down, half_len) of the resampler from sr_in to sr_out: the ratio in lowest terms and the taps on either side of the
     centre of frontend.design_filter's low-pass (0 when nothing is resampled)."""
@@ -278,6 +291,32 @@ class BatchMixin:
                                     host[a:z].tolist(), host[a + nl:z + nl].tolist(), fl[a + 2 * nl:z + 2 * nl].copy()))
             r0 += int(Tp[b])
             l0 += n[b]
+        return out
+
+    def batch_ctc_beam(self, head: int, enc_packed: torch.Tensor, Tp: List[int], beam: int, cand: Optional[int] = None,
+                       nbest: Optional[int] = None) -> List[List[CtcHypothesis]]:
+        """CTC prefix beam search on a text head (ss_batch_ctc_beam): per utterance its `nbest` (default: beam) most likely label
+        strings, best first, each with the log of the summed probability of its alignments.  The rows are packed as
+        batch_ctc_greedy takes them.  Fewer than nbest come back where fewer prefixes are alive, none for an utterance with a NaN
+        in a row.  cand: candidates per frame (default ctc_beam_default_cand).  One buffer, one device-to-host copy.  The library
+        refuses (SS_ERR_ARG, nothing launched) a beam / cand above L.CTC_BEAM_MAX_BEAM / _CAND, an nbest outside [1, beam] and
+        more than L.CTC_BEAM_MAX_FRAMES frames per utterance."""
+        B = len(Tp)
+        cand = ctc_beam_default_cand(beam) if cand is None else int(cand)
+        nbest = int(beam) if nbest is None else int(nbest)
+        stride = max([int(t) for t in Tp] + [1])
+        n = B * max(nbest, 0)
+        # int32 words: hyps [4 n] (a double and two ints each, first: 8-byte aligned) | tokens [n][stride]
+        ibuf = torch.empty((4 * n + n * stride + 1,), dtype=torch.int32, device=self.device)
+        L.check(self.lib.ss_batch_ctc_beam(self.h, _stream(), head, B, _ptr(enc_packed), _i32(Tp), int(beam), cand, nbest, _ptr(ibuf),
+                                           _ptr(ibuf[4 * n:]), stride), "ss_batch_ctc_beam")
+        host = ibuf.cpu().numpy()
+        hyp = host[:4 * n].view(np.dtype([("score", "<f8"), ("n_tokens", "<i4"), ("status", "<i4")]))
+        out = []
+        for b in range(B):
+            out.append([CtcHypothesis(host[4 * n + k * stride: 4 * n + k * stride + int(hyp["n_tokens"][k])].tolist(),
+                                      float(hyp["score"][k]))
+                        for k in range(b * nbest, (b + 1) * nbest) if hyp["status"][k] == 0])
         return out
 
     def batch_mt_greedy(self, enc_packed: torch.Tensor, Tp: List[int], max_len: List[int], min_len: int = 1):
@@ -925,6 +964,11 @@ class HipModel(BatchMixin):
     def ctc_align(self, head: int, enc_out: torch.Tensor, tokens: List[int], want_path: bool = True) -> CtcAlignment:
         """Forced alignment of one utterance: the B = 1 call of batch_ctc_align."""
         return self.batch_ctc_align(head, enc_out.contiguous(), [int(enc_out.shape[0])], [list(tokens)], want_path)[0]
+
+    def ctc_beam(self, head: int, enc_out: torch.Tensor, beam: int, cand: Optional[int] = None,
+                 nbest: Optional[int] = None) -> List[CtcHypothesis]:
+        """CTC prefix beam search of one utterance: the B = 1 call of batch_ctc_beam."""
+        return self.batch_ctc_beam(head, enc_out.contiguous(), [int(enc_out.shape[0])], beam, cand, nbest)[0]
 
     def ctc_greedy(self, head: int, enc_out: torch.Tensor, want_logits: bool = False, want_scores: bool = False):
         """-> (tokens list, frame index list, raw argmax tensor, logits or None); with want_scores three more: last frame per token

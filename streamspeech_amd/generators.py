@@ -70,6 +70,18 @@ class CTCDecoder:
                   "viterbi_score": a.viterbi_score, "status": a.status, "path": a.path, "attn": None, "alignment": None}]]
 
 
+    @torch.no_grad()
+    def beam_search(self, encoder_out, beam, cand=None, nbest=None, **kw):
+        """CTC prefix beam search on this head: what generate takes plus the beam -> [[hypothesis, ...]] best first, each with
+        `tokens` (never blank, pad or unk) and `score`, the log of the summed probability of the alignments of those tokens --
+        the scale of align's `score`, so align(encoder_out, h["tokens"]) places a hypothesis in time for words.*."""
+        enc = encoder_out["encoder_out"][0]
+        enc = enc[:, 0] if enc.dim() == 3 else enc
+        hyps = self.engine.ctc_beam(self.head, enc.contiguous(), int(beam), cand, nbest)
+        return [[{"tokens": torch.tensor(h.tokens, dtype=torch.long), "score": h.score, "attn": None, "alignment": None,
+                  "positional_scores": None} for h in hyps]]
+
+
 class CTCSequenceGenerator:
     """agent/ctc_generator.py:26-123 -- NAR unit search over the T2U+unit-decoder stage
     (blank = tgt_dict.blank_index = 1004)."""

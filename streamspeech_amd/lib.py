@@ -73,6 +73,16 @@ CTC_ALIGN_MAX_FRAMES = 1500     # SS_CTC_ALIGN_MAX_FRAMES / SS_CTC_ALIGN_MAX_LAB
 CTC_ALIGN_MAX_LABELS = 1500
 
 
+class SSCtcBeamHyp(C.Structure):
+    """ss_ctc_beam_hyp: one hypothesis of the CTC prefix beam search (16 bytes)."""
+    _fields_ = [("score", C.c_double), ("n_tokens", C.c_int32), ("status", C.c_int32)]
+
+
+CTC_BEAM_MAX_BEAM = 32          # SS_CTC_BEAM_MAX_BEAM / _CAND / _FRAMES of the header
+CTC_BEAM_MAX_CAND = 32
+CTC_BEAM_MAX_FRAMES = 1500
+
+
 class SSOpAttnArgs(C.Structure):
     """ss_op_attn_args: AttnArgs (csrc/attention.hpp) field for field, pointers as device addresses."""
     _fields_ = [
@@ -259,6 +269,8 @@ SIGNATURES = {
                                 _vp, _vp]),
     "ss_ctc_align_host": (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp,
                                _vp, _vp, _vp]),
+    "ss_batch_ctc_beam": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i]),
+    "ss_ctc_beam_host": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "ss_batch_mt_greedy": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
                                 C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _vp, _i]),
     "ss_batch_mt_beam": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _f, _i,
@@ -375,6 +387,8 @@ SIGNATURES = {
     "ss_op_ctc_collapse_spans": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "ss_op_ctc_align": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp,
                              _vp, _vp, _vp]),
+    "ss_op_ctc_beam": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "ss_debug_ctc_beam_host_max": (_i, [_i]),
     "ss_op_dur_predict": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
     "ss_op_repeat_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),
     "ss_op_embed_tokens": (_i, [_vp, _vp, _vp, _vp, _f, _i, _vp, _i, _i, _i, _i, _i]),

@@ -99,7 +99,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              temperature: float = 1.0, no_repeat_ngram_size: int = 0,
              references: Optional[Dict[str, Dict[int, Sequence[int]]]] = None, spoken_words: bool = False,
              mt_references: Optional[Dict[int, Sequence[int]]] = None, speak_reference: bool = False, sampling: bool = False,
-             sampling_topk: int = -1, sampling_topp: float = -1.0, seed: int = 1) -> Dict[int, Dict]:
+             sampling_topk: int = -1, sampling_topp: float = -1.0, seed: int = 1, ctc_beam: int = 0,
+             ctc_beam_cand: Optional[int] = None, ctc_nbest: Optional[int] = None) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
@@ -133,8 +134,16 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     speak_reference (--speak-reference; needs mt_references): the scored rows' decoder states also go through batch_t2u_units and
     vocoder.batch_forward (speaker_id and dur_prediction as for the hypotheses) into generate-<subset>.ref.unit and
     ref_wav/<n>_pred.wav, laid out as .unit and pred_wav/ are (a line / a number per sample id; a sample without spoken reference has
-    an empty line and no file)."""
+    an empty line and no file).
+    ctc_beam / ctc_beam_cand / ctc_nbest (--ctc-beam K, --ctc-beam-cand C, --ctc-nbest N): one CTC prefix beam search per text head
+    after each batch's encoder (batch_ctc_beam: beam K, C candidates per frame -- default engine.ctc_beam_default_cand -- the N <= K
+    best, default K); writes generate-<subset>.asr.nbest and .st.nbest (id, rank, score in natural log, n_tokens, text; N rows per
+    id in rank order, a slot without hypothesis as score -inf, 0 tokens and no text) and changes no other file: the `A-` / `S-`
+    lines stay the arg-max."""
     from .engine import check_search_options, sampling_from_fairseq
+    nbest_ctc: Dict[str, Dict[int, list]] = {"asr": {}, "st": {}}
+    if ctc_beam:
+        ctc_nbest = int(ctc_beam) if ctc_nbest is None else int(ctc_nbest)
     sampler = sampling_from_fairseq(sampling, sampling_topk, sampling_topp, seed)
     samples: Dict[int, list] = {}
     if spoken_words and not dump_wav:
@@ -193,6 +202,10 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
             st = model.batch_ctc_greedy(1, enc, Tp)
         if references is not None:
             _align_references(model, enc, Tp, ids, references, dicts, ref_words, ref_scores)
+        if ctc_beam:
+            for hd, key in ((0, "asr"), (1, "st")):
+                for sid, lst in zip(ids, model.batch_ctc_beam(hd, enc, Tp, ctc_beam, ctc_beam_cand, ctc_nbest)):
+                    nbest_ctc[key][sid] = lst
         # first-pass text search: max_len = min(int(max_len_a_mt * src_len + max_len_b_mt), max positions - 1) with
         # the task's defaults 0 / 200 (tasks/speech_to_speech_ctc.py:39-40 -> sequence_generator_multi_decoder_ctc.py
         # :130-131); src_len is the fbank frame count.  --max-len-a/-b configure the (NAR) unit generator, which has
@@ -298,6 +311,17 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
                     n, score, vit, status = ref_scores.get((sid, key), (0 if ref is None else len(ref), float("nan"), float("nan"),
                                                                        "no_reference" if ref is None else "no_audio"))
                     print(f"{sid}\t{key}\t{n}\t{score:.6f}\t{vit:.6f}\t{status}", file=f)
+    if ctc_beam:
+        for key, name in (("asr", "source_unigram"), ("st", "ctc_target_unigram")):
+            with open(os.path.join(results_path, f"generate-{subset}.{key}.nbest"), "w", encoding="utf-8") as f:
+                for sid in sorted(hyps):
+                    lst = nbest_ctc[key].get(sid, [])
+                    for rank in range(ctc_nbest):
+                        if rank < len(lst):
+                            text = detok([dicts[name][c] for c in lst[rank].tokens])
+                            print(f"{sid}\t{rank}\t{lst[rank].score:.6f}\t{len(lst[rank].tokens)}\t{text}", file=f)
+                        else:
+                            print(f"{sid}\t{rank}\t-inf\t0\t", file=f)
     if spoken_words:
         with open(os.path.join(results_path, f"generate-{subset}.spoken.words"), "w", encoding="utf-8") as f:
             for sid in sorted(spoken):
@@ -634,6 +658,13 @@ def build_parser() -> argparse.ArgumentParser:
                          "and ctc_target_unigram) to the audio on both CTC heads: writes generate-<subset>.asr.ref.words / .st.ref.words "
                          "(id, word, start_ms, end_ms, confidence) and generate-<subset>.ref.scores (id, head, n_tokens, log_likelihood, "
                          "viterbi_score, status); needs a manifest")
+    ap.add_argument("--ctc-beam", type=int, default=0,
+                    help="also run a CTC prefix beam search of this beam (1 .. 32) on both CTC heads: writes generate-<subset>.asr.nbest "
+                         "and .st.nbest (id, rank, score, n_tokens, text), the most likely texts summed over their alignments; the "
+                         "A- / S- lines stay the arg-max (0 = off)")
+    ap.add_argument("--ctc-beam-cand", type=int, default=None,
+                    help="with --ctc-beam: tokens a prefix is extended by per frame (1 .. 32; default beam + 1, at most 32)")
+    ap.add_argument("--ctc-nbest", type=int, default=None, help="with --ctc-beam: hypotheses written per id (1 .. beam; default the beam)")
     ap.add_argument("--score-reference", action="store_true",
                     help="also score the recipe's reference translation (the multitask manifest <task data>/<gen-subset>.tsv of "
                          "target_unigram) with the first-pass text decoder, teacher-forced, as fairseq's --score-reference does: writes "
@@ -683,6 +714,16 @@ def main(argv: Optional[List[str]] = None):
         sampling_from_fairseq(a.sampling, a.sampling_topk, a.sampling_topp, a.seed)
     except ValueError as e:
         ap.error(str(e))
+    if a.ctc_beam:
+        from .lib import CTC_BEAM_MAX_BEAM, CTC_BEAM_MAX_CAND
+        if not 1 <= a.ctc_beam <= CTC_BEAM_MAX_BEAM:
+            ap.error(f"--ctc-beam must be in [1, {CTC_BEAM_MAX_BEAM}]")
+        if a.ctc_beam_cand is not None and not 1 <= a.ctc_beam_cand <= CTC_BEAM_MAX_CAND:
+            ap.error(f"--ctc-beam-cand must be in [1, {CTC_BEAM_MAX_CAND}]")
+        if a.ctc_nbest is not None and not 1 <= a.ctc_nbest <= a.ctc_beam:
+            ap.error("--ctc-nbest must be in [1, --ctc-beam]")
+    elif a.ctc_beam_cand is not None or a.ctc_nbest is not None:
+        ap.error("--ctc-beam-cand and --ctc-nbest need --ctc-beam")
     if a.spoken_words and a.no_wav:
         ap.error("--spoken-words needs the durations the vocoder predicts: it cannot be combined with --no-wav")
     if a.align_reference and (a.wav_list or a.synthetic > 0 or not a.data):
@@ -794,7 +835,8 @@ def main(argv: Optional[List[str]] = None):
                     **({"len_penalty": a.lenpen, "no_repeat_ngram_size": a.no_repeat_ngram_size}
                        if (a.lenpen, a.no_repeat_ngram_size) != (1.0, 0) else {}),
                     **({"sampling": True, "sampling_topk": a.sampling_topk, "sampling_topp": a.sampling_topp, "seed": a.seed}
-                       if a.sampling else {}))
+                       if a.sampling else {}),
+                    **({"ctc_beam": a.ctc_beam, "ctc_beam_cand": a.ctc_beam_cand, "ctc_nbest": a.ctc_nbest} if a.ctc_beam else {}))
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
 
 
