@@ -985,6 +985,68 @@ int ss_batch_mt_sample_continue(ss_model* m, void* stream, int B, int beam, cons
                                 float unk_penalty, int normalize, int32_t* h_out_tokens, int out_stride, int32_t* h_n_out,
                                 float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows, const ss_mt_search_opts* opts,
                                 const int64_t* h_keys, const ss_mt_sample_opts* sample);
+/* Lexically constrained beam search of the first-pass text decoder: the reference's --constraints with the `ordered`
+ * representation (fairseq/fairseq/search.py::LexicallyConstrainedBeamSearch over token_generation_constraints.py
+ * ::OrderedConstraintState; Post & Vilar 2018, Hu et al. 2019).  Phrases that must stand in every returned hypothesis, in the order
+ * given, with anything between them.
+ *
+ * THE RULE.  An utterance has phrases p_1 .. p_n of token ids; seq is their concatenation, C = len(seq) <= SS_MT_CONS_MAX_TOKENS,
+ * end[i] is set at the last token of each phrase, and U is the number of DISTINCT ids in seq (the reference's
+ * num_constraint_tokens = len(state.tokens), a set: U = C unless an id recurs).  Every hypothesis carries state in -1 .. C - 1:
+ * bank = state + 1 tokens of seq are out, finished = (state + 1 == C).  advance(state, tok), first case that holds:
+ *   1. finished -> state;  2. seq[state + 1] == tok -> state + 1;  3. state == -1 or end[state] -> state;
+ *   4. tok == seq[0] -> 0;  5. -1.
+ * Case 3 at state -1 is the reference reading endpoints[-1], which Python takes as the LAST element, always set: a hypothesis at
+ * the root stays there (cases 4 and 5 would say the same, case 2 having failed).
+ * Per step, for each utterance, in the order of LexicallyConstrainedBeamSearch.step / step_sentence:
+ *   1. At step > 0, </s> of a row whose state is not finished is -inf: after every other mask (NaN, pad, unk, max_len, min_len,
+ *      the no-repeat ban) and before the cumulative score is added.
+ *   2. The candidate list: (a) the global top 2k over beam x vocab, in the plain search's order (score, then flattened index);
+ *      (b) at step > 0 the best candidate of each row, rows ascending; (c) for each row ascending (row 0 alone at step 0) its next
+ *      tokens with their scores from the row: seq[0] if state > 0, seq[state + 1] if not finished -- ascending id, once if equal
+ *      (the reference iterates a Python set of them; the outcome cannot depend on that order, see 4 and 5).
+ *   3. new_state = advance(state[beam], tok) and bank = new_state + 1 of every candidate.
+ *   4. key = (float)((U - bank) * -100) + score: the integer product converted to float32, then one float32 add.  Sort by key
+ *      descending, ties by position in the list of 2.
+ *   5. Of candidates with the same (beam, tok) the first in that order stays.
+ *   6. Order by (rank within the own bank, then higher bank first): round-robin over the banks, furthest-along first.
+ *   7. The first 2k are the step's cand_scores / cand_indices / cand_beams; finalisation, the ignore list, the active hypotheses
+ *      and `done` are the plain search's, unchanged.
+ *   8. Slot j's next state is the new_state of the candidate it continues.
+ * Where the reference leaves the outcome to chance -- its sort is unstable, it removes duplicates only between neighbours, its
+ * stripe numbers can collide once bank gaps reach the candidate count -- the tie-break of 4 and the identity rule of 5 decide;
+ * whenever the reference's own outcome is determined, this is it.  An utterance with no phrase (C = 0) gets the plain search's bits.
+ * Temperature, length penalty and the no-repeat ban compose as in the reference: the ban runs before the step, so a banned
+ * constraint token is a -inf candidate. */
+#define SS_MT_CONS_MAX_TOKENS 64
+/* Ints per utterance of the device table: seq [SS_MT_CONS_MAX_TOKENS] | C | U | end bits 0 .. 31 | end bits 32 .. 63 */
+#define SS_MT_CONS_TABLE_LD (SS_MT_CONS_MAX_TOKENS + 4)
+/* Host only: check the constraints of B utterances and lay out their table.  Utterance b's tokens are h_cons[h_cons_off[b] ..
+ * h_cons_off[b + 1]), phrase after phrase; h_cons_end[i] != 0 marks the last token of a phrase.  Refusals, all SS_ERR_ARG: NULL
+ * offsets, or NULL tokens / markers with any token; offsets that decrease; more than SS_MT_CONS_MAX_TOKENS tokens for an
+ * utterance; a token outside [0, V); pad or </s> in a phrase; an utterance whose last token ends no phrase (an empty or open
+ * phrase); with h_max_len, C > h_max_len[b] (the reference would run into its own `assert step < max_len`).  h_table (may be NULL):
+ * [B][SS_MT_CONS_TABLE_LD]. */
+int ss_mt_cons_table_host(int B, const int32_t* h_cons, const int32_t* h_cons_off, const int32_t* h_cons_end, int V, int pad,
+                          int eos, const int32_t* h_max_len, int32_t* h_table);
+/* ss_batch_mt_beam_opts' argument list plus the constraints as ss_mt_cons_table_host takes them; opts may be NULL.  The refusals
+ * of ss_batch_mt_beam_opts in their order, then those of ss_mt_cons_table_host; nothing is launched or written after one.  The
+ * constrained variants of the top-2k and merge kernels run for every utterance of the call, an utterance without phrases
+ * included, and return for it the bits ss_batch_mt_beam_opts returns.  The forced-prefix and sampling entry points take no
+ * constraints: a constraint bans </s> until every phrase is out, which is not something to do to a partial source. */
+int ss_batch_mt_beam_cons(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                          const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens,
+                          int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows,
+                          const ss_mt_search_opts* opts, const int32_t* h_cons, const int32_t* h_cons_off,
+                          const int32_t* h_cons_end);
+/* Host only: steps 1 - 8 of the rule for one utterance and one step, in plain C++.  h_lprobs [k][V] are the rows' masked
+ * log-probabilities before step 1 and before the cumulative scores h_cum [k] are added (step > 0: v + cum, one float32 add);
+ * h_state [k]; the phrases as above (n_cons tokens).  -> the 2k selected candidates in order: score, token, beam, new state.
+ * 1 <= k <= 32, V >= 2k + 1; at step 0 only row 0 is read.  The refusals of ss_mt_cons_table_host, and a state outside
+ * -1 .. C - 1. */
+int ss_mt_cons_select_host(const float* h_lprobs, const float* h_cum, int k, int V, int step, int eos, const int32_t* h_state,
+                           const int32_t* h_cons, int n_cons, const int32_t* h_cons_end, float* out_scores, int32_t* out_tokens,
+                           int32_t* out_beams, int32_t* out_states);
 /* New fbank rows of B streaming sessions in one launch: session b's frames h_first[b] .. h_first[b] + h_n[b] - 1 of its own 16-kHz
  * sample history h_pcm[b] (device; frame i reads samples 160 i .. 160 i + 399) go to h_feat[b] (device, h_n[b] rows of 80).  The
  * same bits as ss_fbank_cmvn's rows.  h_n[b] = 0 skips a session.  1 <= B <= 65535. */
@@ -1502,6 +1564,15 @@ int ss_op_beam_merge_opts(void* stream, const ss_op_beam_state* st, int B, int k
  * launches. */
 int ss_op_beam_prefix_score_opts(void* stream, const float* logits, int rows, int V, const int32_t* ftok, int pad, int unk,
                                  float unk_pen, float* lp, float temperature);
+/* beam_cons_select_kernel: the selection stage of the constrained search (the rule: ss_batch_mt_beam_cons, steps 2 - 8) alone, one
+ * workgroup per utterance.  All DEVICE pointers: cand_s / cand_t [R][SS_OP_BEAM_CAND] the rows' sorted 2k lists as the top-2k
+ * kernel leaves them (after step 1 and + cum), next_s / next_t [R][2] each row's next tokens (ascending, -1 = none) with their
+ * scores from the row, state [R], cons_table [B][SS_MT_CONS_TABLE_LD] (ss_mt_cons_table_host).  -> per utterance the 2k selected
+ * candidates in order, row stride SS_OP_BEAM_CAND: score, token, beam, new state.  A state outside -1 .. C - 1 is read as the
+ * nearer end. */
+int ss_op_beam_cons_select(void* stream, const float* cand_s, const int32_t* cand_t, const float* next_s, const int32_t* next_t,
+                           const int32_t* state, const int32_t* cons_table, int B, int k, int t_step, float* out_s, int32_t* out_t,
+                           int32_t* out_beam, int32_t* out_state);
 /* sample_step_kernel for one step (the rule: ss_mt_sample_opts).  Every row is an utterance of its own with one chain: logits
  * [R][V], max_len / npre [R], the chain index row_j [R] and the key keys [R] of each row (all DEVICE pointers), the mask and ban
  * arguments of ss_op_beam_topk_opts (tok [t_step + 1][R], anc [R][Lc]).  -> per row the drawn token, its positional score v[token],

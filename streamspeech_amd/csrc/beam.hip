@@ -29,6 +29,9 @@
 // kernels, which are the `false` instantiations of the same bodies.  A forced prefix that itself repeats an n-gram is refused by the
 // planner, so the prefix pass needs no ban; the agents' and pools' committed prefixes never trip that check, because each of their
 // tokens was chosen under the same ban.
+//
+// ss_batch_mt_beam_cons is the search without a prefix under lexical constraints (fairseq's LexicallyConstrainedBeamSearch, ordered):
+// the CONS variants of the same two bodies, chosen on the host in the same way, and one int of state per slot beside the ancestry.
 #include <cmath>
 
 #include "model_internal.hpp"
@@ -40,6 +43,63 @@ constexpr int kMaxBeam = 32, kMaxCand = 2 * kMaxBeam;
 // a beats b: higher score, then lower flattened index (torch.topk order); index < 0 = no candidate
 __device__ __forceinline__ bool beats(float a, int ia, float b, int ib) {
   return ib < 0 || (ia >= 0 && (a > b || (a == b && ia < ib)));
+}
+
+// ---- lexical constraints (ss_batch_mt_beam_cons; the rule stands in include/streamspeech_hip.h) ----
+// The ordered constraint state of a hypothesis is one int.  The CONS variants of the two step kernels are chosen on the host once
+// per search, as OPT and LENPEN are: the top-2k kernel bans </s> for an unfinished row and notes the scores of the row's at most two
+// next tokens while it fills the row; the merge kernel runs cons_select between the rank merge and the step logic.
+constexpr int kConsMax = SS_MT_CONS_MAX_TOKENS, kConsLd = SS_MT_CONS_TABLE_LD;
+constexpr int kConsCand = 5 * kMaxBeam;          // 2k global + k row bests + 2k next tokens
+
+struct ConsArgs {
+  const int* tab = nullptr;      // [B][kConsLd] seq | C | U | end bits lo | hi
+  const int* state = nullptr;    // [R] the states this step reads
+  int* state_nxt = nullptr;      // [R] the states the next step reads
+  float* next_s = nullptr;       // [R][2] scores of the row's next tokens
+  int* next_t = nullptr;         // [R][2] the row's next tokens, ascending; -1 = none
+};
+
+struct ConsRow {
+  const int* seq;
+  int C, U;
+  unsigned long long endm;
+};
+
+__host__ __device__ inline ConsRow cons_row(const int* tab, int b) {
+  const int* cr = tab + (size_t)b * kConsLd;
+  ConsRow c;
+  c.seq = cr;
+  c.C = cr[kConsMax] < 0 ? 0 : cr[kConsMax] > kConsMax ? kConsMax : cr[kConsMax];
+  c.U = cr[kConsMax + 1];
+  c.endm = (unsigned long long)(unsigned)cr[kConsMax + 2] | ((unsigned long long)(unsigned)cr[kConsMax + 3] << 32);
+  return c;
+}
+
+__host__ __device__ inline int cons_clamp_state(const ConsRow& c, int s) { return s < -1 ? -1 : s > c.C - 1 ? c.C - 1 : s; }
+
+// OrderedConstraintState.advance
+__host__ __device__ inline int cons_advance(const ConsRow& c, int s, int tok) {
+  if (s + 1 == c.C) return s;
+  if (c.seq[s + 1] == tok) return s + 1;
+  if (s < 0 || ((c.endm >> s) & 1ull)) return s;   // s == -1: endpoints[-1], the last one, always set
+  return tok == c.seq[0] ? 0 : -1;
+}
+
+// OrderedConstraintState.next_tokens, ascending, -1 = none
+__host__ __device__ inline void cons_next_tokens(const ConsRow& c, int s, int& n0, int& n1) {
+  n0 = n1 = -1;
+  if (s > 0) n0 = c.seq[0];
+  if (s + 1 != c.C) {
+    const int x = c.seq[s + 1];
+    if (n0 < 0) n0 = x;
+    else if (x != n0) { n1 = x > n0 ? x : n0; n0 = x > n0 ? n0 : x; }
+  }
+}
+
+// the sort key of a candidate, formed as the reference forms it: int -> float32, one float32 add
+__host__ __device__ inline float cons_key(const ConsRow& c, int new_state, float score) {
+  return (float)((c.U - (new_state + 1)) * -100) + score;
 }
 
 // Row r = b*k + j of the logits -> its 2k best (score, token), score = masked log-softmax + cumulative score of the hypothesis.
@@ -68,12 +128,16 @@ size_t topk_lds_bytes(int V, int ngram, int Lc) {
   return (size_t)V * sizeof(float) + (ngram >= 2 ? ((size_t)Lc + (size_t)(V + 31) / 32) * sizeof(int) : 0);
 }
 
-template <bool OPT>
+// CONS (ss_batch_mt_beam_cons; no prefix, so step == t_step): at step > 0 </s> of a row whose constraint state is not finished is
+// -inf, after every other mask and before the cumulative score; the scores of the row's next tokens go to ca.next_s as the row is
+// filled, before the extraction loop overwrites taken entries.
+template <bool OPT, bool CONS = false>
 __device__ __forceinline__ void beam_topk_body(const float* __restrict__ logits, int V, int k, int t_step, int min_len,
                                                const int* __restrict__ max_len, const int* __restrict__ npre,
                                                const int* __restrict__ done,
                                                const float* __restrict__ cum, int pad, int unk, int eos, float unk_pen,
-                                               float* __restrict__ cand_s, int* __restrict__ cand_t, const TopkOpts& o) {
+                                               float* __restrict__ cand_s, int* __restrict__ cand_t, const TopkOpts& o,
+                                               const ConsArgs& ca = ConsArgs{}) {
   extern __shared__ float vals[];                  // [V] candidate scores of the row; NaN = already taken
   __shared__ float sa[4];
   __shared__ int si[4];
@@ -126,6 +190,19 @@ __device__ __forceinline__ void beam_topk_body(const float* __restrict__ logits,
   const float lse = logf((sa[0] + sa[1]) + (sa[2] + sa[3]));
   const bool at_max = step >= max_len[b];
   const float c = cum[row];
+  [[maybe_unused]] bool ban_eos = false;
+  [[maybe_unused]] int nt0 = -1, nt1 = -1;
+  if constexpr (CONS) {
+    const ConsRow cr = cons_row(ca.tab, b);
+    const int cs = cons_clamp_state(cr, ca.state[row]);
+    ban_eos = step > 0 && cs + 1 != cr.C;
+    cons_next_tokens(cr, cs, nt0, nt1);
+    if (t == 0) {
+      ca.next_t[2 * row] = nt0; ca.next_t[2 * row + 1] = nt1;
+      if ((unsigned)nt0 >= (unsigned)V) ca.next_s[2 * row] = -INFINITY;
+      if ((unsigned)nt1 >= (unsigned)V) ca.next_s[2 * row + 1] = -INFINITY;
+    }
+  }
   float best = 0.f;
   int bi = -1;
   for (int n = t; n < V; n += 256) {
@@ -138,11 +215,18 @@ __device__ __forceinline__ void beam_topk_body(const float* __restrict__ logits,
     if constexpr (OPT) {
       if (banned && ((banned[n >> 5] >> (n & 31)) & 1u)) v = -INFINITY;
     }
+    if constexpr (CONS) {
+      if (ban_eos && n == eos) v = -INFINITY;
+    }
     if (step > 0) v = v + c;
     if constexpr (OPT) {
       if (o.row_scores) o.row_scores[(size_t)row * V + n] = v;
     }
     vals[n] = v;
+    if constexpr (CONS) {
+      if (n == nt0) ca.next_s[2 * row] = v;
+      if (n == nt1) ca.next_s[2 * row + 1] = v;
+    }
     if (beats(v, n, best, bi)) { best = v; bi = n; }
   }
   const int nc = min(2 * k, V - 1);
@@ -190,6 +274,15 @@ __global__ __launch_bounds__(256) void beam_topk_opts_kernel(const float* __rest
   beam_topk_body<true>(logits, V, k, t_step, min_len, max_len, npre, done, cum, pad, unk, eos, unk_pen, cand_s, cand_t, o);
 }
 
+__global__ __launch_bounds__(256) void beam_topk_cons_kernel(const float* __restrict__ logits, int V, int k, int t_step, int min_len,
+                                                             const int* __restrict__ max_len, const int* __restrict__ npre,
+                                                             const int* __restrict__ done,
+                                                             const float* __restrict__ cum, int pad, int unk, int eos,
+                                                             float unk_pen, float* __restrict__ cand_s, int* __restrict__ cand_t,
+                                                             TopkOpts o, ConsArgs ca) {
+  beam_topk_body<true, true>(logits, V, k, t_step, min_len, max_len, npre, done, cum, pad, unk, eos, unk_pen, cand_s, cand_t, o, ca);
+}
+
 struct BeamState {
   int* tok;        // [Tn + 3][R] token fed at lock-step index t by slot r
   float* cum;      // [Tn + 3][R] cumulative score of the hypothesis fed at lock-step index t by slot r
@@ -210,36 +303,14 @@ struct BeamState {
 // slot wrote cache index c0 + t_step at this step, so the ancestry entries in use are the cache indices 0 .. c0 + t_step.
 // LENPEN (ss_mt_search_opts::len_penalty != 1): a finalised score is divided by (step + 1) ** len_penalty, formed as the reference forms
 // it -- the power in double, rounded to float32, then one float32 division.  The plain search instantiates LENPEN = false.
-template <bool LENPEN>
-__device__ __forceinline__ void beam_merge_body(const BeamState& st, int k, int R, int Lc, int V, int t_step, int c0, int eos,
-                                                int normalize, float len_penalty) {
-  __shared__ float ms[kMaxBeam * kMaxCand];
-  __shared__ int mt[kMaxBeam * kMaxCand];
-  __shared__ float sel_s[kMaxCand];
-  __shared__ int sel_t[kMaxCand], sel_beam[kMaxCand];
-  __shared__ int fin_c[kMaxBeam], fin_e[kMaxBeam], act_c[kMaxBeam];
-  __shared__ int eosm[kMaxCand], f[kMaxBeam];
-  __shared__ int n_fin, is_done;
-  const int t = threadIdx.x, b = blockIdx.x, r0 = b * k;
-  const int npre = st.npre[b], step = t_step + npre;   // the reference's step
-  const int ci = c0 + t_step, na = ci + 2;             // cache index written at this step; ancestry entries the next step reads
-  const int* anc_cur = st.anc + (size_t)(t_step & 1) * R * Lc;
-  int* anc_nxt = st.anc + (size_t)((t_step + 1) & 1) * R * Lc;
-  int* tok_nxt = st.tok + (size_t)(t_step + 1) * R;
-  float* cum_nxt = st.cum + (size_t)(t_step + 1) * R;
-  if (st.done[b]) {                  // finished utterance: its rows keep decoding (lockstep) -- keep their tables valid, nothing else
-    for (int i = t; i < k * na; i += 256) {
-      const int j = i / na, p = i - j * na;
-      anc_nxt[(size_t)(r0 + j) * Lc + p] = p <= ci ? anc_cur[(size_t)(r0 + j) * Lc + p] : r0 + j;
-    }
-    if (t < k) { tok_nxt[r0 + t] = eos; cum_nxt[r0 + t] = 0.f; }
-    return;
-  }
-  const int nl = t_step == 0 ? 1 : k, nc = 2 * k;
+// The rank merge of both merge kernels: the nl sorted lists of nc entries from row r0 on -> sel_* [nc], the global top nc in order.
+__device__ __forceinline__ void beam_rank_merge(const float* __restrict__ cand_s, const int* __restrict__ cand_t, int r0, int nl,
+                                                int nc, float* ms, int* mt, float* sel_s, int* sel_t, int* sel_beam) {
+  const int t = threadIdx.x;
   for (int i = t; i < nl * nc; i += 256) {
     const int l = i / nc, q = i - l * nc;
-    ms[i] = st.cand_s[(size_t)(r0 + l) * kMaxCand + q];
-    mt[i] = st.cand_t[(size_t)(r0 + l) * kMaxCand + q];
+    ms[i] = cand_s[(size_t)(r0 + l) * kMaxCand + q];
+    mt[i] = cand_t[(size_t)(r0 + l) * kMaxCand + q];
   }
   __syncthreads();
   // rank of candidate (list l, position q) = q + the entries of the other lists that beat it; lists are sorted, so each count is a
@@ -261,6 +332,88 @@ __device__ __forceinline__ void beam_merge_body(const BeamState& st, int k, int 
     if (rank < nc) { sel_s[rank] = x; sel_t[rank] = mt[i]; sel_beam[rank] = l; }
   }
   __syncthreads();
+}
+
+// Steps 2 - 8 of the constraint rule for utterance b, by the whole workgroup: sel_* [2k] hold the global top 2k (step 2a) on
+// entry and the step's selection on return, sel_st [2k] its new states.  One thread per candidate (at most kConsCand = 160): the
+// sort, the de-duplication and the stripes are counts over the list in LDS, so every order is decided by comparisons alone.
+__device__ __forceinline__ void cons_select(const ConsArgs& ca, const float* __restrict__ cand_s, const int* __restrict__ cand_t,
+                                            int b, int k, int t_step, float* sel_s, int* sel_t, int* sel_beam, int* sel_st) {
+  __shared__ float c_s[kConsCand], c_key[kConsCand];
+  __shared__ int c_t[kConsCand], c_b[kConsCand], c_st[kConsCand], c_rank[kConsCand], c_ib[kConsCand];
+  const int t = threadIdx.x, r0 = b * k, nc = 2 * k;
+  const ConsRow cr = cons_row(ca.tab, b);
+  const int nrow = t_step == 0 ? 1 : k, n1 = nc + (t_step > 0 ? k : 0), N = n1 + 2 * nrow;
+  float s = 0.f, key = 0.f;
+  int tk = -1, bm = 0, ns = -1;                     // tk < 0: an empty slot of the list
+  if (t < N) {
+    if (t < nc) { s = sel_s[t]; tk = sel_t[t]; bm = sel_beam[t]; }
+    else if (t < n1) { bm = t - nc; s = cand_s[(size_t)(r0 + bm) * kMaxCand]; tk = cand_t[(size_t)(r0 + bm) * kMaxCand]; }
+    else { const int i = t - n1; bm = i >> 1; s = ca.next_s[2 * (r0 + bm) + (i & 1)]; tk = ca.next_t[2 * (r0 + bm) + (i & 1)]; }
+    if (tk >= 0) {
+      ns = cons_advance(cr, cons_clamp_state(cr, ca.state[r0 + bm]), tk);
+      key = cons_key(cr, ns, s);
+    }
+    c_s[t] = s; c_key[t] = key; c_t[t] = tk; c_b[t] = bm; c_st[t] = ns;
+  }
+  __syncthreads();
+  int rank = 0;
+  if (t < N && tk >= 0)                             // key descending, ties by list position
+    for (int j = 0; j < N; ++j)
+      if (c_t[j] >= 0 && (c_key[j] > key || (c_key[j] == key && j < t))) ++rank;
+  if (t < N) c_rank[t] = rank;
+  __syncthreads();
+  bool keep = t < N && tk >= 0;
+  if (keep)                                         // the same (beam, token) earlier in the order
+    for (int j = 0; j < N; ++j)
+      if (c_t[j] == tk && c_b[j] == bm && c_rank[j] < rank) { keep = false; break; }
+  __syncthreads();                                  // c_t is read above and rewritten below
+  if (t < N && !keep) c_t[t] = -1;
+  __syncthreads();
+  int ib = 0;
+  if (keep)                                         // rank within the own bank (equal state = equal bank)
+    for (int j = 0; j < N; ++j)
+      if (c_t[j] >= 0 && c_st[j] == ns && c_rank[j] < rank) ++ib;
+  if (t < N) c_ib[t] = ib;
+  __syncthreads();
+  if (keep) {
+    int pos = 0;                                    // (rank within bank, then higher bank first); the pairs are distinct
+    for (int j = 0; j < N; ++j)
+      if (c_t[j] >= 0 && (c_ib[j] < ib || (c_ib[j] == ib && c_st[j] > ns))) ++pos;
+    if (pos < nc) { sel_s[pos] = s; sel_t[pos] = tk; sel_beam[pos] = bm; sel_st[pos] = ns; }
+  }
+  __syncthreads();
+}
+
+template <bool LENPEN, bool CONS = false>
+__device__ __forceinline__ void beam_merge_body(const BeamState& st, int k, int R, int Lc, int V, int t_step, int c0, int eos,
+                                                int normalize, float len_penalty, const ConsArgs& ca = ConsArgs{}) {
+  __shared__ float ms[kMaxBeam * kMaxCand];
+  __shared__ int mt[kMaxBeam * kMaxCand];
+  __shared__ float sel_s[kMaxCand];
+  __shared__ int sel_t[kMaxCand], sel_beam[kMaxCand];
+  [[maybe_unused]] __shared__ int sel_st[CONS ? kMaxCand : 1];
+  __shared__ int fin_c[kMaxBeam], fin_e[kMaxBeam], act_c[kMaxBeam];
+  __shared__ int eosm[kMaxCand], f[kMaxBeam];
+  __shared__ int n_fin, is_done;
+  const int t = threadIdx.x, b = blockIdx.x, r0 = b * k;
+  const int npre = st.npre[b], step = t_step + npre;   // the reference's step
+  const int ci = c0 + t_step, na = ci + 2;             // cache index written at this step; ancestry entries the next step reads
+  const int* anc_cur = st.anc + (size_t)(t_step & 1) * R * Lc;
+  int* anc_nxt = st.anc + (size_t)((t_step + 1) & 1) * R * Lc;
+  int* tok_nxt = st.tok + (size_t)(t_step + 1) * R;
+  float* cum_nxt = st.cum + (size_t)(t_step + 1) * R;
+  if (st.done[b]) {                  // finished utterance: its rows keep decoding (lockstep) -- keep their tables valid, nothing else
+    for (int i = t; i < k * na; i += 256) {
+      const int j = i / na, p = i - j * na;
+      anc_nxt[(size_t)(r0 + j) * Lc + p] = p <= ci ? anc_cur[(size_t)(r0 + j) * Lc + p] : r0 + j;
+    }
+    if (t < k) { tok_nxt[r0 + t] = eos; cum_nxt[r0 + t] = 0.f; }
+    return;
+  }
+  const int nl = t_step == 0 ? 1 : k, nc = 2 * k;
+  beam_rank_merge(st.cand_s, st.cand_t, r0, nl, nc, ms, mt, sel_s, sel_t, sel_beam);
+  if constexpr (CONS) cons_select(ca, st.cand_s, st.cand_t, b, k, t_step, sel_s, sel_t, sel_beam, sel_st);
   if (t == 0) {
     // finalisation: </s> candidates among the first k, finite, not ignored (unity/sequence_generator.py:345-372)
     for (int q = 0; q < nc; ++q) {
@@ -322,6 +475,7 @@ __device__ __forceinline__ void beam_merge_body(const BeamState& st, int k, int 
     const int q = act_c[t];
     tok_nxt[r0 + t] = sel_t[q];
     cum_nxt[r0 + t] = sel_s[q];
+    if constexpr (CONS) ca.state_nxt[r0 + t] = sel_st[q];   // update_constraints(active_hypos)
   }
   for (int i = t; i < k * na; i += 256) {
     const int j = i / na, p = i - j * na;
@@ -338,6 +492,35 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(BeamState st, int k, in
 __global__ __launch_bounds__(256) void beam_merge_lenpen_kernel(BeamState st, int k, int R, int Lc, int V, int t_step, int c0, int eos,
                                                                 int normalize, float len_penalty) {
   beam_merge_body<true>(st, k, R, Lc, V, t_step, c0, eos, normalize, len_penalty);
+}
+
+__global__ __launch_bounds__(256) void beam_merge_cons_kernel(BeamState st, int k, int R, int Lc, int V, int t_step, int c0, int eos,
+                                                              int normalize, ConsArgs ca) {
+  beam_merge_body<false, true>(st, k, R, Lc, V, t_step, c0, eos, normalize, 1.f, ca);
+}
+
+__global__ __launch_bounds__(256) void beam_merge_cons_lenpen_kernel(BeamState st, int k, int R, int Lc, int V, int t_step, int c0,
+                                                                     int eos, int normalize, float len_penalty, ConsArgs ca) {
+  beam_merge_body<true, true>(st, k, R, Lc, V, t_step, c0, eos, normalize, len_penalty, ca);
+}
+
+// The selection stage alone (ss_op_beam_cons_select): the rank merge and cons_select of beam_merge_cons_kernel, then the selection
+// written out, row stride kMaxCand.
+__global__ __launch_bounds__(256) void beam_cons_select_kernel(const float* __restrict__ cand_s, const int* __restrict__ cand_t,
+                                                               ConsArgs ca, int k, int t_step, float* __restrict__ out_s,
+                                                               int* __restrict__ out_t, int* __restrict__ out_beam,
+                                                               int* __restrict__ out_state) {
+  __shared__ float ms[kMaxBeam * kMaxCand];
+  __shared__ int mt[kMaxBeam * kMaxCand];
+  __shared__ float sel_s[kMaxCand];
+  __shared__ int sel_t[kMaxCand], sel_beam[kMaxCand], sel_st[kMaxCand];
+  const int t = threadIdx.x, b = blockIdx.x, nc = 2 * k;
+  beam_rank_merge(cand_s, cand_t, b * k, t_step == 0 ? 1 : k, nc, ms, mt, sel_s, sel_t, sel_beam);
+  cons_select(ca, cand_s, cand_t, b, k, t_step, sel_s, sel_t, sel_beam, sel_st);
+  if (t < nc) {
+    const size_t o = (size_t)b * kMaxCand + t;
+    out_s[o] = sel_s[t]; out_t[o] = sel_t[t]; out_beam[o] = sel_beam[t]; out_state[o] = sel_st[t];
+  }
 }
 
 // d_feats row i = slot-major state row idx[i]; rows with idx < 0 (past the best hypothesis) are left as they are
@@ -822,6 +1005,32 @@ int read_search_opts(const ss_mt_search_opts* o, SearchOpts& so) {
   return SS_OK;
 }
 
+// The refusals of ss_mt_cons_table_host, and the table the kernels read ([B][kConsLd], ConsArgs::tab).
+int cons_table(int B, const int32_t* h_cons, const int32_t* h_off, const int32_t* h_end, int V, int pad, int eos,
+               const int32_t* h_max_len, std::vector<int>& tab) {
+  if (B <= 0 || !h_off) return SS_ERR_ARG;
+  tab.assign((size_t)B * kConsLd, 0);
+  for (int b = 0; b < B; ++b) {
+    const int o = h_off[b], C = h_off[b + 1] - o;
+    if (o < 0 || C < 0 || C > kConsMax) return SS_ERR_ARG;
+    if (C > 0 && (!h_cons || !h_end)) return SS_ERR_ARG;
+    if (h_max_len && C > h_max_len[b]) return SS_ERR_ARG;
+    int* row = tab.data() + (size_t)b * kConsLd;
+    unsigned long long endm = 0;
+    int U = 0;
+    for (int i = 0; i < C; ++i) {
+      const int id = h_cons[o + i];
+      if (id < 0 || id >= V || id == pad || id == eos) return SS_ERR_ARG;
+      U += std::find(row, row + i, id) == row + i ? 1 : 0;
+      row[i] = id;
+      if (h_end[o + i]) endm |= 1ull << i;
+    }
+    if (C > 0 && !((endm >> (C - 1)) & 1ull)) return SS_ERR_ARG;   // the last phrase is empty or open
+    row[kConsMax] = C; row[kConsMax + 1] = U; row[kConsMax + 2] = (int)(unsigned)endm; row[kConsMax + 3] = (int)(unsigned)(endm >> 32);
+  }
+  return SS_OK;
+}
+
 // tokens[0 .. n) = </s>, then the prefix: does any n-gram stand in it twice?  Then the ban would hit a forced token.
 bool prefix_repeats_ngram(const std::vector<int>& tokens, int ngram) {
   const int L = (int)tokens.size();
@@ -920,13 +1129,13 @@ int beam_continue_plan(int B, int beam, const int32_t* h_Tp, const int32_t* h_pr
 int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp, const int32_t* h_n_prefix,
                 const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, const BcPlan& P, int32_t* h_out_tokens,
                 int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows,
-                const SearchOpts& so, const SampleOpts* smp = nullptr) {
+                const SearchOpts& so, const SampleOpts* smp = nullptr, const std::vector<int>* cons_tab = nullptr) {
   const ss_config& c = m->cfg;
   const int D = c.dec_dim, F = c.dec_ffn, V = c.tgt_vocab, k = beam, R = B * beam;
   const int Lc = P.Lc, Tn = P.Tn, c0 = P.c0, Np = P.Np;
   // the option kernels are chosen here, once: a search without options launches what it always launched
   const bool topk_opts = so.ngram >= 2 || so.temp != 1.f, merge_lenpen = normalize && so.len_penalty != 1.f;
-  if (topk_opts && topk_lds_bytes(V, so.ngram, Lc) > 65536) return SS_ERR_ARG;
+  if ((topk_opts || cons_tab) && topk_lds_bytes(V, so.ngram, Lc) > 65536) return SS_ERR_ARG;
   const int npad = smp ? sample_npad(*smp, V) : 0;
   const size_t smp_lds = smp ? sample_lds_bytes(V, so.ngram, Lc, npad) : 0;
   if (smp_lds > kSampleLdsMax) return SS_ERR_ARG;
@@ -938,7 +1147,9 @@ int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_o
   const size_t np = (size_t)Np;
   const size_t n_tok = (size_t)(Tn + 3) * R, n_anc = (size_t)2 * R * Lc, n_cand = (size_t)R * kMaxCand, n_fin = (size_t)B * k * Lc;
   const size_t n_fin_words = B + 2 * (size_t)B * k + 3 * n_fin;
-  const size_t n_state = 2 * n_tok + n_anc + 2 * n_cand + R + 3 * (size_t)B + n_fin_words;
+  // constraints: states [2][R] (ping-pong, as the ancestry) | next-token scores and ids [R][2] each | the table
+  const size_t n_cons = cons_tab ? 6 * (size_t)R + cons_tab->size() : 0;
+  const size_t n_state = 2 * n_tok + n_anc + 2 * n_cand + R + 3 * (size_t)B + n_fin_words + n_cons;
   RET(m->sc->mt_cross.ensure((size_t)c.mt_layers * oe.total * 2 * D * sizeof(float)));
   RET(m->sc->bmt_self.ensure((size_t)c.mt_layers * R * Lc * 3 * D * sizeof(float)));
   RET(m->sc->bmb_feat.ensure((size_t)R * Lc * D * sizeof(float)));
@@ -973,6 +1184,11 @@ int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_o
   st.fin_tok = w; w += n_fin;
   st.fin_pos = (float*)w; w += n_fin;
   st.fin_anc = w; w += n_fin;
+  int* cons_state = w;
+  ConsArgs ca;
+  if (cons_tab) {
+    ca.next_s = (float*)(w + 2 * R); ca.next_t = w + 4 * R; ca.tab = w + 6 * R;
+  }
   int* d_tab = (int*)m->sc->seg_buf.p;
   const int* d_cross = d_tab;
   const int* d_self = d_tab + P.o_lself;
@@ -994,6 +1210,10 @@ int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_o
       SS_HIP_CHECK(hipMemcpyAsync(d_tab + o_keys, smp->h_keys, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
     }
     if (h_n_prefix) RET(upload(s, st.npre, np0));
+    if (cons_tab) {                              // every hypothesis starts at the root
+      RET(upload(s, cons_state, std::vector<int>((size_t)2 * R, -1)));
+      RET(upload(s, cons_state + 6 * R, *cons_tab));
+    }
   }
   const float* d_prepos = nullptr;
   if (Np > 0) {
@@ -1048,6 +1268,14 @@ int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_o
       SS_MAX_LDS_ONCE(sample_step_kernel, kSampleLdsMax);
       hipLaunchKernelGGL(sample_step_kernel, dim3(R), dim3(256), smp_lds, s, logits, V, k, step, min_len, st.max_len, st.npre, st.done,
                          c.pad, c.unk, c.eos, unk_penalty, to, sa);
+    } else if (cons_tab) {
+      TopkOpts to;
+      to.temp = so.temp; to.ngram = so.ngram; to.tok = st.tok; to.anc = st.anc + (size_t)(step & 1) * R * Lc; to.R = R; to.Lc = Lc;
+      to.c0 = c0; to.ptok = d_tab + P.o_ptok; to.row0 = d_row0;
+      ca.state = cons_state + (size_t)(step & 1) * R; ca.state_nxt = cons_state + (size_t)((step + 1) & 1) * R;
+      hipLaunchKernelGGL(beam_topk_cons_kernel, dim3(R), dim3(256), topk_lds_bytes(V, so.ngram, Lc), s, logits, V, k, step, min_len,
+                         st.max_len, st.npre, st.done, st.cum + (size_t)step * R, c.pad, c.unk, c.eos, unk_penalty, st.cand_s,
+                         st.cand_t, to, ca);
     } else if (topk_opts) {
       TopkOpts to;
       to.temp = so.temp; to.ngram = so.ngram; to.tok = st.tok; to.anc = st.anc + (size_t)(step & 1) * R * Lc; to.R = R; to.Lc = Lc;
@@ -1062,6 +1290,11 @@ int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_o
     SS_LAUNCH_CHECK();
     if (smp)
       hipLaunchKernelGGL(sample_advance_kernel, dim3(B), dim3(64), 0, s, st, k, R, Lc, step, c0, c.eos, normalize ? 1 : 0, so.len_penalty);
+    else if (cons_tab && merge_lenpen)
+      hipLaunchKernelGGL(beam_merge_cons_lenpen_kernel, dim3(B), dim3(256), 0, s, st, k, R, Lc, V, step, c0, c.eos, 1, so.len_penalty,
+                         ca);
+    else if (cons_tab)
+      hipLaunchKernelGGL(beam_merge_cons_kernel, dim3(B), dim3(256), 0, s, st, k, R, Lc, V, step, c0, c.eos, normalize ? 1 : 0, ca);
     else if (merge_lenpen)
       hipLaunchKernelGGL(beam_merge_lenpen_kernel, dim3(B), dim3(256), 0, s, st, k, R, Lc, V, step, c0, c.eos, 1, so.len_penalty);
     else
@@ -1124,7 +1357,8 @@ int beam_search(ss_model* m, void* stream, int B, int beam, const float* d_enc_o
 static int mt_beam_entry(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
                          const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens,
                          int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats, int feat_rows,
-                         const ss_mt_search_opts* opts, const SampleOpts* smp) {
+                         const ss_mt_search_opts* opts, const SampleOpts* smp, const int32_t* h_cons = nullptr,
+                         const int32_t* h_cons_off = nullptr, const int32_t* h_cons_end = nullptr) {
   SearchOpts so;
   RET(read_search_opts(opts, so));
   if (!m || B <= 0 || beam < 1 || beam > kMaxBeam || !d_feats || !h_out_tokens || !h_n_out || !h_scores) return SS_ERR_ARG;
@@ -1140,8 +1374,94 @@ static int mt_beam_entry(ss_model* m, void* stream, int B, int beam, const float
   BcPlan P;
   RET(beam_continue_plan(B, beam, h_Tp, nullptr, nullptr, h_max_len, min_len, out_stride, feat_rows, c.max_tgt_pos, c.tgt_vocab, c.eos,
                          c.pad, 0, P));      // position 0 is a lock-step row at every beam (beam 1 is ss_batch_mt_greedy bit for bit)
+  std::vector<int> cons_tab;
+  if (h_cons_off) RET(cons_table(B, h_cons, h_cons_off, h_cons_end, c.tgt_vocab, c.pad, c.eos, h_max_len, cons_tab));
   return beam_search(m, stream, B, beam, d_enc_out, h_Tp, nullptr, h_max_len, min_len, unk_penalty, normalize, P, h_out_tokens,
-                     out_stride, h_n_out, h_scores, h_pos_scores, d_feats, feat_rows, so, smp);
+                     out_stride, h_n_out, h_scores, h_pos_scores, d_feats, feat_rows, so, smp, h_cons_off ? &cons_tab : nullptr);
+}
+
+extern "C" int ss_batch_mt_beam_cons(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
+                                     const int32_t* h_max_len, int min_len, float unk_penalty, int normalize, int32_t* h_out_tokens,
+                                     int out_stride, int32_t* h_n_out, float* h_scores, float* h_pos_scores, float* d_feats,
+                                     int feat_rows, const ss_mt_search_opts* opts, const int32_t* h_cons, const int32_t* h_cons_off,
+                                     const int32_t* h_cons_end) {
+  if (!h_cons_off) return SS_ERR_ARG;
+  return mt_beam_entry(m, stream, B, beam, d_enc_out, h_Tp, h_max_len, min_len, unk_penalty, normalize, h_out_tokens, out_stride,
+                       h_n_out, h_scores, h_pos_scores, d_feats, feat_rows, opts, nullptr, h_cons, h_cons_off, h_cons_end);
+}
+
+extern "C" int ss_mt_cons_table_host(int B, const int32_t* h_cons, const int32_t* h_cons_off, const int32_t* h_cons_end, int V,
+                                     int pad, int eos, const int32_t* h_max_len, int32_t* h_table) {
+  std::vector<int> tab;
+  RET(cons_table(B, h_cons, h_cons_off, h_cons_end, V, pad, eos, h_max_len, tab));
+  if (h_table) std::copy(tab.begin(), tab.end(), h_table);
+  return SS_OK;
+}
+
+// Steps 1 - 8 of the rule, serially: the twin of beam_topk_cons_kernel's masks and beam_merge_cons_kernel's selection.
+extern "C" int ss_mt_cons_select_host(const float* h_lprobs, const float* h_cum, int k, int V, int step, int eos,
+                                      const int32_t* h_state, const int32_t* h_cons, int n_cons, const int32_t* h_cons_end,
+                                      float* out_scores, int32_t* out_tokens, int32_t* out_beams, int32_t* out_states) {
+  if (!h_lprobs || !h_cum || !h_state || !out_scores || !out_tokens || !out_beams || !out_states) return SS_ERR_ARG;
+  if (k < 1 || k > kMaxBeam || V < 2 * k + 1 || step < 0 || eos < 0 || eos >= V || n_cons < 0) return SS_ERR_ARG;
+  const int32_t off[2] = {0, n_cons};
+  std::vector<int> tab;
+  RET(cons_table(1, h_cons, off, h_cons_end, V, -1, eos, nullptr, tab));
+  const ConsRow cr = cons_row(tab.data(), 0);
+  const int nrow = step == 0 ? 1 : k, nc = 2 * k;
+  for (int j = 0; j < nrow; ++j)
+    if (h_state[j] < -1 || h_state[j] > cr.C - 1) return SS_ERR_ARG;
+  struct Cand { float s, key; int tok, beam, st, bank_rank; };
+  std::vector<float> v((size_t)nrow * V);
+  for (int j = 0; j < nrow; ++j)
+    for (int n = 0; n < V; ++n) {
+      float x = h_lprobs[(size_t)j * V + n];
+      if (step > 0 && n == eos && h_state[j] + 1 != cr.C) x = -INFINITY;
+      if (step > 0) x = x + h_cum[j];
+      v[(size_t)j * V + n] = x;
+    }
+  std::vector<Cand> list;
+  auto push = [&](int j, int n) {
+    Cand c;
+    c.s = v[(size_t)j * V + n]; c.tok = n; c.beam = j; c.st = cons_advance(cr, h_state[j], n); c.key = cons_key(cr, c.st, c.s);
+    c.bank_rank = 0;
+    list.push_back(c);
+  };
+  {
+    std::vector<int> idx((size_t)nrow * V);
+    for (size_t i = 0; i < idx.size(); ++i) idx[i] = (int)i;
+    std::partial_sort(idx.begin(), idx.begin() + nc, idx.end(), [&](int a, int e) { return v[a] > v[e] || (v[a] == v[e] && a < e); });
+    for (int q = 0; q < nc; ++q) push(idx[q] / V, idx[q] % V);
+  }
+  if (step > 0)
+    for (int j = 0; j < k; ++j) {
+      int bi = 0;
+      for (int n = 1; n < V; ++n)
+        if (v[(size_t)j * V + n] > v[(size_t)j * V + bi]) bi = n;
+      push(j, bi);
+    }
+  for (int j = 0; j < nrow; ++j) {
+    int n0, n1;
+    cons_next_tokens(cr, h_state[j], n0, n1);
+    if (n0 >= 0) push(j, n0);
+    if (n1 >= 0) push(j, n1);
+  }
+  std::stable_sort(list.begin(), list.end(), [](const Cand& a, const Cand& e) { return a.key > e.key; });
+  std::vector<Cand> uniq;
+  for (const Cand& c : list) {
+    bool seen = false;
+    for (const Cand& u : uniq) seen = seen || (u.beam == c.beam && u.tok == c.tok);
+    if (!seen) uniq.push_back(c);
+  }
+  for (size_t i = 0; i < uniq.size(); ++i)
+    for (size_t j = 0; j < i; ++j) uniq[i].bank_rank += uniq[j].st == uniq[i].st ? 1 : 0;
+  std::stable_sort(uniq.begin(), uniq.end(), [](const Cand& a, const Cand& e) {
+    return a.bank_rank < e.bank_rank || (a.bank_rank == e.bank_rank && a.st > e.st);
+  });
+  for (int q = 0; q < nc; ++q) {
+    out_scores[q] = uniq[q].s; out_tokens[q] = uniq[q].tok; out_beams[q] = uniq[q].beam; out_states[q] = uniq[q].st;
+  }
+  return SS_OK;
 }
 
 extern "C" int ss_batch_mt_beam_opts(ss_model* m, void* stream, int B, int beam, const float* d_enc_out, const int32_t* h_Tp,
@@ -1307,6 +1627,20 @@ extern "C" int ss_op_beam_prefix_chain(void* stream, const float* lp, const int3
   if (B <= 0 || k < 1) return SS_ERR_ARG;
   hipLaunchKernelGGL(beam_prefix_chain_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, lp, row0, npre, B, k, cum0,
                      pos);
+  SS_LAUNCH_CHECK();
+  return SS_OK;
+}
+
+extern "C" int ss_op_beam_cons_select(void* stream, const float* cand_s, const int32_t* cand_t, const float* next_s,
+                                      const int32_t* next_t, const int32_t* state, const int32_t* cons_table, int B, int k, int t_step,
+                                      float* out_s, int32_t* out_t, int32_t* out_beam, int32_t* out_state) {
+  if (B <= 0 || k < 1 || k > kMaxBeam || t_step < 0) return SS_ERR_ARG;
+  if (!cand_s || !cand_t || !next_s || !next_t || !state || !cons_table || !out_s || !out_t || !out_beam || !out_state)
+    return SS_ERR_ARG;
+  ConsArgs ca;
+  ca.tab = cons_table; ca.state = state; ca.next_s = const_cast<float*>(next_s); ca.next_t = const_cast<int32_t*>(next_t);
+  hipLaunchKernelGGL(beam_cons_select_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, cand_s, cand_t, ca, k, t_step, out_s, out_t,
+                     out_beam, out_state);
   SS_LAUNCH_CHECK();
   return SS_OK;
 }

@@ -427,13 +427,17 @@ class BatchMixin:
         return fbank_sr_rows(n_in, *resample_ratio(sr_in), lib=self.lib)
 
     def _mt_beam(self, entry: str, enc_packed: torch.Tensor, Tp: List[int], prefixes: Optional[List[List[int]]], max_len: List[int],
-                 beam: int, spare_rows: int, min_len: int, unk_penalty: float, normalize: bool, search: tuple, sample=None):
+                 beam: int, spare_rows: int, min_len: int, unk_penalty: float, normalize: bool, search: tuple, sample=None,
+                 constraints=None):
         """The calls behind batch_mt_beam (prefixes None: `entry` takes none) and batch_mt_beam_continue -> (nbest, feats [B, rows, D]),
         rows = the longest max_len + 1 + spare_rows.  A pack with B * beam > 256 rows runs as consecutive sub-calls (plan_beam_groups).
         search = (len_penalty, temperature, no_repeat_ngram_size): at the defaults the call is `entry` itself, otherwise `entry`_opts.
         A hypothesis is its row's prefix + the generated tokens, and its positional scores cover both.
-        sample = (keys, ss_mt_sample_opts): the sampling twin of `entry` (ss_batch_mt_sample / _continue), `beam` chains per row."""
+        sample = (keys, ss_mt_sample_opts): the sampling twin of `entry` (ss_batch_mt_sample / _continue), `beam` chains per row.
+        constraints = per-row phrase lists: ss_batch_mt_beam_cons (the search options always travel with it, NULL at the defaults)."""
         B = len(Tp)
+        if constraints is not None and (prefixes is not None or sample is not None):
+            raise ValueError("constraints go with the offline beam search only, not behind a forced prefix and not with sampling")
         if not 1 <= beam <= MT_BEAM_MAX:
             raise ValueError(f"beam {beam} outside [1, {MT_BEAM_MAX}]")
         opts = check_search_options(*search)
@@ -442,6 +446,9 @@ class BatchMixin:
             name = entry.replace("_beam", "_sample")
             if len(sample[0]) != B:
                 raise ValueError("one key per row")
+        if constraints is not None:
+            L.pack_constraints(constraints, B)       # an empty phrase or a wrong count is refused before anything is booked
+            name = "ss_batch_mt_beam_cons"
         stride = max(max_len) + 1
         rows = stride + spare_rows
         feats = torch.empty((B, rows, self.cfg.dec_dim), dtype=torch.float32, device=self.device)
@@ -459,6 +466,8 @@ class BatchMixin:
             if sample is not None:
                 keys = (C.c_int64 * n)(*[_as_i64(x) for x in sample[0][b0:b1]])
                 tail = (C.byref(opts) if opts is not None else None, keys, C.byref(sample[1]))
+            if constraints is not None:
+                tail = (C.byref(opts) if opts is not None else None,) + tuple(_i32(a) for a in L.pack_constraints(constraints[b0:b1], n))
             L.check(getattr(self.lib, name)(self.h, _stream(), n, beam, _ptr(enc), _i32(Tp[b0:b1]), *forced, _i32(max_len[b0:b1]),
                                             int(min_len), float(unk_penalty), 1 if normalize else 0, out, stride, n_out, sc, pos,
                                             _ptr(feats[b0:b1]), rows, *tail), name)
@@ -476,15 +485,21 @@ class BatchMixin:
 
     def batch_mt_beam(self, enc_packed: torch.Tensor, Tp: List[int], max_len: List[int], beam: int, min_len: int = 1,
                       unk_penalty: float = 0.0, normalize: bool = True, len_penalty: float = 1.0, temperature: float = 1.0,
-                      no_repeat_ngram_size: int = 0):
+                      no_repeat_ngram_size: int = 0, constraints: Optional[List[List[List[int]]]] = None):
         """Beam search of the first-pass text decoder (ss_batch_mt_beam) -> (n-best lists, feats [B, Lcap, D], n_feats list).
         nbest[b] holds up to `beam` dicts {"tokens" (incl. final eos), "score", "positional_scores"} in the reference's final order;
         feats / n_feats are the decoder states of hypothesis 0, as batch_mt_greedy returns them.  A pack with B * beam > 256 rows
         runs as consecutive sub-calls (plan_beam_groups); pack-invariant arithmetic makes the split invisible.  len_penalty,
         temperature and no_repeat_ngram_size are the reference's --lenpen, --temperature and --no-repeat-ngram-size
-        (ss_mt_search_opts); at their defaults the call is ss_batch_mt_beam itself."""
+        (ss_mt_search_opts); at their defaults the call is ss_batch_mt_beam itself.  constraints[b] is a list of phrases (token id
+        lists) that every hypothesis of row b must contain in that order (the reference's --constraints, ordered;
+        ss_batch_mt_beam_cons); None, or no phrase anywhere, is exactly the call without them."""
+        if constraints is not None and not any(len(c or []) for c in constraints):
+            if len(constraints) != len(Tp):
+                raise ValueError("one constraint list per row")
+            constraints = None
         nbest, feats = self._mt_beam("ss_batch_mt_beam", enc_packed, Tp, None, max_len, beam, 1, min_len, unk_penalty, normalize,
-                                     (len_penalty, temperature, no_repeat_ngram_size))
+                                     (len_penalty, temperature, no_repeat_ngram_size), constraints=constraints)
         return nbest, feats, [len(h[0]["tokens"]) if h else 0 for h in nbest]
 
     def batch_mt_beam_continue(self, enc_packed: torch.Tensor, Tp: List[int], prefixes: List[List[int]], max_len: List[int], beam: int,

@@ -111,6 +111,32 @@ class CTCSequenceGenerator:
         return [[{"tokens": torch.tensor(toks, dtype=torch.long), "org_tokens": raw, "attn": None, "alignment": None}]]
 
 
+def unpack_constraints(constraints, B: int):
+    """The ``constraints=`` of a generator call -> per-utterance phrase lists.  Takes fairseq's packed tensor [B, maxlen]
+    (token_generation_constraints.pack_constraints: each row is the phrase count, then every phrase followed by a 0, zero-padded)
+    or a list of B lists of token id lists."""
+    if torch.is_tensor(constraints):
+        if constraints.dim() == 1:
+            constraints = constraints.unsqueeze(0)
+        if constraints.dim() != 2 or constraints.size(0) != B:
+            raise ValueError(f"packed constraints of shape {tuple(constraints.shape)} for a batch of {B}")
+        out = []
+        for row in constraints.tolist():
+            phrases, off = [], 1
+            for _ in range(int(row[0])):
+                if 0 not in row[off:]:
+                    raise ValueError("packed constraints: a phrase without its closing 0")
+                where = row.index(0, off)
+                phrases.append([int(t) for t in row[off:where]])
+                off = where + 1
+            out.append(phrases)
+        return out
+    out = [[[int(t) for t in p] for p in (c or [])] for c in constraints]
+    if len(out) != B:
+        raise ValueError(f"constraints for {len(out)} utterances, batch of {B}")
+    return out
+
+
 class SequenceGenerator:
     """agent/sequence_generator.py:165-582 at beam_size = 1: greedy first-pass text
     decoding with prefix and ``max_new_tokens``.  Keeps the reference's token-buffer semantics
@@ -130,6 +156,11 @@ class SequenceGenerator:
     ``sampling`` the search is ``batch_mt_sample_continue``: beam_size independent ancestral samples behind the prefix, ordered by
     score (the rule: ss_mt_sample_opts in the header).  The stream key of a call is ``sampling_key=`` of generate_decoder, else the
     sample's ``"id"``, else 0: the same key and seed give the same samples.
+
+    constraints= of generate_decoder: phrases every hypothesis must contain, in order (fairseq's --constraints with the ordered
+    representation; the rule: ss_batch_mt_beam_cons in the header), as fairseq's packed tensor or a list of token id lists per
+    utterance (unpack_constraints).  The search is then ``batch_mt_beam`` with them, at every beam size.  A forced prefix with
+    constraints is refused, and a generator built for sampling raises the reference's own error.
 
     want_attention: hypothesis 0 also carries what the reference's generator records (agent/sequence_generator.py:383-392, fairseq's
     finalize_hypos): ``"attention"``, float32 [src_len, tgt_len], the head-averaged cross-attention of the last decoder layer --
@@ -188,9 +219,18 @@ class SequenceGenerator:
         start = len(prefix)
         max_len = mt_max_len(start, src_len, max_new_tokens, self.max_len_a, self.max_len_b, self.max_len, self.min_len)
         eng = self.engine
-        if self.beam_size > 1 or self.search or self.sampling is not None:
+        phrases = unpack_constraints(constraints, 1)[0] if constraints is not None else []
+        if constraints is not None and self.sampling is not None:     # Sampling.supports_constraints is False
+            raise NotImplementedError("Target-side constraints were provided, but search method doesn't support them")
+        if phrases and prefix:
+            raise ValueError("constraints behind a forced prefix are not supported: a constraint bans </s> until every phrase is out")
+        if self.beam_size > 1 or self.search or self.sampling is not None or phrases:
             enc = enc.contiguous()
-            if self.sampling is not None:
+            if phrases:
+                nbest, f, n = eng.batch_mt_beam(enc, [int(enc.shape[0])], [max_len], self.beam_size, self.min_len, self.unk_penalty,
+                                                self.normalize_scores, constraints=[phrases], **self.search)
+                feats = [f[0, :n[0]]]
+            elif self.sampling is not None:
                 key = kw.get("sampling_key")
                 if key is None:
                     ids = sample.get("id") if isinstance(sample, dict) else None

@@ -166,6 +166,28 @@ def sample_opts(topk: int = 0, topp: float = 0.0, seed: int = 1):
     return SSMtSampleOpts(C.sizeof(SSMtSampleOpts), int(topk), float(topp), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
 
 
+MT_CONS_MAX_TOKENS = 64  # SS_MT_CONS_MAX_TOKENS / SS_MT_CONS_TABLE_LD of the header
+MT_CONS_TABLE_LD = MT_CONS_MAX_TOKENS + 4
+
+
+def pack_constraints(constraints, B: int):
+    """Per-utterance phrase lists -> the (tokens, offsets [B + 1], end markers) int32 arrays of ss_batch_mt_beam_cons.
+    ``constraints[b]`` is a list of phrases, each a non-empty list of token ids; None stands for no phrases."""
+    import numpy as np
+    if len(constraints) != B:
+        raise ValueError(f"constraints for {len(constraints)} utterances, batch of {B}")
+    toks, ends, off = [], [], [0]
+    for b, phrases in enumerate(constraints):
+        for p in (phrases or []):
+            p = [int(x) for x in p]
+            if not p:
+                raise ValueError(f"utterance {b}: an empty constraint phrase")
+            toks += p
+            ends += [0] * (len(p) - 1) + [1]
+        off.append(len(toks))
+    return (np.asarray(toks or [0], np.int32), np.asarray(off, np.int32), np.asarray(ends or [0], np.int32))
+
+
 SS_OP_BEAM_CAND = 64     # row stride of the candidate lists of ss_op_beam_topk / ss_op_beam_merge
 
 # symbol -> (restype, argtypes); must list every function include/streamspeech_hip.h declares
@@ -303,6 +325,12 @@ SIGNATURES = {
                                          C.POINTER(C.c_int32), _i, _f, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32),
                                          C.POINTER(_f), C.POINTER(_f), _vp, _i, C.POINTER(SSMtSearchOpts), C.POINTER(_i64),
                                          C.POINTER(SSMtSampleOpts)]),
+    "ss_mt_cons_table_host": (_i, [_i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _i,
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ss_batch_mt_beam_cons": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _f, _i,
+                                   C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(_f), C.POINTER(_f), _vp, _i,
+                                   C.POINTER(SSMtSearchOpts), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ss_mt_cons_select_host": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ss_batch_fbank_frames": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f,
                                    C.POINTER(_vp)]),
     "ss_batch_fbank_frames_sr": (_i, [_vp, _vp, _i, C.POINTER(_vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -407,6 +435,7 @@ SIGNATURES = {
                                   _vp, _vp, _vp]),
     "ss_op_beam_merge_opts": (_i, [_vp, C.POINTER(SSOpBeamState), _i, _i, _i, _i, _i, _i, _i, _i, _f]),
     "ss_op_beam_prefix_score_opts": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _f, _vp, _f]),
+    "ss_op_beam_cons_select": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ss_op_sample_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp,
                                C.POINTER(SSMtSampleOpts), _vp, _vp, _vp, _vp]),
     "ss_op_sample_uniform": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -47,6 +47,9 @@ line goes on rejecting `--temperature`, which the recipe does not pass.
 `--sampling` (with `--sampling-topk K` or `--sampling-topp P`, and `--seed`) samples instead of searching: `--beam-mt N` is then the
 number of independent samples per utterance (ss_batch_mt_sample; the stream key of an utterance is its sample id).  The best-scoring
 sample is the D- text and is spoken, as hypothesis 0 of a beam is; generate-<subset>.mt.samples holds all N (id, rank, score, text).
+`--constraints [ordered] --constraints-file FILE` is fairseq's lexically constrained beam search (ss_batch_mt_beam_cons): every
+phrase the file lists for a sample id stands in its translation, in order; `C-<id>` lines go to the log and
+generate-<subset>.mt.constraints reports each phrase (id, phrase, met 0 / 1, token position).  `--constraints unordered` is refused.
 
 Pinned against the reference's own generator classes run on CPU (oracle/ref_offline.py ->
 tests/golden/offline_generator.json; tests/test_offline_generator_cpu.py, tests/test_offline_generator_gpu.py).
@@ -100,7 +103,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              references: Optional[Dict[str, Dict[int, Sequence[int]]]] = None, spoken_words: bool = False,
              mt_references: Optional[Dict[int, Sequence[int]]] = None, speak_reference: bool = False, sampling: bool = False,
              sampling_topk: int = -1, sampling_topp: float = -1.0, seed: int = 1, ctc_beam: int = 0,
-             ctc_beam_cand: Optional[int] = None, ctc_nbest: Optional[int] = None) -> Dict[int, Dict]:
+             ctc_beam_cand: Optional[int] = None, ctc_nbest: Optional[int] = None,
+             constraints: Optional[Dict[int, Sequence[Sequence[int]]]] = None) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
@@ -139,8 +143,17 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     after each batch's encoder (batch_ctc_beam: beam K, C candidates per frame -- default engine.ctc_beam_default_cand -- the N <= K
     best, default K); writes generate-<subset>.asr.nbest and .st.nbest (id, rank, score in natural log, n_tokens, text; N rows per
     id in rank order, a slot without hypothesis as score -inf, 0 tokens and no text) and changes no other file: the `A-` / `S-`
-    lines stay the arg-max."""
+    lines stay the arg-max.
+    constraints (--constraints with --constraints-file): {sample id: phrases as ids of target_unigram} -- every hypothesis of that
+    sample contains its phrases, in order (fairseq's --constraints, ordered; batch_mt_beam(constraints=), at beam_mt = 1 too).  A
+    `C-<id>` line per phrase goes to the log in front of the sample's `D-` line, as fairseq-generate prints them, and
+    generate-<subset>.mt.constraints holds a line per phrase: id, phrase, met 0 / 1, the position of its first token in the `D-`
+    hypothesis (-1 when not met).  The `D-` text, the units and the waveform follow from the constrained hypothesis; not with
+    sampling."""
     from .engine import check_search_options, sampling_from_fairseq
+    if constraints is not None and sampling:
+        raise ValueError("constraints cannot be combined with sampling: the sampling search does not support them")
+    met: Dict[int, list] = {}
     nbest_ctc: Dict[str, Dict[int, list]] = {"asr": {}, "st": {}}
     if ctc_beam:
         ctc_nbest = int(ctc_beam) if ctc_nbest is None else int(ctc_nbest)
@@ -217,6 +230,10 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
             toks = [h[0]["tokens"] if h else [] for h in nbest]
             for b, sid in enumerate(ids):
                 samples[sid] = [(h["score"], detok([dicts["target_unigram"][c] for c in h["tokens"] if c != cfg.eos])) for h in nbest[b]]
+        elif constraints is not None:
+            nbest, feats, n = model.batch_mt_beam(enc, Tp, mx, beam_mt, 1, unk_penalty, normalize,
+                                                  constraints=[constraints.get(sid) or [] for sid in ids], **search)
+            toks = [h[0]["tokens"] if h else [] for h in nbest]
         elif beam_mt > 1 or search:
             # --beam-mt k: the reference's beam search (generator_mt with beam_size_mt = k, --unkpen, --unnormalized); the D- text
             # and the T2U input are hypothesis 0 of each n-best list (sequence_generator_multi_decoder_ctc.py:265-300)
@@ -272,6 +289,12 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
             d_txt = detok([dicts["target_unigram"][c] for c in mt])
             print(f"A-{sid}\t{a_txt}", file=log_f)
             print(f"S-{sid}\t{s_txt}", file=log_f)
+            if constraints is not None:
+                met[sid] = []
+                for p, at in zip(constraints.get(sid) or [], phrase_positions(mt, constraints.get(sid) or [])):
+                    p_txt = detok([dicts["target_unigram"][c] for c in p])
+                    print(f"C-{sid}\t{p_txt}", file=log_f)
+                    met[sid].append((p_txt, at))
             print(f"D-{sid}\t{d_txt}", file=log_f)
             unit_str = " ".join(str(u) for u in codes[b])
             score, pos = 0.0, None
@@ -335,6 +358,11 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
             for sid in sorted(samples):
                 for rank, (score, text) in enumerate(samples[sid]):
                     print(f"{sid}\t{rank}\t{score:.6f}\t{text}", file=f)
+    if constraints is not None:
+        with open(os.path.join(results_path, f"generate-{subset}.mt.constraints"), "w", encoding="utf-8") as f:
+            for sid in sorted(met):
+                for p_txt, at in met[sid]:
+                    print(f"{sid}\t{p_txt}\t{0 if at is None else 1}\t{-1 if at is None else at}", file=f)
     if mt_alignment:
         with open(os.path.join(results_path, f"generate-{subset}.mt.words"), "w", encoding="utf-8") as f:
             for sid in sorted(words["mt"]):
@@ -527,6 +555,50 @@ def load_mt_references(data_root: str, multitask_yaml: Optional[str], subset: st
     return {i: [dicts["target_unigram"].index(p) for p in text[n]] for i, n in names.items() if n in text}
 
 
+def phrase_positions(tokens: Sequence[int], phrases: Sequence[Sequence[int]]) -> List[Optional[int]]:
+    """Where each phrase starts in tokens, the phrases matched left to right one after the other; None from the first that is
+    missing."""
+    tokens, out, start = [int(t) for t in tokens], [], 0
+    for p in phrases:
+        p = [int(t) for t in p]
+        hit = next((i for i in range(start, len(tokens) - len(p) + 1) if tokens[i:i + len(p)] == p), None)
+        if hit is None:
+            break
+        out.append(hit)
+        start = hit + len(p)
+    return out + [None] * (len(phrases) - len(out))
+
+
+def parse_constraints_file(lines, dictionary) -> Dict[int, List[List[int]]]:
+    """--constraints-file: lines `id<TAB>phrase<TAB>phrase...`, a phrase being the space-separated pieces of the target dictionary
+    (as the multitask manifests spell the reference text) -> {sample id: phrases as ids}.  Blank lines are skipped; an id may stand
+    on several lines.  An id that is no integer, an empty phrase, or a piece the dictionary does not hold is a ValueError naming the
+    id."""
+    out: Dict[int, List[List[int]]] = {}
+    unk, index = dictionary.unk(), {}
+    for i in range(len(dictionary)):
+        index.setdefault(dictionary[i], i)
+    for ln in lines:
+        ln = ln.rstrip("\r\n")
+        if not ln.strip():
+            continue
+        cells = ln.split("\t")
+        try:
+            sid = int(cells[0])
+        except ValueError:
+            raise ValueError(f"constraints file: {cells[0]!r} is not a sample id") from None
+        for cell in cells[1:]:
+            pieces = cell.split()
+            if not pieces:
+                raise ValueError(f"constraints file, id {sid}: an empty phrase")
+            ids = [index.get(p, unk) for p in pieces]
+            bad = [p for p, i in zip(pieces, ids) if i == unk]
+            if bad:
+                raise ValueError(f"constraints file, id {sid}: {bad[0]!r} is not in the target dictionary")
+            out.setdefault(sid, []).append(ids)
+    return out
+
+
 def _pack_batch(model, wavs: List[torch.Tensor]):
     """The waveforms of one batch -> int16 NumPy arrays: one ss_pcm_pack_s16 launch over all of them, one download."""
     n = [int(w.numel()) for w in wavs]
@@ -694,6 +766,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--sampling-topp", type=float, default=-1.0,
                     help="with --sampling: sample from the smallest set of tokens whose mass reaches p (-1 = off; not with top-k)")
     ap.add_argument("--seed", type=int, default=1, help="seed of --sampling; an utterance's stream key is its sample id")
+    ap.add_argument("--constraints", nargs="?", const="ordered", default=None, choices=["ordered", "unordered"],
+                    help="text search: lexically constrained beam search (fairseq's --constraints): every phrase of "
+                         "--constraints-file stands in the translation, in the order given.  Only `ordered` is implemented")
+    ap.add_argument("--constraints-file", default=None,
+                    help="with --constraints: lines `id<TAB>phrase<TAB>phrase...`, phrases as space-separated pieces of the "
+                         "target_unigram dictionary; writes C-<id> lines and generate-<subset>.mt.constraints")
     ap.add_argument("--pcm16-io", action="store_true",
                     help="16-bit WAV sources are staged as raw frames, uploaded once and decoded on the device, and pred_wav/ is "
                          "written from 16-bit PCM packed on the device (one download per batch); the same files as without it")
@@ -714,6 +792,12 @@ def main(argv: Optional[List[str]] = None):
         sampling_from_fairseq(a.sampling, a.sampling_topk, a.sampling_topp, a.seed)
     except ValueError as e:
         ap.error(str(e))
+    if a.constraints == "unordered":
+        ap.error("--constraints unordered is not implemented: only the ordered representation (fairseq's default) is")
+    if bool(a.constraints) != bool(a.constraints_file):
+        ap.error("--constraints and --constraints-file go together")
+    if a.constraints and a.sampling:
+        ap.error("--constraints cannot be combined with --sampling")
     if a.ctc_beam:
         from .lib import CTC_BEAM_MAX_BEAM, CTC_BEAM_MAX_CAND
         if not 1 <= a.ctc_beam <= CTC_BEAM_MAX_BEAM:
@@ -821,6 +905,13 @@ def main(argv: Optional[List[str]] = None):
         items.append((e[0], pcm))
     references = load_references(a.data, a.multitask_config_yaml, a.gen_subset, holder.dict) if a.align_reference else None
     mt_references = load_mt_references(a.data, a.multitask_config_yaml, a.gen_subset, holder.dict) if a.score_reference else None
+    glossary = None
+    if a.constraints:
+        with open(a.constraints_file, encoding="utf-8") as f:
+            try:
+                glossary = parse_constraints_file(f, holder.dict["target_unigram"])
+            except ValueError as e:
+                ap.error(str(e))
     sub = a.gen_subset if a.num_shards == 1 else f"{a.gen_subset}.shard{a.shard_id}"
     hyps = generate(model, voc, items, holder.dict, a.results_path, sub, a.batch_size, a.max_tokens, a.max_len_a,
                     a.max_len_b, a.max_len_a_mt, a.max_len_b_mt, a.dur_prediction, not a.no_wav,
@@ -836,7 +927,8 @@ def main(argv: Optional[List[str]] = None):
                        if (a.lenpen, a.no_repeat_ngram_size) != (1.0, 0) else {}),
                     **({"sampling": True, "sampling_topk": a.sampling_topk, "sampling_topp": a.sampling_topp, "seed": a.seed}
                        if a.sampling else {}),
-                    **({"ctc_beam": a.ctc_beam, "ctc_beam_cand": a.ctc_beam_cand, "ctc_nbest": a.ctc_nbest} if a.ctc_beam else {}))
+                    **({"ctc_beam": a.ctc_beam, "ctc_beam_cand": a.ctc_beam_cand, "ctc_nbest": a.ctc_nbest} if a.ctc_beam else {}),
+                    **({"constraints": glossary} if glossary is not None else {}))
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
 
 
