@@ -28,6 +28,7 @@
   } while (0)
 
 #define SS_LAUNCH_CHECK() SS_HIP_CHECK(hipGetLastError())
+#define RET(x) do { int _r = (x); if (_r != SS_OK) return _r; } while (0)
 
 // Raise a kernel's dynamic-LDS limit once PER DEVICE, from whichever host thread launches it first there (bench.py drives the
 // library from 8 threads; hipFuncSetAttribute applies to the current device's function object only, so a process that drives

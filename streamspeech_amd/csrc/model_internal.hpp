@@ -95,7 +95,6 @@ struct DevBuf {
 struct Lin { const float* w = nullptr; const float* b = nullptr; };
 struct LN { const float* g = nullptr; const float* b = nullptr; };
 
-#define RET(x) do { int _r = (x); if (_r != SS_OK) return _r; } while (0)
 static int mt_persistent_env() {
   const char* e = getenv("SS_MT_PERSISTENT");
   const int v = e ? atoi(e) : 0;

@@ -138,7 +138,7 @@ class SSOpAttnProbsArgs(C.Structure):
 
 
 class SSOpBeamState(C.Structure):
-    """ss_op_beam_state: BeamState (csrc/beam.hip) field for field, pointers as device addresses."""
+    """ss_op_beam_state: BeamState (csrc/beam.hpp) field for field, pointers as device addresses."""
     _fields_ = [(n, _vp) for n in (
         "tok", "cum", "anc", "cand_s", "cand_t", "ignore", "done", "max_len", "npre",
         "fin_cnt", "fin_score", "fin_len", "fin_tok", "fin_pos", "fin_anc")]

@@ -1,5 +1,5 @@
 """Lexically constrained beam search restated in Python (the rule: include/streamspeech_hip.h at ss_batch_mt_beam_cons).
-Written from the rule, not from the kernels: the tests hold csrc/beam.hip against this file, and this file against the reference's
+Written from the rule, not from the kernels: the tests hold csrc/beam_kernels.hip against this file, and this file against the reference's
 LexicallyConstrainedBeamSearch through the per-step traces of tests/golden/mt_constraints.json (tests/make_golden_mt_constraints.py).
 
 Plain Python lists and numpy float32 scalars; nothing here is fast."""

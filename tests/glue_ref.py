@@ -1,8 +1,8 @@
-"""Plain references of the decode glue kernels (csrc/elementwise.hip) and of the beam-search kernels (csrc/beam.hip): NumPy, float64
+"""Plain references of the decode glue kernels (csrc/elementwise.hip) and of the beam-search kernels (csrc/beam_kernels.hip): NumPy, float64
 where there is arithmetic, one obvious expression or loop per operation, no tiling and no tricks.  tests/test_glue_ref_cpu.py checks
 each against the torch expression the kernel's comment cites; tests/test_glue_ops_gpu.py checks the kernels against them.
 
-Shapes and layouts are the kernels' (see the comments of csrc/elementwise.hpp and BeamState in csrc/beam.hip); ids are Python ints or
+Shapes and layouts are the kernels' (see the comments of csrc/elementwise.hpp and BeamState in csrc/beam.hpp); ids are Python ints or
 int64 arrays, never wrapped.
 """
 import numpy as np

@@ -1,5 +1,5 @@
 """Sampling from the first-pass text decoder, restated in numpy from the rule (include/streamspeech_hip.h, ss_mt_sample_opts).
-Written from the rule, not from the kernel: the tests hold csrc/beam.hip against this file, and this file against the reference's
+Written from the rule, not from the kernel: the tests hold csrc/beam_sample.hip against this file, and this file against the reference's
 own Sampling._sample_topp / topk where the reference tree is present (tests/test_sampling_ref_cpu.py).
 
 A row's candidate values v[n] are float64 here: the float32 division of the logits by the temperature, a float64 log-softmax, the

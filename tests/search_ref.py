@@ -1,5 +1,5 @@
 """The three controls of the first-pass text search, restated in numpy over explicit token rows (include/streamspeech_hip.h,
-ss_mt_search_opts).  Written from the rules, not from the kernels: the tests hold csrc/beam.hip against this file, and this file
+ss_mt_search_opts).  Written from the rules, not from the kernels: the tests hold csrc/beam_kernels.hip against this file, and this file
 against the reference's NGramRepeatBlock where the reference tree is present (tests/test_search_options_cpu.py).
 
 A hypothesis row at reference step `step` holds tokens[0 .. step]: </s>, the forced prefix, the generated tokens."""

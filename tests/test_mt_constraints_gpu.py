@@ -1,4 +1,4 @@
-"""Lexically constrained beam search on the GPU (csrc/beam.hip: beam_topk_cons_kernel, beam_merge_cons_kernel,
+"""Lexically constrained beam search on the GPU (csrc/beam_kernels.hip: beam_topk_cons_kernel, beam_merge_cons_kernel,
 beam_cons_select_kernel; ss_batch_mt_beam_cons).
 
 Op level: the selection kernel through ss_op_beam_cons_select against the restatement of the rule in tests/constraint_ref.py, on the

@@ -1,4 +1,4 @@
-"""The sampling kernels at op level (csrc/beam.hip: sample_uniform_kernel, sample_step_kernel) against the restatement of the rule in
+"""The sampling kernels at op level (csrc/beam_sample.hip: sample_uniform_kernel, sample_step_kernel) against the restatement of the rule in
 tests/sampling_ref.py (float64).
 
 Uniforms: the three known Philox vectors and 1024 random (seed, key, step, j), word for word.

@@ -1,4 +1,4 @@
-"""The text search controls on the GPU (csrc/beam.hip: beam_topk_opts_kernel, beam_merge_lenpen_kernel,
+"""The text search controls on the GPU (csrc/beam_kernels.hip: beam_topk_opts_kernel, beam_merge_lenpen_kernel,
 beam_prefix_score_temp_kernel and the *_opts entry points).
 
 Op level, each kernel through its ss_op_* entry: the no-repeat ban against the numpy restatement of tests/search_ref.py on rows whose
