@@ -824,6 +824,66 @@ int ss_batch_ctc_beam(ss_model* m, void* stream, int head, int B, const float* d
  * NaN for a row that holds a NaN) and h_cand_id [sum T][cand] (-1 where a row has fewer) may be NULL. */
 int ss_ctc_beam_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
                      int nbest, ss_ctc_beam_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den, int32_t* h_cand_id);
+/* ---- A back-off n-gram language model on the device, and its shallow fusion into the CTC prefix beam search (csrc/ngram_lm.hpp,
+ * ngram_lm.hip; the fused search: csrc/ctc_beam.hpp).  The model is a forward trie in one open-addressed table: entry 0 is the root
+ * (the empty context), the n-gram (w1 .. wk) is the child (entry of (w1 .. wk-1), wk).  Values are natural logarithms, float32,
+ * taken as given.  THE SCORING RULE lp(c | state), in float64: acc = 0; loop { (state, c) is an entry e: return acc + logp[e], the
+ * new state is e's longest suffix of at most order - 1 tokens that is an entry; state is the root: leave; else acc +=
+ * backoff[state] and state = its longest proper suffix that is an entry }; at the root without a unigram for c: acc + logp[unk]
+ * (new state: from the unk unigram) when the model has a unigram for unk, else acc + oov_logp (new state: the root).  This is ARPA
+ * back-off: the longest context first, a context's weight only where that context exists.  A sequence starts in the state reached
+ * from the root by bos (bos >= 0 and the model has that unigram; else the root); the bos unigram's own value is never scored. ---- */
+typedef struct ss_ngram_lm ss_ngram_lm;
+#define SS_NGRAM_MAX_ORDER 6
+/* Builds the table on the host (checks, trie, suffix links, slot placement); the one upload is made by the first device call that
+ * uses the model, so creation needs no device; the table then lives on the device that was current at that call, and the object
+ * serves that device.  The n-grams are grouped by order, ascending: order k holds h_counts[k - 1] rows of
+ * k ids in h_tokens, and h_logp / h_backoff hold one value per n-gram in that order (backoff 0 where the file gives none).  bos /
+ * eos / unk: ids, or -1 for none.  SS_ERR_ARG, with nothing allocated: an order outside [1, SS_NGRAM_MAX_ORDER], V <= 0, an id
+ * outside [0, V) (bos / eos / unk outside [-1, V)), a duplicate n-gram, an n-gram whose context (itself minus its last token) is
+ * not an entry, a non-finite logp / backoff / oov_logp, more than 2^30 entries, a missing pointer.  A missing SUFFIX is legal.
+ * Read-only afterwards: one object serves every context and stream. */
+int ss_ngram_lm_create(int order, const int64_t* h_counts, const int32_t* h_tokens, const float* h_logp, const float* h_backoff,
+                       int V, int bos, int eos, int unk, float oov_logp, ss_ngram_lm** out);
+void ss_ngram_lm_destroy(ss_ngram_lm* lm);
+/* order, entries (the root included), slots of the table (the power of two >= 2 entries) and the bytes it takes on the device
+ * (12 per slot + 16 per entry); each pointer may be NULL. */
+int ss_ngram_lm_info(const ss_ngram_lm* lm, int32_t* order, int64_t* entries, int64_t* slots, int64_t* device_bytes);
+/* The scoring rule in plain C++ on B packed sequences (h_n[b] tokens each), every one from the start state: h_lp receives per
+ * token its float64 lp and, with with_eos, one more value per sequence, lp(eos | final state) -- h_n[b] + with_eos values per
+ * sequence, packed; h_state (may be NULL) the state after each of them.  SS_ERR_ARG: a NULL lm, B <= 0, a negative count,
+ * with_eos on a model without eos. */
+int ss_ngram_score_host(const ss_ngram_lm* lm, int B, const int32_t* h_tokens, const int32_t* h_n, int with_eos, double* h_lp,
+                        int32_t* h_state);
+/* The LM form of the search above.  A prefix also carries its LM state, lm_sum (the sum of lp over its tokens) and bonus, fixed
+ * when its trie node is made: the child by c with lp = lp(c | state of the parent) has bonus[parent] + ((lm_weight * lp) +
+ * word_score), three rounded float64 operations.  A frame's entries are ordered by fused = tot + bonus in place of tot (ties as
+ * above); pb / pnb / tot stay pure CTC quantities, an entry is alive when its tot is above -inf, and the candidates are chosen
+ * by the acoustic logit alone.  At the end prefix r of the last beam gets fin = fused + lm_weight * lp(eos | its state) with
+ * eos_term (fin = fused without; word_score is not applied to eos), and the n-best are the last beam by fin descending, the
+ * earlier rank first on a tie. */
+typedef struct ss_ctc_lm_opts {
+  double lm_weight;
+  double word_score;
+  int32_t eos_term;    /* non-zero: the eos term (the model needs an eos id) */
+} ss_ctc_lm_opts;
+typedef struct ss_ctc_beam_lm_hyp {
+  double score;        /* fin */
+  double ctc_score;    /* tot: ss_ctc_beam_hyp.score, the aligner's scale */
+  double lm_score;     /* lm_sum (with eos_term, the eos term included): natural log, unweighted */
+  int32_t n_tokens;
+  int32_t status;      /* as ss_ctc_beam_hyp; for 1 and 2: n_tokens = 0, score = ctc_score = -inf / NaN, lm_score = 0 */
+} ss_ctc_beam_lm_hyp;
+/* ss_batch_ctc_beam with a model: its arguments, outputs, refusals and pack invariance, and SS_ERR_ARG, with nothing launched
+ * or written, for a NULL lm or opts, a model whose V is not the head's, a non-finite lm_weight / word_score, eos_term on a model
+ * without eos.  Working memory: ss_batch_ctc_beam's plus 20 (1 + beam Tp) bytes per utterance -- under 76 beam Tp + 136 Tp. */
+int ss_batch_ctc_beam_lm(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int beam, int cand,
+                         int nbest, ss_ctc_beam_lm_hyp* d_hyps, int32_t* d_tokens, int out_stride, const ss_ngram_lm* lm,
+                         const ss_ctc_lm_opts* opts);
+/* The plain-C++ twin, as ss_ctc_beam_host is of the plain search. */
+int ss_ctc_beam_lm_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
+                        int nbest, ss_ctc_beam_lm_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den, int32_t* h_cand_id,
+                        const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts);
 /* Lockstep beam-1 search from [</s>] (offline: no prefix).  h_max_len[b] = forced-</s> step of
  * utterance b.  h_out_tokens [B][out_stride] receives the generated tokens (incl. the final </s>),
  * h_n_out[b] their number (= rows of valid decoder states); d_feats is [B][feat_rows][dec_dim].
@@ -1495,6 +1555,14 @@ int ss_op_unit_spans(void* stream, int B, const int32_t* d_raw, const int32_t* h
 int ss_op_ctc_beam(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam,
                    int cand, int nbest, ss_ctc_beam_hyp* d_hyps, int32_t* d_tokens, int out_stride, float* d_den,
                    int32_t* d_cand_id);
+/* ss_op_ctc_beam with a model: the kernels of ss_batch_ctc_beam_lm on the caller's logits.  tests/test_ctc_beam_lm_gpu.py. */
+int ss_op_ctc_beam_lm(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam,
+                      int cand, int nbest, ss_ctc_beam_lm_hyp* d_hyps, int32_t* d_tokens, int out_stride, float* d_den,
+                      int32_t* d_cand_id, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts);
+/* ss_ngram_score_host on the device, one wave per sequence: d_tokens packed (device), h_n on the host, d_lp / d_state (may be
+ * NULL) device arrays laid out as the host call's.  The op-level handle on the lookup the fused search runs.  Stream-ordered. */
+int ss_op_ngram_score(void* stream, const ss_ngram_lm* lm, int B, const int32_t* d_tokens, const int32_t* h_n, int with_eos,
+                      double* d_lp, int32_t* d_state);
 /* The beam cap of ss_ctc_beam_host alone (the kernels keep SS_CTC_BEAM_MAX_BEAM): tests/test_ctc_beam_cpu.py raises it so that every
  * labelling of a tiny case fits the beam.  -> the cap before the call; max_beam < 1 only reads it. */
 int ss_debug_ctc_beam_host_max(int max_beam);

@@ -254,6 +254,30 @@ extern "C" int ss_batch_ctc_beam(ss_model* m, void* stream, int head, int B, con
   return launch_ctc_beam(logits, V, V, c.pad, c.unk, plan, m->sc->seg_buf.p, m->sc->ws.p, d_hyps, d_tokens, out_stride, nullptr, nullptr, s);
 }
 
+// The same with an n-gram model fused into the order (ctc_beam.hpp): the plain call's GEMM, scopes and buffers, 20 more bytes per
+// trie node in the encoder scratch; the model's refusals come with the plain ones, before the first launch.
+extern "C" int ss_batch_ctc_beam_lm(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int beam,
+                                    int cand, int nbest, ss_ctc_beam_lm_hyp* d_hyps, int32_t* d_tokens, int out_stride,
+                                    const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts) {
+  if (!m || B <= 0 || head < 0 || head > 1 || !d_enc_out || !h_Tp || !d_hyps || !d_tokens) return SS_ERR_ARG;
+  const ss_config& c = m->cfg;
+  const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
+  CtcBeamPlan plan;
+  RET(ctc_beam_plan(V, B, h_Tp, beam, cand, nbest, out_stride, plan));
+  RET(ctc_beam_lm_check(lm, V, opts));
+  SkScope sk_scope(m->sc->skws);
+  CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
+  hipStream_t s = (hipStream_t)stream;
+  RET(m->sc->mt_ws.ensure((size_t)plan.rows * V * sizeof(float)));
+  RET(m->sc->ws.ensure(plan.work_bytes_lm()));
+  RET(m->sc->seg_buf.ensure(ctc_beam_table_bytes(plan)));
+  float* logits = m->sc->mt_ws.f();
+  RET(linear(s, d_enc_out, c.enc_dim, plan.rows, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, logits, V));
+  m->sc->dbg_logits = logits; m->sc->dbg_rows = plan.rows; m->sc->dbg_cols = V;
+  return launch_ctc_beam_lm(logits, V, V, c.pad, c.unk, plan, m->sc->seg_buf.p, m->sc->ws.p, lm, opts, d_hyps, d_tokens, out_stride,
+                            nullptr, nullptr, s);
+}
+
 // Batched beam-1 search: all utterances start from [</s>] and advance in lockstep, one row per
 // utterance (M = B GEMMs stream every decoder weight once per step for the whole batch).
 extern "C" int ss_batch_mt_greedy(ss_model* m, void* stream, int B, const float* d_enc_out, const int32_t* h_Tp,

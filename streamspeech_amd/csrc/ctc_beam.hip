@@ -6,10 +6,13 @@
 //   ctc_beam_search_kernel  one workgroup per utterance, a loop over its frames: beam, candidates and merge state in LDS, the trie
 //                           of label strings and its child table in global scratch, the back-trace of the n-best at the end
 // plus the plain-C++ twin of both (ss_ctc_beam_host) over the same step code (ctc_beam.hpp, where the search and its order are
-// defined).
+// defined).  The search kernel and the twin each have an LM form (ctc_beam_search_lm_kernel, ss_ctc_beam_lm_host): the same body
+// with a back-off n-gram model (ngram_lm.hpp) fused into the order of a frame's entries.
 #include "ctc_beam.hpp"
 
 #include <cstring>
+
+#include "ngram_lm.hpp"
 
 #include "../../include/streamspeech_hip.h"
 #include "elementwise.hpp"
@@ -124,10 +127,24 @@ __global__ __launch_bounds__(256) void ctc_beam_cand_kernel(const float* __restr
 // ctc_align_trellis_kernel).  Every operation of an utterance happens inside its own workgroup in an order that depends on its own
 // data alone (node ids are ctc_beam_new_node's, not a counter's; the child table's contents depend on the insertion order only in
 // which of two colliding keys sits first, never in what a lookup returns), so its outputs are the same bits alone and in any pack.
-__global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __restrict__ logits, int ld, const CtcBeamSeg* __restrict__ segs,
-                                                              int beam, int C, int nbest, const float* den, const int* cand_id,
-                                                              unsigned long long* keys_all, int* vals_all, int2* nodes_all,
-                                                              ss_ctc_beam_hyp* hyps, int* tokens, int out_stride) {
+// The LM form (LM = true; ctc_beam.hpp, ngram_lm.hpp) is the same body: the frame's order compares e_fus = tot + bonus in place of
+// e_tot (8 more bytes of LDS per entry and 8 per beam slot: 8.9 KB at the caps), pass B looks up the bonus of an extension that
+// is alive (its node's, or lp_lm from the parent's state: one chain of dependent probes per entry, parallel over the entries),
+// pass D gives a new node its three LM fields, and the end ranks the last beam by fin.  The plain form compiles to what it was.
+struct CtcBeamLm {
+  NgramView lm;
+  double lm_weight, word_score;
+  int eos_term, pad_;
+  double* n_sum;     // [nodes] of the pack, as nodes_all
+  double* n_bonus;
+  int* n_state;
+};
+
+template <bool LM>
+__device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ logits, int ld, const CtcBeamSeg* __restrict__ segs,
+                                                     int beam, int C, int nbest, const float* den, const int* cand_id,
+                                                     unsigned long long* keys_all, int* vals_all, int2* nodes_all, void* hyps_out,
+                                                     int* tokens, int out_stride, const CtcBeamLm& L) {
   constexpr int MB = CTC_BEAM_MAX_BEAM;
   __shared__ double b_pb[2 * MB], b_pnb[2 * MB], b_tot[2 * MB];
   __shared__ int b_node[2 * MB], b_last[2 * MB];
@@ -137,16 +154,21 @@ __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __res
   __shared__ int s_c[CTC_BEAM_MAX_CAND];
   __shared__ float s_lpc[CTC_BEAM_MAX_CAND], s_lpl[MB], s_lp0;
   __shared__ int s_nb[2];
+  __shared__ double e_fus[LM ? CTC_BEAM_MAX_ENT : 1], b_bonus[LM ? 2 * MB : 1];
   const int tid = threadIdx.x;
   const CtcBeamSeg sg = segs[blockIdx.x];
   unsigned long long* keys = keys_all + sg.tab_off;
   int* vals = vals_all + sg.tab_off;
   int2* nodes = nodes_all + sg.node_off;
+  double* n_sum = LM ? L.n_sum + sg.node_off : nullptr;
+  double* n_bonus = LM ? L.n_bonus + sg.node_off : nullptr;
+  int* n_state = LM ? L.n_state + sg.node_off : nullptr;
   const int mask = sg.tab_mask, W = C + 1;
   if (tid == 0) {
     b_pb[0] = 0.0; b_pnb[0] = -INFINITY; b_tot[0] = 0.0; b_node[0] = 0; b_last[0] = -1;
     s_nb[0] = 1;
     nodes[0] = make_int2(-1, -1);
+    if constexpr (LM) { b_bonus[0] = 0.0; n_sum[0] = 0.0; n_bonus[0] = 0.0; n_state[0] = L.lm.start; }
   }
   __syncthreads();
   int cur = 0;
@@ -197,30 +219,47 @@ __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __res
       }
       e_tot[e] = term;
       e_node[e] = child;
+      if constexpr (LM) {
+        double fus = -INFINITY;
+        if (term > -INFINITY) {                                // (a dead entry needs no bonus: no lookup)
+          double bonus;
+          if (child >= 0) {
+            bonus = n_bonus[child];
+          } else {
+            int nx;
+            bonus = ngram_bonus(b_bonus[co + i], L.lm_weight, ngram_lp(L.lm, n_state[node], c, &nx), L.word_score);
+          }
+          fus = term + bonus;
+        }
+        e_fus[e] = fus;
+      }
     }
     __syncthreads();
     // ---- C ----
     if (tid < nb) {
       const double pnb2 = ctc_beam_logadd(s_pnb[tid], s_give[tid]);
       s_pnb[tid] = pnb2;
-      e_tot[tid * W] = ctc_beam_logadd(s_pb[tid], pnb2);
+      const double tot = ctc_beam_logadd(s_pb[tid], pnb2);
+      e_tot[tid * W] = tot;
+      if constexpr (LM) e_fus[tid * W] = tot > -INFINITY ? tot + b_bonus[co + tid] : -INFINITY;
     }
     __syncthreads();
     // ---- D ---- (a thread's up to PER entries count in ONE walk over the frame's totals: each total is read once per thread,
     //               and no exit depends on a count, so the loads of the unrolled walk overlap)
     constexpr int PER = (CTC_BEAM_MAX_ENT + 255) / 256;
+    const double* e_key = LM ? e_fus : e_tot;                  // (a compile-time choice: what the order compares)
     double my_tot[PER];
     int my_rank[PER];
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
       const int e = tid + 256 * j;
-      my_tot[j] = e < n_ent ? e_tot[e] : -INFINITY;
+      my_tot[j] = e < n_ent ? e_key[e] : -INFINITY;
       my_rank[j] = 0;
     }
     if (n_ent > 256 || my_tot[0] > -INFINITY) {
 #pragma unroll 4
       for (int f = 0; f < n_ent; ++f) {
-        const double tf = e_tot[f];
+        const double tf = e_key[f];
 #pragma unroll
         for (int j = 0; j < PER; ++j) my_rank[j] += ctc_beam_before(tf, f, my_tot[j], tid + 256 * j);
       }
@@ -228,23 +267,33 @@ __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __res
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
       const int e = tid + 256 * j, rank = my_rank[j];
-      const double tot = my_tot[j];
+      double tot = my_tot[j];
       if (!(tot > -INFINITY) || rank >= beam) continue;       // (an entry past n_ent is -inf)
+      if constexpr (LM) tot = e_tot[e];                        // the state keeps the pure CTC total
       const int i = e / W, k = e - i * W - 1;
       int node = e_node[e];
       if (k < 0) {
         b_pb[no + rank] = s_pb[i]; b_pnb[no + rank] = s_pnb[i]; b_last[no + rank] = b_last[co + i];
+        if constexpr (LM) b_bonus[no + rank] = b_bonus[co + i];
       } else {
         const int c = s_c[k];
         if (node < 0) {                                        // a new string: its node, then its place in the child table
           node = ctc_beam_new_node(t, beam, rank);
           nodes[node] = make_int2(b_node[co + i], c);
+          if constexpr (LM) {                                  // its LM fields, written once (the lookup of pass B again)
+            int nx;
+            const double lp = ngram_lp(L.lm, n_state[b_node[co + i]], c, &nx);
+            n_state[node] = nx;
+            n_sum[node] = n_sum[b_node[co + i]] + lp;
+            n_bonus[node] = ngram_bonus(b_bonus[co + i], L.lm_weight, lp, L.word_score);
+          }
           const unsigned long long key = ctc_beam_key(b_node[co + i], c);
           for (int s = ctc_beam_slot(key, mask), n = 0; n <= mask; ++n, s = (s + 1) & mask) {
             if (atomicCAS(&keys[s], CTC_BEAM_EMPTY, key) == CTC_BEAM_EMPTY) { vals[s] = node; break; }
           }
         }
         b_pb[no + rank] = -INFINITY; b_pnb[no + rank] = tot; b_last[no + rank] = c;
+        if constexpr (LM) b_bonus[no + rank] = n_bonus[node];
       }
       b_tot[no + rank] = tot; b_node[no + rank] = node;
       atomicMax(&s_nb[cur ^ 1], rank + 1);                     // ranks are 0 .. alive - 1 without a gap
@@ -252,32 +301,106 @@ __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __res
     __syncthreads();
     cur ^= 1;
   }
-  // ---- the n-best: the last beam in rank order; thread r walks prefix r back through the trie ----
-  if (tid < nbest) {
-    const int nb = bad ? 0 : s_nb[cur];
-    ss_ctc_beam_hyp h;
-    h.score = bad ? (double)__builtin_nanf("") : -INFINITY;
-    h.n_tokens = 0;
-    h.status = bad ? 2 : 1;
+  if constexpr (!LM) {
+    // ---- the n-best: the last beam in rank order; thread r walks prefix r back through the trie ----
+    ss_ctc_beam_hyp* hyps = static_cast<ss_ctc_beam_hyp*>(hyps_out);
+    if (tid < nbest) {
+      const int nb = bad ? 0 : s_nb[cur];
+      ss_ctc_beam_hyp h;
+      h.score = bad ? (double)__builtin_nanf("") : -INFINITY;
+      h.n_tokens = 0;
+      h.status = bad ? 2 : 1;
+      if (tid < nb) {
+        const int node = b_node[cur * MB + tid];
+        int len = 0;
+        for (int n = node; n > 0; n = nodes[n].x) ++len;
+        int* out = tokens + ((size_t)blockIdx.x * nbest + tid) * out_stride;
+        int j = len;
+        for (int n = node; n > 0 && j > 0; n = nodes[n].x) out[--j] = nodes[n].y;
+        h.score = b_tot[cur * MB + tid]; h.n_tokens = len; h.status = 0;
+      }
+      hyps[(size_t)blockIdx.x * nbest + tid] = h;
+    }
+  } else {
+    // ---- the n-best of the LM form: thread r finishes prefix r of the last beam (all of it: the eos term can lift a prefix
+    //      from behind the first nbest), the beam is ranked by fin (s_give), and a prefix of rank < nbest walks back ----
+    ss_ctc_beam_lm_hyp* hyps = static_cast<ss_ctc_beam_lm_hyp*>(hyps_out);
+    const int nb = bad ? 0 : s_nb[cur];                        // (uniform, as the barrier below)
+    double fin = -INFINITY, lm_sum = 0.0;
     if (tid < nb) {
       const int node = b_node[cur * MB + tid];
-      int len = 0;
-      for (int n = node; n > 0; n = nodes[n].x) ++len;
-      int* out = tokens + ((size_t)blockIdx.x * nbest + tid) * out_stride;
-      int j = len;
-      for (int n = node; n > 0 && j > 0; n = nodes[n].x) out[--j] = nodes[n].y;
-      h.score = b_tot[cur * MB + tid]; h.n_tokens = len; h.status = 0;
+      const double fused = b_tot[cur * MB + tid] + b_bonus[cur * MB + tid];
+      lm_sum = n_sum[node];
+      fin = fused;
+      if (L.eos_term) {
+        int nx;
+        const double lp = ngram_lp(L.lm, n_state[node], L.lm.eos, &nx);
+        fin = ngram_finish(fused, L.lm_weight, lp);
+        lm_sum += lp;
+      }
+      s_give[tid] = fin;
     }
-    hyps[(size_t)blockIdx.x * nbest + tid] = h;
+    __syncthreads();
+    if (tid < nb) {
+      int rank = 0;
+      for (int f = 0; f < nb; ++f) rank += ctc_beam_before(s_give[f], f, fin, tid);
+      if (rank < nbest) {
+        const int node = b_node[cur * MB + tid];
+        int len = 0;
+        for (int n = node; n > 0; n = nodes[n].x) ++len;
+        int* out = tokens + ((size_t)blockIdx.x * nbest + rank) * out_stride;
+        int j = len;
+        for (int n = node; n > 0 && j > 0; n = nodes[n].x) out[--j] = nodes[n].y;
+        ss_ctc_beam_lm_hyp h;
+        h.score = fin; h.ctc_score = b_tot[cur * MB + tid]; h.lm_score = lm_sum; h.n_tokens = len; h.status = 0;
+        hyps[(size_t)blockIdx.x * nbest + rank] = h;
+      }
+    } else if (tid < nbest) {                                  // an empty slot
+      ss_ctc_beam_lm_hyp h;
+      h.score = h.ctc_score = bad ? (double)__builtin_nanf("") : -INFINITY;
+      h.lm_score = 0.0; h.n_tokens = 0; h.status = bad ? 2 : 1;
+      hyps[(size_t)blockIdx.x * nbest + tid] = h;
+    }
   }
+}
+
+__global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __restrict__ logits, int ld, const CtcBeamSeg* __restrict__ segs,
+                                                              int beam, int C, int nbest, const float* den, const int* cand_id,
+                                                              unsigned long long* keys_all, int* vals_all, int2* nodes_all,
+                                                              ss_ctc_beam_hyp* hyps, int* tokens, int out_stride) {
+  ctc_beam_search_body<false>(logits, ld, segs, beam, C, nbest, den, cand_id, keys_all, vals_all, nodes_all, hyps, tokens, out_stride,
+                              CtcBeamLm{});
+}
+
+__global__ __launch_bounds__(256) void ctc_beam_search_lm_kernel(const float* __restrict__ logits, int ld,
+                                                                 const CtcBeamSeg* __restrict__ segs, int beam, int C, int nbest,
+                                                                 const float* den, const int* cand_id, unsigned long long* keys_all,
+                                                                 int* vals_all, int2* nodes_all, ss_ctc_beam_lm_hyp* hyps, int* tokens,
+                                                                 int out_stride, CtcBeamLm L) {
+  ctc_beam_search_body<true>(logits, ld, segs, beam, C, nbest, den, cand_id, keys_all, vals_all, nodes_all, hyps, tokens, out_stride, L);
 }
 
 size_t ctc_beam_table_bytes(const CtcBeamPlan& p) { return p.segs.size() * sizeof(CtcBeamSeg); }
 
-int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
-                    ss_ctc_beam_hyp* hyps, int* tokens, int out_stride, float* den_out, int* cand_out, hipStream_t stream) {
+// What an LM call is refused for past the plain refusals, before anything is launched or written.
+int ctc_beam_lm_check(const ss_ngram_lm* lm, int V, const ss_ctc_lm_opts* o) {
+  if (!lm || !o || lm->host.V != V || !std::isfinite(o->lm_weight) || !std::isfinite(o->word_score)) return SS_ERR_ARG;
+  if (o->eos_term && lm->host.eos < 0) return SS_ERR_ARG;
+  return SS_OK;
+}
+
+// lm == nullptr: the plain search, hyps an ss_ctc_beam_hyp array; else the LM form (d_work holds plan.work_bytes_lm()), hyps an
+// ss_ctc_beam_lm_hyp array.
+static int launch_ctc_beam_any(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
+                               const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, void* hyps, int* tokens, int out_stride,
+                               float* den_out, int* cand_out, hipStream_t stream) {
   const int B = (int)p.segs.size();
   if (!logits || ld < V || B <= 0 || !d_table || !d_work || !hyps || !tokens) return SS_ERR_ARG;
+  CtcBeamLm L{};
+  if (lm) {
+    RET(ctc_beam_lm_check(lm, V, opts));
+    RET(ngram_device_view(lm, &L.lm));
+  }
   unsigned char* w = static_cast<unsigned char*>(d_work);
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(w);
   int2* nodes = reinterpret_cast<int2*>(w + p.key_bytes());
@@ -297,10 +420,33 @@ int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const 
   else SS_CBC(0);
 #undef SS_CBC
   SS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(B), dim3(256), 0, stream, logits, ld, static_cast<const CtcBeamSeg*>(d_table), p.beam,
-                     p.cand, p.nbest, den, cand, keys, vals, nodes, hyps, tokens, out_stride);
+  if (!lm) {
+    hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(B), dim3(256), 0, stream, logits, ld, static_cast<const CtcBeamSeg*>(d_table),
+                       p.beam, p.cand, p.nbest, den, cand, keys, vals, nodes, static_cast<ss_ctc_beam_hyp*>(hyps), tokens, out_stride);
+  } else {
+    L.lm_weight = opts->lm_weight; L.word_score = opts->word_score; L.eos_term = opts->eos_term ? 1 : 0;
+    L.n_sum = reinterpret_cast<double*>(w + p.lm_off());
+    L.n_bonus = L.n_sum + p.nodes;
+    L.n_state = reinterpret_cast<int*>(L.n_bonus + p.nodes);
+    hipLaunchKernelGGL(ctc_beam_search_lm_kernel, dim3(B), dim3(256), 0, stream, logits, ld, static_cast<const CtcBeamSeg*>(d_table),
+                       p.beam, p.cand, p.nbest, den, cand, keys, vals, nodes, static_cast<ss_ctc_beam_lm_hyp*>(hyps), tokens,
+                       out_stride, L);
+  }
   SS_LAUNCH_CHECK();
   return SS_OK;
+}
+
+int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
+                    ss_ctc_beam_hyp* hyps, int* tokens, int out_stride, float* den_out, int* cand_out, hipStream_t stream) {
+  return launch_ctc_beam_any(logits, ld, V, pad, unk, p, d_table, d_work, nullptr, nullptr, hyps, tokens, out_stride, den_out, cand_out,
+                             stream);
+}
+
+int launch_ctc_beam_lm(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
+                       const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, ss_ctc_beam_lm_hyp* hyps, int* tokens, int out_stride,
+                       float* den_out, int* cand_out, hipStream_t stream) {
+  if (!lm) return SS_ERR_ARG;
+  return launch_ctc_beam_any(logits, ld, V, pad, unk, p, d_table, d_work, lm, opts, hyps, tokens, out_stride, den_out, cand_out, stream);
 }
 
 namespace {
@@ -355,22 +501,35 @@ extern "C" int ss_debug_ctc_beam_host_max(int max_beam) {
   return was;
 }
 
-extern "C" int ss_ctc_beam_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
-                                int nbest, ss_ctc_beam_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den,
-                                int32_t* h_cand_id) {
-  if (!h_logits || ld < V || !h_hyps || !h_tokens) return SS_ERR_ARG;
+// The twin of both forms: LM = false is ss_ctc_beam_host (lm / o unused, records ss_ctc_beam_hyp), LM = true ss_ctc_beam_lm_host.
+template <bool LM>
+static int ctc_beam_host_any(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
+                             int nbest, const ss_ngram_lm* lm, const ss_ctc_lm_opts* o, void* h_hyps_out, int32_t* h_tokens,
+                             int out_stride, float* h_den, int32_t* h_cand_id) {
+  if (!h_logits || ld < V || !h_hyps_out || !h_tokens) return SS_ERR_ARG;
   CtcBeamPlan p;
   const int rc = ctc_beam_plan(V, B, h_T, beam, cand, nbest, out_stride, p, g_host_max_beam);
   if (rc != SS_OK) return rc;
+  NgramView lv{};
+  double lw = 0.0, ws = 0.0;
+  if constexpr (LM) {
+    RET(ctc_beam_lm_check(lm, V, o));
+    lv = lm->host.view(); lw = o->lm_weight; ws = o->word_score;
+  }
   const int C = cand, W = C + 1;
-  struct Pre { double pb, pnb, tot; int node, last; };
+  struct Pre { double pb, pnb, tot; int node, last; double bonus; };
   for (int b = 0; b < B; ++b) {
     const CtcBeamSeg& sg = p.segs[b];
     const int mask = sg.tab_mask;
     std::vector<unsigned long long> keys((size_t)mask + 1, CTC_BEAM_EMPTY);
     std::vector<int> vals((size_t)mask + 1, -1), par(1 + (size_t)beam * sg.T, -1), tok(1 + (size_t)beam * sg.T, -1);
-    std::vector<Pre> bm(1, Pre{0.0, -INFINITY, 0.0, 0, -1}), nx;
-    std::vector<double> e_tot, s_pb, s_pnb, s_give;
+    std::vector<Pre> bm(1, Pre{0.0, -INFINITY, 0.0, 0, -1, 0.0}), nx;
+    std::vector<double> e_tot, s_pb, s_pnb, s_give, e_fus, n_sum, n_bonus;
+    std::vector<int> n_state;
+    if constexpr (LM) {
+      n_sum.assign(par.size(), 0.0); n_bonus.assign(par.size(), 0.0); n_state.assign(par.size(), 0);
+      n_state[0] = lv.start;
+    }
     std::vector<int> e_node, cid_all((size_t)sg.T * C);
     std::vector<float> den_all(2 * (size_t)sg.T);
     for (int t = 0; t < sg.T; ++t) {                           // the candidate kernel: every row, whatever the search makes of it
@@ -389,6 +548,7 @@ extern "C" int ss_ctc_beam_host(const float* h_logits, int ld, int V, int pad, i
       const int nb = (int)bm.size(), n_ent = nb * W;
       const float lp0 = ctc_beam_lp(r[0], den[0], den[1]);
       e_tot.assign(n_ent, -INFINITY); e_node.assign(n_ent, -1);
+      if constexpr (LM) e_fus.assign(n_ent, -INFINITY);
       s_pb.assign(nb, -INFINITY); s_pnb.assign(nb, -INFINITY); s_give.assign(nb, -INFINITY);
       for (int e = 0; e < n_ent; ++e) {                        // B
         const int i = e / W, k = e - i * W - 1;
@@ -408,51 +568,111 @@ extern "C" int ss_ctc_beam_host(const float* h_logits, int ld, int V, int pad, i
           }
         }
         e_tot[e] = term; e_node[e] = child;
+        if constexpr (LM) {
+          if (term > -INFINITY) {
+            int st;
+            const double bonus = child >= 0 ? n_bonus[child] : ngram_bonus(q.bonus, lw, ngram_lp(lv, n_state[q.node], c, &st), ws);
+            e_fus[e] = term + bonus;
+          }
+        }
       }
       for (int i = 0; i < nb; ++i) {                           // C
         s_pnb[i] = ctc_beam_logadd(s_pnb[i], s_give[i]);
         e_tot[i * W] = ctc_beam_logadd(s_pb[i], s_pnb[i]);
+        if constexpr (LM) e_fus[i * W] = e_tot[i * W] > -INFINITY ? e_tot[i * W] + bm[i].bonus : -INFINITY;
       }
-      nx.assign(beam, Pre{0, 0, 0, -1, -1});                   // D
+      const std::vector<double>& e_key = LM ? e_fus : e_tot;   // what the order compares
+      nx.assign(beam, Pre{0, 0, 0, -1, -1, 0.0});              // D
       int alive = 0;
       for (int e = 0; e < n_ent; ++e) {
-        const double tot = e_tot[e];
-        if (!(tot > -INFINITY)) continue;
+        const double tot = e_tot[e], key = e_key[e];
+        if (!(key > -INFINITY)) continue;
         int rank = 0;
-        for (int f = 0; f < n_ent && rank < beam; ++f) rank += ctc_beam_before(e_tot[f], f, tot, e);
+        for (int f = 0; f < n_ent && rank < beam; ++f) rank += ctc_beam_before(e_key[f], f, key, e);
         if (rank >= beam) continue;
         const int i = e / W, k = e - i * W - 1;
         int node = e_node[e];
         if (k < 0) {
-          nx[rank] = Pre{s_pb[i], s_pnb[i], tot, node, bm[i].last};
+          nx[rank] = Pre{s_pb[i], s_pnb[i], tot, node, bm[i].last, bm[i].bonus};
         } else {
           const int c = cid[k];
           if (node < 0) {
             node = ctc_beam_new_node(t, beam, rank);
             par[node] = bm[i].node; tok[node] = c;
+            if constexpr (LM) {
+              int st;
+              const double lp = ngram_lp(lv, n_state[bm[i].node], c, &st);
+              n_state[node] = st; n_sum[node] = n_sum[bm[i].node] + lp; n_bonus[node] = ngram_bonus(bm[i].bonus, lw, lp, ws);
+            }
             const unsigned long long key = ctc_beam_key(bm[i].node, c);
             for (int s = ctc_beam_slot(key, mask), n = 0; n <= mask; ++n, s = (s + 1) & mask) {
               if (keys[s] == CTC_BEAM_EMPTY) { keys[s] = key; vals[s] = node; break; }
             }
           }
-          nx[rank] = Pre{-INFINITY, tot, tot, node, c};
+          nx[rank] = Pre{-INFINITY, tot, tot, node, c, LM ? n_bonus[node] : 0.0};
         }
         if (rank + 1 > alive) alive = rank + 1;
       }
       nx.resize(alive);
       bm.swap(nx);
     }
-    for (int k = 0; k < nbest; ++k) {
-      ss_ctc_beam_hyp& h = h_hyps[(size_t)b * nbest + k];
-      h.score = bad ? (double)__builtin_nanf("") : -INFINITY; h.n_tokens = 0; h.status = bad ? 2 : 1;
-      if (bad || k >= (int)bm.size()) continue;
-      int len = 0;
-      for (int n = bm[k].node; n > 0; n = par[n]) ++len;
-      int32_t* out = h_tokens + ((size_t)b * nbest + k) * out_stride;
-      int j = len;
-      for (int n = bm[k].node; n > 0; n = par[n]) out[--j] = tok[n];
-      h.score = bm[k].tot; h.n_tokens = len; h.status = 0;
+    if constexpr (!LM) {
+      ss_ctc_beam_hyp* h_hyps = static_cast<ss_ctc_beam_hyp*>(h_hyps_out);
+      for (int k = 0; k < nbest; ++k) {
+        ss_ctc_beam_hyp& h = h_hyps[(size_t)b * nbest + k];
+        h.score = bad ? (double)__builtin_nanf("") : -INFINITY; h.n_tokens = 0; h.status = bad ? 2 : 1;
+        if (bad || k >= (int)bm.size()) continue;
+        int len = 0;
+        for (int n = bm[k].node; n > 0; n = par[n]) ++len;
+        int32_t* out = h_tokens + ((size_t)b * nbest + k) * out_stride;
+        int j = len;
+        for (int n = bm[k].node; n > 0; n = par[n]) out[--j] = tok[n];
+        h.score = bm[k].tot; h.n_tokens = len; h.status = 0;
+      }
+    } else {
+      ss_ctc_beam_lm_hyp* h_hyps = static_cast<ss_ctc_beam_lm_hyp*>(h_hyps_out);
+      const int nb = bad ? 0 : (int)bm.size();
+      std::vector<double> fin(nb), lms(nb);
+      for (int r = 0; r < nb; ++r) {
+        const double fused = bm[r].tot + bm[r].bonus;
+        fin[r] = fused; lms[r] = n_sum[bm[r].node];
+        if (o->eos_term) {
+          int st;
+          const double lp = ngram_lp(lv, n_state[bm[r].node], lv.eos, &st);
+          fin[r] = ngram_finish(fused, lw, lp); lms[r] += lp;
+        }
+      }
+      for (int k = nb; k < nbest; ++k) {
+        ss_ctc_beam_lm_hyp& h = h_hyps[(size_t)b * nbest + k];
+        h.score = h.ctc_score = bad ? (double)__builtin_nanf("") : -INFINITY; h.lm_score = 0.0; h.n_tokens = 0; h.status = bad ? 2 : 1;
+      }
+      for (int r = 0; r < nb; ++r) {
+        int rank = 0;
+        for (int f = 0; f < nb; ++f) rank += ctc_beam_before(fin[f], f, fin[r], r);
+        if (rank >= nbest) continue;
+        ss_ctc_beam_lm_hyp& h = h_hyps[(size_t)b * nbest + rank];
+        int len = 0;
+        for (int n = bm[r].node; n > 0; n = par[n]) ++len;
+        int32_t* out = h_tokens + ((size_t)b * nbest + rank) * out_stride;
+        int j = len;
+        for (int n = bm[r].node; n > 0; n = par[n]) out[--j] = tok[n];
+        h.score = fin[r]; h.ctc_score = bm[r].tot; h.lm_score = lms[r]; h.n_tokens = len; h.status = 0;
+      }
     }
   }
   return SS_OK;
+}
+
+extern "C" int ss_ctc_beam_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
+                                int nbest, ss_ctc_beam_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den,
+                                int32_t* h_cand_id) {
+  return ctc_beam_host_any<false>(h_logits, ld, V, pad, unk, B, h_T, beam, cand, nbest, nullptr, nullptr, h_hyps, h_tokens, out_stride,
+                                  h_den, h_cand_id);
+}
+
+extern "C" int ss_ctc_beam_lm_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
+                                   int nbest, ss_ctc_beam_lm_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den,
+                                   int32_t* h_cand_id, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts) {
+  return ctc_beam_host_any<true>(h_logits, ld, V, pad, unk, B, h_T, beam, cand, nbest, lm, opts, h_hyps, h_tokens, out_stride, h_den,
+                                 h_cand_id);
 }

@@ -17,6 +17,16 @@
 // is itself in the beam is folded into that prefix's own entry.  Entry e comes before entry f when tot_e > tot_f, or the totals are
 // equal and e < f (ctc_beam_before).  The beam that leaves the frame is the first `beam` entries of that order whose total is above
 // -inf, and its ranks are their places in it; the result is the first `nbest` prefixes of the last frame's beam.
+//
+// THE LM FORM (ss_*_ctc_beam_lm; the model and its scoring rule: ngram_lm.hpp) changes none of the above and adds three things.
+// A node also carries lm_state, lm_sum (the sum of lp_lm over its tokens) and bonus, properties of the string written once, when
+// the node is made: the root (start state, 0, 0), the child by c with lp = lp_lm(c | lm_state[parent]) gets lm_sum[parent] + lp and
+// bonus[parent] + ((lm_weight * lp) + word_score) (ngram_bonus: three rounded operations).  The order of a frame's entries compares
+// fused = tot + bonus in place of tot -- an extension's bonus is its node's when the string is in the trie, and is computed from the
+// parent's state otherwise, each frame it is proposed -- while pb / pnb / tot stay pure CTC quantities and an entry is alive when its
+// tot is above -inf.  At the end hypothesis r of the last beam gets fin = fused + lm_weight * lp_lm(eos | lm_state) (eos_term; fin =
+// fused without it; word_score is not applied to eos), and the n-best are the last beam by fin descending, the earlier rank first
+// on a tie.  The candidates are chosen by the acoustic logit alone.  Per utterance 20 more bytes per node.
 #pragma once
 #include <stdint.h>
 
@@ -49,6 +59,9 @@ struct CtcBeamPlan {
   // the work buffer: child keys [slots] u64 | nodes [nodes] int2 | child values [slots] int | den [rows][2] float | cand_id [rows][cand] int
   size_t key_bytes() const { return (size_t)slots * 8; }
   size_t work_bytes() const { return (size_t)slots * 12 + (size_t)nodes * 8 + (size_t)rows * (8 + 4 * (size_t)cand); }
+  // the LM form appends, 8-byte aligned: lm_sum [nodes] double | bonus [nodes] double | lm_state [nodes] int
+  size_t lm_off() const { return (work_bytes() + 7) & ~(size_t)7; }
+  size_t work_bytes_lm() const { return lm_off() + (size_t)nodes * 20; }
 };
 
 // Every refusal of the three entry points past their pointers, before anything is launched or written: B <= 0, a beam / cand

@@ -289,6 +289,28 @@ extern "C" int ss_op_ctc_beam(void* stream, const float* d_logits, int ld, int V
   return launch_ctc_beam(d_logits, ld, V, pad, unk, plan, tmp.first.p, tmp.second.p, d_hyps, d_tokens, out_stride, d_den, d_cand_id,
                          (hipStream_t)stream);
 }
+extern "C" int ss_op_ctc_beam_lm(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam,
+                                 int cand, int nbest, ss_ctc_beam_lm_hyp* d_hyps, int32_t* d_tokens, int out_stride, float* d_den,
+                                 int32_t* d_cand_id, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts) {
+  if (!d_logits || ld < V || !d_hyps || !d_tokens) return SS_ERR_ARG;
+  CtcBeamPlan plan;
+  RET(ctc_beam_plan(V, B, h_T, beam, cand, nbest, out_stride, plan));
+  RET(ctc_beam_lm_check(lm, V, opts));
+  static thread_local std::map<hipStream_t, std::pair<DevBuf, DevBuf>> tmps;
+  auto& tmp = tmps[(hipStream_t)stream];
+  RET(tmp.first.ensure(ctc_beam_table_bytes(plan)));
+  RET(tmp.second.ensure(plan.work_bytes_lm()));
+  return launch_ctc_beam_lm(d_logits, ld, V, pad, unk, plan, tmp.first.p, tmp.second.p, lm, opts, d_hyps, d_tokens, out_stride, d_den,
+                            d_cand_id, (hipStream_t)stream);
+}
+extern "C" int ss_op_ngram_score(void* stream, const ss_ngram_lm* lm, int B, const int32_t* d_tokens, const int32_t* h_n, int with_eos,
+                                 double* d_lp, int32_t* d_state) {
+  if (!lm || B <= 0 || !h_n || !d_lp) return SS_ERR_ARG;
+  static thread_local std::map<hipStream_t, DevBuf> tmps;
+  DevBuf& tmp = tmps[(hipStream_t)stream];
+  RET(tmp.ensure(ngram_score_table_bytes(B)));
+  return launch_ngram_score(lm, B, d_tokens, h_n, with_eos, d_lp, d_state, tmp.p, (hipStream_t)stream);
+}
 extern "C" int ss_op_dur_predict(void* stream, const float* logdur, const int32_t* forced, int K, int32_t* dur, int32_t* cum,
                                  const int32_t* segs, int nseg) {
   return launch_dur_predict(logdur, forced, K, dur, cum, (hipStream_t)stream, segs, nseg);

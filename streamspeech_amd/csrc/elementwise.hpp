@@ -5,6 +5,9 @@
 
 struct ss_ctc_align_result;          // include/streamspeech_hip.h
 struct ss_ctc_beam_hyp;
+struct ss_ctc_beam_lm_hyp;
+struct ss_ctc_lm_opts;
+struct ss_ngram_lm;
 
 namespace ss {
 
@@ -102,6 +105,15 @@ struct CtcBeamPlan;
 size_t ctc_beam_table_bytes(const CtcBeamPlan& p);
 int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
                     ss_ctc_beam_hyp* hyps, int* tokens, int out_stride, float* den_out, int* cand_out, hipStream_t stream);
+// The LM form (ctc_beam.hpp, ngram_lm.hpp): d_work holds plan.work_bytes_lm(); ctc_beam_lm_check is every refusal it adds.
+int ctc_beam_lm_check(const ss_ngram_lm* lm, int V, const ss_ctc_lm_opts* opts);
+int launch_ctc_beam_lm(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
+                       const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, ss_ctc_beam_lm_hyp* hyps, int* tokens, int out_stride,
+                       float* den_out, int* cand_out, hipStream_t stream);
+// The score kernel of ngram_lm.hip: d_table (ngram_score_table_bytes) is the caller's scratch.
+size_t ngram_score_table_bytes(int B);
+int launch_ngram_score(const ss_ngram_lm* lm, int B, const int32_t* d_tokens, const int32_t* h_n, int with_eos, double* d_lp,
+                       int32_t* d_state, void* d_table, hipStream_t stream);
 
 // emb_out[k,:] = table[codes[k],:]
 int launch_gather_rows(const int* idx, const float* table, int D, float* out, int n, hipStream_t stream, int rows);  // ids outside [0, rows) read row 0

@@ -72,6 +72,9 @@ class CtcHypothesis(NamedTuple):
     """One hypothesis of batch_ctc_beam."""
     tokens: List[int]       # the labels (never blank, pad or unk)
     score: float            # log of the summed probability of its alignments: the scale of CtcAlignment.score
+    # with an n-gram model (batch_ctc_beam(lm=...)): score is the fused one, log p_ctc + lm_weight * lm_score + word_score * n
+    ctc_score: Optional[float] = None   # log p_ctc alone, the scale above
+    lm_score: Optional[float] = None    # the model's log-probability of the tokens (and </s>, with lm_eos): natural log, unweighted
 
 
 def ctc_beam_default_cand(beam: int) -> int:
@@ -294,18 +297,34 @@ class BatchMixin:
         return out
 
     def batch_ctc_beam(self, head: int, enc_packed: torch.Tensor, Tp: List[int], beam: int, cand: Optional[int] = None,
-                       nbest: Optional[int] = None) -> List[List[CtcHypothesis]]:
+                       nbest: Optional[int] = None, lm=None, lm_weight: float = 0.0, word_score: float = 0.0,
+                       lm_eos: bool = True) -> List[List[CtcHypothesis]]:
         """CTC prefix beam search on a text head (ss_batch_ctc_beam): per utterance its `nbest` (default: beam) most likely label
         strings, best first, each with the log of the summed probability of its alignments.  The rows are packed as
         batch_ctc_greedy takes them.  Fewer than nbest come back where fewer prefixes are alive, none for an utterance with a NaN
         in a row.  cand: candidates per frame (default ctc_beam_default_cand).  One buffer, one device-to-host copy.  The library
         refuses (SS_ERR_ARG, nothing launched) a beam / cand above L.CTC_BEAM_MAX_BEAM / _CAND, an nbest outside [1, beam] and
-        more than L.CTC_BEAM_MAX_FRAMES frames per utterance."""
+        more than L.CTC_BEAM_MAX_FRAMES frames per utterance.
+        lm (an ngram.NgramLM over this head's dictionary): shallow fusion (ss_batch_ctc_beam_lm) -- the hypotheses are ranked by
+        log p_ctc + lm_weight * log p_lm + word_score * n_tokens, the lm term with the model's </s> when lm_eos, and each carries
+        ctc_score and lm_score besides the fused score.  Without lm the call and its tuples are the plain ones."""
         B = len(Tp)
         cand = ctc_beam_default_cand(beam) if cand is None else int(cand)
         nbest = int(beam) if nbest is None else int(nbest)
         stride = max([int(t) for t in Tp] + [1])
         n = B * max(nbest, 0)
+        if lm is not None:
+            # int32 words: hyps [8 n] (three doubles and two ints each) | tokens [n][stride]
+            ibuf = torch.empty((8 * n + n * stride + 1,), dtype=torch.int32, device=self.device)
+            opts = L.SSCtcLmOpts(float(lm_weight), float(word_score), int(bool(lm_eos)))
+            L.check(self.lib.ss_batch_ctc_beam_lm(self.h, _stream(), head, B, _ptr(enc_packed), _i32(Tp), int(beam), cand, nbest,
+                                                  _ptr(ibuf), _ptr(ibuf[8 * n:]), stride, lm.h, C.byref(opts)), "ss_batch_ctc_beam_lm")
+            host = ibuf.cpu().numpy()
+            hyp = host[:8 * n].view(np.dtype([("score", "<f8"), ("ctc_score", "<f8"), ("lm_score", "<f8"), ("n_tokens", "<i4"),
+                                              ("status", "<i4")]))
+            return [[CtcHypothesis(host[8 * n + k * stride: 8 * n + k * stride + int(hyp["n_tokens"][k])].tolist(),
+                                   float(hyp["score"][k]), float(hyp["ctc_score"][k]), float(hyp["lm_score"][k]))
+                     for k in range(b * nbest, (b + 1) * nbest) if hyp["status"][k] == 0] for b in range(B)]
         # int32 words: hyps [4 n] (a double and two ints each, first: 8-byte aligned) | tokens [n][stride]
         ibuf = torch.empty((4 * n + n * stride + 1,), dtype=torch.int32, device=self.device)
         L.check(self.lib.ss_batch_ctc_beam(self.h, _stream(), head, B, _ptr(enc_packed), _i32(Tp), int(beam), cand, nbest, _ptr(ibuf),
@@ -981,9 +1000,11 @@ class HipModel(BatchMixin):
         return self.batch_ctc_align(head, enc_out.contiguous(), [int(enc_out.shape[0])], [list(tokens)], want_path)[0]
 
     def ctc_beam(self, head: int, enc_out: torch.Tensor, beam: int, cand: Optional[int] = None,
-                 nbest: Optional[int] = None) -> List[CtcHypothesis]:
+                 nbest: Optional[int] = None, lm=None, lm_weight: float = 0.0, word_score: float = 0.0,
+                 lm_eos: bool = True) -> List[CtcHypothesis]:
         """CTC prefix beam search of one utterance: the B = 1 call of batch_ctc_beam."""
-        return self.batch_ctc_beam(head, enc_out.contiguous(), [int(enc_out.shape[0])], beam, cand, nbest)[0]
+        return self.batch_ctc_beam(head, enc_out.contiguous(), [int(enc_out.shape[0])], beam, cand, nbest, lm, lm_weight, word_score,
+                                   lm_eos)[0]
 
     def ctc_greedy(self, head: int, enc_out: torch.Tensor, want_logits: bool = False, want_scores: bool = False):
         """-> (tokens list, frame index list, raw argmax tensor, logits or None); with want_scores three more: last frame per token

@@ -78,6 +78,18 @@ class SSCtcBeamHyp(C.Structure):
     _fields_ = [("score", C.c_double), ("n_tokens", C.c_int32), ("status", C.c_int32)]
 
 
+class SSCtcBeamLmHyp(C.Structure):
+    """ss_ctc_beam_lm_hyp: one hypothesis of the CTC prefix beam search with an n-gram model (32 bytes)."""
+    _fields_ = [("score", C.c_double), ("ctc_score", C.c_double), ("lm_score", C.c_double), ("n_tokens", C.c_int32),
+                ("status", C.c_int32)]
+
+
+class SSCtcLmOpts(C.Structure):
+    """ss_ctc_lm_opts: the weights of the fusion."""
+    _fields_ = [("lm_weight", C.c_double), ("word_score", C.c_double), ("eos_term", C.c_int32)]
+
+
+NGRAM_MAX_ORDER = 6             # SS_NGRAM_MAX_ORDER of the header
 CTC_BEAM_MAX_BEAM = 32          # SS_CTC_BEAM_MAX_BEAM / _CAND / _FRAMES of the header
 CTC_BEAM_MAX_CAND = 32
 CTC_BEAM_MAX_FRAMES = 1500
@@ -293,6 +305,13 @@ SIGNATURES = {
                                _vp, _vp, _vp]),
     "ss_batch_ctc_beam": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i]),
     "ss_ctc_beam_host": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "ss_ngram_lm_create": (_i, [_i, C.POINTER(C.c_int64), _vp, _vp, _vp, _i, _i, _i, _i, _f, C.POINTER(_vp)]),
+    "ss_ngram_lm_destroy": (None, [_vp]),
+    "ss_ngram_lm_info": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ss_ngram_score_host": (_i, [_vp, _i, _vp, C.POINTER(C.c_int32), _i, _vp, _vp]),
+    "ss_batch_ctc_beam_lm": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, C.POINTER(SSCtcLmOpts)]),
+    "ss_ctc_beam_lm_host": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,
+                                 C.POINTER(SSCtcLmOpts)]),
     "ss_batch_mt_greedy": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
                                 C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _vp, _i]),
     "ss_batch_mt_beam": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _f, _i,
@@ -417,6 +436,9 @@ SIGNATURES = {
                              _vp, _vp, _vp]),
     "ss_op_ctc_beam": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "ss_debug_ctc_beam_host_max": (_i, [_i]),
+    "ss_op_ctc_beam_lm": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,
+                               C.POINTER(SSCtcLmOpts)]),
+    "ss_op_ngram_score": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _vp, _vp]),
     "ss_op_dur_predict": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
     "ss_op_repeat_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),
     "ss_op_embed_tokens": (_i, [_vp, _vp, _vp, _vp, _f, _i, _vp, _i, _i, _i, _i, _i]),

@@ -104,7 +104,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              mt_references: Optional[Dict[int, Sequence[int]]] = None, speak_reference: bool = False, sampling: bool = False,
              sampling_topk: int = -1, sampling_topp: float = -1.0, seed: int = 1, ctc_beam: int = 0,
              ctc_beam_cand: Optional[int] = None, ctc_nbest: Optional[int] = None,
-             constraints: Optional[Dict[int, Sequence[Sequence[int]]]] = None) -> Dict[int, Dict]:
+             constraints: Optional[Dict[int, Sequence[Sequence[int]]]] = None, ctc_lm: Optional[Dict[str, object]] = None,
+             ctc_lm_weight: float = 0.5, ctc_word_score: float = 0.0) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
@@ -144,6 +145,11 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     best, default K); writes generate-<subset>.asr.nbest and .st.nbest (id, rank, score in natural log, n_tokens, text; N rows per
     id in rank order, a slot without hypothesis as score -inf, 0 tokens and no text) and changes no other file: the `A-` / `S-`
     lines stay the arg-max.
+    ctc_lm / ctc_lm_weight / ctc_word_score (--ctc-lm-asr FILE, --ctc-lm-st FILE, --ctc-lm-weight A, --ctc-word-score B; with
+    ctc_beam): {"asr": an ngram.NgramLM over source_unigram, "st": one over ctc_target_unigram}, either or both -- that head's
+    search ranks its hypotheses by log p_ctc + A log p_lm + B n_tokens (batch_ctc_beam(lm=)), `score` in its .nbest file is that
+    fused score, and its lines get two more columns behind it, ctc_score and lm_score (natural logs; an empty slot -inf and 0).
+    A head without a model, and every other file, is what it is without them.
     constraints (--constraints with --constraints-file): {sample id: phrases as ids of target_unigram} -- every hypothesis of that
     sample contains its phrases, in order (fairseq's --constraints, ordered; batch_mt_beam(constraints=), at beam_mt = 1 too).  A
     `C-<id>` line per phrase goes to the log in front of the sample's `D-` line, as fairseq-generate prints them, and
@@ -157,6 +163,9 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     nbest_ctc: Dict[str, Dict[int, list]] = {"asr": {}, "st": {}}
     if ctc_beam:
         ctc_nbest = int(ctc_beam) if ctc_nbest is None else int(ctc_nbest)
+    ctc_lm = {k: v for k, v in (ctc_lm or {}).items() if v is not None}
+    if ctc_lm and not ctc_beam:
+        raise ValueError("ctc_lm needs ctc_beam: the model is fused into the CTC prefix beam search")
     sampler = sampling_from_fairseq(sampling, sampling_topk, sampling_topp, seed)
     samples: Dict[int, list] = {}
     if spoken_words and not dump_wav:
@@ -217,7 +226,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
             _align_references(model, enc, Tp, ids, references, dicts, ref_words, ref_scores)
         if ctc_beam:
             for hd, key in ((0, "asr"), (1, "st")):
-                for sid, lst in zip(ids, model.batch_ctc_beam(hd, enc, Tp, ctc_beam, ctc_beam_cand, ctc_nbest)):
+                fuse = {"lm": ctc_lm[key], "lm_weight": ctc_lm_weight, "word_score": ctc_word_score} if key in ctc_lm else {}
+                for sid, lst in zip(ids, model.batch_ctc_beam(hd, enc, Tp, ctc_beam, ctc_beam_cand, ctc_nbest, **fuse)):
                     nbest_ctc[key][sid] = lst
         # first-pass text search: max_len = min(int(max_len_a_mt * src_len + max_len_b_mt), max positions - 1) with
         # the task's defaults 0 / 200 (tasks/speech_to_speech_ctc.py:39-40 -> sequence_generator_multi_decoder_ctc.py
@@ -342,9 +352,10 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
                     for rank in range(ctc_nbest):
                         if rank < len(lst):
                             text = detok([dicts[name][c] for c in lst[rank].tokens])
-                            print(f"{sid}\t{rank}\t{lst[rank].score:.6f}\t{len(lst[rank].tokens)}\t{text}", file=f)
+                            more = f"\t{lst[rank].ctc_score:.6f}\t{lst[rank].lm_score:.6f}" if key in ctc_lm else ""
+                            print(f"{sid}\t{rank}\t{lst[rank].score:.6f}{more}\t{len(lst[rank].tokens)}\t{text}", file=f)
                         else:
-                            print(f"{sid}\t{rank}\t-inf\t0\t", file=f)
+                            print(f"{sid}\t{rank}\t-inf" + ("\t-inf\t0" if key in ctc_lm else "") + "\t0\t", file=f)
     if spoken_words:
         with open(os.path.join(results_path, f"generate-{subset}.spoken.words"), "w", encoding="utf-8") as f:
             for sid in sorted(spoken):
@@ -737,6 +748,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--ctc-beam-cand", type=int, default=None,
                     help="with --ctc-beam: tokens a prefix is extended by per frame (1 .. 32; default beam + 1, at most 32)")
     ap.add_argument("--ctc-nbest", type=int, default=None, help="with --ctc-beam: hypotheses written per id (1 .. beam; default the beam)")
+    ap.add_argument("--ctc-lm-asr", default=None, metavar="FILE",
+                    help="with --ctc-beam: an ARPA n-gram model (.arpa / .arpa.gz) over source_unigram, fused into the ASR head's search: "
+                         "its .nbest lines are ranked by log p_ctc + A log p_lm + B n_tokens and get the columns ctc_score and lm_score "
+                         "after score")
+    ap.add_argument("--ctc-lm-st", default=None, metavar="FILE",
+                    help="the same for the ST head, a model over ctc_target_unigram")
+    ap.add_argument("--ctc-lm-weight", type=float, default=0.5, help="A, the weight of the n-gram model's log-probability (default 0.5)")
+    ap.add_argument("--ctc-word-score", type=float, default=0.0, help="B, added per token of a hypothesis (default 0)")
     ap.add_argument("--score-reference", action="store_true",
                     help="also score the recipe's reference translation (the multitask manifest <task data>/<gen-subset>.tsv of "
                          "target_unigram) with the first-pass text decoder, teacher-forced, as fairseq's --score-reference does: writes "
@@ -808,6 +827,10 @@ def main(argv: Optional[List[str]] = None):
             ap.error("--ctc-nbest must be in [1, --ctc-beam]")
     elif a.ctc_beam_cand is not None or a.ctc_nbest is not None:
         ap.error("--ctc-beam-cand and --ctc-nbest need --ctc-beam")
+    if not a.ctc_beam and (a.ctc_lm_asr or a.ctc_lm_st or a.ctc_lm_weight != 0.5 or a.ctc_word_score != 0.0):
+        ap.error("--ctc-lm-asr, --ctc-lm-st, --ctc-lm-weight and --ctc-word-score need --ctc-beam")
+    if not (math.isfinite(a.ctc_lm_weight) and math.isfinite(a.ctc_word_score)):
+        ap.error("--ctc-lm-weight and --ctc-word-score must be finite")
     if a.spoken_words and a.no_wav:
         ap.error("--spoken-words needs the durations the vocoder predicts: it cannot be combined with --no-wav")
     if a.align_reference and (a.wav_list or a.synthetic > 0 or not a.data):
@@ -912,6 +935,17 @@ def main(argv: Optional[List[str]] = None):
                 glossary = parse_constraints_file(f, holder.dict["target_unigram"])
             except ValueError as e:
                 ap.error(str(e))
+    ctc_lm = {}
+    for key, path, name in (("asr", a.ctc_lm_asr, "source_unigram"), ("st", a.ctc_lm_st, "ctc_target_unigram")):
+        if path:
+            from .ngram import NgramLM, read_arpa
+            try:
+                arrays = read_arpa(path, holder.dict[name])
+            except (OSError, ValueError) as e:
+                ap.error(f"--ctc-lm-{key}: {e}")
+            ctc_lm[key] = NgramLM(arrays)
+            print(f"| --ctc-lm-{key}: order {ctc_lm[key].order}, {ctc_lm[key].entries - 1} n-grams, {arrays['dropped']} dropped (symbols "
+                  f"not in {name}), {ctc_lm[key].device_bytes} bytes on the device", file=sys.stderr)
     sub = a.gen_subset if a.num_shards == 1 else f"{a.gen_subset}.shard{a.shard_id}"
     hyps = generate(model, voc, items, holder.dict, a.results_path, sub, a.batch_size, a.max_tokens, a.max_len_a,
                     a.max_len_b, a.max_len_a_mt, a.max_len_b_mt, a.dur_prediction, not a.no_wav,
@@ -928,7 +962,10 @@ def main(argv: Optional[List[str]] = None):
                     **({"sampling": True, "sampling_topk": a.sampling_topk, "sampling_topp": a.sampling_topp, "seed": a.seed}
                        if a.sampling else {}),
                     **({"ctc_beam": a.ctc_beam, "ctc_beam_cand": a.ctc_beam_cand, "ctc_nbest": a.ctc_nbest} if a.ctc_beam else {}),
-                    **({"constraints": glossary} if glossary is not None else {}))
+                    **({"constraints": glossary} if glossary is not None else {}),
+                    **({"ctc_lm": ctc_lm, "ctc_lm_weight": a.ctc_lm_weight, "ctc_word_score": a.ctc_word_score} if ctc_lm else {}))
+    for lm in ctc_lm.values():
+        lm.close()
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
 
 
