@@ -884,6 +884,55 @@ int ss_batch_ctc_beam_lm(ss_model* m, void* stream, int head, int B, const float
 int ss_ctc_beam_lm_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
                         int nbest, ss_ctc_beam_lm_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den, int32_t* h_cand_id,
                         const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts);
+/* ---- The same search, resumable (csrc/ctc_stream.hip; the kernel: csrc/ctc_beam.hip): a device object holds, for max_sessions slots
+ * of one text head, everything the search needs between launches -- per slot the frames consumed, a sticky "NaN seen" flag, the
+ * beam that left the last frame (pb, pnb, tot, node, last, and bonus in the LM form), the trie, its child table and the LM fields
+ * of its nodes.  The trie's node ids hold the absolute frame, so a search stopped after frame t and taken up at t + 1 IS the one-shot
+ * search: the records of an utterance's last call are ss_batch_ctc_beam's (ss_batch_ctc_beam_lm's) on all its frames, byte for byte,
+ * however the frames were split over the calls, and the records of any other call are those of the one-shot search on the frames
+ * consumed so far (LM form: without the eos term).  Meant for the rows an incremental encoder reports as final (n_final): a final
+ * row's bits never change, and under pack invariance its logits are the same bits whenever they are computed.
+ * Fixed at creation: beam, cand, nbest, the model and its options (copied).  Memory, booked on m's scratch set in one piece of exact
+ * size (SS_ERR_SCRATCH_CAP leaves the set as it was) and released at destroy, per slot, with nodes = 1 + beam * max_frames and
+ * slots = the power of two >= 2 * beam * max_frames: 12 slots + 8 nodes + 40 beam + 8 bytes, and 20 nodes more in the LM form --
+ * at beam 8 and max_frames 1500: 489552 bytes, with a model 729572.
+ * SS_ERR_ARG at creation: head outside {0, 1}, max_sessions <= 0, max_frames outside [1, SS_CTC_BEAM_MAX_FRAMES], beam / cand / nbest
+ * outside ss_batch_ctc_beam's limits, opts without lm or lm without opts, ss_batch_ctc_beam_lm's refusals of a model, a NULL
+ * pointer. ---- */
+typedef struct ss_ctc_stream ss_ctc_stream;
+typedef struct ss_ctc_stream_part {
+  int32_t frames;      /* frames the slot's search has consumed, this call included */
+  int32_t n_stable;    /* length of the longest common prefix of ALL n_alive strings of the beam (not of the first nbest alone):
+                        * every later beam entry is one of them or an extension of one, so these tokens can never change again */
+  int32_t n_alive;     /* strings in the beam; 0 with status 2 */
+  int32_t status;      /* 0, or 2 once a NaN row was seen (sticky until the slot is reset; the hypothesis records are then the
+                        * batch call's NaN records) */
+} ss_ctc_stream_part;
+int ss_ctc_stream_create(ss_model* m, int head, int max_sessions, int max_frames, int beam, int cand, int nbest, const ss_ngram_lm* lm,
+                         const ss_ctc_lm_opts* opts, ss_ctc_stream** out);
+void ss_ctc_stream_destroy(ss_ctc_stream* cs);
+/* A new utterance in `slot`.  Host-only: no stream, nothing launched; the slot's child table is cleared on the stream of its first
+ * advance after the reset.  An input shorter than the frames consumed is a new utterance, and so is a change of the encoder's
+ * chunk sizes (it restarts its finality): the caller resets first. */
+int ss_ctc_stream_reset(ss_ctc_stream* cs, int slot);
+/* One step for n sessions, stream-ordered.  Session i owns h_T[i] packed rows of d_enc_packed -- ALL its encoder output so far, as
+ * ss_stream_pool_forward / ss_encoder_stream_forward return it -- and the search of slot h_slots[i] moves from the f frames it has
+ * consumed to h_upto[i], f <= h_upto[i] <= h_T[i] (equal to f: the state is reported, nothing moves).  Only the rows [f, upto) of
+ * each session are stacked and go through the head (ss_batch_ctc_beam's GEMM and pack-invariance setting), the candidate kernel and
+ * ONE launch of the resumable search kernel, a workgroup per session.  h_final[i] non-zero: the utterance's last call -- the LM form
+ * applies the eos term (with opts->eos_term) and ranks the beam by fin as ss_batch_ctc_beam_lm does, and the slot is reset by the
+ * call itself.  Device outputs: d_hyps [n][nbest] (ss_ctc_beam_hyp; an object made with a model: ss_ctc_beam_lm_hyp, on a non-final
+ * call score = tot + bonus and lm_score = lm_sum, both without eos, in beam order), d_tokens [n][nbest][out_stride], d_part [n].
+ * SS_ERR_ARG, with nothing launched or written and the object as it was: n <= 0, a NULL pointer, m not the object's model, a slot
+ * outside the object or twice in the call, h_upto[i] < f, h_upto[i] > h_T[i], h_upto[i] > max_frames, out_stride < max h_upto. */
+int ss_ctc_stream_advance(ss_model* m, void* stream, ss_ctc_stream* cs, int n, const int32_t* h_slots, const float* d_enc_packed,
+                          const int32_t* h_T, const int32_t* h_upto, const int32_t* h_final, void* d_hyps, int32_t* d_tokens,
+                          int out_stride, ss_ctc_stream_part* d_part);
+/* The plain-C++ twin on an object of ss_debug_ctc_stream_create(on_device = 0): h_logits [sum (upto - f)][ld] are the STACKED NEW
+ * rows alone (session i's behind those of the sessions before it), every pointer a HOST pointer; the same step code, records and
+ * refusals (and ld < V; there is no h_T). */
+int ss_ctc_stream_advance_host(ss_ctc_stream* cs, int n, const int32_t* h_slots, const float* h_logits, int ld, const int32_t* h_upto,
+                               const int32_t* h_final, void* h_hyps, int32_t* h_tokens, int out_stride, ss_ctc_stream_part* h_part);
 /* Lockstep beam-1 search from [</s>] (offline: no prefix).  h_max_len[b] = forced-</s> step of
  * utterance b.  h_out_tokens [B][out_stride] receives the generated tokens (incl. the final </s>),
  * h_n_out[b] their number (= rows of valid decoder states); d_feats is [B][feat_rows][dec_dim].
@@ -1559,6 +1608,16 @@ int ss_op_ctc_beam(void* stream, const float* d_logits, int ld, int V, int pad, 
 int ss_op_ctc_beam_lm(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam,
                       int cand, int nbest, ss_ctc_beam_lm_hyp* d_hyps, int32_t* d_tokens, int out_stride, float* d_den,
                       int32_t* d_cand_id, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts);
+/* An ss_ctc_stream without a model, for V columns with the ids pad / unk (< 0: none): on_device = 0 in host memory, for
+ * ss_ctc_stream_advance_host; else in device memory that no scratch set books, for ss_op_ctc_stream_advance.  Refusals as
+ * ss_ctc_stream_create (V <= 0 in place of the head).  tests/test_ctc_stream_cpu.py, tests/test_ctc_stream_gpu.py. */
+int ss_debug_ctc_stream_create(int V, int pad, int unk, int on_device, int max_sessions, int max_frames, int beam, int cand, int nbest,
+                               const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, ss_ctc_stream** out);
+/* The kernels of ss_ctc_stream_advance on the caller's device logits: arguments as ss_ctc_stream_advance_host with d_logits and
+ * the outputs on the device. */
+int ss_op_ctc_stream_advance(void* stream, ss_ctc_stream* cs, int n, const int32_t* h_slots, const float* d_logits, int ld,
+                             const int32_t* h_upto, const int32_t* h_final, void* d_hyps, int32_t* d_tokens, int out_stride,
+                             ss_ctc_stream_part* d_part);
 /* ss_ngram_score_host on the device, one wave per sequence: d_tokens packed (device), h_n on the host, d_lp / d_state (may be
  * NULL) device arrays laid out as the host call's.  The op-level handle on the lookup the fused search runs.  Stream-ordered. */
 int ss_op_ngram_score(void* stream, const ss_ngram_lm* lm, int B, const int32_t* d_tokens, const int32_t* h_n, int with_eos,

@@ -205,6 +205,8 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
     """Simultaneous speech-to-speech translation agent for StreamSpeech on the HIP backend."""
 
     def __init__(self, args, model=None, vocoder=None):
+        from .text_policy import ctc_beam_flags
+        ctc_beam_flags(args, "S2ST")                       # (raises: the flags are the ASR agent's)
         super().__init__(args)
         self.eos = DEFAULT_EOS
         self.args = args
@@ -333,6 +335,16 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
         a("--word-details", action="store_true", default=False,
           help="after every policy() that ran the encoder, agent.details holds the words of both CTC heads with their time spans, "
                "confidences and stability (streamspeech_amd/words.py); default: off, the heads run exactly as without the flag")
+        a("--ctc-beam", type=int, default=0,
+          help="streaming ASR agent: K > 0 replaces the arg-max frame path by a CTC prefix beam search of beam K that is resumed on "
+               "the encoder rows each call makes final (engine.CtcStream); every call writes the new text of the prefix all beam "
+               "strings share, the last call the rest of the best hypothesis (agent.nbest: the final n-best); 0 = off, every "
+               "launch and every output as without the flag")
+        a("--ctc-beam-cand", type=int, default=None, help="with --ctc-beam: tokens a prefix is extended by per frame (default beam + 1, at most 32)")
+        a("--ctc-lm", default=None, metavar="FILE",
+          help="with --ctc-beam: an ARPA n-gram model (.arpa / .arpa.gz) over source_unigram, fused into the search")
+        a("--ctc-lm-weight", type=float, default=0.5, help="with --ctc-lm: the weight of the model's log-probability (default 0.5)")
+        a("--ctc-word-score", type=float, default=0.0, help="with --ctc-lm: added per token of a hypothesis (default 0)")
         a("--mt-alignment", action="store_true", default=False,
           help="after every policy() that wrote, agent.alignment holds the words of all committed target tokens (the text decoder's, "
                "which the S2TT agent prints and the S2ST path speaks) with the source time span the decoder's cross-attention "

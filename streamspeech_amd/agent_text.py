@@ -10,7 +10,7 @@ from .agent import StreamSpeechS2STAgent, _beam_kwargs, _greedy_mt, _detok, mt_a
 from .frontend import OnlineFeatureExtractor  # noqa: F401  (re-exported for parity with the reference files)
 from .generators import CTCDecoder, SequenceGenerator
 from .simuleval_shim import ReadAction, SpeechToTextAgent, WriteAction, entrypoint
-from .text_policy import s2tt_gate
+from .text_policy import asr_beam_emit, ctc_beam_flags, s2tt_gate
 
 
 def _add_text_args(parser):
@@ -75,6 +75,9 @@ class _TextAgentBase(SpeechToTextAgent):
         enc = getattr(getattr(self, "model", None), "encoder", None)
         if enc is not None and hasattr(enc, "reset_stream"):
             enc.reset_stream()                     # incremental encoder cache: one utterance at a time
+        if getattr(self, "ctc_stream", None) is not None:
+            self.ctc_stream.reset(0)               # --ctc-beam: the search of the utterance before
+            self._ctc_frames = 0
         fe = getattr(self, "feature_extractor", None)
         if fe is not None:
             fe.clear_cache()                       # converted sample history of the previous utterance
@@ -89,18 +92,57 @@ class _TextAgentBase(SpeechToTextAgent):
 
 @entrypoint
 class StreamSpeechASRAgent(_TextAgentBase):
-    """Streaming ASR: encoder + source_unigram CTC greedy, emits the newly confirmed subwords."""
+    """Streaming ASR: encoder + source_unigram CTC greedy, emits the newly confirmed subwords.  With --ctc-beam K the arg-max path
+    gives way to the resumable CTC prefix beam search (engine.CtcStream, one slot): each call moves the search over the rows the
+    incremental encoder has made final and writes the new text of the stable prefix; the last call takes all rows and writes the
+    rest of the best hypothesis, so the writes of an utterance add up to its final best hypothesis and none is ever retracted.
+    An utterance may run to lib.CTC_BEAM_MAX_FRAMES encoder rows (60 s)."""
+
+    ctc_stream = None
+    nbest = None        # --ctc-beam: the engine.CtcHypothesis list of the last finished utterance, best first
+    partial = None      # --ctc-beam: the symbols of the current best hypothesis, unstable tail included (for display)
 
     def __init__(self, args, model=None):
         if getattr(args, "mt_alignment", False):
             raise ValueError("--mt-alignment needs the first-pass text search; the ASR agent has none")
+        opts = ctc_beam_flags(args, "asr")                 # before anything is loaded: the refusals need no GPU
         super().__init__(args, model)
+        if opts is not None:
+            from .engine import CtcStream
+            from .lib import CTC_BEAM_MAX_FRAMES
+            if getattr(args, "ctc_lm", None):
+                from .ngram import NgramLM, read_arpa
+                opts.lm = NgramLM(read_arpa(args.ctc_lm, self.dict["source_unigram"]))
+            self._ctc_frames = 0
+            self.ctc_stream = CtcStream(self.engine, 0, 1, CTC_BEAM_MAX_FRAMES, **opts.stream_kwargs())
+
+    def _beam_policy(self, enc):
+        rows = enc["encoder_out"][0][:, 0, :].contiguous()
+        T2, fin = int(rows.shape[0]), bool(self.states.source_finished)
+        # rows below the incremental encoder's n_final never change; without the incremental encoder nothing is final before the end
+        n_final = int(self.engine.stream_stats[0]) if getattr(self.model.encoder, "incremental", False) else 0
+        upto = T2 if fin else max(self._ctc_frames, min(n_final, T2))
+        part = self.ctc_stream.advance([0], rows, [T2], [upto], [fin])[0]
+        self._ctc_frames = 0 if fin else upto
+        symbols = [self.dict["source_unigram"][c] for c in part.hyps[0].tokens] if part.hyps else []
+        self.partial = symbols
+        new_text, self.asr_text = asr_beam_emit(self.asr_text, symbols, part.n_stable, fin)
+        if fin:
+            self.nbest = part.hyps
+            if not self.quiet:
+                with open(self.asr_file, "a") as f:
+                    print(_detok(symbols), file=f)
+            self.states.target_finished = True
+            self.reset()
+        return WriteAction(new_text, finished=self.states.target_finished)
 
     @torch.inference_mode()
     def policy(self):
         enc, _, _ = self._encode()
         if enc is None:
             return WriteAction("", finished=True) if self.states.source_finished else ReadAction()
+        if self.ctc_stream is not None:
+            return self._beam_policy(enc)
         scored = self._ctc_hyps(enc)
         hyp = scored[0] if scored else self.asr_ctc_generator.generate(enc, aux_task_name="source_unigram")[0][0]
         tokens = [self.dict["source_unigram"][c] for c in hyp["tokens"].int()]
@@ -119,6 +161,10 @@ class StreamSpeechASRAgent(_TextAgentBase):
 @entrypoint
 class StreamSpeechS2TTAgent(_TextAgentBase):
     """Simultaneous speech-to-text translation: encoder + both CTC heads (read/write gate) + MT greedy."""
+
+    def __init__(self, args, model=None):
+        ctc_beam_flags(args, "S2TT")                       # (raises: the flags are the ASR agent's)
+        super().__init__(args, model)
 
     @torch.inference_mode()
     def policy(self):

@@ -7,7 +7,9 @@
 //                           of label strings and its child table in global scratch, the back-trace of the n-best at the end
 // plus the plain-C++ twin of both (ss_ctc_beam_host) over the same step code (ctc_beam.hpp, where the search and its order are
 // defined).  The search kernel and the twin each have an LM form (ctc_beam_search_lm_kernel, ss_ctc_beam_lm_host): the same body
-// with a back-off n-gram model (ngram_lm.hpp) fused into the order of a frame's entries.
+// with a back-off n-gram model (ngram_lm.hpp) fused into the order of a frame's entries.  And each of the four has a RESUMABLE form
+// (ctc_stream_search_kernel / _lm_kernel, ctc_stream_host_run; the object and its entry points: ctc_stream.hip): the same body
+// over a slot's state that outlives the launch, for the frames a call brings, with the stable prefix of the beam at the end.
 #include "ctc_beam.hpp"
 
 #include <cstring>
@@ -140,11 +142,16 @@ struct CtcBeamLm {
   int* n_state;
 };
 
-template <bool LM>
+// The resumable form (RES = true; ctc_beam.hpp, ss_ctc_stream_advance) is the same body again: workgroup b serves session R.sess[b],
+// whose trie, table and stored beam are its slot's (R); the beam is loaded where the one-shot form makes the root (a call that
+// starts at frame 0 makes the root), the loop runs the absolute frames [f, upto) over the stacked new rows, the beam is stored
+// back, the n-best are written as the one-shot form writes them (the eos term only in the utterance's last call), and one pass
+// more finds the stable prefix.  segs / keys_all / vals_all / nodes_all are unused.  The one-shot forms compile to what they were.
+template <bool LM, bool RES>
 __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ logits, int ld, const CtcBeamSeg* __restrict__ segs,
                                                      int beam, int C, int nbest, const float* den, const int* cand_id,
                                                      unsigned long long* keys_all, int* vals_all, int2* nodes_all, void* hyps_out,
-                                                     int* tokens, int out_stride, const CtcBeamLm& L) {
+                                                     int* tokens, int out_stride, const CtcBeamLm& L, const CtcStreamDev& R) {
   constexpr int MB = CTC_BEAM_MAX_BEAM;
   __shared__ double b_pb[2 * MB], b_pnb[2 * MB], b_tot[2 * MB];
   __shared__ int b_node[2 * MB], b_last[2 * MB];
@@ -156,24 +163,47 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
   __shared__ int s_nb[2];
   __shared__ double e_fus[LM ? CTC_BEAM_MAX_ENT : 1], b_bonus[LM ? 2 * MB : 1];
   const int tid = threadIdx.x;
-  const CtcBeamSeg sg = segs[blockIdx.x];
-  unsigned long long* keys = keys_all + sg.tab_off;
-  int* vals = vals_all + sg.tab_off;
-  int2* nodes = nodes_all + sg.node_off;
-  double* n_sum = LM ? L.n_sum + sg.node_off : nullptr;
-  double* n_bonus = LM ? L.n_bonus + sg.node_off : nullptr;
-  int* n_state = LM ? L.n_state + sg.node_off : nullptr;
+  CtcBeamSeg sg;                                               // RES: the slot's offsets; row0 + t is the row of ABSOLUTE frame t
+  CtcStreamSess se{};
+  int t0 = 0;
+  if constexpr (RES) {
+    se = R.sess[blockIdx.x];
+    sg = CtcBeamSeg{se.slot * R.nodes_per, se.slot * R.slots_per, se.row0 - se.f, se.upto, (int)(R.slots_per - 1), 0};
+    t0 = se.f;
+  } else {
+    sg = segs[blockIdx.x];
+  }
+  unsigned long long* keys = (RES ? R.keys : keys_all) + sg.tab_off;
+  int* vals = (RES ? R.vals : vals_all) + sg.tab_off;
+  int2* nodes = (RES ? R.nodes : nodes_all) + sg.node_off;
+  double* n_sum = LM ? (RES ? R.n_sum : L.n_sum) + sg.node_off : nullptr;
+  double* n_bonus = LM ? (RES ? R.n_bonus : L.n_bonus) + sg.node_off : nullptr;
+  int* n_state = LM ? (RES ? R.n_state : L.n_state) + sg.node_off : nullptr;
   const int mask = sg.tab_mask, W = C + 1;
-  if (tid == 0) {
-    b_pb[0] = 0.0; b_pnb[0] = -INFINITY; b_tot[0] = 0.0; b_node[0] = 0; b_last[0] = -1;
-    s_nb[0] = 1;
-    nodes[0] = make_int2(-1, -1);
-    if constexpr (LM) { b_bonus[0] = 0.0; n_sum[0] = 0.0; n_bonus[0] = 0.0; n_state[0] = L.lm.start; }
+  double* st_f64 = RES ? R.b_f64 + (size_t)se.slot * 4 * beam : nullptr;   // the stored beam of the slot
+  int* st_i32 = RES ? R.b_i32 + (size_t)se.slot * (2 * beam + 2) : nullptr;
+  bool bad = false;
+  if (!RES || t0 == 0) {
+    if (tid == 0) {
+      b_pb[0] = 0.0; b_pnb[0] = -INFINITY; b_tot[0] = 0.0; b_node[0] = 0; b_last[0] = -1;
+      s_nb[0] = 1;
+      nodes[0] = make_int2(-1, -1);
+      if constexpr (LM) { b_bonus[0] = 0.0; n_sum[0] = 0.0; n_bonus[0] = 0.0; n_state[0] = L.lm.start; }
+    }
+  } else if constexpr (RES) {
+    const int nb = st_i32[2 * beam];                           // (uniform; at most beam)
+    bad = st_i32[2 * beam + 1] != 0;                           // a NaN row of an earlier call: sticky, no frame runs
+    if (bad) t0 = sg.T;
+    if (tid < nb) {
+      b_pb[tid] = st_f64[tid]; b_pnb[tid] = st_f64[beam + tid]; b_tot[tid] = st_f64[2 * beam + tid];
+      if constexpr (LM) b_bonus[tid] = st_f64[3 * beam + tid];
+      b_node[tid] = st_i32[tid]; b_last[tid] = st_i32[beam + tid];
+    }
+    if (tid == 0) s_nb[0] = nb;
   }
   __syncthreads();
   int cur = 0;
-  bool bad = false;
-  for (int t = 0; t < sg.T; ++t) {
+  for (int t = t0; t < sg.T; ++t) {
     const int row = sg.row0 + t, co = cur * MB, no = (cur ^ 1) * MB;
     const int nb = s_nb[cur];
     const float mx = den[2 * (size_t)row], ls = den[2 * (size_t)row + 1];
@@ -301,6 +331,15 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
     __syncthreads();
     cur ^= 1;
   }
+  if constexpr (RES) {                                         // the beam that left frame upto - 1, for the next call
+    const int nb = bad ? 0 : s_nb[cur];
+    if (tid < nb) {
+      st_f64[tid] = b_pb[cur * MB + tid]; st_f64[beam + tid] = b_pnb[cur * MB + tid]; st_f64[2 * beam + tid] = b_tot[cur * MB + tid];
+      if constexpr (LM) st_f64[3 * beam + tid] = b_bonus[cur * MB + tid];
+      st_i32[tid] = b_node[cur * MB + tid]; st_i32[beam + tid] = b_last[cur * MB + tid];
+    }
+    if (tid == 0) { st_i32[2 * beam] = nb; st_i32[2 * beam + 1] = bad ? 1 : 0; }
+  }
   if constexpr (!LM) {
     // ---- the n-best: the last beam in rank order; thread r walks prefix r back through the trie ----
     ss_ctc_beam_hyp* hyps = static_cast<ss_ctc_beam_hyp*>(hyps_out);
@@ -332,7 +371,7 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
       const double fused = b_tot[cur * MB + tid] + b_bonus[cur * MB + tid];
       lm_sum = n_sum[node];
       fin = fused;
-      if (L.eos_term) {
+      if (L.eos_term && (!RES || se.fin)) {
         int nx;
         const double lp = ngram_lp(L.lm, n_state[node], L.lm.eos, &nx);
         fin = ngram_finish(fused, L.lm_weight, lp);
@@ -362,14 +401,34 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
       hyps[(size_t)blockIdx.x * nbest + tid] = h;
     }
   }
+  if constexpr (RES) {
+    // ---- the stable prefix: what every string of the beam starts with.  Thread r finds the depth of the lowest common ancestor
+    //      of prefix r and prefix 0 by walking parents (at most `frames` steps each, as the n-best walk); the block minimum ----
+    __shared__ int s_stable;
+    const int nb = bad ? 0 : s_nb[cur];
+    if (tid == 0) s_stable = NONE;
+    __syncthreads();
+    if (tid < nb) {
+      int a = b_node[cur * MB + tid], b = b_node[cur * MB];
+      int da = 0, db = 0;
+      for (int n = a; n > 0; n = nodes[n].x) ++da;
+      for (int n = b; n > 0; n = nodes[n].x) ++db;
+      for (; da > db; --da) a = nodes[a].x;
+      for (; db > da; --db) b = nodes[b].x;
+      for (; a != b; --da) { a = nodes[a].x; b = nodes[b].x; }
+      atomicMin(&s_stable, da);
+    }
+    __syncthreads();
+    if (tid == 0) R.part[blockIdx.x] = CtcStreamPart{se.upto, nb > 0 ? s_stable : 0, nb, bad ? 2 : 0};
+  }
 }
 
 __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __restrict__ logits, int ld, const CtcBeamSeg* __restrict__ segs,
                                                               int beam, int C, int nbest, const float* den, const int* cand_id,
                                                               unsigned long long* keys_all, int* vals_all, int2* nodes_all,
                                                               ss_ctc_beam_hyp* hyps, int* tokens, int out_stride) {
-  ctc_beam_search_body<false>(logits, ld, segs, beam, C, nbest, den, cand_id, keys_all, vals_all, nodes_all, hyps, tokens, out_stride,
-                              CtcBeamLm{});
+  ctc_beam_search_body<false, false>(logits, ld, segs, beam, C, nbest, den, cand_id, keys_all, vals_all, nodes_all, hyps, tokens,
+                                     out_stride, CtcBeamLm{}, CtcStreamDev{});
 }
 
 __global__ __launch_bounds__(256) void ctc_beam_search_lm_kernel(const float* __restrict__ logits, int ld,
@@ -377,7 +436,23 @@ __global__ __launch_bounds__(256) void ctc_beam_search_lm_kernel(const float* __
                                                                  const float* den, const int* cand_id, unsigned long long* keys_all,
                                                                  int* vals_all, int2* nodes_all, ss_ctc_beam_lm_hyp* hyps, int* tokens,
                                                                  int out_stride, CtcBeamLm L) {
-  ctc_beam_search_body<true>(logits, ld, segs, beam, C, nbest, den, cand_id, keys_all, vals_all, nodes_all, hyps, tokens, out_stride, L);
+  ctc_beam_search_body<true, false>(logits, ld, segs, beam, C, nbest, den, cand_id, keys_all, vals_all, nodes_all, hyps, tokens,
+                                    out_stride, L, CtcStreamDev{});
+}
+
+// The resumable kernels: one workgroup per session of the call (R.sess), logits the stacked new rows.
+__global__ __launch_bounds__(256) void ctc_stream_search_kernel(const float* __restrict__ logits, int ld, int beam, int C, int nbest,
+                                                                const float* den, const int* cand_id, ss_ctc_beam_hyp* hyps,
+                                                                int* tokens, int out_stride, CtcStreamDev R) {
+  ctc_beam_search_body<false, true>(logits, ld, nullptr, beam, C, nbest, den, cand_id, nullptr, nullptr, nullptr, hyps, tokens,
+                                    out_stride, CtcBeamLm{}, R);
+}
+
+__global__ __launch_bounds__(256) void ctc_stream_search_lm_kernel(const float* __restrict__ logits, int ld, int beam, int C, int nbest,
+                                                                   const float* den, const int* cand_id, ss_ctc_beam_lm_hyp* hyps,
+                                                                   int* tokens, int out_stride, CtcBeamLm L, CtcStreamDev R) {
+  ctc_beam_search_body<true, true>(logits, ld, nullptr, beam, C, nbest, den, cand_id, nullptr, nullptr, nullptr, hyps, tokens,
+                                   out_stride, L, R);
 }
 
 size_t ctc_beam_table_bytes(const CtcBeamPlan& p) { return p.segs.size() * sizeof(CtcBeamSeg); }
@@ -386,6 +461,20 @@ size_t ctc_beam_table_bytes(const CtcBeamPlan& p) { return p.segs.size() * sizeo
 int ctc_beam_lm_check(const ss_ngram_lm* lm, int V, const ss_ctc_lm_opts* o) {
   if (!lm || !o || lm->host.V != V || !std::isfinite(o->lm_weight) || !std::isfinite(o->word_score)) return SS_ERR_ARG;
   if (o->eos_term && lm->host.eos < 0) return SS_ERR_ARG;
+  return SS_OK;
+}
+
+static int launch_ctc_beam_cand(const float* logits, int ld, int V, int pad, int unk, int rows, int C, float* den, int* cand,
+                                hipStream_t stream) {
+#define SS_CBC(PER) \
+  hipLaunchKernelGGL(ctc_beam_cand_kernel<PER>, dim3(rows), dim3(256), 0, stream, logits, ld, V, pad, unk, C, den, cand)
+  if (V <= 2048) SS_CBC(8);
+  else if (V <= 4096) SS_CBC(16);
+  else if (V <= 6144) SS_CBC(24);
+  else if (V <= 8192) SS_CBC(32);
+  else SS_CBC(0);
+#undef SS_CBC
+  SS_LAUNCH_CHECK();
   return SS_OK;
 }
 
@@ -411,15 +500,7 @@ static int launch_ctc_beam_any(const float* logits, int ld, int V, int pad, int 
   if (cand_out) cand = cand_out;
   SS_HIP_CHECK(hipMemcpyAsync(d_table, p.segs.data(), ctc_beam_table_bytes(p), hipMemcpyHostToDevice, stream));
   SS_HIP_CHECK(hipMemsetAsync(keys, 0xff, p.key_bytes(), stream));
-#define SS_CBC(PER)                                                                                                              \
-  hipLaunchKernelGGL(ctc_beam_cand_kernel<PER>, dim3(p.rows), dim3(256), 0, stream, logits, ld, V, pad, unk, p.cand, den, cand)
-  if (V <= 2048) SS_CBC(8);
-  else if (V <= 4096) SS_CBC(16);
-  else if (V <= 6144) SS_CBC(24);
-  else if (V <= 8192) SS_CBC(32);
-  else SS_CBC(0);
-#undef SS_CBC
-  SS_LAUNCH_CHECK();
+  RET(launch_ctc_beam_cand(logits, ld, V, pad, unk, p.rows, p.cand, den, cand, stream));
   if (!lm) {
     hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(B), dim3(256), 0, stream, logits, ld, static_cast<const CtcBeamSeg*>(d_table),
                        p.beam, p.cand, p.nbest, den, cand, keys, vals, nodes, static_cast<ss_ctc_beam_hyp*>(hyps), tokens, out_stride);
@@ -447,6 +528,27 @@ int launch_ctc_beam_lm(const float* logits, int ld, int V, int pad, int unk, con
                        float* den_out, int* cand_out, hipStream_t stream) {
   if (!lm) return SS_ERR_ARG;
   return launch_ctc_beam_any(logits, ld, V, pad, unk, p, d_table, d_work, lm, opts, hyps, tokens, out_stride, den_out, cand_out, stream);
+}
+
+int launch_ctc_stream(const float* logits, int ld, int V, int pad, int unk, int rows, int n, const CtcStreamSess* h_sess, void* d_sess,
+                      float* den, int* cand_id, int beam, int C, int nbest, CtcStreamDev dev, const ss_ngram_lm* lm,
+                      const ss_ctc_lm_opts* opts, void* hyps, int* tokens, int out_stride, CtcStreamPart* part, hipStream_t stream) {
+  CtcBeamLm L{};
+  if (lm) RET(ngram_device_view(lm, &L.lm));
+  SS_HIP_CHECK(hipMemcpyAsync(d_sess, h_sess, (size_t)n * sizeof(CtcStreamSess), hipMemcpyHostToDevice, stream));
+  if (rows > 0) RET(launch_ctc_beam_cand(logits, ld, V, pad, unk, rows, C, den, cand_id, stream));
+  dev.sess = static_cast<const CtcStreamSess*>(d_sess);
+  dev.part = part;
+  if (!lm) {
+    hipLaunchKernelGGL(ctc_stream_search_kernel, dim3(n), dim3(256), 0, stream, logits, ld, beam, C, nbest, den, cand_id,
+                       static_cast<ss_ctc_beam_hyp*>(hyps), tokens, out_stride, dev);
+  } else {
+    L.lm_weight = opts->lm_weight; L.word_score = opts->word_score; L.eos_term = opts->eos_term ? 1 : 0;
+    hipLaunchKernelGGL(ctc_stream_search_lm_kernel, dim3(n), dim3(256), 0, stream, logits, ld, beam, C, nbest, den, cand_id,
+                       static_cast<ss_ctc_beam_lm_hyp*>(hyps), tokens, out_stride, L, dev);
+  }
+  SS_LAUNCH_CHECK();
+  return SS_OK;
 }
 
 namespace {
@@ -501,7 +603,196 @@ extern "C" int ss_debug_ctc_beam_host_max(int max_beam) {
   return was;
 }
 
-// The twin of both forms: LM = false is ss_ctc_beam_host (lm / o unused, records ss_ctc_beam_hyp), LM = true ss_ctc_beam_lm_host.
+// ---- the twin of both forms, in three steps over one utterance's state (CtcBeamHostState, ctc_beam.hpp) so that the one-shot twins
+// (start, all frames, emit) and the resumable twin (ss_ctc_stream_advance_host: start at a reset, some frames and an emit per
+// call) are one statement of the search.  LM = false: lv / lw / ws unused, records ss_ctc_beam_hyp. ----
+namespace ss {
+
+void CtcBeamHostState::start(int beam, int max_T, bool lm, int lm_start) {
+  long long slots = ctc_stream_slots(beam, max_T);
+  mask = (int)(slots - 1);
+  const size_t nodes = 1 + (size_t)beam * max_T;
+  keys.assign((size_t)slots, CTC_BEAM_EMPTY);
+  vals.assign((size_t)slots, -1);
+  par.assign(nodes, -1); tok.assign(nodes, -1);
+  if (lm) { n_sum.assign(nodes, 0.0); n_bonus.assign(nodes, 0.0); n_state.assign(nodes, 0); n_state[0] = lm_start; }
+  bm.assign(1, CtcBeamHostPre{0.0, -INFINITY, 0.0, 0, -1, 0.0});
+  frames = 0; bad = false;
+}
+
+// The frames S.frames .. S.frames + n - 1 from the n rows at `rows`; h_den [n][2] / h_cand [n][C] (may be NULL) receive the
+// candidate kernel's values of every one of them, whatever the search makes of it.
+template <bool LM>
+static void ctc_beam_host_frames(CtcBeamHostState& S, const float* rows, int ld, int V, int pad, int unk, int n, int beam, int C,
+                                 const NgramView& lv, double lw, double ws, float* h_den, int32_t* h_cand_id) {
+  const int W = C + 1, mask = S.mask;
+  std::vector<unsigned long long>& keys = S.keys;
+  std::vector<int>&vals = S.vals, &par = S.par, &tok = S.tok, &n_state = S.n_state;
+  std::vector<double>&n_sum = S.n_sum, &n_bonus = S.n_bonus;
+  std::vector<CtcBeamHostPre>& bm = S.bm;
+  typedef CtcBeamHostPre Pre;
+  std::vector<Pre> nx;
+  std::vector<double> e_tot, s_pb, s_pnb, s_give, e_fus;
+  std::vector<int> e_node, cid_all((size_t)n * C);
+  std::vector<float> den_all(2 * (size_t)n);
+  for (int i = 0; i < n; ++i) {                                // the candidate kernel: every row, whatever the search makes of it
+    const float* r = rows + (size_t)i * ld;
+    row_den_host(r, V, &den_all[2 * (size_t)i]);
+    row_cand_host(r, V, pad, unk, C, &cid_all[(size_t)i * C]);
+  }
+  if (h_den && n > 0) memcpy(h_den, den_all.data(), den_all.size() * sizeof(float));
+  if (h_cand_id && n > 0) memcpy(h_cand_id, cid_all.data(), cid_all.size() * sizeof(int));
+  const int f0 = S.frames;
+  S.frames += n;
+  for (int t = f0; t < f0 + n && !S.bad; ++t) {
+    const float* r = rows + (size_t)(t - f0) * ld;
+    const float* den = &den_all[2 * (size_t)(t - f0)];
+    const int* cid = &cid_all[(size_t)(t - f0) * C];
+    if (den[1] != den[1]) { S.bad = true; break; }
+    const int nb = (int)bm.size(), n_ent = nb * W;
+    const float lp0 = ctc_beam_lp(r[0], den[0], den[1]);
+    e_tot.assign(n_ent, -INFINITY); e_node.assign(n_ent, -1);
+    if constexpr (LM) e_fus.assign(n_ent, -INFINITY);
+    s_pb.assign(nb, -INFINITY); s_pnb.assign(nb, -INFINITY); s_give.assign(nb, -INFINITY);
+    for (int e = 0; e < n_ent; ++e) {                          // B
+      const int i = e / W, k = e - i * W - 1;
+      const Pre& q = bm[i];
+      if (k < 0) {
+        ctc_beam_stay(q.pnb, q.tot, q.last, lp0, q.last >= 0 ? ctc_beam_lp(r[q.last], den[0], den[1]) : -INFINITY, &s_pb[i], &s_pnb[i]);
+        e_node[e] = q.node;
+        continue;
+      }
+      const int c = cid[k];
+      if (c < 0) continue;
+      double term = ctc_beam_ext(q.pb, q.tot, q.last, c, ctc_beam_lp(r[c], den[0], den[1]));
+      const int child = ctc_beam_find(keys.data(), vals.data(), mask, q.node, c);
+      if (child >= 0) {
+        for (int j = 0; j < nb; ++j) {
+          if (bm[j].node == child) { s_give[j] = term; term = -INFINITY; break; }
+        }
+      }
+      e_tot[e] = term; e_node[e] = child;
+      if constexpr (LM) {
+        if (term > -INFINITY) {
+          int st;
+          const double bonus = child >= 0 ? n_bonus[child] : ngram_bonus(q.bonus, lw, ngram_lp(lv, n_state[q.node], c, &st), ws);
+          e_fus[e] = term + bonus;
+        }
+      }
+    }
+    for (int i = 0; i < nb; ++i) {                             // C
+      s_pnb[i] = ctc_beam_logadd(s_pnb[i], s_give[i]);
+      e_tot[i * W] = ctc_beam_logadd(s_pb[i], s_pnb[i]);
+      if constexpr (LM) e_fus[i * W] = e_tot[i * W] > -INFINITY ? e_tot[i * W] + bm[i].bonus : -INFINITY;
+    }
+    const std::vector<double>& e_key = LM ? e_fus : e_tot;     // what the order compares
+    nx.assign(beam, Pre{0, 0, 0, -1, -1, 0.0});                // D
+    int alive = 0;
+    for (int e = 0; e < n_ent; ++e) {
+      const double tot = e_tot[e], key = e_key[e];
+      if (!(key > -INFINITY)) continue;
+      int rank = 0;
+      for (int f = 0; f < n_ent && rank < beam; ++f) rank += ctc_beam_before(e_key[f], f, key, e);
+      if (rank >= beam) continue;
+      const int i = e / W, k = e - i * W - 1;
+      int node = e_node[e];
+      if (k < 0) {
+        nx[rank] = Pre{s_pb[i], s_pnb[i], tot, node, bm[i].last, bm[i].bonus};
+      } else {
+        const int c = cid[k];
+        if (node < 0) {
+          node = ctc_beam_new_node(t, beam, rank);
+          par[node] = bm[i].node; tok[node] = c;
+          if constexpr (LM) {
+            int st;
+            const double lp = ngram_lp(lv, n_state[bm[i].node], c, &st);
+            n_state[node] = st; n_sum[node] = n_sum[bm[i].node] + lp; n_bonus[node] = ngram_bonus(bm[i].bonus, lw, lp, ws);
+          }
+          const unsigned long long key = ctc_beam_key(bm[i].node, c);
+          for (int s = ctc_beam_slot(key, mask), n = 0; n <= mask; ++n, s = (s + 1) & mask) {
+            if (keys[s] == CTC_BEAM_EMPTY) { keys[s] = key; vals[s] = node; break; }
+          }
+        }
+        nx[rank] = Pre{-INFINITY, tot, tot, node, c, LM ? n_bonus[node] : 0.0};
+      }
+      if (rank + 1 > alive) alive = rank + 1;
+    }
+    nx.resize(alive);
+    bm.swap(nx);
+  }
+}
+
+// The n-best of the beam as it stands: h_hyps_b [nbest] records and h_tokens_b [nbest][out_stride] of this utterance.  eos: the LM
+// form's eos term.
+template <bool LM>
+static void ctc_beam_host_emit(const CtcBeamHostState& S, int nbest, bool eos, const NgramView& lv, double lw, void* h_hyps_b,
+                               int32_t* h_tokens_b, int out_stride) {
+  const std::vector<CtcBeamHostPre>& bm = S.bm;
+  const std::vector<int>&par = S.par, &tok = S.tok;
+  const bool bad = S.bad;
+  if constexpr (!LM) {
+    ss_ctc_beam_hyp* h_hyps = static_cast<ss_ctc_beam_hyp*>(h_hyps_b);
+    for (int k = 0; k < nbest; ++k) {
+      ss_ctc_beam_hyp& h = h_hyps[k];
+      h.score = bad ? (double)__builtin_nanf("") : -INFINITY; h.n_tokens = 0; h.status = bad ? 2 : 1;
+      if (bad || k >= (int)bm.size()) continue;
+      int len = 0;
+      for (int n = bm[k].node; n > 0; n = par[n]) ++len;
+      int32_t* out = h_tokens_b + (size_t)k * out_stride;
+      int j = len;
+      for (int n = bm[k].node; n > 0; n = par[n]) out[--j] = tok[n];
+      h.score = bm[k].tot; h.n_tokens = len; h.status = 0;
+    }
+  } else {
+    ss_ctc_beam_lm_hyp* h_hyps = static_cast<ss_ctc_beam_lm_hyp*>(h_hyps_b);
+    const int nb = bad ? 0 : (int)bm.size();
+    std::vector<double> fin(nb), lms(nb);
+    for (int r = 0; r < nb; ++r) {
+      const double fused = bm[r].tot + bm[r].bonus;
+      fin[r] = fused; lms[r] = S.n_sum[bm[r].node];
+      if (eos) {
+        int st;
+        const double lp = ngram_lp(lv, S.n_state[bm[r].node], lv.eos, &st);
+        fin[r] = ngram_finish(fused, lw, lp); lms[r] += lp;
+      }
+    }
+    for (int k = nb; k < nbest; ++k) {
+      ss_ctc_beam_lm_hyp& h = h_hyps[k];
+      h.score = h.ctc_score = bad ? (double)__builtin_nanf("") : -INFINITY; h.lm_score = 0.0; h.n_tokens = 0; h.status = bad ? 2 : 1;
+    }
+    for (int r = 0; r < nb; ++r) {
+      int rank = 0;
+      for (int f = 0; f < nb; ++f) rank += ctc_beam_before(fin[f], f, fin[r], r);
+      if (rank >= nbest) continue;
+      ss_ctc_beam_lm_hyp& h = h_hyps[rank];
+      int len = 0;
+      for (int n = bm[r].node; n > 0; n = par[n]) ++len;
+      int32_t* out = h_tokens_b + (size_t)rank * out_stride;
+      int j = len;
+      for (int n = bm[r].node; n > 0; n = par[n]) out[--j] = tok[n];
+      h.score = fin[r]; h.ctc_score = bm[r].tot; h.lm_score = lms[r]; h.n_tokens = len; h.status = 0;
+    }
+  }
+}
+
+// The stable-prefix pass of the resumable kernel: the smallest depth of the lowest common ancestor of a beam prefix and prefix 0.
+static CtcStreamPart ctc_beam_host_part(const CtcBeamHostState& S) {
+  const int nb = S.bad ? 0 : (int)S.bm.size();
+  int stable = nb > 0 ? NONE : 0;
+  for (int r = 0; r < nb; ++r) {
+    int a = S.bm[r].node, b = S.bm[0].node, da = 0, db = 0;
+    for (int n = a; n > 0; n = S.par[n]) ++da;
+    for (int n = b; n > 0; n = S.par[n]) ++db;
+    for (; da > db; --da) a = S.par[a];
+    for (; db > da; --db) b = S.par[b];
+    for (; a != b; --da) { a = S.par[a]; b = S.par[b]; }
+    if (da < stable) stable = da;
+  }
+  return CtcStreamPart{S.frames, stable, nb, S.bad ? 2 : 0};
+}
+
+}  // namespace ss
+
 template <bool LM>
 static int ctc_beam_host_any(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
                              int nbest, const ss_ngram_lm* lm, const ss_ctc_lm_opts* o, void* h_hyps_out, int32_t* h_tokens,
@@ -516,152 +807,47 @@ static int ctc_beam_host_any(const float* h_logits, int ld, int V, int pad, int 
     RET(ctc_beam_lm_check(lm, V, o));
     lv = lm->host.view(); lw = o->lm_weight; ws = o->word_score;
   }
-  const int C = cand, W = C + 1;
-  struct Pre { double pb, pnb, tot; int node, last; double bonus; };
+  const size_t rec = LM ? sizeof(ss_ctc_beam_lm_hyp) : sizeof(ss_ctc_beam_hyp);
+  CtcBeamHostState S;
   for (int b = 0; b < B; ++b) {
     const CtcBeamSeg& sg = p.segs[b];
-    const int mask = sg.tab_mask;
-    std::vector<unsigned long long> keys((size_t)mask + 1, CTC_BEAM_EMPTY);
-    std::vector<int> vals((size_t)mask + 1, -1), par(1 + (size_t)beam * sg.T, -1), tok(1 + (size_t)beam * sg.T, -1);
-    std::vector<Pre> bm(1, Pre{0.0, -INFINITY, 0.0, 0, -1, 0.0}), nx;
-    std::vector<double> e_tot, s_pb, s_pnb, s_give, e_fus, n_sum, n_bonus;
-    std::vector<int> n_state;
-    if constexpr (LM) {
-      n_sum.assign(par.size(), 0.0); n_bonus.assign(par.size(), 0.0); n_state.assign(par.size(), 0);
-      n_state[0] = lv.start;
-    }
-    std::vector<int> e_node, cid_all((size_t)sg.T * C);
-    std::vector<float> den_all(2 * (size_t)sg.T);
-    for (int t = 0; t < sg.T; ++t) {                           // the candidate kernel: every row, whatever the search makes of it
-      const float* r = h_logits + (size_t)(sg.row0 + t) * ld;
-      row_den_host(r, V, &den_all[2 * (size_t)t]);
-      row_cand_host(r, V, pad, unk, C, &cid_all[(size_t)t * C]);
-    }
-    if (h_den) memcpy(h_den + 2 * (size_t)sg.row0, den_all.data(), den_all.size() * sizeof(float));
-    if (h_cand_id) memcpy(h_cand_id + (size_t)sg.row0 * C, cid_all.data(), cid_all.size() * sizeof(int));
-    bool bad = false;
-    for (int t = 0; t < sg.T; ++t) {
-      const float* r = h_logits + (size_t)(sg.row0 + t) * ld;
-      const float* den = &den_all[2 * (size_t)t];
-      const int* cid = &cid_all[(size_t)t * C];
-      if (den[1] != den[1]) { bad = true; break; }
-      const int nb = (int)bm.size(), n_ent = nb * W;
-      const float lp0 = ctc_beam_lp(r[0], den[0], den[1]);
-      e_tot.assign(n_ent, -INFINITY); e_node.assign(n_ent, -1);
-      if constexpr (LM) e_fus.assign(n_ent, -INFINITY);
-      s_pb.assign(nb, -INFINITY); s_pnb.assign(nb, -INFINITY); s_give.assign(nb, -INFINITY);
-      for (int e = 0; e < n_ent; ++e) {                        // B
-        const int i = e / W, k = e - i * W - 1;
-        const Pre& q = bm[i];
-        if (k < 0) {
-          ctc_beam_stay(q.pnb, q.tot, q.last, lp0, q.last >= 0 ? ctc_beam_lp(r[q.last], den[0], den[1]) : -INFINITY, &s_pb[i], &s_pnb[i]);
-          e_node[e] = q.node;
-          continue;
-        }
-        const int c = cid[k];
-        if (c < 0) continue;
-        double term = ctc_beam_ext(q.pb, q.tot, q.last, c, ctc_beam_lp(r[c], den[0], den[1]));
-        const int child = ctc_beam_find(keys.data(), vals.data(), mask, q.node, c);
-        if (child >= 0) {
-          for (int j = 0; j < nb; ++j) {
-            if (bm[j].node == child) { s_give[j] = term; term = -INFINITY; break; }
-          }
-        }
-        e_tot[e] = term; e_node[e] = child;
-        if constexpr (LM) {
-          if (term > -INFINITY) {
-            int st;
-            const double bonus = child >= 0 ? n_bonus[child] : ngram_bonus(q.bonus, lw, ngram_lp(lv, n_state[q.node], c, &st), ws);
-            e_fus[e] = term + bonus;
-          }
-        }
-      }
-      for (int i = 0; i < nb; ++i) {                           // C
-        s_pnb[i] = ctc_beam_logadd(s_pnb[i], s_give[i]);
-        e_tot[i * W] = ctc_beam_logadd(s_pb[i], s_pnb[i]);
-        if constexpr (LM) e_fus[i * W] = e_tot[i * W] > -INFINITY ? e_tot[i * W] + bm[i].bonus : -INFINITY;
-      }
-      const std::vector<double>& e_key = LM ? e_fus : e_tot;   // what the order compares
-      nx.assign(beam, Pre{0, 0, 0, -1, -1, 0.0});              // D
-      int alive = 0;
-      for (int e = 0; e < n_ent; ++e) {
-        const double tot = e_tot[e], key = e_key[e];
-        if (!(key > -INFINITY)) continue;
-        int rank = 0;
-        for (int f = 0; f < n_ent && rank < beam; ++f) rank += ctc_beam_before(e_key[f], f, key, e);
-        if (rank >= beam) continue;
-        const int i = e / W, k = e - i * W - 1;
-        int node = e_node[e];
-        if (k < 0) {
-          nx[rank] = Pre{s_pb[i], s_pnb[i], tot, node, bm[i].last, bm[i].bonus};
-        } else {
-          const int c = cid[k];
-          if (node < 0) {
-            node = ctc_beam_new_node(t, beam, rank);
-            par[node] = bm[i].node; tok[node] = c;
-            if constexpr (LM) {
-              int st;
-              const double lp = ngram_lp(lv, n_state[bm[i].node], c, &st);
-              n_state[node] = st; n_sum[node] = n_sum[bm[i].node] + lp; n_bonus[node] = ngram_bonus(bm[i].bonus, lw, lp, ws);
-            }
-            const unsigned long long key = ctc_beam_key(bm[i].node, c);
-            for (int s = ctc_beam_slot(key, mask), n = 0; n <= mask; ++n, s = (s + 1) & mask) {
-              if (keys[s] == CTC_BEAM_EMPTY) { keys[s] = key; vals[s] = node; break; }
-            }
-          }
-          nx[rank] = Pre{-INFINITY, tot, tot, node, c, LM ? n_bonus[node] : 0.0};
-        }
-        if (rank + 1 > alive) alive = rank + 1;
-      }
-      nx.resize(alive);
-      bm.swap(nx);
-    }
-    if constexpr (!LM) {
-      ss_ctc_beam_hyp* h_hyps = static_cast<ss_ctc_beam_hyp*>(h_hyps_out);
-      for (int k = 0; k < nbest; ++k) {
-        ss_ctc_beam_hyp& h = h_hyps[(size_t)b * nbest + k];
-        h.score = bad ? (double)__builtin_nanf("") : -INFINITY; h.n_tokens = 0; h.status = bad ? 2 : 1;
-        if (bad || k >= (int)bm.size()) continue;
-        int len = 0;
-        for (int n = bm[k].node; n > 0; n = par[n]) ++len;
-        int32_t* out = h_tokens + ((size_t)b * nbest + k) * out_stride;
-        int j = len;
-        for (int n = bm[k].node; n > 0; n = par[n]) out[--j] = tok[n];
-        h.score = bm[k].tot; h.n_tokens = len; h.status = 0;
-      }
-    } else {
-      ss_ctc_beam_lm_hyp* h_hyps = static_cast<ss_ctc_beam_lm_hyp*>(h_hyps_out);
-      const int nb = bad ? 0 : (int)bm.size();
-      std::vector<double> fin(nb), lms(nb);
-      for (int r = 0; r < nb; ++r) {
-        const double fused = bm[r].tot + bm[r].bonus;
-        fin[r] = fused; lms[r] = n_sum[bm[r].node];
-        if (o->eos_term) {
-          int st;
-          const double lp = ngram_lp(lv, n_state[bm[r].node], lv.eos, &st);
-          fin[r] = ngram_finish(fused, lw, lp); lms[r] += lp;
-        }
-      }
-      for (int k = nb; k < nbest; ++k) {
-        ss_ctc_beam_lm_hyp& h = h_hyps[(size_t)b * nbest + k];
-        h.score = h.ctc_score = bad ? (double)__builtin_nanf("") : -INFINITY; h.lm_score = 0.0; h.n_tokens = 0; h.status = bad ? 2 : 1;
-      }
-      for (int r = 0; r < nb; ++r) {
-        int rank = 0;
-        for (int f = 0; f < nb; ++f) rank += ctc_beam_before(fin[f], f, fin[r], r);
-        if (rank >= nbest) continue;
-        ss_ctc_beam_lm_hyp& h = h_hyps[(size_t)b * nbest + rank];
-        int len = 0;
-        for (int n = bm[r].node; n > 0; n = par[n]) ++len;
-        int32_t* out = h_tokens + ((size_t)b * nbest + rank) * out_stride;
-        int j = len;
-        for (int n = bm[r].node; n > 0; n = par[n]) out[--j] = tok[n];
-        h.score = fin[r]; h.ctc_score = bm[r].tot; h.lm_score = lms[r]; h.n_tokens = len; h.status = 0;
-      }
-    }
+    S.start(beam, sg.T, LM, lv.start);
+    ctc_beam_host_frames<LM>(S, h_logits + (size_t)sg.row0 * ld, ld, V, pad, unk, sg.T, beam, cand, lv, lw, ws,
+                             h_den ? h_den + 2 * (size_t)sg.row0 : nullptr, h_cand_id ? h_cand_id + (size_t)sg.row0 * cand : nullptr);
+    ctc_beam_host_emit<LM>(S, nbest, LM && o->eos_term, lv, lw, static_cast<unsigned char*>(h_hyps_out) + (size_t)b * nbest * rec,
+                           h_tokens + (size_t)b * nbest * out_stride, out_stride);
   }
   return SS_OK;
 }
+
+// The resumable twin: every pointer a HOST pointer, h_logits the stacked new rows (session i's upto - f rows behind those of the
+// sessions before it).  The checks are the caller's (ss_ctc_stream_advance_host, ctc_stream.hip).
+namespace ss {
+int ctc_stream_host_run(std::vector<CtcBeamHostState>& slots, const float* h_logits, int ld, int V, int pad, int unk, int n,
+                        const CtcStreamSess* sess, int beam, int cand, int nbest, const ss_ngram_lm* lm, const ss_ctc_lm_opts* o,
+                        void* h_hyps, int32_t* h_tokens, int out_stride, CtcStreamPart* h_part) {
+  NgramView lv{};
+  double lw = 0.0, ws = 0.0;
+  if (lm) { lv = lm->host.view(); lw = o->lm_weight; ws = o->word_score; }
+  const size_t rec = lm ? sizeof(ss_ctc_beam_lm_hyp) : sizeof(ss_ctc_beam_hyp);
+  for (int i = 0; i < n; ++i) {
+    const CtcStreamSess& se = sess[i];
+    CtcBeamHostState& S = slots[se.slot];
+    const float* rows = h_logits + (size_t)se.row0 * ld;
+    unsigned char* hy = static_cast<unsigned char*>(h_hyps) + (size_t)i * nbest * rec;
+    int32_t* tk = h_tokens + (size_t)i * nbest * out_stride;
+    if (lm) {
+      ctc_beam_host_frames<true>(S, rows, ld, V, pad, unk, se.upto - se.f, beam, cand, lv, lw, ws, nullptr, nullptr);
+      ctc_beam_host_emit<true>(S, nbest, se.fin && o->eos_term, lv, lw, hy, tk, out_stride);
+    } else {
+      ctc_beam_host_frames<false>(S, rows, ld, V, pad, unk, se.upto - se.f, beam, cand, lv, lw, ws, nullptr, nullptr);
+      ctc_beam_host_emit<false>(S, nbest, false, lv, lw, hy, tk, out_stride);
+    }
+    h_part[i] = ctc_beam_host_part(S);
+  }
+  return SS_OK;
+}
+}  // namespace ss
 
 extern "C" int ss_ctc_beam_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
                                 int nbest, ss_ctc_beam_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den,

@@ -34,6 +34,9 @@
 
 #include "ctc_align.hpp"
 
+struct ss_ngram_lm;                  // include/streamspeech_hip.h
+struct ss_ctc_lm_opts;
+
 namespace ss {
 
 constexpr int CTC_BEAM_MAX_BEAM = 32;
@@ -85,6 +88,90 @@ inline int ctc_beam_plan(int V, int B, const int32_t* h_T, int beam, int cand, i
   }
   return SS_OK;
 }
+
+// ---- the resumable form (ss_ctc_stream_*: ctc_stream.hip, the kernel in ctc_beam.hip) ----
+// The same search stopped after any frame and taken up at the next: node ids hold the ABSOLUTE frame, the child table lives as long
+// as the utterance, and the beam that left the last frame of a call is stored beside them, so the frames [f, upto) of a call are the
+// frames f .. upto - 1 of the one-shot search bit for bit.  Every slot of an object has the same sizes, made for max_frames:
+// nodes 1 + beam * max_frames, a table of the power of two >= 2 * beam * max_frames slots (ctc_beam_plan's rule).
+struct CtcStreamSess {  // one session of an advance call
+  int slot;             // whose state
+  int row0;             // its first stacked new row: frame f is row row0
+  int f, upto;          // the frames [f, upto) run in this call
+  int fin, pad_;        // the utterance's last call: the LM form's eos term
+};
+
+struct CtcStreamPart { int frames, n_stable, n_alive, status; };   // ss_ctc_stream_part
+
+// Where the slots' state lies (device pointers; array a of slot s starts at a + s * its per-slot count).
+struct CtcStreamDev {
+  unsigned long long* keys;   // [S][slots]
+  int2* nodes;                // [S][nodes]
+  int* vals;                  // [S][slots]
+  double* n_sum;              // [S][nodes]   LM form
+  double* n_bonus;            // [S][nodes]   LM form
+  int* n_state;               // [S][nodes]   LM form
+  double* b_f64;              // [S][4][beam]: pb | pnb | tot | bonus of the stored beam
+  int* b_i32;                 // [S][2 beam + 2]: node | last | alive, NaN seen
+  long long nodes_per, slots_per;
+  const CtcStreamSess* sess;
+  CtcStreamPart* part;
+};
+
+inline long long ctc_stream_slots(int beam, int max_frames) {
+  long long slots = 2;
+  while (slots < 2LL * beam * max_frames) slots *= 2;
+  return slots;
+}
+inline long long ctc_stream_nodes(int beam, int max_frames) { return 1 + (long long)beam * max_frames; }
+// The bytes of one slot, the header's figure: 12 per table slot, 8 per node (28 in the LM form), 32 + 8 per beam slot, 8.
+inline size_t ctc_stream_slot_bytes(int beam, int max_frames, bool lm) {
+  const size_t nodes = (size_t)ctc_stream_nodes(beam, max_frames), slots = (size_t)ctc_stream_slots(beam, max_frames);
+  return slots * 12 + nodes * (lm ? 28 : 8) + (size_t)beam * 32 + ((size_t)beam * 2 + 2) * 4;
+}
+// The arrays of S slots in one piece of S * ctc_stream_slot_bytes: the 8-byte ones first (keys, nodes, the stored beam's doubles,
+// the LM doubles), then the 4-byte ones, so every array is aligned whatever S, beam and max_frames are.
+inline void ctc_stream_carve(void* mem, int S, int beam, int max_frames, bool lm, CtcStreamDev* d) {
+  const size_t nodes = (size_t)ctc_stream_nodes(beam, max_frames), slots = (size_t)ctc_stream_slots(beam, max_frames);
+  unsigned char* w = static_cast<unsigned char*>(mem);
+  d->keys = reinterpret_cast<unsigned long long*>(w); w += (size_t)S * slots * 8;
+  d->nodes = reinterpret_cast<int2*>(w); w += (size_t)S * nodes * 8;
+  d->b_f64 = reinterpret_cast<double*>(w); w += (size_t)S * beam * 32;
+  d->n_sum = d->n_bonus = nullptr; d->n_state = nullptr;
+  if (lm) {
+    d->n_sum = reinterpret_cast<double*>(w); w += (size_t)S * nodes * 8;
+    d->n_bonus = reinterpret_cast<double*>(w); w += (size_t)S * nodes * 8;
+  }
+  d->vals = reinterpret_cast<int*>(w); w += (size_t)S * slots * 4;
+  if (lm) { d->n_state = reinterpret_cast<int*>(w); w += (size_t)S * nodes * 4; }
+  d->b_i32 = reinterpret_cast<int*>(w);
+  d->nodes_per = (long long)nodes; d->slots_per = (long long)slots;
+  d->sess = nullptr; d->part = nullptr;
+}
+
+// One utterance's state in the plain-C++ twins (ctc_beam.hip): the device's arrays as vectors, the beam in rank order.
+struct CtcBeamHostPre { double pb, pnb, tot; int node, last; double bonus; };
+struct CtcBeamHostState {
+  std::vector<unsigned long long> keys;
+  std::vector<int> vals, par, tok, n_state;
+  std::vector<double> n_sum, n_bonus;
+  std::vector<CtcBeamHostPre> bm;
+  int mask = 0, frames = 0;
+  bool bad = false;
+  void start(int beam, int max_T, bool lm, int lm_start);   // the empty string, an empty table for max_T frames
+};
+
+// One launch of the candidate kernel over the `rows` stacked new rows (none: no launch) into den [rows][2] / cand [rows][C], the
+// upload of the n sessions to d_sess (n * sizeof(CtcStreamSess)) and one launch of the resumable search kernel, one workgroup per
+// session.  dev: the carved state (sess / part are set here).  lm == nullptr: the plain form, hyps ss_ctc_beam_hyp [n][nbest].
+// Nothing is checked here: the refusals and the clearing of a reset slot's table are the caller's (ctc_stream.hip).
+int launch_ctc_stream(const float* logits, int ld, int V, int pad, int unk, int rows, int n, const CtcStreamSess* h_sess, void* d_sess,
+                      float* den, int* cand_id, int beam, int C, int nbest, CtcStreamDev dev, const ss_ngram_lm* lm,
+                      const ss_ctc_lm_opts* opts, void* hyps, int* tokens, int out_stride, CtcStreamPart* part, hipStream_t stream);
+// The same in plain C++ on host logits and host state (one CtcBeamHostState per slot, started by the caller).
+int ctc_stream_host_run(std::vector<CtcBeamHostState>& slots, const float* h_logits, int ld, int V, int pad, int unk, int n,
+                        const CtcStreamSess* sess, int beam, int cand, int nbest, const ss_ngram_lm* lm, const ss_ctc_lm_opts* o,
+                        void* h_hyps, int32_t* h_tokens, int out_stride, CtcStreamPart* h_part);
 
 // ---- the step code ----
 SS_HD float ctc_beam_lp(float x, float mx, float logsum) { return (x - mx) - logsum; }

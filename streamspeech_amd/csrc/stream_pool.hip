@@ -176,8 +176,8 @@ static int launch_pool_gather_ids(int32_t* out, const int32_t* stk, int32_t* cac
   SS_LAUNCH_CHECK();
   return SS_OK;
 }
-// W floats per row: whole float4s, at most one 256-thread workgroup per row
-static int launch_pool_stack_rows(float* out, const float* enc, int W, const int* src, const int* pre, int nsess, int total,
+// W floats per row: whole float4s, at most one 256-thread workgroup per row (also ctc_stream.hip's: the rows a search has not consumed)
+int launch_pool_stack_rows(float* out, const float* enc, int W, const int* src, const int* pre, int nsess, int total,
                                   hipStream_t s) {
   if (W <= 0 || (W & 3) != 0 || W > 1024 || nsess <= 0) return SS_ERR_ARG;
   if (total <= 0) return SS_OK;

@@ -1436,6 +1436,86 @@ class StreamPool:
             pass
 
 
+class CtcPartial(NamedTuple):
+    """What one CtcStream.advance reports for a session."""
+    hyps: List[CtcHypothesis]   # the search's n-best after `frames` frames, best first (none after a NaN row)
+    n_stable: int               # the first n_stable tokens are common to every string of the beam: they can never change again
+    frames: int                 # frames the search has consumed
+    final: bool                 # the utterance's last call (the slot was reset by it)
+
+
+class CtcStream:
+    """The resumable CTC prefix beam search of a text head (ss_ctc_stream): `max_sessions` slots, each the search of one utterance
+    kept on the device between calls.  :meth:`advance` moves any subset of slots forward over encoder rows that are FINAL (the
+    incremental encoder's n_final); the utterance's last call gives exactly batch_ctc_beam's n-best on all its frames, every other
+    call the n-best of the frames so far and how many leading tokens can no longer change.  beam, cand (default
+    ctc_beam_default_cand), nbest (default beam), the model lm (an ngram.NgramLM; kept alive here) and its weights are fixed at
+    creation; the trie is sized for `max_frames` encoder rows per utterance (at most L.CTC_BEAM_MAX_FRAMES).  The state is booked
+    on the model's scratch set and released by :meth:`close`."""
+
+    def __init__(self, model: "HipModel", head: int, max_sessions: int, max_frames: int, beam: int, cand: Optional[int] = None,
+                 nbest: Optional[int] = None, lm=None, lm_weight: float = 0.0, word_score: float = 0.0, lm_eos: bool = True):
+        self.lib, self.model, self.device = model.lib, model, _require_gpu(model.device)
+        self.head, self.max_sessions, self.max_frames, self.beam = int(head), int(max_sessions), int(max_frames), int(beam)
+        self.cand = ctc_beam_default_cand(beam) if cand is None else int(cand)
+        self.nbest = self.beam if nbest is None else int(nbest)
+        self.lm = lm
+        opts = C.byref(L.SSCtcLmOpts(float(lm_weight), float(word_score), int(bool(lm_eos)))) if lm is not None else None
+        self.h = None
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(self.lib.ss_ctc_stream_create(model.h, self.head, self.max_sessions, self.max_frames, self.beam, self.cand,
+                                                  self.nbest, lm.h if lm is not None else None, opts, C.byref(h)), "ss_ctc_stream_create")
+        self.h = h
+
+    def reset(self, slot: int):
+        """A new utterance in `slot` (host-only; the utterance's last advance does it by itself)."""
+        L.check(self.lib.ss_ctc_stream_reset(self.h, int(slot)), "ss_ctc_stream_reset")
+
+    def advance(self, slots: List[int], enc_packed: torch.Tensor, T: List[int], upto: List[int], final: List[bool]) -> List[CtcPartial]:
+        """Session i owns T[i] packed rows of enc_packed (all its encoder output so far); the search of slots[i] moves to upto[i]
+        frames; final[i]: the utterance's last call.  One buffer, one device-to-host copy."""
+        n = len(slots)
+        stride = max([int(u) for u in upto] + [1])
+        k = n * self.nbest
+        w = 8 if self.lm is not None else 4                     # int32 words per hypothesis record
+        # int32 words: hyps [w k] (first: 8-byte aligned) | parts [4 n] | tokens [k][stride]
+        ibuf = torch.empty((w * k + 4 * n + k * stride + 1,), dtype=torch.int32, device=self.device)
+        L.check(self.lib.ss_ctc_stream_advance(self.model.h, _stream(), self.h, n, _i32(slots), _ptr(enc_packed), _i32(T), _i32(upto),
+                                               _i32([1 if f else 0 for f in final]), _ptr(ibuf), _ptr(ibuf[w * k + 4 * n:]), stride,
+                                               _ptr(ibuf[w * k:])), "ss_ctc_stream_advance")
+        host = ibuf.cpu().numpy()
+        part = host[w * k: w * k + 4 * n].reshape(n, 4)
+        tok = host[w * k + 4 * n:]
+        if self.lm is not None:
+            hyp = host[:w * k].view(np.dtype([("score", "<f8"), ("ctc_score", "<f8"), ("lm_score", "<f8"), ("n_tokens", "<i4"),
+                                              ("status", "<i4")]))
+            mk = lambda j: CtcHypothesis(tok[j * stride: j * stride + int(hyp["n_tokens"][j])].tolist(), float(hyp["score"][j]),  # noqa: E731
+                                         float(hyp["ctc_score"][j]), float(hyp["lm_score"][j]))
+        else:
+            hyp = host[:w * k].view(np.dtype([("score", "<f8"), ("n_tokens", "<i4"), ("status", "<i4")]))
+            mk = lambda j: CtcHypothesis(tok[j * stride: j * stride + int(hyp["n_tokens"][j])].tolist(), float(hyp["score"][j]))  # noqa: E731
+        return [CtcPartial([mk(j) for j in range(i * self.nbest, (i + 1) * self.nbest) if hyp["status"][j] == 0], int(part[i, 1]),
+                           int(part[i, 0]), bool(final[i])) for i in range(n)]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ss_ctc_stream_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HipVocoder:
     """ss_vocoder handle (CodeHiFiGANVocoderWithDur replacement)."""
 

@@ -84,6 +84,11 @@ class SSCtcBeamLmHyp(C.Structure):
                 ("status", C.c_int32)]
 
 
+class SSCtcStreamPart(C.Structure):
+    """ss_ctc_stream_part: what one advance of the resumable CTC prefix beam search reports per session (16 bytes)."""
+    _fields_ = [("frames", C.c_int32), ("n_stable", C.c_int32), ("n_alive", C.c_int32), ("status", C.c_int32)]
+
+
 class SSCtcLmOpts(C.Structure):
     """ss_ctc_lm_opts: the weights of the fusion."""
     _fields_ = [("lm_weight", C.c_double), ("word_score", C.c_double), ("eos_term", C.c_int32)]
@@ -312,6 +317,13 @@ SIGNATURES = {
     "ss_batch_ctc_beam_lm": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, C.POINTER(SSCtcLmOpts)]),
     "ss_ctc_beam_lm_host": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,
                                  C.POINTER(SSCtcLmOpts)]),
+    "ss_ctc_stream_create": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(SSCtcLmOpts), C.POINTER(_vp)]),
+    "ss_ctc_stream_destroy": (None, [_vp]),
+    "ss_ctc_stream_reset": (_i, [_vp, _i]),
+    "ss_ctc_stream_advance": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32), _vp, _vp, _i, _vp]),
+    "ss_ctc_stream_advance_host": (_i, [_vp, _i, C.POINTER(C.c_int32), _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp,
+                                        _i, _vp]),
     "ss_batch_mt_greedy": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
                                 C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _vp, _i]),
     "ss_batch_mt_beam": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _f, _i,
@@ -438,6 +450,9 @@ SIGNATURES = {
     "ss_debug_ctc_beam_host_max": (_i, [_i]),
     "ss_op_ctc_beam_lm": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,
                                C.POINTER(SSCtcLmOpts)]),
+    "ss_debug_ctc_stream_create": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(SSCtcLmOpts), C.POINTER(_vp)]),
+    "ss_op_ctc_stream_advance": (_i, [_vp, _vp, _i, C.POINTER(C.c_int32), _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp,
+                                      _vp, _i, _vp]),
     "ss_op_ngram_score": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _vp, _vp]),
     "ss_op_dur_predict": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
     "ss_op_repeat_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),

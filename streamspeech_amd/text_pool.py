@@ -36,7 +36,7 @@ from .frontend import SAMPLE_RATE, OnlineFeatureExtractor, unsettled_fbank_frame
 from . import endpoint as EP
 from .pcm import PcmArena, PcmFormat, PcmOut
 from .simuleval_shim import AgentStates, EmptySegment, TextSegment
-from .text_policy import mt_max_len, s2tt_gate
+from .text_policy import CtcBeamOptions, asr_beam_emit, mt_max_len, s2tt_gate
 from .words import CtcDetails, words_from_ctc
 
 KINDS = ("s2tt", "asr")
@@ -95,6 +95,7 @@ class _Session:
         self.ep = None                        # an endpoint.EndpointState: the pool cuts the session's stream into utterances
         self.details = None                   # a words.CtcDetails of the last step that encoded the session (pools with details)
         self.alignment = None                 # the words.AlignedWord list of the utterance's committed target tokens (pools with align)
+        self.nbest = None                     # pools with ctc_beam: the engine.CtcHypothesis list of the last finished utterance
         self.reset()
 
     def n_source(self) -> int:
@@ -115,6 +116,8 @@ class _Session:
         self.tgt_ctc_prefix_length = 0
         self.asr_text = ""
         self.tgt_text = ""
+        self.partial = None                   # pools with ctc_beam: the symbols of the utterance's current best hypothesis
+        self.ctc_frames = 0                   # ... and the encoder rows its search has consumed
         self.states.reset()
         self.fe.clear_cache()
         if self.pcm_state is not None:        # a fresh utterance: nothing received, nothing emitted, nothing carried
@@ -130,7 +133,7 @@ class TextSessionPool:
 
     def __init__(self, model, max_sessions: int, max_rows: int, beam_mt: int = 1, details: bool = False, align: bool = False,
                  search: Optional[SearchOptions] = None, len_penalty: float = 1.0, temperature: float = 1.0,
-                 no_repeat_ngram_size: int = 0):
+                 no_repeat_ngram_size: int = 0, ctc_beam: Optional[CtcBeamOptions] = None):
         """beam_mt > 1: the step's one ragged continuation is a beam search behind every writer's committed prefix
         (HipModel.batch_mt_beam_continue, the agents' --beam-mt); hypothesis 0's tokens and states go on as the greedy ones do.
         details: the step's one CTC call is the scored form, and details(sid) answers the words of both heads with their time
@@ -146,7 +149,19 @@ class TextSessionPool:
         search=engine.SamplingOptions(topk, topp, seed, search=SearchOptions or None): the agents' --sampling.  Every write draws
         beam_mt chains behind the writer's committed prefix (HipModel.batch_mt_sample_continue) and commits the best-scoring one;
         a write's stream key is engine.sampling_stream_key(session id, the session's writes so far), so a replayed session samples
-        the same and two sessions never share a stream."""
+        the same and two sessions never share a stream.
+        ctc_beam (a text_policy.CtcBeamOptions): ASR sessions decode with the resumable CTC prefix beam search in place of the
+        arg-max frame path -- the pool owns one engine.CtcStream on head 0 whose slots are the pool's, and after the encoder ONE
+        advance serves every ASR session of the step, over the rows the encoder has made final (all rows, with final, for a
+        session whose source is finished).  Such a session writes the new text of the prefix every beam string shares, and the
+        rest of the best hypothesis at the end: the writes of an utterance add up to its final best hypothesis and none is ever
+        retracted.  partial(sid) answers the current best hypothesis, nbest(sid) the last finished utterance's n-best.  S2TT
+        sessions (and a subclass's kinds) run as without the option, and so does every launch of a pool built without it.  Not
+        with details (its spans are the arg-max path's)."""
+        if ctc_beam is not None and details:
+            raise ValueError("ctc_beam cannot be combined with details: the words' spans are those of the arg-max path")
+        if ctc_beam is not None and not isinstance(ctc_beam, CtcBeamOptions):
+            raise ValueError("ctc_beam: a text_policy.CtcBeamOptions")
         if not 1 <= int(beam_mt) <= MT_BEAM_MAX:
             raise ValueError(f"beam_mt {beam_mt} outside [1, {MT_BEAM_MAX}]")
         self.beam_mt = int(beam_mt)
@@ -162,6 +177,12 @@ class TextSessionPool:
         self._align_jobs: list = []            # (session, encoder view index, committed tokens, tokens placed before, record list, t0_ms)
         self.pool = self.model.stream_pool(max_sessions, max_rows, scores=True) if details else self.model.stream_pool(max_sessions, max_rows)
         self.max_sessions, self.max_rows = int(max_sessions), int(max_rows)
+        self.ctc_stream = None                 # pools with ctc_beam: the searches of the ASR sessions, slot for slot
+        self._stream_rows: list = []           # ... and the rows each of the step's searches moved over
+        if ctc_beam is not None:
+            from .engine import CtcStream
+            from .lib import CTC_BEAM_MAX_FRAMES
+            self.ctc_stream = CtcStream(self.model, 0, self.max_sessions, min(self.max_rows, CTC_BEAM_MAX_FRAMES), **ctc_beam.stream_kwargs())
         self.sessions: Dict[int, _Session] = {}
         self.free = list(range(self.max_sessions))
         self._next = 0
@@ -319,9 +340,23 @@ class TextSessionPool:
             raise KeyError(f"no open session {sid}")
         return self.sessions[sid]
 
+    def partial(self, sid: int):
+        """A pool with ctc_beam: the symbols of the ASR session's current best hypothesis, its unstable tail included -- for
+        display; what the session has WRITTEN is the stable part.  None before the utterance's first encoded step."""
+        return self._get(sid).partial if self.ctc_stream is not None else None
+
+    def nbest(self, sid: int):
+        """A pool with ctc_beam: the n-best (engine.CtcHypothesis, best first) of the ASR session's last finished utterance."""
+        return self._get(sid).nbest if self.ctc_stream is not None else None
+
+    def _slot_reset(self, slot: int):
+        self.pool.reset(slot)
+        if self.ctc_stream is not None:        # wherever the encoder's slot starts over, so does its search
+            self.ctc_stream.reset(slot)
+
     def _release(self, s: _Session):
         if s.slot is not None:
-            self.pool.reset(s.slot)
+            self._slot_reset(s.slot)
             self.free.append(s.slot)
             s.slot = None
 
@@ -330,7 +365,7 @@ class TextSessionPool:
             if not self.free:
                 raise ValueError(f"session {s.sid}: all {self.max_sessions} slots of the pool are taken")
             s.slot = self.free.pop(0)
-            self.pool.reset(s.slot)
+            self._slot_reset(s.slot)
             self.pool.set_tail(s.slot, s.tail)
 
     # ---- one call per session ---------------------------------------------------------------------------------------------------
@@ -727,12 +762,18 @@ class TextSessionPool:
         # ---- one encoder step + both CTC heads ----
         enc = [s for s in todo if s.sid in feats]
         writers, n_steps, mine, views, mt_groups = [], 0, [], None, []
+        beam_asr = []                             # pools with ctc_beam: the step's ASR sessions, by their index in enc
         if enc:
             for s in enc:
                 self._acquire(s)
             packed, views, n_fin, _ = self.pool.forward([s.slot for s in enc], [feats[s.sid] for s in enc],
                                                         [s.attn_chunk for s in enc], [s.conv_chunk for s in enc])
-            src, tgt = self.pool.ctc_both()       # (a pool with details: the scored form, records of five)
+            beam_asr = [i for i, s in enumerate(enc) if s.kind == "asr"] if self.ctc_stream is not None else []
+            if len(beam_asr) < len(enc):          # (a pool with details: the scored form, records of five)
+                src, tgt = self.pool.ctc_both()
+            else:                                 # ASR sessions only, all on the prefix search: no arg-max call
+                src = tgt = [None] * len(enc)
+            parts = self._ctc_stream_step(enc, beam_asr, packed, views, n_fin) if beam_asr else {}
             if self.with_details:
                 for i, s in enumerate(enc):
                     self._set_details(s, src[i], tgt[i], n_fin[i])
@@ -742,6 +783,9 @@ class TextSessionPool:
                 self._mp3_arena.synchronized()
             t2 = time.perf_counter()
             for i, s in enumerate(enc):
+                if i in parts:
+                    actions[s.sid] = self._asr_beam(s, parts[i])
+                    continue
                 if s.kind == "asr":
                     actions[s.sid] = self._asr(s, src[i][0])
                     continue
@@ -824,6 +868,9 @@ class TextSessionPool:
         # session inside an utterance (first stream sample, samples, finished) of what the step committed
         self.last_step.update({"vad_scan_calls": 0, "vad_frames": 0, "endpoint_starts": 0, "endpoint_ends": 0, "endpoint_commits": {}}
                               if vad is None else vad)
+        if self.ctc_stream is not None:           # ss_ctc_stream_advance calls of the step (0 or 1), rows they ran through the head
+            self.last_step.update({"ctc_stream_calls": 1 if (enc and beam_asr) else 0,
+                                   "ctc_stream_rows": sum(self._stream_rows) if (enc and beam_asr) else 0})
         self.last_step.update(self._side_times)
         self._side_times = {}
         if eps:
@@ -870,6 +917,27 @@ class TextSessionPool:
         new_text = text[len(s.asr_text):]
         s.asr_text = text
         if s.states.source_finished:
+            self._finish(s)
+        return ("write", new_text, s.states.target_finished)
+
+    def _ctc_stream_step(self, enc, beam_asr, packed, views, n_fin) -> dict:
+        """The step's ONE advance of the prefix searches of its ASR sessions -> {index in enc: engine.CtcPartial}."""
+        T2 = [int(views[i].shape[0]) for i in beam_asr]
+        rows = packed if len(beam_asr) == len(enc) else torch.cat([views[i] for i in beam_asr], 0)
+        final = [bool(enc[i].states.source_finished) for i in beam_asr]
+        upto = [t2 if fin else int(n_fin[i]) for i, t2, fin in zip(beam_asr, T2, final)]
+        got = self.ctc_stream.advance([enc[i].slot for i in beam_asr], rows, T2, upto, final)
+        self._stream_rows = [p.frames - enc[i].ctc_frames for i, p in zip(beam_asr, got)]
+        for i, p in zip(beam_asr, got):
+            enc[i].ctc_frames = 0 if p.final else p.frames
+        return dict(zip(beam_asr, got))
+
+    def _asr_beam(self, s: _Session, part):
+        symbols = [s.dict["source_unigram"][c] for c in part.hyps[0].tokens] if part.hyps else []
+        s.partial = symbols
+        new_text, s.asr_text = asr_beam_emit(s.asr_text, symbols, part.n_stable, part.final)
+        if part.final:
+            s.nbest = part.hyps
             self._finish(s)
         return ("write", new_text, s.states.target_finished)
 
