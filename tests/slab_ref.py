@@ -7,6 +7,9 @@ exception, on purpose: torch's conv_transpose1d per utterance, the independent s
 A pack is a [M, C] tensor of utterances laid end to end; `segs` lists (start, len) per utterance.  Every utterance is convolved
 ALONE: rows outside it read as zero whatever lies next to it in the pack.  Rows of the pack no segment covers come back as NaN --
 no launch may write them.
+
+The second half restates the operand rounding of the reduced-precision routes (csrc/conv_f16.hip, the split-bf16 form of
+csrc/conv_sk2.hip), so that their kernels are held to the float64 conv of the operands they really multiply.
 """
 import torch
 import torch.nn.functional as F
@@ -103,3 +106,103 @@ def resblock(x, segs, W1, B1, W2, B2, dils, slope=0.1, R2=None, div=0.0):
     if div > 0:
         x = x / div
     return x
+
+
+# ---- the reduced-precision routes: the same conv on operands rounded the way the kernel rounds them ------------------------------
+# csrc/conv_f16.hip and the split-bf16 form of csrc/conv_sk2.hip round their operands by a rule that torch restates exactly; every
+# product of two rounded operands is exact in float32, so what is left between a kernel and the float64 conv of the ROUNDED operands
+# is float32 accumulation alone.  accum=torch.float32 runs the same sums in float32 on the CPU: its distance to the float64 result is
+# the figure E the GPU bounds rest on (reference against reference, no kernel involved).
+F16_MAX = 65504.0
+F16_MIN_NORMAL = 2.0 ** -14
+
+
+def to_f16_sat(x):
+    """FP16 image of x in x's dtype, as to_f16_sat of csrc/conv_f16.hip: clamp to +-65504 (so +-inf lands there, never on inf), round
+    to nearest even.  NaN stays NaN."""
+    return x.clamp(-F16_MAX, F16_MAX).half().to(x.dtype)
+
+
+def to_f16_noclamp(x):
+    """MUTANT: the conversion without the clamp (65520 and above become inf)."""
+    return x.half().to(x.dtype)
+
+
+def to_f16_rtz(x):
+    """MUTANT: clamp, then round TOWARD ZERO instead of to nearest even."""
+    c = x.clamp(-F16_MAX, F16_MAX)
+    h = c.half()
+    away = h.to(c.dtype).abs() > c.abs()                    # rounded away from zero: one FP16 step back (sign-magnitude bits)
+    return torch.where(away, (h.view(torch.int16) - 1).view(torch.float16), h).to(x.dtype)
+
+
+def flush_f16_subnormals(round_fn=to_f16_sat):
+    """MUTANT: round_fn followed by a flush of the FP16 subnormals (|h| < 2^-14) to zero."""
+    def f(x):
+        h = round_fn(x)
+        return torch.where(h.abs() < F16_MIN_NORMAL, torch.zeros_like(h), h)
+    return f
+
+
+def split_bf16(x):
+    """(hi, lo) of the split-bf16 form, both float32: hi = bf16(x), lo = bf16(x - hi), round to nearest even (x - hi is exact)."""
+    xf = x.float()
+    hi = xf.bfloat16().float()
+    return hi, (xf - hi).bfloat16().float()
+
+
+def seg_conv_packed(x, w, segs, dil=1, pad=None):
+    """seg_conv written another way, for packs of thousands of short utterances: one matmul per tap over the WHOLE pack, on rows
+    gathered at m - pad + j dil and zeroed where that row lies outside the utterance of m.  Same taps in the same order."""
+    taps = w.shape[2]
+    if pad is None:
+        pad = dil * (taps - 1) // 2
+    M = x.shape[0]
+    lo, hi = torch.zeros(M, dtype=torch.long), torch.zeros(M, dtype=torch.long)       # rows of no utterance: the empty range
+    for s, n in segs:
+        lo[s:s + n], hi[s:s + n] = s, s + n
+    y = x.new_zeros(M, w.shape[0])
+    for j in range(taps):
+        src = torch.arange(M) - pad + j * dil
+        ok = (src >= lo) & (src < hi)
+        y = y + torch.where(ok[:, None], x[src.clamp(0, M - 1)], x.new_zeros(())) @ w[:, :, j].t()
+    y[hi == lo] = float("nan")
+    return y
+
+
+def _in_act_f32(x, in_slope):
+    """The kernels' input activation: float32, fmaxf(v, v * slope)."""
+    xf = x.float()
+    return xf if in_slope is None else torch.maximum(xf, xf * in_slope)
+
+
+def _epi_as(epi, dtype):
+    return {k: (v.to(dtype) if torch.is_tensor(v) else v) for k, v in epi.items()}
+
+
+def conv_f16(x, w, segs, dil, in_slope=None, accum=torch.float64, round_x=to_f16_sat, round_w=to_f16_sat, **epi):
+    """conv() as csrc/conv_f16.hip computes it up to accumulation: the input leaky-ReLU in float32, activations and weights through
+    to_f16_sat, then seg_conv_packed and the epilogue in `accum` (float64: the reference; float32: the figure E).  round_x / round_w take
+    the mutant conversions above."""
+    xh, wh = round_x(_in_act_f32(x, in_slope)), round_w(w.float())
+    return epilogue(seg_conv_packed(xh.to(accum), wh.to(accum), segs, dil), **_epi_as(epi, accum))
+
+
+X3_TERMS = {"hh": (0, 0), "hl": (0, 1), "lh": (1, 0), "ll": (1, 1)}        # term -> (half of W, half of A); 0: hi, 1: lo
+
+
+def x3_parts(x, w, segs, dil, in_slope=None, accum=torch.float64, terms=tuple(X3_TERMS)):
+    """{term: seg_conv_packed of that pair of halves in `accum`}: hh = W_hi . A_hi, hl = W_hi . A_lo, lh = W_lo . A_hi, ll = W_lo . A_lo."""
+    A, W = split_bf16(_in_act_f32(x, in_slope)), split_bf16(w)
+    return {t: seg_conv_packed(A[X3_TERMS[t][1]].to(accum), W[X3_TERMS[t][0]].to(accum), segs, dil) for t in terms}
+
+
+def conv_x3(x, w, segs, dil, in_slope=None, terms=("hh", "hl", "lh"), accum=torch.float64, parts=None, **epi):
+    """conv() as the split-bf16 form of csrc/conv_sk2.hip computes it up to accumulation: the sum of the chosen terms (the kernel's
+    three by default) and the epilogue in `accum`.  parts: x3_parts(...) of the same operands, to share the convs between term sets."""
+    if parts is None:
+        parts = x3_parts(x, w, segs, dil, in_slope, accum, terms)
+    acc = parts[terms[0]].to(accum)
+    for t in terms[1:]:
+        acc = acc + parts[t].to(accum)
+    return epilogue(acc, **_epi_as(epi, accum))

@@ -13,7 +13,10 @@ pack, a census over every profiler class (one launch, of the stream-K class, not
   * three epilogues: every option / plain / what the upsamplers issue on a pre-activated input (bias + twin at 0.1).
 Bounds: the f32 routes TOL = 2e-4 (the per-conv bound of tests/test_ops_gpu.py and tests/test_slab_ops_gpu.py on this data scaling);
 the split-bf16 route against the f32 conv_sk2 result of the same pack and grid with the bars of tests/test_bf16x3_gpu.py (relative RMS
-in (0, 2e-5), max abs < 1e-3) and against float64 with max abs < 1e-3.
+in (0, 2e-5), max abs < 1e-3) and against float64 with max abs < 1e-3 -- and, the sharp one, against the float64 sum of the THREE
+TERMS the kernel multiplies (tests/slab_ref.py conv_x3: hi = bf16(x), lo = bf16(x - hi), W_hi A_hi + W_hi A_lo + W_lo A_hi) with max abs
+< 16 E_case (tests/rounded_cases.py, about 1e-5: float32 accumulation is all that is left), nearer to it than to the four-term sum
+and to either two-term sum.
 """
 import ctypes as C
 import os
@@ -21,6 +24,7 @@ import os
 import pytest
 import torch
 
+from tests import rounded_cases as RC
 from tests import slab_ref as R
 from test_slab_ops_gpu import (SHORT_256, TOL, ConvPack, P, S, bits, census, lib, out_buf, pack_lens, restore, rnd,  # noqa: F401
                                stop_after_a_gpu_error, took_since)
@@ -82,6 +86,33 @@ def pack_of(shape, lens, seed=0):
     return _packs[key]
 
 
+_x3 = {}
+
+
+def x3_of(shape, lens, seed=0):
+    """The rounded-operand references of a pack's three epilogues (RC.x3_refs), for the split-bf16 route; the last two are kept."""
+    key = (shape, tuple(lens), seed)
+    if key not in _x3:
+        while len(_x3) >= 2:
+            del _x3[next(iter(_x3))]
+        _x3[key] = RC.x3_refs(pack_of(shape, lens, seed)[0])
+    return _x3[key]
+
+
+def check_x3(p, out, out2, xr, twin, what):
+    """Split-bf16 against the three-term float64 reference: max abs under 16 E (the twin too), and nearer to it than to the four-term
+    sum (+ll) and the two-term sums (-hl, -lh) by a factor of two.  The figures are printed before anything is asserted."""
+    M = p.M
+    e3, near = RC.err(out[:M], xr.ref), RC.nearest(out, xr, M)
+    print(f"{what} M={M}: vs three-term float64 {e3:.3e} E {xr.E:.3e} bar {xr.bar:.3e} to the mutants "
+          + " ".join(f"[{n}: {dm:.3e}]" for n, (_, dm) in near.items()))
+    assert e3 < xr.bar <= TOL, f"{what}: max abs against the three-term reference {e3} (bar {xr.bar})"
+    if twin:
+        assert RC.err(out2[:M], xr.ref2) < xr.bar, f"{what}: twin against the three-term reference"
+    for n, (d0, dm) in near.items():
+        assert d0 < 0.5 * dm, f"{what}: {d0} from the three-term reference, {dm} from '{n}'"
+
+
 def launch(lib, p, route, G, on, twin, segmented=True):
     """One launch on the route at grid G: rc == 0, one launch of the route's class and nothing else, no stream-K time-out."""
     r = ROUTES[route]
@@ -116,6 +147,7 @@ def check_sk(lib, route, shape, lens, pack, grids=None):
     """All three epilogues of one (route, shape, pack) at every grid."""
     p, refs = pack_of(shape, lens)
     x3 = route == "conv_sk2_x3"
+    xrefs = x3_of(shape, lens) if x3 else None
     tol = X3_TOL if x3 else TOL
     worst = 0.0
     try:
@@ -139,6 +171,7 @@ def check_sk(lib, route, shape, lens, pack, grids=None):
                     print(line)
                     assert 0.0 < rel < X3_REL, f"{what}: relative RMS against the f32 kernel {rel}"
                     assert diff.abs().max().item() < X3_TOL, f"{what}: max abs against the f32 kernel {diff.abs().max().item()}"
+                    check_x3(p, out, out2, xrefs[on], twin, what)
                 else:
                     print(line)
                 worst = max(worst, err)
@@ -179,6 +212,8 @@ def test_one_utterance_with_and_without_a_segment_table(lib, route):
     finally:
         restore(lib)
     check_output(p, *with_table, *refs[True], True, 0.3, X3_TOL if route == "conv_sk2_x3" else TOL, f"{route} one utterance")
+    if route == "conv_sk2_x3":
+        check_x3(p, *with_table, x3_of(shape, [4301])[True], True, f"{route} one utterance G={G}")
     assert torch.equal(bits(with_table[0]), bits(without[0])) and torch.equal(bits(with_table[1]), bits(without[1]))
 
 

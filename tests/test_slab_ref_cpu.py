@@ -1,14 +1,18 @@
 """tests/slab_ref.py against torch.nn.functional.conv1d in float64 -- every utterance cut out of the pack and taken through conv1d on
 its own, the epilogue / pair / ResBlock composed step by step here -- plus the ABI check of the entry points
-tests/test_slab_ops_gpu.py calls (ss_op_conv_gemm_ex, ss_op_conv_pair, ss_op_resblock_fused, ss_debug_slab)."""
+tests/test_slab_ops_gpu.py calls (ss_op_conv_gemm_ex, ss_op_conv_pair, ss_op_resblock_fused, ss_debug_slab).  The last part checks
+the rounded-operand references of the FP16 and split-bf16 convs (to_f16_sat, split_bf16, conv_f16, conv_x3) and, on every pack of
+tests/rounded_cases.py, that the GPU tests' bound of 16 E separates the reference from its mutants -- without a kernel."""
 import ctypes as C
 import os
 import re
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import rounded_cases as RC
 from tests import slab_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -197,3 +201,157 @@ def test_resblock_is_the_hifigan_recurrence(taps, dils, extras):
     f32 = R.resblock(x.float(), segs, [w.float() for w in W1], [b.float() for b in B1], [w.float() for w in W2],
                      [b.float() for b in B2], dils, 0.1, None if R2 is None else R2.float(), 3.0 if extras else 0.0)
     assert f32.dtype == torch.float32 and (f32.double() - got).abs().max() < 1e-4      # the float32 chain is the same function
+
+
+# ---- the rounded-operand references of the reduced-precision routes (tests/test_f16_ops_gpu.py, split-bf16 in tests/test_sk_ops_gpu.py) ----
+# value -> FP16 image, written down by hand: ties at 2^-25 (to 0) and at 2049 (to 2048), the clamp, the subnormal range
+F16_TABLE = [(name, v, img) for name, v, img in RC.LATTICE] + [
+    ("largest below the clamp's tie", 65519.996, 65504.0), ("3e38", 3e38, 65504.0), ("-3e38", -3e38, -65504.0),
+    ("smallest subnormal", 2.0 ** -24, 2.0 ** -24), ("largest subnormal", 1023 * 2.0 ** -24, 1023 * 2.0 ** -24),
+    ("tie at 2^-25", 2.0 ** -25, 0.0), ("tie at 2049", 2049.0, 2048.0), ("-2049", -2049.0, -2048.0),
+]
+
+
+def test_to_f16_sat_on_named_values():
+    """Against the hand-written images and against numpy's own float16 conversion after a numpy clip, bit for bit (the sign of zero
+    included), from float32 and from float64; the mutants differ from it where they should."""
+    names = [n for n, _, _ in F16_TABLE]
+    for dtype in (torch.float32, torch.float64):
+        v = torch.tensor([x for _, x, _ in F16_TABLE], dtype=dtype)
+        img = torch.tensor([i for _, _, i in F16_TABLE], dtype=dtype)
+        got = R.to_f16_sat(v)
+        assert got.dtype == dtype
+        with np.errstate(over="ignore"):
+            by_numpy = torch.from_numpy(np.clip(v.numpy(), -65504, 65504).astype(np.float16).astype(v.numpy().dtype))
+        for want in (img, by_numpy):
+            bad = [names[i] for i in range(len(names)) if got[i] != want[i] or torch.signbit(got[i]) != torch.signbit(want[i])]
+            assert not bad, bad
+        assert torch.equal(got.half().to(dtype), got)                   # every image is an FP16 value
+        free = R.to_f16_noclamp(v)
+        assert [n for n, a, b in zip(names, free, got) if a != b] == [n for n, x, _ in F16_TABLE if abs(x) >= 65520.0]
+        assert torch.isinf(free[[names.index("65520 -> 65504"), names.index("-inf -> -65504")]]).all()
+        rtz = R.to_f16_rtz(v)
+        assert (rtz.abs() <= v.abs()).all() and (rtz.abs() <= got.abs()).all() and torch.equal(rtz.half().to(dtype), rtz)
+        assert rtz[names.index("tie 2051 -> 2052")] == 2050.0 and rtz[names.index("subnormal 2^-25 (1 + 2^-10) -> 2^-24")] == 0.0
+        assert rtz[names.index("-1e5 -> -65504")] == -65504.0 and rtz[names.index("tie -(1 + 2^-11) -> -1")] == -1.0
+        flushed = R.flush_f16_subnormals()(v)
+        sub = got.abs() < 2.0 ** -14
+        assert sub.sum() >= 8 and not flushed[sub].any() and torch.equal(flushed[~sub], got[~sub])
+    assert torch.isnan(R.to_f16_sat(torch.tensor([float("nan")]))).all()
+    # round toward zero, everywhere: the largest FP16 value not above |x|
+    x = torch.cat([rnd(20000, seed=91).float(), rnd(20000, seed=92, scale=1e-4).float(), rnd(2000, seed=93, scale=3e4).float()])
+    rtz, rne = R.to_f16_rtz(x), R.to_f16_sat(x)
+    up = (rtz.half().view(torch.int16) + 1).view(torch.float16).float()          # one FP16 step away from zero
+    inside = x.abs() < 65504.0
+    assert (rtz.abs() <= x.abs()).all() and (up.abs() > x.abs())[inside].all() and ((rtz == rne) | (up == rne))[inside].all()
+    assert 0.3 < (rtz != rne).float().mean() < 0.7
+
+
+def test_split_bf16_halves():
+    """hi and lo are bf16 values (the low 16 bits of their float32 are zero), |x - hi - lo| <= 2^-16 |x|, hi is the nearest bf16."""
+    x = torch.cat([rnd(50000, seed=94).float(), rnd(50000, seed=95, scale=0.02).float(), torch.tensor([0.0, -0.0, 1.0, 3.0e38, 1e-30, 257.0, 259.0])])
+    hi, lo = R.split_bf16(x)
+    assert hi.dtype == lo.dtype == torch.float32
+    assert not (hi.view(torch.int32) & 0xFFFF).any() and not (lo.view(torch.int32) & 0xFFFF).any()
+    assert ((x.double() - hi.double() - lo.double()).abs() <= 2.0 ** -16 * x.double().abs()).all()
+    assert ((x - hi).abs() <= 2.0 ** -8 * x.abs()).all() and (lo.abs() <= 2.0 ** -8 * x.abs()).all()
+    assert hi[-2] == 256.0 and hi[-1] == 260.0                  # ties at 257 / 259 (bf16 step 2 there): to the even significand
+    hi2, lo2 = R.split_bf16(x.double())
+    assert torch.equal(hi2, hi) and torch.equal(lo2, lo)
+
+
+def test_conv_f16_and_conv_x3_are_the_conv_of_the_rounded_operands():
+    segs = R.seg_table(LENS)
+    x, w = rnd(sum(LENS), 16, seed=96).float(), rnd(16, 16, 7, seed=97, scale=0.1).float()
+    x[3] = 1e5
+    b, Rr = rnd(16, seed=98).float(), rnd(sum(LENS), 16, seed=99).float()
+    act = torch.maximum(x, x * 0.1)
+    want = R.conv(R.to_f16_sat(act).double(), R.to_f16_sat(w).double(), segs, 3, bias=b.double(), act_slope=0.1, R=Rr.double(), c2_slope=0.1)
+    got = R.conv_f16(x, w, segs, 3, in_slope=0.1, bias=b, act_slope=0.1, R=Rr, c2_slope=0.1)
+    same = lambda a_, b_: torch.allclose(a_, b_, rtol=1e-13, atol=1e-13, equal_nan=True)      # (seg_conv_packed: other matmul shapes)
+    assert got[0].dtype == torch.float64 and same(got[0], want[0]) and same(got[1], want[1])
+    gap = R.seg_table(LENS, start=3)                        # rows 0..2 and the tail belong to no utterance: NaN in both
+    xg = rnd(gap[-1][0] + gap[-1][1] + 2, 16, seed=90)
+    for taps, dil in [(1, 1), (3, 5), (4, 3), (11, 5)]:
+        wg = rnd(8, 16, taps, seed=89)
+        a_, b_ = R.seg_conv_packed(xg, wg, gap, dil), R.seg_conv(xg, wg, gap, dil)
+        assert same(a_, b_) and torch.equal(torch.isnan(a_), torch.isnan(b_)) and torch.isnan(a_[:3]).all()
+    f32 = R.conv_f16(x, w, segs, 3, in_slope=0.1, accum=torch.float32, bias=b, act_slope=0.1, R=Rr, c2_slope=0.1)
+    assert f32[0].dtype == torch.float32 and 0 < (f32[0].double() - got[0]).abs().max() < 1e-2       # (a row of 65504: f32 ulps of ~1e3)
+    assert not torch.isfinite(R.conv_f16(x, w, segs, 3, round_x=R.to_f16_noclamp)).all()
+    (ah, al), (wh, wl) = R.split_bf16(act), R.split_bf16(w)
+    c = lambda a_, w_: R.seg_conv(a_.double(), w_.double(), segs, 3)
+    assert same(R.conv_x3(x, w, segs, 3, in_slope=0.1), c(ah, wh) + c(al, wh) + c(ah, wl))
+    assert same(R.conv_x3(x, w, segs, 3, in_slope=0.1, terms=("hh", "ll")), c(ah, wh) + c(al, wl))
+    four = R.conv_x3(x, w, segs, 3, in_slope=0.1, terms=("hh", "hl", "lh", "ll"))
+    exact = R.seg_conv(act.double(), w.double(), segs, 3)
+    assert (four - exact).abs().max() < 2.0 ** -14 * exact.abs().max()      # hi + lo is x to 2^-16
+
+
+def separates(refs, what, bar_mutants=None):
+    """The condition that keeps a GPU bound of 16 E meaningful, on the references alone: the bar is under TOL and under half the
+    distance of every mutant reference, and the float32-accumulated reference itself passes the nearest-reference check."""
+    dist = {n: RC.err(m, refs.ref) for n, m in refs.mutants.items()}
+    near = RC.nearest(refs.f32, refs, refs.ref.shape[0])
+    print(f"{what}: E {refs.E:.3e} bar {refs.bar:.3e} mutants " + " ".join(f"[{n}: {v:.3e}]" for n, v in dist.items()))
+    assert 0 < refs.E and refs.bar < RC.TOL, f"{what}: bar {refs.bar}"
+    for n in bar_mutants or dist:
+        assert refs.bar < 0.5 * dist[n], f"{what}: the bar {refs.bar} does not separate the mutant '{n}' at {dist[n]}"
+    for n, (d0, dm) in near.items():
+        assert d0 < 0.5 * dm, f"{what}: the float32 reference is at {d0} from the reference, {dm} from the mutant '{n}'"
+
+
+F16_EDGE = [(Cc, k, d) for Cc in (64, 128, 256) for (k, d) in RC.KD]
+
+
+@pytest.mark.parametrize("Cc,k,d", F16_EDGE)
+def test_f16_bar_separates_the_mutants_on_the_edge_packs(Cc, k, d):
+    h = RC.f16_edge_case(Cc, k, d)
+    bm = RC.F16_BM[Cc]
+    assert h.lens[0] >= bm + 48 + (k - 1) * d and {1, 2, d - 1, d, d + 1, bm - 1, bm, bm + 1, 2 * bm + 3} <= set(h.lens)
+    for on in (False, True):
+        separates(RC.f16_refs(h, on), f"conv_f16 C={Cc} k={k} d={d} on={on}")
+
+
+@pytest.mark.parametrize("Cc,k,d,nseg", RC.SLICE_CASES)
+def test_f16_bar_separates_the_mutants_on_the_slice_packs(Cc, k, d, nseg):
+    h = RC.f16_slice_case(Cc, k, d, nseg)
+    assert len(h.segs) == nseg and h.M == sum(RC.short_lens(nseg))
+    for on in (False, True):
+        separates(RC.f16_refs(h, on), f"conv_f16 C={Cc} k={k} d={d} nseg={nseg} on={on}")
+
+
+def test_f16_unsegmented_and_lattice_references():
+    """The unsegmented launches' reference separates too; the lattice reference is one exact product per sum: R.conv_f16 on it equals,
+    bit for bit in float32, the product of the hand-written images -- no conv involved -- with the input activation off and on."""
+    for Cc in (64, 128, 256):
+        h = RC.f16_unsegmented_case(Cc)
+        assert h.M % RC.F16_BM[Cc] and len(h.segs) == 1
+        for on in (False, True):
+            separates(RC.f16_refs(h, on), f"conv_f16 C={Cc} unsegmented on={on}")
+    for Cc, k, d, sat in [(64, 11, 5, False), (128, 3, 1, True), (256, 11, 5, True)]:
+        h = RC.lattice_case(Cc, k, d, saturated_weights=sat)
+        assert set(h.src.unique().tolist()) == set(range(-1, len(RC.LATTICE)))        # every lattice point reaches an output
+        for slope in (None, 0.1):
+            ref, want = R.conv_f16(h.x, h.w, h.segs, d, in_slope=slope), RC.lattice_expected(h, slope)
+            assert torch.isfinite(ref).all() and torch.equal(ref.float().double(), ref)
+            assert torch.equal(ref.float().view(torch.int32), want.float().view(torch.int32))
+            assert torch.equal(R.conv_f16(h.x, h.w, h.segs, d, in_slope=slope, accum=torch.float32), ref.float())     # exact in float32
+
+
+def _x3_packs():
+    from test_sk_ops_gpu import SHAPES
+    return [(shape, pack) for shape in SHAPES for pack in ("edges", "short256", "short300")] + [((128, 256, 3, 1), "one utterance")]
+
+
+@pytest.mark.parametrize("shape,pack", _x3_packs(), ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else v.replace(" ", "_"))
+def test_x3_bar_separates_the_dropped_terms(shape, pack):
+    """Split-bf16: 16 E lies under half the distance of a dropped hl or lh term (~2^-9 of the output).  The ll term (~2^-17, about
+    1e-5) is nearer than 32 E: no bound separates it, so the GPU test compares distances instead (nearest reference), which the
+    float32-accumulated reference passes here for all three."""
+    from test_sk_ops_gpu import ROUTES, lens_of
+    cin, n, k, d = shape
+    lens = [4301] if pack == "one utterance" else lens_of(pack, ROUTES["conv_sk2_x3"]["bm"], d)
+    h = RC.host_data(cin, k, d, lens, 0, N=n)
+    for on, refs in RC.x3_refs(h).items():
+        separates(refs, f"conv_sk2_x3 {shape} {pack} on={on}", bar_mutants=("-hl", "-lh"))
