@@ -131,50 +131,45 @@ extern "C" int ss_batch_encoder_forward(ss_model* m, void* stream, int B, const 
   return SS_OK;
 }
 
+// The greedy search of a pack: the {offset, length} table of its utterances, the head, the masked arg-max, the collapse.  d_lprob
+// given (with d_last, d_tok_lprob): the same tables, head GEMM and CanonScope, the scored twins of the two glue kernels.
+static int batch_ctc_greedy(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int32_t* d_raw,
+                            int32_t* d_tokens, int32_t* d_index, int32_t* d_counts, float* d_lprob, int32_t* d_last,
+                            float* d_tok_lprob) {
+  SkScope sk_scope(m->sc->skws);
+  CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
+  hipStream_t s = (hipStream_t)stream;
+  const ss_config& c = m->cfg;
+  const Offsets o = prefix(h_Tp, B);
+  const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
+  RET(m->sc->mt_ws.ensure((size_t)o.total * V * sizeof(float)));
+  std::vector<int> tr(2 * B);
+  for (int b = 0; b < B; ++b) { tr[2 * b] = o.off[b]; tr[2 * b + 1] = h_Tp[b]; }
+  RET(m->sc->seg_buf.ensure(tr.size() * sizeof(int)));
+  int* segs = (int*)m->sc->seg_buf.p;
+  RET(upload(s, segs, tr));
+  float* logits = nullptr;
+  RET(ctc_head_logits(m, s, head, d_enc_out, c.enc_dim, o.total, true, &logits));
+  if (!d_lprob) {
+    RET(launch_masked_argmax(logits, V, o.total, V, c.pad, c.unk, -1, -1, d_raw, s));
+    return launch_ctc_collapse(d_raw, 0, 0, c.pad, d_tokens, d_index, d_counts, s, segs, B);
+  }
+  RET(launch_masked_argmax_lprob(logits, V, o.total, V, c.pad, c.unk, -1, d_raw, d_lprob, s));
+  return launch_ctc_collapse_spans(d_raw, d_lprob, 0, 0, c.pad, d_tokens, d_index, d_last, d_tok_lprob, d_counts, s, segs, B);
+}
+
 extern "C" int ss_batch_ctc_greedy(ss_model* m, void* stream, int head, int B, const float* d_enc_out,
                                    const int32_t* h_Tp, int32_t* d_raw, int32_t* d_tokens, int32_t* d_index,
                                    int32_t* d_counts) {
   if (!m || B <= 0 || head < 0 || head > 1) return SS_ERR_ARG;
-  SkScope sk_scope(m->sc->skws);
-  CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
-  hipStream_t s = (hipStream_t)stream;
-  const ss_config& c = m->cfg;
-  const Offsets o = prefix(h_Tp, B);
-  const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
-  RET(m->sc->mt_ws.ensure((size_t)o.total * V * sizeof(float)));
-  float* logits = m->sc->mt_ws.f();
-  std::vector<int> tr(2 * B);
-  for (int b = 0; b < B; ++b) { tr[2 * b] = o.off[b]; tr[2 * b + 1] = h_Tp[b]; }
-  RET(m->sc->seg_buf.ensure(tr.size() * sizeof(int)));
-  RET(upload(s, (int*)m->sc->seg_buf.p, tr));
-  RET(linear(s, d_enc_out, c.enc_dim, o.total, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, logits, V));
-  m->sc->dbg_logits = logits; m->sc->dbg_rows = o.total; m->sc->dbg_cols = V;
-  RET(launch_masked_argmax(logits, V, o.total, V, c.pad, c.unk, -1, -1, d_raw, s));
-  return launch_ctc_collapse(d_raw, 0, 0, c.pad, d_tokens, d_index, d_counts, s, (const int*)m->sc->seg_buf.p, B);
+  return batch_ctc_greedy(m, stream, head, B, d_enc_out, h_Tp, d_raw, d_tokens, d_index, d_counts, nullptr, nullptr, nullptr);
 }
 
-// ss_batch_ctc_greedy with scores: the same tables, head GEMM and CanonScope, the scored twins of the two glue kernels.
 extern "C" int ss_batch_ctc_greedy_scored(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp,
                                           int32_t* d_raw, int32_t* d_tokens, int32_t* d_index, int32_t* d_counts, float* d_lprob,
                                           int32_t* d_last, float* d_tok_lprob) {
   if (!m || B <= 0 || head < 0 || head > 1 || !d_lprob || !d_last || !d_tok_lprob) return SS_ERR_ARG;
-  SkScope sk_scope(m->sc->skws);
-  CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
-  hipStream_t s = (hipStream_t)stream;
-  const ss_config& c = m->cfg;
-  const Offsets o = prefix(h_Tp, B);
-  const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
-  RET(m->sc->mt_ws.ensure((size_t)o.total * V * sizeof(float)));
-  float* logits = m->sc->mt_ws.f();
-  std::vector<int> tr(2 * B);
-  for (int b = 0; b < B; ++b) { tr[2 * b] = o.off[b]; tr[2 * b + 1] = h_Tp[b]; }
-  RET(m->sc->seg_buf.ensure(tr.size() * sizeof(int)));
-  RET(upload(s, (int*)m->sc->seg_buf.p, tr));
-  RET(linear(s, d_enc_out, c.enc_dim, o.total, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, logits, V));
-  m->sc->dbg_logits = logits; m->sc->dbg_rows = o.total; m->sc->dbg_cols = V;
-  RET(launch_masked_argmax_lprob(logits, V, o.total, V, c.pad, c.unk, -1, d_raw, d_lprob, s));
-  return launch_ctc_collapse_spans(d_raw, d_lprob, 0, 0, c.pad, d_tokens, d_index, d_last, d_tok_lprob, d_counts, s,
-                                   (const int*)m->sc->seg_buf.p, B);
+  return batch_ctc_greedy(m, stream, head, B, d_enc_out, h_Tp, d_raw, d_tokens, d_index, d_counts, d_lprob, d_last, d_tok_lprob);
 }
 
 // Forced alignment of given labels on a text head: ss_batch_ctc_greedy_scored's head GEMM (the same linear, CanonScope and workspace),
@@ -195,9 +190,8 @@ extern "C" int ss_batch_ctc_align(ss_model* m, void* stream, int head, int B, co
   RET(m->sc->mt_ws.ensure((size_t)plan.rows * V * sizeof(float)));
   RET(m->sc->ws.ensure(plan.work_bytes()));
   RET(m->sc->seg_buf.ensure(ctc_align_table_bytes(plan)));
-  float* logits = m->sc->mt_ws.f();
-  RET(linear(s, d_enc_out, c.enc_dim, plan.rows, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, logits, V));
-  m->sc->dbg_logits = logits; m->sc->dbg_rows = plan.rows; m->sc->dbg_cols = V;
+  float* logits = nullptr;
+  RET(ctc_head_logits(m, s, head, d_enc_out, c.enc_dim, plan.rows, true, &logits));
   return launch_ctc_align(logits, V, V, plan, h_targets, m->sc->seg_buf.p, m->sc->ws.p, d_results, d_path, d_first, d_last, d_tok_lprob,
                           nullptr, s);
 }
@@ -234,48 +228,39 @@ int mt_decode_rows(ss_model* m, hipStream_t s, const MtRowsWs& w, const MtRowsSt
 
 // Prefix beam search on a text head: ss_batch_ctc_greedy_scored's head GEMM (the same linear, CanonScope and workspace), then the
 // two kernels of ctc_beam.hip.  Every refusal comes before the first launch; the tries, child tables and per-frame values live in
-// the encoder scratch (idle here: d_enc_out is the caller's), the table of the pack in the segment buffer.
-extern "C" int ss_batch_ctc_beam(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int beam,
-                                 int cand, int nbest, ss_ctc_beam_hyp* d_hyps, int32_t* d_tokens, int out_stride) {
+// the encoder scratch (idle here: d_enc_out is the caller's), the table of the pack in the segment buffer.  with_lm: an n-gram
+// model fused into the order (ctc_beam.hpp) -- the plain call's GEMM, scopes and buffers, 20 more bytes per trie node in the encoder
+// scratch; the model's refusals come with the plain ones, before the first launch.
+static int batch_ctc_beam(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int beam, int cand,
+                          int nbest, void* d_hyps, int32_t* d_tokens, int out_stride, bool with_lm, const ss_ngram_lm* lm,
+                          const ss_ctc_lm_opts* opts) {
   if (!m || B <= 0 || head < 0 || head > 1 || !d_enc_out || !h_Tp || !d_hyps || !d_tokens) return SS_ERR_ARG;
   const ss_config& c = m->cfg;
   const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
   CtcBeamPlan plan;
   RET(ctc_beam_plan(V, B, h_Tp, beam, cand, nbest, out_stride, plan));
+  if (with_lm) RET(ctc_beam_lm_check(lm, V, opts));
   SkScope sk_scope(m->sc->skws);
   CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
   hipStream_t s = (hipStream_t)stream;
   RET(m->sc->mt_ws.ensure((size_t)plan.rows * V * sizeof(float)));
-  RET(m->sc->ws.ensure(plan.work_bytes()));
+  RET(m->sc->ws.ensure(with_lm ? plan.work_bytes_lm() : plan.work_bytes()));
   RET(m->sc->seg_buf.ensure(ctc_beam_table_bytes(plan)));
-  float* logits = m->sc->mt_ws.f();
-  RET(linear(s, d_enc_out, c.enc_dim, plan.rows, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, logits, V));
-  m->sc->dbg_logits = logits; m->sc->dbg_rows = plan.rows; m->sc->dbg_cols = V;
-  return launch_ctc_beam(logits, V, V, c.pad, c.unk, plan, m->sc->seg_buf.p, m->sc->ws.p, d_hyps, d_tokens, out_stride, nullptr, nullptr, s);
+  float* logits = nullptr;
+  RET(ctc_head_logits(m, s, head, d_enc_out, c.enc_dim, plan.rows, true, &logits));
+  return launch_ctc_beam(logits, V, V, c.pad, c.unk, plan, m->sc->seg_buf.p, m->sc->ws.p, lm, opts, d_hyps, d_tokens, out_stride, nullptr,
+                         nullptr, s);
 }
 
-// The same with an n-gram model fused into the order (ctc_beam.hpp): the plain call's GEMM, scopes and buffers, 20 more bytes per
-// trie node in the encoder scratch; the model's refusals come with the plain ones, before the first launch.
+extern "C" int ss_batch_ctc_beam(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int beam,
+                                 int cand, int nbest, ss_ctc_beam_hyp* d_hyps, int32_t* d_tokens, int out_stride) {
+  return batch_ctc_beam(m, stream, head, B, d_enc_out, h_Tp, beam, cand, nbest, d_hyps, d_tokens, out_stride, false, nullptr, nullptr);
+}
+
 extern "C" int ss_batch_ctc_beam_lm(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int beam,
                                     int cand, int nbest, ss_ctc_beam_lm_hyp* d_hyps, int32_t* d_tokens, int out_stride,
                                     const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts) {
-  if (!m || B <= 0 || head < 0 || head > 1 || !d_enc_out || !h_Tp || !d_hyps || !d_tokens) return SS_ERR_ARG;
-  const ss_config& c = m->cfg;
-  const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
-  CtcBeamPlan plan;
-  RET(ctc_beam_plan(V, B, h_Tp, beam, cand, nbest, out_stride, plan));
-  RET(ctc_beam_lm_check(lm, V, opts));
-  SkScope sk_scope(m->sc->skws);
-  CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
-  hipStream_t s = (hipStream_t)stream;
-  RET(m->sc->mt_ws.ensure((size_t)plan.rows * V * sizeof(float)));
-  RET(m->sc->ws.ensure(plan.work_bytes_lm()));
-  RET(m->sc->seg_buf.ensure(ctc_beam_table_bytes(plan)));
-  float* logits = m->sc->mt_ws.f();
-  RET(linear(s, d_enc_out, c.enc_dim, plan.rows, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, logits, V));
-  m->sc->dbg_logits = logits; m->sc->dbg_rows = plan.rows; m->sc->dbg_cols = V;
-  return launch_ctc_beam_lm(logits, V, V, c.pad, c.unk, plan, m->sc->seg_buf.p, m->sc->ws.p, lm, opts, d_hyps, d_tokens, out_stride,
-                            nullptr, nullptr, s);
+  return batch_ctc_beam(m, stream, head, B, d_enc_out, h_Tp, beam, cand, nbest, d_hyps, d_tokens, out_stride, true, lm, opts);
 }
 
 // Batched beam-1 search: all utterances start from [</s>] and advance in lockstep, one row per

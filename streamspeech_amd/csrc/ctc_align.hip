@@ -11,21 +11,21 @@
 #include <cstring>
 
 #include "../../include/streamspeech_hip.h"
+#include "ctc_row.hpp"
 #include "elementwise.hpp"
 
 namespace ss {
 
-// One logits row per workgroup.  The denominator is masked_argmax_lprob_kernel's, operation for operation: an f32 max, each thread's
-// f32 sum of expf(x - max) in ascending stride, the xor-shuffle tree, the four wave partials in index order, one logf -- so the
-// suite's 2e-5 bound against the float64 log-softmax holds for every value written here, and a row's values are a function of that
-// row's bits and its utterance's labels alone.  lp[t][0] = blank, lp[t][1 + j] = label j; a row that holds a NaN gives NaN in
+// One logits row per workgroup.  The denominator is ctc_row.hpp's, the greedy search's and the beam search's -- so the suite's 2e-5
+// bound against the float64 log-softmax holds for every value written here, and a row's values are a function of that row's bits
+// and its utterance's labels alone.  lp[t][0] = blank, lp[t][1 + j] = label j; a row that holds a NaN gives NaN in
 // every column (as torch.log_softmax), which is how the trellis learns of it.
 __global__ __launch_bounds__(256) void ctc_align_lp_kernel(const float* __restrict__ logits, int ld, int N,
                                                            const CtcAlignSeg* __restrict__ segs, int B,
                                                            const int* __restrict__ labels, float* __restrict__ lp) {
   __shared__ float sm[4], ssum[4];
   __shared__ int sn[4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   const int row = blockIdx.x;
   int lo = 0, hi = B - 1;                                      // the utterance of this row: row0 ascends strictly (every T >= 1)
   while (lo < hi) {
@@ -34,22 +34,11 @@ __global__ __launch_bounds__(256) void ctc_align_lp_kernel(const float* __restri
   }
   const CtcAlignSeg sg = segs[lo];
   const float* r = logits + (size_t)row * ld;
-  float mx = -INFINITY;
-  int nan = 0;
-  for (int n = t; n < N; n += 256) { const float x = r[n]; nan |= (x != x); mx = fmaxf(mx, x); }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o, 64)); nan |= __shfl_xor(nan, o, 64); }
-  if (lane == 0) { sm[wave] = mx; sn[wave] = nan; }
-  __syncthreads();
-  mx = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-  float sum = 0.f;
-  for (int n = t; n < N; n += 256) sum += expf(r[n] - mx);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-  if (lane == 0) ssum[wave] = sum;
-  __syncthreads();
-  const float lt = logf(((ssum[0] + ssum[1]) + ssum[2]) + ssum[3]);
-  const bool bad = sn[0] | sn[1] | sn[2] | sn[3];
+  float v[1];                                                  // (the re-reading form: any N)
+  const float mx = ctc_row_max<0>(r, N, v, sm, sn);
+  ctc_row_expsum<0>(r, N, v, mx, ssum);
+  const float lt = ctc_row_logsum(ssum);
+  const bool bad = ctc_row_nan(sn);
   float* out = lp + sg.lp_off + (long long)(row - sg.row0) * (sg.L + 1);
   const int* y = labels + sg.lab0;
   for (int j = t; j <= sg.L; j += 256) out[j] = bad ? __builtin_nanf("") : (r[j ? y[j - 1] : 0] - mx) - lt;
@@ -191,29 +180,6 @@ int launch_ctc_align(const float* logits, int ld, int V, const CtcAlignPlan& p, 
   return SS_OK;
 }
 
-namespace {
-
-// The device kernel's denominator on the host, in the device's order: 256 strided partial sums, the xor tree inside each group of
-// 64, the four group sums in index order.
-void row_stats_host(const float* r, int N, float* mx_out, float* lt_out, bool* nan_out) {
-  float mx = -INFINITY;
-  bool nan = false;
-  for (int n = 0; n < N; ++n) { nan |= r[n] != r[n]; mx = fmaxf(mx, r[n]); }
-  float part[256], tmp[256];
-  for (int t = 0; t < 256; ++t) {
-    float s = 0.f;
-    for (int n = t; n < N; n += 256) s += expf(r[n] - mx);
-    part[t] = s;
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    for (int t = 0; t < 256; ++t) tmp[t] = part[t] + part[t ^ o];
-    memcpy(part, tmp, sizeof(part));
-  }
-  *mx_out = mx; *lt_out = logf(((part[0] + part[64]) + part[128]) + part[192]); *nan_out = nan;
-}
-
-}  // namespace
-
 }  // namespace ss
 
 using namespace ss;
@@ -223,8 +189,7 @@ extern "C" int ss_ctc_align_host(const float* h_logits, int ld, int V, int pad, 
                                  int32_t* h_last, float* h_tok_lprob, float* h_frame_lprob) {
   if (!h_logits || ld < V || !h_results) return SS_ERR_ARG;
   CtcAlignPlan p;
-  const int rc = ctc_align_plan(V, pad, B, h_T, h_targets, h_n_targets, p);
-  if (rc != SS_OK) return rc;
+  RET(ctc_align_plan(V, pad, B, h_T, h_targets, h_n_targets, p));
   if (p.labels > 0 && (!h_first || !h_last || !h_tok_lprob)) return SS_ERR_ARG;
   for (int b = 0; b < B; ++b) {
     const CtcAlignSeg& sg = p.segs[b];
@@ -234,8 +199,8 @@ extern "C" int ss_ctc_align_host(const float* h_logits, int ld, int V, int pad, 
     bool nan = false;
     for (int t = 0; t < T; ++t) {
       const float* r = h_logits + (size_t)(sg.row0 + t) * ld;
-      float mx, lt; bool bad;
-      row_stats_host(r, V, &mx, &lt, &bad);
+      float mx, lt;
+      const bool bad = ctc_row_den_host(r, V, &mx, &lt);
       for (int j = 0; j <= L; ++j) lp[(size_t)t * W + j] = bad ? __builtin_nanf("") : (r[j ? y[j - 1] : 0] - mx) - lt;
       nan |= lp[(size_t)t * W] != lp[(size_t)t * W];           // as the kernel learns of it: the blank column of the row
     }

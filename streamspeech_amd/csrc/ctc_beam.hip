@@ -5,8 +5,10 @@
 //                           logits among the unmasked non-blank columns
 //   ctc_beam_search_kernel  one workgroup per utterance, a loop over its frames: beam, candidates and merge state in LDS, the trie
 //                           of label strings and its child table in global scratch, the back-trace of the n-best at the end
-// plus the plain-C++ twin of both (ss_ctc_beam_host) over the same step code (ctc_beam.hpp, where the search and its order are
-// defined).  The search kernel and the twin each have an LM form (ctc_beam_search_lm_kernel, ss_ctc_beam_lm_host): the same body
+// The plain-C++ twin of both (ss_ctc_beam_host) is ctc_beam_host.hip; the search, its order and the frame -- passes B and C, node
+// creation, the back-trace, the LM finish -- are ctc_beam.hpp's, called by the body below and by the twin: this file keeps the loops
+// over 256 threads, the barriers, the rank walk and the slot writes of the next beam.
+// The search kernel and the twin each have an LM form (ctc_beam_search_lm_kernel, ss_ctc_beam_lm_host): the same body
 // with a back-off n-gram model (ngram_lm.hpp) fused into the order of a frame's entries.  And each of the four has a RESUMABLE form
 // (ctc_stream_search_kernel / _lm_kernel, ctc_stream_host_run; the object and its entry points: ctc_stream.hip): the same body
 // over a slot's state that outlives the launch, for the frames a call brings, with the stable prefix of the beam at the end.
@@ -17,6 +19,7 @@
 #include "ngram_lm.hpp"
 
 #include "../../include/streamspeech_hip.h"
+#include "ctc_row.hpp"
 #include "elementwise.hpp"
 
 namespace ss {
@@ -25,9 +28,8 @@ namespace {
 constexpr int NONE = 0x7fffffff;
 }
 
-// One logits row per workgroup.  den[row] = (max, log-sum) with masked_argmax_lprob_kernel's arithmetic, operation for operation:
-// an f32 max, each thread's f32 sum of expf(x - max) in ascending stride, the xor-shuffle tree, the four wave partials in index
-// order, one logf -- (NaN, NaN) for a row that holds a NaN.  cand_id[row][k]: the k-th column in the order (logit descending, id
+// One logits row per workgroup.  den[row] = (max, log-sum), the denominator of ctc_row.hpp -- (NaN, NaN) for a row that holds a
+// NaN.  cand_id[row][k]: the k-th column in the order (logit descending, id
 // ascending) among the columns that are not blank, pad or unk and whose logit is above -inf; -1 where there are fewer.  One round
 // of the block per candidate: every thread offers its best column that comes after the last winner in that order.
 // PER > 0: N <= 256 * PER, the row is read once and kept in registers; PER == 0: any N, every pass reads the row again.
@@ -39,43 +41,13 @@ __global__ __launch_bounds__(256) void ctc_beam_cand_kernel(const float* __restr
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int row = blockIdx.x;
   const float* r = logits + (size_t)row * ld;
-  float v[PER > 0 ? PER : 1];
-  float mx = -INFINITY;
-  int nan = 0;
-  if constexpr (PER > 0) {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int n = t + 256 * i;
-      v[i] = n < N ? r[n] : -INFINITY;                         // past the row: no maximum, exp(-inf - max) = 0, never a candidate
-      nan |= (v[i] != v[i]);
-      mx = fmaxf(mx, v[i]);
-    }
-  } else {
-    for (int n = t; n < N; n += 256) { const float x = r[n]; nan |= (x != x); mx = fmaxf(mx, x); }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o, 64)); nan |= __shfl_xor(nan, o, 64); }
-  if (lane == 0) { sm[wave] = mx; sn[wave] = nan; }
-  __syncthreads();
-  mx = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-  float sum = 0.f;
-  if constexpr (PER > 0) {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const float e = expf(v[i] - mx);
-      if (t + 256 * i < N) sum += e;
-    }
-  } else {
-    for (int n = t; n < N; n += 256) sum += expf(r[n] - mx);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-  if (lane == 0) ssum[wave] = sum;
-  __syncthreads();
+  float v[PER > 0 ? PER : 1];                                  // (a column past the row is -inf: never a candidate either)
+  const float mx = ctc_row_max<PER>(r, N, v, sm, sn);
+  ctc_row_expsum<PER>(r, N, v, mx, ssum);
   if (t == 0) {
-    const bool bad = sn[0] | sn[1] | sn[2] | sn[3];
+    const bool bad = ctc_row_nan(sn);
     den[2 * (size_t)row] = bad ? __builtin_nanf("") : mx;
-    den[2 * (size_t)row + 1] = bad ? __builtin_nanf("") : logf(((ssum[0] + ssum[1]) + ssum[2]) + ssum[3]);
+    den[2 * (size_t)row + 1] = bad ? __builtin_nanf("") : ctc_row_logsum(ssum);
   }
   // ---- the candidates: round k finds the k-th column of the order; (lv, li) is the winner of the round before ----
   float lv = INFINITY;
@@ -120,11 +92,10 @@ __global__ __launch_bounds__(256) void ctc_beam_cand_kernel(const float* __restr
 // the beam's size and the NaN exit are the same for all threads).
 //   A  the frame's values: lp of the blank, of the candidates and of every beam prefix's last label, as (x - max) - logsum from the
 //      row itself and the candidate kernel's den
-//   B  the entries e = r * (C + 1) + k (ctc_beam.hpp): a prefix's own stay terms; an extension's term and its node from the child
-//      table -- an extension whose node is in the beam hands its term to that prefix and dies
-//   C  each prefix's own entry: pnb' = logadd(stay, handed term), total = logadd(pb', pnb')
+//   B  the entries e = r * (C + 1) + k, a thread per entry (ctc_beam_entry_b)
+//   C  each prefix's own entry, a thread per prefix (ctc_beam_entry_c)
 //   D  every live entry counts the entries that come before it (ctc_beam_before); with fewer than `beam` of them it is the next
-//      beam's prefix of that rank, and makes its node if the string is new
+//      beam's prefix of that rank, and makes its node if the string is new (ctc_beam_make_node)
 // The two beams are addressed by an integer offset (0 | CTC_BEAM_MAX_BEAM), never through a pointer picked at run time (see
 // ctc_align_trellis_kernel).  Every operation of an utterance happens inside its own workgroup in an order that depends on its own
 // data alone (node ids are ctc_beam_new_node's, not a counter's; the child table's contents depend on the insertion order only in
@@ -182,6 +153,8 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
   const int mask = sg.tab_mask, W = C + 1;
   double* st_f64 = RES ? R.b_f64 + (size_t)se.slot * 4 * beam : nullptr;   // the stored beam of the slot
   int* st_i32 = RES ? R.b_i32 + (size_t)se.slot * (2 * beam + 2) : nullptr;
+  const CtcBeamFrame F{b_pb, b_pnb, b_tot, b_bonus, b_node, b_last, s_pb, s_pnb, s_give, e_tot, e_fus, e_node,
+                       s_c,  s_lpc, s_lpl, &s_lp0,  keys,   vals,   mask, n_bonus, n_state};
   bool bad = false;
   if (!RES || t0 == 0) {
     if (tid == 0) {
@@ -225,54 +198,10 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
     __syncthreads();
     // ---- B ----
     const int n_ent = nb * W;
-    for (int e = tid; e < n_ent; e += 256) {
-      const int i = e / W, k = e - i * W - 1;
-      const int node = b_node[co + i], last = b_last[co + i];
-      if (k < 0) {
-        double pb2, pnb2;
-        ctc_beam_stay(b_pnb[co + i], b_tot[co + i], last, s_lp0, s_lpl[i], &pb2, &pnb2);
-        s_pb[i] = pb2; s_pnb[i] = pnb2;
-        e_node[e] = node;                                      // (its total: pass C)
-        continue;
-      }
-      const int c = s_c[k];
-      double term = -INFINITY;
-      int child = -1;
-      if (c >= 0) {
-        term = ctc_beam_ext(b_pb[co + i], b_tot[co + i], last, c, s_lpc[k]);
-        child = ctc_beam_find(keys, vals, mask, node, c);
-        if (child >= 0) {
-          for (int j = 0; j < nb; ++j) {
-            if (b_node[co + j] == child) { s_give[j] = term; term = -INFINITY; break; }   // one parent per string: one writer per j
-          }
-        }
-      }
-      e_tot[e] = term;
-      e_node[e] = child;
-      if constexpr (LM) {
-        double fus = -INFINITY;
-        if (term > -INFINITY) {                                // (a dead entry needs no bonus: no lookup)
-          double bonus;
-          if (child >= 0) {
-            bonus = n_bonus[child];
-          } else {
-            int nx;
-            bonus = ngram_bonus(b_bonus[co + i], L.lm_weight, ngram_lp(L.lm, n_state[node], c, &nx), L.word_score);
-          }
-          fus = term + bonus;
-        }
-        e_fus[e] = fus;
-      }
-    }
+    for (int e = tid; e < n_ent; e += 256) ctc_beam_entry_b<LM>(F, co, nb, W, e, L.lm, L.lm_weight, L.word_score);
     __syncthreads();
     // ---- C ----
-    if (tid < nb) {
-      const double pnb2 = ctc_beam_logadd(s_pnb[tid], s_give[tid]);
-      s_pnb[tid] = pnb2;
-      const double tot = ctc_beam_logadd(s_pb[tid], pnb2);
-      e_tot[tid * W] = tot;
-      if constexpr (LM) e_fus[tid * W] = tot > -INFINITY ? tot + b_bonus[co + tid] : -INFINITY;
-    }
+    if (tid < nb) ctc_beam_entry_c<LM>(F, co, W, tid);
     __syncthreads();
     // ---- D ---- (a thread's up to PER entries count in ONE walk over the frame's totals: each total is read once per thread,
     //               and no exit depends on a count, so the loads of the unrolled walk overlap)
@@ -307,21 +236,9 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
         if constexpr (LM) b_bonus[no + rank] = b_bonus[co + i];
       } else {
         const int c = s_c[k];
-        if (node < 0) {                                        // a new string: its node, then its place in the child table
-          node = ctc_beam_new_node(t, beam, rank);
-          nodes[node] = make_int2(b_node[co + i], c);
-          if constexpr (LM) {                                  // its LM fields, written once (the lookup of pass B again)
-            int nx;
-            const double lp = ngram_lp(L.lm, n_state[b_node[co + i]], c, &nx);
-            n_state[node] = nx;
-            n_sum[node] = n_sum[b_node[co + i]] + lp;
-            n_bonus[node] = ngram_bonus(b_bonus[co + i], L.lm_weight, lp, L.word_score);
-          }
-          const unsigned long long key = ctc_beam_key(b_node[co + i], c);
-          for (int s = ctc_beam_slot(key, mask), n = 0; n <= mask; ++n, s = (s + 1) & mask) {
-            if (atomicCAS(&keys[s], CTC_BEAM_EMPTY, key) == CTC_BEAM_EMPTY) { vals[s] = node; break; }
-          }
-        }
+        if (node < 0)                                          // a new string
+          node = ctc_beam_make_node<LM>(t, beam, rank, b_node[co + i], c, LM ? b_bonus[co + i] : 0.0, keys, vals, mask, nodes, n_sum,
+                                        n_bonus, n_state, L.lm, L.lm_weight, L.word_score);
         b_pb[no + rank] = -INFINITY; b_pnb[no + rank] = tot; b_last[no + rank] = c;
         if constexpr (LM) b_bonus[no + rank] = n_bonus[node];
       }
@@ -350,13 +267,8 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
       h.n_tokens = 0;
       h.status = bad ? 2 : 1;
       if (tid < nb) {
-        const int node = b_node[cur * MB + tid];
-        int len = 0;
-        for (int n = node; n > 0; n = nodes[n].x) ++len;
-        int* out = tokens + ((size_t)blockIdx.x * nbest + tid) * out_stride;
-        int j = len;
-        for (int n = node; n > 0 && j > 0; n = nodes[n].x) out[--j] = nodes[n].y;
-        h.score = b_tot[cur * MB + tid]; h.n_tokens = len; h.status = 0;
+        h.n_tokens = ctc_beam_trace(nodes, b_node[cur * MB + tid], tokens + ((size_t)blockIdx.x * nbest + tid) * out_stride);
+        h.score = b_tot[cur * MB + tid]; h.status = 0;
       }
       hyps[(size_t)blockIdx.x * nbest + tid] = h;
     }
@@ -368,15 +280,8 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
     double fin = -INFINITY, lm_sum = 0.0;
     if (tid < nb) {
       const int node = b_node[cur * MB + tid];
-      const double fused = b_tot[cur * MB + tid] + b_bonus[cur * MB + tid];
-      lm_sum = n_sum[node];
-      fin = fused;
-      if (L.eos_term && (!RES || se.fin)) {
-        int nx;
-        const double lp = ngram_lp(L.lm, n_state[node], L.lm.eos, &nx);
-        fin = ngram_finish(fused, L.lm_weight, lp);
-        lm_sum += lp;
-      }
+      ctc_beam_finish(b_tot[cur * MB + tid], b_bonus[cur * MB + tid], n_sum[node], n_state[node],
+                      L.eos_term && (!RES || se.fin) ? L.lm.eos : -1, L.lm, L.lm_weight, &fin, &lm_sum);
       s_give[tid] = fin;
     }
     __syncthreads();
@@ -384,14 +289,9 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
       int rank = 0;
       for (int f = 0; f < nb; ++f) rank += ctc_beam_before(s_give[f], f, fin, tid);
       if (rank < nbest) {
-        const int node = b_node[cur * MB + tid];
-        int len = 0;
-        for (int n = node; n > 0; n = nodes[n].x) ++len;
-        int* out = tokens + ((size_t)blockIdx.x * nbest + rank) * out_stride;
-        int j = len;
-        for (int n = node; n > 0 && j > 0; n = nodes[n].x) out[--j] = nodes[n].y;
         ss_ctc_beam_lm_hyp h;
-        h.score = fin; h.ctc_score = b_tot[cur * MB + tid]; h.lm_score = lm_sum; h.n_tokens = len; h.status = 0;
+        h.n_tokens = ctc_beam_trace(nodes, b_node[cur * MB + tid], tokens + ((size_t)blockIdx.x * nbest + rank) * out_stride);
+        h.score = fin; h.ctc_score = b_tot[cur * MB + tid]; h.lm_score = lm_sum; h.status = 0;
         hyps[(size_t)blockIdx.x * nbest + rank] = h;
       }
     } else if (tid < nbest) {                                  // an empty slot
@@ -408,16 +308,7 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
     const int nb = bad ? 0 : s_nb[cur];
     if (tid == 0) s_stable = NONE;
     __syncthreads();
-    if (tid < nb) {
-      int a = b_node[cur * MB + tid], b = b_node[cur * MB];
-      int da = 0, db = 0;
-      for (int n = a; n > 0; n = nodes[n].x) ++da;
-      for (int n = b; n > 0; n = nodes[n].x) ++db;
-      for (; da > db; --da) a = nodes[a].x;
-      for (; db > da; --db) b = nodes[b].x;
-      for (; a != b; --da) { a = nodes[a].x; b = nodes[b].x; }
-      atomicMin(&s_stable, da);
-    }
+    if (tid < nb) atomicMin(&s_stable, ctc_beam_lca_depth(nodes, b_node[cur * MB + tid], b_node[cur * MB]));
     __syncthreads();
     if (tid == 0) R.part[blockIdx.x] = CtcStreamPart{se.upto, nb > 0 ? s_stable : 0, nb, bad ? 2 : 0};
   }
@@ -457,13 +348,6 @@ __global__ __launch_bounds__(256) void ctc_stream_search_lm_kernel(const float* 
 
 size_t ctc_beam_table_bytes(const CtcBeamPlan& p) { return p.segs.size() * sizeof(CtcBeamSeg); }
 
-// What an LM call is refused for past the plain refusals, before anything is launched or written.
-int ctc_beam_lm_check(const ss_ngram_lm* lm, int V, const ss_ctc_lm_opts* o) {
-  if (!lm || !o || lm->host.V != V || !std::isfinite(o->lm_weight) || !std::isfinite(o->word_score)) return SS_ERR_ARG;
-  if (o->eos_term && lm->host.eos < 0) return SS_ERR_ARG;
-  return SS_OK;
-}
-
 static int launch_ctc_beam_cand(const float* logits, int ld, int V, int pad, int unk, int rows, int C, float* den, int* cand,
                                 hipStream_t stream) {
 #define SS_CBC(PER) \
@@ -480,9 +364,9 @@ static int launch_ctc_beam_cand(const float* logits, int ld, int V, int pad, int
 
 // lm == nullptr: the plain search, hyps an ss_ctc_beam_hyp array; else the LM form (d_work holds plan.work_bytes_lm()), hyps an
 // ss_ctc_beam_lm_hyp array.
-static int launch_ctc_beam_any(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
-                               const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, void* hyps, int* tokens, int out_stride,
-                               float* den_out, int* cand_out, hipStream_t stream) {
+int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
+                    const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, void* hyps, int* tokens, int out_stride, float* den_out,
+                    int* cand_out, hipStream_t stream) {
   const int B = (int)p.segs.size();
   if (!logits || ld < V || B <= 0 || !d_table || !d_work || !hyps || !tokens) return SS_ERR_ARG;
   CtcBeamLm L{};
@@ -517,19 +401,6 @@ static int launch_ctc_beam_any(const float* logits, int ld, int V, int pad, int 
   return SS_OK;
 }
 
-int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
-                    ss_ctc_beam_hyp* hyps, int* tokens, int out_stride, float* den_out, int* cand_out, hipStream_t stream) {
-  return launch_ctc_beam_any(logits, ld, V, pad, unk, p, d_table, d_work, nullptr, nullptr, hyps, tokens, out_stride, den_out, cand_out,
-                             stream);
-}
-
-int launch_ctc_beam_lm(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
-                       const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, ss_ctc_beam_lm_hyp* hyps, int* tokens, int out_stride,
-                       float* den_out, int* cand_out, hipStream_t stream) {
-  if (!lm) return SS_ERR_ARG;
-  return launch_ctc_beam_any(logits, ld, V, pad, unk, p, d_table, d_work, lm, opts, hyps, tokens, out_stride, den_out, cand_out, stream);
-}
-
 int launch_ctc_stream(const float* logits, int ld, int V, int pad, int unk, int rows, int n, const CtcStreamSess* h_sess, void* d_sess,
                       float* den, int* cand_id, int beam, int C, int nbest, CtcStreamDev dev, const ss_ngram_lm* lm,
                       const ss_ctc_lm_opts* opts, void* hyps, int* tokens, int out_stride, CtcStreamPart* part, hipStream_t stream) {
@@ -551,314 +422,4 @@ int launch_ctc_stream(const float* logits, int ld, int V, int pad, int unk, int 
   return SS_OK;
 }
 
-namespace {
-
-int g_host_max_beam = CTC_BEAM_MAX_BEAM;      // ss_debug_ctc_beam_host_max: the host twin's cap alone (the exhaustive test)
-
-// ctc_beam_cand_kernel's denominator on the host, in the device's order (ctc_align.hip: row_stats_host).
-void row_den_host(const float* r, int N, float* den) {
-  float mx = -INFINITY;
-  bool nan = false;
-  for (int n = 0; n < N; ++n) { nan |= r[n] != r[n]; mx = fmaxf(mx, r[n]); }
-  float part[256], tmp[256];
-  for (int t = 0; t < 256; ++t) {
-    float s = 0.f;
-    for (int n = t; n < N; n += 256) s += expf(r[n] - mx);
-    part[t] = s;
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    for (int t = 0; t < 256; ++t) tmp[t] = part[t] + part[t ^ o];
-    memcpy(part, tmp, sizeof(part));
-  }
-  den[0] = nan ? __builtin_nanf("") : mx;
-  den[1] = nan ? __builtin_nanf("") : logf(((part[0] + part[64]) + part[128]) + part[192]);
-}
-
-void row_cand_host(const float* r, int N, int pad, int unk, int C, int* out) {
-  float lv = INFINITY;
-  int li = -1;
-  for (int k = 0; k < C; ++k) {
-    float bv = -INFINITY;
-    int bi = NONE;
-    for (int n = 1; n < N; ++n) {
-      const float x = r[n];
-      if (n == pad || n == unk || !(x > -INFINITY) || !(x < lv || (x == lv && n > li))) continue;
-      if (bi == NONE || x > bv) { bv = x; bi = n; }
-    }
-    out[k] = bi == NONE ? -1 : bi;
-    lv = bi == NONE ? -INFINITY : bv;
-    li = bi;
-  }
-}
-
-}  // namespace
-
 }  // namespace ss
-
-using namespace ss;
-
-extern "C" int ss_debug_ctc_beam_host_max(int max_beam) {
-  const int was = g_host_max_beam;
-  if (max_beam >= 1) g_host_max_beam = max_beam;
-  return was;
-}
-
-// ---- the twin of both forms, in three steps over one utterance's state (CtcBeamHostState, ctc_beam.hpp) so that the one-shot twins
-// (start, all frames, emit) and the resumable twin (ss_ctc_stream_advance_host: start at a reset, some frames and an emit per
-// call) are one statement of the search.  LM = false: lv / lw / ws unused, records ss_ctc_beam_hyp. ----
-namespace ss {
-
-void CtcBeamHostState::start(int beam, int max_T, bool lm, int lm_start) {
-  long long slots = ctc_stream_slots(beam, max_T);
-  mask = (int)(slots - 1);
-  const size_t nodes = 1 + (size_t)beam * max_T;
-  keys.assign((size_t)slots, CTC_BEAM_EMPTY);
-  vals.assign((size_t)slots, -1);
-  par.assign(nodes, -1); tok.assign(nodes, -1);
-  if (lm) { n_sum.assign(nodes, 0.0); n_bonus.assign(nodes, 0.0); n_state.assign(nodes, 0); n_state[0] = lm_start; }
-  bm.assign(1, CtcBeamHostPre{0.0, -INFINITY, 0.0, 0, -1, 0.0});
-  frames = 0; bad = false;
-}
-
-// The frames S.frames .. S.frames + n - 1 from the n rows at `rows`; h_den [n][2] / h_cand [n][C] (may be NULL) receive the
-// candidate kernel's values of every one of them, whatever the search makes of it.
-template <bool LM>
-static void ctc_beam_host_frames(CtcBeamHostState& S, const float* rows, int ld, int V, int pad, int unk, int n, int beam, int C,
-                                 const NgramView& lv, double lw, double ws, float* h_den, int32_t* h_cand_id) {
-  const int W = C + 1, mask = S.mask;
-  std::vector<unsigned long long>& keys = S.keys;
-  std::vector<int>&vals = S.vals, &par = S.par, &tok = S.tok, &n_state = S.n_state;
-  std::vector<double>&n_sum = S.n_sum, &n_bonus = S.n_bonus;
-  std::vector<CtcBeamHostPre>& bm = S.bm;
-  typedef CtcBeamHostPre Pre;
-  std::vector<Pre> nx;
-  std::vector<double> e_tot, s_pb, s_pnb, s_give, e_fus;
-  std::vector<int> e_node, cid_all((size_t)n * C);
-  std::vector<float> den_all(2 * (size_t)n);
-  for (int i = 0; i < n; ++i) {                                // the candidate kernel: every row, whatever the search makes of it
-    const float* r = rows + (size_t)i * ld;
-    row_den_host(r, V, &den_all[2 * (size_t)i]);
-    row_cand_host(r, V, pad, unk, C, &cid_all[(size_t)i * C]);
-  }
-  if (h_den && n > 0) memcpy(h_den, den_all.data(), den_all.size() * sizeof(float));
-  if (h_cand_id && n > 0) memcpy(h_cand_id, cid_all.data(), cid_all.size() * sizeof(int));
-  const int f0 = S.frames;
-  S.frames += n;
-  for (int t = f0; t < f0 + n && !S.bad; ++t) {
-    const float* r = rows + (size_t)(t - f0) * ld;
-    const float* den = &den_all[2 * (size_t)(t - f0)];
-    const int* cid = &cid_all[(size_t)(t - f0) * C];
-    if (den[1] != den[1]) { S.bad = true; break; }
-    const int nb = (int)bm.size(), n_ent = nb * W;
-    const float lp0 = ctc_beam_lp(r[0], den[0], den[1]);
-    e_tot.assign(n_ent, -INFINITY); e_node.assign(n_ent, -1);
-    if constexpr (LM) e_fus.assign(n_ent, -INFINITY);
-    s_pb.assign(nb, -INFINITY); s_pnb.assign(nb, -INFINITY); s_give.assign(nb, -INFINITY);
-    for (int e = 0; e < n_ent; ++e) {                          // B
-      const int i = e / W, k = e - i * W - 1;
-      const Pre& q = bm[i];
-      if (k < 0) {
-        ctc_beam_stay(q.pnb, q.tot, q.last, lp0, q.last >= 0 ? ctc_beam_lp(r[q.last], den[0], den[1]) : -INFINITY, &s_pb[i], &s_pnb[i]);
-        e_node[e] = q.node;
-        continue;
-      }
-      const int c = cid[k];
-      if (c < 0) continue;
-      double term = ctc_beam_ext(q.pb, q.tot, q.last, c, ctc_beam_lp(r[c], den[0], den[1]));
-      const int child = ctc_beam_find(keys.data(), vals.data(), mask, q.node, c);
-      if (child >= 0) {
-        for (int j = 0; j < nb; ++j) {
-          if (bm[j].node == child) { s_give[j] = term; term = -INFINITY; break; }
-        }
-      }
-      e_tot[e] = term; e_node[e] = child;
-      if constexpr (LM) {
-        if (term > -INFINITY) {
-          int st;
-          const double bonus = child >= 0 ? n_bonus[child] : ngram_bonus(q.bonus, lw, ngram_lp(lv, n_state[q.node], c, &st), ws);
-          e_fus[e] = term + bonus;
-        }
-      }
-    }
-    for (int i = 0; i < nb; ++i) {                             // C
-      s_pnb[i] = ctc_beam_logadd(s_pnb[i], s_give[i]);
-      e_tot[i * W] = ctc_beam_logadd(s_pb[i], s_pnb[i]);
-      if constexpr (LM) e_fus[i * W] = e_tot[i * W] > -INFINITY ? e_tot[i * W] + bm[i].bonus : -INFINITY;
-    }
-    const std::vector<double>& e_key = LM ? e_fus : e_tot;     // what the order compares
-    nx.assign(beam, Pre{0, 0, 0, -1, -1, 0.0});                // D
-    int alive = 0;
-    for (int e = 0; e < n_ent; ++e) {
-      const double tot = e_tot[e], key = e_key[e];
-      if (!(key > -INFINITY)) continue;
-      int rank = 0;
-      for (int f = 0; f < n_ent && rank < beam; ++f) rank += ctc_beam_before(e_key[f], f, key, e);
-      if (rank >= beam) continue;
-      const int i = e / W, k = e - i * W - 1;
-      int node = e_node[e];
-      if (k < 0) {
-        nx[rank] = Pre{s_pb[i], s_pnb[i], tot, node, bm[i].last, bm[i].bonus};
-      } else {
-        const int c = cid[k];
-        if (node < 0) {
-          node = ctc_beam_new_node(t, beam, rank);
-          par[node] = bm[i].node; tok[node] = c;
-          if constexpr (LM) {
-            int st;
-            const double lp = ngram_lp(lv, n_state[bm[i].node], c, &st);
-            n_state[node] = st; n_sum[node] = n_sum[bm[i].node] + lp; n_bonus[node] = ngram_bonus(bm[i].bonus, lw, lp, ws);
-          }
-          const unsigned long long key = ctc_beam_key(bm[i].node, c);
-          for (int s = ctc_beam_slot(key, mask), n = 0; n <= mask; ++n, s = (s + 1) & mask) {
-            if (keys[s] == CTC_BEAM_EMPTY) { keys[s] = key; vals[s] = node; break; }
-          }
-        }
-        nx[rank] = Pre{-INFINITY, tot, tot, node, c, LM ? n_bonus[node] : 0.0};
-      }
-      if (rank + 1 > alive) alive = rank + 1;
-    }
-    nx.resize(alive);
-    bm.swap(nx);
-  }
-}
-
-// The n-best of the beam as it stands: h_hyps_b [nbest] records and h_tokens_b [nbest][out_stride] of this utterance.  eos: the LM
-// form's eos term.
-template <bool LM>
-static void ctc_beam_host_emit(const CtcBeamHostState& S, int nbest, bool eos, const NgramView& lv, double lw, void* h_hyps_b,
-                               int32_t* h_tokens_b, int out_stride) {
-  const std::vector<CtcBeamHostPre>& bm = S.bm;
-  const std::vector<int>&par = S.par, &tok = S.tok;
-  const bool bad = S.bad;
-  if constexpr (!LM) {
-    ss_ctc_beam_hyp* h_hyps = static_cast<ss_ctc_beam_hyp*>(h_hyps_b);
-    for (int k = 0; k < nbest; ++k) {
-      ss_ctc_beam_hyp& h = h_hyps[k];
-      h.score = bad ? (double)__builtin_nanf("") : -INFINITY; h.n_tokens = 0; h.status = bad ? 2 : 1;
-      if (bad || k >= (int)bm.size()) continue;
-      int len = 0;
-      for (int n = bm[k].node; n > 0; n = par[n]) ++len;
-      int32_t* out = h_tokens_b + (size_t)k * out_stride;
-      int j = len;
-      for (int n = bm[k].node; n > 0; n = par[n]) out[--j] = tok[n];
-      h.score = bm[k].tot; h.n_tokens = len; h.status = 0;
-    }
-  } else {
-    ss_ctc_beam_lm_hyp* h_hyps = static_cast<ss_ctc_beam_lm_hyp*>(h_hyps_b);
-    const int nb = bad ? 0 : (int)bm.size();
-    std::vector<double> fin(nb), lms(nb);
-    for (int r = 0; r < nb; ++r) {
-      const double fused = bm[r].tot + bm[r].bonus;
-      fin[r] = fused; lms[r] = S.n_sum[bm[r].node];
-      if (eos) {
-        int st;
-        const double lp = ngram_lp(lv, S.n_state[bm[r].node], lv.eos, &st);
-        fin[r] = ngram_finish(fused, lw, lp); lms[r] += lp;
-      }
-    }
-    for (int k = nb; k < nbest; ++k) {
-      ss_ctc_beam_lm_hyp& h = h_hyps[k];
-      h.score = h.ctc_score = bad ? (double)__builtin_nanf("") : -INFINITY; h.lm_score = 0.0; h.n_tokens = 0; h.status = bad ? 2 : 1;
-    }
-    for (int r = 0; r < nb; ++r) {
-      int rank = 0;
-      for (int f = 0; f < nb; ++f) rank += ctc_beam_before(fin[f], f, fin[r], r);
-      if (rank >= nbest) continue;
-      ss_ctc_beam_lm_hyp& h = h_hyps[rank];
-      int len = 0;
-      for (int n = bm[r].node; n > 0; n = par[n]) ++len;
-      int32_t* out = h_tokens_b + (size_t)rank * out_stride;
-      int j = len;
-      for (int n = bm[r].node; n > 0; n = par[n]) out[--j] = tok[n];
-      h.score = fin[r]; h.ctc_score = bm[r].tot; h.lm_score = lms[r]; h.n_tokens = len; h.status = 0;
-    }
-  }
-}
-
-// The stable-prefix pass of the resumable kernel: the smallest depth of the lowest common ancestor of a beam prefix and prefix 0.
-static CtcStreamPart ctc_beam_host_part(const CtcBeamHostState& S) {
-  const int nb = S.bad ? 0 : (int)S.bm.size();
-  int stable = nb > 0 ? NONE : 0;
-  for (int r = 0; r < nb; ++r) {
-    int a = S.bm[r].node, b = S.bm[0].node, da = 0, db = 0;
-    for (int n = a; n > 0; n = S.par[n]) ++da;
-    for (int n = b; n > 0; n = S.par[n]) ++db;
-    for (; da > db; --da) a = S.par[a];
-    for (; db > da; --db) b = S.par[b];
-    for (; a != b; --da) { a = S.par[a]; b = S.par[b]; }
-    if (da < stable) stable = da;
-  }
-  return CtcStreamPart{S.frames, stable, nb, S.bad ? 2 : 0};
-}
-
-}  // namespace ss
-
-template <bool LM>
-static int ctc_beam_host_any(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
-                             int nbest, const ss_ngram_lm* lm, const ss_ctc_lm_opts* o, void* h_hyps_out, int32_t* h_tokens,
-                             int out_stride, float* h_den, int32_t* h_cand_id) {
-  if (!h_logits || ld < V || !h_hyps_out || !h_tokens) return SS_ERR_ARG;
-  CtcBeamPlan p;
-  const int rc = ctc_beam_plan(V, B, h_T, beam, cand, nbest, out_stride, p, g_host_max_beam);
-  if (rc != SS_OK) return rc;
-  NgramView lv{};
-  double lw = 0.0, ws = 0.0;
-  if constexpr (LM) {
-    RET(ctc_beam_lm_check(lm, V, o));
-    lv = lm->host.view(); lw = o->lm_weight; ws = o->word_score;
-  }
-  const size_t rec = LM ? sizeof(ss_ctc_beam_lm_hyp) : sizeof(ss_ctc_beam_hyp);
-  CtcBeamHostState S;
-  for (int b = 0; b < B; ++b) {
-    const CtcBeamSeg& sg = p.segs[b];
-    S.start(beam, sg.T, LM, lv.start);
-    ctc_beam_host_frames<LM>(S, h_logits + (size_t)sg.row0 * ld, ld, V, pad, unk, sg.T, beam, cand, lv, lw, ws,
-                             h_den ? h_den + 2 * (size_t)sg.row0 : nullptr, h_cand_id ? h_cand_id + (size_t)sg.row0 * cand : nullptr);
-    ctc_beam_host_emit<LM>(S, nbest, LM && o->eos_term, lv, lw, static_cast<unsigned char*>(h_hyps_out) + (size_t)b * nbest * rec,
-                           h_tokens + (size_t)b * nbest * out_stride, out_stride);
-  }
-  return SS_OK;
-}
-
-// The resumable twin: every pointer a HOST pointer, h_logits the stacked new rows (session i's upto - f rows behind those of the
-// sessions before it).  The checks are the caller's (ss_ctc_stream_advance_host, ctc_stream.hip).
-namespace ss {
-int ctc_stream_host_run(std::vector<CtcBeamHostState>& slots, const float* h_logits, int ld, int V, int pad, int unk, int n,
-                        const CtcStreamSess* sess, int beam, int cand, int nbest, const ss_ngram_lm* lm, const ss_ctc_lm_opts* o,
-                        void* h_hyps, int32_t* h_tokens, int out_stride, CtcStreamPart* h_part) {
-  NgramView lv{};
-  double lw = 0.0, ws = 0.0;
-  if (lm) { lv = lm->host.view(); lw = o->lm_weight; ws = o->word_score; }
-  const size_t rec = lm ? sizeof(ss_ctc_beam_lm_hyp) : sizeof(ss_ctc_beam_hyp);
-  for (int i = 0; i < n; ++i) {
-    const CtcStreamSess& se = sess[i];
-    CtcBeamHostState& S = slots[se.slot];
-    const float* rows = h_logits + (size_t)se.row0 * ld;
-    unsigned char* hy = static_cast<unsigned char*>(h_hyps) + (size_t)i * nbest * rec;
-    int32_t* tk = h_tokens + (size_t)i * nbest * out_stride;
-    if (lm) {
-      ctc_beam_host_frames<true>(S, rows, ld, V, pad, unk, se.upto - se.f, beam, cand, lv, lw, ws, nullptr, nullptr);
-      ctc_beam_host_emit<true>(S, nbest, se.fin && o->eos_term, lv, lw, hy, tk, out_stride);
-    } else {
-      ctc_beam_host_frames<false>(S, rows, ld, V, pad, unk, se.upto - se.f, beam, cand, lv, lw, ws, nullptr, nullptr);
-      ctc_beam_host_emit<false>(S, nbest, false, lv, lw, hy, tk, out_stride);
-    }
-    h_part[i] = ctc_beam_host_part(S);
-  }
-  return SS_OK;
-}
-}  // namespace ss
-
-extern "C" int ss_ctc_beam_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
-                                int nbest, ss_ctc_beam_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den,
-                                int32_t* h_cand_id) {
-  return ctc_beam_host_any<false>(h_logits, ld, V, pad, unk, B, h_T, beam, cand, nbest, nullptr, nullptr, h_hyps, h_tokens, out_stride,
-                                  h_den, h_cand_id);
-}
-
-extern "C" int ss_ctc_beam_lm_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
-                                   int nbest, ss_ctc_beam_lm_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den,
-                                   int32_t* h_cand_id, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts) {
-  return ctc_beam_host_any<true>(h_logits, ld, V, pad, unk, B, h_T, beam, cand, nbest, lm, opts, h_hyps, h_tokens, out_stride, h_den,
-                                 h_cand_id);
-}

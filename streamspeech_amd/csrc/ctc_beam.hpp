@@ -1,5 +1,6 @@
-// CTC prefix beam search on the two text heads (ctc_beam.hip): what the device search and its host twin (ss_ctc_beam_host) share --
-// the limits, the argument checks, the table of a ragged pack, the trie's child lookup and the step code.
+// CTC prefix beam search on the two text heads: what the device search (ctc_beam.hip) and its host twin (ctc_beam_host.hip) share --
+// the limits, the argument checks, the table of a ragged pack, the trie's child lookup, the step code and the frame: passes B and
+// C, node creation, the back-trace, the LM finish and the stable-prefix depth are stated here once and called by both.
 //
 // A hypothesis is a label string (blank = 0 never in it).  Its state is two float64 numbers: pb, the log-probability of all its
 // alignments that end in blank, and pnb, of those that end in its last label.  Per frame, with tot = logadd(pb, pnb) and lp the
@@ -67,6 +68,14 @@ struct CtcBeamPlan {
   size_t work_bytes_lm() const { return lm_off() + (size_t)nodes * 20; }
 };
 
+// The sizes of one trie of T frames (an utterance of a pack, or a slot of the resumable form made for T = max_frames).
+inline long long ctc_stream_nodes(int beam, int T) { return 1 + (long long)beam * T; }
+inline long long ctc_stream_slots(int beam, int T) {
+  long long slots = 2;
+  while (slots < 2LL * beam * T) slots *= 2;
+  return slots;
+}
+
 // Every refusal of the three entry points past their pointers, before anything is launched or written: B <= 0, a beam / cand
 // outside [1, max_beam] / [1, CTC_BEAM_MAX_CAND], nbest outside [1, beam], a T outside [1, CTC_BEAM_MAX_T], out_stride < max T.
 inline int ctc_beam_plan(int V, int B, const int32_t* h_T, int beam, int cand, int nbest, int out_stride, CtcBeamPlan& p,
@@ -78,10 +87,9 @@ inline int ctc_beam_plan(int V, int B, const int32_t* h_T, int beam, int cand, i
   for (int b = 0; b < B; ++b) {
     const int T = h_T[b];
     if (T < 1 || T > CTC_BEAM_MAX_T || out_stride < T) return SS_ERR_ARG;
-    long long slots = 2;
-    while (slots < 2LL * beam * T) slots *= 2;
+    const long long slots = ctc_stream_slots(beam, T);
     p.segs[b] = CtcBeamSeg{p.nodes, p.slots, p.rows, T, (int)(slots - 1), 0};
-    p.nodes += 1 + (long long)beam * T;
+    p.nodes += ctc_stream_nodes(beam, T);
     p.slots += slots;
     p.rows += T;
     if (T > p.max_T) p.max_T = T;
@@ -118,12 +126,6 @@ struct CtcStreamDev {
   CtcStreamPart* part;
 };
 
-inline long long ctc_stream_slots(int beam, int max_frames) {
-  long long slots = 2;
-  while (slots < 2LL * beam * max_frames) slots *= 2;
-  return slots;
-}
-inline long long ctc_stream_nodes(int beam, int max_frames) { return 1 + (long long)beam * max_frames; }
 // The bytes of one slot, the header's figure: 12 per table slot, 8 per node (28 in the LM form), 32 + 8 per beam slot, 8.
 inline size_t ctc_stream_slot_bytes(int beam, int max_frames, bool lm) {
   const size_t nodes = (size_t)ctc_stream_nodes(beam, max_frames), slots = (size_t)ctc_stream_slots(beam, max_frames);
@@ -149,13 +151,17 @@ inline void ctc_stream_carve(void* mem, int S, int beam, int max_frames, bool lm
   d->sess = nullptr; d->part = nullptr;
 }
 
-// One utterance's state in the plain-C++ twins (ctc_beam.hip): the device's arrays as vectors, the beam in rank order.
-struct CtcBeamHostPre { double pb, pnb, tot; int node, last; double bonus; };
+// One utterance's state in the plain-C++ twins (ctc_beam_host.hip): the kernel's arrays as vectors in the kernel's layout.  The two
+// beams are the halves [0, beam) and [beam, 2 beam) of the b_* arrays; the beam that left the last frame is the first `alive`
+// entries of half `cur`, in rank order -- which is also all a resumable call stores for the next.
 struct CtcBeamHostState {
   std::vector<unsigned long long> keys;
-  std::vector<int> vals, par, tok, n_state;
+  std::vector<int> vals, n_state;
+  std::vector<int2> nodes;
   std::vector<double> n_sum, n_bonus;
-  std::vector<CtcBeamHostPre> bm;
+  std::vector<double> b_pb, b_pnb, b_tot, b_bonus;
+  std::vector<int> b_node, b_last;
+  int beam = 0, cur = 0, alive = 0;
   int mask = 0, frames = 0;
   bool bad = false;
   void start(int beam, int max_T, bool lm, int lm_start);   // the empty string, an empty table for max_T frames
@@ -168,7 +174,7 @@ struct CtcBeamHostState {
 int launch_ctc_stream(const float* logits, int ld, int V, int pad, int unk, int rows, int n, const CtcStreamSess* h_sess, void* d_sess,
                       float* den, int* cand_id, int beam, int C, int nbest, CtcStreamDev dev, const ss_ngram_lm* lm,
                       const ss_ctc_lm_opts* opts, void* hyps, int* tokens, int out_stride, CtcStreamPart* part, hipStream_t stream);
-// The same in plain C++ on host logits and host state (one CtcBeamHostState per slot, started by the caller).
+// The same in plain C++ on host logits and host state (ctc_beam_host.hip; one CtcBeamHostState per slot, started by the caller).
 int ctc_stream_host_run(std::vector<CtcBeamHostState>& slots, const float* h_logits, int ld, int V, int pad, int unk, int n,
                         const CtcStreamSess* sess, int beam, int cand, int nbest, const ss_ngram_lm* lm, const ss_ctc_lm_opts* o,
                         void* h_hyps, int32_t* h_tokens, int out_stride, CtcStreamPart* h_part);
@@ -205,6 +211,138 @@ SS_HD int ctc_beam_find(const unsigned long long* keys, const int* vals, int mas
     if (k == CTC_BEAM_EMPTY) return -1;
   }
   return -1;
+}
+
+// ---- the frame: what ctc_beam_search_body (ctc_beam.hip) and the twin (ctc_beam_host.hip) both call, on one layout ----
+// The LM's lookup and its two rounding rules (ngram_lm.hpp, which includes this file: declared here, defined there).
+struct NgramView;
+SS_HD double ngram_lp(const NgramView& lm, int state, int c, int* next);
+SS_HD double ngram_bonus(double parent, double lm_weight, double lp, double word_score);
+SS_HD double ngram_finish(double fused, double lm_weight, double lp_eos);
+
+// The arrays a frame works on.  The kernel fills it once from its LDS arrays and its utterance's global pointers, the twin from
+// vectors of the same names.  The current and the next beam are integer offsets co / no into the b_* arrays, passed to the
+// functions and never folded into a pointer (ctc_align_trellis_kernel says why); each side has its own stride between the two.
+struct CtcBeamFrame {
+  double *b_pb, *b_pnb, *b_tot, *b_bonus; int *b_node, *b_last;   // the two beams (b_bonus: the LM form)
+  double *s_pb, *s_pnb, *s_give;                                  // per entering prefix: what it keeps, what an extension hands it
+  double *e_tot, *e_fus; int* e_node;                             // per entry (e_fus: the LM form)
+  int* s_c; float *s_lpc, *s_lpl, *s_lp0;                         // the candidates, their lp, the lp of each last label, of the blank
+  unsigned long long* keys; int* vals; int mask;                  // the child table
+  double* n_bonus; int* n_state;                                  // per node (the LM form)
+};
+
+// Pass B for entry e = i * W + (k + 1) of a beam of nb prefixes: prefix i's own stay terms (k < 0; its total is pass C's), or the
+// term of its extension by candidate k and that string's node from the child table -- an extension whose node is in the beam hands
+// its term to that prefix and dies (one parent per string: one writer per s_give[j]).  The LM form adds the entry's fused key.
+template <bool LM>
+SS_HD void ctc_beam_entry_b(const CtcBeamFrame& F, int co, int nb, int W, int e, const NgramView& lm, double lm_weight,
+                            double word_score) {
+  const int i = e / W, k = e - i * W - 1;
+  const int node = F.b_node[co + i], last = F.b_last[co + i];
+  if (k < 0) {
+    double pb2, pnb2;
+    ctc_beam_stay(F.b_pnb[co + i], F.b_tot[co + i], last, *F.s_lp0, F.s_lpl[i], &pb2, &pnb2);
+    F.s_pb[i] = pb2; F.s_pnb[i] = pnb2;
+    F.e_node[e] = node;
+    return;
+  }
+  const int c = F.s_c[k];
+  double term = -INFINITY;
+  int child = -1;
+  if (c >= 0) {
+    term = ctc_beam_ext(F.b_pb[co + i], F.b_tot[co + i], last, c, F.s_lpc[k]);
+    child = ctc_beam_find(F.keys, F.vals, F.mask, node, c);
+    if (child >= 0) {
+      for (int j = 0; j < nb; ++j) {
+        if (F.b_node[co + j] == child) { F.s_give[j] = term; term = -INFINITY; break; }
+      }
+    }
+  }
+  F.e_tot[e] = term;
+  F.e_node[e] = child;
+  if constexpr (LM) {
+    double fus = -INFINITY;
+    if (term > -INFINITY) {                                    // (a dead entry needs no bonus: no lookup)
+      int nx;
+      fus = term + (child >= 0 ? F.n_bonus[child]
+                               : ngram_bonus(F.b_bonus[co + i], lm_weight, ngram_lp(lm, F.n_state[node], c, &nx), word_score));
+    }
+    F.e_fus[e] = fus;
+  }
+}
+
+// Pass C for prefix i: pnb' = logadd(stay, handed term), its entry's total = logadd(pb', pnb') and, in the LM form, fused key.
+template <bool LM>
+SS_HD void ctc_beam_entry_c(const CtcBeamFrame& F, int co, int W, int i) {
+  const double pnb2 = ctc_beam_logadd(F.s_pnb[i], F.s_give[i]);
+  F.s_pnb[i] = pnb2;
+  const double tot = ctc_beam_logadd(F.s_pb[i], pnb2);
+  F.e_tot[i * W] = tot;
+  if constexpr (LM) F.e_fus[i * W] = tot > -INFINITY ? tot + F.b_bonus[co + i] : -INFINITY;
+}
+
+// A new string, parent + c, that takes rank `rank` of the beam leaving frame t: its id, its node with the three LM fields (written
+// once: the lookup of pass B again), and its place in the child table (never more than half full).  A frame's entries claim slots
+// concurrently on the device and one after another on the host: the claim is the one line that differs.
+template <bool LM>
+SS_HD int ctc_beam_make_node(int t, int beam, int rank, int parent, int c, double parent_bonus, unsigned long long* keys, int* vals,
+                             int mask, int2* nodes, double* n_sum, double* n_bonus, int* n_state, const NgramView& lm,
+                             double lm_weight, double word_score) {
+  const int node = ctc_beam_new_node(t, beam, rank);
+  nodes[node] = make_int2(parent, c);
+  if constexpr (LM) {
+    int nx;
+    const double lp = ngram_lp(lm, n_state[parent], c, &nx);
+    n_state[node] = nx;
+    n_sum[node] = n_sum[parent] + lp;
+    n_bonus[node] = ngram_bonus(parent_bonus, lm_weight, lp, word_score);
+  }
+  const unsigned long long key = ctc_beam_key(parent, c);
+  for (int s = ctc_beam_slot(key, mask), n = 0; n <= mask; ++n, s = (s + 1) & mask) {
+#ifdef __HIP_DEVICE_COMPILE__
+    if (atomicCAS(&keys[s], CTC_BEAM_EMPTY, key) == CTC_BEAM_EMPTY) { vals[s] = node; break; }
+#else
+    if (keys[s] == CTC_BEAM_EMPTY) { keys[s] = key; vals[s] = node; break; }
+#endif
+  }
+  return node;
+}
+
+// The string of a node, walked back through the trie: its tokens into out[0 .. len), its length returned.
+SS_HD int ctc_beam_trace(const int2* nodes, int node, int* out) {
+  int len = 0;
+  for (int n = node; n > 0; n = nodes[n].x) ++len;
+  int j = len;
+  for (int n = node; n > 0 && j > 0; n = nodes[n].x) out[--j] = nodes[n].y;
+  return len;
+}
+
+// The LM form's end for one prefix of the last beam: fin = (tot + bonus) and lm_sum = its node's sum, each with the eos term when
+// eos >= 0 (the model's eos id; < 0: no eos term).  (Lm = NgramView: a template for the files that include this header without it.)
+template <class Lm>
+SS_HD void ctc_beam_finish(double tot, double bonus, double node_sum, int node_state, int eos, const Lm& lm, double lm_weight,
+                           double* fin, double* lm_sum) {
+  const double fused = tot + bonus;
+  *fin = fused;
+  *lm_sum = node_sum;
+  if (eos >= 0) {
+    int nx;
+    const double lp = ngram_lp(lm, node_state, eos, &nx);
+    *fin = ngram_finish(fused, lm_weight, lp);
+    *lm_sum = node_sum + lp;
+  }
+}
+
+// The depth of the lowest common ancestor of nodes a and b: the length of what the two strings start with (the stable-prefix pass).
+SS_HD int ctc_beam_lca_depth(const int2* nodes, int a, int b) {
+  int da = 0, db = 0;
+  for (int n = a; n > 0; n = nodes[n].x) ++da;
+  for (int n = b; n > 0; n = nodes[n].x) ++db;
+  for (; da > db; --da) a = nodes[a].x;
+  for (; db > da; --db) b = nodes[b].x;
+  for (; a != b; --da) { a = nodes[a].x; b = nodes[b].x; }
+  return da;
 }
 
 }  // namespace ss

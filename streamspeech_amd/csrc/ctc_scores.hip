@@ -3,6 +3,7 @@
 // (`lprobs.max(dim=2)` after pad / unk are set to -inf, agent/ctc_decoder.py:52-62) and what word time spans and confidences are
 // made of.  Twins of masked_argmax_kernel / ctc_collapse_kernel (elementwise.hip), which stay as they are: with scores off the
 // library launches exactly what it launched before.
+#include "ctc_row.hpp"
 #include "elementwise.hpp"
 
 namespace ss {
@@ -12,8 +13,8 @@ namespace ss {
 // log-softmax first, masks after (agent/ctc_decoder.py:52-60), the quantity of row_max_logprob_kernel; any NaN in the row gives NaN
 // as torch.log_softmax does.  PER > 0: N <= 256 * PER, the row is read from global memory once and each thread keeps its PER values
 // in registers across the max pass and the sum pass.  PER == 0: any N, the sum pass reads the row again.
-// Every reduction in a fixed order -- thread stride ascending, xor-shuffle tree, the four wave partials in index order -- so a row's
-// result is a function of that row's bits alone, never of M or of the row's position.
+// The denominator and its fixed order: ctc_row.hpp (the max pass here shares its shuffle rounds with the arg-max and stays in this
+// kernel; the sum pass is the header's), so a row's result is a function of that row's bits alone, never of M or of its position.
 template <int PER>
 __global__ __launch_bounds__(256) void masked_argmax_lprob_kernel(const float* __restrict__ logits, int ld, int N, int mask0,
                                                                   int mask1, int mask2, int* __restrict__ ids,
@@ -57,29 +58,15 @@ __global__ __launch_bounds__(256) void masked_argmax_lprob_kernel(const float* _
   }
   if (lane == 0) { sb[wave] = best; si[wave] = bi; sm[wave] = mx; sn[wave] = nan; }
   __syncthreads();
-  mx = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-  float sum = 0.f;
-  if constexpr (PER > 0) {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const float e = expf(v[i] - mx);                         // accurate forms, as row_max_logprob_kernel
-      if (t + 256 * i < N) sum += e;
-    }
-  } else {
-    for (int n = t; n < N; n += 256) sum += expf(r[n] - mx);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-  if (lane == 0) ssum[wave] = sum;
-  __syncthreads();
+  mx = ctc_row_max4(sm);
+  ctc_row_expsum<PER>(r, N, v, mx, ssum);
   if (t == 0) {
     for (int w = 1; w < 4; ++w) {
       const float ob = sb[w]; const int oi = si[w];
       if (oi != 0x7fffffff && (bi == 0x7fffffff || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; }
     }
     ids[row] = bi;
-    const float tot = ((ssum[0] + ssum[1]) + ssum[2]) + ssum[3];
-    lprob[row] = (sn[0] | sn[1] | sn[2] | sn[3]) ? __builtin_nanf("") : (best - mx) - logf(tot);
+    lprob[row] = ctc_row_nan(sn) ? __builtin_nanf("") : (best - mx) - ctc_row_logsum(ssum);
   }
 }
 

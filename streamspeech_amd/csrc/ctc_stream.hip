@@ -2,7 +2,7 @@
 // and the three ways to move it -- on a model's encoder rows (ss_ctc_stream_advance: the rows a slot has not consumed are stacked,
 // go through the head under the batch call's pack-invariance setting, then the candidate kernel and one launch of the resumable
 // search kernel), on the caller's device logits (ss_op_ctc_stream_advance) and in plain C++ (ss_ctc_stream_advance_host).  The
-// search itself, its kernel and the twin's step code are ctc_beam.hip's: there is one statement of a frame.
+// kernel is ctc_beam.hip's, the twin ctc_beam_host.hip's, and the frame both run is ctc_beam.hpp's: there is one statement of a frame.
 #include "model_internal.hpp"
 #include "ctc_beam.hpp"
 #include "ngram_lm.hpp"
@@ -175,7 +175,7 @@ extern "C" int ss_ctc_stream_advance(ss_model* m, void* stream, ss_ctc_stream* c
   RET(m->sc->seg_buf.ensure(sess_bytes + ti.size() * sizeof(int)));
   RET(m->sc->mt_ws.ensure((size_t)rows * V * sizeof(float)));
   RET(m->sc->ws.ensure((size_t)rows * ((size_t)d * sizeof(float) + 8 + 4 * (size_t)cs->cand)));
-  float* logits = m->sc->mt_ws.f();
+  float* logits = m->sc->mt_ws.f();         // (a call without new rows launches no head; the search kernel reads no row then)
   float* stk = m->sc->ws.f();
   float* den = stk + (size_t)rows * d;
   int* cand_id = reinterpret_cast<int*>(den + 2 * (size_t)rows);
@@ -184,7 +184,7 @@ extern "C" int ss_ctc_stream_advance(ss_model* m, void* stream, ss_ctc_stream* c
   if (rows > 0) {
     SS_HIP_CHECK(hipMemcpyAsync(dti, ti.data(), ti.size() * sizeof(int), hipMemcpyHostToDevice, s));
     RET(launch_pool_stack_rows(stk, d_enc_packed, d, dti, dti + n, n, rows, s));
-    RET(linear(s, stk, d, rows, cs->head == 0 ? m->ctc_asr : m->ctc_st, V, d, logits, V));
+    RET(ctc_head_logits(m, s, cs->head, stk, d, rows, false, &logits));
   }
   RET(launch_ctc_stream(logits, V, V, cs->pad, cs->unk, rows, n, sess.data(), m->sc->seg_buf.p, den, cand_id, cs->beam, cs->cand,
                         cs->nbest, cs->dev, cs->lm, cs->lm ? &cs->opts : nullptr, d_hyps, d_tokens, out_stride,

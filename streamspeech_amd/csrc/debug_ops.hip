@@ -275,33 +275,32 @@ extern "C" int ss_op_ctc_align(void* stream, const float* d_logits, int ld, int 
   return launch_ctc_align(d_logits, ld, V, plan, h_targets, tmp.first.p, tmp.second.p, d_results, d_path, d_first, d_last, d_tok_lprob,
                           d_frame_lprob, (hipStream_t)stream);
 }
-// the two prefix-search kernels on the caller's logits; scratch as ss_op_ctc_align's
-extern "C" int ss_op_ctc_beam(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam,
-                              int cand, int nbest, ss_ctc_beam_hyp* d_hyps, int32_t* d_tokens, int out_stride, float* d_den,
-                              int32_t* d_cand_id) {
+// the two prefix-search kernels on the caller's logits; scratch as ss_op_ctc_align's.  with_lm: the LM form and its refusals.
+static int op_ctc_beam(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
+                       int nbest, void* d_hyps, int32_t* d_tokens, int out_stride, float* d_den, int32_t* d_cand_id, bool with_lm,
+                       const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts) {
   if (!d_logits || ld < V || !d_hyps || !d_tokens) return SS_ERR_ARG;
   CtcBeamPlan plan;
   RET(ctc_beam_plan(V, B, h_T, beam, cand, nbest, out_stride, plan));
+  if (with_lm) RET(ctc_beam_lm_check(lm, V, opts));
   static thread_local std::map<hipStream_t, std::pair<DevBuf, DevBuf>> tmps;
   auto& tmp = tmps[(hipStream_t)stream];
   RET(tmp.first.ensure(ctc_beam_table_bytes(plan)));
-  RET(tmp.second.ensure(plan.work_bytes()));
-  return launch_ctc_beam(d_logits, ld, V, pad, unk, plan, tmp.first.p, tmp.second.p, d_hyps, d_tokens, out_stride, d_den, d_cand_id,
-                         (hipStream_t)stream);
+  RET(tmp.second.ensure(with_lm ? plan.work_bytes_lm() : plan.work_bytes()));
+  return launch_ctc_beam(d_logits, ld, V, pad, unk, plan, tmp.first.p, tmp.second.p, lm, opts, d_hyps, d_tokens, out_stride, d_den,
+                         d_cand_id, (hipStream_t)stream);
+}
+extern "C" int ss_op_ctc_beam(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam,
+                              int cand, int nbest, ss_ctc_beam_hyp* d_hyps, int32_t* d_tokens, int out_stride, float* d_den,
+                              int32_t* d_cand_id) {
+  return op_ctc_beam(stream, d_logits, ld, V, pad, unk, B, h_T, beam, cand, nbest, d_hyps, d_tokens, out_stride, d_den, d_cand_id, false,
+                     nullptr, nullptr);
 }
 extern "C" int ss_op_ctc_beam_lm(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam,
                                  int cand, int nbest, ss_ctc_beam_lm_hyp* d_hyps, int32_t* d_tokens, int out_stride, float* d_den,
                                  int32_t* d_cand_id, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts) {
-  if (!d_logits || ld < V || !d_hyps || !d_tokens) return SS_ERR_ARG;
-  CtcBeamPlan plan;
-  RET(ctc_beam_plan(V, B, h_T, beam, cand, nbest, out_stride, plan));
-  RET(ctc_beam_lm_check(lm, V, opts));
-  static thread_local std::map<hipStream_t, std::pair<DevBuf, DevBuf>> tmps;
-  auto& tmp = tmps[(hipStream_t)stream];
-  RET(tmp.first.ensure(ctc_beam_table_bytes(plan)));
-  RET(tmp.second.ensure(plan.work_bytes_lm()));
-  return launch_ctc_beam_lm(d_logits, ld, V, pad, unk, plan, tmp.first.p, tmp.second.p, lm, opts, d_hyps, d_tokens, out_stride, d_den,
-                            d_cand_id, (hipStream_t)stream);
+  return op_ctc_beam(stream, d_logits, ld, V, pad, unk, B, h_T, beam, cand, nbest, d_hyps, d_tokens, out_stride, d_den, d_cand_id, true,
+                     lm, opts);
 }
 extern "C" int ss_op_ngram_score(void* stream, const ss_ngram_lm* lm, int B, const int32_t* d_tokens, const int32_t* h_n, int with_eos,
                                  double* d_lp, int32_t* d_state) {

@@ -84,8 +84,8 @@ int launch_mt_token_scores(const float* logits, int ld, int M, int N, const int*
                            int form = 0);
 
 // CTC forced alignment of given labels (ctc_align.hip; the plan, its checks and its limits: ctc_align.hpp).  Two launches over a
-// checked plan: per packed frame row the plain log-softmax at the utterance's states (lp, float32, the denominator arithmetic of
-// launch_masked_argmax_lprob), then one workgroup per utterance for the forward sum, the max-plus pass with 2-bit back-pointers, the
+// checked plan: per packed frame row the plain log-softmax at the utterance's states (lp, float32, the denominator of ctc_row.hpp),
+// then one workgroup per utterance for the forward sum, the max-plus pass with 2-bit back-pointers, the
 // back-trace and each label's first / last frame and float32 sum of lp over its run in ascending frame order.  d_table
 // (ctc_align_table_bytes) and d_work (plan.work_bytes()) are the caller's scratch; path and frame_lprob (the path's lp per frame) may
 // be null.  An utterance's outputs are the same bits alone and at any place of any pack.
@@ -97,19 +97,18 @@ int launch_ctc_align(const float* logits, int ld, int V, const CtcAlignPlan& p, 
 
 // CTC prefix beam search (ctc_beam.hip; the plan, its checks, its limits and the search's definition: ctc_beam.hpp).  A fill of the
 // child tables and two launches over a checked plan: per packed frame row the log-softmax denominator (den [rows][2]: max, log-sum,
-// the arithmetic of launch_masked_argmax_lprob) and the ids of the plan's `cand` largest unmasked non-blank logits (cand_id
-// [rows][cand], -1 where there are fewer), then one workgroup per utterance for the search and the back-trace of its n-best.
-// d_table (ctc_beam_table_bytes) and d_work (plan.work_bytes()) are the caller's scratch; den_out / cand_out, when given, receive
-// the first kernel's outputs instead of d_work.  An utterance's outputs are the same bits alone and at any place of any pack.
+// ctc_row.hpp) and the ids of the plan's `cand` largest unmasked non-blank logits (cand_id [rows][cand], -1 where there are fewer),
+// then one workgroup per utterance for the search and the back-trace of its n-best.  lm == nullptr: the plain form, hyps an
+// ss_ctc_beam_hyp array, d_work holds plan.work_bytes(); else the LM form (ctc_beam.hpp, ngram_lm.hpp), hyps an ss_ctc_beam_lm_hyp
+// array, d_work holds plan.work_bytes_lm(), and ctc_beam_lm_check is every refusal it adds.  d_table (ctc_beam_table_bytes) and
+// d_work are the caller's scratch; den_out / cand_out, when given, receive the first kernel's outputs instead of d_work.  An
+// utterance's outputs are the same bits alone and at any place of any pack.
 struct CtcBeamPlan;
 size_t ctc_beam_table_bytes(const CtcBeamPlan& p);
-int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
-                    ss_ctc_beam_hyp* hyps, int* tokens, int out_stride, float* den_out, int* cand_out, hipStream_t stream);
-// The LM form (ctc_beam.hpp, ngram_lm.hpp): d_work holds plan.work_bytes_lm(); ctc_beam_lm_check is every refusal it adds.
 int ctc_beam_lm_check(const ss_ngram_lm* lm, int V, const ss_ctc_lm_opts* opts);
-int launch_ctc_beam_lm(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
-                       const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, ss_ctc_beam_lm_hyp* hyps, int* tokens, int out_stride,
-                       float* den_out, int* cand_out, hipStream_t stream);
+int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
+                    const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, void* hyps, int* tokens, int out_stride, float* den_out,
+                    int* cand_out, hipStream_t stream);
 // The score kernel of ngram_lm.hip: d_table (ngram_score_table_bytes) is the caller's scratch.
 size_t ngram_score_table_bytes(int B);
 int launch_ngram_score(const ss_ngram_lm* lm, int B, const int32_t* d_tokens, const int32_t* h_n, int with_eos, double* d_lp,

@@ -557,42 +557,49 @@ extern "C" int ss_encoder_stream_forward(ss_model* m, void* stream, const float*
 }
 
 // ---- CTC heads ---------------------------------------------------------------------------------
+int ctc_head_logits(ss_model* m, hipStream_t s, int head, const float* x, int ldx, int rows, bool record, float** logits, int* V_out) {
+  const ss_config& c = m->cfg;
+  const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
+  if (!*logits) {
+    RET(m->sc->mt_ws.ensure((size_t)rows * V * sizeof(float)));
+    *logits = m->sc->mt_ws.f();
+  }
+  RET(linear(s, x, ldx, rows, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, *logits, V));
+  if (record) { m->sc->dbg_logits = *logits; m->sc->dbg_rows = rows; m->sc->dbg_cols = V; }
+  if (V_out) *V_out = V;
+  return SS_OK;
+}
+
+// The greedy search of one utterance: the head, the masked arg-max, the collapse.  d_lprob given (with d_last, d_tok_lprob): the
+// scored twins of the two glue kernels (ctc_scores.hip) in their place -- the same head GEMM, the same number of launches.
+static int ctc_greedy(ss_model* m, void* stream, int head, const float* d_enc_out, int Tp, int32_t* d_raw, int32_t* d_tokens,
+                      int32_t* d_index, int32_t* d_count, float* d_logits, float* d_lprob, int32_t* d_last, float* d_tok_lprob) {
+  SkScope sk_scope(m->sc->skws);
+  hipStream_t s = (hipStream_t)stream;
+  const ss_config& c = m->cfg;
+  float* logits = d_logits;
+  int V = 0;
+  RET(ctc_head_logits(m, s, head, d_enc_out, c.enc_dim, Tp, false, &logits, &V));
+  if (!d_lprob) {
+    RET(launch_masked_argmax(logits, V, Tp, V, c.pad, c.unk, -1, -1, d_raw, s));
+    return launch_ctc_collapse(d_raw, Tp, 0, c.pad, d_tokens, d_index, d_count, s);
+  }
+  RET(launch_masked_argmax_lprob(logits, V, Tp, V, c.pad, c.unk, -1, d_raw, d_lprob, s));
+  return launch_ctc_collapse_spans(d_raw, d_lprob, Tp, 0, c.pad, d_tokens, d_index, d_last, d_tok_lprob, d_count, s);
+}
+
 extern "C" int ss_ctc_greedy(ss_model* m, void* stream, int head, const float* d_enc_out, int Tp,
                              int32_t* d_raw, int32_t* d_tokens, int32_t* d_index, int32_t* d_count,
                              float* d_logits) {
   if (!m || Tp <= 0 || head < 0 || head > 1) return SS_ERR_ARG;
-  SkScope sk_scope(m->sc->skws);
-  hipStream_t s = (hipStream_t)stream;
-  const ss_config& c = m->cfg;
-  const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
-  float* logits = d_logits;
-  if (!logits) {
-    RET(m->sc->mt_ws.ensure((size_t)Tp * V * sizeof(float)));
-    logits = m->sc->mt_ws.f();
-  }
-  RET(linear(s, d_enc_out, c.enc_dim, Tp, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, logits, V));
-  RET(launch_masked_argmax(logits, V, Tp, V, c.pad, c.unk, -1, -1, d_raw, s));
-  return launch_ctc_collapse(d_raw, Tp, 0, c.pad, d_tokens, d_index, d_count, s);
+  return ctc_greedy(m, stream, head, d_enc_out, Tp, d_raw, d_tokens, d_index, d_count, d_logits, nullptr, nullptr, nullptr);
 }
 
-// ss_ctc_greedy with the per-frame log-probability of the arg-max and the spans of the collapsed tokens (ctc_scores.hip): the same
-// head GEMM, the scored twins of the two glue kernels -- the same number of launches.
 extern "C" int ss_ctc_greedy_scored(ss_model* m, void* stream, int head, const float* d_enc_out, int Tp, int32_t* d_raw,
                                     int32_t* d_tokens, int32_t* d_index, int32_t* d_count, float* d_logits, float* d_lprob,
                                     int32_t* d_last, float* d_tok_lprob) {
   if (!m || Tp <= 0 || head < 0 || head > 1 || !d_lprob || !d_last || !d_tok_lprob) return SS_ERR_ARG;
-  SkScope sk_scope(m->sc->skws);
-  hipStream_t s = (hipStream_t)stream;
-  const ss_config& c = m->cfg;
-  const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
-  float* logits = d_logits;
-  if (!logits) {
-    RET(m->sc->mt_ws.ensure((size_t)Tp * V * sizeof(float)));
-    logits = m->sc->mt_ws.f();
-  }
-  RET(linear(s, d_enc_out, c.enc_dim, Tp, head == 0 ? m->ctc_asr : m->ctc_st, V, c.enc_dim, logits, V));
-  RET(launch_masked_argmax_lprob(logits, V, Tp, V, c.pad, c.unk, -1, d_raw, d_lprob, s));
-  return launch_ctc_collapse_spans(d_raw, d_lprob, Tp, 0, c.pad, d_tokens, d_index, d_last, d_tok_lprob, d_count, s);
+  return ctc_greedy(m, stream, head, d_enc_out, Tp, d_raw, d_tokens, d_index, d_count, d_logits, d_lprob, d_last, d_tok_lprob);
 }
 
 int mt_cross_kv(ss_model* m, hipStream_t s, const float* d_enc_out, int n_rows) {

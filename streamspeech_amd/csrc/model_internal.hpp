@@ -467,6 +467,13 @@ int mt_prefix_pass(ss_model* m, hipStream_t s, int B, int Np, int np_max, int n_
 // caller has booked mt_cross: (mt_layers * n_rows * 2D) floats.
 int mt_cross_kv(ss_model* m, hipStream_t s, const float* d_enc_out, int n_rows);
 
+// The head step of everything that reads a text CTC head (model.hip): logits [rows][V] = x [rows][enc_dim, ld ldx] through ctc_asr
+// (head 0) or ctc_st (head 1), V that head's vocabulary.  *logits == nullptr: into mt_ws, ensured here and returned; else into the
+// caller's buffer.  record: the debug logits fields point at the result (the batch calls; the pools and the stream advance leave
+// them alone).  A caller that books other scratch too ensures mt_ws itself, in the order its refusals have always come (the ensure
+// here is then a no-op).  SkScope and CanonScope are the caller's.
+int ctc_head_logits(ss_model* m, hipStream_t s, int head, const float* x, int ldx, int rows, bool record, float** logits, int* V = nullptr);
+
 // The decode rows' workspace of the lock-step text searches, carved from mt_ws: x | h | q2 | ffn | (gap floats) | logits, one row per
 // search row.  floats() is what the five parts take; a search with rows behind the logits books them on top.
 struct MtRowsWs {

@@ -479,8 +479,9 @@ extern "C" int ss_stream_pool_ctc(ss_model* m, void* stream, ss_stream_pool* p, 
   const long long g0 = gemm_census();
   if (Mc > 0) {              // the rows whose arg-max the slots do not hold yet: stacked, through the head, arg-max
     RET(launch_pool_stack_rows(stk, d_enc_packed, d, dsrc, dsp, n, Mc, s));
-    RET(linear(s, stk, d, Mc, head == 0 ? m->ctc_asr : m->ctc_st, V, d, m->sc->mt_ws.f(), V));
-    RET(launch_masked_argmax(m->sc->mt_ws.f(), V, Mc, V, c.pad, c.unk, -1, -1, raw_stk, s));
+    float* logits = nullptr;
+    RET(ctc_head_logits(m, s, head, stk, d, Mc, false, &logits));
+    RET(launch_masked_argmax(logits, V, Mc, V, c.pad, c.unk, -1, -1, raw_stk, s));
     nl += 2;                 // (the head GEMM: counted by the census)
   }
   RET(launch_pool_gather_ids(d_raw, raw_stk, reinterpret_cast<int32_t*>(p->raw.p) + (size_t)head * p->S * p->R, p->R, dgt, dgp, n, total,
@@ -561,8 +562,9 @@ extern "C" int ss_stream_pool_ctc_scored(ss_model* m, void* stream, ss_stream_po
   const long long g0 = gemm_census();
   if (Mc > 0) {
     RET(launch_pool_stack_rows(stk, d_enc_packed, d, dsrc, dsp, n, Mc, s));
-    RET(linear(s, stk, d, Mc, head == 0 ? m->ctc_asr : m->ctc_st, V, d, m->sc->mt_ws.f(), V));
-    RET(launch_masked_argmax_lprob(m->sc->mt_ws.f(), V, Mc, V, c.pad, c.unk, -1, raw_stk, lp_stk, s));
+    float* logits = nullptr;
+    RET(ctc_head_logits(m, s, head, stk, d, Mc, false, &logits));
+    RET(launch_masked_argmax_lprob(logits, V, Mc, V, c.pad, c.unk, -1, raw_stk, lp_stk, s));
     nl += 2;
   }
   const size_t hoff = (size_t)head * p->S * p->R;

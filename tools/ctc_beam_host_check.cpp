@@ -1,8 +1,8 @@
-// Stand-alone check of the CTC prefix beam search's host twin (ss_ctc_beam_host, csrc/ctc_beam.hip) for a sanitizer build of the
+// Stand-alone check of the CTC prefix beam search's host twin (ss_ctc_beam_host, csrc/ctc_beam_host.hip) for a sanitizer build of the
 // host code: two small cases, (T, V, beam, cand) = (12, 6, 4, 3) and (40, 64, 8, 8), in one ragged pack and alone, with guarded
 // outputs.  Host code only; nothing here touches a device.
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
-//         tools/ctc_beam_host_check.cpp streamspeech_amd/csrc/ctc_beam.hip -o ctc_beam_host_check -fsanitize=address,undefined
+//         tools/ctc_beam_host_check.cpp streamspeech_amd/csrc/ctc_beam_host.hip -o ctc_beam_host_check -fsanitize=address,undefined
 //   ./ctc_beam_host_check
 #include <cmath>
 #include <cstdint>

@@ -1,13 +1,14 @@
 // Stand-alone check of the resumable CTC prefix beam search's host twin (ss_ctc_stream_advance_host, csrc/ctc_stream.hip over the
-// step code of csrc/ctc_beam.hip) for a sanitizer build of the host code: (T, V, beam, cand) = (40, 64, 8, 8) and (12, 6, 4, 3),
+// twin of csrc/ctc_beam_host.hip) for a sanitizer build of the host code: (T, V, beam, cand) = (40, 64, 8, 8) and (12, 6, 4, 3),
 // plain and with a small bigram model, two slots, cut into calls of every size from 1 to 7 frames and a call without rows, in an
 // object made for exactly T frames (the trie and the table are filled to their ends) and with exactly sized outputs; the last
 // call's records must be ss_ctc_beam_host's / ss_ctc_beam_lm_host's bytes.  Host code only; nothing here touches a device.
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
-//         tools/ctc_stream_host_check.cpp streamspeech_amd/csrc/ctc_stream.hip streamspeech_amd/csrc/ctc_beam.hip \
-//         streamspeech_amd/csrc/ngram_lm.hip -Lstreamspeech_amd -lstreamspeech_hip -o ctc_stream_host_check -fsanitize=address,undefined
+//         tools/ctc_stream_host_check.cpp streamspeech_amd/csrc/ctc_stream.hip streamspeech_amd/csrc/ctc_beam_host.hip \
+//         streamspeech_amd/csrc/ctc_beam.hip streamspeech_amd/csrc/ngram_lm.hip -Lstreamspeech_amd -lstreamspeech_hip \
+//         -o ctc_stream_host_check -fsanitize=address,undefined
 //   LD_LIBRARY_PATH=streamspeech_amd ./ctc_stream_host_check
-// (the three translation units under test are compiled into the program with the sanitizers; the rest of the library, which
+// (the four translation units under test are compiled into the program with the sanitizers; the rest of the library, which
 // ss_ctc_stream_advance's model path refers to and this program never calls, comes from the built shared object)
 #include <cmath>
 #include <cstdint>
