@@ -884,6 +884,74 @@ int ss_batch_ctc_beam_lm(ss_model* m, void* stream, int head, int B, const float
 int ss_ctc_beam_lm_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
                         int nbest, ss_ctc_beam_lm_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den, int32_t* h_cand_id,
                         const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts);
+/* ---- Hotword biasing of the CTC prefix beam search (csrc/ctc_bias.hpp, ctc_bias.hip; the biased search: csrc/ctc_beam.hpp): a set of
+ * phrases to prefer -- names, products, terms -- given per deployment, where an n-gram model is built offline from a corpus.  A
+ * bias set is P phrases of 1 .. SS_CTC_BIAS_MAX_LEN token ids of the head's vocabulary, each with a boost: finite float32, natural
+ * log units, earned per token, negative to discourage.  THE AUTOMATON: node 0 is the root (the empty string), one node per distinct
+ * phrase prefix; a node's token boost is the largest boost of the phrases that pass through it; held[n] = held[parent] +
+ * (double)boost[n], summed root-down in float64; floor[n] = held of the deepest node on the path root .. n (n included) that ends a
+ * phrase, 0 if none.  THE SCORING RULE: the state of a string y is the longest suffix of y that is a node (Aho-Corasick goto with
+ * fail links).  On token c state s moves to n and the string earns delta = held[n] - held[s] when n is s extended by c (a direct
+ * move), else delta = (held[n] - held[s]) + floor[s]: two separately rounded float64 operations, in that order.  So a partial match
+ * that breaks is paid back, what was earned up to the last completed phrase is kept, and the part of the suffix that still matches
+ * keeps its credit.  With open(s) = held[s] - floor[s], the bias of a finished string is sum(delta) - open(state): an unfinished
+ * phrase earns nothing.  A phrase may be a prefix of another ("new", "new york"); a phrase that occurs inside another at a
+ * position other than its start is refused.  With that restriction the finished bias of y equals the sum of held[end(p)] over the
+ * occurrences (p, i) of phrases in y that are not a proper prefix of another occurrence starting at the same i. ---- */
+typedef struct ss_ctc_bias ss_ctc_bias;
+#define SS_CTC_BIAS_MAX_LEN 32
+#define SS_CTC_BIAS_MAX_PHRASES 4096
+/* Builds the automaton on the host; the one upload is made by the first device call that uses the set, so creation needs no device;
+ * the table then lives on the device that was current at that call.  Phrase p is h_tokens[h_off[p] .. h_off[p + 1]) with the per-token
+ * boost h_boost[p]; h_off holds n_phrases + 1 ascending offsets from 0.  pad / unk: the head's ids, or -1 for none.  SS_ERR_ARG, with
+ * nothing allocated: an empty phrase or one longer than SS_CTC_BIAS_MAX_LEN, an id outside [0, V), blank (0), pad or unk inside a
+ * phrase, a duplicate phrase, a non-finite boost, more than SS_CTC_BIAS_MAX_PHRASES phrases (or fewer than 0), a phrase that occurs
+ * inside another phrase at a position other than its start, V <= 0, pad / unk outside [-1, V), a missing pointer.  Read-only
+ * afterwards: one object serves every context and stream. */
+int ss_ctc_bias_create(int n_phrases, const int32_t* h_tokens, const int32_t* h_off, const float* h_boost, int V, int pad, int unk,
+                       ss_ctc_bias** out);
+void ss_ctc_bias_destroy(ss_ctc_bias* bias);
+/* phrases, nodes (the root included), slots of the child table (the power of two >= 2 nodes) and the bytes it takes on the device
+ * (12 per slot + 32 per node); each pointer may be NULL. */
+int ss_ctc_bias_info(const ss_ctc_bias* bias, int32_t* n_phrases, int64_t* nodes, int64_t* slots, int64_t* device_bytes);
+/* The scoring rule in plain C++ on B packed sequences (h_n[b] tokens each), every one from the root: h_delta receives per token its
+ * float64 delta, h_state (may be NULL) the state after it, h_sum [B] the sum of a sequence's deltas in order, minus open(final
+ * state) with `finish`.  A token no phrase holds leads to the root.  SS_ERR_ARG: a NULL bias, B <= 0, a negative count, a missing
+ * pointer. */
+int ss_ctc_bias_score_host(const ss_ctc_bias* bias, int B, const int32_t* h_tokens, const int32_t* h_n, int finish, double* h_delta,
+                           int32_t* h_state, double* h_sum);
+/* The bias form of the search above, with an n-gram model or without.  A prefix also carries b_state, the automaton's state of its
+ * string, bias_sum, the unscaled sum of its tokens' deltas, and the LM form's bonus, fixed when its trie node is made: the child by
+ * c has bonus = B1 + (scale * delta), the multiply and the add rounded separately, where B1 is the LM form's bonus of the child
+ * with a model and bonus[parent] without.  A frame's entries are ordered by fused = tot + bonus; pb / pnb / tot stay pure CTC
+ * quantities, the candidates are the `cand` largest acoustic logits, and the order of entries, the tie rule and pack invariance
+ * are the plain search's.  At the end fin = fused [+ the eos term] - scale * open(b_state) with `finish`, and the n-best are the
+ * last beam by fin descending, the earlier rank first on a tie. */
+typedef struct ss_ctc_bias_opts {
+  double scale;        /* the weight of the bias in the order (finite; 0: the plain order, or the LM form's) */
+  int32_t finish;      /* non-zero: the finish term -- an unfinished phrase earns nothing */
+  int32_t reserved;
+} ss_ctc_bias_opts;
+typedef struct ss_ctc_beam_bias_hyp {
+  double score;        /* fin */
+  double ctc_score;    /* tot: ss_ctc_beam_hyp.score */
+  double lm_score;     /* as ss_ctc_beam_lm_hyp.lm_score; 0 without a model */
+  double bias_score;   /* bias_sum, after the finish term: natural log, unscaled */
+  int32_t n_tokens;
+  int32_t status;      /* as ss_ctc_beam_hyp; for 1 and 2: n_tokens = 0, score = ctc_score = -inf / NaN, lm_score = bias_score = 0 */
+} ss_ctc_beam_bias_hyp;
+/* ss_batch_ctc_beam_lm with a hotword set: its arguments, outputs, refusals and pack invariance.  lm and opts may both be NULL:
+ * bias alone.  SS_ERR_ARG, with nothing launched or written, also for a NULL bias or bias_opts, a set whose V, pad or unk are not
+ * the head's, a non-finite scale, lm without opts or opts without lm.  Working memory: ss_batch_ctc_beam's plus 20 (1 + beam Tp)
+ * bytes per utterance, 32 (1 + beam Tp) with a model. */
+int ss_batch_ctc_beam_bias(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int beam, int cand,
+                           int nbest, ss_ctc_beam_bias_hyp* d_hyps, int32_t* d_tokens, int out_stride, const ss_ngram_lm* lm,
+                           const ss_ctc_lm_opts* opts, const ss_ctc_bias* bias, const ss_ctc_bias_opts* bias_opts);
+/* The plain-C++ twin, as ss_ctc_beam_host is of the plain search. */
+int ss_ctc_beam_bias_host(const float* h_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
+                          int nbest, ss_ctc_beam_bias_hyp* h_hyps, int32_t* h_tokens, int out_stride, float* h_den, int32_t* h_cand_id,
+                          const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, const ss_ctc_bias* bias,
+                          const ss_ctc_bias_opts* bias_opts);
 /* ---- The same search, resumable (csrc/ctc_stream.hip; the kernel: csrc/ctc_beam.hip): a device object holds, for max_sessions slots
  * of one text head, everything the search needs between launches -- per slot the frames consumed, a sticky "NaN seen" flag, the
  * beam that left the last frame (pb, pnb, tot, node, last, and bonus in the LM form), the trie, its child table and the LM fields
@@ -910,6 +978,13 @@ typedef struct ss_ctc_stream_part {
 } ss_ctc_stream_part;
 int ss_ctc_stream_create(ss_model* m, int head, int max_sessions, int max_frames, int beam, int cand, int nbest, const ss_ngram_lm* lm,
                          const ss_ctc_lm_opts* opts, ss_ctc_stream** out);
+/* The same object for the bias form of the search (a hotword set, with a model or with lm and opts both NULL): ss_ctc_stream_advance
+ * serves it and writes ss_ctc_beam_bias_hyp records, the finish term of bias_opts (copied) only in an utterance's last call, where
+ * the eos term is applied; on any other call score = tot + bonus and bias_score = bias_sum, in beam order.  Per slot 20 bytes
+ * per node more than the plain object, 32 with a model.  SS_ERR_ARG also for ss_batch_ctc_beam_bias's refusals of a set. */
+int ss_ctc_stream_create_bias(ss_model* m, int head, int max_sessions, int max_frames, int beam, int cand, int nbest,
+                              const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, const ss_ctc_bias* bias,
+                              const ss_ctc_bias_opts* bias_opts, ss_ctc_stream** out);
 void ss_ctc_stream_destroy(ss_ctc_stream* cs);
 /* A new utterance in `slot`.  Host-only: no stream, nothing launched; the slot's child table is cleared on the stream of its first
  * advance after the reset.  An input shorter than the frames consumed is a new utterance, and so is a change of the encoder's
@@ -1618,6 +1693,21 @@ int ss_debug_ctc_stream_create(int V, int pad, int unk, int on_device, int max_s
 int ss_op_ctc_stream_advance(void* stream, ss_ctc_stream* cs, int n, const int32_t* h_slots, const float* d_logits, int ld,
                              const int32_t* h_upto, const int32_t* h_final, void* d_hyps, int32_t* d_tokens, int out_stride,
                              ss_ctc_stream_part* d_part);
+/* ss_op_ctc_beam_lm with a hotword set (lm and opts may both be NULL): the kernels of ss_batch_ctc_beam_bias on the caller's logits.
+ * tests/test_ctc_beam_bias_gpu.py. */
+int ss_op_ctc_beam_bias(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam,
+                        int cand, int nbest, ss_ctc_beam_bias_hyp* d_hyps, int32_t* d_tokens, int out_stride, float* d_den,
+                        int32_t* d_cand_id, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, const ss_ctc_bias* bias,
+                        const ss_ctc_bias_opts* bias_opts);
+/* ss_debug_ctc_stream_create for the bias form: the object of ss_ctc_stream_create_bias without a model context.
+ * tests/test_ctc_stream_bias_cpu.py, tests/test_ctc_stream_bias_gpu.py. */
+int ss_debug_ctc_stream_create_bias(int V, int pad, int unk, int on_device, int max_sessions, int max_frames, int beam, int cand,
+                                    int nbest, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, const ss_ctc_bias* bias,
+                                    const ss_ctc_bias_opts* bias_opts, ss_ctc_stream** out);
+/* ss_ctc_bias_score_host on the device, one wave per sequence: d_tokens packed (device), h_n on the host, d_delta / d_state (may be
+ * NULL) / d_sum device arrays of the twin's sizes.  tests/test_ctc_bias_gpu.py. */
+int ss_op_ctc_bias_score(void* stream, const ss_ctc_bias* bias, int B, const int32_t* d_tokens, const int32_t* h_n, int finish,
+                         double* d_delta, int32_t* d_state, double* d_sum);
 /* ss_ngram_score_host on the device, one wave per sequence: d_tokens packed (device), h_n on the host, d_lp / d_state (may be
  * NULL) device arrays laid out as the host call's.  The op-level handle on the lookup the fused search runs.  Stream-ordered. */
 int ss_op_ngram_score(void* stream, const ss_ngram_lm* lm, int B, const int32_t* d_tokens, const int32_t* h_n, int with_eos,

@@ -345,6 +345,11 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
           help="with --ctc-beam: an ARPA n-gram model (.arpa / .arpa.gz) over source_unigram, fused into the search")
         a("--ctc-lm-weight", type=float, default=0.5, help="with --ctc-lm: the weight of the model's log-probability (default 0.5)")
         a("--ctc-word-score", type=float, default=0.0, help="with --ctc-lm: added per token of a hypothesis (default 0)")
+        a("--ctc-hotwords", default=None, metavar="FILE",
+          help="with --ctc-beam: phrases to prefer, one per line as space-separated source_unigram pieces, optionally a tab and the "
+               "phrase's per-token boost (hotwords.read_hotwords); biases the search towards them")
+        a("--ctc-hotword-boost", type=float, default=1.5,
+          help="with --ctc-hotwords: the per-token boost, in natural-log units, of a line that names none (default 1.5)")
         a("--mt-alignment", action="store_true", default=False,
           help="after every policy() that wrote, agent.alignment holds the words of all committed target tokens (the text decoder's, "
                "which the S2TT agent prints and the S2ST path speaks) with the source time span the decoder's cross-attention "

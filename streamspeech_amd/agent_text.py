@@ -113,6 +113,10 @@ class StreamSpeechASRAgent(_TextAgentBase):
             if getattr(args, "ctc_lm", None):
                 from .ngram import NgramLM, read_arpa
                 opts.lm = NgramLM(read_arpa(args.ctc_lm, self.dict["source_unigram"]))
+            if getattr(args, "ctc_hotwords", None):
+                from .hotwords import CtcBias, read_hotwords
+                d = self.dict["source_unigram"]
+                opts.bias = CtcBias(*read_hotwords(args.ctc_hotwords, d, args.ctc_hotword_boost), len(d), d.pad(), d.unk())
             self._ctc_frames = 0
             self.ctc_stream = CtcStream(self.engine, 0, 1, CTC_BEAM_MAX_FRAMES, **opts.stream_kwargs())
 

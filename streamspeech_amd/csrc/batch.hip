@@ -230,26 +230,29 @@ int mt_decode_rows(ss_model* m, hipStream_t s, const MtRowsWs& w, const MtRowsSt
 // two kernels of ctc_beam.hip.  Every refusal comes before the first launch; the tries, child tables and per-frame values live in
 // the encoder scratch (idle here: d_enc_out is the caller's), the table of the pack in the segment buffer.  with_lm: an n-gram
 // model fused into the order (ctc_beam.hpp) -- the plain call's GEMM, scopes and buffers, 20 more bytes per trie node in the encoder
-// scratch; the model's refusals come with the plain ones, before the first launch.
+// scratch; the model's refusals come with the plain ones, before the first launch.  with_bias: a hotword set as well or alone
+// (ctc_bias.hpp): 20 bytes per node, 32 with a model, and its refusals before the first launch too.
 static int batch_ctc_beam(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int beam, int cand,
                           int nbest, void* d_hyps, int32_t* d_tokens, int out_stride, bool with_lm, const ss_ngram_lm* lm,
-                          const ss_ctc_lm_opts* opts) {
+                          const ss_ctc_lm_opts* opts, bool with_bias = false, const ss_ctc_bias* bias = nullptr,
+                          const ss_ctc_bias_opts* bopts = nullptr) {
   if (!m || B <= 0 || head < 0 || head > 1 || !d_enc_out || !h_Tp || !d_hyps || !d_tokens) return SS_ERR_ARG;
   const ss_config& c = m->cfg;
   const int V = head == 0 ? c.src_vocab : c.tgt_vocab;
   CtcBeamPlan plan;
   RET(ctc_beam_plan(V, B, h_Tp, beam, cand, nbest, out_stride, plan));
+  if (with_bias) RET(ctc_beam_bias_check(bias, V, c.pad, c.unk, bopts, lm, opts));
   if (with_lm) RET(ctc_beam_lm_check(lm, V, opts));
   SkScope sk_scope(m->sc->skws);
   CanonScope canon_scope(m->pack_invariant ? CANON_SEQ : CANON_NONE);
   hipStream_t s = (hipStream_t)stream;
   RET(m->sc->mt_ws.ensure((size_t)plan.rows * V * sizeof(float)));
-  RET(m->sc->ws.ensure(with_lm ? plan.work_bytes_lm() : plan.work_bytes()));
+  RET(m->sc->ws.ensure(plan.work_bytes_form((with_lm ? CTC_FORM_LM : 0) | (with_bias ? CTC_FORM_BIAS : 0))));
   RET(m->sc->seg_buf.ensure(ctc_beam_table_bytes(plan)));
   float* logits = nullptr;
   RET(ctc_head_logits(m, s, head, d_enc_out, c.enc_dim, plan.rows, true, &logits));
   return launch_ctc_beam(logits, V, V, c.pad, c.unk, plan, m->sc->seg_buf.p, m->sc->ws.p, lm, opts, d_hyps, d_tokens, out_stride, nullptr,
-                         nullptr, s);
+                         nullptr, s, bias, bopts);
 }
 
 extern "C" int ss_batch_ctc_beam(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int beam,
@@ -261,6 +264,14 @@ extern "C" int ss_batch_ctc_beam_lm(ss_model* m, void* stream, int head, int B, 
                                     int cand, int nbest, ss_ctc_beam_lm_hyp* d_hyps, int32_t* d_tokens, int out_stride,
                                     const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts) {
   return batch_ctc_beam(m, stream, head, B, d_enc_out, h_Tp, beam, cand, nbest, d_hyps, d_tokens, out_stride, true, lm, opts);
+}
+
+extern "C" int ss_batch_ctc_beam_bias(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp, int beam,
+                                      int cand, int nbest, ss_ctc_beam_bias_hyp* d_hyps, int32_t* d_tokens, int out_stride,
+                                      const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, const ss_ctc_bias* bias,
+                                      const ss_ctc_bias_opts* bias_opts) {
+  return batch_ctc_beam(m, stream, head, B, d_enc_out, h_Tp, beam, cand, nbest, d_hyps, d_tokens, out_stride, lm != nullptr, lm, opts, true,
+                        bias, bias_opts);
 }
 
 // Batched beam-1 search: all utterances start from [</s>] and advance in lockstep, one row per

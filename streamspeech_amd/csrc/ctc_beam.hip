@@ -12,10 +12,14 @@
 // with a back-off n-gram model (ngram_lm.hpp) fused into the order of a frame's entries.  And each of the four has a RESUMABLE form
 // (ctc_stream_search_kernel / _lm_kernel, ctc_stream_host_run; the object and its entry points: ctc_stream.hip): the same body
 // over a slot's state that outlives the launch, for the frames a call brings, with the stable prefix of the beam at the end.
+// The BIAS forms (ctc_beam_search_bias_kernel / _lm_bias_kernel and their resumable pair; ctc_beam.hpp, ctc_bias.hpp) are the same
+// body once more, with a hotword set's phrase automaton as one more term of the bonus, alone or beside the model.
 #include "ctc_beam.hpp"
 
 #include <cstring>
+#include <type_traits>
 
+#include "ctc_bias.hpp"
 #include "ngram_lm.hpp"
 
 #include "../../include/streamspeech_hip.h"
@@ -113,17 +117,31 @@ struct CtcBeamLm {
   int* n_state;
 };
 
+// The bias forms (FORM & CTC_FORM_BIAS; ctc_beam.hpp, ctc_bias.hpp) keep their key where the LM form does -- e_fus and b_bonus,
+// nothing more per entry or beam slot -- pass B adds the automaton's step from the parent's b_state to the lookup of a live
+// extension that is not in the trie, pass D gives a new node its bias_sum and b_state, and the end takes the finish term off fin.
+// The arrays are indexed as the LM's: [nodes] of the pack, or [S][nodes] of a resumable object's slots.
+struct CtcBeamBias {
+  BiasView bv;
+  double scale;
+  int finish, pad_;
+  double* n_bsum;
+  int* n_bstate;
+};
+
 // The resumable form (RES = true; ctc_beam.hpp, ss_ctc_stream_advance) is the same body again: workgroup b serves session R.sess[b],
 // whose trie, table and stored beam are its slot's (R); the beam is loaded where the one-shot form makes the root (a call that
 // starts at frame 0 makes the root), the loop runs the absolute frames [f, upto) over the stacked new rows, the beam is stored
 // back, the n-best are written as the one-shot form writes them (the eos term only in the utterance's last call), and one pass
 // more finds the stable prefix.  segs / keys_all / vals_all / nodes_all are unused.  The one-shot forms compile to what they were.
-template <bool LM, bool RES>
+template <int FORM, bool RES>
 __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ logits, int ld, const CtcBeamSeg* __restrict__ segs,
                                                      int beam, int C, int nbest, const float* den, const int* cand_id,
                                                      unsigned long long* keys_all, int* vals_all, int2* nodes_all, void* hyps_out,
-                                                     int* tokens, int out_stride, const CtcBeamLm& L, const CtcStreamDev& R) {
+                                                     int* tokens, int out_stride, const CtcBeamLm& L, const CtcStreamDev& R,
+                                                     const CtcBeamBias& Z) {
   constexpr int MB = CTC_BEAM_MAX_BEAM;
+  constexpr bool LM = (FORM & CTC_FORM_LM) != 0, BIAS = (FORM & CTC_FORM_BIAS) != 0, FUSED = FORM != 0;
   __shared__ double b_pb[2 * MB], b_pnb[2 * MB], b_tot[2 * MB];
   __shared__ int b_node[2 * MB], b_last[2 * MB];
   __shared__ double s_pb[MB], s_pnb[MB], s_give[MB];
@@ -132,7 +150,7 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
   __shared__ int s_c[CTC_BEAM_MAX_CAND];
   __shared__ float s_lpc[CTC_BEAM_MAX_CAND], s_lpl[MB], s_lp0;
   __shared__ int s_nb[2];
-  __shared__ double e_fus[LM ? CTC_BEAM_MAX_ENT : 1], b_bonus[LM ? 2 * MB : 1];
+  __shared__ double e_fus[FUSED ? CTC_BEAM_MAX_ENT : 1], b_bonus[FUSED ? 2 * MB : 1];
   const int tid = threadIdx.x;
   CtcBeamSeg sg;                                               // RES: the slot's offsets; row0 + t is the row of ABSOLUTE frame t
   CtcStreamSess se{};
@@ -148,13 +166,15 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
   int* vals = (RES ? R.vals : vals_all) + sg.tab_off;
   int2* nodes = (RES ? R.nodes : nodes_all) + sg.node_off;
   double* n_sum = LM ? (RES ? R.n_sum : L.n_sum) + sg.node_off : nullptr;
-  double* n_bonus = LM ? (RES ? R.n_bonus : L.n_bonus) + sg.node_off : nullptr;
+  double* n_bonus = FUSED ? (RES ? R.n_bonus : L.n_bonus) + sg.node_off : nullptr;
   int* n_state = LM ? (RES ? R.n_state : L.n_state) + sg.node_off : nullptr;
+  double* n_bsum = BIAS ? Z.n_bsum + sg.node_off : nullptr;
+  int* n_bstate = BIAS ? Z.n_bstate + sg.node_off : nullptr;
   const int mask = sg.tab_mask, W = C + 1;
   double* st_f64 = RES ? R.b_f64 + (size_t)se.slot * 4 * beam : nullptr;   // the stored beam of the slot
   int* st_i32 = RES ? R.b_i32 + (size_t)se.slot * (2 * beam + 2) : nullptr;
   const CtcBeamFrame F{b_pb, b_pnb, b_tot, b_bonus, b_node, b_last, s_pb, s_pnb, s_give, e_tot, e_fus, e_node,
-                       s_c,  s_lpc, s_lpl, &s_lp0,  keys,   vals,   mask, n_bonus, n_state};
+                       s_c,  s_lpc, s_lpl, &s_lp0,  keys,   vals,   mask, n_bonus, n_state, n_bstate};
   bool bad = false;
   if (!RES || t0 == 0) {
     if (tid == 0) {
@@ -162,6 +182,7 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
       s_nb[0] = 1;
       nodes[0] = make_int2(-1, -1);
       if constexpr (LM) { b_bonus[0] = 0.0; n_sum[0] = 0.0; n_bonus[0] = 0.0; n_state[0] = L.lm.start; }
+      if constexpr (BIAS) { b_bonus[0] = 0.0; n_bonus[0] = 0.0; n_bsum[0] = 0.0; n_bstate[0] = 0; }
     }
   } else if constexpr (RES) {
     const int nb = st_i32[2 * beam];                           // (uniform; at most beam)
@@ -169,7 +190,7 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
     if (bad) t0 = sg.T;
     if (tid < nb) {
       b_pb[tid] = st_f64[tid]; b_pnb[tid] = st_f64[beam + tid]; b_tot[tid] = st_f64[2 * beam + tid];
-      if constexpr (LM) b_bonus[tid] = st_f64[3 * beam + tid];
+      if constexpr (FUSED) b_bonus[tid] = st_f64[3 * beam + tid];
       b_node[tid] = st_i32[tid]; b_last[tid] = st_i32[beam + tid];
     }
     if (tid == 0) s_nb[0] = nb;
@@ -198,15 +219,15 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
     __syncthreads();
     // ---- B ----
     const int n_ent = nb * W;
-    for (int e = tid; e < n_ent; e += 256) ctc_beam_entry_b<LM>(F, co, nb, W, e, L.lm, L.lm_weight, L.word_score);
+    for (int e = tid; e < n_ent; e += 256) ctc_beam_entry_b<FORM>(F, co, nb, W, e, L.lm, L.lm_weight, L.word_score, Z.bv, Z.scale);
     __syncthreads();
     // ---- C ----
-    if (tid < nb) ctc_beam_entry_c<LM>(F, co, W, tid);
+    if (tid < nb) ctc_beam_entry_c<FORM>(F, co, W, tid);
     __syncthreads();
     // ---- D ---- (a thread's up to PER entries count in ONE walk over the frame's totals: each total is read once per thread,
     //               and no exit depends on a count, so the loads of the unrolled walk overlap)
     constexpr int PER = (CTC_BEAM_MAX_ENT + 255) / 256;
-    const double* e_key = LM ? e_fus : e_tot;                  // (a compile-time choice: what the order compares)
+    const double* e_key = FUSED ? e_fus : e_tot;               // (a compile-time choice: what the order compares)
     double my_tot[PER];
     int my_rank[PER];
 #pragma unroll
@@ -228,19 +249,19 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
       const int e = tid + 256 * j, rank = my_rank[j];
       double tot = my_tot[j];
       if (!(tot > -INFINITY) || rank >= beam) continue;       // (an entry past n_ent is -inf)
-      if constexpr (LM) tot = e_tot[e];                        // the state keeps the pure CTC total
+      if constexpr (FUSED) tot = e_tot[e];                     // the state keeps the pure CTC total
       const int i = e / W, k = e - i * W - 1;
       int node = e_node[e];
       if (k < 0) {
         b_pb[no + rank] = s_pb[i]; b_pnb[no + rank] = s_pnb[i]; b_last[no + rank] = b_last[co + i];
-        if constexpr (LM) b_bonus[no + rank] = b_bonus[co + i];
+        if constexpr (FUSED) b_bonus[no + rank] = b_bonus[co + i];
       } else {
         const int c = s_c[k];
         if (node < 0)                                          // a new string
-          node = ctc_beam_make_node<LM>(t, beam, rank, b_node[co + i], c, LM ? b_bonus[co + i] : 0.0, keys, vals, mask, nodes, n_sum,
-                                        n_bonus, n_state, L.lm, L.lm_weight, L.word_score);
+          node = ctc_beam_make_node<FORM>(t, beam, rank, b_node[co + i], c, FUSED ? b_bonus[co + i] : 0.0, keys, vals, mask, nodes,
+                                          n_sum, n_bonus, n_state, L.lm, L.lm_weight, L.word_score, n_bsum, n_bstate, Z.bv, Z.scale);
         b_pb[no + rank] = -INFINITY; b_pnb[no + rank] = tot; b_last[no + rank] = c;
-        if constexpr (LM) b_bonus[no + rank] = n_bonus[node];
+        if constexpr (FUSED) b_bonus[no + rank] = n_bonus[node];
       }
       b_tot[no + rank] = tot; b_node[no + rank] = node;
       atomicMax(&s_nb[cur ^ 1], rank + 1);                     // ranks are 0 .. alive - 1 without a gap
@@ -252,12 +273,12 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
     const int nb = bad ? 0 : s_nb[cur];
     if (tid < nb) {
       st_f64[tid] = b_pb[cur * MB + tid]; st_f64[beam + tid] = b_pnb[cur * MB + tid]; st_f64[2 * beam + tid] = b_tot[cur * MB + tid];
-      if constexpr (LM) st_f64[3 * beam + tid] = b_bonus[cur * MB + tid];
+      if constexpr (FUSED) st_f64[3 * beam + tid] = b_bonus[cur * MB + tid];
       st_i32[tid] = b_node[cur * MB + tid]; st_i32[beam + tid] = b_last[cur * MB + tid];
     }
     if (tid == 0) { st_i32[2 * beam] = nb; st_i32[2 * beam + 1] = bad ? 1 : 0; }
   }
-  if constexpr (!LM) {
+  if constexpr (!FUSED) {
     // ---- the n-best: the last beam in rank order; thread r walks prefix r back through the trie ----
     ss_ctc_beam_hyp* hyps = static_cast<ss_ctc_beam_hyp*>(hyps_out);
     if (tid < nbest) {
@@ -273,15 +294,23 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
       hyps[(size_t)blockIdx.x * nbest + tid] = h;
     }
   } else {
-    // ---- the n-best of the LM form: thread r finishes prefix r of the last beam (all of it: the eos term can lift a prefix
-    //      from behind the first nbest), the beam is ranked by fin (s_give), and a prefix of rank < nbest walks back ----
-    ss_ctc_beam_lm_hyp* hyps = static_cast<ss_ctc_beam_lm_hyp*>(hyps_out);
+    // ---- the n-best of the LM and bias forms: thread r finishes prefix r of the last beam (all of it: the eos and finish terms
+    //      can lift a prefix from behind the first nbest), the beam is ranked by fin (s_give), and a prefix of rank < nbest walks
+    //      back ----
+    typedef typename std::conditional<BIAS, ss_ctc_beam_bias_hyp, ss_ctc_beam_lm_hyp>::type Hyp;
+    Hyp* hyps = static_cast<Hyp*>(hyps_out);
     const int nb = bad ? 0 : s_nb[cur];                        // (uniform, as the barrier below)
     double fin = -INFINITY, lm_sum = 0.0;
+    [[maybe_unused]] double bias_sum = 0.0;
     if (tid < nb) {
       const int node = b_node[cur * MB + tid];
-      ctc_beam_finish(b_tot[cur * MB + tid], b_bonus[cur * MB + tid], n_sum[node], n_state[node],
-                      L.eos_term && (!RES || se.fin) ? L.lm.eos : -1, L.lm, L.lm_weight, &fin, &lm_sum);
+      if constexpr (LM)
+        ctc_beam_finish(b_tot[cur * MB + tid], b_bonus[cur * MB + tid], n_sum[node], n_state[node],
+                        L.eos_term && (!RES || se.fin) ? L.lm.eos : -1, L.lm, L.lm_weight, &fin, &lm_sum);
+      else
+        fin = b_tot[cur * MB + tid] + b_bonus[cur * MB + tid];
+      if constexpr (BIAS)
+        ctc_beam_bias_finish(Z.bv, n_bstate[node], n_bsum[node], Z.scale, Z.finish && (!RES || se.fin), &fin, &bias_sum);
       s_give[tid] = fin;
     }
     __syncthreads();
@@ -289,15 +318,17 @@ __device__ __forceinline__ void ctc_beam_search_body(const float* __restrict__ l
       int rank = 0;
       for (int f = 0; f < nb; ++f) rank += ctc_beam_before(s_give[f], f, fin, tid);
       if (rank < nbest) {
-        ss_ctc_beam_lm_hyp h;
+        Hyp h;
         h.n_tokens = ctc_beam_trace(nodes, b_node[cur * MB + tid], tokens + ((size_t)blockIdx.x * nbest + rank) * out_stride);
         h.score = fin; h.ctc_score = b_tot[cur * MB + tid]; h.lm_score = lm_sum; h.status = 0;
+        if constexpr (BIAS) h.bias_score = bias_sum;
         hyps[(size_t)blockIdx.x * nbest + rank] = h;
       }
     } else if (tid < nbest) {                                  // an empty slot
-      ss_ctc_beam_lm_hyp h;
+      Hyp h;
       h.score = h.ctc_score = bad ? (double)__builtin_nanf("") : -INFINITY;
       h.lm_score = 0.0; h.n_tokens = 0; h.status = bad ? 2 : 1;
+      if constexpr (BIAS) h.bias_score = 0.0;
       hyps[(size_t)blockIdx.x * nbest + tid] = h;
     }
   }
@@ -318,8 +349,8 @@ __global__ __launch_bounds__(256) void ctc_beam_search_kernel(const float* __res
                                                               int beam, int C, int nbest, const float* den, const int* cand_id,
                                                               unsigned long long* keys_all, int* vals_all, int2* nodes_all,
                                                               ss_ctc_beam_hyp* hyps, int* tokens, int out_stride) {
-  ctc_beam_search_body<false, false>(logits, ld, segs, beam, C, nbest, den, cand_id, keys_all, vals_all, nodes_all, hyps, tokens,
-                                     out_stride, CtcBeamLm{}, CtcStreamDev{});
+  ctc_beam_search_body<0, false>(logits, ld, segs, beam, C, nbest, den, cand_id, keys_all, vals_all, nodes_all, hyps, tokens,
+                                 out_stride, CtcBeamLm{}, CtcStreamDev{}, CtcBeamBias{});
 }
 
 __global__ __launch_bounds__(256) void ctc_beam_search_lm_kernel(const float* __restrict__ logits, int ld,
@@ -327,23 +358,59 @@ __global__ __launch_bounds__(256) void ctc_beam_search_lm_kernel(const float* __
                                                                  const float* den, const int* cand_id, unsigned long long* keys_all,
                                                                  int* vals_all, int2* nodes_all, ss_ctc_beam_lm_hyp* hyps, int* tokens,
                                                                  int out_stride, CtcBeamLm L) {
-  ctc_beam_search_body<true, false>(logits, ld, segs, beam, C, nbest, den, cand_id, keys_all, vals_all, nodes_all, hyps, tokens,
-                                    out_stride, L, CtcStreamDev{});
+  ctc_beam_search_body<CTC_FORM_LM, false>(logits, ld, segs, beam, C, nbest, den, cand_id, keys_all, vals_all, nodes_all, hyps, tokens,
+                                           out_stride, L, CtcStreamDev{}, CtcBeamBias{});
+}
+
+// The bias forms: L carries the bonus array (and the model, in the LM + bias form; unused otherwise), Z the hotword set.
+__global__ __launch_bounds__(256) void ctc_beam_search_bias_kernel(const float* __restrict__ logits, int ld,
+                                                                   const CtcBeamSeg* __restrict__ segs, int beam, int C, int nbest,
+                                                                   const float* den, const int* cand_id, unsigned long long* keys_all,
+                                                                   int* vals_all, int2* nodes_all, ss_ctc_beam_bias_hyp* hyps,
+                                                                   int* tokens, int out_stride, CtcBeamLm L, CtcBeamBias Z) {
+  ctc_beam_search_body<CTC_FORM_BIAS, false>(logits, ld, segs, beam, C, nbest, den, cand_id, keys_all, vals_all, nodes_all, hyps,
+                                             tokens, out_stride, L, CtcStreamDev{}, Z);
+}
+
+__global__ __launch_bounds__(256) void ctc_beam_search_lm_bias_kernel(const float* __restrict__ logits, int ld,
+                                                                      const CtcBeamSeg* __restrict__ segs, int beam, int C, int nbest,
+                                                                      const float* den, const int* cand_id,
+                                                                      unsigned long long* keys_all, int* vals_all, int2* nodes_all,
+                                                                      ss_ctc_beam_bias_hyp* hyps, int* tokens, int out_stride,
+                                                                      CtcBeamLm L, CtcBeamBias Z) {
+  ctc_beam_search_body<CTC_FORM_LM | CTC_FORM_BIAS, false>(logits, ld, segs, beam, C, nbest, den, cand_id, keys_all, vals_all,
+                                                           nodes_all, hyps, tokens, out_stride, L, CtcStreamDev{}, Z);
 }
 
 // The resumable kernels: one workgroup per session of the call (R.sess), logits the stacked new rows.
 __global__ __launch_bounds__(256) void ctc_stream_search_kernel(const float* __restrict__ logits, int ld, int beam, int C, int nbest,
                                                                 const float* den, const int* cand_id, ss_ctc_beam_hyp* hyps,
                                                                 int* tokens, int out_stride, CtcStreamDev R) {
-  ctc_beam_search_body<false, true>(logits, ld, nullptr, beam, C, nbest, den, cand_id, nullptr, nullptr, nullptr, hyps, tokens,
-                                    out_stride, CtcBeamLm{}, R);
+  ctc_beam_search_body<0, true>(logits, ld, nullptr, beam, C, nbest, den, cand_id, nullptr, nullptr, nullptr, hyps, tokens,
+                                out_stride, CtcBeamLm{}, R, CtcBeamBias{});
 }
 
 __global__ __launch_bounds__(256) void ctc_stream_search_lm_kernel(const float* __restrict__ logits, int ld, int beam, int C, int nbest,
                                                                    const float* den, const int* cand_id, ss_ctc_beam_lm_hyp* hyps,
                                                                    int* tokens, int out_stride, CtcBeamLm L, CtcStreamDev R) {
-  ctc_beam_search_body<true, true>(logits, ld, nullptr, beam, C, nbest, den, cand_id, nullptr, nullptr, nullptr, hyps, tokens,
-                                   out_stride, L, R);
+  ctc_beam_search_body<CTC_FORM_LM, true>(logits, ld, nullptr, beam, C, nbest, den, cand_id, nullptr, nullptr, nullptr, hyps, tokens,
+                                          out_stride, L, R, CtcBeamBias{});
+}
+
+__global__ __launch_bounds__(256) void ctc_stream_search_bias_kernel(const float* __restrict__ logits, int ld, int beam, int C, int nbest,
+                                                                     const float* den, const int* cand_id, ss_ctc_beam_bias_hyp* hyps,
+                                                                     int* tokens, int out_stride, CtcBeamLm L, CtcStreamDev R,
+                                                                     CtcBeamBias Z) {
+  ctc_beam_search_body<CTC_FORM_BIAS, true>(logits, ld, nullptr, beam, C, nbest, den, cand_id, nullptr, nullptr, nullptr, hyps, tokens,
+                                            out_stride, L, R, Z);
+}
+
+__global__ __launch_bounds__(256) void ctc_stream_search_lm_bias_kernel(const float* __restrict__ logits, int ld, int beam, int C,
+                                                                        int nbest, const float* den, const int* cand_id,
+                                                                        ss_ctc_beam_bias_hyp* hyps, int* tokens, int out_stride,
+                                                                        CtcBeamLm L, CtcStreamDev R, CtcBeamBias Z) {
+  ctc_beam_search_body<CTC_FORM_LM | CTC_FORM_BIAS, true>(logits, ld, nullptr, beam, C, nbest, den, cand_id, nullptr, nullptr, nullptr,
+                                                          hyps, tokens, out_stride, L, R, Z);
 }
 
 size_t ctc_beam_table_bytes(const CtcBeamPlan& p) { return p.segs.size() * sizeof(CtcBeamSeg); }
@@ -363,13 +430,19 @@ static int launch_ctc_beam_cand(const float* logits, int ld, int V, int pad, int
 }
 
 // lm == nullptr: the plain search, hyps an ss_ctc_beam_hyp array; else the LM form (d_work holds plan.work_bytes_lm()), hyps an
-// ss_ctc_beam_lm_hyp array.
+// ss_ctc_beam_lm_hyp array.  bias != nullptr: a bias form, with or without lm (d_work holds plan.work_bytes_form(form)), hyps an
+// ss_ctc_beam_bias_hyp array.
 int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
                     const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, void* hyps, int* tokens, int out_stride, float* den_out,
-                    int* cand_out, hipStream_t stream) {
+                    int* cand_out, hipStream_t stream, const ss_ctc_bias* bias, const ss_ctc_bias_opts* bopts) {
   const int B = (int)p.segs.size();
   if (!logits || ld < V || B <= 0 || !d_table || !d_work || !hyps || !tokens) return SS_ERR_ARG;
   CtcBeamLm L{};
+  CtcBeamBias Z{};
+  if (bias) {
+    RET(ctc_beam_bias_check(bias, V, pad, unk, bopts, lm, opts));
+    RET(bias_device_view(bias, &Z.bv));
+  }
   if (lm) {
     RET(ctc_beam_lm_check(lm, V, opts));
     RET(ngram_device_view(lm, &L.lm));
@@ -385,7 +458,22 @@ int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const 
   SS_HIP_CHECK(hipMemcpyAsync(d_table, p.segs.data(), ctc_beam_table_bytes(p), hipMemcpyHostToDevice, stream));
   SS_HIP_CHECK(hipMemsetAsync(keys, 0xff, p.key_bytes(), stream));
   RET(launch_ctc_beam_cand(logits, ld, V, pad, unk, p.rows, p.cand, den, cand, stream));
-  if (!lm) {
+  if (bias) {
+    const int form = CTC_FORM_BIAS | (lm ? CTC_FORM_LM : 0);
+    const CtcFormNodes fn = ctc_form_carve(w + p.lm_off(), (size_t)p.nodes, form);
+    if (lm) { L.lm_weight = opts->lm_weight; L.word_score = opts->word_score; L.eos_term = opts->eos_term ? 1 : 0; }
+    L.n_sum = fn.n_sum; L.n_bonus = fn.n_bonus; L.n_state = fn.n_state;
+    Z.scale = bopts->scale; Z.finish = bopts->finish ? 1 : 0;
+    Z.n_bsum = fn.n_bsum; Z.n_bstate = fn.n_bstate;
+    if (lm)
+      hipLaunchKernelGGL(ctc_beam_search_lm_bias_kernel, dim3(B), dim3(256), 0, stream, logits, ld,
+                         static_cast<const CtcBeamSeg*>(d_table), p.beam, p.cand, p.nbest, den, cand, keys, vals, nodes,
+                         static_cast<ss_ctc_beam_bias_hyp*>(hyps), tokens, out_stride, L, Z);
+    else
+      hipLaunchKernelGGL(ctc_beam_search_bias_kernel, dim3(B), dim3(256), 0, stream, logits, ld,
+                         static_cast<const CtcBeamSeg*>(d_table), p.beam, p.cand, p.nbest, den, cand, keys, vals, nodes,
+                         static_cast<ss_ctc_beam_bias_hyp*>(hyps), tokens, out_stride, L, Z);
+  } else if (!lm) {
     hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(B), dim3(256), 0, stream, logits, ld, static_cast<const CtcBeamSeg*>(d_table),
                        p.beam, p.cand, p.nbest, den, cand, keys, vals, nodes, static_cast<ss_ctc_beam_hyp*>(hyps), tokens, out_stride);
   } else {
@@ -403,14 +491,27 @@ int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const 
 
 int launch_ctc_stream(const float* logits, int ld, int V, int pad, int unk, int rows, int n, const CtcStreamSess* h_sess, void* d_sess,
                       float* den, int* cand_id, int beam, int C, int nbest, CtcStreamDev dev, const ss_ngram_lm* lm,
-                      const ss_ctc_lm_opts* opts, void* hyps, int* tokens, int out_stride, CtcStreamPart* part, hipStream_t stream) {
+                      const ss_ctc_lm_opts* opts, void* hyps, int* tokens, int out_stride, CtcStreamPart* part, hipStream_t stream,
+                      const ss_ctc_bias* bias, const ss_ctc_bias_opts* bopts, CtcStreamBiasDev bdev) {
   CtcBeamLm L{};
+  CtcBeamBias Z{};
   if (lm) RET(ngram_device_view(lm, &L.lm));
+  if (bias) RET(bias_device_view(bias, &Z.bv));
   SS_HIP_CHECK(hipMemcpyAsync(d_sess, h_sess, (size_t)n * sizeof(CtcStreamSess), hipMemcpyHostToDevice, stream));
   if (rows > 0) RET(launch_ctc_beam_cand(logits, ld, V, pad, unk, rows, C, den, cand_id, stream));
   dev.sess = static_cast<const CtcStreamSess*>(d_sess);
   dev.part = part;
-  if (!lm) {
+  if (bias) {
+    if (lm) { L.lm_weight = opts->lm_weight; L.word_score = opts->word_score; L.eos_term = opts->eos_term ? 1 : 0; }
+    Z.scale = bopts->scale; Z.finish = bopts->finish ? 1 : 0;
+    Z.n_bsum = bdev.n_bsum; Z.n_bstate = bdev.n_bstate;
+    if (lm)
+      hipLaunchKernelGGL(ctc_stream_search_lm_bias_kernel, dim3(n), dim3(256), 0, stream, logits, ld, beam, C, nbest, den, cand_id,
+                         static_cast<ss_ctc_beam_bias_hyp*>(hyps), tokens, out_stride, L, dev, Z);
+    else
+      hipLaunchKernelGGL(ctc_stream_search_bias_kernel, dim3(n), dim3(256), 0, stream, logits, ld, beam, C, nbest, den, cand_id,
+                         static_cast<ss_ctc_beam_bias_hyp*>(hyps), tokens, out_stride, L, dev, Z);
+  } else if (!lm) {
     hipLaunchKernelGGL(ctc_stream_search_kernel, dim3(n), dim3(256), 0, stream, logits, ld, beam, C, nbest, den, cand_id,
                        static_cast<ss_ctc_beam_hyp*>(hyps), tokens, out_stride, dev);
   } else {

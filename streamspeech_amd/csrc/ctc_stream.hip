@@ -5,6 +5,7 @@
 // kernel is ctc_beam.hip's, the twin ctc_beam_host.hip's, and the frame both run is ctc_beam.hpp's: there is one statement of a frame.
 #include "model_internal.hpp"
 #include "ctc_beam.hpp"
+#include "ctc_bias.hpp"
 #include "ngram_lm.hpp"
 
 int launch_pool_stack_rows(float* out, const float* enc, int W, const int* src, const int* pre, int nsess, int total,
@@ -15,10 +16,14 @@ struct ss_ctc_stream {
   int S = 0, max_frames = 0, beam = 0, cand = 0, nbest = 0;
   const ss_ngram_lm* lm = nullptr;
   ss_ctc_lm_opts opts{};
+  const ss_ctc_bias* bias = nullptr; // a hotword set (ss_ctc_stream_create_bias): the bias forms, records ss_ctc_beam_bias_hyp
+  ss_ctc_bias_opts bopts{};
   ss_scratch* sc = nullptr;          // the set the state is booked on (ss_ctc_stream_create), else null
   bool on_device = false;
   DevBuf buf;                        // the slots' state, ctc_stream_carve'd into dev
   CtcStreamDev dev{};
+  CtcStreamBiasDev bdev{nullptr, nullptr};
+  int form() const { return (lm ? CTC_FORM_LM : 0) | (bias ? CTC_FORM_BIAS : 0); }
   std::vector<CtcBeamHostState> host;   // ... or the twin's, one per slot
   std::vector<int> frames;           // frames consumed per slot
   std::vector<char> dirty;           // the slot's child table holds an earlier utterance's keys (or nothing yet): cleared at its next advance
@@ -27,7 +32,8 @@ struct ss_ctc_stream {
 namespace {
 
 int stream_make(int V, int pad, int unk, int max_sessions, int max_frames, int beam, int cand, int nbest, const ss_ngram_lm* lm,
-                const ss_ctc_lm_opts* opts, ss_ctc_stream** out) {
+                const ss_ctc_lm_opts* opts, ss_ctc_stream** out, bool with_bias = false, const ss_ctc_bias* bias = nullptr,
+                const ss_ctc_bias_opts* bopts = nullptr) {
   if (!out) return SS_ERR_ARG;
   *out = nullptr;
   if (max_sessions <= 0 || max_sessions > (1 << 16) || max_frames < 1 || max_frames > CTC_BEAM_MAX_T || (lm == nullptr) != (opts == nullptr))
@@ -35,8 +41,10 @@ int stream_make(int V, int pad, int unk, int max_sessions, int max_frames, int b
   CtcBeamPlan plan;                  // the limits of the one-shot calls, on one utterance of max_frames
   const int32_t T1 = max_frames;
   RET(ctc_beam_plan(V, 1, &T1, beam, cand, nbest, max_frames, plan));
+  if (with_bias) RET(ctc_beam_bias_check(bias, V, pad, unk, bopts, lm, opts));
   if (lm) RET(ctc_beam_lm_check(lm, V, opts));
   ss_ctc_stream* cs = new ss_ctc_stream();
+  if (with_bias) { cs->bias = bias; cs->bopts = *bopts; }
   cs->V = V; cs->pad = pad; cs->unk = unk;
   cs->S = max_sessions; cs->max_frames = max_frames; cs->beam = beam; cs->cand = cand; cs->nbest = nbest;
   cs->lm = lm;
@@ -48,8 +56,8 @@ int stream_make(int V, int pad, int unk, int max_sessions, int max_frames, int b
 }
 
 int stream_alloc_device(ss_ctc_stream* cs) {
-  RET(cs->buf.ensure((size_t)cs->S * ctc_stream_slot_bytes(cs->beam, cs->max_frames, cs->lm != nullptr), true));
-  ctc_stream_carve(cs->buf.p, cs->S, cs->beam, cs->max_frames, cs->lm != nullptr, &cs->dev);
+  RET(cs->buf.ensure((size_t)cs->S * ctc_stream_slot_bytes(cs->beam, cs->max_frames, cs->form()), true));
+  ctc_stream_carve(cs->buf.p, cs->S, cs->beam, cs->max_frames, cs->form(), &cs->dev, &cs->bdev);
   cs->on_device = true;
   return SS_OK;
 }
@@ -94,14 +102,16 @@ int stream_clear_device(ss_ctc_stream* cs, const std::vector<CtcStreamSess>& ses
 
 }  // namespace
 
-extern "C" int ss_ctc_stream_create(ss_model* m, int head, int max_sessions, int max_frames, int beam, int cand, int nbest,
-                                    const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, ss_ctc_stream** out) {
+static int stream_create(ss_model* m, int head, int max_sessions, int max_frames, int beam, int cand, int nbest, const ss_ngram_lm* lm,
+                         const ss_ctc_lm_opts* opts, bool with_bias, const ss_ctc_bias* bias, const ss_ctc_bias_opts* bopts,
+                         ss_ctc_stream** out) {
   if (!out) return SS_ERR_ARG;
   *out = nullptr;
   if (!m || head < 0 || head > 1 || (m->cfg.enc_dim & 3) != 0 || m->cfg.enc_dim > 1024) return SS_ERR_ARG;
   const ss_config& c = m->cfg;
   ss_ctc_stream* cs = nullptr;
-  RET(stream_make(head == 0 ? c.src_vocab : c.tgt_vocab, c.pad, c.unk, max_sessions, max_frames, beam, cand, nbest, lm, opts, &cs));
+  RET(stream_make(head == 0 ? c.src_vocab : c.tgt_vocab, c.pad, c.unk, max_sessions, max_frames, beam, cand, nbest, lm, opts, &cs,
+                  with_bias, bias, bopts));
   cs->head = head;
   cs->buf.acct = &m->sc->acct;
   const int rc = stream_alloc_device(cs);   // exact size; refused on the cap (or the device): the set is left as it was
@@ -113,12 +123,24 @@ extern "C" int ss_ctc_stream_create(ss_model* m, int head, int max_sessions, int
   return SS_OK;
 }
 
-extern "C" int ss_debug_ctc_stream_create(int V, int pad, int unk, int on_device, int max_sessions, int max_frames, int beam, int cand,
-                                          int nbest, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, ss_ctc_stream** out) {
+extern "C" int ss_ctc_stream_create(ss_model* m, int head, int max_sessions, int max_frames, int beam, int cand, int nbest,
+                                    const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, ss_ctc_stream** out) {
+  return stream_create(m, head, max_sessions, max_frames, beam, cand, nbest, lm, opts, false, nullptr, nullptr, out);
+}
+
+extern "C" int ss_ctc_stream_create_bias(ss_model* m, int head, int max_sessions, int max_frames, int beam, int cand, int nbest,
+                                         const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, const ss_ctc_bias* bias,
+                                         const ss_ctc_bias_opts* bias_opts, ss_ctc_stream** out) {
+  return stream_create(m, head, max_sessions, max_frames, beam, cand, nbest, lm, opts, true, bias, bias_opts, out);
+}
+
+static int debug_stream_create(int V, int pad, int unk, int on_device, int max_sessions, int max_frames, int beam, int cand, int nbest,
+                               const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, bool with_bias, const ss_ctc_bias* bias,
+                               const ss_ctc_bias_opts* bopts, ss_ctc_stream** out) {
   ss_ctc_stream* cs = nullptr;
   if (!out) return SS_ERR_ARG;
   *out = nullptr;
-  RET(stream_make(V, pad, unk, max_sessions, max_frames, beam, cand, nbest, lm, opts, &cs));
+  RET(stream_make(V, pad, unk, max_sessions, max_frames, beam, cand, nbest, lm, opts, &cs, with_bias, bias, bopts));
   if (on_device) {
     const int rc = stream_alloc_device(cs);
     if (rc != SS_OK) { delete cs; return rc; }
@@ -127,6 +149,17 @@ extern "C" int ss_debug_ctc_stream_create(int V, int pad, int unk, int on_device
   }
   *out = cs;
   return SS_OK;
+}
+
+extern "C" int ss_debug_ctc_stream_create(int V, int pad, int unk, int on_device, int max_sessions, int max_frames, int beam, int cand,
+                                          int nbest, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, ss_ctc_stream** out) {
+  return debug_stream_create(V, pad, unk, on_device, max_sessions, max_frames, beam, cand, nbest, lm, opts, false, nullptr, nullptr, out);
+}
+
+extern "C" int ss_debug_ctc_stream_create_bias(int V, int pad, int unk, int on_device, int max_sessions, int max_frames, int beam,
+                                               int cand, int nbest, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts,
+                                               const ss_ctc_bias* bias, const ss_ctc_bias_opts* bias_opts, ss_ctc_stream** out) {
+  return debug_stream_create(V, pad, unk, on_device, max_sessions, max_frames, beam, cand, nbest, lm, opts, true, bias, bias_opts, out);
 }
 
 extern "C" void ss_ctc_stream_destroy(ss_ctc_stream* cs) {
@@ -188,7 +221,7 @@ extern "C" int ss_ctc_stream_advance(ss_model* m, void* stream, ss_ctc_stream* c
   }
   RET(launch_ctc_stream(logits, V, V, cs->pad, cs->unk, rows, n, sess.data(), m->sc->seg_buf.p, den, cand_id, cs->beam, cs->cand,
                         cs->nbest, cs->dev, cs->lm, cs->lm ? &cs->opts : nullptr, d_hyps, d_tokens, out_stride,
-                        reinterpret_cast<CtcStreamPart*>(d_part), s));
+                        reinterpret_cast<CtcStreamPart*>(d_part), s, cs->bias, cs->bias ? &cs->bopts : nullptr, cs->bdev));
   stream_commit(cs, sess);
   return SS_OK;
 }
@@ -211,7 +244,7 @@ extern "C" int ss_op_ctc_stream_advance(void* stream, ss_ctc_stream* cs, int n, 
   RET(stream_clear_device(cs, sess, s));
   RET(launch_ctc_stream(d_logits, ld, cs->V, cs->pad, cs->unk, rows, n, sess.data(), tmp.p, den, cand_id, cs->beam, cs->cand, cs->nbest,
                         cs->dev, cs->lm, cs->lm ? &cs->opts : nullptr, d_hyps, d_tokens, out_stride,
-                        reinterpret_cast<CtcStreamPart*>(d_part), s));
+                        reinterpret_cast<CtcStreamPart*>(d_part), s, cs->bias, cs->bias ? &cs->bopts : nullptr, cs->bdev));
   stream_commit(cs, sess);
   return SS_OK;
 }
@@ -227,11 +260,12 @@ extern "C" int ss_ctc_stream_advance_host(ss_ctc_stream* cs, int n, const int32_
   RET(stream_check(cs, n, h_slots, nullptr, h_upto, h_final, out_stride, sess, &rows));
   for (const CtcStreamSess& se : sess) {
     if (!cs->dirty[se.slot]) continue;
-    cs->host[se.slot].start(cs->beam, cs->max_frames, cs->lm != nullptr, cs->lm ? cs->lm->host.start : 0);
+    cs->host[se.slot].start(cs->beam, cs->max_frames, cs->form(), cs->lm ? cs->lm->host.start : 0);
     cs->dirty[se.slot] = 0;
   }
   RET(ctc_stream_host_run(cs->host, h_logits, ld, cs->V, cs->pad, cs->unk, n, sess.data(), cs->beam, cs->cand, cs->nbest, cs->lm,
-                          cs->lm ? &cs->opts : nullptr, h_hyps, h_tokens, out_stride, reinterpret_cast<CtcStreamPart*>(h_part)));
+                          cs->lm ? &cs->opts : nullptr, h_hyps, h_tokens, out_stride, reinterpret_cast<CtcStreamPart*>(h_part), cs->bias,
+                          cs->bias ? &cs->bopts : nullptr));
   stream_commit(cs, sess);
   return SS_OK;
 }

@@ -275,20 +275,23 @@ extern "C" int ss_op_ctc_align(void* stream, const float* d_logits, int ld, int 
   return launch_ctc_align(d_logits, ld, V, plan, h_targets, tmp.first.p, tmp.second.p, d_results, d_path, d_first, d_last, d_tok_lprob,
                           d_frame_lprob, (hipStream_t)stream);
 }
-// the two prefix-search kernels on the caller's logits; scratch as ss_op_ctc_align's.  with_lm: the LM form and its refusals.
+// the two prefix-search kernels on the caller's logits; scratch as ss_op_ctc_align's.  with_lm: the LM form and its refusals;
+// with_bias: a bias form (with a model when lm is given) and its refusals.
 static int op_ctc_beam(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam, int cand,
                        int nbest, void* d_hyps, int32_t* d_tokens, int out_stride, float* d_den, int32_t* d_cand_id, bool with_lm,
-                       const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts) {
+                       const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, bool with_bias = false, const ss_ctc_bias* bias = nullptr,
+                       const ss_ctc_bias_opts* bopts = nullptr) {
   if (!d_logits || ld < V || !d_hyps || !d_tokens) return SS_ERR_ARG;
   CtcBeamPlan plan;
   RET(ctc_beam_plan(V, B, h_T, beam, cand, nbest, out_stride, plan));
+  if (with_bias) RET(ctc_beam_bias_check(bias, V, pad, unk, bopts, lm, opts));
   if (with_lm) RET(ctc_beam_lm_check(lm, V, opts));
   static thread_local std::map<hipStream_t, std::pair<DevBuf, DevBuf>> tmps;
   auto& tmp = tmps[(hipStream_t)stream];
   RET(tmp.first.ensure(ctc_beam_table_bytes(plan)));
-  RET(tmp.second.ensure(with_lm ? plan.work_bytes_lm() : plan.work_bytes()));
+  RET(tmp.second.ensure(plan.work_bytes_form((with_lm ? CTC_FORM_LM : 0) | (with_bias ? CTC_FORM_BIAS : 0))));
   return launch_ctc_beam(d_logits, ld, V, pad, unk, plan, tmp.first.p, tmp.second.p, lm, opts, d_hyps, d_tokens, out_stride, d_den,
-                         d_cand_id, (hipStream_t)stream);
+                         d_cand_id, (hipStream_t)stream, bias, bopts);
 }
 extern "C" int ss_op_ctc_beam(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T, int beam,
                               int cand, int nbest, ss_ctc_beam_hyp* d_hyps, int32_t* d_tokens, int out_stride, float* d_den,
@@ -301,6 +304,21 @@ extern "C" int ss_op_ctc_beam_lm(void* stream, const float* d_logits, int ld, in
                                  int32_t* d_cand_id, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts) {
   return op_ctc_beam(stream, d_logits, ld, V, pad, unk, B, h_T, beam, cand, nbest, d_hyps, d_tokens, out_stride, d_den, d_cand_id, true,
                      lm, opts);
+}
+extern "C" int ss_op_ctc_beam_bias(void* stream, const float* d_logits, int ld, int V, int pad, int unk, int B, const int32_t* h_T,
+                                   int beam, int cand, int nbest, ss_ctc_beam_bias_hyp* d_hyps, int32_t* d_tokens, int out_stride,
+                                   float* d_den, int32_t* d_cand_id, const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts,
+                                   const ss_ctc_bias* bias, const ss_ctc_bias_opts* bias_opts) {
+  return op_ctc_beam(stream, d_logits, ld, V, pad, unk, B, h_T, beam, cand, nbest, d_hyps, d_tokens, out_stride, d_den, d_cand_id,
+                     lm != nullptr, lm, opts, true, bias, bias_opts);
+}
+extern "C" int ss_op_ctc_bias_score(void* stream, const ss_ctc_bias* bias, int B, const int32_t* d_tokens, const int32_t* h_n, int finish,
+                                    double* d_delta, int32_t* d_state, double* d_sum) {
+  if (!bias || B <= 0 || !h_n || !d_sum) return SS_ERR_ARG;
+  static thread_local std::map<hipStream_t, DevBuf> tmps;
+  DevBuf& tmp = tmps[(hipStream_t)stream];
+  RET(tmp.ensure(bias_score_table_bytes(B)));
+  return launch_bias_score(bias, B, d_tokens, h_n, finish, d_delta, d_state, d_sum, tmp.p, (hipStream_t)stream);
 }
 extern "C" int ss_op_ngram_score(void* stream, const ss_ngram_lm* lm, int B, const int32_t* d_tokens, const int32_t* h_n, int with_eos,
                                  double* d_lp, int32_t* d_state) {

@@ -8,6 +8,8 @@ struct ss_ctc_beam_hyp;
 struct ss_ctc_beam_lm_hyp;
 struct ss_ctc_lm_opts;
 struct ss_ngram_lm;
+struct ss_ctc_bias;
+struct ss_ctc_bias_opts;
 
 namespace ss {
 
@@ -102,17 +104,25 @@ int launch_ctc_align(const float* logits, int ld, int V, const CtcAlignPlan& p, 
 // ss_ctc_beam_hyp array, d_work holds plan.work_bytes(); else the LM form (ctc_beam.hpp, ngram_lm.hpp), hyps an ss_ctc_beam_lm_hyp
 // array, d_work holds plan.work_bytes_lm(), and ctc_beam_lm_check is every refusal it adds.  d_table (ctc_beam_table_bytes) and
 // d_work are the caller's scratch; den_out / cand_out, when given, receive the first kernel's outputs instead of d_work.  An
-// utterance's outputs are the same bits alone and at any place of any pack.
+// utterance's outputs are the same bits alone and at any place of any pack.  bias != nullptr: a bias form (ctc_bias.hpp), with a
+// model or without (lm and opts both NULL), hyps an ss_ctc_beam_bias_hyp array, d_work holds plan.work_bytes_form(form), and
+// ctc_beam_bias_check is every refusal it adds to the model's.
 struct CtcBeamPlan;
 size_t ctc_beam_table_bytes(const CtcBeamPlan& p);
 int ctc_beam_lm_check(const ss_ngram_lm* lm, int V, const ss_ctc_lm_opts* opts);
+int ctc_beam_bias_check(const ss_ctc_bias* bias, int V, int pad, int unk, const ss_ctc_bias_opts* bopts, const ss_ngram_lm* lm,
+                        const ss_ctc_lm_opts* opts);
 int launch_ctc_beam(const float* logits, int ld, int V, int pad, int unk, const CtcBeamPlan& p, void* d_table, void* d_work,
                     const ss_ngram_lm* lm, const ss_ctc_lm_opts* opts, void* hyps, int* tokens, int out_stride, float* den_out,
-                    int* cand_out, hipStream_t stream);
+                    int* cand_out, hipStream_t stream, const ss_ctc_bias* bias = nullptr, const ss_ctc_bias_opts* bopts = nullptr);
 // The score kernel of ngram_lm.hip: d_table (ngram_score_table_bytes) is the caller's scratch.
 size_t ngram_score_table_bytes(int B);
 int launch_ngram_score(const ss_ngram_lm* lm, int B, const int32_t* d_tokens, const int32_t* h_n, int with_eos, double* d_lp,
                        int32_t* d_state, void* d_table, hipStream_t stream);
+// The score kernel of ctc_bias.hip, likewise.
+size_t bias_score_table_bytes(int B);
+int launch_bias_score(const ss_ctc_bias* bias, int B, const int32_t* d_tokens, const int32_t* h_n, int finish, double* d_delta,
+                      int32_t* d_state, double* d_sum, void* d_table, hipStream_t stream);
 
 // emb_out[k,:] = table[codes[k],:]
 int launch_gather_rows(const int* idx, const float* table, int D, float* out, int n, hipStream_t stream, int rows);  // ids outside [0, rows) read row 0

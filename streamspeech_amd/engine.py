@@ -76,6 +76,26 @@ class CtcHypothesis(NamedTuple):
     ctc_score: Optional[float] = None   # log p_ctc alone, the scale above
     lm_score: Optional[float] = None    # the model's log-probability of the tokens (and </s>, with lm_eos): natural log, unweighted
 
+    @property
+    def bias_score(self) -> Optional[float]:
+        """None: a search without a hotword set (with one the hypotheses are CtcBiasHypothesis, which carry it)."""
+        return None
+
+
+class CtcBiasHypothesis(NamedTuple):
+    """One hypothesis of batch_ctc_beam(bias=...): CtcHypothesis with a trailing bias_score.  score is the fused one, log p_ctc
+    [+ lm_weight * lm_score + word_score * n] + bias_scale * bias_score."""
+    tokens: List[int]
+    score: float
+    ctc_score: float
+    lm_score: Optional[float]           # None without a model
+    bias_score: float                   # the hotword set's credit for the tokens, natural log, unscaled; with bias_finish an
+    #                                     unfinished phrase at the end has earned nothing
+
+
+_BIAS_HYP = np.dtype([("score", "<f8"), ("ctc_score", "<f8"), ("lm_score", "<f8"), ("bias_score", "<f8"), ("n_tokens", "<i4"),
+                      ("status", "<i4")])
+
 
 def ctc_beam_default_cand(beam: int) -> int:
     """Candidates per frame when the caller names none: beam + 1, up to the library's cap.  A new string enters the beam only past
@@ -298,7 +318,7 @@ class BatchMixin:
 
     def batch_ctc_beam(self, head: int, enc_packed: torch.Tensor, Tp: List[int], beam: int, cand: Optional[int] = None,
                        nbest: Optional[int] = None, lm=None, lm_weight: float = 0.0, word_score: float = 0.0,
-                       lm_eos: bool = True) -> List[List[CtcHypothesis]]:
+                       lm_eos: bool = True, bias=None, bias_scale: float = 1.0, bias_finish: bool = True) -> List[List[CtcHypothesis]]:
         """CTC prefix beam search on a text head (ss_batch_ctc_beam): per utterance its `nbest` (default: beam) most likely label
         strings, best first, each with the log of the summed probability of its alignments.  The rows are packed as
         batch_ctc_greedy takes them.  Fewer than nbest come back where fewer prefixes are alive, none for an utterance with a NaN
@@ -307,12 +327,29 @@ class BatchMixin:
         more than L.CTC_BEAM_MAX_FRAMES frames per utterance.
         lm (an ngram.NgramLM over this head's dictionary): shallow fusion (ss_batch_ctc_beam_lm) -- the hypotheses are ranked by
         log p_ctc + lm_weight * log p_lm + word_score * n_tokens, the lm term with the model's </s> when lm_eos, and each carries
-        ctc_score and lm_score besides the fused score.  Without lm the call and its tuples are the plain ones."""
+        ctc_score and lm_score besides the fused score.  Without lm the call and its tuples are the plain ones.
+        bias (a hotwords.CtcBias over this head's dictionary): hotword biasing (ss_batch_ctc_beam_bias), with lm or without --
+        bias_scale * (the set's credit for the string) joins the fused score, an unfinished phrase at the end earns nothing when
+        bias_finish, and the hypotheses are CtcBiasHypothesis.  Without bias the call and its tuples are what they were."""
         B = len(Tp)
         cand = ctc_beam_default_cand(beam) if cand is None else int(cand)
         nbest = int(beam) if nbest is None else int(nbest)
         stride = max([int(t) for t in Tp] + [1])
         n = B * max(nbest, 0)
+        if bias is not None:
+            # int32 words: hyps [10 n] (four doubles and two ints each) | tokens [n][stride]
+            ibuf = torch.empty((10 * n + n * stride + 1,), dtype=torch.int32, device=self.device)
+            opts = C.byref(L.SSCtcLmOpts(float(lm_weight), float(word_score), int(bool(lm_eos)))) if lm is not None else None
+            bopts = L.SSCtcBiasOpts(float(bias_scale), int(bool(bias_finish)), 0)
+            L.check(self.lib.ss_batch_ctc_beam_bias(self.h, _stream(), head, B, _ptr(enc_packed), _i32(Tp), int(beam), cand, nbest,
+                                                    _ptr(ibuf), _ptr(ibuf[10 * n:]), stride, lm.h if lm is not None else None, opts,
+                                                    bias.h, C.byref(bopts)), "ss_batch_ctc_beam_bias")
+            host = ibuf.cpu().numpy()
+            hyp = host[:10 * n].view(_BIAS_HYP)
+            return [[CtcBiasHypothesis(host[10 * n + k * stride: 10 * n + k * stride + int(hyp["n_tokens"][k])].tolist(),
+                                       float(hyp["score"][k]), float(hyp["ctc_score"][k]),
+                                       float(hyp["lm_score"][k]) if lm is not None else None, float(hyp["bias_score"][k]))
+                     for k in range(b * nbest, (b + 1) * nbest) if hyp["status"][k] == 0] for b in range(B)]
         if lm is not None:
             # int32 words: hyps [8 n] (three doubles and two ints each) | tokens [n][stride]
             ibuf = torch.empty((8 * n + n * stride + 1,), dtype=torch.int32, device=self.device)
@@ -1001,10 +1038,10 @@ class HipModel(BatchMixin):
 
     def ctc_beam(self, head: int, enc_out: torch.Tensor, beam: int, cand: Optional[int] = None,
                  nbest: Optional[int] = None, lm=None, lm_weight: float = 0.0, word_score: float = 0.0,
-                 lm_eos: bool = True) -> List[CtcHypothesis]:
+                 lm_eos: bool = True, bias=None, bias_scale: float = 1.0, bias_finish: bool = True) -> List[CtcHypothesis]:
         """CTC prefix beam search of one utterance: the B = 1 call of batch_ctc_beam."""
         return self.batch_ctc_beam(head, enc_out.contiguous(), [int(enc_out.shape[0])], beam, cand, nbest, lm, lm_weight, word_score,
-                                   lm_eos)[0]
+                                   lm_eos, bias, bias_scale, bias_finish)[0]
 
     def ctc_greedy(self, head: int, enc_out: torch.Tensor, want_logits: bool = False, want_scores: bool = False):
         """-> (tokens list, frame index list, raw argmax tensor, logits or None); with want_scores three more: last frame per token
@@ -1449,23 +1486,31 @@ class CtcStream:
     kept on the device between calls.  :meth:`advance` moves any subset of slots forward over encoder rows that are FINAL (the
     incremental encoder's n_final); the utterance's last call gives exactly batch_ctc_beam's n-best on all its frames, every other
     call the n-best of the frames so far and how many leading tokens can no longer change.  beam, cand (default
-    ctc_beam_default_cand), nbest (default beam), the model lm (an ngram.NgramLM; kept alive here) and its weights are fixed at
-    creation; the trie is sized for `max_frames` encoder rows per utterance (at most L.CTC_BEAM_MAX_FRAMES).  The state is booked
+    ctc_beam_default_cand), nbest (default beam), the model lm (an ngram.NgramLM; kept alive here) and its weights, and the hotword
+    set bias (a hotwords.CtcBias; kept alive here: ss_ctc_stream_create_bias, hypotheses CtcBiasHypothesis, the finish term in an
+    utterance's last call alone) and its scale are fixed at creation; the trie is sized for `max_frames` encoder rows per utterance (at most L.CTC_BEAM_MAX_FRAMES).  The state is booked
     on the model's scratch set and released by :meth:`close`."""
 
     def __init__(self, model: "HipModel", head: int, max_sessions: int, max_frames: int, beam: int, cand: Optional[int] = None,
-                 nbest: Optional[int] = None, lm=None, lm_weight: float = 0.0, word_score: float = 0.0, lm_eos: bool = True):
+                 nbest: Optional[int] = None, lm=None, lm_weight: float = 0.0, word_score: float = 0.0, lm_eos: bool = True,
+                 bias=None, bias_scale: float = 1.0, bias_finish: bool = True):
         self.lib, self.model, self.device = model.lib, model, _require_gpu(model.device)
         self.head, self.max_sessions, self.max_frames, self.beam = int(head), int(max_sessions), int(max_frames), int(beam)
         self.cand = ctc_beam_default_cand(beam) if cand is None else int(cand)
         self.nbest = self.beam if nbest is None else int(nbest)
-        self.lm = lm
+        self.lm, self.bias = lm, bias
         opts = C.byref(L.SSCtcLmOpts(float(lm_weight), float(word_score), int(bool(lm_eos)))) if lm is not None else None
         self.h = None
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            L.check(self.lib.ss_ctc_stream_create(model.h, self.head, self.max_sessions, self.max_frames, self.beam, self.cand,
-                                                  self.nbest, lm.h if lm is not None else None, opts, C.byref(h)), "ss_ctc_stream_create")
+            if bias is not None:
+                bopts = L.SSCtcBiasOpts(float(bias_scale), int(bool(bias_finish)), 0)
+                L.check(self.lib.ss_ctc_stream_create_bias(model.h, self.head, self.max_sessions, self.max_frames, self.beam, self.cand,
+                                                           self.nbest, lm.h if lm is not None else None, opts, bias.h, C.byref(bopts),
+                                                           C.byref(h)), "ss_ctc_stream_create_bias")
+            else:
+                L.check(self.lib.ss_ctc_stream_create(model.h, self.head, self.max_sessions, self.max_frames, self.beam, self.cand,
+                                                      self.nbest, lm.h if lm is not None else None, opts, C.byref(h)), "ss_ctc_stream_create")
         self.h = h
 
     def reset(self, slot: int):
@@ -1478,7 +1523,7 @@ class CtcStream:
         n = len(slots)
         stride = max([int(u) for u in upto] + [1])
         k = n * self.nbest
-        w = 8 if self.lm is not None else 4                     # int32 words per hypothesis record
+        w = 10 if self.bias is not None else 8 if self.lm is not None else 4   # int32 words per hypothesis record
         # int32 words: hyps [w k] (first: 8-byte aligned) | parts [4 n] | tokens [k][stride]
         ibuf = torch.empty((w * k + 4 * n + k * stride + 1,), dtype=torch.int32, device=self.device)
         L.check(self.lib.ss_ctc_stream_advance(self.model.h, _stream(), self.h, n, _i32(slots), _ptr(enc_packed), _i32(T), _i32(upto),
@@ -1487,7 +1532,12 @@ class CtcStream:
         host = ibuf.cpu().numpy()
         part = host[w * k: w * k + 4 * n].reshape(n, 4)
         tok = host[w * k + 4 * n:]
-        if self.lm is not None:
+        if self.bias is not None:
+            hyp = host[:w * k].view(_BIAS_HYP)
+            mk = lambda j: CtcBiasHypothesis(tok[j * stride: j * stride + int(hyp["n_tokens"][j])].tolist(), float(hyp["score"][j]),  # noqa: E731
+                                             float(hyp["ctc_score"][j]), float(hyp["lm_score"][j]) if self.lm is not None else None,
+                                             float(hyp["bias_score"][j]))
+        elif self.lm is not None:
             hyp = host[:w * k].view(np.dtype([("score", "<f8"), ("ctc_score", "<f8"), ("lm_score", "<f8"), ("n_tokens", "<i4"),
                                               ("status", "<i4")]))
             mk = lambda j: CtcHypothesis(tok[j * stride: j * stride + int(hyp["n_tokens"][j])].tolist(), float(hyp["score"][j]),  # noqa: E731

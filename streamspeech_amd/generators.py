@@ -71,15 +71,23 @@ class CTCDecoder:
 
 
     @torch.no_grad()
-    def beam_search(self, encoder_out, beam, cand=None, nbest=None, lm=None, lm_weight=0.0, word_score=0.0, **kw):
+    def beam_search(self, encoder_out, beam, cand=None, nbest=None, lm=None, lm_weight=0.0, word_score=0.0, bias=None, bias_scale=1.0,
+                    **kw):
         """CTC prefix beam search on this head: what generate takes plus the beam -> [[hypothesis, ...]] best first, each with
         `tokens` (never blank, pad or unk) and `score`, the log of the summed probability of the alignments of those tokens --
         the scale of align's `score`, so align(encoder_out, h["tokens"]) places a hypothesis in time for words.*.
         lm (an ngram.NgramLM over this head's dictionary), lm_weight, word_score: shallow fusion -- `score` is then the fused one
-        the hypotheses are ranked by, and each hypothesis also has `ctc_score` (the scale above) and `lm_score`."""
+        the hypotheses are ranked by, and each hypothesis also has `ctc_score` (the scale above) and `lm_score`.
+        bias (a hotwords.CtcBias over this head's dictionary), bias_scale: hotword biasing, with lm or without -- `score` is the
+        fused one, and each hypothesis also has `ctc_score` and `bias_score` (and `lm_score` with lm)."""
         enc = encoder_out["encoder_out"][0]
         enc = enc[:, 0] if enc.dim() == 3 else enc
-        if lm is None:
+        if bias is not None:
+            fuse = {} if lm is None else {"lm": lm, "lm_weight": float(lm_weight), "word_score": float(word_score)}
+            hyps = self.engine.ctc_beam(self.head, enc.contiguous(), int(beam), cand, nbest, bias=bias, bias_scale=float(bias_scale), **fuse)
+            extra = lambda h: {"ctc_score": h.ctc_score, **({} if lm is None else {"lm_score": h.lm_score}),  # noqa: E731
+                               "bias_score": h.bias_score}
+        elif lm is None:
             hyps = self.engine.ctc_beam(self.head, enc.contiguous(), int(beam), cand, nbest)
             extra = lambda h: {}  # noqa: E731
         else:

@@ -94,6 +94,19 @@ class SSCtcLmOpts(C.Structure):
     _fields_ = [("lm_weight", C.c_double), ("word_score", C.c_double), ("eos_term", C.c_int32)]
 
 
+class SSCtcBiasOpts(C.Structure):
+    """ss_ctc_bias_opts: the weight of a hotword set in the search's order, and whether the finish term applies (16 bytes)."""
+    _fields_ = [("scale", C.c_double), ("finish", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SSCtcBeamBiasHyp(C.Structure):
+    """ss_ctc_beam_bias_hyp: one hypothesis of the CTC prefix beam search with a hotword set (40 bytes)."""
+    _fields_ = [("score", C.c_double), ("ctc_score", C.c_double), ("lm_score", C.c_double), ("bias_score", C.c_double),
+                ("n_tokens", C.c_int32), ("status", C.c_int32)]
+
+
+CTC_BIAS_MAX_LEN = 32           # SS_CTC_BIAS_MAX_LEN / _PHRASES of the header
+CTC_BIAS_MAX_PHRASES = 4096
 NGRAM_MAX_ORDER = 6             # SS_NGRAM_MAX_ORDER of the header
 CTC_BEAM_MAX_BEAM = 32          # SS_CTC_BEAM_MAX_BEAM / _CAND / _FRAMES of the header
 CTC_BEAM_MAX_CAND = 32
@@ -317,6 +330,16 @@ SIGNATURES = {
     "ss_batch_ctc_beam_lm": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, C.POINTER(SSCtcLmOpts)]),
     "ss_ctc_beam_lm_host": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,
                                  C.POINTER(SSCtcLmOpts)]),
+    "ss_ctc_bias_create": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_vp)]),
+    "ss_ctc_bias_destroy": (None, [_vp]),
+    "ss_ctc_bias_info": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ss_ctc_bias_score_host": (_i, [_vp, _i, _vp, C.POINTER(C.c_int32), _i, _vp, _vp, _vp]),
+    "ss_batch_ctc_beam_bias": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, C.POINTER(SSCtcLmOpts),
+                                    _vp, C.POINTER(SSCtcBiasOpts)]),
+    "ss_ctc_beam_bias_host": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,
+                                   C.POINTER(SSCtcLmOpts), _vp, C.POINTER(SSCtcBiasOpts)]),
+    "ss_ctc_stream_create_bias": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(SSCtcLmOpts), _vp, C.POINTER(SSCtcBiasOpts),
+                                       C.POINTER(_vp)]),
     "ss_ctc_stream_create": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(SSCtcLmOpts), C.POINTER(_vp)]),
     "ss_ctc_stream_destroy": (None, [_vp]),
     "ss_ctc_stream_reset": (_i, [_vp, _i]),
@@ -453,6 +476,11 @@ SIGNATURES = {
     "ss_debug_ctc_stream_create": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(SSCtcLmOpts), C.POINTER(_vp)]),
     "ss_op_ctc_stream_advance": (_i, [_vp, _vp, _i, C.POINTER(C.c_int32), _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp,
                                       _vp, _i, _vp]),
+    "ss_op_ctc_beam_bias": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,
+                                 C.POINTER(SSCtcLmOpts), _vp, C.POINTER(SSCtcBiasOpts)]),
+    "ss_debug_ctc_stream_create_bias": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(SSCtcLmOpts), _vp,
+                                             C.POINTER(SSCtcBiasOpts), C.POINTER(_vp)]),
+    "ss_op_ctc_bias_score": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _vp, _vp, _vp]),
     "ss_op_ngram_score": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _vp, _vp]),
     "ss_op_dur_predict": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
     "ss_op_repeat_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),

@@ -105,7 +105,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              sampling_topk: int = -1, sampling_topp: float = -1.0, seed: int = 1, ctc_beam: int = 0,
              ctc_beam_cand: Optional[int] = None, ctc_nbest: Optional[int] = None,
              constraints: Optional[Dict[int, Sequence[Sequence[int]]]] = None, ctc_lm: Optional[Dict[str, object]] = None,
-             ctc_lm_weight: float = 0.5, ctc_word_score: float = 0.0) -> Dict[int, Dict]:
+             ctc_lm_weight: float = 0.5, ctc_word_score: float = 0.0, ctc_bias: Optional[Dict[str, object]] = None,
+             ctc_bias_scale: float = 1.0) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
@@ -150,6 +151,11 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     search ranks its hypotheses by log p_ctc + A log p_lm + B n_tokens (batch_ctc_beam(lm=)), `score` in its .nbest file is that
     fused score, and its lines get two more columns behind it, ctc_score and lm_score (natural logs; an empty slot -inf and 0).
     A head without a model, and every other file, is what it is without them.
+    ctc_bias / ctc_bias_scale (--ctc-hotwords-asr FILE, --ctc-hotwords-st FILE, --ctc-hotword-boost S; with ctc_beam): {"asr": a
+    hotwords.CtcBias over source_unigram, "st": one over ctc_target_unigram}, either or both -- that head's search is biased
+    towards the set's phrases (batch_ctc_beam(bias=), with the head's model when it has one), and its .nbest lines are id, rank,
+    score, ctc_score, lm_score (0 without a model), bias_score, n_tokens, text.  A head without hotwords, and every other file,
+    is what it is without them.
     constraints (--constraints with --constraints-file): {sample id: phrases as ids of target_unigram} -- every hypothesis of that
     sample contains its phrases, in order (fairseq's --constraints, ordered; batch_mt_beam(constraints=), at beam_mt = 1 too).  A
     `C-<id>` line per phrase goes to the log in front of the sample's `D-` line, as fairseq-generate prints them, and
@@ -166,6 +172,9 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     ctc_lm = {k: v for k, v in (ctc_lm or {}).items() if v is not None}
     if ctc_lm and not ctc_beam:
         raise ValueError("ctc_lm needs ctc_beam: the model is fused into the CTC prefix beam search")
+    ctc_bias = {k: v for k, v in (ctc_bias or {}).items() if v is not None}
+    if ctc_bias and not ctc_beam:
+        raise ValueError("ctc_bias needs ctc_beam: the hotword set biases the CTC prefix beam search")
     sampler = sampling_from_fairseq(sampling, sampling_topk, sampling_topp, seed)
     samples: Dict[int, list] = {}
     if spoken_words and not dump_wav:
@@ -227,6 +236,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
         if ctc_beam:
             for hd, key in ((0, "asr"), (1, "st")):
                 fuse = {"lm": ctc_lm[key], "lm_weight": ctc_lm_weight, "word_score": ctc_word_score} if key in ctc_lm else {}
+                if key in ctc_bias:
+                    fuse.update(bias=ctc_bias[key], bias_scale=ctc_bias_scale)
                 for sid, lst in zip(ids, model.batch_ctc_beam(hd, enc, Tp, ctc_beam, ctc_beam_cand, ctc_nbest, **fuse)):
                     nbest_ctc[key][sid] = lst
         # first-pass text search: max_len = min(int(max_len_a_mt * src_len + max_len_b_mt), max positions - 1) with
@@ -353,9 +364,12 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
                         if rank < len(lst):
                             text = detok([dicts[name][c] for c in lst[rank].tokens])
                             more = f"\t{lst[rank].ctc_score:.6f}\t{lst[rank].lm_score:.6f}" if key in ctc_lm else ""
+                            if key in ctc_bias:
+                                more = f"\t{lst[rank].ctc_score:.6f}\t{lst[rank].lm_score or 0.0:.6f}\t{lst[rank].bias_score:.6f}"
                             print(f"{sid}\t{rank}\t{lst[rank].score:.6f}{more}\t{len(lst[rank].tokens)}\t{text}", file=f)
                         else:
-                            print(f"{sid}\t{rank}\t-inf" + ("\t-inf\t0" if key in ctc_lm else "") + "\t0\t", file=f)
+                            more = "\t-inf\t0\t0" if key in ctc_bias else "\t-inf\t0" if key in ctc_lm else ""
+                            print(f"{sid}\t{rank}\t-inf{more}\t0\t", file=f)
     if spoken_words:
         with open(os.path.join(results_path, f"generate-{subset}.spoken.words"), "w", encoding="utf-8") as f:
             for sid in sorted(spoken):
@@ -756,6 +770,14 @@ def build_parser() -> argparse.ArgumentParser:
                     help="the same for the ST head, a model over ctc_target_unigram")
     ap.add_argument("--ctc-lm-weight", type=float, default=0.5, help="A, the weight of the n-gram model's log-probability (default 0.5)")
     ap.add_argument("--ctc-word-score", type=float, default=0.0, help="B, added per token of a hypothesis (default 0)")
+    ap.add_argument("--ctc-hotwords-asr", default=None, metavar="FILE",
+                    help="with --ctc-beam: bias the ASR head's search towards the phrases of FILE -- one per line as space-separated "
+                         "pieces of source_unigram, optionally a tab and the phrase's per-token boost; its .nbest lines become id, "
+                         "rank, score, ctc_score, lm_score, bias_score, n_tokens, text")
+    ap.add_argument("--ctc-hotwords-st", default=None, metavar="FILE",
+                    help="the same for the ST head, phrases over ctc_target_unigram")
+    ap.add_argument("--ctc-hotword-boost", type=float, default=1.5,
+                    help="S, the per-token boost (natural-log units) of a hotword line that names none (default 1.5)")
     ap.add_argument("--score-reference", action="store_true",
                     help="also score the recipe's reference translation (the multitask manifest <task data>/<gen-subset>.tsv of "
                          "target_unigram) with the first-pass text decoder, teacher-forced, as fairseq's --score-reference does: writes "
@@ -831,6 +853,10 @@ def main(argv: Optional[List[str]] = None):
         ap.error("--ctc-lm-asr, --ctc-lm-st, --ctc-lm-weight and --ctc-word-score need --ctc-beam")
     if not (math.isfinite(a.ctc_lm_weight) and math.isfinite(a.ctc_word_score)):
         ap.error("--ctc-lm-weight and --ctc-word-score must be finite")
+    if not a.ctc_beam and (a.ctc_hotwords_asr or a.ctc_hotwords_st or a.ctc_hotword_boost != 1.5):
+        ap.error("--ctc-hotwords-asr, --ctc-hotwords-st and --ctc-hotword-boost need --ctc-beam")
+    if not math.isfinite(a.ctc_hotword_boost):
+        ap.error("--ctc-hotword-boost must be finite")
     if a.spoken_words and a.no_wav:
         ap.error("--spoken-words needs the durations the vocoder predicts: it cannot be combined with --no-wav")
     if a.align_reference and (a.wav_list or a.synthetic > 0 or not a.data):
@@ -946,6 +972,18 @@ def main(argv: Optional[List[str]] = None):
             ctc_lm[key] = NgramLM(arrays)
             print(f"| --ctc-lm-{key}: order {ctc_lm[key].order}, {ctc_lm[key].entries - 1} n-grams, {arrays['dropped']} dropped (symbols "
                   f"not in {name}), {ctc_lm[key].device_bytes} bytes on the device", file=sys.stderr)
+    ctc_bias = {}
+    for key, path, name in (("asr", a.ctc_hotwords_asr, "source_unigram"), ("st", a.ctc_hotwords_st, "ctc_target_unigram")):
+        if path:
+            from .hotwords import CtcBias, read_hotwords
+            from .lib import StreamSpeechHipError
+            d = holder.dict[name]
+            try:
+                ctc_bias[key] = CtcBias(*read_hotwords(path, d, a.ctc_hotword_boost), len(d), d.pad(), d.unk())
+            except (OSError, ValueError, StreamSpeechHipError) as e:
+                ap.error(f"--ctc-hotwords-{key}: {e}")
+            print(f"| --ctc-hotwords-{key}: {ctc_bias[key].n_phrases} phrases, {ctc_bias[key].states} states, "
+                  f"{ctc_bias[key].device_bytes} bytes on the device", file=sys.stderr)
     sub = a.gen_subset if a.num_shards == 1 else f"{a.gen_subset}.shard{a.shard_id}"
     hyps = generate(model, voc, items, holder.dict, a.results_path, sub, a.batch_size, a.max_tokens, a.max_len_a,
                     a.max_len_b, a.max_len_a_mt, a.max_len_b_mt, a.dur_prediction, not a.no_wav,
@@ -963,9 +1001,12 @@ def main(argv: Optional[List[str]] = None):
                        if a.sampling else {}),
                     **({"ctc_beam": a.ctc_beam, "ctc_beam_cand": a.ctc_beam_cand, "ctc_nbest": a.ctc_nbest} if a.ctc_beam else {}),
                     **({"constraints": glossary} if glossary is not None else {}),
-                    **({"ctc_lm": ctc_lm, "ctc_lm_weight": a.ctc_lm_weight, "ctc_word_score": a.ctc_word_score} if ctc_lm else {}))
+                    **({"ctc_lm": ctc_lm, "ctc_lm_weight": a.ctc_lm_weight, "ctc_word_score": a.ctc_word_score} if ctc_lm else {}),
+                    **({"ctc_bias": ctc_bias} if ctc_bias else {}))
     for lm in ctc_lm.values():
         lm.close()
+    for bias in ctc_bias.values():
+        bias.close()
     print(f"| generated {len(hyps)} utterances into {a.results_path}", file=sys.stderr)
 
 

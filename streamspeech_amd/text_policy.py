@@ -65,18 +65,23 @@ def asr_beam_emit(prev_text: str, symbols_of_best, n_stable: int, finished: bool
     return text[len(prev_text):], text
 
 
+HOTWORD_BOOST = 1.5         # --ctc-hotword-boost: the per-token boost of a hotword line that names none (hotwords.read_hotwords)
+
+
 class CtcBeamOptions:
     """The streaming CTC prefix beam search of ASR sessions (engine.CtcStream): TextSessionPool(ctc_beam=...) and the ASR agent's
     --ctc-beam flags.  beam in [1, 32]; cand (candidates per frame; None: engine.ctc_beam_default_cand) in [1, 32]; nbest (None:
-    the beam) in [1, beam]; lm an ngram.NgramLM over source_unigram fused with lm_weight and word_score, or None.  ValueError
-    here, before any device call, for anything the library would refuse."""
+    the beam) in [1, beam]; lm an ngram.NgramLM over source_unigram fused with lm_weight and word_score, or None; bias a
+    hotwords.CtcBias over source_unigram weighed by bias_scale, or None.  ValueError here, before any device call, for anything
+    the library would refuse."""
 
     def __init__(self, beam: int, cand: Optional[int] = None, nbest: Optional[int] = None, lm=None, lm_weight: float = 0.5,
-                 word_score: float = 0.0):
+                 word_score: float = 0.0, bias=None, bias_scale: float = 1.0):
         self.beam = int(beam)
         self.cand = None if cand is None else int(cand)
         self.nbest = None if nbest is None else int(nbest)
         self.lm, self.lm_weight, self.word_score = lm, float(lm_weight), float(word_score)
+        self.bias, self.bias_scale = bias, float(bias_scale)
         if not 1 <= self.beam <= CTC_BEAM_MAX:
             raise ValueError(f"ctc_beam: beam {beam} outside [1, {CTC_BEAM_MAX}]")
         if self.cand is not None and not 1 <= self.cand <= CTC_BEAM_MAX:
@@ -85,24 +90,31 @@ class CtcBeamOptions:
             raise ValueError(f"ctc_beam: nbest {nbest} outside [1, beam = {self.beam}]")
         if not (math.isfinite(self.lm_weight) and math.isfinite(self.word_score)):
             raise ValueError("ctc_beam: lm_weight and word_score must be finite")
+        if not math.isfinite(self.bias_scale):
+            raise ValueError("ctc_beam: bias_scale must be finite")
 
     def stream_kwargs(self) -> dict:
         """The keywords of engine.CtcStream past (model, head, max_sessions, max_frames)."""
         kw = dict(beam=self.beam, cand=self.cand, nbest=self.nbest)
         if self.lm is not None:
             kw.update(lm=self.lm, lm_weight=self.lm_weight, word_score=self.word_score)
+        if self.bias is not None:
+            kw.update(bias=self.bias, bias_scale=self.bias_scale)
         return kw
 
 
 def ctc_beam_flags(args, agent: str = "asr", want_lm: bool = True) -> Optional[CtcBeamOptions]:
-    """--ctc-beam K [--ctc-beam-cand C] [--ctc-lm FILE --ctc-lm-weight A --ctc-word-score B] of the streaming agents -> the options,
-    or None without --ctc-beam.  ValueError: a dependent flag without --ctc-beam, the flags on another agent than the ASR one (the
+    """--ctc-beam K [--ctc-beam-cand C] [--ctc-lm FILE --ctc-lm-weight A --ctc-word-score B] [--ctc-hotwords FILE
+    --ctc-hotword-boost S] of the streaming agents -> the options, or None without --ctc-beam.  ValueError: a dependent flag without --ctc-beam, the flags on another agent than the ASR one (the
     S2TT gate and the S2ST path read arg-max token counts), with --word-details (its spans are the arg-max path's), or values out of
-    range.  The model file is not read here (the caller reads it over its dictionary and sets .lm)."""
+    range.  The model file and the hotword file are not read here (the caller reads them over its dictionary and sets .lm /
+    .bias)."""
     beam = int(getattr(args, "ctc_beam", 0) or 0)
     cand, lm = getattr(args, "ctc_beam_cand", None), getattr(args, "ctc_lm", None)
+    hot, boost = getattr(args, "ctc_hotwords", None), getattr(args, "ctc_hotword_boost", HOTWORD_BOOST)
     if not beam:
-        for flag, v, default in (("--ctc-beam-cand", cand, None), ("--ctc-lm", lm, None),
+        for flag, v, default in (("--ctc-beam-cand", cand, None), ("--ctc-lm", lm, None), ("--ctc-hotwords", hot, None),
+                                 ("--ctc-hotword-boost", boost, HOTWORD_BOOST),
                                  ("--ctc-lm-weight", getattr(args, "ctc_lm_weight", 0.5), 0.5),
                                  ("--ctc-word-score", getattr(args, "ctc_word_score", 0.0), 0.0)):
             if v != default:
@@ -114,4 +126,8 @@ def ctc_beam_flags(args, agent: str = "asr", want_lm: bool = True) -> Optional[C
         raise ValueError("--ctc-beam cannot be combined with --word-details (its spans are those of the arg-max path)")
     if lm is None and (getattr(args, "ctc_lm_weight", 0.5) != 0.5 or getattr(args, "ctc_word_score", 0.0) != 0.0):
         raise ValueError("--ctc-lm-weight / --ctc-word-score need --ctc-lm")
+    if hot is None and boost != HOTWORD_BOOST:
+        raise ValueError("--ctc-hotword-boost needs --ctc-hotwords")
+    if not math.isfinite(boost):
+        raise ValueError("--ctc-hotword-boost must be finite")
     return CtcBeamOptions(beam, cand, None, None, getattr(args, "ctc_lm_weight", 0.5), getattr(args, "ctc_word_score", 0.0))
