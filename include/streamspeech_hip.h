@@ -13,7 +13,9 @@
  * ss_flac_restore_host, ss_flac_restore (FLAC ingest), ss_batch_cmvn (precomputed fbank rows), ss_batch_mt_attention and
  * ss_op_attention_probs (cross-attention of the first-pass text decoder), ss_batch_unit_spans, ss_unit_spans_host and
  * ss_op_unit_spans (where each text-decoder state is spoken in the output speech), ss_batch_mt_score, ss_op_mt_token_scores and
- * ss_debug_mt_score_form (the text decoder's score of a given translation).
+ * ss_debug_mt_score_form (the text decoder's score of a given translation), ss_ctc_spot_set_*, ss_batch_ctc_spot, ss_ctc_spot_host,
+ * ss_op_ctc_spot, ss_ctc_spot_stream_*, ss_debug_ctc_spot_stream_create and ss_op_ctc_spot_stream_advance (keyword spotting on the
+ * text CTC heads).
  *
  * Weight ownership: the caller owns one packed FP32 weight blob in HBM (built once from a fairseq
  * state dict by streamspeech_amd/weights.py) and lends it to ss_model_create(); the library keeps
@@ -1008,6 +1010,97 @@ int ss_ctc_stream_advance(ss_model* m, void* stream, ss_ctc_stream* cs, int n, c
  * refusals (and ld < V; there is no h_T). */
 int ss_ctc_stream_advance_host(ss_ctc_stream* cs, int n, const int32_t* h_slots, const float* h_logits, int ld, const int32_t* h_upto,
                                const int32_t* h_final, void* h_hyps, int32_t* h_tokens, int out_stride, ss_ctc_stream_part* h_part);
+/* ---- Keyword spotting on a text head (csrc/ctc_spot.hip; the step and the emission rule: csrc/ctc_spot.hpp): did these phrases occur
+ * in this audio, and when -- many keywords at once, each with a free start and a free end.  Blank = 0; pad and unk are not masked
+ * (as in the aligner).  THE RULE:
+ * Per-frame cost.  For a head with V columns c[t][v] = logit[t][v] - max_v logit[t][v], one float32 subtraction, so c <= 0; the
+ * sum of c along a path is the path's log-likelihood ratio against the arg-max path over the same frames (no denominator).  A frame
+ * whose row holds a NaN, or whose maximum is -inf, makes the utterance's status 2: it reports no hits.
+ * States.  A keyword is labels y[0..L), 1 <= L <= SS_CTC_SPOT_MAX_LABELS; its states are [y0, 0, y1, 0, ..., y(L-1)], S = 2L - 1, no
+ * leading or trailing blank.
+ * Recursion, max-plus, the value float64, a start frame carried with every state; before the first frame every value is -inf.
+ * State 0 at frame t takes c[t][y0] plus the better of stay (a[t-1][0], its start) and enter (0.0, start = t); stay wins on equality,
+ * which as c <= 0 is only while y0 has been the arg-max since its start.  Any other state takes c[t][label(s)] plus the best of
+ * stay (s), advance (s - 1) and skip (s - 2, a label state whose label differs from the label before it); ties: stay beats advance
+ * beats skip; the start frame is the chosen predecessor's.  Every sum is value + (double)c, in frame order.
+ * Candidates.  e_t = a[t][S-1] with start s_t; frame t is a candidate when e_t >= -(double)tau * L, tau >= 0 the keyword's
+ * threshold in natural-log units per label.
+ * Hits of one keyword never overlap.  Per keyword a pending candidate P and last_end, the end of its last emitted hit.  A candidate
+ * with s_t <= last_end is ignored (P stays as it is).  A candidate with s_t <= P.end replaces P when e_t >= P.score (the later wins
+ * a tie, so the span covers the last label's run) and is dropped otherwise.  Any other candidate emits P and becomes P.  A frame
+ * that is not a candidate emits P.  The utterance's last frame (a stream: its final call) emits P.
+ * Order.  An utterance's hits come back sorted by (end, keyword, start).  The count record carries the TRUE number of hits; when it
+ * exceeds max_hits the overflow flag is set and WHICH max_hits of them are written is unspecified (they are still sorted). ---- */
+typedef struct ss_ctc_hit {
+  int32_t keyword;     /* index into the set */
+  int32_t start, end;  /* encoder rows of the utterance, both inclusive */
+  int32_t n_labels;    /* L */
+  double score;        /* e at `end`: the sum of c over the path, <= 0; score / n_labels is what tau bounds */
+} ss_ctc_hit;
+typedef struct ss_ctc_spot_count {
+  int32_t n_hits;      /* the true number of hits (0 with status 2); min(n_hits, max_hits) records were written */
+  int32_t status;      /* 0, or 2: a row with a NaN or without a finite maximum (a stream slot: sticky until the slot is reset) */
+  int32_t overflow;    /* n_hits > max_hits */
+  int32_t frames;      /* frames consumed, this call included */
+} ss_ctc_spot_count;
+typedef struct ss_ctc_spot_set ss_ctc_spot_set;
+typedef struct ss_ctc_spot_stream ss_ctc_spot_stream;
+#define SS_CTC_SPOT_MAX_LABELS 32
+#define SS_CTC_SPOT_MAX_KEYWORDS 65536
+#define SS_CTC_SPOT_MAX_HITS 16384     /* the sort is a rank sort, one workgroup per utterance: m written records cost m * m / 256
+                                        * compares per thread -- nothing at the usual 64 .. 256, about 10^6 at the maximum */
+#define SS_CTC_SPOT_MAX_UTTERANCES 65535   /* B of a one-shot call, sessions of a stream object: the DP kernel's grid */
+/* Builds the set's table on the host; the one upload is made by the first device call that uses the set, so creation needs no
+ * device; the table then lives on the device that was current at that call, the object serves THAT device, and a device call
+ * with another device current is refused (SS_ERR_ARG): make one set per device.  Keyword k is h_tokens[h_off[k] .. h_off[k + 1]) with the threshold h_tau[k]; h_off holds n_keywords + 1 ascending offsets
+ * from 0.  pad / unk: the head's ids, or -1 for none.  The table holds the set's U distinct labels (the blank first), each
+ * keyword's states as indices into them, laid onto the lanes of the DP kernel's workgroups in the given order, and the thresholds.
+ * Equal keywords are legal (each reports).  SS_ERR_ARG, with nothing allocated: n_keywords outside [1, SS_CTC_SPOT_MAX_KEYWORDS],
+ * an empty keyword or one longer than SS_CTC_SPOT_MAX_LABELS, a label that is blank (0), pad, negative or >= V, a negative or
+ * non-finite tau, V <= 0, pad / unk outside [-1, V), a missing pointer.  Read-only afterwards: one object serves every context and
+ * stream of its device. */
+int ss_ctc_spot_set_create(int n_keywords, const int32_t* h_tokens, const int32_t* h_off, const float* h_tau, int V, int pad, int unk,
+                           ss_ctc_spot_set** out);
+void ss_ctc_spot_set_destroy(ss_ctc_spot_set* set);
+/* keywords, distinct labels U (the blank included), states (the sum of 2L - 1), workgroups of the DP kernel per utterance (256
+ * lanes each; a keyword never straddles a 64-lane wave) and the bytes the table takes on the device; each pointer may be NULL. */
+int ss_ctc_spot_set_info(const ss_ctc_spot_set* set, int32_t* n_keywords, int32_t* n_labels, int64_t* states, int32_t* workgroups,
+                         int64_t* device_bytes);
+/* B utterances packed as ss_batch_ctc_align takes them (the same head GEMM, pack-invariance setting and scratch booking), stream-
+ * ordered.  Device outputs: d_hits [B][max_hits] (records past min(n_hits, max_hits) are left as they were), d_counts [B].  An
+ * utterance's records are the same bytes alone and in any pack, in any order (below max_hits).  SS_ERR_ARG, with nothing launched
+ * or written: B outside [1, SS_CTC_SPOT_MAX_UTTERANCES], a Tp outside [1, SS_CTC_ALIGN_MAX_FRAMES], max_hits outside [1, SS_CTC_SPOT_MAX_HITS], a set whose V, pad or
+ * unk are not the head's, head outside {0, 1}, a NULL pointer.  Working memory, booked on the context's scratch set: sum Tp * U
+ * floats of per-frame costs and B * max_hits records; the recursion's state lives in registers. */
+int ss_batch_ctc_spot(ss_model* m, void* stream, int head, int B, const float* d_enc_out, const int32_t* h_Tp,
+                      const ss_ctc_spot_set* set, int max_hits, ss_ctc_hit* d_hits, ss_ctc_spot_count* d_counts);
+/* The plain-C++ twin of the kernels on host logits [sum T][ld] (the set's V columns read): the same step code, records and refusals
+ * (and ld < V), every pointer a HOST pointer.  On overflow it writes the first max_hits records of the order. */
+int ss_ctc_spot_host(const float* h_logits, int ld, int B, const int32_t* h_T, const ss_ctc_spot_set* set, int max_hits,
+                     ss_ctc_hit* h_hits, ss_ctc_spot_count* h_counts);
+/* The same search, resumable: a device object holds, for max_sessions slots of one text head and one set, per slot the frames
+ * consumed, the sticky status, per keyword state its value and start frame, and per keyword P and last_end.  THE CONTRACT: the hits
+ * of all calls of an utterance, concatenated and sorted by (end, keyword, start), are byte for byte ss_batch_ctc_spot's on all its
+ * frames, however the frames were split over the calls.  Memory, booked on m's scratch set in one piece of exact size
+ * (SS_ERR_SCRATCH_CAP leaves the set as it was) and released at destroy: max_sessions * (12 NS + 20 K + 4) bytes, rounded up to 8,
+ * with NS the set's states and K its keywords.  SS_ERR_ARG at creation: head outside {0, 1}, max_sessions outside [1, SS_CTC_SPOT_MAX_UTTERANCES], a set
+ * whose V, pad or unk are not the head's, a NULL pointer. */
+int ss_ctc_spot_stream_create(ss_model* m, int head, int max_sessions, const ss_ctc_spot_set* set, ss_ctc_spot_stream** out);
+void ss_ctc_spot_stream_destroy(ss_ctc_spot_stream* ks);
+/* A new utterance in `slot` (host-only; the state and the sticky status start over at the slot's next advance). */
+int ss_ctc_spot_stream_reset(ss_ctc_spot_stream* ks, int slot);
+/* One step for n sessions, stream-ordered: ss_ctc_stream_advance's arguments, slot rules and refusals (h_upto[i] at most
+ * SS_CTC_ALIGN_MAX_FRAMES; max_hits as above, per session and call).  Only the rows [f, upto) of each session are stacked and go
+ * through the head and the gather kernel.  h_final[i] non-zero: the utterance's last call -- P is emitted and the slot is reset by
+ * the call itself.  Device outputs: d_hits [n][max_hits] the hits that were emitted in this call, sorted; d_counts [n]. */
+int ss_ctc_spot_stream_advance(ss_model* m, void* stream, ss_ctc_spot_stream* ks, int n, const int32_t* h_slots,
+                               const float* d_enc_packed, const int32_t* h_T, const int32_t* h_upto, const int32_t* h_final,
+                               int max_hits, ss_ctc_hit* d_hits, ss_ctc_spot_count* d_counts);
+/* The plain-C++ twin on an object of ss_debug_ctc_spot_stream_create(on_device = 0): h_logits [sum (upto - f)][ld] are the STACKED
+ * NEW rows alone, every pointer a HOST pointer; the same step code, records and refusals (and ld < V; there is no h_T). */
+int ss_ctc_spot_stream_advance_host(ss_ctc_spot_stream* ks, int n, const int32_t* h_slots, const float* h_logits, int ld,
+                                    const int32_t* h_upto, const int32_t* h_final, int max_hits, ss_ctc_hit* h_hits,
+                                    ss_ctc_spot_count* h_counts);
 /* Lockstep beam-1 search from [</s>] (offline: no prefix).  h_max_len[b] = forced-</s> step of
  * utterance b.  h_out_tokens [B][out_stride] receives the generated tokens (incl. the final </s>),
  * h_n_out[b] their number (= rows of valid decoder states); d_feats is [B][feat_rows][dec_dim].
@@ -1708,6 +1801,27 @@ int ss_debug_ctc_stream_create_bias(int V, int pad, int unk, int on_device, int 
  * NULL) / d_sum device arrays of the twin's sizes.  tests/test_ctc_bias_gpu.py. */
 int ss_op_ctc_bias_score(void* stream, const ss_ctc_bias* bias, int B, const int32_t* d_tokens, const int32_t* h_n, int finish,
                          double* d_delta, int32_t* d_state, double* d_sum);
+/* The three kernels of ss_batch_ctc_spot on the caller's device logits [sum T][ld]: arguments as ss_ctc_spot_host with d_logits and
+ * the outputs on the device; scratch made here, a buffer per stream of the calling thread.  tests/test_ctc_spot_gpu.py. */
+int ss_op_ctc_spot(void* stream, const float* d_logits, int ld, int B, const int32_t* h_T, const ss_ctc_spot_set* set, int max_hits,
+                   ss_ctc_hit* d_hits, ss_ctc_spot_count* d_counts);
+/* The host twin's recursion laid open on ONE utterance of host logits [T][ld]: h_e / h_start [T][K] receive every keyword's e_t and
+ * s_t (the value and start frame of its last state after frame t).  SS_ERR_ARG also for an utterance of status 2.
+ * tests/test_ctc_spot_cpu.py. */
+int ss_debug_ctc_spot_trace_host(const float* h_logits, int ld, int T, const ss_ctc_spot_set* set, double* h_e, int32_t* h_start);
+/* A measuring knob: which of the spotter's three kernels every later call launches (bit 0 the gather, bit 1 the DP, bit 2 the sort;
+ * 7, the default, all of them).  ONE word for the whole process, read once per call: with anything else no caller's records
+ * are valid, in any context or thread, until it is set back to 7 -- for a measuring process that does nothing else.
+ * tools/ctc_spot_bench.py. */
+int ss_debug_ctc_spot_phases(int mask);
+/* The object of ss_ctc_spot_stream_create without a model context: on_device = 0 for ss_ctc_spot_stream_advance_host (no device is
+ * touched), non-zero for ss_op_ctc_spot_stream_advance (the state in a buffer of its own, booked on no set). */
+int ss_debug_ctc_spot_stream_create(const ss_ctc_spot_set* set, int on_device, int max_sessions, ss_ctc_spot_stream** out);
+/* The kernels of ss_ctc_spot_stream_advance on the caller's device logits: arguments as ss_ctc_spot_stream_advance_host with
+ * d_logits and the outputs on the device. */
+int ss_op_ctc_spot_stream_advance(void* stream, ss_ctc_spot_stream* ks, int n, const int32_t* h_slots, const float* d_logits, int ld,
+                                  const int32_t* h_upto, const int32_t* h_final, int max_hits, ss_ctc_hit* d_hits,
+                                  ss_ctc_spot_count* d_counts);
 /* ss_ngram_score_host on the device, one wave per sequence: d_tokens packed (device), h_n on the host, d_lp / d_state (may be
  * NULL) device arrays laid out as the host call's.  The op-level handle on the lookup the fused search runs.  Stream-ordered. */
 int ss_op_ngram_score(void* stream, const ss_ngram_lm* lm, int B, const int32_t* d_tokens, const int32_t* h_n, int with_eos,

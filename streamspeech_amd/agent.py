@@ -205,8 +205,9 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
     """Simultaneous speech-to-speech translation agent for StreamSpeech on the HIP backend."""
 
     def __init__(self, args, model=None, vocoder=None):
-        from .text_policy import ctc_beam_flags
+        from .text_policy import ctc_beam_flags, ctc_keyword_flags
         ctc_beam_flags(args, "S2ST")                       # (raises: the flags are the ASR agent's)
+        ctc_keyword_flags(args, "S2ST")
         super().__init__(args)
         self.eos = DEFAULT_EOS
         self.args = args
@@ -350,6 +351,14 @@ class StreamSpeechS2STAgent(SpeechToSpeechAgent):
                "phrase's per-token boost (hotwords.read_hotwords); biases the search towards them")
         a("--ctc-hotword-boost", type=float, default=1.5,
           help="with --ctc-hotwords: the per-token boost, in natural-log units, of a line that names none (default 1.5)")
+        a("--ctc-keywords", default=None, metavar="FILE",
+          help="streaming ASR agent: phrases to spot, one per line as space-separated source_unigram pieces, optionally a tab and "
+               "the phrase's threshold (keywords.read_keywords); agent.hits collects their occurrences (keywords.KeywordHit, ms on "
+               "the utterance's clock) as the encoder makes rows final; no beam search is needed; the S2TT and S2ST agents refuse "
+               "the flag; default: off, every launch and every output as without the flag")
+        a("--ctc-keyword-threshold", type=float, default=1.0,
+          help="with --ctc-keywords: the threshold tau, in natural-log units per label, of a line that names none (default 1.0, a "
+               "starting point that was not tuned on a trained checkpoint)")
         a("--mt-alignment", action="store_true", default=False,
           help="after every policy() that wrote, agent.alignment holds the words of all committed target tokens (the text decoder's, "
                "which the S2TT agent prints and the S2ST path speaks) with the source time span the decoder's cross-attention "

@@ -10,7 +10,7 @@ from .agent import StreamSpeechS2STAgent, _beam_kwargs, _greedy_mt, _detok, mt_a
 from .frontend import OnlineFeatureExtractor  # noqa: F401  (re-exported for parity with the reference files)
 from .generators import CTCDecoder, SequenceGenerator
 from .simuleval_shim import ReadAction, SpeechToTextAgent, WriteAction, entrypoint
-from .text_policy import asr_beam_emit, ctc_beam_flags, s2tt_gate
+from .text_policy import asr_beam_emit, ctc_beam_flags, ctc_keyword_flags, s2tt_gate
 
 
 def _add_text_args(parser):
@@ -78,6 +78,9 @@ class _TextAgentBase(SpeechToTextAgent):
         if getattr(self, "ctc_stream", None) is not None:
             self.ctc_stream.reset(0)               # --ctc-beam: the search of the utterance before
             self._ctc_frames = 0
+        if getattr(self, "spot_stream", None) is not None:
+            self.spot_stream.reset(0)              # --ctc-keywords: the spotter of the utterance before (agent.hits stays)
+            self._spot_frames = 0
         fe = getattr(self, "feature_extractor", None)
         if fe is not None:
             fe.clear_cache()                       # converted sample history of the previous utterance
@@ -99,6 +102,8 @@ class StreamSpeechASRAgent(_TextAgentBase):
     An utterance may run to lib.CTC_BEAM_MAX_FRAMES encoder rows (60 s)."""
 
     ctc_stream = None
+    spot_stream = None
+    hits = None         # --ctc-keywords: the keywords.KeywordHit of every policy() so far, in the order they were reported
     nbest = None        # --ctc-beam: the engine.CtcHypothesis list of the last finished utterance, best first
     partial = None      # --ctc-beam: the symbols of the current best hypothesis, unstable tail included (for display)
 
@@ -106,7 +111,14 @@ class StreamSpeechASRAgent(_TextAgentBase):
         if getattr(args, "mt_alignment", False):
             raise ValueError("--mt-alignment needs the first-pass text search; the ASR agent has none")
         opts = ctc_beam_flags(args, "asr")                 # before anything is loaded: the refusals need no GPU
+        kw_file = ctc_keyword_flags(args, "asr")
         super().__init__(args, model)
+        if kw_file:
+            from .engine import CtcSpotStream
+            from .keywords import CtcKeywords
+            self.keywords = CtcKeywords.from_file(args.ctc_keywords, self.dict["source_unigram"], float(args.ctc_keyword_threshold))
+            self.hits, self._spot_frames = [], 0
+            self.spot_stream = CtcSpotStream(self.engine, 0, 1, self.keywords)
         if opts is not None:
             from .engine import CtcStream
             from .lib import CTC_BEAM_MAX_FRAMES
@@ -140,11 +152,27 @@ class StreamSpeechASRAgent(_TextAgentBase):
             self.reset()
         return WriteAction(new_text, finished=self.states.target_finished)
 
+    def _spot(self, enc):
+        """--ctc-keywords: the spotter moves over the rows the incremental encoder has made final (all, with final, at the end),
+        as _beam_policy moves the search; what it emits joins agent.hits."""
+        from .keywords import KeywordHit
+        from .words import FRAME_MS
+        rows = enc["encoder_out"][0][:, 0, :].contiguous()
+        T2, fin = int(rows.shape[0]), bool(self.states.source_finished)
+        n_final = int(self.engine.stream_stats[0]) if getattr(self.model.encoder, "incremental", False) else 0
+        upto = T2 if fin else max(self._spot_frames, min(n_final, T2))
+        got = self.spot_stream.advance([0], rows, [T2], [upto], [fin])[0]
+        self._spot_frames = 0 if fin else upto
+        self.hits.extend(KeywordHit(h.keyword, self.keywords.texts[h.keyword], h.start * FRAME_MS, (h.end + 1) * FRAME_MS, h.score, h.norm)
+                         for h in got.hits)
+
     @torch.inference_mode()
     def policy(self):
         enc, _, _ = self._encode()
         if enc is None:
             return WriteAction("", finished=True) if self.states.source_finished else ReadAction()
+        if self.spot_stream is not None:
+            self._spot(enc)
         if self.ctc_stream is not None:
             return self._beam_policy(enc)
         scored = self._ctc_hyps(enc)
@@ -168,6 +196,7 @@ class StreamSpeechS2TTAgent(_TextAgentBase):
 
     def __init__(self, args, model=None):
         ctc_beam_flags(args, "S2TT")                       # (raises: the flags are the ASR agent's)
+        ctc_keyword_flags(args, "S2TT")
         super().__init__(args, model)
 
     @torch.inference_mode()

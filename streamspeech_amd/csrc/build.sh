@@ -7,7 +7,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result ${SS_EXTRA_FLAGS:-}"
 OUT=${SS_OUT_LIB:-../libstreamspeech_hip.so}
 B=${SS_BUILD_DIR:-build}
-SRCS="gemm prof dispatch conv_sk conv_sk2 conv_slab resblock ffn rtlin conv_c64 conv_c64w conv_f16 conv_c32 conv_c16 attention attn_probs elementwise ctc_scores ctc_align ctc_beam ctc_beam_host ctc_stream ngram_lm ctc_bias mt_score fbank mt_step enc_step model batch stream_pool beam beam_host beam_kernels beam_sample vocoder debug_ops mp3_host mp3 flac_host flac pcm vad unit_spans"
+SRCS="gemm prof dispatch conv_sk conv_sk2 conv_slab resblock ffn rtlin conv_c64 conv_c64w conv_f16 conv_c32 conv_c16 attention attn_probs elementwise ctc_scores ctc_align ctc_beam ctc_beam_host ctc_stream ngram_lm ctc_bias ctc_spot mt_score fbank mt_step enc_step model batch stream_pool beam beam_host beam_kernels beam_sample vocoder debug_ops mp3_host mp3 flac_host flac pcm vad unit_spans"
 mkdir -p $B
 rm -f $B/.failed          # stale flag of an earlier run: cleared BEFORE the jobs start (a fast failure must survive)
 for f in $SRCS; do

@@ -316,6 +316,27 @@ class BatchMixin:
             l0 += n[b]
         return out
 
+    def batch_ctc_spot(self, head: int, enc_packed: torch.Tensor, Tp: List[int], keywords, max_hits: int = 256,
+                       return_counts: bool = False):
+        """Keyword spotting on a text head (ss_batch_ctc_spot): per utterance the occurrences of the set's phrases (a
+        keywords.CtcKeywords over this head's dictionary) as CtcHit tuples, sorted by (end, keyword, start); start and end are
+        encoder rows of the utterance, both inclusive.  The rows are packed as batch_ctc_greedy takes them.  No hits for an
+        utterance with a NaN row.  At most max_hits per utterance come back (which, past that, is unspecified);
+        return_counts: also the count records (n_hits the true number, status, overflow, frames) as a numpy array.  One buffer,
+        one device-to-host copy.  The library refuses (SS_ERR_ARG, nothing launched) a set that is not of this head's vocabulary,
+        pad and unk, more than L.CTC_ALIGN_MAX_FRAMES frames per utterance and a max_hits outside [1, L.CTC_SPOT_MAX_HITS]."""
+        from .keywords import COUNT_DTYPE, HIT_DTYPE, hits_from_records
+        B, mh = len(Tp), int(max_hits)
+        # int32 words: hits [6 B mh] (four ints and a double each, first: 8-byte aligned) | counts [4 B]
+        ibuf = torch.empty((6 * B * max(mh, 0) + 4 * B + 2,), dtype=torch.int32, device=self.device)
+        L.check(self.lib.ss_batch_ctc_spot(self.h, _stream(), head, B, _ptr(enc_packed), _i32(Tp), keywords.h, mh, _ptr(ibuf),
+                                           _ptr(ibuf[6 * B * max(mh, 0):])), "ss_batch_ctc_spot")
+        host = ibuf.cpu().numpy()
+        rec = host[:6 * B * mh].view(HIT_DTYPE).reshape(B, mh)
+        cnt = host[6 * B * mh: 6 * B * mh + 4 * B].view(COUNT_DTYPE)
+        out = [hits_from_records(rec[b, :min(int(cnt["n_hits"][b]), mh)]) for b in range(B)]
+        return (out, cnt.copy()) if return_counts else out
+
     def batch_ctc_beam(self, head: int, enc_packed: torch.Tensor, Tp: List[int], beam: int, cand: Optional[int] = None,
                        nbest: Optional[int] = None, lm=None, lm_weight: float = 0.0, word_score: float = 0.0,
                        lm_eos: bool = True, bias=None, bias_scale: float = 1.0, bias_finish: bool = True) -> List[List[CtcHypothesis]]:
@@ -1036,6 +1057,10 @@ class HipModel(BatchMixin):
         """Forced alignment of one utterance: the B = 1 call of batch_ctc_align."""
         return self.batch_ctc_align(head, enc_out.contiguous(), [int(enc_out.shape[0])], [list(tokens)], want_path)[0]
 
+    def ctc_spot(self, head: int, enc_out: torch.Tensor, keywords, max_hits: int = 256):
+        """Keyword spotting of one utterance: the B = 1 call of batch_ctc_spot."""
+        return self.batch_ctc_spot(head, enc_out.contiguous(), [int(enc_out.shape[0])], keywords, max_hits)[0]
+
     def ctc_beam(self, head: int, enc_out: torch.Tensor, beam: int, cand: Optional[int] = None,
                  nbest: Optional[int] = None, lm=None, lm_weight: float = 0.0, word_score: float = 0.0,
                  lm_eos: bool = True, bias=None, bias_scale: float = 1.0, bias_finish: bool = True) -> List[CtcHypothesis]:
@@ -1551,6 +1576,71 @@ class CtcStream:
     def close(self):
         if getattr(self, "h", None):
             self.lib.ss_ctc_stream_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CtcSpots(NamedTuple):
+    """What one CtcSpotStream.advance reports for a session."""
+    hits: list                  # keywords.CtcHit tuples emitted in this call, sorted by (end, keyword, start); rows of the utterance
+    n_hits: int                 # the true number (above len(hits): max_hits was too small)
+    frames: int                 # frames the spotter has consumed
+    status: int                 # 0, or 2 once a NaN row was seen (sticky until the slot is reset)
+    final: bool                 # the utterance's last call (the slot was reset by it)
+
+
+class CtcSpotStream:
+    """The resumable keyword spotter of a text head (ss_ctc_spot_stream): `max_sessions` slots, each the recursion of one utterance
+    kept on the device between calls.  :meth:`advance` moves any subset of slots forward over encoder rows that are FINAL (the
+    incremental encoder's n_final) and returns the hits that were emitted on the way; the hits of all calls of an utterance are
+    exactly batch_ctc_spot's on all its frames.  The set (a keywords.CtcKeywords; kept alive here) is fixed at creation.  The state
+    is booked on the model's scratch set and released by :meth:`close`."""
+
+    def __init__(self, model: "HipModel", head: int, max_sessions: int, keywords):
+        self.lib, self.model, self.device = model.lib, model, _require_gpu(model.device)
+        self.head, self.max_sessions, self.keywords = int(head), int(max_sessions), keywords
+        self.h = None
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(self.lib.ss_ctc_spot_stream_create(model.h, self.head, self.max_sessions, keywords.h, C.byref(h)),
+                    "ss_ctc_spot_stream_create")
+        self.h = h
+
+    def reset(self, slot: int):
+        """A new utterance in `slot` (host-only; the utterance's last advance does it by itself)."""
+        L.check(self.lib.ss_ctc_spot_stream_reset(self.h, int(slot)), "ss_ctc_spot_stream_reset")
+
+    def advance(self, slots: List[int], enc_packed: torch.Tensor, T: List[int], upto: List[int], final: List[bool],
+                max_hits: int = 64) -> List[CtcSpots]:
+        """Session i owns T[i] packed rows of enc_packed (all its encoder output so far); the spotter of slots[i] moves to upto[i]
+        frames; final[i]: the utterance's last call.  One buffer, one device-to-host copy."""
+        from .keywords import COUNT_DTYPE, HIT_DTYPE, hits_from_records
+        n, mh = len(slots), int(max_hits)
+        # int32 words: hits [6 n mh] (first: 8-byte aligned) | counts [4 n]
+        ibuf = torch.empty((6 * n * max(mh, 0) + 4 * n + 2,), dtype=torch.int32, device=self.device)
+        L.check(self.lib.ss_ctc_spot_stream_advance(self.model.h, _stream(), self.h, n, _i32(slots), _ptr(enc_packed), _i32(T), _i32(upto),
+                                                    _i32([1 if f else 0 for f in final]), mh, _ptr(ibuf), _ptr(ibuf[6 * n * max(mh, 0):])),
+                "ss_ctc_spot_stream_advance")
+        host = ibuf.cpu().numpy()
+        rec = host[:6 * n * mh].view(HIT_DTYPE).reshape(n, mh)
+        cnt = host[6 * n * mh: 6 * n * mh + 4 * n].view(COUNT_DTYPE)
+        return [CtcSpots(hits_from_records(rec[i, :min(int(cnt["n_hits"][i]), mh)]), int(cnt["n_hits"][i]), int(cnt["frames"][i]),
+                         int(cnt["status"][i]), bool(final[i])) for i in range(n)]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ss_ctc_spot_stream_destroy(self.h)
             self.h = None
 
     def __enter__(self):

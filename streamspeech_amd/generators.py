@@ -97,6 +97,16 @@ class CTCDecoder:
         return [[{"tokens": torch.tensor(h.tokens, dtype=torch.long), "score": h.score, "attn": None, "alignment": None,
                   "positional_scores": None, **extra(h)} for h in hyps]]
 
+    @torch.no_grad()
+    def spot(self, encoder_out, keywords, max_hits=256, **kw):
+        """Keyword spotting on this head: what generate takes plus the set (a keywords.CtcKeywords over this head's dictionary)
+        -> the utterance's keywords.CtcHit tuples sorted by (end, keyword, start), start and end in encoder rows, both inclusive
+        (words.FRAME_MS each).  No beam search is involved, and a phrase the arg-max path got a piece wrong on is still found
+        within its threshold."""
+        enc = encoder_out["encoder_out"][0]
+        enc = enc[:, 0] if enc.dim() == 3 else enc
+        return self.engine.ctc_spot(self.head, enc.contiguous(), keywords, int(max_hits))
+
 
 class CTCSequenceGenerator:
     """agent/ctc_generator.py:26-123 -- NAR unit search over the T2U+unit-decoder stage

@@ -105,6 +105,19 @@ class SSCtcBeamBiasHyp(C.Structure):
                 ("n_tokens", C.c_int32), ("status", C.c_int32)]
 
 
+class SSCtcHit(C.Structure):
+    """ss_ctc_hit: one occurrence of a keyword (24 bytes)."""
+    _fields_ = [("keyword", C.c_int32), ("start", C.c_int32), ("end", C.c_int32), ("n_labels", C.c_int32), ("score", C.c_double)]
+
+
+class SSCtcSpotCount(C.Structure):
+    """ss_ctc_spot_count: what a keyword-spotting call reports per utterance or session (16 bytes)."""
+    _fields_ = [("n_hits", C.c_int32), ("status", C.c_int32), ("overflow", C.c_int32), ("frames", C.c_int32)]
+
+
+CTC_SPOT_MAX_LABELS = 32        # SS_CTC_SPOT_MAX_LABELS / _KEYWORDS / _HITS of the header
+CTC_SPOT_MAX_KEYWORDS = 65536
+CTC_SPOT_MAX_HITS = 16384
 CTC_BIAS_MAX_LEN = 32           # SS_CTC_BIAS_MAX_LEN / _PHRASES of the header
 CTC_BIAS_MAX_PHRASES = 4096
 NGRAM_MAX_ORDER = 6             # SS_NGRAM_MAX_ORDER of the header
@@ -347,6 +360,19 @@ SIGNATURES = {
                                    C.POINTER(C.c_int32), _vp, _vp, _i, _vp]),
     "ss_ctc_stream_advance_host": (_i, [_vp, _i, C.POINTER(C.c_int32), _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp,
                                         _i, _vp]),
+    "ss_ctc_spot_set_create": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_vp)]),
+    "ss_ctc_spot_set_destroy": (None, [_vp]),
+    "ss_ctc_spot_set_info": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_int64)]),
+    "ss_batch_ctc_spot": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), _vp, _i, _vp, _vp]),
+    "ss_ctc_spot_host": (_i, [_vp, _i, _i, C.POINTER(C.c_int32), _vp, _i, _vp, _vp]),
+    "ss_ctc_spot_stream_create": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
+    "ss_ctc_spot_stream_destroy": (None, [_vp]),
+    "ss_ctc_spot_stream_reset": (_i, [_vp, _i]),
+    "ss_ctc_spot_stream_advance": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), _i, _vp, _vp]),
+    "ss_ctc_spot_stream_advance_host": (_i, [_vp, _i, C.POINTER(C.c_int32), _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
+                                             _vp, _vp]),
     "ss_batch_mt_greedy": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
                                 C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), _vp, _i]),
     "ss_batch_mt_beam": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _f, _i,
@@ -481,6 +507,12 @@ SIGNATURES = {
     "ss_debug_ctc_stream_create_bias": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(SSCtcLmOpts), _vp,
                                              C.POINTER(SSCtcBiasOpts), C.POINTER(_vp)]),
     "ss_op_ctc_bias_score": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _vp, _vp, _vp]),
+    "ss_op_ctc_spot": (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _vp, _i, _vp, _vp]),
+    "ss_debug_ctc_spot_phases": (_i, [_i]),
+    "ss_debug_ctc_spot_trace_host": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "ss_debug_ctc_spot_stream_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
+    "ss_op_ctc_spot_stream_advance": (_i, [_vp, _vp, _i, C.POINTER(C.c_int32), _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i,
+                                           _vp, _vp]),
     "ss_op_ngram_score": (_i, [_vp, _vp, _i, _vp, C.POINTER(C.c_int32), _i, _vp, _vp]),
     "ss_op_dur_predict": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
     "ss_op_repeat_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i]),

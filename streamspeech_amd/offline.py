@@ -65,7 +65,7 @@ import torch
 
 from . import frontend
 from .pipeline import units_from_tokens
-from .words import segments_from_spans, spoken_from_segments, words_from_attention, words_from_ctc, words_from_scores
+from .words import FRAME_MS, segments_from_spans, spoken_from_segments, words_from_attention, words_from_ctc, words_from_scores
 
 
 def detok(symbols: Sequence[str]) -> str:
@@ -106,7 +106,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
              ctc_beam_cand: Optional[int] = None, ctc_nbest: Optional[int] = None,
              constraints: Optional[Dict[int, Sequence[Sequence[int]]]] = None, ctc_lm: Optional[Dict[str, object]] = None,
              ctc_lm_weight: float = 0.5, ctc_word_score: float = 0.0, ctc_bias: Optional[Dict[str, object]] = None,
-             ctc_bias_scale: float = 1.0) -> Dict[int, Dict]:
+             ctc_bias_scale: float = 1.0, ctc_keywords: Optional[Dict[str, object]] = None,
+             ctc_keyword_max_hits: int = 256) -> Dict[int, Dict]:
     """items: (sample id, 16 kHz float PCM in [-1, 1] on the device).  Writes generate-<subset>.log/.txt,
     the cut .asr/.tgt/.unit files and pred_wav/<n>_pred.wav; returns the per-id hypotheses.
     features=True: the items are (sample id, raw fbank rows [T, 80] float32 on the device) instead -- the recipe's precomputed
@@ -161,7 +162,12 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     `C-<id>` line per phrase goes to the log in front of the sample's `D-` line, as fairseq-generate prints them, and
     generate-<subset>.mt.constraints holds a line per phrase: id, phrase, met 0 / 1, the position of its first token in the `D-`
     hypothesis (-1 when not met).  The `D-` text, the units and the waveform follow from the constrained hypothesis; not with
-    sampling."""
+    sampling.
+    ctc_keywords (--ctc-keywords-asr FILE, --ctc-keywords-st FILE, --ctc-keyword-threshold T; no ctc_beam needed): {"asr": a
+    keywords.CtcKeywords over source_unigram, "st": one over ctc_target_unigram}, either or both -- ONE keyword-spotting call per
+    head and batch after the encoder (batch_ctc_spot, at most ctc_keyword_max_hits hits per utterance), and
+    generate-<subset>.asr.hits / .st.hits hold a line per occurrence: id, phrase, start_ms, end_ms, score, norm (= score per label;
+    times as the .words files place words).  It reads the encoder rows and changes no other file."""
     from .engine import check_search_options, sampling_from_fairseq
     if constraints is not None and sampling:
         raise ValueError("constraints cannot be combined with sampling: the sampling search does not support them")
@@ -175,6 +181,8 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
     ctc_bias = {k: v for k, v in (ctc_bias or {}).items() if v is not None}
     if ctc_bias and not ctc_beam:
         raise ValueError("ctc_bias needs ctc_beam: the hotword set biases the CTC prefix beam search")
+    ctc_keywords = {k: v for k, v in (ctc_keywords or {}).items() if v is not None}
+    kw_hits: Dict[str, Dict[int, list]] = {"asr": {}, "st": {}}
     sampler = sampling_from_fairseq(sampling, sampling_topk, sampling_topp, seed)
     samples: Dict[int, list] = {}
     if spoken_words and not dump_wav:
@@ -240,6 +248,10 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
                     fuse.update(bias=ctc_bias[key], bias_scale=ctc_bias_scale)
                 for sid, lst in zip(ids, model.batch_ctc_beam(hd, enc, Tp, ctc_beam, ctc_beam_cand, ctc_nbest, **fuse)):
                     nbest_ctc[key][sid] = lst
+        for hd, key in ((0, "asr"), (1, "st")):
+            if key in ctc_keywords:
+                for sid, lst in zip(ids, model.batch_ctc_spot(hd, enc, Tp, ctc_keywords[key], ctc_keyword_max_hits)):
+                    kw_hits[key][sid] = lst
         # first-pass text search: max_len = min(int(max_len_a_mt * src_len + max_len_b_mt), max positions - 1) with
         # the task's defaults 0 / 200 (tasks/speech_to_speech_ctc.py:39-40 -> sequence_generator_multi_decoder_ctc.py
         # :130-131); src_len is the fbank frame count.  --max-len-a/-b configure the (NAR) unit generator, which has
@@ -370,6 +382,13 @@ def generate(model, vocoder, items: Sequence[Tuple[int, torch.Tensor]], dicts: D
                         else:
                             more = "\t-inf\t0\t0" if key in ctc_bias else "\t-inf\t0" if key in ctc_lm else ""
                             print(f"{sid}\t{rank}\t-inf{more}\t0\t", file=f)
+    for key in ("asr", "st"):
+        if key in ctc_keywords:
+            with open(os.path.join(results_path, f"generate-{subset}.{key}.hits"), "w", encoding="utf-8") as f:
+                for sid in sorted(kw_hits[key]):
+                    for h in kw_hits[key][sid]:
+                        print(f"{sid}\t{ctc_keywords[key].texts[h.keyword]}\t{h.start * FRAME_MS}\t{(h.end + 1) * FRAME_MS}\t"
+                              f"{h.score:.6f}\t{h.norm:.6f}", file=f)
     if spoken_words:
         with open(os.path.join(results_path, f"generate-{subset}.spoken.words"), "w", encoding="utf-8") as f:
             for sid in sorted(spoken):
@@ -778,6 +797,15 @@ def build_parser() -> argparse.ArgumentParser:
                     help="the same for the ST head, phrases over ctc_target_unigram")
     ap.add_argument("--ctc-hotword-boost", type=float, default=1.5,
                     help="S, the per-token boost (natural-log units) of a hotword line that names none (default 1.5)")
+    ap.add_argument("--ctc-keywords-asr", default=None, metavar="FILE",
+                    help="spot the phrases of FILE on the ASR head -- one per line as space-separated pieces of source_unigram, optionally "
+                         "a tab and the phrase's threshold; writes generate-<subset>.asr.hits (id, phrase, start_ms, end_ms, score, norm); "
+                         "needs no --ctc-beam, every other file as without the flag")
+    ap.add_argument("--ctc-keywords-st", default=None, metavar="FILE",
+                    help="the same for the ST head, phrases over ctc_target_unigram: generate-<subset>.st.hits")
+    ap.add_argument("--ctc-keyword-threshold", type=float, default=1.0,
+                    help="T, the threshold (natural-log units per label) of a keyword line that names none (default 1.0: a starting "
+                         "point, not tuned on a trained checkpoint)")
     ap.add_argument("--score-reference", action="store_true",
                     help="also score the recipe's reference translation (the multitask manifest <task data>/<gen-subset>.tsv of "
                          "target_unigram) with the first-pass text decoder, teacher-forced, as fairseq's --score-reference does: writes "
@@ -853,6 +881,10 @@ def main(argv: Optional[List[str]] = None):
         ap.error("--ctc-lm-asr, --ctc-lm-st, --ctc-lm-weight and --ctc-word-score need --ctc-beam")
     if not (math.isfinite(a.ctc_lm_weight) and math.isfinite(a.ctc_word_score)):
         ap.error("--ctc-lm-weight and --ctc-word-score must be finite")
+    if not (a.ctc_keywords_asr or a.ctc_keywords_st) and a.ctc_keyword_threshold != 1.0:
+        ap.error("--ctc-keyword-threshold needs --ctc-keywords-asr or --ctc-keywords-st")
+    if not a.ctc_keyword_threshold >= 0.0 or a.ctc_keyword_threshold == float("inf"):
+        ap.error("--ctc-keyword-threshold must be a finite number >= 0")
     if not a.ctc_beam and (a.ctc_hotwords_asr or a.ctc_hotwords_st or a.ctc_hotword_boost != 1.5):
         ap.error("--ctc-hotwords-asr, --ctc-hotwords-st and --ctc-hotword-boost need --ctc-beam")
     if not math.isfinite(a.ctc_hotword_boost):
@@ -984,6 +1016,17 @@ def main(argv: Optional[List[str]] = None):
                 ap.error(f"--ctc-hotwords-{key}: {e}")
             print(f"| --ctc-hotwords-{key}: {ctc_bias[key].n_phrases} phrases, {ctc_bias[key].states} states, "
                   f"{ctc_bias[key].device_bytes} bytes on the device", file=sys.stderr)
+    ctc_keywords = {}
+    for key, path, name in (("asr", a.ctc_keywords_asr, "source_unigram"), ("st", a.ctc_keywords_st, "ctc_target_unigram")):
+        if path:
+            from .keywords import CtcKeywords
+            from .lib import StreamSpeechHipError
+            try:
+                ctc_keywords[key] = CtcKeywords.from_file(path, holder.dict[name], a.ctc_keyword_threshold)
+            except (OSError, ValueError, StreamSpeechHipError) as e:
+                ap.error(f"--ctc-keywords-{key}: {e}")
+            print(f"| --ctc-keywords-{key}: {ctc_keywords[key].n_keywords} phrases, {ctc_keywords[key].states} states, "
+                  f"{ctc_keywords[key].device_bytes} bytes on the device", file=sys.stderr)
     sub = a.gen_subset if a.num_shards == 1 else f"{a.gen_subset}.shard{a.shard_id}"
     hyps = generate(model, voc, items, holder.dict, a.results_path, sub, a.batch_size, a.max_tokens, a.max_len_a,
                     a.max_len_b, a.max_len_a_mt, a.max_len_b_mt, a.dur_prediction, not a.no_wav,
@@ -1002,7 +1045,10 @@ def main(argv: Optional[List[str]] = None):
                     **({"ctc_beam": a.ctc_beam, "ctc_beam_cand": a.ctc_beam_cand, "ctc_nbest": a.ctc_nbest} if a.ctc_beam else {}),
                     **({"constraints": glossary} if glossary is not None else {}),
                     **({"ctc_lm": ctc_lm, "ctc_lm_weight": a.ctc_lm_weight, "ctc_word_score": a.ctc_word_score} if ctc_lm else {}),
-                    **({"ctc_bias": ctc_bias} if ctc_bias else {}))
+                    **({"ctc_bias": ctc_bias} if ctc_bias else {}),
+                    **({"ctc_keywords": ctc_keywords} if ctc_keywords else {}))
+    for kw in ctc_keywords.values():
+        kw.close()
     for lm in ctc_lm.values():
         lm.close()
     for bias in ctc_bias.values():

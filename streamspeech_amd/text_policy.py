@@ -131,3 +131,23 @@ def ctc_beam_flags(args, agent: str = "asr", want_lm: bool = True) -> Optional[C
     if not math.isfinite(boost):
         raise ValueError("--ctc-hotword-boost must be finite")
     return CtcBeamOptions(beam, cand, None, None, getattr(args, "ctc_lm_weight", 0.5), getattr(args, "ctc_word_score", 0.0))
+
+
+KEYWORD_THRESHOLD = 1.0     # --ctc-keyword-threshold: tau of a keyword line that names none (keywords.DEFAULT_THRESHOLD)
+
+
+def ctc_keyword_flags(args, agent: str = "asr") -> Optional[str]:
+    """--ctc-keywords FILE [--ctc-keyword-threshold T] of the streaming agents -> the file, or None without the flag.  ValueError:
+    the threshold without the file, a threshold that is not a finite number >= 0, the flags on another agent than the ASR one (the
+    set is read over source_unigram and spotted on the ASR head; the other agents would ignore it silently).  The file is not read
+    here."""
+    path, tau = getattr(args, "ctc_keywords", None), float(getattr(args, "ctc_keyword_threshold", KEYWORD_THRESHOLD))
+    if path is None:
+        if tau != KEYWORD_THRESHOLD:
+            raise ValueError("--ctc-keyword-threshold needs --ctc-keywords")
+        return None
+    if agent != "asr":
+        raise ValueError(f"--ctc-keywords is the streaming ASR agent's: the {agent} agent reports no keyword hits")
+    if not tau >= 0.0 or not math.isfinite(tau):
+        raise ValueError("--ctc-keyword-threshold must be a finite number >= 0")
+    return path

@@ -96,6 +96,7 @@ class _Session:
         self.details = None                   # a words.CtcDetails of the last step that encoded the session (pools with details)
         self.alignment = None                 # the words.AlignedWord list of the utterance's committed target tokens (pools with align)
         self.nbest = None                     # pools with ctc_beam: the engine.CtcHypothesis list of the last finished utterance
+        self.spot_hits = []                   # pools with spot: the keywords.KeywordHit that arrived since hits(sid) was last asked
         self.reset()
 
     def n_source(self) -> int:
@@ -118,6 +119,7 @@ class _Session:
         self.tgt_text = ""
         self.partial = None                   # pools with ctc_beam: the symbols of the utterance's current best hypothesis
         self.ctc_frames = 0                   # ... and the encoder rows its search has consumed
+        self.spot_frames = 0                  # pools with spot: the encoder rows the utterance's spotter has consumed
         self.states.reset()
         self.fe.clear_cache()
         if self.pcm_state is not None:        # a fresh utterance: nothing received, nothing emitted, nothing carried
@@ -133,7 +135,7 @@ class TextSessionPool:
 
     def __init__(self, model, max_sessions: int, max_rows: int, beam_mt: int = 1, details: bool = False, align: bool = False,
                  search: Optional[SearchOptions] = None, len_penalty: float = 1.0, temperature: float = 1.0,
-                 no_repeat_ngram_size: int = 0, ctc_beam: Optional[CtcBeamOptions] = None):
+                 no_repeat_ngram_size: int = 0, ctc_beam: Optional[CtcBeamOptions] = None, spot=None, spot_max_hits: int = 64):
         """beam_mt > 1: the step's one ragged continuation is a beam search behind every writer's committed prefix
         (HipModel.batch_mt_beam_continue, the agents' --beam-mt); hypothesis 0's tokens and states go on as the greedy ones do.
         details: the step's one CTC call is the scored form, and details(sid) answers the words of both heads with their time
@@ -157,7 +159,13 @@ class TextSessionPool:
         rest of the best hypothesis at the end: the writes of an utterance add up to its final best hypothesis and none is ever
         retracted.  partial(sid) answers the current best hypothesis, nbest(sid) the last finished utterance's n-best.  S2TT
         sessions (and a subclass's kinds) run as without the option, and so does every launch of a pool built without it.  Not
-        with details (its spans are the arg-max path's)."""
+        with details (its spans are the arg-max path's).
+        spot (a keywords.CtcKeywords over the source dictionary): ASR sessions are searched for the set's phrases as they speak --
+        the pool owns one engine.CtcSpotStream on head 0 whose slots are the pool's, and after the encoder ONE advance serves every
+        ASR session of the step, over the rows the encoder has made final (as the prefix search: all rows, with final, for a
+        session whose source is finished), at most spot_max_hits hits per session and step.  hits(sid) answers what arrived.
+        With the greedy sessions, with ctc_beam and with details; it reads the encoder rows and touches none of their outputs,
+        and a pool built without it launches what it always did."""
         if ctc_beam is not None and details:
             raise ValueError("ctc_beam cannot be combined with details: the words' spans are those of the arg-max path")
         if ctc_beam is not None and not isinstance(ctc_beam, CtcBeamOptions):
@@ -183,6 +191,13 @@ class TextSessionPool:
             from .engine import CtcStream
             from .lib import CTC_BEAM_MAX_FRAMES
             self.ctc_stream = CtcStream(self.model, 0, self.max_sessions, min(self.max_rows, CTC_BEAM_MAX_FRAMES), **ctc_beam.stream_kwargs())
+        self.spot_stream = None                # pools with spot: the spotters of the ASR sessions, slot for slot
+        self._spot_rows: list = []             # ... and the rows each of the step's spotters moved over
+        self._spot_lost = 0                    # ... and the hits of the step past spot_max_hits
+        self.spot_max_hits = int(spot_max_hits)
+        if spot is not None:
+            from .engine import CtcSpotStream
+            self.spot_stream = CtcSpotStream(self.model, 0, self.max_sessions, spot)
         self.sessions: Dict[int, _Session] = {}
         self.free = list(range(self.max_sessions))
         self._next = 0
@@ -349,8 +364,21 @@ class TextSessionPool:
         """A pool with ctc_beam: the n-best (engine.CtcHypothesis, best first) of the ASR session's last finished utterance."""
         return self._get(sid).nbest if self.ctc_stream is not None else None
 
+    def hits(self, sid: int):
+        """A pool with spot: the keyword hits (keywords.KeywordHit) of the ASR session that arrived since this was last asked, in
+        the order they were reported (a step's by end, keyword, start); start_ms / end_ms on the session's own clock (an
+        endpointed session: the stream's), placed as words.py places words.  They survive reset(sid): a finished utterance's last
+        hits arrive with its last step.  None in a pool without spot."""
+        if self.spot_stream is None:
+            return None
+        s = self._get(sid)
+        got, s.spot_hits = s.spot_hits, []
+        return got
+
     def _slot_reset(self, slot: int):
         self.pool.reset(slot)
+        if self.spot_stream is not None:       # ... and its spotter
+            self.spot_stream.reset(slot)
         if self.ctc_stream is not None:        # wherever the encoder's slot starts over, so does its search
             self.ctc_stream.reset(slot)
 
@@ -774,6 +802,9 @@ class TextSessionPool:
             else:                                 # ASR sessions only, all on the prefix search: no arg-max call
                 src = tgt = [None] * len(enc)
             parts = self._ctc_stream_step(enc, beam_asr, packed, views, n_fin) if beam_asr else {}
+            spot_asr = [i for i, s in enumerate(enc) if s.kind == "asr"] if self.spot_stream is not None else []
+            if spot_asr:
+                self._spot_step(enc, spot_asr, packed, views, n_fin)
             if self.with_details:
                 for i, s in enumerate(enc):
                     self._set_details(s, src[i], tgt[i], n_fin[i])
@@ -871,6 +902,10 @@ class TextSessionPool:
         if self.ctc_stream is not None:           # ss_ctc_stream_advance calls of the step (0 or 1), rows they ran through the head
             self.last_step.update({"ctc_stream_calls": 1 if (enc and beam_asr) else 0,
                                    "ctc_stream_rows": sum(self._stream_rows) if (enc and beam_asr) else 0})
+        if self.spot_stream is not None:          # ss_ctc_spot_stream_advance calls of the step (0 or 1), rows through the head, hits lost
+            ran = bool(enc) and any(s.kind == "asr" for s in enc)
+            self.last_step.update({"ctc_spot_calls": 1 if ran else 0, "ctc_spot_rows": sum(self._spot_rows) if ran else 0,
+                                   "ctc_spot_lost": self._spot_lost if ran else 0})
         self.last_step.update(self._side_times)
         self._side_times = {}
         if eps:
@@ -931,6 +966,26 @@ class TextSessionPool:
         for i, p in zip(beam_asr, got):
             enc[i].ctc_frames = 0 if p.final else p.frames
         return dict(zip(beam_asr, got))
+
+    def _spot_step(self, enc, spot_asr, packed, views, n_fin):
+        """The step's ONE advance of the spotters of its ASR sessions, over the rows _ctc_stream_step takes; what they emit joins
+        the sessions' spot_hits on the session clock."""
+        from .keywords import KeywordHit
+        from .words import FRAME_MS
+        T2 = [int(views[i].shape[0]) for i in spot_asr]
+        rows = packed if len(spot_asr) == len(enc) else torch.cat([views[i] for i in spot_asr], 0)
+        final = [bool(enc[i].states.source_finished) for i in spot_asr]
+        upto = [t2 if fin else int(n_fin[i]) for i, t2, fin in zip(spot_asr, T2, final)]
+        got = self.spot_stream.advance([enc[i].slot for i in spot_asr], rows, T2, upto, final, self.spot_max_hits)
+        self._spot_rows = [p.frames - enc[i].spot_frames for i, p in zip(spot_asr, got)]
+        self._spot_lost = sum(p.n_hits - len(p.hits) for p in got)
+        texts = self.spot_stream.keywords.texts
+        for i, p in zip(spot_asr, got):
+            s = enc[i]
+            s.spot_frames = 0 if p.final else p.frames
+            t0 = self._t0_ms(s)
+            s.spot_hits.extend(KeywordHit(h.keyword, texts[h.keyword], t0 + h.start * FRAME_MS, t0 + (h.end + 1) * FRAME_MS, h.score, h.norm)
+                               for h in p.hits)
 
     def _asr_beam(self, s: _Session, part):
         symbols = [s.dict["source_unigram"][c] for c in part.hyps[0].tokens] if part.hyps else []
